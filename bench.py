@@ -406,6 +406,35 @@ def team_contact_leg(rank, world, local_rank, config, steps=10, warmup=3):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(g, out_dir, limit=DUMP_LIMIT_BYTES, seed=0):
+    """--dump-outputs: the state a caller of the timed path reads back after its last substep (mpm_download_array),
+    written as DIR/<name>.npy in float32.  Particle rows go in original particle-id order (the download's order is the
+    slot order the last re-sort left, which two builds need not share), faces in original face order.  Above `limit`
+    bytes in all (headers included), every array keeps the same fraction of its rows: a fixed sample drawn with `seed`, in ascending order."""
+    from drake_amd import ARR
+    pids = g.download(ARR.PIDS).astype(np.int64)
+    if not np.array_equal(np.sort(pids), np.arange(pids.size)):
+        raise RuntimeError("--dump-outputs: the particle ids are not a permutation")
+    by_id = np.argsort(pids)
+    arrays = dict(positions=g.download(ARR.POSITIONS)[by_id], velocities=g.download(ARR.VELOCITIES)[by_id],
+                  deformation_gradients=g.download(ARR.DEFORMATION_GRADIENTS))
+    total = sum(a.nbytes for a in arrays.values())
+    frac = min(1.0, (limit - 4096) / total)   # (4 KiB for the .npy headers)
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, a in arrays.items():
+        rows = a.shape[0]
+        if frac < 1.0:
+            keep = int(rows * frac)
+            a = a[np.sort(np.random.default_rng(seed).choice(rows, keep, replace=False))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+        info[name] = dict(shape=list(a.shape), rows_of=rows)
+    return dict(dir=os.path.abspath(out_dir), sample_seed=seed if frac < 1.0 else None, arrays=info)
+
+
 def launch_ranks(n, argv):
     """`python bench.py --gpus N` without torchrun: start N rank processes of this same script
     (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in their environment, rendezvous on 127.0.0.1) and
@@ -451,8 +480,13 @@ def main():
     ap.add_argument("--no-contact-leg", action="store_true", help="skip the config-3 (contact) record")
     ap.add_argument("--contact-only", action="store_true",
                     help="only the config-3 (contact) record: the command whose rocprofv3 kernel trace is profiles/rNN_contact_*")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state they left (positions, velocities, deformation "
+                         "gradients) as DIR/<name>.npy in float32, at most 64 MB in all (single GPU only)")
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.dump_outputs and (args.gpus > 1 or args.contact_only):
+        ap.error("--dump-outputs writes the single-GPU timed path's outputs: not with --gpus > 1 or --contact-only")
 
     if args.launcher_selftest and "WORLD_SIZE" in os.environ:
         # (tests/test_bench_helpers.py: what a rank process sees, without touching torch or the GPU)
@@ -709,6 +743,7 @@ def main():
     # inside the quiet time the last re-sort estimated)
     region["resort_check_launches_since_finalize"] = st["resort_checks"] - 1   # (Finalize's own sort is one)
     region["substeps_since_finalize"] = args.warmup + args.steps
+    dumped = dump_outputs(g, args.dump_outputs) if args.dump_outputs else None
     # The steady state next to the driver's window: SURVEY 8(d)'s 200 substeps after 20 (the cloth has picked up
     # speed, re-sorts included), whatever --steps / --warmup were.  Not `value`.
     steady = None
@@ -875,6 +910,8 @@ def main():
                                slot_sort_every=args.sort_every, parallelism=par, geometry=geometry if world > 1 else None),
                    transport=transport, roofline=roofline)
         out["timed_region"] = region
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if steady is not None:
             out["steady_state"] = steady
         if ref_pattern is not None:

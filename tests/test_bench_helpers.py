@@ -73,3 +73,53 @@ def test_gpus_flag_launches_that_many_ranks():
     bad = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--no-such-flag"],
                          capture_output=True, text=True, timeout=120, env=env)
     assert bad.returncode != 0
+
+
+class _FakeEngine:
+    """download() of a tiny engine whose slots are a shuffle of the particle ids"""
+
+    def __init__(self, n_particles, n_faces):
+        import numpy as np
+        from drake_amd import ARR
+        self.pids = np.random.default_rng(7).permutation(n_particles).astype(np.int32)
+        ids = self.pids.astype(np.float32)[:, None]
+        self.arrays = {ARR.PIDS: self.pids, ARR.POSITIONS: ids * np.float32([1, 2, 3]),
+                       ARR.VELOCITIES: -ids * np.float32([1, 1, 1]),
+                       ARR.DEFORMATION_GRADIENTS: np.arange(n_faces * 9, dtype=np.float32).reshape(n_faces, 9)}
+
+    def download(self, which):
+        return self.arrays[which].copy()
+
+
+def test_dump_outputs_writes_particles_in_id_order(tmp_path):
+    import numpy as np
+    b = _bench()
+    g = _FakeEngine(100, 40)
+    info = b.dump_outputs(g, str(tmp_path))
+    assert sorted(os.listdir(tmp_path)) == ["deformation_gradients.npy", "positions.npy", "velocities.npy"]
+    pos, vel, F = (np.load(tmp_path / f"{n}.npy") for n in ("positions", "velocities", "deformation_gradients"))
+    assert pos.dtype == vel.dtype == F.dtype == np.float32
+    ids = np.arange(100, dtype=np.float32)[:, None]
+    np.testing.assert_array_equal(pos, ids * np.float32([1, 2, 3]))
+    np.testing.assert_array_equal(vel, -ids * np.float32([1, 1, 1]))
+    np.testing.assert_array_equal(F, np.arange(360, dtype=np.float32).reshape(40, 9))
+    assert info["sample_seed"] is None and info["arrays"]["positions"]["shape"] == [100, 3]
+
+
+def test_dump_outputs_samples_the_same_rows_under_the_limit(tmp_path):
+    import numpy as np
+    b = _bench()
+    g = _FakeEngine(1000, 500)
+    limit = 8000   # of 12000 + 12000 + 18000 bytes
+    first, second = tmp_path / "a", tmp_path / "b"
+    b.dump_outputs(g, str(first), limit=limit)
+    b.dump_outputs(_FakeEngine(1000, 500), str(second), limit=limit)
+    total = 0
+    for n in ("positions", "velocities", "deformation_gradients"):
+        x, y = np.load(first / f"{n}.npy"), np.load(second / f"{n}.npy")
+        np.testing.assert_array_equal(x, y)
+        total += x.nbytes
+    assert 0 < total <= limit
+    pos = np.load(first / "positions.npy")
+    assert np.all(np.diff(pos[:, 0]) > 0)   # a subset of the ids, ascending
+    np.testing.assert_array_equal(pos[:, 1], 2 * pos[:, 0])
