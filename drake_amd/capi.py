@@ -22,8 +22,18 @@ class MpmError(RuntimeError):
         self.code = code
 
 
+# mpm_collider_t::kind (include/mpm_hip.h)
+COLLIDER_HALF_SPACE, COLLIDER_SPHERE, COLLIDER_BOX, COLLIDER_CAPSULE, COLLIDER_CYLINDER, COLLIDER_ELLIPSOID = range(6)
+COLLIDER_KINDS = {"MPM_COLLIDER_HALF_SPACE": COLLIDER_HALF_SPACE, "MPM_COLLIDER_SPHERE": COLLIDER_SPHERE,
+                  "MPM_COLLIDER_BOX": COLLIDER_BOX, "MPM_COLLIDER_CAPSULE": COLLIDER_CAPSULE,
+                  "MPM_COLLIDER_CYLINDER": COLLIDER_CYLINDER, "MPM_COLLIDER_ELLIPSOID": COLLIDER_ELLIPSOID}
+
+
 class Collider(C.Structure):
-    """mpm_collider_t: kind 0 half-space (z_B <= 0 inside), 1 sphere, 2 box (half extents), 3 capsule (z_B)."""
+    """mpm_collider_t: kind 0 half-space (z_B <= 0 inside), 1 sphere (radius dims[0]), 2 box (half extents dims),
+    3 capsule (radius dims[0], half length dims[1] along z_B), 4 cylinder (radius dims[0], half length dims[1] along
+    z_B: Drake's Cylinder(radius, length) is (radius, length / 2)), 5 ellipsoid (semi-axes dims along x_B, y_B, z_B:
+    Drake's Ellipsoid(a, b, c))."""
     _fields_ = [("kind", C.c_int32), ("body", C.c_uint32), ("p_WB", C.c_float * 3), ("R_WB", C.c_float * 9),
                 ("dims", C.c_float * 3), ("v", C.c_float * 3), ("w", C.c_float * 3)]
 
@@ -125,7 +135,7 @@ SYMBOLS = [
     "mpm_counts", "mpm_grid_touched_cnt", "mpm_dump_cpu_state", "mpm_reallocate_external_bodies",
     "mpm_external_body_force_to_host", "mpm_rebuild_mapping", "mpm_calc_fem_state_and_force", "mpm_particle_to_grid",
     "mpm_update_grid", "mpm_grid_to_particle", "mpm_sync", "mpm_sync_particle_state_to_cpu", "mpm_dump_obj",
-    "mpm_copy_contact_pairs", "mpm_generate_contact_pairs", "mpm_download_contact_pairs", "mpm_update_contact", "mpm_set_dump_dir", "mpm_substep", "mpm_run_substeps",
+    "mpm_copy_contact_pairs", "mpm_generate_contact_pairs", "mpm_collider_signed_distance", "mpm_download_contact_pairs", "mpm_update_contact", "mpm_set_dump_dir", "mpm_substep", "mpm_run_substeps",
     "mpm_profile_substeps", "mpm_set_stream", "mpm_set_deterministic", "mpm_get_stats", "mpm_debug_counters", "mpm_grid_gather",
     "mpm_halo_buffer_bytes", "mpm_halo_pack", "mpm_halo_add", "mpm_update_grid_from_sums", "mpm_substep_begin",
     "mpm_substep_end", "mpm_substep_begin_halo", "mpm_substep_mid_halo", "mpm_substep_end_halo", "mpm_chain_unique_id",
@@ -232,6 +242,7 @@ def load_library(build: bool = True):
         "mpm_substep_begin": [vp, f],
         "mpm_substep_end": [vp, f, i],
         "mpm_generate_contact_pairs": [vp, sz, vp, P(sz)],
+        "mpm_collider_signed_distance": [vp, vp, sz, vp, vp, vp],
         "mpm_download_contact_pairs": [vp, vp, vp, vp, vp, vp, vp, vp],
         "mpm_set_deterministic": [vp, i],
         "mpm_set_fast_math": [vp, i],
@@ -531,6 +542,15 @@ class GpuMpm:
         self._ck(self.lib.mpm_generate_contact_pairs(self.h, nc, arr, C.byref(n)))
         self._n_contacts = int(n.value)
         return self._n_contacts
+
+    def collider_signed_distance(self, collider, points):
+        """QueryObject::ComputeSignedDistanceToPoint for one collider on the device (mpm_collider_signed_distance):
+        points (n, 3) in the world -> (phi (n,), unit world gradient (n, 3)), float32."""
+        x = _f32(points, (-1, 3))
+        n = int(x.shape[0])
+        phi, grad = np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        self._ck(self.lib.mpm_collider_signed_distance(self.h, C.byref(collider), n, _ptr(x), _ptr(phi), _ptr(grad)))
+        return phi, grad
 
     def contact_pair_count(self) -> int:
         n = C.c_size_t()

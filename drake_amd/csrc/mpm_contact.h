@@ -1,6 +1,7 @@
 // Host orchestration of the contact solve (CopyContactPairs / UpdateContact,
 // cuda_mpm_solver.cu:193-621).
 #pragma once
+#include <algorithm>
 #include <chrono>
 #include <memory>
 #include <cmath>
@@ -251,13 +252,27 @@ static int generate_contacts_launch(mpm_engine* e) {
     c.slot = b.slot; c.body = b.body; c.dist = b.dist; c.normal = b.normal; c.pos = b.pos;
     c.rigid_v = b.rigid_v; c.p_WB = b.p_WB; c.vel = b.vel;
     b.gen_stamp += 1;   // (the solve that follows names this generation: k_ct_keys refuses a count another one left)
-    hipLaunchKernelGGL(k_ct_gen_write, dim3(e->g_np), dim3(256), 0, s, p, (const int*)e->d_pids_api, tab, (const int*)b.gen_cnt,
+    hipLaunchKernelGGL(b.has_ellipsoid ? k_ct_gen_write<true> : k_ct_gen_write<false>, dim3(e->g_np), dim3(256), 0, s, p, (const int*)e->d_pids_api, tab, (const int*)b.gen_cnt,
                        (const int*)b.gen_sums, nb, (int)std::min<size_t>(b.cap, 0x7FFFFFFF), b.api_idx, c, b.gen_stamp);
     HIP_TRY(hipGetLastError());
     b.dev_counted = true;
     b.n = 0;
     // (the block tables are what they are now: the keys of the solve's sort are as wide as the active blocks need.
     // The host's last reading of that count, mpm_sync / mpm_get_stats, may be older than a re-sort: unknown then)
+    return 0;
+}
+
+// the kinds of mpm_collider_t and the dimensions each new kind uses (finite, > 0); kinds 0-3 check their kind only
+static int validate_colliders(size_t n_col, const mpm_collider_t* cols) {
+    for (size_t j = 0; j < n_col; ++j) {
+        const mpm_collider_t& c = cols[j];
+        REQUIRE(c.kind >= MPM_COLLIDER_HALF_SPACE && c.kind <= MPM_COLLIDER_ELLIPSOID, "unknown collider kind");
+        const int used = c.kind == MPM_COLLIDER_CYLINDER ? 2 : (c.kind == MPM_COLLIDER_ELLIPSOID ? 3 : 0);
+        for (int d = 0; d < used; ++d)
+            REQUIRE(std::isfinite(c.dims[d]) && c.dims[d] > 0.f,
+                    c.kind == MPM_COLLIDER_CYLINDER ? "cylinder: radius and half length must be finite and > 0"
+                                                    : "ellipsoid: semi-axes must be finite and > 0");
+    }
     return 0;
 }
 
@@ -270,13 +285,15 @@ static int generate_contacts(mpm_engine* e, size_t n_col, const mpm_collider_t* 
     b.dev_counted = false;
     if (n_out) *n_out = 0;
     if (n_col == 0) return 0;
-    for (size_t j = 0; j < n_col; ++j) {
-        REQUIRE(cols[j].kind >= 0 && cols[j].kind <= 3, "unknown collider kind");
+    if (int rc = validate_colliders(n_col, cols)) return rc;
+    for (size_t j = 0; j < n_col; ++j)
         REQUIRE(cols[j].body < std::max<size_t>(b.n_bodies, 1), "collider body index out of range");
-    }
     const Collider* in = reinterpret_cast<const Collider*>(cols);
     const bool same = b.last_colliders.size() == n_col && std::memcmp(b.last_colliders.data(), in, n_col * sizeof(Collider)) == 0;
-    if (!same) b.last_colliders.assign(in, in + n_col);
+    if (!same) {
+        b.last_colliders.assign(in, in + n_col);
+        b.has_ellipsoid = std::any_of(in, in + n_col, [](const Collider& c) { return c.kind == MPM_COLLIDER_ELLIPSOID; });
+    }
     if (n_col > (size_t)CT_COLLIDER_ARGS) {
         if (n_col > b.cap_colliders) {
             if (int rc = grow(&b.colliders, n_col)) return rc;
@@ -301,6 +318,29 @@ static int generate_contacts(mpm_engine* e, size_t n_col, const mpm_collider_t* 
         if (int rc = resolve_contact_count(e)) return rc;
         *n_out = b.n;
     }
+    return 0;
+}
+
+// mpm_collider_signed_distance: k_ct_sdf_query on the engine's stream, through a scratch allocation of this call
+static int collider_signed_distance(mpm_engine* e, const mpm_collider_t* col, size_t n, const float* x, float* phi, float* grad) {
+    if (int rc = validate_colliders(1, col)) return rc;
+    if (n == 0) return 0;
+    REQUIRE(n <= (size_t)0x7FFFFFFF / 3, "too many points");
+    struct Scratch {
+        float* p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } buf;
+    HIP_TRY(hipMalloc((void**)&buf.p, n * 7 * sizeof(float)));
+    float *dx = buf.p, *dphi = buf.p + 3 * n, *dgrad = buf.p + 4 * n;
+    HIP_TRY(hipMemcpyAsync(dx, x, n * 12, hipMemcpyHostToDevice, e->stream));
+    Collider c;
+    std::memcpy(&c, col, sizeof(Collider));
+    hipLaunchKernelGGL(k_ct_sdf_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, c, (int)n, (const float*)dx,
+                       dphi, dgrad);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(phi, dphi, n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(grad, dgrad, n * 12, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
 }
 

@@ -225,6 +225,7 @@ struct ContactBuffers {
     uint32_t *prev_key = nullptr, *prev_api = nullptr, *prev_body = nullptr;
     // the colliders of the last mpm_generate_contact_pairs (a buffer overflow repeats the generation)
     std::vector<Collider> last_colliders;
+    bool has_ellipsoid = false;   // (one of last_colliders is kind 5: k_ct_gen_write<true>)
     bool sorted_in_alt = false;         // the sorted (key, order) of the last set-up sit in key2 / order2
     bool last_unchanged = false;        // the last solve found its pair list equal to its predecessor's
     // F_Bq_W_tau / F_Bq_W_f of the reference (cuda_mpm_model.cuh: float arrays fed by float atomics, whose sums depend on
@@ -280,13 +281,24 @@ __global__ __launch_bounds__(256) void k_ct_init_vel(DP p, ContactDev c) {
 }
 
 // ---- device-side CalcMpmContactPairs (deformable_driver.h:120-194) ---------------------------
-// signed distance of the world point x to collider c and its unit gradient in the world
-MPM_DEV float collider_sdf(const Collider& c, const float* x, float* grad) {
-    const float d[3] = {x[0] - c.p[0], x[1] - c.p[1], x[2] - c.p[2]};
-    // body frame: xb = R^T d
-    const float xb[3] = {c.R[0] * d[0] + c.R[3] * d[1] + c.R[6] * d[2], c.R[1] * d[0] + c.R[4] * d[1] + c.R[7] * d[2],
-                         c.R[2] * d[0] + c.R[5] * d[1] + c.R[8] * d[2]};
-    float gb[3] = {0.f, 0.f, 1.f}, phi;
+// Kinds (mpm_collider_t): 0 half-space, 1 sphere, 2 box, 3 capsule, 4 cylinder, 5 ellipsoid.
+// Membership ("is this pair?") and distance ("its phi and normal") are two functions.  The count kernel and the write
+// kernel decide membership with the SAME predicate (collider_inside): the write kernel fills the offsets the count kernel
+// scanned, and a disagreement between the two would overrun into the next slot's pairs.  Kinds 0-4 decide it with their
+// closed-form phi < 0; the ellipsoid with its implicit function sum (x_i / a_i)^2 < 1, so that its iterative distance
+// (FP64 root solve) runs in the write kernel only, for members only.  k_ct_watch asks a conservative version of the same
+// question (collider_near).
+
+// Cylinder (kind 4): Drake maps the query to the (r, z) cross-section box [-R, R] x [-h, h] and classifies each coordinate
+// as inside, on the boundary (within a tolerance) or outside (distance_to_point_callback.cc:206-299, 401-489).  Drake's
+// tolerance is 1e-14 max(1, bound) in double; in float it is CYL_TOL max(1, bound), four float epsilons.  The same
+// tolerance decides "on the axis" (r below it: radial direction +x_B).
+constexpr float CYL_TOL = 4.f * 1.1920929e-7f;
+
+// kinds 0-4 in the body frame: signed distance, unit gradient gb (body frame)
+MPM_DEV float sdf_closed(const Collider& c, const float* xb, float* gb) {
+    gb[0] = 0.f; gb[1] = 0.f; gb[2] = 1.f;
+    float phi;
     if (c.kind == 0) {            // half-space z_B <= 0
         phi = xb[2];
     } else if (c.kind == 1) {     // sphere
@@ -306,15 +318,230 @@ MPM_DEV float collider_sdf(const Collider& c, const float* x, float* grad) {
             phi = sqrtf(o[0] * o[0] + o[1] * o[1] + o[2] * o[2]);
             gb[0] = sg[0] * o[0] / phi; gb[1] = sg[1] * o[1] / phi; gb[2] = sg[2] * o[2] / phi;
         }
-    } else {                      // capsule along z_B
+    } else if (c.kind == 3) {     // capsule along z_B
         const float zc = fminf(fmaxf(xb[2], -c.dims[1]), c.dims[1]);
         const float r[3] = {xb[0], xb[1], xb[2] - zc};
         const float len = sqrtf(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
         phi = len - c.dims[0];
         if (len > 0.f) { gb[0] = r[0] / len; gb[1] = r[1] / len; gb[2] = r[2] / len; }
+    } else {                      // cylinder along z_B: radius dims[0], half length dims[1]
+        const float R = c.dims[0], h = c.dims[1];
+        const float r = sqrtf(xb[0] * xb[0] + xb[1] * xb[1]), z = xb[2], az = fabsf(z);
+        const float tr = CYL_TOL * fmaxf(1.f, R), tz = CYL_TOL * fmaxf(1.f, h);
+        const float sz = z < 0.f ? -1.f : 1.f;   // Sign(0) = +1
+        // radial unit vector; +x_B on the axis (distance_to_point_callback.cc:262-270)
+        const bool axis = r < tr;
+        const float ux = axis ? 1.f : xb[0] / r, uy = axis ? 0.f : xb[1] / r;
+        const bool out_r = r > R + tr, out_z = az > h + tz;
+        const bool bnd_r = !out_r && r >= R - tr, bnd_z = !out_z && az >= h - tz;
+        float gr, gz;
+        if (out_r || out_z) {     // outside: (Q - clamp(Q)) / |...|, the clamp of a boundary coordinate being the bound
+            const float dr = (out_r || bnd_r) ? r - R : 0.f, dz = (out_z || bnd_z) ? sz * (az - h) : 0.f;
+            phi = sqrtf(dr * dr + dz * dz);
+            gr = dr / phi; gz = dz / phi;
+        } else if (bnd_r || bnd_z) {   // on the boundary: the normalised sum of the boundary coordinates' directions
+            const float w = bnd_r && bnd_z ? 0.70710678f : 1.f;
+            gr = bnd_r ? w : 0.f;
+            gz = bnd_z ? w * sz : 0.f;
+            phi = (bnd_r ? w * (r - R) : 0.f) + (bnd_z ? w * (az - h) : 0.f);   // grad . (Q - clamp(Q))
+        } else if (h - az < R - r) {   // inside, nearest feature a cap (ExtremalAxis: +r, -r, +z, -z, strict <)
+            gr = 0.f; gz = sz;
+            phi = az - h;
+        } else {                  // inside, the barrel (wins a tie)
+            gr = 1.f; gz = 0.f;
+            phi = r - R;
+        }
+        gb[0] = gr * ux; gb[1] = gr * uy; gb[2] = gz;
+    }
+    return phi;
+}
+
+MPM_DEV void body_coords(const Collider& c, const float* x, float* xb) {
+    const float d[3] = {x[0] - c.p[0], x[1] - c.p[1], x[2] - c.p[2]};
+    // body frame: xb = R^T d
+    xb[0] = c.R[0] * d[0] + c.R[3] * d[1] + c.R[6] * d[2];
+    xb[1] = c.R[1] * d[0] + c.R[4] * d[1] + c.R[7] * d[2];
+    xb[2] = c.R[2] * d[0] + c.R[5] * d[1] + c.R[8] * d[2];
+}
+
+// Ellipsoid (kind 5): the exact signed distance by D. Eberly, "Distance from a Point to an Ellipse, an Ellipsoid, or a
+// Hyperellipsoid" (Geometric Tools): axes sorted e0 >= e1 >= e2, the query reflected into the first octant, zero
+// coordinates and the medial set handled by the lower-dimensional problems, the root of the secular equation
+//   g(s) = (n0 / (s + r0))^2 + (n1 / (s + r1))^2 + (z2 / (s + 1))^2 - 1,  r_i = (e_i / e2)^2, n_i = r_i z_i, z_i = y_i / e_i
+// bracketed in [z2 - 1, |(n0, n1, z2)| - 1] and found by bisection, all in FP64.  The loop stops when the bracket is
+// below 2^-50 of s + 1 (the smallest denominator: the nearest point to ~1e-15) and runs ELL_MAX_ITERS times at most.
+// The 2D problem is the same with n1 = 0.
+constexpr int ELL_MAX_ITERS = 128;
+MPM_DEV double ell_root(double n0, double r0, double n1, double r1, double z2, double g) {
+    double s0 = z2 - 1.0, s1 = g < 0.0 ? 0.0 : sqrt(n0 * n0 + n1 * n1 + z2 * z2) - 1.0, s = 0.5 * (s0 + s1);
+    for (int i = 0; i < ELL_MAX_ITERS; ++i) {
+        s = 0.5 * (s0 + s1);
+        if (s == s0 || s == s1 || s1 - s0 <= 0x1p-50 * (s0 + 1.0)) break;
+        const double a = n0 / (s + r0), b = n1 / (s + r1), q = z2 / (s + 1.0);
+        const double gs = a * a + b * b + q * q - 1.0;
+        if (gs > 0.0) s0 = s;
+        else if (gs < 0.0) s1 = s;
+        else break;
+    }
+    return s;
+}
+// ellipse e0 >= e1 > 0, query (y0, y1) >= 0: nearest point (x0, x1)
+MPM_DEV void ell_nearest2(double e0, double e1, double y0, double y1, double& x0, double& x1) {
+    if (y1 > 0.0) {
+        if (y0 > 0.0) {
+            const double z0 = y0 / e0, z1 = y1 / e1, g = z0 * z0 + z1 * z1 - 1.0;
+            if (g != 0.0) {
+                const double r0 = (e0 / e1) * (e0 / e1), s = ell_root(r0 * z0, r0, 0.0, 1.0, z1, g);
+                x0 = r0 * y0 / (s + r0);
+                x1 = y1 / (s + 1.0);
+            } else {
+                x0 = y0; x1 = y1;
+            }
+        } else {
+            x0 = 0.0; x1 = e1;
+        }
+    } else {
+        const double numer0 = e0 * y0, denom0 = e0 * e0 - e1 * e1;
+        if (numer0 < denom0) {
+            const double xde0 = numer0 / denom0;
+            x0 = e0 * xde0;
+            x1 = e1 * sqrt(fmax(1.0 - xde0 * xde0, 0.0));
+        } else {
+            x0 = e0; x1 = 0.0;
+        }
+    }
+}
+// ellipsoid e0 >= e1 >= e2 > 0, query y >= 0: nearest point x
+MPM_DEV void ell_nearest3(double e0, double e1, double e2, double y0, double y1, double y2, double& x0, double& x1, double& x2) {
+    if (y2 > 0.0) {
+        if (y1 > 0.0) {
+            if (y0 > 0.0) {
+                const double z0 = y0 / e0, z1 = y1 / e1, z2 = y2 / e2, g = z0 * z0 + z1 * z1 + z2 * z2 - 1.0;
+                if (g != 0.0) {
+                    const double r0 = (e0 / e2) * (e0 / e2), r1 = (e1 / e2) * (e1 / e2);
+                    const double s = ell_root(r0 * z0, r0, r1 * z1, r1, z2, g);
+                    x0 = r0 * y0 / (s + r0);
+                    x1 = r1 * y1 / (s + r1);
+                    x2 = y2 / (s + 1.0);
+                } else {
+                    x0 = y0; x1 = y1; x2 = y2;
+                }
+            } else {
+                x0 = 0.0;
+                ell_nearest2(e1, e2, y1, y2, x1, x2);
+            }
+        } else if (y0 > 0.0) {
+            x1 = 0.0;
+            ell_nearest2(e0, e2, y0, y2, x0, x2);
+        } else {
+            x0 = 0.0; x1 = 0.0; x2 = e2;
+        }
+    } else {
+        const double denom0 = e0 * e0 - e2 * e2, denom1 = e1 * e1 - e2 * e2;
+        const double numer0 = e0 * y0, numer1 = e1 * y1;
+        if (numer0 < denom0 && numer1 < denom1) {
+            const double xde0 = numer0 / denom0, xde1 = numer1 / denom1, discr = 1.0 - xde0 * xde0 - xde1 * xde1;
+            if (discr > 0.0) {   // (the medial set: the nearest point leaves the plane y2 = 0)
+                x0 = e0 * xde0; x1 = e1 * xde1; x2 = e2 * sqrt(discr);
+                return;
+            }
+        }
+        x2 = 0.0;
+        ell_nearest2(e0, e1, y0, y1, x0, x1);
+    }
+}
+// signed distance to the ellipsoid with semi-axes dims along x_B, y_B, z_B; gb = normalize(N / a^2) at the nearest point
+// N (distance_to_point_callback.cc:331-350)
+MPM_DEV float sdf_ellipsoid(const Collider& c, const float* x, float* gb) {
+    const double d[3] = {(double)x[0] - c.p[0], (double)x[1] - c.p[1], (double)x[2] - c.p[2]};
+    double y[3], a[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        y[i] = (double)c.R[i] * d[0] + (double)c.R[3 + i] * d[1] + (double)c.R[6 + i] * d[2];
+        a[i] = c.dims[i];
+    }
+    // sort the axes (descending), carrying which body axis each one is: compare-swaps of scalars, no indexed arrays
+    double e0 = a[0], e1 = a[1], e2 = a[2], y0 = fabs(y[0]), y1 = fabs(y[1]), y2 = fabs(y[2]);
+    int l0 = 0, l1 = 1, l2 = 2;
+    auto sw = [](double& p, double& q, double& u, double& v, int& i, int& j) {
+        const double t = p; p = q; q = t;
+        const double w = u; u = v; v = w;
+        const int k = i; i = j; j = k;
+    };
+    if (e0 < e1) sw(e0, e1, y0, y1, l0, l1);
+    if (e1 < e2) sw(e1, e2, y1, y2, l1, l2);
+    if (e0 < e1) sw(e0, e1, y0, y1, l0, l1);
+    double x0, x1, x2;
+    ell_nearest3(e0, e1, e2, y0, y1, y2, x0, x1, x2);
+    const double dist = sqrt((x0 - y0) * (x0 - y0) + (x1 - y1) * (x1 - y1) + (x2 - y2) * (x2 - y2));
+    double n[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const double xi = l0 == i ? x0 : (l1 == i ? x1 : x2);
+        n[i] = (y[i] < 0.0 ? -xi : xi) / (a[i] * a[i]);   // (reflected back out of the first octant)
+    }
+    const double inv = 1.0 / sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+    gb[0] = (float)(n[0] * inv); gb[1] = (float)(n[1] * inv); gb[2] = (float)(n[2] * inv);
+    const double g = (y[0] / a[0]) * (y[0] / a[0]) + (y[1] / a[1]) * (y[1] / a[1]) + (y[2] / a[2]) * (y[2] / a[2]);
+    return (float)(g < 1.0 ? -dist : dist);
+}
+
+// signed distance of the world point x to collider c and its unit gradient in the world
+MPM_DEV float collider_sdf(const Collider& c, const float* x, float* grad) {
+    float gb[3], phi;
+    if (c.kind == 5) {
+        phi = sdf_ellipsoid(c, x, gb);
+    } else {
+        float xb[3];
+        body_coords(c, x, xb);
+        phi = sdf_closed(c, xb, gb);
     }
     mulv3(c.R, gb, grad);         // world = R gb
     return phi;
+}
+
+// kinds 0-4 only: the same as collider_sdf without the ellipsoid's solve (k_ct_gen_write<false>)
+MPM_DEV float collider_sdf_closed(const Collider& c, const float* x, float* grad) {
+    float xb[3], gb[3];
+    body_coords(c, x, xb);
+    const float phi = sdf_closed(c, xb, gb);
+    mulv3(c.R, gb, grad);
+    return phi;
+}
+
+// the ellipsoid's implicit function sum (x_i / (s a_i))^2 at the body-frame point xb (no iteration)
+MPM_DEV float ell_implicit(const Collider& c, const float* xb, float s) {
+    const float u = xb[0] / (s * c.dims[0]), v = xb[1] / (s * c.dims[1]), w = xb[2] / (s * c.dims[2]);
+    return u * u + v * v + w * w;
+}
+
+// membership of a contact pair: THE predicate of k_ct_gen_count_scan and k_ct_gen_write
+MPM_DEV bool collider_inside(const Collider& c, const float* x) {
+    float xb[3], gb[3];
+    body_coords(c, x, xb);
+    return c.kind == 5 ? ell_implicit(c, xb, 1.f) < 1.f : sdf_closed(c, xb, gb) < 0.f;
+}
+
+// k_ct_watch: may x be within `margin` of the inside?  Never false when phi(x) < margin.  Kinds 0-4 ask it of their
+// closed form (exact); the ellipsoid asks whether x lies in the ellipsoid scaled by s = 1 + margin / min a_i: the support
+// function of E is at least min a_i in every direction, so E + margin B lies inside s E (conservative; a false positive
+// costs one coupled substep).
+MPM_DEV bool collider_near(const Collider& c, const float* x, float margin) {
+    float xb[3], gb[3];
+    body_coords(c, x, xb);
+    return c.kind == 5 ? ell_implicit(c, xb, 1.f + margin / fminf(c.dims[0], fminf(c.dims[1], c.dims[2]))) < 1.f
+                       : sdf_closed(c, xb, gb) < margin;
+}
+
+// mpm_collider_signed_distance: phi and the unit world gradient of one collider at n world points (the pair generator's
+// distance function)
+__global__ __launch_bounds__(256) void k_ct_sdf_query(Collider c, int n, const float* x, float* phi, float* grad) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const float xk[3] = {x[k * 3], x[k * 3 + 1], x[k * 3 + 2]};
+    float g[3];
+    phi[k] = collider_sdf(c, xk, g);
+    grad[k * 3] = g[0]; grad[k * 3 + 1] = g[1]; grad[k * 3 + 2] = g[2];
 }
 
 // The colliders of a call travel as a kernel ARGUMENT while there are at most CT_COLLIDER_ARGS of them (no upload, no
@@ -361,10 +588,7 @@ __global__ __launch_bounds__(1024) void k_ct_gen_count_scan(DP p, const int* pid
         const float x[3] = {q[k].x, q[k].y, q[k].z};
         n[k] = 0;
         // (partitioned domain: only the particles this rank owns make contacts here)
-        for (int j = 0; j < cols.n && q[k].w > 0.f; ++j) {
-            float g[3];
-            n[k] += collider_sdf(collider_of(cols, j), x, g) < 0.f ? 1 : 0;
-        }
+        for (int j = 0; j < cols.n && q[k].w > 0.f; ++j) n[k] += collider_inside(collider_of(cols, j), x) ? 1 : 0;
     }
     const int sum = n[0] + n[1] + n[2] + n[3];
     int inc = sum;
@@ -412,10 +636,7 @@ __global__ __launch_bounds__(256) void k_ct_watch(DP p, ColliderTable cols, unsi
             const float4 q = S.q[0][slot];
             x[0] = q.x; x[1] = q.y; x[2] = q.z;
         }
-        for (int j = 0; j < cols.n; ++j) {
-            float g[3];
-            hit |= collider_sdf(collider_of(cols, j), x, g) < margin;
-        }
+        for (int j = 0; j < cols.n; ++j) hit |= collider_near(collider_of(cols, j), x, margin);
     }
     if (__ballot(hit) && (threadIdx.x & 63) == 0) p.ctl->watch_hit = seq;
 }
@@ -424,6 +645,9 @@ __global__ __launch_bounds__(256) void k_ct_watch(DP p, ColliderTable cols, unsi
 // (slot, collider).  Every workgroup adds up the block totals it needs itself (a few hundred ints: rounds 1 - 4 scanned
 // them with a single-workgroup kernel in between); workgroup 0 leaves the pair count where the solve reads it --
 // ContactState::n / n_wanted / gen_fault -- instead of sending it to the host.
+// ELL: the call has an ellipsoid.  Its FP64 distance solve needs about twice the registers of the rest of the kernel, so a
+// call without one runs the instance that leaves it out (and keeps the occupancy of the closed forms).
+template <bool ELL>
 __global__ __launch_bounds__(256) void k_ct_gen_write(DP p, const int* pids_api, ColliderTable cols, const int* offs,
                                                       const int* sums, int nb, int cap, uint32_t* api_idx, ContactDev c,
                                                       unsigned stamp) {
@@ -469,9 +693,11 @@ __global__ __launch_bounds__(256) void k_ct_gen_write(DP p, const int* pids_api,
     const float x[3] = {q.x, q.y, q.z};
     for (int j = 0; j < cols.n; ++j) {
         const Collider& cl = collider_of(cols, j);
+        if (!collider_inside(cl, x)) continue;   // (the count kernel's predicate)
+        if (at >= end || at >= cap) break;       // (defensive: never taken while the two kernels share the predicate)
         float g[3];
-        const float phi = collider_sdf(cl, x, g);
-        if (!(phi < 0.f) || at >= cap) continue;
+        // (the reference only emits distance < 0: a member's phi stays negative whatever the distance function's rounding)
+        const float phi = fminf(ELL ? collider_sdf(cl, x, g) : collider_sdf_closed(cl, x, g), -1.17549435e-38f);
         api_idx[at] = (uint32_t)s;
         const_cast<uint32_t*>(c.slot)[at] = slot;
         const_cast<uint32_t*>(c.body)[at] = cl.body;

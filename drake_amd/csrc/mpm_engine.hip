@@ -2462,6 +2462,13 @@ int mpm_generate_contact_pairs(mpm_handle_t e, size_t n_colliders, const mpm_col
     return generate_contacts(e, n_colliders, colliders, n_out);
 } MPM_CATCH_ALL
 
+int mpm_collider_signed_distance(mpm_handle_t e, const mpm_collider_t* c, size_t n, const float* x_W, float* phi_out,
+                                 float* grad_W_out) try {
+    READY(e);
+    REQUIRE(c && (n == 0 || (x_W && phi_out && grad_W_out)), "null argument");
+    return collider_signed_distance(e, c, n, x_W, phi_out, grad_W_out);
+} MPM_CATCH_ALL
+
 int mpm_download_contact_pairs(mpm_handle_t e, uint32_t* particle, uint32_t* body, float* dist, float* normal,
                                float* pos, float* rigid_v, float* p_WB) try {
     READY(e);
@@ -2607,6 +2614,7 @@ int mpm_world_coupled_substeps(mpm_handle_t* handles, int n_local, int n, const 
                                const mpm_collider_t* colliders, mpm_coupled_result_t* const* results) try {
     REQUIRE(handles && n_local >= 1 && n_local <= TEAM_MAX && prm && n >= 0, "bad arguments");
     REQUIRE(n_colliders > 0 && colliders && n_colliders <= 1024, "bad collider array");
+    if (int rc = validate_colliders(n_colliders, colliders)) return rc;   // (before any substep is enqueued)
     std::vector<mpm_engine*> L(handles, handles + n_local);
     for (mpm_engine* e : L) {
         READY(e);
@@ -2621,6 +2629,7 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
     REQUIRE(prm && n >= 0, "bad arguments");
     REQUIRE(n_colliders == 0 || colliders, "null collider array");
     REQUIRE(n_colliders <= 1024, "too many colliders");
+    if (int rc = validate_colliders(n_colliders, colliders)) return rc;   // (before any substep is enqueued)
     if (e->dp.dist.on) {
         REQUIRE(n_colliders > 0, "coupled substeps on a partitioned domain need colliders (contact-free: mpm_chain_substeps)");
         mpm_coupled_result_t* one[1] = {results};

@@ -182,6 +182,15 @@ class GpuMpmSolver {
     void GenerateContactPairsOnDevice(GpuMpmState<T>* s, const std::vector<mpm_collider_t>& colliders) const {
         mpm_check(mpm_generate_contact_pairs(s->h_, colliders.size(), colliders.data(), nullptr));
     }
+    // Extension: QueryObject::ComputeSignedDistanceToPoint for one analytic collider (any of the six kinds) at n world
+    // points, by the pair generator's distance function: phi (n) and the unit world gradient (3n) into phi / grad_W.
+    void ColliderSignedDistance(const GpuMpmState<T>& s, const mpm_collider_t& c, const std::vector<T>& p_WQ,
+                                std::vector<T>* phi, std::vector<T>* grad_W) const {
+        const size_t n = p_WQ.size() / 3;
+        phi->resize(n);
+        grad_W->resize(3 * n);
+        mpm_check(mpm_collider_signed_distance(s.h_, &c, n, p_WQ.data(), phi->data(), grad_W->data()));
+    }
     size_t ContactPairCount(GpuMpmState<T>* s) const {
         size_t n = 0;
         mpm_check(mpm_get_contact_pair_count(s->h_, &n));

@@ -346,8 +346,23 @@ MPM_API int mpm_copy_contact_pairs(mpm_handle_t h, size_t n_contacts, const uint
  *   kind 1 sphere:     radius dims[0], centre p_WB
  *   kind 2 box:        half extents dims[0..2] in the body frame
  *   kind 3 capsule:    radius dims[0], half length dims[1] along z_B
+ *   kind 4 cylinder:   radius dims[0], half length dims[1] along z_B (Drake's Cylinder(radius, length): (radius, length/2));
+ *                      Drake's conventions (distance_to_point_callback.cc:206-299, 401-489): inside, the nearest feature is
+ *                      the barrel on a tie with a cap; a point on the axis takes the radial direction +x_B
+ *   kind 5 ellipsoid:  semi-axes dims[0..2] along x_B, y_B, z_B (Drake's Ellipsoid(a, b, c): (a, b, c)); the exact signed
+ *                      distance (the reference's GJK/EPA answer is good to ~1e-6), gradient normalize(N / a^2) at the
+ *                      nearest point N
+ * Kinds 4 and 5 need every dimension they use finite and > 0 (MPM_ERR_INVALID otherwise, before anything is enqueued).
  * The pairs are left in the engine as if mpm_copy_contact_pairs had been called;
  * mpm_download_contact_pairs returns them (any pointer may be NULL). */
+enum {
+    MPM_COLLIDER_HALF_SPACE = 0,
+    MPM_COLLIDER_SPHERE = 1,
+    MPM_COLLIDER_BOX = 2,
+    MPM_COLLIDER_CAPSULE = 3,
+    MPM_COLLIDER_CYLINDER = 4,
+    MPM_COLLIDER_ELLIPSOID = 5
+};
 typedef struct mpm_collider {
     int32_t kind;
     uint32_t body;      /* index into the external-body accumulators */
@@ -358,6 +373,12 @@ typedef struct mpm_collider {
 } mpm_collider_t;
 MPM_API int mpm_generate_contact_pairs(mpm_handle_t h, size_t n_colliders, const mpm_collider_t *colliders,
                                        size_t *n_contacts_out);
+/* QueryObject::ComputeSignedDistanceToPoint (query_object.h) for ONE collider of any kind, on the device: the signed
+ * distance phi and the unit world gradient of phi at n world points x_W (float[3n]), everywhere -- outside, inside and
+ * on the surface -- computed by the distance function of mpm_generate_contact_pairs.  phi_out: float[n],
+ * grad_W_out: float[3n]; caller-owned host arrays.  A synchronisation point. */
+MPM_API int mpm_collider_signed_distance(mpm_handle_t h, const mpm_collider_t *c, size_t n, const float *x_W,
+                                         float *phi_out, float *grad_W_out);
 /* n_contacts_out may be NULL: the call then waits for nothing -- the pairs are counted on the device and STAY counted
  * there; mpm_update_contact's launches have fixed grids and read the count on the device (the reference's driver reads
  * every position back, loops over the particles on the host and uploads the pairs, per substep:

@@ -35,6 +35,9 @@ def main():
                     help="SURVEY.md 8(d) config 3: floor z<0.25, k=1e6, d=1e-5, mu=1, dt=2e-4")
     ap.add_argument("--device-pairs", action="store_true",
                     help="contact pairs from mpm_generate_contact_pairs instead of the host round trip")
+    ap.add_argument("--colliders", default="floor", choices=["floor", "capsules16", "cylinders16", "ellipsoids16"],
+                    help="with --device-pairs: the floor, or 16 bodies of one kind on a 4 x 4 grid across the floor plane "
+                         "(rotated, cutting the cloth; no floor)")
     args = ap.parse_args()
     if args.survey_config3:
         args.floor, args.stiffness, args.damping, args.mu, args.dt = 0.25, 1e6, 1e-5, 1.0, 2e-4
@@ -42,6 +45,14 @@ def main():
     bits, layers, res = scenes.CONFIGS[args.config]
     dt, stiffness, damping = args.dt, args.stiffness, args.damping
     floor = [Collider(0, body=0, p_WB=(0.5, 0.5, args.floor))]
+    if args.colliders != "floor":
+        assert args.device_pairs, "--colliders needs --device-pairs"
+        kind, dims = {"capsules16": (3, (0.02, 0.05, 0)), "cylinders16": (4, (0.02, 0.05, 0)),
+                      "ellipsoids16": (5, (0.06, 0.03, 0.02))}[args.colliders]
+        c, s_ = np.cos(1.2), np.sin(1.2)
+        R = ((1, 0, 0), (0, c, -s_), (0, s_, c))   # tilted about x: a slanted cut through the sheets
+        floor = [Collider(kind, body=0, p_WB=(0.2 + 0.2 * (j % 4), 0.2 + 0.2 * (j // 4), args.floor), R_WB=R, dims=dims)
+                 for j in range(16)]
     g = GpuMpm(bits)
     # the stack starts with its lowest sheets already touching the floor and moves down at 0.5 m/s
     sheets = scenes.cloth_stack(layers, res, bits, z0=args.floor - 0.004)
@@ -94,7 +105,7 @@ def main():
             ncontacts.append(n)
     k = args.steps
     out = dict(config=args.config, particles=g.n_particles, steps=k, mu=args.mu, dt=dt, stiffness=stiffness,
-               damping=damping, floor=args.floor, pairs="device" if args.device_pairs else "host",
+               damping=damping, floor=args.floor, pairs="device" if args.device_pairs else "host", colliders=args.colliders,
                contacts_mean=float(np.mean(ncontacts)), contacts_max=int(np.max(ncontacts)),
                newton_iterations_mean=float(np.mean(iters)), newton_iterations_max=int(np.max(iters)),
                ms_per_substep={a: 1e3 * b / k for a, b in T.items()},
