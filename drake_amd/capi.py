@@ -48,6 +48,22 @@ class Collider(C.Structure):
         self.w[:] = [float(x) for x in w]
 
 
+class SdfCollider(C.Structure):
+    """mpm_sdf_collider_t: a mesh collider -- a lattice of mpm_sdf_shape_from_mesh (GpuMpm.sdf_shape_from_mesh) posed as
+    body `body` with the body's spatial velocity (an extension: the reference's driver never sees Mesh / Convex)."""
+    _fields_ = [("shape", C.c_uint32), ("body", C.c_uint32), ("p_WB", C.c_float * 3), ("R_WB", C.c_float * 9),
+                ("v", C.c_float * 3), ("w", C.c_float * 3)]
+
+    def __init__(self, shape, body=0, p_WB=(0, 0, 0), R_WB=None, v=(0, 0, 0), w=(0, 0, 0)):
+        super().__init__()
+        self.shape, self.body = int(shape), int(body)
+        R = np.eye(3, dtype=np.float32) if R_WB is None else np.asarray(R_WB, np.float32).reshape(3, 3)
+        self.p_WB[:] = [float(x) for x in p_WB]
+        self.R_WB[:] = [float(x) for x in R.reshape(-1)]
+        self.v[:] = [float(x) for x in v]
+        self.w[:] = [float(x) for x in w]
+
+
 class GridCollider(C.Structure):
     """mpm_grid_collider_t: shape 0 sphere / 1 half-space; mode 0 fixed / 1 slip while approaching / 2 slip."""
     _fields_ = [("shape", C.c_int32), ("mode", C.c_int32), ("p", C.c_float * 3), ("n", C.c_float * 3),
@@ -135,7 +151,8 @@ SYMBOLS = [
     "mpm_counts", "mpm_grid_touched_cnt", "mpm_dump_cpu_state", "mpm_reallocate_external_bodies",
     "mpm_external_body_force_to_host", "mpm_rebuild_mapping", "mpm_calc_fem_state_and_force", "mpm_particle_to_grid",
     "mpm_update_grid", "mpm_grid_to_particle", "mpm_sync", "mpm_sync_particle_state_to_cpu", "mpm_dump_obj",
-    "mpm_copy_contact_pairs", "mpm_generate_contact_pairs", "mpm_collider_signed_distance", "mpm_download_contact_pairs", "mpm_update_contact", "mpm_set_dump_dir", "mpm_substep", "mpm_run_substeps",
+    "mpm_copy_contact_pairs", "mpm_generate_contact_pairs", "mpm_collider_signed_distance", "mpm_sdf_shape_from_mesh", "mpm_sdf_shape_info", "mpm_sdf_shape_download",
+    "mpm_set_sdf_colliders", "mpm_sdf_collider_signed_distance", "mpm_download_contact_pairs", "mpm_update_contact", "mpm_set_dump_dir", "mpm_substep", "mpm_run_substeps",
     "mpm_profile_substeps", "mpm_set_stream", "mpm_set_deterministic", "mpm_get_stats", "mpm_debug_counters", "mpm_grid_gather",
     "mpm_halo_buffer_bytes", "mpm_halo_pack", "mpm_halo_add", "mpm_update_grid_from_sums", "mpm_substep_begin",
     "mpm_substep_end", "mpm_substep_begin_halo", "mpm_substep_mid_halo", "mpm_substep_end_halo", "mpm_chain_unique_id",
@@ -243,6 +260,11 @@ def load_library(build: bool = True):
         "mpm_substep_end": [vp, f, i],
         "mpm_generate_contact_pairs": [vp, sz, vp, P(sz)],
         "mpm_collider_signed_distance": [vp, vp, sz, vp, vp, vp],
+        "mpm_sdf_shape_from_mesh": [vp, vp, sz, vp, sz, f, i, P(C.c_uint32)],
+        "mpm_sdf_shape_info": [vp, C.c_uint32, vp, vp, P(f)],
+        "mpm_sdf_shape_download": [vp, C.c_uint32, vp],
+        "mpm_set_sdf_colliders": [vp, sz, vp],
+        "mpm_sdf_collider_signed_distance": [vp, vp, sz, vp, vp, vp],
         "mpm_download_contact_pairs": [vp, vp, vp, vp, vp, vp, vp, vp],
         "mpm_set_deterministic": [vp, i],
         "mpm_set_fast_math": [vp, i],
@@ -550,6 +572,42 @@ class GpuMpm:
         n = int(x.shape[0])
         phi, grad = np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
         self._ck(self.lib.mpm_collider_signed_distance(self.h, C.byref(collider), n, _ptr(x), _ptr(phi), _ptr(grad)))
+        return phi, grad
+
+    def sdf_shape_from_mesh(self, verts, tris, cell, pad_cells=2) -> int:
+        """mpm_sdf_shape_from_mesh: the signed-distance lattice of a triangle mesh (verts (n, 3) in the body frame, tris
+        (m, 3) vertex indices) built on the device; -> its shape id (the engine's until it is destroyed)"""
+        v = _f32(verts, (-1, 3))
+        t = np.ascontiguousarray(np.asarray(tris).reshape(-1, 3), dtype=np.int32)
+        out = C.c_uint32()
+        self._ck(self.lib.mpm_sdf_shape_from_mesh(self.h, _ptr(v), int(v.shape[0]), _ptr(t), int(t.shape[0]), float(cell),
+                                                  int(pad_cells), C.byref(out)))
+        return int(out.value)
+
+    def sdf_shape_info(self, shape):
+        """-> (nodes per axis (3,) int, lo (3,) float32, cell)"""
+        n, lo, cell = np.zeros(3, np.int32), np.zeros(3, np.float32), C.c_float()
+        self._ck(self.lib.mpm_sdf_shape_info(self.h, int(shape), _ptr(n), _ptr(lo), C.byref(cell)))
+        return n, lo, float(cell.value)
+
+    def sdf_shape_download(self, shape):
+        """the lattice values as an array (n_z, n_y, n_x) (x fastest in memory)"""
+        n, _, _ = self.sdf_shape_info(shape)
+        out = np.zeros((int(n[2]), int(n[1]), int(n[0])), np.float32)
+        self._ck(self.lib.mpm_sdf_shape_download(self.h, int(shape), _ptr(out)))
+        return out
+
+    def set_sdf_colliders(self, colliders):
+        """mpm_set_sdf_colliders: the engine's mesh colliders (SdfCollider list; empty clears them)"""
+        arr = (SdfCollider * max(len(colliders), 1))(*colliders)
+        self._ck(self.lib.mpm_set_sdf_colliders(self.h, len(colliders), arr))
+
+    def sdf_collider_signed_distance(self, collider, points):
+        """mpm_sdf_collider_signed_distance: points (n, 3) in the world -> (phi (n,), unit world gradient (n, 3))"""
+        x = _f32(points, (-1, 3))
+        n = int(x.shape[0])
+        phi, grad = np.zeros(n, np.float32), np.zeros((n, 3), np.float32)
+        self._ck(self.lib.mpm_sdf_collider_signed_distance(self.h, C.byref(collider), n, _ptr(x), _ptr(phi), _ptr(grad)))
         return phi, grad
 
     def contact_pair_count(self) -> int:

@@ -232,11 +232,14 @@ static ColliderTable collider_table(const ContactBuffers& b) {
     } else {
         tab.dev = b.colliders;   // (uploaded by generate_contacts when they changed)
     }
+    tab.n_mesh = (int)b.last_mesh.size();
+    tab.mesh = b.mesh;           // (likewise)
     return tab;
 }
 // see k_ct_watch (mpm_run_coupled_substeps); `p` carries the gate of the substep in front of it
 static void launch_contact_watch(mpm_engine* e, const DP& p, unsigned seq) {
-    hipLaunchKernelGGL(k_ct_watch, dim3(1024), dim3(256), 0, e->stream, p, collider_table(e->cb), seq);
+    const ColliderTable tab = collider_table(e->cb);
+    hipLaunchKernelGGL(tab.n_mesh ? k_ct_watch<true> : k_ct_watch<false>, dim3(1024), dim3(256), 0, e->stream, p, tab, seq);
 }
 static int generate_contacts_launch(mpm_engine* e) {
     ContactBuffers& b = e->cb;
@@ -245,14 +248,18 @@ static int generate_contacts_launch(mpm_engine* e) {
     const ColliderTable tab = collider_table(b);
     const size_t np = e->np, padded = ((np + 1 + 4095) / 4096) * 4096;
     const int nb = (int)(padded / 4096);
-    hipLaunchKernelGGL(k_ct_gen_count_scan, dim3(nb), dim3(1024), 0, s, p, (const int*)e->d_pids_api, tab, b.gen_cnt, b.gen_sums);
+    const bool mesh = tab.n_mesh > 0;
+    hipLaunchKernelGGL(mesh ? k_ct_gen_count_scan<true> : k_ct_gen_count_scan<false>, dim3(nb), dim3(1024), 0, s, p,
+                       (const int*)e->d_pids_api, tab, b.gen_cnt, b.gen_sums);
     ContactDev c{};
     c.n = -1;
     c.st = b.st;
     c.slot = b.slot; c.body = b.body; c.dist = b.dist; c.normal = b.normal; c.pos = b.pos;
     c.rigid_v = b.rigid_v; c.p_WB = b.p_WB; c.vel = b.vel;
     b.gen_stamp += 1;   // (the solve that follows names this generation: k_ct_keys refuses a count another one left)
-    hipLaunchKernelGGL(b.has_ellipsoid ? k_ct_gen_write<true> : k_ct_gen_write<false>, dim3(e->g_np), dim3(256), 0, s, p, (const int*)e->d_pids_api, tab, (const int*)b.gen_cnt,
+    auto* write = b.has_ellipsoid ? (mesh ? k_ct_gen_write<true, true> : k_ct_gen_write<true, false>)
+                                  : (mesh ? k_ct_gen_write<false, true> : k_ct_gen_write<false, false>);
+    hipLaunchKernelGGL(write, dim3(e->g_np), dim3(256), 0, s, p, (const int*)e->d_pids_api, tab, (const int*)b.gen_cnt,
                        (const int*)b.gen_sums, nb, (int)std::min<size_t>(b.cap, 0x7FFFFFFF), b.api_idx, c, b.gen_stamp);
     HIP_TRY(hipGetLastError());
     b.dev_counted = true;
@@ -276,6 +283,50 @@ static int validate_colliders(size_t n_col, const mpm_collider_t* cols) {
     return 0;
 }
 
+// the bodies of the engine's mesh colliders (checked where the pairs are made, and before a coupled call enqueues anything)
+static int validate_mesh_bodies(const mpm_engine* e) {
+    for (const mpm_sdf_collider_t& m : e->cb.mesh_set)
+        REQUIRE(m.body < std::max<size_t>(e->cb.n_bodies, 1), "mesh collider body index out of range");
+    return 0;
+}
+
+// the engine's mesh colliders as the kernels read them; uploaded (a synchronisation point) only when they have changed
+static MeshCollider mesh_collider(const SdfShape& sh, const mpm_sdf_collider_t& c) {
+    MeshCollider m;
+    std::memset(&m, 0, sizeof(m));   // (padding included: the table is compared bytewise)
+    m.val = sh.val;
+    for (int a = 0; a < 3; ++a) {
+        m.n[a] = sh.n[a];
+        m.cmin[a] = sh.cmin[a];
+        m.cmax[a] = sh.cmax[a];
+        m.lo[a] = sh.lo[a];
+        m.hi[a] = sh.hi[a];
+        m.p[a] = c.p_WB[a];
+        m.v[a] = c.v[a];
+        m.w[a] = c.w[a];
+    }
+    for (int a = 0; a < 9; ++a) m.R[a] = c.R_WB[a];
+    m.cell = sh.cell;
+    m.inv = 1.f / sh.cell;
+    m.body = c.body;
+    return m;
+}
+static int upload_mesh_table(mpm_engine* e) {
+    ContactBuffers& b = e->cb;
+    std::vector<MeshCollider> t;
+    t.reserve(b.mesh_set.size());
+    for (const mpm_sdf_collider_t& c : b.mesh_set) t.push_back(mesh_collider(b.shapes[c.shape], c));
+    if (t.size() == b.last_mesh.size() && (t.empty() || std::memcmp(t.data(), b.last_mesh.data(), t.size() * sizeof(MeshCollider)) == 0))
+        return 0;
+    if (t.size() > b.cap_mesh) {
+        if (int rc = grow(&b.mesh, t.size())) return rc;
+        b.cap_mesh = t.size();
+    }
+    if (!t.empty()) H2D(e, b.mesh, t.data(), t.size() * sizeof(MeshCollider));
+    b.last_mesh = std::move(t);
+    return 0;
+}
+
 static int generate_contacts(mpm_engine* e, size_t n_col, const mpm_collider_t* cols, size_t* n_out) {
     GrowPoison gp(e);
     TraceRange tr("mpm:contact pairs (device)");
@@ -284,16 +335,20 @@ static int generate_contacts(mpm_engine* e, size_t n_col, const mpm_collider_t* 
     b.n = 0;
     b.dev_counted = false;
     if (n_out) *n_out = 0;
-    if (n_col == 0) return 0;
+    // ("colliders": the call's analytic ones and the engine's mesh colliders)
+    const size_t n_mesh = b.mesh_set.size();
+    if (n_col + n_mesh == 0) return 0;
     if (int rc = validate_colliders(n_col, cols)) return rc;
     for (size_t j = 0; j < n_col; ++j)
         REQUIRE(cols[j].body < std::max<size_t>(b.n_bodies, 1), "collider body index out of range");
+    if (int rc = validate_mesh_bodies(e)) return rc;
     const Collider* in = reinterpret_cast<const Collider*>(cols);
     const bool same = b.last_colliders.size() == n_col && std::memcmp(b.last_colliders.data(), in, n_col * sizeof(Collider)) == 0;
     if (!same) {
         b.last_colliders.assign(in, in + n_col);
         b.has_ellipsoid = std::any_of(in, in + n_col, [](const Collider& c) { return c.kind == MPM_COLLIDER_ELLIPSOID; });
     }
+    if (int rc = upload_mesh_table(e)) return rc;
     if (n_col > (size_t)CT_COLLIDER_ARGS) {
         if (n_col > b.cap_colliders) {
             if (int rc = grow(&b.colliders, n_col)) return rc;
@@ -337,6 +392,157 @@ static int collider_signed_distance(mpm_engine* e, const mpm_collider_t* col, si
     std::memcpy(&c, col, sizeof(Collider));
     hipLaunchKernelGGL(k_ct_sdf_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, c, (int)n, (const float*)dx,
                        dphi, dgrad);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(phi, dphi, n * 4, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipMemcpyAsync(grad, dgrad, n * 12, hipMemcpyDeviceToHost, e->stream));
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+// ---- mesh colliders: the lattice build, the set, the query -------------------------------------------------------------
+
+// the build's launches: at least SDF_MIN_BRICKS workgroups each (a few per CU) while the lattice has them, and as many
+// triangles as keep one launch near SDF_PAIRS_PER_LAUNCH (node, triangle) pairs (whole LDS tiles)
+constexpr double SDF_PAIRS_PER_LAUNCH = 4.0e9;
+constexpr int SDF_MIN_BRICKS = 2048;
+
+static int sdf_shape_from_mesh(mpm_engine* e, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris,
+                               float cell, int pad, uint32_t* shape_out) {
+    GrowPoison gp(e);
+    TraceRange tr("mpm:sdf shape from mesh");
+    ContactBuffers& b = e->cb;
+    REQUIRE(n_tris > 0, "mesh: no triangles");
+    REQUIRE(n_tris <= (size_t)1 << 21, "mesh: more than 2^21 triangles");
+    REQUIRE(std::isfinite(cell) && cell > 0.f, "mesh: the lattice cell must be finite and > 0");
+    REQUIRE(pad >= 2, "mesh: pad_cells must be >= 2");
+    REQUIRE(n_verts > 0 && verts, "mesh: no vertices");
+    double mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (size_t t = 0; t < 3 * n_tris; ++t)
+        REQUIRE(tris[t] >= 0 && (size_t)tris[t] < n_verts, "mesh: a vertex index is out of range");
+    for (size_t v = 0; v < n_verts; ++v)
+        for (int a = 0; a < 3; ++a) {
+            const float x = verts[3 * v + a];
+            REQUIRE(std::isfinite(x), "mesh: a vertex is not finite");
+        }
+    for (size_t t = 0; t < 3 * n_tris; ++t)   // (the box of the vertices the triangles use)
+        for (int a = 0; a < 3; ++a) {
+            mn[a] = std::min(mn[a], (double)verts[3 * (size_t)tris[t] + a]);
+            mx[a] = std::max(mx[a], (double)verts[3 * (size_t)tris[t] + a]);
+        }
+    SdfShape sh;
+    double nodes = 1.0;
+    for (int a = 0; a < 3; ++a) {
+        const double na = std::ceil((mx[a] - mn[a]) / (double)cell) + 2.0 * pad + 1.0;
+        REQUIRE(std::isfinite(na) && na <= (double)(1 << 24), "mesh: more than 2^24 lattice nodes");
+        nodes *= na;
+        sh.n[a] = (int)na;
+    }
+    REQUIRE(nodes <= (double)(1 << 24), "mesh: more than 2^24 lattice nodes");
+    sh.cell = cell;
+    for (int a = 0; a < 3; ++a) {
+        sh.lo[a] = (float)mn[a] - (float)pad * cell;
+        sh.hi[a] = sh.lo[a] + (float)(sh.n[a] - 1) * cell;
+    }
+    REQUIRE(std::isfinite(sh.lo[0]) && std::isfinite(sh.lo[1]) && std::isfinite(sh.lo[2]) && std::isfinite(sh.hi[0]) &&
+            std::isfinite(sh.hi[1]) && std::isfinite(sh.hi[2]), "mesh: the lattice box is not finite");
+    // the corners of every triangle, three float4 each
+    std::vector<float> corners(n_tris * 12, 0.f);
+    for (size_t t = 0; t < n_tris; ++t)
+        for (int c = 0; c < 3; ++c)
+            for (int a = 0; a < 3; ++a) corners[t * 12 + c * 4 + a] = verts[3 * (size_t)tris[3 * t + c] + a];
+    const size_t n_nodes = (size_t)nodes;
+    struct Scratch {
+        float4* tri = nullptr;
+        int* box = nullptr;
+        float* val = nullptr;   // (released unless the shape keeps it)
+        float2* state = nullptr;
+        ~Scratch() {
+            if (tri) (void)hipFree(tri);
+            if (state) (void)hipFree(state);
+            if (box) (void)hipFree(box);
+            if (val) (void)hipFree(val);
+        }
+    } buf;
+    HIP_TRY(hipMalloc((void**)&buf.val, n_nodes * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&buf.tri, n_tris * 3 * sizeof(float4)));
+    HIP_TRY(hipMalloc((void**)&buf.box, 6 * sizeof(int)));
+    H2D(e, buf.tri, corners.data(), corners.size() * sizeof(float));
+    const int bx = (sh.n[0] + SDF_BX - 1) / SDF_BX, by = (sh.n[1] + SDF_BY - 1) / SDF_BY, bz = (sh.n[2] + SDF_BZ - 1) / SDF_BZ;
+    const int n_bricks = bx * by * bz;
+    const int per = (int)std::min<double>(n_bricks, std::max<double>(SDF_MIN_BRICKS, SDF_PAIRS_PER_LAUNCH / (256.0 * (double)n_tris)));
+    const int tiles = (int)std::max(1.0, std::floor(SDF_PAIRS_PER_LAUNCH / (256.0 * per * SDF_TILE)));
+    const int t_per = (int)std::min<size_t>(n_tris, (size_t)tiles * SDF_TILE);
+    if ((size_t)t_per < n_tris) HIP_TRY(hipMalloc((void**)&buf.state, n_nodes * sizeof(float2)));
+    for (int b0 = 0; b0 < n_bricks; b0 += per)
+        for (int t0 = 0; t0 < (int)n_tris; t0 += t_per) {
+            const int t1 = std::min<int>((int)n_tris, t0 + t_per);
+            hipLaunchKernelGGL(k_sdf_build, dim3((unsigned)std::min(per, n_bricks - b0)), dim3(256), 0, e->stream,
+                               (const float4*)buf.tri, t0, t1, sh.n[0], sh.n[1], sh.n[2], bx, by, sh.lo[0], sh.lo[1],
+                               sh.lo[2], cell, b0, t0 == 0 ? 1 : 0, t1 == (int)n_tris ? 1 : 0, buf.state, buf.val);
+            HIP_TRY(hipGetLastError());
+        }
+    const int init[6] = {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF, -1, -1, -1};
+    HIP_TRY(hipMemcpyAsync(buf.box, init, sizeof(init), hipMemcpyHostToDevice, e->stream));
+    hipLaunchKernelGGL(k_sdf_cull_box, dim3(1024), dim3(256), 0, e->stream, (const float*)buf.val, sh.n[0], sh.n[1], sh.n[2],
+                       cell, buf.box);
+    HIP_TRY(hipGetLastError());
+    int box[6];
+    D2H(e, box, buf.box, sizeof(box));
+    for (int a = 0; a < 3; ++a) {
+        sh.cmin[a] = box[a];          // (no cell below: cmin > cmax, every point is culled -- and phi >= cell everywhere)
+        sh.cmax[a] = box[3 + a];
+    }
+    REQUIRE(b.shapes.size() < 0xFFFFFFFFu, "too many shapes");
+    b.shapes.push_back(sh);
+    b.shapes.back().val = buf.val;
+    buf.val = nullptr;
+    *shape_out = (uint32_t)(b.shapes.size() - 1);
+    return 0;
+}
+
+static int sdf_shape_info(mpm_engine* e, uint32_t shape, int32_t* n, float* lo, float* cell) {
+    const ContactBuffers& b = e->cb;
+    REQUIRE(shape < b.shapes.size(), "unknown shape id");
+    const SdfShape& sh = b.shapes[shape];
+    for (int a = 0; a < 3; ++a) {
+        if (n) n[a] = sh.n[a];
+        if (lo) lo[a] = sh.lo[a];
+    }
+    if (cell) *cell = sh.cell;
+    return 0;
+}
+
+static int sdf_shape_download(mpm_engine* e, uint32_t shape, float* values) {
+    const ContactBuffers& b = e->cb;
+    REQUIRE(shape < b.shapes.size(), "unknown shape id");
+    const SdfShape& sh = b.shapes[shape];
+    D2H(e, values, sh.val, (size_t)sh.n[0] * sh.n[1] * sh.n[2] * sizeof(float));
+    return 0;
+}
+
+static int set_sdf_colliders(mpm_engine* e, size_t n, const mpm_sdf_collider_t* cols) {
+    ContactBuffers& b = e->cb;
+    for (size_t m = 0; m < n; ++m) REQUIRE(cols[m].shape < b.shapes.size(), "mesh collider: unknown shape id");
+    b.mesh_set.assign(cols, cols + n);   // (the next generation uploads the table: generate_contacts)
+    return 0;
+}
+
+// mpm_sdf_collider_signed_distance: k_ct_sdf_mesh_query on the engine's stream, through a scratch allocation of this call
+static int sdf_collider_signed_distance(mpm_engine* e, const mpm_sdf_collider_t* col, size_t n, const float* x, float* phi,
+                                        float* grad) {
+    REQUIRE(col->shape < e->cb.shapes.size(), "mesh collider: unknown shape id");
+    if (n == 0) return 0;
+    REQUIRE(n <= (size_t)0x7FFFFFFF / 3, "too many points");
+    struct Scratch {
+        float* p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } buf;
+    HIP_TRY(hipMalloc((void**)&buf.p, n * 7 * sizeof(float)));
+    float *dx = buf.p, *dphi = buf.p + 3 * n, *dgrad = buf.p + 4 * n;
+    HIP_TRY(hipMemcpyAsync(dx, x, n * 12, hipMemcpyHostToDevice, e->stream));
+    const MeshCollider m = mesh_collider(e->cb.shapes[col->shape], *col);
+    hipLaunchKernelGGL(k_ct_sdf_mesh_query, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, e->stream, m, (int)n,
+                       (const float*)dx, dphi, dgrad);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(phi, dphi, n * 4, hipMemcpyDeviceToHost, e->stream));
     HIP_TRY(hipMemcpyAsync(grad, dgrad, n * 12, hipMemcpyDeviceToHost, e->stream));

@@ -30,6 +30,7 @@
 #include "mpm_sort.h"
 #include "mpm_rootfind.h"
 #include "mpm_team_dev.h"
+#include "mpm_sdf_dev.h"
 
 namespace mpm {
 
@@ -173,6 +174,14 @@ struct Collider {        // mirrors mpm_collider_t (include/mpm_hip.h)
     float p[3], R[9], dims[3], v[3], w[3];
 };
 
+struct SdfShape {        // one lattice of mpm_sdf_shape_from_mesh (owned by the engine)
+    float* val = nullptr;
+    int n[3] = {0, 0, 0};
+    int cmin[3] = {0, 0, 0}, cmax[3] = {0, 0, 0};
+    float lo[3] = {0.f, 0.f, 0.f}, hi[3] = {0.f, 0.f, 0.f};
+    float cell = 0.f;
+};
+
 struct ContactBuffers {
     size_t n = 0, cap = 0;
     size_t n_bodies = 0, cap_bodies = 0;
@@ -225,7 +234,14 @@ struct ContactBuffers {
     uint32_t *prev_key = nullptr, *prev_api = nullptr, *prev_body = nullptr;
     // the colliders of the last mpm_generate_contact_pairs (a buffer overflow repeats the generation)
     std::vector<Collider> last_colliders;
-    bool has_ellipsoid = false;   // (one of last_colliders is kind 5: k_ct_gen_write<true>)
+    bool has_ellipsoid = false;   // (one of last_colliders is kind 5: k_ct_gen_write<true, *>)
+    // mesh colliders: the engine's lattices (mpm_sdf_shape_from_mesh), its set (mpm_set_sdf_colliders), and the table of
+    // the last generation as the kernels read it (uploaded to `mesh` when it changed)
+    std::vector<SdfShape> shapes;
+    std::vector<mpm_sdf_collider_t> mesh_set;
+    std::vector<MeshCollider> last_mesh;
+    MeshCollider* mesh = nullptr;
+    size_t cap_mesh = 0;
     bool sorted_in_alt = false;         // the sorted (key, order) of the last set-up sit in key2 / order2
     bool last_unchanged = false;        // the last solve found its pair list equal to its predecessor's
     // F_Bq_W_tau / F_Bq_W_f of the reference (cuda_mpm_model.cuh: float arrays fed by float atomics, whose sums depend on
@@ -235,7 +251,9 @@ struct ContactBuffers {
     double imp_unfix = 0.0;     // 1 / scale of what has been accumulated since the last reset
 
     void release() {
-        void* ptrs[] = {api_idx, colliders, gen_cnt, gen_sums, slot, body, dist, normal, pos, rigid_v, p_WB, vel, vel0, key, order, key2, order2, sort_hist,
+        for (SdfShape& sh : shapes)
+            if (sh.val) (void)hipFree(sh.val);
+        void* ptrs[] = {api_idx, colliders, mesh, gen_cnt, gen_sums, slot, body, dist, normal, pos, rigid_v, p_WB, vel, vel0, key, order, key2, order2, sort_hist,
                         cnode, cfx, cmass, cphi0, cR, cv0, crv, cvel, run, node_flag, flag_bits, node_list, node_runs, seg_part, gD, hg,
                         zone_buf[0], zone_buf[1], zone_buf[2], zone_buf[3], part, part_dir, st, it_log, body_acc,
                         prev_key, prev_api, prev_body};
@@ -548,10 +566,14 @@ __global__ __launch_bounds__(256) void k_ct_sdf_query(Collider c, int n, const f
 // synchronisation: an upload of 92 bytes per collider costs a blit launch and, with the host buffer on the stack, a wait
 // for the stream); beyond that through a device array that the host refreshes only when the colliders have changed.
 constexpr int CT_COLLIDER_ARGS = 16;
+// Mesh colliders (the engine's set, mpm_set_sdf_colliders) come after the call's analytic ones: collider index n + m.
+// They always travel through a device table; the kernels that read them are the MESH instances.
 struct ColliderTable {
     int n;
     const Collider* dev;   // non-null: n colliders there
     Collider c[CT_COLLIDER_ARGS];
+    int n_mesh;
+    const MeshCollider* mesh;
 };
 MPM_DEV const Collider& collider_of(const ColliderTable& t, int j) { return t.dev ? t.dev[j] : t.c[j]; }
 
@@ -568,6 +590,7 @@ MPM_DEV int ct_count(const ContactDev& c) { return min(max(ct_count_raw(c), 0), 
 // substep): a workgroup of 1024 threads owns a 4096-block, a thread four consecutive slots -- their three dependent loads
 // (API slot -> original id -> slot -> position) are four independent chains --, then the exclusive scan of the block's
 // counts in place and the block's total (what a count kernel + k_scan_blocks left until then).
+template <bool MESH>
 __global__ __launch_bounds__(1024) void k_ct_gen_count_scan(DP p, const int* pids_api, ColliderTable cols, int* cnt, int* sums) {
     __shared__ int s_w[16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -589,6 +612,8 @@ __global__ __launch_bounds__(1024) void k_ct_gen_count_scan(DP p, const int* pid
         n[k] = 0;
         // (partitioned domain: only the particles this rank owns make contacts here)
         for (int j = 0; j < cols.n && q[k].w > 0.f; ++j) n[k] += collider_inside(collider_of(cols, j), x) ? 1 : 0;
+        if (MESH)
+            for (int m = 0; m < cols.n_mesh && q[k].w > 0.f; ++m) n[k] += mesh_below(cols.mesh[m], x, 0.f) ? 1 : 0;
     }
     const int sum = n[0] + n[1] + n[2] + n[3];
     int inc = sum;
@@ -616,6 +641,7 @@ __global__ __launch_bounds__(1024) void k_ct_gen_count_scan(DP p, const int* pid
 // GridToParticle has just put them, faces at the centroid of their corners (CalcFemStateAndForce's first act,
 // cuda_mpm_kernels.cuh:203-207) -- so "no particle with phi < margin" means "no pairs", and the margin (a thousandth of a
 // cell) only absorbs the last bit of the centroid.  A hit is a plain store of the launch's number (any wave that sees one).
+template <bool MESH>
 __global__ __launch_bounds__(256) void k_ct_watch(DP p, ColliderTable cols, unsigned seq) {
     const Ctl* c = p.ctl;
     if (p.gated && c->skip_this) return;   // (the substep in front of this launch skipped itself: nothing has moved)
@@ -637,6 +663,8 @@ __global__ __launch_bounds__(256) void k_ct_watch(DP p, ColliderTable cols, unsi
             x[0] = q.x; x[1] = q.y; x[2] = q.z;
         }
         for (int j = 0; j < cols.n; ++j) hit |= collider_near(collider_of(cols, j), x, margin);
+        if (MESH)
+            for (int m = 0; m < cols.n_mesh; ++m) hit |= mesh_below(cols.mesh[m], x, margin);
     }
     if (__ballot(hit) && (threadIdx.x & 63) == 0) p.ctl->watch_hit = seq;
 }
@@ -647,7 +675,8 @@ __global__ __launch_bounds__(256) void k_ct_watch(DP p, ColliderTable cols, unsi
 // ContactState::n / n_wanted / gen_fault -- instead of sending it to the host.
 // ELL: the call has an ellipsoid.  Its FP64 distance solve needs about twice the registers of the rest of the kernel, so a
 // call without one runs the instance that leaves it out (and keeps the occupancy of the closed forms).
-template <bool ELL>
+// MESH: the engine has mesh colliders (they follow the analytic ones).
+template <bool ELL, bool MESH>
 __global__ __launch_bounds__(256) void k_ct_gen_write(DP p, const int* pids_api, ColliderTable cols, const int* offs,
                                                       const int* sums, int nb, int cap, uint32_t* api_idx, ContactDev c,
                                                       unsigned stamp) {
@@ -713,6 +742,30 @@ __global__ __launch_bounds__(256) void k_ct_gen_write(DP p, const int* pids_api,
             const_cast<float*>(c.p_WB)[at * 3 + d] = cl.p[d];
         }
         // initialize_contact_velocities (cuda_mpm_kernels.cuh:926-938)
+        c.vel[at * 3] = vq.x; c.vel[at * 3 + 1] = vq.y; c.vel[at * 3 + 2] = vq.z;
+        ++at;
+    }
+    if (!MESH) return;
+    for (int m = 0; m < cols.n_mesh; ++m) {
+        const MeshCollider& cl = cols.mesh[m];
+        if (!mesh_below(cl, x, 0.f)) continue;   // (the count kernel's predicate)
+        if (at >= end || at >= cap) break;
+        float g[3];
+        const float phi = fminf(mesh_sdf(cl, x, g), -1.17549435e-38f);
+        api_idx[at] = (uint32_t)s;
+        const_cast<uint32_t*>(c.slot)[at] = slot;
+        const_cast<uint32_t*>(c.body)[at] = cl.body;
+        const_cast<float*>(c.dist)[at] = phi;
+        const float r[3] = {x[0] - cl.p[0], x[1] - cl.p[1], x[2] - cl.p[2]};
+        const float rv[3] = {cl.v[0] + cl.w[1] * r[2] - cl.w[2] * r[1], cl.v[1] + cl.w[2] * r[0] - cl.w[0] * r[2],
+                             cl.v[2] + cl.w[0] * r[1] - cl.w[1] * r[0]};
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            const_cast<float*>(c.normal)[at * 3 + d] = -g[d];
+            const_cast<float*>(c.pos)[at * 3 + d] = x[d];
+            const_cast<float*>(c.rigid_v)[at * 3 + d] = rv[d];
+            const_cast<float*>(c.p_WB)[at * 3 + d] = cl.p[d];
+        }
         c.vel[at * 3] = vq.x; c.vel[at * 3 + 1] = vq.y; c.vel[at * 3 + 2] = vq.z;
         ++at;
     }

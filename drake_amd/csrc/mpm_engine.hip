@@ -2469,6 +2469,38 @@ int mpm_collider_signed_distance(mpm_handle_t e, const mpm_collider_t* c, size_t
     return collider_signed_distance(e, c, n, x_W, phi_out, grad_W_out);
 } MPM_CATCH_ALL
 
+int mpm_sdf_shape_from_mesh(mpm_handle_t e, const float* verts, size_t n_verts, const int32_t* tris, size_t n_tris, float cell,
+                            int pad_cells, uint32_t* shape_out) try {
+    READY(e);
+    REQUIRE(tris && shape_out, "null argument");
+    return sdf_shape_from_mesh(e, verts, n_verts, tris, n_tris, cell, pad_cells, shape_out);
+} MPM_CATCH_ALL
+
+int mpm_sdf_shape_info(mpm_handle_t e, uint32_t shape, int32_t n[3], float lo[3], float* cell) try {
+    READY(e);
+    return sdf_shape_info(e, shape, n, lo, cell);
+} MPM_CATCH_ALL
+
+int mpm_sdf_shape_download(mpm_handle_t e, uint32_t shape, float* values) try {
+    READY(e);
+    REQUIRE(values, "null argument");
+    return sdf_shape_download(e, shape, values);
+} MPM_CATCH_ALL
+
+int mpm_set_sdf_colliders(mpm_handle_t e, size_t n, const mpm_sdf_collider_t* colliders) try {
+    READY(e);
+    REQUIRE(n == 0 || colliders, "null collider array");
+    REQUIRE(n <= 1024, "too many mesh colliders");
+    return set_sdf_colliders(e, n, colliders);
+} MPM_CATCH_ALL
+
+int mpm_sdf_collider_signed_distance(mpm_handle_t e, const mpm_sdf_collider_t* c, size_t n, const float* x_W, float* phi_out,
+                                     float* grad_W_out) try {
+    READY(e);
+    REQUIRE(c && (n == 0 || (x_W && phi_out && grad_W_out)), "null argument");
+    return sdf_collider_signed_distance(e, c, n, x_W, phi_out, grad_W_out);
+} MPM_CATCH_ALL
+
 int mpm_download_contact_pairs(mpm_handle_t e, uint32_t* particle, uint32_t* body, float* dist, float* normal,
                                float* pos, float* rigid_v, float* p_WB) try {
     READY(e);
@@ -2613,12 +2645,15 @@ static int team_coupled_substeps(const std::vector<mpm_engine*>& L, int n, const
 int mpm_world_coupled_substeps(mpm_handle_t* handles, int n_local, int n, const mpm_coupled_params_t* prm, size_t n_colliders,
                                const mpm_collider_t* colliders, mpm_coupled_result_t* const* results) try {
     REQUIRE(handles && n_local >= 1 && n_local <= TEAM_MAX && prm && n >= 0, "bad arguments");
-    REQUIRE(n_colliders > 0 && colliders && n_colliders <= 1024, "bad collider array");
+    REQUIRE((n_colliders == 0 || colliders) && n_colliders <= 1024, "bad collider array");
     if (int rc = validate_colliders(n_colliders, colliders)) return rc;   // (before any substep is enqueued)
     std::vector<mpm_engine*> L(handles, handles + n_local);
     for (mpm_engine* e : L) {
         READY(e);
         REQUIRE(e->stream == L[0]->stream, "an in-process world runs on ONE stream (mpm_set_stream)");
+        // (colliders: the call's analytic ones and each rank's mesh colliders)
+        REQUIRE(n_colliders + e->cb.mesh_set.size() > 0, "bad collider array");
+        if (int rc = validate_mesh_bodies(e)) return rc;
     }
     return team_coupled_substeps(L, n, prm, n_colliders, colliders, results);
 } MPM_CATCH_ALL
@@ -2630,12 +2665,15 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
     REQUIRE(n_colliders == 0 || colliders, "null collider array");
     REQUIRE(n_colliders <= 1024, "too many colliders");
     if (int rc = validate_colliders(n_colliders, colliders)) return rc;   // (before any substep is enqueued)
+    // colliders: the call's analytic ones and the engine's mesh colliders (mpm_set_sdf_colliders)
+    const size_t n_all = n_colliders + e->cb.mesh_set.size();
+    if (int rc = validate_mesh_bodies(e)) return rc;
     if (e->dp.dist.on) {
-        REQUIRE(n_colliders > 0, "coupled substeps on a partitioned domain need colliders (contact-free: mpm_chain_substeps)");
+        REQUIRE(n_all > 0, "coupled substeps on a partitioned domain need colliders (contact-free: mpm_chain_substeps)");
         mpm_coupled_result_t* one[1] = {results};
         return team_coupled_substeps({e}, n, prm, n_colliders, colliders, results ? one : nullptr);
     }
-    if (n_colliders == 0) {   // nothing to couple with: contact-free substeps
+    if (n_all == 0) {   // nothing to couple with: contact-free substeps
         if (results)
             for (int s = 0; s < n; ++s) results[s] = mpm_coupled_result_t{};
         return mpm_run_substeps(e, n, prm->dt, prm->mpm_bc);
@@ -2673,7 +2711,7 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
     // since `watch_base` has seen a particle in a collider" (DP::gated bit 2).  After a chunk the host synchronises once and
     // reads how many of its substeps skipped themselves -- always the last ones: a hit is sticky -- and runs those as
     // coupled substeps.  A cloth that falls towards a body costs a contact-free substep plus the watch until it arrives.
-    const bool may_watch = n_colliders > 0 && !e->ct_no_watch;
+    const bool may_watch = n_all > 0 && !e->ct_no_watch;
     bool spec = false, spec_check = true;
     float spec_quiet_left = 0.f;
     unsigned watch_base = 0;
@@ -2742,7 +2780,7 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
         }
         auto t0 = clk::now();
         // (without colliders there is no solve whose publication would report a skipped substep: always checked)
-        const bool gate = n_colliders > 0 && !force_check && (e->ct_gate_always || e->quiet_factor * e->ct_quiet_left > 2.f * dt);
+        const bool gate = n_all > 0 && !force_check && (e->ct_gate_always || e->quiet_factor * e->ct_quiet_left > 2.f * dt);
         may_resort(e, dt);
         e->dp.gated = gate ? 1 : 0;
         if (!gate) {

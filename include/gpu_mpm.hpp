@@ -191,6 +191,26 @@ class GpuMpmSolver {
         grad_W->resize(3 * n);
         mpm_check(mpm_collider_signed_distance(s.h_, &c, n, p_WQ.data(), phi->data(), grad_W->data()));
     }
+    // Extension: mesh colliders (a Drake Mesh / Convex: the OBJ's vertices with the scale and X_BG baked in, body frame).
+    // The lattice is built once on the device; the set is posed once per step and tested after the analytic colliders
+    // by every pair generation.
+    uint32_t SdfShapeFromMesh(GpuMpmState<T>* s, const std::vector<float>& verts_B, const std::vector<int32_t>& tris,
+                              float cell, int pad_cells = 2) const {
+        uint32_t id = 0;
+        mpm_check(mpm_sdf_shape_from_mesh(s->h_, verts_B.data(), verts_B.size() / 3, tris.data(), tris.size() / 3, cell,
+                                          pad_cells, &id));
+        return id;
+    }
+    void SetSdfColliders(GpuMpmState<T>* s, const std::vector<mpm_sdf_collider_t>& colliders) const {
+        mpm_check(mpm_set_sdf_colliders(s->h_, colliders.size(), colliders.data()));
+    }
+    void SdfColliderSignedDistance(const GpuMpmState<T>& s, const mpm_sdf_collider_t& c, const std::vector<T>& p_WQ,
+                                   std::vector<T>* phi, std::vector<T>* grad_W) const {
+        const size_t n = p_WQ.size() / 3;
+        phi->resize(n);
+        grad_W->resize(3 * n);
+        mpm_check(mpm_sdf_collider_signed_distance(s.h_, &c, n, p_WQ.data(), phi->data(), grad_W->data()));
+    }
     size_t ContactPairCount(GpuMpmState<T>* s) const {
         size_t n = 0;
         mpm_check(mpm_get_contact_pair_count(s->h_, &n));

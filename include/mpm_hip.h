@@ -379,6 +379,60 @@ MPM_API int mpm_generate_contact_pairs(mpm_handle_t h, size_t n_colliders, const
  * grad_W_out: float[3n]; caller-owned host arrays.  A synchronisation point. */
 MPM_API int mpm_collider_signed_distance(mpm_handle_t h, const mpm_collider_t *c, size_t n, const float *x_W,
                                          float *phi_out, float *grad_W_out);
+
+/* ---- Mesh colliders (an extension) ----
+ * A rigid body made of triangles -- Drake's Mesh or Convex, whose ComputeSignedDistanceToPoint the reference's driver
+ * never sees (query_object.h: those shapes are ignored) -- as a signed-distance lattice held by the engine.  A scene with
+ * mesh colliders therefore makes contact pairs the reference would not make.
+ *
+ * mpm_sdf_shape_from_mesh builds the lattice of one mesh on the device and returns its shape id in *shape_out.  verts:
+ * float[3 n_verts] in the body frame B (the caller bakes in X_BG and the Mesh's scale); tris: int32[3 n_tris] vertex
+ * indices.  The lattice is axis-aligned in B with spacing `cell` and covers the mesh's bounding box plus pad_cells cells
+ * on every side: lo = min - pad_cells cell, n_a = ceil((max_a - min_a) / cell) + 2 pad_cells + 1 nodes per axis, node
+ * (i, j, k) at lo + (i, j, k) cell, values float, x fastest.  A node's value is the distance to the nearest triangle,
+ * negative where the generalised winding number w (the sum of the triangles' signed solid angles over 4 pi) has
+ * |w| > 0.5: the sign does not depend on the triangles' orientation and survives small cracks.  Refused with
+ * MPM_ERR_INVALID before anything is allocated or enqueued: a vertex index out of range, a non-finite vertex, n_tris == 0,
+ * a cell that is not finite and > 0, pad_cells < 2, more than 2^24 lattice nodes or more than 2^21 triangles.  The shape
+ * is the engine's until mpm_destroy.  A synchronisation point (a one-time build: O(nodes x triangles), split into
+ * launches over node bricks and triangle ranges so that none runs long; the result does not depend on the split).
+ * mpm_sdf_shape_info: the lattice's nodes per axis, lo and cell (any pointer may be NULL); mpm_sdf_shape_download: its
+ * n[0] n[1] n[2] values into a caller-owned float array. */
+MPM_API int mpm_sdf_shape_from_mesh(mpm_handle_t h, const float *verts, size_t n_verts, const int32_t *tris, size_t n_tris,
+                                    float cell, int pad_cells, uint32_t *shape_out);
+MPM_API int mpm_sdf_shape_info(mpm_handle_t h, uint32_t shape, int32_t n[3], float lo[3], float *cell);
+MPM_API int mpm_sdf_shape_download(mpm_handle_t h, uint32_t shape, float *values);
+/* A mesh collider: a shape posed as body `body` (p_WB, R_WB row-major as in mpm_collider_t) with the body's spatial
+ * velocity (v, w).  Its signed distance at a world point x, in float:
+ *   x_B = R_WB^T (x - p_WB); q = x_B clamped to the lattice box [lo, lo + (n - 1) cell] per axis;
+ *   t_a = (q_a - lo_a) * inv in float, inv = 1 / cell rounded to float once (a product, not a division);
+ *   the cell of q: i_a = min(floor(t_a), n_a - 2), fraction f_a = min(t_a - i_a, 1);
+ *   phi = trilinear(q) + |x_B - q|, the trilinear interpolation of the cell's eight corner values (x, then y, then z);
+ *   gradient: outside the box (|x_B - q| > 0) normalize(x_B - q), inside the analytic gradient of the trilinear cell at q,
+ *   normalised; when its squared length (value per cell inside, length outside) is <= 1e-30: +z_B; rotated to the world
+ *   with R_WB.
+ * A pair is a particle with phi < 0; its fields are those of mpm_collider_t's pairs: dist = phi, normal = -gradient,
+ * rigid_v = v + w x (x - p_WB), p_WB. */
+typedef struct mpm_sdf_collider {
+    uint32_t shape;
+    uint32_t body;
+    float p_WB[3];
+    float R_WB[9];
+    float v[3];
+    float w[3];
+} mpm_sdf_collider_t;
+/* The engine's mesh colliders, until the next call (n = 0 clears them; at most 1024, MPM_ERR_INVALID beyond).  Pair generation (mpm_generate_contact_pairs,
+ * mpm_run_coupled_substeps, mpm_world_coupled_substeps) tests them AFTER the call's analytic colliders: pairs in
+ * ascending (slot, collider) order, mesh collider m having index n_analytic + m, and "colliders" there means the analytic
+ * ones plus these (a call with no analytic collider but mesh colliders is not contact-free).  Rigid poses are fixed within
+ * a step: set them once per step, then run its substeps.  Stream-ordered: generations enqueued after this call see the
+ * new set.  An unknown shape id is refused here; a body out of range at the generating call, before anything is
+ * enqueued, as for mpm_collider_t. */
+MPM_API int mpm_set_sdf_colliders(mpm_handle_t h, size_t n, const mpm_sdf_collider_t *colliders);
+/* mpm_collider_signed_distance for one mesh collider: phi and the unit world gradient at n world points, by the pair
+ * generator's own function.  A synchronisation point. */
+MPM_API int mpm_sdf_collider_signed_distance(mpm_handle_t h, const mpm_sdf_collider_t *c, size_t n, const float *x_W,
+                                             float *phi_out, float *grad_W_out);
 /* n_contacts_out may be NULL: the call then waits for nothing -- the pairs are counted on the device and STAY counted
  * there; mpm_update_contact's launches have fixed grids and read the count on the device (the reference's driver reads
  * every position back, loops over the particles on the host and uploads the pairs, per substep:

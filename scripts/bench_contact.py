@@ -21,6 +21,21 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 
+def box_mesh(half):
+    """12 triangles: the box with half extents `half`, centred on the body origin"""
+    v = np.array([[sx * half[0], sy * half[1], sz * half[2]] for sx in (-1, 1) for sy in (-1, 1) for sz in (-1, 1)], np.float32)
+    f = np.array([(0, 1, 3), (0, 3, 2), (4, 6, 7), (4, 7, 5), (0, 4, 5), (0, 5, 1), (2, 3, 7), (2, 7, 6), (0, 2, 6), (0, 6, 4),
+                  (1, 5, 7), (1, 7, 3)], np.int32)
+    return v, f
+
+
+def slab_mesh(half_xy=0.5, depth=0.125):
+    """a slab under the whole domain whose top face is the body frame's z = 0"""
+    v, f = box_mesh((half_xy, half_xy, depth / 2))
+    v[:, 2] -= depth / 2
+    return v, f
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=30)
@@ -35,24 +50,36 @@ def main():
                     help="SURVEY.md 8(d) config 3: floor z<0.25, k=1e6, d=1e-5, mu=1, dt=2e-4")
     ap.add_argument("--device-pairs", action="store_true",
                     help="contact pairs from mpm_generate_contact_pairs instead of the host round trip")
-    ap.add_argument("--colliders", default="floor", choices=["floor", "capsules16", "cylinders16", "ellipsoids16"],
+    ap.add_argument("--colliders", default="floor",
+                    choices=["floor", "capsules16", "cylinders16", "ellipsoids16", "boxes16", "mesh", "mesh1", "mesh_floor"],
                     help="with --device-pairs: the floor, or 16 bodies of one kind on a 4 x 4 grid across the floor plane "
-                         "(rotated, cutting the cloth; no floor)")
+                         "(rotated, cutting the cloth; no floor).  Mesh colliders (mpm_set_sdf_colliders): mesh = the 16 "
+                         "boxes of boxes16 as 12-triangle meshes, mesh1 = one of them (on the cloth) alone, mesh_floor = a slab mesh "
+                         "whose top face is the floor plane")
     args = ap.parse_args()
     if args.survey_config3:
         args.floor, args.stiffness, args.damping, args.mu, args.dt = 0.25, 1e6, 1e-5, 1.0, 2e-4
-    from drake_amd import Collider, GpuMpm, scenes
+    from drake_amd import Collider, GpuMpm, SdfCollider, scenes
     bits, layers, res = scenes.CONFIGS[args.config]
     dt, stiffness, damping = args.dt, args.stiffness, args.damping
     floor = [Collider(0, body=0, p_WB=(0.5, 0.5, args.floor))]
+    mesh = []          # (shape builder, per-collider poses) of the mesh choices
     if args.colliders != "floor":
         assert args.device_pairs, "--colliders needs --device-pairs"
-        kind, dims = {"capsules16": (3, (0.02, 0.05, 0)), "cylinders16": (4, (0.02, 0.05, 0)),
-                      "ellipsoids16": (5, (0.06, 0.03, 0.02))}[args.colliders]
         c, s_ = np.cos(1.2), np.sin(1.2)
         R = ((1, 0, 0), (0, c, -s_), (0, s_, c))   # tilted about x: a slanted cut through the sheets
-        floor = [Collider(kind, body=0, p_WB=(0.2 + 0.2 * (j % 4), 0.2 + 0.2 * (j // 4), args.floor), R_WB=R, dims=dims)
-                 for j in range(16)]
+        grid = [(0.2 + 0.2 * (j % 4), 0.2 + 0.2 * (j // 4), args.floor) for j in range(16)]
+        box_half = (0.06, 0.03, 0.02)
+        if args.colliders in ("mesh", "mesh1"):
+            floor = []
+            mesh = [(box_mesh(box_half), 0.005, dict(p_WB=p, R_WB=R)) for p in (grid if args.colliders == "mesh" else grid[5:6])]
+        elif args.colliders == "mesh_floor":
+            floor = []
+            mesh = [(slab_mesh(), 1.0 / 128, dict(p_WB=(0.5, 0.5, args.floor)))]
+        else:
+            kind, dims = {"capsules16": (3, (0.02, 0.05, 0)), "cylinders16": (4, (0.02, 0.05, 0)),
+                          "ellipsoids16": (5, (0.06, 0.03, 0.02)), "boxes16": (2, box_half)}[args.colliders]
+            floor = [Collider(kind, body=0, p_WB=p, R_WB=R, dims=dims) for p in grid]
     g = GpuMpm(bits)
     # the stack starts with its lowest sheets already touching the floor and moves down at 0.5 m/s
     sheets = scenes.cloth_stack(layers, res, bits, z0=args.floor - 0.004)
@@ -60,6 +87,16 @@ def main():
         vel[:, 2] -= 0.5
     scenes.populate(g, sheets)
     g.reallocate_external_bodies(1)
+    build_ms = 0.0
+    if mesh:
+        shapes = {}
+        for (v, f), cell, pose in mesh:     # (one lattice per distinct mesh; a build is a synchronisation point)
+            key = (v.tobytes(), cell)
+            if key not in shapes:
+                t = time.perf_counter()
+                shapes[key] = g.sdf_shape_from_mesh(v, f, cell)
+                build_ms += 1e3 * (time.perf_counter() - t)
+        g.set_sdf_colliders([SdfCollider(shapes[(v.tobytes(), cell)], body=0, **pose) for (v, f), cell, pose in mesh])
     T = dict(transfer=0.0, pairs_host=0.0, copy_pairs=0.0, solve=0.0, step=0.0)
     iters, ncontacts = [], []
     for s in range(args.warmup + args.steps):
@@ -110,6 +147,8 @@ def main():
                newton_iterations_mean=float(np.mean(iters)), newton_iterations_max=int(np.max(iters)),
                ms_per_substep={a: 1e3 * b / k for a, b in T.items()},
                solve_us_per_iteration=1e6 * T["solve"] / max(1, int(np.sum(iters))), stats=g.stats())
+    if mesh:
+        out["sdf_build_ms"] = build_ms
     print(json.dumps(out))
 
 
