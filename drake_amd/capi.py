@@ -64,6 +64,25 @@ class SdfCollider(C.Structure):
         self.w[:] = [float(x) for x in w]
 
 
+class Pin(C.Structure):
+    """mpm_pin_t (include/mpm_hip.h): vertex `vertex` fixed to body `body` at p_BQ (body frame)."""
+    _fields_ = [("vertex", C.c_uint32), ("body", C.c_uint32), ("p_BQ", C.c_float * 3)]
+
+    def __init__(self, vertex=0, body=0, p_BQ=(0, 0, 0)):
+        super().__init__(int(vertex), int(body), (C.c_float * 3)(*[float(x) for x in p_BQ]))
+
+
+class BodyMotion(C.Structure):
+    """mpm_body_motion_t: pose (p_WB, R_WB row-major) at the start of the next substep, constant (v, w), world frame."""
+    _fields_ = [("body", C.c_uint32), ("p_WB", C.c_float * 3), ("R_WB", C.c_float * 9), ("v", C.c_float * 3),
+                ("w", C.c_float * 3)]
+
+    def __init__(self, body=0, p_WB=(0, 0, 0), R_WB=None, v=(0, 0, 0), w=(0, 0, 0)):
+        R = np.eye(3, dtype=np.float64).ravel() if R_WB is None else np.asarray(R_WB, dtype=np.float64).ravel()
+        super().__init__(int(body), (C.c_float * 3)(*[float(x) for x in p_WB]), (C.c_float * 9)(*[float(x) for x in R]),
+                         (C.c_float * 3)(*[float(x) for x in v]), (C.c_float * 3)(*[float(x) for x in w]))
+
+
 class GridCollider(C.Structure):
     """mpm_grid_collider_t: shape 0 sphere / 1 half-space; mode 0 fixed / 1 slip while approaching / 2 slip."""
     _fields_ = [("shape", C.c_int32), ("mode", C.c_int32), ("p", C.c_float * 3), ("n", C.c_float * 3),
@@ -168,7 +187,7 @@ SYMBOLS = [
     "mpm_get_contact_pair_count", "mpm_download_contact_log", "mpm_last_contact_counts",
     "mpm_debug_contact_counters", "mpm_run_coupled_substeps", "mpm_chain_direct_prepare", "mpm_chain_direct_connect",
     "mpm_debug_contact_count", "mpm_chain_direct_base", "mpm_chain_direct_connect_local", "mpm_team_prepare", "mpm_team_connect",
-    "mpm_world_coupled_substeps",
+    "mpm_world_coupled_substeps", "mpm_set_pins", "mpm_set_body_motions", "mpm_pins_inside_collider", "mpm_get_pins",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -279,6 +298,10 @@ def load_library(build: bool = True):
         "mpm_team_connect": [vp, vp, P(vp)],
         "mpm_world_coupled_substeps": [P(vp), i, i, vp, sz, vp, P(vp)],
         "mpm_run_coupled_substeps": [vp, i, vp, sz, vp, vp],
+        "mpm_set_pins": [vp, sz, vp],
+        "mpm_set_body_motions": [vp, sz, vp],
+        "mpm_pins_inside_collider": [vp, vp, C.c_uint32, vp, vp, P(sz)],
+        "mpm_get_pins": [vp, vp, sz, P(sz)],
         "mpm_get_fast_math": [vp, P(i)],
         "mpm_substep_begin_halo": [vp, f, i, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_void_p), sz],
         "mpm_substep_end_halo": [vp, f, i, i, P(C.c_void_p), sz],
@@ -632,6 +655,35 @@ class GpuMpm:
         if out:
             self._n_contacts = out[-1]["contacts"]
         return out
+
+    def set_pins(self, pins):
+        """mpm_set_pins: replaces the pin set by `pins` (a list of Pin, or a ctypes array of them; empty clears it)"""
+        arr = pins if isinstance(pins, C.Array) else (Pin * max(len(pins), 1))(*pins)
+        self._ck(self.lib.mpm_set_pins(self.h, len(pins), arr if len(pins) else None))
+
+    def set_body_motions(self, motions):
+        """mpm_set_body_motions: a list of BodyMotion (restarts those bodies' clocks)"""
+        arr = motions if isinstance(motions, C.Array) else (BodyMotion * max(len(motions), 1))(*motions)
+        self._ck(self.lib.mpm_set_body_motions(self.h, len(motions), arr))
+
+    def pins_inside_collider(self, shape, body, p_WB=(0, 0, 0), R_WB=None) -> int:
+        """mpm_pins_inside_collider (AddFixedConstraint's selection): pins every vertex with phi <= 0 for `shape` (a
+        Collider) to `body`, p_BQ from the body pose (p_WB, R_WB); -> the number of pins added"""
+        p = _f32(p_WB, (3,))
+        R = _f32(np.eye(3) if R_WB is None else R_WB, (9,))
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_pins_inside_collider(self.h, C.byref(shape), int(body), _ptr(p), _ptr(R), C.byref(n)))
+        return int(n.value)
+
+    def get_pins(self):
+        """mpm_get_pins: -> (vertex (n,) uint32, body (n,) uint32, p_BQ (n, 3) float32)"""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_pins(self.h, None, 0, C.byref(n)))
+        arr = (Pin * max(int(n.value), 1))()
+        self._ck(self.lib.mpm_get_pins(self.h, arr, int(n.value), C.byref(n)))
+        k = int(n.value)
+        return (np.array([arr[j].vertex for j in range(k)], np.uint32), np.array([arr[j].body for j in range(k)], np.uint32),
+                np.array([list(arr[j].p_BQ) for j in range(k)], np.float32).reshape(k, 3))
 
     @staticmethod
     def world_coupled_substeps(engines, n, dt, colliders, friction_mu, stiffness, damping, mpm_bc=-1, exact_line_search=False,

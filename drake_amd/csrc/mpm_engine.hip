@@ -16,6 +16,8 @@
 #include <string>
 #include <thread>
 #include <type_traits>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include "../../include/mpm_hip.h"
@@ -218,10 +220,21 @@ static void launch_fem_p2g(mpm_engine* e, float dt) {
     if (!forces) launch_fem_vertices(e);
     launch_p2g(e, dt, forces);
 }
-// (`p` may carry a halo class restriction)
+// the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins launches it (pins_ready has resolved the
+// table).  Everything after GridToParticle -- the coupled path's watch kernel included -- comes after it on the stream.
+static void launch_pins(mpm_engine* e, const DP& p, float dt) {
+    TraceRange tr("mpm:Pins");
+    const mpm_engine::PinState& ps = e->pin;
+    PinArgs a{ps.d_pins, (int)ps.set.size(), ps.d_mot, (int)ps.motion_body.size(), e->cb.body_acc, (int)e->cb.n_bodies,
+              e->dp.fix_p, ps.d_ticket};
+    const unsigned groups = (unsigned)std::min<size_t>((ps.set.size() + 255) / 256, 1024);
+    hipLaunchKernelGGL(k_pin, dim3(groups), dim3(256), 0, e->stream, p, a, dt);
+}
+// (`p` may carry a halo class restriction: only an engine without pins splits GridToParticle, see pins_refused)
 static void launch_g2p_with(mpm_engine* e, DP p, float dt) {
     TraceRange tr("mpm:GridToParticle");
     hipLaunchKernelGGL(k_g2p, dim3(std::min(768u, p.capI) * G2P_SPLIT), dim3(G2P_THREADS), 0, e->stream, p, dt);
+    if (!e->pin.set.empty() && p.halo_cls < 0) launch_pins(e, p, dt);
     e->last_tile_kernel = 2;
 }
 static void launch_grid(mpm_engine* e, const GridColliders& gc) {
@@ -643,6 +656,42 @@ int mpm_sync(mpm_handle_t e) try {
     return 0;
 } MPM_CATCH_ALL
 
+// ---- fixed constraints: checks of the substep entry points ------------------------------------------------------------
+// Every pin's body has a motion (MPM_ERR_INVALID otherwise, before anything is enqueued), and the device table is the
+// current pin set with each pin's motion slot resolved.
+static int pins_ready(mpm_engine* e) {
+    mpm_engine::PinState& ps = e->pin;
+    if (ps.set.empty()) return 0;
+    std::unordered_map<uint32_t, uint32_t> slot_of;
+    for (size_t k = 0; k < ps.motion_body.size(); ++k) slot_of[ps.motion_body[k]] = (uint32_t)k;
+    for (const mpm_pin_t& q : ps.set)
+        if (!slot_of.count(q.body))
+            return fail(MPM_ERR_INVALID, "pin on body " + std::to_string(q.body) + ", which has no motion: call mpm_set_body_motions first");
+    if (!ps.table_dirty) return 0;
+    std::vector<PinDev> t(ps.set.size());
+    for (size_t k = 0; k < t.size(); ++k) {
+        const mpm_pin_t& q = ps.set[k];
+        t[k] = PinDev{(uint32_t)e->dp.NfG + q.vertex, slot_of[q.body], q.body, {q.p_BQ[0], q.p_BQ[1], q.p_BQ[2]}};
+    }
+    if (t.size() > ps.cap_pins) {
+        HIP_TRY(hipStreamSynchronize(e->stream));   // (earlier substeps may still read the old table)
+        e->dfree(ps.d_pins);
+        ps.cap_pins = 0;
+        if (int rc = e->dalloc(&ps.d_pins, t.size(), false)) return rc;
+        ps.cap_pins = t.size();
+    }
+    if (!ps.d_ticket)
+        if (int rc = e->dalloc(&ps.d_ticket, 1, true)) return rc;
+    H2D(e, ps.d_pins, t.data(), t.size() * sizeof(PinDev));
+    ps.table_dirty = false;
+    return 0;
+}
+// partitioned and multi-rank engines have no pins (out of scope)
+static int pins_refused(const mpm_engine* e, const char* what) {
+    if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
+    return 0;
+}
+
 // ---- the solver calls -----------------------------------------------------
 static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, bool allow_gate, bool lean = false);
 
@@ -954,6 +1003,7 @@ int mpm_substep_begin(mpm_handle_t e, float dt) try {
 
 int mpm_substep_end(mpm_handle_t e, float dt, int bc) try {
     READY(e);
+    if (int rc = pins_ready(e)) return rc;
     REQUIRE(e->grid_state == 3, "mpm_substep_end without mpm_substep_begin");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
@@ -994,6 +1044,7 @@ int mpm_substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, co
 static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
                               void* const* send_bufs, size_t cap, uint32_t* const* counters) {
     READY(e);
+    if (int rc = pins_refused(e, "halo substeps")) return rc;
     may_resort(e, dt);
     REQUIRE(n >= 0 && n <= 2 && (n == 0 || (bx_lo && bx_hi && shift_bx && send_bufs)), "bad halo zone list");
     REQUIRE(n == 0 || (cap > 0 && cap < (1u << 24)), "bad halo buffer");
@@ -1040,6 +1091,7 @@ static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo,
 // neighbours' sums, to be overlapped with the exchange.  Zones = the ranges given to begin.
 int mpm_substep_mid_halo(mpm_handle_t e, float dt, int bc) try {
     READY(e);
+    if (int rc = pins_refused(e, "halo substeps")) return rc;
     REQUIRE(e->grid_state == 3 && !e->halo_mid_done, "mpm_substep_mid_halo needs mpm_substep_begin_halo first");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
@@ -1060,6 +1112,7 @@ int mpm_substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* co
 // with_g2p = false: the grid update only -- a coupled substep puts the contact solve between it and GridToParticle
 static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p) {
     READY(e);
+    if (int rc = pins_refused(e, "halo substeps")) return rc;
     REQUIRE(n >= 0 && n <= 2 && (n == 0 || recv_bufs), "bad halo buffer list");
     REQUIRE(e->grid_state == 3, "mpm_substep_end_halo without mpm_substep_begin_halo");
     GridColliders gc;
@@ -1177,6 +1230,7 @@ int mpm_chain_enable_migration(mpm_handle_t e, int every, size_t capacity_partic
 int mpm_chain_init(mpm_handle_t e, const char id[128], int rank, int world, int cut_lo_block, int cut_hi_block,
                    int pitch_blocks, int zone_blocks, size_t capacity_blocks, int periodic) try {
     READY(e);
+    if (int rc = pins_refused(e, "mpm_chain_init")) return rc;
     REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank / world");
     REQUIRE(zone_blocks >= 1 && capacity_blocks > 0 && capacity_blocks < (1u << 24), "bad halo geometry");
     // (id == NULL: the geometry only, no RCCL communicator -- for the direct transport, mpm_chain_direct_prepare)
@@ -1216,6 +1270,7 @@ static uint32_t* direct_flag(const mpm_engine::Chain& c, void* base, int side) {
 
 int mpm_chain_direct_prepare(mpm_handle_t e, char handle_out[64]) try {
     READY(e);
+    if (int rc = pins_refused(e, "mpm_chain_direct_prepare")) return rc;
     mpm_engine::Chain& c = e->chain;
     REQUIRE(handle_out, "null argument");
     REQUIRE(c.cap > 0, "mpm_chain_init first (with a NULL id for the geometry alone)");
@@ -1462,6 +1517,7 @@ static int chain_direct_end(mpm_engine* e, float dt, int bc, bool with_g2p) {
 
 int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     READY(e);
+    if (int rc = pins_refused(e, "mpm_chain_substeps")) return rc;
     mpm_engine::Chain& c = e->chain;
     REQUIRE(c.comm || c.direct, "mpm_chain_init first");
     const rccl_rt::Api* a = c.comm ? rccl_rt::api() : nullptr;
@@ -1577,6 +1633,8 @@ int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
 } MPM_CATCH_ALL
 
 int mpm_grid_to_particle(mpm_handle_t e, float dt) try {
+    if (e && e->finalized)
+        if (int rc = pins_ready(e)) return rc;   // (before the held-back phases are let go)
     if (e && can_defer(e) && e->pend.n == 4 && dt == e->pend.dt) {
         // the substep is complete: one gated substep, as mpm_run_substeps(1) enqueues it
         e->pend.n = 0;
@@ -1632,7 +1690,8 @@ static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, boo
 // kernel-to-kernel hand-over is cheaper than nine stream dispatches.
 static int step_graph_for(mpm_engine* e, float dt, int bc, const GridColliders& gc) {
     if (e->step_graph && e->step_graph_dt == dt && e->step_graph_bc == bc && e->step_graph_stream == e->stream &&
-        e->step_graph_gcv == e->grid_colliders_version)
+        e->step_graph_gcv == e->grid_colliders_version && e->step_graph_pinv == e->pin.version &&
+        e->step_graph_acc == e->cb.body_acc && e->step_graph_nb == e->cb.n_bodies)
         return 0;
     drop_step_graph(e);
     hipGraph_t g = nullptr;
@@ -1645,12 +1704,16 @@ static int step_graph_for(mpm_engine* e, float dt, int bc, const GridColliders& 
     e->step_graph_dt = dt;
     e->step_graph_bc = bc;
     e->step_graph_gcv = e->grid_colliders_version;
+    e->step_graph_pinv = e->pin.version;   // (k_pin's arguments: the pin table, the motions, the impulse accumulators)
+    e->step_graph_acc = e->cb.body_acc;
+    e->step_graph_nb = e->cb.n_bodies;
     e->step_graph_stream = e->stream;
     return 0;
 }
 
 int mpm_run_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     READY_NO_SETTLE(e);
+    if (int rc = pins_ready(e)) return rc;
     // owed substeps are run with the parameters they were enqueued with: settle before these change (and before phase
     // calls that were held back, which come first)
     if (e->pend.n || (e->maybe_owed && (dt != e->owed_dt || bc != e->owed_bc || e->grid_colliders_version != e->owed_gcv)))
@@ -1683,6 +1746,7 @@ int mpm_run_substeps(mpm_handle_t e, int n, float dt, int bc) try {
 
 int mpm_profile_substeps(mpm_handle_t e, int n, float dt, int bc, float* phase_ms, float* total_ms) try {
     READY(e);
+    if (int rc = pins_ready(e)) return rc;
     REQUIRE(n > 0 && n <= 4096, "n out of range");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
@@ -2046,6 +2110,7 @@ static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) 
 
 int mpm_dist_init(mpm_handle_t e, const mpm_dist_config_t* cfg) try {
     READY(e);
+    if (int rc = pins_refused(e, "mpm_dist_init")) return rc;
     REQUIRE(cfg, "null configuration");
     REQUIRE(!e->dp.dist.on, "mpm_dist_init called twice");
     REQUIRE(e->api_identity, "mpm_dist_init must precede RebuildMapping(sort = true)");
@@ -2600,6 +2665,7 @@ static int team_coupled_substeps(const std::vector<mpm_engine*>& L, int n, const
                                  const mpm_collider_t* colliders, mpm_coupled_result_t* const* results) {
     const float dt = prm->dt;
     for (mpm_engine* e : L) {
+        if (int rc = pins_refused(e, "team coupled substeps")) return rc;
         REQUIRE(e->dp.dist.on && e->team.on && e->chain.direct,
                 "coupled substeps on a partitioned domain need the direct halo (mpm_chain_direct_connect) and the team transport (mpm_team_connect)");
         REQUIRE(e->chain.pitch == 0, "coupled substeps: a partitioned domain has pitch 0");
@@ -2665,6 +2731,7 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
     REQUIRE(n_colliders == 0 || colliders, "null collider array");
     REQUIRE(n_colliders <= 1024, "too many colliders");
     if (int rc = validate_colliders(n_colliders, colliders)) return rc;   // (before any substep is enqueued)
+    if (int rc = pins_ready(e)) return rc;
     // colliders: the call's analytic ones and the engine's mesh colliders (mpm_set_sdf_colliders)
     const size_t n_all = n_colliders + e->cb.mesh_set.size();
     if (int rc = validate_mesh_bodies(e)) return rc;
@@ -2892,3 +2959,135 @@ int mpm_newton_bisect_f32(mpm_rootfind_fn fn, void* user, float x_lo, float x_hi
 } MPM_CATCH_ALL
 
 }  // extern "C"
+
+// ---- fixed constraints (mpm_set_pins, mpm_set_body_motions, mpm_pins_inside_collider, mpm_get_pins) --------------------
+static bool finite_n(const float* a, int n) {
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(a[k])) return false;
+    return true;
+}
+// R^T R = I and det R = 1, each entry within 1e-4 (float rotations that went through a few products)
+static bool is_rotation(const float* R) {
+    if (!finite_n(R, 9)) return false;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double d = 0.0;
+            for (int k = 0; k < 3; ++k) d += (double)R[k * 3 + i] * (double)R[k * 3 + j];
+            if (std::fabs(d - (i == j ? 1.0 : 0.0)) > 1e-4) return false;
+        }
+    const double det = (double)R[0] * ((double)R[4] * R[8] - (double)R[5] * R[7]) -
+                       (double)R[1] * ((double)R[3] * R[8] - (double)R[5] * R[6]) +
+                       (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
+    return std::fabs(det - 1.0) <= 1e-4;
+}
+static bool multi_rank(const mpm_engine* e) { return e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on; }
+
+int mpm_set_pins(mpm_handle_t e, size_t n, const mpm_pin_t* pins) try {
+    READY(e);
+    REQUIRE(!multi_rank(e), "pins are not available on a partitioned or multi-rank engine");
+    REQUIRE(n == 0 || pins, "null pin array");
+    std::vector<uint8_t> seen(e->nv, 0);
+    for (size_t k = 0; k < n; ++k) {
+        REQUIRE(pins[k].vertex < e->nv, "pin vertex out of range");
+        REQUIRE(!seen[pins[k].vertex], "a vertex is pinned twice");
+        seen[pins[k].vertex] = 1;
+        REQUIRE(finite_n(pins[k].p_BQ, 3), "pin p_BQ not finite");
+    }
+    e->pin.set.assign(pins, pins + n);
+    e->pin.table_dirty = true;
+    e->pin.version += 1;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_set_body_motions(mpm_handle_t e, size_t n, const mpm_body_motion_t* m) try {
+    READY(e);
+    REQUIRE(!multi_rank(e), "pins are not available on a partitioned or multi-rank engine");
+    REQUIRE(n == 0 || m, "null motion array");
+    std::unordered_set<uint32_t> bodies;
+    for (size_t k = 0; k < n; ++k) {
+        REQUIRE(bodies.insert(m[k].body).second, "a body appears twice in one mpm_set_body_motions");
+        REQUIRE(finite_n(m[k].p_WB, 3) && finite_n(m[k].v, 3) && finite_n(m[k].w, 3), "body motion not finite");
+        REQUIRE(is_rotation(m[k].R_WB), "body motion: R_WB is not a rotation");
+    }
+    mpm_engine::PinState& ps = e->pin;
+    std::vector<uint32_t> slot(n);
+    size_t n_slots = ps.motion_body.size();
+    for (size_t k = 0; k < n; ++k) {
+        const auto it = std::find(ps.motion_body.begin(), ps.motion_body.end(), m[k].body);
+        slot[k] = it != ps.motion_body.end() ? (uint32_t)(it - ps.motion_body.begin()) : (uint32_t)n_slots++;
+    }
+    if (n_slots > ps.cap_mot) {   // grow, keeping the clocks of the motions already set
+        const size_t cap = std::max<size_t>(n_slots, std::max<size_t>(16, ps.cap_mot * 2));
+        BodyMotionDev* bigger = nullptr;
+        if (int rc = e->dalloc(&bigger, cap, true)) return rc;
+        if (ps.d_mot)
+            HIP_TRY(hipMemcpyAsync(bigger, ps.d_mot, ps.motion_body.size() * sizeof(BodyMotionDev), hipMemcpyDeviceToDevice, e->stream));
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        e->dfree(ps.d_mot);
+        ps.d_mot = bigger;
+        ps.cap_mot = cap;
+    }
+    for (size_t k = 0; k < n; ++k)
+        if (slot[k] >= ps.motion_body.size()) ps.motion_body.push_back(m[k].body);
+    std::vector<BodyMotionDev> rec(n);
+    for (size_t k = 0; k < n; ++k) {
+        BodyMotionDev& r = rec[k];
+        r = BodyMotionDev{};
+        for (int i = 0; i < 3; ++i) {
+            r.p[i] = m[k].p_WB[i];
+            r.v[i] = m[k].v[i];
+            r.w[i] = m[k].w[i];
+        }
+        for (int i = 0; i < 9; ++i) r.R[i] = m[k].R_WB[i];
+        r.t = 0.0;
+        HIP_TRY(hipMemcpyAsync(ps.d_mot + slot[k], &rec[k], sizeof(BodyMotionDev), hipMemcpyHostToDevice, e->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    ps.table_dirty = true;   // (a pin whose body has just got its first motion is resolved at the next substep)
+    ps.version += 1;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_pins_inside_collider(mpm_handle_t e, const mpm_collider_t* shape, uint32_t body, const float p_WB[3],
+                             const float R_WB[9], size_t* n_added) try {
+    READY(e);
+    REQUIRE(!multi_rank(e), "pins are not available on a partitioned or multi-rank engine");
+    REQUIRE(shape && p_WB && R_WB, "null argument");
+    REQUIRE(finite_n(p_WB, 3), "body pose not finite");
+    REQUIRE(is_rotation(R_WB), "R_WB is not a rotation");
+    if (int rc = validate_colliders(1, shape)) return rc;
+    const size_t nv = e->nv;
+    std::vector<float> x(nv * 3), phi(nv), grad(nv * 3);
+    if (nv) {
+        if (int rc = download_original_vertices(e, x.data())) return rc;
+        if (int rc = collider_signed_distance(e, shape, nv, x.data(), phi.data(), grad.data())) return rc;
+    }
+    mpm_engine::PinState& ps = e->pin;
+    std::vector<uint8_t> pinned(nv, 0);
+    for (const mpm_pin_t& q : ps.set) pinned[q.vertex] = 1;
+    std::vector<mpm_pin_t> add;
+    for (size_t v = 0; v < nv; ++v) {
+        if (!(phi[v] <= 0.f) || pinned[v]) continue;
+        mpm_pin_t q{(uint32_t)v, body, {0.f, 0.f, 0.f}};
+        const double d[3] = {(double)x[v * 3] - p_WB[0], (double)x[v * 3 + 1] - p_WB[1], (double)x[v * 3 + 2] - p_WB[2]};
+        for (int i = 0; i < 3; ++i)
+            q.p_BQ[i] = (float)((double)R_WB[i] * d[0] + (double)R_WB[3 + i] * d[1] + (double)R_WB[6 + i] * d[2]);
+        add.push_back(q);
+    }
+    if (n_added) *n_added = 0;
+    REQUIRE(!add.empty(), "no vertex that is not pinned already lies inside the shape");
+    ps.set.insert(ps.set.end(), add.begin(), add.end());
+    ps.table_dirty = true;
+    ps.version += 1;
+    if (n_added) *n_added = add.size();
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_get_pins(mpm_handle_t e, mpm_pin_t* out, size_t capacity, size_t* n_out) try {
+    READY(e);
+    REQUIRE(out || capacity == 0, "null output");
+    const std::vector<mpm_pin_t>& set = e->pin.set;
+    std::copy(set.begin(), set.begin() + std::min(capacity, set.size()), out);
+    if (n_out) *n_out = set.size();
+    return 0;
+} MPM_CATCH_ALL

@@ -16,6 +16,7 @@
 #include "mpm_rebuild.h"
 #include "mpm_step.h"
 #include "mpm_contact_dev.h"
+#include "mpm_pins.h"
 #include "mpm_team.h"
 #include "mpm_trace.h"
 
@@ -185,6 +186,21 @@ struct mpm_engine {
     // analytic colliders of the grid update selected by mpm_bc = MPM_BC_TABLE (mpm_set_grid_colliders)
     GridColliders grid_colliders{};
     uint64_t grid_colliders_version = 0;
+    // fixed constraints (mpm_set_pins, mpm_set_body_motions; k_pin in mpm_pins.h)
+    struct PinState {
+        std::vector<mpm_pin_t> set;              // the caller's pins, in order
+        std::vector<uint32_t> motion_body;       // body of every motion slot (slots are never given back)
+        PinDev* d_pins = nullptr;
+        size_t cap_pins = 0;
+        BodyMotionDev* d_mot = nullptr;          // [slot] pose, velocity and clock
+        size_t cap_mot = 0;
+        unsigned* d_ticket = nullptr;
+        bool table_dirty = false;                // d_pins is not `set` yet (resolved at the next substep entry point)
+        uint64_t version = 0;                    // every change (captured graphs carry the launch arguments)
+    } pin;
+    uint64_t step_graph_pinv = 0;
+    long long* step_graph_acc = nullptr;
+    size_t step_graph_nb = 0;
     int step_graph_len = 1;
     hipStream_t step_graph_stream = nullptr;
     // the two halves of the multi-GPU substep as replayable graphs (host enqueue time matters there)

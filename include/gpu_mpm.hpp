@@ -129,6 +129,27 @@ struct GpuMpmState {
                                                   reinterpret_cast<float*>(h_external_forces_.F_Bq_W_f.data())));
     }
     uint32_t grid_touched_cnt_host() const { uint32_t c = 0; mpm_check(mpm_grid_touched_cnt(h_, &c)); return c; }
+    // Extension: DeformableModel::AddFixedConstraint (deformable_model.h:227-230) for the cloth.  Pins every vertex inside
+    // shape G (an analytic collider posed in the world) to body `body`, whose pose is X_WB = (p_WB, R_WB row-major);
+    // returns the number of pins added (none: throws, as Drake does).  See mpm_pins_inside_collider.
+    size_t AddFixedConstraint(uint32_t body, const mpm_collider_t& shape_G, const Vec3<T>& p_WB, const std::array<T, 9>& R_WB) {
+        size_t n = 0;
+        mpm_check(mpm_pins_inside_collider(h_, &shape_G, body, p_WB.data(), R_WB.data(), &n));
+        return n;
+    }
+    // the poses of the pinned bodies at the start of the plant step and their spatial velocities (CalcAbstractStates):
+    // once per step, before its substeps.  See mpm_set_body_motions.
+    void SetBodyMotions(const std::vector<mpm_body_motion_t>& motions) {
+        mpm_check(mpm_set_body_motions(h_, motions.size(), motions.data()));
+    }
+    void SetPins(const std::vector<mpm_pin_t>& pins) { mpm_check(mpm_set_pins(h_, pins.size(), pins.data())); }
+    std::vector<mpm_pin_t> GetPins() const {
+        size_t n = 0;
+        mpm_check(mpm_get_pins(h_, nullptr, 0, &n));
+        std::vector<mpm_pin_t> out(n);
+        mpm_check(mpm_get_pins(h_, out.data(), n, &n));
+        return out;
+    }
     std::vector<Vec3<T>>& positions_host() { return h_positions_; }
     const std::vector<Vec3<T>>& positions_host() const { return h_positions_; }
     ExternalSpatialForce<T>& external_forces_host() { return h_external_forces_; }

@@ -537,6 +537,60 @@ MPM_API int mpm_run_coupled_substeps(mpm_handle_t h, int n, const mpm_coupled_pa
 MPM_API int mpm_world_coupled_substeps(mpm_handle_t *handles, int n_local, int n, const mpm_coupled_params_t *params,
                                        size_t n_colliders, const mpm_collider_t *colliders, mpm_coupled_result_t *const *results);
 
+/* ---- Fixed constraints: cloth vertices pinned to rigid bodies (an extension) ----
+ * DeformableModel::AddFixedConstraint (deformable_model.h:227-230) for the MPM cloth.
+ * A pin is (vertex, body, p_BQ): `vertex` indexes the vertex numbering of mpm_add_qr_cloth / mpm_dump_cpu_state (global
+ * over all cloths in call order; particle id n_faces + vertex), p_BQ is the attachment point in the body frame.
+ * A body motion is set per body: the pose (p_WB, R_WB row-major, body -> world) at the start of the next substep and a
+ * constant spatial velocity (v, w), world frame.  Setting it restarts that body's clock: t = 0.
+ * At the end of every GridToParticle that runs -- mpm_grid_to_particle, mpm_substep, mpm_run_substeps (owed substeps
+ * included), mpm_run_coupled_substeps and the contact-free substeps it enqueues behind a watch -- the clock first advances
+ * by the substep's dt (after the k-th substep t = sum of the dt), then every pinned vertex gets, with p(t) = p_WB + t v and
+ * R(t) = Rodrigues(t w) R_WB:
+ *   x = p(t) + R(t) p_BQ;   v_Q = v + w x (x - p(t));   C = [w]x  (the exact velocity gradient of the rigid motion;
+ *   GridToParticle's RPIC blend maps a skew C to itself).
+ * A substep that skips itself (it is run again later) neither moves a pin nor advances a clock.
+ * Reaction: with m the particle's ParticleToGrid mass and v_g2p the velocity GridToParticle wrote for it, the constraint
+ * gives the cloth the impulse m (v_Q - v_g2p); body `body` receives force impulse l = m (v_g2p - v_Q) and torque
+ * (x - p_WB) x l about the p_WB of its motion, in the accumulators of the contact impulses (64-bit fixed point: the sums
+ * do not depend on the order) read by mpm_external_body_force_to_host and mpm_finalize_external_contact_forces.  A pin
+ * whose body is >= the mpm_reallocate_external_bodies count moves its vertex and adds no impulse.
+ * Pinned vertices still take part in CalcFemStateAndForce, ParticleToGrid and contact-pair generation like any other
+ * vertex: a selection shape that is also a collision geometry of the same body produces contacts with the pinned
+ * vertices.  A target that leaves its block's tile asks for a re-sort as an advected particle does; one outside the grid
+ * is reported as MPM_ERR_DOMAIN.
+ * Refused with MPM_ERR_INVALID before anything is enqueued, the state untouched: a call before mpm_finalize, a vertex
+ * >= n_verts, a vertex twice in one mpm_set_pins, a non-finite p_BQ, pose or velocity, an R_WB that is not a rotation
+ * (|R^T R - I| and |det R - 1| within 1e-4), a body twice in one mpm_set_body_motions, and any partitioned or multi-rank
+ * engine (mpm_dist_init, mpm_chain_*, mpm_team_*: out of scope) -- the pin calls on such an engine, and mpm_dist_init,
+ * the halo, chain and team substeps on an engine with pins.  A substep entry point called while some pin's body has no
+ * motion is refused the same way.  With no pins nothing is launched.  Stream-ordered: substeps enqueued after a call see
+ * its pins and motions. */
+typedef struct mpm_pin {
+    uint32_t vertex;
+    uint32_t body;
+    float p_BQ[3];
+} mpm_pin_t;
+typedef struct mpm_body_motion {
+    uint32_t body;
+    float p_WB[3];
+    float R_WB[9];
+    float v[3], w[3];
+} mpm_body_motion_t;
+/* Replaces the pin set (n = 0 clears it; pins may then be NULL). */
+MPM_API int mpm_set_pins(mpm_handle_t h, size_t n, const mpm_pin_t *pins);
+/* Sets the motion of n bodies (once per plant step: the body poses of CalcAbstractStates). */
+MPM_API int mpm_set_body_motions(mpm_handle_t h, size_t n, const mpm_body_motion_t *motions);
+/* AddFixedConstraint's selection: every vertex whose current position has phi <= 0 for the analytic shape (kinds 0-5;
+ * phi by the function of mpm_collider_signed_distance, the shape posed by its own p_WB / R_WB) is pinned to `body`
+ * with p_BQ = R_WB^T (x - p_WB) for the body pose given here.  The new pins are appended to the set; a vertex already
+ * pinned keeps its pin and is not counted.  *n_added (may be NULL): the pins added.  No new vertex inside:
+ * MPM_ERR_INVALID, nothing added.  A synchronisation point. */
+MPM_API int mpm_pins_inside_collider(mpm_handle_t h, const mpm_collider_t *shape, uint32_t body, const float p_WB[3],
+                                     const float R_WB[9], size_t *n_added);
+/* The pin set in order: min(n, capacity) pins into out (may be NULL when capacity is 0), n into *n_out. */
+MPM_API int mpm_get_pins(mpm_handle_t h, mpm_pin_t *out, size_t capacity, size_t *n_out);
+
 /* Runs n substeps with HIP events around every kernel group on the engine's
  * stream and returns the mean milliseconds per substep of each phase
  * (phase_ms[MPM_PHASE_COUNT]) and of the whole substep. */
