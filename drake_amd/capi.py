@@ -118,6 +118,21 @@ class Material(C.Structure):
     ]
 
 
+class ClothMaterial(C.Structure):
+    """mpm_cloth_material_t: the per-cloth fields of mpm_material_t (mpm_add_qr_cloth_with_material); V, gravity, epsv,
+    sdf_friction and the wall cells stay the engine's."""
+    _fields_ = [("youngs_modulus", C.c_float), ("poisson_ratio", C.c_float), ("density", C.c_float), ("gamma", C.c_float),
+                ("K", C.c_float), ("c_F", C.c_float)]
+
+    @staticmethod
+    def of(material: "Material") -> "ClothMaterial":
+        """the per-cloth fields of an engine material"""
+        return ClothMaterial(*[getattr(material, f) for f, _ in ClothMaterial._fields_])
+
+    def as_dict(self) -> dict:
+        return {f: float(getattr(self, f)) for f, _ in self._fields_}
+
+
 class ContactStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("line_search_evals", C.c_int32), ("contacts", C.c_uint32),
                 ("nodes", C.c_uint32), ("residual", C.c_float), ("alpha", C.c_float), ("energy", C.c_float),
@@ -160,6 +175,7 @@ class ARR:
     POSITIONS, VELOCITIES, VOLUMES, AFFINE, PIDS, INDEX_MAPPINGS, SORT_KEYS, FORCES, TAUS = range(9)
     DEFORMATION_GRADIENTS, DM_INVERSES, INDICES, GRID_MASSES, GRID_MOMENTUM, GRID_V_STAR = range(9, 15)
     GRID_TOUCHED_FLAGS, GRID_TOUCHED_IDS, CONTACT_VEL, CONTACT_VEL0, GRID_DIR = range(15, 20)
+    MASSES = 20
 
 
 PHASES = ("rebuild", "fem", "vforce", "p2g", "grid", "g2p")
@@ -188,6 +204,7 @@ SYMBOLS = [
     "mpm_debug_contact_counters", "mpm_run_coupled_substeps", "mpm_chain_direct_prepare", "mpm_chain_direct_connect",
     "mpm_debug_contact_count", "mpm_chain_direct_base", "mpm_chain_direct_connect_local", "mpm_team_prepare", "mpm_team_connect",
     "mpm_world_coupled_substeps", "mpm_set_pins", "mpm_set_body_motions", "mpm_pins_inside_collider", "mpm_get_pins",
+    "mpm_add_qr_cloth_with_material", "mpm_get_cloth_info", "mpm_cloth_count",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -302,6 +319,9 @@ def load_library(build: bool = True):
         "mpm_set_body_motions": [vp, sz, vp],
         "mpm_pins_inside_collider": [vp, vp, C.c_uint32, vp, vp, P(sz)],
         "mpm_get_pins": [vp, vp, sz, P(sz)],
+        "mpm_add_qr_cloth_with_material": [vp, vp, vp, sz, vp, sz, vp],
+        "mpm_get_cloth_info": [vp, sz, P(sz), P(sz), P(sz), P(sz), vp],
+        "mpm_cloth_count": [vp, P(sz)],
         "mpm_get_fast_math": [vp, P(i)],
         "mpm_substep_begin_halo": [vp, f, i, P(C.c_int), P(C.c_int), P(C.c_int), P(C.c_void_p), sz],
         "mpm_substep_end_halo": [vp, f, i, i, P(C.c_void_p), sz],
@@ -445,11 +465,29 @@ class GpuMpm:
         return m
 
     # ---- GpuMpmState --------------------------------------------------------
-    def add_qr_cloth(self, pos, vel, indices):
+    def add_qr_cloth(self, pos, vel, indices, material: ClothMaterial | None = None):
+        """AddQRCloth; `material` (a ClothMaterial): the cloth's own material, mpm_add_qr_cloth_with_material (the
+        engine becomes multi-material)"""
         pos = _f32(pos, (-1, 3))
         vel = _f32(vel, (-1, 3))
         idx = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1)
-        self._ck(self.lib.mpm_add_qr_cloth(self.h, _ptr(pos), _ptr(vel), pos.shape[0], _ptr(idx), idx.size // 3))
+        if material is None:
+            self._ck(self.lib.mpm_add_qr_cloth(self.h, _ptr(pos), _ptr(vel), pos.shape[0], _ptr(idx), idx.size // 3))
+        else:
+            self._ck(self.lib.mpm_add_qr_cloth_with_material(self.h, _ptr(pos), _ptr(vel), pos.shape[0], _ptr(idx),
+                                                             idx.size // 3, C.byref(material)))
+
+    def cloth_count(self) -> int:
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_cloth_count(self.h, C.byref(n)))
+        return int(n.value)
+
+    def cloth_info(self, cloth: int) -> dict:
+        """mpm_get_cloth_info: first_vertex, n_verts, first_face, n_faces and material (a ClothMaterial)"""
+        r = [C.c_size_t() for _ in range(4)]
+        m = ClothMaterial()
+        self._ck(self.lib.mpm_get_cloth_info(self.h, int(cloth), *[C.byref(x) for x in r], C.byref(m)))
+        return dict(first_vertex=r[0].value, n_verts=r[1].value, first_face=r[2].value, n_faces=r[3].value, material=m)
 
     def finalize(self):
         self._ck(self.lib.mpm_finalize(self.h))
@@ -997,7 +1035,7 @@ class GpuMpm:
         ARR.GRID_MOMENTUM: ("cells", 3, np.float32), ARR.GRID_V_STAR: ("cells", 3, np.float32),
         ARR.GRID_TOUCHED_FLAGS: ("blocks", 1, np.uint32), ARR.GRID_TOUCHED_IDS: ("blocks", 1, np.uint32),
         ARR.CONTACT_VEL: ("nk", 3, np.float32), ARR.CONTACT_VEL0: ("nk", 3, np.float32),
-        ARR.GRID_DIR: ("cells", 3, np.float32),
+        ARR.GRID_DIR: ("cells", 3, np.float32), ARR.MASSES: ("np", 1, np.float32),
     }
 
     def download(self, which: int) -> np.ndarray:

@@ -87,20 +87,71 @@ int mpm_create(int domain_bits, const mpm_material_t* material, int device, mpm_
     return 0;
 } MPM_CATCH_ALL
 
-int mpm_add_qr_cloth(mpm_handle_t e, const float* pos, const float* vel, size_t n_verts, const int32_t* indices,
-                     size_t n_faces) try {
+// (m: the cloth's own material, or null for the engine's; checked by the caller.  Nothing is recorded on a refusal.)
+static int add_cloth(mpm_engine* e, const float* pos, const float* vel, size_t n_verts, const int32_t* indices,
+                     size_t n_faces, const mpm_cloth_material_t* m) {
     REQUIRE(e, "null handle");
     REQUIRE(!e->finalized, "AddQRCloth after Finalize");
     REQUIRE(pos && vel && (indices || n_faces == 0), "null input array");
-    for (size_t i = 0; i < n_faces * 3; ++i) {
+    for (size_t i = 0; i < n_faces * 3; ++i)
         REQUIRE(indices[i] >= 0 && (size_t)indices[i] < n_verts, "triangle index out of range");
-        e->h_idx.push_back(indices[i] + (int)e->nv);
-    }
+    REQUIRE(!(e->multi_mat || m) || e->cloths.size() < MAX_CLOTH_MATERIALS,
+            "more than 256 cloths in a multi-material engine (mpm_add_qr_cloth_with_material)");
+    mpm_engine::Cloth c{e->nv, n_verts, e->nf, n_faces, {}};
+    const mpm_material_t& em = e->mat;
+    c.m = m ? *m : mpm_cloth_material_t{em.youngs_modulus, em.poisson_ratio, em.density, em.gamma, em.K, em.c_F};
+    e->cloths.push_back(c);
+    if (m) e->multi_mat = true;
+    for (size_t i = 0; i < n_faces * 3; ++i) e->h_idx.push_back(indices[i] + (int)e->nv);
     e->h_pos.insert(e->h_pos.end(), pos, pos + 3 * n_verts);
     e->h_vel.insert(e->h_vel.end(), vel, vel + 3 * n_verts);
     e->nv += n_verts;
     e->nf += n_faces;
     e->np = e->nv + e->nf;
+    return 0;
+}
+
+int mpm_add_qr_cloth(mpm_handle_t e, const float* pos, const float* vel, size_t n_verts, const int32_t* indices,
+                     size_t n_faces) try {
+    return add_cloth(e, pos, vel, n_verts, indices, n_faces, nullptr);
+} MPM_CATCH_ALL
+
+int mpm_add_qr_cloth_with_material(mpm_handle_t e, const float* pos, const float* vel, size_t n_verts,
+                                   const int32_t* indices, size_t n_faces, const mpm_cloth_material_t* m) try {
+    REQUIRE(e, "null handle");
+    mpm_cloth_material_t c;
+    if (m) {
+        c = *m;
+    } else {
+        const mpm_material_t& em = e->mat;
+        c = mpm_cloth_material_t{em.youngs_modulus, em.poisson_ratio, em.density, em.gamma, em.K, em.c_F};
+    }
+    REQUIRE(std::isfinite(c.youngs_modulus) && std::isfinite(c.poisson_ratio) && std::isfinite(c.density) &&
+                std::isfinite(c.gamma) && std::isfinite(c.K) && std::isfinite(c.c_F),
+            "cloth material: a field is not finite");
+    REQUIRE(c.youngs_modulus > 0.f, "cloth material: youngs_modulus must be > 0");
+    REQUIRE(c.poisson_ratio >= 0.f && c.poisson_ratio < .5f, "cloth material: poisson_ratio must be in [0, 0.5)");
+    REQUIRE(c.density > 0.f, "cloth material: density must be > 0");
+    REQUIRE(c.gamma >= 0.f && c.K >= 0.f && c.c_F >= 0.f, "cloth material: gamma, K and c_F must be >= 0");
+    return add_cloth(e, pos, vel, n_verts, indices, n_faces, &c);
+} MPM_CATCH_ALL
+
+int mpm_cloth_count(mpm_handle_t e, size_t* n_out) try {
+    REQUIRE(e && n_out, "null argument");
+    *n_out = e->cloths.size();
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_get_cloth_info(mpm_handle_t e, size_t cloth, size_t* first_vertex, size_t* n_verts, size_t* first_face,
+                       size_t* n_faces, mpm_cloth_material_t* m) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(cloth < e->cloths.size(), "cloth index out of range");
+    const mpm_engine::Cloth& c = e->cloths[cloth];
+    if (first_vertex) *first_vertex = c.first_vertex;
+    if (n_verts) *n_verts = c.n_verts;
+    if (first_face) *first_face = c.first_face;
+    if (n_faces) *n_faces = c.n_faces;
+    if (m) *m = c.m;
     return 0;
 } MPM_CATCH_ALL
 
@@ -179,8 +230,15 @@ static void drop_step_graph(mpm_engine* e) {
 static void launch_fem_faces(mpm_engine* e, float dt) {
     TraceRange tr("mpm:CalcFemStateAndForce (faces)");
     if (!e->nf) return;
-    if (e->fast_math) hipLaunchKernelGGL(k_fem<1>, dim3((e->g_nf + 7u) & ~7u), dim3(256), 0, e->stream, e->dp, dt);
-    else hipLaunchKernelGGL(k_fem<0>, dim3((e->g_nf + 7u) & ~7u), dim3(256), 0, e->stream, e->dp, dt);
+    const dim3 g((e->g_nf + 7u) & ~7u), b(256);
+    if (e->multi_mat) {   // (per-cloth materials, mpm_add_qr_cloth_with_material)
+        const ClothMat* t = e->d_cloth_mat;
+        if (e->fast_math) hipLaunchKernelGGL(k_fem_mat<1>, g, b, 0, e->stream, e->dp, dt, t);
+        else hipLaunchKernelGGL(k_fem_mat<0>, g, b, 0, e->stream, e->dp, dt, t);
+        return;
+    }
+    if (e->fast_math) hipLaunchKernelGGL(k_fem<1>, g, b, 0, e->stream, e->dp, dt);
+    else hipLaunchKernelGGL(k_fem<0>, g, b, 0, e->stream, e->dp, dt);
 }
 static void launch_fem_vertices(mpm_engine* e) {
     TraceRange tr("mpm:CalcFemStateAndForce (vertex forces)");
@@ -230,7 +288,7 @@ static void launch_pins(mpm_engine* e, const DP& p, float dt) {
     const unsigned groups = (unsigned)std::min<size_t>((ps.set.size() + 255) / 256, 1024);
     hipLaunchKernelGGL(k_pin, dim3(groups), dim3(256), 0, e->stream, p, a, dt);
 }
-// (`p` may carry a halo class restriction: only an engine without pins splits GridToParticle, see pins_refused)
+// (`p` may carry a halo class restriction: only an engine without pins splits GridToParticle, see extensions_refused)
 static void launch_g2p_with(mpm_engine* e, DP p, float dt) {
     TraceRange tr("mpm:GridToParticle");
     hipLaunchKernelGGL(k_g2p, dim3(std::min(768u, p.capI) * G2P_SPLIT), dim3(G2P_THREADS), 0, e->stream, p, dt);
@@ -275,6 +333,28 @@ static int set_fixed_point_scales(mpm_engine* e) {
     return 0;
 }
 
+// A multi-material engine at Finalize, after the volumes are in place: k_fem_mat's table (the Lame parameters formed as
+// for the engine's material) and every particle's q[0].w scaled to its mass.  cloth_of_pid: [original id] cloth.
+static int init_cloth_materials(mpm_engine* e, const std::vector<uint8_t>& cloth_of_pid) {
+    std::vector<ClothMat> t(e->cloths.size());
+    for (size_t c = 0; c < t.size(); ++c) {
+        const mpm_cloth_material_t& m = e->cloths[c].m;
+        t[c] = ClothMat{m.youngs_modulus / (2.f * (1.f + m.poisson_ratio)),
+                        m.youngs_modulus * m.poisson_ratio / ((1.f + m.poisson_ratio) * (1.f - 2.f * m.poisson_ratio)),
+                        m.gamma, m.K, m.c_F, m.density, 0.f, 0.f};
+    }
+    if (int rc = e->dalloc(&e->d_cloth_mat, t.size(), false)) return rc;
+    H2D(e, e->d_cloth_mat, t.data(), t.size() * sizeof(ClothMat));
+    uint8_t* d_cloth = nullptr;
+    if (int rc = e->dalloc(&d_cloth, e->np, false)) return rc;
+    H2D(e, d_cloth, cloth_of_pid.data(), e->np);
+    hipLaunchKernelGGL(k_init_masses, dim3(e->g_np), dim3(256), 0, e->stream, e->dp, (const ClothMat*)e->d_cloth_mat,
+                       (const uint8_t*)d_cloth);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->dfree(d_cloth);
+    return 0;
+}
+
 int mpm_finalize(mpm_handle_t e) try {
     REQUIRE(e, "null handle");
     REQUIRE(!e->finalized, "Finalize called twice");
@@ -310,6 +390,9 @@ int mpm_finalize(mpm_handle_t e) try {
     p.M.mu = m.youngs_modulus / (2.f * (1.f + m.poisson_ratio));
     p.M.lambda = m.youngs_modulus * m.poisson_ratio / ((1.f + m.poisson_ratio) * (1.f - 2.f * m.poisson_ratio));
     p.M.density = m.density; p.M.gamma = m.gamma; p.M.K = m.K; p.M.V = m.V; p.M.cF = m.c_F;
+    // a multi-material engine stores each particle's mass in q[0].w (k_init_masses below, k_fem_mat for the faces):
+    // every reader that multiplies q[0].w by DP::M.density then gets it unchanged
+    if (e->multi_mat) p.M.density = 1.f;
     p.M.sdf_friction = m.sdf_friction; p.M.gravity = m.gravity; p.M.epsv = m.epsv;
     p.M.gravity_axis = m.gravity_axis; p.M.wall = m.wall_cells;
 
@@ -419,6 +502,24 @@ int mpm_finalize(mpm_handle_t e) try {
     std::vector<int> f3(nf * 4, 0);
     for (size_t f = 0; f < nf; ++f)
         for (int d = 0; d < 3; ++d) f3[f * 4 + 1 + d] = e->h_idx[f * 3 + d] + (int)nf;
+    // a multi-material engine: the face's cloth above the corners' ranks (k_fem_mat; re-sorts move the word whole)
+    std::vector<uint8_t> cloth_of_pid;
+    if (e->multi_mat) {
+        cloth_of_pid.resize(np);
+        e->h_rho_of_pid.resize(np);
+        for (size_t c = 0; c < e->cloths.size(); ++c) {
+            const mpm_engine::Cloth& cl = e->cloths[c];
+            for (size_t f = cl.first_face; f < cl.first_face + cl.n_faces; ++f) {
+                f3[f * 4] = (int)(c << FACE_CLOTH_SHIFT);
+                cloth_of_pid[f] = (uint8_t)c;
+                e->h_rho_of_pid[f] = cl.m.density;
+            }
+            for (size_t v = cl.first_vertex; v < cl.first_vertex + cl.n_verts; ++v) {
+                cloth_of_pid[nf + v] = (uint8_t)c;
+                e->h_rho_of_pid[nf + v] = cl.m.density;
+            }
+        }
+    }
     // vertex -> (face, corner) adjacency, ascending face id
     std::vector<int> off(nv + 1, 0), fc(3 * nf);
     for (size_t k = 0; k < 3 * nf; ++k) off[e->h_idx[k] + 1]++;
@@ -454,6 +555,8 @@ int mpm_finalize(mpm_handle_t e) try {
     if (nf) hipLaunchKernelGGL(k_init_faces, dim3(e->g_nf), dim3(256), 0, e->stream, p);
     if (nv) hipLaunchKernelGGL(k_init_vertex_adjacency, dim3(e->g_nv), dim3(256), 0, e->stream, p);
     if (nv) hipLaunchKernelGGL(k_init_vertex_volumes, dim3(e->g_nv), dim3(256), 0, e->stream, p);
+    if (e->multi_mat)
+        if (int rc2 = init_cloth_materials(e, cloth_of_pid)) return rc2;
     if (int rc2 = set_fixed_point_scales(e)) return rc2;
     Ctl c0{};
     c0.cur = 0;
@@ -686,9 +789,11 @@ static int pins_ready(mpm_engine* e) {
     ps.table_dirty = false;
     return 0;
 }
-// partitioned and multi-rank engines have no pins (out of scope)
-static int pins_refused(const mpm_engine* e, const char* what) {
+// partitioned and multi-rank engines have no pins and no per-cloth materials (out of scope)
+static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
+    if (e->multi_mat)
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on a multi-material engine (mpm_add_qr_cloth_with_material)");
     return 0;
 }
 
@@ -1044,7 +1149,7 @@ int mpm_substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, co
 static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
                               void* const* send_bufs, size_t cap, uint32_t* const* counters) {
     READY(e);
-    if (int rc = pins_refused(e, "halo substeps")) return rc;
+    if (int rc = extensions_refused(e, "halo substeps")) return rc;
     may_resort(e, dt);
     REQUIRE(n >= 0 && n <= 2 && (n == 0 || (bx_lo && bx_hi && shift_bx && send_bufs)), "bad halo zone list");
     REQUIRE(n == 0 || (cap > 0 && cap < (1u << 24)), "bad halo buffer");
@@ -1091,7 +1196,7 @@ static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo,
 // neighbours' sums, to be overlapped with the exchange.  Zones = the ranges given to begin.
 int mpm_substep_mid_halo(mpm_handle_t e, float dt, int bc) try {
     READY(e);
-    if (int rc = pins_refused(e, "halo substeps")) return rc;
+    if (int rc = extensions_refused(e, "halo substeps")) return rc;
     REQUIRE(e->grid_state == 3 && !e->halo_mid_done, "mpm_substep_mid_halo needs mpm_substep_begin_halo first");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
@@ -1112,7 +1217,7 @@ int mpm_substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* co
 // with_g2p = false: the grid update only -- a coupled substep puts the contact solve between it and GridToParticle
 static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p) {
     READY(e);
-    if (int rc = pins_refused(e, "halo substeps")) return rc;
+    if (int rc = extensions_refused(e, "halo substeps")) return rc;
     REQUIRE(n >= 0 && n <= 2 && (n == 0 || recv_bufs), "bad halo buffer list");
     REQUIRE(e->grid_state == 3, "mpm_substep_end_halo without mpm_substep_begin_halo");
     GridColliders gc;
@@ -1202,6 +1307,7 @@ int mpm_chain_destroy(mpm_handle_t e) try {
 
 int mpm_chain_enable_migration(mpm_handle_t e, int every, size_t capacity_particles) try {
     READY(e);
+    if (int rc = extensions_refused(e, "mpm_chain_enable_migration")) return rc;
     mpm_engine::Chain& c = e->chain;
     REQUIRE(c.comm, "mpm_chain_init first");
     REQUIRE(e->dp.dist.on, "mpm_dist_init first");
@@ -1230,7 +1336,7 @@ int mpm_chain_enable_migration(mpm_handle_t e, int every, size_t capacity_partic
 int mpm_chain_init(mpm_handle_t e, const char id[128], int rank, int world, int cut_lo_block, int cut_hi_block,
                    int pitch_blocks, int zone_blocks, size_t capacity_blocks, int periodic) try {
     READY(e);
-    if (int rc = pins_refused(e, "mpm_chain_init")) return rc;
+    if (int rc = extensions_refused(e, "mpm_chain_init")) return rc;
     REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank / world");
     REQUIRE(zone_blocks >= 1 && capacity_blocks > 0 && capacity_blocks < (1u << 24), "bad halo geometry");
     // (id == NULL: the geometry only, no RCCL communicator -- for the direct transport, mpm_chain_direct_prepare)
@@ -1270,7 +1376,7 @@ static uint32_t* direct_flag(const mpm_engine::Chain& c, void* base, int side) {
 
 int mpm_chain_direct_prepare(mpm_handle_t e, char handle_out[64]) try {
     READY(e);
-    if (int rc = pins_refused(e, "mpm_chain_direct_prepare")) return rc;
+    if (int rc = extensions_refused(e, "mpm_chain_direct_prepare")) return rc;
     mpm_engine::Chain& c = e->chain;
     REQUIRE(handle_out, "null argument");
     REQUIRE(c.cap > 0, "mpm_chain_init first (with a NULL id for the geometry alone)");
@@ -1380,6 +1486,7 @@ int mpm_chain_direct_connect_local(mpm_handle_t e, void* left_base, void* right_
 // ---- TEAM transport of the distributed contact solve (mpm_team.h) --------------------------------------------------------
 int mpm_team_prepare(mpm_handle_t e, size_t zone_capacity_blocks, char handle_out[64], void** base_out) try {
     READY(e);
+    if (int rc = extensions_refused(e, "mpm_team_prepare")) return rc;
     REQUIRE(e->dp.dist.on, "mpm_dist_init first");
     REQUIRE(e->dp.dist.world <= TEAM_MAX, "the team transport serves the ranks of one node (at most 8)");
     REQUIRE(zone_capacity_blocks > 0 && zone_capacity_blocks < (1u << 20), "bad zone capacity");
@@ -1421,6 +1528,7 @@ int mpm_team_prepare(mpm_handle_t e, size_t zone_capacity_blocks, char handle_ou
 // a rank of this process is named by its region's pointer (mpm_team_prepare's base_out), every other one by its handle
 int mpm_team_connect(mpm_handle_t e, const char* handles, void* const* local_bases) try {
     READY(e);
+    if (int rc = extensions_refused(e, "mpm_team_connect")) return rc;
     mpm_engine::Team& t = e->team;
     REQUIRE(t.base, "mpm_team_prepare first");
     for (int r = 0; r < t.world; ++r) {
@@ -1517,7 +1625,7 @@ static int chain_direct_end(mpm_engine* e, float dt, int bc, bool with_g2p) {
 
 int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     READY(e);
-    if (int rc = pins_refused(e, "mpm_chain_substeps")) return rc;
+    if (int rc = extensions_refused(e, "mpm_chain_substeps")) return rc;
     mpm_engine::Chain& c = e->chain;
     REQUIRE(c.comm || c.direct, "mpm_chain_init first");
     const rccl_rt::Api* a = c.comm ? rccl_rt::api() : nullptr;
@@ -2110,7 +2218,7 @@ static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) 
 
 int mpm_dist_init(mpm_handle_t e, const mpm_dist_config_t* cfg) try {
     READY(e);
-    if (int rc = pins_refused(e, "mpm_dist_init")) return rc;
+    if (int rc = extensions_refused(e, "mpm_dist_init")) return rc;
     REQUIRE(cfg, "null configuration");
     REQUIRE(!e->dp.dist.on, "mpm_dist_init called twice");
     REQUIRE(e->api_identity, "mpm_dist_init must precede RebuildMapping(sort = true)");
@@ -2665,7 +2773,7 @@ static int team_coupled_substeps(const std::vector<mpm_engine*>& L, int n, const
                                  const mpm_collider_t* colliders, mpm_coupled_result_t* const* results) {
     const float dt = prm->dt;
     for (mpm_engine* e : L) {
-        if (int rc = pins_refused(e, "team coupled substeps")) return rc;
+        if (int rc = extensions_refused(e, "team coupled substeps")) return rc;
         REQUIRE(e->dp.dist.on && e->team.on && e->chain.direct,
                 "coupled substeps on a partitioned domain need the direct halo (mpm_chain_direct_connect) and the team transport (mpm_team_connect)");
         REQUIRE(e->chain.pitch == 0, "coupled substeps: a partitioned domain has pitch 0");

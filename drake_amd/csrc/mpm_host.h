@@ -79,6 +79,8 @@ static int exception_to_status() noexcept {
         if (!(cond)) return fail(MPM_ERR_INVALID, (msg));    \
     } while (0)
 
+constexpr size_t MAX_CLOTH_MATERIALS = 256;
+
 struct mpm_engine {
     std::atomic<int> pins{0};   // mpm_device_synchronize of another thread is working on this engine (mpm_destroy waits)
     int device = 0;
@@ -90,6 +92,16 @@ struct mpm_engine {
     std::vector<float> h_pos, h_vel;
     std::vector<int> h_idx;  // vertex ids local to the vertex array
     size_t nv = 0, nf = 0, np = 0;
+    // every cloth in call order, and the per-cloth materials (mpm_add_qr_cloth_with_material: at most
+    // MAX_CLOTH_MATERIALS cloths; a face's cloth rides in fq[3].x, see FACE_CLOTH_SHIFT)
+    struct Cloth {
+        size_t first_vertex, n_verts, first_face, n_faces;
+        mpm_cloth_material_t m;
+    };
+    std::vector<Cloth> cloths;
+    bool multi_mat = false;             // some cloth came with a material of its own: k_fem_mat, q[0].w holds the mass
+    ClothMat* d_cloth_mat = nullptr;    // [cloth] k_fem_mat's table (multi-material engines)
+    std::vector<float> h_rho_of_pid;    // [original particle id] the density of its cloth (multi-material engines)
     DP dp{};
     std::vector<void*> allocs;
     std::vector<size_t> alloc_bytes;   // (parallel to allocs)

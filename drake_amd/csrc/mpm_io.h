@@ -61,8 +61,18 @@ __global__ __launch_bounds__(256) void k_init_vertex_volumes(DP p) {
     p.set[0].q[0][p.Nf + k].w = v;
 }
 
+// a multi-material engine: every particle's q[0].w becomes its mass, volume x the density of its cloth (rounded as
+// ParticleToGrid rounds vol * density); slot == original id before the first sort, `cloth` indexed by it
+__global__ __launch_bounds__(256) void k_init_masses(DP p, const ClothMat* mats, const uint8_t* cloth) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= p.Np) return;
+    float4& q = p.set[0].q[0][i];
+    q.w = q.w * mats[cloth[i]].rho;
+}
+
 // ---- slot-order views -------------------------------------------------------
-enum Field { F_POS, F_VEL, F_VOL, F_AFFINE, F_FORCE, F_DEFGRAD, F_DMINV };
+// (F_MASS: q[0].w alone -- the mass of a multi-material engine; a face's static volume fq[2].w is F_VOL's to write)
+enum Field { F_POS, F_VEL, F_VOL, F_AFFINE, F_FORCE, F_DEFGRAD, F_DMINV, F_MASS };
 
 template <int FIELD>
 struct FieldInfo;
@@ -73,6 +83,7 @@ template <> struct FieldInfo<F_AFFINE> { static constexpr int N = 9; };
 template <> struct FieldInfo<F_FORCE> { static constexpr int N = 3; };
 template <> struct FieldInfo<F_DEFGRAD> { static constexpr int N = 9; };
 template <> struct FieldInfo<F_DMINV> { static constexpr int N = 4; };
+template <> struct FieldInfo<F_MASS> { static constexpr int N = 1; };
 
 template <int FIELD>
 MPM_DEV void read_field(const DP& p, const PSet& S, int j, float* o) {
@@ -106,6 +117,7 @@ MPM_DEV void write_field(const DP& p, const PSet& S, int j, const float* v) {
         S.q[0][j].w = S.q[0][j].w < 0.f ? -v[0] : v[0];
         if (j < p.Nf) S.fq[2][j].w = fabsf(v[0]);   // (the copy k_fem reads)
     }
+    if (FIELD == F_MASS) S.q[0][j].w = S.q[0][j].w < 0.f ? -v[0] : v[0];
     if (FIELD == F_AFFINE) {
         S.q[2][j] = make_float4(v[0], v[1], v[2], v[3]);
         S.q[3][j] = make_float4(v[4], v[5], v[6], v[7]);
@@ -313,6 +325,32 @@ static int download_grid(mpm_engine* e, int which, void* out, size_t bytes, size
     return 0;
 }
 
+// a multi-material engine: the density of the cloth of the particle in every API slot
+static int rho_of_slots(mpm_engine* e, std::vector<float>& rho) {
+    std::vector<int> pid(e->np);
+    D2H(e, pid.data(), e->d_pids_api, e->np * 4);
+    rho.resize(e->np);
+    for (size_t s = 0; s < e->np; ++s) rho[s] = e->h_rho_of_pid[pid[s]];
+    return 0;
+}
+
+// MPM_ARR_VOLUMES and MPM_ARR_MASSES.  q[0].w holds the volume in a single-material engine (ParticleToGrid multiplies
+// it by DP::M.density) and the mass in a multi-material one (DP::M.density = 1).
+static int download_volumes_or_masses(mpm_engine* e, bool masses, float* out) {
+    const size_t np = e->np;
+    if (int rc = gather_to_host<F_VOL>(e, out, np, e->d_pids_api)) return rc;
+    if (!e->multi_mat) {
+        if (masses)
+            for (size_t s = 0; s < np; ++s) out[s] = out[s] * e->dp.M.density;
+        return 0;
+    }
+    if (masses) return 0;
+    std::vector<float> rho;
+    if (int rc = rho_of_slots(e, rho)) return rc;
+    for (size_t s = 0; s < np; ++s) out[s] = (float)((double)out[s] / (double)rho[s]);
+    return 0;
+}
+
 static int download_array(mpm_engine* e, int which, void* out, size_t bytes, size_t* written) {
     const size_t np = e->np, nf = e->nf;
     const DP& p = e->dp;
@@ -330,8 +368,9 @@ static int download_array(mpm_engine* e, int which, void* out, size_t bytes, siz
             if ((rc = need(np * 12))) return rc;
             return gather_to_host<F_VEL>(e, (float*)out, np, e->d_pids_api);
         case MPM_ARR_VOLUMES:
+        case MPM_ARR_MASSES:
             if ((rc = need(np * 4))) return rc;
-            return gather_to_host<F_VOL>(e, (float*)out, np, e->d_pids_api);
+            return download_volumes_or_masses(e, which == MPM_ARR_MASSES, (float*)out);
         case MPM_ARR_AFFINE:
             if ((rc = need(np * 36))) return rc;
             return gather_to_host<F_AFFINE>(e, (float*)out, np, e->d_pids_api);
@@ -427,6 +466,13 @@ static int upload_state(mpm_engine* e, const float* pos, const float* vel, const
     if (vel && (rc = scatter_from_host<F_VEL>(e, vel, np, e->d_pids_api))) return rc;
     if (affine && (rc = scatter_from_host<F_AFFINE>(e, affine, np, e->d_pids_api))) return rc;
     if (volumes && (rc = scatter_from_host<F_VOL>(e, volumes, np, e->d_pids_api))) return rc;
+    if (volumes && e->multi_mat) {
+        // the volumes went to the faces' static records (what the FEM reads); q[0].w takes the masses
+        std::vector<float> rho, mass(np);
+        if ((rc = rho_of_slots(e, rho))) return rc;
+        for (size_t s = 0; s < np; ++s) mass[s] = volumes[s] * rho[s];
+        if ((rc = scatter_from_host<F_MASS>(e, mass.data(), np, e->d_pids_api))) return rc;
+    }
     if (Fdef && e->nf) {
         int* iota = nullptr;
         if ((rc = device_iota(e, &iota))) return rc;

@@ -109,6 +109,20 @@ struct GpuMpmState {
                                    reinterpret_cast<const float*>(vel.data()), pos.size(), indices.data(),
                                    indices.size() / 3));
     }
+    // Extension: a cloth with a material of its own (DeformableBodyConfig per body, deformable_model.h:161-163): E, nu,
+    // rho, gamma, K and c_F; the rest stays the engine's.  See mpm_add_qr_cloth_with_material.
+    void AddQRCloth(const std::vector<Vec3<T>>& pos, const std::vector<Vec3<T>>& vel, const std::vector<int>& indices,
+                    const mpm_cloth_material_t& material) {
+        mpm_check(mpm_add_qr_cloth_with_material(h_, reinterpret_cast<const float*>(pos.data()),
+                                                 reinterpret_cast<const float*>(vel.data()), pos.size(), indices.data(),
+                                                 indices.size() / 3, &material));
+    }
+    size_t n_cloths() const { size_t n = 0; mpm_check(mpm_cloth_count(h_, &n)); return n; }
+    mpm_cloth_material_t cloth_material(size_t cloth) const {
+        mpm_cloth_material_t m{};
+        mpm_check(mpm_get_cloth_info(h_, cloth, nullptr, nullptr, nullptr, nullptr, &m));
+        return m;
+    }
     void Finalize() { mpm_check(mpm_finalize(h_)); }
     void Destroy() { mpm_check(mpm_destroy(h_)); h_ = nullptr; }
 

@@ -100,7 +100,10 @@ typedef enum {
     MPM_ARR_GRID_TOUCHED_IDS = 16,   /* uint32[cnt] ascending block ids        */
     MPM_ARR_CONTACT_VEL = 17,    /* float[3*nk]   contact_vel()                */
     MPM_ARR_CONTACT_VEL0 = 18,   /* float[3*nk]   contact_vel0()               */
-    MPM_ARR_GRID_DIR = 19        /* float[3*cells] grid_Dir()                  */
+    MPM_ARR_GRID_DIR = 19,       /* float[3*cells] grid_Dir()                  */
+    MPM_ARR_MASSES = 20          /* float[np]     the mass ParticleToGrid uses for each particle: vol * density
+                                    rounded to float as ParticleToGrid rounds it (per-cloth density: see
+                                    mpm_add_qr_cloth_with_material) */
 } mpm_array_id;
 
 /* Timed phases reported by mpm_profile_substeps. */
@@ -590,6 +593,36 @@ MPM_API int mpm_pins_inside_collider(mpm_handle_t h, const mpm_collider_t *shape
                                      const float R_WB[9], size_t *n_added);
 /* The pin set in order: min(n, capacity) pins into out (may be NULL when capacity is 0), n into *n_out. */
 MPM_API int mpm_get_pins(mpm_handle_t h, mpm_pin_t *out, size_t capacity, size_t *n_out);
+
+/* ---- Per-cloth materials (an extension) ----
+ * DeformableModel::RegisterDeformableBody takes a DeformableBodyConfig per body (deformable_model.h:161-163); this is
+ * that choice for the MPM cloth.  The per-cloth fields are E, nu, rho, gamma, K and c_F, with the meanings of the
+ * same fields of mpm_material_t.  Everything else stays engine-wide, taken from the material given to mpm_create:
+ * the RPIC blend V (read by GridToParticle), gravity and its axis, epsv, sdf_friction and the wall cells.
+ * An engine that receives at least one mpm_add_qr_cloth_with_material call becomes multi-material at mpm_finalize;
+ * its cloths added with plain mpm_add_qr_cloth (before or after) get the engine's material, as does a NULL `m`.
+ * An engine that never calls it runs exactly as before.
+ * In a multi-material engine a particle's ParticleToGrid mass is the float product vol * rho of its cloth, the same
+ * float a single-material engine with that density forms; MPM_ARR_MASSES returns it on every engine.  MPM_ARR_VOLUMES
+ * still returns volumes (within one float ulp: mass / rho) and mpm_upload_particle_state still takes volumes.
+ * Refused with MPM_ERR_INVALID, nothing recorded: a call after mpm_finalize, a non-finite field, E <= 0, nu outside
+ * [0, 0.5), rho <= 0, gamma, K or c_F below 0, and more than 256 cloths in a multi-material engine (a plain
+ * mpm_add_qr_cloth that would be the 257th included).  Partitioned and multi-rank engines are out of scope: a
+ * multi-material engine refuses mpm_dist_init, mpm_chain_*, mpm_team_* and the halo, chain, team and world substeps
+ * with MPM_ERR_INVALID.  Materials cannot change after mpm_finalize. */
+typedef struct mpm_cloth_material {
+    float youngs_modulus, poisson_ratio, density, gamma, K, c_F;   /* meanings as in mpm_material_t */
+} mpm_cloth_material_t;
+/* GpuMpmState::AddQRCloth with a material of its own (m NULL: the engine's material). */
+MPM_API int mpm_add_qr_cloth_with_material(mpm_handle_t h, const float *pos, const float *vel, size_t n_verts,
+                                           const int32_t *indices, size_t n_faces, const mpm_cloth_material_t *m);
+/* Cloth `cloth` in call order (plain mpm_add_qr_cloth calls count too): its vertex range (vertex numbering of
+ * mpm_dump_cpu_state), its face range (original face order) and its material.  Any output may be NULL.  Valid before
+ * and after mpm_finalize. */
+MPM_API int mpm_get_cloth_info(mpm_handle_t h, size_t cloth, size_t *first_vertex, size_t *n_verts,
+                               size_t *first_face, size_t *n_faces, mpm_cloth_material_t *m);
+/* The number of cloths added so far. */
+MPM_API int mpm_cloth_count(mpm_handle_t h, size_t *n_out);
 
 /* Runs n substeps with HIP events around every kernel group on the engine's
  * stream and returns the mean milliseconds per substep of each phase
