@@ -764,13 +764,15 @@ struct SolveOutcome {
 
 static int solve_once(mpm_engine* e, float dt, float mu, float stiffness, float damping, int exact, int max_iters, bool full_setup,
                       SolveOutcome* oc, std::vector<float>* s_res, std::vector<int>* s_ls, std::vector<float>* s_energy,
-                      float* s_alpha_last, float* s_E0_last);
+                      float* s_alpha_last, float* s_E0_last, const std::function<void()>& before_impulse);
 static int contact_stats_from_device(mpm_engine* e);
 static int team_solve(const std::vector<mpm_engine*>& L, float dt, float mu, float stiffness, float damping, int exact, int max_iters,
                       const std::function<void(size_t)>& before_impulse, std::vector<SolveOutcome>* ocs);
 
+// before_impulse (or empty): launched between the solve's last update and its impulses (mpm_run_coupled_substeps)
 static int update_contact(mpm_engine* e, int frame, int substep, float dt, float mu, float stiffness, float damping,
-                          int dump, int exact, int max_iters, int* iters_out, float* residual_out) {
+                          int dump, int exact, int max_iters, int* iters_out, float* residual_out,
+                          const std::function<void()>& before_impulse) {
     ContactBuffers& b = e->cb;
     if (max_iters <= 0) max_iters = 2000;  // cuda_mpm_solver.cu:234
     if (b.n_bodies == 0) {
@@ -782,7 +784,7 @@ static int update_contact(mpm_engine* e, int frame, int substep, float dt, float
         REQUIRE(!dump, "the JSON statistics dump is not available on a partitioned domain");
         std::vector<SolveOutcome> ocs;
         std::function<void(size_t)> hook;
-        if (e->ct_before_impulse) hook = [e](size_t) { e->ct_before_impulse(); };
+        if (before_impulse) hook = [&](size_t) { before_impulse(); };
         if (int rc = team_solve({e}, dt, mu, stiffness, damping, exact, max_iters, hook, &ocs)) return rc;
         if (iters_out) *iters_out = ocs[0].mb.iters;
         if (residual_out) *residual_out = ocs[0].mb.residual;
@@ -808,7 +810,7 @@ static int update_contact(mpm_engine* e, int frame, int substep, float dt, float
         REQUIRE(attempt < 8, "contact solve: the set-up keeps being refused");
         s_res.clear(); s_energy.clear(); s_ls.clear();
         if (int rc = solve_once(e, dt, mu, stiffness, damping, exact, max_iters, full_setup, &oc, &s_res, &s_ls, &s_energy,
-                                &s_alpha_last, &s_E0_last))
+                                &s_alpha_last, &s_E0_last, before_impulse))
             return rc;
         if (oc.mb.done == CT_DONE_CORRUPT) {
             // the count on the device is not one the solve may index with; nothing ran, nothing is repeated: the pairs
@@ -941,7 +943,7 @@ static int contact_stats_from_device(mpm_engine* e) {
 
 static int solve_once(mpm_engine* e, float dt, float mu, float stiffness, float damping, int exact, int max_iters, bool full_setup,
                       SolveOutcome* oc, std::vector<float>* s_res_p, std::vector<int>* s_ls_p, std::vector<float>* s_energy_p,
-                      float* s_alpha_last_p, float* s_E0_last_p) {
+                      float* s_alpha_last_p, float* s_E0_last_p, const std::function<void()>& before_impulse) {
     ContactBuffers& b = e->cb;
     std::vector<float>&s_res = *s_res_p, &s_energy = *s_energy_p;
     std::vector<int>& s_ls = *s_ls_p;
@@ -1196,8 +1198,8 @@ static int solve_once(mpm_engine* e, float dt, float mu, float stiffness, float 
     // over and the device's queue is short -- a long kernel first gives the host time to enqueue what follows; the
     // impulses read the grid velocities and the contact arrays, which GridToParticle does not touch)
     // (not behind a solve that refused itself: the caller repeats that one, and GridToParticle belongs behind the repeat)
-    if (e->ct_before_impulse && (host_driven || (oc->mb.done != CT_DONE_FAULT && oc->mb.done != CT_DONE_STALE && oc->mb.done != CT_DONE_CORRUPT)))
-        e->ct_before_impulse();
+    if (before_impulse && (host_driven || (oc->mb.done != CT_DONE_FAULT && oc->mb.done != CT_DONE_STALE && oc->mb.done != CT_DONE_CORRUPT)))
+        before_impulse();
     hipLaunchKernelGGL(k_ct_impulse, dim3(std::min(gc, 256u)), dim3(256), 0, s, p, c);
     HIP_TRY(hipGetLastError());
     if (host_driven) {

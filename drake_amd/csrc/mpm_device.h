@@ -167,7 +167,9 @@ struct DP {
     int gated;             // bit 0: this substep was enqueued without the re-sort launches and returns at once when it finds a
                            // re-sort pending; bit 1: it returns at once when the slab pool has overflowed (every substep
                            // of mpm_run_substeps; the phase-by-phase calls cannot be repeated by the engine).  Either way it
-                           // counts itself in Ctl::skipped and the host runs it again (settle, mpm_engine.hip)
+                           // counts itself in Ctl::skipped and the host runs it again (settle, mpm_engine.hip).  Per
+                           // launch; the engine's own DP carries it only inside one coupled substep (coupled_substep),
+                           // where the pair generation and the contact solve read it from there
     unsigned watch_base;   // gated bit 2 (mpm_run_coupled_substeps: a substep enqueued WITHOUT pair generation and contact solve, on
                            // the strength of a k_ct_watch that found no particle in any collider): it returns at once when a watch
                            // numbered >= watch_base has found one since (Ctl::watch_hit), counts itself in Ctl::skipped, and the

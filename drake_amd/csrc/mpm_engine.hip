@@ -78,7 +78,6 @@ int mpm_create(int domain_bits, const mpm_material_t* material, int device, mpm_
     if (getenv("MPM_RESORT_EVERY")) e->check_every = std::max(1, atoi(getenv("MPM_RESORT_EVERY")));
     if (getenv("MPM_DEFER_PHASES")) e->defer_phases = atoi(getenv("MPM_DEFER_PHASES")) != 0;
     if (getenv("MPM_QUIET_FACTOR")) e->quiet_factor = std::min(1.f, std::max(0.f, (float)atof(getenv("MPM_QUIET_FACTOR"))));
-    if (getenv("MPM_GRAPH")) e->graph_len = std::max(0, atoi(getenv("MPM_GRAPH")));
     {
         std::lock_guard<std::mutex> lock(g_live_mutex);
         g_live.push_back(e);
@@ -201,65 +200,63 @@ static int grid_colliders_for(mpm_engine* e, int bc, GridColliders* out) {
     return 0;
 }
 
-static void launch_rebuild(mpm_engine* e) {
+// lean: CalcFemStateAndForce follows at once (DP::lean_resort).  Callers that enqueue a possible re-sort call may_resort()
+// themselves.
+static void launch_rebuild(mpm_engine* e, DP p, bool lean = false) {
     // anticipatory binning over the next `horizon` substeps of the last known length (not in a partitioned
     // domain, where ownership and ghost bands are defined by the position itself)
-    e->dp.anticip = e->dp.dist.on ? 0.f : e->anticipate_horizon * e->last_dt * e->dp.dxinv;
-    const DP& p = e->dp;
+    p.anticip = p.dist.on ? 0.f : e->anticipate_horizon * e->last_dt * p.dxinv;
+    p.lean_resort = lean && !p.dist.on;
     e->checks_launched += 1;
     TraceRange tr("mpm:RebuildMapping (conditional re-sort)");
-    // (host state only -- nothing below may depend on this function running: captured graphs replay the launches
-    // without it.  Callers that enqueue a possible re-sort call may_resort() themselves.)
     hipLaunchKernelGGL(k_rb_count, dim3(std::min(e->g_np, e->g_rb)), dim3(256), 0, e->stream, p);
     hipLaunchKernelGGL(k_rb_tables, dim3(33), dim3(1024), 0, e->stream, p);
     hipLaunchKernelGGL(k_rb_scatter, dim3(std::min(e->g_np, e->g_rb)), dim3(256), 0, e->stream, p);
     if (e->deterministic) hipLaunchKernelGGL(k_rb_canon, dim3(512), dim3(256), 0, e->stream, p);
     hipLaunchKernelGGL(k_rb_finish, dim3((std::min(e->g_np, e->g_rb) + 7u) & ~7u), dim3(256), 0, e->stream, p);
 }
-// A re-sort may be about to run (directly or inside a replayed graph): the block tables may change, so contact
+// A re-sort may be about to run: the block tables may change, so contact
 // pairs handed over before are re-keyed with the full width, and the anticipatory binning uses this substep length.
 static void may_resort(mpm_engine* e, float dt) {
     // (the contact solve's guess of how many blocks are active survives a re-sort: k_ct_keys verifies it on the device)
     if (dt > 0.f) e->last_dt = dt;
 }
-static void drop_step_graph(mpm_engine* e) {
-    if (e->step_graph) (void)hipGraphExecDestroy(e->step_graph);
-    e->step_graph = nullptr;
-}
 
-static void launch_fem_faces(mpm_engine* e, float dt) {
+// The launch helpers below take the DP of the launch: e->dp, or a copy of it with the per-launch fields set (DP::lean_g2p,
+// gated, watch_base, halo_hdr, halo_*).
+static void launch_fem_faces(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:CalcFemStateAndForce (faces)");
     if (!e->nf) return;
     const dim3 g((e->g_nf + 7u) & ~7u), b(256);
     if (e->multi_mat) {   // (per-cloth materials, mpm_add_qr_cloth_with_material)
         const ClothMat* t = e->d_cloth_mat;
-        if (e->fast_math) hipLaunchKernelGGL(k_fem_mat<1>, g, b, 0, e->stream, e->dp, dt, t);
-        else hipLaunchKernelGGL(k_fem_mat<0>, g, b, 0, e->stream, e->dp, dt, t);
+        if (e->fast_math) hipLaunchKernelGGL(k_fem_mat<1>, g, b, 0, e->stream, p, dt, t);
+        else hipLaunchKernelGGL(k_fem_mat<0>, g, b, 0, e->stream, p, dt, t);
         return;
     }
-    if (e->fast_math) hipLaunchKernelGGL(k_fem<1>, g, b, 0, e->stream, e->dp, dt);
-    else hipLaunchKernelGGL(k_fem<0>, g, b, 0, e->stream, e->dp, dt);
+    if (e->fast_math) hipLaunchKernelGGL(k_fem<1>, g, b, 0, e->stream, p, dt);
+    else hipLaunchKernelGGL(k_fem<0>, g, b, 0, e->stream, p, dt);
 }
-static void launch_fem_vertices(mpm_engine* e) {
+static void launch_fem_vertices(mpm_engine* e, const DP& p) {
     TraceRange tr("mpm:CalcFemStateAndForce (vertex forces)");
-    if (e->nv) hipLaunchKernelGGL(k_vforce, dim3((e->g_nv + 7u) & ~7u), dim3(256), 0, e->stream, e->dp);
+    if (e->nv) hipLaunchKernelGGL(k_vforce, dim3((e->g_nv + 7u) & ~7u), dim3(256), 0, e->stream, p);
 }
-static void launch_fem(mpm_engine* e, float dt) {
+static void launch_fem(mpm_engine* e, const DP& p, float dt) {
     e->last_dt = dt;
-    launch_fem_faces(e, dt);
-    launch_fem_vertices(e);
+    launch_fem_faces(e, p, dt);
+    launch_fem_vertices(e, p);
 }
 // `forces`: where k_p2g's vertex lanes find the force on their vertex (the kernel's template parameter: 0 = in p.f,
 // k_vforce ran; 1 = summed inside the kernel)
-static void launch_p2g(mpm_engine* e, float dt, int forces = 0) {
+static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
     TraceRange tr(forces ? "mpm:ParticleToGrid (+ vertex forces)" : "mpm:ParticleToGrid");
     const dim3 g(e->g_tile), b(P2G_THREADS);
     // (deterministic mode accumulates in fixed point: exact sums whatever the order of arrival, see k_p2g's EXACT)
     const bool exact = e->deterministic || e->p2g_fixed_point;
 #define MPM_P2G_LAUNCH(F)                                                                          \
     do {                                                                                           \
-        if (exact) hipLaunchKernelGGL((k_p2g<F, 1>), g, b, 0, e->stream, e->dp, dt);               \
-        else hipLaunchKernelGGL((k_p2g<F, 0>), g, b, 0, e->stream, e->dp, dt);                     \
+        if (exact) hipLaunchKernelGGL((k_p2g<F, 1>), g, b, 0, e->stream, p, dt);                   \
+        else hipLaunchKernelGGL((k_p2g<F, 0>), g, b, 0, e->stream, p, dt);                         \
     } while (0)
     if (forces == 1) MPM_P2G_LAUNCH(1);
     else MPM_P2G_LAUNCH(0);
@@ -271,12 +268,12 @@ static void launch_p2g(mpm_engine* e, float dt, int forces = 0) {
 static int fused_forces(const mpm_engine* e) { return e->max_valence <= 8 ? 1 : 0; }
 // FEM faces, then P2G with the vertex forces of every work item computed inside it (no k_vforce launch): the
 // batched substeps use this; the phase-by-phase calls keep the two FEM kernels, whose forces a caller may read
-static void launch_fem_p2g(mpm_engine* e, float dt) {
+static void launch_fem_p2g(mpm_engine* e, const DP& p, float dt) {
     e->last_dt = dt;
-    launch_fem_faces(e, dt);
+    launch_fem_faces(e, p, dt);
     const int forces = fused_forces(e);
-    if (!forces) launch_fem_vertices(e);
-    launch_p2g(e, dt, forces);
+    if (!forces) launch_fem_vertices(e, p);
+    launch_p2g(e, p, dt, forces);
 }
 // the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins launches it (pins_ready has resolved the
 // table).  Everything after GridToParticle -- the coupled path's watch kernel included -- comes after it on the stream.
@@ -284,22 +281,21 @@ static void launch_pins(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:Pins");
     const mpm_engine::PinState& ps = e->pin;
     PinArgs a{ps.d_pins, (int)ps.set.size(), ps.d_mot, (int)ps.motion_body.size(), e->cb.body_acc, (int)e->cb.n_bodies,
-              e->dp.fix_p, ps.d_ticket};
+              p.fix_p, ps.d_ticket};
     const unsigned groups = (unsigned)std::min<size_t>((ps.set.size() + 255) / 256, 1024);
     hipLaunchKernelGGL(k_pin, dim3(groups), dim3(256), 0, e->stream, p, a, dt);
 }
 // (`p` may carry a halo class restriction: only an engine without pins splits GridToParticle, see extensions_refused)
-static void launch_g2p_with(mpm_engine* e, DP p, float dt) {
+static void launch_g2p(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:GridToParticle");
     hipLaunchKernelGGL(k_g2p, dim3(std::min(768u, p.capI) * G2P_SPLIT), dim3(G2P_THREADS), 0, e->stream, p, dt);
     if (!e->pin.set.empty() && p.halo_cls < 0) launch_pins(e, p, dt);
     e->last_tile_kernel = 2;
 }
-static void launch_grid(mpm_engine* e, const GridColliders& gc) {
+static void launch_grid(mpm_engine* e, const DP& p, const GridColliders& gc) {
     TraceRange tr("mpm:UpdateGrid");
-    hipLaunchKernelGGL(k_grid<1>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, gc);
+    hipLaunchKernelGGL(k_grid<1>, dim3(e->g_grid), dim3(256), 0, e->stream, p, gc);
 }
-static void launch_g2p(mpm_engine* e, float dt) { launch_g2p_with(e, e->dp, dt); }
 
 // The P2G tiles accumulate in 64-bit fixed point.  Scales are powers of two chosen from the
 // total particle mass M: a node can never hold more than M, and its momentum is allowed
@@ -323,13 +319,6 @@ static int set_fixed_point_scales(mpm_engine* e) {
     p.fix_p = std::ldexp(1.0, k - 14);
     p.unfix_m = 1.0 / p.fix_m;
     p.unfix_p = 1.0 / p.fix_p;
-    // captured launches carry the scales by value
-    if (e->step_graph) (void)hipGraphExecDestroy(e->step_graph);
-    e->step_graph = nullptr;
-    for (auto& kg : e->halo_graph) {
-        if (kg.exec) (void)hipGraphExecDestroy(kg.exec);
-        kg.exec = nullptr;
-    }
     return 0;
 }
 
@@ -564,7 +553,7 @@ int mpm_finalize(mpm_handle_t e) try {
     c0.nfa = (int)nf;
     c0.nva = (int)nv;
     HIP_TRY(hipMemcpyAsync(p.ctl, &c0, sizeof(Ctl), hipMemcpyHostToDevice, e->stream));
-    launch_rebuild(e);
+    launch_rebuild(e, e->dp);
     HIP_TRY(hipStreamSynchronize(e->stream));
     HIP_TRY(hipGetLastError());
     {
@@ -601,9 +590,6 @@ int mpm_destroy(mpm_handle_t e) try {
     hipSetDevice(e->device);
     if (e->own_stream) hipStreamSynchronize(e->own_stream);
     (void)mpm_chain_destroy(e);
-    drop_step_graph(e);
-    for (auto& kg : e->halo_graph)
-        if (kg.exec) (void)hipGraphExecDestroy(kg.exec);
     for (void* a : e->allocs) hipFree(a);
     if (e->dp.slab) hipFree(e->dp.slab);
     if (e->d_stage) hipFree(e->d_stage);
@@ -630,7 +616,6 @@ int mpm_set_deterministic(mpm_handle_t e, int on) try {
         if (int rc = use(e)) return rc;
         if (int rc = settle(e)) return rc;
     }
-    if (e->deterministic != (on != 0)) drop_step_graph(e);   // the captured substep has one kernel more or less
     e->deterministic = on != 0;
     return 0;
 } MPM_CATCH_ALL
@@ -640,13 +625,6 @@ int mpm_set_fast_math(mpm_handle_t e, int on) try {
     if (e->finalized) {
         if (int rc = use(e)) return rc;
         if (int rc = settle(e)) return rc;   // (owed substeps run with the arithmetic they were enqueued with)
-    }
-    if (e->fast_math != (on != 0)) {
-        drop_step_graph(e);   // captured launches name the kernel
-        for (auto& kg : e->halo_graph) {
-            if (kg.exec) (void)hipGraphExecDestroy(kg.exec);
-            kg.exec = nullptr;
-        }
     }
     e->fast_math = on != 0;
     e->dp.fem_fast = e->fast_math ? 1 : 0;
@@ -685,11 +663,6 @@ static int slab_pool_grow(mpm_engine* e, const Ctl& c) {
     HIP_TRY(hipFree(p.slab));
     p.slab = bigger;
     p.capS = want;
-    drop_step_graph(e);   // captured launches carry the old pointer
-    for (auto& kg : e->halo_graph) {
-        if (kg.exec) (void)hipGraphExecDestroy(kg.exec);
-        kg.exec = nullptr;
-    }
     return 0;
 }
 
@@ -707,7 +680,7 @@ static int recover_slab_overflow(mpm_engine* e, Ctl& c) {
         H2D(e, &e->dp.ctl->error, &zero, sizeof(unsigned));
         H2D(e, &e->dp.ctl->need_rebuild, &one, sizeof(int));
         may_resort(e, 0.f);
-        launch_rebuild(e);
+        launch_rebuild(e, e->dp);
         D2H(e, &c, e->dp.ctl, sizeof(Ctl));
     }
     return 0;
@@ -818,7 +791,6 @@ static int settle(mpm_engine* e, Ctl* fresh) {
 }
 static int settle_owed(mpm_engine* e, Ctl* fresh) {
     e->force_check = true;   // whatever comes next starts with the re-sort launches
-    e->dp.gated = 0;
     e->quiet_left = 0.f;     // (the call that settles may change the state: the hint is only kept from a settle that
                              // has just read it, below, to the substeps enqueued right after)
     if (!e->maybe_owed) return 0;
@@ -853,7 +825,6 @@ static int settle_owed(mpm_engine* e, Ctl* fresh) {
         if (int rc = grid_colliders_for(e, e->owed_bc, &gc)) return rc;
         may_resort(e, e->owed_dt);
         for (unsigned k = 0; k < owed; ++k) launch_substep(e, e->owed_dt, gc, false);
-        e->dp.gated = 0;
     }
     e->force_check = true;
     return 0;
@@ -978,19 +949,19 @@ static int flush_phases(mpm_engine* e) {
     e->pend.n = 0;
     if (n >= 1) {
         may_resort(e, 0.f);
-        launch_rebuild(e);
+        launch_rebuild(e, e->dp);
     }
-    if (n == 2) launch_fem(e, e->pend.dt);
+    if (n == 2) launch_fem(e, e->dp, e->pend.dt);
     if (n >= 3) {
         // (nobody looked at the forces between CalcFemStateAndForce and ParticleToGrid: the vertex forces are
         // gathered inside k_p2g, which also writes them out -- one launch less, the same numbers)
-        launch_fem_p2g(e, e->pend.dt);
+        launch_fem_p2g(e, e->dp, e->pend.dt);
         e->grid_state = 1;
     }
     if (n >= 4) {
         GridColliders gc;
         if (int rc = grid_colliders_for(e, e->pend.bc, &gc)) return rc;
-        launch_grid(e, gc);
+        launch_grid(e, e->dp, gc);
         e->grid_state = 2;
     }
     return 0;
@@ -1004,7 +975,7 @@ int mpm_rebuild_mapping(mpm_handle_t e, int sort) try {
     }
     READY(e);
     may_resort(e, 0.f);
-    launch_rebuild(e);
+    launch_rebuild(e, e->dp);
     if (sort) {
         REQUIRE(!e->dp.dist.on, "RebuildMapping(sort = true) is not available on a partitioned domain");
         return api_sort(e);
@@ -1020,7 +991,7 @@ int mpm_calc_fem_state_and_force(mpm_handle_t e, float dt) try {
         return 0;
     }
     READY(e);
-    launch_fem(e, dt);
+    launch_fem(e, e->dp, dt);
     return 0;
 } MPM_CATCH_ALL
 
@@ -1031,7 +1002,7 @@ int mpm_particle_to_grid(mpm_handle_t e, float dt) try {
         return 0;
     }
     READY(e);
-    launch_p2g(e, dt);
+    launch_p2g(e, e->dp, dt);
     e->grid_state = 1;
     return 0;
 } MPM_CATCH_ALL
@@ -1049,7 +1020,7 @@ int mpm_update_grid(mpm_handle_t e, int bc) try {
     REQUIRE(e->grid_state >= 1, "UpdateGrid before ParticleToGrid");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
-    launch_grid(e, gc);
+    launch_grid(e, e->dp, gc);
     e->grid_state = 2;
     return 0;
 } MPM_CATCH_ALL
@@ -1099,8 +1070,8 @@ int mpm_update_grid_from_sums(mpm_handle_t e, int bc) try {
 int mpm_substep_begin(mpm_handle_t e, float dt) try {
     READY(e);
     may_resort(e, dt);
-    launch_rebuild(e);
-    launch_fem_p2g(e, dt);
+    launch_rebuild(e, e->dp);
+    launch_fem_p2g(e, e->dp, dt);
     hipLaunchKernelGGL(k_grid<0>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, GridColliders{});
     e->grid_state = 3;
     return 0;
@@ -1114,40 +1085,21 @@ int mpm_substep_end(mpm_handle_t e, float dt, int bc) try {
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
     hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, gc);
     e->grid_state = 2;
-    launch_g2p(e, dt);
+    launch_g2p(e, e->dp, dt);
     e->substeps += 1;
     return 0;
 } MPM_CATCH_ALL
 
-// Replays `body` (a sequence of launches on e->stream) from a graph cached under `key`.
-static int replay_keyed(mpm_engine* e, mpm_engine::KeyedGraph& kg, const std::vector<uint64_t>& key,
-                        const std::function<void()>& body) {
-    if (!kg.exec || kg.key != key) {
-        if (kg.exec) (void)hipGraphExecDestroy(kg.exec);
-        kg.exec = nullptr;
-        hipGraph_t g = nullptr;
-        HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-        body();
-        HIP_TRY(hipStreamEndCapture(e->stream, &g));
-        const hipError_t err = hipGraphInstantiate(&kg.exec, g, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(g);
-        HIP_TRY(err);
-        kg.key = key;
-    }
-    HIP_TRY(hipGraphLaunch(kg.exec, e->stream));
-    return 0;
-}
-static uint64_t bits_of(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
-
+// lean: another substep of the same batch follows (mpm_chain_substeps, see DP::lean_g2p)
 static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
-                              void* const* send_bufs, size_t cap, uint32_t* const* counters);
+                              void* const* send_bufs, size_t cap, uint32_t* const* counters, bool lean);
 int mpm_substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
                            void* const* send_bufs, size_t cap) try {
-    return substep_begin_halo(e, dt, n, bx_lo, bx_hi, shift_bx, send_bufs, cap, nullptr);
+    return substep_begin_halo(e, dt, n, bx_lo, bx_hi, shift_bx, send_bufs, cap, nullptr, false);
 } MPM_CATCH_ALL
 // counters: per zone the word the pack counts its entries in (null: word 0 of the send buffer itself)
 static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
-                              void* const* send_bufs, size_t cap, uint32_t* const* counters) {
+                              void* const* send_bufs, size_t cap, uint32_t* const* counters, bool lean) {
     READY(e);
     if (int rc = extensions_refused(e, "halo substeps")) return rc;
     may_resort(e, dt);
@@ -1157,34 +1109,17 @@ static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo,
     DP pp = e->dp;  // ... and k_p2g, in front of it, resets their entry counters
     p.halo_pn = n;
     p.halo_pcap = (unsigned)cap;
-    // (mpm_chain_substeps: another substep of the same batch follows, see DP::lean_g2p)
-    const int lean = e->chain_lean && !e->dp.dist.on;
-    std::vector<uint64_t> key = {1, bits_of(dt), (uint64_t)n, (uint64_t)cap, (uint64_t)(uintptr_t)e->stream, (uint64_t)lean};
+    pp.lean_g2p = lean && !e->dp.dist.on;
     for (int i = 0; i < n; ++i) {
         REQUIRE(send_bufs[i], "null halo buffer");
         pp.halo_hdr[i] = counters && counters[i] ? counters[i] : static_cast<uint32_t*>(send_bufs[i]);
         p.halo_plo[i] = bx_lo[i]; p.halo_phi[i] = bx_hi[i]; p.halo_pshift[i] = shift_bx[i];
         p.halo_pbuf[i] = static_cast<uint32_t*>(send_bufs[i]);
         p.halo_pcnt[i] = counters ? counters[i] : nullptr;
-        key.insert(key.end(), {(uint64_t)(uint32_t)bx_lo[i], (uint64_t)(uint32_t)bx_hi[i], (uint64_t)(uint32_t)shift_bx[i],
-                               (uint64_t)(uintptr_t)send_bufs[i], (uint64_t)(uintptr_t)p.halo_pcnt[i]});
     }
-    auto body = [&]() {
-        e->dp.lean_resort = !e->dp.dist.on;   // (CalcFemStateAndForce follows at once)
-        launch_rebuild(e);
-        e->dp.lean_resort = 0;
-        e->dp.lean_g2p = lean;
-        for (int i = 0; i < 2; ++i) e->dp.halo_hdr[i] = pp.halo_hdr[i];
-        launch_fem_p2g(e, dt);
-        for (int i = 0; i < 2; ++i) e->dp.halo_hdr[i] = nullptr;
-        e->dp.lean_g2p = 0;
-        hipLaunchKernelGGL(k_grid<0>, dim3(e->g_grid), dim3(256), 0, e->stream, p, GridColliders{});
-    };
-    if (e->use_halo_graphs) {
-        if (int rc = replay_keyed(e, e->halo_graph[2 * e->halo_graph_parity], key, body)) return rc;
-    } else {
-        body();
-    }
+    launch_rebuild(e, e->dp, true);
+    launch_fem_p2g(e, pp, dt);
+    hipLaunchKernelGGL(k_grid<0>, dim3(e->g_grid), dim3(256), 0, e->stream, p, GridColliders{});
     e->grid_state = 3;
     e->halo_mid_done = false;
     e->halo_nz = n;
@@ -1205,17 +1140,20 @@ int mpm_substep_mid_halo(mpm_handle_t e, float dt, int bc) try {
     p.halo_nz = e->halo_nz;
     for (int i = 0; i < e->halo_nz; ++i) { p.halo_zlo[i] = e->halo_zlo[i]; p.halo_zhi[i] = e->halo_zhi[i]; }
     hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, p, gc);
-    launch_g2p_with(e, p, dt);
+    launch_g2p(e, p, dt);
     e->halo_mid_done = true;
     return 0;
 } MPM_CATCH_ALL
 
-static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p);
+static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p,
+                            bool lean);
 int mpm_substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap) try {
-    return substep_end_halo(e, dt, bc, n, recv_bufs, cap, true);
+    return substep_end_halo(e, dt, bc, n, recv_bufs, cap, true, false);
 } MPM_CATCH_ALL
 // with_g2p = false: the grid update only -- a coupled substep puts the contact solve between it and GridToParticle
-static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p) {
+// lean: as for substep_begin_halo
+static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p,
+                            bool lean) {
     READY(e);
     if (int rc = extensions_refused(e, "halo substeps")) return rc;
     REQUIRE(n >= 0 && n <= 2 && (n == 0 || recv_bufs), "bad halo buffer list");
@@ -1223,18 +1161,13 @@ static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void*
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
     HaloBufs b{};
-    const int lean = e->chain_lean && !e->dp.dist.on;
-    std::vector<uint64_t> key = {2, bits_of(dt), (uint64_t)(uint32_t)bc, (uint64_t)n, (uint64_t)cap,
-                                 (uint64_t)(uintptr_t)e->stream, e->grid_colliders_version, (uint64_t)lean, (uint64_t)with_g2p};
     for (int i = 0; i < n; ++i) {
         REQUIRE(recv_bufs[i], "null halo buffer");
         b.buf[i] = static_cast<const uint32_t*>(recv_bufs[i]);
-        key.push_back((uint64_t)(uintptr_t)recv_bufs[i]);
     }
-    const bool split = e->halo_mid_done;
     DP p = e->dp;
-    p.lean_g2p = lean;
-    if (split) {   // the interior is done: only what the received sums touch is left
+    p.lean_g2p = lean && !e->dp.dist.on;
+    if (e->halo_mid_done) {   // the interior is done: only what the received sums touch is left
         p.halo_cls = 1;
         p.halo_nz = e->halo_nz;
         for (int i = 0; i < e->halo_nz; ++i) { p.halo_zlo[i] = e->halo_zlo[i]; p.halo_zhi[i] = e->halo_zhi[i]; }
@@ -1251,16 +1184,9 @@ static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void*
             pg.halo_pbuf[i] = const_cast<uint32_t*>(b.buf[i]);
         }
     }
-    auto body = [&]() {
-        if (n > 0 && !folded) hipLaunchKernelGGL(k_halo_add2, dim3(64, n), dim3(256), 0, e->stream, p, b, (unsigned)cap);
-        hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, pg, gc);
-        if (with_g2p) launch_g2p_with(e, p, dt);
-    };
-    if (e->use_halo_graphs && !split) {
-        if (int rc = replay_keyed(e, e->halo_graph[2 * e->halo_graph_parity + 1], key, body)) return rc;
-    } else {
-        body();
-    }
+    if (n > 0 && !folded) hipLaunchKernelGGL(k_halo_add2, dim3(64, n), dim3(256), 0, e->stream, p, b, (unsigned)cap);
+    hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, pg, gc);
+    if (with_g2p) launch_g2p(e, p, dt);
     e->halo_mid_done = false;
     e->grid_state = 2;
     if (with_g2p) e->substeps += 1;
@@ -1568,7 +1494,8 @@ static int chain_zones(const mpm_engine::Chain& c, int* lo, int* hi, int* sh) {
     if (c.right >= 0) { lo[nz] = c.zone_lo[1]; hi[nz] = c.zone_hi[1]; sh[nz] = -c.pitch; ++nz; }
     return nz;
 }
-static int chain_direct_begin(mpm_engine* e, float dt) {
+// lean: another substep of the same batch follows (see substep_begin_halo)
+static int chain_direct_begin(mpm_engine* e, float dt, bool lean) {
     mpm_engine::Chain& c = e->chain;
     REQUIRE(c.direct, "mpm_chain_direct_connect first");
     int lo[2], hi[2], sh[2];
@@ -1594,16 +1521,13 @@ static int chain_direct_begin(mpm_engine* e, float dt) {
         counters[k] = cnt[1];
         ++k;
     }
-    e->halo_graph_parity = parity;
-    const int rc = substep_begin_halo(e, dt, nz, lo, hi, sh, dsb, c.cap, counters);
-    e->halo_graph_parity = 0;
-    if (rc) return rc;
+    if (int rc = substep_begin_halo(e, dt, nz, lo, hi, sh, dsb, c.cap, counters, lean)) return rc;
     if (!c.direct_mute && nz > 0)
         hipLaunchKernelGGL(k_halo_signal, dim3(1), dim3(64), 0, e->stream, sig[0], sig[1], seq, (const uint32_t*)cnt[0], hdr[0],
                            (const uint32_t*)cnt[1], hdr[1], (unsigned)c.cap);
     return 0;
 }
-static int chain_direct_end(mpm_engine* e, float dt, int bc, bool with_g2p) {
+static int chain_direct_end(mpm_engine* e, float dt, int bc, bool with_g2p, bool lean) {
     mpm_engine::Chain& c = e->chain;
     int lo[2], hi[2], sh[2];
     const int nz = chain_zones(c, lo, hi, sh);
@@ -1617,10 +1541,7 @@ static int chain_direct_end(mpm_engine* e, float dt, int bc, bool with_g2p) {
     if (nz > 0)
         hipLaunchKernelGGL(k_halo_wait, dim3(1), dim3(64), 0, e->stream, (const uint32_t*)mine[0], (const uint32_t*)mine[1], seq,
                            (unsigned long long)((double)c.direct_timeout_s * 1e8), e->dp.ctl);
-    e->halo_graph_parity = parity;
-    const int rc = substep_end_halo(e, dt, bc, nz, drb, c.cap, with_g2p);
-    e->halo_graph_parity = 0;
-    return rc;
+    return substep_end_halo(e, dt, bc, nz, drb, c.cap, with_g2p, lean);
 }
 
 int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
@@ -1630,10 +1551,6 @@ int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     REQUIRE(c.comm || c.direct, "mpm_chain_init first");
     const rccl_rt::Api* a = c.comm ? rccl_rt::api() : nullptr;
     REQUIRE(c.comm || c.mig_cap == 0, "migration needs the RCCL communicator (mpm_chain_init with an id)");
-    struct LeanReset {   // (whatever way this function is left)
-        mpm_engine* e;
-        ~LeanReset() { e->chain_lean = 0; }
-    } lean_reset{e};
     // zones / buffers in the order (left, right), leaving out a missing neighbour
     int lo[2], hi[2], sh[2], nz = 0;
     void *sb[2], *rb[2];
@@ -1700,24 +1617,19 @@ int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
                 if (int rc = mpm_dist_retune(e, t, dt, nullptr)) return rc;   // (band widths for the migrations to come)
             }
         }
-        e->chain_lean = s + 1 < n;   // (reset below; the two calls are public entry points of their own as well)
+        const bool lean = s + 1 < n;
         if (c.direct && nz > 0) {
             // DIRECT: the pack kernel stores into the neighbours' receive buffers of this substep's parity (two in
             // rotation: a neighbour may still be reading the other one -- it cannot be reading this one: its read of
             // substep s - 2 precedes its signal of s - 1, which this rank's update of s - 1 has waited for), a one-thread
             // kernel raises the flags over there, a one-wave kernel waits for this rank's.
-            int rc_d = chain_direct_begin(e, dt);
-            if (!rc_d) rc_d = chain_direct_end(e, dt, bc, true);
-            e->chain_lean = 0;
-            if (rc_d) return rc_d;
+            if (int rc = chain_direct_begin(e, dt, lean)) return rc;
+            if (int rc = chain_direct_end(e, dt, bc, true, lean)) return rc;
             continue;
         }
         c.mig_elapsed += dt;
         c.steps += 1;
-        if (int rc = mpm_substep_begin_halo(e, dt, nz, lo, hi, sh, sb, c.cap)) {
-            e->chain_lean = 0;
-            return rc;
-        }
+        if (int rc = substep_begin_halo(e, dt, nz, lo, hi, sh, sb, c.cap, nullptr, lean)) return rc;
         if (nz > 0) {
             RCCL_TRY(a->group_start());
             // what goes to the left arrives "from the right" over there: when both neighbours are the
@@ -1732,9 +1644,7 @@ int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
             RCCL_TRY(rc_g);
             RCCL_TRY(rc_e);
         }
-        const int rc_end = mpm_substep_end_halo(e, dt, bc, nz, rb, c.cap);
-        e->chain_lean = 0;
-        if (rc_end) return rc_end;
+        if (int rc = substep_end_halo(e, dt, bc, nz, rb, c.cap, true, lean)) return rc;
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1750,14 +1660,22 @@ int mpm_grid_to_particle(mpm_handle_t e, float dt) try {
     }
     READY(e);
     REQUIRE(e->grid_state == 2, "GridToParticle before UpdateGrid");
-    launch_g2p(e, dt);
+    launch_g2p(e, e->dp, dt);
     e->substeps += 1;
     return 0;
 } MPM_CATCH_ALL
 
 int mpm_substep(mpm_handle_t e, float dt, int bc) try { return mpm_run_substeps(e, 1, dt, bc); } MPM_CATCH_ALL
 
-// allow_gate: the substep may go without the re-sort launches (mpm_run_substeps outside graphs)
+// The front of a batched substep, all from the launch's DP `p`: the re-sort launches when the substep is checked, FEM +
+// ParticleToGrid (the vertex forces inside it), the grid update.  The caller launches GridToParticle with the same DP.
+static void launch_substep_front(mpm_engine* e, const DP& p, float dt, const GridColliders& gc, bool check) {
+    if (check) launch_rebuild(e, p, true);
+    launch_fem_p2g(e, p, dt);
+    launch_grid(e, p, gc);
+}
+
+// allow_gate: the substep may go without the re-sort launches (mpm_run_substeps; settle_owed runs the owed ones with them)
 // lean: another substep follows in the same batch, GridToParticle need not refresh what only a download reads
 static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, bool allow_gate, bool lean) {
     e->last_dt = dt;
@@ -1778,45 +1696,13 @@ static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, boo
         }
     }
     e->step_phase += 1;
-    e->dp.gated = check ? 2 : 3;   // (bit 1: it also skips itself while the slab pool is too small, see DP::gated)
-    if (check) {
-        e->dp.lean_resort = !e->dp.dist.on;
-        launch_rebuild(e);
-        e->dp.lean_resort = 0;
-        e->force_check = false;
-    }
+    if (check) e->force_check = false;
     e->maybe_owed = true;
-    e->dp.lean_g2p = lean && !e->dp.dist.on;   // (k_p2g: the forces stay in LDS; k_g2p: no face x / v records)
-    launch_fem_p2g(e, dt);
-    launch_grid(e, gc);
-    launch_g2p(e, dt);
-    e->dp.lean_g2p = 0;
-}
-
-// A substep is nine dependent kernels with constant arguments and no host decisions (the re-sort
-// is decided on the device), so a batch of substeps replays one captured graph: the graph's
-// kernel-to-kernel hand-over is cheaper than nine stream dispatches.
-static int step_graph_for(mpm_engine* e, float dt, int bc, const GridColliders& gc) {
-    if (e->step_graph && e->step_graph_dt == dt && e->step_graph_bc == bc && e->step_graph_stream == e->stream &&
-        e->step_graph_gcv == e->grid_colliders_version && e->step_graph_pinv == e->pin.version &&
-        e->step_graph_acc == e->cb.body_acc && e->step_graph_nb == e->cb.n_bodies)
-        return 0;
-    drop_step_graph(e);
-    hipGraph_t g = nullptr;
-    HIP_TRY(hipStreamBeginCapture(e->stream, hipStreamCaptureModeThreadLocal));
-    for (int k = 0; k < e->step_graph_len; ++k) launch_substep(e, dt, gc, false);
-    HIP_TRY(hipStreamEndCapture(e->stream, &g));
-    const hipError_t err = hipGraphInstantiate(&e->step_graph, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    HIP_TRY(err);
-    e->step_graph_dt = dt;
-    e->step_graph_bc = bc;
-    e->step_graph_gcv = e->grid_colliders_version;
-    e->step_graph_pinv = e->pin.version;   // (k_pin's arguments: the pin table, the motions, the impulse accumulators)
-    e->step_graph_acc = e->cb.body_acc;
-    e->step_graph_nb = e->cb.n_bodies;
-    e->step_graph_stream = e->stream;
-    return 0;
+    DP p = e->dp;
+    p.gated = check ? 2 : 3;   // (bit 1: it also skips itself while the slab pool is too small, see DP::gated)
+    p.lean_g2p = lean && !p.dist.on;   // (k_p2g: the forces stay in LDS; k_g2p: no face x / v records)
+    launch_substep_front(e, p, dt, gc, check);
+    launch_g2p(e, p, dt);
 }
 
 int mpm_run_substeps(mpm_handle_t e, int n, float dt, int bc) try {
@@ -1829,23 +1715,10 @@ int mpm_run_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     e->owed_dt = dt;
     e->owed_bc = bc;
     e->owed_gcv = e->grid_colliders_version;
-    // MPM_GRAPH=<substeps per graph> replays captured graphs; measured slower than plain stream
-    // dispatch on ROCm 7.2, hence opt-in
-    const int graph_len = e->graph_len;
     may_resort(e, dt);
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
-    int s = 0;
-    if (graph_len > 0 && n >= graph_len) {
-        e->step_graph_len = graph_len;
-        if (int rc = step_graph_for(e, dt, bc, gc)) return rc;
-        for (; s + graph_len <= n; s += graph_len) {
-            HIP_TRY(hipGraphLaunch(e->step_graph, e->stream));
-            // (launch_substep sets this while a graph is CAPTURED; a replay enqueues the same self-skipping substeps)
-            e->maybe_owed = true;
-        }
-    }
-    for (; s < n; ++s) launch_substep(e, dt, gc, true, s + 1 < n);
+    for (int s = 0; s < n; ++s) launch_substep(e, dt, gc, true, s + 1 < n);
     e->grid_state = 2;
     e->substeps += (uint64_t)std::max(n, 0);
     HIP_TRY(hipGetLastError());
@@ -1865,23 +1738,23 @@ int mpm_profile_substeps(mpm_handle_t e, int n, float dt, int bc, float* phase_m
     for (int s = 0; s < n; ++s) {
         hipEvent_t* q = &ev[(size_t)s * NE];
         HIP_TRY(hipEventRecord(q[0], e->stream));
-        launch_rebuild(e);
+        launch_rebuild(e, e->dp);
         HIP_TRY(hipEventRecord(q[1], e->stream));
-        launch_fem_faces(e, dt);
+        launch_fem_faces(e, e->dp, dt);
         HIP_TRY(hipEventRecord(q[2], e->stream));
         // (as in mpm_run_substeps: the vertex forces are part of k_p2g; this phase is empty)
         HIP_TRY(hipEventRecord(q[3], e->stream));
-        e->dp.lean_g2p = s + 1 < n && !e->dp.dist.on;   // (as in mpm_run_substeps)
+        DP p = e->dp;
+        p.lean_g2p = s + 1 < n && !p.dist.on;   // (as in mpm_run_substeps)
         {
             const int forces = fused_forces(e);
-            if (!forces) launch_fem_vertices(e);
-            launch_p2g(e, dt, forces);
+            if (!forces) launch_fem_vertices(e, p);
+            launch_p2g(e, p, dt, forces);
         }
         HIP_TRY(hipEventRecord(q[4], e->stream));
-        launch_grid(e, gc);
+        launch_grid(e, p, gc);
         HIP_TRY(hipEventRecord(q[5], e->stream));
-        launch_g2p(e, dt);
-        e->dp.lean_g2p = 0;
+        launch_g2p(e, p, dt);
         HIP_TRY(hipEventRecord(q[6], e->stream));
     }
     e->grid_state = 2;
@@ -2199,11 +2072,6 @@ static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) 
     p.Np = (int)new_np; p.Nf = (int)new_nf; p.Nv = (int)new_nv;
     p.q_stride = new_q_stride;
     p.f_stride = new_q_stride;
-    drop_step_graph(e);
-    for (auto& kg : e->halo_graph) {
-        if (kg.exec) (void)hipGraphExecDestroy(kg.exec);
-        kg.exec = nullptr;
-    }
     hipLaunchKernelGGL(k_dist_shift_slots, dim3(1024), dim3(256), 0, e->stream, p, (int)old_nf, (int)new_nf, (int)nfa);
     // block tables, work items and wave groups hold slot ranges: rebuild them on the new slot space
     const int one = 1;
@@ -2211,7 +2079,7 @@ static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) 
     e->dist_resizes += 1;
     if (!first) return 0;   // (a migration follows, and the re-sort that merges what it brings)
     may_resort(e, 0.f);
-    launch_rebuild(e);
+    launch_rebuild(e, e->dp);
     D2H(e, &c, p.ctl, sizeof(Ctl));
     return recover_slab_overflow(e, c);
 }
@@ -2309,12 +2177,11 @@ int mpm_dist_init(mpm_handle_t e, const mpm_dist_config_t* cfg) try {
     hipLaunchKernelGGL(k_dist_build_topology, dim3(std::min(e->g_np, 2048u)), dim3(256), 0, e->stream, e->dp);
     e->dp.dist = d;
     e->dist_cfg = *cfg;
-    drop_step_graph(e);
     hipLaunchKernelGGL(k_dist_init_roles, dim3(e->g_np), dim3(256), 0, e->stream, e->dp);
     int one = 1;
     H2D(e, &e->dp.ctl->need_rebuild, &one, sizeof(int));
     may_resort(e, 0.f);
-    launch_rebuild(e);
+    launch_rebuild(e, e->dp);
     {
         Ctl c;
         D2H(e, &c, e->dp.ctl, sizeof(Ctl));
@@ -2381,11 +2248,6 @@ int mpm_dist_retune(mpm_handle_t e, float quiet_time_all, float dt, int* changed
     d.vert_w = d.ghost_w + e->dist_reach;
     d.mig_reach = d.vert_w + 2.f * e->dist_reach + 1.f;
     e->dist_retunes += 1;
-    drop_step_graph(e);
-    for (auto& kg : e->halo_graph) {   // (captured launches carry the Dist by value)
-        if (kg.exec) (void)hipGraphExecDestroy(kg.exec);
-        kg.exec = nullptr;
-    }
     if (changed_out) *changed_out = 1;
     return 0;
 } MPM_CATCH_ALL
@@ -2750,7 +2612,7 @@ int mpm_update_contact(mpm_handle_t e, int frame, int substep, float dt, float m
     if (!e->cb.dev_counted && e->cb.n == 0 && !(e->dp.dist.on && e->team.on)) return 0;  // cuda_mpm_solver.cu:216-217
     REQUIRE(e->grid_state == 2, "UpdateContact before UpdateGrid");
     return update_contact(e, frame, substep, dt, mu, stiffness, damping, dump, exact, max_iters, iters_out,
-                          residual_out);
+                          residual_out, nullptr);
 } MPM_CATCH_ALL
 
 // The body of DeformableDriver::CalcAbstractStates' substep loop (multibody/plant/deformable_driver.h:240-258) for
@@ -2783,15 +2645,14 @@ static int team_coupled_substeps(const std::vector<mpm_engine*>& L, int n, const
     for (int s = 0; s < n; ++s) {
         for (mpm_engine* e : L) {
             may_resort(e, dt);
-            e->chain_lean = 0;
-            if (int rc = chain_direct_begin(e, dt)) return rc;
+            if (int rc = chain_direct_begin(e, dt, false)) return rc;
         }
         for (mpm_engine* e : L)
-            if (int rc = chain_direct_end(e, dt, prm->mpm_bc, false)) return rc;
+            if (int rc = chain_direct_end(e, dt, prm->mpm_bc, false, false)) return rc;
         for (mpm_engine* e : L)
             if (int rc = generate_contacts(e, n_colliders, colliders, nullptr)) return rc;
         std::vector<SolveOutcome> ocs;
-        auto g2p = [&](size_t i) { launch_g2p(L[i], dt); };
+        auto g2p = [&](size_t i) { launch_g2p(L[i], L[i]->dp, dt); };
         if (int rc = team_solve(L, dt, prm->friction_mu, prm->stiffness, prm->damping, prm->exact_line_search, prm->max_newton_iterations,
                                 g2p, &ocs))
             return rc;
@@ -2832,6 +2693,165 @@ int mpm_world_coupled_substeps(mpm_handle_t* handles, int n_local, int n, const 
     return team_coupled_substeps(L, n, prm, n_colliders, colliders, results);
 } MPM_CATCH_ALL
 
+// The state that mpm_run_coupled_substeps carries from one substep to the next.
+// Re-sort check launches (four kernels that return at once unless GridToParticle has raised need_rebuild): with every
+// substep that may not skip itself; none while the quiet time that the last re-sort estimated lasts -- the host learns
+// what is left of it from every solve's publication.  A substep that goes without them and finds a re-sort pending
+// skips itself as a whole (DP::gated: transfer kernels, contact solve, GridToParticle) and is run again, with the
+// re-sort in front: a wrong guess costs time, not correctness.
+// Contact-free stretches (round 5): when a coupled substep had no pairs, a watch kernel behind its GridToParticle asks
+// whether the NEXT one would have any (k_ct_watch: exact); the following substeps are then enqueued in chunks WITHOUT
+// pair generation, contact solve or any wait, each with its own watch behind it and the gate "skip yourself if a watch
+// since `watch_base` has seen a particle in a collider" (DP::gated bit 2).  After a chunk the host synchronises once and
+// reads how many of its substeps skipped themselves -- always the last ones: a hit is sticky -- and runs those as
+// coupled substeps.  A cloth that falls towards a body costs a contact-free substep plus the watch until it arrives.
+struct CoupledSpec {
+    bool spec = false;            // the next substeps go in contact-free chunks
+    int chunk = 2;                // substeps of the next chunk
+    unsigned watch_base = 0;      // the watch that opened the stretch
+    bool spec_check = true;       // the next chunk's substeps all carry their re-sort launches
+    float spec_quiet_left = 0.f;  // seconds of quiet time left as of the last look at the control block
+    bool force_check = true;      // the next coupled substep carries its re-sort launches
+};
+// (MPM_CT_DEBUG: where the HOST's time of the call goes)
+struct CoupledTimes {
+    double base = 0, gen = 0, solve = 0, tail = 0;
+};
+
+// Coupled substep s of n: pairs, contact solve, GridToParticle in front of the solve's impulses.  *done: 1, or 0 when the
+// substep skipped itself as a whole (last_contact_gated) and is to be run again.
+static int coupled_substep(mpm_engine* e, int s, int n, const mpm_coupled_params_t* prm, const GridColliders& gc,
+                           size_t n_colliders, const mpm_collider_t* colliders, CoupledSpec* sp, CoupledTimes* t,
+                           mpm_coupled_result_t* results, int* done) {
+    using clk = std::chrono::steady_clock;
+    auto since = [](clk::time_point a) { return std::chrono::duration<double, std::micro>(clk::now() - a).count(); };
+    const float dt = prm->dt;
+    *done = 0;
+    auto t0 = clk::now();
+    const bool gate = !sp->force_check && (e->ct_gate_always || e->quiet_factor * e->ct_quiet_left > 2.f * dt);
+    may_resort(e, dt);
+    DP p = e->dp;
+    p.gated = gate ? 1 : 0;
+    p.lean_g2p = s + 1 < n;
+    int rc = 0, iters = 0;
+    float residual = 0.f;
+    bool g2p_done = false;
+    {
+        // the pair generation and the contact solve read the gate from the engine's DP: set for them, and cleared
+        // however this block is left
+        struct GateOff {
+            mpm_engine* e;
+            ~GateOff() { e->dp.gated = 0; }
+        } gate_off{e};
+        e->dp.gated = p.gated;
+        launch_substep_front(e, p, dt, gc, !gate);
+        sp->force_check = false;
+        e->grid_state = 2;
+        t->base += since(t0); t0 = clk::now();
+        rc = generate_contacts(e, n_colliders, colliders, nullptr);
+        t->gen += since(t0); t0 = clk::now();
+        e->last_contact_gated = false;
+        if (!rc && (e->cb.dev_counted || e->cb.n > 0))
+            rc = update_contact(e, 0, s, dt, prm->friction_mu, prm->stiffness, prm->damping, 0, prm->exact_line_search,
+                                prm->max_newton_iterations, &iters, &residual, [&]() {
+                                    launch_g2p(e, p, dt);
+                                    g2p_done = true;
+                                });
+        else if (!rc)
+            e->last_contact = mpm_contact_stats_t{};
+        t->solve += since(t0); t0 = clk::now();
+    }
+    if (rc) return rc;
+    if (!g2p_done) launch_g2p(e, p, dt);
+    t->tail += since(t0);
+    if (e->last_contact_gated) {
+        // nothing of this substep has run (its GridToParticle counted it in Ctl::skipped, which belongs to
+        // mpm_run_substeps' bookkeeping: cleared): once more, with the re-sort in front
+        REQUIRE(gate, "contact solve: a substep with its re-sort launches reported itself as skipped");
+        HIP_TRY(hipMemsetAsync(&e->dp.ctl->skipped, 0, sizeof(unsigned), e->stream));
+        e->ct_counters[2] += 1;
+        e->ct_quiet_left = 0.f;
+        sp->force_check = true;
+        return 0;
+    }
+    *done = 1;
+    e->substeps += 1;
+    if (results) {
+        mpm_coupled_result_t& r = results[s];
+        r.iterations = iters;
+        r.contacts = e->last_contact.contacts;
+        r.nodes = e->last_contact.nodes;
+        r.residual = residual;
+        r.setup_reused = e->last_contact_reused ? 1 : 0;
+    }
+    // no pairs in this substep: ask whether the next one has any, and go on without pair generation while it has not
+    if (!e->ct_no_watch && s + 1 < n && e->last_contact.contacts == 0 && !e->cb.dev_counted) {
+        sp->watch_base = ++e->watch_seq;
+        launch_contact_watch(e, e->dp, sp->watch_base);
+        sp->spec = true;
+        sp->spec_check = false;
+        sp->spec_quiet_left = e->ct_quiet_left;   // (what the solve's publication said is left of the quiet time)
+    }
+    return 0;
+}
+
+// A contact-free chunk from substep s of n (see CoupledSpec).  *done: how many of its substeps ran.
+static int coupled_chunk(mpm_engine* e, int s, int n, float dt, const GridColliders& gc, CoupledSpec* sp,
+                         mpm_coupled_result_t* results, int* done) {
+    const int m = std::min(sp->chunk, n - s);
+    // (the re-sort checks of a chunk: none while the quiet time lasts that the last look at the control block left
+    // -- a substep that meets a pending re-sort then skips itself like one that meets a hit, and the chunk's tail is
+    // repeated with the checks --, else with every substep)
+    float quiet = sp->spec_check ? 0.f : e->quiet_factor * sp->spec_quiet_left;
+    for (int q = 0; q < m; ++q) {
+        const bool unchecked = quiet > 2.f * dt;
+        quiet -= dt;
+        may_resort(e, dt);
+        DP p = e->dp;
+        p.gated = 4 | (unchecked ? 1 : 0);
+        p.watch_base = sp->watch_base;
+        p.lean_g2p = s + q + 1 < n;
+        launch_substep_front(e, p, dt, gc, !unchecked);
+        launch_g2p(e, p, dt);
+        launch_contact_watch(e, p, ++e->watch_seq);
+    }
+    e->grid_state = 2;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    Ctl c;
+    D2H(e, &c, e->dp.ctl, sizeof(Ctl));
+    const int skipped = (int)std::min<unsigned>(c.skipped, (unsigned)m);
+    if (c.skipped) {
+        const unsigned zero = 0;
+        H2D(e, &e->dp.ctl->skipped, &zero, sizeof(unsigned));
+    }
+    const int ran = m - skipped;
+    const bool hit = (int)(c.watch_hit - sp->watch_base) >= 0;
+    e->ct_counters[4] += (uint64_t)m;
+    e->ct_counters[5] += (uint64_t)skipped;
+    for (int q = 0; q < ran; ++q) {
+        e->substeps += 1;
+        if (results) results[s + q] = mpm_coupled_result_t{};
+    }
+    if (ran > 0) {
+        e->last_contact = mpm_contact_stats_t{};
+        e->last_contact_reused = false;
+    }
+    sp->spec_quiet_left = c.need_rebuild || c.error ? 0.f : std::max(0.f, c.quiet_time - c.time_since_resort);
+    sp->spec_check = skipped > 0;   // (whatever made them skip: the repeated ones carry their checks)
+    // (an error flag ends the speculation too: the coupled substep that follows reports it where it always was)
+    if (hit || c.error) {
+        sp->spec = false;
+        sp->chunk = 2;
+        sp->force_check = true;
+    } else if (skipped > 0) {
+        sp->chunk = 2;           // a re-sort was pending: the tail of the chunk again, contact-free, with its checks
+    } else {
+        sp->chunk = std::min(sp->chunk * 2, 32);
+    }
+    *done = ran;
+    return 0;
+}
+
 int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* prm, size_t n_colliders,
                              const mpm_collider_t* colliders, mpm_coupled_result_t* results) try {
     READY(e);
@@ -2855,172 +2875,23 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
     }
     GridColliders gc;
     if (int rc = grid_colliders_for(e, prm->mpm_bc, &gc)) return rc;
-    const float dt = prm->dt;
-    // (MPM_CT_DEBUG: where the HOST's time of the call goes, per substep)
-    using clk = std::chrono::steady_clock;
-    double t_base = 0, t_gen = 0, t_solve = 0, t_tail = 0;
-    auto since = [](clk::time_point a) { return std::chrono::duration<double, std::micro>(clk::now() - a).count(); };
-    struct Report {
-        mpm_engine* e; int n; double *a, *b, *c, *d;
+    struct Report {   // (MPM_CT_DEBUG: per substep, however the function is left)
+        mpm_engine* e; int n; CoupledTimes t;
         ~Report() {
             if (e->ct_debug && n > 0)
                 std::fprintf(stderr, "[mpm_hip] coupled substeps, host us per substep: base launches %.1f, pairs %.1f, solve (set-up + "
-                                     "iterations + waits: %.1f polling) %.1f, GridToParticle %.1f\n", *a / n, *b / n, e->ct_wait_us / n, *c / n, *d / n);
+                                     "iterations + waits: %.1f polling) %.1f, GridToParticle %.1f\n", t.base / n, t.gen / n, e->ct_wait_us / n,
+                             t.solve / n, t.tail / n);
         }
-    } report{e, n, &t_base, &t_gen, &t_solve, &t_tail};
+    } report{e, n, {}};
     e->ct_wait_us = 0;
-    struct HookReset {   // (however the function is left)
-        mpm_engine* e;
-        ~HookReset() { e->ct_before_impulse = nullptr; e->dp.lean_g2p = 0; e->dp.gated = 0; }
-    } hook_reset{e};
-    bool g2p_done = false;
-    // Re-sort check launches (four kernels that return at once unless GridToParticle has raised need_rebuild): with every
-    // substep that may not skip itself; none while the quiet time that the last re-sort estimated lasts -- the host learns
-    // what is left of it from every solve's publication.  A substep that goes without them and finds a re-sort pending
-    // skips itself as a whole (DP::gated: transfer kernels, contact solve, GridToParticle) and is run again, with the
-    // re-sort in front: a wrong guess costs time, not correctness.
-    bool force_check = true;
-    // Contact-free stretches (round 5): when a coupled substep had no pairs, a watch kernel behind its GridToParticle asks
-    // whether the NEXT one would have any (k_ct_watch: exact); the following substeps are then enqueued in chunks WITHOUT
-    // pair generation, contact solve or any wait, each with its own watch behind it and the gate "skip yourself if a watch
-    // since `watch_base` has seen a particle in a collider" (DP::gated bit 2).  After a chunk the host synchronises once and
-    // reads how many of its substeps skipped themselves -- always the last ones: a hit is sticky -- and runs those as
-    // coupled substeps.  A cloth that falls towards a body costs a contact-free substep plus the watch until it arrives.
-    const bool may_watch = n_all > 0 && !e->ct_no_watch;
-    bool spec = false, spec_check = true;
-    float spec_quiet_left = 0.f;
-    unsigned watch_base = 0;
-    int chunk = 2;
-    for (int s = 0; s < n; ++s) {
-        if (spec) {
-            const int m = std::min(chunk, n - s);
-            // (the re-sort checks of a chunk: none while the quiet time lasts that the last look at the control block left
-            // -- a substep that meets a pending re-sort then skips itself like one that meets a hit, and the chunk's tail is
-            // repeated with the checks --, else with every substep)
-            float quiet = spec_check ? 0.f : e->quiet_factor * spec_quiet_left;
-            for (int q = 0; q < m; ++q) {
-                const bool unchecked = quiet > 2.f * dt;
-                quiet -= dt;
-                may_resort(e, dt);
-                e->dp.gated = 4 | (unchecked ? 1 : 0);
-                e->dp.watch_base = watch_base;
-                if (!unchecked) {
-                    e->dp.lean_resort = 1;
-                    launch_rebuild(e);
-                    e->dp.lean_resort = 0;
-                }
-                e->dp.lean_g2p = s + q + 1 < n;
-                launch_fem_p2g(e, dt);
-                launch_grid(e, gc);
-                launch_g2p(e, dt);
-                launch_contact_watch(e, e->dp, ++e->watch_seq);
-            }
-            e->dp.gated = 0;
-            e->dp.lean_g2p = 0;
-            e->grid_state = 2;
-            HIP_TRY(hipStreamSynchronize(e->stream));
-            Ctl c;
-            D2H(e, &c, e->dp.ctl, sizeof(Ctl));
-            const int skipped = (int)std::min<unsigned>(c.skipped, (unsigned)m);
-            if (c.skipped) {
-                const unsigned zero = 0;
-                H2D(e, &e->dp.ctl->skipped, &zero, sizeof(unsigned));
-            }
-            const int ran = m - skipped;
-            const bool hit = (int)(c.watch_hit - watch_base) >= 0;
-            e->ct_counters[4] += (uint64_t)m;
-            e->ct_counters[5] += (uint64_t)skipped;
-            for (int q = 0; q < ran; ++q) {
-                e->substeps += 1;
-                if (results) results[s + q] = mpm_coupled_result_t{};
-            }
-            if (ran > 0) {
-                e->last_contact = mpm_contact_stats_t{};
-                e->last_contact_reused = false;
-            }
-            spec_quiet_left = c.need_rebuild || c.error ? 0.f : std::max(0.f, c.quiet_time - c.time_since_resort);
-            spec_check = skipped > 0;   // (whatever made them skip: the repeated ones carry their checks)
-            // (an error flag ends the speculation too: the coupled substep that follows reports it where it always was)
-            if (hit || c.error) {
-                spec = false;
-                chunk = 2;
-                force_check = true;
-            } else if (skipped > 0) {
-                chunk = 2;           // a re-sort was pending: the tail of the chunk again, contact-free, with its checks
-            } else {
-                chunk = std::min(chunk * 2, 32);
-            }
-            s += ran - 1;   // (the loop's own increment makes it `ran`)
-            continue;
-        }
-        auto t0 = clk::now();
-        // (without colliders there is no solve whose publication would report a skipped substep: always checked)
-        const bool gate = n_all > 0 && !force_check && (e->ct_gate_always || e->quiet_factor * e->ct_quiet_left > 2.f * dt);
-        may_resort(e, dt);
-        e->dp.gated = gate ? 1 : 0;
-        if (!gate) {
-            e->dp.lean_resort = 1;   // (CalcFemStateAndForce follows at once)
-            launch_rebuild(e);
-            e->dp.lean_resort = 0;
-        }
-        force_check = false;
-        e->dp.lean_g2p = s + 1 < n;
-        launch_fem_p2g(e, dt);
-        launch_grid(e, gc);
-        e->grid_state = 2;
-        int iters = 0;
-        float residual = 0.f;
-        t_base += since(t0); t0 = clk::now();
-        int rc = generate_contacts(e, n_colliders, colliders, nullptr);
-        t_gen += since(t0); t0 = clk::now();
-        g2p_done = false;
-        e->ct_before_impulse = [&]() {
-            launch_g2p(e, dt);
-            g2p_done = true;
-        };
-        e->last_contact_gated = false;
-        if (!rc && (e->cb.dev_counted || e->cb.n > 0))
-            rc = update_contact(e, 0, s, dt, prm->friction_mu, prm->stiffness, prm->damping, 0, prm->exact_line_search,
-                                prm->max_newton_iterations, &iters, &residual);
-        else if (!rc)
-            e->last_contact = mpm_contact_stats_t{};
-        e->ct_before_impulse = nullptr;
-        t_solve += since(t0); t0 = clk::now();
-        if (rc) return rc;
-        if (!g2p_done) launch_g2p(e, dt);
-        e->dp.lean_g2p = 0;
-        t_tail += since(t0);
-        if (e->last_contact_gated) {
-            // nothing of this substep has run (its GridToParticle counted it in Ctl::skipped, which belongs to
-            // mpm_run_substeps' bookkeeping: cleared): once more, with the re-sort in front
-            REQUIRE(gate, "contact solve: a substep with its re-sort launches reported itself as skipped");
-            HIP_TRY(hipMemsetAsync(&e->dp.ctl->skipped, 0, sizeof(unsigned), e->stream));
-            e->ct_counters[2] += 1;
-            e->ct_quiet_left = 0.f;
-            force_check = true;
-            --s;
-            continue;
-        }
-        e->substeps += 1;
-        if (results) {
-            mpm_coupled_result_t& r = results[s];
-            r.iterations = iters;
-            r.contacts = e->last_contact.contacts;
-            r.nodes = e->last_contact.nodes;
-            r.residual = residual;
-            r.setup_reused = e->last_contact_reused ? 1 : 0;
-        }
-        // no pairs in this substep: ask whether the next one has any, and go on without pair generation while it has not
-        spec = false;
-        if (may_watch && s + 1 < n && e->last_contact.contacts == 0 && !e->cb.dev_counted) {
-            watch_base = ++e->watch_seq;
-            DP pw = e->dp;
-            pw.gated = 0;
-            launch_contact_watch(e, pw, watch_base);
-            spec = true;
-            spec_check = false;
-            spec_quiet_left = e->ct_quiet_left;   // (what the solve's publication said is left of the quiet time)
-        }
+    CoupledSpec sp;
+    for (int s = 0; s < n;) {
+        int done = 0;
+        if (int rc = sp.spec ? coupled_chunk(e, s, n, prm->dt, gc, &sp, results, &done)
+                             : coupled_substep(e, s, n, prm, gc, n_colliders, colliders, &sp, &report.t, results, &done))
+            return rc;
+        s += done;
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -3103,7 +2974,6 @@ int mpm_set_pins(mpm_handle_t e, size_t n, const mpm_pin_t* pins) try {
     }
     e->pin.set.assign(pins, pins + n);
     e->pin.table_dirty = true;
-    e->pin.version += 1;
     return 0;
 } MPM_CATCH_ALL
 
@@ -3152,7 +3022,6 @@ int mpm_set_body_motions(mpm_handle_t e, size_t n, const mpm_body_motion_t* m) t
     }
     HIP_TRY(hipStreamSynchronize(e->stream));
     ps.table_dirty = true;   // (a pin whose body has just got its first motion is resolved at the next substep)
-    ps.version += 1;
     return 0;
 } MPM_CATCH_ALL
 
@@ -3186,7 +3055,6 @@ int mpm_pins_inside_collider(mpm_handle_t e, const mpm_collider_t* shape, uint32
     REQUIRE(!add.empty(), "no vertex that is not pinned already lies inside the shape");
     ps.set.insert(ps.set.end(), add.begin(), add.end());
     ps.table_dirty = true;
-    ps.version += 1;
     if (n_added) *n_added = add.size();
     return 0;
 } MPM_CATCH_ALL

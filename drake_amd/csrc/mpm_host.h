@@ -114,9 +114,8 @@ struct mpm_engine {
     float last_dt = 0.f;   // length of the last substep (anticipatory binning of the re-sort)
     // gated substeps of mpm_run_substeps (see gated_out in mpm_step.h)
     // the re-sort launches precede every check_every-th substep of mpm_run_substeps (1 = all); read from
-    // MPM_RESORT_EVERY when the engine is created, like graph_len (MPM_GRAPH): per handle, not per process
+    // MPM_RESORT_EVERY when the engine is created: per handle, not per process
     int check_every = 4;
-    int graph_len = 0;         // > 0: mpm_run_substeps replays captured graphs of this many substeps
     unsigned step_phase = 0;
     bool force_check = true;   // the next substep gets them whatever its number (after any other call)
     float quiet_left = 0.f;    // seconds of Ctl::quiet_time left as of the last settle() (0: unknown)
@@ -127,7 +126,6 @@ struct mpm_engine {
         float dt = 0.f;
         int bc = 0;
     } pend;
-    int chain_lean = 0;             // mpm_chain_substeps: another substep of the batch follows (DP::lean_g2p)
     bool defer_phases = true;       // MPM_DEFER_PHASES=0: every phase call launches its kernels at once
     uint64_t checks_launched = 0;   // (diagnostics)
     Ctl* h_ctl = nullptr;           // pinned landing place of the control block (settle)
@@ -190,11 +188,6 @@ struct mpm_engine {
     unsigned g_rb = 2048;  // workgroups of the particle-parallel re-sort kernels
     int grid_state = 0;  // 0 nothing, 1 slabs valid (after P2G), 2 grid updated
     uint64_t substeps = 0;
-    // one captured substep (run_substeps replays it): launch arguments are all by-value constants
-    hipGraphExec_t step_graph = nullptr;
-    float step_graph_dt = 0.f;
-    int step_graph_bc = 0;
-    uint64_t step_graph_gcv = 0;
     // analytic colliders of the grid update selected by mpm_bc = MPM_BC_TABLE (mpm_set_grid_colliders)
     GridColliders grid_colliders{};
     uint64_t grid_colliders_version = 0;
@@ -208,21 +201,7 @@ struct mpm_engine {
         size_t cap_mot = 0;
         unsigned* d_ticket = nullptr;
         bool table_dirty = false;                // d_pins is not `set` yet (resolved at the next substep entry point)
-        uint64_t version = 0;                    // every change (captured graphs carry the launch arguments)
     } pin;
-    uint64_t step_graph_pinv = 0;
-    long long* step_graph_acc = nullptr;
-    size_t step_graph_nb = 0;
-    int step_graph_len = 1;
-    hipStream_t step_graph_stream = nullptr;
-    // the two halves of the multi-GPU substep as replayable graphs (host enqueue time matters there)
-    // (one pair per parity of the direct transport's receive slots: its buffer addresses alternate with every substep,
-    // and a single cached graph would be re-captured every time -- ADVICE r5)
-    struct KeyedGraph {
-        hipGraphExec_t exec = nullptr;
-        std::vector<uint64_t> key;
-    } halo_graph[4];
-    int halo_graph_parity = 0;   // which pair the next begin / end halo call replays (mpm_chain_substeps, direct transport)
     int max_valence = 0;       // most faces around one vertex of the mesh (Finalize): above 8, k_vforce stays (see fused_forces)
     int last_tile_kernel = 0;  // 1 = P2G, 2 = G2P (see launch_p2g)
     // launch geometry
@@ -234,7 +213,6 @@ struct mpm_engine {
     bool last_contact_exact = false;
     bool last_contact_gated = false;      // ... skipped itself with its whole substep (CT_DONE_GATED)
     float ct_quiet_left = 0.f;            // Ctl::quiet_time left as of the last solve's publication
-    std::function<void()> ct_before_impulse;   // (mpm_run_coupled_substeps) launched between the solve's last update and its impulses
     bool last_contact_reused = false;     // ... ran on the previous solve's sorted order and node list (settled scene)
     // MPM_CT_NO_REUSE=1: every solve runs the full set-up (sort, per-cell runs, node list), also when the pair list repeats
     bool ct_no_reuse = getenv("MPM_CT_NO_REUSE") != nullptr;
@@ -288,8 +266,6 @@ struct mpm_engine {
     bool poison() const { return poison_fill; }
     // MPM_ANTICIPATE: horizon (substeps) of the re-sort's anticipatory binning (launch_rebuild)
     float anticipate_horizon = getenv("MPM_ANTICIPATE") ? (float)atof(getenv("MPM_ANTICIPATE")) : 32.f;
-    // MPM_HALO_GRAPH=1: the two halves of a chain substep are replayed from captured graphs
-    bool use_halo_graphs = getenv("MPM_HALO_GRAPH") != nullptr && atoi(getenv("MPM_HALO_GRAPH")) != 0;
     // MPM_CT_EAGER=1: the contact solve applies every accepted step with a kernel of its own (update_contact)
     bool ct_eager = getenv("MPM_CT_EAGER") != nullptr;
     // MPM_CT_RELAX: Jacobi relaxation of the contact solve instead of the reference's 0.3 (tests: overshoot on purpose)

@@ -57,7 +57,7 @@ MPM_DEV void pin_pose(const BodyMotionDev& m, double t, double* pt, double* Rt) 
     }
 }
 
-// One lane per pin, behind k_g2p on the same stream (launch_g2p_with).  Honours k_g2p's gate: a substep that skipped
+// One lane per pin, behind k_g2p on the same stream (launch_g2p).  Honours k_g2p's gate: a substep that skipped
 // itself neither moves a pin nor advances a clock.
 __global__ __launch_bounds__(256) void k_pin(DP p, PinArgs a, float dt) {
     __shared__ unsigned long long s_acc[CT_LDS_BODIES][6];
