@@ -251,8 +251,13 @@ MPM_API int mpm_grid_collider_preset(int mpm_bc, float sdf_friction, mpm_grid_co
 /* GpuMpmSolver::GridToParticle (cuda_mpm_solver.cu:153-161). */
 MPM_API int mpm_grid_to_particle(mpm_handle_t h, float dt);
 
-/* GpuMpmSolver::GpuSync (cuda_mpm_solver.cu:163-166); also surfaces sticky
- * device error flags as MPM_ERR_DRIFT / MPM_ERR_CAPACITY / MPM_ERR_DOMAIN. */
+/* GpuMpmSolver::GpuSync (cuda_mpm_solver.cu:163-166); also surfaces the sticky
+ * device error flags, checked in this order: MPM_ERR_DRIFT, MPM_ERR_DOMAIN,
+ * MPM_ERR_HALO (partitioned domain), MPM_ERR_RANGE (a ParticleToGrid node sum
+ * was not finite, or left the fixed-point range of a deterministic engine) and
+ * MPM_ERR_CAPACITY (a table or the slab pool overflowed).  A failure of the
+ * HIP runtime while it runs owed substeps or synchronises is MPM_ERR_HIP
+ * (MPM_ERR_NOMEM, MPM_ERR_INTERNAL as for every call). */
 MPM_API int mpm_sync(mpm_handle_t h);
 
 /* GpuMpmSolver::GpuSync() as the reference declares and calls it -- no state argument, a
