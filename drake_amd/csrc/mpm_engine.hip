@@ -288,7 +288,7 @@ static void launch_pins(mpm_engine* e, const DP& p, float dt) {
 // (`p` may carry a halo class restriction: only an engine without pins splits GridToParticle, see extensions_refused)
 static void launch_g2p(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:GridToParticle");
-    hipLaunchKernelGGL(k_g2p, dim3(std::min(768u, p.capI) * G2P_SPLIT), dim3(G2P_THREADS), 0, e->stream, p, dt);
+    hipLaunchKernelGGL(k_g2p, dim3(std::min(768u, p.capI)), dim3(G2P_THREADS), 0, e->stream, p, dt);
     if (!e->pin.set.empty() && p.halo_cls < 0) launch_pins(e, p, dt);
     e->last_tile_kernel = 2;
 }

@@ -37,7 +37,7 @@
     // partitioned domain: the sign of q[0].w is the particle's role (ghost copies are negative) and changes
     // with migration; a single-domain engine never looks at the face particle's own record
     const float volw = MPM_FEM_VOLW;
-    if (MPM_FEM_SETPRIO) __builtin_amdgcn_s_setprio(2);   // (a wave that has its data computes and stores ahead of waves still issuing loads)
+    __builtin_amdgcn_s_setprio(2);   // (a wave that has its data computes and stores ahead of waves still issuing loads)
     const float x0[3] = {xa.x, xa.y, xa.z}, x1[3] = {xb.x, xb.y, xb.z}, x2[3] = {xc.x, xc.y, xc.z};
     // the face particle sits at the centroid and moves with the mean velocity (:203-207);
     // vol and C8 ride along unchanged

@@ -8,23 +8,6 @@
 #pragma once
 #include "mpm_device.h"
 
-// (A/B switches used before their kernels are defined: all at the top, an undefined macro in an #if reads as 0)
-#ifndef MPM_P2G_PEEL
-#define MPM_P2G_PEEL 0
-#endif
-#ifndef MPM_FEM_SETPRIO
-#define MPM_FEM_SETPRIO 1    // (A/B switch, round 4: no difference measured)
-#endif
-#ifndef MPM_G2P_ZPAIR
-// the z components of the tile nodes broadcast by the packed instructions' operand select from the (z, m) pair (inline
-// assembly: the compiler loads 12 bytes per node and then moves every z into a pair of its own): 27 moves less per
-// particle, k_g2p 21.85 -> 20.95 us (event time, same box)
-#define MPM_G2P_ZPAIR 1
-#endif
-#ifndef MPM_G2P_PREFETCH
-#define MPM_G2P_PREFETCH 1   // 0 (experiment): a particle's position is loaded when its turn comes
-#endif
-
 namespace mpm {
 
 // ---------------------------------------------------------------------------
@@ -156,7 +139,7 @@ __global__ __launch_bounds__(256) void k_vforce(DP p) {
 //   2. the wave groups its 64 particles by base cell (ballot loop, ranks by v_mbcnt) and stages
 //      them in a wave-private LDS area,
 //   3. per cell: 4 particles per MFMA step, 2 MFMAs per step (nodes 0-15 and 16-26).  Since round 6 the staged
-//      columns are the A operand and the weights the B operand (MPM_P2G_SWAP): a lane's four accumulator registers
+//      columns are the A operand and the weights the B operand: a lane's four accumulator registers
 //      are then the four TERMS (1, i, j, k) of one (node, component), folded in the lane with 4 products and 3
 //      sums -- rounds 1-5 had nodes as rows and folded across a quad with DPP -- and added to the tile: 2 LDS
 //      atomics (64 distinct words each) per cell, doubles or 64-bit fixed point (EXACT).
@@ -166,24 +149,9 @@ __global__ __launch_bounds__(256) void k_vforce(DP p) {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// A/B switches of the round-3 P2G experiments (defaults = what ships; scratch/ab_build.py builds variants,
-// scratch/ab_run.py times them on one box; results in DESIGN_HISTORY.md section 8)
-#ifndef MPM_P2G_STG16
-#define MPM_P2G_STG16 1
-#endif
-#if MPM_P2G_STG16
 // staged floats per particle: the 13 columns of Y that carry numbers, then fx, fy, fz in the three columns of the
 // mass component that Y leaves empty (their products are discarded by a zero in `fac`)
 constexpr int STG = 16, STG_FX = 13;
-#else
-constexpr int STG = 20, STG_FX = 16;  // 16 columns of Y, fx, fy, fz, pad
-#endif
-
-template <int CTRL>
-MPM_DEV float quad_perm(float v) {
-    return __builtin_bit_cast(float,
-                              __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
 
 // LDS accumulation is done in 64-bit fixed point: on gfx950 a wave-wide ds_add_f32
 // costs ~190 LDS cycles per instruction (measured, scratch/lds_atomic_bench.hip)
@@ -245,8 +213,7 @@ MPM_DEV Stencil make_stencil(const DP& p, float x, float y, float z, int ox, int
 }
 
 // neighbour blocks (27-bit set) reached by the 3^3 stencil of base cell (rx, ry, rz) of a tile
-// (an outer product of three 3-bit sets, formed with shifts and masks: this runs on the scalar unit once
-// per cell group of every wave, and the scalar unit is shared by the 16 waves of a CU)
+// (an outer product of three 3-bit sets, formed with shifts and masks; k_p2g tabulates it per lane at its start)
 MPM_DEV unsigned tile_reach_mask(int rx, int ry, int rz) {
     // Per axis the stencil of base cell r in 0..7 (tile coordinates, block origin at FREE_ZONE = 2) reaches the
     // block offsets {-1,0}, {0}, {0,+1}, {+1} for r >> 1 = 0, 1, 2, 3: as 3-bit sets 3, 2, 6, 4.
@@ -262,45 +229,8 @@ MPM_DEV unsigned tile_reach_mask(int rx, int ry, int rz) {
     return rep & xexp;
 }
 
-#ifndef MPM_P2G_WAVES
-#define MPM_P2G_WAVES 8
-#endif
-#ifndef MPM_P2G_SETPRIO
-#define MPM_P2G_SETPRIO 1
-#endif
-#ifndef MPM_P2G_DYNAMIC
-#define MPM_P2G_DYNAMIC 0   // 1 (experiment): the waves of a workgroup take the item's groups from an LDS counter
-#endif
-#ifndef MPM_P2G_DESC_AHEAD
-// the group descriptor alone fetched a group ahead (4 registers): nothing with the vertex forces in a prologue (49.2 vs
-// 49.3 us); with the lazy forces a group's chain is descriptor -> adjacency -> corner records, and it is worth 1 us
-#define MPM_P2G_DESC_AHEAD 1
-#endif
-#ifndef MPM_P2G_PIPE2
-#define MPM_P2G_PIPE2 0      // 1 (experiment): MFMA operands fetched two steps ahead in two named register sets
-#endif
-#ifndef MPM_P2G_SWAP
-// 1 (round 6): the contraction transposed -- the particles' 16 columns are the A operand of the MFMA and the 27 weights the
-// B operand, so that a lane's four accumulator registers are the four TERMS (1, i, j, k) of one (node, component) instead of
-// four node rows of one term: the fold over the terms is four products and three sums in the lane (same pairing as the
-// quad exchange it replaces: bit-identical) instead of 4 + 6 selects + 3 DPP adds, per cell and MFMA.
-#define MPM_P2G_SWAP 1
-#endif
-#ifndef MPM_P2G_REACH_TABLE
-#define MPM_P2G_REACH_TABLE 1   // (round 6) the reach mask of a cell read from a per-lane table instead of ~25 scalar instructions
-#endif
-#ifndef MPM_P2G_LOOP3
-#define MPM_P2G_LOOP3 1   // (round 6) first / middle / last steps of a cell as three bodies, see the contraction loop
-#endif
-#ifndef MPM_P2G_PREFETCH
-// 0 (what ships since round 4): a group's records are loaded when its turn comes.  Rounds 1-3 fetched them one group
-// ahead; with four waves per SIMD the other waves cover the two round trips anyway, and the 25 registers the prefetched
-// records occupied through the contraction cost more than the wait: 128 VGPRs + 12 bytes of scratch -> 103, none;
-// k_p2g 51.6 -> 49.4 us (event time), 20-substep window 105.0 -> 101.5 us (same-box A/B, scratch/ab_run.py).
-#define MPM_P2G_PREFETCH 0
-#endif
-constexpr int P2G_WAVES = MPM_P2G_WAVES, P2G_THREADS = 64 * P2G_WAVES;
-// two workgroups per CU: 8 waves each at <= 128 VGPRs (4 per SIMD), or 10 at <= 96 (5 per SIMD; -DMPM_P2G_WAVES=10)
+constexpr int P2G_WAVES = 8, P2G_THREADS = 64 * P2G_WAVES;
+// two workgroups per CU: 8 waves each at <= 128 VGPRs (4 per SIMD)
 // FORCES: where a vertex lane finds the internal force on its vertex.
 //   0  in p.f (k_vforce ran before this kernel: the phase-by-phase API, meshes with a vertex of more than eight faces)
 //   1  in the eight planes of DP::VF, summed here (one round trip of coalesced loads; a partitioned domain went through
@@ -319,13 +249,9 @@ constexpr int P2G_WAVES = MPM_P2G_WAVES, P2G_THREADS = 64 * P2G_WAVES;
 //      in magnitude; beyond that its LAST bit (2^-53 of the sum, rounded to float afterwards) may depend on the order.
 //      The default: without the canonical particle order of deterministic mode the order INSIDE a cell already
 //      differs from run to run at float level.
-// one step of the per-cell contraction: acc += W^T Y (MPM_P2G_SWAP: rows = the 16 columns of the staged particles,
-// columns = 16 node rows) or acc += W Y^T (rows = nodes)
-#if MPM_P2G_SWAP
-#define MPM_P2G_MFMA(w, y, acc) __builtin_amdgcn_mfma_f32_16x16x4f32(y, w, acc, 0, 0, 0)
-#else
-#define MPM_P2G_MFMA(w, y, acc) __builtin_amdgcn_mfma_f32_16x16x4f32(w, y, acc, 0, 0, 0)
-#endif
+// one step of the per-cell contraction: rows = the 16 columns of the staged particles (A operand), columns = 16 node
+// rows (B operand); the transposed form of round 6, see point 3 above and DESIGN.md section 3.2
+MPM_DEV f32x4 p2g_mfma(float y, float w, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(y, w, acc, 0, 0, 0); }
 template <int FORCES, int EXACT>
 __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G_WAVES / 2, P2G_WAVES / 2))) void k_p2g(DP p, float dt) {
     if (gated_out(p)) return;
@@ -335,9 +261,6 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
     // wave-private staging: 64 particles (+8 slack rows touched by the operand prefetch)
     __shared__ __attribute__((aligned(16))) float stage_all[P2G_WAVES][(64 + 8) * STG];
     __shared__ unsigned s_mask;
-#if MPM_P2G_DYNAMIC
-    __shared__ int s_next;   // next unclaimed group of the item (waves take groups as they finish, not round robin)
-#endif
     static_assert(sizeof(long long) * TILE_N * 4 + sizeof(float) * P2G_WAVES * (64 + 8) * STG + 4 <= 81920,
                   "two workgroups per CU need <= 80 KB of LDS each");
     Ctl* ctl = p.ctl;
@@ -348,9 +271,8 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
     float* stage = stage_all[wv];
 
     // ---- lane constants of the contraction ---------------------------------
-    const int j16 = lane & 15, g4 = lane >> 4, tt = lane & 3, dcomp = (lane >> 2) & 3;
-    (void)tt; (void)dcomp;   // (only the untransposed contraction, MPM_P2G_SWAP=0, uses them)
-    float ax[2][3], ay[2][3], az[2][3];  // A operand: weight polynomials of node rows j16 and 16 + j16
+    const int j16 = lane & 15, g4 = lane >> 4;
+    float ax[2][3], ay[2][3], az[2][3];  // B operand: weight polynomials of node rows j16 and 16 + j16
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
         const int n = 16 * t + j16;
@@ -362,45 +284,31 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
     const f32x2 cx0 = {ax[0][0], ax[1][0]}, cx1 = {ax[0][1], ax[1][1]}, cx2 = {ax[0][2], ax[1][2]};
     const f32x2 cy0 = {ay[0][0], ay[1][0]}, cy1 = {ay[0][1], ay[1][1]}, cy2 = {ay[0][2], ay[1][2]};
     const f32x2 cz0 = {az[0][0], az[1][0]}, cz1 = {az[0][1], az[1][1]}, cz2 = {az[0][2], az[1][2]};
-    // epilogue: (1, i, j, k)[tt] of node row 16 t + 4 g4 + r, times the fixed-point scale of this lane's
-    // component (a power of two: scaling before or after the sums gives the same bits)
+    // epilogue: (1, i, j, k)[r] of node 16 t + j16, times the fixed-point scale of this lane's component g4 (a power
+    // of two: scaling before or after the sums gives the same bits)
     float fac[2][4];
     int delta[2];        // float offset of this lane's node/component in the tile, -1 if none
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-#if MPM_P2G_SWAP
         // lane (j16, g4) of MFMA t ends up with the four terms of node 16 t + j16, component g4
         const int n = 16 * t + j16;
         const int ni = n / 9, nj = (n / 3) % 3, nk = n % 3;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             fac[t][r] = n >= 27 ? 0.f : (r == 0 ? 1.f : (float)(r == 1 ? ni : (r == 2 ? nj : nk)));
-            if (MPM_P2G_STG16 && g4 == 3 && r != 0) fac[t][r] = 0.f;   // (columns 13..15 carry fx, fy, fz)
+            if (g4 == 3 && r != 0) fac[t][r] = 0.f;   // (columns 13..15 carry fx, fy, fz)
         }
         delta[t] = n < 27 ? ((ni * TILE_W + nj) * TILE_W + nk) * 4 + g4 : -1;
-#else
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int n = 16 * t + 4 * g4 + r;
-            const int ni = n / 9, nj = (n / 3) % 3, nk = n % 3;
-            fac[t][r] = n >= 27 ? 0.f : (tt == 0 ? 1.f : (float)(tt == 1 ? ni : (tt == 2 ? nj : nk)));
-            if (MPM_P2G_STG16 && dcomp == 3 && tt != 0) fac[t][r] = 0.f;   // (columns 13..15 carry fx, fy, fz)
-        }
-        const int n = 16 * t + 4 * g4 + tt;
-        delta[t] = n < 27 ? (((n / 9) * TILE_W + (n / 3) % 3) * TILE_W + n % 3) * 4 + dcomp : -1;
-#endif
     }
     {
-        const float fscale = EXACT ? (float)((MPM_P2G_SWAP ? g4 : dcomp) == 3 ? p.fix_m : p.fix_p) : 1.f;
+        const float fscale = EXACT ? (float)(g4 == 3 ? p.fix_m : p.fix_p) : 1.f;
 #pragma unroll
         for (int t = 0; t < 2; ++t)
 #pragma unroll
             for (int r = 0; r < 4; ++r) fac[t][r] *= fscale;
     }
-#if MPM_P2G_REACH_TABLE
     // lane l = (ix, iy, iz) in 2-bit fields: the neighbour blocks reached from base cells (2 ix.., 2 iy.., 2 iz..) of the tile
     const unsigned reach_of_lane = tile_reach_mask(2 * (lane >> 4), 2 * ((lane >> 2) & 3), 2 * (lane & 3));
-#endif
     // A step reads 4 staged rows; rows that do not belong to the cell (the next cell's particles,
     // rows never written) are masked in the B operand only, so every row must hold finite numbers
     for (int k = lane; k < (64 + 8) * STG; k += 64) stage[k] = 0.f;
@@ -417,9 +325,6 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
         const unsigned long long tb0 = (diag_flags(p) & 4) ? __builtin_readcyclecounter() : 0ull;
         for (int n = tid; n < TILE_N * 4; n += P2G_THREADS) tile[n] = 0;
         if (tid == 0) s_mask = 0;
-#if MPM_P2G_DYNAMIC
-        if (tid == 0) s_next = P2G_WAVES;
-#endif
         int bx, by, bz;
         block_coords((uint32_t)fa.z, bx, by, bz);
         const int ox = bx * 4 - FREE_ZONE, oy = by * 4 - FREE_ZONE, oz = bz * 4 - FREE_ZONE;
@@ -443,8 +348,8 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
 #pragma unroll
             for (int d = 0; d < 3; ++d) f[d] = fbase[(size_t)d * p.f_stride];
         };
-        // a group's descriptor is fetched one group ahead of its records (which are fetched one group ahead of their
-        // use): no dependent round trip in front of the record loads
+        // a group's descriptor is fetched one group ahead of its records: no dependent round trip in front of the record
+        // loads (45.3 -> 43.9 us once the vertex forces came with the records; DESIGN_HISTORY.md section 3.2)
         auto desc_of = [&](int g) { return groups[min(g, ngroups - 1)]; };
         int4 gd_next = make_int4(0, 0, 0, 0);
         auto load_raw = [&](int4 gr) {
@@ -489,37 +394,17 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
         unsigned mymask = 0;
         bool halo_bad = false;
         unsigned out_worst = 0, fix_worst = 0;   // error conditions, collected as integers in vector registers
-        if (MPM_P2G_PREFETCH && wv < ngroups) {
-            cur = load_raw(desc_of(wv));
-            gd_next = desc_of(wv + P2G_WAVES);
-        }
-        // (without the record prefetch only the group DESCRIPTOR is fetched a group ahead: four registers, and the
-        // records' loads no longer wait for a dependent round trip)
-        if (!MPM_P2G_PREFETCH && MPM_P2G_DESC_AHEAD && wv < ngroups) gd_next = desc_of(wv);
+        if (wv < ngroups) gd_next = desc_of(wv);
         const bool prof = (diag_flags(p) & 4) != 0 && wv == 0;
         unsigned long long tq[3] = {0, 0, 0}, pc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         if (prof && lane == 0) atomicAdd(&p.dbgbuf[14], (unsigned long long)__builtin_readcyclecounter() - tb0);   // prologue
-#if MPM_P2G_DYNAMIC
-        static_assert(!MPM_P2G_PREFETCH, "dynamic group assignment has no place for a prefetched group");
-        auto next_group = [&]() {
-            int n = 0;
-            if (lane == 0) n = atomicAdd(&s_next, 1);
-            return __builtin_amdgcn_readfirstlane(n);
-        };
-        for (int g = wv; g < ngroups; g = next_group()) {
-#else
         for (int g = wv; g < ngroups; g += P2G_WAVES) {
-#endif
-            // ---- 1. one particle per lane (its raw state was prefetched) ----------
+            // ---- 1. one particle per lane ---------------------------------------
+            // (a group's records are loaded when its turn comes: fetched a group ahead, as in rounds 1-3, they held 25
+            // registers through the contraction, 128 VGPRs + scratch, and cost more than the wait)
             if (prof) tq[0] = __builtin_readcyclecounter();
-            if (!MPM_P2G_PREFETCH) {
-                if (MPM_P2G_DESC_AHEAD) {
-                    cur = load_raw(gd_next);
-                    gd_next = desc_of(g + P2G_WAVES);
-                } else {
-                    cur = load_raw(desc_of(g));
-                }
-            }
+            cur = load_raw(gd_next);
+            gd_next = desc_of(g + P2G_WAVES);
             const bool act = cur.act, is_face = cur.is_face;
             const Stencil st = make_stencil(p, cur.x[0], cur.x[1], cur.x[2], ox, oy, oz);
             // partitioned domain: a ghost copy (vol < 0) scatters nothing, its owner does
@@ -565,12 +450,6 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
                 const int gx = ox + st.rx;
                 halo_bad |= gx < p.dist.own_lo - p.dist.zone_cells || gx + 2 >= p.dist.own_hi + p.dist.zone_cells;
             }
-            // the raw registers are dead now: start the next group's loads, they complete while this
-            // group goes through the LDS / matrix-pipe phases below (which never wait on vmcnt)
-            if (MPM_P2G_PREFETCH && g + P2G_WAVES < ngroups) {
-                cur = load_raw(gd_next);
-                gd_next = desc_of(g + 2 * P2G_WAVES);
-            }
             if (diag_flags(p) & 2) {
                 float acc = 0.f;
 #pragma unroll
@@ -604,12 +483,7 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
                 sp[0] = make_float4(Y[0], Y[1], Y[2], Y[3]);
                 sp[1] = make_float4(Y[4], Y[5], Y[6], Y[7]);
                 sp[2] = make_float4(Y[8], Y[9], Y[10], Y[11]);
-#if MPM_P2G_STG16
                 sp[3] = make_float4(Y[12], st.fx[0], st.fx[1], st.fx[2]);
-#else
-                sp[3] = make_float4(Y[12], Y[13], Y[14], Y[15]);
-                sp[4] = make_float4(st.fx[0], st.fx[1], st.fx[2], 0.f);
-#endif
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -618,56 +492,13 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
             // ---- 4. per-cell contraction on the matrix pipe ----------------------
             unsigned long long todo = actmask;
             int s0 = 0;
-#if MPM_P2G_PIPE2
-            // Operands two steps deep: set A feeds step s, set B step s + 4; A is re-loaded (for s + 8) while B's step
-            // computes and the other way round, so every LDS read has a whole step of arithmetic to arrive in.  The
-            // two sets are named, not rotated: no moves.  Rows beyond the staged ones are clamped to the last row
-            // (they are masked in the B operand anyway).
-            float afx, afy, afz, ay, bfx, bfy, bfz, by;
-            auto ld = [&](int row, float& fx_, float& fy_, float& fz_, float& y_) {
-                const float* sn = stage + min(row + g4, 64 + 8 - 1) * STG;
-                fx_ = sn[STG_FX]; fy_ = sn[STG_FX + 1]; fz_ = sn[STG_FX + 2]; y_ = sn[j16];
-            };
-            ld(0, afx, afy, afz, ay);
-            ld(4, bfx, bfy, bfz, by);
-            if (prof) tq[1] = __builtin_readcyclecounter();
-            __builtin_amdgcn_s_setprio(2);
-            while (todo) {
-                const int ckey = __builtin_amdgcn_readlane(key, __builtin_ctzll(todo));
-                const unsigned long long same = __ballot(key == ckey) & todo;
-                todo &= ~same;
-                const int s1 = s0 + (int)__popcll(same);
-                f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-                if (prof) { pc[4] += 1; pc[5] += (unsigned)((s1 - s0 + 3) >> 2); tq[2] = __builtin_readcyclecounter(); }
-                auto step = [&](int s, float fx, float fy, float fz, float y) {
-                    const bool ok = s + g4 < s1;
-                    const f32x2 fx2 = {fx, fx}, fy2 = {fy, fy}, fz2 = {fz, fz};
-                    const f32x2 w01 = __builtin_elementwise_fma(__builtin_elementwise_fma(cx2, fx2, cx1), fx2, cx0) *
-                                      __builtin_elementwise_fma(__builtin_elementwise_fma(cy2, fy2, cy1), fy2, cy0) *
-                                      __builtin_elementwise_fma(__builtin_elementwise_fma(cz2, fz2, cz1), fz2, cz0);
-                    if (!ok) y = 0.f;
-                    acc0 = MPM_P2G_MFMA(w01.x, y, acc0);
-                    acc1 = MPM_P2G_MFMA(w01.y, y, acc1);
-                };
-                for (int s = s0; s < s1; s += 8) {
-                    step(s, afx, afy, afz, ay);
-                    if (s + 8 < s1) ld(s + 8, afx, afy, afz, ay);
-                    if (s + 4 < s1) {
-                        step(s + 4, bfx, bfy, bfz, by);
-                        if (s + 12 < s1) ld(s + 12, bfx, bfy, bfz, by);
-                    }
-                }
-                // the next cell starts at s1: its first two steps' operands arrive during this cell's epilogue
-                ld(s1, afx, afy, afz, ay);
-                ld(s1 + 4, bfx, bfy, bfz, by);
-#else
             float nfx, nfy, nfz, ny;
             {
                 const float* sn = stage + g4 * STG;
                 nfx = sn[STG_FX]; nfy = sn[STG_FX + 1]; nfz = sn[STG_FX + 2]; ny = sn[j16];
             }
             if (prof) tq[1] = __builtin_readcyclecounter();
-            if (MPM_P2G_SETPRIO) __builtin_amdgcn_s_setprio(2);   // (waves in the contraction keep the matrix pipe fed: ahead of waves that derive / group)
+            __builtin_amdgcn_s_setprio(2);   // (waves in the contraction keep the matrix pipe fed: ahead of waves that derive / group)
             while (todo) {
                 const int ckey = __builtin_amdgcn_readlane(key, __builtin_ctzll(todo));
                 const unsigned long long same = __ballot(key == ckey) & todo;
@@ -675,107 +506,55 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
                 const int s1 = s0 + (int)__popcll(same);
                 f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
                 if (prof) { pc[4] += 1; pc[5] += (unsigned)((s1 - s0 + 3) >> 2); tq[2] = __builtin_readcyclecounter(); }
-                // operands of a step are fetched one step ahead (the first step's during the previous
-                // cell's epilogue), so the LDS latency hides behind the MFMAs
-#if !MPM_P2G_LOOP3
-                auto one_step = [&](int s, bool first_step) {
-                    const bool ok = g4 < s1 - s;   // (rows of this cell; the difference is wave-uniform: one vector instruction)
+                // Operands of a step are fetched one step ahead (the first step's during the previous cell's epilogue), so
+                // the LDS latency hides behind the MFMAs.  Three kinds of step: the first accumulates onto the inline
+                // constant 0 (no eight moves to clear the accumulators of every cell), only the last one has rows of the
+                // NEXT cell to mask (a cell's rows are contiguous: every row of an earlier step is the cell's own).
+                auto step = [&](int s, bool first_step, bool last_step) {
                     const float fx = nfx, fy = nfy, fz = nfz;
                     float y = ny;
                     {
                         const float* sn = stage + (s + 4 + g4) * STG;
                         nfx = sn[STG_FX]; nfy = sn[STG_FX + 1]; nfz = sn[STG_FX + 2]; ny = sn[j16];
                     }
-                    // both rows' weights in one chain of packed operations (v_pk_fma_f32: the same fused
-                    // multiply-adds as two scalar chains, half the issue slots)
+                    // both rows' weights in one chain of packed operations (v_pk_fma_f32: the same fused multiply-adds
+                    // as two scalar chains, half the issue slots)
                     const f32x2 fx2 = {fx, fx}, fy2 = {fy, fy}, fz2 = {fz, fz};
                     const f32x2 w01 = __builtin_elementwise_fma(__builtin_elementwise_fma(cx2, fx2, cx1), fx2, cx0) *
                                       __builtin_elementwise_fma(__builtin_elementwise_fma(cy2, fy2, cy1), fy2, cy0) *
                                       __builtin_elementwise_fma(__builtin_elementwise_fma(cz2, fz2, cz1), fz2, cz0);
-                    float w0 = w01.x, w1 = w01.y;
-                    if (diag_flags(p) & 128) { w0 = fx; w1 = fy; }
-                    if (!ok) y = 0.f;   // (weights of foreign rows are finite: 0 * w = 0)
-                    if (diag_flags(p) & 64) {
-                        acc0[0] = fmaf(w0, y, acc0[0]);
-                        acc1[0] = fmaf(w1, y, acc1[0]);
-                    } else if (MPM_P2G_PEEL && first_step) {
-                        // (the first step of a cell accumulates onto the constant 0 -- an inline operand of the MFMA --
-                        // instead of onto eight registers that have to be cleared first)
+                    if (last_step && !(g4 < s1 - s)) y = 0.f;   // (weights of foreign rows are finite: 0 * w = 0)
+                    if (first_step) {
                         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                        acc0 = MPM_P2G_MFMA(w0, y, zero);
-                        acc1 = MPM_P2G_MFMA(w1, y, zero);
+                        acc0 = p2g_mfma(y, w01.x, zero);
+                        acc1 = p2g_mfma(y, w01.y, zero);
                     } else {
-                        acc0 = MPM_P2G_MFMA(w0, y, acc0);
-                        acc1 = MPM_P2G_MFMA(w1, y, acc1);
+                        acc0 = p2g_mfma(y, w01.x, acc0);
+                        acc1 = p2g_mfma(y, w01.y, acc1);
                     }
                 };
-#endif
-#if MPM_P2G_LOOP3
-                {
-                    // Three kinds of step: the first accumulates onto the inline constant 0 (no eight moves to clear the
-                    // accumulators of every cell), only the last one has rows of the NEXT cell to mask (a cell's rows are
-                    // contiguous: every row of an earlier step is the cell's own).  Same operations on the same operands.
-                    auto step3 = [&](int s, bool first_step, bool last_step) {
-                        const float fx = nfx, fy = nfy, fz = nfz;
-                        float y = ny;
-                        {
-                            const float* sn = stage + (s + 4 + g4) * STG;
-                            nfx = sn[STG_FX]; nfy = sn[STG_FX + 1]; nfz = sn[STG_FX + 2]; ny = sn[j16];
-                        }
-                        const f32x2 fx2 = {fx, fx}, fy2 = {fy, fy}, fz2 = {fz, fz};
-                        const f32x2 w01 = __builtin_elementwise_fma(__builtin_elementwise_fma(cx2, fx2, cx1), fx2, cx0) *
-                                          __builtin_elementwise_fma(__builtin_elementwise_fma(cy2, fy2, cy1), fy2, cy0) *
-                                          __builtin_elementwise_fma(__builtin_elementwise_fma(cz2, fz2, cz1), fz2, cz0);
-                        if (last_step && !(g4 < s1 - s)) y = 0.f;
-                        if (first_step) {
-                            const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                            acc0 = MPM_P2G_MFMA(w01.x, y, zero);
-                            acc1 = MPM_P2G_MFMA(w01.y, y, zero);
-                        } else {
-                            acc0 = MPM_P2G_MFMA(w01.x, y, acc0);
-                            acc1 = MPM_P2G_MFMA(w01.y, y, acc1);
-                        }
-                    };
-                    const int last = s0 + ((s1 - s0 - 1) & ~3);   // (a cell has at least one particle: s0 < s1)
-                    if (last == s0) {
-                        step3(s0, true, true);
-                    } else {
-                        step3(s0, true, false);
-                        for (int s = s0 + 4; s < last; s += 4) step3(s, false, false);
-                        step3(last, false, true);
-                    }
+                const int last = s0 + ((s1 - s0 - 1) & ~3);   // (a cell has at least one particle: s0 < s1)
+                if (last == s0) {
+                    step(s0, true, true);
+                } else {
+                    step(s0, true, false);
+                    for (int s = s0 + 4; s < last; s += 4) step(s, false, false);
+                    step(last, false, true);
                 }
-#else
-                {
-                    int s = (diag_flags(p) & 8) ? s1 : s0;
-                    if (MPM_P2G_PEEL && s < s1) {   // (a cell has at least one particle: s0 < s1)
-                        one_step(s, true);
-                        s += 4;
-                    }
-                    for (; s < s1; s += 4) one_step(s, false);
-                }
-#endif
                 // the loop leaves row block (last step + 4) preloaded; the next cell starts at s1
-                if (((s1 - s0) & 3) != 0 || (diag_flags(p) & 8)) {
+                if (((s1 - s0) & 3) != 0) {
                     const float* sn = stage + (s1 + g4) * STG;
                     nfx = sn[STG_FX]; nfy = sn[STG_FX + 1]; nfz = sn[STG_FX + 2]; ny = sn[j16];
                 }
-#endif
                 if (prof) { asm volatile("" :: "v"(acc0), "v"(acc1)); const unsigned long long tm = __builtin_readcyclecounter(); pc[2] += tm - tq[2]; tq[2] = tm; }
                 s0 = s1;
-                // rows = nodes, columns = (component d, term tt): fold the 4 terms of each component
                 const int crx = ckey >> 6, cry = (ckey >> 3) & 7, crz = ckey & 7;
-#if MPM_P2G_REACH_TABLE
                 // the mask depends on (rx >> 1, ry >> 1, rz >> 1) only: 64 combinations, one per lane of `reach_of_lane`
                 mymask |= (unsigned)__builtin_amdgcn_readlane((int)reach_of_lane, ((ckey >> 3) & 0x30) | ((ckey >> 2) & 0xC) | ((ckey >> 1) & 3));
-#else
-                mymask |= tile_reach_mask(crx, cry, crz);   // wave-uniform: scalar unit
-#endif
                 long long* tb = tile + ((crx * TILE_W + cry) * TILE_W + crz) * 4;
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const f32x4 a = t ? acc1 : acc0;
-#if MPM_P2G_SWAP
                     // the four terms of this lane's (node, component): products, then the sums paired as (0 + 1) + (2 + 3)
                     float val;
                     {
@@ -783,18 +562,6 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
                         const float x0 = a[0] * fac[t][0], x1 = a[1] * fac[t][1], x2 = a[2] * fac[t][2], x3 = a[3] * fac[t][3];
                         val = (x0 + x1) + (x2 + x3);
                     }
-#else
-                    // Lane (g4, dcomp, tt) of a quad holds the four terms' products of rows r = 0..3 and has to end up
-                    // with the sum over the quad's four lanes of row r = tt: a 4 x 4 transpose-and-add in two
-                    // exchanges (lane ^ 1, then lane ^ 2), each lane passing on what its partner keeps -- 4 + 2
-                    // selects and 3 DPP adds instead of folding all four rows on every lane (8 DPP adds + 4 moves)
-                    // and selecting afterwards.  Same operands in the same order: the sums are bit-identical.
-                    const float x0 = a[0] * fac[t][0], x1 = a[1] * fac[t][1], x2 = a[2] * fac[t][2], x3 = a[3] * fac[t][3];
-                    const bool b0 = (tt & 1) != 0, b1 = (tt & 2) != 0;
-                    const float ua = (b0 ? x1 : x0) + quad_perm<0xB1>(b0 ? x0 : x1);   // row b0, lanes l and l ^ 1
-                    const float ub = (b0 ? x3 : x2) + quad_perm<0xB1>(b0 ? x2 : x3);   // row 2 + b0
-                    const float val = (b1 ? ub : ua) + quad_perm<0x4E>(b1 ? ua : ub);
-#endif
                     if (delta[t] >= 0 && !(diag_flags(p) & 16)) {
                         if (EXACT) lds_add_fixed(tb + delta[t], val, fix_worst);
                         else __hip_atomic_fetch_add(reinterpret_cast<double*>(tb + delta[t]), (double)val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1075,16 +842,7 @@ __global__ __launch_bounds__(256) void k_grid(DP p, GridColliders gc) {
 // G2P
 // ---------------------------------------------------------------------------
 // Stage the (TILE_W)^3 node velocities around a home block into LDS.
-#ifndef MPM_G2P_THREADS
-#define MPM_G2P_THREADS 512
-#endif
-#ifndef MPM_G2P_WAVES
-#define MPM_G2P_WAVES 4
-#endif
-#ifndef MPM_G2P_SPLIT
-#define MPM_G2P_SPLIT 1   // workgroups per work item (each takes every SPLIT-th batch of the item's particles)
-#endif
-constexpr int G2P_THREADS = MPM_G2P_THREADS, G2P_SPLIT = MPM_G2P_SPLIT;
+constexpr int G2P_THREADS = 512, G2P_WAVES = 4;
 constexpr int LOAD_TILE_NQ = (TILE_N + G2P_THREADS - 1) / G2P_THREADS;
 MPM_DEV void load_tile(const DP& p, unsigned h, float4* tile, const float4* field, int nthreads, unsigned long long* stamps = nullptr) {
     const int* nbr = p.home_nbr_act + (size_t)h * 27;
@@ -1150,10 +908,11 @@ MPM_DEV int g2p_particle(const DP& p, const PSet& S, const float4* tile, unsigne
 #pragma unroll
             for (int r = 0; r < 3; ++r) {
                 f32x2 AA;   // (A, Az)[r]
-                if (MPM_G2P_ZPAIR && r == 2) {
+                if (r == 2) {
                     // the z components sit in the low halves of the (z, m) pairs of the three nodes: broadcast by the
                     // instruction's operand select instead of by a move each (the compiler loads 12 bytes per node and
-                    // then has no pair to select from)
+                    // then has no pair to select from): 27 moves less per particle, k_g2p 21.85 -> 20.95 us
+                    // (DESIGN_HISTORY.md section 3.2)
                     const f32x2 z0 = {g0.z, g0.w}, z1 = {g1.z, g1.w}, z2 = {g2.z, g2.w};
                     // (one block with its own wait states between the dependent packed operations: the compiler puts an
                     // s_nop between its own, and must not be relied on to know what is inside an asm statement)
@@ -1222,7 +981,7 @@ MPM_DEV int g2p_particle(const DP& p, const PSet& S, const float4* tile, unsigne
     return bits | (int)!(tx >= guard && tx < top && ty >= guard && ty < top && tz >= guard && tz < top);
 }
 
-__global__ __launch_bounds__(G2P_THREADS) __attribute__((amdgpu_waves_per_eu(MPM_G2P_WAVES, MPM_G2P_WAVES))) void k_g2p(DP p, float dt) {
+__global__ __launch_bounds__(G2P_THREADS) __attribute__((amdgpu_waves_per_eu(G2P_WAVES, G2P_WAVES))) void k_g2p(DP p, float dt) {
     __shared__ float4 tile[TILE_N];
     const Ctl* ctl = p.ctl;
     if (p.gated && ctl->skip_this) {   // (not need_rebuild itself: this kernel raises it while it runs)
@@ -1232,8 +991,7 @@ __global__ __launch_bounds__(G2P_THREADS) __attribute__((amdgpu_waves_per_eu(MPM
     if (blockIdx.x == 0 && threadIdx.x == 0) p.ctl->time_since_resort += dt;   // (see Ctl::quiet_time)
     const PSet& S = p.set[ctl->cur];
     const unsigned n_items = ctl->n_items;
-    for (unsigned vq = blockIdx.x; vq < n_items * G2P_SPLIT; vq += gridDim.x) {
-        const unsigned q = vq / G2P_SPLIT, part = vq % G2P_SPLIT;
+    for (unsigned q = blockIdx.x; q < n_items; q += gridDim.x) {
         __syncthreads();  // everybody is done with the previous tile
         const int4 fa = p.item_flat[2 * q];
         const unsigned h = (unsigned)fa.y;
@@ -1253,7 +1011,7 @@ __global__ __launch_bounds__(G2P_THREADS) __attribute__((amdgpu_waves_per_eu(MPM
         auto slot_of = [&](int u) { return (unsigned)(u < nfb ? rg.x + u : rg.z + (u - nfb)); };
         // the first positions are requested before the tile is staged, later ones one iteration
         // ahead, so the HBM latency of the particle stream hides behind LDS work
-        int u = (int)(threadIdx.x + part * G2P_THREADS);
+        int u = (int)threadIdx.x;
         int left = 0;
         unsigned i = slot_of(u < total ? u : 0);
         float4 pq = S.q[0][i];
@@ -1269,15 +1027,11 @@ __global__ __launch_bounds__(G2P_THREADS) __attribute__((amdgpu_waves_per_eu(MPM
         block_coords((uint32_t)fa.z, bx, by, bz);
         const int ox = bx * 4 - FREE_ZONE, oy = by * 4 - FREE_ZONE, oz = bz * 4 - FREE_ZONE;
 #pragma unroll 1
-        for (; u < total; u += G2P_THREADS * G2P_SPLIT) {
-            if (!MPM_G2P_PREFETCH) {
-                i = slot_of(u);
-                pq = S.q[0][i];
-            }
+        for (; u < total; u += G2P_THREADS) {
             const unsigned ci = i;
             const float4 c = pq;
-            const int un = u + G2P_THREADS * G2P_SPLIT;
-            if (MPM_G2P_PREFETCH && un < total) {
+            const int un = u + G2P_THREADS;
+            if (un < total) {
                 i = slot_of(un);
                 pq = S.q[0][i];
             }

@@ -1,4 +1,4 @@
-// Checks the inline assembly of k_g2p's z broadcast (mpm_step.h, MPM_G2P_ZPAIR) against scalar arithmetic, bit for bit.
+// Checks the inline assembly of k_g2p's z broadcast (mpm_step.h, g2p_particle) against scalar arithmetic, bit for bit.
 // hipcc --offload-arch=gfx950 -O2 -ffp-contract=off scratch/opsel_test.hip -o scratch/opsel_test && scratch/opsel_test
 #include <hip/hip_runtime.h>
 #include <cstdio>

@@ -1,7 +1,6 @@
 """P2G ablations of the diagnostic build (variant library built with -DMPM_DIAG=1): event time of each phase with
 parts of k_p2g switched off by MPM_DBG bits (results are wrong by construction; timing only).
-  2: stop after the per-particle derivation   1: stop after grouping + staging   8: no MFMA steps (cells and
-  epilogues still run)   16: no LDS atomics   64: one FMA instead of each MFMA   128: no weight polynomials"""
+  2: stop after the per-particle derivation   1: stop after grouping + staging   16: no LDS atomics"""
 import json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if len(sys.argv) > 1 and sys.argv[1] == "child":
@@ -19,7 +18,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
             best = dict(ph)
     print(json.dumps({"dbg": int(os.environ.get("MPM_DBG", "0")), **{k: round(v * 1e3, 1) for k, v in best.items()}}))
     sys.exit(0)
-for flags in (0, 128, 16, 2, 1, 8, 0):
+for flags in (0, 16, 2, 1, 0):
     env = dict(os.environ, MPM_DBG=str(flags), MPM_HIP_LIBRARY=os.path.join(ROOT, "drake_amd/variants/libmpm_hip_diag.so"))
     r = subprocess.run([sys.executable, os.path.abspath(__file__), "child"], env=env, capture_output=True, text=True, timeout=300)
     print(r.stdout.strip().splitlines()[-1] if r.stdout.strip() else ("FAILED " + r.stderr[-300:]), flush=True)
