@@ -137,8 +137,8 @@ __global__ __launch_bounds__(256) void k_vforce(DP p) {
 // Every wave works on its own 64-particle groups, without workgroup barriers:
 //   1. every lane loads one particle (four 16-byte records), finds its base cell in the tile and builds its columns,
 //   2. the wave groups its 64 particles by base cell (ballot loop, ranks by v_mbcnt) and stages
-//      them in a wave-private LDS area,
-//   3. per cell: 4 particles per MFMA step, 2 MFMAs per step (nodes 0-15 and 16-26).  Since round 6 the staged
+//      them in a wave-private LDS area, with the products px[i] * py[j] of their B-spline factors,
+//   3. per cell: 4 particles per MFMA step, 2 MFMAs per step (nodes 0-14 and 15-26).  Since round 6 the staged
 //      columns are the A operand and the weights the B operand: a lane's four accumulator registers
 //      are then the four TERMS (1, i, j, k) of one (node, component), folded in the lane with 4 products and 3
 //      sums -- rounds 1-5 had nodes as rows and folded across a quad with DPP -- and added to the tile: 2 LDS
@@ -149,9 +149,13 @@ __global__ __launch_bounds__(256) void k_vforce(DP p) {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-// staged floats per particle: the 13 columns of Y that carry numbers, then fx, fy, fz in the three columns of the
-// mass component that Y leaves empty (their products are discarded by a zero in `fac`)
-constexpr int STG = 16, STG_FX = 13;
+// staged floats per particle (one row of 23): the 13 columns of Y that carry numbers, the nine products px[i] * py[j]
+// of the particle's B-spline factors (index 3 i + j) and fz.  Y[0..7] sit in floats 0..7, the products in 8..16, fz in
+// 17 and Y[8..12] in 18..22: the Y windows of two consecutive rows then fall on disjoint halves of the 32 banks of
+// ds_read_b32 (rows of 23 floats with Y in 0..12 would overlap in four banks).  67 rows per wave: 64 particles and the
+// three rows past them that a step starting at row 61..63 reads (and masks).
+constexpr int STG = 23, STG_PXY = 8, STG_FZ = 17, STG_ROWS = 67;
+MPM_DEV int stg_col(int c) { return c < 8 ? c : c + 10; }   // float of Y[c] in a row
 
 // LDS accumulation is done in 64-bit fixed point: on gfx950 a wave-wide ds_add_f32
 // costs ~190 LDS cycles per instruction (measured, scratch/lds_atomic_bench.hip)
@@ -258,10 +262,10 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
     // chain substep: the entry counters of the halo send buffers, which the k_grid<0> behind this kernel fills
     if (blockIdx.x == 0 && threadIdx.x < 2 && p.halo_hdr[threadIdx.x]) p.halo_hdr[threadIdx.x][0] = 0u;
     __shared__ long long tile[TILE_N * 4];  // (mvx, mvy, mvz, m) per node: fixed point, or the bits of doubles (EXACT)
-    // wave-private staging: 64 particles (+8 slack rows touched by the operand prefetch)
-    __shared__ __attribute__((aligned(16))) float stage_all[P2G_WAVES][(64 + 8) * STG];
+    // wave-private staging: 64 particles (+3 slack rows touched by the operand reads)
+    __shared__ __attribute__((aligned(16))) float stage_all[P2G_WAVES][STG_ROWS * STG];
     __shared__ unsigned s_mask;
-    static_assert(sizeof(long long) * TILE_N * 4 + sizeof(float) * P2G_WAVES * (64 + 8) * STG + 4 <= 81920,
+    static_assert(sizeof(long long) * TILE_N * 4 + sizeof(float) * P2G_WAVES * STG_ROWS * STG + 4 <= 81920,
                   "two workgroups per CU need <= 80 KB of LDS each");
     Ctl* ctl = p.ctl;
     const PSet& S = p.set[ctl->cur];
@@ -271,34 +275,32 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
     float* stage = stage_all[wv];
 
     // ---- lane constants of the contraction ---------------------------------
+    // Node n = 9 i + 3 j + k = 3 a + k with a = 3 i + j.  B-operand column j16 of MFMA 0 is node j16 (lanes 0..14), of
+    // MFMA 1 node j16 + 12 (lanes 3..14): both share k = j16 % 3 and their pairs (i, j) are a0 = j16 / 3 and a0 + 4, so
+    // a lane reads its two staged products px * py with one ds_read2_b32 (floats a0 and a0 + 4 of the row's nine) and
+    // multiplies both by the same pz.  The other slots (MFMA 0 lane 15, MFMA 1 lanes 0..2 and 15) carry no node: their
+    // weights are whatever finite floats of the row the same reads return, and their columns of the result are dropped.
     const int j16 = lane & 15, g4 = lane >> 4;
-    float ax[2][3], ay[2][3], az[2][3];  // B operand: weight polynomials of node rows j16 and 16 + j16
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int n = 16 * t + j16;
-        const bool on = n < 27;
-        bspline_coeff(n / 9, on, ax[t][0], ax[t][1], ax[t][2]);
-        bspline_coeff((n / 3) % 3, true, ay[t][0], ay[t][1], ay[t][2]);
-        bspline_coeff(n % 3, true, az[t][0], az[t][1], az[t][2]);
-    }
-    const f32x2 cx0 = {ax[0][0], ax[1][0]}, cx1 = {ax[0][1], ax[1][1]}, cx2 = {ax[0][2], ax[1][2]};
-    const f32x2 cy0 = {ay[0][0], ay[1][0]}, cy1 = {ay[0][1], ay[1][1]}, cy2 = {ay[0][2], ay[1][2]};
-    const f32x2 cz0 = {az[0][0], az[1][0]}, cz1 = {az[0][1], az[1][1]}, cz2 = {az[0][2], az[1][2]};
-    // epilogue: (1, i, j, k)[r] of node 16 t + j16, times the fixed-point scale of this lane's component g4 (a power
-    // of two: scaling before or after the sums gives the same bits)
+    const int node[2] = {j16 < 15 ? j16 : -1, j16 >= 3 && j16 < 15 ? j16 + 12 : -1};
+    float cz0, cz1, cz2;   // pz: the weight polynomial of k = j16 % 3
+    bspline_coeff(j16 % 3, true, cz0, cz1, cz2);
+    const int ycol = j16 < 13 ? stg_col(j16) : 0;    // A operand: Y[j16] (rows 13..15 of the product are dropped)
+    const int xycol = STG_PXY + j16 / 3;              // px * py of (a0) and, 4 floats on, of (a0 + 4)
+    // epilogue: (1, i, j, k)[r] of this lane's node of MFMA t, times the fixed-point scale of this lane's component g4 (a
+    // power of two: scaling before or after the sums gives the same bits)
     float fac[2][4];
     int delta[2];        // float offset of this lane's node/component in the tile, -1 if none
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        // lane (j16, g4) of MFMA t ends up with the four terms of node 16 t + j16, component g4
-        const int n = 16 * t + j16;
+        // lane (j16, g4) of MFMA t ends up with the four terms of node[t], component g4
+        const int n = node[t];
         const int ni = n / 9, nj = (n / 3) % 3, nk = n % 3;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            fac[t][r] = n >= 27 ? 0.f : (r == 0 ? 1.f : (float)(r == 1 ? ni : (r == 2 ? nj : nk)));
-            if (g4 == 3 && r != 0) fac[t][r] = 0.f;   // (columns 13..15 carry fx, fy, fz)
+            fac[t][r] = n < 0 ? 0.f : (r == 0 ? 1.f : (float)(r == 1 ? ni : (r == 2 ? nj : nk)));
+            if (g4 == 3 && r != 0) fac[t][r] = 0.f;   // (A rows 13..15: lanes 13..15 read Y[0] in their place)
         }
-        delta[t] = n < 27 ? ((ni * TILE_W + nj) * TILE_W + nk) * 4 + g4 : -1;
+        delta[t] = n >= 0 ? ((ni * TILE_W + nj) * TILE_W + nk) * 4 + g4 : -1;
     }
     {
         const float fscale = EXACT ? (float)(g4 == 3 ? p.fix_m : p.fix_p) : 1.f;
@@ -311,7 +313,7 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
     const unsigned reach_of_lane = tile_reach_mask(2 * (lane >> 4), 2 * ((lane >> 2) & 3), 2 * (lane & 3));
     // A step reads 4 staged rows; rows that do not belong to the cell (the next cell's particles,
     // rows never written) are masked in the B operand only, so every row must hold finite numbers
-    for (int k = lane; k < (64 + 8) * STG; k += 64) stage[k] = 0.f;
+    for (int k = lane; k < STG_ROWS * STG; k += 64) stage[k] = 0.f;
 
     // Work items (a home block, or a run of the wave groups of a heavy one) are taken round-robin
     // from the heaviest-first order: workgroup w processes entries w, w + G, ...; with G resident
@@ -479,11 +481,22 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
             }
             // ---- 3. stage at the grouped position (wave-private LDS, in-order) --
             if (act) {
-                float4* sp = reinterpret_cast<float4*>(stage + pos * STG);
-                sp[0] = make_float4(Y[0], Y[1], Y[2], Y[3]);
-                sp[1] = make_float4(Y[4], Y[5], Y[6], Y[7]);
-                sp[2] = make_float4(Y[8], Y[9], Y[10], Y[11]);
-                sp[3] = make_float4(Y[12], st.fx[0], st.fx[1], st.fx[2]);
+                // the B-spline factors once per particle, each as fma(fma(c2, f, c1), f, c0) with bspline_coeff's
+                // coefficients; the contraction forms the weight of node (i, j, k) as (px[i] * py[j]) * pz[k]
+                float px[3], py[3];
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    float c0, c1, c2;
+                    bspline_coeff(a, true, c0, c1, c2);
+                    px[a] = fmaf(fmaf(c2, st.fx[0], c1), st.fx[0], c0);
+                    py[a] = fmaf(fmaf(c2, st.fx[1], c1), st.fx[1], c0);
+                }
+                float* sp = stage + pos * STG;
+#pragma unroll
+                for (int c = 0; c < 13; ++c) sp[stg_col(c)] = Y[c];
+#pragma unroll
+                for (int a = 0; a < 9; ++a) sp[STG_PXY + a] = px[a / 3] * py[a % 3];
+                sp[STG_FZ] = st.fx[2];
             }
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
@@ -492,38 +505,45 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
             // ---- 4. per-cell contraction on the matrix pipe ----------------------
             unsigned long long todo = actmask;
             int s0 = 0;
-            float nfx, nfy, nfz, ny;
-            {
-                const float* sn = stage + g4 * STG;
-                nfx = sn[STG_FX]; nfy = sn[STG_FX + 1]; nfz = sn[STG_FX + 2]; ny = sn[j16];
-            }
+            // operands of the next step: Y[j16], the two products px * py and fz of row (step + g4)
+            float ny, nfz;
+            f32x2 nxy;
+            // ... read from the cell's first row + `off` (this lane's three addresses, set once per cell)
+            const float *ry, *rxy, *rz;
+            auto load_ops = [&](int off) {
+                ny = ry[off]; nxy = f32x2{rxy[off], rxy[off + 4]}; nfz = rz[off];
+            };
+            auto cell_rows = [&](int s) {   // the next cell starts at row s
+                const float* row = stage + (s + g4) * STG;
+                ry = row + ycol; rxy = row + xycol; rz = row + STG_FZ;
+                load_ops(0);
+            };
+            cell_rows(0);
             if (prof) tq[1] = __builtin_readcyclecounter();
             __builtin_amdgcn_s_setprio(2);   // (waves in the contraction keep the matrix pipe fed: ahead of waves that derive / group)
             while (todo) {
                 const int ckey = __builtin_amdgcn_readlane(key, __builtin_ctzll(todo));
                 const unsigned long long same = __ballot(key == ckey) & todo;
                 todo &= ~same;
-                const int s1 = s0 + (int)__popcll(same);
+                // (two 32-bit counts: compared as one 64-bit count, the step tests below become vector instructions)
+                const int s1 = s0 + __builtin_popcount((unsigned)same) + __builtin_popcount((unsigned)(same >> 32));
+                const int nsteps = (s1 - s0 + 3) >> 2;   // (a cell has 1..64 particles: 1..16 steps)
                 f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-                if (prof) { pc[4] += 1; pc[5] += (unsigned)((s1 - s0 + 3) >> 2); tq[2] = __builtin_readcyclecounter(); }
+                if (prof) { pc[4] += 1; pc[5] += (unsigned)nsteps; tq[2] = __builtin_readcyclecounter(); }
                 // Operands of a step are fetched one step ahead (the first step's during the previous cell's epilogue), so
                 // the LDS latency hides behind the MFMAs.  Three kinds of step: the first accumulates onto the inline
                 // constant 0 (no eight moves to clear the accumulators of every cell), only the last one has rows of the
                 // NEXT cell to mask (a cell's rows are contiguous: every row of an earlier step is the cell's own).
-                auto step = [&](int s, bool first_step, bool last_step) {
-                    const float fx = nfx, fy = nfy, fz = nfz;
+                // Per step: pz (two fused multiply-adds), both weights (one v_pk_mul_f32), two MFMAs.  The middle steps are
+                // written out (<= 14 of them, each with a scalar exit to the shared last step): their operand reads take
+                // the row offset from the cell's first row as an immediate, instead of advancing three lane addresses per
+                // step.  (A `for` with a break is re-rolled into such a loop; with a guard per step, leaving walks the
+                // remaining guards.)
+                auto step = [&](int k, bool first_step, bool last_step) {   // k: step of the cell
+                    const float pz = fmaf(fmaf(cz2, nfz, cz1), nfz, cz0);
+                    const f32x2 w01 = nxy * f32x2{pz, pz};
                     float y = ny;
-                    {
-                        const float* sn = stage + (s + 4 + g4) * STG;
-                        nfx = sn[STG_FX]; nfy = sn[STG_FX + 1]; nfz = sn[STG_FX + 2]; ny = sn[j16];
-                    }
-                    // both rows' weights in one chain of packed operations (v_pk_fma_f32: the same fused multiply-adds
-                    // as two scalar chains, half the issue slots)
-                    const f32x2 fx2 = {fx, fx}, fy2 = {fy, fy}, fz2 = {fz, fz};
-                    const f32x2 w01 = __builtin_elementwise_fma(__builtin_elementwise_fma(cx2, fx2, cx1), fx2, cx0) *
-                                      __builtin_elementwise_fma(__builtin_elementwise_fma(cy2, fy2, cy1), fy2, cy0) *
-                                      __builtin_elementwise_fma(__builtin_elementwise_fma(cz2, fz2, cz1), fz2, cz0);
-                    if (last_step && !(g4 < s1 - s)) y = 0.f;   // (weights of foreign rows are finite: 0 * w = 0)
+                    if (last_step && !(g4 < s1 - s0 - 4 * k)) y = 0.f;   // (weights of foreign rows are finite: 0 * w = 0)
                     if (first_step) {
                         const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
                         acc0 = p2g_mfma(y, w01.x, zero);
@@ -532,20 +552,24 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
                         acc0 = p2g_mfma(y, w01.x, acc0);
                         acc1 = p2g_mfma(y, w01.y, acc1);
                     }
+                    // (after the MFMAs, which have read this step's operands: the next ones go to the same registers)
+                    if (!last_step) load_ops(4 * (k + 1) * STG);
                 };
-                const int last = s0 + ((s1 - s0 - 1) & ~3);   // (a cell has at least one particle: s0 < s1)
-                if (last == s0) {
-                    step(s0, true, true);
+                if (nsteps == 1) {
+                    step(0, true, true);
                 } else {
-                    step(s0, true, false);
-                    for (int s = s0 + 4; s < last; s += 4) step(s, false, false);
-                    step(last, false, true);
+                    step(0, true, false);
+#define MPM_P2G_MIDDLE(k) if (nsteps - 1 == k) goto last_step; step(k, false, false);
+                    MPM_P2G_MIDDLE(1) MPM_P2G_MIDDLE(2) MPM_P2G_MIDDLE(3) MPM_P2G_MIDDLE(4) MPM_P2G_MIDDLE(5)
+                    MPM_P2G_MIDDLE(6) MPM_P2G_MIDDLE(7) MPM_P2G_MIDDLE(8) MPM_P2G_MIDDLE(9) MPM_P2G_MIDDLE(10)
+                    MPM_P2G_MIDDLE(11) MPM_P2G_MIDDLE(12) MPM_P2G_MIDDLE(13) MPM_P2G_MIDDLE(14)
+#undef MPM_P2G_MIDDLE
+                last_step:
+                    step(nsteps - 1, false, true);
                 }
-                // the loop leaves row block (last step + 4) preloaded; the next cell starts at s1
-                if (((s1 - s0) & 3) != 0) {
-                    const float* sn = stage + (s1 + g4) * STG;
-                    nfx = sn[STG_FX]; nfy = sn[STG_FX + 1]; nfz = sn[STG_FX + 2]; ny = sn[j16];
-                }
+                // the next cell's first step: rows s1 .. s1 + 3 <= 66 (a next cell starts at s1 <= 63; after the last one
+                // the reads are not used, and an unconditional read leaves no old operands to carry over)
+                cell_rows(min(s1, 63));
                 if (prof) { asm volatile("" :: "v"(acc0), "v"(acc1)); const unsigned long long tm = __builtin_readcyclecounter(); pc[2] += tm - tq[2]; tq[2] = tm; }
                 s0 = s1;
                 const int crx = ckey >> 6, cry = (ckey >> 3) & 7, crz = ckey & 7;
