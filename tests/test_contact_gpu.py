@@ -84,7 +84,7 @@ def _diagnose(g, o):
 
 # (stiffness, damping, dt, friction): the first test's historical values, and SURVEY.md 8(d) config 3 =
 # the bagging demo's parameters (examples/multibody/deformable/mpm_bagging.cc:9,15-17)
-CONTACT_PARAMS = {"soft": (1e5, 1e-3, 1e-3), "config3": (1e6, 1e-5, 2e-4)}
+from tests.contact_layouts import CONTACT_PARAMS  # noqa: E402  (shared with the contact layouts)
 
 
 # (deterministic: engine in mpm_set_deterministic mode against the oracle's fixed-order sums -- one number per comparison,
