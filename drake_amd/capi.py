@@ -97,6 +97,24 @@ class GridCollider(C.Structure):
 
 
 BC_TABLE = 4   # mpm_bc value that selects the table of set_grid_colliders
+BC_BODIES = 5  # mpm_bc value that selects the table of set_grid_bodies
+GB_NO_MESH = 0xFFFFFFFF
+GC_FIXED, GC_SLIP_APPROACHING, GC_SLIP = 0, 1, 2
+
+
+class GridBody(C.Structure):
+    """mpm_grid_body_t: a rigid body of the grid update -- `shape` (a Collider: kind, body, pose, dims, v, w), or the
+    mesh lattice `sdf_shape` posed by shape's p_WB / R_WB; mode 0 fixed / 1 slip while approaching / 2 slip; friction < 0
+    selects the engine's material.sdf_friction."""
+    _fields_ = [("shape", Collider), ("sdf_shape", C.c_uint32), ("mode", C.c_int32), ("friction", C.c_float)]
+
+    def __init__(self, shape=None, sdf_shape=GB_NO_MESH, mode=0, friction=-1.0):
+        super().__init__()
+        if shape is not None:
+            C.memmove(C.byref(self.shape), C.byref(shape), C.sizeof(Collider))
+        else:
+            self.shape.R_WB[:] = [1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0]
+        self.sdf_shape, self.mode, self.friction = int(sdf_shape), int(mode), float(friction)
 
 
 def grid_collider_preset(mpm_bc: int, sdf_friction: float = 0.3):
@@ -204,7 +222,8 @@ SYMBOLS = [
     "mpm_debug_contact_counters", "mpm_run_coupled_substeps", "mpm_chain_direct_prepare", "mpm_chain_direct_connect",
     "mpm_debug_contact_count", "mpm_chain_direct_base", "mpm_chain_direct_connect_local", "mpm_team_prepare", "mpm_team_connect",
     "mpm_world_coupled_substeps", "mpm_set_pins", "mpm_set_body_motions", "mpm_pins_inside_collider", "mpm_get_pins",
-    "mpm_add_qr_cloth_with_material", "mpm_get_cloth_info", "mpm_cloth_count",
+    "mpm_add_qr_cloth_with_material", "mpm_get_cloth_info", "mpm_cloth_count", "mpm_set_grid_bodies",
+    "mpm_get_grid_bodies",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -319,6 +338,8 @@ def load_library(build: bool = True):
         "mpm_set_body_motions": [vp, sz, vp],
         "mpm_pins_inside_collider": [vp, vp, C.c_uint32, vp, vp, P(sz)],
         "mpm_get_pins": [vp, vp, sz, P(sz)],
+        "mpm_set_grid_bodies": [vp, sz, vp],
+        "mpm_get_grid_bodies": [vp, vp, sz, P(sz)],
         "mpm_add_qr_cloth_with_material": [vp, vp, vp, sz, vp, sz, vp],
         "mpm_get_cloth_info": [vp, sz, P(sz), P(sz), P(sz), P(sz), vp],
         "mpm_cloth_count": [vp, P(sz)],
@@ -553,6 +574,20 @@ class GpuMpm:
         """Table of analytic grid colliders used by mpm_bc = BC_TABLE (list of GridCollider)."""
         arr = (GridCollider * max(len(colliders), 1))(*colliders)
         self._ck(self.lib.mpm_set_grid_colliders(self.h, len(colliders), arr))
+
+    def set_grid_bodies(self, bodies):
+        """Table of rigid bodies of the grid update used by mpm_bc = BC_BODIES (list of GridBody, at most 16; an empty
+        list clears it).  Set once per plant step, then run its substeps."""
+        arr = (GridBody * max(len(bodies), 1))(*bodies)
+        self._ck(self.lib.mpm_set_grid_bodies(self.h, len(bodies), arr))
+
+    def get_grid_bodies(self):
+        """mpm_get_grid_bodies: the table in force, a list of GridBody."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_grid_bodies(self.h, None, 0, C.byref(n)))
+        arr = (GridBody * max(int(n.value), 1))()
+        self._ck(self.lib.mpm_get_grid_bodies(self.h, arr, int(n.value), C.byref(n)))
+        return [arr[k] for k in range(int(n.value))]
 
     def grid_to_particle(self, dt: float):
         self._ck(self.lib.mpm_grid_to_particle(self.h, dt))

@@ -190,13 +190,19 @@ static int grid_collider_preset(int bc, float sdf_friction, GridColliders* out) 
         default: return -1;
     }
 }
+// MPM_BC_BODIES: n = -1 stands for "the engine's body table" (launch_grid picks k_grid_bodies); an empty table is mpm_bc = -1
 static int grid_colliders_for(mpm_engine* e, int bc, GridColliders* out) {
+    if (bc == MPM_BC_BODIES) {
+        *out = GridColliders{};
+        out->n = e->grid_bodies.empty() ? 0 : -1;
+        return 0;
+    }
     if (bc == MPM_BC_TABLE) {
         *out = e->grid_colliders;
         return 0;
     }
     if (grid_collider_preset(bc, e->mat.sdf_friction, out))
-        return fail(MPM_ERR_INVALID, "mpm_bc must be -1, 0, 1, 2, 3 or MPM_BC_TABLE");
+        return fail(MPM_ERR_INVALID, "mpm_bc must be -1, 0, 1, 2, 3, MPM_BC_TABLE or MPM_BC_BODIES");
     return 0;
 }
 
@@ -294,6 +300,19 @@ static void launch_g2p(mpm_engine* e, const DP& p, float dt) {
 }
 static void launch_grid(mpm_engine* e, const DP& p, const GridColliders& gc) {
     TraceRange tr("mpm:UpdateGrid");
+    if (gc.n < 0) {   // MPM_BC_BODIES with a table (grid_colliders_for): the instance the table needs
+        const dim3 g(e->g_grid), b(256);
+        const GridBodyTable* t = e->d_grid_bodies;
+        long long* acc = e->cb.body_acc;
+        const int nb = (int)e->cb.n_bodies;
+        switch (e->grid_bodies_kinds) {
+            case 0: hipLaunchKernelGGL(k_grid_bodies<0>, g, b, 0, e->stream, p, t, acc, nb); break;
+            case 1: hipLaunchKernelGGL(k_grid_bodies<1>, g, b, 0, e->stream, p, t, acc, nb); break;
+            case 2: hipLaunchKernelGGL(k_grid_bodies<2>, g, b, 0, e->stream, p, t, acc, nb); break;
+            default: hipLaunchKernelGGL(k_grid_bodies<3>, g, b, 0, e->stream, p, t, acc, nb); break;
+        }
+        return;
+    }
     hipLaunchKernelGGL(k_grid<1>, dim3(e->g_grid), dim3(256), 0, e->stream, p, gc);
 }
 
@@ -762,11 +781,13 @@ static int pins_ready(mpm_engine* e) {
     ps.table_dirty = false;
     return 0;
 }
-// partitioned and multi-rank engines have no pins and no per-cloth materials (out of scope)
+// partitioned and multi-rank engines have no pins, no per-cloth materials and no grid bodies (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on a multi-material engine (mpm_add_qr_cloth_with_material)");
+    if (!e->grid_bodies.empty())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with grid bodies (mpm_set_grid_bodies)");
     return 0;
 }
 
@@ -1062,6 +1083,7 @@ int mpm_update_grid_from_sums(mpm_handle_t e, int bc) try {
     REQUIRE(e->grid_state == 3, "needs mpm_grid_gather first");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
+    REQUIRE(gc.n >= 0, "MPM_BC_BODIES is not available in the halo substeps (grid bodies: single-engine only)");
     hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, gc);
     e->grid_state = 2;
     return 0;
@@ -1083,6 +1105,7 @@ int mpm_substep_end(mpm_handle_t e, float dt, int bc) try {
     REQUIRE(e->grid_state == 3, "mpm_substep_end without mpm_substep_begin");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
+    REQUIRE(gc.n >= 0, "MPM_BC_BODIES is not available in the halo substeps (grid bodies: single-engine only)");
     hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, gc);
     e->grid_state = 2;
     launch_g2p(e, e->dp, dt);
@@ -3063,6 +3086,105 @@ int mpm_get_pins(mpm_handle_t e, mpm_pin_t* out, size_t capacity, size_t* n_out)
     READY(e);
     REQUIRE(out || capacity == 0, "null output");
     const std::vector<mpm_pin_t>& set = e->pin.set;
+    std::copy(set.begin(), set.begin() + std::min(capacity, set.size()), out);
+    if (n_out) *n_out = set.size();
+    return 0;
+} MPM_CATCH_ALL
+
+// ---- rigid bodies of the grid update (mpm_set_grid_bodies, mpm_get_grid_bodies; k_grid_bodies in mpm_grid_bodies.h) ----
+// no point of the body is farther from its origin than this (k_grid_bodies' test per wave); a little slack for the float
+// evaluation, infinite when the dimensions say nothing (a half-space; NaN or infinite dimensions of kinds 1-3)
+static float grid_body_bound(const mpm_grid_body_t& b, const SdfShape* sh) {
+    double r;
+    if (sh) {
+        r = 0.0;
+        for (int a = 0; a < 3; ++a) {
+            const double m = std::max(std::fabs((double)sh->lo[a]), std::fabs((double)sh->hi[a]));
+            r += m * m;
+        }
+        r = std::sqrt(r);
+    } else {
+        const double d0 = std::fabs((double)b.shape.dims[0]), d1 = std::fabs((double)b.shape.dims[1]),
+                     d2 = std::fabs((double)b.shape.dims[2]);
+        switch (b.shape.kind) {
+            case MPM_COLLIDER_SPHERE: r = d0; break;
+            case MPM_COLLIDER_BOX: r = std::sqrt(d0 * d0 + d1 * d1 + d2 * d2); break;
+            case MPM_COLLIDER_CAPSULE: r = d0 + d1; break;
+            case MPM_COLLIDER_CYLINDER: r = std::sqrt(d0 * d0 + d1 * d1); break;
+            case MPM_COLLIDER_ELLIPSOID: r = std::max(d0, std::max(d1, d2)); break;
+            default: return INFINITY;
+        }
+    }
+    r = r * (1.0 + 1e-4) + 1e-6;
+    return std::isfinite(r) && r < 1e30 ? (float)r : INFINITY;
+}
+
+int mpm_set_grid_bodies(mpm_handle_t e, size_t n, const mpm_grid_body_t* bodies) try {
+    static_assert(sizeof(Collider) == sizeof(mpm_collider_t), "collider layouts differ");
+    READY_NO_SETTLE(e);
+    REQUIRE(!multi_rank(e), "grid bodies are not available on a partitioned or multi-rank engine");
+    REQUIRE(n <= (size_t)MAX_GRID_COLLIDERS, "too many grid bodies (at most 16)");
+    REQUIRE(n == 0 || bodies, "null grid body array");
+    for (size_t k = 0; k < n; ++k) {
+        const mpm_grid_body_t& b = bodies[k];
+        if (b.sdf_shape == MPM_GB_NO_MESH) {
+            if (int rc = validate_colliders(1, &b.shape)) return rc;
+        } else {
+            REQUIRE(b.sdf_shape < e->cb.shapes.size(), "grid body: unknown shape id");
+        }
+        REQUIRE(b.mode >= MPM_GC_FIXED && b.mode <= MPM_GC_SLIP, "unknown grid body mode");
+        REQUIRE(std::isfinite(b.friction), "grid body: friction not finite");
+        REQUIRE(finite_n(b.shape.p_WB, 3) && finite_n(b.shape.v, 3) && finite_n(b.shape.w, 3), "grid body: pose or velocity not finite");
+        REQUIRE(is_rotation(b.shape.R_WB), "grid body: R_WB is not a rotation");
+    }
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    auto table = std::make_unique<GridBodyTable>();
+    std::memset(table.get(), 0, sizeof(GridBodyTable));
+    int kinds = 0, n_mesh = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const mpm_grid_body_t& b = bodies[k];
+        GridBody& d = table->b[k];
+        std::memcpy(&d.c, &b.shape, sizeof(Collider));
+        d.mode = b.mode;
+        d.friction = b.friction < 0.f ? e->mat.sdf_friction : b.friction;
+        d.mesh = -1;
+        const SdfShape* sh = nullptr;
+        if (b.sdf_shape != MPM_GB_NO_MESH) {
+            sh = &e->cb.shapes[b.sdf_shape];
+            mpm_sdf_collider_t sc{};
+            sc.shape = b.sdf_shape;
+            sc.body = b.shape.body;
+            std::memcpy(sc.p_WB, b.shape.p_WB, sizeof(sc.p_WB));
+            std::memcpy(sc.R_WB, b.shape.R_WB, sizeof(sc.R_WB));
+            std::memcpy(sc.v, b.shape.v, sizeof(sc.v));
+            std::memcpy(sc.w, b.shape.w, sizeof(sc.w));
+            table->mesh[n_mesh] = mesh_collider(*sh, sc);
+            d.mesh = n_mesh++;
+            d.c.kind = 0;   // (kind and dims of a mesh body are not read)
+            kinds |= 2;
+        } else if (b.shape.kind == MPM_COLLIDER_ELLIPSOID) {
+            kinds |= 1;
+        }
+        d.bound = grid_body_bound(b, sh);
+    }
+    table->n = (int)n;
+    if (n) {
+        if (!e->d_grid_bodies)
+            if (int rc = e->dalloc(&e->d_grid_bodies, 1, true)) return rc;
+        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
+        H2D(e, e->d_grid_bodies, table.get(), sizeof(GridBodyTable));
+    }
+    e->grid_bodies.assign(bodies, bodies + n);
+    e->grid_bodies_kinds = kinds;
+    e->grid_colliders_version += 1;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_get_grid_bodies(mpm_handle_t e, mpm_grid_body_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    const std::vector<mpm_grid_body_t>& set = e->grid_bodies;
     std::copy(set.begin(), set.begin() + std::min(capacity, set.size()), out);
     if (n_out) *n_out = set.size();
     return 0;

@@ -17,6 +17,7 @@
 #include "mpm_step.h"
 #include "mpm_contact_dev.h"
 #include "mpm_pins.h"
+#include "mpm_grid_bodies.h"
 #include "mpm_team.h"
 #include "mpm_trace.h"
 
@@ -190,7 +191,11 @@ struct mpm_engine {
     uint64_t substeps = 0;
     // analytic colliders of the grid update selected by mpm_bc = MPM_BC_TABLE (mpm_set_grid_colliders)
     GridColliders grid_colliders{};
-    uint64_t grid_colliders_version = 0;
+    uint64_t grid_colliders_version = 0;   // (counts the changes of both tables: substeps are owed with the tables of their call)
+    // rigid bodies of the grid update selected by mpm_bc = MPM_BC_BODIES (mpm_set_grid_bodies; k_grid_bodies)
+    std::vector<mpm_grid_body_t> grid_bodies;   // the caller's table, as given
+    GridBodyTable* d_grid_bodies = nullptr;     // ... as the kernel reads it
+    int grid_bodies_kinds = 0;                  // the instance it needs (bit 0: an ellipsoid, bit 1: a mesh body)
     // fixed constraints (mpm_set_pins, mpm_set_body_motions; k_pin in mpm_pins.h)
     struct PinState {
         std::vector<mpm_pin_t> set;              // the caller's pins, in order

@@ -673,193 +673,9 @@ MPM_DEV size_t halo_ids_offset() { return 4; }                       // in uint3
 MPM_DEV size_t halo_data_offset(unsigned cap) { return ((size_t)(4 + cap) * 4 + 15) / 16; }  // in float4 units
 template <int MODE>
 __global__ __launch_bounds__(256) void k_grid(DP p, GridColliders gc) {
-    __shared__ int2 s_list[4][GRID_LIST];   // (item, offset index)
-    const Ctl* ctl = p.ctl;
-    {
-        const bool out = gated_out(p);
-        if (blockIdx.x == 0 && threadIdx.x == 0) p.ctl->skip_this = out;
-        if (out) return;
-    }
-    const unsigned n_active = ctl->n_active;
-    const int tid = threadIdx.x;
-    const int cell = tid & 63;
-    const int cx = cell >> 4, cy = (cell >> 2) & 3, cz = cell & 3;
-    // the multi-GPU path packs halo buffers right after this kernel: reset their entry counters here
-    if (MODE == 0 && blockIdx.x == 0 && tid < 2 && p.halo_hdr[tid]) p.halo_hdr[tid][0] = 0u;
-    if (MODE == 2 && p.halo_pn > 0 && tid < 64 && blockIdx.x * 64u < p.halo_pcap) {
-        // Diagnostics of the received lists (what k_halo_add2 reports for the public mpm_halo_add): the add
-        // below looks a zone block up in ITS zone's buffer, so a received block that lies in this rank's grid but outside
-        // the zone its buffer belongs to would be dropped without a trace.  The first few workgroups look at 64 ids each.
-        for (int k = 0; k < p.halo_pn; ++k) {
-            const uint32_t* buf = p.halo_pbuf[k];
-            const unsigned n = min(buf[0], p.halo_pcap);
-            for (unsigned e = blockIdx.x * 64u + (unsigned)tid; e < n; e += gridDim.x * 64u) {
-                const uint32_t id = buf[halo_ids_offset() + e];
-                if (id >= p.nblocks) {   // (no sender writes such an id: the buffer is not a halo buffer of this grid)
-                    atomicOr(&p.ctl->error, ERR_HALO);
-                    continue;
-                }
-                if (p.lut_act[id] < 0) continue;   // nothing of ours reaches that block
-                int hx, hy, hz;
-                block_coords(id, hx, hy, hz);
-                if (hx < p.halo_plo[k] || hx > p.halo_phi[k]) atomicOr(&p.ctl->error, ERR_CAPACITY);
-            }
-        }
-    }
-    for (unsigned a = blockIdx.x * 4 + (tid >> 6); a < n_active; a += gridDim.x * 4) {
-        if (MODE == 2 && p.halo_cls >= 0) {   // split update around the halo exchange (wave-uniform)
-            int hx, hy, hz;
-            block_coords(p.act_block[a], hx, hy, hz);
-            if (!halo_block_selected(p, hx)) continue;
-        }
-        const int* nbr = p.act_nbr_items + (size_t)a * 27;
-        float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (MODE == 2) {
-            s = p.gv[(size_t)a * 64 + cell];
-            if (p.halo_pn > 0) {
-                // chain substep: the neighbour's sums for this block, straight from the received buffer (what k_halo_add2
-                // does as a launch of its own for the public mpm_halo_add).  The buffer lists its blocks in the order its
-                // sender's atomics fell: the wave scans the ids, 64 per step (a zone holds a few hundred blocks).  own +
-                // received is the same pair of numbers on both ranks, so both compute identical node values.
-                const uint32_t myid = p.act_block[a];
-                int bx, by, bz;
-                block_coords(myid, bx, by, bz);
-                for (int k = 0; k < p.halo_pn; ++k) {
-                    if (bx < p.halo_plo[k] || bx > p.halo_phi[k]) continue;   // wave-uniform
-                    const uint32_t* buf = p.halo_pbuf[k];
-                    const unsigned n = min(buf[0], p.halo_pcap);
-                    int found = -1;
-                    for (unsigned base = 0; base < n && found < 0; base += 64) {
-                        const uint32_t id = base + (unsigned)cell < n ? buf[halo_ids_offset() + base + (unsigned)cell] : 0xFFFFFFFFu;
-                        const unsigned long long m = __ballot(id == myid);
-                        if (m) found = (int)base + __builtin_ctzll(m);
-                    }
-                    if (found >= 0) {
-                        const float4 r = (reinterpret_cast<const float4*>(buf) + halo_data_offset(p.halo_pcap))[(size_t)found * 64 + cell];
-                        s.x += r.x; s.y += r.y; s.z += r.z; s.w += r.w;
-                    }
-                }
-            }
-        }
-        if (MODE != 2) {
-            // Phase 1: lanes 0..26 look at one neighbour home block each and list the slabs (one per
-            // work item of that block) whose stencils reached this block, in a fixed order
-            // (split index, then offset).  Phase 2 streams through the list: all table walks are
-            // done, the slab reads are independent and overlap.
-            int2* list = s_list[tid >> 6];
-            const int packed = cell < 27 ? nbr[cell] : -1;
-            const int it0 = packed & 0xFFFFFF, ni = packed < 0 ? 0 : (packed >> 24);
-            int cnt = 0;
-            const int nimax = __reduce_max_sync_i32(ni);
-            for (int k = 0; k < nimax; ++k) {
-                // this block seen from the home block is at offset -o
-                const bool hit = k < ni && ((p.slab_mask[it0 + k] >> (26 - cell)) & 1u);
-                const unsigned long long m = __ballot(hit);
-                if (hit) {
-                    const int at = cnt + (int)__popcll(m & ((1ull << cell) - 1ull));
-                    if (at < GRID_LIST) list[at] = make_int2(it0 + k, cell);
-                }
-                cnt += (int)__popcll(m);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-            if (cnt > GRID_LIST) {   // > 160 slabs over one block (dozens of split, very heavy neighbours)
-                if (cell == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
-                cnt = GRID_LIST;
-            }
-#pragma unroll 4
-            for (int e = 0; e < cnt; ++e) {
-                const int2 en = list[e];
-                const int it = en.x, o = en.y;
-                const int tx = cx - 4 * (o / 9 - 1) + FREE_ZONE;
-                const int ty = cy - 4 * ((o / 3) % 3 - 1) + FREE_ZONE;
-                const int tz = cz - 4 * (o % 3 - 1) + FREE_ZONE;
-                // branch-free so that the unrolled loads are issued back to back: lanes outside the
-                // slab read its node 0 and add nothing
-                const bool in_tile = !(tx < 0 || ty < 0 || tz < 0 || tx >= TILE_W || ty >= TILE_W || tz >= TILE_W);
-                const int node = in_tile ? (tx * TILE_W + ty) * TILE_W + tz : 0;
-                const float4 t = p.slab[(size_t)it * TILE_N + node];
-                s.x += in_tile ? t.x : 0.f; s.y += in_tile ? t.y : 0.f;
-                s.z += in_tile ? t.z : 0.f; s.w += in_tile ? t.w : 0.f;
-            }
-            __builtin_amdgcn_wave_barrier();   // the list is reused by the wave's next block
-        }
-        const size_t gi = (size_t)a * 64 + cell;
-        if (MODE == 0) {
-            p.gv[gi] = s;
-            if (p.halo_pn > 0) {   // chain substep: blocks next to a cut go into the send buffers from here
-                int bx, by, bz;
-                block_coords(p.act_block[a], bx, by, bz);
-                for (int k = 0; k < p.halo_pn; ++k) {
-                    if (bx < p.halo_plo[k] || bx > p.halo_phi[k]) continue;   // wave-uniform
-                    const int nbx = bx + p.halo_pshift[k];
-                    if (nbx < 0 || nbx >= p.nb) continue;
-                    uint32_t* buf = p.halo_pbuf[k];
-                    unsigned slot = 0;
-                    if (cell == 0) slot = atomicAdd(p.halo_pcnt[k] ? p.halo_pcnt[k] : &buf[0], 1u);   // (a LOCAL word: see DP::halo_pcnt)
-                    slot = __builtin_amdgcn_readfirstlane(slot);
-                    if (slot >= p.halo_pcap) {
-                        if (cell == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
-                        continue;
-                    }
-                    if (cell == 0) buf[halo_ids_offset() + slot] = block_id((uint32_t)nbx, (uint32_t)by, (uint32_t)bz);
-                    (reinterpret_cast<float4*>(buf) + halo_data_offset(p.halo_pcap))[(size_t)slot * 64 + cell] = s;
-                }
-            }
-            continue;
-        }
-        float4 vs = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (s.w > 0.f) {
-            float v[3] = {s.x / s.w, s.y / s.w, s.z / s.w};
-            int bx, by, bz;
-            block_coords(p.act_block[a], bx, by, bz);
-            const int gx = bx * 4 + cx, gy = by * 4 + cy, gz = bz * 4 + cz;
-            const int N = 1 << p.bits, wl = p.M.wall;
-            if (gx < wl && v[0] < 0.f) v[0] = 0.f;
-            if (gx >= N - wl && v[0] > 0.f) v[0] = 0.f;
-            if (gy < wl && v[1] < 0.f) v[1] = 0.f;
-            if (gy >= N - wl && v[1] > 0.f) v[1] = 0.f;
-            if (gz < wl && v[2] < 0.f) v[2] = 0.f;
-            if (gz >= N - wl && v[2] > 0.f) v[2] = 0.f;
-            if (gc.n > 0) {
-                const float pos[3] = {((float)gx + .5f) * p.dx, ((float)gy + .5f) * p.dx, ((float)gz + .5f) * p.dx};
-                for (int k = 0; k < gc.n; ++k) {      // (uniform trip count: the table is a kernel argument)
-                    const GridCollider& cl = gc.c[k];
-                    float n[3], dist;
-                    if (cl.shape == 0) {
-                        const float d0 = pos[0] - cl.p[0], d1 = pos[1] - cl.p[1], d2 = pos[2] - cl.p[2];
-                        const float len = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
-                        const float inv = 1.f / len;
-                        n[0] = d0 * inv; n[1] = d1 * inv; n[2] = d2 * inv;
-                        dist = len - cl.radius;
-                    } else {
-                        n[0] = cl.n[0]; n[1] = cl.n[1]; n[2] = cl.n[2];
-                        dist = n[0] * (pos[0] - cl.p[0]) + n[1] * (pos[1] - cl.p[1]) + n[2] * (pos[2] - cl.p[2]);
-                    }
-                    if (!(dist < 0.f)) continue;
-                    // diff_vel = v_collider - v, dotnv = n . diff_vel  (:683-687)
-                    const float dv[3] = {cl.v[0] - v[0], cl.v[1] - v[1], cl.v[2] - v[2]};
-                    const float dn = n[0] * dv[0] + n[1] * dv[1] + n[2] * dv[2];
-                    if (cl.mode == 0) {
-                        v[0] += dv[0]; v[1] += dv[1]; v[2] += dv[2];          // :778-781
-                    } else if (cl.mode == 2 || dn > 0.f) {
-                        // :783-786; `dotnv * (1. - SDF_FRICTION)` is a double product in the reference
-                        const float fr = cl.friction;
-                        const float frac = (float)((double)dn * (1.0 - (double)fr));
-                        v[0] += dv[0] * fr + n[0] * frac;
-                        v[1] += dv[1] * fr + n[1] * frac;
-                        v[2] += dv[2] * fr + n[2] * frac;
-                    }
-                    break;
-                }
-            }
-            s.x = v[0]; s.y = v[1]; s.z = v[2];
-            vs = make_float4(v[0], v[1], v[2], 0.f);
-        }
-        p.gv[gi] = s;
-        p.gvs[gi] = vs;
-    }
+#define MPM_GRID_BODIES 0
+#include "mpm_grid_update.inc"
+#undef MPM_GRID_BODIES
 }
 
 // ---------------------------------------------------------------------------

@@ -164,6 +164,20 @@ struct GpuMpmState {
         mpm_check(mpm_get_pins(h_, out.data(), n, &n));
         return out;
     }
+    // Extension: rigid bodies in UpdateGrid's boundary condition (mpm_set_grid_bodies).  The table that
+    // UpdateGrid(state, MPM_BC_BODIES) and the substep calls with that mpm_bc use: once per plant step, from the body
+    // poses and spatial velocities of CalcAbstractStates, before its substeps.  The bodies' reactions arrive in
+    // external_forces_host() with the contact impulses (ExternelBodyForceToHost).
+    void SetGridBodies(const std::vector<mpm_grid_body_t>& bodies) {
+        mpm_check(mpm_set_grid_bodies(h_, bodies.size(), bodies.data()));
+    }
+    std::vector<mpm_grid_body_t> GetGridBodies() const {
+        size_t n = 0;
+        mpm_check(mpm_get_grid_bodies(h_, nullptr, 0, &n));
+        std::vector<mpm_grid_body_t> out(n);
+        mpm_check(mpm_get_grid_bodies(h_, out.data(), n, &n));
+        return out;
+    }
     std::vector<Vec3<T>>& positions_host() { return h_positions_; }
     const std::vector<Vec3<T>>& positions_host() const { return h_positions_; }
     ExternalSpatialForce<T>& external_forces_host() { return h_external_forces_; }

@@ -218,8 +218,8 @@ MPM_API int mpm_particle_to_grid(mpm_handle_t h, float dt);
 
 /* GpuMpmSolver::UpdateGrid (cuda_mpm_solver.cu:107-151).  mpm_bc in {-1,0,1,2,3} are the
  * reference's scenes (update_grid_kernel<T, BC>, cuda_mpm_kernels.cuh:673-774); MPM_BC_TABLE
- * uses the colliders set with mpm_set_grid_colliders.  The same values are accepted wherever an
- * entry point takes mpm_bc. */
+ * uses the colliders set with mpm_set_grid_colliders, MPM_BC_BODIES (below) the rigid bodies set with
+ * mpm_set_grid_bodies.  The same values are accepted wherever an entry point takes mpm_bc. */
 #define MPM_BC_TABLE 4
 MPM_API int mpm_update_grid(mpm_handle_t h, int mpm_bc);
 
@@ -628,6 +628,57 @@ MPM_API int mpm_get_cloth_info(mpm_handle_t h, size_t cloth, size_t *first_verte
                                size_t *first_face, size_t *n_faces, mpm_cloth_material_t *m);
 /* The number of cloths added so far. */
 MPM_API int mpm_cloth_count(mpm_handle_t h, size_t *n_out);
+
+/* ---- Rigid bodies in the grid update (an extension) ----
+ * The boundary condition of UpdateGrid for posed, moving rigid bodies of every kind the contact path knows, with the
+ * reaction on the bodies: what mpm_set_grid_colliders does for an unposed sphere and a half-space, for the six analytic
+ * kinds of mpm_collider_t and the mesh lattices of mpm_sdf_shape_from_mesh, at the cost of the grid update instead of the
+ * contact solve.  mpm_bc = MPM_BC_BODIES selects the table set with mpm_set_grid_bodies wherever an entry point takes
+ * mpm_bc: mpm_update_grid, mpm_substep, mpm_run_substeps (owed and replayed substeps included),
+ * mpm_run_coupled_substeps, mpm_profile_substeps.  With an empty table it behaves as mpm_bc = -1.
+ * The domain walls act first, as always.  Then, for a node with mass at x = (idx + 0.5) dx, the FIRST body of the table
+ * that contains the node decides:
+ *   membership and normal are the pair generator's (mpm_generate_contact_pairs), so that both coupling paths agree about
+ *     where a body's surface is: an analytic body contains x when mpm_collider_t's membership holds (phi(x) < 0 for
+ *     kinds 0-4, sum (x_B,i / a_i)^2 < 1 for the ellipsoid), a mesh body when the interpolant of mpm_sdf_collider_t gives
+ *     phi(x) < 0; n is the unit world gradient of phi that mpm_collider_signed_distance /
+ *     mpm_sdf_collider_signed_distance return at x (the ellipsoid's exact nearest-point gradient, evaluated for member
+ *     nodes only);
+ *   the body's velocity at the node is the rigid velocity field v_c(x) = v + w x (x - p_WB);
+ *   the three modes of mpm_grid_collider_t apply with v_c(x) as the collider velocity:
+ *     MPM_GC_FIXED             v <- v_c(x)   (v + (v_c - v), :778-781, written without the rounding residue of v)
+ *     MPM_GC_SLIP_APPROACHING  only if n.(v_c - v) > 0, then
+ *     MPM_GC_SLIP              v += mu (v_c - v) + (1 - mu) n (n.(v_c - v)), the product (n.(v_c - v)) (1 - mu) formed in
+ *                              double as in the reference (:783-786).
+ * Reaction: for a node of mass m decided by a body, with v_in the velocity after the walls and v_out the velocity
+ * written, body `shape.body` receives the force impulse l = -m (v_out - v_in) and the torque impulse (x - p_WB) x l, in
+ * the accumulators of the contact impulses (64-bit fixed point, the contact impulses' scale: the sums do not depend on the
+ * order) read by mpm_external_body_force_to_host and mpm_finalize_external_contact_forces.  A body index >= the
+ * mpm_reallocate_external_bodies count acts on the cloth and accumulates nothing.  A substep that skips itself adds
+ * nothing; its replay adds once.  A contribution outside the fixed-point range raises MPM_ERR_RANGE at the next
+ * mpm_sync, as a contact impulse does.
+ * Poses are fixed between two calls of mpm_set_grid_bodies: set the table once per plant step, then run its substeps.
+ * The call needs mpm_finalize, is ordered on the engine's stream and is a synchronisation point; substeps that
+ * mpm_run_substeps still owes are run with the table they were enqueued with before the new one takes effect.
+ * Refused with MPM_ERR_INVALID before anything is enqueued, the previous table staying in force: n > 16; for an analytic
+ * body a kind outside 0-5 or dimensions mpm_collider_t refuses; a sdf_shape that is neither MPM_GB_NO_MESH nor a shape
+ * of this engine; a mode outside 0-2; a friction that is not finite; a non-finite p_WB, v or w; an R_WB that is not a
+ * rotation (|R^T R - I| and |det R - 1| within 1e-4); and any partitioned or multi-rank engine (mpm_dist_init,
+ * mpm_chain_*, mpm_team_*: shared blocks are updated by two ranks there and would count their impulses twice) -- this
+ * call on such an engine, and mpm_dist_init, the halo, chain, team and world substeps on an engine with a non-empty
+ * table.  mpm_update_grid_from_sums and mpm_substep_end refuse MPM_BC_BODIES with a non-empty table. */
+#define MPM_BC_BODIES 5                 /* mpm_bc value: walls + the table of mpm_set_grid_bodies */
+#define MPM_GB_NO_MESH 0xFFFFFFFFu
+typedef struct mpm_grid_body {
+    mpm_collider_t shape;   /* kind 0-5, body, p_WB, R_WB, dims, v, w: meanings and validity rules of mpm_collider_t */
+    uint32_t sdf_shape;     /* MPM_GB_NO_MESH, or a shape id of mpm_sdf_shape_from_mesh: then kind and dims are ignored */
+    int32_t mode;           /* MPM_GC_FIXED, MPM_GC_SLIP_APPROACHING, MPM_GC_SLIP */
+    float friction;         /* < 0: the engine's material.sdf_friction, as in mpm_grid_collider_t */
+} mpm_grid_body_t;
+/* Replaces the table (n <= 16; n = 0 clears it, bodies may then be NULL). */
+MPM_API int mpm_set_grid_bodies(mpm_handle_t h, size_t n, const mpm_grid_body_t *bodies);
+/* The table as given: min(n, capacity) entries into out (may be NULL when capacity is 0), n into *n_out. */
+MPM_API int mpm_get_grid_bodies(mpm_handle_t h, mpm_grid_body_t *out, size_t capacity, size_t *n_out);
 
 /* Runs n substeps with HIP events around every kernel group on the engine's
  * stream and returns the mean milliseconds per substep of each phase
