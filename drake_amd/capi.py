@@ -117,6 +117,53 @@ class GridBody(C.Structure):
         self.sdf_shape, self.mode, self.friction = int(sdf_shape), int(mode), float(friction)
 
 
+FF_ACCEL, FF_DRAG, FF_NORMAL_DRAG = 0, 1, 2
+FF_QUADRATIC, FF_REGION = 1, 2
+MAX_FORCE_FIELDS = 8
+
+
+class ForceField(C.Structure):
+    """mpm_force_field_t: an external force field per unit mass on u(x) = u0 + G (x - x0) -- kind FF_ACCEL (u),
+    FF_DRAG (-gamma (v - u)) or FF_NORMAL_DRAG (-gamma s n, s = (v - u) . n, faces only; quadratic=True: -gamma s |s| n);
+    region = (lo, hi) restricts it to the closed box lo <= x <= hi."""
+    _fields_ = [("kind", C.c_int32), ("flags", C.c_uint32), ("gamma", C.c_float), ("u0", C.c_float * 3),
+                ("G", C.c_float * 9), ("x0", C.c_float * 3), ("lo", C.c_float * 3), ("hi", C.c_float * 3)]
+
+    def __init__(self, kind=FF_ACCEL, gamma=0.0, u0=(0, 0, 0), G=None, x0=(0, 0, 0), region=None, quadratic=False, flags=None):
+        super().__init__()
+        self.kind, self.gamma = int(kind), float(gamma)
+        self.u0[:] = [float(a) for a in u0]
+        self.G[:] = [float(a) for a in (np.asarray(G, np.float64).reshape(9) if G is not None else [0.0] * 9)]
+        self.x0[:] = [float(a) for a in x0]
+        f = FF_QUADRATIC if quadratic else 0
+        if region is not None:
+            f |= FF_REGION
+            self.lo[:] = [float(a) for a in region[0]]
+            self.hi[:] = [float(a) for a in region[1]]
+        self.flags = f if flags is None else int(flags)
+
+
+def force_field_acceleration(fields, x, v, director=None):
+    """mpm_force_field_acceleration: the acceleration (n, 3) float32 of particles at x with velocities v under the table
+    `fields` (list of ForceField), evaluated on the host by the function ParticleToGrid calls; director: (n, 3) F[:,2]
+    of face particles, None for vertex particles.  Needs no engine and no GPU."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 3)
+    v = np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+    assert v.shape == x.shape
+    d = None
+    if director is not None:
+        d = np.ascontiguousarray(director, np.float32).reshape(-1, 3)
+        assert d.shape == x.shape
+    out = np.zeros_like(x)
+    arr = (ForceField * max(len(fields), 1))(*fields)
+    rc = lib.mpm_force_field_acceleration(arr, len(fields), len(x), x.ctypes.data, v.ctypes.data,
+                                          d.ctypes.data if d is not None else None, out.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return out
+
+
 def grid_collider_preset(mpm_bc: int, sdf_friction: float = 0.3):
     """The collider table that reproduces the reference's scene mpm_bc (cuda_mpm_kernels.cuh:673-774)."""
     lib = load_library()
@@ -223,7 +270,7 @@ SYMBOLS = [
     "mpm_debug_contact_count", "mpm_chain_direct_base", "mpm_chain_direct_connect_local", "mpm_team_prepare", "mpm_team_connect",
     "mpm_world_coupled_substeps", "mpm_set_pins", "mpm_set_body_motions", "mpm_pins_inside_collider", "mpm_get_pins",
     "mpm_add_qr_cloth_with_material", "mpm_get_cloth_info", "mpm_cloth_count", "mpm_set_grid_bodies",
-    "mpm_get_grid_bodies",
+    "mpm_get_grid_bodies", "mpm_set_force_fields", "mpm_get_force_fields", "mpm_force_field_acceleration",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -340,6 +387,9 @@ def load_library(build: bool = True):
         "mpm_get_pins": [vp, vp, sz, P(sz)],
         "mpm_set_grid_bodies": [vp, sz, vp],
         "mpm_get_grid_bodies": [vp, vp, sz, P(sz)],
+        "mpm_set_force_fields": [vp, sz, vp],
+        "mpm_get_force_fields": [vp, vp, sz, P(sz)],
+        "mpm_force_field_acceleration": [vp, sz, sz, vp, vp, vp, vp],
         "mpm_add_qr_cloth_with_material": [vp, vp, vp, sz, vp, sz, vp],
         "mpm_get_cloth_info": [vp, sz, P(sz), P(sz), P(sz), P(sz), vp],
         "mpm_cloth_count": [vp, P(sz)],
@@ -580,6 +630,20 @@ class GpuMpm:
         list clears it).  Set once per plant step, then run its substeps."""
         arr = (GridBody * max(len(bodies), 1))(*bodies)
         self._ck(self.lib.mpm_set_grid_bodies(self.h, len(bodies), arr))
+
+    def set_force_fields(self, fields):
+        """Table of external force fields evaluated inside ParticleToGrid (list of ForceField, at most 8; an empty list
+        clears it).  A synchronisation point; owed substeps run with the table of their call first."""
+        arr = (ForceField * max(len(fields), 1))(*fields)
+        self._ck(self.lib.mpm_set_force_fields(self.h, len(fields), arr))
+
+    def get_force_fields(self):
+        """mpm_get_force_fields: the table in force, a list of ForceField."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_force_fields(self.h, None, 0, C.byref(n)))
+        arr = (ForceField * max(int(n.value), 1))()
+        self._ck(self.lib.mpm_get_force_fields(self.h, arr, int(n.value), C.byref(n)))
+        return [arr[k] for k in range(int(n.value))]
 
     def get_grid_bodies(self):
         """mpm_get_grid_bodies: the table in force, a list of GridBody."""

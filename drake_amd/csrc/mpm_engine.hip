@@ -264,8 +264,19 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
         if (exact) hipLaunchKernelGGL((k_p2g<F, 1>), g, b, 0, e->stream, p, dt);                   \
         else hipLaunchKernelGGL((k_p2g<F, 0>), g, b, 0, e->stream, p, dt);                         \
     } while (0)
-    if (forces == 1) MPM_P2G_LAUNCH(1);
+    // (an engine with a table of force fields: the instances that evaluate it, mpm_set_force_fields)
+#define MPM_P2G_LAUNCH_FIELDS(F)                                                                                      \
+    do {                                                                                                              \
+        const ForceFieldTable* t = e->d_force_fields;                                                                 \
+        if (exact) hipLaunchKernelGGL((k_p2g<F, 1, 1, ForceFieldTable>), g, b, 0, e->stream, p, dt, t);        \
+        else hipLaunchKernelGGL((k_p2g<F, 0, 1, ForceFieldTable>), g, b, 0, e->stream, p, dt, t);              \
+    } while (0)
+    if (!e->force_fields.empty()) {
+        if (forces == 1) MPM_P2G_LAUNCH_FIELDS(1);
+        else MPM_P2G_LAUNCH_FIELDS(0);
+    } else if (forces == 1) MPM_P2G_LAUNCH(1);
     else MPM_P2G_LAUNCH(0);
+#undef MPM_P2G_LAUNCH_FIELDS
 #undef MPM_P2G_LAUNCH
     e->last_tile_kernel = 1;
 }
@@ -781,15 +792,29 @@ static int pins_ready(mpm_engine* e) {
     ps.table_dirty = false;
     return 0;
 }
-// partitioned and multi-rank engines have no pins, no per-cloth materials and no grid bodies (out of scope)
+// partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies and no force fields (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on a multi-material engine (mpm_add_qr_cloth_with_material)");
     if (!e->grid_bodies.empty())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with grid bodies (mpm_set_grid_bodies)");
+    if (!e->force_fields.empty())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with force fields (mpm_set_force_fields)");
     return 0;
 }
+// An explicit linear drag beyond dt * gamma = 1 reverses the relative velocity: the substep entry points that take a dt
+// refuse it, once per call, before anything is enqueued.  (An engine without a table never gets past the first test.)
+static int fields_stable(const mpm_engine* e, float dt) {
+    if (e->force_fields.empty()) return 0;
+    if (!((double)dt * e->force_fields_gamma <= 1.0))
+        return fail(MPM_ERR_INVALID, "force fields: dt * (sum of gamma over the linear drag fields) = " +
+                                         std::to_string((double)dt * e->force_fields_gamma) + " > 1: the explicit drag is unstable -- reduce dt or gamma");
+    return 0;
+}
+// The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
+// takes it as 0, i.e. every batch starts with its re-sort check launches.
+static float quiet_hint(const mpm_engine* e, float seconds) { return e->force_fields.empty() ? seconds : 0.f; }
 
 // ---- the solver calls -----------------------------------------------------
 static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, bool allow_gate, bool lean = false);
@@ -1017,6 +1042,8 @@ int mpm_calc_fem_state_and_force(mpm_handle_t e, float dt) try {
 } MPM_CATCH_ALL
 
 int mpm_particle_to_grid(mpm_handle_t e, float dt) try {
+    if (e && e->finalized)
+        if (int rc = fields_stable(e, dt)) return rc;   // (before the phase is held back or enqueued)
     if (e && can_defer(e) && e->pend.n == 2 && dt == e->pend.dt) {
         READY_NO_SETTLE(e);
         e->pend.n = 3;
@@ -1091,6 +1118,7 @@ int mpm_update_grid_from_sums(mpm_handle_t e, int bc) try {
 
 int mpm_substep_begin(mpm_handle_t e, float dt) try {
     READY(e);
+    if (int rc = fields_stable(e, dt)) return rc;
     may_resort(e, dt);
     launch_rebuild(e, e->dp);
     launch_fem_p2g(e, e->dp, dt);
@@ -1708,7 +1736,7 @@ static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, boo
     // pending without their check skip themselves and are run again by settle().
     // (a quiet time left over from the settle() that has just read it also stands for "no re-sort pending, nothing
     // has touched the state since": the check that otherwise follows every other call is not needed either)
-    const bool quiet = allow_gate && e->quiet_factor * e->quiet_left > dt;
+    const bool quiet = allow_gate && e->quiet_factor * quiet_hint(e, e->quiet_left) > dt;
     bool check = !allow_gate || (e->force_check && !quiet) || e->check_every <= 1 || e->dp.dist.on;
     if (!check) {
         if (quiet) {
@@ -1731,6 +1759,7 @@ static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, boo
 int mpm_run_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     READY_NO_SETTLE(e);
     if (int rc = pins_ready(e)) return rc;
+    if (int rc = fields_stable(e, dt)) return rc;
     // owed substeps are run with the parameters they were enqueued with: settle before these change (and before phase
     // calls that were held back, which come first)
     if (e->pend.n || (e->maybe_owed && (dt != e->owed_dt || bc != e->owed_bc || e->grid_colliders_version != e->owed_gcv)))
@@ -1751,6 +1780,7 @@ int mpm_run_substeps(mpm_handle_t e, int n, float dt, int bc) try {
 int mpm_profile_substeps(mpm_handle_t e, int n, float dt, int bc, float* phase_ms, float* total_ms) try {
     READY(e);
     if (int rc = pins_ready(e)) return rc;
+    if (int rc = fields_stable(e, dt)) return rc;
     REQUIRE(n > 0 && n <= 4096, "n out of range");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
@@ -2813,7 +2843,7 @@ static int coupled_substep(mpm_engine* e, int s, int n, const mpm_coupled_params
         launch_contact_watch(e, e->dp, sp->watch_base);
         sp->spec = true;
         sp->spec_check = false;
-        sp->spec_quiet_left = e->ct_quiet_left;   // (what the solve's publication said is left of the quiet time)
+        sp->spec_quiet_left = quiet_hint(e, e->ct_quiet_left);   // (what the solve's publication said is left of the quiet time)
     }
     return 0;
 }
@@ -2859,7 +2889,7 @@ static int coupled_chunk(mpm_engine* e, int s, int n, float dt, const GridCollid
         e->last_contact = mpm_contact_stats_t{};
         e->last_contact_reused = false;
     }
-    sp->spec_quiet_left = c.need_rebuild || c.error ? 0.f : std::max(0.f, c.quiet_time - c.time_since_resort);
+    sp->spec_quiet_left = c.need_rebuild || c.error ? 0.f : quiet_hint(e, std::max(0.f, c.quiet_time - c.time_since_resort));
     sp->spec_check = skipped > 0;   // (whatever made them skip: the repeated ones carry their checks)
     // (an error flag ends the speculation too: the coupled substep that follows reports it where it always was)
     if (hit || c.error) {
@@ -2883,6 +2913,7 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
     REQUIRE(n_colliders <= 1024, "too many colliders");
     if (int rc = validate_colliders(n_colliders, colliders)) return rc;   // (before any substep is enqueued)
     if (int rc = pins_ready(e)) return rc;
+    if (int rc = fields_stable(e, prm->dt)) return rc;
     // colliders: the call's analytic ones and the engine's mesh colliders (mpm_set_sdf_colliders)
     const size_t n_all = n_colliders + e->cb.mesh_set.size();
     if (int rc = validate_mesh_bodies(e)) return rc;
@@ -3189,3 +3220,71 @@ int mpm_get_grid_bodies(mpm_handle_t e, mpm_grid_body_t* out, size_t capacity, s
     if (n_out) *n_out = set.size();
     return 0;
 } MPM_CATCH_ALL
+
+// ---- external force fields (mpm_set_force_fields, mpm_get_force_fields, mpm_force_field_acceleration; mpm_fields.h) ----
+static int validate_force_fields(size_t n, const mpm_force_field_t* f) {
+    static_assert(sizeof(ForceField) == sizeof(mpm_force_field_t), "force field layouts differ");
+    REQUIRE(n <= (size_t)MAX_FORCE_FIELDS, "too many force fields (at most 8)");
+    REQUIRE(n == 0 || f, "null force field array");
+    for (size_t k = 0; k < n; ++k) {
+        const mpm_force_field_t& q = f[k];
+        REQUIRE(q.kind >= MPM_FF_ACCEL && q.kind <= MPM_FF_NORMAL_DRAG, "force field: unknown kind");
+        REQUIRE((q.flags & ~(uint32_t)(MPM_FF_QUADRATIC | MPM_FF_REGION)) == 0, "force field: unknown flags");
+        REQUIRE(std::isfinite(q.gamma) && finite_n(q.u0, 3) && finite_n(q.G, 9) && finite_n(q.x0, 3) && finite_n(q.lo, 3) &&
+                    finite_n(q.hi, 3),
+                "force field: a number is not finite");
+        REQUIRE(q.gamma >= 0.f, "force field: gamma < 0");
+        REQUIRE(q.lo[0] <= q.hi[0] && q.lo[1] <= q.hi[1] && q.lo[2] <= q.hi[2], "force field: lo > hi");
+    }
+    return 0;
+}
+
+extern "C" {
+
+int mpm_set_force_fields(mpm_handle_t e, size_t n, const mpm_force_field_t* fields) try {
+    READY_NO_SETTLE(e);
+    REQUIRE(!multi_rank(e), "force fields are not available on a partitioned or multi-rank engine");
+    if (int rc = validate_force_fields(n, fields)) return rc;
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    double gamma = 0.0;
+    if (n) {
+        ForceFieldTable table;
+        std::memset(&table, 0, sizeof(table));
+        table.n = (int)n;
+        std::memcpy(table.f, fields, n * sizeof(ForceField));
+        for (size_t k = 0; k < n; ++k)
+            if (fields[k].kind != MPM_FF_ACCEL && !(fields[k].flags & MPM_FF_QUADRATIC)) gamma += (double)fields[k].gamma;
+        if (!e->d_force_fields)
+            if (int rc = e->dalloc(&e->d_force_fields, 1, true)) return rc;
+        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
+        H2D(e, e->d_force_fields, &table, sizeof(table));
+    }
+    e->force_fields.assign(fields, fields + n);
+    e->force_fields_gamma = gamma;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_get_force_fields(mpm_handle_t e, mpm_force_field_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    const std::vector<mpm_force_field_t>& set = e->force_fields;
+    std::copy(set.begin(), set.begin() + std::min(capacity, set.size()), out);
+    if (n_out) *n_out = set.size();
+    return 0;
+} MPM_CATCH_ALL
+
+// host code only: no device is touched
+int mpm_force_field_acceleration(const mpm_force_field_t* fields, size_t n_fields, size_t n, const float* x, const float* v,
+                                 const float* director, float* acc_out) try {
+    if (int rc = validate_force_fields(n_fields, fields)) return rc;
+    REQUIRE(n == 0 || (x && v && acc_out), "null argument");
+    const ForceField* f = reinterpret_cast<const ForceField*>(fields);
+    const float zero[3] = {0.f, 0.f, 0.f};
+    for (size_t k = 0; k < n; ++k)
+        force_field_acceleration(f, (int)n_fields, x + 3 * k, v + 3 * k, director ? director + 3 * k : zero, director != nullptr,
+                                 acc_out + 3 * k);
+    return 0;
+} MPM_CATCH_ALL
+
+}  // extern "C"

@@ -196,6 +196,10 @@ struct mpm_engine {
     std::vector<mpm_grid_body_t> grid_bodies;   // the caller's table, as given
     GridBodyTable* d_grid_bodies = nullptr;     // ... as the kernel reads it
     int grid_bodies_kinds = 0;                  // the instance it needs (bit 0: an ellipsoid, bit 1: a mesh body)
+    // external force fields (mpm_set_force_fields; mpm_fields.h): a non-empty table selects k_p2g's FIELDS instances
+    std::vector<mpm_force_field_t> force_fields;   // the caller's table, as given
+    ForceFieldTable* d_force_fields = nullptr;     // ... as the kernel reads it
+    double force_fields_gamma = 0.0;               // sum of gamma over the linear drags: dt * this <= 1 (fields_stable)
     // fixed constraints (mpm_set_pins, mpm_set_body_motions; k_pin in mpm_pins.h)
     struct PinState {
         std::vector<mpm_pin_t> set;              // the caller's pins, in order

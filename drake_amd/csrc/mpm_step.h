@@ -7,6 +7,7 @@
 //   k_g2p     : GridToParticle              (cuda_mpm_kernels.cuh:798-924)
 #pragma once
 #include "mpm_device.h"
+#include "mpm_fields.h"
 
 namespace mpm {
 
@@ -256,8 +257,16 @@ constexpr int P2G_WAVES = 8, P2G_THREADS = 64 * P2G_WAVES;
 // one step of the per-cell contraction: rows = the 16 columns of the staged particles (A operand), columns = 16 node
 // rows (B operand); the transposed form of round 6, see point 3 above and DESIGN.md section 3.2
 MPM_DEV f32x4 p2g_mfma(float y, float w, f32x4 acc) { return __builtin_amdgcn_mfma_f32_16x16x4f32(y, w, acc, 0, 0, 0); }
-template <int FORCES, int EXACT>
-__global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G_WAVES / 2, P2G_WAVES / 2))) void k_p2g(DP p, float dt) {
+// FIELDS: 1 = the engine has a table of external force fields (mpm_set_force_fields, mpm_fields.h): every particle's
+// acceleration a(x, v) is evaluated where its staged momentum column is formed and enters it as m (a dt) -- no pass of
+// its own over the particles, every record it needs is in the lane's registers.  The table's pointer is the one
+// argument of the pack TABLE (= ForceFieldTable), which only these instances have: the FIELDS = 0 instances keep their
+// arguments and their code (launch_p2g picks the instance).  __restrict__: the table is read-only to the kernel, its
+// loads are scalar.
+MPM_DEV const ForceFieldTable* p2g_field_table(const ForceFieldTable* t) { return t; }
+template <int FORCES, int EXACT, int FIELDS = 0, typename... TABLE>
+__global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G_WAVES / 2, P2G_WAVES / 2))) void k_p2g(DP p, float dt, const TABLE* __restrict__... table) {
+    static_assert(sizeof...(TABLE) == FIELDS, "the table is the argument of the FIELDS = 1 instances only");
     if (gated_out(p)) return;
     // chain substep: the entry counters of the halo send buffers, which the k_grid<0> behind this kernel fills
     if (blockIdx.x == 0 && threadIdx.x < 2 && p.halo_hdr[threadIdx.x]) p.halo_hdr[threadIdx.x][0] = 0u;
@@ -428,6 +437,14 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
                 } else {
 #pragma unroll
                     for (int r = 0; r < 3; ++r) fext[r] = cur.frc[r] * dt;
+                }
+                if constexpr (FIELDS != 0) {
+                    // (uniform loads: every lane reads the same entries of the table)
+                    const ForceFieldTable* ft = p2g_field_table(table...);
+                    float a[3];
+                    force_field_acceleration(ft->f, ft->n, cur.x, cur.v, cur.tb, is_face, a);
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) fext[r] = fmaf(m, a[r] * dt, fext[r]);
                 }
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {

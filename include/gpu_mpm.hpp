@@ -178,6 +178,19 @@ struct GpuMpmState {
         mpm_check(mpm_get_grid_bodies(h_, out.data(), n, &n));
         return out;
     }
+    // Extension: external force fields evaluated inside ParticleToGrid (mpm_set_force_fields): off-axis gravity,
+    // springs, drag towards a wind, drag along the cloth's normal.  Coefficients are per unit mass: a Drake force
+    // density with coefficient c per unit volume maps to gamma = c / rho.  Once per plant step, before its substeps.
+    void SetForceFields(const std::vector<mpm_force_field_t>& fields) {
+        mpm_check(mpm_set_force_fields(h_, fields.size(), fields.data()));
+    }
+    std::vector<mpm_force_field_t> GetForceFields() const {
+        size_t n = 0;
+        mpm_check(mpm_get_force_fields(h_, nullptr, 0, &n));
+        std::vector<mpm_force_field_t> out(n);
+        mpm_check(mpm_get_force_fields(h_, out.data(), n, &n));
+        return out;
+    }
     std::vector<Vec3<T>>& positions_host() { return h_positions_; }
     const std::vector<Vec3<T>>& positions_host() const { return h_positions_; }
     ExternalSpatialForce<T>& external_forces_host() { return h_external_forces_; }

@@ -680,6 +680,62 @@ MPM_API int mpm_set_grid_bodies(mpm_handle_t h, size_t n, const mpm_grid_body_t 
 /* The table as given: min(n, capacity) entries into out (may be NULL when capacity is 0), n into *n_out. */
 MPM_API int mpm_get_grid_bodies(mpm_handle_t h, mpm_grid_body_t *out, size_t capacity, size_t *n_out);
 
+/* ---- External force fields on the cloth (an extension) ----
+ * Body loads other than the material's one gravity on one axis: off-axis gravity, springs towards a point, the
+ * centrifugal term of a rotating frame, air drag towards a wind, drag along the cloth's normal.  A table of at most
+ * MPM_MAX_FORCE_FIELDS fields.  Each field has an affine vector field u(x) = u0 + G (x - x0), G row-major 3 x 3, and,
+ * with MPM_FF_REGION, acts only on particles with lo <= x <= hi (closed, per axis, tested on the particle's float
+ * position).  ALL COEFFICIENTS ARE PER UNIT MASS: a particle's acceleration is the sum, in table order, over the fields
+ * whose region contains it, of
+ *   MPM_FF_ACCEL        u(x)                                  face and vertex particles
+ *   MPM_FF_DRAG         -gamma (v - u(x))                     face and vertex particles; gamma in 1/s, u the wind velocity
+ *   MPM_FF_NORMAL_DRAG  -gamma s n, s = (v - u(x)) . n        face particles only; with MPM_FF_QUADRATIC -gamma s |s| n
+ *                                                             (gamma then in 1/m)
+ * with n = d / |d|, d = F[:,2] the face's director (its sign cancels; a field contributes nothing where |d|^2 < 1e-30),
+ * 1 / |d| formed with a correctly rounded square root and division whatever mpm_set_fast_math says.  The force on a
+ * particle is m a with m the mass ParticleToGrid forms (volume x density, per-cloth densities included); a caller
+ * with a coefficient c per unit VOLUME (a force density c (u - v), N/m^3 per m/s) passes gamma = c / rho.
+ * Evaluation is explicit, inside ParticleToGrid, on the state it reads: m a dt joins the particle's momentum; a face
+ * particle's velocity is the mean of its corners' that CalcFemStateAndForce wrote.  It works with pins, per-cloth
+ * materials, grid bodies, deterministic mode, fast math and the coupled path.
+ * Stability: every substep entry point that takes a dt (mpm_particle_to_grid, mpm_substep_begin, mpm_substep,
+ * mpm_run_substeps, mpm_run_coupled_substeps, mpm_profile_substeps) returns MPM_ERR_INVALID, before anything is
+ * enqueued, when dt * (sum of gamma over the MPM_FF_DRAG and linear MPM_FF_NORMAL_DRAG fields) > 1: an explicit drag
+ * beyond that reverses the relative velocity.  Quadratic fields cannot be bounded this way (their rate is gamma |s|):
+ * keeping dt gamma |s| well below 1 is the caller's responsibility.
+ * mpm_set_force_fields needs mpm_finalize, is ordered on the engine's stream and is a synchronisation point; substeps
+ * that mpm_run_substeps still owes are run with the table they were enqueued with before the new one takes effect.
+ * Time-dependent fields: set the table between batches.  While a table is set the engine does not use the re-sort's
+ * quiet-time estimate (which assumes gravity alone) to omit re-sort check launches.
+ * Refused with MPM_ERR_INVALID, the previous table staying in force: n > 8; an unknown kind or unknown flags; a number
+ * that is not finite; gamma < 0; lo > hi on any axis (checked whether or not MPM_FF_REGION is set); any partitioned or
+ * multi-rank engine -- this call on such an engine, and mpm_dist_init, the halo, chain, team and world substeps on an
+ * engine with a non-empty table. */
+#define MPM_MAX_FORCE_FIELDS 8
+#define MPM_FF_ACCEL 0
+#define MPM_FF_DRAG 1
+#define MPM_FF_NORMAL_DRAG 2
+#define MPM_FF_QUADRATIC 1u             /* flags: MPM_FF_NORMAL_DRAG is quadratic in the normal speed */
+#define MPM_FF_REGION 2u                /* flags: the field acts inside lo <= x <= hi only */
+typedef struct mpm_force_field {
+    int32_t kind;           /* MPM_FF_ACCEL, MPM_FF_DRAG, MPM_FF_NORMAL_DRAG */
+    uint32_t flags;         /* MPM_FF_QUADRATIC | MPM_FF_REGION */
+    float gamma;            /* drag rate per unit mass, >= 0 (ignored by MPM_FF_ACCEL) */
+    float u0[3];            /* u(x) = u0 + G (x - x0) */
+    float G[9];             /* row-major */
+    float x0[3];
+    float lo[3], hi[3];     /* the region (MPM_FF_REGION); lo <= hi always */
+} mpm_force_field_t;
+/* Replaces the table (n <= 8; n = 0 clears it, fields may then be NULL). */
+MPM_API int mpm_set_force_fields(mpm_handle_t h, size_t n, const mpm_force_field_t *fields);
+/* The table as given: min(n, capacity) entries into out (may be NULL when capacity is 0), n into *n_out. */
+MPM_API int mpm_get_force_fields(mpm_handle_t h, mpm_force_field_t *out, size_t capacity, size_t *n_out);
+/* The acceleration of n particles under a table, on the host (no handle, no device): the inline function
+ * ParticleToGrid calls, compiled for the host.  x, v, acc_out: n x 3 floats; director: n x 3 floats (F[:,2] of face
+ * particles), or NULL for vertex particles.  The table is validated as by mpm_set_force_fields. */
+MPM_API int mpm_force_field_acceleration(const mpm_force_field_t *fields, size_t n_fields, size_t n, const float *x,
+                                         const float *v, const float *director, float *acc_out);
+
 /* Runs n substeps with HIP events around every kernel group on the engine's
  * stream and returns the mean milliseconds per substep of each phase
  * (phase_ms[MPM_PHASE_COUNT]) and of the whole substep. */
