@@ -568,13 +568,13 @@ static int download_contacts(mpm_engine* e, uint32_t* particle, uint32_t* body, 
 
 // `sorted`: the arrays the solve's kernels read after the sort (the sorted keys / order may sit in the second pair of
 // buffers: radix_sort_pairs does not copy them back); otherwise the pair the set-up fills
-static ContactDev make_contact_dev(mpm_engine* e, float dt, float mu, float k, float d, int max_iters, bool sorted = true) {
+static ContactDev make_contact_dev(mpm_engine* e, const SolveParams& prm, bool sorted = true) {
     ContactBuffers& b = e->cb;
     ContactDev c{};
     c.n = b.dev_counted ? -1 : (int)b.n;
     c.stride = (int)b.cap;
-    c.max_iters = max_iters;
-    c.dt = dt; c.mu = mu; c.k = k; c.d = d;
+    c.max_iters = prm.max_iters;
+    c.dt = prm.dt; c.mu = prm.mu; c.k = prm.stiffness; c.d = prm.damping;
     c.epsv = e->mat.epsv;
     c.relax = 0.3f;   // jacobi_relax_coeff, cuda_mpm_solver.cu:239
     if (e->ct_relax > 0.f) c.relax = e->ct_relax;   // (tests: overshoot on purpose, so that the backtracking has work)
@@ -668,6 +668,108 @@ static int dist_allreduce(mpm_engine* e, double* dev, size_t n) {
     return 0;
 }
 
+// ---- the solve's host driver: one engine, or the local ranks of a team ------------------------------------------------
+// What sizes an attempt's launches.  n: the count, or -- counted on the device -- a bound (every kernel strides over its
+// grid and reads the count itself): the last solve's count with some room, at most the buffers' capacity.
+// bits: keys are compact cells (active block * 64 + cell).  How many blocks are active the host knows from the last
+// solve's publication (it changes with re-sorts only); with config 3's 1805 blocks that is 18 key bits, two passes of 9,
+// instead of 22 bits for the table capacity, three passes of 8.  Checked on the device as well: keys wider than the guess
+// refuse the solve (CT_DONE_STALE).
+struct SolveGeometry {
+    size_t n;
+    unsigned gc, n_tile_wg;
+    int bits;
+};
+static SolveGeometry solve_geometry(const ContactBuffers& b, const DP& p, bool full_setup) {
+    SolveGeometry g;
+    g.n = b.n;
+    if (b.dev_counted) g.n = b.n_hint && !full_setup ? std::min<size_t>(b.cap, b.n_hint + b.n_hint / 8 + 256) : b.cap;
+    g.n = std::max<size_t>(g.n, 1);
+    g.gc = (unsigned)std::min<size_t>((g.n + 255) / 256, 2048);
+    g.n_tile_wg = (unsigned)std::min<size_t>((g.n + CT_TILE - 1) / CT_TILE, CT_TILE_WG);
+    const size_t blocks = b.n_active_hint && !full_setup ? std::min<size_t>((size_t)b.n_active_hint * 2, p.capA) : p.capA;
+    g.bits = 1;
+    while (((size_t)1 << g.bits) < blocks * 64) ++g.bits;
+    return g;
+}
+
+// One engine's share of an attempt: what its launches are made of
+struct SolveCtx {
+    mpm_engine* e;
+    SolveGeometry g;
+    ContactDev c;
+    TeamDev t;   // (a single engine: all zero, k_ct_decide's default)
+};
+// What a finished (or refused) solve left for the host: the mailbox's last words
+struct SolveOutcome {
+    MailboxState mb;
+    ContactState st;          // (only the paths that copy the state back fill it: partitioned domain)
+    bool have_state = false;
+    struct {                  // (host-driven exact search: per iteration, and of the last one)
+        std::vector<float> res, energy;
+        std::vector<int> ls;
+        float alpha_last = 0.f, E0_last = 0.f;
+    } log;
+};
+// launched for local rank i between the solve's last update and its impulses (GridToParticle of a coupled substep), or empty
+using BeforeImpulse = std::function<void(size_t)>;
+static bool refused(int done) { return done == CT_DONE_FAULT || done == CT_DONE_STALE || done == CT_DONE_CORRUPT; }
+// (MPM_CT_FORCE_DIST=1, tests: a partitioned engine of ONE rank takes the distributed paths too -- split direction
+// kernels, sums through the all-reduce -- so that they can run on a box with one GPU)
+static bool partitioned_solve(const mpm_engine* e) { return e->dp.dist.on && (e->dp.dist.world > 1 || e->ct_force_dist); }
+
+// grid-stride contact part of k_ct_ls: 4 lanes per contact
+// (always all CT_ROWS_CON rows: tile t goes to row t mod CT_ROWS_CON whatever the count or the buffers' capacity, so
+// the energy sums -- and with them every `E1 <= E0` decision -- do not depend on what sized the launch; workgroups
+// without a tile write a row of zeros), then CT_ROWS workgroups of its grid-stride node part
+static void launch_ls(const SolveCtx& x, int exact, float alpha) {
+    hipLaunchKernelGGL(k_ct_ls, dim3(CT_ROWS_CON + CT_ROWS), dim3(CT_WG), 0, x.e->stream, x.e->dp, x.c, CT_ROWS_CON, exact, alpha);
+}
+static void launch_decide(const SolveCtx& x, int exact, int phase) {
+    hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, x.e->stream, x.c, CT_DIR_WG, CT_ROWS_CON, CT_ROWS, exact, phase, x.t);
+}
+static void launch_apply(const SolveCtx& x, int mode) {
+    hipLaunchKernelGGL(k_ct_apply, dim3(CT_ROWS), dim3(CT_WG), 0, x.e->stream, x.e->dp, x.c, mode);
+}
+
+// The set-up's first part: keys, then the sort and the ContactDev of the sorted arrays (a team puts each rank's status
+// between the two).  Returns the ContactDev of the arrays as the pair generation left them.
+// The pairs name particles by the caller's slot; the engine's internal slots change with every re-sort (which the device
+// decides by itself, e.g. inside a RebuildMapping between CopyContactPairs and this call): k_ct_keys resolves them again,
+// from the kept caller indices.
+static ContactDev enqueue_keys(const SolveCtx& x, const SolveParams& prm, bool reuse, bool full_setup, bool team) {
+    mpm_engine* e = x.e;
+    ContactBuffers& b = e->cb;
+    const SolveGeometry& g = x.g;
+    e->last_contact_reused = false;
+    e->last_contact_gated = false;
+    b.solves += 1;
+    const ContactDev c_in = make_contact_dev(e, prm, /* sorted = */ false);
+    hipLaunchKernelGGL(k_ct_keys, dim3(1024), dim3(256), 0, e->stream, e->dp, c_in, (const uint32_t*)b.api_idx, (const int*)e->d_pids_api,
+                       b.slot, b.published, b.solves, g.bits, (int)std::min<size_t>(g.n, 0x7FFFFFFF), reuse ? 1 : 0, full_setup ? 1 : 0,
+                       b.gen_stamp, team ? 1 : 0);
+    return c_in;
+}
+static int enqueue_sort(SolveCtx* x, const SolveParams& prm, bool reuse) {
+    mpm_engine* e = x->e;
+    ContactBuffers& b = e->cb;
+    const SolveGeometry& g = x->g;
+    if (!reuse) {
+        // CT_NO_CELL has all those bits set and more: it sorts behind every real cell as long as
+        // one more bit takes part
+        // (a sort's tiles are fixed chunks, not a stride over the grid: with the count on the device its launch covers
+        // the guess `n` -- the last solve's count with an eighth of room --, and k_ct_keys refuses the solve when the
+        // count has outgrown it: a sheet of the stack landing doubles the count from one substep to the next, once)
+        bool in_alt = false;
+        if (radix_sort_pairs(e->stream, b.key, b.order, b.key2, b.order2, b.sort_hist, g.n, std::min(g.bits + 1, 31), &in_alt,
+                             b.dev_counted ? &b.st->n : nullptr))
+            return fail(MPM_ERR_HIP, "contact sort failed");
+        b.sorted_in_alt = in_alt;
+    }
+    x->c = make_contact_dev(e, prm);
+    return 0;
+}
+
 // The batched Newton loops: `pattern(i)` enqueues the launches of one iteration (kernels of an iteration that starts
 // after convergence return at once) and returns how many of them PUBLISH the solver state in the host-mapped mailbox
 // (k_ct_decide, k_ct_exact_finish: ContactMailbox).  The host never copies the state back: it polls the mailbox for
@@ -676,33 +778,42 @@ static int dist_allreduce(mpm_engine* e, double* dev, size_t n) {
 // engine's stream each, 8 - 20 per solve); the price is one batch of idle launches at the end.
 // (batch sizes: MPM_CT_BATCH="first,next" overrides the defaults, for measurements)
 static int ct_batch(const mpm_engine* e, int which, int dflt) { return e->ct_batch[which] > 0 ? e->ct_batch[which] : dflt; }
+// (a search that never terminates cannot happen -- the root finder stops after 200 evaluations, which in float it often
+// needs: |dx| < 3e-9 is out of reach -- but the launches are bounded too: every Newton iteration may take
+// 200 / CT_PROBES + 1 patterns)
+constexpr int CT_PROBES = 6;   // probes of the exact search per pattern
+static int exact_max_patterns(int max_iters) { return (200 / CT_PROBES + 2) * max_iters + 64; }
 
+// L: the local engines a pattern serves, each with its own mailbox and the same publications; the host waits for the first.
 // speculate = false: one pattern at a time, each waited for before the next is enqueued -- every rank of a partitioned
 // domain then enqueues EXACTLY the same number of patterns (what it sees after pattern k does not depend on how fast its
 // host polls), which patterns that contain a COLLECTIVE need: with speculation two ranks may see "finished" one
 // publication apart and enqueue different numbers of ncclAllReduce calls (round 6: found by reading, the path had only
 // ever run on a ring of one).
 template <class Pattern>
-static int run_batches(mpm_engine* e, Pattern&& pattern, int first_batch, int batch, int max_iters, MailboxState* out,
-                       int max_patterns = 1 << 30, bool speculate = true) {
-    ContactBuffers& b = e->cb;
+static int run_batches(mpm_engine* const* L, size_t n_local, Pattern&& pattern, int first_batch, int batch, int max_iters,
+                       MailboxState* out, int max_patterns = 1 << 30, bool speculate = true) {
+    const unsigned& published = L[0]->cb.published;
     int launched = 0;
     auto enqueue = [&](int count) {
-        for (int q = 0; q < count; ++q) b.published += (unsigned)pattern(launched + q);
+        for (int q = 0; q < count; ++q) {
+            const unsigned pub = (unsigned)pattern(launched + q);
+            for (size_t i = 0; i < n_local; ++i) L[i]->cb.published += pub;
+        }
         launched += count;
     };
     if (!speculate) {
         while (true) {
             enqueue(1);
-            if (int rc = wait_mailbox(e, b.published, out)) return rc;
+            if (int rc = wait_mailbox(L[0], published, out)) return rc;
             if (out->done || out->iters >= max_iters || launched > max_patterns) return 0;
         }
     }
     enqueue(first_batch);
     while (true) {
-        const unsigned older = b.published;                // the last publication of what is enqueued so far
-        enqueue(batch);                                    // speculative: idle if the previous batch finished
-        if (int rc = wait_mailbox(e, older, out)) return rc;
+        const unsigned older = published;                  // the last publication of what is enqueued so far
+        enqueue(batch);                                    // speculative: idle (exchanges included) if the previous batch finished
+        if (int rc = wait_mailbox(L[0], older, out)) return rc;
         if (out->done || out->iters >= max_iters || launched > max_patterns) break;
     }
     return 0;
@@ -716,26 +827,22 @@ static int run_batches(mpm_engine* e, Pattern&& pattern, int first_batch, int ba
 static int profile_contact_iteration(mpm_engine* e, int reps, float* kernel_ms) {
     ContactBuffers& b = e->cb;
     REQUIRE(b.n > 0 && b.last_iters > 0, "mpm_profile_contact_iteration needs a finished mpm_update_contact on this state");
-    const mpm_contact_stats_t& lc = e->last_contact;
-    (void)lc;
     if (int rc = resolve_contact_count(e)) return rc;
-    ContactDev c = make_contact_dev(e, e->last_contact_dt, e->last_contact_mu, e->last_contact_k, e->last_contact_d, 1 << 30);
-    c.force = 1;
-    c.mbox = nullptr;   // (nothing here is waited for through the mailbox)
+    SolveParams prm = e->last_contact_prm;
+    prm.max_iters = 1 << 30;
+    SolveCtx x{e, solve_geometry(b, e->dp, true), make_contact_dev(e, prm), TeamDev{}};   // (launched as the solve launches them)
+    x.c.force = 1;
+    x.c.mbox = nullptr;   // (nothing here is waited for through the mailbox)
     const DP& p = e->dp;
     hipStream_t s = e->stream;
-    const size_t n = b.n;
-    const int n_con_wg = CT_ROWS_CON;   // (as the solve launches it)
-    const int n_grid_wg = CT_ROWS, n_dir_wg = CT_DIR_WG;
-    const unsigned n_tile_wg = (unsigned)std::min<size_t>((n + CT_TILE - 1) / CT_TILE, CT_TILE_WG);
     hipEvent_t ev[5];
-    for (auto& x : ev) HIP_TRY(hipEventCreate(&x));
+    for (auto& ev_k : ev) HIP_TRY(hipEventCreate(&ev_k));
     auto phase = [&](int k) {
         for (int r = 0; r < reps; ++r) {
-            if (k == 0) hipLaunchKernelGGL(k_ct_tile, dim3(n_tile_wg), dim3(256), 0, s, p, c, 0, 0);
-            if (k == 1) hipLaunchKernelGGL(k_ct_node_dir<0>, dim3(n_dir_wg), dim3(CT_WG), 0, s, p, c, 0);
-            if (k == 2) hipLaunchKernelGGL(k_ct_ls, dim3(n_con_wg + n_grid_wg), dim3(CT_WG), 0, s, p, c, n_con_wg, 0, 0.f);
-            if (k == 3) hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 0, 0);
+            if (k == 0) hipLaunchKernelGGL(k_ct_tile, dim3(x.g.n_tile_wg), dim3(256), 0, s, p, x.c, 0, 0);
+            if (k == 1) hipLaunchKernelGGL(k_ct_node_dir<0>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, x.c, 0);
+            if (k == 2) launch_ls(x, 0, 0.f);
+            if (k == 3) launch_decide(x, 0, 0);
         }
     };
     phase(0);   // warm-up
@@ -750,269 +857,62 @@ static int profile_contact_iteration(mpm_engine* e, int reps, float* kernel_ms) 
         HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
         kernel_ms[k] = ms / (float)reps;
     }
-    for (auto& x : ev) (void)hipEventDestroy(x);
+    for (auto& ev_k : ev) (void)hipEventDestroy(ev_k);
     HIP_TRY(hipMemsetAsync(b.st, 0, offsetof(ContactState, n), s));
     return 0;
 }
 
-// What a finished (or refused) solve left for the host: the mailbox's last words
-struct SolveOutcome {
-    MailboxState mb;
-    ContactState st;          // (only the paths that copy the state back fill it: partitioned domain)
-    bool have_state = false;
-};
-
-static int solve_once(mpm_engine* e, float dt, float mu, float stiffness, float damping, int exact, int max_iters, bool full_setup,
-                      SolveOutcome* oc, std::vector<float>* s_res, std::vector<int>* s_ls, std::vector<float>* s_energy,
-                      float* s_alpha_last, float* s_E0_last, const std::function<void()>& before_impulse);
-static int contact_stats_from_device(mpm_engine* e);
-static int team_solve(const std::vector<mpm_engine*>& L, float dt, float mu, float stiffness, float damping, int exact, int max_iters,
-                      const std::function<void(size_t)>& before_impulse, std::vector<SolveOutcome>* ocs);
-
-// before_impulse (or empty): launched between the solve's last update and its impulses (mpm_run_coupled_substeps)
-static int update_contact(mpm_engine* e, int frame, int substep, float dt, float mu, float stiffness, float damping,
-                          int dump, int exact, int max_iters, int* iters_out, float* residual_out,
-                          const std::function<void()>& before_impulse) {
-    ContactBuffers& b = e->cb;
-    if (max_iters <= 0) max_iters = 2000;  // cuda_mpm_solver.cu:234
-    if (b.n_bodies == 0) {
-        // the reference requires ReallocateExternelBodies first; size the accumulators to the ids in use
-        return fail(MPM_ERR_INVALID, "call mpm_reallocate_external_bodies before mpm_update_contact");
-    }
-    if (e->dp.dist.on && e->team.on) {
-        // partitioned domain with the TEAM transport: device resident, every rank takes part whatever its own pair count
-        REQUIRE(!dump, "the JSON statistics dump is not available on a partitioned domain");
-        std::vector<SolveOutcome> ocs;
-        std::function<void(size_t)> hook;
-        if (before_impulse) hook = [&](size_t) { before_impulse(); };
-        if (int rc = team_solve({e}, dt, mu, stiffness, damping, exact, max_iters, hook, &ocs)) return rc;
-        if (iters_out) *iters_out = ocs[0].mb.iters;
-        if (residual_out) *residual_out = ocs[0].mb.residual;
-        return 0;
-    }
-    e->last_contact_dt = dt; e->last_contact_mu = mu; e->last_contact_k = stiffness; e->last_contact_d = damping;
-    const bool dist = e->dp.dist.on && (e->dp.dist.world > 1 || e->ct_force_dist);
-    // (the distributed paths are host-driven per iteration anyway: they work with a count the host knows)
-    if (dist)
-        if (int rc = resolve_contact_count(e)) return rc;
-    if (!b.dev_counted && b.n == 0) return 0;   // cuda_mpm_solver.cu:216-217
-    TraceRange tr_all("mpm:UpdateContact");
-    SolveOutcome oc;
-    std::vector<float> s_res, s_energy;
-    std::vector<int> s_ls;
-    float s_alpha_last = 0.f, s_E0_last = 0.f;
-    // A solve may REFUSE to run, in which case none of its kernels has touched the grid and it is repeated:
-    //   CT_DONE_FAULT  pairs counted on the device did not fit the buffers: grow them, make the pairs again;
-    //   CT_DONE_STALE  the set-up was enqueued on a guess that the device found wrong (the previous solve's sorted order
-    //                  reused for a pair list that has changed; sort keys narrower than the active blocks need): full set-up.
-    bool full_setup = false;
-    for (int attempt = 0;; ++attempt) {
-        REQUIRE(attempt < 8, "contact solve: the set-up keeps being refused");
-        s_res.clear(); s_energy.clear(); s_ls.clear();
-        if (int rc = solve_once(e, dt, mu, stiffness, damping, exact, max_iters, full_setup, &oc, &s_res, &s_ls, &s_energy,
-                                &s_alpha_last, &s_E0_last, before_impulse))
-            return rc;
-        if (oc.mb.done == CT_DONE_CORRUPT) {
-            // the count on the device is not one the solve may index with; nothing ran, nothing is repeated: the pairs
-            // have to be made again (mpm_generate_contact_pairs / mpm_copy_contact_pairs) before the next solve
-            const long long raw = (long long)(int)oc.mb.count;
-            b.dev_counted = false;
-            b.n = 0;
-            b.last_unchanged = false;
-            if (raw < 0 || (size_t)raw > b.cap)
-                return fail(MPM_ERR_CAPACITY, "contact solve: the pair count on the device (" + std::to_string(raw) +
-                                                  ") is outside the capacity that sized the per-pair buffers (" + std::to_string(b.cap) +
-                                                  "): nothing was indexed with it, nothing was solved; make the pairs again");
-            return fail(MPM_ERR_INTERNAL, "contact solve: the pair count on the device was not written by the pair generation this "
-                                          "solve was enqueued for (a stale count): nothing was solved; make the pairs again");
-        }
-        if (oc.mb.done == CT_DONE_FAULT) {
-            e->ct_counters[3] += 1;
-            if (int rc = ensure_contact_capacity(e, (size_t)oc.mb.count)) return rc;
-            if (int rc = generate_contacts_launch(e)) return rc;
-            full_setup = true;
-            continue;
-        }
-        if (oc.mb.done == CT_DONE_GATED) {
-            // (mpm_run_coupled_substeps enqueued the substep without its re-sort launches and a re-sort was pending: nothing
-            // of the substep has run; the caller repeats all of it)
-            e->last_contact_gated = true;
-            if (iters_out) *iters_out = 0;
-            if (residual_out) *residual_out = 0.f;
-            return 0;
-        }
-        if (oc.mb.done == CT_DONE_STALE) {
-            e->ct_counters[2] += 1;
-            b.n_active_hint = 0;
-            full_setup = true;
-            continue;
-        }
-        break;
-    }
-    const int iters = oc.mb.iters;
-    const float residual = oc.mb.residual;
-    e->ct_quiet_left = oc.mb.quiet_left;
-    e->ct_counters[0] += 1;
-    e->ct_counters[1] += e->last_contact_reused ? 1 : 0;
-    if (b.dev_counted) {   // the count has arrived with the solve's first publication
-        b.n = oc.mb.count;
-        b.dev_counted = false;
-    }
-    b.last_iters = iters;
-    b.last_unchanged = oc.mb.unchanged;
-    if (e->ct_debug) fprintf(stderr, "contact solve: n %zu nodes %u iters %d unchanged %d\n", b.n, oc.mb.nodes, iters, (int)oc.mb.unchanged);
-    if (iters_out) *iters_out = iters;
-    if (residual_out) *residual_out = residual;
-    {
-        // what the reference prints / dumps per substep (cuda_mpm_solver.cu:577-612), kept for mpm_get_contact_stats: the
-        // mailbox carries the iteration count, the residual, the contact and node counts; the other numbers stay on the
-        // device until somebody asks (contact_stats_from_device: a synchronisation point of its own)
-        mpm_contact_stats_t& cs = e->last_contact;
-        cs = mpm_contact_stats_t{};
-        cs.iterations = iters;
-        cs.contacts = (uint32_t)b.n;
-        cs.nodes = oc.mb.nodes;
-        cs.residual = residual;
-        e->last_contact_on_device = !oc.have_state;
-        e->last_contact_exact = exact != 0;
-        if (oc.have_state) {
-            const ContactState& st = oc.st;
-            cs.norm_dir_sq = st.norm_dir_sq;
-            cs.dofs = st.dofs;
-            cs.line_search_evals = st.ls_total;
-            cs.alpha = st.alpha;
-            cs.energy = st.energy;
-            cs.E0 = st.E0;
-            if (exact && !s_ls.empty()) {   // (host-driven exact search: its own bookkeeping)
-                cs.line_search_evals = 0;
-                for (int v : s_ls) cs.line_search_evals += v;
-                cs.alpha = s_alpha_last;
-                cs.energy = s_energy.empty() ? 0.f : s_energy.back();
-                cs.E0 = s_E0_last;
-            }
-        }
-    }
-    if (dump) {
-        // per-substep statistics, same fields as cuda_mpm_solver.cu:587-612
-        if (int rc = contact_stats_from_device(e)) return rc;
-        const mpm_contact_stats_t& cs = e->last_contact;
-        if (exact && s_res.empty() && iters > 0) {
-            std::vector<float> log((size_t)CT_LOG_F * std::min(iters, CT_LOG));
-            D2H(e, log.data(), b.it_log, log.size() * 4);
-            for (int i = 0; i < std::min(iters, CT_LOG); ++i) {
-                s_res.push_back(log[(size_t)i * CT_LOG_F]);
-                s_ls.push_back((int)log[(size_t)i * CT_LOG_F + 1]);
-                s_energy.push_back(log[(size_t)i * CT_LOG_F + 2]);
-            }
-        }
-        const std::string fn = e->dump_dir + "/jacobi_iter_" + std::to_string(max_iters) + "_frame_" +
-                               std::to_string(frame) + "_substep_" + std::to_string(substep) + ".json";
-        std::ofstream f(fn);
-        if (!f) return fail(MPM_ERR_INVALID, "cannot write " + fn);
-        f << "[\n";
-        if (exact) {
-            for (size_t i = 0; i < s_res.size(); ++i)
-                f << "  {\n      \"residual\": " << s_res[i] << ",\n      \"line_search_cnt\": " << s_ls[i]
-                  << ",\n      \"energy\": " << s_energy[i] << "\n  }" << (i + 1 < s_res.size() ? "," : "") << "\n";
-        } else {
-            f << "  {\n      \"iterations\": " << iters << ",\n      \"residual\": " << residual
-              << ",\n      \"line_search_cnt\": " << (iters ? (double)cs.line_search_evals / iters : 0.0)
-              << ",\n      \"energy\": " << cs.energy << "\n  }\n";
-        }
-        f << "]\n";
-    }
-    return 0;
-}
-
 // the numbers of the last solve that the mailbox does not carry (step, energies, |Dir|^2, DoFs, line-search count)
+static void stats_from_state(mpm_contact_stats_t* cs, const ContactState& st) {
+    cs->norm_dir_sq = st.norm_dir_sq;
+    cs->dofs = st.dofs;
+    cs->line_search_evals = st.ls_total;
+    cs->alpha = st.alpha;
+    cs->energy = st.energy;
+    cs->E0 = st.E0;
+}
 static int contact_stats_from_device(mpm_engine* e) {
     if (!e->last_contact_on_device) return 0;
-    ContactBuffers& b = e->cb;
     ContactState st;
-    D2H(e, &st, b.st, sizeof(ContactState));
-    mpm_contact_stats_t& cs = e->last_contact;
-    cs.norm_dir_sq = st.norm_dir_sq;
-    cs.dofs = st.dofs;
-    cs.line_search_evals = st.ls_total;
-    cs.alpha = st.alpha;
-    cs.energy = st.energy;
-    cs.E0 = st.E0;
+    D2H(e, &st, e->cb.st, sizeof(ContactState));
+    stats_from_state(&e->last_contact, st);
     e->last_contact_on_device = false;
     return 0;
 }
 
-static int solve_once(mpm_engine* e, float dt, float mu, float stiffness, float damping, int exact, int max_iters, bool full_setup,
-                      SolveOutcome* oc, std::vector<float>* s_res_p, std::vector<int>* s_ls_p, std::vector<float>* s_energy_p,
-                      float* s_alpha_last_p, float* s_E0_last_p, const std::function<void()>& before_impulse) {
+// ---- one engine ------------------------------------------------------------------------------------------------------------
+// the four ways to iterate, below (this file's first uses of the kernel templates are in the order the code object has
+// them in: a host-only change can then be checked by comparing the device code byte for byte)
+static int newton_backtracking(const SolveCtx& x, const SolveParams& prm, SolveOutcome* oc);
+static int newton_exact(const SolveCtx& x, const SolveParams& prm, SolveOutcome* oc);
+static int newton_backtracking_host(const SolveCtx& x, const SolveParams& prm, SolveOutcome* oc);
+static int newton_exact_host(const SolveCtx& x, const SolveParams& prm, SolveOutcome* oc);
+
+// One attempt on one engine: set-up, iterations, impulses
+static int solve_once(mpm_engine* e, const SolveParams& prm, bool full_setup, SolveOutcome* oc, const BeforeImpulse& before_impulse) {
     ContactBuffers& b = e->cb;
-    std::vector<float>&s_res = *s_res_p, &s_energy = *s_energy_p;
-    std::vector<int>& s_ls = *s_ls_p;
-    float &s_alpha_last = *s_alpha_last_p, &s_E0_last = *s_E0_last_p;
-    *oc = SolveOutcome();
-    e->last_contact_reused = false;
-    e->last_contact_gated = false;
     const DP& p = e->dp;
     hipStream_t s = e->stream;
-    // what sizes the grids: the count, or -- counted on the device -- a bound (every kernel strides over its grid and
-    // reads the count itself): the last solve's count with some room, at most the buffers' capacity
-    size_t n = b.n;
-    if (b.dev_counted) n = b.n_hint && !full_setup ? std::min<size_t>(b.cap, b.n_hint + b.n_hint / 8 + 256) : b.cap;
-    n = std::max<size_t>(n, 1);
-    const unsigned gc = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
-    // The pairs name particles by the caller's slot; the engine's internal slots change with every
-    // re-sort (which the device decides by itself, e.g. inside a RebuildMapping between
-    // CopyContactPairs and this call): k_ct_keys resolves them again, from the kept caller indices.
-    // grid-stride contact part of k_ct_ls: 4 lanes per contact
-    // (always all CT_ROWS_CON rows: tile t goes to row t mod CT_ROWS_CON whatever the count or the buffers' capacity, so
-    // the energy sums -- and with them every `E1 <= E0` decision -- do not depend on what sized the launch; workgroups
-    // without a tile write a row of zeros)
-    const int n_con_wg = CT_ROWS_CON;
-    const int n_grid_wg = CT_ROWS;                               // grid-stride node part
-    const int n_dir_wg = CT_DIR_WG;
-    // (MPM_CT_FORCE_DIST=1, tests: a partitioned engine of ONE rank takes the distributed paths too -- split direction
-    // kernels, sums through the all-reduce -- so that they can run on a box with one GPU)
-    const bool dist = p.dist.on && (p.dist.world > 1 || e->ct_force_dist);
+    const bool dist = partitioned_solve(e);
     // ---- set-up: contacts in base-cell order, per-cell runs, nodes that see contacts ---------
     std::unique_ptr<TraceRange> tr_phase(new TraceRange("mpm:UpdateContact set-up (sort, per-cell runs, node list)"));
     auto trace_phase = [&](const char* name) {   // (phases end where the next begins; early returns close them too)
         tr_phase.reset();
         tr_phase.reset(new TraceRange(name));
     };
-    b.solves += 1;
     // Settled scenes: when the last solve found its pair list equal to its predecessor's, this one
     // is enqueued on the guess that it is again -- no sort, no per-cell runs, no node list: the last full set-up's stand
     // -- and k_ct_keys checks the guess on the device, entry by entry (same particle, body and base cell, same count, same
     // block tables).  A wrong guess refuses the solve (CT_DONE_STALE), the caller repeats it with the full set-up.
     const bool reuse = !full_setup && b.last_unchanged && !dist && !e->ct_no_reuse;
-    // Keys are compact cells (active block * 64 + cell).  How many blocks are active the host knows from the last
-    // solve's publication (it changes with re-sorts only); with config 3's 1805 blocks that is 18 key bits, two passes
-    // of 9, instead of 22 bits for the table capacity, three passes of 8.  Checked on the device as well: keys wider
-    // than the guess refuse the solve (CT_DONE_STALE).
-    const size_t blocks = b.n_active_hint && !full_setup ? std::min<size_t>((size_t)b.n_active_hint * 2, p.capA) : p.capA;
-    int bits = 1;
-    while (((size_t)1 << bits) < blocks * 64) ++bits;
-    {
-        ContactDev c_in = make_contact_dev(e, dt, mu, stiffness, damping, max_iters, /* sorted = */ false);
-        hipLaunchKernelGGL(k_ct_keys, dim3(1024), dim3(256), 0, s, p, c_in, (const uint32_t*)b.api_idx, (const int*)e->d_pids_api, b.slot,
-                           b.published, b.solves, bits, (int)std::min<size_t>(n, 0x7FFFFFFF), reuse ? 1 : 0, full_setup ? 1 : 0, b.gen_stamp, 0);
-    }
-    if (!reuse) {
-        // CT_NO_CELL has all those bits set and more: it sorts behind every real cell as long as
-        // one more bit takes part
-        // (a sort's tiles are fixed chunks, not a stride over the grid: with the count on the device its launch covers
-        // the guess `n` -- the last solve's count with an eighth of room --, and k_ct_keys refuses the solve when the
-        // count has outgrown it: a sheet of the stack landing doubles the count from one substep to the next, once)
-        bool in_alt = false;
-        if (radix_sort_pairs(s, b.key, b.order, b.key2, b.order2, b.sort_hist, n, std::min(bits + 1, 31), &in_alt,
-                             b.dev_counted ? &b.st->n : nullptr))
-            return fail(MPM_ERR_HIP, "contact sort failed");
-        b.sorted_in_alt = in_alt;
-    }
-    ContactDev c = make_contact_dev(e, dt, mu, stiffness, damping, max_iters);
+    SolveCtx x{e, solve_geometry(b, p, full_setup), ContactDev{}, TeamDev{}};
+    enqueue_keys(x, prm, reuse, full_setup, false);
+    if (int rc = enqueue_sort(&x, prm, reuse)) return rc;
+    const ContactDev& c = x.c;
     if (reuse) {
-        hipLaunchKernelGGL(k_ct_prepare<true>, dim3(gc), dim3(256), 0, s, p, c);
+        hipLaunchKernelGGL(k_ct_prepare<true>, dim3(x.g.gc), dim3(256), 0, s, p, c);
     } else {
-        hipLaunchKernelGGL(k_ct_prepare<false>, dim3(gc), dim3(256), 0, s, p, c);
+        hipLaunchKernelGGL(k_ct_prepare<false>, dim3(x.g.gc), dim3(256), 0, s, p, c);
         if (dist) {
             // a node in a zone may be reached by the neighbour's contacts only: both ranks need it listed
             hipLaunchKernelGGL(k_ct_flags_to_field, dim3(512), dim3(256), 0, s, p, c, 0);
@@ -1025,194 +925,29 @@ static int solve_once(mpm_engine* e, float dt, float mu, float stiffness, float 
     }
 
     trace_phase("mpm:UpdateContact Newton iterations");
-    ContactState st{};
-    int iters = 0;
-    float residual = 1e10f;
-    const unsigned n_tile_wg = (unsigned)std::max<size_t>(1, std::min<size_t>((n + CT_TILE - 1) / CT_TILE, CT_TILE_WG));
     // the iterations are driven by the host, step by step, with the state copied back (partitioned domain without the
     // device-resident exact search): nothing is published, nothing is polled
-    const bool host_driven = dist && !(exact && e->chain.comm && rccl_rt::api()->all_reduce);
-    if (host_driven) c.mbox = nullptr;
-    // contact gradients/Hessians and their per-cell sums, then (H, G) and the direction per node
-    auto launch_dir = [&](int first, int lazy) {
-        hipLaunchKernelGGL(k_ct_tile, dim3(n_tile_wg), dim3(256), 0, s, p, c, first, lazy);
-        hipLaunchKernelGGL(k_ct_node_dir<0>, dim3(n_dir_wg), dim3(CT_WG), 0, s, p, c, lazy);
-    };
-    auto newton_direction = [&](int first) -> int {
-        if (!dist) {
-            launch_dir(first, 0);
-            return 0;
-        }
-        hipLaunchKernelGGL(k_ct_tile, dim3(n_tile_wg), dim3(256), 0, s, p, c, first, 0);
-        hipLaunchKernelGGL(k_ct_node_dir<1>, dim3(n_dir_wg), dim3(CT_WG), 0, s, p, c, 0);
-        if (int rc = zone_exchange3(e, b.hg)) return rc;
-        hipLaunchKernelGGL(k_ct_node_dir<2>, dim3(n_dir_wg), dim3(CT_WG), 0, s, p, c, 0);
-        return 0;
-    };
-    if (!exact && dist) {
-        // one iteration at a time: every iteration has two exchanges with the other ranks
-        while (true) {
-            if (int rc = newton_direction(iters == 0)) return rc;
-            hipLaunchKernelGGL(k_ct_ls, dim3(n_con_wg + n_grid_wg), dim3(CT_WG), 0, s, p, c, n_con_wg, 0, 0.f);
-            hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 0, 1);
-            if (int rc = dist_allreduce(e, b.st->red, 32)) return rc;
-            hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 0, 2);
-            hipLaunchKernelGGL(k_ct_apply, dim3(CT_ROWS), dim3(CT_WG), 0, s, p, c);
-            iters += 1;
-            HIP_TRY(hipMemcpyAsync(&st, b.st, sizeof(ContactState), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (st.done || st.iters >= max_iters) break;   // (the same on every rank: decided from the global sums)
-        }
-        iters = st.iters;
-        residual = st.residual;
-    } else if (!exact) {
-        // device-resident loop: iterations are launched in batches, kernels of an iteration
-        // that starts after convergence return immediately
-        // Four launches per iteration: contacts -> sums per cell, nodes -> direction, energies of the
-        // candidate steps, decision.  The accepted step reaches the grid velocity at the start of the
-        // next iteration (k_ct_node_dir, lazy; k_ct_tile reads v - alpha D meanwhile) and, for the last
-        // iteration, in the k_ct_apply after the loop.  MPM_CT_EAGER=1 keeps the separate k_ct_apply.
-        // (the first iteration has no step to catch up with -- and, with a reused set-up, directions of the previous
-        // solve in place: it never reads them)
-        const bool eager = e->ct_eager;   // (per handle, read at mpm_create)
-        auto pattern = [&](int index) -> int {
-            launch_dir(index == 0, eager || index == 0 ? 0 : 1);
-            hipLaunchKernelGGL(k_ct_ls, dim3(n_con_wg + n_grid_wg), dim3(CT_WG), 0, s, p, c, n_con_wg, 0, 0.f);
-            hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 0, 0);
-            if (eager) hipLaunchKernelGGL(k_ct_apply, dim3(CT_ROWS), dim3(CT_WG), 0, s, p, c, 0);
-            return 1;
-        };
-        // two iterations first, then one at a time: an iteration is ~34 us of device time, the host needs ~20 to see a
-        // publication and enqueue the next four launches, so one iteration in flight behind the one it waits for keeps
-        // the device busy, and what is enqueued in vain when the solve converges is one iteration's idle launches.
-        // (Round 5 first enqueued as many iterations as the LAST solve had taken: where the counts fall from solve to
-        // solve -- 64, 26, 19, 17, 12 ... after an impact -- that was 5-10 idle patterns of 8 us per solve; measured
-        // over four runs each, scratch/ct_batch_ab.sh: the time of a coupled substep beyond its iterations 0.32 -> 0.30
-        // ms in the window of the impact, unchanged once settled.)
-        const int first = ct_batch(e, 0, 2);
-        if (int rc = run_batches(e, pattern, first, ct_batch(e, 1, 1), max_iters, &oc->mb)) return rc;
-        if (!eager) hipLaunchKernelGGL(k_ct_apply, dim3(CT_ROWS), dim3(CT_WG), 0, s, p, c, 2);
-        iters = oc->mb.iters;
-        residual = oc->mb.residual;
-    } else if (!host_driven) {
-        // Exact line search, device resident: a fixed pattern of launches per Newton iteration --
-        // direction, PROBES x (energies at st->alpha_probe, one-thread state machine = root finder of
-        // mpm_rootfind.h), apply, close -- whose kernels skip themselves according to the state: a search
-        // that needs more probes continues in the next pattern (direction skipped), patterns after
-        // convergence are idle.  No read-back at all: the host polls the mailbox.
-        // Partitioned domain with the native chain: the same pattern; the sums of a probe go through ncclAllReduce ON
-        // THE ENGINE'S STREAM between the two halves of the decision (k_ct_decide phase 1: this rank's sums; phase 2:
-        // the state machine, on the global sums -- identical on every rank, so all ranks walk the same states and
-        // every collective of the pattern is entered by all of them), the direction through the zone exchange.  No
-        // host loop per probe: the root finder is inherently sequential (every probe is placed by the one before), so
-        // one all-reduce per probe is the floor; what goes is the host round trip around each of them.
-        const int PROBES = 6;
-        int rc_pattern = 0;
-        auto pattern = [&](int index) -> int {
-            int published = 0;
-            if (!dist) {
-                launch_dir(index == 0, 0);
-            } else if (int rc = newton_direction(index == 0)) {
-                rc_pattern = rc;
-            }
-            for (int k = 0; k < PROBES; ++k) {
-                hipLaunchKernelGGL(k_ct_ls, dim3(n_con_wg + n_grid_wg), dim3(CT_WG), 0, s, p, c, n_con_wg, 2, 0.f);
-                if (!dist) {
-                    hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 2, 0);
-                    published += 1;
-                } else {
-                    hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 2, 1);
-                    if (int rc = dist_allreduce(e, b.st->red, 32)) rc_pattern = rc;
-                    hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 2, 2);
-                    published += 2;
-                }
-            }
-            hipLaunchKernelGGL(k_ct_apply, dim3(CT_ROWS), dim3(CT_WG), 0, s, p, c, 1);
-            hipLaunchKernelGGL(k_ct_exact_finish, dim3(1), dim3(64), 0, s, c);
-            return published + 1;
-        };
-        // (a search that never terminates cannot happen -- the root finder stops after 200 evaluations, which in
-        // float it often needs: |dx| < 3e-9 is out of reach -- but the launches are bounded too: every Newton
-        // iteration may take 200 / PROBES + 1 patterns)
-        // (patterns with ncclAllReduce in them: every rank must enqueue the same number -- no speculation beyond one rank)
-        const bool collective = dist && p.dist.world > 1;
-        if (int rc = run_batches(e, pattern, ct_batch(e, 0, 1), ct_batch(e, 1, 1), max_iters, &oc->mb,
-                                 (200 / PROBES + 2) * max_iters + 64, !collective))
-            return rc;
-        if (rc_pattern) return rc_pattern;
-        iters = oc->mb.iters;
-        residual = oc->mb.residual;
-    } else {
-        // exact line search on a partitioned domain whose transport is a pair of host callbacks
-        // (mpm_dist_set_transport): every all-reduce is a host round trip anyway, so the search is driven from the
-        // host, probe by probe, exactly like cuda_mpm_solver.cu:383-471 (itself a clone of Drake's
-        // DoNewtonWithBisectionFallback)
-        auto probe = [&](float alpha, std::tuple<float, float, float>* out) -> int {
-            hipLaunchKernelGGL(k_ct_ls, dim3(n_con_wg + n_grid_wg), dim3(CT_WG), 0, s, p, c, n_con_wg, 1, alpha);
-            hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 1, 1);
-            if (int rc2 = dist_allreduce(e, b.st->red, 32)) return rc2;
-            hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, s, c, n_dir_wg, n_con_wg, n_grid_wg, 1, 2);
-            HIP_TRY(hipMemcpyAsync(&st, b.st, sizeof(ContactState), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            *out = std::make_tuple((float)st.scal[0], (float)st.scal[1], (float)st.scal[2]);
-            return 0;
-        };
-        const float f_tol = 1e-8f, x_tol = f_tol * c.relax;   // cuda_mpm_solver.cu:383-385
-        while (residual > c.tol && iters < max_iters) {
-            int rc;
-            if ((rc = newton_direction(iters == 0))) return rc;
-            std::tuple<float, float, float> f_lo, f_hi, f_root;
-            if ((rc = probe(0.f, &f_lo)) || (rc = probe(1.f, &f_hi))) return rc;
-            s_E0_last = std::get<0>(f_lo);   // E(alpha = 0)
-            float x_lo = 0.f;
-            if (std::get<1>(f_lo) < 0.f && std::get<1>(f_hi) < 0.f) {   // :395-398
-                x_lo = 1.f;
-                f_lo = f_hi;
-            }
-            // Newton with bisection fallback on dE/dalpha, starting at the upper end (:399), with the
-            // clone's three deviations from Drake's routine (mpm_rootfind.h)
-            RootFinder<float> rf;
-            rf.start(x_lo, std::get<1>(f_lo), 1.f, std::get<1>(f_hi), 1.f, x_tol, f_tol, 200,
-                     RF_SIGN3 | RF_NO_ENDS | RF_STEP_LAST);
-            float energy = 0.f;
-            while (rf.status == 0) {
-                if ((rc = probe(rf.root, &f_root))) return rc;
-                energy = std::get<0>(f_root);
-                rf.feed(std::get<1>(f_root), std::get<2>(f_root));
-            }
-            const float alpha = rf.root;
-            const int ls = rf.evals;
-            s_alpha_last = alpha;
-            HIP_TRY(hipMemcpyAsync(&b.st->alpha, &alpha, 4, hipMemcpyHostToDevice, s));
-            hipLaunchKernelGGL(k_ct_apply, dim3(CT_ROWS), dim3(CT_WG), 0, s, p, c);
-            residual = std::sqrt(st.norm_dir_sq) / st.dofs;
-            iters += 1;
-            s_res.push_back(residual);
-            s_energy.push_back(energy);
-            s_ls.push_back(ls);
-        }
-    }
+    const bool host_driven = dist && !(prm.exact && e->chain.comm && rccl_rt::api()->all_reduce);
+    if (host_driven) x.c.mbox = nullptr;
+    if (int rc = host_driven ? (prm.exact ? newton_exact_host(x, prm, oc) : newton_backtracking_host(x, prm, oc))
+                             : (prm.exact ? newton_exact(x, prm, oc) : newton_backtracking(x, prm, oc)))
+        return rc;
     // contact velocities after the solve and the reaction on the rigid bodies
     trace_phase("mpm:UpdateContact impulses");
     // (mpm_run_coupled_substeps puts GridToParticle in front of this kernel: the host has just learnt that the solve is
     // over and the device's queue is short -- a long kernel first gives the host time to enqueue what follows; the
     // impulses read the grid velocities and the contact arrays, which GridToParticle does not touch)
     // (not behind a solve that refused itself: the caller repeats that one, and GridToParticle belongs behind the repeat)
-    if (before_impulse && (host_driven || (oc->mb.done != CT_DONE_FAULT && oc->mb.done != CT_DONE_STALE && oc->mb.done != CT_DONE_CORRUPT)))
-        before_impulse();
-    hipLaunchKernelGGL(k_ct_impulse, dim3(std::min(gc, 256u)), dim3(256), 0, s, p, c);
+    if (before_impulse && !refused(oc->mb.done)) before_impulse(0);
+    hipLaunchKernelGGL(k_ct_impulse, dim3(std::min(x.g.gc, 256u)), dim3(256), 0, s, p, c);
     HIP_TRY(hipGetLastError());
     if (host_driven) {
         // (these paths know the state: hand it over like a publication)
-        oc->st = st;
         oc->have_state = true;
-        oc->mb.done = st.done ? st.done : 1;
-        oc->mb.iters = iters;
-        oc->mb.residual = residual;
+        oc->mb.done = oc->st.done && oc->st.done != 2 ? oc->st.done : 1;
         oc->mb.count = (unsigned)b.n;
-        oc->mb.nodes = (unsigned)st.n_nodes;
+        oc->mb.nodes = (unsigned)oc->st.n_nodes;
         oc->mb.unchanged = false;
-        if (oc->mb.done == 2) oc->mb.done = 1;
     } else {
         e->last_contact_reused = reuse && oc->mb.done != CT_DONE_STALE;
         b.n_hint = oc->mb.count;
@@ -1222,6 +957,178 @@ static int solve_once(mpm_engine* e, float dt, float mu, float stiffness, float 
     return 0;
 }
 
+// ---- the iteration strategies of one engine ------------------------------------------------------------------------------
+// contact gradients/Hessians and their per-cell sums, then (H, G) and the direction per node
+static void launch_direction(const SolveCtx& x, int first, int lazy) {
+    const DP& p = x.e->dp;
+    hipLaunchKernelGGL(k_ct_tile, dim3(x.g.n_tile_wg), dim3(256), 0, x.e->stream, p, x.c, first, lazy);
+    hipLaunchKernelGGL(k_ct_node_dir<0>, dim3(CT_DIR_WG), dim3(CT_WG), 0, x.e->stream, p, x.c, lazy);
+}
+// ... of a partitioned domain: this rank's (H, G) per node | zone exchange | solve per node
+static int partitioned_direction(const SolveCtx& x, int first) {
+    const DP& p = x.e->dp;
+    hipStream_t s = x.e->stream;
+    hipLaunchKernelGGL(k_ct_tile, dim3(x.g.n_tile_wg), dim3(256), 0, s, p, x.c, first, 0);
+    hipLaunchKernelGGL(k_ct_node_dir<1>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, x.c, 0);
+    if (int rc = zone_exchange3(x.e, x.e->cb.hg)) return rc;
+    hipLaunchKernelGGL(k_ct_node_dir<2>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, x.c, 0);
+    return 0;
+}
+static int state_to_host(const SolveCtx& x, ContactState* st) {
+    HIP_TRY(hipMemcpyAsync(st, x.e->cb.st, sizeof(ContactState), hipMemcpyDeviceToHost, x.e->stream));
+    HIP_TRY(hipStreamSynchronize(x.e->stream));
+    return 0;
+}
+
+// Backtracking, device resident: iterations are launched in batches, kernels of an iteration that starts after
+// convergence return immediately.
+// Four launches per iteration: contacts -> sums per cell, nodes -> direction, energies of the
+// candidate steps, decision.  The accepted step reaches the grid velocity at the start of the
+// next iteration (k_ct_node_dir, lazy; k_ct_tile reads v - alpha D meanwhile) and, for the last
+// iteration, in the k_ct_apply after the loop.  MPM_CT_EAGER=1 keeps the separate k_ct_apply.
+// (the first iteration has no step to catch up with -- and, with a reused set-up, directions of the previous
+// solve in place: it never reads them)
+static int newton_backtracking(const SolveCtx& x, const SolveParams& prm, SolveOutcome* oc) {
+    const bool eager = x.e->ct_eager;   // (per handle, read at mpm_create)
+    auto pattern = [&](int index) -> int {
+        launch_direction(x, index == 0, eager || index == 0 ? 0 : 1);
+        launch_ls(x, 0, 0.f);
+        launch_decide(x, 0, 0);
+        if (eager) launch_apply(x, 0);
+        return 1;
+    };
+    // two iterations first, then one at a time: an iteration is ~34 us of device time, the host needs ~20 to see a
+    // publication and enqueue the next four launches, so one iteration in flight behind the one it waits for keeps
+    // the device busy, and what is enqueued in vain when the solve converges is one iteration's idle launches.
+    // (Round 5 first enqueued as many iterations as the LAST solve had taken: where the counts fall from solve to
+    // solve -- 64, 26, 19, 17, 12 ... after an impact -- that was 5-10 idle patterns of 8 us per solve; measured
+    // over four runs each, scratch/ct_batch_ab.sh: the time of a coupled substep beyond its iterations 0.32 -> 0.30
+    // ms in the window of the impact, unchanged once settled.)
+    if (int rc = run_batches(&x.e, 1, pattern, ct_batch(x.e, 0, 2), ct_batch(x.e, 1, 1), prm.max_iters, &oc->mb)) return rc;
+    if (!eager) launch_apply(x, 2);
+    return 0;
+}
+
+// Exact line search, device resident: a fixed pattern of launches per Newton iteration --
+// direction, CT_PROBES x (energies at st->alpha_probe, one-thread state machine = root finder of
+// mpm_rootfind.h), apply, close -- whose kernels skip themselves according to the state: a search
+// that needs more probes continues in the next pattern (direction skipped), patterns after
+// convergence are idle.  No read-back at all: the host polls the mailbox.
+// Partitioned domain with the native chain: the same pattern; the sums of a probe go through ncclAllReduce ON
+// THE ENGINE'S STREAM between the two halves of the decision (k_ct_decide phase 1: this rank's sums; phase 2:
+// the state machine, on the global sums -- identical on every rank, so all ranks walk the same states and
+// every collective of the pattern is entered by all of them), the direction through the zone exchange.  No
+// host loop per probe: the root finder is inherently sequential (every probe is placed by the one before), so
+// one all-reduce per probe is the floor; what goes is the host round trip around each of them.
+static int newton_exact(const SolveCtx& x, const SolveParams& prm, SolveOutcome* oc) {
+    mpm_engine* e = x.e;
+    const bool dist = partitioned_solve(e);
+    int rc_pattern = 0;
+    auto pattern = [&](int index) -> int {
+        int published = 0;
+        if (!dist) {
+            launch_direction(x, index == 0, 0);
+        } else if (int rc = partitioned_direction(x, index == 0)) {
+            rc_pattern = rc;
+        }
+        for (int k = 0; k < CT_PROBES; ++k) {
+            launch_ls(x, 2, 0.f);
+            if (!dist) {
+                launch_decide(x, 2, 0);
+                published += 1;
+            } else {
+                launch_decide(x, 2, 1);
+                if (int rc = dist_allreduce(e, e->cb.st->red, 32)) rc_pattern = rc;
+                launch_decide(x, 2, 2);
+                published += 2;
+            }
+        }
+        launch_apply(x, 1);
+        hipLaunchKernelGGL(k_ct_exact_finish, dim3(1), dim3(64), 0, e->stream, x.c);
+        return published + 1;
+    };
+    // (patterns with ncclAllReduce in them: every rank must enqueue the same number -- no speculation beyond one rank)
+    const bool collective = dist && e->dp.dist.world > 1;
+    if (int rc = run_batches(&x.e, 1, pattern, ct_batch(e, 0, 1), ct_batch(e, 1, 1), prm.max_iters, &oc->mb,
+                             exact_max_patterns(prm.max_iters), !collective))
+        return rc;
+    return rc_pattern;
+}
+
+// Backtracking on a partitioned domain, driven by the host with the state copied back: one iteration at a time, every
+// iteration has two exchanges with the other ranks.  Nothing is published, nothing is polled.
+static int newton_backtracking_host(const SolveCtx& x, const SolveParams& prm, SolveOutcome* oc) {
+    ContactState& st = oc->st;
+    for (int iters = 0;; ++iters) {
+        if (int rc = partitioned_direction(x, iters == 0)) return rc;
+        launch_ls(x, 0, 0.f);
+        launch_decide(x, 0, 1);
+        if (int rc = dist_allreduce(x.e, x.e->cb.st->red, 32)) return rc;
+        launch_decide(x, 0, 2);
+        launch_apply(x, 0);
+        if (int rc = state_to_host(x, &st)) return rc;
+        if (st.done || st.iters >= prm.max_iters) break;   // (the same on every rank: decided from the global sums)
+    }
+    oc->mb.iters = st.iters;
+    oc->mb.residual = st.residual;
+    return 0;
+}
+
+// Exact line search on a partitioned domain whose transport is a pair of host callbacks (mpm_dist_set_transport): every
+// all-reduce is a host round trip anyway, so the search is driven from the host, probe by probe, exactly like
+// cuda_mpm_solver.cu:383-471 (itself a clone of Drake's DoNewtonWithBisectionFallback)
+static int newton_exact_host(const SolveCtx& x, const SolveParams& prm, SolveOutcome* oc) {
+    mpm_engine* e = x.e;
+    ContactBuffers& b = e->cb;
+    ContactState& st = oc->st;
+    auto probe = [&](float alpha, std::tuple<float, float, float>* out) -> int {
+        launch_ls(x, 1, alpha);
+        launch_decide(x, 1, 1);
+        if (int rc2 = dist_allreduce(e, b.st->red, 32)) return rc2;
+        launch_decide(x, 1, 2);
+        if (int rc2 = state_to_host(x, &st)) return rc2;
+        *out = std::make_tuple((float)st.scal[0], (float)st.scal[1], (float)st.scal[2]);
+        return 0;
+    };
+    const float f_tol = 1e-8f, x_tol = f_tol * x.c.relax;   // cuda_mpm_solver.cu:383-385
+    int iters = 0;
+    float residual = 1e10f;
+    while (residual > x.c.tol && iters < prm.max_iters) {
+        int rc;
+        if ((rc = partitioned_direction(x, iters == 0))) return rc;
+        std::tuple<float, float, float> f_lo, f_hi, f_root;
+        if ((rc = probe(0.f, &f_lo)) || (rc = probe(1.f, &f_hi))) return rc;
+        oc->log.E0_last = std::get<0>(f_lo);   // E(alpha = 0)
+        float x_lo = 0.f;
+        if (std::get<1>(f_lo) < 0.f && std::get<1>(f_hi) < 0.f) {   // :395-398
+            x_lo = 1.f;
+            f_lo = f_hi;
+        }
+        // Newton with bisection fallback on dE/dalpha, starting at the upper end (:399), with the
+        // clone's three deviations from Drake's routine (mpm_rootfind.h)
+        RootFinder<float> rf;
+        rf.start(x_lo, std::get<1>(f_lo), 1.f, std::get<1>(f_hi), 1.f, x_tol, f_tol, 200,
+                 RF_SIGN3 | RF_NO_ENDS | RF_STEP_LAST);
+        float energy = 0.f;
+        while (rf.status == 0) {
+            if ((rc = probe(rf.root, &f_root))) return rc;
+            energy = std::get<0>(f_root);
+            rf.feed(std::get<1>(f_root), std::get<2>(f_root));
+        }
+        const float alpha = rf.root;
+        oc->log.alpha_last = alpha;
+        HIP_TRY(hipMemcpyAsync(&b.st->alpha, &alpha, 4, hipMemcpyHostToDevice, e->stream));
+        launch_apply(x, 0);
+        residual = std::sqrt(st.norm_dir_sq) / st.dofs;
+        iters += 1;
+        oc->log.res.push_back(residual);
+        oc->log.energy.push_back(energy);
+        oc->log.ls.push_back(rf.evals);
+    }
+    oc->mb.iters = iters;
+    oc->mb.residual = residual;
+    return 0;
+}
 
 // ---- TEAM solve: the distributed contact solve, device resident (mpm_team.h) ------------------------------------------
 static TeamDev team_dev(const mpm_engine* e) {
@@ -1248,66 +1155,31 @@ static TeamDev team_dev(const mpm_engine* e) {
 // with several ranks on ONE stream every signal is enqueued before the wait that needs it, so the waits return at once
 // and the same kernels serve both set-ups.  The host waits for nothing but the mailbox of the first local rank (all ranks
 // take the same decisions from the same global sums, in the same pattern).
-// `before_impulse(i)`: launched for rank i between the solve's last update and its impulses (GridToParticle), unless the
-// solve refused itself.
-static int team_solve_once(const std::vector<mpm_engine*>& L, float dt, float mu, float stiffness, float damping, int exact, int max_iters,
-                           bool full_setup, std::vector<SolveOutcome>* ocs, const std::function<void(size_t)>& before_impulse) {
-    struct Rank {
-        mpm_engine* e;
-        ContactDev c;
-        TeamDev t;
-        size_t n;
-        unsigned gc, n_tile_wg;
-    };
-    std::vector<Rank> R(L.size());
-    ocs->assign(L.size(), SolveOutcome());
-    const int n_con_wg = CT_ROWS_CON, n_grid_wg = CT_ROWS, n_dir_wg = CT_DIR_WG;
+static int team_solve_once(const std::vector<mpm_engine*>& L, const SolveParams& prm, bool full_setup, std::vector<SolveOutcome>* ocs,
+                           const BeforeImpulse& before_impulse) {
+    std::vector<SolveCtx> R(L.size());
     // ---- S1: keys, state reset, this rank's status on its way to every rank ---------------------------------------------
     for (size_t i = 0; i < L.size(); ++i) {
-        mpm_engine* e = L[i];
-        ContactBuffers& b = e->cb;
-        Rank& r = R[i];
-        r.e = e;
-        r.t = team_dev(e);
-        e->last_contact_reused = false;
-        e->last_contact_gated = false;
-        size_t n = b.n;
-        if (b.dev_counted) n = b.n_hint && !full_setup ? std::min<size_t>(b.cap, b.n_hint + b.n_hint / 8 + 256) : b.cap;
-        n = std::max<size_t>(n, 1);
-        r.n = n;
-        r.gc = (unsigned)std::min<size_t>((n + 255) / 256, 2048);
-        r.n_tile_wg = (unsigned)std::max<size_t>(1, std::min<size_t>((n + CT_TILE - 1) / CT_TILE, CT_TILE_WG));
-        b.solves += 1;
-        const DP& p = e->dp;
-        const size_t blocks = b.n_active_hint && !full_setup ? std::min<size_t>((size_t)b.n_active_hint * 2, p.capA) : p.capA;
-        int bits = 1;
-        while (((size_t)1 << bits) < blocks * 64) ++bits;
-        ContactDev c_in = make_contact_dev(e, dt, mu, stiffness, damping, max_iters, /* sorted = */ false);
-        hipLaunchKernelGGL(k_ct_keys, dim3(1024), dim3(256), 0, e->stream, p, c_in, (const uint32_t*)b.api_idx, (const int*)e->d_pids_api,
-                           b.slot, b.published, b.solves, bits, (int)std::min<size_t>(n, 0x7FFFFFFF), 0, full_setup ? 1 : 0, b.gen_stamp, 1);
-        hipLaunchKernelGGL(k_team_status<0>, dim3(1), dim3(64), 0, e->stream, c_in, r.t, e->dp.ctl);
-        // (the sort below runs whatever the status says: it only moves keys inside the buffers)
-        bool in_alt = false;
-        if (radix_sort_pairs(e->stream, b.key, b.order, b.key2, b.order2, b.sort_hist, n, std::min(bits + 1, 31), &in_alt,
-                             b.dev_counted ? &b.st->n : nullptr))
-            return fail(MPM_ERR_HIP, "contact sort failed");
-        b.sorted_in_alt = in_alt;
-        r.c = make_contact_dev(e, dt, mu, stiffness, damping, max_iters);
+        R[i] = SolveCtx{L[i], solve_geometry(L[i]->cb, L[i]->dp, full_setup), ContactDev{}, team_dev(L[i])};
+        const ContactDev c_in = enqueue_keys(R[i], prm, false, full_setup, true);
+        hipLaunchKernelGGL(k_team_status<0>, dim3(1), dim3(64), 0, L[i]->stream, c_in, R[i].t, L[i]->dp.ctl);
+        // (the sort runs whatever the status says: it only moves keys inside the buffers)
+        if (int rc = enqueue_sort(&R[i], prm, false)) return rc;
     }
     // ---- S2: the status of all ranks, constants in sorted order, node flags on their way to the neighbours ---------------
-    for (Rank& r : R) {
+    for (SolveCtx& r : R) {
         mpm_engine* e = r.e;
         hipStream_t s = e->stream;
         const DP& p = e->dp;
         hipLaunchKernelGGL(k_team_status<1>, dim3(1), dim3(64), 0, s, r.c, r.t, e->dp.ctl);
-        hipLaunchKernelGGL(k_ct_prepare<false>, dim3(r.gc), dim3(256), 0, s, p, r.c);
+        hipLaunchKernelGGL(k_ct_prepare<false>, dim3(r.g.gc), dim3(256), 0, s, p, r.c);
         // a node in a zone may be reached by the neighbour's contacts only: both ranks need it listed
         hipLaunchKernelGGL(k_ct_flags_to_field, dim3(512), dim3(256), 0, s, p, r.c, 0);
         hipLaunchKernelGGL(k_team_zone_pack<3>, dim3(e->g_grid, 2), dim3(256), 0, s, p, r.c, r.t, (const float4*)e->cb.hg, 0);
         hipLaunchKernelGGL(k_team_zone_signal, dim3(1), dim3(64), 0, s, r.c, r.t, 0);
     }
     // ---- S3: the neighbours' flags, node list ---------------------------------------------------------------------------
-    for (Rank& r : R) {
+    for (SolveCtx& r : R) {
         mpm_engine* e = r.e;
         hipStream_t s = e->stream;
         const DP& p = e->dp;
@@ -1320,91 +1192,71 @@ static int team_solve_once(const std::vector<mpm_engine*>& L, float dt, float mu
     }
     // ---- Newton iterations ---------------------------------------------------------------------------------------------
     // direction: contacts -> per-cell sums -> this rank's (H, G) per node | zone exchange | solve per node
-    auto direction_out = [&](Rank& r, int first, int lazy) {
+    auto direction_out = [&](SolveCtx& r, int first, int lazy) {
         mpm_engine* e = r.e;
         hipStream_t s = e->stream;
         const DP& p = e->dp;
-        hipLaunchKernelGGL(k_ct_tile, dim3(r.n_tile_wg), dim3(256), 0, s, p, r.c, first, lazy);
-        hipLaunchKernelGGL(k_ct_node_dir<1>, dim3(n_dir_wg), dim3(CT_WG), 0, s, p, r.c, 0);
+        hipLaunchKernelGGL(k_ct_tile, dim3(r.g.n_tile_wg), dim3(256), 0, s, p, r.c, first, lazy);
+        hipLaunchKernelGGL(k_ct_node_dir<1>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, r.c, 0);
         hipLaunchKernelGGL(k_team_zone_pack<3>, dim3(e->g_grid, 2), dim3(256), 0, s, p, r.c, r.t, (const float4*)e->cb.hg, 1);
         hipLaunchKernelGGL(k_team_zone_signal, dim3(1), dim3(64), 0, s, r.c, r.t, 1);
     };
-    auto direction_in = [&](Rank& r, int lazy) {
+    auto direction_in = [&](SolveCtx& r, int lazy) {
         mpm_engine* e = r.e;
         hipStream_t s = e->stream;
         const DP& p = e->dp;
         hipLaunchKernelGGL(k_team_zone_wait, dim3(1), dim3(64), 0, s, r.c, r.t, 1, e->dp.ctl);
         hipLaunchKernelGGL(k_team_zone_add<3>, dim3(64, 2), dim3(256), 0, s, p, r.c, r.t, e->cb.hg, 1);
-        hipLaunchKernelGGL(k_ct_node_dir<2>, dim3(n_dir_wg), dim3(CT_WG), 0, s, p, r.c, lazy);
+        hipLaunchKernelGGL(k_ct_node_dir<2>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, r.c, lazy);
     };
-    const int PROBES = 6;
     auto pattern = [&](int index) -> int {
-        if (!exact) {
+        if (!prm.exact) {
             // (lazy update as on one GPU: the accepted step reaches the grid in the next iteration's k_ct_node_dir<2>)
             const int lazy = index == 0 ? 0 : 1;
-            for (Rank& r : R) direction_out(r, index == 0, lazy);
-            for (Rank& r : R) {
+            for (SolveCtx& r : R) direction_out(r, index == 0, lazy);
+            for (SolveCtx& r : R) {
                 direction_in(r, lazy);
-                hipLaunchKernelGGL(k_ct_ls, dim3(n_con_wg + n_grid_wg), dim3(CT_WG), 0, r.e->stream, r.e->dp, r.c, n_con_wg, 0, 0.f);
-                hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, r.e->stream, r.c, n_dir_wg, n_con_wg, n_grid_wg, 0, 4, r.t);
+                launch_ls(r, 0, 0.f);
+                launch_decide(r, 0, 4);
             }
-            for (Rank& r : R)
-                hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, r.e->stream, r.c, n_dir_wg, n_con_wg, n_grid_wg, 0, 3, r.t);
+            for (SolveCtx& r : R) launch_decide(r, 0, 3);
             return 2;
         }
-        // exact line search: direction, PROBES x (energies at st->alpha_probe | all ranks' sums | state machine), apply, close
-        for (Rank& r : R) direction_out(r, index == 0, 0);
-        for (Rank& r : R) direction_in(r, 0);
-        for (int k = 0; k < PROBES; ++k) {
-            for (Rank& r : R) {
-                hipLaunchKernelGGL(k_ct_ls, dim3(n_con_wg + n_grid_wg), dim3(CT_WG), 0, r.e->stream, r.e->dp, r.c, n_con_wg, 2, 0.f);
-                hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, r.e->stream, r.c, n_dir_wg, n_con_wg, n_grid_wg, 2, 4, r.t);
+        // exact line search: direction, CT_PROBES x (energies at st->alpha_probe | all ranks' sums | state machine), apply, close
+        for (SolveCtx& r : R) direction_out(r, index == 0, 0);
+        for (SolveCtx& r : R) direction_in(r, 0);
+        for (int k = 0; k < CT_PROBES; ++k) {
+            for (SolveCtx& r : R) {
+                launch_ls(r, 2, 0.f);
+                launch_decide(r, 2, 4);
             }
-            for (Rank& r : R)
-                hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, r.e->stream, r.c, n_dir_wg, n_con_wg, n_grid_wg, 2, 3, r.t);
+            for (SolveCtx& r : R) launch_decide(r, 2, 3);
         }
-        for (Rank& r : R) {
-            hipLaunchKernelGGL(k_ct_apply, dim3(CT_ROWS), dim3(CT_WG), 0, r.e->stream, r.e->dp, r.c, 1);
+        for (SolveCtx& r : R) {
+            launch_apply(r, 1);
             hipLaunchKernelGGL(k_ct_exact_finish, dim3(1), dim3(64), 0, r.e->stream, r.c);
         }
-        return 2 * PROBES + 1;
+        return 2 * CT_PROBES + 1;
     };
-    {
-        const int max_patterns = exact ? (200 / PROBES + 2) * max_iters + 64 : 1 << 30;
-        int launched = 0;
-        std::vector<unsigned> older(L.size());
-        auto enqueue = [&](int count) {
-            for (int q = 0; q < count; ++q) {
-                const int pub = pattern(launched + q);
-                for (mpm_engine* e : L) e->cb.published += (unsigned)pub;
-            }
-            launched += count;
-        };
-        enqueue(exact ? ct_batch(L[0], 0, 1) : ct_batch(L[0], 0, 2));
-        while (true) {
-            for (size_t i = 0; i < L.size(); ++i) older[i] = L[i]->cb.published;
-            enqueue(ct_batch(L[0], 1, 1));   // speculative: idle (exchanges included) if the previous batch finished
-            MailboxState& mb = (*ocs)[0].mb;
-            if (int rc = wait_mailbox(L[0], older[0], &mb)) return rc;
-            if (mb.done || mb.iters >= max_iters || launched > max_patterns) break;
-        }
-        // (the other local ranks' words of THE SAME publication -- the one the first rank's poll happened to see, which may
-        // be later than the one it waited for --: the same decisions, their own counts)
-        const unsigned ahead = (*ocs)[0].mb.seq - older[0];
-        for (size_t i = 1; i < L.size(); ++i) {
-            if (int rc = wait_mailbox(L[i], older[i] + ahead, &(*ocs)[i].mb)) return rc;
-            if ((*ocs)[i].mb.done != (*ocs)[0].mb.done && (*ocs)[i].mb.seq == older[i] + ahead)
-                return fail(MPM_ERR_INTERNAL, "team solve: two ranks of one process disagree about the state of the solve");
-        }
+    MailboxState& mb = (*ocs)[0].mb;
+    if (int rc = run_batches(L.data(), L.size(), pattern, ct_batch(L[0], 0, prm.exact ? 1 : 2), ct_batch(L[0], 1, 1), prm.max_iters, &mb,
+                             prm.exact ? exact_max_patterns(prm.max_iters) : 1 << 30))
+        return rc;
+    // (the other local ranks' words of THE SAME publication -- the one the first rank's poll happened to see, which may
+    // be later than the one it waited for --: the same decisions, their own counts)
+    for (size_t i = 1; i < L.size(); ++i) {
+        const unsigned same = mb.seq + (L[i]->cb.published - L[0]->cb.published);   // (every pattern counts alike on all of them)
+        if (int rc = wait_mailbox(L[i], same, &(*ocs)[i].mb)) return rc;
+        if ((*ocs)[i].mb.done != mb.done && (*ocs)[i].mb.seq == same)
+            return fail(MPM_ERR_INTERNAL, "team solve: two ranks of one process disagree about the state of the solve");
     }
     // ---- the last step, GridToParticle, impulses -----------------------------------------------------------------------
     for (size_t i = 0; i < L.size(); ++i) {
-        Rank& r = R[i];
+        SolveCtx& r = R[i];
         mpm_engine* e = r.e;
-        const int done = (*ocs)[i].mb.done;
-        if (!exact) hipLaunchKernelGGL(k_ct_apply, dim3(CT_ROWS), dim3(CT_WG), 0, e->stream, e->dp, r.c, 2);
-        if (before_impulse && done != CT_DONE_FAULT && done != CT_DONE_STALE && done != CT_DONE_CORRUPT) before_impulse(i);
-        hipLaunchKernelGGL(k_ct_impulse, dim3(std::min(r.gc, 256u)), dim3(256), 0, e->stream, e->dp, r.c);
+        if (!prm.exact) launch_apply(r, 2);
+        if (before_impulse && !refused((*ocs)[i].mb.done)) before_impulse(i);
+        hipLaunchKernelGGL(k_ct_impulse, dim3(std::min(r.g.gc, 256u)), dim3(256), 0, e->stream, e->dp, r.c);
         HIP_TRY(hipGetLastError());
         e->cb.n_hint = (*ocs)[i].mb.count;
         e->cb.n_active_hint = (*ocs)[i].mb.n_active;
@@ -1412,45 +1264,98 @@ static int team_solve_once(const std::vector<mpm_engine*>& L, float dt, float mu
     return 0;
 }
 
-// The solve of all local ranks, refusals repeated (as update_contact does for one engine): the ranks agree on a refusal on
-// the device (k_team_status), so every rank's host sees the same code and all repeat together.
-static int team_solve(const std::vector<mpm_engine*>& L, float dt, float mu, float stiffness, float damping, int exact, int max_iters,
-                      const std::function<void(size_t)>& before_impulse, std::vector<SolveOutcome>* ocs) {
-    if (max_iters <= 0) max_iters = 2000;  // cuda_mpm_solver.cu:234
-    for (mpm_engine* e : L) {
-        REQUIRE(e->team.on && e->dp.dist.on, "team solve: mpm_dist_init and mpm_team_connect first");
-        REQUIRE(e->cb.n_bodies > 0, "call mpm_reallocate_external_bodies before the contact solve");
-        GrowPoison gp(e);
-        // (a rank without a single pair so far takes part all the same: its buffers must exist)
-        if (int rc = ensure_contact_capacity(e, std::max<size_t>(e->cb.cap, e->ct_initial_capacity ? e->ct_initial_capacity
-                                                                                                    : std::max<size_t>(4096, e->np / 16))))
-            return rc;
-        e->last_contact_dt = dt; e->last_contact_mu = mu; e->last_contact_k = stiffness; e->last_contact_d = damping;
+// What a finished solve leaves on its engine: the counters, and what the reference prints / dumps per substep
+// (cuda_mpm_solver.cu:577-612), kept for mpm_get_contact_stats: the mailbox carries the iteration count, the residual, the
+// contact and node counts; the other numbers stay on the device until somebody asks (contact_stats_from_device: a
+// synchronisation point of its own)
+static void record_outcome(mpm_engine* e, const SolveParams& prm, const SolveOutcome& oc, bool team) {
+    ContactBuffers& b = e->cb;
+    const MailboxState& mb = oc.mb;
+    e->ct_quiet_left = mb.quiet_left;
+    e->ct_counters[0] += 1;
+    e->ct_counters[1] += e->last_contact_reused ? 1 : 0;
+    if (b.dev_counted) {   // the count has arrived with the solve's first publication
+        b.n = mb.count;
+        b.dev_counted = false;
     }
+    b.last_iters = mb.iters;
+    b.last_unchanged = !team && mb.unchanged;   // (a team's set-up is never reused)
+    if (e->ct_debug && !team)
+        fprintf(stderr, "contact solve: n %zu nodes %u iters %d unchanged %d\n", b.n, mb.nodes, mb.iters, (int)mb.unchanged);
+    mpm_contact_stats_t& cs = e->last_contact;
+    cs = mpm_contact_stats_t{};
+    cs.iterations = mb.iters;
+    cs.contacts = (uint32_t)b.n;
+    cs.nodes = mb.nodes;
+    cs.residual = mb.residual;
+    e->last_contact_on_device = !oc.have_state;
+    e->last_contact_exact = prm.exact != 0;
+    if (!oc.have_state) return;
+    stats_from_state(&cs, oc.st);
+    if (prm.exact && !oc.log.ls.empty()) {   // (host-driven exact search: its own bookkeeping)
+        cs.line_search_evals = 0;
+        for (int v : oc.log.ls) cs.line_search_evals += v;
+        cs.alpha = oc.log.alpha_last;
+        cs.energy = oc.log.energy.empty() ? 0.f : oc.log.energy.back();
+        cs.E0 = oc.log.E0_last;
+    }
+}
+
+// The solve of one engine (`team` false, L of one) or of all local ranks of a team, refusals repeated.  A solve may REFUSE
+// to run, in which case none of its kernels has touched the grid:
+//   CT_DONE_CORRUPT  the count on the device is not one the solve may index with; nothing ran, nothing is repeated: the
+//                    pairs have to be made again (mpm_generate_contact_pairs / mpm_copy_contact_pairs) before the next solve;
+//   CT_DONE_FAULT    pairs counted on the device did not fit the buffers: grow them, make the pairs again, repeat;
+//   CT_DONE_GATED    mpm_run_coupled_substeps enqueued the substep without its re-sort launches and a re-sort was pending:
+//                    nothing of the substep has run; the caller repeats all of it (last_contact_gated);
+//   CT_DONE_STALE    the set-up was enqueued on a guess that the device found wrong (the previous solve's sorted order
+//                    reused for a pair list that has changed; sort keys narrower than the active blocks need): repeat with
+//                    the full set-up.
+// The ranks of a team agree on a refusal on the device (k_team_status), so every rank's host sees the same code and all
+// repeat together.
+static int solve_until_accepted(const std::vector<mpm_engine*>& L, bool team, const SolveParams& prm, const BeforeImpulse& before_impulse,
+                                std::vector<SolveOutcome>* ocs) {
     bool full_setup = false;
     for (int attempt = 0;; ++attempt) {
         REQUIRE(attempt < 8, "contact solve: the set-up keeps being refused");
-        if (int rc = team_solve_once(L, dt, mu, stiffness, damping, exact, max_iters, full_setup, ocs, before_impulse)) return rc;
+        ocs->assign(L.size(), SolveOutcome());
+        if (int rc = team ? team_solve_once(L, prm, full_setup, ocs, before_impulse)
+                          : solve_once(L[0], prm, full_setup, &(*ocs)[0], before_impulse))
+            return rc;
         const int done = (*ocs)[0].mb.done;
         if (done == CT_DONE_CORRUPT) {
             for (mpm_engine* e : L) {
                 e->cb.dev_counted = false;
                 e->cb.n = 0;
+                if (!team) e->cb.last_unchanged = false;
             }
-            return fail(MPM_ERR_CAPACITY, "contact solve: a rank's pair count on the device is not one the solve may index with "
-                                          "(outside the capacity of its buffers, or stale): nothing was solved on any rank; make the pairs again");
+            if (team)
+                return fail(MPM_ERR_CAPACITY, "contact solve: a rank's pair count on the device is not one the solve may index with "
+                                              "(outside the capacity of its buffers, or stale): nothing was solved on any rank; make the pairs again");
+            const long long raw = (long long)(int)(*ocs)[0].mb.count;
+            const size_t cap = L[0]->cb.cap;
+            if (raw < 0 || (size_t)raw > cap)
+                return fail(MPM_ERR_CAPACITY, "contact solve: the pair count on the device (" + std::to_string(raw) +
+                                                  ") is outside the capacity that sized the per-pair buffers (" + std::to_string(cap) +
+                                                  "): nothing was indexed with it, nothing was solved; make the pairs again");
+            return fail(MPM_ERR_INTERNAL, "contact solve: the pair count on the device was not written by the pair generation this "
+                                          "solve was enqueued for (a stale count): nothing was solved; make the pairs again");
         }
         if (done == CT_DONE_FAULT) {
             for (size_t i = 0; i < L.size(); ++i) {
                 mpm_engine* e = L[i];
-                GrowPoison gp(e);
                 e->ct_counters[3] += 1;
-                if (int rc = ensure_contact_capacity(e, std::max<size_t>((size_t)(*ocs)[i].mb.count, e->cb.cap))) return rc;
-                if (e->cb.dev_counted)   // (pairs made on the device: again, into the grown buffers; nothing has used them yet)
+                if (int rc = ensure_contact_capacity(e, (size_t)(*ocs)[i].mb.count)) return rc;
+                // (a team: only pairs made on the device are made again, into the grown buffers; nothing has used them yet)
+                if (!team || e->cb.dev_counted)
                     if (int rc = generate_contacts_launch(e)) return rc;
             }
             full_setup = true;
             continue;
+        }
+        if (done == CT_DONE_GATED && !team) {
+            L[0]->last_contact_gated = true;
+            return 0;
         }
         if (done == CT_DONE_STALE) {
             for (mpm_engine* e : L) {
@@ -1462,26 +1367,81 @@ static int team_solve(const std::vector<mpm_engine*>& L, float dt, float mu, flo
         }
         break;
     }
-    for (size_t i = 0; i < L.size(); ++i) {
-        mpm_engine* e = L[i];
-        ContactBuffers& b = e->cb;
-        const MailboxState& mb = (*ocs)[i].mb;
-        e->ct_quiet_left = mb.quiet_left;
-        e->ct_counters[0] += 1;
-        if (b.dev_counted) {
-            b.n = mb.count;
-            b.dev_counted = false;
-        }
-        b.last_iters = mb.iters;
-        b.last_unchanged = false;
-        mpm_contact_stats_t& cs = e->last_contact;
-        cs = mpm_contact_stats_t{};
-        cs.iterations = mb.iters;
-        cs.contacts = (uint32_t)b.n;
-        cs.nodes = mb.nodes;
-        cs.residual = mb.residual;
-        e->last_contact_on_device = true;
-        e->last_contact_exact = exact != 0;
+    for (size_t i = 0; i < L.size(); ++i) record_outcome(L[i], prm, (*ocs)[i], team);
+    return 0;
+}
+
+// The solve of a team's local ranks (mpm_world_coupled_substeps; mpm_update_contact of a rank)
+static int team_solve(const std::vector<mpm_engine*>& L, const SolveParams& prm, const BeforeImpulse& before_impulse,
+                      std::vector<SolveOutcome>* ocs) {
+    for (mpm_engine* e : L) {
+        REQUIRE(e->team.on && e->dp.dist.on, "team solve: mpm_dist_init and mpm_team_connect first");
+        REQUIRE(e->cb.n_bodies > 0, "call mpm_reallocate_external_bodies before the contact solve");
+        GrowPoison gp(e);
+        // (a rank without a single pair so far takes part all the same: its buffers must exist)
+        if (int rc = ensure_contact_capacity(e, std::max<size_t>(e->cb.cap, e->ct_initial_capacity ? e->ct_initial_capacity
+                                                                                                    : std::max<size_t>(4096, e->np / 16))))
+            return rc;
+        e->last_contact_prm = prm;
     }
+    return solve_until_accepted(L, true, prm, before_impulse, ocs);
+}
+
+static int update_contact(mpm_engine* e, int frame, int substep, const SolveParams& prm, int dump, int* iters_out, float* residual_out,
+                          const BeforeImpulse& before_impulse) {
+    ContactBuffers& b = e->cb;
+    if (b.n_bodies == 0) {
+        // the reference requires ReallocateExternelBodies first; size the accumulators to the ids in use
+        return fail(MPM_ERR_INVALID, "call mpm_reallocate_external_bodies before mpm_update_contact");
+    }
+    const std::vector<mpm_engine*> L{e};
+    std::vector<SolveOutcome> ocs;
+    if (e->dp.dist.on && e->team.on) {
+        // partitioned domain with the TEAM transport: device resident, every rank takes part whatever its own pair count
+        REQUIRE(!dump, "the JSON statistics dump is not available on a partitioned domain");
+        if (int rc = team_solve(L, prm, before_impulse, &ocs)) return rc;
+    } else {
+        e->last_contact_prm = prm;
+        // (the distributed paths are host-driven per iteration anyway: they work with a count the host knows)
+        if (partitioned_solve(e))
+            if (int rc = resolve_contact_count(e)) return rc;
+        if (!b.dev_counted && b.n == 0) return 0;   // cuda_mpm_solver.cu:216-217
+        TraceRange tr_all("mpm:UpdateContact");
+        if (int rc = solve_until_accepted(L, false, prm, before_impulse, &ocs)) return rc;
+    }
+    const bool gated = e->last_contact_gated;
+    const int iters = gated ? 0 : ocs[0].mb.iters;
+    const float residual = gated ? 0.f : ocs[0].mb.residual;
+    if (iters_out) *iters_out = iters;
+    if (residual_out) *residual_out = residual;
+    if (!dump || gated) return 0;
+    // per-substep statistics, same fields as cuda_mpm_solver.cu:587-612
+    if (int rc = contact_stats_from_device(e)) return rc;
+    const mpm_contact_stats_t& cs = e->last_contact;
+    auto& log = ocs[0].log;
+    if (prm.exact && log.res.empty() && iters > 0) {
+        std::vector<float> it_log((size_t)CT_LOG_F * std::min(iters, CT_LOG));
+        D2H(e, it_log.data(), b.it_log, it_log.size() * 4);
+        for (int i = 0; i < std::min(iters, CT_LOG); ++i) {
+            log.res.push_back(it_log[(size_t)i * CT_LOG_F]);
+            log.ls.push_back((int)it_log[(size_t)i * CT_LOG_F + 1]);
+            log.energy.push_back(it_log[(size_t)i * CT_LOG_F + 2]);
+        }
+    }
+    const std::string fn = e->dump_dir + "/jacobi_iter_" + std::to_string(prm.max_iters) + "_frame_" +
+                           std::to_string(frame) + "_substep_" + std::to_string(substep) + ".json";
+    std::ofstream f(fn);
+    if (!f) return fail(MPM_ERR_INVALID, "cannot write " + fn);
+    f << "[\n";
+    if (prm.exact) {
+        for (size_t i = 0; i < log.res.size(); ++i)
+            f << "  {\n      \"residual\": " << log.res[i] << ",\n      \"line_search_cnt\": " << log.ls[i]
+              << ",\n      \"energy\": " << log.energy[i] << "\n  }" << (i + 1 < log.res.size() ? "," : "") << "\n";
+    } else {
+        f << "  {\n      \"iterations\": " << iters << ",\n      \"residual\": " << residual
+          << ",\n      \"line_search_cnt\": " << (iters ? (double)cs.line_search_evals / iters : 0.0)
+          << ",\n      \"energy\": " << cs.energy << "\n  }\n";
+    }
+    f << "]\n";
     return 0;
 }

@@ -2664,9 +2664,13 @@ int mpm_update_contact(mpm_handle_t e, int frame, int substep, float dt, float m
     // (a rank of a TEAM takes part in the solve whatever its own pair count: "no contacts" is decided by all ranks together)
     if (!e->cb.dev_counted && e->cb.n == 0 && !(e->dp.dist.on && e->team.on)) return 0;  // cuda_mpm_solver.cu:216-217
     REQUIRE(e->grid_state == 2, "UpdateContact before UpdateGrid");
-    return update_contact(e, frame, substep, dt, mu, stiffness, damping, dump, exact, max_iters, iters_out,
-                          residual_out, nullptr);
+    return update_contact(e, frame, substep, SolveParams(dt, mu, stiffness, damping, exact, max_iters), dump, iters_out, residual_out,
+                          nullptr);
 } MPM_CATCH_ALL
+
+static SolveParams solve_params(const mpm_coupled_params_t* prm) {
+    return SolveParams(prm->dt, prm->friction_mu, prm->stiffness, prm->damping, prm->exact_line_search, prm->max_newton_iterations);
+}
 
 // The body of DeformableDriver::CalcAbstractStates' substep loop (multibody/plant/deformable_driver.h:240-258) for
 // rigid bodies with analytic signed distance fields, n times, in one call: RebuildMapping, CalcFemStateAndForce,
@@ -2695,6 +2699,7 @@ static int team_coupled_substeps(const std::vector<mpm_engine*>& L, int n, const
     }
     GridColliders gc;
     if (int rc = grid_colliders_for(L[0], prm->mpm_bc, &gc)) return rc;
+    const SolveParams solve = solve_params(prm);
     for (int s = 0; s < n; ++s) {
         for (mpm_engine* e : L) {
             may_resort(e, dt);
@@ -2706,9 +2711,7 @@ static int team_coupled_substeps(const std::vector<mpm_engine*>& L, int n, const
             if (int rc = generate_contacts(e, n_colliders, colliders, nullptr)) return rc;
         std::vector<SolveOutcome> ocs;
         auto g2p = [&](size_t i) { launch_g2p(L[i], L[i]->dp, dt); };
-        if (int rc = team_solve(L, dt, prm->friction_mu, prm->stiffness, prm->damping, prm->exact_line_search, prm->max_newton_iterations,
-                                g2p, &ocs))
-            return rc;
+        if (int rc = team_solve(L, solve, g2p, &ocs)) return rc;
         for (size_t i = 0; i < L.size(); ++i) {
             mpm_engine* e = L[i];
             e->substeps += 1;
@@ -2805,11 +2808,10 @@ static int coupled_substep(mpm_engine* e, int s, int n, const mpm_coupled_params
         t->gen += since(t0); t0 = clk::now();
         e->last_contact_gated = false;
         if (!rc && (e->cb.dev_counted || e->cb.n > 0))
-            rc = update_contact(e, 0, s, dt, prm->friction_mu, prm->stiffness, prm->damping, 0, prm->exact_line_search,
-                                prm->max_newton_iterations, &iters, &residual, [&]() {
-                                    launch_g2p(e, p, dt);
-                                    g2p_done = true;
-                                });
+            rc = update_contact(e, 0, s, solve_params(prm), 0, &iters, &residual, [&](size_t) {
+                launch_g2p(e, p, dt);
+                g2p_done = true;
+            });
         else if (!rc)
             e->last_contact = mpm_contact_stats_t{};
         t->solve += since(t0); t0 = clk::now();

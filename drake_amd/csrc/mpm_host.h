@@ -82,6 +82,15 @@ static int exception_to_status() noexcept {
 
 constexpr size_t MAX_CLOTH_MATERIALS = 256;
 
+// What the caller of a contact solve sets (mpm_update_contact, mpm_coupled_params_t)
+struct SolveParams {
+    float dt = 0.f, mu = 0.f, stiffness = 0.f, damping = 0.f;
+    int exact = 0, max_iters = 0;
+    SolveParams() = default;
+    SolveParams(float dt, float mu, float stiffness, float damping, int exact, int max_iters)
+        : dt(dt), mu(mu), stiffness(stiffness), damping(damping), exact(exact), max_iters(max_iters > 0 ? max_iters : 2000) {}   // cuda_mpm_solver.cu:234
+};
+
 struct mpm_engine {
     std::atomic<int> pins{0};   // mpm_device_synchronize of another thread is working on this engine (mpm_destroy waits)
     int device = 0;
@@ -236,7 +245,7 @@ struct mpm_engine {
                                                      // coupled substeps that ran contact-free on a watch, of them skipped and repeated
     unsigned watch_seq = 0;                          // number of the last k_ct_watch launch (Ctl::watch_hit)
     bool ct_no_watch = getenv("MPM_CT_NO_WATCH") != nullptr;   // every coupled substep generates pairs and solves (A/B, tests)
-    float last_contact_dt = 0.f, last_contact_mu = 0.f, last_contact_k = 0.f, last_contact_d = 0.f;   // its parameters
+    SolveParams last_contact_prm;   // its parameters
     mpm_dist_config_t dist_cfg{};         // partitioned domain (mpm_dist_init)
     // slot space of a partitioned rank = headroom x what it holds (mpm_dist_set_headroom, MPM_DIST_HEADROOM; 0 = the whole
     // scene's size, no shrink); grown at the migration that would overflow it (dist_resize)

@@ -286,3 +286,57 @@ def test_exact_line_search_and_a_buffer_overflow_on_a_team(monkeypatch):
     close(pos, rp, scale=1.0, rtol=1e-5, what="team, exact search: positions vs single engine")
     close(vel, rv, scale=1.0, rtol=tol, what="team, exact search: velocities vs single engine")
     close(f_sum, rf, scale=float(np.abs(rf).max()), rtol=IMPULSE_RTOL, what="team, exact search: per-body impulses")
+
+
+def test_a_pair_count_a_team_solve_may_not_index_with_is_refused_with_an_error_code():
+    """The team solve's arm of the refusal that tests/test_contact_noroundtrip_gpu.py checks on a single engine
+    (test_a_pair_count_the_solve_may_not_index_with_is_refused_with_an_error_code): a pair count on the device that lies
+    outside the capacity of the per-pair buffers makes every rank refuse (k_team_status), the host reports MPM_ERR_CAPACITY
+    and nothing has been solved; with the pairs made again the rank runs on like the single engine.
+    A team of ONE rank through mpm_update_contact: a count can only be spoilt between the pair generation and the solve,
+    mpm_world_coupled_substeps makes the pairs itself (a count spoilt before the call is overwritten, the call does not
+    raise), and one rank of a larger in-process world cannot enter the solve alone
+    (test_a_rank_that_never_arrives_is_an_error_code_not_a_hang)."""
+    import torch
+    from drake_amd import ARR, MpmError
+    from drake_amd.dist import LocalWorld
+    from tests.helpers import IMPULSE_RTOL, close, solve_tolerance
+    sheets = _scene()
+    ref, g = _engine(sheets), _engine(sheets)
+    w = LocalWorld([g], [0, 16], zone_blocks=2, ghost_cells=0, ghost_margin_cells=0, capacity_blocks=512, migrate_every=0,
+                   migrate_capacity=1 << 14, device=torch.device("cuda", 0))
+    w.enable_team(512)
+    cols = _colliders(0.0)
+    # one good coupled substep on both (buffers allocated, a previous solve's count in place)
+    first = w.coupled_substeps(1, DT, cols, MU, K, D)[0]
+    first_ref = ref.run_coupled_substeps(1, DT, cols, MU, K, D)
+    assert first[0]["contacts"] == first_ref[0]["contacts"] > 300
+    with torch.cuda.stream(w.stream):
+        w._substep(DT, -1)                  # (a grid to solve on)
+        g.generate_contact_pairs(cols, want_count=False)
+        g.debug_contact_count(count=50_000_000)
+        with pytest.raises(MpmError) as err:
+            g.update_contact(DT, MU, K, D)
+        assert err.value.code == -4, err.value          # MPM_ERR_CAPACITY
+        assert "a rank's pair count" in str(err.value)  # (the team's refusal, not the single engine's)
+        g.generate_contact_pairs(cols, want_count=False)
+        r_g = g.update_contact(DT, MU, K, D)
+    ref.substep(DT, -1)
+    ref.generate_contact_pairs(cols, want_count=False)
+    r_ref = ref.update_contact(DT, MU, K, D)
+    assert r_g["contacts"] == r_ref["contacts"] > 300
+    assert abs(r_g["iterations"] - r_ref["iterations"]) <= max(1, r_ref["iterations"] // 8), (r_g, r_ref)
+    out = w.coupled_substeps(3, DT, cols, MU, K, D)[0]
+    out_ref = ref.run_coupled_substeps(3, DT, cols, MU, K, D)
+    w.sync()
+    ref.gpu_sync()
+    assert g.stats()["error_flags"] == 0 and ref.stats()["error_flags"] == 0
+    for s in range(3):
+        assert out[s]["contacts"] == out_ref[s]["contacts"]
+        assert abs(out[s]["iterations"] - out_ref[s]["iterations"]) <= max(1, out_ref[s]["iterations"] // 8), (s, out[s], out_ref[s])
+    assert np.all(g.dist_roles() == 1)
+    close(g.download(ARR.POSITIONS), ref.download(ARR.POSITIONS), scale=1.0, rtol=1e-5, what="team of one: positions vs single engine")
+    close(g.download(ARR.VELOCITIES), ref.download(ARR.VELOCITIES), scale=1.0, rtol=solve_tolerance(ref.contact_stats()["dofs"]),
+          what="team of one: velocities vs single engine")
+    f, f_ref = g.external_body_force_to_host()[1], ref.external_body_force_to_host()[1]
+    close(f, f_ref, scale=float(np.abs(f_ref).max()), rtol=IMPULSE_RTOL, what="team of one: per-body impulses")
