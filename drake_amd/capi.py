@@ -243,6 +243,25 @@ class ARR:
     MASSES = 20
 
 
+class RT:
+    """mpm_resort_table: the tables of the last re-sort that mpm_debug_resort_tables copies out"""
+    NAMES = ("CTL", "PARAMS", "PKEY", "PRANK", "SRC_OF", "DST_OF", "IMAP", "PID", "HOME_BLOCK", "HOME_RANGE", "HOME_ITEMS",
+             "HOME_NGROUPS", "HOME_GROUPS", "HOME_NBR_ACT", "ACT_BLOCK", "ACT_NBR_HOME", "ACT_NBR_ITEMS", "LUT_HOME",
+             "LUT_ACT", "ITEM_DESC", "ITEM_ORDER", "ITEM_POS", "ITEM_FLAT", "ITEM_RNG", "BLKSTART0", "BLKSTART1", "BLKCNT0",
+             "BLKCNT1", "CELLCNT0", "CELLCNT1", "HOME_BITS", "TICKETS", "FACE_REFS")
+    # words per record, where a table is not a plain array
+    WIDTH = dict(HOME_RANGE=4, HOME_ITEMS=2, HOME_GROUPS=4, HOME_NBR_ACT=27, ACT_NBR_HOME=27, ACT_NBR_ITEMS=27, ITEM_DESC=4,
+                 ITEM_FLAT=8, ITEM_RNG=4, FACE_REFS=4)
+    UNSIGNED = ("PKEY", "PRANK", "SRC_OF", "HOME_BLOCK", "ACT_BLOCK", "ITEM_ORDER", "ITEM_POS", "HOME_BITS", "TICKETS")
+    CTL_FIELDS = ("cur", "need_rebuild", "rebuilds", "nfa", "nva", "add_f", "add_v", "n_home", "n_active", "n_items",
+                  "n_items_wanted", "error", "quiet_time", "ticket")
+    PARAM_FIELDS = ("Nf", "Np", "bits", "nb", "nblocks", "capH", "capA", "capI", "capS", "item_groups", "item_groups_small",
+                    "item_small_below", "anticip", "fem_fast", "dist_on", "NpG")
+
+
+for _k, _n in enumerate(RT.NAMES):
+    setattr(RT, _n, _k)
+
 PHASES = ("rebuild", "fem", "vforce", "p2g", "grid", "g2p")
 
 # every symbol include/mpm_hip.h declares (checked by tests/test_capi_symbols.py)
@@ -271,6 +290,7 @@ SYMBOLS = [
     "mpm_world_coupled_substeps", "mpm_set_pins", "mpm_set_body_motions", "mpm_pins_inside_collider", "mpm_get_pins",
     "mpm_add_qr_cloth_with_material", "mpm_get_cloth_info", "mpm_cloth_count", "mpm_set_grid_bodies",
     "mpm_get_grid_bodies", "mpm_set_force_fields", "mpm_get_force_fields", "mpm_force_field_acceleration",
+    "mpm_debug_resort_tables", "mpm_debug_sort_pairs",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -421,6 +441,8 @@ def load_library(build: bool = True):
         "mpm_dist_plan_migration": [vp, vp, sz, sz, sz, sz, sz, sz, sz, f, P(sz)],
         "mpm_debug_throw": [i],
         "mpm_debug_fail_alloc": [vp, i],
+        "mpm_debug_resort_tables": [vp, i, vp, sz, P(sz)],
+        "mpm_debug_sort_pairs": [vp, vp, vp, sz, i, i, i, vp, vp, P(i)],
         "mpm_chain_enable_migration": [vp, i, sz],
         "mpm_dist_set_transport": [vp, EXCHANGE_FN, ALLREDUCE_FN, vp, sz],
         "mpm_grid_collider_preset": [i, f, vp, sz, P(sz)],
@@ -682,6 +704,50 @@ class GpuMpm:
         ms = (C.c_float * 4)()
         self._ck(self.lib.mpm_profile_contact_iteration(self.h, reps, ms))
         return dict(zip(("k_ct_tile", "k_ct_node_dir", "k_ct_ls", "k_ct_decide"), (float(x) for x in ms)))
+
+    def resort_table(self, which):
+        """mpm_debug_resort_tables: one table of the last re-sort (RT.*, or its name).  CTL and PARAMS come as dicts
+        (quiet_time / anticip as floats), the others as int32 or uint32 arrays, records as rows."""
+        which = getattr(RT, which) if isinstance(which, str) else int(which)
+        name = RT.NAMES[which]
+        n = C.c_size_t()
+        probe = np.zeros(16, np.int32)
+        rc = self.lib.mpm_debug_resort_tables(self.h, which, _ptr(probe), probe.nbytes, C.byref(n))
+        out = probe[:n.value]
+        if n.value > probe.size:
+            out = np.zeros(n.value, np.int32)
+            rc = self.lib.mpm_debug_resort_tables(self.h, which, _ptr(out), out.nbytes, C.byref(n))
+        self._ck(rc)
+        if name in ("CTL", "PARAMS"):
+            fields = RT.CTL_FIELDS if name == "CTL" else RT.PARAM_FIELDS
+            d = {k: int(v) for k, v in zip(fields, out)}
+            fl = "quiet_time" if name == "CTL" else "anticip"
+            d[fl] = float(out[fields.index(fl):fields.index(fl) + 1].view(np.float32)[0])
+            if name == "CTL":
+                d["rebuilds"] &= 0xFFFFFFFF
+                d["error"] &= 0xFFFFFFFF
+            return d
+        out = out.copy()
+        if name in RT.UNSIGNED:
+            out = out.view(np.uint32)
+        w = RT.WIDTH.get(name, 1)
+        return out.reshape(-1, w) if w > 1 else out
+
+    def resort_tables(self, names=None):
+        """{name (lower case): table} of every table of RT.NAMES, or of the ones named"""
+        return {k.lower(): self.resort_table(k) for k in (names or RT.NAMES)}
+
+    def debug_sort_pairs(self, keys, vals, bits, device_count=-1, want_in_place=True):
+        """mpm_debug_sort_pairs -> (keys (2, n), vals (2, n): buffer pair a and b after the sort, info dict)"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint32)
+        vals = np.ascontiguousarray(vals, dtype=np.uint32)
+        n = int(keys.shape[0])
+        assert vals.shape == (n,)
+        ko, vo = np.zeros((2, n), np.uint32), np.zeros((2, n), np.uint32)
+        info = (C.c_int * 4)()
+        self._ck(self.lib.mpm_debug_sort_pairs(self.h, _ptr(keys), _ptr(vals), n, int(bits), int(device_count),
+                                               1 if want_in_place else 0, _ptr(ko), _ptr(vo), info))
+        return ko, vo, dict(digit_bits=info[0], passes=info[1], tiles=info[2], in_b=bool(info[3]))
 
     def owed_substeps(self) -> int:
         n = C.c_uint32()

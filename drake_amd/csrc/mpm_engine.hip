@@ -23,6 +23,7 @@
 #include "../../include/mpm_hip.h"
 #include "mpm_host.h"
 #include "mpm_io.h"
+#include "mpm_debug_tables.h"
 #include "mpm_contact.h"
 #include "mpm_chain.h"
 #include "mpm_feedback.h"
@@ -1936,6 +1937,19 @@ int mpm_debug_counters(mpm_handle_t e, uint64_t* out16, int reset) try {
     if (reset) HIP_TRY(hipMemsetAsync(e->dp.dbgbuf, 0, 16 * 8, e->stream));
     HIP_TRY(hipStreamSynchronize(e->stream));
     return 0;
+} MPM_CATCH_ALL
+
+int mpm_debug_resort_tables(mpm_handle_t e, int which, void* out, size_t capacity_bytes, size_t* count_out) try {
+    READY(e);
+    REQUIRE(out || capacity_bytes == 0, "null output");
+    return debug_resort_table(e, which, out, capacity_bytes, count_out);
+} MPM_CATCH_ALL
+
+int mpm_debug_sort_pairs(mpm_handle_t e, const uint32_t* keys, const uint32_t* vals, size_t n, int bits, int device_count,
+                         int want_in_place, uint32_t* keys_out, uint32_t* vals_out, int info_out[4]) try {
+    REQUIRE(e, "null handle");
+    if (int rc = use(e)) return rc;
+    return debug_sort_pairs(e, keys, vals, n, bits, device_count, want_in_place, keys_out, vals_out, info_out);
 } MPM_CATCH_ALL
 
 int mpm_set_dump_dir(mpm_handle_t e, const char* dir) try {

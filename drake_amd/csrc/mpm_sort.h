@@ -1,5 +1,5 @@
-// Stable LSD radix sort of (key, value) pairs on the device, 8 to 11 bits per pass (as few passes as
-// the key width allows: a pass is three launches).
+// Stable LSD radix sort of (key, value) pairs on the device, 8 to 11 bits per pass (the digit width and with it the
+// number of passes come from a cost model, sort_plan below: a pass is two launches).
 //
 // Used where an order has to be *stable* and reproducible: the slot order of
 // RebuildMapping(sort = true) (the reference's 16-bit radix sort,
@@ -51,124 +51,6 @@ __global__ __launch_bounds__(64 * SORT_WAVES) void k_sort_hist(const uint32_t* k
     }
     __syncthreads();
     for (int d = tid; d < ND; d += 64 * SORT_WAVES) hist[(size_t)tile * ND + d] = s_cnt[d];
-}
-
-// Exclusive scan of one int per thread across a 1024-thread workgroup (shared by the scans below).
-MPM_DEV int wg1024_exclusive(int v, int& total, int* s_w) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    __syncthreads();   // s_w may still be read from the previous call
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int pre = 0, tot = 0;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) {
-        const int t = s_w[k];
-        pre += k < w ? t : 0;
-        tot += t;
-    }
-    total = tot;
-    return pre + inc - v;
-}
-
-// exclusive scan of `total` ints in place, one 1024-thread workgroup; every thread owns 16
-// consecutive entries (four 16-byte loads) of each 16384-entry block.  `a` must be 16-byte
-// aligned and padded to a multiple of 4 entries.
-MPM_DEV void wg1024_scan_inplace(int* a, int total, int* s_w /* [16] shared */) {
-    const int tid = threadIdx.x;
-    int carry = 0;
-    for (int base = 0; base < total; base += 16384) {
-        int4 v[4];
-        int sum = 0;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = base + tid * 16 + q * 4;
-            v[q] = i < total ? *reinterpret_cast<const int4*>(a + i) : make_int4(0, 0, 0, 0);
-            if (i + 1 >= total) v[q].y = 0;
-            if (i + 2 >= total) v[q].z = 0;
-            if (i + 3 >= total) v[q].w = 0;
-            sum += v[q].x + v[q].y + v[q].z + v[q].w;
-        }
-        int block_total;
-        int run = carry + wg1024_exclusive(sum, block_total, s_w);
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int i = base + tid * 16 + q * 4;
-            int4 o;
-            o.x = run; run += v[q].x;
-            o.y = run; run += v[q].y;
-            o.z = run; run += v[q].z;
-            o.w = run; run += v[q].w;
-            if (i + 3 < total) {
-                *reinterpret_cast<int4*>(a + i) = o;
-            } else {
-                if (i < total) a[i] = o.x;
-                if (i + 1 < total) a[i + 1] = o.y;
-                if (i + 2 < total) a[i + 2] = o.z;
-            }
-        }
-        carry += block_total;
-    }
-}
-__global__ __launch_bounds__(1024) void k_sort_scan(int* a, int total) {
-    __shared__ int s_w[16];
-    wg1024_scan_inplace(a, total, s_w);
-}
-
-// Large exclusive scan: k_scan_blocks scans 4096-entry blocks in place and records their totals,
-// k_sort_scan scans the totals, k_scan_add adds them back.  `n` entries, padded storage to a
-// multiple of 4096.
-__global__ __launch_bounds__(256) void k_scan_blocks(int* a, int n, int* sums) {
-    __shared__ int s_w[4];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int base = blockIdx.x * 4096 + tid * 16;
-    int4 v[4];
-    int sum = 0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const int i = base + q * 4;
-        v[q] = *reinterpret_cast<const int4*>(a + i);
-        if (i >= n) v[q].x = 0;
-        if (i + 1 >= n) v[q].y = 0;
-        if (i + 2 >= n) v[q].z = 0;
-        if (i + 3 >= n) v[q].w = 0;
-        sum += v[q].x + v[q].y + v[q].z + v[q].w;
-    }
-    int inc = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int t = __shfl_up(inc, d);
-        if (lane >= d) inc += t;
-    }
-    if (lane == 63) s_w[w] = inc;
-    __syncthreads();
-    int run = inc - sum;
-    for (int k = 0; k < w; ++k) run += s_w[k];
-    if (tid == 255) sums[blockIdx.x] = run + sum;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        int4 o;
-        o.x = run; run += v[q].x;
-        o.y = run; run += v[q].y;
-        o.z = run; run += v[q].z;
-        o.w = run; run += v[q].w;
-        *reinterpret_cast<int4*>(a + base + q * 4) = o;
-    }
-}
-__global__ __launch_bounds__(256) void k_scan_add(int* a, const int* sums) {
-    const int off = sums[blockIdx.x];
-    int4* q = reinterpret_cast<int4*>(a + blockIdx.x * 4096) + threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        int4 v = q[k * 256];
-        v.x += off; v.y += off; v.z += off; v.w += off;
-        q[k * 256] = v;
-    }
 }
 
 template <int DB>
@@ -322,18 +204,6 @@ __global__ __launch_bounds__(64 * SORT_WAVES) void k_sort_scatter(const uint32_t
 
 }  // namespace mpm
 
-// In-place exclusive scan of n ints (storage padded to a multiple of 4096); sums: n/4096 + 2 ints,
-// sums[nblocks] receives the grand total.
-static int device_exclusive_scan(hipStream_t s, int* a, size_t n, int* sums) {
-    using namespace mpm;
-    const int nb = (int)((n + 4095) / 4096);
-    if (hipMemsetAsync(sums + nb, 0, 4, s) != hipSuccess) return -1;
-    hipLaunchKernelGGL(k_scan_blocks, dim3(nb), dim3(256), 0, s, a, (int)n, sums);
-    hipLaunchKernelGGL(k_sort_scan, dim3(1), dim3(1024), 0, s, sums, nb + 1);
-    hipLaunchKernelGGL(k_scan_add, dim3(nb), dim3(256), 0, s, a, (const int*)sums);
-    return 0;
-}
-
 static inline int sort_items_for(size_t n) { return n > (1u << 18) ? 64 : 16; }
 
 constexpr int SORT_MAX_DIGIT_BITS = 11;
@@ -349,6 +219,31 @@ static inline size_t sort_hist_ints(size_t n) {
 static inline size_t sort_hist_ints_upto(size_t n) {
     const size_t knee = (size_t)1 << 18;
     return n > knee ? std::max(sort_hist_ints(n), sort_hist_ints(knee)) : sort_hist_ints(n);
+}
+
+// Tile size, digit width and passes of a sort of n pairs by `bits` key bits (radix_sort_pairs; mpm_debug_sort_pairs
+// reports it).  Digit width: a pass costs two launches (~11 us at the contact solve's sizes) plus, in every workgroup of
+// the scatter, a walk over the 2^db x ntiles table of all tiles' histograms (L2 reads, ~1 us per 64 KB).
+struct SortPlan {
+    int items, ntiles, digit_bits, passes;
+};
+static inline SortPlan sort_plan(size_t n, int bits) {
+    SortPlan pl;
+    pl.items = sort_items_for(n);
+    pl.ntiles = (int)((n + (size_t)64 * pl.items - 1) / ((size_t)64 * pl.items));
+    pl.digit_bits = 8;
+    pl.passes = (bits + 7) / 8;
+    double best = 1e30;
+    for (int d = 8; d <= SORT_MAX_DIGIT_BITS; ++d) {
+        const int ps = (bits + d - 1) / d;
+        const double cost = ps * (11.0 + (double)(((size_t)1 << d) * pl.ntiles * 4) / 65536.0);
+        if (cost < best) {
+            best = cost;
+            pl.digit_bits = d;
+            pl.passes = ps;
+        }
+    }
+    return pl;
 }
 
 template <int DB>
@@ -369,23 +264,8 @@ static int radix_sort_pairs(hipStream_t s, uint32_t* ka, uint32_t* va, uint32_t*
     using namespace mpm;
     if (in_b) *in_b = false;
     if (n < 2 || bits <= 0) return 0;
-    const int items = sort_items_for(n);
-    const int ntiles = (int)((n + (size_t)64 * items - 1) / ((size_t)64 * items));
-    // digit width: a pass costs two launches (~11 us at the contact solve's sizes) plus, in every workgroup of the
-    // scatter, a walk over the 2^db x ntiles table of all tiles' histograms (L2 reads, ~1 us per 64 KB)
-    int db = 8, passes = (bits + 7) / 8;
-    {
-        double best = 1e30;
-        for (int d = 8; d <= SORT_MAX_DIGIT_BITS; ++d) {
-            const int ps = (bits + d - 1) / d;
-            const double cost = ps * (11.0 + (double)(((size_t)1 << d) * ntiles * 4) / 65536.0);
-            if (cost < best) {
-                best = cost;
-                db = d;
-                passes = ps;
-            }
-        }
-    }
+    const SortPlan pl = sort_plan(n, bits);
+    const int items = pl.items, ntiles = pl.ntiles, db = pl.digit_bits, passes = pl.passes;
     uint32_t *ki = ka, *vi = va, *ko = kb, *vo = vb;
     for (int pass = 0; pass < passes; ++pass) {
         const int shift = pass * db;

@@ -975,6 +975,45 @@ MPM_API int mpm_get_stats(mpm_handle_t h, mpm_stats_t *out);
  * MPM_DBG environment variable has bit 2 set (see DESIGN.md "Diagnostics"). */
 MPM_API int mpm_debug_counters(mpm_handle_t h, uint64_t *out16, int reset);
 
+/* Tests: one table of the last conditional re-sort (drake_amd/csrc/mpm_rebuild.h), copied to the host as it stands.
+ * Launches what phase calls have held back, waits for the engine's stream, then copies.  Every table is an array of
+ * 4-byte words (int4 / int2 records flattened); *count_out gets the number of words (also when `out` is too small,
+ * which fails with MPM_ERR_INVALID).
+ *   MPM_RT_CTL     14 words: cur, need_rebuild, rebuilds, nfa, nva, add_f, add_v, n_home, n_active, n_items,
+ *                  n_items_wanted, error, quiet_time (float bits), ticket
+ *   MPM_RT_PARAMS  16 words: Nf, Np, bits, nb, nblocks, capH, capA, capI, capS, item_groups, item_groups_small,
+ *                  item_small_below, anticip (float bits: cells binned ahead per unit of velocity, as the next re-sort
+ *                  would use it), fem_fast, dist.on, NpG
+ *   per slot (Np words): PKEY, PRANK, SRC_OF, DST_OF, PID (of the current particle set); IMAP: NpG words
+ *   per home block (n_home records): HOME_BLOCK, HOME_RANGE (4), HOME_ITEMS (2), HOME_NGROUPS, HOME_NBR_ACT (27);
+ *                  HOME_GROUPS: the whole pool, (Np / 64 + capH + 2) records of 4
+ *   per active block (n_active records): ACT_BLOCK, ACT_NBR_HOME (27), ACT_NBR_ITEMS (27)
+ *   per item (n_items records): ITEM_DESC (4), ITEM_ORDER, ITEM_POS, ITEM_FLAT (8), ITEM_RNG (4)
+ *   whole arrays: LUT_HOME, LUT_ACT, BLKSTART0/1, BLKCNT0/1 (nblocks), CELLCNT0/1 (cells), HOME_BITS (nblocks / 32 + 1),
+ *                  TICKETS (1024)
+ *   FACE_REFS      per face slot (Nf records of 4): the face's record of corner references in the current set, bit
+ *                  for bit: (corner ranks, slot of corner 0, of corner 1, of corner 2) */
+enum mpm_resort_table {
+    MPM_RT_CTL = 0, MPM_RT_PARAMS, MPM_RT_PKEY, MPM_RT_PRANK, MPM_RT_SRC_OF, MPM_RT_DST_OF, MPM_RT_IMAP, MPM_RT_PID,
+    MPM_RT_HOME_BLOCK, MPM_RT_HOME_RANGE, MPM_RT_HOME_ITEMS, MPM_RT_HOME_NGROUPS, MPM_RT_HOME_GROUPS, MPM_RT_HOME_NBR_ACT,
+    MPM_RT_ACT_BLOCK, MPM_RT_ACT_NBR_HOME, MPM_RT_ACT_NBR_ITEMS, MPM_RT_LUT_HOME, MPM_RT_LUT_ACT,
+    MPM_RT_ITEM_DESC, MPM_RT_ITEM_ORDER, MPM_RT_ITEM_POS, MPM_RT_ITEM_FLAT, MPM_RT_ITEM_RNG,
+    MPM_RT_BLKSTART0, MPM_RT_BLKSTART1, MPM_RT_BLKCNT0, MPM_RT_BLKCNT1, MPM_RT_CELLCNT0, MPM_RT_CELLCNT1,
+    MPM_RT_HOME_BITS, MPM_RT_TICKETS, MPM_RT_FACE_REFS
+};
+MPM_API int mpm_debug_resort_tables(mpm_handle_t h, int which, void *out, size_t capacity_bytes, size_t *count_out);
+
+/* Tests: the device radix sort (drake_amd/csrc/mpm_sort.h) on caller-made pairs.  Two buffer pairs a and b of n pairs
+ * each are filled with byte patterns (keys a 0xA5, values a 0x5A, keys b 0xB6, values b 0x6B); the first n pairs --
+ * with device_count >= 0 only the first device_count -- are uploaded into a; the n pairs are sorted by the key bits
+ * [0, bits), stable.  device_count >= 0: the count is handed over in device memory and n is only the launch bound.
+ * want_in_place != 0: the result is asked for in a; 0: wherever the last pass left it, info_out[3] says where.
+ * keys_out / vals_out: uint32[2 n], pair a then pair b, both downloaded in full.
+ * info_out: {digit bits, passes, tiles, result in b}. */
+MPM_API int mpm_debug_sort_pairs(mpm_handle_t h, const uint32_t *keys, const uint32_t *vals, size_t n, int bits,
+                                 int device_count, int want_in_place, uint32_t *keys_out, uint32_t *vals_out,
+                                 int info_out[4]);
+
 /* Copies one engine array to the host (see mpm_array_id).  `bytes` is the
  * size of `out`; the call fails if it is too small. *written gets the number
  * of bytes produced (may be NULL). */
