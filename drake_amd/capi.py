@@ -198,6 +198,11 @@ class ClothMaterial(C.Structure):
         return {f: float(getattr(self, f)) for f, _ in self._fields_}
 
 
+class ContactMaterial(C.Structure):
+    """mpm_contact_material_t: a rigid body's contact parameters; a field < 0 inherits the solving call's scalar"""
+    _fields_ = [("friction_mu", C.c_float), ("stiffness", C.c_float), ("damping", C.c_float)]
+
+
 class ContactStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("line_search_evals", C.c_int32), ("contacts", C.c_uint32),
                 ("nodes", C.c_uint32), ("residual", C.c_float), ("alpha", C.c_float), ("energy", C.c_float),
@@ -290,7 +295,8 @@ SYMBOLS = [
     "mpm_world_coupled_substeps", "mpm_set_pins", "mpm_set_body_motions", "mpm_pins_inside_collider", "mpm_get_pins",
     "mpm_add_qr_cloth_with_material", "mpm_get_cloth_info", "mpm_cloth_count", "mpm_set_grid_bodies",
     "mpm_get_grid_bodies", "mpm_set_force_fields", "mpm_get_force_fields", "mpm_force_field_acceleration",
-    "mpm_debug_resort_tables", "mpm_debug_sort_pairs",
+    "mpm_debug_resort_tables", "mpm_debug_sort_pairs", "mpm_set_body_contact_materials",
+    "mpm_get_body_contact_materials",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -387,6 +393,8 @@ def load_library(build: bool = True):
         "mpm_sdf_shape_download": [vp, C.c_uint32, vp],
         "mpm_set_sdf_colliders": [vp, sz, vp],
         "mpm_sdf_collider_signed_distance": [vp, vp, sz, vp, vp, vp],
+        "mpm_set_body_contact_materials": [vp, sz, vp],
+        "mpm_get_body_contact_materials": [vp, vp, sz, P(sz)],
         "mpm_download_contact_pairs": [vp, vp, vp, vp, vp, vp, vp, vp],
         "mpm_set_deterministic": [vp, i],
         "mpm_set_fast_math": [vp, i],
@@ -827,6 +835,21 @@ class GpuMpm:
         """mpm_set_sdf_colliders: the engine's mesh colliders (SdfCollider list; empty clears them)"""
         arr = (SdfCollider * max(len(colliders), 1))(*colliders)
         self._ck(self.lib.mpm_set_sdf_colliders(self.h, len(colliders), arr))
+
+    def set_body_contact_materials(self, materials):
+        """mpm_set_body_contact_materials: array-like (n, 3) of (friction_mu, stiffness, damping), row b for rigid body b;
+        a field < 0 and every body >= n take the solving call's scalar; an empty table clears it"""
+        m = _f32(materials if len(materials) else np.zeros((0, 3), np.float32), (-1, 3))
+        self._ck(self.lib.mpm_set_body_contact_materials(self.h, int(m.shape[0]), _ptr(m) if m.shape[0] else None))
+
+    def body_contact_materials(self):
+        """mpm_get_body_contact_materials: the table as it was set, (n, 3) float32"""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_body_contact_materials(self.h, None, 0, C.byref(n)))
+        out = np.zeros((int(n.value), 3), np.float32)
+        if n.value:
+            self._ck(self.lib.mpm_get_body_contact_materials(self.h, _ptr(out), int(n.value), C.byref(n)))
+        return out
 
     def sdf_collider_signed_distance(self, collider, points):
         """mpm_sdf_collider_signed_distance: points (n, 3) in the world -> (phi (n,), unit world gradient (n, 3))"""

@@ -51,6 +51,7 @@ static int ensure_contact_capacity(mpm_engine* e, size_t n) {
             (rc = grow(&b.order2, pad)) || (rc = grow(&b.cnode, 27 * cap)) || (rc = grow(&b.cfx, 3 * cap)) ||
             (rc = grow(&b.cmass, cap)) || (rc = grow(&b.cphi0, cap)) || (rc = grow(&b.cR, 9 * cap)) ||
             (rc = grow(&b.cv0, 3 * cap)) || (rc = grow(&b.crv, 3 * cap)) || (rc = grow(&b.cvel, 3 * cap)) ||
+            (rc = grow(&b.cmat, 3 * cap)) ||
             (rc = grow(&b.seg_part, cap * CT_SEG_F)) || (rc = grow(&b.prev_key, cap)) || (rc = grow(&b.prev_api, cap)) ||
             (rc = grow(&b.prev_body, cap)))
             return rc;
@@ -527,6 +528,39 @@ static int set_sdf_colliders(mpm_engine* e, size_t n, const mpm_sdf_collider_t* 
     return 0;
 }
 
+// mpm_set_body_contact_materials: the table as given stays on the host (mpm_get_body_contact_materials, the comparison of
+// a world's ranks), a copy goes to the device on the engine's stream: solves enqueued afterwards read it (k_ct_prepare)
+constexpr size_t MAX_BODY_MATERIALS = 65536;
+static int validate_body_contact_materials(size_t n, const mpm_contact_material_t* m) {
+    REQUIRE(n <= MAX_BODY_MATERIALS, "too many body contact materials");
+    for (size_t k = 0; k < n; ++k)
+        REQUIRE(std::isfinite(m[k].friction_mu) && std::isfinite(m[k].stiffness) && std::isfinite(m[k].damping),
+                "body contact material: a field is not finite");
+    return 0;
+}
+static int set_body_contact_materials(mpm_engine* e, size_t n, const mpm_contact_material_t* m) {
+    ContactBuffers& b = e->cb;
+    if (n > b.cap_mat) {
+        GrowPoison gp(e);
+        if (int rc = grow(&b.mat, 3 * n)) {
+            b.cap_mat = 0;
+            b.materials.clear();
+            return rc;
+        }
+        b.cap_mat = n;
+    }
+    static_assert(sizeof(mpm_contact_material_t) == 12, "k_ct_prepare reads the table as [n][3] floats");
+    // (the upload first: a copy that fails leaves no table at all rather than a length over stale device contents)
+    b.materials.clear();
+    if (n) H2D(e, b.mat, m, n * sizeof(mpm_contact_material_t));   // (synchronises: the caller's array is free on return)
+    b.materials.assign(m, m + n);
+    return 0;
+}
+static bool same_body_contact_materials(const mpm_engine* a, const mpm_engine* b) {
+    const auto &x = a->cb.materials, &y = b->cb.materials;
+    return x.size() == y.size() && (x.empty() || std::memcmp(x.data(), y.data(), x.size() * sizeof(mpm_contact_material_t)) == 0);
+}
+
 // mpm_sdf_collider_signed_distance: k_ct_sdf_mesh_query on the engine's stream, through a scratch allocation of this call
 static int sdf_collider_signed_distance(mpm_engine* e, const mpm_sdf_collider_t* col, size_t n, const float* x, float* phi,
                                         float* grad) {
@@ -586,6 +620,7 @@ static ContactDev make_contact_dev(mpm_engine* e, const SolveParams& prm, bool s
     c.order = alt ? b.order2 : b.order;
     c.cnode = b.cnode; c.cfx = b.cfx; c.cmass = b.cmass; c.cphi0 = b.cphi0; c.cR = b.cR; c.cv0 = b.cv0;
     c.crv = b.crv; c.cvel = b.cvel; c.seg_part = b.seg_part;
+    c.cmat = b.cmat; c.mat = b.mat; c.n_mat = (int)b.materials.size();
     c.run = b.run; c.node_flag = b.node_flag; c.node_list = b.node_list; c.flag_bits = b.flag_bits; c.node_runs = b.node_runs;
     c.cap_nodes = (int)b.cap_cells; c.gD = b.gD; c.hg = b.hg;
     c.part = b.part; c.part_dir = b.part_dir; c.st = b.st; c.it_log = b.it_log;
@@ -596,6 +631,13 @@ static ContactDev make_contact_dev(mpm_engine* e, const SolveParams& prm, bool s
     c.imp_fix = e->dp.fix_p;
     b.imp_unfix = e->dp.unfix_p;
     return c;
+}
+
+// k_ct_tile: the instance that reads the per-contact parameter planes only when the engine holds a table of per-body
+// materials; without one, the instance that is the kernel of an engine without the feature
+static void launch_ct_tile(dim3 grid, hipStream_t s, const DP& p, const ContactDev& c, int first, int lazy) {
+    if (c.n_mat) hipLaunchKernelGGL(k_ct_tile<true>, grid, dim3(256), 0, s, p, c, first, lazy);
+    else hipLaunchKernelGGL(k_ct_tile<false>, grid, dim3(256), 0, s, p, c, first, lazy);
 }
 
 // ---- partitioned domain: transports of the distributed solve ----------------------------------
@@ -723,7 +765,8 @@ static bool partitioned_solve(const mpm_engine* e) { return e->dp.dist.on && (e-
 // the energy sums -- and with them every `E1 <= E0` decision -- do not depend on what sized the launch; workgroups
 // without a tile write a row of zeros), then CT_ROWS workgroups of its grid-stride node part
 static void launch_ls(const SolveCtx& x, int exact, float alpha) {
-    hipLaunchKernelGGL(k_ct_ls, dim3(CT_ROWS_CON + CT_ROWS), dim3(CT_WG), 0, x.e->stream, x.e->dp, x.c, CT_ROWS_CON, exact, alpha);
+    if (x.c.n_mat) hipLaunchKernelGGL(k_ct_ls<true>, dim3(CT_ROWS_CON + CT_ROWS), dim3(CT_WG), 0, x.e->stream, x.e->dp, x.c, CT_ROWS_CON, exact, alpha);
+    else hipLaunchKernelGGL(k_ct_ls<false>, dim3(CT_ROWS_CON + CT_ROWS), dim3(CT_WG), 0, x.e->stream, x.e->dp, x.c, CT_ROWS_CON, exact, alpha);
 }
 static void launch_decide(const SolveCtx& x, int exact, int phase) {
     hipLaunchKernelGGL(k_ct_decide, dim3(1), dim3(1024), 0, x.e->stream, x.c, CT_DIR_WG, CT_ROWS_CON, CT_ROWS, exact, phase, x.t);
@@ -839,7 +882,7 @@ static int profile_contact_iteration(mpm_engine* e, int reps, float* kernel_ms) 
     for (auto& ev_k : ev) HIP_TRY(hipEventCreate(&ev_k));
     auto phase = [&](int k) {
         for (int r = 0; r < reps; ++r) {
-            if (k == 0) hipLaunchKernelGGL(k_ct_tile, dim3(x.g.n_tile_wg), dim3(256), 0, s, p, x.c, 0, 0);
+            if (k == 0) launch_ct_tile(dim3(x.g.n_tile_wg), s, p, x.c, 0, 0);
             if (k == 1) hipLaunchKernelGGL(k_ct_node_dir<0>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, x.c, 0);
             if (k == 2) launch_ls(x, 0, 0.f);
             if (k == 3) launch_decide(x, 0, 0);
@@ -910,9 +953,11 @@ static int solve_once(mpm_engine* e, const SolveParams& prm, bool full_setup, So
     if (int rc = enqueue_sort(&x, prm, reuse)) return rc;
     const ContactDev& c = x.c;
     if (reuse) {
-        hipLaunchKernelGGL(k_ct_prepare<true>, dim3(x.g.gc), dim3(256), 0, s, p, c);
+        if (c.n_mat) hipLaunchKernelGGL((k_ct_prepare<true, true>), dim3(x.g.gc), dim3(256), 0, s, p, c);
+        else hipLaunchKernelGGL(k_ct_prepare<true>, dim3(x.g.gc), dim3(256), 0, s, p, c);
     } else {
-        hipLaunchKernelGGL(k_ct_prepare<false>, dim3(x.g.gc), dim3(256), 0, s, p, c);
+        if (c.n_mat) hipLaunchKernelGGL((k_ct_prepare<false, true>), dim3(x.g.gc), dim3(256), 0, s, p, c);
+        else hipLaunchKernelGGL(k_ct_prepare<false>, dim3(x.g.gc), dim3(256), 0, s, p, c);
         if (dist) {
             // a node in a zone may be reached by the neighbour's contacts only: both ranks need it listed
             hipLaunchKernelGGL(k_ct_flags_to_field, dim3(512), dim3(256), 0, s, p, c, 0);
@@ -961,14 +1006,14 @@ static int solve_once(mpm_engine* e, const SolveParams& prm, bool full_setup, So
 // contact gradients/Hessians and their per-cell sums, then (H, G) and the direction per node
 static void launch_direction(const SolveCtx& x, int first, int lazy) {
     const DP& p = x.e->dp;
-    hipLaunchKernelGGL(k_ct_tile, dim3(x.g.n_tile_wg), dim3(256), 0, x.e->stream, p, x.c, first, lazy);
+    launch_ct_tile(dim3(x.g.n_tile_wg), x.e->stream, p, x.c, first, lazy);
     hipLaunchKernelGGL(k_ct_node_dir<0>, dim3(CT_DIR_WG), dim3(CT_WG), 0, x.e->stream, p, x.c, lazy);
 }
 // ... of a partitioned domain: this rank's (H, G) per node | zone exchange | solve per node
 static int partitioned_direction(const SolveCtx& x, int first) {
     const DP& p = x.e->dp;
     hipStream_t s = x.e->stream;
-    hipLaunchKernelGGL(k_ct_tile, dim3(x.g.n_tile_wg), dim3(256), 0, s, p, x.c, first, 0);
+    launch_ct_tile(dim3(x.g.n_tile_wg), s, p, x.c, first, 0);
     hipLaunchKernelGGL(k_ct_node_dir<1>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, x.c, 0);
     if (int rc = zone_exchange3(x.e, x.e->cb.hg)) return rc;
     hipLaunchKernelGGL(k_ct_node_dir<2>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, x.c, 0);
@@ -1172,7 +1217,8 @@ static int team_solve_once(const std::vector<mpm_engine*>& L, const SolveParams&
         hipStream_t s = e->stream;
         const DP& p = e->dp;
         hipLaunchKernelGGL(k_team_status<1>, dim3(1), dim3(64), 0, s, r.c, r.t, e->dp.ctl);
-        hipLaunchKernelGGL(k_ct_prepare<false>, dim3(r.g.gc), dim3(256), 0, s, p, r.c);
+        if (r.c.n_mat) hipLaunchKernelGGL((k_ct_prepare<false, true>), dim3(r.g.gc), dim3(256), 0, s, p, r.c);
+        else hipLaunchKernelGGL(k_ct_prepare<false>, dim3(r.g.gc), dim3(256), 0, s, p, r.c);
         // a node in a zone may be reached by the neighbour's contacts only: both ranks need it listed
         hipLaunchKernelGGL(k_ct_flags_to_field, dim3(512), dim3(256), 0, s, p, r.c, 0);
         hipLaunchKernelGGL(k_team_zone_pack<3>, dim3(e->g_grid, 2), dim3(256), 0, s, p, r.c, r.t, (const float4*)e->cb.hg, 0);
@@ -1196,7 +1242,7 @@ static int team_solve_once(const std::vector<mpm_engine*>& L, const SolveParams&
         mpm_engine* e = r.e;
         hipStream_t s = e->stream;
         const DP& p = e->dp;
-        hipLaunchKernelGGL(k_ct_tile, dim3(r.g.n_tile_wg), dim3(256), 0, s, p, r.c, first, lazy);
+        launch_ct_tile(dim3(r.g.n_tile_wg), s, p, r.c, first, lazy);
         hipLaunchKernelGGL(k_ct_node_dir<1>, dim3(CT_DIR_WG), dim3(CT_WG), 0, s, p, r.c, 0);
         hipLaunchKernelGGL(k_team_zone_pack<3>, dim3(e->g_grid, 2), dim3(256), 0, s, p, r.c, r.t, (const float4*)e->cb.hg, 1);
         hipLaunchKernelGGL(k_team_zone_signal, dim3(1), dim3(64), 0, s, r.c, r.t, 1);

@@ -166,6 +166,14 @@ struct ContactDev {
     long long* body_acc;    // [n_bodies][6] (tau, f) impulse sums in 64-bit fixed point (k_ct_impulse)
     double imp_fix;         // its scale (DP::fix_p: the momentum scale of ParticleToGrid's tiles)
     int n_bodies;
+    // per-body contact materials (mpm_set_body_contact_materials).  n_mat == 0: no table, every contact takes (mu, k, d)
+    // above and the kernels touch neither `mat` nor `cmat`
+    // (k_ct_tile<false> / k_ct_ls<false>: the kernels of an engine without the feature).  Otherwise k_ct_prepare resolves every contact's triple --
+    // a select per field between the table entry of its body and the call's scalar, never arithmetic -- into cmat, and
+    // k_ct_tile / k_ct_ls read it from there
+    const float* mat;       // [n_mat][3] (friction_mu, stiffness, damping) per body; a field < 0 inherits the call's
+    int n_mat;
+    float* cmat;            // [3][n] resolved (mu, k, d) per contact (sorted order)
 };
 
 struct Collider {        // mirrors mpm_collider_t (include/mpm_hip.h)
@@ -205,7 +213,11 @@ struct ContactBuffers {
     size_t cap_hist = 0;
     int* cnode = nullptr;
     float *cfx = nullptr, *cmass = nullptr, *cphi0 = nullptr, *cR = nullptr, *cv0 = nullptr, *crv = nullptr,
-          *cvel = nullptr;
+          *cvel = nullptr, *cmat = nullptr;
+    // per-body contact materials (mpm_set_body_contact_materials): the caller's table as given, and as the kernels read it
+    std::vector<mpm_contact_material_t> materials;
+    float* mat = nullptr;
+    size_t cap_mat = 0;
     int2* run = nullptr;
     int* node_flag = nullptr;
     unsigned long long* flag_bits = nullptr;
@@ -254,7 +266,7 @@ struct ContactBuffers {
         for (SdfShape& sh : shapes)
             if (sh.val) (void)hipFree(sh.val);
         void* ptrs[] = {api_idx, colliders, mesh, gen_cnt, gen_sums, slot, body, dist, normal, pos, rigid_v, p_WB, vel, vel0, key, order, key2, order2, sort_hist,
-                        cnode, cfx, cmass, cphi0, cR, cv0, crv, cvel, run, node_flag, flag_bits, node_list, node_runs, seg_part, gD, hg,
+                        cnode, cfx, cmass, cphi0, cR, cv0, crv, cvel, cmat, mat, run, node_flag, flag_bits, node_list, node_runs, seg_part, gD, hg,
                         zone_buf[0], zone_buf[1], zone_buf[2], zone_buf[3], part, part_dir, st, it_log, body_acc,
                         prev_key, prev_api, prev_body};
         for (void* q : ptrs)
@@ -911,7 +923,9 @@ MPM_DEV void gather_from_nodes(const DP& p, const int* g, float fx, float fy, fl
 // REUSE: the pair list equals the previous solve's (ContactState::changed_solve, verified by k_ct_keys in front of this
 // launch): the sorted order, the per-cell runs, the stencil nodes and the node list of that solve stand; only what
 // moves with the particles is refreshed.
-template <bool REUSE>
+// MAT: the engine holds a table of per-body contact materials (ContactDev::n_mat > 0: the host launches that instance);
+// every contact's (mu, k, d) is resolved here, for k_ct_tile<true> and k_ct_ls<true>.
+template <bool REUSE, bool MAT = false>
 __global__ __launch_bounds__(256) void k_ct_prepare(DP p, ContactDev c) {
     const int n = ct_count(c);
     const int N = c.stride;
@@ -998,6 +1012,17 @@ __global__ __launch_bounds__(256) void k_ct_prepare(DP p, ContactDev c) {
         c.cvel[t * N + j] = c.vel[k * 3 + t];   // contact_vel of CopyContactPairs (first iteration)
     }
     c.cphi0[j] = -c.dist[k];
+    if (MAT) {
+        // this contact's (mu, k, d): the entry of its body where the table has one and the field is set, else the call's
+        const uint32_t bd = c.body[k];
+        const bool has = bd < (uint32_t)c.n_mat;   // (compared before the table is read)
+        const float call[3] = {c.mu, c.k, c.d};
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const float m = has ? c.mat[(size_t)bd * 3 + t] : -1.f;
+            c.cmat[t * N + j] = m < 0.f ? call[t] : m;
+        }
+    }
     // pre-contact velocity at the contact point (what k_ct_gather_vel did as a launch of its own)
     float vg[3];
     gather_from_nodes(p, gn, fx[0], fx[1], fx[2], vg);
@@ -1233,6 +1258,15 @@ MPM_DEV void tile_segments(uint32_t key, int cnt, int* s_seg, int* s_cseg, int* 
     }
 }
 
+// The contact model's parameters of sorted contact j (j < ct_count() <= N) with a table of per-body materials: the triple
+// k_ct_prepare resolved, three coalesced loads beside those of cR / cv0 / cphi0.  Without a table (MAT = false) the
+// call's scalars as they are: no load, no branch -- the host launches that instance when ContactDev::n_mat == 0.
+template <bool MAT>
+MPM_DEV ContactParams contact_params_of(const ContactDev& c, const ContactParams& call, int N, int j) {
+    if (!MAT) return call;
+    return ContactParams{call.dt, c.cmat[j], c.cmat[N + j], c.cmat[2 * N + j], call.epsv};
+}
+
 // C1 + G1a: one workgroup per tile of CT_TILE sorted contacts.
 //  0. Contacts of one cell share their 27 stencil nodes: the nodes of every segment are read once, into
 //     LDS (per contact, the 62k x 27 gathers of config 3 kept the L1 tag lookup busy for ~9 us).
@@ -1248,6 +1282,7 @@ MPM_DEV void tile_segments(uint32_t key, int cnt, int* s_seg, int* s_cseg, int* 
 // 31-47 us per Newton iteration on config 3, 62k contacts in 4225 cells.)
 // lazy: the step of the previous Newton iteration has not been added to the grid yet (k_ct_node_dir does
 // that, after this kernel): velocities are read as v - alpha D.
+template <bool MAT>
 __global__ __launch_bounds__(256) void k_ct_tile(DP p, ContactDev c, int first, int lazy) {
     // (the first tile's keys are requested together with the solver state: one round trip instead of two before the
     // kernel knows what to do -- the state was written by a single workgroup of the previous kernel and is a miss in
@@ -1276,7 +1311,7 @@ __global__ __launch_bounds__(256) void k_ct_tile(DP p, ContactDev c, int first, 
     __shared__ int s_nseg;
     const float al = lazy ? st_alpha : 0.f;
     const int tid = threadIdx.x, lc = tid >> 2, part = tid & 3;
-    const ContactParams cp = {c.dt, c.mu, c.k, c.d, c.epsv};
+    const ContactParams cp_call = {c.dt, c.mu, c.k, c.d, c.epsv};
     for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         const int lo = tile * CT_TILE, cnt = min(CT_TILE, cn - lo);
         const uint32_t key = key_next;
@@ -1297,6 +1332,7 @@ __global__ __launch_bounds__(256) void k_ct_tile(DP p, ContactDev c, int first, 
             crv[t] = c.crv[t * N + j];
         }
         const float phi0_j = c.cphi0[j], mass = c.cmass[j];
+        const ContactParams cp = contact_params_of<MAT>(c, cp_call, N, j);
         tile_segments(key, cnt, s_seg, s_cseg, &s_nseg);
         __syncthreads();
         tstamp(0);
@@ -1539,6 +1575,7 @@ __global__ __launch_bounds__(CT_WG) void k_ct_node_dir(DP p, ContactDev c, int l
 // inertia part (cuda_mpm_kernels.cuh:1536-1589) in the rest
 // exact: 0 = backtracking (all candidate steps at once); 1 = (E, dE, d2E) at the step given by the
 // host; 2 = the same at st->alpha_probe, the device-resident search (skipped once the step is decided)
+template <bool MAT>
 __global__ __launch_bounds__(CT_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_ct_ls(DP p, ContactDev c, int n_con_wg, int exact,
                                                                                              float alpha_probe) {
     // (as in k_ct_tile: the first tile's keys are requested together with the solver state)
@@ -1566,7 +1603,7 @@ __global__ __launch_bounds__(CT_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) v
         __shared__ int s_nseg;
         const int tid = threadIdx.x, lc = tid >> 2;
         const int part = threadIdx.x & 3, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-        const ContactParams cp = {c.dt, c.mu, c.k, c.d, c.epsv};
+        const ContactParams cp_call = {c.dt, c.mu, c.k, c.d, c.epsv};
         double acc[6] = {0, 0, 0, 0, 0, 0}, e0 = 0;
         for (int tile = blockIdx.x; tile < n_tiles; tile += n_con_wg) {
             const int lo = tile * CT_TILE, cnt = min(CT_TILE, cn - lo);
@@ -1624,6 +1661,7 @@ __global__ __launch_bounds__(CT_WG) __attribute__((amdgpu_waves_per_eu(4, 4))) v
 #pragma unroll
             for (int t = 0; t < 3; ++t) v0[t] = c.cv0[t * N + j];
             const float phi0 = c.cphi0[j], mass = counted ? c.cmass[j] : 0.f;
+            const ContactParams cp = contact_params_of<MAT>(c, cp_call, N, j);
             float ovl[3], ddl[3];
             {
                 const float t[3] = {ov[0] - c.crv[j], ov[1] - c.crv[N + j], ov[2] - c.crv[2 * N + j]};

@@ -2596,6 +2596,23 @@ int mpm_set_sdf_colliders(mpm_handle_t e, size_t n, const mpm_sdf_collider_t* co
     return set_sdf_colliders(e, n, colliders);
 } MPM_CATCH_ALL
 
+int mpm_set_body_contact_materials(mpm_handle_t e, size_t n, const mpm_contact_material_t* materials) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(n == 0 || materials, "null material array");
+    if (int rc = validate_body_contact_materials(n, materials)) return rc;   // (before anything is enqueued or allocated)
+    READY(e);
+    return set_body_contact_materials(e, n, materials);
+} MPM_CATCH_ALL
+
+int mpm_get_body_contact_materials(mpm_handle_t e, mpm_contact_material_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(capacity == 0 || out, "null argument");
+    const std::vector<mpm_contact_material_t>& m = e->cb.materials;
+    std::copy(m.begin(), m.begin() + (long)std::min(capacity, m.size()), out);
+    if (n_out) *n_out = m.size();
+    return 0;
+} MPM_CATCH_ALL
+
 int mpm_sdf_collider_signed_distance(mpm_handle_t e, const mpm_sdf_collider_t* c, size_t n, const float* x_W, float* phi_out,
                                      float* grad_W_out) try {
     READY(e);
@@ -2753,6 +2770,11 @@ int mpm_world_coupled_substeps(mpm_handle_t* handles, int n_local, int n, const 
     REQUIRE((n_colliders == 0 || colliders) && n_colliders <= 1024, "bad collider array");
     if (int rc = validate_colliders(n_colliders, colliders)) return rc;   // (before any substep is enqueued)
     std::vector<mpm_engine*> L(handles, handles + n_local);
+    for (mpm_engine* e : L) {
+        // (body ids are global: the ranks solve ONE problem, with one table; refused before anything is enqueued)
+        REQUIRE(e, "null handle");
+        REQUIRE(same_body_contact_materials(e, L[0]), "the ranks of a world hold different body contact materials");
+    }
     for (mpm_engine* e : L) {
         READY(e);
         REQUIRE(e->stream == L[0]->stream, "an in-process world runs on ONE stream (mpm_set_stream)");

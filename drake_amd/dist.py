@@ -331,6 +331,11 @@ class DomainChain(HaloChain):
             left -= k
         return out
 
+    def set_body_contact_materials(self, materials):
+        """mpm_set_body_contact_materials on this rank's engine.  Body ids are global: every rank of the partition is given
+        the same table ((n, 3): friction_mu, stiffness, damping per rigid body; empty clears it)"""
+        self.e.set_body_contact_materials(materials)
+
     def migrate(self):
         if self.world == 1:
             return
@@ -544,6 +549,13 @@ class LocalWorld:
                     c.mig_elapsed += k * dt
                 left -= k
         return out
+
+    def set_body_contact_materials(self, materials):
+        """the same table of per-body contact materials on every rank's engine (mpm_world_coupled_substeps refuses ranks
+        whose tables differ)"""
+        with torch.cuda.stream(self.stream):
+            for c in self.chains:
+                c.set_body_contact_materials(materials)
 
     def sync(self):
         for c in self.chains:

@@ -106,6 +106,21 @@ int main(int argc, char** argv) {
         CHECK(max_contacts > 0);
         CHECK(fz < 0);                        // the cloth pushed the floor down
         z_of_mode[device_pairs][0] = zmin; z_of_mode[device_pairs][1] = zmax;
+        // the config's per-body contact materials reach the engine with the next plant step, stay while the vector is
+        // unchanged, and leave with the step after it is emptied
+        {
+            GpuMpmSolver<T> solver;
+            CHECK(solver.GetBodyContactMaterials(state).empty());
+            driver.config().body_contact_materials = {{0.5f, -1.f, -1.f}};
+            for (int frame = 100; frame < 102; ++frame) {
+                driver.CalcAbstractStates(T(2e-4), frame);
+                const auto m = solver.GetBodyContactMaterials(state);
+                CHECK(m.size() == 1 && m[0].friction_mu == 0.5f && m[0].stiffness == -1.f && m[0].damping == -1.f);
+            }
+            driver.config().body_contact_materials.clear();
+            driver.CalcAbstractStates(T(2e-4), 102);
+            CHECK(solver.GetBodyContactMaterials(state).empty());
+        }
         state.Destroy();
     }
     // the batched call is the seven calls (bit for bit in deterministic mode: tests/test_contact_noroundtrip_gpu.py)

@@ -4,6 +4,7 @@
 #pragma once
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 #include "../../include/gpu_mpm.hpp"
@@ -61,6 +62,7 @@ class MpmDriver {
   public:
     MpmDriver(GpuMpmState<float>* state, MpmConfigParams<float> config) : state_(state), config_(config) {}
     std::vector<RigidBody>& bodies() { return bodies_; }
+    MpmConfigParams<float>& config() { return config_; }
 
     // CalcMpmContactPairs (deformable_driver.h:120-194): one contact per (particle, body) with phi < 0
     void CalcMpmContactPairs(MpmParticleContactPairs<float>* result) const {
@@ -85,6 +87,12 @@ class MpmDriver {
             for (const auto& b : bodies_) origins.push_back(b.origin);
             if (origins.empty()) origins.push_back({0, 0, 0});
             drake::multibody::gmpm::InitalizeExternalContactForces(state_, origins);
+        }
+        // the per-body contact materials of the config, once per plant step and only when they changed (the call uploads
+        // the table and waits for the copy; an unchanged table costs a comparison on the host)
+        if (!same_materials(config_.body_contact_materials, materials_last_)) {
+            solver_.SetBodyContactMaterials(state_, config_.body_contact_materials);
+            materials_last_ = config_.body_contact_materials;
         }
         if (coupled_batch) {
             // the whole loop below as ONE call per run of equal substeps (mpm_run_coupled_substeps): the host waits once
@@ -145,6 +153,11 @@ class MpmDriver {
     GpuMpmSolver<float> solver_;
     std::vector<RigidBody> bodies_;
     size_t last_contacts_ = 0, n_pairs_last_ = 0;
+    std::vector<mpm_contact_material_t> materials_last_;   // the table the engine holds (empty: none was ever set)
+    // (bitwise: equal tables resolve every contact alike)
+    static bool same_materials(const std::vector<mpm_contact_material_t>& a, const std::vector<mpm_contact_material_t>& b) {
+        return a.size() == b.size() && (a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(a[0])) == 0);
+    }
 };
 
 }  // namespace drake_amd

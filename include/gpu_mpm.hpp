@@ -40,6 +40,9 @@ struct MpmConfigParams {
     int contact_query_frequency{1};
     int mpm_bc{-1};
     bool exact_line_search{false};
+    // extension: contact material per rigid body (mpm_set_body_contact_materials); entry b belongs to body b, a field < 0
+    // and every body beyond the vector take the three scalars above.  Empty: the scalars for every body.
+    std::vector<mpm_contact_material_t> body_contact_materials;
 };
 
 // cpu_mpm_model.h:32-40
@@ -265,6 +268,20 @@ class GpuMpmSolver {
     }
     void SetSdfColliders(GpuMpmState<T>* s, const std::vector<mpm_sdf_collider_t>& colliders) const {
         mpm_check(mpm_set_sdf_colliders(s->h_, colliders.size(), colliders.data()));
+    }
+    // Extension: contact material per rigid body (Drake keeps coulomb_friction, point_stiffness and
+    // hunt_crossley_dissipation in the ProximityProperties of a geometry).  materials[b] belongs to body b; a field < 0
+    // and every body >= materials.size() take what UpdateContact / RunCoupledSubsteps pass.  An empty vector clears the
+    // table.  Once per plant step at most; every solve enqueued afterwards uses it.  See mpm_set_body_contact_materials.
+    void SetBodyContactMaterials(GpuMpmState<T>* s, const std::vector<mpm_contact_material_t>& materials) const {
+        mpm_check(mpm_set_body_contact_materials(s->h_, materials.size(), materials.data()));
+    }
+    std::vector<mpm_contact_material_t> GetBodyContactMaterials(const GpuMpmState<T>& s) const {
+        size_t n = 0;
+        mpm_check(mpm_get_body_contact_materials(s.h_, nullptr, 0, &n));
+        std::vector<mpm_contact_material_t> out(n);
+        mpm_check(mpm_get_body_contact_materials(s.h_, out.data(), n, &n));
+        return out;
     }
     void SdfColliderSignedDistance(const GpuMpmState<T>& s, const mpm_sdf_collider_t& c, const std::vector<T>& p_WQ,
                                    std::vector<T>* phi, std::vector<T>* grad_W) const {

@@ -437,6 +437,29 @@ typedef struct mpm_sdf_collider {
  * new set.  An unknown shape id is refused here; a body out of range at the generating call, before anything is
  * enqueued, as for mpm_collider_t. */
 MPM_API int mpm_set_sdf_colliders(mpm_handle_t h, size_t n, const mpm_sdf_collider_t *colliders);
+/* Contact material of a rigid body: the three parameters of the contact model that the solving calls take as scalars
+ * (friction_mu, stiffness, damping of mpm_update_contact and mpm_coupled_params_t), per body.  materials[b] belongs to
+ * rigid body b: non_mpm_id of an uploaded pair, `body` of mpm_collider_t and mpm_sdf_collider_t.  Field by field, a
+ * value < 0 means "what the solving call passes"; bodies b >= n inherit all three.  Every contact's parameters are a
+ * SELECT between its body's entry and the call's scalars, never arithmetic: bit for bit one or the other.  Values >= 0
+ * are all legal (stiffness = 0: the body exerts nothing; damping = 0; friction_mu = 0).  The engine does not combine
+ * these with properties of the cloth: where both sides have some (Drake's CalcContactFrictionFromSurfaceProperties,
+ * 2 mu_A mu_B / (mu_A + mu_B)), the caller combines them and passes the result.
+ * mpm_set_body_contact_materials: the engine's table until the next call (n = 0 clears it: every contact takes the
+ * call's scalars again, through the kernel instances and with the bits of an engine of this library that never had a
+ * table).  Independent of
+ * mpm_reallocate_external_bodies.  MPM_ERR_INVALID, with the table unchanged and nothing enqueued or allocated, for a
+ * field that is not finite, n > 65536, or materials == NULL with n > 0.  Stream-ordered like mpm_set_sdf_colliders
+ * (and a synchronisation point: the call waits for its upload on the engine's stream): solves enqueued after the call --
+ * mpm_update_contact, mpm_run_coupled_substeps, mpm_world_coupled_substeps, mpm_profile_contact_iteration -- read the new
+ * table, also a solve that reuses the previous solve's set-up.  The
+ * caller's array may be freed on return.  Body ids are global in a partitioned world: mpm_world_coupled_substeps refuses
+ * (MPM_ERR_INVALID, nothing enqueued) local handles whose tables differ.
+ * mpm_get_body_contact_materials: the table as given; min(n, capacity) entries into out (NULL with capacity 0), n into
+ * *n_out. */
+typedef struct { float friction_mu, stiffness, damping; } mpm_contact_material_t;
+MPM_API int mpm_set_body_contact_materials(mpm_handle_t h, size_t n, const mpm_contact_material_t *materials);
+MPM_API int mpm_get_body_contact_materials(mpm_handle_t h, mpm_contact_material_t *out, size_t capacity, size_t *n_out);
 /* mpm_collider_signed_distance for one mesh collider: phi and the unit world gradient at n world points, by the pair
  * generator's own function.  A synchronisation point. */
 MPM_API int mpm_sdf_collider_signed_distance(mpm_handle_t h, const mpm_sdf_collider_t *c, size_t n, const float *x_W,

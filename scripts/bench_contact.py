@@ -56,6 +56,9 @@ def main():
                          "(rotated, cutting the cloth; no floor).  Mesh colliders (mpm_set_sdf_colliders): mesh = the 16 "
                          "boxes of boxes16 as 12-triangle meshes, mesh1 = one of them (on the cloth) alone, mesh_floor = a slab mesh "
                          "whose top face is the floor plane")
+    ap.add_argument("--uniform-table", action="store_true",
+                    help="mpm_set_body_contact_materials with one entry equal to the call's scalars: the same solve through "
+                         "the per-contact parameter planes")
     args = ap.parse_args()
     if args.survey_config3:
         args.floor, args.stiffness, args.damping, args.mu, args.dt = 0.25, 1e6, 1e-5, 1.0, 2e-4
@@ -87,6 +90,8 @@ def main():
         vel[:, 2] -= 0.5
     scenes.populate(g, sheets)
     g.reallocate_external_bodies(1)
+    if args.uniform_table:
+        g.set_body_contact_materials([(args.mu, stiffness, damping)])
     build_ms = 0.0
     if mesh:
         shapes = {}
@@ -143,6 +148,7 @@ def main():
     k = args.steps
     out = dict(config=args.config, particles=g.n_particles, steps=k, mu=args.mu, dt=dt, stiffness=stiffness,
                damping=damping, floor=args.floor, pairs="device" if args.device_pairs else "host", colliders=args.colliders,
+               uniform_table=bool(args.uniform_table),
                contacts_mean=float(np.mean(ncontacts)), contacts_max=int(np.max(ncontacts)),
                newton_iterations_mean=float(np.mean(iters)), newton_iterations_max=int(np.max(iters)),
                ms_per_substep={a: 1e3 * b / k for a, b in T.items()},

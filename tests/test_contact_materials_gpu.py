@@ -1,0 +1,476 @@
+"""Per-body contact materials on the device (mpm_set_body_contact_materials): the contact solve with the table of
+tests/contact_materials.py against the float64 restatement of that module, per contact, node and body, and the table's
+contract -- a uniform table is the scalar call to the bit, inheritance field by field, locality of the direction, a table
+changed between two solves of an unchanged pair list, the coupled substeps in one call and in seven, a partitioned world,
+what it is for (a frictionless body beside a rough one in ONE solve), and the refused inputs.  Engines that are compared
+with each other are deterministic."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import contact_layouts as cl
+from tests import contact_materials as cm
+from tests import transfer_layouts as tl
+from tests import test_contact_layouts_gpu as base
+from tests import test_contact_noroundtrip_gpu as nr
+from tests import test_team_gpu as team
+
+pytestmark = pytest.mark.gpu
+
+MPM_ERR_INVALID = -1
+WRONG = (3e5, 0.02, None, 0.9)     # (k, d, -, mu) scalars that no test's table lets through
+
+
+def _solve(g, call, iters, exact=False):
+    """base._solve with the call's scalars given: call = (k, d, dt, mu)"""
+    from drake_amd import ARR as A
+    k, d, dt, mu = call
+    rg = g.update_contact(dt, mu, k, d, exact_line_search=exact, max_newton_iterations=iters)
+    out = dict(rg=rg, cs=g.contact_stats(), D=g.download(A.GRID_DIR), gv1=g.download(A.GRID_MOMENTUM),
+               vel0=g.download(A.CONTACT_VEL0), vel=g.download(A.CONTACT_VEL), log=g.contact_log(), stats=g.stats())
+    out["tau"], out["f"] = g.external_body_force_to_host()
+    return out
+
+
+def _run(lay, tab, call=None, iters=1, exact=False, env=None, deterministic=True):
+    g, pre = base._engine(lay, deterministic=deterministic, env=env)
+    if tab is not None:
+        g.set_body_contact_materials(tab)
+    out = _solve(g, cl.params32(lay["params"]) if call is None else call, iters, exact)
+    g.destroy()
+    return pre, out
+
+
+def _bit_equal(a, b, what):
+    for k in ("D", "gv1", "vel", "vel0", "log", "tau", "f"):
+        x, y = np.ascontiguousarray(a[k]), np.ascontiguousarray(b[k])
+        assert x.shape == y.shape and np.array_equal(x.view(np.uint32), y.view(np.uint32)), (what, k)
+    for k, x in a["cs"].items():
+        y = b["cs"][k]
+        assert x == y or (x != x and y != y), (what, k, x, y)     # (a NaN residual -- no DoF -- equals itself)
+
+
+def _iteration_checks(lay, P, pre, out, chk, relax=cl.RELAX):
+    """test_contact_layouts_gpu._iteration_checks, judged by the restatement with per-contact parameters P"""
+    gm, gv, gvs = pre["gm"], pre["gv"], pre["gvs"]
+    b, wt, keys, T = cm.prepare(lay, P, gm, gv, gvs, pre["vp"], pre["mass_c"])
+    cs = out["cs"]
+    nc = len(lay["cp"]["particle"])
+    assert out["stats"]["error_flags"] == 0, out["stats"]
+    assert cs["contacts"] == nc and cs["iterations"] == 1
+    vel0, e0 = cm.gather(wt, keys, gv, gm)
+    chk("vel0", out["vel0"] - vel0, e0)
+    dr = cm.direction(lay, P, wt, keys, pre["mass_c"], T, gm, gv, gvs, relax=relax)
+    nodes = dr["nodes"]
+    assert cs["nodes"] == len(nodes), (cs["nodes"], len(nodes))
+    D = out["D"].astype(np.float64)
+    ok = dr["dof"] & ~dr["amb"]
+    assert dr["amb"].sum() <= 0.05 * len(nodes)
+    chk("Dir", D[nodes][ok] - dr["D"][ok], dr["eD"][ok])
+    off = ~dr["dof"] & ~dr["amb"]
+    assert not D[nodes][off].any(), f"{chk.tag}: a direction where the restatement has no DoF"
+    rest = np.ones(len(D), bool)
+    rest[nodes] = False
+    assert not D[rest].any()
+    lo, hi = int((dr["dof"] & ~dr["amb"]).sum()), int(dr["dof"].sum() + dr["amb"].sum())
+    assert lo <= cs["dofs"] <= hi, (cs["dofs"], lo, hi)
+    if not dr["amb"].any():
+        assert cs["dofs"] == lo
+        d = dr["D"] / relax
+        chk("|Dir|^2", [cs["norm_dir_sq"] - dr["nd"]], [2 * (np.abs(d) * dr["eD"] / relax).sum() + cl.U32 * dr["nd"]])
+    al = float(cs["alpha"])
+    cands = [a for a in base.CANDIDATES if a >= al]
+    ls = cm.line_search(lay, P, wt, keys, pre["mass_c"], T, gm, gv, gvs, D, nodes, [0.0] + cands)
+    chk("E0", [cs["E0"] - ls[0]["E"]], [ls[0]["eE"]])
+    chk("E(alpha)", [cs["energy"] - ls[-1]["E"]], [ls[-1]["eE"]])
+    base._alpha_consistent(ls, al, chk, "alpha")
+    v = gv.astype(np.float64).copy()
+    live = np.zeros(len(v), bool)
+    live[nodes] = gm[nodes] > 0
+    want = v.copy()
+    want[live] = v[live] - al * D[live]
+    chk("grid v after the step", out["gv1"][live] - want[live], 2 * cl.U32 * (np.abs(want[live]) + al * np.abs(D[live])))
+    assert np.array_equal(out["gv1"][~live], gv[~live])
+    q = tl.fixed_quanta(pre["mass_all"])[1]
+    imp = cm.impulses(lay, wt, keys, gm, gv, out["gv1"], pre["mass_c"], quantum=q)
+    chk("contact vel", out["vel"] - imp["v"], imp["ev"])
+    chk("F_f", out["f"] - imp["f"], imp["ef"])
+    chk("F_tau", out["tau"] - imp["tau"], imp["et"])
+    return dict(wt=wt, keys=keys, T=T, dr=dr)
+
+
+# ---- 1, 2: against float64 -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("relax", [None, 40.0])
+def test_one_newton_iteration_with_the_table_per_node(relax):
+    """relax 40: the Newton step overshoots and the backtracking search goes into its deep pass"""
+    from tests import helpers
+    helpers.tag_default_engine(True)
+    lay = cl.layout(cm.LAYOUT)
+    tab = cm.table(lay["n_bodies"])
+    pre, out = _run(lay, tab, env={"MPM_CT_RELAX": "40"} if relax else None, deterministic=False)
+    if relax:
+        assert out["cs"]["alpha"] < 1.0 / 8.0, out["cs"]
+    chk = base._Checks(f"contact materials: bodies, relax {relax or cl.RELAX}")
+    _iteration_checks(lay, cm.params(lay, tab), pre, out, chk, relax=relax or cl.RELAX)
+    chk.done()
+
+
+def test_the_table_is_seen_by_the_restatement_of_the_scalars():
+    """the same solve judged by the SCALAR restatement fails by far: the checks above can tell the table from none"""
+    lay = cl.layout(cm.LAYOUT)
+    tab = cm.table(lay["n_bodies"])
+    pre, out = _run(lay, tab)
+    P = cl.params32(lay["params"])
+    b, wt, keys, T = cl.prepare(lay, P, pre["gm"], pre["gv"], pre["gvs"], pre["vp"], pre["mass_c"])
+    dr = cl.direction(lay, P, wt, keys, pre["mass_c"], T, pre["gm"], pre["gv"], pre["gvs"])
+    ok = dr["dof"] & ~dr["amb"]
+    assert cl.margin(np.abs(out["D"].astype(np.float64)[dr["nodes"]][ok] - dr["D"][ok]), dr["eD"][ok]) > 100
+
+
+def test_exact_line_search_with_the_table_ends_at_the_restated_root():
+    lay = cl.layout(cm.LAYOUT)
+    tab = cm.table(lay["n_bodies"])
+    pre, out = _run(lay, tab, exact=True, deterministic=False)
+    P = cm.params(lay, tab)
+    gm, gv, gvs = pre["gm"], pre["gv"], pre["gvs"]
+    b, wt, keys, T = cm.prepare(lay, P, gm, gv, gvs, pre["vp"], pre["mass_c"])
+    dr = cm.direction(lay, P, wt, keys, pre["mass_c"], T, gm, gv, gvs)
+    al = float(out["cs"]["alpha"])
+    a, one = cm.line_search(lay, P, wt, keys, pre["mass_c"], T, gm, gv, gvs, out["D"].astype(np.float64), dr["nodes"],
+                            [al, 1.0], derivs=True, vp=pre["vp"])
+    f_tol, x_tol = 1e-8, 1e-8 * cl.RELAX
+    at_root = abs(a["dE"]) <= a["edE"] + f_tol + 2 * x_tol * abs(a["d2E"])
+    at_end = al == 1.0 and one["dE"] < one["edE"]
+    r = abs(a["dE"]) / (a["edE"] + f_tol + 2 * x_tol * abs(a["d2E"]))
+    base._record("contact materials: bodies exact search dE(alpha)", r if not at_end else 0.0)
+    assert at_root or at_end, (al, a, one)
+
+
+# ---- 3, 4, 5: the table's contract, to the bit -------------------------------------------------------------------------
+def test_a_uniform_table_is_the_scalar_call_to_the_bit():
+    lay = cl.layout(cm.LAYOUT)
+    call = cl.params32(lay["params"])
+    wrong = (WRONG[0], WRONG[1], call[2], WRONG[3])
+    _, a = _run(lay, None, call, iters=5)
+    _, b = _run(lay, cm.uniform_table(call), wrong, iters=5)
+    _, c = _run(lay, np.full((lay["n_bodies"], 3), -1.0, np.float32), call, iters=5)
+    assert a["cs"]["iterations"] == 5 and np.abs(a["D"]).max() > 0
+    _bit_equal(a, b, "no table / uniform table behind wrong scalars")
+    _bit_equal(a, c, "no table / a table that inherits everything")
+    # (the scalars of B do matter where nothing overrides them)
+    _, w = _run(lay, None, wrong, iters=5)
+    assert not np.array_equal(a["D"], w["D"])
+
+
+def test_inheritance_by_length_and_by_field():
+    lay = cl.layout(cm.LAYOUT)
+    nb = lay["n_bodies"]
+    tab = cm.table(nb)
+    short, padded = tab[:10].copy(), tab.copy()
+    padded[10:] = -1.0
+    _, a = _run(lay, short, iters=3)
+    _, b = _run(lay, padded, iters=3)
+    _bit_equal(a, b, "a table of 10 / 40 entries padded with -1")
+    # entry 6 overrides mu only: the same bits as the entry written out in full
+    k, d, dt, mu = cl.params32(lay["params"])
+    full = tab.copy()
+    six = cm.entry_of_body(nb) == 6
+    assert six.any() and (tab[six, 1:] < 0).all()
+    full[six, 1], full[six, 2] = k, d
+    _, e = _run(lay, tab, iters=3)
+    _, f = _run(lay, full, iters=3)
+    _bit_equal(e, f, "mu only / the entry in full")
+    assert not np.array_equal(a["D"], e["D"])
+
+
+def test_the_direction_is_local_to_the_contacts_parameters():
+    """on the nodes whose contacts all resolve to one triple, the direction is the scalar solve's with that triple"""
+    lay = cl.layout(cm.LAYOUT)
+    tab = cm.table(lay["n_bodies"])
+    call = cl.params32(lay["params"])
+    P = cm.params(lay, tab)
+    _, wt, keys = cm.stencil(lay)
+    _, out = _run(lay, tab)
+    checked, moved, others = 0, 0, 0
+    for (k, d, mu), nodes in cm.uniform_nodes(P, keys):
+        if len(nodes) == 0:
+            continue
+        _, s = _run(lay, None, (cl.f32v(k), cl.f32v(d), call[2], cl.f32v(mu)))
+        assert np.array_equal(out["D"][nodes].view(np.uint32), s["D"][nodes].view(np.uint32)), (k, d, mu)
+        checked += 1
+        if (k, d, mu) != (call[0], call[1], call[3]):
+            others += 1
+            moved += bool(np.abs(s["D"][nodes]).max() > 0)
+    # (node sets of at least three triples, of them at least two that are not the call's own, with a direction on them)
+    assert checked >= 3 and others >= 2 and moved >= 1, (checked, others, moved)
+
+
+# ---- 6: a table changed between two solves of an unchanged pair list ----------------------------------------------------
+def _repeat_solves(tables):
+    """the pressed stack on the floor, len(tables) times: transfers from the SAME particle state (no GridToParticle in
+    between: the pair list repeats, the previous solve's effect on the grid is gone), impulses reset, tables[i] set in front
+    of solve i (None: left as it is).  -> the last solve's results"""
+    from drake_amd import ARR as A, Collider
+    floor = [Collider(0, body=0, p_WB=(0.5, 0.5, nr.Z_FLOOR))]
+    g = nr._engine(None, nr._pressed_stack())
+    outs = []
+    for tab in tables:
+        g.rebuild_mapping(False)
+        g.calc_fem_state_and_force(nr.DT)
+        g.particle_to_grid(nr.DT)
+        g.update_grid(-1)
+        g.reallocate_external_bodies(1)
+        g.generate_contact_pairs(floor, want_count=False)
+        if tab is not None:
+            g.set_body_contact_materials(tab)
+        r = g.update_contact(nr.DT, nr.MU, nr.K, nr.D, max_newton_iterations=4)
+        tau, f = g.external_body_force_to_host()
+        outs.append(dict(r=r, D=g.download(A.GRID_DIR), gv1=g.download(A.GRID_MOMENTUM), vel=g.download(A.CONTACT_VEL),
+                         log=g.contact_log().copy(), tau=tau, f=f))
+    assert g.stats()["error_flags"] == 0
+    g.destroy()
+    return outs
+
+
+def test_a_reused_setup_picks_up_a_new_table():
+    t1 = np.array([(0.2, 5e5, 1e-4)], np.float32)
+    t2 = np.array([(0.7, -1.0, 1e-3)], np.float32)
+    x = _repeat_solves([t1, None, None, t2])
+    y = _repeat_solves([t2, None, None, None])
+    assert not x[0]["r"]["setup_reused"]
+    assert x[2]["r"]["setup_reused"] and x[3]["r"]["setup_reused"] and y[3]["r"]["setup_reused"], [o["r"] for o in x + y]
+    assert x[3]["r"]["contacts"] > 500 and x[3]["r"]["contacts"] == y[3]["r"]["contacts"]
+    assert not np.array_equal(x[2]["D"], y[2]["D"])          # (the tables do differ in what they give)
+    for k in ("D", "gv1", "vel", "log", "tau", "f"):
+        assert np.array_equal(x[3][k].view(np.uint32), y[3][k].view(np.uint32)), k
+    assert x[3]["r"]["iterations"] == y[3]["r"]["iterations"]
+    # ... and the twin's reused solve is its own full one (same table, same state) to the bit
+    for k in ("D", "gv1", "vel", "tau", "f"):
+        assert np.array_equal(y[3][k].view(np.uint32), y[0][k].view(np.uint32)), k
+
+
+# ---- 7: coupled substeps ------------------------------------------------------------------------------------------------
+def _two_boxes():
+    """the floor of the pressed stack as two boxes side by side (bodies 0 and 1), their top faces at Z_FLOOR"""
+    from drake_amd import Collider
+    return [Collider(2, body=0, p_WB=(0.35, 0.5, nr.Z_FLOOR - 0.05), dims=(0.15, 0.4, 0.05)),
+            Collider(2, body=1, p_WB=(0.65, 0.5, nr.Z_FLOOR - 0.05), dims=(0.15, 0.4, 0.05))]
+
+
+BOX_TABLE = np.array([(0.1, 1e6, 1e-5), (1.0, 5e5, -1.0)], np.float32)
+
+
+def test_coupled_substeps_in_one_call_equal_the_seven_calls_with_a_table():
+    sheets = nr._pressed_stack()
+    cols = _two_boxes()
+    big, small = {"MPM_CT_INITIAL_CAPACITY": "100000"}, {"MPM_CT_INITIAL_CAPACITY": "100"}
+    a, b, c = (nr._engine(env, sheets, bodies=2) for env in (big, big, small))
+    for g in (a, b, c):
+        g.set_body_contact_materials(BOX_TABLE)
+    ra = nr._coupled_with(a, cols, 3, False)
+    rb = b.run_coupled_substeps(3, nr.DT, cols, nr.MU, nr.K, nr.D)
+    rc = c.run_coupled_substeps(3, nr.DT, cols, nr.MU, nr.K, nr.D)
+    for g in (a, b, c):
+        g.gpu_sync()
+        assert g.stats()["error_flags"] == 0
+    assert ra[0]["contacts"] > 500
+    assert b.contact_counters()["repeated_overflow"] == 0 and c.contact_counters()["repeated_overflow"] >= 1
+    sa, sb, sc = nr._state(a), nr._state(b), nr._state(c)
+    nr._same_rows(ra, rb, "iterations", "contacts", "residual")
+    nr._same_rows(ra, rc, "iterations", "contacts", "residual")
+    nr._same(sa, sb)
+    nr._same(sa, sc)
+    assert np.abs(sa["f"][0]).max() > 0 and np.abs(sa["f"][1]).max() > 0
+    # the table is in it: the scalar call gives something else
+    s = nr._engine(big, sheets, bodies=2)
+    s.run_coupled_substeps(3, nr.DT, cols, nr.MU, nr.K, nr.D)
+    s.gpu_sync()
+    assert not np.array_equal(nr._state(s)["vel"], sa["vel"])
+    for g in (a, b, c, s):
+        g.destroy()
+
+
+# ---- 8: what it is for --------------------------------------------------------------------------------------------------
+SLIDE_DT, SLIDE_K, SLIDE_D, SLIDE_N, SLIDE_V = 1e-3, 1e5, 1e-3, 4, 0.5
+
+
+def _sliding_patches(tab, mu):
+    """two patches, each lying on its own box (bodies 0 and 1), both moving along y.  -> mean (v_x, v_y) per patch, the
+    last substep's DoFs and iterations"""
+    from drake_amd import ARR as A, Collider, GpuMpm, scenes
+    z = nr.Z_FLOOR
+    sheets = []
+    for cx, seed in ((0.3, 3), (0.7, 4)):
+        sheets += scenes.cloth_stack(1, 16, 6, z0=z - 0.0005, side=0.12, seed=seed, vel_amp=0.0, center=(cx, 0.45))
+    for pos, vel, idx in sheets:
+        vel[:, 1] += SLIDE_V
+    cols = [Collider(2, body=b, p_WB=(cx, 0.5, z - 0.05), dims=(0.12, 0.3, 0.05)) for b, cx in enumerate((0.3, 0.7))]
+    g = GpuMpm(6)
+    g.set_deterministic(True)
+    scenes.populate(g, sheets)
+    g.reallocate_external_bodies(2)
+    if tab is not None:
+        g.set_body_contact_materials(tab)
+    res = g.run_coupled_substeps(SLIDE_N, SLIDE_DT, cols, mu, SLIDE_K, SLIDE_D)
+    g.gpu_sync()
+    assert g.stats()["error_flags"] == 0
+    pos, vel = g.download(A.POSITIONS), g.download(A.VELOCITIES).astype(np.float64)
+    cs = g.contact_stats()
+    g.destroy()
+    left = pos[:, 0] < 0.5
+    assert left.sum() > 100 and (~left).sum() > 100 and all(r["contacts"] > 100 for r in res)
+    return dict(v=[vel[left, :2].mean(0), vel[~left, :2].mean(0)], dofs=cs["dofs"], iters=res[-1]["iterations"])
+
+
+def test_a_frictionless_body_beside_a_rough_one_in_one_solve():
+    from tests import helpers
+    tab = np.array([(0.0, -1.0, -1.0), (1.0, -1.0, -1.0)], np.float32)
+    mixed = _sliding_patches(tab, 0.5)
+    smooth, rough = _sliding_patches(None, 0.0), _sliding_patches(None, 1.0)
+    for patch, ref, what in ((0, smooth, "mu = 0"), (1, rough, "mu = 1")):
+        tol = helpers.solve_tolerance(ref["dofs"])
+        err = float(np.abs(mixed["v"][patch] - ref["v"][patch]).max())
+        print(f"patch {patch} against the scalar run with {what}: |dv| = {err:.3e} m/s, allowed {tol:.3e}")
+        helpers.MARGINS.append((err / tol, f"contact materials: patch on body {patch} vs the scalar run with {what}", tol,
+                                err, err / SLIDE_V))
+        assert err <= tol, (what, err, tol)
+    lost = [SLIDE_V - mixed["v"][p][1] for p in (0, 1)]
+    print("tangential velocity lost: frictionless", lost[0], "mu = 1", lost[1])
+    assert lost[1] > lost[0] + 0.02 and lost[1] > 0.05, lost
+    # (the scalar runs differ by as much: the table run is not one of them)
+    assert abs(smooth["v"][1][1] - rough["v"][1][1]) > 0.02
+
+
+# ---- 9: partitioned world -----------------------------------------------------------------------------------------------
+WORLD_TABLE = np.array([(-1.0, -1.0, -1.0), (0.1, 2e5, -1.0), (1.0, -1.0, 1e-2)], np.float32)
+
+
+def _single_engine_run(sheets, tab):
+    """test_team_gpu._single_engine_run with a table"""
+    from drake_amd import ARR
+    g = team._engine(sheets)
+    g.set_body_contact_materials(tab)
+    res, logs, done = [], [], 0
+    for k in team.CHUNKS:
+        res += g.run_coupled_substeps(k, team.DT, team._colliders(done * team.DT), team.MU, team.K, team.D)
+        done += k
+        logs.append(g.contact_log().copy())
+    g.gpu_sync()
+    assert g.stats()["error_flags"] == 0
+    tau, f = g.external_body_force_to_host()
+    out = dict(res=res, logs=logs, pos=g.download(ARR.POSITIONS), vel=g.download(ARR.VELOCITIES), tau=tau, f=f,
+               dofs=g.contact_stats()["dofs"], n=g.n_particles)
+    g.destroy()
+    return out
+
+
+def test_in_process_world_with_a_table_matches_the_single_engine():
+    import torch
+    from drake_amd import ARR, MpmError
+    from drake_amd.dist import LocalWorld
+    world, cuts = 2, [0, 8, 16]
+    sheets = team._scene()
+    ref = _single_engine_run(sheets, WORLD_TABLE)
+    engines = [team._engine(sheets) for _ in range(world)]
+    w = LocalWorld(engines, cuts, zone_blocks=2, ghost_cells=0, ghost_margin_cells=0, capacity_blocks=512, migrate_every=0,
+                   migrate_capacity=1 << 14, device=torch.device("cuda", 0))
+    w.enable_team(512)
+    # ranks that hold different tables are refused, and nothing runs
+    engines[0].set_body_contact_materials(WORLD_TABLE)
+    w.sync()
+    before = [g.download(ARR.POSITIONS).copy() for g in engines]
+    steps = [g.stats()["substeps"] for g in engines]
+    from drake_amd import GpuMpm
+    with pytest.raises(MpmError) as err, torch.cuda.stream(w.stream):
+        GpuMpm.world_coupled_substeps(engines, 1, team.DT, team._colliders(0.0), team.MU, team.K, team.D)
+    assert err.value.code == MPM_ERR_INVALID
+    w.sync()
+    for g, p, s in zip(engines, before, steps):
+        assert np.array_equal(g.download(ARR.POSITIONS), p, equal_nan=True) and g.stats()["substeps"] == s
+        assert g.contact_counters()["solves"] == 0
+    w.set_body_contact_materials(WORLD_TABLE)
+    for g in engines:
+        assert np.array_equal(g.body_contact_materials(), WORLD_TABLE)
+    res = [[] for _ in range(world)]
+    logs = [[] for _ in range(world)]
+    done = 0
+    for k in team.CHUNKS:
+        out = w.coupled_substeps(k, team.DT, team._colliders(done * team.DT), team.MU, team.K, team.D)
+        done += k
+        for r in range(world):
+            res[r] += out[r]
+            logs[r].append(engines[r].contact_log().copy())
+    w.sync()
+    n = ref["n"]
+    owned = np.zeros(n, np.int32)
+    pos, vel = np.full((n, 3), np.nan, np.float32), np.full((n, 3), np.nan, np.float32)
+    f_sum, tau_sum = np.zeros_like(ref["f"]), np.zeros_like(ref["tau"])
+    for g in engines:
+        st = g.stats()
+        assert st["error_flags"] == 0, st
+        own = g.dist_roles() == 1
+        owned += own
+        pos[own], vel[own] = g.download(ARR.POSITIONS)[own], g.download(ARR.VELOCITIES)[own]
+        tau, f = g.external_body_force_to_host()
+        f_sum += f
+        tau_sum += tau
+    assert w.migrations >= 1
+    team._check_against_single_engine(ref, res, logs, owned, pos, vel, f_sum, tau_sum, "in-process world of 2 with a table")
+
+
+# ---- 10: error paths ----------------------------------------------------------------------------------------------------
+def test_refused_tables_leave_the_engine_as_it_was():
+    from drake_amd import MpmError
+    lay = cl.layout(cm.LAYOUT)
+    call = cl.params32(lay["params"])
+    _, ref = _run(lay, None, call, iters=2)
+    tab = cm.table(lay["n_bodies"])
+    _, ref_tab = _run(lay, tab, call, iters=2)
+
+    g, _ = base._engine(lay, deterministic=True)
+    assert g.body_contact_materials().shape == (0, 3)
+    bad = []
+    for v in (np.nan, np.inf, -np.inf):
+        for field in range(3):
+            t = tab.copy()
+            t[17, field] = v
+            bad.append(t)
+    for t in bad:
+        with pytest.raises(MpmError) as err:
+            g.set_body_contact_materials(t)
+        assert err.value.code == MPM_ERR_INVALID
+    with pytest.raises(MpmError) as err:
+        g.set_body_contact_materials(np.zeros((65537, 3), np.float32))
+    assert err.value.code == MPM_ERR_INVALID
+    assert g.lib.mpm_set_body_contact_materials(g.h, 3, None) == MPM_ERR_INVALID
+    assert g.body_contact_materials().shape == (0, 3)
+    _bit_equal(_solve(g, call, 2), ref, "after refused tables: as if nothing happened")
+    g.destroy()
+
+    # 65536 entries are legal; a refused call leaves the table that was set; n = 0 restores the scalar call to the bit
+    g, _ = base._engine(lay, deterministic=True)
+    big = np.full((65536, 3), -1.0, np.float32)
+    big[:lay["n_bodies"]] = tab
+    g.set_body_contact_materials(big)
+    with pytest.raises(MpmError):
+        g.set_body_contact_materials(bad[0])
+    assert np.array_equal(g.body_contact_materials(), big)
+    g.set_body_contact_materials(tab)
+    # the getter: the table as given, n reported whatever the buffer holds
+    got = g.body_contact_materials()
+    assert got.dtype == np.float32 and np.array_equal(got.view(np.uint32), tab.view(np.uint32))
+    short, n = np.full((5, 3), 7.0, np.float32), C.c_size_t()
+    assert g.lib.mpm_get_body_contact_materials(g.h, short.ctypes.data_as(C.c_void_p), 4, C.byref(n)) == 0
+    assert n.value == len(tab) and np.array_equal(short[:4], tab[:4]) and (short[4] == 7.0).all()
+    assert g.lib.mpm_get_body_contact_materials(g.h, None, 0, C.byref(n)) == 0 and n.value == len(tab)
+    assert g.lib.mpm_get_body_contact_materials(g.h, None, 3, C.byref(n)) == MPM_ERR_INVALID
+    _bit_equal(_solve(g, call, 2), ref_tab, "a table set after refused ones")
+    g.destroy()
+
+    g, _ = base._engine(lay, deterministic=True)
+    g.set_body_contact_materials(tab)
+    g.set_body_contact_materials(np.zeros((0, 3), np.float32))
+    assert g.body_contact_materials().shape == (0, 3)
+    _bit_equal(_solve(g, call, 2), ref, "n = 0 restores the scalar behaviour")
+    g.destroy()
