@@ -164,6 +164,27 @@ def force_field_acceleration(fields, x, v, director=None):
     return out
 
 
+def bending_matrix(pos, indices):
+    """mpm_bending_matrix: Q of the quadratic hinge energy (E = 1/2 k x^T Q x) of one cloth with the float rest positions
+    `pos` (n, 3) and triangles `indices`, assembled on the host in double, as CSR (row_offsets (n + 1,) int64, cols int32
+    ascending with the diagonal, vals float64).  Needs no engine and no GPU."""
+    lib = load_library()
+    pos = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1)
+    off = np.zeros(len(pos) + 1, np.uint64)
+    nnz = C.c_size_t()
+
+    def call(cols, vals, cap):
+        rc = lib.mpm_bending_matrix(pos.ctypes.data, len(pos), idx.ctypes.data, idx.size // 3, off.ctypes.data,
+                                    cols.ctypes.data if cap else None, vals.ctypes.data if cap else None, cap, C.byref(nnz))
+        if rc:
+            raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    call(None, None, 0)
+    cols, vals = np.zeros(max(nnz.value, 1), np.int32), np.zeros(max(nnz.value, 1), np.float64)
+    call(cols, vals, int(nnz.value))
+    return off.astype(np.int64), cols[:nnz.value], vals[:nnz.value]
+
+
 def grid_collider_preset(mpm_bc: int, sdf_friction: float = 0.3):
     """The collider table that reproduces the reference's scene mpm_bc (cuda_mpm_kernels.cuh:673-774)."""
     lib = load_library()
@@ -296,7 +317,8 @@ SYMBOLS = [
     "mpm_add_qr_cloth_with_material", "mpm_get_cloth_info", "mpm_cloth_count", "mpm_set_grid_bodies",
     "mpm_get_grid_bodies", "mpm_set_force_fields", "mpm_get_force_fields", "mpm_force_field_acceleration",
     "mpm_debug_resort_tables", "mpm_debug_sort_pairs", "mpm_set_body_contact_materials",
-    "mpm_get_body_contact_materials",
+    "mpm_get_body_contact_materials", "mpm_set_bending", "mpm_get_bending", "mpm_bending_forces",
+    "mpm_bending_max_stable_dt", "mpm_bending_matrix",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -418,6 +440,11 @@ def load_library(build: bool = True):
         "mpm_set_force_fields": [vp, sz, vp],
         "mpm_get_force_fields": [vp, vp, sz, P(sz)],
         "mpm_force_field_acceleration": [vp, sz, sz, vp, vp, vp, vp],
+        "mpm_set_bending": [vp, sz, vp],
+        "mpm_get_bending": [vp, vp, sz, P(sz)],
+        "mpm_bending_forces": [vp, vp],
+        "mpm_bending_max_stable_dt": [vp, P(f)],
+        "mpm_bending_matrix": [vp, sz, vp, sz, vp, vp, vp, sz, P(sz)],
         "mpm_add_qr_cloth_with_material": [vp, vp, vp, sz, vp, sz, vp],
         "mpm_get_cloth_info": [vp, sz, P(sz), P(sz), P(sz), P(sz), vp],
         "mpm_cloth_count": [vp, P(sz)],
@@ -674,6 +701,32 @@ class GpuMpm:
         arr = (ForceField * max(int(n.value), 1))()
         self._ck(self.lib.mpm_get_force_fields(self.h, arr, int(n.value), C.byref(n)))
         return [arr[k] for k in range(int(n.value))]
+
+    def set_bending(self, stiffness):
+        """mpm_set_bending: the bending stiffness k (N m) of every cloth, in cloth order (quadratic hinge energy on the
+        flat rest shape); all zeros or an empty list switches it off.  A synchronisation point."""
+        k = np.ascontiguousarray(stiffness, np.float32).reshape(-1)
+        self._ck(self.lib.mpm_set_bending(self.h, k.size, _ptr(k) if k.size else None))
+
+    def get_bending(self):
+        """mpm_get_bending: the stiffness in force, one float32 per cloth (zeros while off)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_bending(self.h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), np.float32)
+        self._ck(self.lib.mpm_get_bending(self.h, _ptr(out) if out.size else None, out.size, C.byref(n)))
+        return out
+
+    def bending_forces(self):
+        """mpm_bending_forces: -k Q x on the current positions, (n_verts, 3) float32 in dump_cpu_state's numbering."""
+        out = np.zeros((self.n_verts, 3), np.float32)
+        self._ck(self.lib.mpm_bending_forces(self.h, _ptr(out)))
+        return out
+
+    def bending_max_stable_dt(self) -> float:
+        """mpm_bending_max_stable_dt: the dt above which the substep entry points refuse (inf while bending is off)."""
+        dt = C.c_float()
+        self._ck(self.lib.mpm_bending_max_stable_dt(self.h, C.byref(dt)))
+        return float(dt.value)
 
     def get_grid_bodies(self):
         """mpm_get_grid_bodies: the table in force, a list of GridBody."""

@@ -247,6 +247,9 @@ static void launch_fem_faces(mpm_engine* e, const DP& p, float dt) {
 static void launch_fem_vertices(mpm_engine* e, const DP& p) {
     TraceRange tr("mpm:CalcFemStateAndForce (vertex forces)");
     if (e->nv) hipLaunchKernelGGL(k_vforce, dim3((e->g_nv + 7u) & ~7u), dim3(256), 0, e->stream, p);
+    // (an engine with bending stiffness, mpm_set_bending: f += -k Q x on the forces k_vforce has just written)
+    if (e->bend.on())
+        hipLaunchKernelGGL(k_bend, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->bend.args);
 }
 static void launch_fem(mpm_engine* e, const DP& p, float dt) {
     e->last_dt = dt;
@@ -282,8 +285,9 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
     e->last_tile_kernel = 1;
 }
 // the vertex forces inside k_p2g, from the vertices' entries of DP::VF (single and partitioned domains alike since round
-// 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch
-static int fused_forces(const mpm_engine* e) { return e->max_valence <= 8 ? 1 : 0; }
+// 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch, and so does an engine with bending
+// stiffness, whose k_bend adds to the forces in DP::f
+static int fused_forces(const mpm_engine* e) { return e->max_valence <= 8 && !e->bend.on() ? 1 : 0; }
 // FEM faces, then P2G with the vertex forces of every work item computed inside it (no k_vforce launch): the
 // batched substeps use this; the phase-by-phase calls keep the two FEM kernels, whose forces a caller may read
 static void launch_fem_p2g(mpm_engine* e, const DP& p, float dt) {
@@ -793,7 +797,8 @@ static int pins_ready(mpm_engine* e) {
     ps.table_dirty = false;
     return 0;
 }
-// partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies and no force fields (out of scope)
+// partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields and no bending
+// stiffness (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
@@ -802,11 +807,22 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with grid bodies (mpm_set_grid_bodies)");
     if (!e->force_fields.empty())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with force fields (mpm_set_force_fields)");
+    if (e->bend.on())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with bending stiffness (mpm_set_bending)");
     return 0;
 }
 // An explicit linear drag beyond dt * gamma = 1 reverses the relative velocity: the substep entry points that take a dt
 // refuse it, once per call, before anything is enqueued.  (An engine without a table never gets past the first test.)
+// The same entry points refuse a dt above mpm_bending_max_stable_dt on an engine with bending stiffness: symplectic Euler
+// on the lumped system needs dt * omega <= 2, with Gershgorin's bound on omega^2 (a guard, not a guarantee).
 static int fields_stable(const mpm_engine* e, float dt) {
+    if (e->bend.on() && !(dt <= e->bend.max_dt))
+    {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "bending: dt = %g is above the limit mpm_bending_max_stable_dt = %g: the explicit bending "
+                      "force is unstable -- reduce dt or the stiffness", (double)dt, (double)e->bend.max_dt);
+        return fail(MPM_ERR_INVALID, msg);
+    }
     if (e->force_fields.empty()) return 0;
     if (!((double)dt * e->force_fields_gamma <= 1.0))
         return fail(MPM_ERR_INVALID, "force fields: dt * (sum of gamma over the linear drag fields) = " +
@@ -814,8 +830,8 @@ static int fields_stable(const mpm_engine* e, float dt) {
     return 0;
 }
 // The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
-// takes it as 0, i.e. every batch starts with its re-sort check launches.
-static float quiet_hint(const mpm_engine* e, float seconds) { return e->force_fields.empty() ? seconds : 0.f; }
+// takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness is set.
+static float quiet_hint(const mpm_engine* e, float seconds) { return e->force_fields.empty() && !e->bend.on() ? seconds : 0.f; }
 
 // ---- the solver calls -----------------------------------------------------
 static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, bool allow_gate, bool lean = false);
@@ -1796,13 +1812,16 @@ int mpm_profile_substeps(mpm_handle_t e, int n, float dt, int bc, float* phase_m
         HIP_TRY(hipEventRecord(q[1], e->stream));
         launch_fem_faces(e, e->dp, dt);
         HIP_TRY(hipEventRecord(q[2], e->stream));
-        // (as in mpm_run_substeps: the vertex forces are part of k_p2g; this phase is empty)
+        // (as in mpm_run_substeps: the vertex forces are part of k_p2g; this phase is empty -- but for an engine with
+        // bending stiffness, whose k_vforce and k_bend are timed here)
+        const bool vforce_phase = e->bend.on();   // (else k_vforce, where it runs at all, is part of the P2G phase as before)
+        if (vforce_phase) launch_fem_vertices(e, e->dp);
         HIP_TRY(hipEventRecord(q[3], e->stream));
         DP p = e->dp;
         p.lean_g2p = s + 1 < n && !p.dist.on;   // (as in mpm_run_substeps)
         {
             const int forces = fused_forces(e);
-            if (!forces) launch_fem_vertices(e, p);
+            if (!forces && !vforce_phase) launch_fem_vertices(e, p);
             launch_p2g(e, p, dt, forces);
         }
         HIP_TRY(hipEventRecord(q[4], e->stream));
@@ -3322,6 +3341,181 @@ int mpm_force_field_acceleration(const mpm_force_field_t* fields, size_t n_field
     for (size_t k = 0; k < n; ++k)
         force_field_acceleration(f, (int)n_fields, x + 3 * k, v + 3 * k, director ? director + 3 * k : zero, director != nullptr,
                                  acc_out + 3 * k);
+    return 0;
+} MPM_CATCH_ALL
+
+}  // extern "C"
+
+// ---- bending stiffness (mpm_set_bending, mpm_get_bending, mpm_bending_forces, mpm_bending_max_stable_dt,
+// mpm_bending_matrix; mpm_bending.h) ----
+extern "C" {
+
+// host code only: no device is touched
+int mpm_bending_matrix(const float* pos, size_t n_verts, const int32_t* indices, size_t n_faces, size_t* row_offsets,
+                       int32_t* cols, double* vals, size_t capacity, size_t* nnz_out) try {
+    REQUIRE((pos || n_verts == 0) && (indices || n_faces == 0), "null input array");
+    REQUIRE(capacity == 0 || (cols && vals), "null output");
+    REQUIRE(n_verts < (size_t)1 << 30 && n_faces < (size_t)1 << 30, "mesh too large");
+    for (size_t i = 0; i < n_faces * 3; ++i)
+        REQUIRE(indices[i] >= 0 && (size_t)indices[i] < n_verts, "triangle index out of range");
+    BendCsr Q;
+    std::string why;
+    if (!bending_matrix(pos, n_verts, indices, n_faces, 0, Q, why)) return fail(MPM_ERR_INVALID, why);
+    if (row_offsets) std::copy(Q.off.begin(), Q.off.end(), row_offsets);
+    const size_t n = std::min(capacity, Q.col.size());
+    std::copy(Q.col.begin(), Q.col.begin() + (long)n, cols);
+    std::copy(Q.val.begin(), Q.val.begin() + (long)n, vals);
+    if (nnz_out) *nnz_out = Q.col.size();
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try {
+    READY_NO_SETTLE(e);
+    REQUIRE(!multi_rank(e), "bending stiffness is not available on a partitioned or multi-rank engine");
+    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_bending: n_cloths must be mpm_cloth_count (or 0: off)");
+    REQUIRE(n_cloths == 0 || stiffness, "null stiffness array");
+    bool any = false;
+    for (size_t c = 0; c < n_cloths; ++c) {
+        REQUIRE(std::isfinite(stiffness[c]) && stiffness[c] >= 0.f, "bending: a stiffness is negative or not finite");
+        any = any || stiffness[c] > 0.f;
+    }
+    // the table on the host: rows in ascending vertex id, k folded in, the diagonal dropped (mpm_bending.h)
+    auto id_bits = [](int id) {
+        float f;
+        std::memcpy(&f, &id, sizeof f);
+        return f;
+    };
+    std::vector<int> row_pid;
+    std::vector<std::vector<float2>> rows;
+    std::vector<double> abs_sum;   // per row: sum_j |k Q_ij|, the diagonal included
+    for (size_t c = 0; c < n_cloths && any; ++c) {
+        if (!(stiffness[c] > 0.f)) continue;
+        const mpm_engine::Cloth& cl = e->cloths[c];
+        std::vector<int32_t> idx(3 * cl.n_faces);
+        for (size_t i = 0; i < idx.size(); ++i) idx[i] = e->h_idx[3 * cl.first_face + i] - (int32_t)cl.first_vertex;
+        BendCsr Q;
+        std::string why;
+        if (!bending_matrix(e->h_pos.data() + 3 * cl.first_vertex, cl.n_verts, idx.data(), cl.n_faces, cl.first_face, Q, why))
+            return fail(MPM_ERR_INVALID, why);
+        const double k = (double)stiffness[c];
+        for (size_t v = 0; v < cl.n_verts; ++v) {
+            const int own = (int)(e->nf + cl.first_vertex + v);
+            row_pid.push_back(own);
+            rows.emplace_back();
+            double a = 0.0;
+            for (size_t q = Q.off[v]; q < Q.off[v + 1]; ++q) {
+                a += std::fabs(k * Q.val[q]);
+                if ((size_t)Q.col[q] == v) continue;
+                rows.back().push_back(make_float2((float)(k * Q.val[q]), id_bits((int)(e->nf + cl.first_vertex) + Q.col[q])));
+            }
+            abs_sum.push_back(a);
+        }
+    }
+    const size_t n_rows = row_pid.size(), n_slices = (n_rows + BEND_SLICE - 1) / BEND_SLICE;
+    std::vector<unsigned> slice_off(n_slices + 1, 0u);
+    for (size_t s = 0; s < n_slices; ++s) {
+        size_t width = 0;
+        for (size_t r = s * BEND_SLICE; r < std::min(n_rows, (s + 1) * BEND_SLICE); ++r) width = std::max(width, rows[r].size());
+        REQUIRE((size_t)slice_off[s] + width * BEND_SLICE < (size_t)1 << 31, "bending: the table is too large");
+        slice_off[s + 1] = slice_off[s] + (unsigned)(width * BEND_SLICE);
+    }
+    std::vector<float2> ent(slice_off[n_slices]);
+    for (size_t s = 0; s < n_slices; ++s) {
+        const size_t width = (slice_off[s + 1] - slice_off[s]) / BEND_SLICE;
+        for (size_t l = 0; l < BEND_SLICE; ++l) {
+            const size_t r = s * BEND_SLICE + l;
+            // (padding: coefficient 0 and the row's own id; the lanes past the last row are never read)
+            const int own = r < n_rows ? row_pid[r] : row_pid[n_rows - 1];
+            for (size_t q = 0; q < width; ++q)
+                ent[slice_off[s] + q * BEND_SLICE + l] = r < n_rows && q < rows[r].size() ? rows[r][q] : make_float2(0.f, id_bits(own));
+        }
+    }
+    // substeps that mpm_run_substeps deferred are owed with the stiffness they were enqueued with
+    if (int rc = settle(e)) return rc;
+    float max_dt = INFINITY;
+    mpm_engine::Bending next;
+    if (n_rows) {
+        // m_i: the mass ParticleToGrid forms for the vertex particle (q[0].w x DP::M.density, both floats)
+        std::vector<float> vol(e->nv);
+        int* iota = nullptr;
+        if (int rc = device_iota(e, &iota)) return rc;
+        if (int rc = gather_to_host<F_VOL>(e, vol.data(), e->nv, iota + e->nf)) return rc;
+        double w2 = 0.0;
+        for (size_t r = 0; r < n_rows; ++r) {
+            const double m = (double)(std::fabs(vol[(size_t)row_pid[r] - e->nf]) * e->dp.M.density);
+            if (abs_sum[r] > 0.0) w2 = std::max(w2, m > 0.0 ? abs_sum[r] / m : (double)INFINITY);
+        }
+        if (w2 > 0.0) {
+            const double lim = 2.0 / std::sqrt(w2);
+            max_dt = (float)lim;
+            if ((double)max_dt > lim) max_dt = std::nextafterf(max_dt, 0.f);   // (rounded towards zero: never above the bound)
+        }
+        int* d_row = nullptr;
+        unsigned* d_off = nullptr;
+        float2* d_ent = nullptr;
+        if (int rc = e->dalloc(&d_row, n_rows, false)) return rc;
+        if (int rc = e->dalloc(&d_off, n_slices + 1, false)) { e->dfree(d_row); return rc; }
+        if (int rc = e->dalloc(&d_ent, ent.size(), false)) { e->dfree(d_row); e->dfree(d_off); return rc; }
+        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
+        auto upload = [&]() -> int {
+            H2D(e, d_row, row_pid.data(), n_rows * sizeof(int));
+            H2D(e, d_off, slice_off.data(), (n_slices + 1) * sizeof(unsigned));
+            if (!ent.empty()) H2D(e, d_ent, ent.data(), ent.size() * sizeof(float2));
+            return 0;
+        };
+        if (int rc = upload()) {   // (nothing changed: the new buffers go, the table in force stays)
+            e->dfree(d_row);
+            e->dfree(d_off);
+            e->dfree(d_ent);
+            return rc;
+        }
+        next.args = BendArgs{d_row, d_off, d_ent, (int)n_rows};
+    } else {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    {
+        BendArgs& old = e->bend.args;
+        int* o_row = const_cast<int*>(old.row_pid);
+        unsigned* o_off = const_cast<unsigned*>(old.slice_off);
+        float2* o_ent = const_cast<float2*>(old.ent);
+        e->dfree(o_row);
+        e->dfree(o_off);
+        e->dfree(o_ent);
+    }
+    next.k.assign(stiffness, stiffness + n_cloths);
+    next.max_dt = max_dt;
+    e->bend = next;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_get_bending(mpm_handle_t e, float* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    const size_t n = e->cloths.size();
+    for (size_t c = 0; c < std::min(capacity, n); ++c) out[c] = c < e->bend.k.size() ? e->bend.k[c] : 0.f;
+    if (n_out) *n_out = n;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_bending_forces(mpm_handle_t e, float* f_out) try {
+    READY(e);
+    REQUIRE(f_out || e->nv == 0, "null output");
+    const size_t bytes = e->nv * 12;
+    if (!e->bend.on()) {
+        std::memset(f_out, 0, bytes);
+        return 0;
+    }
+    if (int rc = e->stage(bytes)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
+    hipLaunchKernelGGL(k_bend_eval, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
+                       e->bend.args, (float*)e->d_stage);
+    D2H(e, f_out, e->d_stage, bytes);
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_bending_max_stable_dt(mpm_handle_t e, float* dt_out) try {
+    REQUIRE(e && dt_out, "null argument");
+    *dt_out = e->bend.on() ? e->bend.max_dt : INFINITY;
     return 0;
 } MPM_CATCH_ALL
 

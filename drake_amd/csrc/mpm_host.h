@@ -17,6 +17,7 @@
 #include "mpm_step.h"
 #include "mpm_contact_dev.h"
 #include "mpm_pins.h"
+#include "mpm_bending.h"
 #include "mpm_grid_bodies.h"
 #include "mpm_team.h"
 #include "mpm_trace.h"
@@ -209,6 +210,13 @@ struct mpm_engine {
     std::vector<mpm_force_field_t> force_fields;   // the caller's table, as given
     ForceFieldTable* d_force_fields = nullptr;     // ... as the kernel reads it
     double force_fields_gamma = 0.0;               // sum of gamma over the linear drags: dt * this <= 1 (fields_stable)
+    // bending stiffness (mpm_set_bending; mpm_bending.h): a cloth with k > 0 switches k_bend on behind k_vforce
+    struct Bending {
+        std::vector<float> k;            // [cloth] as given; empty or all zero: off
+        BendArgs args{};                 // the table as k_bend reads it (device memory, in `allocs`)
+        float max_dt = INFINITY;         // 2 / sqrt(max_i (1 / m_i) sum_j |k Q_ij|) (fields_stable)
+        bool on() const { return args.n_rows > 0; }
+    } bend;
     // fixed constraints (mpm_set_pins, mpm_set_body_motions; k_pin in mpm_pins.h)
     struct PinState {
         std::vector<mpm_pin_t> set;              // the caller's pins, in order

@@ -194,6 +194,28 @@ struct GpuMpmState {
         mpm_check(mpm_get_force_fields(h_, out.data(), n, &n));
         return out;
     }
+    // Extension: bending stiffness per cloth (mpm_set_bending), the quadratic hinge energy on a flat rest shape; all
+    // zeros or an empty vector switches it off.  A synchronisation point, like SetForceFields.
+    void SetBending(const std::vector<float>& stiffness) { mpm_check(mpm_set_bending(h_, stiffness.size(), stiffness.data())); }
+    std::vector<float> GetBending() const {
+        size_t n = 0;
+        mpm_check(mpm_get_bending(h_, nullptr, 0, &n));
+        std::vector<float> out(n);
+        mpm_check(mpm_get_bending(h_, out.data(), n, &n));
+        return out;
+    }
+    // -k Q x on the current positions, 3 floats per vertex in the numbering of DumpCpuState (a diagnostic)
+    std::vector<float> BendingForces(size_t n_verts) const {
+        std::vector<float> f(3 * n_verts);
+        mpm_check(mpm_bending_forces(h_, f.data()));
+        return f;
+    }
+    // the dt above which the substep entry points refuse an engine with bending (+inf while it is off)
+    float BendingMaxStableDt() const {
+        float dt = 0.f;
+        mpm_check(mpm_bending_max_stable_dt(h_, &dt));
+        return dt;
+    }
     std::vector<Vec3<T>>& positions_host() { return h_positions_; }
     const std::vector<Vec3<T>>& positions_host() const { return h_positions_; }
     ExternalSpatialForce<T>& external_forces_host() { return h_external_forces_; }

@@ -759,6 +759,51 @@ MPM_API int mpm_get_force_fields(mpm_handle_t h, mpm_force_field_t *out, size_t 
 MPM_API int mpm_force_field_acceleration(const mpm_force_field_t *fields, size_t n_fields, size_t n, const float *x,
                                          const float *v, const float *director, float *acc_out);
 
+/* ---- Bending stiffness of the cloth, per cloth (an extension) ----
+ * The membrane model resists stretch, shear and change of the director, not folding: an isometric fold costs nothing.
+ * This adds the quadratic hinge energy of Bergou et al. 2006 / Wardetzky et al. 2007 for a rest shape that is flat per
+ * hinge (the positions given to mpm_add_qr_cloth*; rest angles zero).  Every interior edge x0 x1 shared by exactly two
+ * faces of one cloth is a hinge (x0, x1 | x2, x3), x2 opposite the edge in face A, x3 in face B.  With a0, a1 the rest
+ * angles of face A at x0, x1, b0, b1 those of face B and A_A, A_B the rest areas,
+ *   K = (cot a1 + cot b1, cot a0 + cot b0, -(cot a0 + cot a1), -(cot b0 + cot b1)),   c = 3 / (A_A + A_B),
+ *   E = 1/2 k sum_h c_h |sum_j K_hj x_j|^2 = 1/2 x^T (k Q) x,   f = -k Q x   on the vertex particles.
+ * Q is constant, symmetric, sparse (13 entries per row on a regular valence-6 mesh), its rows sum to zero: the force is
+ * linear in the positions, zero on every affine image of the rest shape, and its total and total torque vanish.
+ * Boundary edges and edges with more than two faces form no hinge.  k is a flexural rigidity (N m); the discrete energy
+ * of a right-triangle grid bent onto a cylinder of radius R is about 3 x 1/2 k A / R^2 (the model's mesh-dependent
+ * factor: calibrate k against the mesh in use).
+ * The force joins the vertex forces of CalcFemStateAndForce (MPM_ARR_FORCES includes it; its kernel runs behind the
+ * vertex-force kernel and counts under MPM_PHASE_VFORCE).  It works with pins, per-cloth materials, grid bodies, force
+ * fields, deterministic mode, fast math and the coupled path, and is the same bits whatever the particle order.
+ * mpm_set_bending needs mpm_finalize, is ordered on the engine's stream and is a synchronisation point; substeps that
+ * mpm_run_substeps still owes are run first, with the stiffness they were enqueued with.  stiffness[c] >= 0 is cloth
+ * c's k; n_cloths must be mpm_cloth_count, or 0.  All zeros or n_cloths = 0 switches the feature off: the engine then
+ * launches exactly what it launches without this call.  While it is on the engine does not use the re-sort's quiet-time
+ * estimate to omit re-sort check launches, and every batched substep launches the vertex-force kernel.
+ * Stability: the entry points that take a dt and check the force fields' (see above) also return MPM_ERR_INVALID,
+ * before anything is enqueued, for a dt above mpm_bending_max_stable_dt = 2 / sqrt(max_i (1 / m_i) sum_j |k Q_ij|), m_i
+ * the vertex particle's mass as of mpm_set_bending: Gershgorin's bound on the lumped system, on which symplectic Euler
+ * needs dt omega <= 2.  It is conservative for MPM (the grid shares a vertex's impulse with the face particles around
+ * it): a guard, not a guarantee.  +inf while the feature is off.
+ * Refused with MPM_ERR_INVALID, nothing changed: a stiffness that is negative or not finite; a wrong count; a call
+ * before mpm_finalize; a face with a hinge whose rest area is zero or whose rest cotangent is not finite, in a cloth
+ * with k > 0 (the message names the face); any partitioned or multi-rank engine -- this call on such an engine, and
+ * mpm_dist_init, the halo, chain, team and world substeps on an engine with bending on. */
+MPM_API int mpm_set_bending(mpm_handle_t h, size_t n_cloths, const float *stiffness);
+/* The stiffness in force: min(mpm_cloth_count, capacity) values into out (zeros while off), the cloth count into *n_out. */
+MPM_API int mpm_get_bending(mpm_handle_t h, float *out, size_t capacity, size_t *n_out);
+/* -k Q x on the current positions: f_out[3 * n_verts], in the vertex numbering of mpm_dump_cpu_state (zeros for the
+ * vertices of cloths without bending).  The device function of the substep's kernel; changes no state. */
+MPM_API int mpm_bending_forces(mpm_handle_t h, float *f_out);
+MPM_API int mpm_bending_max_stable_dt(mpm_handle_t h, float *dt_out);
+/* Q of one cloth on the host (no handle, no device), in double from the float rest positions pos[3 * n_verts] and the
+ * triangles indices[3 * n_faces], as CSR: ascending columns, the diagonal included, every pair of vertices that shares
+ * a hinge present.  row_offsets[n_verts + 1] (may be NULL); min(nnz, capacity) entries into cols / vals (may be NULL
+ * when capacity is 0); nnz into *nnz_out: call once with capacity 0 for the size.  MPM_ERR_INVALID, naming the face,
+ * when a face with a hinge has zero rest area or a cotangent that is not finite. */
+MPM_API int mpm_bending_matrix(const float *pos, size_t n_verts, const int32_t *indices, size_t n_faces, size_t *row_offsets,
+                               int32_t *cols, double *vals, size_t capacity, size_t *nnz_out);
+
 /* Runs n substeps with HIP events around every kernel group on the engine's
  * stream and returns the mean milliseconds per substep of each phase
  * (phase_ms[MPM_PHASE_COUNT]) and of the whole substep. */
