@@ -788,7 +788,9 @@ static ContactDev enqueue_keys(const SolveCtx& x, const SolveParams& prm, bool r
     e->last_contact_gated = false;
     b.solves += 1;
     const ContactDev c_in = make_contact_dev(e, prm, /* sorted = */ false);
-    hipLaunchKernelGGL(k_ct_keys, dim3(1024), dim3(256), 0, e->stream, e->dp, c_in, (const uint32_t*)b.api_idx, (const int*)e->d_pids_api,
+    DP p = e->dp;
+    p.gated = prm.gated;   // (the gate of the coupled substep in front: a substep that skipped itself refuses its solve)
+    hipLaunchKernelGGL(k_ct_keys, dim3(1024), dim3(256), 0, e->stream, p, c_in, (const uint32_t*)b.api_idx, (const int*)e->d_pids_api,
                        b.slot, b.published, b.solves, g.bits, (int)std::min<size_t>(g.n, 0x7FFFFFFF), reuse ? 1 : 0, full_setup ? 1 : 0,
                        b.gen_stamp, team ? 1 : 0);
     return c_in;
@@ -878,8 +880,8 @@ static int profile_contact_iteration(mpm_engine* e, int reps, float* kernel_ms) 
     x.c.mbox = nullptr;   // (nothing here is waited for through the mailbox)
     const DP& p = e->dp;
     hipStream_t s = e->stream;
-    hipEvent_t ev[5];
-    for (auto& ev_k : ev) HIP_TRY(hipEventCreate(&ev_k));
+    Events ev;
+    if (int rc = ev.create(5)) return rc;
     auto phase = [&](int k) {
         for (int r = 0; r < reps; ++r) {
             if (k == 0) launch_ct_tile(dim3(x.g.n_tile_wg), s, p, x.c, 0, 0);
@@ -900,7 +902,6 @@ static int profile_contact_iteration(mpm_engine* e, int reps, float* kernel_ms) 
         HIP_TRY(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
         kernel_ms[k] = ms / (float)reps;
     }
-    for (auto& ev_k : ev) (void)hipEventDestroy(ev_k);
     HIP_TRY(hipMemsetAsync(b.st, 0, offsetof(ContactState, n), s));
     return 0;
 }
@@ -1335,7 +1336,6 @@ static void record_outcome(mpm_engine* e, const SolveParams& prm, const SolveOut
     cs.nodes = mb.nodes;
     cs.residual = mb.residual;
     e->last_contact_on_device = !oc.have_state;
-    e->last_contact_exact = prm.exact != 0;
     if (!oc.have_state) return;
     stats_from_state(&cs, oc.st);
     if (prm.exact && !oc.log.ls.empty()) {   // (host-driven exact search: its own bookkeeping)

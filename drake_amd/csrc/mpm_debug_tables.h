@@ -41,7 +41,7 @@ static int debug_resort_table(mpm_engine* e, int which, void* out, size_t capaci
         case MPM_RT_PARAMS: {
             const int32_t rec[16] = {p.Nf, p.Np, p.bits, p.nb, (int32_t)p.nblocks, (int32_t)p.capH, (int32_t)p.capA,
                                      (int32_t)p.capI, (int32_t)p.capS, p.item_groups, p.item_groups_small, p.item_small_below,
-                                     bits_of(p.dist.on ? 0.f : e->anticipate_horizon * e->last_dt * p.dxinv),   // (launch_rebuild)
+                                     bits_of(e->anticipation()),   // (as launch_rebuild sets DP::anticip)
                                      p.fem_fast, p.dist.on, p.NpG};
             return give(rec, 16);
         }

@@ -87,6 +87,10 @@ int mpm_create(int domain_bits, const mpm_material_t* material, int device, mpm_
     return 0;
 } MPM_CATCH_ALL
 
+static mpm_cloth_material_t engine_cloth_material(const mpm_engine* e) {
+    const mpm_material_t& em = e->mat;
+    return mpm_cloth_material_t{em.youngs_modulus, em.poisson_ratio, em.density, em.gamma, em.K, em.c_F};
+}
 // (m: the cloth's own material, or null for the engine's; checked by the caller.  Nothing is recorded on a refusal.)
 static int add_cloth(mpm_engine* e, const float* pos, const float* vel, size_t n_verts, const int32_t* indices,
                      size_t n_faces, const mpm_cloth_material_t* m) {
@@ -98,8 +102,7 @@ static int add_cloth(mpm_engine* e, const float* pos, const float* vel, size_t n
     REQUIRE(!(e->multi_mat || m) || e->cloths.size() < MAX_CLOTH_MATERIALS,
             "more than 256 cloths in a multi-material engine (mpm_add_qr_cloth_with_material)");
     mpm_engine::Cloth c{e->nv, n_verts, e->nf, n_faces, {}};
-    const mpm_material_t& em = e->mat;
-    c.m = m ? *m : mpm_cloth_material_t{em.youngs_modulus, em.poisson_ratio, em.density, em.gamma, em.K, em.c_F};
+    c.m = m ? *m : engine_cloth_material(e);
     e->cloths.push_back(c);
     if (m) e->multi_mat = true;
     for (size_t i = 0; i < n_faces * 3; ++i) e->h_idx.push_back(indices[i] + (int)e->nv);
@@ -119,13 +122,7 @@ int mpm_add_qr_cloth(mpm_handle_t e, const float* pos, const float* vel, size_t 
 int mpm_add_qr_cloth_with_material(mpm_handle_t e, const float* pos, const float* vel, size_t n_verts,
                                    const int32_t* indices, size_t n_faces, const mpm_cloth_material_t* m) try {
     REQUIRE(e, "null handle");
-    mpm_cloth_material_t c;
-    if (m) {
-        c = *m;
-    } else {
-        const mpm_material_t& em = e->mat;
-        c = mpm_cloth_material_t{em.youngs_modulus, em.poisson_ratio, em.density, em.gamma, em.K, em.c_F};
-    }
+    const mpm_cloth_material_t c = m ? *m : engine_cloth_material(e);
     REQUIRE(std::isfinite(c.youngs_modulus) && std::isfinite(c.poisson_ratio) && std::isfinite(c.density) &&
                 std::isfinite(c.gamma) && std::isfinite(c.K) && std::isfinite(c.c_F),
             "cloth material: a field is not finite");
@@ -207,12 +204,13 @@ static int grid_colliders_for(mpm_engine* e, int bc, GridColliders* out) {
     return 0;
 }
 
-// lean: CalcFemStateAndForce follows at once (DP::lean_resort).  Callers that enqueue a possible re-sort call may_resort()
-// themselves.
-static void launch_rebuild(mpm_engine* e, DP p, bool lean = false) {
-    // anticipatory binning over the next `horizon` substeps of the last known length (not in a partitioned
-    // domain, where ownership and ghost bands are defined by the position itself)
-    p.anticip = p.dist.on ? 0.f : e->anticipate_horizon * e->last_dt * p.dxinv;
+// The conditional re-sort.  lean: CalcFemStateAndForce follows at once (DP::lean_resort).  dt: the length of the substep the
+// launches belong to, where there is one -- the anticipatory binning then uses it; the last known length stays otherwise.
+// (The block tables may change: the contact solve's guess of how many blocks are active survives that, k_ct_keys verifies
+// it on the device.)
+static void launch_rebuild(mpm_engine* e, DP p, bool lean = false, float dt = 0.f) {
+    if (dt > 0.f) e->last_dt = dt;
+    p.anticip = e->anticipation();
     p.lean_resort = lean && !p.dist.on;
     e->checks_launched += 1;
     TraceRange tr("mpm:RebuildMapping (conditional re-sort)");
@@ -222,15 +220,9 @@ static void launch_rebuild(mpm_engine* e, DP p, bool lean = false) {
     if (e->deterministic) hipLaunchKernelGGL(k_rb_canon, dim3(512), dim3(256), 0, e->stream, p);
     hipLaunchKernelGGL(k_rb_finish, dim3((std::min(e->g_np, e->g_rb) + 7u) & ~7u), dim3(256), 0, e->stream, p);
 }
-// A re-sort may be about to run: the block tables may change, so contact
-// pairs handed over before are re-keyed with the full width, and the anticipatory binning uses this substep length.
-static void may_resort(mpm_engine* e, float dt) {
-    // (the contact solve's guess of how many blocks are active survives a re-sort: k_ct_keys verifies it on the device)
-    if (dt > 0.f) e->last_dt = dt;
-}
 
 // The launch helpers below take the DP of the launch: e->dp, or a copy of it with the per-launch fields set (DP::lean_g2p,
-// gated, watch_base, halo_hdr, halo_*).
+// gated, watch_base, halo_hdr, halo_*).  Nothing writes those fields of e->dp itself.
 static void launch_fem_faces(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:CalcFemStateAndForce (faces)");
     if (!e->nf) return;
@@ -251,6 +243,7 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p) {
     if (e->bend.on())
         hipLaunchKernelGGL(k_bend, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->bend.args);
 }
+// (mpm_calc_fem_state_and_force: the two FEM kernels, whose forces a caller may read)
 static void launch_fem(mpm_engine* e, const DP& p, float dt) {
     e->last_dt = dt;
     launch_fem_faces(e, p, dt);
@@ -282,21 +275,11 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
     else MPM_P2G_LAUNCH(0);
 #undef MPM_P2G_LAUNCH_FIELDS
 #undef MPM_P2G_LAUNCH
-    e->last_tile_kernel = 1;
 }
 // the vertex forces inside k_p2g, from the vertices' entries of DP::VF (single and partitioned domains alike since round
 // 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch, and so does an engine with bending
 // stiffness, whose k_bend adds to the forces in DP::f
 static int fused_forces(const mpm_engine* e) { return e->max_valence <= 8 && !e->bend.on() ? 1 : 0; }
-// FEM faces, then P2G with the vertex forces of every work item computed inside it (no k_vforce launch): the
-// batched substeps use this; the phase-by-phase calls keep the two FEM kernels, whose forces a caller may read
-static void launch_fem_p2g(mpm_engine* e, const DP& p, float dt) {
-    e->last_dt = dt;
-    launch_fem_faces(e, p, dt);
-    const int forces = fused_forces(e);
-    if (!forces) launch_fem_vertices(e, p);
-    launch_p2g(e, p, dt, forces);
-}
 // the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins launches it (pins_ready has resolved the
 // table).  Everything after GridToParticle -- the coupled path's watch kernel included -- comes after it on the stream.
 static void launch_pins(mpm_engine* e, const DP& p, float dt) {
@@ -312,7 +295,6 @@ static void launch_g2p(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:GridToParticle");
     hipLaunchKernelGGL(k_g2p, dim3(std::min(768u, p.capI)), dim3(G2P_THREADS), 0, e->stream, p, dt);
     if (!e->pin.set.empty() && p.halo_cls < 0) launch_pins(e, p, dt);
-    e->last_tile_kernel = 2;
 }
 static void launch_grid(mpm_engine* e, const DP& p, const GridColliders& gc) {
     TraceRange tr("mpm:UpdateGrid");
@@ -330,6 +312,47 @@ static void launch_grid(mpm_engine* e, const DP& p, const GridColliders& gc) {
         return;
     }
     hipLaunchKernelGGL(k_grid<1>, dim3(e->g_grid), dim3(256), 0, e->stream, p, gc);
+}
+
+// ---- the substep's kernel sequence, stated once --------------------------------------------------------------------------
+// Every entry point that runs a substep enqueues it through the two functions below, each from the DP of the launch (e->dp,
+// or a copy with the per-launch fields set); only the phase-by-phase calls, whose separate kernels are their contract,
+// launch FEM and ParticleToGrid themselves.  `mark`, where given, is called with the number of every phase of
+// mpm_profile_substeps' list as its launches end.
+using PhaseMark = std::function<void(int)>;
+// the re-sort launches in front of a substep: none; lean (FEM follows at once); all of them; the held-back RebuildMapping(false)
+// of the phase-by-phase calls, which came before its substep's dt and keeps the last known length for its binning
+enum class Resort { None, Lean, Full, Held };
+// The front: re-sort launches if asked, FEM faces, vertex forces (and bending) as kernels of their own unless ParticleToGrid
+// computes them (fused_forces), ParticleToGrid.
+static void enqueue_substep_front(mpm_engine* e, const DP& p, float dt, Resort resort, const PhaseMark& mark = {}) {
+    if (resort != Resort::None) launch_rebuild(e, p, resort == Resort::Lean, resort == Resort::Held ? 0.f : dt);
+    e->last_dt = dt;
+    if (mark) mark(MPM_PHASE_REBUILD);
+    launch_fem_faces(e, p, dt);
+    if (mark) mark(MPM_PHASE_FEM);
+    const int forces = fused_forces(e);
+    if (!forces) launch_fem_vertices(e, p);
+    if (mark) mark(MPM_PHASE_VFORCE);
+    launch_p2g(e, p, dt, forces);
+    if (mark) mark(MPM_PHASE_P2G);
+}
+// The rest: the grid kernel in one of three forms -- the fused update (launch_grid), the gather of the raw sums (a halo
+// exchange follows), the update from sums -- from `pg`, then GridToParticle from `*p2`.  p2 == nullptr: no GridToParticle
+// (the gather; a coupled substep, whose contact solve comes first and which launches it itself).
+enum class GridForm { Fused, Gather, FromSums };
+static void enqueue_substep_rest(mpm_engine* e, GridForm form, const DP& pg, const GridColliders& gc, const DP* p2, float dt,
+                                 const PhaseMark& mark = {}) {
+    const dim3 g(e->g_grid), b(256);
+    switch (form) {
+        case GridForm::Fused: launch_grid(e, pg, gc); break;
+        case GridForm::Gather: hipLaunchKernelGGL(k_grid<0>, g, b, 0, e->stream, pg, GridColliders{}); break;
+        case GridForm::FromSums: hipLaunchKernelGGL(k_grid<2>, g, b, 0, e->stream, pg, gc); break;
+    }
+    if (mark) mark(MPM_PHASE_GRID);
+    if (!p2) return;
+    launch_g2p(e, *p2, dt);
+    if (mark) mark(MPM_PHASE_G2P);
 }
 
 // The P2G tiles accumulate in 64-bit fixed point.  Scales are powers of two chosen from the
@@ -714,19 +737,20 @@ static int recover_slab_overflow(mpm_engine* e, Ctl& c) {
         const int one = 1;
         H2D(e, &e->dp.ctl->error, &zero, sizeof(unsigned));
         H2D(e, &e->dp.ctl->need_rebuild, &one, sizeof(int));
-        may_resort(e, 0.f);
         launch_rebuild(e, e->dp);
         D2H(e, &c, e->dp.ctl, sizeof(Ctl));
     }
     return 0;
 }
 
-// The stream is idle and `c` is the control block as it stands: what is left of the quiet time the last re-sort
-// estimated.  Substeps enqueued right after go without check launches while it lasts (launch_substep); any call that
-// may change the state resets it (settle_owed).
-static void note_quiet_time(mpm_engine* e, const Ctl& c) {
-    e->quiet_left = c.skipped || c.need_rebuild || c.error ? 0.f : std::max(0.f, c.quiet_time - c.time_since_resort);
+// `c` is the control block as it stands on an idle stream: what is left of the quiet time the last re-sort estimated
+// (Ctl::quiet_time).  Nothing while a re-sort is pending, substeps are owed or an error flag is up.
+static float quiet_time_left(const Ctl& c) {
+    return c.skipped || c.need_rebuild || c.error ? 0.f : std::max(0.f, c.quiet_time - c.time_since_resort);
 }
+// Substeps enqueued right after go without check launches while it lasts (launch_substep); any call that may change the
+// state resets it (settle_owed).
+static void note_quiet_time(mpm_engine* e, const Ctl& c) { e->quiet_left = quiet_time_left(c); }
 
 int mpm_sync(mpm_handle_t e) try {
     REQUIRE(e, "null handle");
@@ -869,9 +893,7 @@ static int settle_owed(mpm_engine* e, Ctl* fresh) {
         // every substep since the overflowing re-sort has skipped itself: the pool can be grown and the re-sort repeated
         if (int rc = recover_slab_overflow(e, c)) return rc;
         const unsigned owed = c.skipped;
-        // what is left of the quiet time the last re-sort estimated (Ctl::quiet_time): substeps enqueued from here
-        // on go without check launches while it lasts (launch_substep).  Nothing left when a re-sort is pending.
-        e->quiet_left = owed || c.need_rebuild || c.error ? 0.f : std::max(0.f, c.quiet_time - c.time_since_resort);
+        note_quiet_time(e, c);
         if (e->dp.dbg & 32)
             std::fprintf(stderr, "[mpm_hip] settle: quiet time %.4g s, %.4g s since the re-sort, %u owed, re-sort pending %d, checks launched %llu\n",
                          c.quiet_time, c.time_since_resort, owed, c.need_rebuild, (unsigned long long)e->checks_launched);
@@ -886,7 +908,6 @@ static int settle_owed(mpm_engine* e, Ctl* fresh) {
         H2D(e, &e->dp.ctl->skipped, &zero, sizeof(unsigned));
         GridColliders gc;
         if (int rc = grid_colliders_for(e, e->owed_bc, &gc)) return rc;
-        may_resort(e, e->owed_dt);
         for (unsigned k = 0; k < owed; ++k) launch_substep(e, e->owed_dt, gc, false);
     }
     e->force_check = true;
@@ -1010,21 +1031,18 @@ static bool can_defer(const mpm_engine* e) { return e->defer_phases && e->finali
 static int flush_phases(mpm_engine* e) {
     const int n = e->pend.n;
     e->pend.n = 0;
-    if (n >= 1) {
-        may_resort(e, 0.f);
-        launch_rebuild(e, e->dp);
-    }
+    if (n == 1 || n == 2) launch_rebuild(e, e->dp);
     if (n == 2) launch_fem(e, e->dp, e->pend.dt);
     if (n >= 3) {
         // (nobody looked at the forces between CalcFemStateAndForce and ParticleToGrid: the vertex forces are
         // gathered inside k_p2g, which also writes them out -- one launch less, the same numbers)
-        launch_fem_p2g(e, e->dp, e->pend.dt);
+        enqueue_substep_front(e, e->dp, e->pend.dt, Resort::Held);
         e->grid_state = 1;
     }
     if (n >= 4) {
         GridColliders gc;
         if (int rc = grid_colliders_for(e, e->pend.bc, &gc)) return rc;
-        launch_grid(e, e->dp, gc);
+        enqueue_substep_rest(e, GridForm::Fused, e->dp, gc, nullptr, 0.f);
         e->grid_state = 2;
     }
     return 0;
@@ -1037,7 +1055,6 @@ int mpm_rebuild_mapping(mpm_handle_t e, int sort) try {
         return 0;
     }
     READY(e);
-    may_resort(e, 0.f);
     launch_rebuild(e, e->dp);
     if (sort) {
         REQUIRE(!e->dp.dist.on, "RebuildMapping(sort = true) is not available on a partitioned domain");
@@ -1085,7 +1102,7 @@ int mpm_update_grid(mpm_handle_t e, int bc) try {
     REQUIRE(e->grid_state >= 1, "UpdateGrid before ParticleToGrid");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
-    launch_grid(e, e->dp, gc);
+    enqueue_substep_rest(e, GridForm::Fused, e->dp, gc, nullptr, 0.f);
     e->grid_state = 2;
     return 0;
 } MPM_CATCH_ALL
@@ -1093,7 +1110,7 @@ int mpm_update_grid(mpm_handle_t e, int bc) try {
 int mpm_grid_gather(mpm_handle_t e) try {
     READY(e);
     REQUIRE(e->grid_state >= 1, "grid gather before ParticleToGrid");
-    hipLaunchKernelGGL(k_grid<0>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, GridColliders{});
+    enqueue_substep_rest(e, GridForm::Gather, e->dp, GridColliders{}, nullptr, 0.f);
     e->grid_state = 3;  // raw sums in gv
     return 0;
 } MPM_CATCH_ALL
@@ -1128,7 +1145,7 @@ int mpm_update_grid_from_sums(mpm_handle_t e, int bc) try {
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
     REQUIRE(gc.n >= 0, "MPM_BC_BODIES is not available in the halo substeps (grid bodies: single-engine only)");
-    hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, gc);
+    enqueue_substep_rest(e, GridForm::FromSums, e->dp, gc, nullptr, 0.f);
     e->grid_state = 2;
     return 0;
 } MPM_CATCH_ALL
@@ -1136,10 +1153,8 @@ int mpm_update_grid_from_sums(mpm_handle_t e, int bc) try {
 int mpm_substep_begin(mpm_handle_t e, float dt) try {
     READY(e);
     if (int rc = fields_stable(e, dt)) return rc;
-    may_resort(e, dt);
-    launch_rebuild(e, e->dp);
-    launch_fem_p2g(e, e->dp, dt);
-    hipLaunchKernelGGL(k_grid<0>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, GridColliders{});
+    enqueue_substep_front(e, e->dp, dt, Resort::Full);
+    enqueue_substep_rest(e, GridForm::Gather, e->dp, GridColliders{}, nullptr, 0.f);
     e->grid_state = 3;
     return 0;
 } MPM_CATCH_ALL
@@ -1151,26 +1166,18 @@ int mpm_substep_end(mpm_handle_t e, float dt, int bc) try {
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
     REQUIRE(gc.n >= 0, "MPM_BC_BODIES is not available in the halo substeps (grid bodies: single-engine only)");
-    hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, e->dp, gc);
+    enqueue_substep_rest(e, GridForm::FromSums, e->dp, gc, &e->dp, dt);
     e->grid_state = 2;
-    launch_g2p(e, e->dp, dt);
     e->substeps += 1;
     return 0;
 } MPM_CATCH_ALL
 
 // lean: another substep of the same batch follows (mpm_chain_substeps, see DP::lean_g2p)
-static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
-                              void* const* send_bufs, size_t cap, uint32_t* const* counters, bool lean);
-int mpm_substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
-                           void* const* send_bufs, size_t cap) try {
-    return substep_begin_halo(e, dt, n, bx_lo, bx_hi, shift_bx, send_bufs, cap, nullptr, false);
-} MPM_CATCH_ALL
 // counters: per zone the word the pack counts its entries in (null: word 0 of the send buffer itself)
 static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
                               void* const* send_bufs, size_t cap, uint32_t* const* counters, bool lean) {
     READY(e);
     if (int rc = extensions_refused(e, "halo substeps")) return rc;
-    may_resort(e, dt);
     REQUIRE(n >= 0 && n <= 2 && (n == 0 || (bx_lo && bx_hi && shift_bx && send_bufs)), "bad halo zone list");
     REQUIRE(n == 0 || (cap > 0 && cap < (1u << 24)), "bad halo buffer");
     DP p = e->dp;   // per-launch copy: k_grid<0> packs the zones' sums into the send buffers as it gathers them
@@ -1185,14 +1192,24 @@ static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo,
         p.halo_pbuf[i] = static_cast<uint32_t*>(send_bufs[i]);
         p.halo_pcnt[i] = counters ? counters[i] : nullptr;
     }
-    launch_rebuild(e, e->dp, true);
-    launch_fem_p2g(e, pp, dt);
-    hipLaunchKernelGGL(k_grid<0>, dim3(e->g_grid), dim3(256), 0, e->stream, p, GridColliders{});
+    enqueue_substep_front(e, pp, dt, Resort::Lean);
+    enqueue_substep_rest(e, GridForm::Gather, p, GridColliders{}, nullptr, 0.f);
     e->grid_state = 3;
     e->halo_mid_done = false;
     e->halo_nz = n;
     for (int i = 0; i < n; ++i) { e->halo_zlo[i] = bx_lo[i]; e->halo_zhi[i] = bx_hi[i]; }
     return 0;
+}
+int mpm_substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
+                           void* const* send_bufs, size_t cap) try {
+    return substep_begin_halo(e, dt, n, bx_lo, bx_hi, shift_bx, send_bufs, cap, nullptr, false);
+} MPM_CATCH_ALL
+
+// the zones of the last mpm_substep_begin_halo into a DP's zone list (halo_nz / halo_zlo / halo_zhi of a split update, or
+// halo_pn / halo_plo / halo_phi of an update that adds the received sums itself)
+static void halo_zones_into(const mpm_engine* e, int* n, int* lo, int* hi) {
+    *n = e->halo_nz;
+    for (int i = 0; i < e->halo_nz; ++i) { lo[i] = e->halo_zlo[i]; hi[i] = e->halo_zhi[i]; }
 }
 
 // Between begin and end: the part of the grid update and of G2P that does not depend on the
@@ -1205,19 +1222,12 @@ int mpm_substep_mid_halo(mpm_handle_t e, float dt, int bc) try {
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
     DP p = e->dp;
     p.halo_cls = 0;
-    p.halo_nz = e->halo_nz;
-    for (int i = 0; i < e->halo_nz; ++i) { p.halo_zlo[i] = e->halo_zlo[i]; p.halo_zhi[i] = e->halo_zhi[i]; }
-    hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, p, gc);
-    launch_g2p(e, p, dt);
+    halo_zones_into(e, &p.halo_nz, p.halo_zlo, p.halo_zhi);
+    enqueue_substep_rest(e, GridForm::FromSums, p, gc, &p, dt);
     e->halo_mid_done = true;
     return 0;
 } MPM_CATCH_ALL
 
-static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p,
-                            bool lean);
-int mpm_substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap) try {
-    return substep_end_halo(e, dt, bc, n, recv_bufs, cap, true, false);
-} MPM_CATCH_ALL
 // with_g2p = false: the grid update only -- a coupled substep puts the contact solve between it and GridToParticle
 // lean: as for substep_begin_halo
 static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p,
@@ -1237,29 +1247,27 @@ static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void*
     p.lean_g2p = lean && !e->dp.dist.on;
     if (e->halo_mid_done) {   // the interior is done: only what the received sums touch is left
         p.halo_cls = 1;
-        p.halo_nz = e->halo_nz;
-        for (int i = 0; i < e->halo_nz; ++i) { p.halo_zlo[i] = e->halo_zlo[i]; p.halo_zhi[i] = e->halo_zhi[i]; }
+        halo_zones_into(e, &p.halo_nz, p.halo_zlo, p.halo_zhi);
     }
     // The received sums are added inside the grid update (k_grid<2> looks its zone blocks up in the buffers): one launch
     // less per substep than add + update.  Needs the zones of the matching mpm_substep_begin_halo, buffer i <-> zone i.
     DP pg = p;
     const bool folded = n > 0 && n == e->halo_nz;
     if (folded) {
-        pg.halo_pn = n;
+        halo_zones_into(e, &pg.halo_pn, pg.halo_plo, pg.halo_phi);
         pg.halo_pcap = (unsigned)cap;
-        for (int i = 0; i < n; ++i) {
-            pg.halo_plo[i] = e->halo_zlo[i]; pg.halo_phi[i] = e->halo_zhi[i];
-            pg.halo_pbuf[i] = const_cast<uint32_t*>(b.buf[i]);
-        }
+        for (int i = 0; i < n; ++i) pg.halo_pbuf[i] = const_cast<uint32_t*>(b.buf[i]);
     }
     if (n > 0 && !folded) hipLaunchKernelGGL(k_halo_add2, dim3(64, n), dim3(256), 0, e->stream, p, b, (unsigned)cap);
-    hipLaunchKernelGGL(k_grid<2>, dim3(e->g_grid), dim3(256), 0, e->stream, pg, gc);
-    if (with_g2p) launch_g2p(e, p, dt);
+    enqueue_substep_rest(e, GridForm::FromSums, pg, gc, with_g2p ? &p : nullptr, dt);
     e->halo_mid_done = false;
     e->grid_state = 2;
     if (with_g2p) e->substeps += 1;
     return 0;
 }
+int mpm_substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap) try {
+    return substep_end_halo(e, dt, bc, n, recv_bufs, cap, true, false);
+} MPM_CATCH_ALL
 
 int mpm_chain_unique_id(char id_out[128]) try {
     REQUIRE(id_out, "null argument");
@@ -1270,6 +1278,14 @@ int mpm_chain_unique_id(char id_out[128]) try {
     std::memcpy(id_out, id.internal, rccl_rt::kIdBytes);
     return 0;
 } MPM_CATCH_ALL
+
+// the neighbours' regions of the direct halo, unmapped (a ring of two maps one region for both sides)
+static void chain_unmap_peers(mpm_engine::Chain& c) {
+    for (int k = 0; k < 2; ++k)
+        if (c.peer_mapped[k] && c.peer_base[k] && !(k == 1 && c.peer_base[1] == c.peer_base[0])) (void)hipIpcCloseMemHandle(c.peer_base[k]);
+    c.peer_mapped[0] = c.peer_mapped[1] = false;
+    c.peer_base[0] = c.peer_base[1] = nullptr;
+}
 
 int mpm_chain_destroy(mpm_handle_t e) try {
     REQUIRE(e, "null handle");
@@ -1283,8 +1299,7 @@ int mpm_chain_destroy(mpm_handle_t e) try {
     for (void* q : {c.send_l, c.send_r, c.recv_l, c.recv_r, c.mig_send_l, c.mig_send_r, c.mig_recv_l, c.mig_recv_r,
                     (void*)c.mig_quiet_all})
         if (q) (void)hipFree(q);
-    for (int k = 0; k < 2; ++k)
-        if (c.peer_mapped[k] && c.peer_base[k] && !(k == 1 && c.peer_base[1] == c.peer_base[0])) (void)hipIpcCloseMemHandle(c.peer_base[k]);
+    chain_unmap_peers(c);
     if (c.direct_base) (void)hipFree(c.direct_base);
     if (c.direct_cnt) (void)hipFree(c.direct_cnt);
     c = mpm_engine::Chain();
@@ -1390,7 +1405,6 @@ int mpm_chain_direct_prepare(mpm_handle_t e, char handle_out[64]) try {
                 return fail(MPM_ERR_HIP, std::string("mpm_chain_direct_prepare: fine-grained device memory is not available (") +
                                              hipGetErrorString(fg) + "): the direct halo exchange needs it; stay on the RCCL transport");
             HIP_TRY(hipMalloc(&c.direct_base, bytes));
-            c.direct_coarse = true;
         }
         HIP_TRY(hipMemsetAsync(c.direct_base, 0, bytes, e->stream));
         if (!c.direct_cnt) {
@@ -1413,11 +1427,7 @@ int mpm_chain_direct_connect(mpm_handle_t e, const char left_handle[64], const c
     REQUIRE(c.direct_base, "mpm_chain_direct_prepare first");
     const char* hs[2] = {left_handle, right_handle};
     const int nbr[2] = {c.left, c.right};
-    for (int k = 0; k < 2; ++k) {
-        if (c.peer_mapped[k] && c.peer_base[k] && !(k == 1 && c.peer_base[1] == c.peer_base[0])) (void)hipIpcCloseMemHandle(c.peer_base[k]);
-        c.peer_base[k] = nullptr;
-        c.peer_mapped[k] = false;
-    }
+    chain_unmap_peers(c);
     const bool foreign = (c.left >= 0 && c.left != c.rank) || (c.right >= 0 && c.right != c.rank);
     if (foreign && !left_handle && !right_handle) {   // switched off again: the chain is RCCL's (or nobody's) once more
         c.direct = false;
@@ -1467,10 +1477,7 @@ int mpm_chain_direct_connect_local(mpm_handle_t e, void* left_base, void* right_
     mpm_engine::Chain& c = e->chain;
     REQUIRE(c.direct_base, "mpm_chain_direct_prepare first");
     REQUIRE((c.left < 0 || left_base) && (c.right < 0 || right_base), "missing region of a neighbour");
-    for (int k = 0; k < 2; ++k) {
-        if (c.peer_mapped[k] && c.peer_base[k] && !(k == 1 && c.peer_base[1] == c.peer_base[0])) (void)hipIpcCloseMemHandle(c.peer_base[k]);
-        c.peer_mapped[k] = false;
-    }
+    chain_unmap_peers(c);
     c.peer_base[0] = c.left >= 0 ? left_base : nullptr;
     c.peer_base[1] = c.right >= 0 ? right_base : nullptr;
     c.direct = true;
@@ -1501,7 +1508,6 @@ int mpm_team_prepare(mpm_handle_t e, size_t zone_capacity_blocks, char handle_ou
                 return fail(MPM_ERR_HIP, std::string("mpm_team_prepare: fine-grained device memory is not available (") + hipGetErrorString(fg) +
                                              "): the team transport needs it; the solve stays on the host-driven transports");
             HIP_TRY(hipMalloc(&t.base, bytes));
-            t.coarse = true;
         }
         HIP_TRY(hipMemsetAsync(t.base, 0, bytes, e->stream));
         HIP_TRY(hipMalloc((void**)&t.ts, sizeof(TeamState)));
@@ -1562,6 +1568,30 @@ static int chain_zones(const mpm_engine::Chain& c, int* lo, int* hi, int* sh) {
     if (c.right >= 0) { lo[nz] = c.zone_lo[1]; hi[nz] = c.zone_hi[1]; sh[nz] = -c.pitch; ++nz; }
     return nz;
 }
+// ... and a (left, right) pair of buffers in the same order
+static void chain_sides(const mpm_engine::Chain& c, void* left, void* right, void** out) {
+    int k = 0;
+    if (c.left >= 0) out[k++] = left;
+    if (c.right >= 0) out[k++] = right;
+}
+// One RCCL group with both neighbours: out_l / out_r bytes from send_l / send_r, in_l / in_r bytes into recv_l / recv_r (a
+// size of 0 leaves the call out).  What goes to the left arrives "from the right" over there: when both neighbours are the
+// same rank (a ring of one or two) the k-th send pairs with the k-th receive, so the receives are posted right-then-left
+// against sends left-then-right.
+static int chain_exchange(mpm_engine* e, const rccl_rt::Api* a, void* send_l, size_t out_l, void* send_r, size_t out_r, void* recv_l,
+                          size_t in_l, void* recv_r, size_t in_r) {
+    const mpm_engine::Chain& c = e->chain;
+    RCCL_TRY(a->group_start());
+    int rc_g = 0;
+    if (!rc_g && c.left >= 0 && out_l) rc_g = a->send(send_l, out_l, 0 /* ncclChar */, c.left, c.comm, e->stream);
+    if (!rc_g && c.right >= 0 && out_r) rc_g = a->send(send_r, out_r, 0, c.right, c.comm, e->stream);
+    if (!rc_g && c.right >= 0 && in_r) rc_g = a->recv(recv_r, in_r, 0, c.right, c.comm, e->stream);
+    if (!rc_g && c.left >= 0 && in_l) rc_g = a->recv(recv_l, in_l, 0, c.left, c.comm, e->stream);
+    const int rc_e = a->group_end();   // (always closes the group, also after a failed call)
+    RCCL_TRY(rc_g);
+    RCCL_TRY(rc_e);
+    return 0;
+}
 // lean: another substep of the same batch follows (see substep_begin_halo)
 static int chain_direct_begin(mpm_engine* e, float dt, bool lean) {
     mpm_engine::Chain& c = e->chain;
@@ -1620,10 +1650,11 @@ int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     const rccl_rt::Api* a = c.comm ? rccl_rt::api() : nullptr;
     REQUIRE(c.comm || c.mig_cap == 0, "migration needs the RCCL communicator (mpm_chain_init with an id)");
     // zones / buffers in the order (left, right), leaving out a missing neighbour
-    int lo[2], hi[2], sh[2], nz = 0;
+    int lo[2], hi[2], sh[2];
+    const int nz = chain_zones(c, lo, hi, sh);
     void *sb[2], *rb[2];
-    if (c.left >= 0) { lo[nz] = c.zone_lo[0]; hi[nz] = c.zone_hi[0]; sh[nz] = +c.pitch; sb[nz] = c.send_l; rb[nz] = c.recv_l; ++nz; }
-    if (c.right >= 0) { lo[nz] = c.zone_lo[1]; hi[nz] = c.zone_hi[1]; sh[nz] = -c.pitch; sb[nz] = c.send_r; rb[nz] = c.recv_r; ++nz; }
+    chain_sides(c, c.send_l, c.send_r, sb);
+    chain_sides(c, c.recv_l, c.recv_r, rb);
     for (int s = 0; s < n; ++s) {
         // Migration: every mig_every substeps, or (mig_every = 0, adaptive) when half of the time has passed in which,
         // by the ranks' common estimate, no particle can have drifted further than the bands allow (Dist::mig_delta).
@@ -1640,16 +1671,8 @@ int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
             // migration is a synchronisation point anyway (mpm_dist_migrate_apply).
             if (int rc = mpm_dist_migrate_pack(e, c.mig_send_l, c.mig_send_r, c.mig_cap)) return rc;
             auto exchange = [&](size_t out_l, size_t out_r, size_t in_l, size_t in_r, size_t offset) -> int {
-                RCCL_TRY(a->group_start());
-                int rc_g = 0;
-                if (!rc_g && c.left >= 0 && out_l) rc_g = a->send((char*)c.mig_send_l + offset, out_l, 0, c.left, c.comm, e->stream);
-                if (!rc_g && c.right >= 0 && out_r) rc_g = a->send((char*)c.mig_send_r + offset, out_r, 0, c.right, c.comm, e->stream);
-                if (!rc_g && c.right >= 0 && in_r) rc_g = a->recv((char*)c.mig_recv_r + offset, in_r, 0, c.right, c.comm, e->stream);
-                if (!rc_g && c.left >= 0 && in_l) rc_g = a->recv((char*)c.mig_recv_l + offset, in_l, 0, c.left, c.comm, e->stream);
-                const int rc_e = a->group_end();   // (always closes the group, also after a failed call)
-                RCCL_TRY(rc_g);
-                RCCL_TRY(rc_e);
-                return 0;
+                return chain_exchange(e, a, (char*)c.mig_send_l + offset, out_l, (char*)c.mig_send_r + offset, out_r,
+                                      (char*)c.mig_recv_l + offset, in_l, (char*)c.mig_recv_r + offset, in_r);
             };
             if (int rc = exchange(16, 16, 16, 16, 0)) return rc;
             if (c.mig_every == 0) {
@@ -1698,20 +1721,8 @@ int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
         c.mig_elapsed += dt;
         c.steps += 1;
         if (int rc = substep_begin_halo(e, dt, nz, lo, hi, sh, sb, c.cap, nullptr, lean)) return rc;
-        if (nz > 0) {
-            RCCL_TRY(a->group_start());
-            // what goes to the left arrives "from the right" over there: when both neighbours are the
-            // same rank (ring of one or two) the k-th send pairs with the k-th receive, so the receives
-            // are posted right-then-left against sends left-then-right
-            int rc_g = 0;
-            if (!rc_g && c.left >= 0) rc_g = a->send(c.send_l, c.bytes, 0 /* ncclChar */, c.left, c.comm, e->stream);
-            if (!rc_g && c.right >= 0) rc_g = a->send(c.send_r, c.bytes, 0, c.right, c.comm, e->stream);
-            if (!rc_g && c.right >= 0) rc_g = a->recv(c.recv_r, c.bytes, 0, c.right, c.comm, e->stream);
-            if (!rc_g && c.left >= 0) rc_g = a->recv(c.recv_l, c.bytes, 0, c.left, c.comm, e->stream);
-            const int rc_e = a->group_end();   // a failed call must not leave the group open
-            RCCL_TRY(rc_g);
-            RCCL_TRY(rc_e);
-        }
+        if (nz > 0)
+            if (int rc = chain_exchange(e, a, c.send_l, c.bytes, c.send_r, c.bytes, c.recv_l, c.bytes, c.recv_r, c.bytes)) return rc;
         if (int rc = substep_end_halo(e, dt, bc, nz, rb, c.cap, true, lean)) return rc;
     }
     HIP_TRY(hipGetLastError());
@@ -1735,18 +1746,9 @@ int mpm_grid_to_particle(mpm_handle_t e, float dt) try {
 
 int mpm_substep(mpm_handle_t e, float dt, int bc) try { return mpm_run_substeps(e, 1, dt, bc); } MPM_CATCH_ALL
 
-// The front of a batched substep, all from the launch's DP `p`: the re-sort launches when the substep is checked, FEM +
-// ParticleToGrid (the vertex forces inside it), the grid update.  The caller launches GridToParticle with the same DP.
-static void launch_substep_front(mpm_engine* e, const DP& p, float dt, const GridColliders& gc, bool check) {
-    if (check) launch_rebuild(e, p, true);
-    launch_fem_p2g(e, p, dt);
-    launch_grid(e, p, gc);
-}
-
 // allow_gate: the substep may go without the re-sort launches (mpm_run_substeps; settle_owed runs the owed ones with them)
 // lean: another substep follows in the same batch, GridToParticle need not refresh what only a download reads
 static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, bool allow_gate, bool lean) {
-    e->last_dt = dt;
     // Re-sort check launches: with every substep that may not skip itself; otherwise none while the quiet time that
     // the last re-sort estimated lasts (half of it: the estimate is ballistic, elastic forces are not in it), then
     // with every check_every-th substep.  A wrong guess costs time, not correctness: substeps that find a re-sort
@@ -1769,8 +1771,8 @@ static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, boo
     DP p = e->dp;
     p.gated = check ? 2 : 3;   // (bit 1: it also skips itself while the slab pool is too small, see DP::gated)
     p.lean_g2p = lean && !p.dist.on;   // (k_p2g: the forces stay in LDS; k_g2p: no face x / v records)
-    launch_substep_front(e, p, dt, gc, check);
-    launch_g2p(e, p, dt);
+    enqueue_substep_front(e, p, dt, check ? Resort::Lean : Resort::None);
+    enqueue_substep_rest(e, GridForm::Fused, p, gc, &p, dt);
 }
 
 int mpm_run_substeps(mpm_handle_t e, int n, float dt, int bc) try {
@@ -1784,7 +1786,6 @@ int mpm_run_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     e->owed_dt = dt;
     e->owed_bc = bc;
     e->owed_gcv = e->grid_colliders_version;
-    may_resort(e, dt);
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
     for (int s = 0; s < n; ++s) launch_substep(e, dt, gc, true, s + 1 < n);
@@ -1801,41 +1802,30 @@ int mpm_profile_substeps(mpm_handle_t e, int n, float dt, int bc, float* phase_m
     REQUIRE(n > 0 && n <= 4096, "n out of range");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
+    // (what mpm_run_substeps launches, with events between the phases; but every substep carries its re-sort launches, all
+    // of them, and none skips itself)
     const int NE = MPM_PHASE_COUNT + 1;
-    may_resort(e, dt);
-    std::vector<hipEvent_t> ev((size_t)n * NE);
-    for (auto& x : ev) HIP_TRY(hipEventCreate(&x));
-    for (int s = 0; s < n; ++s) {
-        hipEvent_t* q = &ev[(size_t)s * NE];
-        HIP_TRY(hipEventRecord(q[0], e->stream));
-        launch_rebuild(e, e->dp);
-        HIP_TRY(hipEventRecord(q[1], e->stream));
-        launch_fem_faces(e, e->dp, dt);
-        HIP_TRY(hipEventRecord(q[2], e->stream));
-        // (as in mpm_run_substeps: the vertex forces are part of k_p2g; this phase is empty -- but for an engine with
-        // bending stiffness, whose k_vforce and k_bend are timed here)
-        const bool vforce_phase = e->bend.on();   // (else k_vforce, where it runs at all, is part of the P2G phase as before)
-        if (vforce_phase) launch_fem_vertices(e, e->dp);
-        HIP_TRY(hipEventRecord(q[3], e->stream));
+    Events ev;
+    if (int rc = ev.create((size_t)n * NE)) return rc;
+    hipError_t err = hipSuccess;
+    for (int s = 0; s < n && err == hipSuccess; ++s) {
+        const hipEvent_t* q = &ev[(size_t)s * NE];
+        const PhaseMark mark = [&](int phase) {
+            if (err == hipSuccess) err = hipEventRecord(q[phase + 1], e->stream);
+        };
+        err = hipEventRecord(q[0], e->stream);
         DP p = e->dp;
         p.lean_g2p = s + 1 < n && !p.dist.on;   // (as in mpm_run_substeps)
-        {
-            const int forces = fused_forces(e);
-            if (!forces && !vforce_phase) launch_fem_vertices(e, p);
-            launch_p2g(e, p, dt, forces);
-        }
-        HIP_TRY(hipEventRecord(q[4], e->stream));
-        launch_grid(e, p, gc);
-        HIP_TRY(hipEventRecord(q[5], e->stream));
-        launch_g2p(e, p, dt);
-        HIP_TRY(hipEventRecord(q[6], e->stream));
+        enqueue_substep_front(e, p, dt, Resort::Full, mark);
+        enqueue_substep_rest(e, GridForm::Fused, p, gc, &p, dt, mark);
     }
+    if (err != hipSuccess) return fail(MPM_ERR_HIP, std::string("hipEventRecord: ") + hipGetErrorString(err));
     e->grid_state = 2;
     e->substeps += (uint64_t)n;
     HIP_TRY(hipStreamSynchronize(e->stream));
     double acc[MPM_PHASE_COUNT] = {}, tot = 0;
     for (int s = 0; s < n; ++s) {
-        hipEvent_t* q = &ev[(size_t)s * NE];
+        const hipEvent_t* q = &ev[(size_t)s * NE];
         for (int k = 0; k < MPM_PHASE_COUNT; ++k) {
             float ms = 0;
             HIP_TRY(hipEventElapsedTime(&ms, q[k], q[k + 1]));
@@ -1845,7 +1835,6 @@ int mpm_profile_substeps(mpm_handle_t e, int n, float dt, int bc, float* phase_m
         HIP_TRY(hipEventElapsedTime(&ms, q[0], q[MPM_PHASE_COUNT]));
         tot += ms;
     }
-    for (auto& x : ev) hipEventDestroy(x);
     if (phase_ms)
         for (int k = 0; k < MPM_PHASE_COUNT; ++k) phase_ms[k] = (float)(acc[k] / n);
     if (total_ms) *total_ms = (float)(tot / n);
@@ -2027,9 +2016,9 @@ __global__ __launch_bounds__(256) void k_dist_shift_slots(DP p, int old_nf, int 
 // slot the rank keeps the same information by original id, DP::fg / vg, and migration records carry it); a migration
 // that would overflow the slot space calls it again to GROW (mpm_dist_migrate_apply: the stream is idle there).  What
 // stays whole-scene sized is the id -> slot map and the slot-order bookkeeping (13 bytes per particle of the scene).
-static size_t dist_slot_capacity(const mpm_engine* e, size_t held, size_t all) {
-    if (!(e->dist_headroom > 0.f)) return all;   // (0: keep the whole scene's size)
-    return std::min(all, std::max<size_t>((size_t)((double)held * std::max(1.f, e->dist_headroom)) + 256, 1024));
+static size_t dist_slot_capacity(float headroom, size_t held, size_t all) {
+    if (!(headroom > 0.f)) return all;   // (0: keep the whole scene's size)
+    return std::min(all, std::max<size_t>((size_t)((double)held * std::max(1.f, headroom)) + 256, 1024));
 }
 // TWO-PHASE: phase 1 allocates every new array and touches nothing of the engine -- a failure there (device
 // memory exhausted) frees what phase 1 got and returns with the engine exactly as it was, still usable at its old size;
@@ -2059,19 +2048,12 @@ static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) 
     };
     std::vector<Plan> plans;
     plans.reserve(64);
-    const size_t allocs_before = e->allocs.size();
-    auto rollback = [&]() {
-        for (Plan& pl : plans) {
-            void* q = pl.fresh;
-            if (q) e->dfree(q);
-        }
-        (void)allocs_before;
-    };
+    FreshArrays fresh_arrays(e);   // (freed again unless phase 1 gets all of them)
     int rc = 0;
     auto plan = [&](auto*& ptr, size_t n_new, std::vector<Copy> keep_elems) -> int {
         using T = std::remove_pointer_t<std::remove_reference_t<decltype(ptr)>>;
         T* fresh = nullptr;
-        if (int r = e->dalloc(&fresh, n_new, true)) return r;
+        if (int r = fresh_arrays.alloc(&fresh, n_new, true)) return r;
         Plan pl;
         pl.owner = (void**)(&ptr);
         pl.fresh = (void*)fresh;
@@ -2115,13 +2097,13 @@ static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) 
     if (!rc) rc = plan(p.home_groups, new_np / 64 + p.capH + 2, {});
     if (rc) {
         const std::string why = g_last_error;
-        rollback();
         (void)hipStreamSynchronize(e->stream);
         return fail(rc, "dist_resize: " + why + " -- the rank keeps its slot space of " + std::to_string(p.Nf) + " + " +
                             std::to_string(p.Nv) + " slots and stays usable");
     }
 
     // ---- phase 2: copy, swap, free (no allocation from here on) ------------------------------------------------------
+    fresh_arrays.commit();
     for (Plan& pl : plans)
         for (const Copy& k : pl.keep)
             HIP_TRY(hipMemcpyAsync((char*)pl.fresh + k.dst_off, (const char*)*pl.owner + k.src_off, k.bytes,
@@ -2164,7 +2146,6 @@ static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) 
     H2D(e, &p.ctl->need_rebuild, &one, sizeof(int));
     e->dist_resizes += 1;
     if (!first) return 0;   // (a migration follows, and the re-sort that merges what it brings)
-    may_resort(e, 0.f);
     launch_rebuild(e, e->dp);
     D2H(e, &c, p.ctl, sizeof(Ctl));
     return recover_slab_overflow(e, c);
@@ -2262,11 +2243,9 @@ int mpm_dist_init(mpm_handle_t e, const mpm_dist_config_t* cfg) try {
     }
     hipLaunchKernelGGL(k_dist_build_topology, dim3(std::min(e->g_np, 2048u)), dim3(256), 0, e->stream, e->dp);
     e->dp.dist = d;
-    e->dist_cfg = *cfg;
     hipLaunchKernelGGL(k_dist_init_roles, dim3(e->g_np), dim3(256), 0, e->stream, e->dp);
     int one = 1;
     H2D(e, &e->dp.ctl->need_rebuild, &one, sizeof(int));
-    may_resort(e, 0.f);
     launch_rebuild(e, e->dp);
     {
         Ctl c;
@@ -2277,8 +2256,8 @@ int mpm_dist_init(mpm_handle_t e, const mpm_dist_config_t* cfg) try {
     {
         Ctl c;
         D2H(e, &c, e->dp.ctl, sizeof(Ctl));
-        if (int rc = dist_resize(e, dist_slot_capacity(e, (size_t)c.nfa, (size_t)e->dp.Nf),
-                                 dist_slot_capacity(e, (size_t)c.nva, (size_t)e->dp.Nv), true))
+        if (int rc = dist_resize(e, dist_slot_capacity(e->dist_headroom, (size_t)c.nfa, (size_t)e->dp.Nf),
+                                 dist_slot_capacity(e->dist_headroom, (size_t)c.nva, (size_t)e->dp.Nv), true))
             return rc;
     }
     return mpm_sync(e);
@@ -2403,15 +2382,11 @@ static int plan_migration(const uint32_t* hdr_left, const uint32_t* hdr_right, s
     // but never more than the scene has: a particle has one slot)
     m.need_f = std::min(scene_f, held_f + m.in_f);
     m.need_v = std::min(scene_v, held_v + m.in_v);
-    auto capacity_for = [&](size_t held, size_t all) {
-        if (!(headroom > 0.f)) return all;   // (0: keep the whole scene's size)
-        return std::min(all, std::max<size_t>((size_t)((double)held * std::max(1.f, headroom)) + 256, 1024));
-    };
     m.want_f = slots_f;
     m.want_v = slots_v;
     if (m.need_f > slots_f || m.need_v > slots_v) {
-        m.want_f = std::max(slots_f, capacity_for(m.need_f, scene_f));
-        m.want_v = std::max(slots_v, capacity_for(m.need_v, scene_v));
+        m.want_f = std::max(slots_f, dist_slot_capacity(headroom, m.need_f, scene_f));
+        m.want_v = std::max(slots_v, dist_slot_capacity(headroom, m.need_v, scene_v));
     }
     *out = m;
     return 0;
@@ -2626,10 +2601,7 @@ int mpm_set_body_contact_materials(mpm_handle_t e, size_t n, const mpm_contact_m
 int mpm_get_body_contact_materials(mpm_handle_t e, mpm_contact_material_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
     REQUIRE(capacity == 0 || out, "null argument");
-    const std::vector<mpm_contact_material_t>& m = e->cb.materials;
-    std::copy(m.begin(), m.begin() + (long)std::min(capacity, m.size()), out);
-    if (n_out) *n_out = m.size();
-    return 0;
+    return copy_out(e->cb.materials, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_sdf_collider_signed_distance(mpm_handle_t e, const mpm_sdf_collider_t* c, size_t n, const float* x_W, float* phi_out,
@@ -2751,10 +2723,8 @@ static int team_coupled_substeps(const std::vector<mpm_engine*>& L, int n, const
     if (int rc = grid_colliders_for(L[0], prm->mpm_bc, &gc)) return rc;
     const SolveParams solve = solve_params(prm);
     for (int s = 0; s < n; ++s) {
-        for (mpm_engine* e : L) {
-            may_resort(e, dt);
+        for (mpm_engine* e : L)
             if (int rc = chain_direct_begin(e, dt, false)) return rc;
-        }
         for (mpm_engine* e : L)
             if (int rc = chain_direct_end(e, dt, prm->mpm_bc, false, false)) return rc;
         for (mpm_engine* e : L)
@@ -2840,38 +2810,33 @@ static int coupled_substep(mpm_engine* e, int s, int n, const mpm_coupled_params
     *done = 0;
     auto t0 = clk::now();
     const bool gate = !sp->force_check && (e->ct_gate_always || e->quiet_factor * e->ct_quiet_left > 2.f * dt);
-    may_resort(e, dt);
     DP p = e->dp;
     p.gated = gate ? 1 : 0;
     p.lean_g2p = s + 1 < n;
-    int rc = 0, iters = 0;
+    int iters = 0;
     float residual = 0.f;
     bool g2p_done = false;
-    {
-        // the pair generation and the contact solve read the gate from the engine's DP: set for them, and cleared
-        // however this block is left
-        struct GateOff {
-            mpm_engine* e;
-            ~GateOff() { e->dp.gated = 0; }
-        } gate_off{e};
-        e->dp.gated = p.gated;
-        launch_substep_front(e, p, dt, gc, !gate);
-        sp->force_check = false;
-        e->grid_state = 2;
-        t->base += since(t0); t0 = clk::now();
-        rc = generate_contacts(e, n_colliders, colliders, nullptr);
-        t->gen += since(t0); t0 = clk::now();
-        e->last_contact_gated = false;
-        if (!rc && (e->cb.dev_counted || e->cb.n > 0))
-            rc = update_contact(e, 0, s, solve_params(prm), 0, &iters, &residual, [&](size_t) {
+    enqueue_substep_front(e, p, dt, gate ? Resort::None : Resort::Lean);
+    enqueue_substep_rest(e, GridForm::Fused, p, gc, nullptr, dt);   // (GridToParticle: inside the solve, or below)
+    sp->force_check = false;
+    e->grid_state = 2;
+    t->base += since(t0); t0 = clk::now();
+    // (the pair generation's kernels do not read the gate: its pairs are refused with the solve, k_ct_keys)
+    if (int rc = generate_contacts(e, n_colliders, colliders, nullptr)) return rc;
+    t->gen += since(t0); t0 = clk::now();
+    e->last_contact_gated = false;
+    if (e->cb.dev_counted || e->cb.n > 0) {
+        SolveParams solve = solve_params(prm);
+        solve.gated = p.gated;
+        if (int rc = update_contact(e, 0, s, solve, 0, &iters, &residual, [&](size_t) {
                 launch_g2p(e, p, dt);
                 g2p_done = true;
-            });
-        else if (!rc)
-            e->last_contact = mpm_contact_stats_t{};
-        t->solve += since(t0); t0 = clk::now();
+            }))
+            return rc;
+    } else {
+        e->last_contact = mpm_contact_stats_t{};
     }
-    if (rc) return rc;
+    t->solve += since(t0); t0 = clk::now();
     if (!g2p_done) launch_g2p(e, p, dt);
     t->tail += since(t0);
     if (e->last_contact_gated) {
@@ -2916,13 +2881,12 @@ static int coupled_chunk(mpm_engine* e, int s, int n, float dt, const GridCollid
     for (int q = 0; q < m; ++q) {
         const bool unchecked = quiet > 2.f * dt;
         quiet -= dt;
-        may_resort(e, dt);
         DP p = e->dp;
         p.gated = 4 | (unchecked ? 1 : 0);
         p.watch_base = sp->watch_base;
         p.lean_g2p = s + q + 1 < n;
-        launch_substep_front(e, p, dt, gc, !unchecked);
-        launch_g2p(e, p, dt);
+        enqueue_substep_front(e, p, dt, unchecked ? Resort::None : Resort::Lean);
+        enqueue_substep_rest(e, GridForm::Fused, p, gc, &p, dt);
         launch_contact_watch(e, p, ++e->watch_seq);
     }
     e->grid_state = 2;
@@ -2946,7 +2910,8 @@ static int coupled_chunk(mpm_engine* e, int s, int n, float dt, const GridCollid
         e->last_contact = mpm_contact_stats_t{};
         e->last_contact_reused = false;
     }
-    sp->spec_quiet_left = c.need_rebuild || c.error ? 0.f : quiet_hint(e, std::max(0.f, c.quiet_time - c.time_since_resort));
+    // (a non-zero c.skipped sets spec_check, which discards the value, or comes with a hit, which ends the speculation)
+    sp->spec_quiet_left = quiet_hint(e, quiet_time_left(c));
     sp->spec_check = skipped > 0;   // (whatever made them skip: the repeated ones carry their checks)
     // (an error flag ends the speculation too: the coupled substep that follows reports it where it always was)
     if (hit || c.error) {
@@ -3008,46 +2973,38 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
     return 0;
 } MPM_CATCH_ALL
 
+}  // extern "C"
+
 // The root finder of the exact line search behind a C callback, for the known-answer tests
 // (host code only: no device is touched).
-int mpm_newton_bisect_f64(mpm_rootfind_fn fn, void* user, double x_lo, double x_hi, double guess, double x_tol,
-                          double f_tol, int max_evals, int flags, double* root_out, int* evals_out) try {
-    REQUIRE(fn && root_out && evals_out, "null argument");
-    REQUIRE(x_lo < x_hi && x_lo <= guess && guess <= x_hi && x_tol > 0 && f_tol > 0, "bad bracket / tolerances");
-    double f_lo, f_hi, d;
-    fn(user, x_lo, &f_lo, &d);
-    fn(user, x_hi, &f_hi, &d);
-    RootFinder<double> rf;
-    rf.start(x_lo, f_lo, x_hi, f_hi, guess, x_tol, f_tol, max_evals, flags);
-    while (rf.status == 0) {
-        double f, df;
-        fn(user, rf.root, &f, &df);
-        rf.feed(f, df);
-    }
-    *root_out = rf.root;
-    *evals_out = rf.evals;
-    return rf.status == 1 ? 0 : 1;
-} MPM_CATCH_ALL
-
-int mpm_newton_bisect_f32(mpm_rootfind_fn fn, void* user, float x_lo, float x_hi, float guess, float x_tol,
-                          float f_tol, int max_evals, int flags, float* root_out, int* evals_out) try {
+template <class T>
+static int newton_bisect(mpm_rootfind_fn fn, void* user, T x_lo, T x_hi, T guess, T x_tol, T f_tol, int max_evals, int flags,
+                         T* root_out, int* evals_out) {
     REQUIRE(fn && root_out && evals_out, "null argument");
     REQUIRE(x_lo < x_hi && x_lo <= guess && guess <= x_hi && x_tol > 0 && f_tol > 0, "bad bracket / tolerances");
     double f_lo, f_hi, d;
     fn(user, (double)x_lo, &f_lo, &d);
     fn(user, (double)x_hi, &f_hi, &d);
-    RootFinder<float> rf;
-    rf.start(x_lo, (float)f_lo, x_hi, (float)f_hi, guess, x_tol, f_tol, max_evals, flags);
+    RootFinder<T> rf;
+    rf.start(x_lo, (T)f_lo, x_hi, (T)f_hi, guess, x_tol, f_tol, max_evals, flags);
     while (rf.status == 0) {
         double f, df;
         fn(user, (double)rf.root, &f, &df);
-        rf.feed((float)f, (float)df);
+        rf.feed((T)f, (T)df);
     }
     *root_out = rf.root;
     *evals_out = rf.evals;
     return rf.status == 1 ? 0 : 1;
+}
+extern "C" {
+int mpm_newton_bisect_f64(mpm_rootfind_fn fn, void* user, double x_lo, double x_hi, double guess, double x_tol, double f_tol,
+                          int max_evals, int flags, double* root_out, int* evals_out) try {
+    return newton_bisect(fn, user, x_lo, x_hi, guess, x_tol, f_tol, max_evals, flags, root_out, evals_out);
 } MPM_CATCH_ALL
-
+int mpm_newton_bisect_f32(mpm_rootfind_fn fn, void* user, float x_lo, float x_hi, float guess, float x_tol, float f_tol,
+                          int max_evals, int flags, float* root_out, int* evals_out) try {
+    return newton_bisect(fn, user, x_lo, x_hi, guess, x_tol, f_tol, max_evals, flags, root_out, evals_out);
+} MPM_CATCH_ALL
 }  // extern "C"
 
 // ---- fixed constraints (mpm_set_pins, mpm_set_body_motions, mpm_pins_inside_collider, mpm_get_pins) --------------------
@@ -3070,11 +3027,17 @@ static bool is_rotation(const float* R) {
                        (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
     return std::fabs(det - 1.0) <= 1e-4;
 }
-static bool multi_rank(const mpm_engine* e) { return e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on; }
+// pins, grid bodies, force fields and bending stiffness are refused on a partitioned or multi-rank engine (out of scope);
+// what_is: "pins are", "bending stiffness is", ...
+static int single_engine_only(const mpm_engine* e, const char* what_is) {
+    if (e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on)
+        return fail(MPM_ERR_INVALID, std::string(what_is) + " not available on a partitioned or multi-rank engine");
+    return 0;
+}
 
 int mpm_set_pins(mpm_handle_t e, size_t n, const mpm_pin_t* pins) try {
     READY(e);
-    REQUIRE(!multi_rank(e), "pins are not available on a partitioned or multi-rank engine");
+    if (int rc = single_engine_only(e, "pins are")) return rc;
     REQUIRE(n == 0 || pins, "null pin array");
     std::vector<uint8_t> seen(e->nv, 0);
     for (size_t k = 0; k < n; ++k) {
@@ -3090,7 +3053,7 @@ int mpm_set_pins(mpm_handle_t e, size_t n, const mpm_pin_t* pins) try {
 
 int mpm_set_body_motions(mpm_handle_t e, size_t n, const mpm_body_motion_t* m) try {
     READY(e);
-    REQUIRE(!multi_rank(e), "pins are not available on a partitioned or multi-rank engine");
+    if (int rc = single_engine_only(e, "pins are")) return rc;
     REQUIRE(n == 0 || m, "null motion array");
     std::unordered_set<uint32_t> bodies;
     for (size_t k = 0; k < n; ++k) {
@@ -3139,7 +3102,7 @@ int mpm_set_body_motions(mpm_handle_t e, size_t n, const mpm_body_motion_t* m) t
 int mpm_pins_inside_collider(mpm_handle_t e, const mpm_collider_t* shape, uint32_t body, const float p_WB[3],
                              const float R_WB[9], size_t* n_added) try {
     READY(e);
-    REQUIRE(!multi_rank(e), "pins are not available on a partitioned or multi-rank engine");
+    if (int rc = single_engine_only(e, "pins are")) return rc;
     REQUIRE(shape && p_WB && R_WB, "null argument");
     REQUIRE(finite_n(p_WB, 3), "body pose not finite");
     REQUIRE(is_rotation(R_WB), "R_WB is not a rotation");
@@ -3173,10 +3136,7 @@ int mpm_pins_inside_collider(mpm_handle_t e, const mpm_collider_t* shape, uint32
 int mpm_get_pins(mpm_handle_t e, mpm_pin_t* out, size_t capacity, size_t* n_out) try {
     READY(e);
     REQUIRE(out || capacity == 0, "null output");
-    const std::vector<mpm_pin_t>& set = e->pin.set;
-    std::copy(set.begin(), set.begin() + std::min(capacity, set.size()), out);
-    if (n_out) *n_out = set.size();
-    return 0;
+    return copy_out(e->pin.set, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 // ---- rigid bodies of the grid update (mpm_set_grid_bodies, mpm_get_grid_bodies; k_grid_bodies in mpm_grid_bodies.h) ----
@@ -3210,7 +3170,7 @@ static float grid_body_bound(const mpm_grid_body_t& b, const SdfShape* sh) {
 int mpm_set_grid_bodies(mpm_handle_t e, size_t n, const mpm_grid_body_t* bodies) try {
     static_assert(sizeof(Collider) == sizeof(mpm_collider_t), "collider layouts differ");
     READY_NO_SETTLE(e);
-    REQUIRE(!multi_rank(e), "grid bodies are not available on a partitioned or multi-rank engine");
+    if (int rc = single_engine_only(e, "grid bodies are")) return rc;
     REQUIRE(n <= (size_t)MAX_GRID_COLLIDERS, "too many grid bodies (at most 16)");
     REQUIRE(n == 0 || bodies, "null grid body array");
     for (size_t k = 0; k < n; ++k) {
@@ -3272,10 +3232,7 @@ int mpm_set_grid_bodies(mpm_handle_t e, size_t n, const mpm_grid_body_t* bodies)
 int mpm_get_grid_bodies(mpm_handle_t e, mpm_grid_body_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
     REQUIRE(out || capacity == 0, "null output");
-    const std::vector<mpm_grid_body_t>& set = e->grid_bodies;
-    std::copy(set.begin(), set.begin() + std::min(capacity, set.size()), out);
-    if (n_out) *n_out = set.size();
-    return 0;
+    return copy_out(e->grid_bodies, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 // ---- external force fields (mpm_set_force_fields, mpm_get_force_fields, mpm_force_field_acceleration; mpm_fields.h) ----
@@ -3300,7 +3257,7 @@ extern "C" {
 
 int mpm_set_force_fields(mpm_handle_t e, size_t n, const mpm_force_field_t* fields) try {
     READY_NO_SETTLE(e);
-    REQUIRE(!multi_rank(e), "force fields are not available on a partitioned or multi-rank engine");
+    if (int rc = single_engine_only(e, "force fields are")) return rc;
     if (int rc = validate_force_fields(n, fields)) return rc;
     // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
     if (int rc = settle(e)) return rc;
@@ -3325,10 +3282,7 @@ int mpm_set_force_fields(mpm_handle_t e, size_t n, const mpm_force_field_t* fiel
 int mpm_get_force_fields(mpm_handle_t e, mpm_force_field_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
     REQUIRE(out || capacity == 0, "null output");
-    const std::vector<mpm_force_field_t>& set = e->force_fields;
-    std::copy(set.begin(), set.begin() + std::min(capacity, set.size()), out);
-    if (n_out) *n_out = set.size();
-    return 0;
+    return copy_out(e->force_fields, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 // host code only: no device is touched
@@ -3371,7 +3325,7 @@ int mpm_bending_matrix(const float* pos, size_t n_verts, const int32_t* indices,
 
 int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try {
     READY_NO_SETTLE(e);
-    REQUIRE(!multi_rank(e), "bending stiffness is not available on a partitioned or multi-rank engine");
+    if (int rc = single_engine_only(e, "bending stiffness is")) return rc;
     REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_bending: n_cloths must be mpm_cloth_count (or 0: off)");
     REQUIRE(n_cloths == 0 || stiffness, "null stiffness array");
     bool any = false;
@@ -3434,6 +3388,7 @@ int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try
     if (int rc = settle(e)) return rc;
     float max_dt = INFINITY;
     mpm_engine::Bending next;
+    FreshArrays fresh(e);   // (a failure below changes nothing: the new buffers go, the table in force stays)
     if (n_rows) {
         // m_i: the mass ParticleToGrid forms for the vertex particle (q[0].w x DP::M.density, both floats)
         std::vector<float> vol(e->nv);
@@ -3453,22 +3408,13 @@ int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try
         int* d_row = nullptr;
         unsigned* d_off = nullptr;
         float2* d_ent = nullptr;
-        if (int rc = e->dalloc(&d_row, n_rows, false)) return rc;
-        if (int rc = e->dalloc(&d_off, n_slices + 1, false)) { e->dfree(d_row); return rc; }
-        if (int rc = e->dalloc(&d_ent, ent.size(), false)) { e->dfree(d_row); e->dfree(d_off); return rc; }
+        if (int rc = fresh.alloc(&d_row, n_rows, false)) return rc;
+        if (int rc = fresh.alloc(&d_off, n_slices + 1, false)) return rc;
+        if (int rc = fresh.alloc(&d_ent, ent.size(), false)) return rc;
         // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
-        auto upload = [&]() -> int {
-            H2D(e, d_row, row_pid.data(), n_rows * sizeof(int));
-            H2D(e, d_off, slice_off.data(), (n_slices + 1) * sizeof(unsigned));
-            if (!ent.empty()) H2D(e, d_ent, ent.data(), ent.size() * sizeof(float2));
-            return 0;
-        };
-        if (int rc = upload()) {   // (nothing changed: the new buffers go, the table in force stays)
-            e->dfree(d_row);
-            e->dfree(d_off);
-            e->dfree(d_ent);
-            return rc;
-        }
+        H2D(e, d_row, row_pid.data(), n_rows * sizeof(int));
+        H2D(e, d_off, slice_off.data(), (n_slices + 1) * sizeof(unsigned));
+        if (!ent.empty()) H2D(e, d_ent, ent.data(), ent.size() * sizeof(float2));
         next.args = BendArgs{d_row, d_off, d_ent, (int)n_rows};
     } else {
         HIP_TRY(hipStreamSynchronize(e->stream));
@@ -3485,16 +3431,16 @@ int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try
     next.k.assign(stiffness, stiffness + n_cloths);
     next.max_dt = max_dt;
     e->bend = next;
+    fresh.commit();
     return 0;
 } MPM_CATCH_ALL
 
 int mpm_get_bending(mpm_handle_t e, float* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
     REQUIRE(out || capacity == 0, "null output");
-    const size_t n = e->cloths.size();
-    for (size_t c = 0; c < std::min(capacity, n); ++c) out[c] = c < e->bend.k.size() ? e->bend.k[c] : 0.f;
-    if (n_out) *n_out = n;
-    return 0;
+    std::vector<float> k = e->bend.k;   // (one entry per cloth; 0 where nothing was set)
+    k.resize(e->cloths.size(), 0.f);
+    return copy_out(k, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_bending_forces(mpm_handle_t e, float* f_out) try {

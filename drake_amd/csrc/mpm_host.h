@@ -87,6 +87,7 @@ constexpr size_t MAX_CLOTH_MATERIALS = 256;
 struct SolveParams {
     float dt = 0.f, mu = 0.f, stiffness = 0.f, damping = 0.f;
     int exact = 0, max_iters = 0;
+    int gated = 0;   // DP::gated of the coupled substep the solve belongs to (k_ct_keys reads its verdict); 0: none
     SolveParams() = default;
     SolveParams(float dt, float mu, float stiffness, float damping, int exact, int max_iters)
         : dt(dt), mu(mu), stiffness(stiffness), damping(damping), exact(exact), max_iters(max_iters > 0 ? max_iters : 2000) {}   // cuda_mpm_solver.cu:234
@@ -113,6 +114,8 @@ struct mpm_engine {
     bool multi_mat = false;             // some cloth came with a material of its own: k_fem_mat, q[0].w holds the mass
     ClothMat* d_cloth_mat = nullptr;    // [cloth] k_fem_mat's table (multi-material engines)
     std::vector<float> h_rho_of_pid;    // [original particle id] the density of its cloth (multi-material engines)
+    // Per-launch fields (gated, lean_g2p, lean_resort, watch_base, anticip, every halo_* field) keep mpm_finalize's values
+    // for the engine's life: a launch that needs one sets it in a copy of its own (launch_rebuild, enqueue_substep_*).
     DP dp{};
     std::vector<void*> allocs;
     std::vector<size_t> alloc_bytes;   // (parallel to allocs)
@@ -179,7 +182,6 @@ struct mpm_engine {
         float direct_timeout_s = 5.f;
         bool direct_mute = false;   // MPM_HALO_DEBUG_MUTE (tests): the signal kernel is left out
         uint32_t* direct_cnt = nullptr;   // [2] entry counters of the two zones a substep packs, in THIS device's memory
-        bool direct_coarse = false;       // the region is NOT fine-grained (MPM_DIRECT_COARSE_OK=1: one-device rehearsals only)
     } chain;
     // TEAM transport of the distributed contact solve (mpm_team.h, mpm_team_prepare / _connect): this rank's region, every
     // rank's region as mapped here, the device-side exchange counters
@@ -191,7 +193,6 @@ struct mpm_engine {
         bool mapped[TEAM_MAX] = {};           // ... through hipIpcOpenMemHandle (else: a pointer of this process)
         size_t zone_cap = 0, zone_bytes = 0;
         TeamState* ts = nullptr;
-        bool coarse = false;                  // NOT fine-grained (MPM_DIRECT_COARSE_OK=1: one-device rehearsals only)
         float timeout_s = 5.f;
     } team;
     bool halo_mid_done = false;   // mpm_substep_mid_halo ran in this substep
@@ -229,14 +230,12 @@ struct mpm_engine {
         bool table_dirty = false;                // d_pins is not `set` yet (resolved at the next substep entry point)
     } pin;
     int max_valence = 0;       // most faces around one vertex of the mesh (Finalize): above 8, k_vforce stays (see fused_forces)
-    int last_tile_kernel = 0;  // 1 = P2G, 2 = G2P (see launch_p2g)
     // launch geometry
     unsigned g_np = 0, g_nf = 0, g_nv = 0, g_tile = 0, g_grid = 0;
     // contacts / rigid bodies
     ContactBuffers cb{};
     mpm_contact_stats_t last_contact{};   // of the last mpm_update_contact
     bool last_contact_on_device = false;  // ... of which only what the mailbox carries has reached the host (contact_stats_from_device)
-    bool last_contact_exact = false;
     bool last_contact_gated = false;      // ... skipped itself with its whole substep (CT_DONE_GATED)
     float ct_quiet_left = 0.f;            // Ctl::quiet_time left as of the last solve's publication
     bool last_contact_reused = false;     // ... ran on the previous solve's sorted order and node list (settled scene)
@@ -254,7 +253,6 @@ struct mpm_engine {
     unsigned watch_seq = 0;                          // number of the last k_ct_watch launch (Ctl::watch_hit)
     bool ct_no_watch = getenv("MPM_CT_NO_WATCH") != nullptr;   // every coupled substep generates pairs and solves (A/B, tests)
     SolveParams last_contact_prm;   // its parameters
-    mpm_dist_config_t dist_cfg{};         // partitioned domain (mpm_dist_init)
     // slot space of a partitioned rank = headroom x what it holds (mpm_dist_set_headroom, MPM_DIST_HEADROOM; 0 = the whole
     // scene's size, no shrink); grown at the migration that would overflow it (dist_resize)
     float dist_headroom = getenv("MPM_DIST_HEADROOM") ? std::max(0.f, (float)atof(getenv("MPM_DIST_HEADROOM"))) : 1.5f;
@@ -292,6 +290,9 @@ struct mpm_engine {
     bool poison() const { return poison_fill; }
     // MPM_ANTICIPATE: horizon (substeps) of the re-sort's anticipatory binning (launch_rebuild)
     float anticipate_horizon = getenv("MPM_ANTICIPATE") ? (float)atof(getenv("MPM_ANTICIPATE")) : 32.f;
+    // ... in cells, over that many substeps of the last known length (not in a partitioned domain, where ownership and
+    // ghost bands are defined by the position itself)
+    float anticipation() const { return dp.dist.on ? 0.f : anticipate_horizon * last_dt * dp.dxinv; }
     // MPM_CT_EAGER=1: the contact solve applies every accepted step with a kernel of its own (update_contact)
     bool ct_eager = getenv("MPM_CT_EAGER") != nullptr;
     // MPM_CT_RELAX: Jacobi relaxation of the contact solve instead of the reference's 0.3 (tests: overshoot on purpose)
@@ -366,6 +367,49 @@ struct mpm_engine {
 
 static int use(mpm_engine* e) {
     HIP_TRY(hipSetDevice(e->device));
+    return 0;
+}
+
+// Fresh device arrays that replace something the engine holds: freed again unless the caller commits them ("all new
+// arrays or none": mpm_set_bending, dist_resize).  Allocation itself is the engine's dalloc.
+struct FreshArrays {
+    mpm_engine* e;
+    std::vector<void*> got;
+    explicit FreshArrays(mpm_engine* e) : e(e) {}
+    FreshArrays(const FreshArrays&) = delete;
+    ~FreshArrays() { for (void* q : got) e->dfree(q); }
+    template <class T>
+    int alloc(T** out, size_t n, bool zero) {
+        if (int rc = e->dalloc(out, n, zero)) return rc;
+        got.push_back((void*)*out);
+        return 0;
+    }
+    void commit() { got.clear(); }
+};
+
+// hipEvents of a measurement, destroyed however the function is left
+struct Events {
+    std::vector<hipEvent_t> ev;
+    Events() = default;
+    Events(const Events&) = delete;
+    ~Events() { for (hipEvent_t x : ev) (void)hipEventDestroy(x); }
+    int create(size_t n) {
+        for (ev.reserve(n); ev.size() < n;) {
+            hipEvent_t x;
+            HIP_TRY(hipEventCreate(&x));
+            ev.push_back(x);
+        }
+        return 0;
+    }
+    const hipEvent_t& operator[](size_t k) const { return ev[k]; }
+};
+
+// The getters of the caller's tables (pins, grid bodies, force fields, body contact materials): as many entries as fit,
+// and the whole count (each getter checks its own arguments first)
+template <class T>
+static int copy_out(const std::vector<T>& set, T* out, size_t capacity, size_t* n_out) {
+    std::copy(set.begin(), set.begin() + (long)std::min(capacity, set.size()), out);
+    if (n_out) *n_out = set.size();
     return 0;
 }
 

@@ -110,7 +110,7 @@ typedef enum {
 enum {
     MPM_PHASE_REBUILD = 0,
     MPM_PHASE_FEM = 1,     /* per-face kernel of CalcFemStateAndForce */
-    MPM_PHASE_VFORCE = 2,  /* its per-vertex force gather */
+    MPM_PHASE_VFORCE = 2,  /* its per-vertex force gather, whenever that is a launch of its own (see mpm_profile_substeps) */
     MPM_PHASE_P2G = 3,
     MPM_PHASE_GRID = 4,
     MPM_PHASE_G2P = 5,
@@ -806,7 +806,10 @@ MPM_API int mpm_bending_matrix(const float *pos, size_t n_verts, const int32_t *
 
 /* Runs n substeps with HIP events around every kernel group on the engine's
  * stream and returns the mean milliseconds per substep of each phase
- * (phase_ms[MPM_PHASE_COUNT]) and of the whole substep. */
+ * (phase_ms[MPM_PHASE_COUNT]) and of the whole substep.  The launches are those of mpm_run_substeps, but every substep
+ * carries its re-sort launches and none skips itself.  MPM_PHASE_VFORCE is the vertex-force kernel (and the bending
+ * kernel behind it) wherever the engine launches it -- a mesh with a vertex of more than eight faces, an engine with
+ * bending stiffness --; on every other engine ParticleToGrid sums the vertex forces itself and the phase is empty. */
 MPM_API int mpm_profile_substeps(mpm_handle_t h, int n, float dt, int mpm_bc, float *phase_ms, float *total_ms);
 
 /* ---- multi-GPU: one engine per GPU, domains tiled along x ------------------
