@@ -1,0 +1,855 @@
+"""The partitioned domain's per-particle state machine (drake_amd/csrc/mpm_dist.h: k_dist_init_roles, k_dist_classify,
+dist_emit, k_dist_apply, k_dist_mig_reduce; the predicates dist_in_my_band / dist_in_neighbour_bands of mpm_device.h; the
+host rules mpm_dist_init, mpm_dist_retune and plan_migration of mpm_engine.hip) restated on the host, and particle
+layouts that put particles ON every threshold of it and move them across the cuts in both directions.  CPU only:
+nothing here imports the engine.
+
+The rule (as mpm_dist.h states it)
+----------------------------------
+One domain is cut into x slabs at block boundaries; rank r owns the base cells [own_lo, own_hi).  Everything is decided
+from ONE float per particle: xi = float32(x 2^bits - 1/2) (2^bits is a power of two, so this is a single rounding whether
+the device fuses it or not), and from its base cell bx = min(max(0, trunc(xi)), 2^bits - 3).  Per rank and original id
+the device keeps a role (0 not here, 1 owned, 2 ghost) and two bits `prev` (bit 0 / 1: "was inside the band in which the
+left / right neighbour keeps ghosts at the last migration"); w is the band width of the particle's kind (ghost_w for a
+face particle, vert_w for a vertex particle) and h the hysteresis; every threshold is formed in float32 in the
+kernel's order, e.g. float32(own_hi) + float32(w + h).
+
+init      role = owned if own_lo <= bx < own_hi; else ghost if (left: bx < own_lo and xi >= own_lo - w; right:
+          bx >= own_hi and xi < own_hi + w); else 0.  prev = the two band bits (below, without h) of an owned particle.
+classify  an OWNED particle
+            with xi < own_lo - h (left) or xi >= own_hi + h (right) changes owner: a record with role OWNED goes to
+            that neighbour; here it becomes a ghost if it is inside this rank's band (the init test, WITHOUT h), else
+            it is released; prev = 0.  A base cell beyond the neighbour's slab raises the halo flag.
+            otherwise its band bits are re-evaluated: left bit = xi < own_lo + (w + (h if the bit was set)), right bit
+            = xi >= own_hi - (w + (h if the bit was set)); a bit that turns on sends a record with role GHOST to that
+            side, one that stays on sends nothing, prev = the new bits.
+          a GHOST whose base cell is inside the slab waits for its owner's record; one outside stays while the init
+          test WITH w + h holds, else it is released.
+          Records are (original id, role, ...): the buffers' headers count records and, of those, faces; a buffer that
+          is too small raises the capacity flag and the header still counts every record.  A release forces the re-sort.
+apply     per record: a particle the rank has no slot for is appended (a slot lasts from the re-sort that merged the
+          particle to the re-sort after its release); one it has a slot for is overwritten in place.  The role is the
+          record's; a record with role OWNED clears prev.  Any record forces the re-sort.
+So after a handover prev is 0 on both sides, and the new owner, at the next migration, finds the particle inside the old
+owner's band with its bit clear: it announces the particle ONCE more (role GHOST) to the old owner, which already holds
+it as a ghost and overwrites it in place with the same state.  The restatement models that.
+
+Nothing in roles, records, headers, counts or flags is a tolerance; no case is excluded or ambiguous.
+
+Quiet time (Ctl::mig_quiet)
+---------------------------
+quiet_time(rank) = min over every particle the rank holds (ghosts included) of t = 2 d / (v + sqrt(v^2 + 2 a d)) in
+float64, d = mig_delta + max(far - mig_reach, 0), far = |xi - cut| for the nearer cut the rank has, v = |v_x| 2^bits,
+a = |g| 2^bits when gravity acts along x, else 0.  Every term is non-negative.  The kernel forms the same in float32;
+with u = 2^-24 its relative error is bounded, particle by particle, by
+
+    e_d = u (2 + far / d)      far (one rounding, u far absolute), far - mig_reach (u |far - mig_reach| <= u d), the sum d (u d)
+    disc = v v + (2 a) d       two products and a sum of non-negative terms: 2 u, plus e_d on the second term
+    sqrt                       (2 u + e_d) / 2 carried + 2 u (one ulp of the hardware square root)
+    den = v + sqrt             u more
+    2 d rcp(den)               e_d (numerator) + 2 u (one ulp of the hardware reciprocal) + u (the product)
+    total                      b = 1.5 e_d + 7 u = u (10 + 1.5 far / d)
+
+and the test allows K b with K = 2 as elsewhere in the suite: the engine's minimum must lie in
+[min_i t_i (1 - K b_i), min_i t_i (1 + K b_i)].  An infinite estimate (v = 0 and a = 0 for everything held, or nothing
+held) must be infinite on both sides.
+
+Layouts
+-------
+Small disconnected triangles (a face particle at the centroid of its three corners, edges of 0.4 - 0.6 cells), each
+translated rigidly from stage to stage, plus one still "gauge" triangle far from every cut whose longest edge is exactly
+0.625 cells (an axis-aligned edge between dyadic coordinates: its float32 length, and everything mpm_dist_init derives
+from it, is the same number on the host and in this module whatever the compiler fuses).  A layout is a list of stages
+(positions, velocities); stage 0 is what the ranks are partitioned with, every later stage is uploaded and followed by
+one migration.  `place_x` finds the float32 x whose xi is exactly a target and its neighbours: below 2^k, x 2^bits is
+coarser than xi, so "the float just below / above" means the nearest xi that some float32 x produces.
+
+    thresholds      for every cut, both sides, faces and vertices: xi at, just below and just above c -+ h (ownership),
+                    c -+ w (band edge), c -+ (w + h) (sticky edge), each band edge approached from outside (bit clear)
+                    and from inside (bit set), and c +- w met by a particle that changes owner (kept as a ghost or not),
+                    coming from next to the cut (bit set) and from outside the band (bit clear)
+    there_and_back  triangles cross a cut, stop and cross back in steps of at most mig_delta, from the left and (mirrored)
+                    from the right; others oscillate inside the hysteresis of a cut and of a band edge: no traffic
+    waves           a middle rank whose 64-lane groups feed both buffers, one, or none, senders not contiguous, partial
+                    last wave, a wave across the face / vertex boundary
+    promotion       records that overwrite a held ghost in place and records that are appended, in one buffer
+    retune          still particles; the bands are widened, then narrowed between migrations (mpm_dist_retune)
+    bulk            > 2048 x 256 active particles on one rank, > 256 x 256 records in one buffer (the grid-stride
+                    loops of k_dist_classify and k_dist_apply take a second trip)
+    quiet0/quiet2   velocities over four decades, gravity along x / not along x, a rank that holds nothing
+    contract_halo, contract_capacity   error codes (kept apart from the exact-protocol layouts)
+A vertex that is inside BOTH neighbours' bands of a middle rank does not exist in any geometry mpm_dist_init accepts (a
+middle slab is at least 8 zone_blocks cells wide, a band at most 4 zone_blocks - 2): that lane kind of `waves` is
+left out.
+"""
+import numpy as np
+
+F32 = np.float32
+U32 = 2.0 ** -24
+K = 2.0
+ROLE_OWNED, ROLE_GHOST = 1, 2
+ERR_CAPACITY, ERR_HALO = 2, 16
+INF32 = F32(np.inf)
+DT = 1e-3
+CLASSIFY_PASS = 2048 * 256     # mpm_dist_migrate_pack: min(blocks of the slot space, 2048) workgroups of 256
+APPLY_PASS = 256 * 256         # mpm_dist_migrate_apply: 256 workgroups of 256
+GAUGE_EDGE = 0.625             # cells: the longest edge of every layout's mesh
+
+
+def xi32(x, bits):
+    """xi = float32(x 2^bits - 1/2): one rounding"""
+    return (np.asarray(x, F32).astype(np.float64) * float(1 << bits) - 0.5).astype(F32)
+
+
+def cell_x(xi, bits):
+    return np.minimum(np.maximum(np.trunc(np.asarray(xi, F32)), 0), (1 << bits) - 3).astype(np.int64)
+
+
+# ---- mpm_dist_init's band rules ------------------------------------------------------------------------------------
+def longest_edge_cells(rest, idx, bits):
+    """the host's float32 loop over the mesh as it was handed over"""
+    p = np.asarray(rest, F32)
+    best = F32(0)
+    for k in range(3):
+        d = p[idx[:, k]] - p[idx[:, (k + 1) % 3]]
+        s = (d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2]
+        best = max(best, F32(np.sqrt(s).max()))
+    return F32(best * F32(1 << bits))
+
+
+def band_rules(longest_edge, zone_blocks, ghost_cells, margin_cells, drift_target=0.5):
+    """-> dict: ghost_w, vert_w, hyst, mig_delta, mig_reach, reach, delta_max, auto (float32, mpm_dist_init's order)"""
+    longest_edge = F32(longest_edge)
+    reach = F32(0.75) * longest_edge
+    zone_room = F32(4 * zone_blocks - 2)
+    hyst = F32(0.125)
+    auto = ghost_cells == 0 and margin_cells == 0
+    two, three, one = F32(2), F32(3), F32(1)
+    if auto:
+        delta = min((zone_room - two * reach - two * hyst) / three, zone_room - one - hyst, F32(max(0.06, drift_target)))
+        ghost_w = reach + two * delta + hyst
+        vert_w = ghost_w + reach
+    else:
+        ghost_w, vert_w = F32(ghost_cells), F32(ghost_cells + margin_cells)
+        if zone_room - vert_w < two * hyst:
+            hyst = F32(0)
+        delta = max(F32(0), min((ghost_w - reach - hyst) * F32(0.5), zone_room - vert_w - hyst, zone_room - one - hyst))
+    delta_max = min((zone_room - two * reach - two * hyst) / three, zone_room - one - hyst)
+    return dict(ghost_w=F32(ghost_w), vert_w=F32(vert_w), hyst=F32(hyst), mig_delta=F32(delta),
+                mig_reach=F32(vert_w + two * reach + one), reach=F32(reach), delta_max=F32(delta_max), auto=auto,
+                longest_edge=longest_edge)
+
+
+def rules_from_geometry(geo, zone_blocks, ghost_cells, margin_cells):
+    """the same from what dist_geometry() reports: hyst, reach and mig_reach follow mpm_dist_init's rules"""
+    r = band_rules(geo["longest_edge_cells"], zone_blocks, ghost_cells, margin_cells)
+    r.update(ghost_w=F32(geo["face_band_cells"]), vert_w=F32(geo["vertex_band_cells"]), mig_delta=F32(geo["drift_budget_cells"]))
+    r["mig_reach"] = F32(r["vert_w"] + F32(2) * r["reach"] + F32(1))
+    return r
+
+
+def slot_capacity(headroom, held, scene):
+    if not headroom > 0:
+        return scene
+    return min(scene, max(int(float(held) * max(1.0, float(F32(headroom)))) + 256, 1024))
+
+
+def plan(in_f, in_v, scene_f, scene_v, held_f, held_v, slots_f, slots_v, headroom=1.5):
+    """plan_migration: -> (need_f, need_v, want_f, want_v)"""
+    need_f, need_v = min(scene_f, held_f + in_f), min(scene_v, held_v + in_v)
+    want_f, want_v = slots_f, slots_v
+    if need_f > slots_f or need_v > slots_v:
+        want_f = max(slots_f, slot_capacity(headroom, need_f, scene_f))
+        want_v = max(slots_v, slot_capacity(headroom, need_v, scene_v))
+    return need_f, need_v, want_f, want_v
+
+
+# ---- the restatement ---------------------------------------------------------------------------------------------------
+class _Rank:
+    pass
+
+
+class MigrationModel:
+    """What every rank's device keeps: role and prev per original id, the held x and v_x, the slots, the band widths."""
+
+    def __init__(self, bits, cuts, zone_blocks, ghost_w, vert_w, hyst, mig_delta, mig_reach, n_faces, n_particles, *,
+                 reach=None, delta_max=None, auto=True, interval=16.0, safety=0.5, retune_on=True, gravity_cells=0.0):
+        self.bits, self.cuts, self.zone_blocks = bits, list(cuts), zone_blocks
+        self.world = len(cuts) - 1
+        self.nf, self.n = int(n_faces), int(n_particles)
+        self.hyst = F32(hyst)
+        self.reach = None if reach is None else F32(reach)
+        self.delta_max = None if delta_max is None else F32(delta_max)
+        self.auto, self.retune_on = bool(auto), bool(retune_on)
+        self.interval, self.safety = F32(max(2.0, interval)), F32(min(1.0, max(0.05, safety)))
+        self.gravity_cells = float(gravity_cells)     # |g| 2^bits when gravity acts along x, else 0
+        self.face = np.arange(self.n) < self.nf
+        N = 1 << bits
+        self.ranks = []
+        for r in range(self.world):
+            R = _Rank()
+            R.has_left, R.has_right = r > 0, r < self.world - 1
+            R.own_lo = cuts[r] * 4 if R.has_left else 0
+            R.own_hi = cuts[r + 1] * 4 if R.has_right else N
+            R.nbr_lo = cuts[r - 1] * 4 if r > 1 else 0
+            R.nbr_hi = cuts[r + 2] * 4 if r < self.world - 2 else N
+            R.ghost_w, R.vert_w, R.mig_delta, R.mig_reach = F32(ghost_w), F32(vert_w), F32(mig_delta), F32(mig_reach)
+            R.role = np.zeros(self.n, np.uint8)
+            R.prev = np.zeros(self.n, np.uint8)
+            R.slot = np.zeros(self.n, bool)
+            R.x = np.zeros(self.n, F32)
+            R.vx = np.zeros(self.n, F32)
+            R.active = (0, 0)       # active faces / vertices as of the last re-sort
+            R.add = (0, 0)          # appended since
+            R.branches = set()
+            self.ranks.append(R)
+
+    # -- predicates (float32, the kernel's order)
+    def _w(self, R):
+        return np.where(self.face, R.ghost_w, R.vert_w).astype(F32)
+
+    def _in_my_band(self, R, bx, xi, extra):
+        w = (self._w(R) + F32(extra)).astype(F32)
+        left = (bx < R.own_lo) & (xi >= (F32(R.own_lo) - w).astype(F32)) if R.has_left else np.zeros(self.n, bool)
+        right = (bx >= R.own_hi) & (xi < (F32(R.own_hi) + w).astype(F32)) if R.has_right else np.zeros(self.n, bool)
+        return left | right
+
+    def _in_neighbour_bands(self, R, xi, old):
+        w = self._w(R)
+        wl = (w + np.where(old & 1, self.hyst, F32(0)).astype(F32)).astype(F32)
+        wr = (w + np.where(old & 2, self.hyst, F32(0)).astype(F32)).astype(F32)
+        out = np.zeros(self.n, np.uint8)
+        if R.has_left:
+            out |= (xi < (F32(R.own_lo) + wl).astype(F32)).astype(np.uint8)
+        if R.has_right:
+            out |= (xi >= (F32(R.own_hi) - wr).astype(F32)).astype(np.uint8) << 1
+        return out
+
+    # -- the state
+    def init(self, x, vx=None):
+        """mpm_dist_init: every rank sees the whole scene.  -> roles per rank"""
+        x = np.asarray(x, F32)
+        xi, bx = xi32(x, self.bits), cell_x(xi32(x, self.bits), self.bits)
+        for R in self.ranks:
+            mine = (bx >= R.own_lo) & (bx < R.own_hi)
+            R.role = np.where(mine, 1, np.where(self._in_my_band(R, bx, xi, 0.0), 2, 0)).astype(np.uint8)
+            R.prev = np.where(mine, self._in_neighbour_bands(R, xi, np.zeros(self.n, np.uint8)), 0).astype(np.uint8)
+            R.x = x.copy()
+            R.vx = np.zeros(self.n, F32) if vx is None else np.asarray(vx, F32).copy()
+            self.resort(self.ranks.index(R))
+        return [R.role.copy() for R in self.ranks]
+
+    def upload(self, x, vx=None):
+        """upload_particle_state on every rank: written where the rank has a slot; the role is left alone"""
+        for R in self.ranks:
+            R.x = np.where(R.slot, np.asarray(x, F32), R.x).astype(F32)
+            if vx is not None:
+                R.vx = np.where(R.slot, np.asarray(vx, F32), R.vx).astype(F32)
+
+    def resort(self, rank):
+        R = self.ranks[rank]
+        R.slot = R.role != 0
+        R.active = (int(np.count_nonzero(R.slot[:self.nf])), int(np.count_nonzero(R.slot[self.nf:])))
+        R.add = (0, 0)
+
+    def held(self, rank):
+        R = self.ranks[rank]
+        return (int(np.count_nonzero(R.role[:self.nf])), int(np.count_nonzero(R.role[self.nf:])))
+
+    def quiet_terms(self, rank):
+        """per held particle: (ids, t in float64, relative bound b)"""
+        R = self.ranks[rank]
+        ids = np.nonzero(R.role != 0)[0]
+        xi = xi32(R.x[ids], self.bits).astype(np.float64)
+        far = np.full(len(ids), np.inf)
+        if R.has_left:
+            far = np.minimum(far, np.abs(xi - R.own_lo))
+        if R.has_right:
+            far = np.minimum(far, np.abs(xi - R.own_hi))
+        with np.errstate(invalid="ignore", divide="ignore"):
+            d = float(R.mig_delta) + np.maximum(far - float(R.mig_reach), 0.0)
+            v = np.abs(R.vx[ids].astype(np.float64)) * float(1 << self.bits)
+            a = self.gravity_cells
+            den = v + np.sqrt(v * v + 2.0 * a * d)
+            t = np.where(den > 0, 2.0 * d / den, np.inf)
+            b = U32 * (10.0 + 1.5 * np.where(np.isfinite(far), far, 0.0) / d)
+        return ids, t, b
+
+    def quiet_time(self, rank):
+        _, t, _ = self.quiet_terms(rank)
+        return float(t.min()) if len(t) else float("inf")
+
+    def quiet_interval(self, rank):
+        """[lo, hi] that the engine's float32 estimate must lie in"""
+        _, t, b = self.quiet_terms(rank)
+        if not len(t) or not np.isfinite(t.min()):
+            return float("inf"), float("inf")
+        fin = np.isfinite(t)
+        return float((t[fin] * (1 - K * b[fin])).min()), float((t[fin] * (1 + K * b[fin])).min())
+
+    def classify(self, rank, cap=1 << 28):
+        """k_dist_classify.  -> dict: left / right ((m, 2) int arrays of (gid, role)), header_l / header_r
+        (records, faces), roles, prev, forced (a release forces the re-sort), flags, quiet"""
+        R = self.ranks[rank]
+        n, face = self.n, self.face
+        quiet = self.quiet_time(rank)
+        xi = xi32(R.x, self.bits)
+        bx = cell_x(xi, self.bits)
+        owned, ghost = R.role == 1, R.role == 2
+        flags = 0
+        left = owned & (xi < F32(F32(R.own_lo) - self.hyst)) if R.has_left else np.zeros(n, bool)
+        right = owned & (xi >= F32(F32(R.own_hi) + self.hyst)) if R.has_right else np.zeros(n, bool)
+        right &= ~left
+        hand = left | right
+        if np.any((left & (bx < R.nbr_lo)) | (right & (bx >= R.nbr_hi))):
+            flags |= ERR_HALO
+        keep = self._in_my_band(R, bx, xi, 0.0)
+        old = R.prev.copy()
+        inb = self._in_neighbour_bands(R, xi, old)
+        stay = owned & ~hand
+        to_l = left | (stay & ((inb & 1) != 0) & ((old & 1) == 0))
+        to_r = right | (stay & ((inb & 2) != 0) & ((old & 2) == 0))
+        rec_role = np.where(hand, ROLE_OWNED, ROLE_GHOST)
+        new_role = R.role.copy()
+        new_role[hand & keep] = 2
+        new_role[hand & ~keep] = 0
+        new_prev = R.prev.copy()
+        new_prev[hand] = 0
+        new_prev[stay] = inb[stay]
+        mine = (bx >= R.own_lo) & (bx < R.own_hi)
+        gstay = self._in_my_band(R, bx, xi, self.hyst)
+        new_role[ghost & ~mine & ~gstay] = 0
+        # which branches ran: (cut of this rank, kind, role, the side's prev bit, decision)
+        kinds = np.where(face, "f", "v")
+        for side, bit, has, hd in (("l", 1, R.has_left, left), ("r", 2, R.has_right, right)):
+            if not has:
+                continue
+            ob, nb = (old & bit) != 0, (inb & bit) != 0
+            near = (bx < R.own_lo) if side == "l" else (bx >= R.own_hi)
+            mid = 0.5 * (R.own_lo + R.own_hi)
+            sidemask = (xi < mid) if side == "l" else (xi >= mid)
+            cases = (("handover_keep", hd & keep), ("handover_release", hd & ~keep),
+                     ("send", stay & nb & ~ob), ("no_resend", stay & nb & ob), ("drop_bit", stay & ~nb & ob),
+                     ("outside", stay & ~nb & ~ob))
+            for name, m in cases:
+                for kd, km in (("f", face), ("v", ~face)):
+                    for bit_was in (0, 1):
+                        if np.any(m & km & (ob == bool(bit_was))):
+                            R.branches.add((side, kd, "owned", bit_was, name))
+            for name, m in (("ghost_waits", ghost & mine & sidemask), ("ghost_stays", ghost & near & gstay),
+                            ("ghost_released", ghost & near & ~gstay)):
+                for k in np.unique(kinds[m]):
+                    R.branches.add((side, str(k), "ghost", 0, name))
+        out = {}
+        for name, m in (("left", to_l), ("right", to_r)):
+            ids = np.nonzero(m)[0]
+            out[name] = np.stack([ids, rec_role[ids]], 1).astype(np.int64)
+            out["header_" + name[0]] = (len(ids), int(np.count_nonzero(ids < self.nf)))
+            if len(ids) > cap:
+                flags |= ERR_CAPACITY
+        forced = bool(np.any((new_role == 0) & (R.role != 0)))
+        R.role, R.prev = new_role, new_prev
+        out.update(roles=new_role.copy(), prev=new_prev.copy(), forced=forced, flags=flags, quiet=quiet)
+        return out
+
+    def apply(self, rank, from_left, from_right):
+        """k_dist_apply with the (gid, role) lists the neighbours' classify returned; the payload is the sender's held
+        state.  -> dict: appended (faces, vertices), in_place, forced"""
+        R = self.ranks[rank]
+        app, inplace = [0, 0], 0
+        n_rec = 0
+        for recs, src in ((from_left, rank - 1), (from_right, rank + 1)):
+            if recs is None or not len(recs):
+                continue
+            S = self.ranks[src]
+            n_rec += len(recs)
+            for gid, role in np.asarray(recs):
+                if not R.slot[gid]:
+                    app[0 if gid < self.nf else 1] += 1
+                    R.slot[gid] = True
+                else:
+                    inplace += 1
+                R.role[gid] = 1 if role == ROLE_OWNED else 2
+                R.x[gid], R.vx[gid] = S.x[gid], S.vx[gid]
+                if role == ROLE_OWNED:
+                    R.prev[gid] = 0
+        R.add = (R.add[0] + app[0], R.add[1] + app[1])
+        return dict(appended=tuple(app), in_place=inplace, forced=n_rec > 0)
+
+    def apply_fast(self, rank, from_left, from_right):
+        """apply() for large buffers (no id twice in one migration, which apply() does not assume)"""
+        R = self.ranks[rank]
+        app, inplace, n_rec = [0, 0], 0, 0
+        for recs, src in ((from_left, rank - 1), (from_right, rank + 1)):
+            if recs is None or not len(recs):
+                continue
+            S = self.ranks[src]
+            g, role = np.asarray(recs)[:, 0], np.asarray(recs)[:, 1]
+            assert len(np.unique(g)) == len(g)
+            n_rec += len(g)
+            new = ~R.slot[g]
+            app[0] += int(np.count_nonzero(new & (g < self.nf)))
+            app[1] += int(np.count_nonzero(new & (g >= self.nf)))
+            inplace += int(np.count_nonzero(~new))
+            R.slot[g] = True
+            R.role[g] = np.where(role == ROLE_OWNED, 1, 2)
+            R.x[g], R.vx[g] = S.x[g], S.vx[g]
+            R.prev[g[role == ROLE_OWNED]] = 0
+        R.add = (R.add[0] + app[0], R.add[1] + app[1])
+        return dict(appended=tuple(app), in_place=inplace, forced=n_rec > 0)
+
+    def retune(self, rank, quiet_all, dt):
+        """mpm_dist_retune (float32, the host's order).  -> changed"""
+        R = self.ranks[rank]
+        t, dt = F32(quiet_all), F32(dt)
+        if not self.auto or not self.retune_on or not dt > 0:
+            return False
+        want = self.delta_max
+        if t > 0 and np.isfinite(t):
+            speed = F32(R.mig_delta / t)
+            with np.errstate(over="ignore"):
+                want = F32(F32(F32(speed * dt) * self.interval) / self.safety)
+                want = F32(np.ceil(F32(want * F32(8))) * F32(0.125))
+        elif t > 0:
+            want = F32(0.125)
+        want = min(max(want, F32(0.125)), self.delta_max)
+        self.last_want = F32(want)
+        if not want > F32(0.05) or abs(F32(want - R.mig_delta)) < F32(0.06):
+            return False
+        R.mig_delta = F32(want)
+        R.ghost_w = F32(F32(self.reach + F32(2) * want) + self.hyst)
+        R.vert_w = F32(R.ghost_w + self.reach)
+        R.mig_reach = F32(F32(R.vert_w + F32(2) * self.reach) + F32(1))
+        return True
+
+    def migrate(self, cap=1 << 28, fast=False):
+        """one migration of the whole world: classify everywhere, apply everywhere, re-sort where forced.
+        -> per rank dict(classify result + appended, in_place, forced, active_before, in_f, in_v, held)"""
+        cls = [self.classify(r, cap) for r in range(self.world)]
+        out = []
+        for r in range(self.world):
+            fl = cls[r - 1]["right"] if r > 0 else None
+            fr = cls[r + 1]["left"] if r < self.world - 1 else None
+            before = (self.ranks[r].active[0] + self.ranks[r].add[0], self.ranks[r].active[1] + self.ranks[r].add[1])
+            a = (self.apply_fast if fast else self.apply)(r, fl, fr)
+            d = dict(cls[r])
+            d.update(appended=a["appended"], in_place=a["in_place"], forced=cls[r]["forced"] or a["forced"], active_before=before)
+            hs = [(cls[r - 1]["header_r"] if r > 0 else (0, 0)), (cls[r + 1]["header_l"] if r < self.world - 1 else (0, 0))]
+            d["in_f"] = hs[0][1] + hs[1][1]
+            d["in_v"] = hs[0][0] + hs[1][0] - d["in_f"]
+            out.append(d)
+        for r in range(self.world):
+            out[r]["roles"] = self.ranks[r].role.copy()
+            out[r]["prev"] = self.ranks[r].prev.copy()
+            if out[r]["forced"]:
+                self.resort(r)
+            out[r]["held"] = self.held(r)
+        return out
+
+    # -- invariants of a state that keeps the drift contract
+    def check_invariants(self, idx, what=""):
+        """one owner per particle; every ghost inside its holder's band (hysteresis included); every held face has its
+        corners on the rank; every owned vertex has its faces on the rank"""
+        owners = sum((R.role == 1).astype(int) for R in self.ranks)
+        assert np.all(owners == 1), (what, "owners", np.nonzero(owners != 1)[0][:8])
+        x_owner = np.zeros(self.n, F32)
+        for R in self.ranks:
+            x_owner[R.role == 1] = R.x[R.role == 1]
+        for r, R in enumerate(self.ranks):
+            held = R.role != 0
+            assert np.array_equal(R.x[held], x_owner[held]), (what, "a copy differs from its owner's", r)
+            xi = xi32(R.x, self.bits)
+            bx = cell_x(xi, self.bits)
+            g = R.role == 2
+            mine = (bx >= R.own_lo) & (bx < R.own_hi)
+            ok = mine | self._in_my_band(R, bx, xi, self.hyst)
+            assert np.all(ok[g]), (what, "ghost outside the band", r, np.nonzero(g & ~ok)[0][:8])
+            hf = np.nonzero(held[:self.nf])[0]
+            corners = held[self.nf + idx[hf]]
+            assert np.all(corners), (what, "a held face misses a corner", r, hf[~corners.all(axis=1)][:8])
+            # vertex j of face f is particle nf + idx[f, j]
+            lacks = ~held[:self.nf]
+            vmiss = np.zeros(self.n, bool)
+            vmiss[self.nf + idx[lacks].reshape(-1)] = True
+            bad = vmiss & (R.role == 1)
+            assert not np.any(bad), (what, "an owned vertex misses a face", r, np.nonzero(bad)[0][:8])
+
+
+# ---- exact placement --------------------------------------------------------------------------------------------------
+def place_x(target, bits, mode="at"):
+    """the float32 x with xi32(x) == target exactly (asserted), or -- mode 'below' / 'above' -- the float32 x next to it
+    whose xi differs: the nearest attainable xi on that side"""
+    t = F32(target)
+    x0 = F32((float(t) + 0.5) / float(1 << bits))
+    cands, a, b = [x0], x0, x0
+    for _ in range(8):
+        a, b = np.nextafter(a, F32(-np.inf)), np.nextafter(b, F32(np.inf))
+        cands += [a, b]
+    hits = [c for c in cands if xi32(c, bits) == t]
+    assert hits, f"no float32 x has xi == {float(t)!r}"
+    x = min(hits, key=lambda c: abs(float(c) - float(x0)))
+    if mode == "at":
+        return F32(x)
+    toward = F32(-np.inf) if mode == "below" else F32(np.inf)
+    y = x
+    for _ in range(8):
+        y = np.nextafter(y, toward)
+        if xi32(y, bits) != t:
+            break
+    assert (xi32(y, bits) < t) if mode == "below" else (xi32(y, bits) > t)
+    return F32(y)
+
+
+def band_thresholds(c, w, hyst):
+    """float32 thresholds about the cut at cell c, in the kernel's order of operations"""
+    c, w, hyst = F32(c), F32(w), F32(hyst)
+    wh = F32(w + hyst)
+    return {"own-": F32(c - hyst), "own+": F32(c + hyst), "edge-": F32(c - w), "edge+": F32(c + w),
+            "sticky-": F32(c - wh), "sticky+": F32(c + wh)}
+
+
+# ---- scenes ---------------------------------------------------------------------------------------------------------------
+class _Scene:
+    """triangles in cell units; per stage and triangle the xi of one designated particle (-1 the face, 0..2 a corner),
+    optionally exact (mode at / below / above)"""
+
+    def __init__(self, bits, seed):
+        self.bits, self.rng = bits, np.random.default_rng(seed)
+        self.shapes, self.anchor, self.which, self.track, self.vel = [], [], [], [], []
+        self._slot = 0
+
+    def shape(self):
+        """corner offsets from the centroid, edges within [0.4, 0.6] cells"""
+        while True:
+            s = self.rng.uniform(0.45, 0.56)
+            a = self.rng.uniform(0, 2 * np.pi)
+            tilt = self.rng.uniform(-0.3, 0.3, 3)
+            d = np.array([[s / np.sqrt(3) * np.cos(a + k * 2 * np.pi / 3), s / np.sqrt(3) * np.sin(a + k * 2 * np.pi / 3), 0.15 * tilt[k]]
+                          for k in range(3)])
+            d -= d.mean(axis=0)
+            e = [np.linalg.norm(d[k] - d[(k + 1) % 3]) for k in range(3)]
+            if min(e) >= 0.4 and max(e) <= 0.6:
+                return d
+
+    def add(self, track, which=-1, vel=None, shape=None):
+        """track: per stage xi, or (xi, mode); -> triangle index"""
+        k = self._slot
+        self._slot += 1
+        per_row = 26
+        self.anchor.append((6.0 + 2.0 * (k % per_row), 6.0 + 2.0 * (k // per_row)))
+        assert k // per_row < per_row, "too many triangles for the y-z lattice"
+        self.shapes.append(self.shape() if shape is None else shape)
+        self.which.append(which)
+        self.track.append([t if isinstance(t, tuple) else (t, None) for t in track])
+        self.vel.append(vel)
+        return k
+
+    def build(self, n_stages):
+        """-> rest vertices (3 nt + 3, 3) f32 with the gauge triangle first, idx, stages [(pos, vel)] in original order"""
+        bits = self.bits
+        dx = 1.0 / (1 << bits)
+        nt = len(self.shapes) + 1
+        idx = np.arange(3 * nt, dtype=np.int32).reshape(nt, 3)
+        gauge = np.array([[12.0, 20.0, 20.0], [12.0, 20.0 + GAUGE_EDGE, 20.0], [12.25, 20.25, 20.25]]) * dx
+        stages = []
+        for s in range(n_stages):
+            xv = np.zeros((3 * nt, 3), F32)
+            xf = np.zeros((nt, 3), F32)
+            vv = np.zeros((3 * nt, 3), F32)
+            xv[:3] = gauge.astype(F32)
+            xf[0] = ((xv[0] + xv[1]) + xv[2]) / F32(3)
+            for t, d in enumerate(self.shapes):
+                xi, mode = self.track[t][min(s, len(self.track[t]) - 1)]
+                wh = self.which[t]
+                cu = float(xi) + 0.5 - (0.0 if wh < 0 else d[wh, 0])
+                ay, az = self.anchor[t]
+                cen = np.array([cu, ay, az])
+                xv[3 * (t + 1):3 * (t + 2)] = ((cen + d) * dx).astype(F32)
+                xf[t + 1] = (cen * dx).astype(F32)
+                if mode is not None:
+                    px = place_x(xi, bits, mode)
+                    if wh < 0:
+                        xf[t + 1, 0] = px
+                    else:
+                        xv[3 * (t + 1) + wh, 0] = px
+                if self.vel[t] is not None:
+                    v = self.vel[t][min(s, len(self.vel[t]) - 1)]
+                    vv[3 * (t + 1):3 * (t + 2), 0] = v
+            vf = ((vv[idx[:, 0]] + vv[idx[:, 1]]) + vv[idx[:, 2]]) / F32(3)
+            stages.append((np.concatenate([xf, xv]), np.concatenate([vf, vv])))
+        return idx, stages
+
+
+PARTITIONS = {2: [0, 8, 16], 3: [0, 6, 10, 16]}
+# (ranks, zone_blocks, ghost_cells, ghost_margin_cells): bands from the mesh (0, 0) and given (2, 2; they need a zone of 2)
+CONFIGS = [(2, 1, 0, 0), (2, 2, 0, 0), (2, 2, 2, 2), (3, 1, 0, 0), (3, 2, 0, 0), (3, 2, 2, 2)]
+BITS = 6
+
+
+def _finish(name, scene, n_stages, cfg, claims, contract=None, **extra):
+    ranks, zone_blocks, gc, gm = cfg
+    idx, stages = scene.build(n_stages)
+    nf = len(idx)
+    n = nf + 3 * nf
+    rest = stages[0][0][nf:]
+    lay = dict(name=name, bits=scene.bits, cuts=PARTITIONS[ranks], zone_blocks=zone_blocks, ghost_cells=gc,
+               ghost_margin_cells=gm, cfg=cfg, idx=idx, nf=nf, nv=3 * nf, n=n, cloth=(rest.copy(), np.zeros_like(rest), idx),
+               stages=[dict(pos=p, vel=v, contract=True if contract is None else contract[s], retune=None)
+                       for s, (p, v) in enumerate(stages)],
+               claims=list(claims), gravity_axis=2, gravity=-9.8, capacity=8192, exact=True)
+    lay.update(extra)
+    lay["rules"] = band_rules(longest_edge_cells(rest, idx, scene.bits), zone_blocks, gc, gm)
+    return lay
+
+
+def _rules(cfg):
+    return band_rules(F32(GAUGE_EDGE), cfg[1], cfg[2], cfg[3])
+
+
+def _cut_cells(cfg):
+    return [4 * c for c in PARTITIONS[cfg[0]][1:-1]]
+
+
+def thresholds(cfg):
+    """stage 0 home, stage 1 the probes, stage 2 home again.  lay['probes']: (particle id, cut, owner side, kind,
+    threshold name, variant, approach, float32 threshold)"""
+    R = _rules(cfg)
+    sc = _Scene(BITS, 11)
+    h = float(R["hyst"])
+    probes = []
+    for c in _cut_cells(cfg):
+        for side in ("L", "R"):             # the rank that owns the particle at first: left or right of the cut
+            sg = 1.0 if side == "L" else -1.0      # xi = c + sg e, e = how far beyond the cut
+            for kind in ("f", "v"):
+                w = float(R["ghost_w"] if kind == "f" else R["vert_w"])
+                T = band_thresholds(c, w, h)
+                which = -1 if kind == "f" else 0
+                far_home, in_home, cut_home = c - sg * (w + h + 1.0), c - sg * 0.5 * w, c - sg * 0.5
+                into, back = ("+", "-") if side == "L" else ("-", "+")
+                plan_ = [("own" + into, cut_home, "ownership")]
+                for nm in ("edge" + back, "sticky" + back):
+                    plan_ += [(nm, far_home, "outside"), (nm, in_home, "inside")]
+                plan_ += [("edge" + into, cut_home, "handover"), ("edge" + into, far_home, "far_handover")]
+                for nm, home, approach in plan_:
+                    for variant in ("below", "at", "above"):
+                        t = sc.add([home, (float(T[nm]), variant), home], which=which)
+                        probes.append((t, c, side, kind, nm, variant, approach, T[nm]))
+    # jumps of several cells: the drift contract is kept by stage 0 only
+    lay = _finish("thresholds", sc, 3, cfg, ["probes_exact", "probes_decide", "branches"], contract=[True, False, False])
+    nf = lay["nf"]
+    lay["probes"] = [((t + 1) if k == "f" else nf + 3 * (t + 1), c, side, k, nm, var, ap, T)
+                     for t, c, side, k, nm, var, ap, T in probes]
+    return lay
+
+
+def there_and_back(cfg):
+    """stages 1-4: only the oscillators move (no traffic at all); stages 5-11: the crossers go over the cut, stop, and
+    come back while the oscillators keep oscillating"""
+    R = _rules(cfg)
+    h, delta = float(R["hyst"]), float(R["mig_delta"])
+    step = 0.98 * min(delta, 0.5)
+    n_stages = 12
+    for seed in range(40):
+        sc = _Scene(BITS, 100 + seed)
+        osc, crossers = [], []
+        for c in _cut_cells(cfg):
+            for sg in (1.0, -1.0):          # start on the left / (mirrored) on the right
+                for k in range(4):
+                    ph = 0.11 * k
+                    e = [-1.8, -1.8, -1.8, -1.8, -1.8, -0.8, 0.2, 1.2, 1.2, 0.2, -0.8, -1.8]
+                    crossers.append(sc.add([c + sg * (ee + ph) * step for ee in e], which=-1 if k % 2 == 0 else k % 3))
+                for kind in (-1, 0):
+                    w = float(R["ghost_w"] if kind < 0 else R["vert_w"])
+                    amp = 0.8 * h
+                    # about the cut (never h beyond it), and about the band edge from inside (the bit stays set)
+                    t = sc.add([c + sg * (amp if s % 2 else -amp) for s in range(n_stages)], which=kind)
+                    osc.append(t)
+                    t = sc.add([c - sg * (w - 0.02 + (amp if s % 2 else 0.0)) for s in range(n_stages)], which=kind)
+                    osc.append(t)
+        lay = _finish("there_and_back", sc, n_stages, cfg, ["quiet_stages", "crossings", "invariants"], quiet_stages=[1, 2, 3, 4],
+                      oscillators=osc, crossers=crossers)
+        if h == 0:
+            lay["quiet_stages"] = []
+        res = replay(lay)
+        if all(not (d["header_l"][0] or d["header_r"][0] or d["forced"]) for s in lay["quiet_stages"] for d in res[s]):
+            return lay
+    raise AssertionError("no shapes found for which the oscillation stages are quiet")
+
+
+def waves(cfg=(3, 2, 0, 0)):
+    """the middle rank of three: triangles next to its left cut and next to its right cut, every second one moving into
+    the neighbour's band or across the cut at stage 1"""
+    R = _rules(cfg)
+    sc = _Scene(BITS, 31)
+    c_l, c_r = _cut_cells(cfg)
+    gw = float(R["ghost_w"])
+    for k in range(58):
+        for c, sg in ((c_l, 1.0), (c_r, -1.0)):
+            if k >= 50 and sg < 0:
+                continue
+            move = 0.45 if k % 2 == 0 else 0.0
+            home = (gw + 0.25 + 0.02 * (k % 5)) if k % 4 < 2 else (0.2 + 0.02 * (k % 5))   # outside the band / next to the cut
+            sc.add([c + sg * home, c + sg * (home - move)], which=-1)
+    return _finish("waves", sc, 2, cfg, ["mixed_wave", "face_counts", "invariants"])
+
+
+def promotion(cfg=(2, 2, 0, 0)):
+    R = _rules(cfg)
+    sc = _Scene(BITS, 41)
+    c = _cut_cells(cfg)[0]
+    vw = float(R["vert_w"])
+    for k in range(24):
+        sg = 1.0 if k % 2 == 0 else -1.0
+        if k % 4 < 2:
+            sc.add([c - sg * 0.45, c + sg * 0.45], which=-1)                    # held as a ghost over there: promoted in place
+        else:
+            sc.add([c - sg * (vw + 1.2), c + sg * 0.6], which=-1)               # not held over there: appended
+    return _finish("promotion", sc, 2, cfg, ["both_kinds_in_one_buffer"], contract=[True, False])
+
+
+def retune(cfg=(2, 2, 0, 0)):
+    sc = _Scene(BITS, 51)
+    c = _cut_cells(cfg)[0]
+    for k in range(90):
+        sc.add([c - 4.0 + 8.0 * (k + 0.37) / 90.0] * 3, which=-1)
+    lay = _finish("retune", sc, 3, cfg, ["widen_sends", "narrow_releases"])
+    # want = ceil(8 x 0.5 / 0.0165 x 1e-3 x 16 / 0.5) / 8 = 1 cell of drift, then the narrowest
+    lay["stages"][1]["retune"] = (0.0165, DT)
+    lay["stages"][2]["retune"] = (float("inf"), DT)
+    return lay
+
+
+def quiet(axis):
+    """velocities over four decades (1e-3 .. 10 m/s), near and far from the cut; the third rank holds nothing; the last
+    stage is at rest"""
+    cfg = (3, 2, 0, 0)
+    sc = _Scene(BITS, 61 + axis)
+    c = _cut_cells(cfg)[0]
+    rng = np.random.default_rng(5)
+    for k in range(60):
+        v1 = 10.0 ** rng.uniform(-3, 1) * (1 if k % 2 else -1)
+        v2 = 10.0 ** rng.uniform(-3, 1) * (1 if k % 3 else -1)
+        x = c - 9.0 + 14.0 * (k + 0.5) / 60.0
+        sc.add([x, x, x], which=-1, vel=[0.0, v1, v2, 0.0])
+    lay = _finish("quiet%d" % axis, sc, 4, cfg, ["four_decades", "empty_rank", "rest_is_infinite"], gravity_axis=axis)
+    return lay
+
+
+def bulk():
+    """a lattice of identical triangles left of the cut, dense along x; stage 1 shifts all of it by 0.45 cells"""
+    cfg = (2, 2, 0, 0)
+    bits = BITS
+    dx = 1.0 / (1 << bits)
+    c = _cut_cells(cfg)[0]
+    d = np.array([[0.26, -0.15, 0.02], [-0.26, -0.15, -0.02], [0.0, 0.30, 0.0]])
+    d -= d.mean(axis=0)
+    us = c - 0.02 - 0.1 * np.arange(41)
+    ys = 4.0 + np.arange(57.0)
+    U, Y, Z = (a.reshape(-1) for a in np.meshgrid(us, ys, ys, indexing="ij"))
+    cen = np.stack([U + 0.5, Y, Z], 1)
+    right = np.array([[c + 3.0 + 0.5, 10.0 + 2 * k, 10.0] for k in range(8)])
+    cen = np.concatenate([cen, right])
+    nt = len(cen) + 1
+    idx = np.arange(3 * nt, dtype=np.int32).reshape(nt, 3)
+    gauge = (np.array([[12.0, 20.0, 20.5], [12.0, 20.0 + GAUGE_EDGE, 20.5], [12.25, 20.25, 20.75]]) * dx).astype(F32)
+    stages = []
+    for shift in (0.0, 0.45):
+        cc = cen + np.array([shift, 0.0, 0.0])
+        xv = np.concatenate([gauge, ((cc[:, None, :] + d[None]) * dx).reshape(-1, 3).astype(F32)])
+        xf = np.concatenate([(((gauge[0] + gauge[1]) + gauge[2]) / F32(3))[None], (cc * dx).astype(F32)])
+        pos = np.concatenate([xf, xv])
+        stages.append(dict(pos=pos, vel=np.zeros_like(pos), contract=True, retune=None))
+    rest = stages[0]["pos"][nt:]
+    lay = dict(name="bulk", bits=bits, cuts=PARTITIONS[2], zone_blocks=2, ghost_cells=0, ghost_margin_cells=0, cfg=cfg, idx=idx,
+               nf=nt, nv=3 * nt, n=4 * nt, cloth=(rest.copy(), np.zeros_like(rest), idx), stages=stages,
+               claims=["second_trips"], gravity_axis=2, gravity=-9.8, capacity=1 << 18, exact=True, fast=True)
+    lay["rules"] = band_rules(longest_edge_cells(rest, idx, bits), 2, 0, 0)
+    return lay
+
+
+def contract_halo():
+    """a triangle of rank 0 lands in rank 2's slab within one interval"""
+    cfg = (3, 2, 0, 0)
+    sc = _Scene(BITS, 71)
+    c_l, c_r = _cut_cells(cfg)
+    sc.add([c_l - 1.0, c_r + 1.5], which=-1)
+    sc.add([c_l - 1.0, c_l - 0.9], which=-1)
+    return _finish("contract_halo", sc, 2, cfg, ["halo_flag"], contract=[True, False], exact=False)
+
+
+def contract_capacity():
+    cfg = (2, 2, 0, 0)
+    sc = _Scene(BITS, 81)
+    c = _cut_cells(cfg)[0]
+    for k in range(6):
+        sc.add([c - 0.45, c + 0.45], which=-1)
+    return _finish("contract_capacity", sc, 2, cfg, ["one_record_short"], exact=False)
+
+
+_CACHE = {}
+
+
+def layout(name, cfg=None):
+    key = (name, cfg)
+    if key not in _CACHE:
+        f = dict(thresholds=thresholds, there_and_back=there_and_back, waves=waves, promotion=promotion, retune=retune,
+                 bulk=bulk, quiet0=lambda: quiet(0), quiet2=lambda: quiet(2), contract_halo=contract_halo,
+                 contract_capacity=contract_capacity)[name]
+        _CACHE[key] = f(cfg) if cfg is not None else f()
+    return _CACHE[key]
+
+
+# the exact-protocol layouts and the configurations each is built for
+EXACT = [("thresholds", c) for c in CONFIGS] + [("there_and_back", c) for c in CONFIGS] + \
+        [("waves", None), ("promotion", None), ("retune", None), ("quiet0", None), ("quiet2", None), ("bulk", None)]
+
+
+def model_of(lay, rules=None, **kw):
+    r = lay["rules"] if rules is None else rules
+    g = float(F32(abs(F32(lay["gravity"])) * F32(1 << lay["bits"]))) if lay["gravity_axis"] == 0 else 0.0
+    return MigrationModel(lay["bits"], lay["cuts"], lay["zone_blocks"], r["ghost_w"], r["vert_w"], r["hyst"], r["mig_delta"],
+                          r["mig_reach"], lay["nf"], lay["n"], reach=r["reach"], delta_max=r["delta_max"], auto=r["auto"],
+                          gravity_cells=g, **kw)
+
+
+def replay(lay, rules=None, model=None, cap=None, pos0=None):
+    """the model through every stage -> [stage 0: list of roles per rank, stage s: MigrationModel.migrate()'s result];
+    result[s][r]['quiet_interval'] is the allowed interval of the engine's estimate; result.model is the model as the last
+    stage left it.  pos0: the positions the ranks were partitioned with, where they are not the layout's own stage 0
+    (the engine puts a face particle at the float32 centroid it computes itself)"""
+    m = model_of(lay, rules) if model is None else model
+    out = _Replay()
+    out.model = m
+    st0 = lay["stages"][0]
+    out.append(m.init(st0["pos"][:, 0] if pos0 is None else pos0[:, 0], st0["vel"][:, 0]))
+    for st in lay["stages"][1:]:
+        if st["retune"] is not None:
+            st_changed = [m.retune(r, *st["retune"]) for r in range(m.world)]
+        m.upload(st["pos"][:, 0], st["vel"][:, 0])
+        qi = [m.quiet_interval(r) for r in range(m.world)]
+        res = m.migrate(cap=lay["capacity"] if cap is None else cap, fast=lay.get("fast", False))
+        for r, d in enumerate(res):
+            d["quiet_interval"] = qi[r]
+            d["bands"] = (m.ranks[r].ghost_w, m.ranks[r].vert_w, m.ranks[r].mig_delta)
+            if st["retune"] is not None:
+                d["retuned"] = st_changed[r]
+        out.append(res)
+    return out
+
+
+class _Replay(list):
+    model = None
+
+
+def active_order(lay, stage, roles):
+    """the order k_dist_classify walks a rank's active particles in after the re-sort that followed stage `stage`: faces
+    then vertices, each sorted by the key of the base cell (ties by id: the layouts that use this keep every particle of
+    a kind in a cell of its own where it matters)"""
+    from tests.transfer_layouts import base_cells, cell_key
+    pos = lay["stages"][stage]["pos"]
+    b, _ = base_cells(pos, lay["bits"])
+    key = cell_key(b[:, 0], b[:, 1], b[:, 2])
+    nf = lay["nf"]
+    ids = np.nonzero(roles != 0)[0]
+    f, v = ids[ids < nf], ids[ids >= nf]
+    return np.concatenate([f[np.argsort(key[f], kind="stable")], v[np.argsort(key[v], kind="stable")]])
