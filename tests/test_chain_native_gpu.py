@@ -54,8 +54,9 @@ def test_ring_of_one_equals_device_copies():
     solo.run_substeps(STEPS, DT, -1)
     v_ref, v_nat, v_solo = (x.download(ARR.VELOCITIES) for x in (ref, g, solo))
     assert np.abs(v_ref - v_solo).max() > 1e-3
-    np.testing.assert_allclose(v_nat, v_ref, rtol=0, atol=2e-6)
-    np.testing.assert_allclose(g.download(ARR.POSITIONS), ref.download(ARR.POSITIONS), rtol=0, atol=1e-7)
+    # deterministic engines adding the same pair of numbers per block: to the bit, whatever carries the buffers
+    assert np.array_equal(v_nat, v_ref)
+    assert np.array_equal(g.download(ARR.POSITIONS), ref.download(ARR.POSITIONS))
     g.chain_destroy()
 
 
