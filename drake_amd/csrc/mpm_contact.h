@@ -641,8 +641,6 @@ static void launch_ct_tile(dim3 grid, hipStream_t s, const DP& p, const ContactD
 }
 
 // ---- partitioned domain: transports of the distributed solve ----------------------------------
-static size_t zone_buffer_bytes(size_t cap, int nv) { return (((4 + cap) * 4 + 15) / 16) * 16 + cap * 64 * nv * 16; }
-
 // contact fields of the zone blocks to both neighbours and back: pack -> transport -> add
 static int zone_exchange3(mpm_engine* e, float4* field) {
     ContactBuffers& b = e->cb;
@@ -664,12 +662,11 @@ static int zone_exchange3(mpm_engine* e, float4* field) {
     const Dist& d = p.dist;
     const int Z = d.zone_cells / 4;
     // [0] = towards / from the left neighbour, [1] = right
-    ZoneX zs{}, zr{};
-    int n = 0, side[2];
-    if (d.has_left) { zs.lo[n] = d.own_lo / 4 - Z; zs.hi[n] = d.own_lo / 4 + Z - 1; zs.buf[n] = (uint32_t*)b.zone_buf[0]; zr.buf[n] = (uint32_t*)b.zone_buf[2]; side[n++] = 0; }
-    if (d.has_right) { zs.lo[n] = d.own_hi / 4 - Z; zs.hi[n] = d.own_hi / 4 + Z - 1; zs.buf[n] = (uint32_t*)b.zone_buf[1]; zr.buf[n] = (uint32_t*)b.zone_buf[3]; side[n++] = 1; }
+    Zones zs{}, zr{};
+    int n = 0;
+    if (d.has_left) { zs.lo[n] = d.own_lo / 4 - Z; zs.hi[n] = d.own_lo / 4 + Z - 1; zs.buf[n] = (uint32_t*)b.zone_buf[0]; zr.buf[n] = (uint32_t*)b.zone_buf[2]; ++n; }
+    if (d.has_right) { zs.lo[n] = d.own_hi / 4 - Z; zs.hi[n] = d.own_hi / 4 + Z - 1; zs.buf[n] = (uint32_t*)b.zone_buf[1]; zr.buf[n] = (uint32_t*)b.zone_buf[3]; ++n; }
     if (n == 0) return 0;
-    (void)side;
     for (int k = 0; k < n; ++k) HIP_TRY(hipMemsetAsync(zs.buf[k], 0, 16, s));
     hipLaunchKernelGGL(k_zone_pack<3>, dim3(e->g_grid, n), dim3(256), 0, s, p, zs, (unsigned)cap, (const float4*)field);
     if (ch.comm) {

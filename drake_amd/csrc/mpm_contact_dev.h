@@ -1138,54 +1138,30 @@ MPM_DEV bool node_owned(const DP& p, int g) {
     return gx >= p.dist.own_lo && gx < p.dist.own_hi;
 }
 
-// Buffer: [0] block count, [4 ..) block ids (cap), then cap * 64 * NV float4.  Same shape as the
-// halo buffers of the grid sums (mpm_step.h) with NV vectors per cell.
-MPM_DEV size_t zone_data_offset(unsigned cap) { return ((size_t)(4 + cap) * 4 + 15) / 16; }
-struct ZoneX {
-    int lo[2], hi[2];
-    uint32_t* buf[2];
-};
+// The per-node fields travel in zone exchange buffers (mpm_zone_buffer.h) with NV vectors per cell, under the block's
+// own id: the ranks of a partitioned domain share one grid.
 template <int NV>
-__global__ __launch_bounds__(256) void k_zone_pack(DP p, ZoneX z, unsigned cap, const float4* field) {
+__global__ __launch_bounds__(256) void k_zone_pack(DP p, Zones z, unsigned cap, const float4* field) {
     const int k = blockIdx.y;
     uint32_t* buf = z.buf[k];
     const unsigned n_active = p.ctl->n_active;
-    float4* data = reinterpret_cast<float4*>(buf) + zone_data_offset(cap);
     for (unsigned a = blockIdx.x * 4 + (threadIdx.x >> 6); a < n_active; a += gridDim.x * 4) {
         int bx, by, bz;
         block_coords(p.act_block[a], bx, by, bz);
         if (bx < z.lo[k] || bx > z.hi[k]) continue;   // wave-uniform
-        unsigned slot = 0;
-        if ((threadIdx.x & 63) == 0) slot = atomicAdd(&buf[0], 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
-        if (slot >= cap) {
-            if ((threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
-            continue;
-        }
-        if ((threadIdx.x & 63) == 0) buf[4 + slot] = p.act_block[a];
-        const size_t cell = (size_t)a * 64 + (threadIdx.x & 63);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) data[((size_t)slot * 64 + (threadIdx.x & 63)) * NV + v] = field[cell * NV + v];
+        const int slot = zbuf_claim(&buf[0], cap, p.ctl);
+        if (slot < 0) continue;
+        zbuf_store<NV>(buf, cap, (unsigned)slot, p.act_block[a], field + ((size_t)a * 64 + (threadIdx.x & 63)) * NV);
     }
 }
 template <int NV>
-__global__ __launch_bounds__(256) void k_zone_add(DP p, ZoneX z, unsigned cap, float4* field) {
+__global__ __launch_bounds__(256) void k_zone_add(DP p, Zones z, unsigned cap, float4* field) {
     const uint32_t* buf = z.buf[blockIdx.y];
-    const unsigned n = min(buf[0], cap);
-    const float4* data = reinterpret_cast<const float4*>(buf) + zone_data_offset(cap);
+    const unsigned n = zbuf_count(buf, cap);
     for (unsigned e = blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += gridDim.x * 4) {
-        const uint32_t id = buf[4 + e];
-        if (id >= p.nblocks) continue;
-        const int a = p.lut_act[id];
-        if (a < 0) continue;   // nothing of this rank reaches that block
-        const size_t cell = (size_t)a * 64 + (threadIdx.x & 63);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const float4 r = data[((size_t)e * 64 + (threadIdx.x & 63)) * NV + v];
-            float4 q = field[cell * NV + v];
-            q.x += r.x; q.y += r.y; q.z += r.z; q.w += r.w;
-            field[cell * NV + v] = q;
-        }
+        const int a = zbuf_entry_block(p, buf, e);
+        if (a < 0) continue;
+        zbuf_add<NV>(buf, cap, e, field + ((size_t)a * 64 + (threadIdx.x & 63)) * NV);
     }
 }
 // node_flag (int) <-> the first vector of hg, for the one-off exchange of "this node sees a contact"

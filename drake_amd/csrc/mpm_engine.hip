@@ -1115,14 +1115,14 @@ int mpm_grid_gather(mpm_handle_t e) try {
     return 0;
 } MPM_CATCH_ALL
 
-size_t mpm_halo_buffer_bytes(size_t cap) { return (((4 + cap) * 4 + 15) / 16) * 16 + cap * 64 * 16; }
+size_t mpm_halo_buffer_bytes(size_t cap) { return zone_buffer_bytes(cap, 1); }
 
 int mpm_halo_pack(mpm_handle_t e, int bx_lo, int bx_hi, int shift_bx, void* dev_buf, size_t cap) try {
     READY(e);
     REQUIRE(e->grid_state == 3, "halo pack needs mpm_grid_gather first");
     REQUIRE(dev_buf && cap > 0 && cap < (1u << 24), "bad halo buffer");
     HIP_TRY(hipMemsetAsync(dev_buf, 0, 16, e->stream));
-    HaloZones z{};
+    Zones z{};
     z.lo[0] = bx_lo; z.hi[0] = bx_hi; z.shift[0] = shift_bx;
     z.buf[0] = static_cast<uint32_t*>(dev_buf);
     hipLaunchKernelGGL(k_halo_pack2, dim3(e->g_grid, 1), dim3(256), 0, e->stream, e->dp, z, (unsigned)cap);
@@ -1133,9 +1133,9 @@ int mpm_halo_add(mpm_handle_t e, const void* dev_buf, size_t cap) try {
     READY(e);
     REQUIRE(e->grid_state == 3, "halo add needs mpm_grid_gather first");
     REQUIRE(dev_buf && cap > 0, "bad halo buffer");
-    HaloBufs hb{};
-    hb.buf[0] = static_cast<const uint32_t*>(dev_buf);
-    hipLaunchKernelGGL(k_halo_add2, dim3(64, 1), dim3(256), 0, e->stream, e->dp, hb, (unsigned)cap);
+    Zones z{};
+    z.buf[0] = static_cast<uint32_t*>(const_cast<void*>(dev_buf));   // (read only)
+    hipLaunchKernelGGL(k_halo_add2, dim3(64, 1), dim3(256), 0, e->stream, e->dp, z, (unsigned)cap);
     return 0;
 } MPM_CATCH_ALL
 
@@ -1238,10 +1238,10 @@ static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void*
     REQUIRE(e->grid_state == 3, "mpm_substep_end_halo without mpm_substep_begin_halo");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
-    HaloBufs b{};
+    Zones b{};   // (read only)
     for (int i = 0; i < n; ++i) {
         REQUIRE(recv_bufs[i], "null halo buffer");
-        b.buf[i] = static_cast<const uint32_t*>(recv_bufs[i]);
+        b.buf[i] = static_cast<uint32_t*>(const_cast<void*>(recv_bufs[i]));
     }
     DP p = e->dp;
     p.lean_g2p = lean && !e->dp.dist.on;
@@ -1256,7 +1256,7 @@ static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void*
     if (folded) {
         halo_zones_into(e, &pg.halo_pn, pg.halo_plo, pg.halo_phi);
         pg.halo_pcap = (unsigned)cap;
-        for (int i = 0; i < n; ++i) pg.halo_pbuf[i] = const_cast<uint32_t*>(b.buf[i]);
+        for (int i = 0; i < n; ++i) pg.halo_pbuf[i] = b.buf[i];
     }
     if (n > 0 && !folded) hipLaunchKernelGGL(k_halo_add2, dim3(64, n), dim3(256), 0, e->stream, p, b, (unsigned)cap);
     enqueue_substep_rest(e, GridForm::FromSums, pg, gc, with_g2p ? &p : nullptr, dt);

@@ -27,14 +27,12 @@
         // the zone its buffer belongs to would be dropped without a trace.  The first few workgroups look at 64 ids each.
         for (int k = 0; k < p.halo_pn; ++k) {
             const uint32_t* buf = p.halo_pbuf[k];
-            const unsigned n = min(buf[0], p.halo_pcap);
+            const unsigned n = zbuf_count(buf, p.halo_pcap);
             for (unsigned e = blockIdx.x * 64u + (unsigned)tid; e < n; e += gridDim.x * 64u) {
-                const uint32_t id = buf[halo_ids_offset() + e];
-                if (id >= p.nblocks) {   // (no sender writes such an id: the buffer is not a halo buffer of this grid)
-                    atomicOr(&p.ctl->error, ERR_HALO);
-                    continue;
-                }
-                if (p.lut_act[id] < 0) continue;   // nothing of ours reaches that block
+                uint32_t id;
+                const int a = zbuf_entry_block(p, buf, e, &id);
+                if (a == ZBUF_BAD_ID) atomicOr(&p.ctl->error, ERR_HALO);   // (the buffer is not a halo buffer of this grid)
+                if (a < 0) continue;
                 int hx, hy, hz;
                 block_coords(id, hx, hy, hz);
                 if (hx < p.halo_plo[k] || hx > p.halo_phi[k]) atomicOr(&p.ctl->error, ERR_CAPACITY);
@@ -62,17 +60,8 @@
                 for (int k = 0; k < p.halo_pn; ++k) {
                     if (bx < p.halo_plo[k] || bx > p.halo_phi[k]) continue;   // wave-uniform
                     const uint32_t* buf = p.halo_pbuf[k];
-                    const unsigned n = min(buf[0], p.halo_pcap);
-                    int found = -1;
-                    for (unsigned base = 0; base < n && found < 0; base += 64) {
-                        const uint32_t id = base + (unsigned)cell < n ? buf[halo_ids_offset() + base + (unsigned)cell] : 0xFFFFFFFFu;
-                        const unsigned long long m = __ballot(id == myid);
-                        if (m) found = (int)base + __builtin_ctzll(m);
-                    }
-                    if (found >= 0) {
-                        const float4 r = (reinterpret_cast<const float4*>(buf) + halo_data_offset(p.halo_pcap))[(size_t)found * 64 + cell];
-                        s.x += r.x; s.y += r.y; s.z += r.z; s.w += r.w;
-                    }
+                    const int found = zbuf_find(buf, zbuf_count(buf, p.halo_pcap), myid);
+                    if (found >= 0) zbuf_add<1>(buf, p.halo_pcap, (unsigned)found, &s);
                 }
             }
         }
@@ -131,15 +120,9 @@
                     const int nbx = bx + p.halo_pshift[k];
                     if (nbx < 0 || nbx >= p.nb) continue;
                     uint32_t* buf = p.halo_pbuf[k];
-                    unsigned slot = 0;
-                    if (cell == 0) slot = atomicAdd(p.halo_pcnt[k] ? p.halo_pcnt[k] : &buf[0], 1u);   // (a LOCAL word: see DP::halo_pcnt)
-                    slot = __builtin_amdgcn_readfirstlane(slot);
-                    if (slot >= p.halo_pcap) {
-                        if (cell == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
-                        continue;
-                    }
-                    if (cell == 0) buf[halo_ids_offset() + slot] = block_id((uint32_t)nbx, (uint32_t)by, (uint32_t)bz);
-                    (reinterpret_cast<float4*>(buf) + halo_data_offset(p.halo_pcap))[(size_t)slot * 64 + cell] = s;
+                    const int slot = zbuf_claim(p.halo_pcnt[k] ? p.halo_pcnt[k] : &buf[0], p.halo_pcap, p.ctl);   // (see DP::halo_pcnt)
+                    if (slot < 0) continue;
+                    zbuf_store<1>(buf, p.halo_pcap, (unsigned)slot, block_id((uint32_t)nbx, (uint32_t)by, (uint32_t)bz), &s);
                 }
             }
             continue;

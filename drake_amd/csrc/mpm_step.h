@@ -8,6 +8,7 @@
 #pragma once
 #include "mpm_device.h"
 #include "mpm_fields.h"
+#include "mpm_zone_buffer.h"
 
 namespace mpm {
 
@@ -685,9 +686,6 @@ MPM_DEV int __reduce_max_sync_i32(int v) {
     return v;
 }
 
-// halo buffer layout: [0] count, [4..) block ids (cap), then cap * 64 float4 (see the multi-GPU section below)
-MPM_DEV size_t halo_ids_offset() { return 4; }                       // in uint32 units
-MPM_DEV size_t halo_data_offset(unsigned cap) { return ((size_t)(4 + cap) * 4 + 15) / 16; }  // in float4 units
 template <int MODE>
 __global__ __launch_bounds__(256) void k_grid(DP p, GridColliders gc) {
 #define MPM_GRID_BODIES 0
@@ -913,89 +911,59 @@ __global__ __launch_bounds__(G2P_THREADS) __attribute__((amdgpu_waves_per_eu(G2P
 // the local gather (k_grid<0>) a rank packs the raw node sums of its active blocks in the layers
 // next to a cut, relabelled into the neighbour's block coordinates; the neighbour adds them to
 // its own sums (k_halo_add) and both then run the same grid update (k_grid<2>) on shared blocks.
-// Buffer: [0] count, [4..) block ids (cap), then cap * 64 float4.
+// The buffers are zone exchange buffers with one vector per cell (mpm_zone_buffer.h).
 // ---------------------------------------------------------------------------
 
 // both zones / both received buffers of a chain rank in one launch each (blockIdx.y selects)
-struct HaloZones {
-    int lo[2], hi[2], shift[2];
-    uint32_t* buf[2];
-};
-__global__ __launch_bounds__(256) void k_halo_pack2(DP p, HaloZones z, unsigned cap) {
+__global__ __launch_bounds__(256) void k_halo_pack2(DP p, Zones z, unsigned cap) {
     const int k = blockIdx.y;
     uint32_t* buf = z.buf[k];
-    const int bx_lo = z.lo[k], bx_hi = z.hi[k], shift_bx = z.shift[k];
     const unsigned n_active = p.ctl->n_active;
-    float4* data = reinterpret_cast<float4*>(buf) + halo_data_offset(cap);
     for (unsigned a = blockIdx.x * 4 + (threadIdx.x >> 6); a < n_active; a += gridDim.x * 4) {
         int bx, by, bz;
         block_coords(p.act_block[a], bx, by, bz);
-        if (bx < bx_lo || bx > bx_hi) continue;   // wave-uniform
-        const int nbx = bx + shift_bx;
+        if (bx < z.lo[k] || bx > z.hi[k]) continue;   // wave-uniform
+        const int nbx = bx + z.shift[k];
         if (nbx < 0 || nbx >= p.nb) continue;
-        unsigned slot = 0;
-        if ((threadIdx.x & 63) == 0) slot = atomicAdd(&buf[0], 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
-        if (slot >= cap) {
-            if ((threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
-            continue;
-        }
-        if ((threadIdx.x & 63) == 0) buf[halo_ids_offset() + slot] = block_id((uint32_t)nbx, (uint32_t)by, (uint32_t)bz);
-        data[(size_t)slot * 64 + (threadIdx.x & 63)] = p.gv[(size_t)a * 64 + (threadIdx.x & 63)];
+        const int slot = zbuf_claim(&buf[0], cap, p.ctl);
+        if (slot < 0) continue;
+        zbuf_store<1>(buf, cap, (unsigned)slot, block_id((uint32_t)nbx, (uint32_t)by, (uint32_t)bz), p.gv + (size_t)a * 64 + (threadIdx.x & 63));
     }
 }
-struct HaloBufs {
-    const uint32_t* buf[2];
-};
 
 // ---- DIRECT halo (peer-to-peer stores + sequence flags) ---------------------------------------------------------------
 // k_grid<0> of substep s has stored the zone sums into the neighbours' receive buffers (its halo_pbuf point into peer
 // memory).  This one-thread kernel, behind it on the same stream, tells the neighbours: the kernel boundary in front of
-// it has made those stores complete; the system-scope fence and release store order the flag behind them for an observer
-// on another device.  (Cross-device ordering cannot be observed on a box with one GPU: the protocol, not its memory
-// model, is what the one-GPU tests exercise -- DESIGN.md section 5.)
-// (cnt_* / hdr_*: the pack kernel counted its entries in words of THIS device's memory -- no returning atomic on peer
-// memory --; the counts go into the neighbours' buffer headers here, in front of the flags)
+// it has made those stores complete; publish_then_flag orders the flag behind them for an observer on another device.
+// (Cross-device ordering cannot be observed on a box with one GPU: the protocol, not its memory model, is what the
+// one-GPU tests exercise -- DESIGN.md section 5.)  cnt_* / hdr_*: the pack counted its entries in words of THIS device's
+// memory (zbuf_claim); the counts go into the neighbours' buffer headers here, in front of the flags.
 __global__ void k_halo_signal(uint32_t* flag_a, uint32_t* flag_b, uint32_t seq, const uint32_t* cnt_a, uint32_t* hdr_a,
                               const uint32_t* cnt_b, uint32_t* hdr_b, unsigned cap) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     if (hdr_a) __hip_atomic_store(hdr_a, min(*cnt_a, cap), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     if (hdr_b) __hip_atomic_store(hdr_b, min(*cnt_b, cap), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    __threadfence_system();
-    // (MI355X_MICROARCH.md, "Compiler hazard": the wait behind the write-back may be dropped when the wave's vmcnt is
-    // provably empty -- the flag could then overtake the data; an inline-asm wait is invisible to that pass)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if (flag_a) __hip_atomic_store(flag_a, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    if (flag_b) __hip_atomic_store(flag_b, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    publish_then_flag(2, seq, [&](int k) { return k == 0 ? flag_a : flag_b; });
 }
-// ... and this one, one wave, waits until both neighbours have said so for substep `seq` (sequence numbers only grow:
-// signed difference), BOUNDED: after `timeout_ticks` of the 100 MHz wall clock it gives up and raises ERR_HALO, so that a
-// neighbour that never arrives is an error code, not a hung device.  The kernel boundary behind it is the acquire for
-// k_grid<2>, which then reads the received sums (fine-grained memory: not held in this device's L2).
+// ... and this one, one thread, waits (wait_flag: bounded) until both neighbours have said so for substep `seq`; a
+// neighbour that never arrives raises ERR_HALO.  The kernel boundary behind it is the acquire for k_grid<2>, which then
+// reads the received sums (fine-grained memory: not held in this device's L2).
 __global__ void k_halo_wait(const uint32_t* flag_a, const uint32_t* flag_b, uint32_t seq, unsigned long long timeout_ticks, Ctl* ctl) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     const unsigned long long t0 = wall_clock64();
-    while (true) {
-        const bool a = !flag_a || (int)(__hip_atomic_load(flag_a, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - seq) >= 0;
-        const bool b = !flag_b || (int)(__hip_atomic_load(flag_b, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - seq) >= 0;
-        if (a && b) return;
-        if (wall_clock64() - t0 > timeout_ticks) {
-            atomicOr(&ctl->error, ERR_HALO);
-            return;
-        }
-        __builtin_amdgcn_s_sleep(20);
-    }
+    bool ok = true;
+    if (flag_a) ok &= wait_flag<20>(flag_a, seq, t0, timeout_ticks);
+    if (flag_b) ok &= wait_flag<20>(flag_b, seq, t0, timeout_ticks);
+    if (!ok) atomicOr(&ctl->error, ERR_HALO);
 }
 // (a block lies in one zone only, so the two buffers of a launch touch disjoint cells)
-__global__ __launch_bounds__(256) void k_halo_add2(DP p, HaloBufs b, unsigned cap) {
-    const uint32_t* buf = b.buf[blockIdx.y];
-    const unsigned n = min(buf[0], cap);
-    const float4* data = reinterpret_cast<const float4*>(buf) + halo_data_offset(cap);
+__global__ __launch_bounds__(256) void k_halo_add2(DP p, Zones z, unsigned cap) {
+    const uint32_t* buf = z.buf[blockIdx.y];
+    const unsigned n = zbuf_count(buf, cap);
     for (unsigned e = blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += gridDim.x * 4) {
-        const uint32_t id = buf[halo_ids_offset() + e];
-        if (id >= p.nblocks) continue;
-        const int a = p.lut_act[id];
-        if (a < 0) continue;  // nothing of ours reaches that block
+        uint32_t id;
+        const int a = zbuf_entry_block(p, buf, e, &id);
+        if (a < 0) continue;
         if (p.halo_nz > 0) {  // with a split update only zone blocks are still raw sums
             int hx, hy, hz;
             block_coords(id, hx, hy, hz);
@@ -1004,11 +972,7 @@ __global__ __launch_bounds__(256) void k_halo_add2(DP p, HaloBufs b, unsigned ca
                 continue;
             }
         }
-        const size_t g = (size_t)a * 64 + (threadIdx.x & 63);
-        const float4 r = data[(size_t)e * 64 + (threadIdx.x & 63)];
-        float4 q = p.gv[g];
-        q.x += r.x; q.y += r.y; q.z += r.z; q.w += r.w;
-        p.gv[g] = q;
+        zbuf_add<1>(buf, cap, e, p.gv + (size_t)a * 64 + (threadIdx.x & 63));
     }
 }
 

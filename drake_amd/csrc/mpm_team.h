@@ -49,7 +49,7 @@ MPM_DEV bool team_gate_closed(const ContactDev& c, int gate) {
 
 // ---- zone exchange of a per-node field (NV float4 per cell) with the two neighbours ---------------------------------
 // pack: like k_zone_pack, but straight into the NEIGHBOUR's slot of this exchange's parity; entries are counted in a word
-// of this rank's own memory (no returning atomic on peer memory), the count travels with the signal
+// of this rank's own memory (zbuf_claim), the count travels with the signal
 template <int NV>
 __global__ __launch_bounds__(256) void k_team_zone_pack(DP p, ContactDev c, TeamDev t, const float4* field, int gate) {
     if (team_gate_closed(c, gate)) return;
@@ -59,23 +59,14 @@ __global__ __launch_bounds__(256) void k_team_zone_pack(DP p, ContactDev c, Team
     const int parity = (int)(t.ts->z_seq & 1u);
     // what goes to the left arrives "from the right" over there
     uint32_t* buf = reinterpret_cast<uint32_t*>(team_zone_slot(t.peer[nbr], t.zone_bytes, 1 - side, parity));
-    float4* data = reinterpret_cast<float4*>(buf) + zone_data_offset(t.zone_cap);
     const unsigned n_active = p.ctl->n_active;
     for (unsigned a = blockIdx.x * 4 + (threadIdx.x >> 6); a < n_active; a += gridDim.x * 4) {
         int bx, by, bz;
         block_coords(p.act_block[a], bx, by, bz);
         if (bx < t.lo[side] || bx > t.hi[side]) continue;   // wave-uniform
-        unsigned slot = 0;
-        if ((threadIdx.x & 63) == 0) slot = atomicAdd(&t.ts->cnt[side], 1u);
-        slot = __builtin_amdgcn_readfirstlane(slot);
-        if (slot >= t.zone_cap) {
-            if ((threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
-            continue;
-        }
-        if ((threadIdx.x & 63) == 0) buf[4 + slot] = p.act_block[a];
-        const size_t cell = (size_t)a * 64 + (threadIdx.x & 63);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) data[((size_t)slot * 64 + (threadIdx.x & 63)) * NV + v] = field[cell * NV + v];
+        const int slot = zbuf_claim(&t.ts->cnt[side], t.zone_cap, p.ctl);
+        if (slot < 0) continue;
+        zbuf_store<NV>(buf, t.zone_cap, (unsigned)slot, p.act_block[a], field + ((size_t)a * 64 + (threadIdx.x & 63)) * NV);
     }
 }
 // one thread, behind the pack's kernel boundary: the counts into the neighbours' headers, then the flags
@@ -92,15 +83,10 @@ __global__ void k_team_zone_signal(ContactDev c, TeamDev t, int gate) {
         __hip_atomic_store(hdr, min(ts->cnt[side], t.zone_cap), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         ts->cnt[side] = 0u;
     }
-    __threadfence_system();
-    // (MI355X_MICROARCH.md, "Compiler hazard": the wait behind the write-back may be dropped when the wave's vmcnt is
-    // provably empty -- the flag could then overtake the data; an inline-asm wait is invisible to that pass)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    for (int side = 0; side < 2; ++side) {
+    publish_then_flag(2, seq, [&](int side) -> uint32_t* {
         const int nbr = side == 0 ? t.left : t.right;
-        if (nbr < 0) continue;
-        __hip_atomic_store(team_zone_flag(t.peer[nbr], t.zone_bytes, 1 - side), seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
+        return nbr < 0 ? nullptr : team_zone_flag(t.peer[nbr], t.zone_bytes, 1 - side);
+    });
 }
 // one thread: waits for both neighbours' signals of this exchange, then moves the counters on (the add kernel behind the
 // kernel boundary reads z_cur: no kernel reads a counter that another thread of the same launch writes)
@@ -111,8 +97,8 @@ __global__ void k_team_zone_wait(ContactDev c, TeamDev t, int gate, Ctl* ctl) {
     const uint32_t q = ts->z_seq;
     const unsigned long long t0 = wall_clock64();
     bool ok = true;
-    if (t.left >= 0) ok &= team_wait_flag(team_zone_flag(t.peer[t.rank], t.zone_bytes, 0), q + 1u, t0, t.timeout_ticks);
-    if (t.right >= 0) ok &= team_wait_flag(team_zone_flag(t.peer[t.rank], t.zone_bytes, 1), q + 1u, t0, t.timeout_ticks);
+    if (t.left >= 0) ok &= wait_flag<TEAM_SLEEP>(team_zone_flag(t.peer[t.rank], t.zone_bytes, 0), q + 1u, t0, t.timeout_ticks);
+    if (t.right >= 0) ok &= wait_flag<TEAM_SLEEP>(team_zone_flag(t.peer[t.rank], t.zone_bytes, 1), q + 1u, t0, t.timeout_ticks);
     if (!ok) {
         atomicOr(&ctl->error, ERR_HALO);
         ts->timeouts += 1u;
@@ -126,21 +112,11 @@ __global__ __launch_bounds__(256) void k_team_zone_add(DP p, ContactDev c, TeamD
     const int side = blockIdx.y;
     if ((side == 0 ? t.left : t.right) < 0) return;
     const uint32_t* buf = reinterpret_cast<const uint32_t*>(team_zone_slot(t.peer[t.rank], t.zone_bytes, side, (int)(t.ts->z_cur & 1u)));
-    const unsigned n = min(buf[0], t.zone_cap);
-    const float4* data = reinterpret_cast<const float4*>(buf) + zone_data_offset(t.zone_cap);
+    const unsigned n = zbuf_count(buf, t.zone_cap);
     for (unsigned e = blockIdx.x * 4 + (threadIdx.x >> 6); e < n; e += gridDim.x * 4) {
-        const uint32_t id = buf[4 + e];
-        if (id >= p.nblocks) continue;
-        const int a = p.lut_act[id];
-        if (a < 0) continue;   // nothing of this rank reaches that block
-        const size_t cell = (size_t)a * 64 + (threadIdx.x & 63);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-            const float4 r = data[((size_t)e * 64 + (threadIdx.x & 63)) * NV + v];
-            float4 q = field[cell * NV + v];
-            q.x += r.x; q.y += r.y; q.z += r.z; q.w += r.w;
-            field[cell * NV + v] = q;
-        }
+        const int a = zbuf_entry_block(p, buf, e);
+        if (a < 0) continue;
+        zbuf_add<NV>(buf, t.zone_cap, e, field + ((size_t)a * 64 + (threadIdx.x & 63)) * NV);
     }
 }
 

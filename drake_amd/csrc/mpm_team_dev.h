@@ -1,16 +1,18 @@
 // Device-side pieces of the TEAM transport that the contact kernels themselves use (k_ct_keys, k_ct_decide): the layout of
-// a rank's region, the bounded flag wait, and the push / collect of the line-search sums.  See mpm_team.h for the
-// protocol and for the zone-exchange and status kernels.
+// a rank's region and the push / collect of the line-search sums.  See mpm_team.h for the protocol and for the
+// zone-exchange and status kernels, mpm_zone_buffer.h for the zone slots' format and the flag helpers.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "mpm_device.h"
+#include "mpm_zone_buffer.h"
 
 namespace mpm {
 
 constexpr int TEAM_MAX = 8;          // ranks of one node
 constexpr int TEAM_RED = 32;         // doubles per rank and reduction (ContactState::red)
+constexpr int TEAM_SLEEP = 10;       // s_sleep between two looks at a flag (wait_flag)
 
 struct TeamState {                   // device memory of THIS rank, zero at set-up, never reset afterwards
     unsigned z_seq;                  // zone exchanges this rank has completed (k_team_zone_wait)
@@ -34,8 +36,7 @@ struct TeamDev {                     // kernel argument
 
 // ---- region layout (host and device) ----------------------------------------------------------------------------
 __host__ __device__ inline size_t team_zone_slot_bytes(size_t cap) {
-    const size_t b = (((4 + cap) * 4 + 15) / 16) * 16 + cap * 64 * 3 * 16;   // header + ids, then 3 float4 per cell
-    return (b + 255) & ~(size_t)255;
+    return (zone_buffer_bytes(cap, 3) + 255) & ~(size_t)255;   // (H, G): 3 float4 per cell
 }
 __host__ __device__ inline size_t team_region_bytes(size_t zone_bytes) {
     return 4 * zone_bytes + (size_t)2 * TEAM_MAX * TEAM_RED * 8 + (size_t)(2 + TEAM_MAX) * 64;
@@ -53,15 +54,6 @@ __host__ __device__ inline uint32_t* team_sum_flag(char* base, size_t zone_bytes
     return reinterpret_cast<uint32_t*>(base + 4 * zone_bytes + (size_t)2 * TEAM_MAX * TEAM_RED * 8 + (size_t)(2 + src) * 64);
 }
 
-// bounded wait for `flag >= seq` (sequence numbers only grow: signed difference)
-MPM_DEV bool team_wait_flag(const uint32_t* flag, uint32_t seq, unsigned long long t0, unsigned long long timeout_ticks) {
-    while (true) {
-        if ((int)(__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - seq) >= 0) return true;
-        if (wall_clock64() - t0 > timeout_ticks) return false;
-        __builtin_amdgcn_s_sleep(10);
-    }
-}
-
 // ---- sums over all ranks ------------------------------------------------------------------------------------------
 // One wave: lane l < TEAM_RED holds this rank's l-th partial sum; it goes into the slot [parity][this rank] of EVERY
 // rank's region (its own included: the consumer adds all slots alike), then the flags.
@@ -75,12 +67,8 @@ MPM_DEV void team_push_sums(const TeamDev& t, double v) {
             __hip_atomic_store(reinterpret_cast<unsigned long long*>(slot) + lane, (unsigned long long)__double_as_longlong(v),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
-    __threadfence_system();   // (one wave: the fence is the wave's, it covers every lane's stores)
-    // (MI355X_MICROARCH.md, "Compiler hazard": the wait behind the write-back may be dropped when the wave's vmcnt is
-    // provably empty -- the flag could then overtake the data; an inline-asm wait is invisible to that pass)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    for (int d = 0; d < t.world; ++d)
-        if (lane == 0) __hip_atomic_store(team_sum_flag(t.peer[d], t.zone_bytes, t.rank), q + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    // (one wave: the fence in there is the wave's, it covers every lane's stores)
+    publish_then_flag(t.world, q + 1u, [&](int d) { return lane == 0 ? team_sum_flag(t.peer[d], t.zone_bytes, t.rank) : nullptr; });
 }
 // Wave 0 of a workgroup: waits (bounded) until every rank's sums of this reduction have arrived, adds them IN RANK ORDER
 // (the same order on every rank: identical bits, identical decisions) and returns lane l's total.  *ok = false: a rank
@@ -92,7 +80,7 @@ MPM_DEV double team_collect_sums(const TeamDev& t, Ctl* ctl, bool* ok_out) {
     const int parity = (int)(q & 1u);
     const unsigned long long t0 = wall_clock64();
     bool ok = true;
-    if (lane < t.world) ok = team_wait_flag(team_sum_flag(t.peer[t.rank], t.zone_bytes, lane), q + 1u, t0, t.timeout_ticks);
+    if (lane < t.world) ok = wait_flag<TEAM_SLEEP>(team_sum_flag(t.peer[t.rank], t.zone_bytes, lane), q + 1u, t0, t.timeout_ticks);
     ok = __ballot(!ok) == 0ull;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");   // (system scope: the loads below must not be served from before the flags)
     double v = 0.0;

@@ -39,7 +39,8 @@ pack_ref    {relabelled block id: (64, 4) float32} of the active blocks of a zon
 add_ref     float32 add per cell for the listed blocks that are active; everything else untouched
 update_ref  tl.grid32 on the result: what GRID_MASSES / GRID_MOMENTUM / GRID_V_STAR hold after k_grid<2>
 selected / selected_pm1   halo_block_selected and halo_item_selected: the two passes of the split update
-buffer layout             mpm_halo_buffer_bytes: word 0 the count, ids from word 4, the sums 16-byte aligned behind
+buffer layout             mpm_zone_buffer.h (mpm_halo_buffer_bytes): word 0 the count, ids from word 4, the sums 16-byte
+                          aligned behind
 
 Bound of a sum formed in two halves (u = 2^-24)
 --------
@@ -164,7 +165,7 @@ def selected_pm1(bx, zones, cls):
     return np.ones(bx.shape, bool) if cls < 0 else near == bool(cls)
 
 
-# ---- buffer layout (mpm_halo_buffer_bytes, halo_ids_offset, halo_data_offset) -----------------------------------------
+# ---- buffer layout (mpm_halo_buffer_bytes; zbuf_ids_offset, zbuf_data_offset, zone_buffer_bytes in mpm_zone_buffer.h) ---
 def buffer_bytes(cap):
     return (((4 + cap) * 4 + 15) // 16) * 16 + cap * 64 * 16
 
