@@ -219,6 +219,29 @@ class ClothMaterial(C.Structure):
         return {f: float(getattr(self, f)) for f, _ in self._fields_}
 
 
+# mpm_cloth_measure_t (184 bytes) as a numpy record: GpuMpm.measure returns arrays of it, so that rows compare bit by bit
+MEASURE_DTYPE = np.dtype([
+    ("mass", "<f8"), ("mass_position", "<f8", 3), ("momentum", "<f8", 3), ("angular_momentum", "<f8", 3),
+    ("affine_angular_momentum", "<f8", 3), ("kinetic", "<f8"), ("kinetic_affine", "<f8"), ("gravity_potential", "<f8"),
+    ("elastic_in_plane", "<f8"), ("elastic_normal", "<f8"), ("elastic_shear", "<f8"), ("bending", "<f8"),
+    ("stretch_max", "<f4"), ("stretch_min", "<f4"), ("normal_min", "<f4"), ("speed_max", "<f4"),
+    ("faces", "<u4"), ("vertices", "<u4")])
+assert MEASURE_DTYPE.itemsize == 184
+
+
+def cloth_energy_density(material: "ClothMaterial", F):
+    """mpm_cloth_energy_density: (n, 6) float64 rows s1, s2, r22, psi_in, psi_n, psi_s of the row-major float32
+    deformation gradients F (n, 3, 3) under `material` -- the function of mpm_measure's kernels, compiled for the host.
+    Needs no engine and no GPU."""
+    lib = load_library()
+    F = np.ascontiguousarray(F, np.float32).reshape(-1, 9)
+    out = np.zeros((len(F), 6), np.float64)
+    rc = lib.mpm_cloth_energy_density(C.byref(material), len(F), F.ctypes.data, out.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return out
+
+
 class ContactMaterial(C.Structure):
     """mpm_contact_material_t: a rigid body's contact parameters; a field < 0 inherits the solving call's scalar"""
     _fields_ = [("friction_mu", C.c_float), ("stiffness", C.c_float), ("damping", C.c_float)]
@@ -318,7 +341,7 @@ SYMBOLS = [
     "mpm_get_grid_bodies", "mpm_set_force_fields", "mpm_get_force_fields", "mpm_force_field_acceleration",
     "mpm_debug_resort_tables", "mpm_debug_sort_pairs", "mpm_set_body_contact_materials",
     "mpm_get_body_contact_materials", "mpm_set_bending", "mpm_get_bending", "mpm_bending_forces",
-    "mpm_bending_max_stable_dt", "mpm_bending_matrix",
+    "mpm_bending_max_stable_dt", "mpm_bending_matrix", "mpm_measure", "mpm_face_strain", "mpm_cloth_energy_density",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -445,6 +468,9 @@ def load_library(build: bool = True):
         "mpm_bending_forces": [vp, vp],
         "mpm_bending_max_stable_dt": [vp, P(f)],
         "mpm_bending_matrix": [vp, sz, vp, sz, vp, vp, vp, sz, P(sz)],
+        "mpm_measure": [vp, vp, sz, P(sz), vp],
+        "mpm_face_strain": [vp, vp],
+        "mpm_cloth_energy_density": [vp, sz, vp, vp],
         "mpm_add_qr_cloth_with_material": [vp, vp, vp, sz, vp, sz, vp],
         "mpm_get_cloth_info": [vp, sz, P(sz), P(sz), P(sz), P(sz), vp],
         "mpm_cloth_count": [vp, P(sz)],
@@ -727,6 +753,23 @@ class GpuMpm:
         dt = C.c_float()
         self._ck(self.lib.mpm_bending_max_stable_dt(self.h, C.byref(dt)))
         return float(dt.value)
+
+    def measure(self, capacity: int | None = None):
+        """mpm_measure: (rows, total) -- one MEASURE_DTYPE record per cloth (the first `capacity` of them if given) and
+        the record of their sum: masses, momenta, kinetic / potential / elastic / bending energies, strain extremes.
+        Reduced on the device in double, in original id order: the same bits whatever the particle order."""
+        n = C.c_size_t()
+        cap = self.cloth_count() if capacity is None else int(capacity)
+        rows = np.zeros(cap, MEASURE_DTYPE)
+        total = np.zeros((), MEASURE_DTYPE)
+        self._ck(self.lib.mpm_measure(self.h, rows.ctypes.data if cap else None, cap, C.byref(n), total.ctypes.data))
+        return rows[:min(cap, int(n.value))], total
+
+    def face_strain(self):
+        """mpm_face_strain: (n_faces, 4) float32 rows s1, s2, r22, V psi in original face order."""
+        out = np.zeros((self.n_faces, 4), np.float32)
+        self._ck(self.lib.mpm_face_strain(self.h, _ptr(out) if out.size else None))
+        return out
 
     def get_grid_bodies(self):
         """mpm_get_grid_bodies: the table in force, a list of GridBody."""

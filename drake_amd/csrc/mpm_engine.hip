@@ -3466,3 +3466,147 @@ int mpm_bending_max_stable_dt(mpm_handle_t e, float* dt_out) try {
 } MPM_CATCH_ALL
 
 }  // extern "C"
+
+// ---- the per-cloth report (mpm_measure, mpm_face_strain, mpm_cloth_energy_density; mpm_measure.h) ----
+// The chunk table: every cloth's faces, then every cloth's vertices, in runs of at most MEASURE_CHUNK original ids that
+// never straddle a cloth.  Built once; the vertex chunks' rows of the bending table follow mpm_set_bending.
+static int measure_ready(mpm_engine* e) {
+    mpm_engine::Measure& ms = e->measure;
+    const size_t nc = e->cloths.size();
+    if (!ms.built) {
+        std::vector<int4> chunks, ranges(nc, make_int4(0, 0, 0, 0));
+        const int nfg = e->dp.NfG;
+        for (int pass = 0; pass < 2; ++pass) {
+            for (size_t c = 0; c < nc; ++c) {
+                const mpm_engine::Cloth& cl = e->cloths[c];
+                const int first = pass == 0 ? (int)cl.first_face : nfg + (int)cl.first_vertex;
+                const int end = first + (int)(pass == 0 ? cl.n_faces : cl.n_verts);
+                (pass == 0 ? ranges[c].x : ranges[c].z) = (int)chunks.size();
+                for (int b = first; b < end; b += MEASURE_CHUNK) chunks.push_back(make_int4((int)c, b, std::min(end, b + MEASURE_CHUNK), -1));
+                (pass == 0 ? ranges[c].y : ranges[c].w) = (int)chunks.size();
+            }
+            if (pass == 0) ms.n_face_chunks = (int)chunks.size();
+        }
+        ms.n_vertex_chunks = (int)chunks.size() - ms.n_face_chunks;
+        FreshArrays fresh(e);
+        int4 *d_chunks = nullptr, *d_ranges = nullptr;
+        mpm_cloth_measure_t *d_rows = nullptr, *d_out = nullptr;
+        if (int rc = fresh.alloc(&d_chunks, chunks.size(), false)) return rc;
+        if (int rc = fresh.alloc(&d_ranges, nc, false)) return rc;
+        if (int rc = fresh.alloc(&d_rows, chunks.size(), true)) return rc;
+        if (int rc = fresh.alloc(&d_out, nc, true)) return rc;
+        if (nc) H2D(e, d_ranges, ranges.data(), nc * sizeof(int4));
+        fresh.commit();
+        ms.d_chunks = d_chunks; ms.d_ranges = d_ranges; ms.d_rows = d_rows; ms.d_out = d_out;
+        ms.chunks.swap(chunks);
+        ms.rows_stale = true;
+        ms.built = true;
+    }
+    if (ms.rows_stale || ms.k_seen != e->bend.k) {
+        // row of the bending table of every cloth's first vertex: the table holds the cloths with k > 0, in cloth order
+        std::vector<int> row0(nc, -1);
+        int r = 0;
+        for (size_t c = 0; c < nc && e->bend.on(); ++c)
+            if (c < e->bend.k.size() && e->bend.k[c] > 0.f) {
+                row0[c] = r;
+                r += (int)e->cloths[c].n_verts;
+            }
+        if (r != (e->bend.on() ? e->bend.args.n_rows : 0)) return fail(MPM_ERR_INTERNAL, "mpm_measure: the bending table does not match the cloths");
+        for (int k = ms.n_face_chunks; k < (int)ms.chunks.size(); ++k) {
+            int4& ch = ms.chunks[(size_t)k];
+            const int base = e->dp.NfG + (int)e->cloths[(size_t)ch.x].first_vertex;
+            ch.w = row0[(size_t)ch.x] < 0 ? -1 : row0[(size_t)ch.x] + (ch.y - base);
+        }
+        if (!ms.chunks.empty()) H2D(e, ms.d_chunks, ms.chunks.data(), ms.chunks.size() * sizeof(int4));
+        ms.k_seen = e->bend.k;
+        ms.rows_stale = false;
+    }
+    return 0;
+}
+static MeasureArgs measure_args(const mpm_engine* e) {
+    const mpm_engine::Measure& ms = e->measure;
+    MeasureArgs a{};
+    a.chunks = ms.d_chunks;
+    a.n_face_chunks = ms.n_face_chunks;
+    a.n_vertex_chunks = ms.n_vertex_chunks;
+    a.rows = ms.d_rows;
+    a.mats = e->multi_mat ? e->d_cloth_mat : nullptr;
+    a.bend = e->bend.args;
+    return a;
+}
+
+extern "C" {
+
+int mpm_measure(mpm_handle_t e, mpm_cloth_measure_t* per_cloth, size_t capacity, size_t* n_cloths_out,
+                mpm_cloth_measure_t* total) try {
+    READY(e);
+    REQUIRE(per_cloth || capacity == 0, "null output");
+    if (int rc = measure_ready(e)) return rc;
+    const size_t nc = e->cloths.size();
+    const MeasureArgs a = measure_args(e);
+    // at most three launches: face chunks, vertex chunks, one workgroup per cloth
+    if (a.n_face_chunks) hipLaunchKernelGGL(k_measure_faces, dim3((unsigned)a.n_face_chunks), dim3(256), 0, e->stream, e->dp, a);
+    if (a.n_vertex_chunks) hipLaunchKernelGGL(k_measure_vertices, dim3((unsigned)a.n_vertex_chunks), dim3(256), 0, e->stream, e->dp, a);
+    std::vector<mpm_cloth_measure_t> rows(nc);
+    if (nc) {
+        hipLaunchKernelGGL(k_measure_final, dim3((unsigned)nc), dim3(256), 0, e->stream, a, (const int4*)e->measure.d_ranges,
+                           e->measure.d_out);
+        HIP_TRY(hipGetLastError());
+        D2H(e, rows.data(), e->measure.d_out, nc * sizeof(mpm_cloth_measure_t));
+    }
+    std::copy(rows.begin(), rows.begin() + (long)std::min(capacity, nc), per_cloth);
+    if (n_cloths_out) *n_cloths_out = nc;
+    if (total) {
+        mpm_cloth_measure_t t{};
+        t.stretch_min = INFINITY;
+        t.normal_min = INFINITY;
+        double* ts = reinterpret_cast<double*>(&t);
+        for (const mpm_cloth_measure_t& r : rows) {
+            const double* rs = reinterpret_cast<const double*>(&r);
+            for (int k = 0; k < MEASURE_SUMS; ++k) ts[k] += rs[k];
+            t.stretch_max = std::max(t.stretch_max, r.stretch_max);
+            t.stretch_min = std::min(t.stretch_min, r.stretch_min);
+            t.normal_min = std::min(t.normal_min, r.normal_min);
+            t.speed_max = std::max(t.speed_max, r.speed_max);
+            t.faces += r.faces;
+            t.vertices += r.vertices;
+        }
+        *total = t;
+    }
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_face_strain(mpm_handle_t e, float* out) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "mpm_face_strain is")) return rc;
+    REQUIRE(out || e->nf == 0, "null output");
+    if (int rc = settle(e)) return rc;
+    if (e->nf == 0) return 0;
+    if (int rc = measure_ready(e)) return rc;
+    const MeasureArgs a = measure_args(e);
+    const size_t bytes = e->nf * 16;
+    if (int rc = e->stage(bytes)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
+    hipLaunchKernelGGL(k_measure_face_strain, dim3((unsigned)a.n_face_chunks), dim3(256), 0, e->stream, e->dp, a, (float*)e->d_stage);
+    HIP_TRY(hipGetLastError());
+    D2H(e, out, e->d_stage, bytes);
+    return 0;
+} MPM_CATCH_ALL
+
+// host code only: the device function of the kernels, compiled for the host
+int mpm_cloth_energy_density(const mpm_cloth_material_t* m, size_t n, const float* F, double* out) try {
+    REQUIRE(m, "null material");
+    REQUIRE((F && out) || n == 0, "null array");
+    // the Lame parameters as mpm_finalize forms them, in float
+    const float mu = m->youngs_modulus / (2.f * (1.f + m->poisson_ratio));
+    const float lambda = m->youngs_modulus * m->poisson_ratio / ((1.f + m->poisson_ratio) * (1.f - 2.f * m->poisson_ratio));
+    for (size_t i = 0; i < n; ++i) {
+        const float* f = F + 9 * i;
+        const double d1[3] = {(double)f[0], (double)f[3], (double)f[6]}, d2[3] = {(double)f[1], (double)f[4], (double)f[7]};
+        const double d3[3] = {(double)f[2], (double)f[5], (double)f[8]};
+        cloth_energy_density(mu, lambda, m->K, m->gamma, d1, d2, d3, out + 6 * i);
+    }
+    return 0;
+} MPM_CATCH_ALL
+
+}  // extern "C"

@@ -18,6 +18,7 @@
 #include "mpm_contact_dev.h"
 #include "mpm_pins.h"
 #include "mpm_bending.h"
+#include "mpm_measure.h"
 #include "mpm_grid_bodies.h"
 #include "mpm_team.h"
 #include "mpm_trace.h"
@@ -218,6 +219,18 @@ struct mpm_engine {
         float max_dt = INFINITY;         // 2 / sqrt(max_i (1 / m_i) sum_j |k Q_ij|) (fields_stable)
         bool on() const { return args.n_rows > 0; }
     } bend;
+    // the per-cloth report (mpm_measure, mpm_face_strain; mpm_measure.h): chunk table and scratch, made at first use
+    struct Measure {
+        bool built = false;
+        std::vector<int4> chunks;        // the host's copy of d_chunks (face chunks, then vertex chunks)
+        std::vector<float> k_seen;       // Bending::k the vertex chunks' rows of the bending table were worked out for
+        bool rows_stale = true;          // ... not yet
+        int n_face_chunks = 0, n_vertex_chunks = 0;
+        int4* d_chunks = nullptr;
+        int4* d_ranges = nullptr;        // [cloth] its chunks (k_measure_final)
+        mpm_cloth_measure_t* d_rows = nullptr;   // [chunk] partial sums
+        mpm_cloth_measure_t* d_out = nullptr;    // [cloth]
+    } measure;
     // fixed constraints (mpm_set_pins, mpm_set_body_motions; k_pin in mpm_pins.h)
     struct PinState {
         std::vector<mpm_pin_t> set;              // the caller's pins, in order

@@ -216,6 +216,33 @@ struct GpuMpmState {
         mpm_check(mpm_bending_max_stable_dt(h_, &dt));
         return dt;
     }
+    // Extension: the per-cloth report (mpm_measure) -- masses, momenta, kinetic, potential, elastic and bending energies,
+    // strain extremes, reduced on the device in double.  One row per cloth; `total`, if given, receives their sum.
+    // System::CalcKineticEnergy is total.kinetic + total.kinetic_affine, CalcPotentialEnergy is gravity_potential +
+    // elastic_in_plane + elastic_normal + elastic_shear + bending.  A synchronisation point.
+    std::vector<mpm_cloth_measure_t> Measure(mpm_cloth_measure_t* total = nullptr) const {
+        size_t n = 0;
+        mpm_check(mpm_cloth_count(h_, &n));
+        std::vector<mpm_cloth_measure_t> rows(n);
+        mpm_check(mpm_measure(h_, rows.data(), n, &n, total));
+        return rows;
+    }
+    double CalcKineticEnergy() const {
+        mpm_cloth_measure_t t;
+        mpm_check(mpm_measure(h_, nullptr, 0, nullptr, &t));
+        return t.kinetic + t.kinetic_affine;
+    }
+    double CalcPotentialEnergy() const {
+        mpm_cloth_measure_t t;
+        mpm_check(mpm_measure(h_, nullptr, 0, nullptr, &t));
+        return t.gravity_potential + t.elastic_in_plane + t.elastic_normal + t.elastic_shear + t.bending;
+    }
+    // (s1, s2, r22, V psi) per face in original face order (mpm_face_strain; single engines only)
+    std::vector<float> FaceStrain(size_t n_faces) const {
+        std::vector<float> s(4 * n_faces);
+        mpm_check(mpm_face_strain(h_, s.data()));
+        return s;
+    }
     std::vector<Vec3<T>>& positions_host() { return h_positions_; }
     const std::vector<Vec3<T>>& positions_host() const { return h_positions_; }
     ExternalSpatialForce<T>& external_forces_host() { return h_external_forces_; }

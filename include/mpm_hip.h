@@ -804,6 +804,68 @@ MPM_API int mpm_bending_max_stable_dt(mpm_handle_t h, float *dt_out);
 MPM_API int mpm_bending_matrix(const float *pos, size_t n_verts, const int32_t *indices, size_t n_faces, size_t *row_offsets,
                                int32_t *cols, double *vals, size_t capacity, size_t *nnz_out);
 
+/* ---- Energy, momentum and strain report per cloth (an extension) ----
+ * What System::CalcKineticEnergy / CalcPotentialEnergy answer for a Drake plant, and what a caller choosing dt or
+ * calibrating a stiffness needs: one device-side reduction instead of seven downloads and a host restatement of the
+ * constitutive model.  All arithmetic is in double, from the engine's float records:
+ *   m       the float MPM_ARR_MASSES returns for the particle.
+ *   vertex  x, v and C are the particle's own records.
+ *   face    x and v are the means of its three corner vertices' current x and v -- the state the next
+ *           CalcFemStateAndForce gives it; the face particle's own x / v record is stale inside and after the batched
+ *           substeps and is not used.  C is its own record.
+ *   D       dx^2 / 4, the second moment of the quadratic B-spline: 1/2 m D |C|_F^2 and m D (C21-C12, C02-C20, C10-C01)
+ *           are the kinetic energy and the angular momentum of the particle's affine velocity field on the grid.
+ *   strain  d1, d2 = (x_b - x_a, x_c - x_a) Dm^-1 from the CURRENT corner positions, d3 the stored normal column F[:,2].
+ *           a11 = d1.d1, a12 = d1.d2, a22 = d2.d2, J = sqrt(max(a11 a22 - a12^2, 0)), T = a11 + a22,
+ *           s1 +- s2 = sqrt(max(T +- 2 J, 0)) (the singular values of [d1 d2]); with n = d1 x d2, r22 = d3.n / |n|; a
+ *           face with |n| = 0 takes r22 = 0 and contributes no normal or shear energy.
+ *   energy  psi_in = mu ((s1-1)^2 + (s2-1)^2) + 1/2 lambda (J-1)^2,  psi_n = K/3 (1-r22)^3 if r22 < 1, else 0,
+ *           psi_s = 1/2 gamma max(|d3|^2 - r22^2, 0), with the floats mu, lambda, K, gamma the FEM kernel uses for the
+ *           face's cloth, times the face's rest volume V.  This is the published energy of Jiang et al. 2017, whose
+ *           gradient the FEM stress is for gamma = 0.  For gamma != 0 the report STATES this energy; no claim is made
+ *           that the stress the engine applies (the reference's) is its gradient.
+ *   bending E = -1/4 sum_i sum_{j != i} c_ij |x_j - x_i|^2 with c_ij the float coefficients of the table the bending
+ *           kernel reads (= 1/2 x^T k Q x: Q is symmetric with zero row sums), per cloth; 0 while bending is off.
+ *   The potentials of force fields (mpm_set_force_fields) are NOT reported: most of them (drag, wind) have none.
+ * gravity_potential is -sum m g x[gravity_axis] with g = mpm_material_t::gravity (signed) -- zero at the world origin.
+ * The sums are formed in ORIGINAL id order in a fixed tree, without floating-point atomics: a row is the same bits
+ * whatever the particle order (slot order, arrival order inside a cell, deterministic mode on or off). */
+typedef struct mpm_cloth_measure {
+    double mass;                        /* sum m                                          */
+    double mass_position[3];            /* sum m x        (centre of mass = this / mass)  */
+    double momentum[3];                 /* sum m v                                        */
+    double angular_momentum[3];         /* sum m x cross v, about the world origin        */
+    double affine_angular_momentum[3];  /* sum m D (C21-C12, C02-C20, C10-C01)            */
+    double kinetic;                     /* sum 1/2 m |v|^2                                */
+    double kinetic_affine;              /* sum 1/2 m D |C|_F^2                            */
+    double gravity_potential;           /* -sum m g x[gravity_axis], g = material.gravity */
+    double elastic_in_plane, elastic_normal, elastic_shear;   /* sum over faces of V psi_* */
+    double bending;                     /* 1/2 x^T (k Q) x of the cloth, 0 while off      */
+    float stretch_max, stretch_min;     /* max s1, min s2 over the faces                  */
+    float normal_min;                   /* min r22 over the faces                         */
+    float speed_max;                    /* max |v| over the VERTEX particles              */
+    uint32_t faces, vertices;           /* particles counted                              */
+} mpm_cloth_measure_t;                  /* 184 bytes */
+/* One row per cloth, in cloth order: min(mpm_cloth_count, capacity) rows into per_cloth (may be NULL when capacity is
+ * 0), the cloth count into *n_cloths_out, and into *total the sum of ALL the cloths' rows in cloth order, formed in
+ * double -- its extremes the max / min over the rows, its counts the sums of theirs.  Either output may be NULL.  A cloth
+ * with nothing counted reports stretch_max = speed_max = 0 and stretch_min = normal_min = +inf.
+ * Needs mpm_finalize (MPM_ERR_INVALID before).  Ordered on the engine's stream and a synchronisation point; substeps
+ * that mpm_run_substeps still owes are run first.  At most three kernel launches.  Changes no state, no counter of
+ * mpm_stats_t and no sticky error.
+ * A partitioned engine (mpm_dist_init) counts the particles the rank OWNS and skips the others: the ranks' rows add up
+ * to the scene's, and a multi-rank caller adds them itself. */
+MPM_API int mpm_measure(mpm_handle_t h, mpm_cloth_measure_t *per_cloth, size_t capacity, size_t *n_cloths_out,
+                        mpm_cloth_measure_t *total);
+/* The faces' terms of the report, per face: out[4 * n_faces] = (s1, s2, r22, V (psi_in + psi_n + psi_s)) as floats,
+ * in original face order.  Same calling rules as mpm_measure; refused (MPM_ERR_INVALID, nothing enqueued) on a
+ * partitioned or multi-rank engine. */
+MPM_API int mpm_face_strain(mpm_handle_t h, float *out);
+/* The energy density on the host (no handle, no device): the inline function of the report's kernels, compiled for
+ * the host.  F: n row-major 3x3 deformation gradients (columns d1, d2, d3); out[6 * n] = s1, s2, r22, psi_in, psi_n,
+ * psi_s in double.  The Lame parameters are formed from m in float, as mpm_finalize forms them. */
+MPM_API int mpm_cloth_energy_density(const mpm_cloth_material_t *m, size_t n, const float *F, double *out);
+
 /* Runs n substeps with HIP events around every kernel group on the engine's
  * stream and returns the mean milliseconds per substep of each phase
  * (phase_ms[MPM_PHASE_COUNT]) and of the whole substep.  The launches are those of mpm_run_substeps, but every substep

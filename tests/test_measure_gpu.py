@@ -1,0 +1,470 @@
+"""mpm_measure and mpm_face_strain on the engine, against the float64 restatement of tests/measure.py.
+
+The scene (domain_bits = 6): three cloths with materials of their own -- a 40 x 40 sheet (3042 faces: three face chunks, two
+vertex chunks), the 2-triangle strip (gamma > 0) and the fan of tests/bending.py (a hub of valence 12; another density).
+The state, uploaded with mpm_upload_particle_state: vertices displaced in and out of the plane, random v and C, the
+stored normal column of F compressed to 0.8 on even faces and stretched to 1.2 on odd ones, tilted by 0.05 towards the
+first tangent; bending on for the sheet and the fan.
+
+1. Every field of every row and of the total: the sums of float records within 1e-9 sum|terms|, the elastic sums within
+   8 x 2^-24 sum B, bending within 4 x 2^-24 x 1/4 sum |c_ij| |x_j - x_i|^2, extremes and counts equal to the reference
+   rounded to float (tests/measure.py has the reasons).
+2. mpm_face_strain per face: s1, s2, r22 equal to the reference rounded to float, V psi within 8 x 2^-24 V B plus the
+   rounding of the float it is returned in (2^-24 |V psi|: the row sums, kept in double, have no such term).
+3. The 184-byte rows are the same bits after mpm_rebuild_mapping(h, 1), on a deterministic and a non-deterministic engine,
+   and after substeps that forced a re-sort followed by the same upload.
+4. No side effects: every particle array and mpm_get_stats bit-equal around a call; a deterministic engine that measures
+   between batches ends bit-equal to a twin that never does.
+5. The momentum ParticleToGrid puts on the grid (see test_p2g_identity for the count of roundings).
+6. A state the engine reached itself: 30 coupled substeps onto a floor, bending and a drag field on; then item 1 again.
+7. Two ranks of one partitioned scene: counts add up exactly, the rows added in double agree with the single engine's.
+8. Calling convention."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from tests import bending as bd
+from tests import measure as ms
+from tests import transfer_layouts as tl
+
+pytestmark = pytest.mark.gpu
+
+U = ms.U
+DT = 2e-4
+DX = 1.0 / 64
+_CACHE = {}
+
+
+def _A():
+    from drake_amd import ARR
+    return ARR
+
+
+def _record(what, ratio):
+    from tests import helpers
+    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
+
+
+def _meshes():
+    if "meshes" not in _CACHE:
+        out = []
+        for (X, T), dz in ((bd.sheet(40, 40), 0.0), (bd.strip(), 0.06), (bd.fan(), -0.06)):
+            # (one spacing along x: the cut of the partitioned test, x = 32.5 cells, then goes through the strip too)
+            out.append(((X + np.array([bd.H0, 0.0, dz], np.float32)).astype(np.float32), T))
+        _CACHE["meshes"] = out
+    return _CACHE["meshes"]
+
+
+def _materials():
+    from drake_amd import ClothMaterial, GpuMpm
+    mats = [ClothMaterial.of(GpuMpm.default_material()) for _ in range(3)]
+    mats[1].youngs_modulus, mats[1].poisson_ratio, mats[1].gamma, mats[1].K, mats[1].c_F = 2.5e5, 0.25, 400.0, 6e4, 0.3
+    mats[2].youngs_modulus, mats[2].density = 6e5, 1300.0
+    return mats
+
+
+def _engine(deterministic=True, multi=True, bodies=0, meshes=None):
+    from drake_amd import GpuMpm
+    meshes = meshes or _meshes()
+    g = GpuMpm(6, GpuMpm.default_material())
+    g.set_deterministic(deterministic)
+    for (X, T), m in zip(meshes, _materials()):
+        g.add_qr_cloth(X, np.zeros_like(X), T, m if multi else None)
+    g.finalize()
+    if bodies:
+        g.reallocate_external_bodies(bodies)
+    return g
+
+
+def _download(g):
+    A = _A()
+    nf = g.n_faces
+    return dict(pids=g.download(A.PIDS), x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE),
+                m=g.download(A.MASSES), vol=g.download(A.VOLUMES), F=g.download(A.DEFORMATION_GRADIENTS),
+                dminv=g.download(A.DM_INVERSES), tri=g.download(A.INDICES).reshape(-1, 3) - nf)
+
+
+def _cloths(g):
+    out = []
+    for c in range(g.cloth_count()):
+        i = g.cloth_info(c)
+        m = i["material"]
+        out.append(dict(first_vertex=i["first_vertex"], n_verts=i["n_verts"], first_face=i["first_face"], n_faces=i["n_faces"],
+                        E=m.youngs_modulus, nu=m.poisson_ratio, K=m.K, gamma=m.gamma))
+    return out
+
+
+def _state():
+    """the uploaded state in original id order: x (nv, 3), v, C (np, ..), F (nf, 9); made once"""
+    if "state" in _CACHE:
+        return _CACHE["state"]
+    g = _engine()
+    d = _download(g)
+    g.destroy()
+    tri, nf = d["tri"], len(d["tri"])
+    r = np.random.default_rng(11)
+    X = np.concatenate([m[0] for m in _meshes()]).astype(np.float64)
+    nv = len(X)
+    x = (X + bd.H0 * r.normal(size=(nv, 3)) * np.array([0.05, 0.05, 0.15])).astype(np.float32)
+    v = np.zeros((nf + nv, 3), np.float32)
+    v[nf:] = 0.3 * r.normal(size=(nv, 3))
+    v[:nf] = v[nf:][tri].mean(axis=1)
+    Cm = (4.0 * r.normal(size=(nf + nv, 9))).astype(np.float32)
+    xd = x.astype(np.float64)
+    dm = d["dminv"].astype(np.float64)
+    e0, e1 = xd[tri[:, 1]] - xd[tri[:, 0]], xd[tri[:, 2]] - xd[tri[:, 0]]
+    d1, d2 = e0 * dm[:, 0:1] + e1 * dm[:, 2:3], e0 * dm[:, 1:2] + e1 * dm[:, 3:4]
+    n = np.cross(d1, d2)
+    n /= np.linalg.norm(n, axis=1)[:, None]
+    s = np.where(np.arange(nf) % 2 == 0, 0.8, 1.2)[:, None]
+    d3 = s * n + 0.05 * d1 / np.linalg.norm(d1, axis=1)[:, None]
+    F = np.stack([d1, d2, d3], axis=2).reshape(nf, 9).astype(np.float32)
+    _CACHE["state"] = dict(x=x, v=v, C=Cm, F=F, tri=tri)
+    return _CACHE["state"]
+
+
+def _upload(g, st=None, shift=(0.0, 0.0, 0.0)):
+    st = st or _state()
+    x = (st["x"] + np.asarray(shift, np.float32)).astype(np.float32)
+    pos = np.concatenate([x[st["tri"]].astype(np.float64).mean(axis=1).astype(np.float32), x])
+    pids = g.download(_A().PIDS)
+    g.upload_particle_state(pos[pids], st["v"][pids], st["C"][pids], None, st["F"])
+
+
+def _stiffness():
+    """[k] for the sheet and the fan such that DT is a quarter of mpm_bending_max_stable_dt; made once"""
+    if "ks" not in _CACHE:
+        g = _engine()
+        g.set_bending([1.0, 0.0, 1.0])
+        lim = g.bending_max_stable_dt()
+        g.destroy()
+        k = float(np.float32((0.25 * lim / DT) ** 2))
+        _CACHE["ks"] = [k, 0.0, k]
+    return _CACHE["ks"]
+
+
+def _bending_refs():
+    if "Q" not in _CACHE:
+        out = []
+        for (X, T), k in zip(_meshes(), _stiffness()):
+            out.append((k, bd.q_dense(len(X), bd.hinges(X, T))[0]) if k else None)
+        _CACHE["Q"] = out
+    return _CACHE["Q"]
+
+
+def _prepared(deterministic=True, bodies=0):
+    g = _engine(deterministic, bodies=bodies)
+    g.set_bending(_stiffness())
+    _upload(g)
+    return g
+
+
+def _restate(g, bending=True):
+    mat = g.default_material()
+    return ms.restate(_download(g), _cloths(g), DX, float(mat.gravity), int(mat.gravity_axis),
+                      _bending_refs() if bending else None)
+
+
+def _reference():
+    """the restatement of the uploaded state (rows, faces); made once and left unchanged"""
+    if "ref" not in _CACHE:
+        g = _prepared()
+        _CACHE["ref"] = _restate(g)
+        g.destroy()
+    return _CACHE["ref"]
+
+
+def _check_rows(rows, total, ref_rows, what):
+    assert len(rows) == len(ref_rows)
+    worst = 0.0
+    for c, (row, ref) in enumerate(zip(rows, ref_rows)):
+        worst = max(worst, ms.compare(row, ref, f"{what}: cloth {c}"))
+    worst = max(worst, ms.compare(total, ms.total_of(ref_rows), f"{what}: total"))
+    print(f"{what}: worst {worst:.3g} of the bound")
+    _record(f"measure: {what}", worst)
+
+
+# ---- 1 -------------------------------------------------------------------------------------------------------------
+def test_sums_against_the_restatement():
+    ref_rows, _ = _reference()
+    g = _prepared()
+    rows, total = g.measure()
+    _check_rows(rows, total, ref_rows, "uploaded state")
+    # the scene exercises every term
+    assert [int(r["faces"]) for r in rows] == [3042, 2, len(_meshes()[2][1])] and rows[0]["vertices"] == 1600
+    assert rows[0]["bending"] > 0 and rows[1]["bending"] == 0 and rows[2]["bending"] > 0
+    assert rows[0]["elastic_shear"] == 0 and rows[1]["elastic_shear"] > 0 and rows[2]["elastic_shear"] == 0
+    assert all(r["elastic_normal"] > 0 and r["elastic_in_plane"] > 0 and r["kinetic_affine"] > 0 for r in rows)
+    assert all(r["normal_min"] < 0.85 for r in rows) and rows[0]["stretch_max"] > 1.0 > rows[0]["stretch_min"]
+    # total is the rows added in cloth order, in double
+    for k in ms.SUM_FIELDS + ms.ELASTIC_FIELDS + ("bending",):
+        acc = np.zeros_like(np.asarray(total[k], np.float64))
+        for r in rows:
+            acc = acc + np.asarray(r[k], np.float64)
+        assert np.array_equal(acc, np.asarray(total[k], np.float64)), k
+    assert g.stats()["error_flags"] == 0
+    g.destroy()
+
+
+# ---- 2 -------------------------------------------------------------------------------------------------------------
+def test_face_strain_per_face():
+    _, faces = _reference()
+    g = _prepared()
+    s = g.face_strain()
+    for col, k in enumerate(("s1", "s2", "r22")):
+        assert np.array_equal(s[:, col], faces[k].astype(np.float32)), (k, float(np.abs(s[:, col] - faces[k]).max()))
+    err = np.abs(s[:, 3].astype(np.float64) - faces["Vpsi"])
+    bnd = 8 * U * faces["VB"] + U * np.abs(faces["Vpsi"])
+    w = float((err / bnd).max())
+    print(f"face strain: V psi worst {w:.3g} of the bound")
+    _record("measure: face strain V psi", w)
+    assert w <= 1.0, w
+    # in another particle order: the same bits
+    g.rebuild_mapping(True)
+    assert np.array_equal(g.face_strain().view(np.uint32), s.view(np.uint32))
+    g.destroy()
+
+
+# ---- 3 -------------------------------------------------------------------------------------------------------------
+def _bytes(rows, total):
+    return rows.tobytes() + total.tobytes()
+
+
+def test_rows_are_the_same_bits_in_every_particle_order():
+    g = _prepared()
+    b0 = _bytes(*g.measure())
+    assert len(b0) == 4 * 184
+    pids0 = g.download(_A().PIDS)
+    g.rebuild_mapping(True)
+    assert not np.array_equal(g.download(_A().PIDS), pids0), "sort = 1 changed the slot order"
+    assert _bytes(*g.measure()) == b0
+    # a non-deterministic engine given the same upload
+    h = _prepared(deterministic=False)
+    assert _bytes(*h.measure()) == b0
+    h.destroy()
+    # substeps that force a re-sort (the state five cells further along x), then the same upload again
+    before = g.stats()["rebuilds"]
+    imap0 = g.resort_table("IMAP").copy()
+    _upload(g, shift=(5.0 / 64, 0.0, 0.0))
+    g.run_substeps(2, 1e-5, -1)
+    g.gpu_sync()
+    assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
+    assert not np.array_equal(g.resort_table("IMAP"), imap0), "the re-sort moved particles to other slots"
+    _upload(g)
+    assert _bytes(*g.measure()) == b0
+    g.destroy()
+
+
+# ---- 4 -------------------------------------------------------------------------------------------------------------
+_PARTICLE_ARRAYS = ("POSITIONS", "VELOCITIES", "VOLUMES", "AFFINE", "PIDS", "INDEX_MAPPINGS", "SORT_KEYS", "FORCES", "TAUS",
+                    "DEFORMATION_GRADIENTS", "DM_INVERSES", "INDICES", "MASSES")
+
+
+def _arrays(g):
+    return {k: g.download(getattr(_A(), k)).tobytes() for k in _PARTICLE_ARRAYS}
+
+
+def test_a_call_changes_nothing():
+    g = _prepared()
+    g.run_substeps(3, DT, -1)
+    g.gpu_sync()
+    a0, s0 = _arrays(g), g.stats()
+    g.measure()
+    g.face_strain()
+    a1, s1 = _arrays(g), g.stats()
+    assert s0 == s1, (s0, s1)
+    for k in a0:
+        assert a0[k] == a1[k], k
+    assert s1["error_flags"] == 0
+    g.destroy()
+
+
+def test_measuring_between_batches_leaves_the_trajectory_alone():
+    a, b = _prepared(), _prepared()
+    seen = []
+    for _ in range(3):
+        a.run_substeps(8, DT, -1)
+        seen.append(a.measure()[1]["kinetic"])
+        b.run_substeps(8, DT, -1)
+    for g in (a, b):
+        g.gpu_sync()
+        assert g.stats()["error_flags"] == 0, g.stats()
+    assert len(set(float(k) for k in seen)) == 3, "the state moves between the calls"
+    for k in ("POSITIONS", "VELOCITIES", "AFFINE", "DEFORMATION_GRADIENTS", "MASSES"):
+        assert a.download(getattr(_A(), k)).tobytes() == b.download(getattr(_A(), k)).tobytes(), k
+    assert _bytes(*a.measure()) == _bytes(*b.measure())
+    for g in (a, b):
+        g.destroy()
+
+
+# ---- 5 -------------------------------------------------------------------------------------------------------------
+def test_p2g_identity():
+    """A rest-shape sheet with a rigid plus affine velocity field, phase by phase.  After mpm_calc_fem_state_and_force the
+    report's momentum + dt g mass e_axis must equal the float64 sum over the nodes of MPM_ARR_GRID_MOMENTUM after
+    mpm_particle_to_grid, per component within R 2^-24 sum m (|v| + |g| dt).
+
+    R, counted from k_p2g as tests/transfer_layouts.py counts it per node (|engine - exact| <= K (L_n + 16) 2^-24 A_n,
+    K = 2): a node's sum is a chain of at most L fused multiply-adds on the matrix pipe, L the most particles that share
+    a base cell (partial sums bounded by A_n), and 16 covers forming B, qq and the affine columns (<= 5 roundings each),
+    the weight polynomials (three products of two fused multiply-adds each), the epilogue (4 products, 3 sums) and the
+    rounding of the node's sum to float.  Summed over the nodes, sum_n A_n = sum_p (m |v_r| + m |g| dt [r = axis] +
+    |f_r| dt + 2 dx sum_c (|C_rc m| + |dt Dinv tau_rc|) fx_c): the report's yardstick sum m (|v| + |g| dt) times
+    (1 + alpha), alpha the share of the force and affine columns -- they cancel in the exact total (the weights sum to
+    one, sum_n w_n n_c = fx_c) but each is rounded.  The scene keeps alpha <= 1/4 (|v| >= 0.8 m/s against
+    3 dx sum_c |C_rc| <= 0.1 m/s; rest shape: forces at rounding level), asserted from the kernel's INPUTS (the yardstick
+    has the norm |v| where A_n has the component |v_r|: the alpha the test computes may come out negative).  The report
+    takes a face's v as the double mean of its corners, k_fem stores the float mean (two sums, one division): 3 more.
+        R = K (L + 16) (1 + 1/4) + 3,   L from the positions (here 2.5 (L + 16) + 3; L is 12 on this sheet: R = 73).
+    The engine runs with the double tile (not deterministic): no fixed-point quantum enters."""
+    from drake_amd import GpuMpm
+    from tests import helpers
+    A = _A()
+    X, T = bd.sheet(24, 24)
+    g = GpuMpm(6, GpuMpm.default_material())
+    g.add_qr_cloth(X, np.zeros_like(X), T)
+    g.finalize()
+    nf, dt = len(T), tl.DT32
+    mat = g.default_material()
+    grav, axis = float(mat.gravity), int(mat.gravity_axis)
+    r = np.random.default_rng(3)
+    w, v0 = np.array([0.5, -0.3, 0.8]), np.array([0.8, -0.5, 0.6])
+    S = 0.3 * r.normal(size=(3, 3))
+    G = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]]) + 0.5 * (S + S.T)
+    x = np.concatenate([X[T].astype(np.float64).mean(axis=1), X.astype(np.float64)])
+    vel = (v0 + (x - bd.CENTER) @ G.T).astype(np.float32)
+    pids = g.download(A.PIDS)
+    g.upload_particle_state(None, vel[pids], np.broadcast_to(G.reshape(9).astype(np.float32), (len(x), 9))[pids], None, None)
+    g.rebuild_mapping(False)
+    g.calc_fem_state_and_force(dt)
+    rows, total = g.measure()
+    d = {k: g.download(a) for k, a in (("pids", A.PIDS), ("x", A.POSITIONS), ("v", A.VELOCITIES), ("C", A.AFFINE),
+                                       ("m", A.MASSES), ("taus", A.TAUS), ("f", A.FORCES))}
+    g.particle_to_grid(dt)
+    gmv = g.download(A.GRID_MOMENTUM).astype(np.float64).sum(axis=0)
+    assert g.stats()["error_flags"] == 0
+    g.destroy()
+    face = d["pids"] < nf
+    ref = tl.p2g64(d["x"], d["v"], d["C"], d["m"], np.where(face[:, None], d["taus"], 0.0), np.where(face[:, None], 0.0, d["f"]),
+                   6, axis, dt, grav)
+    m = d["m"].astype(np.float64)
+    speed = np.linalg.norm(d["v"].astype(np.float64), axis=1)
+    yard = float((m * (speed + abs(grav) * dt)).sum())
+    alpha = float(ref["A_mv"].sum(axis=0).max()) / yard - 1.0
+    L = float(ref["L"].max())
+    assert speed.min() > 0.8 and alpha <= 0.25, (speed.min(), alpha)
+    R = tl.K * (L + 16) * 1.25 + 3
+    want = np.asarray(total["momentum"], np.float64).copy()
+    want[axis] += dt * grav * float(total["mass"])
+    ratio = float(np.abs(gmv - want).max() / (R * U * yard))
+    print(f"p2g identity: L = {L:.0f}, alpha = {alpha:.3g}, R = {R:.1f}; |grid - report| = {ratio:.3g} of R 2^-24 sum m (|v| + |g| dt)")
+    helpers.MARGINS.append((ratio, "measure: p2g identity", 1.0, ratio, ratio))
+    assert ratio <= 1.0, (gmv, want, ratio)
+    # (gravity is in the identity: without it the difference is far outside)
+    assert abs(gmv[axis] - float(total["momentum"][axis])) > 100 * R * U * yard
+
+
+# ---- 6 -------------------------------------------------------------------------------------------------------------
+def test_a_state_the_engine_reached():
+    from drake_amd import FF_DRAG, Collider, ForceField
+    g = _engine(bodies=1)
+    before = g.stats()["rebuilds"]
+    g.set_bending(_stiffness())
+    g.set_force_fields([ForceField(FF_DRAG, gamma=5.0)])
+    st = dict(_state())
+    st["v"] = (st["v"] + np.array([3.0, 0.3, -1.0], np.float32)).astype(np.float32)
+    _upload(g, st)
+    z_floor = float(st["x"][:, 2].min()) - 0.002
+    res = g.run_coupled_substeps(30, DT, [Collider(0, body=0, p_WB=(0.5, 0.5, z_floor))], 0.5, 1e5, 1e-4)
+    g.gpu_sync()
+    assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
+    assert max(r["contacts"] for r in res) > 0, "the cloths never reached the floor"
+    rows, total = g.measure()
+    ref_rows, _ = _restate(g)
+    _check_rows(rows, total, ref_rows, "after 30 coupled substeps")
+    assert total["kinetic"] > 0 and total["bending"] > 0 and rows[1]["elastic_shear"] >= 0
+    g.destroy()
+
+
+# ---- 7 -------------------------------------------------------------------------------------------------------------
+def test_partitioned_ranks_add_up():
+    from drake_amd import MpmError
+    nb = 64 // 4
+    single = _engine(multi=False)
+    _upload(single)
+    ref_rows, _ = _restate(single, bending=False)
+    rows1, total1 = single.measure()
+    _check_rows(rows1, total1, ref_rows, "single-material engine")
+    ranks = []
+    for rk in range(2):
+        g = _engine(multi=False)
+        _upload(g)
+        g.dist_init(rk, 2, [0, nb // 2, nb], 2, 2, 2)
+        ranks.append(g)
+    got = [g.measure() for g in ranks]
+    for c in range(3):
+        for k in ms.COUNT_FIELDS:
+            assert int(got[0][0][c][k]) + int(got[1][0][c][k]) == int(rows1[c][k]), (c, k)
+            assert 0 < int(got[0][0][c][k]) < int(rows1[c][k]), "the cut goes through every cloth"
+    worst = 0.0
+    for c in range(3):
+        for k in ms.SUM_FIELDS + ms.ELASTIC_FIELDS + ("bending",):
+            both = np.asarray(got[0][0][c][k], np.float64) + np.asarray(got[1][0][c][k], np.float64)
+            err = np.abs(both - np.asarray(rows1[c][k], np.float64))
+            bnd = ms.bound_of(k, ref_rows[c][k][1])
+            w = float(np.max(np.where(err == 0, 0.0, err / np.maximum(bnd, 1e-300))))
+            assert w <= 1.0, (c, k, w)
+            worst = max(worst, w)
+        assert max(got[0][0][c]["stretch_max"], got[1][0][c]["stretch_max"]) == rows1[c]["stretch_max"]
+        assert max(got[0][0][c]["speed_max"], got[1][0][c]["speed_max"]) == rows1[c]["speed_max"]
+        assert min(got[0][0][c]["stretch_min"], got[1][0][c]["stretch_min"]) == rows1[c]["stretch_min"]
+        assert min(got[0][0][c]["normal_min"], got[1][0][c]["normal_min"]) == rows1[c]["normal_min"]
+    print(f"partition: the ranks' rows against the single engine's: worst {worst:.3g} of the bound")
+    _record("measure: two ranks against one engine", worst)
+    # mpm_face_strain is refused on a partitioned engine, nothing enqueued
+    s0 = ranks[0].stats()
+    with pytest.raises(MpmError) as e:
+        ranks[0].face_strain()
+    assert e.value.code == -1 and "partitioned" in str(e.value), e.value
+    assert ranks[0].stats() == s0
+    for g in ranks + [single]:
+        assert g.stats()["error_flags"] == 0
+        g.destroy()
+
+
+# ---- 8 -------------------------------------------------------------------------------------------------------------
+def test_calling_convention():
+    from drake_amd import MEASURE_DTYPE, GpuMpm, MpmError
+    X, T = bd.mesh("regular")
+    g0 = GpuMpm(6)
+    g0.add_qr_cloth(X, np.zeros_like(X), T)
+    with pytest.raises(MpmError) as e:
+        g0.measure()
+    assert e.value.code == -1 and "finalize" in str(e.value), e.value
+    g0.destroy()
+    g = _prepared()
+    rows, total = g.measure()
+    # a capacity below the cloth count fills `capacity` rows and reports the count
+    buf = np.zeros(3, MEASURE_DTYPE)
+    buf["mass"] = -1.0
+    n = C.c_size_t()
+    assert g.lib.mpm_measure(g.h, buf.ctypes.data, 2, C.byref(n), None) == 0
+    assert n.value == 3 and buf[:2].tobytes() == rows[:2].tobytes() and buf[2]["mass"] == -1.0
+    # NULL outputs
+    assert g.lib.mpm_measure(g.h, None, 0, None, None) == 0
+    assert g.lib.mpm_measure(g.h, None, 0, C.byref(n), None) == 0 and n.value == 3
+    t = np.zeros((), MEASURE_DTYPE)
+    assert g.lib.mpm_measure(g.h, None, 0, None, t.ctypes.data) == 0 and t.tobytes() == total.tobytes()
+    assert g.lib.mpm_measure(g.h, None, 1, None, None) == -1
+    assert g.measure(capacity=1)[0].tobytes() == rows[:1].tobytes()
+    # bending switched off and on again: the report follows the table in force
+    g.set_bending([])
+    off = g.measure()[0]
+    assert not off["bending"].any() and off["elastic_normal"].tobytes() == rows["elastic_normal"].tobytes()
+    g.set_bending(_stiffness())
+    assert g.measure()[0].tobytes() == rows.tobytes()
+    g.set_bending([0.0, 0.0, _stiffness()[2]])
+    one = g.measure()[0]
+    assert one["bending"][0] == 0 and one["bending"][2] == rows["bending"][2]
+    assert g.stats()["error_flags"] == 0
+    g.destroy()
