@@ -81,7 +81,9 @@ __global__ __launch_bounds__(256) void k_rb_count(DP p) {
             vx = vq.x; vy = vq.y; vz = vq.z;
         }
     }
-    const bool valid = listed && xq.w != 0.f;   // volume 0: released by the migration, dropped here
+    // partitioned domain: volume 0 = released by the migration, dropped here.  Elsewhere volume 0 is a vertex in no face
+    // (Finalize sums nothing into it): a particle without mass that moves with the grid, as in the reference
+    const bool valid = listed && (xq.w != 0.f || !p.dist.on);
 #if MPM_DIAG
     if (diag_flags(p) & 1024) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); cstamp(0); }
 #endif
