@@ -185,6 +185,24 @@ def bending_matrix(pos, indices):
     return off.astype(np.int64), cols[:nnz.value], vals[:nnz.value]
 
 
+def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
+    """mpm_damping_face_records: the membrane damping kernel's face function on the host.  dminv3 (n, 3) = (Dm0, Dm1, Dm3),
+    vol, mu, lam, beta (n,) (scalars are broadcast), x, v (n, 3, 3) corner positions and velocities; returns the corner
+    records G (n, 3, 3) float32, [face][corner][component] (the force on a corner is -G).  Needs no engine and no GPU."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 3, 3)
+    n = len(x)
+    v = np.ascontiguousarray(v, np.float32).reshape(n, 3, 3)
+    dm = np.ascontiguousarray(dminv3, np.float32).reshape(n, 3)
+    s = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), (n,))) for a in (vol, mu, lam, beta)]
+    out = np.zeros((n, 3, 3), np.float32)
+    rc = lib.mpm_damping_face_records(n, dm.ctypes.data, s[0].ctypes.data, s[1].ctypes.data, s[2].ctypes.data,
+                                      s[3].ctypes.data, x.ctypes.data, v.ctypes.data, out.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return out
+
+
 def grid_collider_preset(mpm_bc: int, sdf_friction: float = 0.3):
     """The collider table that reproduces the reference's scene mpm_bc (cuda_mpm_kernels.cuh:673-774)."""
     lib = load_library()
@@ -342,6 +360,7 @@ SYMBOLS = [
     "mpm_debug_resort_tables", "mpm_debug_sort_pairs", "mpm_set_body_contact_materials",
     "mpm_get_body_contact_materials", "mpm_set_bending", "mpm_get_bending", "mpm_bending_forces",
     "mpm_bending_max_stable_dt", "mpm_bending_matrix", "mpm_measure", "mpm_face_strain", "mpm_cloth_energy_density",
+    "mpm_set_damping", "mpm_get_damping", "mpm_damping_forces", "mpm_damping_max_stable_dt", "mpm_damping_face_records",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -468,6 +487,11 @@ def load_library(build: bool = True):
         "mpm_bending_forces": [vp, vp],
         "mpm_bending_max_stable_dt": [vp, P(f)],
         "mpm_bending_matrix": [vp, sz, vp, sz, vp, vp, vp, sz, P(sz)],
+        "mpm_set_damping": [vp, sz, vp],
+        "mpm_get_damping": [vp, vp, sz, P(sz)],
+        "mpm_damping_forces": [vp, vp],
+        "mpm_damping_max_stable_dt": [vp, P(f)],
+        "mpm_damping_face_records": [sz, vp, vp, vp, vp, vp, vp, vp, vp],
         "mpm_measure": [vp, vp, sz, P(sz), vp],
         "mpm_face_strain": [vp, vp],
         "mpm_cloth_energy_density": [vp, sz, vp, vp],
@@ -753,6 +777,38 @@ class GpuMpm:
         dt = C.c_float()
         self._ck(self.lib.mpm_bending_max_stable_dt(self.h, C.byref(dt)))
         return float(dt.value)
+
+    def set_damping(self, damping):
+        """mpm_set_damping: (beta_membrane, beta_bending) in seconds for every cloth, in cloth order -- stiffness-
+        proportional damping of the membrane (Kelvin-Voigt on the in-plane Green strain) and of the hinges (on a cloth
+        with bending stiffness); all zeros or an empty list switches it off.  A synchronisation point."""
+        d = np.ascontiguousarray(damping, np.float32).reshape(-1, 2)
+        self._ck(self.lib.mpm_set_damping(self.h, len(d), _ptr(d) if d.size else None))
+
+    def get_damping(self):
+        """mpm_get_damping: the coefficients in force, (n_cloths, 2) float32 (zeros while off)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_damping(self.h, None, 0, C.byref(n)))
+        out = np.zeros((int(n.value), 2), np.float32)
+        self._ck(self.lib.mpm_get_damping(self.h, _ptr(out) if out.size else None, len(out), C.byref(n)))
+        return out
+
+    def damping_forces(self):
+        """mpm_damping_forces: the membrane + bending damping force on the current positions and velocities, (n_verts, 3)
+        float32 in dump_cpu_state's numbering."""
+        out = np.zeros((self.n_verts, 3), np.float32)
+        self._ck(self.lib.mpm_damping_forces(self.h, _ptr(out)))
+        return out
+
+    def damping_max_stable_dt(self) -> float:
+        """mpm_damping_max_stable_dt: the dt above which the substep entry points refuse (inf while damping is off)."""
+        dt = C.c_float()
+        self._ck(self.lib.mpm_damping_max_stable_dt(self.h, C.byref(dt)))
+        return float(dt.value)
+
+    @staticmethod
+    def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
+        return damping_face_records(dminv3, vol, mu, lam, beta, x, v)
 
     def measure(self, capacity: int | None = None):
         """mpm_measure: (rows, total) -- one MEASURE_DTYPE record per cloth (the first `capacity` of them if given) and

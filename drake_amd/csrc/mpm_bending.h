@@ -52,7 +52,9 @@ struct BendArgs {
 // Row r of the table on the current positions.  Every index into a per-particle array comes through DP::imap from an id
 // of the host-built table; a slot that is no vertex slot (a particle this engine does not hold) is reported, never used
 // as an address: the entry then reads the row's own position (a zero difference).  false: the row's own vertex has no slot.
-MPM_DEV bool bend_row(const DP& p, const PSet& S, const BendArgs& a, int r, int& s_out, float f[3], bool& bad) {
+// PLANE 1 (mpm_damping.h): the same row on the velocities, PSet::q[1], every coefficient times `scale` (one more rounding).
+template <int PLANE = 0>
+MPM_DEV bool bend_row(const DP& p, const PSet& S, const BendArgs& a, int r, int& s_out, float f[3], bool& bad, float scale = 1.f) {
     const unsigned b0 = a.slice_off[r >> 6], b1 = a.slice_off[(r >> 6) + 1];
     const int width = (int)((b1 - b0) / BEND_SLICE);
     const int s = p.imap[a.row_pid[r]];
@@ -61,7 +63,7 @@ MPM_DEV bool bend_row(const DP& p, const PSet& S, const BendArgs& a, int r, int&
         bad = true;
         return false;
     }
-    const float4 xi = S.q[0][s];
+    const float4 xi = S.q[PLANE][s];
     const float2* ent = a.ent + b0 + (r & 63);
     float f0 = 0.f, f1 = 0.f, f2 = 0.f;
     // BEND_BATCH entries at a time: their records, then their slots, then their positions -- three round trips of
@@ -80,11 +82,11 @@ MPM_DEV bool bend_row(const DP& p, const PSet& S, const BendArgs& a, int r, int&
         for (int u = 0; u < BEND_BATCH; ++u) {
             const bool ok = sj[u] >= p.Nf && sj[u] < p.Np;
             bad |= !ok;
-            xj[u] = S.q[0][ok ? sj[u] : s];
+            xj[u] = S.q[PLANE][ok ? sj[u] : s];
         }
 #pragma unroll
         for (int u = 0; u < BEND_BATCH; ++u) {   // (in stored order)
-            const float c = e0 + u < width ? -q[u].x : -0.f;
+            const float c = e0 + u < width ? -(PLANE ? scale * q[u].x : q[u].x) : -0.f;
             f0 = fmaf(c, xj[u].x - xi.x, f0);
             f1 = fmaf(c, xj[u].y - xi.y, f1);
             f2 = fmaf(c, xj[u].z - xi.z, f2);

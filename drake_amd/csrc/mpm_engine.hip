@@ -231,10 +231,10 @@ static void launch_fem_faces(mpm_engine* e, const DP& p, float dt) {
         const ClothMat* t = e->d_cloth_mat;
         if (e->fast_math) hipLaunchKernelGGL(k_fem_mat<1>, g, b, 0, e->stream, p, dt, t);
         else hipLaunchKernelGGL(k_fem_mat<0>, g, b, 0, e->stream, p, dt, t);
-        return;
-    }
-    if (e->fast_math) hipLaunchKernelGGL(k_fem<1>, g, b, 0, e->stream, p, dt);
+    } else if (e->fast_math) hipLaunchKernelGGL(k_fem<1>, g, b, 0, e->stream, p, dt);
     else hipLaunchKernelGGL(k_fem<0>, g, b, 0, e->stream, p, dt);
+    // (an engine with membrane damping, mpm_set_damping: the same faces again, adding to the records just written)
+    if (e->damp.membrane()) hipLaunchKernelGGL(k_damp, g, b, 0, e->stream, p, e->damp.args);
 }
 static void launch_fem_vertices(mpm_engine* e, const DP& p) {
     TraceRange tr("mpm:CalcFemStateAndForce (vertex forces)");
@@ -242,6 +242,10 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p) {
     // (an engine with bending stiffness, mpm_set_bending: f += -k Q x on the forces k_vforce has just written)
     if (e->bend.on())
         hipLaunchKernelGGL(k_bend, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->bend.args);
+    // (... and with bending damping, mpm_set_damping: f += -beta k Q v from the same table)
+    if (e->bend.on() && e->damp.bending())
+        hipLaunchKernelGGL(k_bend_damp, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->bend.args,
+                           (const float*)e->damp.d_beta_vertex);
 }
 // (mpm_calc_fem_state_and_force: the two FEM kernels, whose forces a caller may read)
 static void launch_fem(mpm_engine* e, const DP& p, float dt) {
@@ -821,8 +825,8 @@ static int pins_ready(mpm_engine* e) {
     ps.table_dirty = false;
     return 0;
 }
-// partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields and no bending
-// stiffness (out of scope)
+// partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
+// stiffness and no damping (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
@@ -833,13 +837,22 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with force fields (mpm_set_force_fields)");
     if (e->bend.on())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with bending stiffness (mpm_set_bending)");
+    if (e->damp.any())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with damping (mpm_set_damping)");
     return 0;
 }
 // An explicit linear drag beyond dt * gamma = 1 reverses the relative velocity: the substep entry points that take a dt
 // refuse it, once per call, before anything is enqueued.  (An engine without a table never gets past the first test.)
 // The same entry points refuse a dt above mpm_bending_max_stable_dt on an engine with bending stiffness: symplectic Euler
-// on the lumped system needs dt * omega <= 2, with Gershgorin's bound on omega^2 (a guard, not a guarantee).
+// on the lumped system needs dt * omega <= 2, with Gershgorin's bound on omega^2 (a guard, not a guarantee).  And a dt
+// above mpm_damping_max_stable_dt on an engine with damping: the explicit viscous force needs dt * rho(M^-1 D) <= 2.
 static int fields_stable(const mpm_engine* e, float dt) {
+    if (e->damp.any() && !(dt <= e->damp.max_dt)) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "damping: dt = %g is above the limit mpm_damping_max_stable_dt = %g: the explicit damping "
+                      "force is unstable -- reduce dt or the coefficients", (double)dt, (double)e->damp.max_dt);
+        return fail(MPM_ERR_INVALID, msg);
+    }
     if (e->bend.on() && !(dt <= e->bend.max_dt))
     {
         char msg[200];
@@ -854,8 +867,10 @@ static int fields_stable(const mpm_engine* e, float dt) {
     return 0;
 }
 // The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
-// takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness is set.
-static float quiet_hint(const mpm_engine* e, float seconds) { return e->force_fields.empty() && !e->bend.on() ? seconds : 0.f; }
+// takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness or damping is set.
+static float quiet_hint(const mpm_engine* e, float seconds) {
+    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() ? seconds : 0.f;
+}
 
 // ---- the solver calls -----------------------------------------------------
 static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, bool allow_gate, bool lean = false);
@@ -3027,7 +3042,7 @@ static bool is_rotation(const float* R) {
                        (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
     return std::fabs(det - 1.0) <= 1e-4;
 }
-// pins, grid bodies, force fields and bending stiffness are refused on a partitioned or multi-rank engine (out of scope);
+// pins, grid bodies, force fields, bending stiffness and damping are refused on a partitioned or multi-rank engine (out of scope);
 // what_is: "pins are", "bending stiffness is", ...
 static int single_engine_only(const mpm_engine* e, const char* what_is) {
     if (e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on)
@@ -3302,6 +3317,7 @@ int mpm_force_field_acceleration(const mpm_force_field_t* fields, size_t n_field
 
 // ---- bending stiffness (mpm_set_bending, mpm_get_bending, mpm_bending_forces, mpm_bending_max_stable_dt,
 // mpm_bending_matrix; mpm_bending.h) ----
+static void damping_limit(mpm_engine* e);
 extern "C" {
 
 // host code only: no device is touched
@@ -3430,8 +3446,12 @@ int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try
     }
     next.k.assign(stiffness, stiffness + n_cloths);
     next.max_dt = max_dt;
+    next.row_vertex.resize(n_rows);
+    for (size_t r = 0; r < n_rows; ++r) next.row_vertex[r] = row_pid[r] - (int)e->nf;
+    next.abs_sum.swap(abs_sum);
     e->bend = next;
     fresh.commit();
+    damping_limit(e);   // (the hinge damping is beta k Q: its share of mpm_damping_max_stable_dt follows the new k)
     return 0;
 } MPM_CATCH_ALL
 
@@ -3462,6 +3482,196 @@ int mpm_bending_forces(mpm_handle_t e, float* f_out) try {
 int mpm_bending_max_stable_dt(mpm_handle_t e, float* dt_out) try {
     REQUIRE(e && dt_out, "null argument");
     *dt_out = e->bend.on() ? e->bend.max_dt : INFINITY;
+    return 0;
+} MPM_CATCH_ALL
+
+}  // extern "C"
+
+// ---- stiffness-proportional damping (mpm_set_damping, mpm_get_damping, mpm_damping_forces, mpm_damping_max_stable_dt,
+// mpm_damping_face_records; mpm_damping.h) ----
+// the Lame parameters of cloth c as the elastic kernels use them (init_cloth_materials; DP::M of a single-material engine)
+static void cloth_lame(const mpm_engine* e, size_t c, float* mu, float* lambda) {
+    if (!e->multi_mat) {
+        *mu = e->dp.M.mu;
+        *lambda = e->dp.M.lambda;
+        return;
+    }
+    const mpm_cloth_material_t& m = e->cloths[c].m;
+    *mu = m.youngs_modulus / (2.f * (1.f + m.poisson_ratio));
+    *lambda = m.youngs_modulus * m.poisson_ratio / ((1.f + m.poisson_ratio) * (1.f - 2.f * m.poisson_ratio));
+}
+// mpm_damping_max_stable_dt from what the engine holds: the membrane row sums and vertex masses of the last
+// mpm_set_damping, the rows of the bending table in force.  Host only; cannot fail.  Also says whether k_bend_damp has a
+// row to work on (a cloth with beta_bending > 0 and bending stiffness > 0).
+static void damping_limit(mpm_engine* e) {
+    mpm_engine::Damping& dm = e->damp;
+    dm.max_dt = INFINITY;
+    dm.bend_rows = false;
+    if (!dm.any()) return;
+    std::vector<double> D(e->nv, 0.0);
+    if (dm.membrane()) D = dm.D_membrane;
+    if (e->bend.on())
+        for (size_t r = 0; r < e->bend.row_vertex.size(); ++r) {
+            const size_t v = (size_t)e->bend.row_vertex[r];
+            const float beta = dm.beta_vertex[v];
+            if (!(beta > 0.f)) continue;
+            dm.bend_rows = true;
+            D[v] += (double)beta * e->bend.abs_sum[r];
+        }
+    double worst = 0.0;
+    for (size_t i = 0; i < e->nv; ++i)
+        if (D[i] > 0.0) worst = std::max(worst, dm.mass[i] > 0.0 ? D[i] / dm.mass[i] : (double)INFINITY);
+    if (worst > 0.0) {
+        const double lim = 2.0 / worst;
+        dm.max_dt = (float)lim;
+        if ((double)dm.max_dt > lim) dm.max_dt = std::nextafterf(dm.max_dt, 0.f);   // (rounded towards zero: never above the bound)
+    }
+}
+// Puts the coefficients `d` (checked; one per cloth, or none) in force: k_damp's tables, k_bend_damp's coefficient per
+// vertex (it reads the bending table in force) and the stability limit.  The caller has settled the owed substeps.  A
+// failure changes nothing.
+static int damping_apply(mpm_engine* e, std::vector<mpm_cloth_damping_t> d) {
+    const size_t nc = d.size();
+    bool membrane = false, bending = false;
+    for (size_t c = 0; c < nc; ++c) {
+        membrane = membrane || d[c].membrane > 0.f;
+        bending = bending || d[c].bending > 0.f;
+    }
+    mpm_engine::Damping next;
+    FreshArrays fresh(e);
+    if (membrane || bending) {
+        std::vector<float4> coef(std::max<size_t>(nc, 1), make_float4(0.f, 0.f, 0.f, 0.f));
+        std::vector<int> cloth_of_face(e->nf, 0);
+        next.beta_vertex.assign(e->nv, 0.f);
+        for (size_t c = 0; c < nc; ++c) {
+            const mpm_engine::Cloth& cl = e->cloths[c];
+            float mu, lambda;
+            cloth_lame(e, c, &mu, &lambda);
+            coef[c] = make_float4(mu, lambda, d[c].membrane, 0.f);
+            std::fill(cloth_of_face.begin() + (long)cl.first_face, cloth_of_face.begin() + (long)(cl.first_face + cl.n_faces), (int)c);
+            std::fill(next.beta_vertex.begin() + (long)cl.first_vertex, next.beta_vertex.begin() + (long)(cl.first_vertex + cl.n_verts),
+                      d[c].bending);
+        }
+        // every particle's q[0].w in original order: a vertex's mass as ParticleToGrid forms it (x DP::M.density, both floats),
+        // a face's rest volume (a multi-material engine holds the mass there: / the cloth's density)
+        std::vector<float> w(e->np);
+        int* iota = nullptr;
+        if (int rc = device_iota(e, &iota)) return rc;
+        if (int rc = gather_to_host<F_VOL>(e, w.data(), e->np, iota)) return rc;
+        next.mass.resize(e->nv);
+        for (size_t i = 0; i < e->nv; ++i) next.mass[i] = (double)(std::fabs(w[e->nf + i]) * e->dp.M.density);
+        if (membrane) {
+            // sum_j |D_ij| of the membrane's damping matrix at the rest shape, per vertex (Gershgorin)
+            std::vector<float> dminv(e->nf * 4);
+            if (int rc = gather_to_host<F_DMINV>(e, dminv.data(), e->nf, iota)) return rc;
+            next.D_membrane.assign(e->nv, 0.0);
+            for (size_t f = 0; f < e->nf; ++f) {
+                const float4 c = coef[(size_t)cloth_of_face[f]];
+                if (!(c.z > 0.f)) continue;
+                const double Dm0 = dminv[4 * f], Dm1 = dminv[4 * f + 1], Dm3 = dminv[4 * f + 3];
+                const double vol = std::fabs((double)w[f]) / (e->multi_mat ? (double)e->h_rho_of_pid[f] : 1.0);
+                const double g[3] = {std::hypot(Dm0, Dm1 + Dm3), std::hypot(Dm0, Dm1), std::fabs(Dm3)};   // |columns of grad_N|
+                const double s = (double)c.z * vol * (2.0 * (double)c.x + 2.0 * (double)c.y) * (g[0] + g[1] + g[2]);
+                for (int k = 0; k < 3; ++k) next.D_membrane[(size_t)e->h_idx[3 * f + k]] += s * g[k];
+            }
+            float4* d_coef = nullptr;
+            int* d_cloth = nullptr;
+            if (int rc = fresh.alloc(&d_coef, coef.size(), false)) return rc;
+            if (int rc = fresh.alloc(&d_cloth, cloth_of_face.size(), false)) return rc;
+            H2D(e, d_coef, coef.data(), coef.size() * sizeof(float4));
+            if (!cloth_of_face.empty()) H2D(e, d_cloth, cloth_of_face.data(), cloth_of_face.size() * sizeof(int));
+            next.args = DampArgs{d_coef, d_cloth};
+        }
+        if (bending) {
+            if (int rc = fresh.alloc(&next.d_beta_vertex, e->nv, false)) return rc;
+            H2D(e, next.d_beta_vertex, next.beta_vertex.data(), e->nv * sizeof(float));
+        }
+    }
+    // (a synchronisation point: the kernels enqueued so far have read the old tables)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    {
+        float4* o_coef = const_cast<float4*>(e->damp.args.coef);
+        int* o_cloth = const_cast<int*>(e->damp.args.cloth_of_face);
+        e->dfree(o_coef);
+        e->dfree(o_cloth);
+        e->dfree(e->damp.d_beta_vertex);
+    }
+    next.d.swap(d);
+    e->damp = next;
+    fresh.commit();
+    damping_limit(e);
+    return 0;
+}
+
+extern "C" {
+
+int mpm_set_damping(mpm_handle_t e, size_t n_cloths, const mpm_cloth_damping_t* d) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "damping is")) return rc;
+    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_damping: n_cloths must be mpm_cloth_count (or 0: off)");
+    REQUIRE(n_cloths == 0 || d, "null damping array");
+    for (size_t c = 0; c < n_cloths; ++c)
+        REQUIRE(std::isfinite(d[c].membrane) && d[c].membrane >= 0.f && std::isfinite(d[c].bending) && d[c].bending >= 0.f,
+                "damping: a coefficient is negative or not finite");
+    // substeps that mpm_run_substeps deferred are owed with the coefficients they were enqueued with
+    if (int rc = settle(e)) return rc;
+    return damping_apply(e, n_cloths ? std::vector<mpm_cloth_damping_t>(d, d + n_cloths) : std::vector<mpm_cloth_damping_t>());
+} MPM_CATCH_ALL
+
+int mpm_get_damping(mpm_handle_t e, mpm_cloth_damping_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    std::vector<mpm_cloth_damping_t> d = e->damp.d;   // (one entry per cloth; zeros where nothing was set)
+    d.resize(e->cloths.size(), mpm_cloth_damping_t{0.f, 0.f});
+    return copy_out(d, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_damping_forces(mpm_handle_t e, float* f_out) try {
+    READY(e);
+    REQUIRE(f_out || e->nv == 0, "null output");
+    std::memset(f_out, 0, e->nv * 12);
+    const bool hinges = e->bend.on() && e->damp.bending();
+    if (!e->damp.membrane() && !hinges) return 0;
+    // the face records in original face order, behind them the bending rows in original vertex order
+    const size_t n_rec = e->nf * 9, n_all = n_rec + e->nv * 3;
+    if (int rc = e->stage(n_all * 4)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, n_all * 4, e->stream));
+    if (e->damp.membrane() && e->nf)
+        hipLaunchKernelGGL(k_damp_eval, dim3((unsigned)((e->nf + 255) / 256)), dim3(256), 0, e->stream, e->dp, e->damp.args,
+                           (float*)e->d_stage);
+    if (hinges)
+        hipLaunchKernelGGL(k_bend_damp_eval, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
+                           e->bend.args, (const float*)e->damp.d_beta_vertex, (float*)e->d_stage + n_rec);
+    HIP_TRY(hipGetLastError());
+    std::vector<float> h(n_all);
+    D2H(e, h.data(), e->d_stage, n_all * 4);
+    // a vertex's records in ascending original face id, as k_vforce sums them; then the bending row, as k_bend_damp adds it
+    for (size_t f = 0; f < e->nf; ++f)
+        for (int c = 0; c < 3; ++c) {
+            float* o = f_out + 3 * (size_t)e->h_idx[3 * f + c];
+            for (int k = 0; k < 3; ++k) o[k] += -h[9 * f + 3 * c + k];
+        }
+    for (size_t i = 0; i < e->nv * 3; ++i) f_out[i] += h[n_rec + i];
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_damping_max_stable_dt(mpm_handle_t e, float* dt_out) try {
+    REQUIRE(e && dt_out, "null argument");
+    *dt_out = e->damp.any() ? e->damp.max_dt : INFINITY;
+    return 0;
+} MPM_CATCH_ALL
+
+// host code only: the device function of the kernels, compiled for the host
+int mpm_damping_face_records(size_t n_faces, const float* dminv3, const float* vol, const float* mu, const float* lambda,
+                             const float* beta, const float* x9, const float* v9, float* rec9_out) try {
+    REQUIRE((dminv3 && vol && mu && lambda && beta && x9 && v9 && rec9_out) || n_faces == 0, "null array");
+    for (size_t f = 0; f < n_faces; ++f) {
+        float x[3][3], v[3][3], rec[3][3];
+        std::memcpy(x, x9 + 9 * f, sizeof x);
+        std::memcpy(v, v9 + 9 * f, sizeof v);
+        damp_face(dminv3[3 * f], dminv3[3 * f + 1], dminv3[3 * f + 2], vol[f], mu[f], lambda[f], beta[f], x, v, rec);
+        std::memcpy(rec9_out + 9 * f, rec, sizeof rec);
+    }
     return 0;
 } MPM_CATCH_ALL
 

@@ -18,6 +18,7 @@
 #include "mpm_contact_dev.h"
 #include "mpm_pins.h"
 #include "mpm_bending.h"
+#include "mpm_damping.h"
 #include "mpm_measure.h"
 #include "mpm_grid_bodies.h"
 #include "mpm_team.h"
@@ -217,8 +218,28 @@ struct mpm_engine {
         std::vector<float> k;            // [cloth] as given; empty or all zero: off
         BendArgs args{};                 // the table as k_bend reads it (device memory, in `allocs`)
         float max_dt = INFINITY;         // 2 / sqrt(max_i (1 / m_i) sum_j |k Q_ij|) (fields_stable)
+        std::vector<int> row_vertex;     // [row] its vertex (original, 0-based), and
+        std::vector<double> abs_sum;     // sum_j |k Q_ij| of the row, the diagonal included (mpm_damping_max_stable_dt)
         bool on() const { return args.n_rows > 0; }
     } bend;
+    // stiffness-proportional damping (mpm_set_damping; mpm_damping.h): k_damp behind k_fem for the cloths with
+    // beta_membrane > 0, k_bend_damp behind k_bend for those with beta_bending > 0 and bending stiffness k > 0
+    struct Damping {
+        std::vector<mpm_cloth_damping_t> d;   // [cloth] as given; empty or all zero: off
+        DampArgs args{};                      // k_damp's tables (device memory, in `allocs`); coef == nullptr: no membrane damping
+        float* d_beta_vertex = nullptr;       // [vertex] its cloth's beta_bending, for k_bend_damp; null: none is > 0
+        std::vector<float> beta_vertex;       // ... on the host
+        std::vector<double> D_membrane, mass; // [vertex] Gershgorin row sum of the membrane's damping matrix at the rest shape; mass
+        bool bend_rows = false;               // the bending table in force has a row with beta_bending > 0 (damping_limit)
+        float max_dt = INFINITY;              // 2 / max_i (D_i / m_i) (damping_limit, fields_stable)
+        bool membrane() const { return args.coef != nullptr; }
+        bool bending() const { return d_beta_vertex != nullptr && bend_rows; }
+        bool any() const {                    // some coefficient > 0: the feature is on
+            for (const mpm_cloth_damping_t& c : d)
+                if (c.membrane > 0.f || c.bending > 0.f) return true;
+            return false;
+        }
+    } damp;
     // the per-cloth report (mpm_measure, mpm_face_strain; mpm_measure.h): chunk table and scratch, made at first use
     struct Measure {
         bool built = false;

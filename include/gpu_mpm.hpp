@@ -216,6 +216,36 @@ struct GpuMpmState {
         mpm_check(mpm_bending_max_stable_dt(h_, &dt));
         return dt;
     }
+    // Extension: stiffness-proportional damping per cloth (mpm_set_damping), the counterpart of Drake's
+    // DeformableBodyConfig::stiffness_damping_coefficient: {membrane, bending} in seconds; all zeros or an empty vector
+    // switches it off.  A synchronisation point, like SetBending.
+    void SetDamping(const std::vector<mpm_cloth_damping_t>& d) { mpm_check(mpm_set_damping(h_, d.size(), d.data())); }
+    std::vector<mpm_cloth_damping_t> GetDamping() const {
+        size_t n = 0;
+        mpm_check(mpm_get_damping(h_, nullptr, 0, &n));
+        std::vector<mpm_cloth_damping_t> out(n);
+        mpm_check(mpm_get_damping(h_, out.data(), n, &n));
+        return out;
+    }
+    // the damping force on the current positions and velocities, 3 floats per vertex in the numbering of DumpCpuState
+    std::vector<float> DampingForces(size_t n_verts) const {
+        std::vector<float> f(3 * n_verts);
+        mpm_check(mpm_damping_forces(h_, f.data()));
+        return f;
+    }
+    // the dt above which the substep entry points refuse an engine with damping (+inf while it is off)
+    float DampingMaxStableDt() const {
+        float dt = 0.f;
+        mpm_check(mpm_damping_max_stable_dt(h_, &dt));
+        return dt;
+    }
+    // the membrane damping kernel's face function on the host: n faces, see mpm_damping_face_records
+    static std::vector<float> DampingFaceRecords(size_t n, const float* dminv3, const float* vol, const float* mu,
+                                                 const float* lambda, const float* beta, const float* x9, const float* v9) {
+        std::vector<float> rec(9 * n);
+        mpm_check(mpm_damping_face_records(n, dminv3, vol, mu, lambda, beta, x9, v9, rec.data()));
+        return rec;
+    }
     // Extension: the per-cloth report (mpm_measure) -- masses, momenta, kinetic, potential, elastic and bending energies,
     // strain extremes, reduced on the device in double.  One row per cloth; `total`, if given, receives their sum.
     // System::CalcKineticEnergy is total.kinetic + total.kinetic_affine, CalcPotentialEnergy is gravity_potential +

@@ -804,6 +804,57 @@ MPM_API int mpm_bending_max_stable_dt(mpm_handle_t h, float *dt_out);
 MPM_API int mpm_bending_matrix(const float *pos, size_t n_verts, const int32_t *indices, size_t n_faces, size_t *row_offsets,
                                int32_t *cols, double *vals, size_t capacity, size_t *nnz_out);
 
+/* ---- Stiffness-proportional damping of the cloth, per cloth (an extension) ----
+ * The stiffness half of a Rayleigh pair (Drake's DeformableBodyConfig::stiffness_damping_coefficient), as a material
+ * damper: per cloth two coefficients in seconds, both >= 0.
+ *   membrane  Kelvin-Voigt on the in-plane Green strain.  Per face, with F2 = [x1 - x0, x2 - x0] Dm^-1 the in-plane
+ *             columns of F and dF2 the same of the corner velocities: Edot = 1/2 (F2^T dF2 + dF2^T F2),
+ *             S = beta (2 mu Edot + lambda tr(Edot) I) with the cloth's Lame parameters, P = F2 S, corner records
+ *             G = vol P grad_N, vertex force -sum G.  Linear in v; zero for every rigid velocity field whatever the
+ *             deformation; total force and torque vanish; power -sum f.v = sum vol S:Edot >= 0.  The director column
+ *             of F (the gamma, K and c_F terms) is not damped.
+ *   bending   f = -beta k Q v, the hinge operator of mpm_set_bending on the velocities; it acts only on a cloth whose
+ *             bending stiffness k is > 0 (a beta on a cloth with k = 0 is accepted and does nothing), and follows a
+ *             later mpm_set_bending.
+ * The forces join the vertex forces of CalcFemStateAndForce (MPM_ARR_FORCES includes them): the membrane kernel runs
+ * directly behind the face kernel and adds its records to the elastic ones (it counts under MPM_PHASE_FEM), the bending
+ * one behind the bending kernel (MPM_PHASE_VFORCE).  It works with pins, per-cloth materials, grid bodies, force
+ * fields, bending, fast math, deterministic mode and the coupled path.
+ * mpm_set_damping needs mpm_finalize, is ordered on the engine's stream and is a synchronisation point; substeps that
+ * mpm_run_substeps still owes are run first, with the old coefficients.  n_cloths must be mpm_cloth_count, or 0.  All
+ * zeros or n_cloths = 0 switches the feature off: the engine then launches exactly what it launches without this call.
+ * While it is on the engine does not use the re-sort's quiet-time estimate to omit re-sort check launches.
+ * Stability: explicit viscous forces need dt rho(M^-1 D) <= 2.  The entry points that check
+ * mpm_bending_max_stable_dt also return MPM_ERR_INVALID, before anything is enqueued, for a dt above
+ *   mpm_damping_max_stable_dt = 2 / max_i (1 / m_i) [ sum_{faces f around i} beta_m vol_f (2 mu + 2 lambda) |g_i| (|g_0| + |g_1| + |g_2|)
+ *                                                     + beta_b sum_j |k Q_ij| ],
+ * g_j the columns of the face's grad_N, m_i the vertex particle's mass as of the call, 2 mu + 2 lambda the largest
+ * eigenvalue of Edot -> 2 mu Edot + lambda tr(Edot) I: Gershgorin's bound at the REST shape.  A cloth stretched by a
+ * factor s lowers the true limit by about s^2 (F2 enters twice); on the other hand the grid shares a vertex's impulse
+ * with the face particles around it.  It is a guard, not a guarantee, and how conservative it is has not been
+ * measured.  +inf while the feature is off.
+ * Refused with MPM_ERR_INVALID, nothing changed: a coefficient that is negative or not finite; a wrong count; a call
+ * before mpm_finalize; any partitioned or multi-rank engine -- this call on such an engine, and mpm_dist_init, the
+ * halo, chain, team and world substeps on an engine with damping on. */
+typedef struct mpm_cloth_damping {
+    float membrane, bending;   /* seconds, >= 0 */
+} mpm_cloth_damping_t;
+MPM_API int mpm_set_damping(mpm_handle_t h, size_t n_cloths, const mpm_cloth_damping_t *d);
+/* The coefficients in force: min(mpm_cloth_count, capacity) entries into out (zeros while off), the cloth count into *n_out. */
+MPM_API int mpm_get_damping(mpm_handle_t h, mpm_cloth_damping_t *out, size_t capacity, size_t *n_out);
+/* The membrane + bending damping force on the current positions and velocities: f_out[3 * n_verts], in the vertex
+ * numbering of mpm_dump_cpu_state (zeros for the vertices of undamped cloths).  The device functions of the substep's
+ * kernels; a vertex's face records are summed on the host in ascending face id, as the vertex-force kernel sums them.
+ * Changes no state. */
+MPM_API int mpm_damping_forces(mpm_handle_t h, float *f_out);
+MPM_API int mpm_damping_max_stable_dt(mpm_handle_t h, float *dt_out);
+/* The membrane kernel's face function on the host (no handle, no device), face by face: dminv3[3 n] = (Dm0, Dm1, Dm3)
+ * of Dm^-1 = [Dm0 Dm1; 0 Dm3], vol[n], mu[n], lambda[n], beta[n], x9 / v9[9 n] the corners' positions and velocities
+ * ([corner][component]); rec9_out[9 n] the corner records G ([corner][component]; the force on a corner is -G). */
+MPM_API int mpm_damping_face_records(size_t n_faces, const float *dminv3, const float *vol, const float *mu,
+                                     const float *lambda, const float *beta, const float *x9, const float *v9,
+                                     float *rec9_out);
+
 /* ---- Energy, momentum and strain report per cloth (an extension) ----
  * What System::CalcKineticEnergy / CalcPotentialEnergy answer for a Drake plant, and what a caller choosing dt or
  * calibrating a stiffness needs: one device-side reduction instead of seven downloads and a host restatement of the
