@@ -9,7 +9,8 @@
 // the positions (no angle, no trigonometry, no singular configuration), vanishes on every affine image of the rest
 // shape, and its total and its total torque vanish identically.
 //
-// Host: bending_matrix assembles Q of one cloth in double (mpm_bending_matrix).  Device: k_bend, one lane per vertex of
+// Host: bending_matrix assembles Q of one cloth in double (mpm_bending_matrix), bending_table lays the table of all
+// cloths out (mpm_set_bending, whose device half is in mpm_cloth_host.h).  Device: k_bend, one lane per vertex of
 // the cloths with k > 0, adds f to the vertex forces k_vforce left in DP::f (launch_fem_vertices); k_bend_eval writes
 // the same numbers into a buffer in original vertex order (mpm_bending_forces).  The table is k Q without its diagonal,
 // as (float coefficient, particle id of the column) records in sliced ELL: slices of 64 rows, a slice's records column-
@@ -30,6 +31,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
+#include <string.h>
 
 #include <algorithm>
 #include <string>
@@ -224,6 +226,75 @@ inline bool bending_matrix(const float* pos, size_t n_verts, const int32_t* idx,
         k = m;
     }
     for (size_t v = 0; v < n_verts; ++v) out.off[v + 1] += out.off[v];
+    return true;
+}
+
+// The table k_bend reads, as the host lays it out (no device is touched): one row per vertex of the cloths with k > 0, in
+// ascending vertex id, k folded in, the diagonal dropped, in sliced ELL as described above.
+struct BendRecord {
+    float coef, pid_bits;   // BendArgs::ent's float2: (coefficient, int bits of the column's particle id)
+};
+struct BendTable {
+    std::vector<int> row_pid;          // [row] particle id (nf + vertex) of the row's vertex
+    std::vector<unsigned> slice_off;   // [slices + 1]
+    std::vector<BendRecord> ent;
+    std::vector<double> abs_sum;       // [row] sum_j |k Q_ij|, the diagonal included
+};
+// cloths: anything with first_vertex, n_verts, first_face, n_faces; h_pos: the rest positions, h_idx: the faces' vertex
+// ids (0-based over all cloths); stiffness: n_cloths values (0: the cloth has no rows); slice: rows per slice (BEND_SLICE).
+// false with `why` set: bending_matrix refused a cloth, or the table does not fit 2^31 records.
+template <class Cloth>
+inline bool bending_table(const std::vector<Cloth>& cloths, const float* h_pos, const int* h_idx, size_t nf, size_t n_cloths,
+                          const float* stiffness, size_t slice, BendTable& out, std::string& why) {
+    auto id_bits = [](int id) {
+        float f;
+        memcpy(&f, &id, sizeof f);
+        return f;
+    };
+    out = BendTable{};
+    std::vector<std::vector<BendRecord>> rows;
+    for (size_t c = 0; c < n_cloths; ++c) {
+        if (!(stiffness[c] > 0.f)) continue;
+        const Cloth& cl = cloths[c];
+        std::vector<int32_t> idx(3 * cl.n_faces);
+        for (size_t i = 0; i < idx.size(); ++i) idx[i] = h_idx[3 * cl.first_face + i] - (int32_t)cl.first_vertex;
+        BendCsr Q;
+        if (!bending_matrix(h_pos + 3 * cl.first_vertex, cl.n_verts, idx.data(), cl.n_faces, cl.first_face, Q, why)) return false;
+        const double k = (double)stiffness[c];
+        for (size_t v = 0; v < cl.n_verts; ++v) {
+            out.row_pid.push_back((int)(nf + cl.first_vertex + v));
+            rows.emplace_back();
+            double a = 0.0;
+            for (size_t q = Q.off[v]; q < Q.off[v + 1]; ++q) {
+                a += std::fabs(k * Q.val[q]);
+                if ((size_t)Q.col[q] == v) continue;
+                rows.back().push_back(BendRecord{(float)(k * Q.val[q]), id_bits((int)(nf + cl.first_vertex) + Q.col[q])});
+            }
+            out.abs_sum.push_back(a);
+        }
+    }
+    const size_t n_rows = out.row_pid.size(), n_slices = (n_rows + slice - 1) / slice;
+    out.slice_off.assign(n_slices + 1, 0u);
+    for (size_t s = 0; s < n_slices; ++s) {
+        size_t width = 0;
+        for (size_t r = s * slice; r < std::min(n_rows, (s + 1) * slice); ++r) width = std::max(width, rows[r].size());
+        if (!((size_t)out.slice_off[s] + width * slice < (size_t)1 << 31)) {
+            why = "bending: the table is too large";
+            return false;
+        }
+        out.slice_off[s + 1] = out.slice_off[s] + (unsigned)(width * slice);
+    }
+    out.ent.resize(out.slice_off[n_slices]);
+    for (size_t s = 0; s < n_slices; ++s) {
+        const size_t width = (out.slice_off[s + 1] - out.slice_off[s]) / slice;
+        for (size_t l = 0; l < slice; ++l) {
+            const size_t r = s * slice + l;
+            // (padding: coefficient 0 and the row's own id; the lanes past the last row are never read)
+            const int own = r < n_rows ? out.row_pid[r] : out.row_pid[n_rows - 1];
+            for (size_t q = 0; q < width; ++q)
+                out.ent[out.slice_off[s] + q * slice + l] = r < n_rows && q < rows[r].size() ? rows[r][q] : BendRecord{0.f, id_bits(own)};
+        }
+    }
     return true;
 }
 

@@ -1,0 +1,499 @@
+// Host side of the per-cloth features: cloth materials, external force fields, bending stiffness, damping and the
+// per-cloth report -- what the entry points in mpm_engine.hip call once their arguments are checked.
+// Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
+#pragma once
+#include "mpm_host.h"
+#include "mpm_io.h"
+
+// ---- cloth materials ------------------------------------------------------------------------------------------------------
+static mpm_cloth_material_t engine_cloth_material(const mpm_engine* e) {
+    const mpm_material_t& em = e->mat;
+    return mpm_cloth_material_t{em.youngs_modulus, em.poisson_ratio, em.density, em.gamma, em.K, em.c_F};
+}
+// The Lame parameters from Young's modulus and Poisson's ratio, in float: the one place that forms them (DP::M at Finalize,
+// k_fem_mat's table, the damping coefficients, mpm_cloth_energy_density), so that all of them hold the same bits.
+static void lame(float youngs_modulus, float poisson_ratio, float* mu, float* lambda) {
+    *mu = youngs_modulus / (2.f * (1.f + poisson_ratio));
+    *lambda = youngs_modulus * poisson_ratio / ((1.f + poisson_ratio) * (1.f - 2.f * poisson_ratio));
+}
+// A multi-material engine at Finalize, after the volumes are in place: k_fem_mat's table (the Lame parameters formed as
+// for the engine's material) and every particle's q[0].w scaled to its mass.  cloth_of_pid: [original id] cloth.
+static int init_cloth_materials(mpm_engine* e, const std::vector<uint8_t>& cloth_of_pid) {
+    std::vector<ClothMat> t(e->cloths.size());
+    for (size_t c = 0; c < t.size(); ++c) {
+        const mpm_cloth_material_t& m = e->cloths[c].m;
+        float mu, lambda;
+        lame(m.youngs_modulus, m.poisson_ratio, &mu, &lambda);
+        t[c] = ClothMat{mu, lambda, m.gamma, m.K, m.c_F, m.density, 0.f, 0.f};
+    }
+    if (int rc = e->dalloc(&e->d_cloth_mat, t.size(), false)) return rc;
+    H2D(e, e->d_cloth_mat, t.data(), t.size() * sizeof(ClothMat));
+    uint8_t* d_cloth = nullptr;
+    if (int rc = e->dalloc(&d_cloth, e->np, false)) return rc;
+    H2D(e, d_cloth, cloth_of_pid.data(), e->np);
+    hipLaunchKernelGGL(k_init_masses, dim3(e->g_np), dim3(256), 0, e->stream, e->dp, (const ClothMat*)e->d_cloth_mat,
+                       (const uint8_t*)d_cloth);
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    e->dfree(d_cloth);
+    return 0;
+}
+
+// the Lame parameters of cloth c as the elastic kernels use them (init_cloth_materials; DP::M of a single-material engine)
+static void cloth_lame(const mpm_engine* e, size_t c, float* mu, float* lambda) {
+    if (!e->multi_mat) {
+        *mu = e->dp.M.mu;
+        *lambda = e->dp.M.lambda;
+        return;
+    }
+    lame(e->cloths[c].m.youngs_modulus, e->cloths[c].m.poisson_ratio, mu, lambda);
+}
+
+// ---- external force fields (mpm_set_force_fields, mpm_get_force_fields, mpm_force_field_acceleration; mpm_fields.h) ----
+static int validate_force_fields(size_t n, const mpm_force_field_t* f) {
+    static_assert(sizeof(ForceField) == sizeof(mpm_force_field_t), "force field layouts differ");
+    REQUIRE(n <= (size_t)MAX_FORCE_FIELDS, "too many force fields (at most 8)");
+    REQUIRE(n == 0 || f, "null force field array");
+    for (size_t k = 0; k < n; ++k) {
+        const mpm_force_field_t& q = f[k];
+        REQUIRE(q.kind >= MPM_FF_ACCEL && q.kind <= MPM_FF_NORMAL_DRAG, "force field: unknown kind");
+        REQUIRE((q.flags & ~(uint32_t)(MPM_FF_QUADRATIC | MPM_FF_REGION)) == 0, "force field: unknown flags");
+        REQUIRE(std::isfinite(q.gamma) && finite_n(q.u0, 3) && finite_n(q.G, 9) && finite_n(q.x0, 3) && finite_n(q.lo, 3) &&
+                    finite_n(q.hi, 3),
+                "force field: a number is not finite");
+        REQUIRE(q.gamma >= 0.f, "force field: gamma < 0");
+        REQUIRE(q.lo[0] <= q.hi[0] && q.lo[1] <= q.hi[1] && q.lo[2] <= q.hi[2], "force field: lo > hi");
+    }
+    return 0;
+}
+
+static int set_force_fields(mpm_engine* e, size_t n, const mpm_force_field_t* fields) {
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    double gamma = 0.0;
+    if (n) {
+        ForceFieldTable table;
+        std::memset(&table, 0, sizeof(table));
+        table.n = (int)n;
+        std::memcpy(table.f, fields, n * sizeof(ForceField));
+        for (size_t k = 0; k < n; ++k)
+            if (fields[k].kind != MPM_FF_ACCEL && !(fields[k].flags & MPM_FF_QUADRATIC)) gamma += (double)fields[k].gamma;
+        if (!e->d_force_fields)
+            if (int rc = e->dalloc(&e->d_force_fields, 1, true)) return rc;
+        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
+        H2D(e, e->d_force_fields, &table, sizeof(table));
+    }
+    e->force_fields.assign(fields, fields + n);
+    e->force_fields_gamma = gamma;
+    return 0;
+}
+
+// host code only: no device is touched
+static int force_field_accelerations(const mpm_force_field_t* fields, size_t n_fields, size_t n, const float* x, const float* v,
+                                     const float* director, float* acc_out) {
+    const ForceField* f = reinterpret_cast<const ForceField*>(fields);
+    const float zero[3] = {0.f, 0.f, 0.f};
+    for (size_t k = 0; k < n; ++k)
+        force_field_acceleration(f, (int)n_fields, x + 3 * k, v + 3 * k, director ? director + 3 * k : zero, director != nullptr,
+                                 acc_out + 3 * k);
+    return 0;
+}
+
+// ---- bending stiffness (mpm_set_bending, mpm_get_bending, mpm_bending_forces, mpm_bending_max_stable_dt,
+// mpm_bending_matrix; mpm_bending.h) ----
+static void damping_limit(mpm_engine* e);
+// host code only: no device is touched
+static int bending_matrix_out(const float* pos, size_t n_verts, const int32_t* indices, size_t n_faces, size_t* row_offsets,
+                              int32_t* cols, double* vals, size_t capacity, size_t* nnz_out) {
+    BendCsr Q;
+    std::string why;
+    if (!bending_matrix(pos, n_verts, indices, n_faces, 0, Q, why)) return fail(MPM_ERR_INVALID, why);
+    if (row_offsets) std::copy(Q.off.begin(), Q.off.end(), row_offsets);
+    const size_t n = std::min(capacity, Q.col.size());
+    std::copy(Q.col.begin(), Q.col.begin() + (long)n, cols);
+    std::copy(Q.val.begin(), Q.val.begin() + (long)n, vals);
+    if (nnz_out) *nnz_out = Q.col.size();
+    return 0;
+}
+
+// The stability limit of an explicit step against a rate omega (dt * omega <= 2): the float not above 2 / omega, rounded
+// towards zero so that it is never above the bound; INFINITY when nothing limits the step (omega not positive).
+static float stable_dt_limit(double omega) {
+    if (!(omega > 0.0)) return INFINITY;
+    const double lim = 2.0 / omega;
+    float dt = (float)lim;
+    if ((double)dt > lim) dt = std::nextafterf(dt, 0.f);
+    return dt;
+}
+// Every vertex's mass as ParticleToGrid forms it: q[0].w x DP::M.density, both floats, by original vertex id.  One gather:
+// with `w_all` every particle's q[0].w in original order (faces, then vertices) is handed out too.
+static int vertex_masses(mpm_engine* e, std::vector<float>& mass, std::vector<float>* w_all = nullptr) {
+    int* iota = nullptr;
+    if (int rc = device_iota(e, &iota)) return rc;
+    mass.resize(e->nv);
+    const float* w = mass.data();
+    if (w_all) {
+        w_all->resize(e->np);
+        if (int rc = gather_to_host<F_VOL>(e, w_all->data(), e->np, iota)) return rc;
+        w = w_all->data() + e->nf;
+    } else if (int rc = gather_to_host<F_VOL>(e, mass.data(), e->nv, iota + e->nf)) {
+        return rc;
+    }
+    for (size_t i = 0; i < e->nv; ++i) mass[i] = std::fabs(w[i]) * e->dp.M.density;
+    return 0;
+}
+
+// mpm_bending_max_stable_dt of a table (bending_table's rows) on the vertices' masses: symplectic Euler on the lumped
+// system needs dt * omega <= 2, with Gershgorin's bound omega^2 <= max_i (1 / m_i) sum_j |k Q_ij|
+static float bending_limit(const BendTable& t, const std::vector<float>& mass, size_t nf) {
+    double w2 = 0.0;
+    for (size_t r = 0; r < t.row_pid.size(); ++r) {
+        const double m = (double)mass[(size_t)t.row_pid[r] - nf];
+        if (t.abs_sum[r] > 0.0) w2 = std::max(w2, m > 0.0 ? t.abs_sum[r] / m : (double)INFINITY);
+    }
+    return stable_dt_limit(std::sqrt(w2));
+}
+// The table `t` with its limit and the caller's stiffnesses put in force: new device arrays, upload, swap.  The caller has
+// settled the owed substeps.  A failure changes nothing: the new buffers go, the table in force stays.
+static int bending_swap(mpm_engine* e, BendTable& t, float max_dt, size_t n_cloths, const float* stiffness) {
+    static_assert(sizeof(BendRecord) == sizeof(float2), "bending record layouts differ");
+    const size_t n_rows = t.row_pid.size();
+    mpm_engine::Bending next;
+    FreshArrays fresh(e);
+    if (n_rows) {
+        int* d_row = nullptr;
+        unsigned* d_off = nullptr;
+        float2* d_ent = nullptr;
+        if (int rc = fresh.alloc(&d_row, n_rows, false)) return rc;
+        if (int rc = fresh.alloc(&d_off, t.slice_off.size(), false)) return rc;
+        if (int rc = fresh.alloc(&d_ent, t.ent.size(), false)) return rc;
+        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
+        H2D(e, d_row, t.row_pid.data(), n_rows * sizeof(int));
+        H2D(e, d_off, t.slice_off.data(), t.slice_off.size() * sizeof(unsigned));
+        if (!t.ent.empty()) H2D(e, d_ent, t.ent.data(), t.ent.size() * sizeof(float2));
+        next.args = BendArgs{d_row, d_off, d_ent, (int)n_rows};
+    } else {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    {
+        BendArgs& old = e->bend.args;
+        int* o_row = const_cast<int*>(old.row_pid);
+        unsigned* o_off = const_cast<unsigned*>(old.slice_off);
+        float2* o_ent = const_cast<float2*>(old.ent);
+        e->dfree(o_row);
+        e->dfree(o_off);
+        e->dfree(o_ent);
+    }
+    next.k.assign(stiffness, stiffness + n_cloths);
+    next.max_dt = max_dt;
+    next.row_vertex.resize(n_rows);
+    for (size_t r = 0; r < n_rows; ++r) next.row_vertex[r] = t.row_pid[r] - (int)e->nf;
+    next.abs_sum.swap(t.abs_sum);
+    e->bend = next;
+    fresh.commit();
+    return 0;
+}
+// mpm_set_bending in three steps: the table on the host, its limit from the vertices' masses, the swap
+static int set_bending(mpm_engine* e, size_t n_cloths, const float* stiffness) {
+    for (size_t c = 0; c < n_cloths; ++c)
+        REQUIRE(std::isfinite(stiffness[c]) && stiffness[c] >= 0.f, "bending: a stiffness is negative or not finite");
+    BendTable t;
+    std::string why;
+    if (!bending_table(e->cloths, e->h_pos.data(), e->h_idx.data(), e->nf, n_cloths, stiffness, BEND_SLICE, t, why))
+        return fail(MPM_ERR_INVALID, why);
+    // substeps that mpm_run_substeps deferred are owed with the stiffness they were enqueued with
+    if (int rc = settle(e)) return rc;
+    float max_dt = INFINITY;
+    if (!t.row_pid.empty()) {
+        std::vector<float> mass;
+        if (int rc = vertex_masses(e, mass)) return rc;
+        max_dt = bending_limit(t, mass, e->nf);
+    }
+    if (int rc = bending_swap(e, t, max_dt, n_cloths, stiffness)) return rc;
+    damping_limit(e);   // (the hinge damping is beta k Q: its share of mpm_damping_max_stable_dt follows the new k)
+    return 0;
+}
+
+static int bending_forces(mpm_engine* e, float* f_out) {
+    const size_t bytes = e->nv * 12;
+    if (!e->bend.on()) {
+        std::memset(f_out, 0, bytes);
+        return 0;
+    }
+    if (int rc = e->stage(bytes)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
+    hipLaunchKernelGGL(k_bend_eval, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
+                       e->bend.args, (float*)e->d_stage);
+    D2H(e, f_out, e->d_stage, bytes);
+    return 0;
+}
+
+// ---- stiffness-proportional damping (mpm_set_damping, mpm_get_damping, mpm_damping_forces, mpm_damping_max_stable_dt,
+// mpm_damping_face_records; mpm_damping.h) ----
+// mpm_damping_max_stable_dt from what the engine holds: the membrane row sums and vertex masses of the last
+// mpm_set_damping, the rows of the bending table in force.  Host only; cannot fail.  Also says whether k_bend_damp has a
+// row to work on (a cloth with beta_bending > 0 and bending stiffness > 0).
+static void damping_limit(mpm_engine* e) {
+    mpm_engine::Damping& dm = e->damp;
+    dm.max_dt = INFINITY;
+    dm.bend_rows = false;
+    if (!dm.any()) return;
+    std::vector<double> D(e->nv, 0.0);
+    if (dm.membrane()) D = dm.D_membrane;
+    if (e->bend.on())
+        for (size_t r = 0; r < e->bend.row_vertex.size(); ++r) {
+            const size_t v = (size_t)e->bend.row_vertex[r];
+            const float beta = dm.beta_vertex[v];
+            if (!(beta > 0.f)) continue;
+            dm.bend_rows = true;
+            D[v] += (double)beta * e->bend.abs_sum[r];
+        }
+    double worst = 0.0;
+    for (size_t i = 0; i < e->nv; ++i)
+        if (D[i] > 0.0) worst = std::max(worst, dm.mass[i] > 0.0 ? D[i] / dm.mass[i] : (double)INFINITY);
+    dm.max_dt = stable_dt_limit(worst);
+}
+// Puts the coefficients `d` (checked; one per cloth, or none) in force: k_damp's tables, k_bend_damp's coefficient per
+// vertex (it reads the bending table in force) and the stability limit.  The caller has settled the owed substeps.  A
+// failure changes nothing.
+static int damping_apply(mpm_engine* e, std::vector<mpm_cloth_damping_t> d) {
+    const size_t nc = d.size();
+    bool membrane = false, bending = false;
+    for (size_t c = 0; c < nc; ++c) {
+        membrane = membrane || d[c].membrane > 0.f;
+        bending = bending || d[c].bending > 0.f;
+    }
+    mpm_engine::Damping next;
+    FreshArrays fresh(e);
+    if (membrane || bending) {
+        std::vector<float4> coef(std::max<size_t>(nc, 1), make_float4(0.f, 0.f, 0.f, 0.f));
+        std::vector<int> cloth_of_face(e->nf, 0);
+        next.beta_vertex.assign(e->nv, 0.f);
+        for (size_t c = 0; c < nc; ++c) {
+            const mpm_engine::Cloth& cl = e->cloths[c];
+            float mu, lambda;
+            cloth_lame(e, c, &mu, &lambda);
+            coef[c] = make_float4(mu, lambda, d[c].membrane, 0.f);
+            std::fill(cloth_of_face.begin() + (long)cl.first_face, cloth_of_face.begin() + (long)(cl.first_face + cl.n_faces), (int)c);
+            std::fill(next.beta_vertex.begin() + (long)cl.first_vertex, next.beta_vertex.begin() + (long)(cl.first_vertex + cl.n_verts),
+                      d[c].bending);
+        }
+        // every particle's q[0].w in original order: a vertex's mass as ParticleToGrid forms it (x DP::M.density, both floats),
+        // a face's rest volume (a multi-material engine holds the mass there: / the cloth's density)
+        std::vector<float> w, mass;
+        if (int rc = vertex_masses(e, mass, &w)) return rc;
+        next.mass.assign(mass.begin(), mass.end());
+        if (membrane) {
+            // sum_j |D_ij| of the membrane's damping matrix at the rest shape, per vertex (Gershgorin)
+            std::vector<float> dminv(e->nf * 4);
+            int* iota = nullptr;
+            if (int rc = device_iota(e, &iota)) return rc;
+            if (int rc = gather_to_host<F_DMINV>(e, dminv.data(), e->nf, iota)) return rc;
+            next.D_membrane.assign(e->nv, 0.0);
+            for (size_t f = 0; f < e->nf; ++f) {
+                const float4 c = coef[(size_t)cloth_of_face[f]];
+                if (!(c.z > 0.f)) continue;
+                const double Dm0 = dminv[4 * f], Dm1 = dminv[4 * f + 1], Dm3 = dminv[4 * f + 3];
+                const double vol = std::fabs((double)w[f]) / (e->multi_mat ? (double)e->h_rho_of_pid[f] : 1.0);
+                const double g[3] = {std::hypot(Dm0, Dm1 + Dm3), std::hypot(Dm0, Dm1), std::fabs(Dm3)};   // |columns of grad_N|
+                const double s = (double)c.z * vol * (2.0 * (double)c.x + 2.0 * (double)c.y) * (g[0] + g[1] + g[2]);
+                for (int k = 0; k < 3; ++k) next.D_membrane[(size_t)e->h_idx[3 * f + k]] += s * g[k];
+            }
+            float4* d_coef = nullptr;
+            int* d_cloth = nullptr;
+            if (int rc = fresh.alloc(&d_coef, coef.size(), false)) return rc;
+            if (int rc = fresh.alloc(&d_cloth, cloth_of_face.size(), false)) return rc;
+            H2D(e, d_coef, coef.data(), coef.size() * sizeof(float4));
+            if (!cloth_of_face.empty()) H2D(e, d_cloth, cloth_of_face.data(), cloth_of_face.size() * sizeof(int));
+            next.args = DampArgs{d_coef, d_cloth};
+        }
+        if (bending) {
+            if (int rc = fresh.alloc(&next.d_beta_vertex, e->nv, false)) return rc;
+            H2D(e, next.d_beta_vertex, next.beta_vertex.data(), e->nv * sizeof(float));
+        }
+    }
+    // (a synchronisation point: the kernels enqueued so far have read the old tables)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    {
+        float4* o_coef = const_cast<float4*>(e->damp.args.coef);
+        int* o_cloth = const_cast<int*>(e->damp.args.cloth_of_face);
+        e->dfree(o_coef);
+        e->dfree(o_cloth);
+        e->dfree(e->damp.d_beta_vertex);
+    }
+    next.d.swap(d);
+    e->damp = next;
+    fresh.commit();
+    damping_limit(e);
+    return 0;
+}
+
+static int damping_forces(mpm_engine* e, float* f_out) {
+    std::memset(f_out, 0, e->nv * 12);
+    const bool hinges = e->bend.on() && e->damp.bending();
+    if (!e->damp.membrane() && !hinges) return 0;
+    // the face records in original face order, behind them the bending rows in original vertex order
+    const size_t n_rec = e->nf * 9, n_all = n_rec + e->nv * 3;
+    if (int rc = e->stage(n_all * 4)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, n_all * 4, e->stream));
+    if (e->damp.membrane() && e->nf)
+        hipLaunchKernelGGL(k_damp_eval, dim3((unsigned)((e->nf + 255) / 256)), dim3(256), 0, e->stream, e->dp, e->damp.args,
+                           (float*)e->d_stage);
+    if (hinges)
+        hipLaunchKernelGGL(k_bend_damp_eval, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
+                           e->bend.args, (const float*)e->damp.d_beta_vertex, (float*)e->d_stage + n_rec);
+    HIP_TRY(hipGetLastError());
+    std::vector<float> h(n_all);
+    D2H(e, h.data(), e->d_stage, n_all * 4);
+    // a vertex's records in ascending original face id, as k_vforce sums them; then the bending row, as k_bend_damp adds it
+    for (size_t f = 0; f < e->nf; ++f)
+        for (int c = 0; c < 3; ++c) {
+            float* o = f_out + 3 * (size_t)e->h_idx[3 * f + c];
+            for (int k = 0; k < 3; ++k) o[k] += -h[9 * f + 3 * c + k];
+        }
+    for (size_t i = 0; i < e->nv * 3; ++i) f_out[i] += h[n_rec + i];
+    return 0;
+}
+
+// host code only: the device function of the kernels, compiled for the host
+static int damping_face_records(size_t n_faces, const float* dminv3, const float* vol, const float* mu, const float* lambda,
+                                const float* beta, const float* x9, const float* v9, float* rec9_out) {
+    for (size_t f = 0; f < n_faces; ++f) {
+        float x[3][3], v[3][3], rec[3][3];
+        std::memcpy(x, x9 + 9 * f, sizeof x);
+        std::memcpy(v, v9 + 9 * f, sizeof v);
+        damp_face(dminv3[3 * f], dminv3[3 * f + 1], dminv3[3 * f + 2], vol[f], mu[f], lambda[f], beta[f], x, v, rec);
+        std::memcpy(rec9_out + 9 * f, rec, sizeof rec);
+    }
+    return 0;
+}
+
+// ---- the per-cloth report (mpm_measure, mpm_face_strain, mpm_cloth_energy_density; mpm_measure.h) ----
+// The chunk table: every cloth's faces, then every cloth's vertices, in runs of at most MEASURE_CHUNK original ids that
+// never straddle a cloth.  Built once; the vertex chunks' rows of the bending table follow mpm_set_bending.
+static int measure_ready(mpm_engine* e) {
+    mpm_engine::Measure& ms = e->measure;
+    const size_t nc = e->cloths.size();
+    if (!ms.built) {
+        std::vector<int4> chunks, ranges(nc, make_int4(0, 0, 0, 0));
+        const int nfg = e->dp.NfG;
+        for (int pass = 0; pass < 2; ++pass) {
+            for (size_t c = 0; c < nc; ++c) {
+                const mpm_engine::Cloth& cl = e->cloths[c];
+                const int first = pass == 0 ? (int)cl.first_face : nfg + (int)cl.first_vertex;
+                const int end = first + (int)(pass == 0 ? cl.n_faces : cl.n_verts);
+                (pass == 0 ? ranges[c].x : ranges[c].z) = (int)chunks.size();
+                for (int b = first; b < end; b += MEASURE_CHUNK) chunks.push_back(make_int4((int)c, b, std::min(end, b + MEASURE_CHUNK), -1));
+                (pass == 0 ? ranges[c].y : ranges[c].w) = (int)chunks.size();
+            }
+            if (pass == 0) ms.n_face_chunks = (int)chunks.size();
+        }
+        ms.n_vertex_chunks = (int)chunks.size() - ms.n_face_chunks;
+        FreshArrays fresh(e);
+        int4 *d_chunks = nullptr, *d_ranges = nullptr;
+        mpm_cloth_measure_t *d_rows = nullptr, *d_out = nullptr;
+        if (int rc = fresh.alloc(&d_chunks, chunks.size(), false)) return rc;
+        if (int rc = fresh.alloc(&d_ranges, nc, false)) return rc;
+        if (int rc = fresh.alloc(&d_rows, chunks.size(), true)) return rc;
+        if (int rc = fresh.alloc(&d_out, nc, true)) return rc;
+        if (nc) H2D(e, d_ranges, ranges.data(), nc * sizeof(int4));
+        fresh.commit();
+        ms.d_chunks = d_chunks; ms.d_ranges = d_ranges; ms.d_rows = d_rows; ms.d_out = d_out;
+        ms.chunks.swap(chunks);
+        ms.rows_stale = true;
+        ms.built = true;
+    }
+    if (ms.rows_stale || ms.k_seen != e->bend.k) {
+        // row of the bending table of every cloth's first vertex: the table holds the cloths with k > 0, in cloth order
+        std::vector<int> row0(nc, -1);
+        int r = 0;
+        for (size_t c = 0; c < nc && e->bend.on(); ++c)
+            if (c < e->bend.k.size() && e->bend.k[c] > 0.f) {
+                row0[c] = r;
+                r += (int)e->cloths[c].n_verts;
+            }
+        if (r != (e->bend.on() ? e->bend.args.n_rows : 0)) return fail(MPM_ERR_INTERNAL, "mpm_measure: the bending table does not match the cloths");
+        for (int k = ms.n_face_chunks; k < (int)ms.chunks.size(); ++k) {
+            int4& ch = ms.chunks[(size_t)k];
+            const int base = e->dp.NfG + (int)e->cloths[(size_t)ch.x].first_vertex;
+            ch.w = row0[(size_t)ch.x] < 0 ? -1 : row0[(size_t)ch.x] + (ch.y - base);
+        }
+        if (!ms.chunks.empty()) H2D(e, ms.d_chunks, ms.chunks.data(), ms.chunks.size() * sizeof(int4));
+        ms.k_seen = e->bend.k;
+        ms.rows_stale = false;
+    }
+    return 0;
+}
+static MeasureArgs measure_args(const mpm_engine* e) {
+    const mpm_engine::Measure& ms = e->measure;
+    MeasureArgs a{};
+    a.chunks = ms.d_chunks;
+    a.n_face_chunks = ms.n_face_chunks;
+    a.n_vertex_chunks = ms.n_vertex_chunks;
+    a.rows = ms.d_rows;
+    a.mats = e->multi_mat ? e->d_cloth_mat : nullptr;
+    a.bend = e->bend.args;
+    return a;
+}
+
+static int measure_cloths(mpm_engine* e, mpm_cloth_measure_t* per_cloth, size_t capacity, size_t* n_cloths_out,
+                          mpm_cloth_measure_t* total) {
+    if (int rc = measure_ready(e)) return rc;
+    const size_t nc = e->cloths.size();
+    const MeasureArgs a = measure_args(e);
+    // at most three launches: face chunks, vertex chunks, one workgroup per cloth
+    if (a.n_face_chunks) hipLaunchKernelGGL(k_measure_faces, dim3((unsigned)a.n_face_chunks), dim3(256), 0, e->stream, e->dp, a);
+    if (a.n_vertex_chunks) hipLaunchKernelGGL(k_measure_vertices, dim3((unsigned)a.n_vertex_chunks), dim3(256), 0, e->stream, e->dp, a);
+    std::vector<mpm_cloth_measure_t> rows(nc);
+    if (nc) {
+        hipLaunchKernelGGL(k_measure_final, dim3((unsigned)nc), dim3(256), 0, e->stream, a, (const int4*)e->measure.d_ranges,
+                           e->measure.d_out);
+        HIP_TRY(hipGetLastError());
+        D2H(e, rows.data(), e->measure.d_out, nc * sizeof(mpm_cloth_measure_t));
+    }
+    std::copy(rows.begin(), rows.begin() + (long)std::min(capacity, nc), per_cloth);
+    if (n_cloths_out) *n_cloths_out = nc;
+    if (total) {
+        mpm_cloth_measure_t t{};
+        t.stretch_min = INFINITY;
+        t.normal_min = INFINITY;
+        double* ts = reinterpret_cast<double*>(&t);
+        for (const mpm_cloth_measure_t& r : rows) {
+            const double* rs = reinterpret_cast<const double*>(&r);
+            for (int k = 0; k < MEASURE_SUMS; ++k) ts[k] += rs[k];
+            t.stretch_max = std::max(t.stretch_max, r.stretch_max);
+            t.stretch_min = std::min(t.stretch_min, r.stretch_min);
+            t.normal_min = std::min(t.normal_min, r.normal_min);
+            t.speed_max = std::max(t.speed_max, r.speed_max);
+            t.faces += r.faces;
+            t.vertices += r.vertices;
+        }
+        *total = t;
+    }
+    return 0;
+}
+
+static int face_strain(mpm_engine* e, float* out) {
+    if (e->nf == 0) return 0;
+    if (int rc = measure_ready(e)) return rc;
+    const MeasureArgs a = measure_args(e);
+    const size_t bytes = e->nf * 16;
+    if (int rc = e->stage(bytes)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
+    hipLaunchKernelGGL(k_measure_face_strain, dim3((unsigned)a.n_face_chunks), dim3(256), 0, e->stream, e->dp, a, (float*)e->d_stage);
+    HIP_TRY(hipGetLastError());
+    D2H(e, out, e->d_stage, bytes);
+    return 0;
+}
+
+// host code only: the device function of the kernels, compiled for the host
+static int cloth_energy_densities(const mpm_cloth_material_t* m, size_t n, const float* F, double* out) {
+    float mu, lambda;   // (as mpm_finalize forms them, in float)
+    lame(m->youngs_modulus, m->poisson_ratio, &mu, &lambda);
+    for (size_t i = 0; i < n; ++i) {
+        const float* f = F + 9 * i;
+        const double d1[3] = {(double)f[0], (double)f[3], (double)f[6]}, d2[3] = {(double)f[1], (double)f[4], (double)f[7]};
+        const double d3[3] = {(double)f[2], (double)f[5], (double)f[8]};
+        cloth_energy_density(mu, lambda, m->K, m->gamma, d1, d2, d3, out + 6 * i);
+    }
+    return 0;
+}

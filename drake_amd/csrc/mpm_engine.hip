@@ -1,6 +1,10 @@
 // Host side of the engine and the C ABI declared in include/mpm_hip.h.
 // One translation unit: the kernels are header-only so hipcc can inline the
 // device math into them.
+// This file holds EVERY entry point of the C ABI, the substep's launch sequence (launch_*, enqueue_substep_front / _rest),
+// settle and the deferral of phase calls, the halo entry points and the run, profile and coupled drivers.  What a feature
+// does behind its entry points is in the feature's host header (mpm_io.h, mpm_contact.h, mpm_cloth_host.h,
+// mpm_bodies_host.h, mpm_dist_host.h, mpm_chain_host.h): an entry point here checks its arguments and makes one call.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,9 +19,6 @@
 #include <numeric>
 #include <string>
 #include <thread>
-#include <type_traits>
-#include <unordered_map>
-#include <unordered_set>
 #include <vector>
 
 #include "../../include/mpm_hip.h"
@@ -28,6 +29,10 @@
 #include "mpm_chain.h"
 #include "mpm_feedback.h"
 #include "mpm_dist.h"
+#include "mpm_cloth_host.h"
+#include "mpm_bodies_host.h"
+#include "mpm_dist_host.h"
+#include "mpm_chain_host.h"
 
 // every engine alive in this process (mpm_device_synchronize)
 static std::mutex g_live_mutex;
@@ -87,10 +92,6 @@ int mpm_create(int domain_bits, const mpm_material_t* material, int device, mpm_
     return 0;
 } MPM_CATCH_ALL
 
-static mpm_cloth_material_t engine_cloth_material(const mpm_engine* e) {
-    const mpm_material_t& em = e->mat;
-    return mpm_cloth_material_t{em.youngs_modulus, em.poisson_ratio, em.density, em.gamma, em.K, em.c_F};
-}
 // (m: the cloth's own material, or null for the engine's; checked by the caller.  Nothing is recorded on a refusal.)
 static int add_cloth(mpm_engine* e, const float* pos, const float* vel, size_t n_verts, const int32_t* indices,
                      size_t n_faces, const mpm_cloth_material_t* m) {
@@ -152,63 +153,11 @@ int mpm_get_cloth_info(mpm_handle_t e, size_t cloth, size_t* first_vertex, size_
     return 0;
 } MPM_CATCH_ALL
 
-// ---- analytic colliders of the grid update ---------------------------------------------------
-// The reference's compile-time scenes (cuda_mpm_kernels.cuh:673-774) as tables; MPM_BC_TABLE selects
-// the table set with mpm_set_grid_colliders.
-static GridCollider gc_sphere(float x, float y, float z, float r, int mode, float friction) {
-    GridCollider c{};
-    c.shape = 0; c.mode = mode;
-    c.p[0] = x; c.p[1] = y; c.p[2] = z;
-    c.radius = r; c.friction = friction;
-    return c;
-}
-static int grid_collider_preset(int bc, float sdf_friction, GridColliders* out) {
-    out->n = 0;
-    switch (bc) {
-        case -1: return 0;
-        case 0:   // one sphere, slip, active while approaching (:673-692)
-            out->c[out->n++] = gc_sphere(.5f, .5f, .5f, .08f, 1, sdf_friction);
-            return 0;
-        case 1:   // two fixed spheres (:694-734)
-            out->c[out->n++] = gc_sphere(.38f, .38f, .75f, .04f, 0, sdf_friction);
-            out->c[out->n++] = gc_sphere(.38f, .62f, .75f, .04f, 0, sdf_friction);
-            return 0;
-        case 2: { // plane z < 0.11, slip, active whenever inside (:737-749)
-            GridCollider c{};
-            c.shape = 1; c.mode = 2;
-            c.p[2] = .11f; c.n[2] = 1.f; c.friction = sdf_friction;
-            out->c[out->n++] = c;
-            return 0;
-        }
-        case 3: { // four pin spheres (:752-774)
-            const float span[2] = {.3f, .7f};
-            for (int k = 0; k < 4; ++k) out->c[out->n++] = gc_sphere(span[k % 2], span[k / 2], .5f, .02f, 0, sdf_friction);
-            return 0;
-        }
-        default: return -1;
-    }
-}
-// MPM_BC_BODIES: n = -1 stands for "the engine's body table" (launch_grid picks k_grid_bodies); an empty table is mpm_bc = -1
-static int grid_colliders_for(mpm_engine* e, int bc, GridColliders* out) {
-    if (bc == MPM_BC_BODIES) {
-        *out = GridColliders{};
-        out->n = e->grid_bodies.empty() ? 0 : -1;
-        return 0;
-    }
-    if (bc == MPM_BC_TABLE) {
-        *out = e->grid_colliders;
-        return 0;
-    }
-    if (grid_collider_preset(bc, e->mat.sdf_friction, out))
-        return fail(MPM_ERR_INVALID, "mpm_bc must be -1, 0, 1, 2, 3, MPM_BC_TABLE or MPM_BC_BODIES");
-    return 0;
-}
-
 // The conditional re-sort.  lean: CalcFemStateAndForce follows at once (DP::lean_resort).  dt: the length of the substep the
 // launches belong to, where there is one -- the anticipatory binning then uses it; the last known length stays otherwise.
 // (The block tables may change: the contact solve's guess of how many blocks are active survives that, k_ct_keys verifies
 // it on the device.)
-static void launch_rebuild(mpm_engine* e, DP p, bool lean = false, float dt = 0.f) {
+static void launch_rebuild(mpm_engine* e, DP p, bool lean, float dt) {
     if (dt > 0.f) e->last_dt = dt;
     p.anticip = e->anticipation();
     p.lean_resort = lean && !p.dist.on;
@@ -362,7 +311,6 @@ static void enqueue_substep_rest(mpm_engine* e, GridForm form, const DP& pg, con
 // The P2G tiles accumulate in 64-bit fixed point.  Scales are powers of two chosen from the
 // total particle mass M: a node can never hold more than M, and its momentum is allowed
 // |v| < 2^15 length units per time unit.  Resolution: M * 2^-61 (mass), M * 2^-47 (momentum).
-static int recover_slab_overflow(mpm_engine* e, Ctl& c);
 static int set_fixed_point_scales(mpm_engine* e) {
     DP& p = e->dp;
     // (slot space: the whole scene, or -- rare: volumes uploaded to a partitioned engine -- what this rank holds;
@@ -381,28 +329,6 @@ static int set_fixed_point_scales(mpm_engine* e) {
     p.fix_p = std::ldexp(1.0, k - 14);
     p.unfix_m = 1.0 / p.fix_m;
     p.unfix_p = 1.0 / p.fix_p;
-    return 0;
-}
-
-// A multi-material engine at Finalize, after the volumes are in place: k_fem_mat's table (the Lame parameters formed as
-// for the engine's material) and every particle's q[0].w scaled to its mass.  cloth_of_pid: [original id] cloth.
-static int init_cloth_materials(mpm_engine* e, const std::vector<uint8_t>& cloth_of_pid) {
-    std::vector<ClothMat> t(e->cloths.size());
-    for (size_t c = 0; c < t.size(); ++c) {
-        const mpm_cloth_material_t& m = e->cloths[c].m;
-        t[c] = ClothMat{m.youngs_modulus / (2.f * (1.f + m.poisson_ratio)),
-                        m.youngs_modulus * m.poisson_ratio / ((1.f + m.poisson_ratio) * (1.f - 2.f * m.poisson_ratio)),
-                        m.gamma, m.K, m.c_F, m.density, 0.f, 0.f};
-    }
-    if (int rc = e->dalloc(&e->d_cloth_mat, t.size(), false)) return rc;
-    H2D(e, e->d_cloth_mat, t.data(), t.size() * sizeof(ClothMat));
-    uint8_t* d_cloth = nullptr;
-    if (int rc = e->dalloc(&d_cloth, e->np, false)) return rc;
-    H2D(e, d_cloth, cloth_of_pid.data(), e->np);
-    hipLaunchKernelGGL(k_init_masses, dim3(e->g_np), dim3(256), 0, e->stream, e->dp, (const ClothMat*)e->d_cloth_mat,
-                       (const uint8_t*)d_cloth);
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    e->dfree(d_cloth);
     return 0;
 }
 
@@ -438,8 +364,7 @@ int mpm_finalize(mpm_handle_t e) try {
     p.dx = 1.f / p.dxinv;
     p.Dinv = 4.f * p.dxinv * p.dxinv;
     const mpm_material_t& m = e->mat;
-    p.M.mu = m.youngs_modulus / (2.f * (1.f + m.poisson_ratio));
-    p.M.lambda = m.youngs_modulus * m.poisson_ratio / ((1.f + m.poisson_ratio) * (1.f - 2.f * m.poisson_ratio));
+    lame(m.youngs_modulus, m.poisson_ratio, &p.M.mu, &p.M.lambda);
     p.M.density = m.density; p.M.gamma = m.gamma; p.M.K = m.K; p.M.V = m.V; p.M.cF = m.c_F;
     // a multi-material engine stores each particle's mass in q[0].w (k_init_masses below, k_fem_mat for the faces):
     // every reader that multiplies q[0].w by DP::M.density then gets it unchanged
@@ -670,8 +595,6 @@ int mpm_counts(mpm_handle_t e, size_t* nv, size_t* nf, size_t* np) try {
     return 0;
 } MPM_CATCH_ALL
 
-static int settle(mpm_engine* e, Ctl* fresh = nullptr);
-
 int mpm_set_deterministic(mpm_handle_t e, int on) try {
     REQUIRE(e, "null handle");
     if (e->finalized) {
@@ -795,36 +718,6 @@ int mpm_sync(mpm_handle_t e) try {
     return 0;
 } MPM_CATCH_ALL
 
-// ---- fixed constraints: checks of the substep entry points ------------------------------------------------------------
-// Every pin's body has a motion (MPM_ERR_INVALID otherwise, before anything is enqueued), and the device table is the
-// current pin set with each pin's motion slot resolved.
-static int pins_ready(mpm_engine* e) {
-    mpm_engine::PinState& ps = e->pin;
-    if (ps.set.empty()) return 0;
-    std::unordered_map<uint32_t, uint32_t> slot_of;
-    for (size_t k = 0; k < ps.motion_body.size(); ++k) slot_of[ps.motion_body[k]] = (uint32_t)k;
-    for (const mpm_pin_t& q : ps.set)
-        if (!slot_of.count(q.body))
-            return fail(MPM_ERR_INVALID, "pin on body " + std::to_string(q.body) + ", which has no motion: call mpm_set_body_motions first");
-    if (!ps.table_dirty) return 0;
-    std::vector<PinDev> t(ps.set.size());
-    for (size_t k = 0; k < t.size(); ++k) {
-        const mpm_pin_t& q = ps.set[k];
-        t[k] = PinDev{(uint32_t)e->dp.NfG + q.vertex, slot_of[q.body], q.body, {q.p_BQ[0], q.p_BQ[1], q.p_BQ[2]}};
-    }
-    if (t.size() > ps.cap_pins) {
-        HIP_TRY(hipStreamSynchronize(e->stream));   // (earlier substeps may still read the old table)
-        e->dfree(ps.d_pins);
-        ps.cap_pins = 0;
-        if (int rc = e->dalloc(&ps.d_pins, t.size(), false)) return rc;
-        ps.cap_pins = t.size();
-    }
-    if (!ps.d_ticket)
-        if (int rc = e->dalloc(&ps.d_ticket, 1, true)) return rc;
-    H2D(e, ps.d_pins, t.data(), t.size() * sizeof(PinDev));
-    ps.table_dirty = false;
-    return 0;
-}
 // partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
 // stiffness and no damping (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
@@ -928,14 +821,6 @@ static int settle_owed(mpm_engine* e, Ctl* fresh) {
     e->force_check = true;
     return 0;
 }
-
-#define READY_NO_SETTLE(e)                              \
-    REQUIRE(e, "null handle");                          \
-    REQUIRE((e)->finalized, "call mpm_finalize first"); \
-    if (int rc__ = use(e)) return rc__
-#define READY(e)         \
-    READY_NO_SETTLE(e);  \
-    if (int rc2__ = settle(e)) return rc2__
 
 int mpm_halo_zone_blocks(mpm_handle_t e, int bx_lo, int bx_hi, uint32_t* count_out) try {
     READY(e);
@@ -1284,77 +1169,21 @@ int mpm_substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* co
     return substep_end_halo(e, dt, bc, n, recv_bufs, cap, true, false);
 } MPM_CATCH_ALL
 
+// ---- the native chain, its direct halo and the team transport's set-up (mpm_chain_host.h) -----------------------------
 int mpm_chain_unique_id(char id_out[128]) try {
     REQUIRE(id_out, "null argument");
-    const rccl_rt::Api* a = rccl_rt::api();
-    if (!a) return fail(MPM_ERR_HIP, "RCCL (librccl.so) is not available in this process");
-    rccl_rt::UniqueId id;
-    RCCL_TRY(a->get_unique_id(&id));
-    std::memcpy(id_out, id.internal, rccl_rt::kIdBytes);
-    return 0;
+    return chain_unique_id(id_out);
 } MPM_CATCH_ALL
-
-// the neighbours' regions of the direct halo, unmapped (a ring of two maps one region for both sides)
-static void chain_unmap_peers(mpm_engine::Chain& c) {
-    for (int k = 0; k < 2; ++k)
-        if (c.peer_mapped[k] && c.peer_base[k] && !(k == 1 && c.peer_base[1] == c.peer_base[0])) (void)hipIpcCloseMemHandle(c.peer_base[k]);
-    c.peer_mapped[0] = c.peer_mapped[1] = false;
-    c.peer_base[0] = c.peer_base[1] = nullptr;
-}
 
 int mpm_chain_destroy(mpm_handle_t e) try {
     REQUIRE(e, "null handle");
-    mpm_engine::Chain& c = e->chain;
-    if (int rc = use(e)) return rc;
-    (void)hipStreamSynchronize(e->stream);
-    if (c.comm) {   // (RCCL is only looked up by engines that use it)
-        const rccl_rt::Api* a = rccl_rt::api();
-        if (a) (void)a->comm_destroy(c.comm);
-    }
-    for (void* q : {c.send_l, c.send_r, c.recv_l, c.recv_r, c.mig_send_l, c.mig_send_r, c.mig_recv_l, c.mig_recv_r,
-                    (void*)c.mig_quiet_all})
-        if (q) (void)hipFree(q);
-    chain_unmap_peers(c);
-    if (c.direct_base) (void)hipFree(c.direct_base);
-    if (c.direct_cnt) (void)hipFree(c.direct_cnt);
-    c = mpm_engine::Chain();
-    {
-        mpm_engine::Team& t = e->team;
-        for (int r = 0; r < TEAM_MAX; ++r)
-            if (t.mapped[r] && t.peer[r]) (void)hipIpcCloseMemHandle(t.peer[r]);
-        if (t.base) (void)hipFree(t.base);
-        if (t.ts) (void)hipFree(t.ts);
-        t = mpm_engine::Team();
-    }
-    return 0;
+    return chain_destroy(e);
 } MPM_CATCH_ALL
 
 int mpm_chain_enable_migration(mpm_handle_t e, int every, size_t capacity_particles) try {
     READY(e);
     if (int rc = extensions_refused(e, "mpm_chain_enable_migration")) return rc;
-    mpm_engine::Chain& c = e->chain;
-    REQUIRE(c.comm, "mpm_chain_init first");
-    REQUIRE(e->dp.dist.on, "mpm_dist_init first");
-    REQUIRE(c.pitch == 0 && c.rank == e->dp.dist.rank && c.world == e->dp.dist.world,
-            "the chain of a partitioned domain has pitch 0 and the rank / world given to mpm_dist_init");
-    REQUIRE(every >= 0 && capacity_particles > 0 && capacity_particles < (1u << 28), "bad migration parameters");
-    REQUIRE(every > 0 || rccl_rt::api()->all_reduce, "adaptive migration (every = 0) needs ncclAllReduce");
-    for (void** q : {&c.mig_send_l, &c.mig_send_r, &c.mig_recv_l, &c.mig_recv_r, (void**)&c.mig_quiet_all}) {
-        if (*q) (void)hipFree(*q);
-        *q = nullptr;
-    }
-    HIP_TRY(hipMalloc((void**)&c.mig_quiet_all, 16));
-    c.mig_budget = 0.f;    // (the first substep starts with a migration: it yields the first estimate)
-    c.mig_elapsed = 0.f;
-    c.mig_every = every;
-    c.mig_cap = capacity_particles;
-    c.mig_bytes = mpm_dist_migration_buffer_bytes(capacity_particles);
-    for (void** q : {&c.mig_send_l, &c.mig_send_r, &c.mig_recv_l, &c.mig_recv_r}) {
-        HIP_TRY(hipMalloc(q, c.mig_bytes));
-        HIP_TRY(hipMemsetAsync(*q, 0, c.mig_bytes, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return 0;
+    return chain_enable_migration(e, every, capacity_particles);
 } MPM_CATCH_ALL
 
 int mpm_chain_init(mpm_handle_t e, const char id[128], int rank, int world, int cut_lo_block, int cut_hi_block,
@@ -1363,116 +1192,18 @@ int mpm_chain_init(mpm_handle_t e, const char id[128], int rank, int world, int 
     if (int rc = extensions_refused(e, "mpm_chain_init")) return rc;
     REQUIRE(world >= 1 && rank >= 0 && rank < world, "bad rank / world");
     REQUIRE(zone_blocks >= 1 && capacity_blocks > 0 && capacity_blocks < (1u << 24), "bad halo geometry");
-    // (id == NULL: the geometry only, no RCCL communicator -- for the direct transport, mpm_chain_direct_prepare)
-    const rccl_rt::Api* a = id ? rccl_rt::api() : nullptr;
-    if (id && !a) return fail(MPM_ERR_HIP, "RCCL (librccl.so) is not available in this process");
-    if (int rc = mpm_chain_destroy(e)) return rc;
-    mpm_engine::Chain& c = e->chain;
-    c.rank = rank; c.world = world; c.pitch = pitch_blocks; c.cap = capacity_blocks;
-    c.left = rank > 0 ? rank - 1 : (periodic ? world - 1 : -1);
-    c.right = rank < world - 1 ? rank + 1 : (periodic ? 0 : -1);
-    c.zone_lo[0] = cut_lo_block - zone_blocks; c.zone_hi[0] = cut_lo_block + zone_blocks - 1;
-    c.zone_lo[1] = cut_hi_block - zone_blocks; c.zone_hi[1] = cut_hi_block + zone_blocks - 1;
-    c.bytes = mpm_halo_buffer_bytes(capacity_blocks);
-    for (void** q : {&c.send_l, &c.send_r, &c.recv_l, &c.recv_r}) {
-        HIP_TRY(hipMalloc(q, c.bytes));
-        HIP_TRY(hipMemsetAsync(*q, 0, c.bytes, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    if (id) {
-        rccl_rt::UniqueId uid;
-        std::memcpy(uid.internal, id, rccl_rt::kIdBytes);
-        RCCL_TRY(a->comm_init_rank(&c.comm, world, uid, rank));
-    }
-    return 0;
+    return chain_init(e, id, rank, world, cut_lo_block, cut_hi_block, pitch_blocks, zone_blocks, capacity_blocks, periodic);
 } MPM_CATCH_ALL
-
-// ---- direct halo: peer-to-peer stores + sequence flags -------------------------------------------
-static size_t direct_slot_bytes(const mpm_engine::Chain& c) { return (c.bytes + 255) & ~(size_t)255; }
-static size_t direct_total_bytes(const mpm_engine::Chain& c) { return 4 * direct_slot_bytes(c) + 256; }
-// [side 0 = from the left neighbour, 1 = from the right][parity] inside an allocation laid out as above
-static void* direct_buffer(const mpm_engine::Chain& c, void* base, int side, int parity) {
-    return (char*)base + (size_t)(side * 2 + parity) * direct_slot_bytes(c);
-}
-static uint32_t* direct_flag(const mpm_engine::Chain& c, void* base, int side) {
-    return reinterpret_cast<uint32_t*>((char*)base + 4 * direct_slot_bytes(c)) + side * 16;   // (64 bytes apart)
-}
 
 int mpm_chain_direct_prepare(mpm_handle_t e, char handle_out[64]) try {
     READY(e);
     if (int rc = extensions_refused(e, "mpm_chain_direct_prepare")) return rc;
-    mpm_engine::Chain& c = e->chain;
-    REQUIRE(handle_out, "null argument");
-    REQUIRE(c.cap > 0, "mpm_chain_init first (with a NULL id for the geometry alone)");
-    static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size");
-    if (!c.direct_base) {
-        const size_t bytes = direct_total_bytes(c);
-        // FINE-GRAINED, or not at all: the protocol's consumer (k_grid<2>) reads the count, the ids and the sums with plain
-        // loads and relies on a peer's stores not being shadowed by stale lines of this device's L2.  A coarse-grained
-        // region would add stale halo sums without any error flag, so a refused allocation is an error of
-        // this call -- the caller stays on RCCL (the connect protocol allows that: mpm_chain_direct_connect(NULL, NULL)).
-        // MPM_DIRECT_COARSE_OK=1 accepts plain device memory for rehearsals on ONE device, where both ends share the L2.
-        const hipError_t fg = hipExtMallocWithFlags(&c.direct_base, bytes, hipDeviceMallocFinegrained);
-        if (fg != hipSuccess) {
-            (void)hipGetLastError();
-            c.direct_base = nullptr;
-            if (!getenv("MPM_DIRECT_COARSE_OK"))
-                return fail(MPM_ERR_HIP, std::string("mpm_chain_direct_prepare: fine-grained device memory is not available (") +
-                                             hipGetErrorString(fg) + "): the direct halo exchange needs it; stay on the RCCL transport");
-            HIP_TRY(hipMalloc(&c.direct_base, bytes));
-        }
-        HIP_TRY(hipMemsetAsync(c.direct_base, 0, bytes, e->stream));
-        if (!c.direct_cnt) {
-            HIP_TRY(hipMalloc((void**)&c.direct_cnt, 64));
-            HIP_TRY(hipMemsetAsync(c.direct_cnt, 0, 64, e->stream));
-        }
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    hipIpcMemHandle_t h;
-    HIP_TRY(hipIpcGetMemHandle(&h, c.direct_base));
-    std::memcpy(handle_out, &h, 64);
-    if (const char* t = getenv("MPM_HALO_TIMEOUT_S")) c.direct_timeout_s = std::max(.001f, (float)atof(t));
-    c.direct_mute = getenv("MPM_HALO_DEBUG_MUTE") != nullptr;   // (tests: this rank never signals)
-    return 0;
+    return chain_direct_prepare(e, handle_out);
 } MPM_CATCH_ALL
 
 int mpm_chain_direct_connect(mpm_handle_t e, const char left_handle[64], const char right_handle[64]) try {
     READY(e);
-    mpm_engine::Chain& c = e->chain;
-    REQUIRE(c.direct_base, "mpm_chain_direct_prepare first");
-    const char* hs[2] = {left_handle, right_handle};
-    const int nbr[2] = {c.left, c.right};
-    chain_unmap_peers(c);
-    const bool foreign = (c.left >= 0 && c.left != c.rank) || (c.right >= 0 && c.right != c.rank);
-    if (foreign && !left_handle && !right_handle) {   // switched off again: the chain is RCCL's (or nobody's) once more
-        c.direct = false;
-        return 0;
-    }
-    for (int k = 0; k < 2; ++k) {
-        if (nbr[k] < 0) continue;
-        if (nbr[k] == c.rank) {   // a ring of one: the neighbour is this rank, no mapping
-            c.peer_base[k] = c.direct_base;
-            continue;
-        }
-        REQUIRE(hs[k], "missing IPC handle of a neighbour");
-        if (k == 1 && c.left == c.right && c.peer_base[0]) {   // a ring of two: both neighbours are the same rank
-            c.peer_base[1] = c.peer_base[0];
-            c.peer_mapped[1] = c.peer_mapped[0];
-            continue;
-        }
-        hipIpcMemHandle_t h;
-        std::memcpy(&h, hs[k], 64);
-        const hipError_t err = hipIpcOpenMemHandle(&c.peer_base[k], h, hipIpcMemLazyEnablePeerAccess);
-        if (err != hipSuccess) {
-            (void)hipGetLastError();   // (not sticky: the engine stays usable, with RCCL or without neighbours)
-            c.peer_base[k] = nullptr;
-            return fail(MPM_ERR_HIP, std::string("hipIpcOpenMemHandle: ") + hipGetErrorString(err) +
-                                         " (the neighbour's buffers cannot be mapped: another node, or a handle of this very process)");
-        }
-        c.peer_mapped[k] = true;
-    }
-    c.direct = true;
-    return 0;
+    return chain_direct_connect(e, left_handle, right_handle);
 } MPM_CATCH_ALL
 
 // Neighbours that live in THIS process (an in-process world: several engines of one partition on one stream, for tests and
@@ -1489,54 +1220,16 @@ int mpm_chain_direct_base(mpm_handle_t e, void** base_out) try {
 
 int mpm_chain_direct_connect_local(mpm_handle_t e, void* left_base, void* right_base) try {
     READY(e);
-    mpm_engine::Chain& c = e->chain;
-    REQUIRE(c.direct_base, "mpm_chain_direct_prepare first");
-    REQUIRE((c.left < 0 || left_base) && (c.right < 0 || right_base), "missing region of a neighbour");
-    chain_unmap_peers(c);
-    c.peer_base[0] = c.left >= 0 ? left_base : nullptr;
-    c.peer_base[1] = c.right >= 0 ? right_base : nullptr;
-    c.direct = true;
-    return 0;
+    return chain_direct_connect_local(e, left_base, right_base);
 } MPM_CATCH_ALL
 
-// ---- TEAM transport of the distributed contact solve (mpm_team.h) --------------------------------------------------------
 int mpm_team_prepare(mpm_handle_t e, size_t zone_capacity_blocks, char handle_out[64], void** base_out) try {
     READY(e);
     if (int rc = extensions_refused(e, "mpm_team_prepare")) return rc;
     REQUIRE(e->dp.dist.on, "mpm_dist_init first");
     REQUIRE(e->dp.dist.world <= TEAM_MAX, "the team transport serves the ranks of one node (at most 8)");
     REQUIRE(zone_capacity_blocks > 0 && zone_capacity_blocks < (1u << 20), "bad zone capacity");
-    mpm_engine::Team& t = e->team;
-    REQUIRE(!t.on, "mpm_team_prepare after mpm_team_connect");
-    if (!t.base) {
-        t.rank = e->dp.dist.rank;
-        t.world = e->dp.dist.world;
-        t.zone_cap = zone_capacity_blocks;
-        t.zone_bytes = team_zone_slot_bytes(zone_capacity_blocks);
-        const size_t bytes = team_region_bytes(t.zone_bytes);
-        // fine-grained or not at all, as for the direct halo (mpm_chain_direct_prepare)
-        const hipError_t fg = hipExtMallocWithFlags(&t.base, bytes, hipDeviceMallocFinegrained);
-        if (fg != hipSuccess) {
-            (void)hipGetLastError();
-            t.base = nullptr;
-            if (!getenv("MPM_DIRECT_COARSE_OK"))
-                return fail(MPM_ERR_HIP, std::string("mpm_team_prepare: fine-grained device memory is not available (") + hipGetErrorString(fg) +
-                                             "): the team transport needs it; the solve stays on the host-driven transports");
-            HIP_TRY(hipMalloc(&t.base, bytes));
-        }
-        HIP_TRY(hipMemsetAsync(t.base, 0, bytes, e->stream));
-        HIP_TRY(hipMalloc((void**)&t.ts, sizeof(TeamState)));
-        HIP_TRY(hipMemsetAsync(t.ts, 0, sizeof(TeamState), e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        if (const char* s2 = getenv("MPM_HALO_TIMEOUT_S")) t.timeout_s = std::max(.001f, (float)atof(s2));
-    }
-    if (handle_out) {
-        hipIpcMemHandle_t h;
-        HIP_TRY(hipIpcGetMemHandle(&h, t.base));
-        std::memcpy(handle_out, &h, 64);
-    }
-    if (base_out) *base_out = t.base;
-    return 0;
+    return team_prepare(e, zone_capacity_blocks, handle_out, base_out);
 } MPM_CATCH_ALL
 
 // handles: world x 64 bytes (the IPC handles of all ranks, own slot ignored) or NULL; local_bases: world pointers or NULL --
@@ -1544,204 +1237,13 @@ int mpm_team_prepare(mpm_handle_t e, size_t zone_capacity_blocks, char handle_ou
 int mpm_team_connect(mpm_handle_t e, const char* handles, void* const* local_bases) try {
     READY(e);
     if (int rc = extensions_refused(e, "mpm_team_connect")) return rc;
-    mpm_engine::Team& t = e->team;
-    REQUIRE(t.base, "mpm_team_prepare first");
-    for (int r = 0; r < t.world; ++r) {
-        if (r == t.rank) {
-            t.peer[r] = t.base;
-            continue;
-        }
-        if (t.mapped[r] && t.peer[r]) (void)hipIpcCloseMemHandle(t.peer[r]);
-        t.mapped[r] = false;
-        t.peer[r] = nullptr;
-        if (local_bases && local_bases[r]) {
-            t.peer[r] = local_bases[r];
-            continue;
-        }
-        REQUIRE(handles, "missing IPC handle of a rank");
-        hipIpcMemHandle_t h;
-        std::memcpy(&h, handles + (size_t)r * 64, 64);
-        const hipError_t err = hipIpcOpenMemHandle(&t.peer[r], h, hipIpcMemLazyEnablePeerAccess);
-        if (err != hipSuccess) {
-            (void)hipGetLastError();
-            t.peer[r] = nullptr;
-            return fail(MPM_ERR_HIP, std::string("mpm_team_connect: hipIpcOpenMemHandle: ") + hipGetErrorString(err) +
-                                         " (a rank's region cannot be mapped: another node, or a handle of this very process)");
-        }
-        t.mapped[r] = true;
-    }
-    t.on = true;
-    return 0;
+    return team_connect(e, handles, local_bases);
 } MPM_CATCH_ALL
-
-// The two halves of a chain substep over the DIRECT transport (see mpm_chain_substeps): begin = re-sort checks, FEM,
-// ParticleToGrid, raw sums packed into the neighbours' slots of this substep's parity, signal; end = wait, add + grid
-// update (+ GridToParticle).  Between them a coupled substep runs nothing that touches the grid.
-static int chain_zones(const mpm_engine::Chain& c, int* lo, int* hi, int* sh) {
-    int nz = 0;
-    if (c.left >= 0) { lo[nz] = c.zone_lo[0]; hi[nz] = c.zone_hi[0]; sh[nz] = +c.pitch; ++nz; }
-    if (c.right >= 0) { lo[nz] = c.zone_lo[1]; hi[nz] = c.zone_hi[1]; sh[nz] = -c.pitch; ++nz; }
-    return nz;
-}
-// ... and a (left, right) pair of buffers in the same order
-static void chain_sides(const mpm_engine::Chain& c, void* left, void* right, void** out) {
-    int k = 0;
-    if (c.left >= 0) out[k++] = left;
-    if (c.right >= 0) out[k++] = right;
-}
-// One RCCL group with both neighbours: out_l / out_r bytes from send_l / send_r, in_l / in_r bytes into recv_l / recv_r (a
-// size of 0 leaves the call out).  What goes to the left arrives "from the right" over there: when both neighbours are the
-// same rank (a ring of one or two) the k-th send pairs with the k-th receive, so the receives are posted right-then-left
-// against sends left-then-right.
-static int chain_exchange(mpm_engine* e, const rccl_rt::Api* a, void* send_l, size_t out_l, void* send_r, size_t out_r, void* recv_l,
-                          size_t in_l, void* recv_r, size_t in_r) {
-    const mpm_engine::Chain& c = e->chain;
-    RCCL_TRY(a->group_start());
-    int rc_g = 0;
-    if (!rc_g && c.left >= 0 && out_l) rc_g = a->send(send_l, out_l, 0 /* ncclChar */, c.left, c.comm, e->stream);
-    if (!rc_g && c.right >= 0 && out_r) rc_g = a->send(send_r, out_r, 0, c.right, c.comm, e->stream);
-    if (!rc_g && c.right >= 0 && in_r) rc_g = a->recv(recv_r, in_r, 0, c.right, c.comm, e->stream);
-    if (!rc_g && c.left >= 0 && in_l) rc_g = a->recv(recv_l, in_l, 0, c.left, c.comm, e->stream);
-    const int rc_e = a->group_end();   // (always closes the group, also after a failed call)
-    RCCL_TRY(rc_g);
-    RCCL_TRY(rc_e);
-    return 0;
-}
-// lean: another substep of the same batch follows (see substep_begin_halo)
-static int chain_direct_begin(mpm_engine* e, float dt, bool lean) {
-    mpm_engine::Chain& c = e->chain;
-    REQUIRE(c.direct, "mpm_chain_direct_connect first");
-    int lo[2], hi[2], sh[2];
-    const int nz = chain_zones(c, lo, hi, sh);
-    c.mig_elapsed += dt;
-    c.steps += 1;
-    const int parity = (int)(c.steps & 1u);
-    const uint32_t seq = (uint32_t)c.steps;
-    void* dsb[2] = {nullptr, nullptr};
-    uint32_t *sig[2] = {nullptr, nullptr}, *cnt[2] = {nullptr, nullptr}, *hdr[2] = {nullptr, nullptr}, *counters[2] = {nullptr, nullptr};
-    int k = 0;
-    if (c.left >= 0) {   // my left zone goes to the left neighbour's "from the right" buffer
-        dsb[k] = direct_buffer(c, c.peer_base[0], 1, parity);
-        sig[0] = direct_flag(c, c.peer_base[0], 1);
-        cnt[0] = c.direct_cnt; hdr[0] = static_cast<uint32_t*>(dsb[k]);
-        counters[k] = cnt[0];
-        ++k;
-    }
-    if (c.right >= 0) {
-        dsb[k] = direct_buffer(c, c.peer_base[1], 0, parity);
-        sig[1] = direct_flag(c, c.peer_base[1], 0);
-        cnt[1] = c.direct_cnt + 8; hdr[1] = static_cast<uint32_t*>(dsb[k]);
-        counters[k] = cnt[1];
-        ++k;
-    }
-    if (int rc = substep_begin_halo(e, dt, nz, lo, hi, sh, dsb, c.cap, counters, lean)) return rc;
-    if (!c.direct_mute && nz > 0)
-        hipLaunchKernelGGL(k_halo_signal, dim3(1), dim3(64), 0, e->stream, sig[0], sig[1], seq, (const uint32_t*)cnt[0], hdr[0],
-                           (const uint32_t*)cnt[1], hdr[1], (unsigned)c.cap);
-    return 0;
-}
-static int chain_direct_end(mpm_engine* e, float dt, int bc, bool with_g2p, bool lean) {
-    mpm_engine::Chain& c = e->chain;
-    int lo[2], hi[2], sh[2];
-    const int nz = chain_zones(c, lo, hi, sh);
-    const int parity = (int)(c.steps & 1u);
-    const uint32_t seq = (uint32_t)c.steps;
-    void* drb[2] = {nullptr, nullptr};
-    uint32_t* mine[2] = {nullptr, nullptr};
-    int k = 0;
-    if (c.left >= 0) { drb[k++] = direct_buffer(c, c.direct_base, 0, parity); mine[0] = direct_flag(c, c.direct_base, 0); }
-    if (c.right >= 0) { drb[k++] = direct_buffer(c, c.direct_base, 1, parity); mine[1] = direct_flag(c, c.direct_base, 1); }
-    if (nz > 0)
-        hipLaunchKernelGGL(k_halo_wait, dim3(1), dim3(64), 0, e->stream, (const uint32_t*)mine[0], (const uint32_t*)mine[1], seq,
-                           (unsigned long long)((double)c.direct_timeout_s * 1e8), e->dp.ctl);
-    return substep_end_halo(e, dt, bc, nz, drb, c.cap, with_g2p, lean);
-}
 
 int mpm_chain_substeps(mpm_handle_t e, int n, float dt, int bc) try {
     READY(e);
     if (int rc = extensions_refused(e, "mpm_chain_substeps")) return rc;
-    mpm_engine::Chain& c = e->chain;
-    REQUIRE(c.comm || c.direct, "mpm_chain_init first");
-    const rccl_rt::Api* a = c.comm ? rccl_rt::api() : nullptr;
-    REQUIRE(c.comm || c.mig_cap == 0, "migration needs the RCCL communicator (mpm_chain_init with an id)");
-    // zones / buffers in the order (left, right), leaving out a missing neighbour
-    int lo[2], hi[2], sh[2];
-    const int nz = chain_zones(c, lo, hi, sh);
-    void *sb[2], *rb[2];
-    chain_sides(c, c.send_l, c.send_r, sb);
-    chain_sides(c, c.recv_l, c.recv_r, rb);
-    for (int s = 0; s < n; ++s) {
-        // Migration: every mig_every substeps, or (mig_every = 0, adaptive) when half of the time has passed in which,
-        // by the ranks' common estimate, no particle can have drifted further than the bands allow (Dist::mig_delta).
-        bool due = false;
-        if (c.mig_cap > 0 && nz > 0) {
-            if (c.mig_every > 0) due = c.steps > 0 && c.steps % (uint64_t)c.mig_every == 0;
-            else due = !(c.mig_elapsed + dt <= c.mig_budget);
-        }
-        if (due) {
-            // particles change hands (mpm_dist.h): records to / from both neighbours, same pairing as below.  In two
-            // rounds: the 16-byte headers first (record counts), then exactly the records that exist -- a RCCL
-            // send needs its size when it is enqueued, and the buffers are sized for the worst case (9 MB for 65536
-            // records) while a migration of a cloth at rest moves none.  The host reads the counts in between; a
-            // migration is a synchronisation point anyway (mpm_dist_migrate_apply).
-            if (int rc = mpm_dist_migrate_pack(e, c.mig_send_l, c.mig_send_r, c.mig_cap)) return rc;
-            auto exchange = [&](size_t out_l, size_t out_r, size_t in_l, size_t in_r, size_t offset) -> int {
-                return chain_exchange(e, a, (char*)c.mig_send_l + offset, out_l, (char*)c.mig_send_r + offset, out_r,
-                                      (char*)c.mig_recv_l + offset, in_l, (char*)c.mig_recv_r + offset, in_r);
-            };
-            if (int rc = exchange(16, 16, 16, 16, 0)) return rc;
-            if (c.mig_every == 0) {
-                // the ranks agree on the smallest estimate (one float, ncclMin), read back with the headers
-                RCCL_TRY(a->all_reduce(&e->dp.ctl->mig_quiet, c.mig_quiet_all, 1, 7 /* ncclFloat32 */, 3 /* ncclMin */, c.comm,
-                                       e->stream));
-            }
-            {
-                uint32_t h[4][4] = {};
-                void* bufs[4] = {c.mig_send_l, c.mig_send_r, c.mig_recv_l, c.mig_recv_r};
-                for (int k = 0; k < 4; ++k) HIP_TRY(hipMemcpyAsync(h[k], bufs[k], 16, hipMemcpyDeviceToHost, e->stream));
-                HIP_TRY(hipStreamSynchronize(e->stream));
-                auto bytes = [&](int k, bool there) {
-                    return there ? (size_t)std::min<size_t>(h[k][0], c.mig_cap) * DIST_REC_F4 * 16 : (size_t)0;
-                };
-                // (a ring of one or two ranks pairs the k-th send with the k-th receive: what goes left arrives "from the
-                // right" over there -- the received headers say how much comes from each side)
-                if (int rc = exchange(bytes(0, c.left >= 0), bytes(1, c.right >= 0), bytes(2, c.left >= 0), bytes(3, c.right >= 0), 16))
-                    return rc;
-            }
-            if (int rc = mpm_dist_migrate_apply(e, c.left >= 0 ? c.mig_recv_l : nullptr, c.right >= 0 ? c.mig_recv_r : nullptr,
-                                                c.mig_cap))
-                return rc;
-            if (c.mig_every == 0) {
-                float t = 0.f;
-                D2H(e, &t, c.mig_quiet_all, sizeof(float));   // (the stream is idle: apply has just synchronised it)
-                // (the estimate is ballistic: forces can speed particles up before the next look.  The interval may at
-                // most double from one migration to the next -- 4 substeps after the first --, so a change of the
-                // velocities is seen after at most as long as they have been watched)
-                const float t_est = e->mig_safety * (t >= 0.f ? t : 0.f);   // (NaN -> 0: migrate again next substep)
-                c.mig_budget = std::min(t_est, std::max(4.f * dt, 2.f * c.mig_elapsed));
-                c.mig_elapsed = 0.f;
-                if (int rc = mpm_dist_retune(e, t, dt, nullptr)) return rc;   // (band widths for the migrations to come)
-            }
-        }
-        const bool lean = s + 1 < n;
-        if (c.direct && nz > 0) {
-            // DIRECT: the pack kernel stores into the neighbours' receive buffers of this substep's parity (two in
-            // rotation: a neighbour may still be reading the other one -- it cannot be reading this one: its read of
-            // substep s - 2 precedes its signal of s - 1, which this rank's update of s - 1 has waited for), a one-thread
-            // kernel raises the flags over there, a one-wave kernel waits for this rank's.
-            if (int rc = chain_direct_begin(e, dt, lean)) return rc;
-            if (int rc = chain_direct_end(e, dt, bc, true, lean)) return rc;
-            continue;
-        }
-        c.mig_elapsed += dt;
-        c.steps += 1;
-        if (int rc = substep_begin_halo(e, dt, nz, lo, hi, sh, sb, c.cap, nullptr, lean)) return rc;
-        if (nz > 0)
-            if (int rc = chain_exchange(e, a, c.send_l, c.bytes, c.send_r, c.bytes, c.recv_l, c.bytes, c.recv_r, c.bytes)) return rc;
-        if (int rc = substep_end_halo(e, dt, bc, nz, rb, c.cap, true, lean)) return rc;
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return chain_substeps(e, n, dt, bc);
 } MPM_CATCH_ALL
 
 int mpm_grid_to_particle(mpm_handle_t e, float dt) try {
@@ -2004,278 +1506,14 @@ int mpm_external_body_force_to_host(mpm_handle_t e, float* tau_out, float* f_out
     return 0;
 } MPM_CATCH_ALL
 
-// ---- partitioned domain ----------------------------------------------------------------------
-namespace mpm {
-// after the arrays have moved: vertex slots start at new_nf instead of old_nf
-__global__ __launch_bounds__(256) void k_dist_shift_slots(DP p, int old_nf, int new_nf, int nfa) {
-    const PSet& S = p.set[p.ctl->cur];
-    const int gs = gridDim.x * 256, t0 = blockIdx.x * 256 + threadIdx.x;
-    auto shifted = [&](int s) { return s >= old_nf ? s - old_nf + new_nf : s; };
-    for (int i = t0; i < nfa; i += gs) {
-        float4 f3 = S.fq[3][i];
-        f3.y = __int_as_float(shifted(__float_as_int(f3.y)));
-        f3.z = __int_as_float(shifted(__float_as_int(f3.z)));
-        f3.w = __int_as_float(shifted(__float_as_int(f3.w)));
-        S.fq[3][i] = f3;
-    }
-    for (int g = t0; g < p.NpG; g += gs) p.imap[g] = shifted(p.imap[g]);
-}
-}  // namespace mpm
-
-// Slot space of a partitioned rank.  The rank was finalised with the whole scene (every rank runs the same Finalize, so
-// ghost copies start bit-identical to their owners'); the first partitioned re-sort has compacted what it keeps into
-// slots [0, nfa) and [Nf, Nf + nva).  dist_resize re-allocates every array indexed by particle slot for `new_nf` face and
-// `new_nv` vertex slots, copies the held ranges, shifts the slot references and asks for a re-sort (block tables, work
-// items and wave groups hold slot ranges).  mpm_dist_init calls it once to SHRINK the rank to headroom x its share and
-// to release the tables of the whole scene's topology (corner ids per face, adjacency CSR, Dm^-1 by original id: per
-// slot the rank keeps the same information by original id, DP::fg / vg, and migration records carry it); a migration
-// that would overflow the slot space calls it again to GROW (mpm_dist_migrate_apply: the stream is idle there).  What
-// stays whole-scene sized is the id -> slot map and the slot-order bookkeeping (13 bytes per particle of the scene).
-static size_t dist_slot_capacity(float headroom, size_t held, size_t all) {
-    if (!(headroom > 0.f)) return all;   // (0: keep the whole scene's size)
-    return std::min(all, std::max<size_t>((size_t)((double)held * std::max(1.f, headroom)) + 256, 1024));
-}
-// TWO-PHASE: phase 1 allocates every new array and touches nothing of the engine -- a failure there (device
-// memory exhausted) frees what phase 1 got and returns with the engine exactly as it was, still usable at its old size;
-// phase 2 (copies, swaps, frees) cannot fail for lack of memory.
-static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) {
-    DP& p = e->dp;
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    Ctl c;
-    D2H(e, &c, p.ctl, sizeof(Ctl));
-    // (what a migration appended behind the active particles and the re-sort has not merged yet is kept too)
-    REQUIRE(c.nfa >= 0 && c.nva >= 0 && c.add_f >= 0 && c.add_v >= 0, "dist_resize: corrupt control block");
-    const size_t nfa = (size_t)c.nfa + (size_t)c.add_f, nva = (size_t)c.nva + (size_t)c.add_v;
-    const size_t old_nf = (size_t)p.Nf;
-    REQUIRE(nfa <= old_nf && nva <= (size_t)p.Nv, "dist_resize: the control block counts more particles than the slot space holds");
-    REQUIRE(new_nf >= nfa && new_nv >= nva, "dist_resize: smaller than what the rank holds");
-    REQUIRE(new_nf + new_nv < ((size_t)1 << 30), "dist_resize: too many particle slots");
-    const size_t new_np = new_nf + new_nv;
-    const int cur = c.cur & 1;
-    const unsigned new_q_stride = (unsigned)((new_np + 63) & ~(size_t)63);
-
-    // ---- phase 1: allocate ----------------------------------------------------------------------------------------
-    struct Copy { size_t dst_off, src_off, bytes; };
-    struct Plan {
-        void** owner;             // where the engine keeps the allocation's base pointer
-        void* fresh;              // its replacement
-        std::vector<Copy> keep;   // byte ranges carried over (old base -> fresh)
-    };
-    std::vector<Plan> plans;
-    plans.reserve(64);
-    FreshArrays fresh_arrays(e);   // (freed again unless phase 1 gets all of them)
-    int rc = 0;
-    auto plan = [&](auto*& ptr, size_t n_new, std::vector<Copy> keep_elems) -> int {
-        using T = std::remove_pointer_t<std::remove_reference_t<decltype(ptr)>>;
-        T* fresh = nullptr;
-        if (int r = fresh_arrays.alloc(&fresh, n_new, true)) return r;
-        Plan pl;
-        pl.owner = (void**)(&ptr);
-        pl.fresh = (void*)fresh;
-        for (Copy k : keep_elems)
-            if (k.bytes) pl.keep.push_back(Copy{k.dst_off * sizeof(T), k.src_off * sizeof(T), k.bytes * sizeof(T)});
-        plans.push_back(std::move(pl));
-        return 0;
-    };
-    float4* q_base[2] = {p.set[0].q[0], p.set[1].q[0]};   // (the four planes of a set are one allocation)
-    float* f_base = p.f[0];
-    for (int s = 0; s < 2 && !rc; ++s) {
-        PSet& S = p.set[s];
-        const bool live = s == cur;
-        std::vector<Copy> planes;
-        if (live)
-            for (int d = 0; d < 4; ++d) {
-                planes.push_back(Copy{(size_t)d * new_q_stride, (size_t)d * p.q_stride, nfa});
-                planes.push_back(Copy{(size_t)d * new_q_stride + new_nf, (size_t)d * p.q_stride + old_nf, nva});
-            }
-        rc = plan(q_base[s], 4 * (size_t)new_q_stride, planes);
-        if (!rc) rc = plan(S.pid, new_np, live ? std::vector<Copy>{{0, 0, nfa}, {new_nf, old_nf, nva}} : std::vector<Copy>{});
-        const std::vector<Copy> kf = live ? std::vector<Copy>{{0, 0, nfa}} : std::vector<Copy>{};
-        const std::vector<Copy> kv = live ? std::vector<Copy>{{0, 0, nva}} : std::vector<Copy>{};
-        for (int d = 0; d < 4 && !rc; ++d) rc = plan(S.fq[d], new_nf, kf);
-        if (!rc) rc = plan(S.f8, new_nf, kf);
-        if (!rc) rc = plan(S.c8, new_nf, kf);
-        if (!rc) rc = plan(p.fg[s], new_nf, kf);
-        for (int d = 0; d < 2 && !rc; ++d) rc = plan(p.vg[s][d], new_nv, kv);
-    }
-    // per-substep outputs and re-sort scratch: nothing to keep
-    if (!rc) rc = plan(p.ta, new_nf, {});
-    if (!rc) rc = plan(p.G3, 3 * new_nf, {});
-    // (the vertices' rows of force triples: zero-filled; the re-sort that follows writes the zeros / marks of every held
-    // vertex again and k_fem the rest before anything reads them)
-    if (!rc) rc = plan(p.VF, 3 * vf_entry((unsigned)new_nv + VF_CHUNK, 0), {});
-    if (!rc) rc = plan(f_base, 3 * (size_t)new_q_stride, {});
-    if (!rc) rc = plan(p.pkey, new_np, {});
-    if (!rc) rc = plan(p.prank, new_np, {});
-    if (!rc) rc = plan(p.src_of, new_np, {});
-    if (!rc) rc = plan(p.dst_of, new_np, {});
-    if (!rc) rc = plan(p.home_groups, new_np / 64 + p.capH + 2, {});
-    if (rc) {
-        const std::string why = g_last_error;
-        (void)hipStreamSynchronize(e->stream);
-        return fail(rc, "dist_resize: " + why + " -- the rank keeps its slot space of " + std::to_string(p.Nf) + " + " +
-                            std::to_string(p.Nv) + " slots and stays usable");
-    }
-
-    // ---- phase 2: copy, swap, free (no allocation from here on) ------------------------------------------------------
-    fresh_arrays.commit();
-    for (Plan& pl : plans)
-        for (const Copy& k : pl.keep)
-            HIP_TRY(hipMemcpyAsync((char*)pl.fresh + k.dst_off, (const char*)*pl.owner + k.src_off, k.bytes,
-                                   hipMemcpyDeviceToDevice, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    for (Plan& pl : plans) {
-        void* old = *pl.owner;
-        e->dfree(old);
-        *pl.owner = pl.fresh;
-    }
-    for (int s = 0; s < 2; ++s)
-        for (int d = 0; d < 4; ++d) p.set[s].q[d] = q_base[s] + (size_t)d * new_q_stride;
-    for (int d = 0; d < 3; ++d) p.f[d] = f_base + (size_t)d * new_q_stride;
-    if (first) {
-        // the whole scene's topology tables
-        for (int d = 0; d < 3; ++d) {
-            int* t = const_cast<int*>(p.idx_orig[d]);
-            e->dfree(t);
-            p.idx_orig[d] = nullptr;
-        }
-        float4* dm = const_cast<float4*>(p.dm_orig);
-        e->dfree(dm);
-        p.dm_orig = nullptr;
-        if (e->max_valence <= 8) {
-            int* a = const_cast<int*>(p.adj_off);
-            int* b = const_cast<int*>(p.adj_fc);
-            e->dfree(a); e->dfree(b);
-            p.adj_off = nullptr; p.adj_fc = nullptr;
-        }
-        // (a mesh with a vertex of more than eight faces keeps the scene's adjacency -- 4 bytes per vertex and 12 per face
-        // on every rank: such a vertex's record holds a mark instead of face ids, and its force walks the adjacency by
-        // original id through the id -> slot map, wherever the vertex migrates: vertex_force_csr)
-    }
-    p.Np = (int)new_np; p.Nf = (int)new_nf; p.Nv = (int)new_nv;
-    p.q_stride = new_q_stride;
-    p.f_stride = new_q_stride;
-    hipLaunchKernelGGL(k_dist_shift_slots, dim3(1024), dim3(256), 0, e->stream, p, (int)old_nf, (int)new_nf, (int)nfa);
-    // block tables, work items and wave groups hold slot ranges: rebuild them on the new slot space
-    const int one = 1;
-    H2D(e, &p.ctl->need_rebuild, &one, sizeof(int));
-    e->dist_resizes += 1;
-    if (!first) return 0;   // (a migration follows, and the re-sort that merges what it brings)
-    launch_rebuild(e, e->dp);
-    D2H(e, &c, p.ctl, sizeof(Ctl));
-    return recover_slab_overflow(e, c);
-}
-
+// ---- partitioned domain (mpm_dist_host.h) -----------------------------------------------------------------------------------
 int mpm_dist_init(mpm_handle_t e, const mpm_dist_config_t* cfg) try {
     READY(e);
     if (int rc = extensions_refused(e, "mpm_dist_init")) return rc;
     REQUIRE(cfg, "null configuration");
     REQUIRE(!e->dp.dist.on, "mpm_dist_init called twice");
     REQUIRE(e->api_identity, "mpm_dist_init must precede RebuildMapping(sort = true)");
-    const int nb = e->dp.nb;
-    REQUIRE(cfg->world >= 1 && cfg->rank >= 0 && cfg->rank < cfg->world, "bad rank / world");
-    REQUIRE(cfg->own_lo_block >= 0 && cfg->own_lo_block < cfg->own_hi_block && cfg->own_hi_block <= nb,
-            "bad slab: need 0 <= own_lo_block < own_hi_block <= blocks per axis");
-    const bool auto_bands = cfg->ghost_cells == 0 && cfg->ghost_margin_cells == 0;
-    REQUIRE(cfg->zone_blocks >= 1 && (auto_bands || (cfg->ghost_cells >= 1 && cfg->ghost_margin_cells >= 1)),
-            "zone_blocks must be positive; ghost_cells and ghost_margin_cells both positive, or both 0 (bands from the mesh)");
-    // a ghost vertex may sit ghost_cells + ghost_margin_cells beyond the cut and its stencil reaches 2 nodes further
-    REQUIRE(auto_bands || cfg->zone_blocks * 4 >= cfg->ghost_cells + cfg->ghost_margin_cells + 2,
-            "zone too shallow for the ghost band: need 4 * zone_blocks >= ghost_cells + ghost_margin_cells + 2");
-    // Reach of a face: how far a corner vertex can be from the face particle (the centroid), in cells -- 2/3 of a
-    // median, bounded by 0.75 x the longest edge of the mesh as it was handed over (a cloth stretches by per cent).
-    float longest_edge = 0.f;
-    for (size_t f = 0; f < e->nf; ++f)
-        for (int k = 0; k < 3; ++k) {
-            const float* A = &e->h_pos[(size_t)e->h_idx[f * 3 + k] * 3];
-            const float* B = &e->h_pos[(size_t)e->h_idx[f * 3 + (k + 1) % 3] * 3];
-            longest_edge = std::max(longest_edge, std::sqrt((A[0] - B[0]) * (A[0] - B[0]) + (A[1] - B[1]) * (A[1] - B[1]) +
-                                                            (A[2] - B[2]) * (A[2] - B[2])));
-        }
-    longest_edge *= e->dp.dxinv;
-    const float reach = .75f * longest_edge;
-    // Drift budget.  Between two migrations nothing joins or leaves a rank, so what a rank holds must cover what its
-    // owned particles need even after every particle has drifted `delta` cells along x:
-    //   an owned vertex needs its adjacent faces:  ghost_w >= reach + 2 delta   (both may have moved)
-    //   a face needs its corners:                  vert_w  >= ghost_w + reach   (holds at the migration, nothing leaves after)
-    //   a ghost's stencil stays inside the zone:   vert_w + delta <= 4 zone_blocks - 2
-    //   an owned particle's stencil does:          delta <= 4 zone_blocks - 3
-    // bands from the mesh (ghost_cells = ghost_margin_cells = 0): the widths that make delta largest; given widths:
-    // the delta they allow (0: migrate with every substep).
-    // (with the hysteresis h of ownership and band membership, Dist::hyst: an owned particle may sit h beyond a cut and a
-    // held ghost h beyond its band when the drift starts)
-    //   ghost_w >= reach + 2 delta + h;  vert_w >= ghost_w + reach;  vert_w + h + delta <= 4 zone_blocks - 2;
-    //   h + delta <= 4 zone_blocks - 3
-    const float zone_room = (float)(4 * cfg->zone_blocks - 2);
-    float ghost_w, vert_w, delta, hyst = .125f;
-    if (auto_bands) {
-        // (as much drift as the zone allows, but no more than dist_drift_target: every cell of band is a cell of ghost
-        // particles that FEM and GridToParticle advance with every substep -- with slabs of 16 cells the widest bands
-        // of a two-block zone, 3.8 / 4.3 cells, are half as many ghosts as owned particles)
-        delta = std::min({(zone_room - 2.f * reach - 2.f * hyst) / 3.f, zone_room - 1.f - hyst, e->dist_drift_target});
-        REQUIRE(delta > .05f, "mpm_dist_init: the exchanged zone is too shallow for this mesh (4 zone_blocks - 2 must exceed 1.5 x "
-                              "the longest mesh edge in cells): use more zone_blocks or a finer mesh");
-        ghost_w = reach + 2.f * delta + hyst;
-        vert_w = ghost_w + reach;
-    } else {
-        ghost_w = (float)cfg->ghost_cells;
-        vert_w = (float)(cfg->ghost_cells + cfg->ghost_margin_cells);
-        if (zone_room - vert_w < 2.f * hyst) hyst = 0.f;   // (bands that fill the zone: no room for it)
-        delta = std::max(0.f, std::min({(ghost_w - reach - hyst) * .5f, zone_room - vert_w - hyst, zone_room - 1.f - hyst}));
-    }
-    const bool has_left = cfg->rank > 0, has_right = cfg->rank < cfg->world - 1;
-    // the zones of the two cuts must not overlap (a block is shared by at most two ranks)
-    REQUIRE(!(has_left && has_right) || cfg->own_hi_block - cfg->own_lo_block >= 2 * cfg->zone_blocks,
-            "slab narrower than two zones: use fewer ranks or zone_blocks = 1");
-    REQUIRE(!has_left || (cfg->left_lo_block >= 0 && cfg->left_lo_block < cfg->own_lo_block), "bad left neighbour range");
-    REQUIRE(!has_right || (cfg->right_hi_block > cfg->own_hi_block && cfg->right_hi_block <= nb), "bad right neighbour range");
-    Dist d{};
-    d.on = 1;
-    d.rank = cfg->rank; d.world = cfg->world;
-    d.own_lo = has_left ? cfg->own_lo_block * 4 : 0;
-    d.own_hi = has_right ? cfg->own_hi_block * 4 : nb * 4;
-    d.nbr_lo = has_left ? (cfg->rank > 1 ? cfg->left_lo_block * 4 : 0) : 0;
-    d.nbr_hi = has_right ? (cfg->rank < cfg->world - 2 ? cfg->right_hi_block * 4 : nb * 4) : nb * 4;
-    d.has_left = has_left; d.has_right = has_right;
-    d.ghost_w = ghost_w;
-    d.vert_w = vert_w;
-    d.hyst = hyst;
-    d.zone_cells = cfg->zone_blocks * 4;
-    d.mig_delta = delta;
-    d.mig_reach = vert_w + 2.f * reach + 1.f;
-    e->dist_longest_edge = longest_edge;
-    e->dist_auto = auto_bands;
-    e->dist_reach = reach;
-    e->dist_hyst = hyst;
-    e->dist_delta_max = std::min((zone_room - 2.f * reach - 2.f * hyst) / 3.f, zone_room - 1.f - hyst);
-    if (int rc = e->dalloc(&d.prev, e->np, true)) return rc;
-    if (int rc = e->dalloc(&d.mig_min, 32 * 32, true)) return rc;
-    // per-slot topology by original id, for every particle at first (nobody has been released yet)
-    for (int s = 0; s < 2; ++s) {
-        if (int rc = e->dalloc(&e->dp.fg[s], e->nf, false)) return rc;
-        for (int k = 0; k < 2; ++k)
-            if (int rc = e->dalloc(&e->dp.vg[s][k], e->nv, false)) return rc;
-    }
-    hipLaunchKernelGGL(k_dist_build_topology, dim3(std::min(e->g_np, 2048u)), dim3(256), 0, e->stream, e->dp);
-    e->dp.dist = d;
-    hipLaunchKernelGGL(k_dist_init_roles, dim3(e->g_np), dim3(256), 0, e->stream, e->dp);
-    int one = 1;
-    H2D(e, &e->dp.ctl->need_rebuild, &one, sizeof(int));
-    launch_rebuild(e, e->dp);
-    {
-        Ctl c;
-        D2H(e, &c, e->dp.ctl, sizeof(Ctl));
-        if (int rc = recover_slab_overflow(e, c)) return rc;
-    }
-    // the rank keeps its share: the particle arrays shrink to it, the whole scene's topology tables go
-    {
-        Ctl c;
-        D2H(e, &c, e->dp.ctl, sizeof(Ctl));
-        if (int rc = dist_resize(e, dist_slot_capacity(e->dist_headroom, (size_t)c.nfa, (size_t)e->dp.Nf),
-                                 dist_slot_capacity(e->dist_headroom, (size_t)c.nva, (size_t)e->dp.Nv), true))
-            return rc;
-    }
-    return mpm_sync(e);
+    return dist_init(e, cfg);
 } MPM_CATCH_ALL
 
 int mpm_dist_set_headroom(mpm_handle_t e, float factor) try {
@@ -2290,46 +1528,13 @@ int mpm_dist_get_geometry(mpm_handle_t e, mpm_dist_geometry_t* out) try {
     READY_NO_SETTLE(e);
     REQUIRE(out, "null output");
     REQUIRE(e->dp.dist.on, "mpm_dist_init first");
-    const Dist& d = e->dp.dist;
-    out->face_band_cells = d.ghost_w;
-    out->vertex_band_cells = d.vert_w;
-    out->drift_budget_cells = d.mig_delta;
-    out->longest_edge_cells = e->dist_longest_edge;
-    out->slot_resizes = e->dist_resizes;
-    out->migrations = e->dist_migrations;
-    out->retunes = e->dist_retunes;
-    return 0;
+    return dist_get_geometry(e, out);
 } MPM_CATCH_ALL
 
 int mpm_dist_retune(mpm_handle_t e, float quiet_time_all, float dt, int* changed_out) try {
     REQUIRE(e, "null handle");
     REQUIRE(e->dp.dist.on, "mpm_dist_init first");
-    if (changed_out) *changed_out = 0;
-    if (!e->dist_auto || !e->dist_retune || !(dt > 0.f)) return 0;
-    Dist& d = e->dp.dist;
-    // The ranks' common estimate says the fastest relevant particle uses up the CURRENT budget in quiet_time_all: that
-    // is a speed.  The budget that makes a migration due every dist_target_interval substeps at that speed (half of
-    // the estimate is trusted), in steps of an eighth of a cell so that it does not flutter, within what the zone allows:
-    float want = e->dist_delta_max;   // (an estimate of 0 or NaN: as wide as the zone allows)
-    if (quiet_time_all > 0.f && std::isfinite(quiet_time_all)) {
-        const float speed = d.mig_delta / quiet_time_all;   // cells per second
-        want = speed * dt * e->dist_target_interval / e->mig_safety;
-        want = std::ceil(want * 8.f) * .125f;
-    } else if (quiet_time_all > 0.f) {
-        want = .125f;   // (an infinite estimate -- nothing moves along x --: the narrowest bands)
-    }
-    want = std::min(std::max(want, .125f), e->dist_delta_max);
-    if (!(want > .05f) || std::fabs(want - d.mig_delta) < .06f) return 0;
-    // Every rank computes this from the same numbers at the same migration, so all switch together.  The new widths
-    // take effect at the NEXT migration's classification (particles newly inside a wider band are sent then, ghosts
-    // outside a narrower one are released then); the interval up to it was budgeted with the old widths.
-    d.mig_delta = want;
-    d.ghost_w = e->dist_reach + 2.f * want + e->dist_hyst;
-    d.vert_w = d.ghost_w + e->dist_reach;
-    d.mig_reach = d.vert_w + 2.f * e->dist_reach + 1.f;
-    e->dist_retunes += 1;
-    if (changed_out) *changed_out = 1;
-    return 0;
+    return dist_retune(e, quiet_time_all, dt, changed_out);
 } MPM_CATCH_ALL
 
 int mpm_dist_migration_quiet_time(mpm_handle_t e, float* seconds_out) try {
@@ -2346,66 +1551,8 @@ int mpm_dist_migrate_pack(mpm_handle_t e, void* send_left, void* send_right, siz
     READY(e);
     REQUIRE(e->dp.dist.on, "mpm_dist_init first");
     REQUIRE(send_left && send_right && capacity_particles > 0 && capacity_particles < (1u << 28), "bad migration buffers");
-    HIP_TRY(hipMemsetAsync(send_left, 0, 16, e->stream));
-    HIP_TRY(hipMemsetAsync(send_right, 0, 16, e->stream));
-    hipLaunchKernelGGL(k_dist_classify, dim3(std::min(e->g_np, 2048u)), dim3(256), 0, e->stream, e->dp,
-                       static_cast<float4*>(send_left), static_cast<float4*>(send_right), (unsigned)capacity_particles);
-    // (the time until the next migration is due, as far as this rank can tell: Ctl::mig_quiet)
-    hipLaunchKernelGGL(k_dist_mig_reduce, dim3(1), dim3(64), 0, e->stream, e->dp);
-    e->dist_migrations += 1;
-    return 0;
+    return dist_migrate_pack(e, send_left, send_right, capacity_particles);
 } MPM_CATCH_ALL
-
-// What a migration brings, from the two 16-byte headers of the received buffers ([0] records, [1] how many of them are
-// faces, [2..3] zero), and the slot space it needs.  Host arithmetic on numbers that came out of BUFFERS (another rank
-// wrote them, a transport carried them): nothing is sized from them before they have been checked against the
-// buffers' capacity and against the scene -- a header that fails the checks is an error code, never an allocation.
-struct MigrationPlan {
-    size_t in_f = 0, in_v = 0;       // arriving records: faces, vertices
-    size_t need_f = 0, need_v = 0;   // slots the rank must have before k_dist_apply runs
-    size_t want_f = 0, want_v = 0;   // slot space to re-allocate to (= the current one when it suffices)
-};
-static int plan_migration(const uint32_t* hdr_left, const uint32_t* hdr_right, size_t capacity, size_t scene_f, size_t scene_v,
-                          size_t held_f, size_t held_v, size_t slots_f, size_t slots_v, float headroom, MigrationPlan* out) {
-    REQUIRE(capacity > 0 && capacity < ((size_t)1 << 28), "migration: bad buffer capacity");
-    REQUIRE(scene_f + scene_v < ((size_t)1 << 30), "migration: bad scene size");
-    if (held_f > slots_f || held_v > slots_v || slots_f > scene_f || slots_v > scene_v)
-        return fail(MPM_ERR_INTERNAL, "migration: the rank's own counts are inconsistent (holds " + std::to_string(held_f) + " + " +
-                                          std::to_string(held_v) + " particles in " + std::to_string(slots_f) + " + " +
-                                          std::to_string(slots_v) + " slots of a scene of " + std::to_string(scene_f) + " + " +
-                                          std::to_string(scene_v) + ")");
-    MigrationPlan m;
-    const uint32_t* hdrs[2] = {hdr_left, hdr_right};
-    for (int k = 0; k < 2; ++k) {
-        const uint32_t* h = hdrs[k];
-        if (!h) continue;
-        const char* side = k ? "right" : "left";
-        // (a sender whose buffer overflowed keeps counting: it raises MPM_ERR_CAPACITY on its side, and the records
-        // beyond the capacity were never written -- applying the rest would lose particles silently)
-        if (h[0] > capacity)
-            return fail(MPM_ERR_CAPACITY, std::string("migration: the ") + side + " neighbour packed " + std::to_string(h[0]) +
-                                              " records into buffers of " + std::to_string(capacity) +
-                                              " (mpm_chain_enable_migration / DomainChain: raise capacity_particles)");
-        if (h[1] > h[0] || h[2] != 0 || h[3] != 0)
-            return fail(MPM_ERR_INVALID, std::string("migration: corrupt header from the ") + side + " neighbour (" +
-                                             std::to_string(h[0]) + " records, " + std::to_string(h[1]) + " faces, " +
-                                             std::to_string(h[2]) + ", " + std::to_string(h[3]) + ")");
-        m.in_f += h[1];
-        m.in_v += h[0] - h[1];
-    }
-    // (every arriving record counted as a new particle -- promotions of ghosts the rank already holds need no slot --,
-    // but never more than the scene has: a particle has one slot)
-    m.need_f = std::min(scene_f, held_f + m.in_f);
-    m.need_v = std::min(scene_v, held_v + m.in_v);
-    m.want_f = slots_f;
-    m.want_v = slots_v;
-    if (m.need_f > slots_f || m.need_v > slots_v) {
-        m.want_f = std::max(slots_f, dist_slot_capacity(headroom, m.need_f, scene_f));
-        m.want_v = std::max(slots_v, dist_slot_capacity(headroom, m.need_v, scene_v));
-    }
-    *out = m;
-    return 0;
-}
 
 int mpm_dist_plan_migration(const uint32_t* hdr_left, const uint32_t* hdr_right, size_t capacity_particles, size_t scene_faces,
                             size_t scene_vertices, size_t held_faces, size_t held_vertices, size_t face_slots,
@@ -2423,32 +1570,7 @@ int mpm_dist_migrate_apply(mpm_handle_t e, const void* recv_left, const void* re
     READY(e);
     REQUIRE(e->dp.dist.on, "mpm_dist_init first");
     REQUIRE(capacity_particles > 0 && capacity_particles < (1u << 28), "bad migration buffers");
-    // A migration is a synchronisation point: the host reads how many particles arrive and what the rank holds, and
-    // re-allocates the slot space first if they would not fit (a cloth that slides across a cut, an uneven split).
-    {
-        DP& p = e->dp;
-        uint32_t hdr[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
-        // (pinned landing places are not needed: the copies are followed by a synchronisation at once)
-        Ctl c;
-        HIP_TRY(hipMemcpyAsync(&c, p.ctl, sizeof(Ctl), hipMemcpyDeviceToHost, e->stream));
-        const void* bufs[2] = {recv_left, recv_right};
-        for (int k = 0; k < 2; ++k)
-            if (bufs[k]) HIP_TRY(hipMemcpyAsync(hdr[k], bufs[k], 16, hipMemcpyDeviceToHost, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        REQUIRE(c.nfa >= 0 && c.nva >= 0 && c.add_f >= 0 && c.add_v >= 0, "migration: corrupt control block");
-        MigrationPlan m;
-        if (int rc = plan_migration(recv_left ? hdr[0] : nullptr, recv_right ? hdr[1] : nullptr, capacity_particles, e->nf, e->nv,
-                                    (size_t)c.nfa + (size_t)c.add_f, (size_t)c.nva + (size_t)c.add_v, (size_t)p.Nf, (size_t)p.Nv,
-                                    e->dist_headroom, &m))
-            return rc;
-        if (m.want_f != (size_t)p.Nf || m.want_v != (size_t)p.Nv)
-            if (int rc = dist_resize(e, m.want_f, m.want_v, false)) return rc;
-    }
-    for (const void* b : {recv_left, recv_right})
-        if (b)
-            hipLaunchKernelGGL(k_dist_apply, dim3(256), dim3(256), 0, e->stream, e->dp, static_cast<const float4*>(b),
-                               (unsigned)capacity_particles);
-    return 0;
+    return dist_migrate_apply(e, recv_left, recv_right, capacity_particles);
 } MPM_CATCH_ALL
 
 // Tests of the exception barrier and of the allocation-failure paths.  mpm_debug_throw raises a C++ exception of the given
@@ -2487,51 +1609,21 @@ int mpm_dist_set_transport(mpm_handle_t e, mpm_exchange_fn exchange, mpm_allredu
 int mpm_dist_roles(mpm_handle_t e, uint8_t* out) try {
     READY(e);
     REQUIRE(out, "null output");
-    if (int rc = e->stage(e->np)) return rc;
-    hipLaunchKernelGGL(k_dist_roles, dim3(e->g_np), dim3(256), 0, e->stream, e->dp, (const int*)e->d_pids_api,
-                       (unsigned char*)e->d_stage);
-    HIP_TRY(hipMemcpyAsync(out, e->d_stage, e->np, hipMemcpyDeviceToHost, e->stream));
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    return 0;
+    return dist_roles(e, out);
 } MPM_CATCH_ALL
 
+// ---- analytic colliders of the grid update (mpm_bodies_host.h) ------------------------------------------------------------
 int mpm_set_grid_colliders(mpm_handle_t e, size_t n, const mpm_grid_collider_t* colliders) try {
     static_assert(sizeof(GridCollider) == sizeof(mpm_grid_collider_t), "grid collider layouts differ");
     REQUIRE(e, "null handle");
     REQUIRE(n <= (size_t)MAX_GRID_COLLIDERS, "too many grid colliders (at most 16)");
     REQUIRE(n == 0 || colliders, "null collider array");
-    if (e->finalized) {
-        // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
-        if (int rc = use(e)) return rc;
-        if (int rc = settle(e)) return rc;
-    }
-    GridColliders gc{};
-    for (size_t k = 0; k < n; ++k) {
-        const mpm_grid_collider_t& c = colliders[k];
-        REQUIRE(c.shape == MPM_GC_SPHERE || c.shape == MPM_GC_HALF_SPACE, "unknown grid collider shape");
-        REQUIRE(c.mode >= MPM_GC_FIXED && c.mode <= MPM_GC_SLIP, "unknown grid collider mode");
-        if (c.shape == MPM_GC_SPHERE) REQUIRE(c.radius > 0.f, "sphere radius must be positive");
-        if (c.shape == MPM_GC_HALF_SPACE) {
-            const float l = c.n[0] * c.n[0] + c.n[1] * c.n[1] + c.n[2] * c.n[2];
-            REQUIRE(std::fabs(l - 1.f) < 1e-4f, "half-space normal must be a unit vector");
-        }
-        std::memcpy(&gc.c[k], &c, sizeof(GridCollider));
-        if (c.friction < 0.f) gc.c[k].friction = e->mat.sdf_friction;
-    }
-    gc.n = (int)n;
-    e->grid_colliders = gc;
-    e->grid_colliders_version += 1;
-    return 0;
+    return set_grid_colliders(e, n, colliders);
 } MPM_CATCH_ALL
 
 int mpm_grid_collider_preset(int mpm_bc, float sdf_friction, mpm_grid_collider_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(n_out, "null argument");
-    GridColliders gc{};
-    if (grid_collider_preset(mpm_bc, sdf_friction, &gc)) return fail(MPM_ERR_INVALID, "mpm_bc must be -1, 0, 1, 2 or 3");
-    *n_out = (size_t)gc.n;
-    REQUIRE((size_t)gc.n <= capacity && (gc.n == 0 || out), "output array too small");
-    for (int k = 0; k < gc.n; ++k) std::memcpy(&out[k], &gc.c[k], sizeof(GridCollider));
-    return 0;
+    return grid_collider_preset_out(mpm_bc, sdf_friction, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_finalize_external_contact_forces(mpm_handle_t e, float dt, float* tau_out, float* f_out) try {
@@ -2988,130 +2080,34 @@ int mpm_run_coupled_substeps(mpm_handle_t e, int n, const mpm_coupled_params_t* 
     return 0;
 } MPM_CATCH_ALL
 
-}  // extern "C"
-
-// The root finder of the exact line search behind a C callback, for the known-answer tests
-// (host code only: no device is touched).
-template <class T>
-static int newton_bisect(mpm_rootfind_fn fn, void* user, T x_lo, T x_hi, T guess, T x_tol, T f_tol, int max_evals, int flags,
-                         T* root_out, int* evals_out) {
-    REQUIRE(fn && root_out && evals_out, "null argument");
-    REQUIRE(x_lo < x_hi && x_lo <= guess && guess <= x_hi && x_tol > 0 && f_tol > 0, "bad bracket / tolerances");
-    double f_lo, f_hi, d;
-    fn(user, (double)x_lo, &f_lo, &d);
-    fn(user, (double)x_hi, &f_hi, &d);
-    RootFinder<T> rf;
-    rf.start(x_lo, (T)f_lo, x_hi, (T)f_hi, guess, x_tol, f_tol, max_evals, flags);
-    while (rf.status == 0) {
-        double f, df;
-        fn(user, (double)rf.root, &f, &df);
-        rf.feed((T)f, (T)df);
-    }
-    *root_out = rf.root;
-    *evals_out = rf.evals;
-    return rf.status == 1 ? 0 : 1;
-}
-extern "C" {
+// The root finder of the exact line search behind a C callback, for the known-answer tests (host code only: no device
+// is touched; newton_bisect in mpm_rootfind.h).
 int mpm_newton_bisect_f64(mpm_rootfind_fn fn, void* user, double x_lo, double x_hi, double guess, double x_tol, double f_tol,
                           int max_evals, int flags, double* root_out, int* evals_out) try {
+    REQUIRE(fn && root_out && evals_out, "null argument");
+    REQUIRE(x_lo < x_hi && x_lo <= guess && guess <= x_hi && x_tol > 0 && f_tol > 0, "bad bracket / tolerances");
     return newton_bisect(fn, user, x_lo, x_hi, guess, x_tol, f_tol, max_evals, flags, root_out, evals_out);
 } MPM_CATCH_ALL
 int mpm_newton_bisect_f32(mpm_rootfind_fn fn, void* user, float x_lo, float x_hi, float guess, float x_tol, float f_tol,
                           int max_evals, int flags, float* root_out, int* evals_out) try {
+    REQUIRE(fn && root_out && evals_out, "null argument");
+    REQUIRE(x_lo < x_hi && x_lo <= guess && guess <= x_hi && x_tol > 0 && f_tol > 0, "bad bracket / tolerances");
     return newton_bisect(fn, user, x_lo, x_hi, guess, x_tol, f_tol, max_evals, flags, root_out, evals_out);
 } MPM_CATCH_ALL
-}  // extern "C"
 
-// ---- fixed constraints (mpm_set_pins, mpm_set_body_motions, mpm_pins_inside_collider, mpm_get_pins) --------------------
-static bool finite_n(const float* a, int n) {
-    for (int k = 0; k < n; ++k)
-        if (!std::isfinite(a[k])) return false;
-    return true;
-}
-// R^T R = I and det R = 1, each entry within 1e-4 (float rotations that went through a few products)
-static bool is_rotation(const float* R) {
-    if (!finite_n(R, 9)) return false;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) {
-            double d = 0.0;
-            for (int k = 0; k < 3; ++k) d += (double)R[k * 3 + i] * (double)R[k * 3 + j];
-            if (std::fabs(d - (i == j ? 1.0 : 0.0)) > 1e-4) return false;
-        }
-    const double det = (double)R[0] * ((double)R[4] * R[8] - (double)R[5] * R[7]) -
-                       (double)R[1] * ((double)R[3] * R[8] - (double)R[5] * R[6]) +
-                       (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
-    return std::fabs(det - 1.0) <= 1e-4;
-}
-// pins, grid bodies, force fields, bending stiffness and damping are refused on a partitioned or multi-rank engine (out of scope);
-// what_is: "pins are", "bending stiffness is", ...
-static int single_engine_only(const mpm_engine* e, const char* what_is) {
-    if (e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on)
-        return fail(MPM_ERR_INVALID, std::string(what_is) + " not available on a partitioned or multi-rank engine");
-    return 0;
-}
-
+// ---- fixed constraints (mpm_bodies_host.h) --------------------------------------------------------------------------------
 int mpm_set_pins(mpm_handle_t e, size_t n, const mpm_pin_t* pins) try {
     READY(e);
     if (int rc = single_engine_only(e, "pins are")) return rc;
     REQUIRE(n == 0 || pins, "null pin array");
-    std::vector<uint8_t> seen(e->nv, 0);
-    for (size_t k = 0; k < n; ++k) {
-        REQUIRE(pins[k].vertex < e->nv, "pin vertex out of range");
-        REQUIRE(!seen[pins[k].vertex], "a vertex is pinned twice");
-        seen[pins[k].vertex] = 1;
-        REQUIRE(finite_n(pins[k].p_BQ, 3), "pin p_BQ not finite");
-    }
-    e->pin.set.assign(pins, pins + n);
-    e->pin.table_dirty = true;
-    return 0;
+    return set_pins(e, n, pins);
 } MPM_CATCH_ALL
 
 int mpm_set_body_motions(mpm_handle_t e, size_t n, const mpm_body_motion_t* m) try {
     READY(e);
     if (int rc = single_engine_only(e, "pins are")) return rc;
     REQUIRE(n == 0 || m, "null motion array");
-    std::unordered_set<uint32_t> bodies;
-    for (size_t k = 0; k < n; ++k) {
-        REQUIRE(bodies.insert(m[k].body).second, "a body appears twice in one mpm_set_body_motions");
-        REQUIRE(finite_n(m[k].p_WB, 3) && finite_n(m[k].v, 3) && finite_n(m[k].w, 3), "body motion not finite");
-        REQUIRE(is_rotation(m[k].R_WB), "body motion: R_WB is not a rotation");
-    }
-    mpm_engine::PinState& ps = e->pin;
-    std::vector<uint32_t> slot(n);
-    size_t n_slots = ps.motion_body.size();
-    for (size_t k = 0; k < n; ++k) {
-        const auto it = std::find(ps.motion_body.begin(), ps.motion_body.end(), m[k].body);
-        slot[k] = it != ps.motion_body.end() ? (uint32_t)(it - ps.motion_body.begin()) : (uint32_t)n_slots++;
-    }
-    if (n_slots > ps.cap_mot) {   // grow, keeping the clocks of the motions already set
-        const size_t cap = std::max<size_t>(n_slots, std::max<size_t>(16, ps.cap_mot * 2));
-        BodyMotionDev* bigger = nullptr;
-        if (int rc = e->dalloc(&bigger, cap, true)) return rc;
-        if (ps.d_mot)
-            HIP_TRY(hipMemcpyAsync(bigger, ps.d_mot, ps.motion_body.size() * sizeof(BodyMotionDev), hipMemcpyDeviceToDevice, e->stream));
-        HIP_TRY(hipStreamSynchronize(e->stream));
-        e->dfree(ps.d_mot);
-        ps.d_mot = bigger;
-        ps.cap_mot = cap;
-    }
-    for (size_t k = 0; k < n; ++k)
-        if (slot[k] >= ps.motion_body.size()) ps.motion_body.push_back(m[k].body);
-    std::vector<BodyMotionDev> rec(n);
-    for (size_t k = 0; k < n; ++k) {
-        BodyMotionDev& r = rec[k];
-        r = BodyMotionDev{};
-        for (int i = 0; i < 3; ++i) {
-            r.p[i] = m[k].p_WB[i];
-            r.v[i] = m[k].v[i];
-            r.w[i] = m[k].w[i];
-        }
-        for (int i = 0; i < 9; ++i) r.R[i] = m[k].R_WB[i];
-        r.t = 0.0;
-        HIP_TRY(hipMemcpyAsync(ps.d_mot + slot[k], &rec[k], sizeof(BodyMotionDev), hipMemcpyHostToDevice, e->stream));
-    }
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    ps.table_dirty = true;   // (a pin whose body has just got its first motion is resolved at the next substep)
-    return 0;
+    return set_body_motions(e, n, m);
 } MPM_CATCH_ALL
 
 int mpm_pins_inside_collider(mpm_handle_t e, const mpm_collider_t* shape, uint32_t body, const float p_WB[3],
@@ -3119,33 +2115,7 @@ int mpm_pins_inside_collider(mpm_handle_t e, const mpm_collider_t* shape, uint32
     READY(e);
     if (int rc = single_engine_only(e, "pins are")) return rc;
     REQUIRE(shape && p_WB && R_WB, "null argument");
-    REQUIRE(finite_n(p_WB, 3), "body pose not finite");
-    REQUIRE(is_rotation(R_WB), "R_WB is not a rotation");
-    if (int rc = validate_colliders(1, shape)) return rc;
-    const size_t nv = e->nv;
-    std::vector<float> x(nv * 3), phi(nv), grad(nv * 3);
-    if (nv) {
-        if (int rc = download_original_vertices(e, x.data())) return rc;
-        if (int rc = collider_signed_distance(e, shape, nv, x.data(), phi.data(), grad.data())) return rc;
-    }
-    mpm_engine::PinState& ps = e->pin;
-    std::vector<uint8_t> pinned(nv, 0);
-    for (const mpm_pin_t& q : ps.set) pinned[q.vertex] = 1;
-    std::vector<mpm_pin_t> add;
-    for (size_t v = 0; v < nv; ++v) {
-        if (!(phi[v] <= 0.f) || pinned[v]) continue;
-        mpm_pin_t q{(uint32_t)v, body, {0.f, 0.f, 0.f}};
-        const double d[3] = {(double)x[v * 3] - p_WB[0], (double)x[v * 3 + 1] - p_WB[1], (double)x[v * 3 + 2] - p_WB[2]};
-        for (int i = 0; i < 3; ++i)
-            q.p_BQ[i] = (float)((double)R_WB[i] * d[0] + (double)R_WB[3 + i] * d[1] + (double)R_WB[6 + i] * d[2]);
-        add.push_back(q);
-    }
-    if (n_added) *n_added = 0;
-    REQUIRE(!add.empty(), "no vertex that is not pinned already lies inside the shape");
-    ps.set.insert(ps.set.end(), add.begin(), add.end());
-    ps.table_dirty = true;
-    if (n_added) *n_added = add.size();
-    return 0;
+    return pins_inside_collider(e, shape, body, p_WB, R_WB, n_added);
 } MPM_CATCH_ALL
 
 int mpm_get_pins(mpm_handle_t e, mpm_pin_t* out, size_t capacity, size_t* n_out) try {
@@ -3154,94 +2124,14 @@ int mpm_get_pins(mpm_handle_t e, mpm_pin_t* out, size_t capacity, size_t* n_out)
     return copy_out(e->pin.set, out, capacity, n_out);
 } MPM_CATCH_ALL
 
-// ---- rigid bodies of the grid update (mpm_set_grid_bodies, mpm_get_grid_bodies; k_grid_bodies in mpm_grid_bodies.h) ----
-// no point of the body is farther from its origin than this (k_grid_bodies' test per wave); a little slack for the float
-// evaluation, infinite when the dimensions say nothing (a half-space; NaN or infinite dimensions of kinds 1-3)
-static float grid_body_bound(const mpm_grid_body_t& b, const SdfShape* sh) {
-    double r;
-    if (sh) {
-        r = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            const double m = std::max(std::fabs((double)sh->lo[a]), std::fabs((double)sh->hi[a]));
-            r += m * m;
-        }
-        r = std::sqrt(r);
-    } else {
-        const double d0 = std::fabs((double)b.shape.dims[0]), d1 = std::fabs((double)b.shape.dims[1]),
-                     d2 = std::fabs((double)b.shape.dims[2]);
-        switch (b.shape.kind) {
-            case MPM_COLLIDER_SPHERE: r = d0; break;
-            case MPM_COLLIDER_BOX: r = std::sqrt(d0 * d0 + d1 * d1 + d2 * d2); break;
-            case MPM_COLLIDER_CAPSULE: r = d0 + d1; break;
-            case MPM_COLLIDER_CYLINDER: r = std::sqrt(d0 * d0 + d1 * d1); break;
-            case MPM_COLLIDER_ELLIPSOID: r = std::max(d0, std::max(d1, d2)); break;
-            default: return INFINITY;
-        }
-    }
-    r = r * (1.0 + 1e-4) + 1e-6;
-    return std::isfinite(r) && r < 1e30 ? (float)r : INFINITY;
-}
-
+// ---- rigid bodies of the grid update (mpm_bodies_host.h; k_grid_bodies in mpm_grid_bodies.h) ------------------------------
 int mpm_set_grid_bodies(mpm_handle_t e, size_t n, const mpm_grid_body_t* bodies) try {
     static_assert(sizeof(Collider) == sizeof(mpm_collider_t), "collider layouts differ");
     READY_NO_SETTLE(e);
     if (int rc = single_engine_only(e, "grid bodies are")) return rc;
     REQUIRE(n <= (size_t)MAX_GRID_COLLIDERS, "too many grid bodies (at most 16)");
     REQUIRE(n == 0 || bodies, "null grid body array");
-    for (size_t k = 0; k < n; ++k) {
-        const mpm_grid_body_t& b = bodies[k];
-        if (b.sdf_shape == MPM_GB_NO_MESH) {
-            if (int rc = validate_colliders(1, &b.shape)) return rc;
-        } else {
-            REQUIRE(b.sdf_shape < e->cb.shapes.size(), "grid body: unknown shape id");
-        }
-        REQUIRE(b.mode >= MPM_GC_FIXED && b.mode <= MPM_GC_SLIP, "unknown grid body mode");
-        REQUIRE(std::isfinite(b.friction), "grid body: friction not finite");
-        REQUIRE(finite_n(b.shape.p_WB, 3) && finite_n(b.shape.v, 3) && finite_n(b.shape.w, 3), "grid body: pose or velocity not finite");
-        REQUIRE(is_rotation(b.shape.R_WB), "grid body: R_WB is not a rotation");
-    }
-    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
-    if (int rc = settle(e)) return rc;
-    auto table = std::make_unique<GridBodyTable>();
-    std::memset(table.get(), 0, sizeof(GridBodyTable));
-    int kinds = 0, n_mesh = 0;
-    for (size_t k = 0; k < n; ++k) {
-        const mpm_grid_body_t& b = bodies[k];
-        GridBody& d = table->b[k];
-        std::memcpy(&d.c, &b.shape, sizeof(Collider));
-        d.mode = b.mode;
-        d.friction = b.friction < 0.f ? e->mat.sdf_friction : b.friction;
-        d.mesh = -1;
-        const SdfShape* sh = nullptr;
-        if (b.sdf_shape != MPM_GB_NO_MESH) {
-            sh = &e->cb.shapes[b.sdf_shape];
-            mpm_sdf_collider_t sc{};
-            sc.shape = b.sdf_shape;
-            sc.body = b.shape.body;
-            std::memcpy(sc.p_WB, b.shape.p_WB, sizeof(sc.p_WB));
-            std::memcpy(sc.R_WB, b.shape.R_WB, sizeof(sc.R_WB));
-            std::memcpy(sc.v, b.shape.v, sizeof(sc.v));
-            std::memcpy(sc.w, b.shape.w, sizeof(sc.w));
-            table->mesh[n_mesh] = mesh_collider(*sh, sc);
-            d.mesh = n_mesh++;
-            d.c.kind = 0;   // (kind and dims of a mesh body are not read)
-            kinds |= 2;
-        } else if (b.shape.kind == MPM_COLLIDER_ELLIPSOID) {
-            kinds |= 1;
-        }
-        d.bound = grid_body_bound(b, sh);
-    }
-    table->n = (int)n;
-    if (n) {
-        if (!e->d_grid_bodies)
-            if (int rc = e->dalloc(&e->d_grid_bodies, 1, true)) return rc;
-        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
-        H2D(e, e->d_grid_bodies, table.get(), sizeof(GridBodyTable));
-    }
-    e->grid_bodies.assign(bodies, bodies + n);
-    e->grid_bodies_kinds = kinds;
-    e->grid_colliders_version += 1;
-    return 0;
+    return set_grid_bodies(e, n, bodies);
 } MPM_CATCH_ALL
 
 int mpm_get_grid_bodies(mpm_handle_t e, mpm_grid_body_t* out, size_t capacity, size_t* n_out) try {
@@ -3250,48 +2140,12 @@ int mpm_get_grid_bodies(mpm_handle_t e, mpm_grid_body_t* out, size_t capacity, s
     return copy_out(e->grid_bodies, out, capacity, n_out);
 } MPM_CATCH_ALL
 
-// ---- external force fields (mpm_set_force_fields, mpm_get_force_fields, mpm_force_field_acceleration; mpm_fields.h) ----
-static int validate_force_fields(size_t n, const mpm_force_field_t* f) {
-    static_assert(sizeof(ForceField) == sizeof(mpm_force_field_t), "force field layouts differ");
-    REQUIRE(n <= (size_t)MAX_FORCE_FIELDS, "too many force fields (at most 8)");
-    REQUIRE(n == 0 || f, "null force field array");
-    for (size_t k = 0; k < n; ++k) {
-        const mpm_force_field_t& q = f[k];
-        REQUIRE(q.kind >= MPM_FF_ACCEL && q.kind <= MPM_FF_NORMAL_DRAG, "force field: unknown kind");
-        REQUIRE((q.flags & ~(uint32_t)(MPM_FF_QUADRATIC | MPM_FF_REGION)) == 0, "force field: unknown flags");
-        REQUIRE(std::isfinite(q.gamma) && finite_n(q.u0, 3) && finite_n(q.G, 9) && finite_n(q.x0, 3) && finite_n(q.lo, 3) &&
-                    finite_n(q.hi, 3),
-                "force field: a number is not finite");
-        REQUIRE(q.gamma >= 0.f, "force field: gamma < 0");
-        REQUIRE(q.lo[0] <= q.hi[0] && q.lo[1] <= q.hi[1] && q.lo[2] <= q.hi[2], "force field: lo > hi");
-    }
-    return 0;
-}
-
-extern "C" {
-
+// ---- external force fields (mpm_cloth_host.h; mpm_fields.h) -----------------------------------------------------------------
 int mpm_set_force_fields(mpm_handle_t e, size_t n, const mpm_force_field_t* fields) try {
     READY_NO_SETTLE(e);
     if (int rc = single_engine_only(e, "force fields are")) return rc;
     if (int rc = validate_force_fields(n, fields)) return rc;
-    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
-    if (int rc = settle(e)) return rc;
-    double gamma = 0.0;
-    if (n) {
-        ForceFieldTable table;
-        std::memset(&table, 0, sizeof(table));
-        table.n = (int)n;
-        std::memcpy(table.f, fields, n * sizeof(ForceField));
-        for (size_t k = 0; k < n; ++k)
-            if (fields[k].kind != MPM_FF_ACCEL && !(fields[k].flags & MPM_FF_QUADRATIC)) gamma += (double)fields[k].gamma;
-        if (!e->d_force_fields)
-            if (int rc = e->dalloc(&e->d_force_fields, 1, true)) return rc;
-        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
-        H2D(e, e->d_force_fields, &table, sizeof(table));
-    }
-    e->force_fields.assign(fields, fields + n);
-    e->force_fields_gamma = gamma;
-    return 0;
+    return set_force_fields(e, n, fields);
 } MPM_CATCH_ALL
 
 int mpm_get_force_fields(mpm_handle_t e, mpm_force_field_t* out, size_t capacity, size_t* n_out) try {
@@ -3300,27 +2154,14 @@ int mpm_get_force_fields(mpm_handle_t e, mpm_force_field_t* out, size_t capacity
     return copy_out(e->force_fields, out, capacity, n_out);
 } MPM_CATCH_ALL
 
-// host code only: no device is touched
 int mpm_force_field_acceleration(const mpm_force_field_t* fields, size_t n_fields, size_t n, const float* x, const float* v,
                                  const float* director, float* acc_out) try {
     if (int rc = validate_force_fields(n_fields, fields)) return rc;
     REQUIRE(n == 0 || (x && v && acc_out), "null argument");
-    const ForceField* f = reinterpret_cast<const ForceField*>(fields);
-    const float zero[3] = {0.f, 0.f, 0.f};
-    for (size_t k = 0; k < n; ++k)
-        force_field_acceleration(f, (int)n_fields, x + 3 * k, v + 3 * k, director ? director + 3 * k : zero, director != nullptr,
-                                 acc_out + 3 * k);
-    return 0;
+    return force_field_accelerations(fields, n_fields, n, x, v, director, acc_out);
 } MPM_CATCH_ALL
 
-}  // extern "C"
-
-// ---- bending stiffness (mpm_set_bending, mpm_get_bending, mpm_bending_forces, mpm_bending_max_stable_dt,
-// mpm_bending_matrix; mpm_bending.h) ----
-static void damping_limit(mpm_engine* e);
-extern "C" {
-
-// host code only: no device is touched
+// ---- bending stiffness (mpm_cloth_host.h; mpm_bending.h) ----------------------------------------------------------------------
 int mpm_bending_matrix(const float* pos, size_t n_verts, const int32_t* indices, size_t n_faces, size_t* row_offsets,
                        int32_t* cols, double* vals, size_t capacity, size_t* nnz_out) try {
     REQUIRE((pos || n_verts == 0) && (indices || n_faces == 0), "null input array");
@@ -3328,15 +2169,7 @@ int mpm_bending_matrix(const float* pos, size_t n_verts, const int32_t* indices,
     REQUIRE(n_verts < (size_t)1 << 30 && n_faces < (size_t)1 << 30, "mesh too large");
     for (size_t i = 0; i < n_faces * 3; ++i)
         REQUIRE(indices[i] >= 0 && (size_t)indices[i] < n_verts, "triangle index out of range");
-    BendCsr Q;
-    std::string why;
-    if (!bending_matrix(pos, n_verts, indices, n_faces, 0, Q, why)) return fail(MPM_ERR_INVALID, why);
-    if (row_offsets) std::copy(Q.off.begin(), Q.off.end(), row_offsets);
-    const size_t n = std::min(capacity, Q.col.size());
-    std::copy(Q.col.begin(), Q.col.begin() + (long)n, cols);
-    std::copy(Q.val.begin(), Q.val.begin() + (long)n, vals);
-    if (nnz_out) *nnz_out = Q.col.size();
-    return 0;
+    return bending_matrix_out(pos, n_verts, indices, n_faces, row_offsets, cols, vals, capacity, nnz_out);
 } MPM_CATCH_ALL
 
 int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try {
@@ -3344,115 +2177,7 @@ int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try
     if (int rc = single_engine_only(e, "bending stiffness is")) return rc;
     REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_bending: n_cloths must be mpm_cloth_count (or 0: off)");
     REQUIRE(n_cloths == 0 || stiffness, "null stiffness array");
-    bool any = false;
-    for (size_t c = 0; c < n_cloths; ++c) {
-        REQUIRE(std::isfinite(stiffness[c]) && stiffness[c] >= 0.f, "bending: a stiffness is negative or not finite");
-        any = any || stiffness[c] > 0.f;
-    }
-    // the table on the host: rows in ascending vertex id, k folded in, the diagonal dropped (mpm_bending.h)
-    auto id_bits = [](int id) {
-        float f;
-        std::memcpy(&f, &id, sizeof f);
-        return f;
-    };
-    std::vector<int> row_pid;
-    std::vector<std::vector<float2>> rows;
-    std::vector<double> abs_sum;   // per row: sum_j |k Q_ij|, the diagonal included
-    for (size_t c = 0; c < n_cloths && any; ++c) {
-        if (!(stiffness[c] > 0.f)) continue;
-        const mpm_engine::Cloth& cl = e->cloths[c];
-        std::vector<int32_t> idx(3 * cl.n_faces);
-        for (size_t i = 0; i < idx.size(); ++i) idx[i] = e->h_idx[3 * cl.first_face + i] - (int32_t)cl.first_vertex;
-        BendCsr Q;
-        std::string why;
-        if (!bending_matrix(e->h_pos.data() + 3 * cl.first_vertex, cl.n_verts, idx.data(), cl.n_faces, cl.first_face, Q, why))
-            return fail(MPM_ERR_INVALID, why);
-        const double k = (double)stiffness[c];
-        for (size_t v = 0; v < cl.n_verts; ++v) {
-            const int own = (int)(e->nf + cl.first_vertex + v);
-            row_pid.push_back(own);
-            rows.emplace_back();
-            double a = 0.0;
-            for (size_t q = Q.off[v]; q < Q.off[v + 1]; ++q) {
-                a += std::fabs(k * Q.val[q]);
-                if ((size_t)Q.col[q] == v) continue;
-                rows.back().push_back(make_float2((float)(k * Q.val[q]), id_bits((int)(e->nf + cl.first_vertex) + Q.col[q])));
-            }
-            abs_sum.push_back(a);
-        }
-    }
-    const size_t n_rows = row_pid.size(), n_slices = (n_rows + BEND_SLICE - 1) / BEND_SLICE;
-    std::vector<unsigned> slice_off(n_slices + 1, 0u);
-    for (size_t s = 0; s < n_slices; ++s) {
-        size_t width = 0;
-        for (size_t r = s * BEND_SLICE; r < std::min(n_rows, (s + 1) * BEND_SLICE); ++r) width = std::max(width, rows[r].size());
-        REQUIRE((size_t)slice_off[s] + width * BEND_SLICE < (size_t)1 << 31, "bending: the table is too large");
-        slice_off[s + 1] = slice_off[s] + (unsigned)(width * BEND_SLICE);
-    }
-    std::vector<float2> ent(slice_off[n_slices]);
-    for (size_t s = 0; s < n_slices; ++s) {
-        const size_t width = (slice_off[s + 1] - slice_off[s]) / BEND_SLICE;
-        for (size_t l = 0; l < BEND_SLICE; ++l) {
-            const size_t r = s * BEND_SLICE + l;
-            // (padding: coefficient 0 and the row's own id; the lanes past the last row are never read)
-            const int own = r < n_rows ? row_pid[r] : row_pid[n_rows - 1];
-            for (size_t q = 0; q < width; ++q)
-                ent[slice_off[s] + q * BEND_SLICE + l] = r < n_rows && q < rows[r].size() ? rows[r][q] : make_float2(0.f, id_bits(own));
-        }
-    }
-    // substeps that mpm_run_substeps deferred are owed with the stiffness they were enqueued with
-    if (int rc = settle(e)) return rc;
-    float max_dt = INFINITY;
-    mpm_engine::Bending next;
-    FreshArrays fresh(e);   // (a failure below changes nothing: the new buffers go, the table in force stays)
-    if (n_rows) {
-        // m_i: the mass ParticleToGrid forms for the vertex particle (q[0].w x DP::M.density, both floats)
-        std::vector<float> vol(e->nv);
-        int* iota = nullptr;
-        if (int rc = device_iota(e, &iota)) return rc;
-        if (int rc = gather_to_host<F_VOL>(e, vol.data(), e->nv, iota + e->nf)) return rc;
-        double w2 = 0.0;
-        for (size_t r = 0; r < n_rows; ++r) {
-            const double m = (double)(std::fabs(vol[(size_t)row_pid[r] - e->nf]) * e->dp.M.density);
-            if (abs_sum[r] > 0.0) w2 = std::max(w2, m > 0.0 ? abs_sum[r] / m : (double)INFINITY);
-        }
-        if (w2 > 0.0) {
-            const double lim = 2.0 / std::sqrt(w2);
-            max_dt = (float)lim;
-            if ((double)max_dt > lim) max_dt = std::nextafterf(max_dt, 0.f);   // (rounded towards zero: never above the bound)
-        }
-        int* d_row = nullptr;
-        unsigned* d_off = nullptr;
-        float2* d_ent = nullptr;
-        if (int rc = fresh.alloc(&d_row, n_rows, false)) return rc;
-        if (int rc = fresh.alloc(&d_off, n_slices + 1, false)) return rc;
-        if (int rc = fresh.alloc(&d_ent, ent.size(), false)) return rc;
-        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
-        H2D(e, d_row, row_pid.data(), n_rows * sizeof(int));
-        H2D(e, d_off, slice_off.data(), (n_slices + 1) * sizeof(unsigned));
-        if (!ent.empty()) H2D(e, d_ent, ent.data(), ent.size() * sizeof(float2));
-        next.args = BendArgs{d_row, d_off, d_ent, (int)n_rows};
-    } else {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    {
-        BendArgs& old = e->bend.args;
-        int* o_row = const_cast<int*>(old.row_pid);
-        unsigned* o_off = const_cast<unsigned*>(old.slice_off);
-        float2* o_ent = const_cast<float2*>(old.ent);
-        e->dfree(o_row);
-        e->dfree(o_off);
-        e->dfree(o_ent);
-    }
-    next.k.assign(stiffness, stiffness + n_cloths);
-    next.max_dt = max_dt;
-    next.row_vertex.resize(n_rows);
-    for (size_t r = 0; r < n_rows; ++r) next.row_vertex[r] = row_pid[r] - (int)e->nf;
-    next.abs_sum.swap(abs_sum);
-    e->bend = next;
-    fresh.commit();
-    damping_limit(e);   // (the hinge damping is beta k Q: its share of mpm_damping_max_stable_dt follows the new k)
-    return 0;
+    return set_bending(e, n_cloths, stiffness);
 } MPM_CATCH_ALL
 
 int mpm_get_bending(mpm_handle_t e, float* out, size_t capacity, size_t* n_out) try {
@@ -3466,17 +2191,7 @@ int mpm_get_bending(mpm_handle_t e, float* out, size_t capacity, size_t* n_out) 
 int mpm_bending_forces(mpm_handle_t e, float* f_out) try {
     READY(e);
     REQUIRE(f_out || e->nv == 0, "null output");
-    const size_t bytes = e->nv * 12;
-    if (!e->bend.on()) {
-        std::memset(f_out, 0, bytes);
-        return 0;
-    }
-    if (int rc = e->stage(bytes)) return rc;
-    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
-    hipLaunchKernelGGL(k_bend_eval, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
-                       e->bend.args, (float*)e->d_stage);
-    D2H(e, f_out, e->d_stage, bytes);
-    return 0;
+    return bending_forces(e, f_out);
 } MPM_CATCH_ALL
 
 int mpm_bending_max_stable_dt(mpm_handle_t e, float* dt_out) try {
@@ -3485,126 +2200,7 @@ int mpm_bending_max_stable_dt(mpm_handle_t e, float* dt_out) try {
     return 0;
 } MPM_CATCH_ALL
 
-}  // extern "C"
-
-// ---- stiffness-proportional damping (mpm_set_damping, mpm_get_damping, mpm_damping_forces, mpm_damping_max_stable_dt,
-// mpm_damping_face_records; mpm_damping.h) ----
-// the Lame parameters of cloth c as the elastic kernels use them (init_cloth_materials; DP::M of a single-material engine)
-static void cloth_lame(const mpm_engine* e, size_t c, float* mu, float* lambda) {
-    if (!e->multi_mat) {
-        *mu = e->dp.M.mu;
-        *lambda = e->dp.M.lambda;
-        return;
-    }
-    const mpm_cloth_material_t& m = e->cloths[c].m;
-    *mu = m.youngs_modulus / (2.f * (1.f + m.poisson_ratio));
-    *lambda = m.youngs_modulus * m.poisson_ratio / ((1.f + m.poisson_ratio) * (1.f - 2.f * m.poisson_ratio));
-}
-// mpm_damping_max_stable_dt from what the engine holds: the membrane row sums and vertex masses of the last
-// mpm_set_damping, the rows of the bending table in force.  Host only; cannot fail.  Also says whether k_bend_damp has a
-// row to work on (a cloth with beta_bending > 0 and bending stiffness > 0).
-static void damping_limit(mpm_engine* e) {
-    mpm_engine::Damping& dm = e->damp;
-    dm.max_dt = INFINITY;
-    dm.bend_rows = false;
-    if (!dm.any()) return;
-    std::vector<double> D(e->nv, 0.0);
-    if (dm.membrane()) D = dm.D_membrane;
-    if (e->bend.on())
-        for (size_t r = 0; r < e->bend.row_vertex.size(); ++r) {
-            const size_t v = (size_t)e->bend.row_vertex[r];
-            const float beta = dm.beta_vertex[v];
-            if (!(beta > 0.f)) continue;
-            dm.bend_rows = true;
-            D[v] += (double)beta * e->bend.abs_sum[r];
-        }
-    double worst = 0.0;
-    for (size_t i = 0; i < e->nv; ++i)
-        if (D[i] > 0.0) worst = std::max(worst, dm.mass[i] > 0.0 ? D[i] / dm.mass[i] : (double)INFINITY);
-    if (worst > 0.0) {
-        const double lim = 2.0 / worst;
-        dm.max_dt = (float)lim;
-        if ((double)dm.max_dt > lim) dm.max_dt = std::nextafterf(dm.max_dt, 0.f);   // (rounded towards zero: never above the bound)
-    }
-}
-// Puts the coefficients `d` (checked; one per cloth, or none) in force: k_damp's tables, k_bend_damp's coefficient per
-// vertex (it reads the bending table in force) and the stability limit.  The caller has settled the owed substeps.  A
-// failure changes nothing.
-static int damping_apply(mpm_engine* e, std::vector<mpm_cloth_damping_t> d) {
-    const size_t nc = d.size();
-    bool membrane = false, bending = false;
-    for (size_t c = 0; c < nc; ++c) {
-        membrane = membrane || d[c].membrane > 0.f;
-        bending = bending || d[c].bending > 0.f;
-    }
-    mpm_engine::Damping next;
-    FreshArrays fresh(e);
-    if (membrane || bending) {
-        std::vector<float4> coef(std::max<size_t>(nc, 1), make_float4(0.f, 0.f, 0.f, 0.f));
-        std::vector<int> cloth_of_face(e->nf, 0);
-        next.beta_vertex.assign(e->nv, 0.f);
-        for (size_t c = 0; c < nc; ++c) {
-            const mpm_engine::Cloth& cl = e->cloths[c];
-            float mu, lambda;
-            cloth_lame(e, c, &mu, &lambda);
-            coef[c] = make_float4(mu, lambda, d[c].membrane, 0.f);
-            std::fill(cloth_of_face.begin() + (long)cl.first_face, cloth_of_face.begin() + (long)(cl.first_face + cl.n_faces), (int)c);
-            std::fill(next.beta_vertex.begin() + (long)cl.first_vertex, next.beta_vertex.begin() + (long)(cl.first_vertex + cl.n_verts),
-                      d[c].bending);
-        }
-        // every particle's q[0].w in original order: a vertex's mass as ParticleToGrid forms it (x DP::M.density, both floats),
-        // a face's rest volume (a multi-material engine holds the mass there: / the cloth's density)
-        std::vector<float> w(e->np);
-        int* iota = nullptr;
-        if (int rc = device_iota(e, &iota)) return rc;
-        if (int rc = gather_to_host<F_VOL>(e, w.data(), e->np, iota)) return rc;
-        next.mass.resize(e->nv);
-        for (size_t i = 0; i < e->nv; ++i) next.mass[i] = (double)(std::fabs(w[e->nf + i]) * e->dp.M.density);
-        if (membrane) {
-            // sum_j |D_ij| of the membrane's damping matrix at the rest shape, per vertex (Gershgorin)
-            std::vector<float> dminv(e->nf * 4);
-            if (int rc = gather_to_host<F_DMINV>(e, dminv.data(), e->nf, iota)) return rc;
-            next.D_membrane.assign(e->nv, 0.0);
-            for (size_t f = 0; f < e->nf; ++f) {
-                const float4 c = coef[(size_t)cloth_of_face[f]];
-                if (!(c.z > 0.f)) continue;
-                const double Dm0 = dminv[4 * f], Dm1 = dminv[4 * f + 1], Dm3 = dminv[4 * f + 3];
-                const double vol = std::fabs((double)w[f]) / (e->multi_mat ? (double)e->h_rho_of_pid[f] : 1.0);
-                const double g[3] = {std::hypot(Dm0, Dm1 + Dm3), std::hypot(Dm0, Dm1), std::fabs(Dm3)};   // |columns of grad_N|
-                const double s = (double)c.z * vol * (2.0 * (double)c.x + 2.0 * (double)c.y) * (g[0] + g[1] + g[2]);
-                for (int k = 0; k < 3; ++k) next.D_membrane[(size_t)e->h_idx[3 * f + k]] += s * g[k];
-            }
-            float4* d_coef = nullptr;
-            int* d_cloth = nullptr;
-            if (int rc = fresh.alloc(&d_coef, coef.size(), false)) return rc;
-            if (int rc = fresh.alloc(&d_cloth, cloth_of_face.size(), false)) return rc;
-            H2D(e, d_coef, coef.data(), coef.size() * sizeof(float4));
-            if (!cloth_of_face.empty()) H2D(e, d_cloth, cloth_of_face.data(), cloth_of_face.size() * sizeof(int));
-            next.args = DampArgs{d_coef, d_cloth};
-        }
-        if (bending) {
-            if (int rc = fresh.alloc(&next.d_beta_vertex, e->nv, false)) return rc;
-            H2D(e, next.d_beta_vertex, next.beta_vertex.data(), e->nv * sizeof(float));
-        }
-    }
-    // (a synchronisation point: the kernels enqueued so far have read the old tables)
-    HIP_TRY(hipStreamSynchronize(e->stream));
-    {
-        float4* o_coef = const_cast<float4*>(e->damp.args.coef);
-        int* o_cloth = const_cast<int*>(e->damp.args.cloth_of_face);
-        e->dfree(o_coef);
-        e->dfree(o_cloth);
-        e->dfree(e->damp.d_beta_vertex);
-    }
-    next.d.swap(d);
-    e->damp = next;
-    fresh.commit();
-    damping_limit(e);
-    return 0;
-}
-
-extern "C" {
-
+// ---- stiffness-proportional damping (mpm_cloth_host.h; mpm_damping.h) ------------------------------------------------------
 int mpm_set_damping(mpm_handle_t e, size_t n_cloths, const mpm_cloth_damping_t* d) try {
     READY_NO_SETTLE(e);
     if (int rc = single_engine_only(e, "damping is")) return rc;
@@ -3629,30 +2225,7 @@ int mpm_get_damping(mpm_handle_t e, mpm_cloth_damping_t* out, size_t capacity, s
 int mpm_damping_forces(mpm_handle_t e, float* f_out) try {
     READY(e);
     REQUIRE(f_out || e->nv == 0, "null output");
-    std::memset(f_out, 0, e->nv * 12);
-    const bool hinges = e->bend.on() && e->damp.bending();
-    if (!e->damp.membrane() && !hinges) return 0;
-    // the face records in original face order, behind them the bending rows in original vertex order
-    const size_t n_rec = e->nf * 9, n_all = n_rec + e->nv * 3;
-    if (int rc = e->stage(n_all * 4)) return rc;
-    HIP_TRY(hipMemsetAsync(e->d_stage, 0, n_all * 4, e->stream));
-    if (e->damp.membrane() && e->nf)
-        hipLaunchKernelGGL(k_damp_eval, dim3((unsigned)((e->nf + 255) / 256)), dim3(256), 0, e->stream, e->dp, e->damp.args,
-                           (float*)e->d_stage);
-    if (hinges)
-        hipLaunchKernelGGL(k_bend_damp_eval, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
-                           e->bend.args, (const float*)e->damp.d_beta_vertex, (float*)e->d_stage + n_rec);
-    HIP_TRY(hipGetLastError());
-    std::vector<float> h(n_all);
-    D2H(e, h.data(), e->d_stage, n_all * 4);
-    // a vertex's records in ascending original face id, as k_vforce sums them; then the bending row, as k_bend_damp adds it
-    for (size_t f = 0; f < e->nf; ++f)
-        for (int c = 0; c < 3; ++c) {
-            float* o = f_out + 3 * (size_t)e->h_idx[3 * f + c];
-            for (int k = 0; k < 3; ++k) o[k] += -h[9 * f + 3 * c + k];
-        }
-    for (size_t i = 0; i < e->nv * 3; ++i) f_out[i] += h[n_rec + i];
-    return 0;
+    return damping_forces(e, f_out);
 } MPM_CATCH_ALL
 
 int mpm_damping_max_stable_dt(mpm_handle_t e, float* dt_out) try {
@@ -3661,129 +2234,18 @@ int mpm_damping_max_stable_dt(mpm_handle_t e, float* dt_out) try {
     return 0;
 } MPM_CATCH_ALL
 
-// host code only: the device function of the kernels, compiled for the host
 int mpm_damping_face_records(size_t n_faces, const float* dminv3, const float* vol, const float* mu, const float* lambda,
                              const float* beta, const float* x9, const float* v9, float* rec9_out) try {
     REQUIRE((dminv3 && vol && mu && lambda && beta && x9 && v9 && rec9_out) || n_faces == 0, "null array");
-    for (size_t f = 0; f < n_faces; ++f) {
-        float x[3][3], v[3][3], rec[3][3];
-        std::memcpy(x, x9 + 9 * f, sizeof x);
-        std::memcpy(v, v9 + 9 * f, sizeof v);
-        damp_face(dminv3[3 * f], dminv3[3 * f + 1], dminv3[3 * f + 2], vol[f], mu[f], lambda[f], beta[f], x, v, rec);
-        std::memcpy(rec9_out + 9 * f, rec, sizeof rec);
-    }
-    return 0;
+    return damping_face_records(n_faces, dminv3, vol, mu, lambda, beta, x9, v9, rec9_out);
 } MPM_CATCH_ALL
 
-}  // extern "C"
-
-// ---- the per-cloth report (mpm_measure, mpm_face_strain, mpm_cloth_energy_density; mpm_measure.h) ----
-// The chunk table: every cloth's faces, then every cloth's vertices, in runs of at most MEASURE_CHUNK original ids that
-// never straddle a cloth.  Built once; the vertex chunks' rows of the bending table follow mpm_set_bending.
-static int measure_ready(mpm_engine* e) {
-    mpm_engine::Measure& ms = e->measure;
-    const size_t nc = e->cloths.size();
-    if (!ms.built) {
-        std::vector<int4> chunks, ranges(nc, make_int4(0, 0, 0, 0));
-        const int nfg = e->dp.NfG;
-        for (int pass = 0; pass < 2; ++pass) {
-            for (size_t c = 0; c < nc; ++c) {
-                const mpm_engine::Cloth& cl = e->cloths[c];
-                const int first = pass == 0 ? (int)cl.first_face : nfg + (int)cl.first_vertex;
-                const int end = first + (int)(pass == 0 ? cl.n_faces : cl.n_verts);
-                (pass == 0 ? ranges[c].x : ranges[c].z) = (int)chunks.size();
-                for (int b = first; b < end; b += MEASURE_CHUNK) chunks.push_back(make_int4((int)c, b, std::min(end, b + MEASURE_CHUNK), -1));
-                (pass == 0 ? ranges[c].y : ranges[c].w) = (int)chunks.size();
-            }
-            if (pass == 0) ms.n_face_chunks = (int)chunks.size();
-        }
-        ms.n_vertex_chunks = (int)chunks.size() - ms.n_face_chunks;
-        FreshArrays fresh(e);
-        int4 *d_chunks = nullptr, *d_ranges = nullptr;
-        mpm_cloth_measure_t *d_rows = nullptr, *d_out = nullptr;
-        if (int rc = fresh.alloc(&d_chunks, chunks.size(), false)) return rc;
-        if (int rc = fresh.alloc(&d_ranges, nc, false)) return rc;
-        if (int rc = fresh.alloc(&d_rows, chunks.size(), true)) return rc;
-        if (int rc = fresh.alloc(&d_out, nc, true)) return rc;
-        if (nc) H2D(e, d_ranges, ranges.data(), nc * sizeof(int4));
-        fresh.commit();
-        ms.d_chunks = d_chunks; ms.d_ranges = d_ranges; ms.d_rows = d_rows; ms.d_out = d_out;
-        ms.chunks.swap(chunks);
-        ms.rows_stale = true;
-        ms.built = true;
-    }
-    if (ms.rows_stale || ms.k_seen != e->bend.k) {
-        // row of the bending table of every cloth's first vertex: the table holds the cloths with k > 0, in cloth order
-        std::vector<int> row0(nc, -1);
-        int r = 0;
-        for (size_t c = 0; c < nc && e->bend.on(); ++c)
-            if (c < e->bend.k.size() && e->bend.k[c] > 0.f) {
-                row0[c] = r;
-                r += (int)e->cloths[c].n_verts;
-            }
-        if (r != (e->bend.on() ? e->bend.args.n_rows : 0)) return fail(MPM_ERR_INTERNAL, "mpm_measure: the bending table does not match the cloths");
-        for (int k = ms.n_face_chunks; k < (int)ms.chunks.size(); ++k) {
-            int4& ch = ms.chunks[(size_t)k];
-            const int base = e->dp.NfG + (int)e->cloths[(size_t)ch.x].first_vertex;
-            ch.w = row0[(size_t)ch.x] < 0 ? -1 : row0[(size_t)ch.x] + (ch.y - base);
-        }
-        if (!ms.chunks.empty()) H2D(e, ms.d_chunks, ms.chunks.data(), ms.chunks.size() * sizeof(int4));
-        ms.k_seen = e->bend.k;
-        ms.rows_stale = false;
-    }
-    return 0;
-}
-static MeasureArgs measure_args(const mpm_engine* e) {
-    const mpm_engine::Measure& ms = e->measure;
-    MeasureArgs a{};
-    a.chunks = ms.d_chunks;
-    a.n_face_chunks = ms.n_face_chunks;
-    a.n_vertex_chunks = ms.n_vertex_chunks;
-    a.rows = ms.d_rows;
-    a.mats = e->multi_mat ? e->d_cloth_mat : nullptr;
-    a.bend = e->bend.args;
-    return a;
-}
-
-extern "C" {
-
+// ---- the per-cloth report (mpm_cloth_host.h; mpm_measure.h) --------------------------------------------------------------------
 int mpm_measure(mpm_handle_t e, mpm_cloth_measure_t* per_cloth, size_t capacity, size_t* n_cloths_out,
                 mpm_cloth_measure_t* total) try {
     READY(e);
     REQUIRE(per_cloth || capacity == 0, "null output");
-    if (int rc = measure_ready(e)) return rc;
-    const size_t nc = e->cloths.size();
-    const MeasureArgs a = measure_args(e);
-    // at most three launches: face chunks, vertex chunks, one workgroup per cloth
-    if (a.n_face_chunks) hipLaunchKernelGGL(k_measure_faces, dim3((unsigned)a.n_face_chunks), dim3(256), 0, e->stream, e->dp, a);
-    if (a.n_vertex_chunks) hipLaunchKernelGGL(k_measure_vertices, dim3((unsigned)a.n_vertex_chunks), dim3(256), 0, e->stream, e->dp, a);
-    std::vector<mpm_cloth_measure_t> rows(nc);
-    if (nc) {
-        hipLaunchKernelGGL(k_measure_final, dim3((unsigned)nc), dim3(256), 0, e->stream, a, (const int4*)e->measure.d_ranges,
-                           e->measure.d_out);
-        HIP_TRY(hipGetLastError());
-        D2H(e, rows.data(), e->measure.d_out, nc * sizeof(mpm_cloth_measure_t));
-    }
-    std::copy(rows.begin(), rows.begin() + (long)std::min(capacity, nc), per_cloth);
-    if (n_cloths_out) *n_cloths_out = nc;
-    if (total) {
-        mpm_cloth_measure_t t{};
-        t.stretch_min = INFINITY;
-        t.normal_min = INFINITY;
-        double* ts = reinterpret_cast<double*>(&t);
-        for (const mpm_cloth_measure_t& r : rows) {
-            const double* rs = reinterpret_cast<const double*>(&r);
-            for (int k = 0; k < MEASURE_SUMS; ++k) ts[k] += rs[k];
-            t.stretch_max = std::max(t.stretch_max, r.stretch_max);
-            t.stretch_min = std::min(t.stretch_min, r.stretch_min);
-            t.normal_min = std::min(t.normal_min, r.normal_min);
-            t.speed_max = std::max(t.speed_max, r.speed_max);
-            t.faces += r.faces;
-            t.vertices += r.vertices;
-        }
-        *total = t;
-    }
-    return 0;
+    return measure_cloths(e, per_cloth, capacity, n_cloths_out, total);
 } MPM_CATCH_ALL
 
 int mpm_face_strain(mpm_handle_t e, float* out) try {
@@ -3791,32 +2253,13 @@ int mpm_face_strain(mpm_handle_t e, float* out) try {
     if (int rc = single_engine_only(e, "mpm_face_strain is")) return rc;
     REQUIRE(out || e->nf == 0, "null output");
     if (int rc = settle(e)) return rc;
-    if (e->nf == 0) return 0;
-    if (int rc = measure_ready(e)) return rc;
-    const MeasureArgs a = measure_args(e);
-    const size_t bytes = e->nf * 16;
-    if (int rc = e->stage(bytes)) return rc;
-    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
-    hipLaunchKernelGGL(k_measure_face_strain, dim3((unsigned)a.n_face_chunks), dim3(256), 0, e->stream, e->dp, a, (float*)e->d_stage);
-    HIP_TRY(hipGetLastError());
-    D2H(e, out, e->d_stage, bytes);
-    return 0;
+    return face_strain(e, out);
 } MPM_CATCH_ALL
 
-// host code only: the device function of the kernels, compiled for the host
 int mpm_cloth_energy_density(const mpm_cloth_material_t* m, size_t n, const float* F, double* out) try {
     REQUIRE(m, "null material");
     REQUIRE((F && out) || n == 0, "null array");
-    // the Lame parameters as mpm_finalize forms them, in float
-    const float mu = m->youngs_modulus / (2.f * (1.f + m->poisson_ratio));
-    const float lambda = m->youngs_modulus * m->poisson_ratio / ((1.f + m->poisson_ratio) * (1.f - 2.f * m->poisson_ratio));
-    for (size_t i = 0; i < n; ++i) {
-        const float* f = F + 9 * i;
-        const double d1[3] = {(double)f[0], (double)f[3], (double)f[6]}, d2[3] = {(double)f[1], (double)f[4], (double)f[7]};
-        const double d3[3] = {(double)f[2], (double)f[5], (double)f[8]};
-        cloth_energy_density(mu, lambda, m->K, m->gamma, d1, d2, d3, out + 6 * i);
-    }
-    return 0;
+    return cloth_energy_densities(m, n, F, out);
 } MPM_CATCH_ALL
 
 }  // extern "C"

@@ -1,9 +1,12 @@
-// Host-side engine object shared by the C-ABI implementation files.
+// Host-side engine object shared by the C-ABI implementation: mpm_engine.hip (every entry point, the substep's launch
+// sequence, settle and the drivers) and the host headers it includes -- mpm_io.h, mpm_contact.h, mpm_sort.h, and per
+// feature mpm_cloth_host.h, mpm_bodies_host.h, mpm_dist_host.h, mpm_chain_host.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <exception>
 #include <functional>
 #include <new>
@@ -444,6 +447,50 @@ template <class T>
 static int copy_out(const std::vector<T>& set, T* out, size_t capacity, size_t* n_out) {
     std::copy(set.begin(), set.begin() + (long)std::min(capacity, set.size()), out);
     if (n_out) *n_out = set.size();
+    return 0;
+}
+
+// ---- what the features' host headers need from mpm_engine.hip -------------------------------------------------------------
+// (mpm_cloth_host.h, mpm_bodies_host.h, mpm_dist_host.h, mpm_chain_host.h: included by mpm_engine.hip, which defines these)
+// the owed substeps and the held-back phase calls, run before a call looks at or changes the state
+static int settle(mpm_engine* e, Ctl* fresh = nullptr);
+// the conditional re-sort
+static void launch_rebuild(mpm_engine* e, DP p, bool lean = false, float dt = 0.f);
+static int recover_slab_overflow(mpm_engine* e, Ctl& c);
+
+#define READY_NO_SETTLE(e)                              \
+    REQUIRE(e, "null handle");                          \
+    REQUIRE((e)->finalized, "call mpm_finalize first"); \
+    if (int rc__ = use(e)) return rc__
+#define READY(e)         \
+    READY_NO_SETTLE(e);  \
+    if (int rc2__ = settle(e)) return rc2__
+
+// ---- argument checks shared by pins, grid bodies and force fields ----------------------------------------------------------
+static bool finite_n(const float* a, int n) {
+    for (int k = 0; k < n; ++k)
+        if (!std::isfinite(a[k])) return false;
+    return true;
+}
+// R^T R = I and det R = 1, each entry within 1e-4 (float rotations that went through a few products)
+static bool is_rotation(const float* R) {
+    if (!finite_n(R, 9)) return false;
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) {
+            double d = 0.0;
+            for (int k = 0; k < 3; ++k) d += (double)R[k * 3 + i] * (double)R[k * 3 + j];
+            if (std::fabs(d - (i == j ? 1.0 : 0.0)) > 1e-4) return false;
+        }
+    const double det = (double)R[0] * ((double)R[4] * R[8] - (double)R[5] * R[7]) -
+                       (double)R[1] * ((double)R[3] * R[8] - (double)R[5] * R[6]) +
+                       (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
+    return std::fabs(det - 1.0) <= 1e-4;
+}
+// pins, grid bodies, force fields, bending stiffness and damping are refused on a partitioned or multi-rank engine (out of scope);
+// what_is: "pins are", "bending stiffness is", ...
+static int single_engine_only(const mpm_engine* e, const char* what_is) {
+    if (e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on)
+        return fail(MPM_ERR_INVALID, std::string(what_is) + " not available on a partitioned or multi-rank engine");
     return 0;
 }
 

@@ -85,4 +85,24 @@ struct RootFinder {
     }
 };
 
+// The host loop: the root of a function behind a C callback (mpm_newton_bisect_f64 / _f32, whose entry points have
+// checked the bracket and the tolerances).  `fn` evaluates in double whatever T is.  0: converged, 1: out of evaluations.
+template <class T>
+inline int newton_bisect(void (*fn)(void* user, double x, double* f, double* df), void* user, T x_lo, T x_hi, T guess, T x_tol,
+                         T f_tol, int max_evals, int flags, T* root_out, int* evals_out) {
+    double f_lo, f_hi, d;
+    fn(user, (double)x_lo, &f_lo, &d);
+    fn(user, (double)x_hi, &f_hi, &d);
+    RootFinder<T> rf;
+    rf.start(x_lo, (T)f_lo, x_hi, (T)f_hi, guess, x_tol, f_tol, max_evals, flags);
+    while (rf.status == 0) {
+        double f, df;
+        fn(user, (double)rf.root, &f, &df);
+        rf.feed((T)f, (T)df);
+    }
+    *root_out = rf.root;
+    *evals_out = rf.evals;
+    return rf.status == 1 ? 0 : 1;
+}
+
 }  // namespace mpm

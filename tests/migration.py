@@ -1,6 +1,6 @@
 """The partitioned domain's per-particle state machine (drake_amd/csrc/mpm_dist.h: k_dist_init_roles, k_dist_classify,
 dist_emit, k_dist_apply, k_dist_mig_reduce; the predicates dist_in_my_band / dist_in_neighbour_bands of mpm_device.h; the
-host rules mpm_dist_init, mpm_dist_retune and plan_migration of mpm_engine.hip) restated on the host, and particle
+host rules dist_init, dist_retune and plan_migration of mpm_dist_host.h) restated on the host, and particle
 layouts that put particles ON every threshold of it and move them across the cuts in both directions.  CPU only:
 nothing here imports the engine.
 

@@ -54,7 +54,7 @@ def _bits(a):
 
 
 def _lame32(E, nu):
-    """the engine's float Lame parameters (mpm_finalize, init_cloth_materials): float32 arithmetic throughout"""
+    """the engine's float Lame parameters (lame, mpm_cloth_host.h): float32 arithmetic throughout"""
     E, nu, one, two = (np.float32(a) for a in (E, nu, 1.0, 2.0))
     return E / (two * (one + nu)), E * nu / ((one + nu) * (one - two * nu))
 

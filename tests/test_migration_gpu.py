@@ -1,6 +1,6 @@
 """The partition's migration kernels (k_dist_init_roles, k_dist_classify, dist_emit, k_dist_apply, k_dist_mig_reduce of
-drake_amd/csrc/mpm_dist.h) and their host side (mpm_dist_init, mpm_dist_retune, plan_migration, mpm_dist_migrate_pack /
-apply) against the exact restatement and the layouts of tests/migration.py, with all ranks in one process
+drake_amd/csrc/mpm_dist.h) and their host side (mpm_dist_host.h: mpm_dist_init, mpm_dist_retune, plan_migration,
+mpm_dist_migrate_pack / apply) against the exact restatement and the layouts of tests/migration.py, with all ranks in one process
 (drake_amd.dist.LocalWorld).
 
 One stage: upload_particle_state(pos, vel) on every rank (written where the rank has a slot; the role is left alone),
