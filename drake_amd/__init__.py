@@ -9,5 +9,6 @@ CPU fallback: every compute call goes to the HIP library or raises.
 from .capi import (MpmError, GpuMpm, load_library, library_path, Material, Collider, SdfCollider, GridCollider, BC_TABLE,  # noqa: F401
                    grid_collider_preset, ARR, RT, PHASES, Pin, BodyMotion, ClothMaterial, GridBody, BC_BODIES, GB_NO_MESH, ForceField,
                    force_field_acceleration, FF_ACCEL, FF_DRAG, FF_NORMAL_DRAG, FF_QUADRATIC, FF_REGION, bending_matrix,
-                   cloth_energy_density, MEASURE_DTYPE, damping_face_records)
+                   cloth_energy_density, MEASURE_DTYPE, damping_face_records, LINK_DTYPE, LINK_TENSION_ONLY, links,
+                   link_force)
 from . import scenes  # noqa: F401

@@ -185,6 +185,36 @@ def bending_matrix(pos, indices):
     return off.astype(np.int64), cols[:nnz.value], vals[:nnz.value]
 
 
+# mpm_link_t (24 bytes) as a numpy record: GpuMpm.set_links takes, and get_links returns, arrays of it
+LINK_TENSION_ONLY = 1
+LINK_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("stiffness", "<f4"), ("rest_length", "<f4"), ("damping", "<f4"),
+                       ("flags", "<u4")])
+assert LINK_DTYPE.itemsize == 24
+
+
+def links(a, b, stiffness, rest_length=0.0, damping=0.0, flags=0):
+    """an array of LINK_DTYPE from vertex ids a, b (dump_cpu_state's numbering) and per-link or scalar k, L, c, flags"""
+    a = np.asarray(a).reshape(-1)
+    out = np.zeros(len(a), LINK_DTYPE)
+    out["a"], out["b"] = a, np.asarray(b).reshape(-1)
+    out["stiffness"], out["rest_length"], out["damping"], out["flags"] = stiffness, rest_length, damping, flags
+    return out
+
+
+def link_force(link, xa, xb, va, vb):
+    """mpm_link_force: the force (3,) float32 of one link (a LINK_DTYPE record) on its end a, evaluated on the host by the
+    function the link kernel calls; the force on b is its negative.  Needs no engine and no GPU."""
+    lib = load_library()
+    rec = np.array(link, LINK_DTYPE).reshape(1)
+    v = [np.ascontiguousarray(q, np.float32).reshape(3) for q in (xa, xb, va, vb)]
+    out = np.zeros(3, np.float32)
+    rc = lib.mpm_link_force(rec.ctypes.data, v[0].ctypes.data, v[1].ctypes.data, v[2].ctypes.data, v[3].ctypes.data,
+                            out.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return out
+
+
 def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
     """mpm_damping_face_records: the membrane damping kernel's face function on the host.  dminv3 (n, 3) = (Dm0, Dm1, Dm3),
     vol, mu, lam, beta (n,) (scalars are broadcast), x, v (n, 3, 3) corner positions and velocities; returns the corner
@@ -361,6 +391,7 @@ SYMBOLS = [
     "mpm_get_body_contact_materials", "mpm_set_bending", "mpm_get_bending", "mpm_bending_forces",
     "mpm_bending_max_stable_dt", "mpm_bending_matrix", "mpm_measure", "mpm_face_strain", "mpm_cloth_energy_density",
     "mpm_set_damping", "mpm_get_damping", "mpm_damping_forces", "mpm_damping_max_stable_dt", "mpm_damping_face_records",
+    "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -487,6 +518,12 @@ def load_library(build: bool = True):
         "mpm_bending_forces": [vp, vp],
         "mpm_bending_max_stable_dt": [vp, P(f)],
         "mpm_bending_matrix": [vp, sz, vp, sz, vp, vp, vp, sz, P(sz)],
+        "mpm_set_links": [vp, sz, vp],
+        "mpm_get_links": [vp, vp, sz, P(sz)],
+        "mpm_link_forces": [vp, vp],
+        "mpm_link_energy": [vp, P(C.c_double), vp],
+        "mpm_links_max_stable_dt": [vp, P(f)],
+        "mpm_link_force": [vp, vp, vp, vp, vp, vp],
         "mpm_set_damping": [vp, sz, vp],
         "mpm_get_damping": [vp, vp, sz, P(sz)],
         "mpm_damping_forces": [vp, vp],
@@ -809,6 +846,47 @@ class GpuMpm:
     @staticmethod
     def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
         return damping_face_records(dminv3, vol, mu, lam, beta, x, v)
+
+    def set_links(self, table):
+        """mpm_set_links: the links between cloth vertices -- seams (rest_length 0), springs and tension-only cords --, an
+        array of LINK_DTYPE (see `links`) with vertex ids in dump_cpu_state's numbering; an empty table clears them.  A
+        synchronisation point."""
+        t = np.ascontiguousarray(table, LINK_DTYPE).reshape(-1)
+        self._ck(self.lib.mpm_set_links(self.h, t.size, t.ctypes.data if t.size else None))
+
+    def get_links(self):
+        """mpm_get_links: the table in force, an array of LINK_DTYPE."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_links(self.h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), LINK_DTYPE)
+        self._ck(self.lib.mpm_get_links(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
+    def link_forces(self):
+        """mpm_link_forces: the links' force on the current positions and velocities, (n_verts, 3) float32 in
+        dump_cpu_state's numbering (zeros for vertices without a link)."""
+        out = np.zeros((self.n_verts, 3), np.float32)
+        self._ck(self.lib.mpm_link_forces(self.h, _ptr(out)))
+        return out
+
+    def link_energy(self):
+        """mpm_link_energy: (sum of 1/2 k (l - L)^2 over the links that act, every link's float length (n,) float32)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_links(self.h, None, 0, C.byref(n)))
+        length = np.zeros(int(n.value), np.float32)
+        e = C.c_double()
+        self._ck(self.lib.mpm_link_energy(self.h, C.byref(e), length.ctypes.data if length.size else None))
+        return float(e.value), length
+
+    def links_max_stable_dt(self) -> float:
+        """mpm_links_max_stable_dt: the dt above which the substep entry points refuse (inf while no link is set)."""
+        dt = C.c_float()
+        self._ck(self.lib.mpm_links_max_stable_dt(self.h, C.byref(dt)))
+        return float(dt.value)
+
+    @staticmethod
+    def link_force(link, xa, xb, va, vb):
+        return link_force(link, xa, xb, va, vb)
 
     def measure(self, capacity: int | None = None):
         """mpm_measure: (rows, total) -- one MEASURE_DTYPE record per cloth (the first `capacity` of them if given) and

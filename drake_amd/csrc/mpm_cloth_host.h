@@ -227,6 +227,106 @@ static int bending_forces(mpm_engine* e, float* f_out) {
     return 0;
 }
 
+// ---- links between cloth vertices (mpm_set_links, mpm_get_links, mpm_link_forces, mpm_link_energy,
+// mpm_links_max_stable_dt; mpm_links.h) ----
+// The table `t` with its limit and the caller's links put in force: new device arrays, upload, swap.  The caller has
+// settled the owed substeps.  A failure changes nothing: the new buffers go, the table in force stays.
+static int links_swap(mpm_engine* e, LinkTable& t, float max_dt, size_t n, const mpm_link_t* links) {
+    static_assert(sizeof(LinkRecord) == sizeof(float4) && sizeof(LinkPair) == sizeof(float4), "link record layouts differ");
+    const size_t n_rows = t.row_pid.size();
+    mpm_engine::Links next;
+    FreshArrays fresh(e);
+    if (n_rows) {
+        int* d_row = nullptr;
+        unsigned* d_off = nullptr;
+        float4 *d_ent = nullptr, *d_pair = nullptr;
+        if (int rc = fresh.alloc(&d_row, n_rows, false)) return rc;
+        if (int rc = fresh.alloc(&d_off, t.slice_off.size(), false)) return rc;
+        if (int rc = fresh.alloc(&d_ent, t.ent.size(), false)) return rc;
+        if (int rc = fresh.alloc(&d_pair, t.pair.size(), false)) return rc;
+        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
+        H2D(e, d_row, t.row_pid.data(), n_rows * sizeof(int));
+        H2D(e, d_off, t.slice_off.data(), t.slice_off.size() * sizeof(unsigned));
+        H2D(e, d_ent, t.ent.data(), t.ent.size() * sizeof(float4));
+        H2D(e, d_pair, t.pair.data(), t.pair.size() * sizeof(float4));
+        next.args = LinkArgs{d_row, d_off, d_ent, (int)n_rows};
+        next.d_pair = d_pair;
+    } else {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    {
+        LinkArgs& old = e->links.args;
+        int* o_row = const_cast<int*>(old.row_pid);
+        unsigned* o_off = const_cast<unsigned*>(old.slice_off);
+        float4 *o_ent = const_cast<float4*>(old.ent), *o_pair = const_cast<float4*>(e->links.d_pair);
+        e->dfree(o_row);
+        e->dfree(o_off);
+        e->dfree(o_ent);
+        e->dfree(o_pair);
+    }
+    next.set.assign(links, links + n);
+    next.max_dt = max_dt;
+    e->links = next;
+    fresh.commit();
+    return 0;
+}
+// mpm_set_links in three steps: the table on the host, its limit from the vertices' masses, the swap
+static int set_links(mpm_engine* e, size_t n, const mpm_link_t* links) {
+    static_assert(sizeof(Link) == sizeof(mpm_link_t), "link layouts differ");
+    const Link* L = reinterpret_cast<const Link*>(links);
+    const std::string refusal = link_table_refusal(L, n, e->nv);
+    if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    REQUIRE(e->np < (size_t)1 << 31, "links: too many particles");
+    LinkTable t;
+    std::string why;
+    if (!link_table(L, n, e->nf, e->nv, LINK_SLICE, t, why)) return fail(MPM_ERR_INVALID, why);
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    float max_dt = INFINITY;
+    if (n) {
+        std::vector<float> mass;
+        if (int rc = vertex_masses(e, mass)) return rc;
+        double W, G;
+        link_rates(t, mass.data(), e->nf, &W, &G);
+        max_dt = link_limit(W, G);
+    }
+    return links_swap(e, t, max_dt, n, links);
+}
+
+static int link_forces(mpm_engine* e, float* f_out) {
+    const size_t bytes = e->nv * 12;
+    if (!e->links.on()) {
+        std::memset(f_out, 0, bytes);
+        return 0;
+    }
+    if (int rc = e->stage(bytes)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
+    hipLaunchKernelGGL(k_link_eval, dim3(((unsigned)e->links.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
+                       e->links.args, (float*)e->d_stage);
+    D2H(e, f_out, e->d_stage, bytes);
+    return 0;
+}
+
+// One double term and one float length per link from the device, the terms added here in link order: a fixed order,
+// no atomics (the sums of mpm_measure.h follow the same rule)
+static int link_energy(mpm_engine* e, double* energy_out, float* length_out) {
+    const size_t n = e->links.set.size();
+    double sum = 0.0;
+    if (n) {
+        if (int rc = e->stage(n * 12)) return rc;
+        double* d_term = (double*)e->d_stage;
+        float* d_len = (float*)(d_term + n);
+        hipLaunchKernelGGL(k_link_energy, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, e->stream, e->dp, e->links.d_pair, (int)n,
+                           d_term, d_len);
+        std::vector<double> term(n);
+        D2H(e, term.data(), d_term, n * 8);
+        if (length_out) D2H(e, length_out, d_len, n * 4);
+        for (size_t i = 0; i < n; ++i) sum += term[i];
+    }
+    *energy_out = sum;
+    return 0;
+}
+
 // ---- stiffness-proportional damping (mpm_set_damping, mpm_get_damping, mpm_damping_forces, mpm_damping_max_stable_dt,
 // mpm_damping_face_records; mpm_damping.h) ----
 // mpm_damping_max_stable_dt from what the engine holds: the membrane row sums and vertex masses of the last

@@ -195,6 +195,9 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p) {
     if (e->bend.on() && e->damp.bending())
         hipLaunchKernelGGL(k_bend_damp, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->bend.args,
                            (const float*)e->damp.d_beta_vertex);
+    // (an engine with links, mpm_set_links: f += the seams', springs' and cords' forces, one lane per linked vertex)
+    if (e->links.on())
+        hipLaunchKernelGGL(k_link, dim3(((unsigned)e->links.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->links.args);
 }
 // (mpm_calc_fem_state_and_force: the two FEM kernels, whose forces a caller may read)
 static void launch_fem(mpm_engine* e, const DP& p, float dt) {
@@ -231,8 +234,8 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
 }
 // the vertex forces inside k_p2g, from the vertices' entries of DP::VF (single and partitioned domains alike since round
 // 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch, and so does an engine with bending
-// stiffness, whose k_bend adds to the forces in DP::f
-static int fused_forces(const mpm_engine* e) { return e->max_valence <= 8 && !e->bend.on() ? 1 : 0; }
+// stiffness or links, whose k_bend and k_link add to the forces in DP::f
+static int fused_forces(const mpm_engine* e) { return e->max_valence <= 8 && !e->bend.on() && !e->links.on() ? 1 : 0; }
 // the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins launches it (pins_ready has resolved the
 // table).  Everything after GridToParticle -- the coupled path's watch kernel included -- comes after it on the stream.
 static void launch_pins(mpm_engine* e, const DP& p, float dt) {
@@ -719,7 +722,7 @@ int mpm_sync(mpm_handle_t e) try {
 } MPM_CATCH_ALL
 
 // partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
-// stiffness and no damping (out of scope)
+// stiffness, no damping and no links (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
@@ -732,14 +735,23 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with bending stiffness (mpm_set_bending)");
     if (e->damp.any())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with damping (mpm_set_damping)");
+    if (e->links.on())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with links (mpm_set_links)");
     return 0;
 }
 // An explicit linear drag beyond dt * gamma = 1 reverses the relative velocity: the substep entry points that take a dt
 // refuse it, once per call, before anything is enqueued.  (An engine without a table never gets past the first test.)
 // The same entry points refuse a dt above mpm_bending_max_stable_dt on an engine with bending stiffness: symplectic Euler
 // on the lumped system needs dt * omega <= 2, with Gershgorin's bound on omega^2 (a guard, not a guarantee).  And a dt
-// above mpm_damping_max_stable_dt on an engine with damping: the explicit viscous force needs dt * rho(M^-1 D) <= 2.
+// above mpm_damping_max_stable_dt on an engine with damping: the explicit viscous force needs dt * rho(M^-1 D) <= 2.  And
+// a dt above mpm_links_max_stable_dt on an engine with links: W dt^2 + 2 G dt <= 4 (mpm_links.h; a guard, not a guarantee).
 static int fields_stable(const mpm_engine* e, float dt) {
+    if (e->links.on() && !(dt <= e->links.max_dt)) {
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "links: dt = %g is above the limit mpm_links_max_stable_dt = %g: the explicit link "
+                      "force is unstable -- reduce dt, the stiffness or the damping", (double)dt, (double)e->links.max_dt);
+        return fail(MPM_ERR_INVALID, msg);
+    }
     if (e->damp.any() && !(dt <= e->damp.max_dt)) {
         char msg[200];
         std::snprintf(msg, sizeof msg, "damping: dt = %g is above the limit mpm_damping_max_stable_dt = %g: the explicit damping "
@@ -760,9 +772,10 @@ static int fields_stable(const mpm_engine* e, float dt) {
     return 0;
 }
 // The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
-// takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness or damping is set.
+// takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness, damping or
+// links are set.
 static float quiet_hint(const mpm_engine* e, float seconds) {
-    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() ? seconds : 0.f;
+    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->links.on() ? seconds : 0.f;
 }
 
 // ---- the solver calls -----------------------------------------------------
@@ -2238,6 +2251,45 @@ int mpm_damping_face_records(size_t n_faces, const float* dminv3, const float* v
                              const float* beta, const float* x9, const float* v9, float* rec9_out) try {
     REQUIRE((dminv3 && vol && mu && lambda && beta && x9 && v9 && rec9_out) || n_faces == 0, "null array");
     return damping_face_records(n_faces, dminv3, vol, mu, lambda, beta, x9, v9, rec9_out);
+} MPM_CATCH_ALL
+
+// ---- links between cloth vertices (mpm_cloth_host.h; mpm_links.h) --------------------------------------------------------------
+int mpm_set_links(mpm_handle_t e, size_t n, const mpm_link_t* links) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "links are")) return rc;
+    REQUIRE(n == 0 || links, "null link array");
+    return set_links(e, n, links);
+} MPM_CATCH_ALL
+
+int mpm_get_links(mpm_handle_t e, mpm_link_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    return copy_out(e->links.set, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_link_forces(mpm_handle_t e, float* f_out) try {
+    READY(e);
+    REQUIRE(f_out || e->nv == 0, "null output");
+    return link_forces(e, f_out);
+} MPM_CATCH_ALL
+
+int mpm_link_energy(mpm_handle_t e, double* energy_out, float* length_out) try {
+    READY(e);
+    REQUIRE(energy_out, "null output");
+    return link_energy(e, energy_out, length_out);
+} MPM_CATCH_ALL
+
+int mpm_links_max_stable_dt(mpm_handle_t e, float* dt_out) try {
+    REQUIRE(e && dt_out, "null argument");
+    *dt_out = e->links.on() ? e->links.max_dt : INFINITY;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_link_force(const mpm_link_t* link, const float* xa, const float* xb, const float* va, const float* vb, float* f_on_a) try {
+    REQUIRE(link && xa && xb && va && vb && f_on_a, "null argument");
+    const float d[3] = {xb[0] - xa[0], xb[1] - xa[1], xb[2] - xa[2]}, w[3] = {vb[0] - va[0], vb[1] - va[1], vb[2] - va[2]};
+    link_force(link->stiffness, link->rest_length, link->damping, (link->flags & MPM_LINK_TENSION_ONLY) != 0u, d, w, f_on_a);
+    return 0;
 } MPM_CATCH_ALL
 
 // ---- the per-cloth report (mpm_cloth_host.h; mpm_measure.h) --------------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include "mpm_pins.h"
 #include "mpm_bending.h"
 #include "mpm_damping.h"
+#include "mpm_links.h"
 #include "mpm_measure.h"
 #include "mpm_grid_bodies.h"
 #include "mpm_team.h"
@@ -243,6 +244,14 @@ struct mpm_engine {
             return false;
         }
     } damp;
+    // links between cloth vertices (mpm_set_links; mpm_links.h): a non-empty table switches k_link on behind k_vforce
+    struct Links {
+        std::vector<mpm_link_t> set;     // the caller's table, as given
+        LinkArgs args{};                 // ... as k_link reads it (device memory, in `allocs`)
+        const float4* d_pair = nullptr;  // [link] k_link_energy's records
+        float max_dt = INFINITY;         // the positive root of W dt^2 + 2 G dt = 4 (fields_stable)
+        bool on() const { return args.n_rows > 0; }
+    } links;
     // the per-cloth report (mpm_measure, mpm_face_strain; mpm_measure.h): chunk table and scratch, made at first use
     struct Measure {
         bool built = false;
@@ -486,7 +495,7 @@ static bool is_rotation(const float* R) {
                        (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
     return std::fabs(det - 1.0) <= 1e-4;
 }
-// pins, grid bodies, force fields, bending stiffness and damping are refused on a partitioned or multi-rank engine (out of scope);
+// pins, grid bodies, force fields, bending stiffness, damping and links are refused on a partitioned or multi-rank engine (out of scope);
 // what_is: "pins are", "bending stiffness is", ...
 static int single_engine_only(const mpm_engine* e, const char* what_is) {
     if (e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on)

@@ -246,6 +246,44 @@ struct GpuMpmState {
         mpm_check(mpm_damping_face_records(n, dminv3, vol, mu, lambda, beta, x9, v9, rec.data()));
         return rec;
     }
+    // Extension: links between cloth vertices (mpm_set_links) -- seams, springs, tension-only cords; an empty vector
+    // clears them.  A synchronisation point, like SetBending.
+    void SetLinks(const std::vector<mpm_link_t>& links) { mpm_check(mpm_set_links(h_, links.size(), links.data())); }
+    std::vector<mpm_link_t> GetLinks() const {
+        size_t n = 0;
+        mpm_check(mpm_get_links(h_, nullptr, 0, &n));
+        std::vector<mpm_link_t> out(n);
+        mpm_check(mpm_get_links(h_, out.data(), n, &n));
+        return out;
+    }
+    // the links' force on the current positions and velocities, 3 floats per vertex in the numbering of DumpCpuState
+    std::vector<float> LinkForces(size_t n_verts) const {
+        std::vector<float> f(3 * n_verts);
+        mpm_check(mpm_link_forces(h_, f.data()));
+        return f;
+    }
+    // sum of 1/2 k (l - L)^2 over the links that act; `lengths`, if given, receives every link's float length
+    double LinkEnergy(std::vector<float>* lengths = nullptr) const {
+        double e = 0.0;
+        if (lengths) {
+            size_t n = 0;
+            mpm_check(mpm_get_links(h_, nullptr, 0, &n));
+            lengths->resize(n);
+        }
+        mpm_check(mpm_link_energy(h_, &e, lengths && !lengths->empty() ? lengths->data() : nullptr));
+        return e;
+    }
+    // the dt above which the substep entry points refuse an engine with links (+inf while the table is empty)
+    float LinksMaxStableDt() const {
+        float dt = 0.f;
+        mpm_check(mpm_links_max_stable_dt(h_, &dt));
+        return dt;
+    }
+    // one link's force on its end a, on the host: see mpm_link_force
+    static void LinkForce(const mpm_link_t& link, const float xa[3], const float xb[3], const float va[3], const float vb[3],
+                          float f_on_a[3]) {
+        mpm_check(mpm_link_force(&link, xa, xb, va, vb, f_on_a));
+    }
     // Extension: the per-cloth report (mpm_measure) -- masses, momenta, kinetic, potential, elastic and bending energies,
     // strain extremes, reduced on the device in double.  One row per cloth; `total`, if given, receives their sum.
     // System::CalcKineticEnergy is total.kinetic + total.kinetic_affine, CalcPotentialEnergy is gravity_potential +

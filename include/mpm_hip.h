@@ -855,6 +855,65 @@ MPM_API int mpm_damping_face_records(size_t n_faces, const float *dminv3, const 
                                      const float *lambda, const float *beta, const float *x9, const float *v9,
                                      float *rec9_out);
 
+/* ---- Links between cloth vertices: seams, springs and tension-only cords (an extension) ----
+ * Every mpm_add_qr_cloth* call makes an island; pins are hard constraints to rigid bodies only.  A link joins two
+ * distinct cloth vertices a, b -- of one cloth or of two -- by a damped spring: panels sewn into a garment, a sheet laced
+ * to another, a banner hung by cords, a tether that stops a flap at a length.  Ids are in the vertex numbering of
+ * mpm_dump_cpu_state, over all cloths.  With d = x_b - x_a and w = v_b - v_a, in float, the force on a is
+ *   seam   (rest_length L == 0)  f_j = fma(k, d_j, c w_j): linear and isotropic, no square root, no singular configuration
+ *   spring (L > 0)               l2 = fma(d2, d2, fma(d1, d1, d0 d0)), l = sqrt(l2), s = fma(w2, d2, fma(w1, d1, w0 d0)) / l,
+ *                                t = fma(c, s, k (l - L)), g = t / l, f_j = g d_j; nothing where l2 < 1e-30
+ *   MPM_LINK_TENSION_ONLY        nothing unless l > L (a cord): the elastic and the damping part are gated together
+ * and the force on b is its negative -- bit for bit: every intermediate is even or odd in (d, w), the square root and
+ * both divisions are correctly rounded whatever mpm_set_fast_math says, no product is contracted.  A vertex's links are
+ * added in link order by one lane, without atomics: the result is the same bits whatever the particle order, and the
+ * links' total force is zero within the rounding of those additions.  Duplicate pairs are allowed; each is a link of
+ * its own.  Elastic energy of a link that acts: 1/2 k (l - L)^2.  A seam of n stitches that should act as one spring of
+ * stiffness K takes k = K / n per link.
+ * The force joins the vertex forces of CalcFemStateAndForce (MPM_ARR_FORCES includes it; its kernel runs behind the
+ * vertex-force, bending and bending-damping kernels and counts under MPM_PHASE_VFORCE).  It works with pins, per-cloth
+ * materials, grid bodies, force fields, bending, damping, deterministic mode, fast math and the coupled path.
+ * mpm_set_links replaces the table (n = 0 clears it, links may then be NULL); it needs mpm_finalize, is ordered on the
+ * engine's stream and is a synchronisation point; substeps that mpm_run_substeps still owes are run first, with the
+ * table they were enqueued with.  With an empty table the engine launches exactly what it launches without this call.
+ * While links are set the engine does not use the re-sort's quiet-time estimate to omit re-sort check launches, and
+ * every batched substep launches the vertex-force kernel.
+ * Stability: symplectic Euler on a damped oscillator, v' = v + dt (-W x - G v), x' = x + dt v', is stable iff
+ * W dt^2 + 2 G dt <= 4.  With Gershgorin's bounds on the lumped system, W = max_i (2 / m_i) sum_j k_ij and
+ * G = max_i (2 / m_i) sum_j c_ij over vertex i's links, m_i the vertex particle's mass as of mpm_set_links,
+ * mpm_links_max_stable_dt is the positive root of that quadratic (2 / G where W = 0), and the entry points that check
+ * mpm_bending_max_stable_dt also return MPM_ERR_INVALID, before anything is enqueued, for a dt above it.  A guard, not a
+ * guarantee: a compressed spring with L > 0 has a transverse (geometric) stiffness k (L - l) / l that the bound does
+ * not cover, and the grid shares a vertex's impulse with the faces around it.  +inf while the table is empty.
+ * Refused with MPM_ERR_INVALID, the previous table staying in force and nothing enqueued: a call before mpm_finalize; a
+ * or b >= the vertex count; a == b; a stiffness, rest_length or damping that is negative or not finite; unknown flags; a
+ * table that does not fit 2^31 records; any partitioned or multi-rank engine -- this call on such an engine, and
+ * mpm_dist_init, the halo, chain, team and world substeps on an engine with links. */
+#define MPM_LINK_TENSION_ONLY 1u   /* acts only while length > rest_length (a cord) */
+typedef struct mpm_link {
+    uint32_t a, b;       /* the two vertices, distinct */
+    float stiffness;     /* k, N/m,   >= 0 */
+    float rest_length;   /* L, m,     >= 0; 0 is a seam */
+    float damping;       /* c, N s/m, >= 0 */
+    uint32_t flags;      /* MPM_LINK_TENSION_ONLY */
+} mpm_link_t;
+MPM_API int mpm_set_links(mpm_handle_t h, size_t n, const mpm_link_t *links);
+/* The table as given: min(n, capacity) entries into out (may be NULL when capacity is 0), n into *n_out. */
+MPM_API int mpm_get_links(mpm_handle_t h, mpm_link_t *out, size_t capacity, size_t *n_out);
+/* The links' force on the current positions and velocities: f_out[3 * n_verts], in the vertex numbering of
+ * mpm_dump_cpu_state (zeros for vertices without a link).  The device function of the substep's kernel; changes no state. */
+MPM_API int mpm_link_forces(mpm_handle_t h, float *f_out);
+/* Sum of 1/2 k (l - L)^2 over the links that act (the gates above, decided on the float differences), every term formed
+ * in double from the float positions on the device, the terms added in link order, without atomics: the same bits
+ * whatever the particle order.  length_out (n links, may be NULL): every link's length, acting or not, formed in double and rounded to float once.  This
+ * energy is not part of mpm_measure's record.  Changes no state. */
+MPM_API int mpm_link_energy(mpm_handle_t h, double *energy_out, float *length_out);
+MPM_API int mpm_links_max_stable_dt(mpm_handle_t h, float *dt_out);
+/* The force of one link on its end a, on the host (no handle, no device): the inline function the link kernel calls,
+ * compiled for the host.  xa, xb, va, vb, f_on_a: 3 floats each.  The link is not validated (a and b are not read). */
+MPM_API int mpm_link_force(const mpm_link_t *link, const float xa[3], const float xb[3], const float va[3], const float vb[3],
+                           float f_on_a[3]);
+
 /* ---- Energy, momentum and strain report per cloth (an extension) ----
  * What System::CalcKineticEnergy / CalcPotentialEnergy answer for a Drake plant, and what a caller choosing dt or
  * calibrating a stiffness needs: one device-side reduction instead of seven downloads and a host restatement of the
@@ -878,6 +937,8 @@ MPM_API int mpm_damping_face_records(size_t n_faces, const float *dminv3, const 
  *   bending E = -1/4 sum_i sum_{j != i} c_ij |x_j - x_i|^2 with c_ij the float coefficients of the table the bending
  *           kernel reads (= 1/2 x^T k Q x: Q is symmetric with zero row sums), per cloth; 0 while bending is off.
  *   The potentials of force fields (mpm_set_force_fields) are NOT reported: most of them (drag, wind) have none.
+ *   The elastic energy of the links (mpm_set_links) is NOT in this record either, whose layout is unchanged: links join
+ *   cloths, so it belongs to no row; mpm_link_energy reports it.
  * gravity_potential is -sum m g x[gravity_axis] with g = mpm_material_t::gravity (signed) -- zero at the world origin.
  * The sums are formed in ORIGINAL id order in a fixed tree, without floating-point atomics: a row is the same bits
  * whatever the particle order (slot order, arrival order inside a cell, deterministic mode on or off). */
