@@ -12,10 +12,10 @@
 // Host: bending_matrix assembles Q of one cloth in double (mpm_bending_matrix), bending_table lays the table of all
 // cloths out (mpm_set_bending, whose device half is in mpm_cloth_host.h).  Device: k_bend, one lane per vertex of
 // the cloths with k > 0, adds f to the vertex forces k_vforce left in DP::f (launch_fem_vertices); k_bend_eval writes
-// the same numbers into a buffer in original vertex order (mpm_bending_forces).  The table is k Q without its diagonal,
-// as (float coefficient, particle id of the column) records in sliced ELL: slices of 64 rows, a slice's records column-
-// major (record e of the slice's lane l at slice_off + 64 e + l: a wave reads 512 contiguous bytes per step), a slice
-// as wide as its longest row, shorter rows padded with (0, the row's own id).  Any valence is the same path.
+// the same numbers into a buffer in original vertex order (mpm_bending_forces).  The table is a vertex row table
+// (mpm_row_table.h: sliced ELL, slices of 64 rows) of k Q without its diagonal: a record is (float coefficient, int bits
+// of the column's particle id), 8 bytes -- a wave reads 512 contiguous bytes per step --, the padding record is (0, the
+// row's own id).  Any valence is the same path.
 //
 // A row is evaluated as f_i = sum_j -c_ij (x_j - x_i), in stored (ascending column) order, one fused multiply-add per
 // component and entry: the diagonal is -sum_j c_ij because the rows sum to zero, and differences against the row's own
@@ -36,6 +36,8 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+
+#include "mpm_row_table.h"
 
 #ifdef __HIPCC__
 #include "mpm_step.h"
@@ -230,14 +232,11 @@ inline bool bending_matrix(const float* pos, size_t n_verts, const int32_t* idx,
 }
 
 // The table k_bend reads, as the host lays it out (no device is touched): one row per vertex of the cloths with k > 0, in
-// ascending vertex id, k folded in, the diagonal dropped, in sliced ELL as described above.
+// ascending vertex id, k folded in, the diagonal dropped, laid out by sliced_ell (mpm_row_table.h).
 struct BendRecord {
     float coef, pid_bits;   // BendArgs::ent's float2: (coefficient, int bits of the column's particle id)
 };
-struct BendTable {
-    std::vector<int> row_pid;          // [row] particle id (nf + vertex) of the row's vertex
-    std::vector<unsigned> slice_off;   // [slices + 1]
-    std::vector<BendRecord> ent;
+struct BendTable : RowTable<BendRecord> {
     std::vector<double> abs_sum;       // [row] sum_j |k Q_ij|, the diagonal included
 };
 // cloths: anything with first_vertex, n_verts, first_face, n_faces; h_pos: the rest positions, h_idx: the faces' vertex
@@ -273,27 +272,11 @@ inline bool bending_table(const std::vector<Cloth>& cloths, const float* h_pos, 
             out.abs_sum.push_back(a);
         }
     }
-    const size_t n_rows = out.row_pid.size(), n_slices = (n_rows + slice - 1) / slice;
-    out.slice_off.assign(n_slices + 1, 0u);
-    for (size_t s = 0; s < n_slices; ++s) {
-        size_t width = 0;
-        for (size_t r = s * slice; r < std::min(n_rows, (s + 1) * slice); ++r) width = std::max(width, rows[r].size());
-        if (!((size_t)out.slice_off[s] + width * slice < (size_t)1 << 31)) {
-            why = "bending: the table is too large";
-            return false;
-        }
-        out.slice_off[s + 1] = out.slice_off[s] + (unsigned)(width * slice);
-    }
-    out.ent.resize(out.slice_off[n_slices]);
-    for (size_t s = 0; s < n_slices; ++s) {
-        const size_t width = (out.slice_off[s + 1] - out.slice_off[s]) / slice;
-        for (size_t l = 0; l < slice; ++l) {
-            const size_t r = s * slice + l;
-            // (padding: coefficient 0 and the row's own id; the lanes past the last row are never read)
-            const int own = r < n_rows ? out.row_pid[r] : out.row_pid[n_rows - 1];
-            for (size_t q = 0; q < width; ++q)
-                out.ent[out.slice_off[s] + q * slice + l] = r < n_rows && q < rows[r].size() ? rows[r][q] : BendRecord{0.f, id_bits(own)};
-        }
+    // (padding: coefficient 0 and the row's own id)
+    if (!sliced_ell(rows.size(), slice, [&](size_t r) { return rows[r].size(); }, [&](size_t r, size_t q) { return rows[r][q]; },
+                    [&](size_t r) { return BendRecord{0.f, id_bits(out.row_pid[r])}; }, out.slice_off, out.ent)) {
+        why = "bending: the table is too large";
+        return false;
     }
     return true;
 }

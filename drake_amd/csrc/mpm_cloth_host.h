@@ -1,5 +1,5 @@
-// Host side of the per-cloth features: cloth materials, external force fields, bending stiffness, damping and the
-// per-cloth report -- what the entry points in mpm_engine.hip call once their arguments are checked.
+// Host side of the per-cloth features: cloth materials, external force fields, row tables, bending stiffness, links,
+// damping and the per-cloth report -- what the entry points in mpm_engine.hip call once their arguments are checked.
 // Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
 #pragma once
 #include "mpm_host.h"
@@ -98,6 +98,56 @@ static int force_field_accelerations(const mpm_force_field_t* fields, size_t n_f
     return 0;
 }
 
+// ---- vertex row tables on the device (mpm_row_table.h): what bending, hinge damping and links share ----
+// one lane per row, 256 to a block
+static dim3 rows_grid(int n_rows) { return dim3(((unsigned)n_rows + 255u) / 256u); }
+// A table's three arrays as new device arrays in `fresh`, and `out` (BendArgs, LinkArgs) filled; a table without rows
+// leaves `out` empty.  Stream-ordered, and a synchronisation point either way: the kernels enqueued so far have read the
+// old table.  (A table whose rows all have width 0 has no record to copy: a cloth with k > 0 and no hinge.)
+template <class Args, class Record>
+static int rows_upload(mpm_engine* e, FreshArrays& fresh, const RowTable<Record>& t, Args* out) {
+    static_assert(sizeof(Record) == sizeof(*out->ent), "record layouts differ");
+    *out = Args{};
+    if (t.row_pid.empty()) {
+        HIP_TRY(hipStreamSynchronize(e->stream));
+        return 0;
+    }
+    int* d_row = nullptr;
+    unsigned* d_off = nullptr;
+    Record* d_ent = nullptr;
+    if (int rc = fresh.alloc(&d_row, t.row_pid.size(), false)) return rc;
+    if (int rc = fresh.alloc(&d_off, t.slice_off.size(), false)) return rc;
+    if (int rc = fresh.alloc(&d_ent, t.ent.size(), false)) return rc;
+    H2D(e, d_row, t.row_pid.data(), t.row_pid.size() * sizeof(int));
+    H2D(e, d_off, t.slice_off.data(), t.slice_off.size() * sizeof(unsigned));
+    if (!t.ent.empty()) H2D(e, d_ent, t.ent.data(), t.ent.size() * sizeof(Record));
+    *out = Args{d_row, d_off, reinterpret_cast<decltype(out->ent)>(d_ent), (int)t.row_pid.size()};
+    return 0;
+}
+// ... and the arrays of the table that was in force released (the caller assigns the new one)
+template <class Args>
+static void rows_free(mpm_engine* e, const Args& a) {
+    void *row = (void*)a.row_pid, *off = (void*)a.slice_off, *ent = (void*)a.ent;   // (dfree looks the address up)
+    e->dfree(row);
+    e->dfree(off);
+    e->dfree(ent);
+}
+// mpm_bending_forces, mpm_link_forces: a table's rows on the current state through its *_eval kernel, in original vertex
+// order; zero for the vertices without a row, and for all of them where the table is empty
+template <class Args>
+static int rows_eval(mpm_engine* e, void (*kernel)(DP, Args, float*), const Args& a, float* f_out) {
+    const size_t bytes = e->nv * 12;
+    if (a.n_rows <= 0) {
+        std::memset(f_out, 0, bytes);
+        return 0;
+    }
+    if (int rc = e->stage(bytes)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
+    hipLaunchKernelGGL(kernel, rows_grid(a.n_rows), dim3(256), 0, e->stream, e->dp, a, (float*)e->d_stage);
+    D2H(e, f_out, e->d_stage, bytes);
+    return 0;
+}
+
 // ---- bending stiffness (mpm_set_bending, mpm_get_bending, mpm_bending_forces, mpm_bending_max_stable_dt,
 // mpm_bending_matrix; mpm_bending.h) ----
 static void damping_limit(mpm_engine* e);
@@ -145,44 +195,17 @@ static int vertex_masses(mpm_engine* e, std::vector<float>& mass, std::vector<fl
 // mpm_bending_max_stable_dt of a table (bending_table's rows) on the vertices' masses: symplectic Euler on the lumped
 // system needs dt * omega <= 2, with Gershgorin's bound omega^2 <= max_i (1 / m_i) sum_j |k Q_ij|
 static float bending_limit(const BendTable& t, const std::vector<float>& mass, size_t nf) {
-    double w2 = 0.0;
-    for (size_t r = 0; r < t.row_pid.size(); ++r) {
-        const double m = (double)mass[(size_t)t.row_pid[r] - nf];
-        if (t.abs_sum[r] > 0.0) w2 = std::max(w2, m > 0.0 ? t.abs_sum[r] / m : (double)INFINITY);
-    }
-    return stable_dt_limit(std::sqrt(w2));
+    return stable_dt_limit(std::sqrt(max_row_rate(t.abs_sum.data(), t.row_pid.size(), 1.0,
+                                                  [&](size_t r) { return mass[(size_t)t.row_pid[r] - nf]; })));
 }
 // The table `t` with its limit and the caller's stiffnesses put in force: new device arrays, upload, swap.  The caller has
 // settled the owed substeps.  A failure changes nothing: the new buffers go, the table in force stays.
 static int bending_swap(mpm_engine* e, BendTable& t, float max_dt, size_t n_cloths, const float* stiffness) {
-    static_assert(sizeof(BendRecord) == sizeof(float2), "bending record layouts differ");
     const size_t n_rows = t.row_pid.size();
     mpm_engine::Bending next;
     FreshArrays fresh(e);
-    if (n_rows) {
-        int* d_row = nullptr;
-        unsigned* d_off = nullptr;
-        float2* d_ent = nullptr;
-        if (int rc = fresh.alloc(&d_row, n_rows, false)) return rc;
-        if (int rc = fresh.alloc(&d_off, t.slice_off.size(), false)) return rc;
-        if (int rc = fresh.alloc(&d_ent, t.ent.size(), false)) return rc;
-        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
-        H2D(e, d_row, t.row_pid.data(), n_rows * sizeof(int));
-        H2D(e, d_off, t.slice_off.data(), t.slice_off.size() * sizeof(unsigned));
-        if (!t.ent.empty()) H2D(e, d_ent, t.ent.data(), t.ent.size() * sizeof(float2));
-        next.args = BendArgs{d_row, d_off, d_ent, (int)n_rows};
-    } else {
-        HIP_TRY(hipStreamSynchronize(e->stream));
-    }
-    {
-        BendArgs& old = e->bend.args;
-        int* o_row = const_cast<int*>(old.row_pid);
-        unsigned* o_off = const_cast<unsigned*>(old.slice_off);
-        float2* o_ent = const_cast<float2*>(old.ent);
-        e->dfree(o_row);
-        e->dfree(o_off);
-        e->dfree(o_ent);
-    }
+    if (int rc = rows_upload(e, fresh, t, &next.args)) return rc;
+    rows_free(e, e->bend.args);
     next.k.assign(stiffness, stiffness + n_cloths);
     next.max_dt = max_dt;
     next.row_vertex.resize(n_rows);
@@ -213,57 +236,26 @@ static int set_bending(mpm_engine* e, size_t n_cloths, const float* stiffness) {
     return 0;
 }
 
-static int bending_forces(mpm_engine* e, float* f_out) {
-    const size_t bytes = e->nv * 12;
-    if (!e->bend.on()) {
-        std::memset(f_out, 0, bytes);
-        return 0;
-    }
-    if (int rc = e->stage(bytes)) return rc;
-    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
-    hipLaunchKernelGGL(k_bend_eval, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
-                       e->bend.args, (float*)e->d_stage);
-    D2H(e, f_out, e->d_stage, bytes);
-    return 0;
-}
+static int bending_forces(mpm_engine* e, float* f_out) { return rows_eval(e, k_bend_eval, e->bend.args, f_out); }
 
 // ---- links between cloth vertices (mpm_set_links, mpm_get_links, mpm_link_forces, mpm_link_energy,
 // mpm_links_max_stable_dt; mpm_links.h) ----
 // The table `t` with its limit and the caller's links put in force: new device arrays, upload, swap.  The caller has
 // settled the owed substeps.  A failure changes nothing: the new buffers go, the table in force stays.
 static int links_swap(mpm_engine* e, LinkTable& t, float max_dt, size_t n, const mpm_link_t* links) {
-    static_assert(sizeof(LinkRecord) == sizeof(float4) && sizeof(LinkPair) == sizeof(float4), "link record layouts differ");
-    const size_t n_rows = t.row_pid.size();
+    static_assert(sizeof(LinkPair) == sizeof(float4), "link record layouts differ");
     mpm_engine::Links next;
     FreshArrays fresh(e);
-    if (n_rows) {
-        int* d_row = nullptr;
-        unsigned* d_off = nullptr;
-        float4 *d_ent = nullptr, *d_pair = nullptr;
-        if (int rc = fresh.alloc(&d_row, n_rows, false)) return rc;
-        if (int rc = fresh.alloc(&d_off, t.slice_off.size(), false)) return rc;
-        if (int rc = fresh.alloc(&d_ent, t.ent.size(), false)) return rc;
-        if (int rc = fresh.alloc(&d_pair, t.pair.size(), false)) return rc;
-        // (stream-ordered, and a synchronisation point: the kernels enqueued so far have read the old table)
-        H2D(e, d_row, t.row_pid.data(), n_rows * sizeof(int));
-        H2D(e, d_off, t.slice_off.data(), t.slice_off.size() * sizeof(unsigned));
-        H2D(e, d_ent, t.ent.data(), t.ent.size() * sizeof(float4));
-        H2D(e, d_pair, t.pair.data(), t.pair.size() * sizeof(float4));
-        next.args = LinkArgs{d_row, d_off, d_ent, (int)n_rows};
+    if (int rc = rows_upload(e, fresh, t, &next.args)) return rc;
+    if (n) {   // (k_link_energy's records, behind the table's)
+        float4* d_pair = nullptr;
+        if (int rc = fresh.alloc(&d_pair, n, false)) return rc;
+        H2D(e, d_pair, t.pair.data(), n * sizeof(float4));
         next.d_pair = d_pair;
-    } else {
-        HIP_TRY(hipStreamSynchronize(e->stream));
     }
-    {
-        LinkArgs& old = e->links.args;
-        int* o_row = const_cast<int*>(old.row_pid);
-        unsigned* o_off = const_cast<unsigned*>(old.slice_off);
-        float4 *o_ent = const_cast<float4*>(old.ent), *o_pair = const_cast<float4*>(e->links.d_pair);
-        e->dfree(o_row);
-        e->dfree(o_off);
-        e->dfree(o_ent);
-        e->dfree(o_pair);
-    }
+    rows_free(e, e->links.args);
+    float4* o_pair = const_cast<float4*>(e->links.d_pair);
+    e->dfree(o_pair);
     next.set.assign(links, links + n);
     next.max_dt = max_dt;
     e->links = next;
@@ -293,19 +285,7 @@ static int set_links(mpm_engine* e, size_t n, const mpm_link_t* links) {
     return links_swap(e, t, max_dt, n, links);
 }
 
-static int link_forces(mpm_engine* e, float* f_out) {
-    const size_t bytes = e->nv * 12;
-    if (!e->links.on()) {
-        std::memset(f_out, 0, bytes);
-        return 0;
-    }
-    if (int rc = e->stage(bytes)) return rc;
-    HIP_TRY(hipMemsetAsync(e->d_stage, 0, bytes, e->stream));
-    hipLaunchKernelGGL(k_link_eval, dim3(((unsigned)e->links.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
-                       e->links.args, (float*)e->d_stage);
-    D2H(e, f_out, e->d_stage, bytes);
-    return 0;
-}
+static int link_forces(mpm_engine* e, float* f_out) { return rows_eval(e, k_link_eval, e->links.args, f_out); }
 
 // One double term and one float length per link from the device, the terms added here in link order: a fixed order,
 // no atomics (the sums of mpm_measure.h follow the same rule)
@@ -347,10 +327,7 @@ static void damping_limit(mpm_engine* e) {
             dm.bend_rows = true;
             D[v] += (double)beta * e->bend.abs_sum[r];
         }
-    double worst = 0.0;
-    for (size_t i = 0; i < e->nv; ++i)
-        if (D[i] > 0.0) worst = std::max(worst, dm.mass[i] > 0.0 ? D[i] / dm.mass[i] : (double)INFINITY);
-    dm.max_dt = stable_dt_limit(worst);
+    dm.max_dt = stable_dt_limit(max_row_rate(D.data(), e->nv, 1.0, [&](size_t i) { return dm.mass[i]; }));
 }
 // Puts the coefficients `d` (checked; one per cloth, or none) in force: k_damp's tables, k_bend_damp's coefficient per
 // vertex (it reads the bending table in force) and the stability limit.  The caller has settled the owed substeps.  A
@@ -439,8 +416,8 @@ static int damping_forces(mpm_engine* e, float* f_out) {
         hipLaunchKernelGGL(k_damp_eval, dim3((unsigned)((e->nf + 255) / 256)), dim3(256), 0, e->stream, e->dp, e->damp.args,
                            (float*)e->d_stage);
     if (hinges)
-        hipLaunchKernelGGL(k_bend_damp_eval, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, e->dp,
-                           e->bend.args, (const float*)e->damp.d_beta_vertex, (float*)e->d_stage + n_rec);
+        hipLaunchKernelGGL(k_bend_damp_eval, rows_grid(e->bend.args.n_rows), dim3(256), 0, e->stream, e->dp, e->bend.args,
+                           (const float*)e->damp.d_beta_vertex, (float*)e->d_stage + n_rec);
     HIP_TRY(hipGetLastError());
     std::vector<float> h(n_all);
     D2H(e, h.data(), e->d_stage, n_all * 4);

@@ -189,15 +189,13 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p) {
     TraceRange tr("mpm:CalcFemStateAndForce (vertex forces)");
     if (e->nv) hipLaunchKernelGGL(k_vforce, dim3((e->g_nv + 7u) & ~7u), dim3(256), 0, e->stream, p);
     // (an engine with bending stiffness, mpm_set_bending: f += -k Q x on the forces k_vforce has just written)
-    if (e->bend.on())
-        hipLaunchKernelGGL(k_bend, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->bend.args);
+    if (e->bend.on()) hipLaunchKernelGGL(k_bend, rows_grid(e->bend.args.n_rows), dim3(256), 0, e->stream, p, e->bend.args);
     // (... and with bending damping, mpm_set_damping: f += -beta k Q v from the same table)
     if (e->bend.on() && e->damp.bending())
-        hipLaunchKernelGGL(k_bend_damp, dim3(((unsigned)e->bend.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->bend.args,
+        hipLaunchKernelGGL(k_bend_damp, rows_grid(e->bend.args.n_rows), dim3(256), 0, e->stream, p, e->bend.args,
                            (const float*)e->damp.d_beta_vertex);
     // (an engine with links, mpm_set_links: f += the seams', springs' and cords' forces, one lane per linked vertex)
-    if (e->links.on())
-        hipLaunchKernelGGL(k_link, dim3(((unsigned)e->links.args.n_rows + 255u) / 256u), dim3(256), 0, e->stream, p, e->links.args);
+    if (e->links.on()) hipLaunchKernelGGL(k_link, rows_grid(e->links.args.n_rows), dim3(256), 0, e->stream, p, e->links.args);
 }
 // (mpm_calc_fem_state_and_force: the two FEM kernels, whose forces a caller may read)
 static void launch_fem(mpm_engine* e, const DP& p, float dt) {
@@ -739,6 +737,13 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with links (mpm_set_links)");
     return 0;
 }
+// the refusal of a dt above a feature's mpm_<feature>_max_stable_dt (fields_stable)
+static int dt_above_limit(float dt, float max_dt, const char* feature, const char* force, const char* reduce) {
+    char msg[200];
+    std::snprintf(msg, sizeof msg, "%s: dt = %g is above the limit mpm_%s_max_stable_dt = %g: the explicit %s force is unstable -- "
+                  "reduce %s", feature, (double)dt, feature, (double)max_dt, force, reduce);
+    return fail(MPM_ERR_INVALID, msg);
+}
 // An explicit linear drag beyond dt * gamma = 1 reverses the relative velocity: the substep entry points that take a dt
 // refuse it, once per call, before anything is enqueued.  (An engine without a table never gets past the first test.)
 // The same entry points refuse a dt above mpm_bending_max_stable_dt on an engine with bending stiffness: symplectic Euler
@@ -746,25 +751,10 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
 // above mpm_damping_max_stable_dt on an engine with damping: the explicit viscous force needs dt * rho(M^-1 D) <= 2.  And
 // a dt above mpm_links_max_stable_dt on an engine with links: W dt^2 + 2 G dt <= 4 (mpm_links.h; a guard, not a guarantee).
 static int fields_stable(const mpm_engine* e, float dt) {
-    if (e->links.on() && !(dt <= e->links.max_dt)) {
-        char msg[200];
-        std::snprintf(msg, sizeof msg, "links: dt = %g is above the limit mpm_links_max_stable_dt = %g: the explicit link "
-                      "force is unstable -- reduce dt, the stiffness or the damping", (double)dt, (double)e->links.max_dt);
-        return fail(MPM_ERR_INVALID, msg);
-    }
-    if (e->damp.any() && !(dt <= e->damp.max_dt)) {
-        char msg[200];
-        std::snprintf(msg, sizeof msg, "damping: dt = %g is above the limit mpm_damping_max_stable_dt = %g: the explicit damping "
-                      "force is unstable -- reduce dt or the coefficients", (double)dt, (double)e->damp.max_dt);
-        return fail(MPM_ERR_INVALID, msg);
-    }
-    if (e->bend.on() && !(dt <= e->bend.max_dt))
-    {
-        char msg[200];
-        std::snprintf(msg, sizeof msg, "bending: dt = %g is above the limit mpm_bending_max_stable_dt = %g: the explicit bending "
-                      "force is unstable -- reduce dt or the stiffness", (double)dt, (double)e->bend.max_dt);
-        return fail(MPM_ERR_INVALID, msg);
-    }
+    if (e->links.on() && !(dt <= e->links.max_dt))
+        return dt_above_limit(dt, e->links.max_dt, "links", "link", "dt, the stiffness or the damping");
+    if (e->damp.any() && !(dt <= e->damp.max_dt)) return dt_above_limit(dt, e->damp.max_dt, "damping", "damping", "dt or the coefficients");
+    if (e->bend.on() && !(dt <= e->bend.max_dt)) return dt_above_limit(dt, e->bend.max_dt, "bending", "bending", "dt or the stiffness");
     if (e->force_fields.empty()) return 0;
     if (!((double)dt * e->force_fields_gamma <= 1.0))
         return fail(MPM_ERR_INVALID, "force fields: dt * (sum of gamma over the linear drag fields) = " +

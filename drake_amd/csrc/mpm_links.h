@@ -15,13 +15,12 @@
 // sums of the stability guard.  Device: k_link, one lane per vertex with at least one link, adds to the vertex forces
 // k_vforce (and k_bend, k_bend_damp) left in DP::f (launch_fem_vertices); k_link_eval writes the same numbers into a
 // buffer in original vertex order (mpm_link_forces); k_link_energy forms one double term and one float length per link
-// (mpm_link_energy).  The table has one row per linked vertex, in ascending vertex id; a row's entries are that vertex's
-// links in link order, so a link appears in two rows.  An entry is one 16-byte record (the other end's particle id with
-// the tension-only flag in bit 31, which an id cannot use; k; L; c -- the caller's floats, no host rounding enters), in
-// sliced ELL exactly as the bending table: slices of 64 rows, a slice's records column-major (record e of the slice's
-// lane l at slice_off + 64 e + l: a wave reads 1 KiB of contiguous records per step), a slice as wide as its longest
-// row, shorter rows padded with (the row's own id, 0, 0, 0), which is an exact zero through the seam branch.  Table and
-// order are those of the original vertex ids: the result is the same bits whatever the particle order.
+// (mpm_link_energy).  The table is a vertex row table (mpm_row_table.h: sliced ELL, slices of 64 rows) with one row per
+// linked vertex; a row's entries are that vertex's links in link order, so a link appears in two rows.  An entry is one
+// 16-byte record (the other end's particle id with the tension-only flag in bit 31, which an id cannot use; k; L; c --
+// the caller's floats, no host rounding enters): a wave reads 1 KiB of contiguous records per step.  The padding record
+// is (the row's own id, 0, 0, 0), an exact zero through the seam branch.  Table and order are those of the original
+// vertex ids: the result is the same bits whatever the particle order.
 //
 // Roundings of one component of one link's force, for the bound of tests/links.py (first order, in units of 2^-24 of
 // S = k (l + L) + c |w|; the cancellation in l - L is at the scale of l + L, not of the stretch):
@@ -43,6 +42,8 @@
 #include <algorithm>
 #include <string>
 #include <vector>
+
+#include "mpm_row_table.h"
 
 #ifdef __HIPCC__
 #define MPM_LINK_FN __host__ __device__ inline
@@ -249,10 +250,7 @@ struct LinkPair {
     uint32_t a, b;        // the ends' particle ids, b's | LINK_FLAG_BIT for a tension-only link
     float k, L;           // k_link_energy's float4
 };
-struct LinkTable {
-    std::vector<int> row_pid;          // [row] particle id (nf + vertex) of the row's vertex, ascending
-    std::vector<unsigned> slice_off;   // [slices + 1]
-    std::vector<LinkRecord> ent;
+struct LinkTable : RowTable<LinkRecord> {
     std::vector<LinkPair> pair;        // [link] k_link_energy's records
     std::vector<double> k_sum, c_sum;  // [row] sum of k, sum of c over the row's links
 };
@@ -308,41 +306,21 @@ inline bool link_table(const Link* links, size_t n, size_t nf, size_t n_verts, s
             out.k_sum.push_back(ks);
             out.c_sum.push_back(cs);
         }
-    const size_t n_rows = row_vertex.size(), n_slices = (n_rows + slice - 1) / slice;
-    auto len = [&](size_t r) { return first[row_vertex[r] + 1] - first[row_vertex[r]]; };
-    out.slice_off.assign(n_slices + 1, 0u);
-    for (size_t s = 0; s < n_slices; ++s) {
-        size_t width = 0;
-        for (size_t r = s * slice; r < std::min(n_rows, (s + 1) * slice); ++r) width = std::max(width, len(r));
-        if (!((size_t)out.slice_off[s] + width * slice < (size_t)1 << 31)) {
-            why = "links: the table is too large";
-            return false;
-        }
-        out.slice_off[s + 1] = out.slice_off[s] + (unsigned)(width * slice);
-    }
-    out.ent.resize(out.slice_off[n_slices]);
-    for (size_t s = 0; s < n_slices; ++s) {
-        const size_t width = (out.slice_off[s + 1] - out.slice_off[s]) / slice;
-        for (size_t l = 0; l < slice; ++l) {
-            const size_t r = s * slice + l;
-            // (padding: the row's own id and zeros; the lanes past the last row are never read)
-            const uint32_t own = (uint32_t)(r < n_rows ? out.row_pid[r] : out.row_pid[n_rows - 1]);
-            for (size_t q = 0; q < width; ++q)
-                out.ent[out.slice_off[s] + q * slice + l] =
-                    r < n_rows && q < len(r) ? flat[first[row_vertex[r]] + q] : LinkRecord{own, 0.f, 0.f, 0.f};
-        }
+    // (padding: the row's own id and zeros)
+    if (!sliced_ell(row_vertex.size(), slice, [&](size_t r) { return first[row_vertex[r] + 1] - first[row_vertex[r]]; },
+                    [&](size_t r, size_t q) { return flat[first[row_vertex[r]] + q]; },
+                    [&](size_t r) { return LinkRecord{(uint32_t)out.row_pid[r], 0.f, 0.f, 0.f}; }, out.slice_off, out.ent)) {
+        why = "links: the table is too large";
+        return false;
     }
     return true;
 }
 
 // The guard's rates on the vertices' masses (mass[vertex]): W = max_i (2 / m_i) sum_j k_ij, G = max_i (2 / m_i) sum_j c_ij
 inline void link_rates(const LinkTable& t, const float* mass, size_t nf, double* W, double* G) {
-    *W = *G = 0.0;
-    for (size_t r = 0; r < t.row_pid.size(); ++r) {
-        const double m = (double)mass[(size_t)t.row_pid[r] - nf];
-        if (t.k_sum[r] > 0.0) *W = std::max(*W, m > 0.0 ? 2.0 * t.k_sum[r] / m : (double)INFINITY);
-        if (t.c_sum[r] > 0.0) *G = std::max(*G, m > 0.0 ? 2.0 * t.c_sum[r] / m : (double)INFINITY);
-    }
+    auto m = [&](size_t r) { return mass[(size_t)t.row_pid[r] - nf]; };
+    *W = max_row_rate(t.k_sum.data(), t.row_pid.size(), 2.0, m);
+    *G = max_row_rate(t.c_sum.data(), t.row_pid.size(), 2.0, m);
 }
 // mpm_links_max_stable_dt: symplectic Euler on x'' = -W x - G x' (v' = v + dt (-W x - G v), x' = x + dt v') is stable
 // iff W dt^2 + 2 G dt <= 4.  The positive root of that quadratic, 4 / (G + sqrt(G^2 + 4 W)) (2 / G where W = 0), as the
