@@ -215,6 +215,41 @@ def link_force(link, xa, xb, va, vb):
     return out
 
 
+# mpm_cloth_pressure_t (20 bytes) and mpm_cloth_pressure_state_t (24 bytes) as numpy records: GpuMpm.set_pressure takes,
+# get_pressure returns, arrays of the first, one per cloth; pressure_state returns an array of the second
+PRESSURE_OFF, PRESSURE_CONSTANT, PRESSURE_GAS = 0, 1, 2
+PRESSURE_DTYPE = np.dtype([("mode", "<u4"), ("p", "<f4"), ("pv", "<f4"), ("p_ambient", "<f4"), ("p_max", "<f4")])
+PRESSURE_STATE_DTYPE = np.dtype([("volume", "<f8"), ("energy", "<f8"), ("gauge", "<f4"), ("capped", "<u4")])
+assert PRESSURE_DTYPE.itemsize == 20 and PRESSURE_STATE_DTYPE.itemsize == 24
+
+
+def mesh_is_closed(indices, n_verts):
+    """mpm_mesh_is_closed: (True, None) when every directed edge of the (n, 3) int32 faces occurs exactly once and its
+    reverse exactly once, else (False, (a, b)) with the first offending directed edge.  Needs no engine and no GPU."""
+    lib = load_library()
+    t = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    edge = np.zeros(2, np.int32)
+    rc = lib.mpm_mesh_is_closed(t.ctypes.data if t.size else None, len(t), int(n_verts), edge.ctypes.data)
+    if rc < 0:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return (True, None) if rc == 1 else (False, (int(edge[0]), int(edge[1])))
+
+
+def pressure_vertex_force(g, x_own, x_b, x_c):
+    """mpm_pressure_vertex_force: (g / 6) sum_e (x_b[e] - x_own) x (x_c[e] - x_own), (3,) float32, evaluated on the host
+    by the function the pressure kernel calls, the entries added in order.  Needs no engine and no GPU."""
+    lib = load_library()
+    x = np.ascontiguousarray(x_own, np.float32).reshape(3)
+    b, c = (np.ascontiguousarray(q, np.float32).reshape(-1, 3) for q in (x_b, x_c))
+    assert len(b) == len(c)
+    out = np.zeros(3, np.float32)
+    rc = lib.mpm_pressure_vertex_force(float(g), x.ctypes.data, len(b), b.ctypes.data if len(b) else None,
+                                       c.ctypes.data if len(b) else None, out.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return out
+
+
 def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
     """mpm_damping_face_records: the membrane damping kernel's face function on the host.  dminv3 (n, 3) = (Dm0, Dm1, Dm3),
     vol, mu, lam, beta (n,) (scalars are broadcast), x, v (n, 3, 3) corner positions and velocities; returns the corner
@@ -392,6 +427,8 @@ SYMBOLS = [
     "mpm_bending_max_stable_dt", "mpm_bending_matrix", "mpm_measure", "mpm_face_strain", "mpm_cloth_energy_density",
     "mpm_set_damping", "mpm_get_damping", "mpm_damping_forces", "mpm_damping_max_stable_dt", "mpm_damping_face_records",
     "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
+    "mpm_set_pressure", "mpm_get_pressure", "mpm_pressure_forces", "mpm_pressure_state", "mpm_mesh_is_closed",
+    "mpm_pressure_vertex_force",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -524,6 +561,12 @@ def load_library(build: bool = True):
         "mpm_link_energy": [vp, P(C.c_double), vp],
         "mpm_links_max_stable_dt": [vp, P(f)],
         "mpm_link_force": [vp, vp, vp, vp, vp, vp],
+        "mpm_set_pressure": [vp, sz, vp],
+        "mpm_get_pressure": [vp, vp, sz, P(sz)],
+        "mpm_pressure_forces": [vp, vp],
+        "mpm_pressure_state": [vp, vp, sz, P(sz)],
+        "mpm_mesh_is_closed": [vp, sz, sz, vp],
+        "mpm_pressure_vertex_force": [f, vp, sz, vp, vp, vp],
         "mpm_set_damping": [vp, sz, vp],
         "mpm_get_damping": [vp, vp, sz, P(sz)],
         "mpm_damping_forces": [vp, vp],
@@ -887,6 +930,45 @@ class GpuMpm:
     @staticmethod
     def link_force(link, xa, xb, va, vb):
         return link_force(link, xa, xb, va, vb)
+
+    def set_pressure(self, table):
+        """mpm_set_pressure: the enclosed-volume pressure of every cloth, an array of PRESSURE_DTYPE in cloth order
+        (mode PRESSURE_OFF / PRESSURE_CONSTANT with p / PRESSURE_GAS with pv, p_ambient, p_max); an empty table turns it
+        off.  A synchronisation point."""
+        t = np.ascontiguousarray(table, PRESSURE_DTYPE).reshape(-1)
+        self._ck(self.lib.mpm_set_pressure(self.h, t.size, t.ctypes.data if t.size else None))
+
+    def get_pressure(self):
+        """mpm_get_pressure: the table in force, one PRESSURE_DTYPE record per cloth (zeros while off)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_pressure(self.h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), PRESSURE_DTYPE)
+        self._ck(self.lib.mpm_get_pressure(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
+    def pressure_forces(self):
+        """mpm_pressure_forces: the pressure force on the current positions, (n_verts, 3) float32 in dump_cpu_state's
+        numbering; V and g are formed anew."""
+        out = np.zeros((self.n_verts, 3), np.float32)
+        self._ck(self.lib.mpm_pressure_forces(self.h, _ptr(out)))
+        return out
+
+    def pressure_state(self):
+        """mpm_pressure_state: one PRESSURE_STATE_DTYPE record per cloth (volume, energy, gauge, capped) on the current
+        positions; the volume of every cloth, pressurised or not."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_pressure_state(self.h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), PRESSURE_STATE_DTYPE)
+        self._ck(self.lib.mpm_pressure_state(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
+    @staticmethod
+    def mesh_is_closed(indices, n_verts):
+        return mesh_is_closed(indices, n_verts)
+
+    @staticmethod
+    def pressure_vertex_force(g, x_own, x_b, x_c):
+        return pressure_vertex_force(g, x_own, x_b, x_c)
 
     def measure(self, capacity: int | None = None):
         """mpm_measure: (rows, total) -- one MEASURE_DTYPE record per cloth (the first `capacity` of them if given) and

@@ -1,5 +1,5 @@
 // Host side of the per-cloth features: cloth materials, external force fields, row tables, bending stiffness, links,
-// damping and the per-cloth report -- what the entry points in mpm_engine.hip call once their arguments are checked.
+// pressure, damping and the per-cloth report -- what the entry points in mpm_engine.hip call once their arguments are checked.
 // Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
 #pragma once
 #include "mpm_host.h"
@@ -305,6 +305,124 @@ static int link_energy(mpm_engine* e, double* energy_out, float* length_out) {
     }
     *energy_out = sum;
     return 0;
+}
+
+// ---- enclosed-volume pressure per cloth (mpm_set_pressure, mpm_get_pressure, mpm_pressure_forces, mpm_pressure_state,
+// mpm_mesh_is_closed, mpm_pressure_vertex_force; mpm_pressure.h) ----
+// The table `t` for the caller's per-cloth parameters (checked; none: off) put in force: new device arrays, upload, swap.
+// Beside the row table go the rows' cloths, the parameters, the chunk list of k_pressure_volume (the gas cloths' chunks,
+// then all cloths'), its partial sums, both range tables and the per-cloth state.  The caller has settled the owed
+// substeps.  A failure changes nothing: the new buffers go, the table in force stays.
+static int pressure_swap(mpm_engine* e, const PressureTable& t, size_t n_cloths, const mpm_cloth_pressure_t* per_cloth) {
+    static_assert(sizeof(ClothPressure) == sizeof(mpm_cloth_pressure_t) && sizeof(ClothPressureState) == sizeof(mpm_cloth_pressure_state_t) &&
+                      sizeof(ClothPressureState) == 24,
+                  "pressure layouts differ");
+    const size_t nc = e->cloths.size();
+    std::vector<ClothPressure> par(nc, ClothPressure{PRESSURE_OFF, 0.f, 0.f, 0.f, 0.f});
+    if (n_cloths) std::memcpy(par.data(), per_cloth, nc * sizeof(ClothPressure));
+    std::vector<int4> chunks, ranges_gas, ranges_all;
+    pressure_chunks(e->cloths, [&](size_t c) { return par[c].mode == PRESSURE_GAS; }, chunks, ranges_gas);
+    const int n_gas = (int)chunks.size();
+    pressure_chunks(e->cloths, [](size_t) { return true; }, chunks, ranges_all);
+    mpm_engine::Pressure next;
+    FreshArrays fresh(e);
+    if (int rc = rows_upload(e, fresh, t, &next.args)) return rc;
+    int4 *d_chunks = nullptr, *d_rg = nullptr, *d_ra = nullptr;
+    double* d_partial = nullptr;
+    ClothPressure* d_par = nullptr;
+    ClothPressureState* d_state = nullptr;
+    int* d_row_cloth = nullptr;
+    if (int rc = fresh.alloc(&d_chunks, std::max<size_t>(chunks.size(), 1), false)) return rc;
+    if (int rc = fresh.alloc(&d_partial, std::max<size_t>(chunks.size(), 1), true)) return rc;
+    if (int rc = fresh.alloc(&d_rg, std::max<size_t>(nc, 1), false)) return rc;
+    if (int rc = fresh.alloc(&d_ra, std::max<size_t>(nc, 1), false)) return rc;
+    if (int rc = fresh.alloc(&d_par, std::max<size_t>(nc, 1), true)) return rc;
+    if (int rc = fresh.alloc(&d_state, std::max<size_t>(nc, 1), true)) return rc;
+    if (!chunks.empty()) H2D(e, d_chunks, chunks.data(), chunks.size() * sizeof(int4));
+    if (nc) {
+        H2D(e, d_rg, ranges_gas.data(), nc * sizeof(int4));
+        H2D(e, d_ra, ranges_all.data(), nc * sizeof(int4));
+        H2D(e, d_par, par.data(), nc * sizeof(ClothPressure));
+    }
+    if (next.args.n_rows) {
+        if (int rc = fresh.alloc(&d_row_cloth, t.row_cloth.size(), false)) return rc;
+        H2D(e, d_row_cloth, t.row_cloth.data(), t.row_cloth.size() * sizeof(int));
+    }
+    next.args.row_cloth = d_row_cloth;
+    next.args.par = d_par;
+    next.args.state = d_state;
+    next.vol = PressureVolumeArgs{d_chunks, d_partial, d_ra, d_par, d_state, 0};
+    next.d_ranges_gas = d_rg;
+    next.n_gas_chunks = n_gas;
+    next.n_all_chunks = (int)chunks.size() - n_gas;
+    next.built = true;
+    if (n_cloths) next.set.assign(per_cloth, per_cloth + n_cloths);
+    {   // the arrays of the table that was in force
+        const mpm_engine::Pressure& o = e->pressure;
+        rows_free(e, o.args);
+        void* old[] = {(void*)o.args.row_cloth, (void*)o.vol.chunks, (void*)o.vol.partial, (void*)o.vol.ranges, (void*)o.vol.par,
+                       (void*)o.vol.state, (void*)o.d_ranges_gas};
+        for (void* q : old) e->dfree(q);
+    }
+    e->pressure = next;
+    fresh.commit();
+    return 0;
+}
+// mpm_set_pressure: the numbers, the gas cloths' meshes and rest volumes, the table on the host, the swap
+static int set_pressure(mpm_engine* e, size_t n_cloths, const mpm_cloth_pressure_t* per_cloth) {
+    const ClothPressure* P = reinterpret_cast<const ClothPressure*>(per_cloth);
+    const std::string refusal = pressure_refusal(P, n_cloths);
+    if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    REQUIRE(e->np < (size_t)1 << 31, "pressure: too many particles");
+    for (size_t c = 0; c < n_cloths; ++c) {
+        if (P[c].mode != PRESSURE_GAS) continue;
+        const mpm_engine::Cloth& cl = e->cloths[c];
+        int32_t edge[2] = {0, 0};
+        if (!mesh_is_closed(e->h_idx.data() + 3 * cl.first_face, cl.n_faces, edge))
+            return fail(MPM_ERR_INVALID, "pressure: cloth " + std::to_string(c) + " is in gas mode but its mesh is not closed and consistently "
+                        "wound: the edge " + std::to_string(edge[0]) + " -> " + std::to_string(edge[1]) +
+                        " does not occur exactly once with its reverse exactly once");
+        if (!(mesh_volume(e->h_pos.data(), e->h_idx.data(), cl.first_face, cl.n_faces) > 0.0))
+            return fail(MPM_ERR_INVALID, "pressure: cloth " + std::to_string(c) + " is in gas mode but its rest volume is not positive: "
+                        "reverse the winding of its faces");
+    }
+    PressureTable t;
+    if (n_cloths) {
+        std::string why;
+        if (!pressure_table(e->cloths, e->h_idx.data(), e->nf, P, PRESSURE_SLICE, t, why)) return fail(MPM_ERR_INVALID, why);
+    } else {
+        t.slice_off.assign(1, 0u);
+    }
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    return pressure_swap(e, t, n_cloths, per_cloth);
+}
+
+// V, E, g and the cap of every cloth from the current positions into Pressure::vol.state (stream-ordered; e->dp: no gate)
+static int pressure_measure(mpm_engine* e) {
+    mpm_engine::Pressure& ps = e->pressure;
+    if (!ps.built) {   // (never set: the chunk list of all cloths and a table without rows)
+        PressureTable t;
+        t.slice_off.assign(1, 0u);
+        if (int rc = pressure_swap(e, t, 0, nullptr)) return rc;
+    }
+    if (ps.n_all_chunks)
+        hipLaunchKernelGGL(k_pressure_volume, dim3((unsigned)ps.n_all_chunks), dim3(256), 0, e->stream, e->dp, ps.vol, ps.n_gas_chunks);
+    if (!e->cloths.empty()) hipLaunchKernelGGL(k_pressure_gauge, dim3((unsigned)e->cloths.size()), dim3(64), 0, e->stream, e->dp, ps.vol);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int pressure_forces(mpm_engine* e, float* f_out) {
+    if (e->pressure.on())
+        if (int rc = pressure_measure(e)) return rc;
+    return rows_eval(e, k_pressure_eval, e->pressure.args, f_out);
+}
+static int pressure_state(mpm_engine* e, mpm_cloth_pressure_state_t* out, size_t capacity, size_t* n_out) {
+    const size_t nc = e->cloths.size();
+    if (int rc = pressure_measure(e)) return rc;
+    std::vector<mpm_cloth_pressure_state_t> rows(nc);
+    if (nc) D2H(e, rows.data(), e->pressure.vol.state, nc * sizeof(mpm_cloth_pressure_state_t));
+    return copy_out(rows, out, capacity, n_out);
 }
 
 // ---- stiffness-proportional damping (mpm_set_damping, mpm_get_damping, mpm_damping_forces, mpm_damping_max_stable_dt,

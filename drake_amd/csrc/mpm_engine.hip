@@ -196,6 +196,19 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p) {
                            (const float*)e->damp.d_beta_vertex);
     // (an engine with links, mpm_set_links: f += the seams', springs' and cords' forces, one lane per linked vertex)
     if (e->links.on()) hipLaunchKernelGGL(k_link, rows_grid(e->links.args.n_rows), dim3(256), 0, e->stream, p, e->links.args);
+    // (an engine with pressure, mpm_set_pressure: where a cloth is in gas mode, the gas cloths' volumes and gauge pressures
+    // from the current positions, on the device; then f += the pressure force, one lane per vertex of a pressurised cloth)
+    if (e->pressure.on()) {
+        const mpm_engine::Pressure& ps = e->pressure;
+        if (ps.gas()) {
+            PressureVolumeArgs va = ps.vol;
+            va.ranges = ps.d_ranges_gas;
+            va.only_gas = 1;
+            hipLaunchKernelGGL(k_pressure_volume, dim3((unsigned)ps.n_gas_chunks), dim3(256), 0, e->stream, p, va, 0);
+            hipLaunchKernelGGL(k_pressure_gauge, dim3((unsigned)e->cloths.size()), dim3(64), 0, e->stream, p, va);
+        }
+        hipLaunchKernelGGL(k_pressure, rows_grid(ps.args.n_rows), dim3(256), 0, e->stream, p, ps.args);
+    }
 }
 // (mpm_calc_fem_state_and_force: the two FEM kernels, whose forces a caller may read)
 static void launch_fem(mpm_engine* e, const DP& p, float dt) {
@@ -232,8 +245,10 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
 }
 // the vertex forces inside k_p2g, from the vertices' entries of DP::VF (single and partitioned domains alike since round
 // 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch, and so does an engine with bending
-// stiffness or links, whose k_bend and k_link add to the forces in DP::f
-static int fused_forces(const mpm_engine* e) { return e->max_valence <= 8 && !e->bend.on() && !e->links.on() ? 1 : 0; }
+// stiffness, links or pressure, whose k_bend, k_link and k_pressure add to the forces in DP::f
+static int fused_forces(const mpm_engine* e) {
+    return e->max_valence <= 8 && !e->bend.on() && !e->links.on() && !e->pressure.on() ? 1 : 0;
+}
 // the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins launches it (pins_ready has resolved the
 // table).  Everything after GridToParticle -- the coupled path's watch kernel included -- comes after it on the stream.
 static void launch_pins(mpm_engine* e, const DP& p, float dt) {
@@ -720,7 +735,7 @@ int mpm_sync(mpm_handle_t e) try {
 } MPM_CATCH_ALL
 
 // partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
-// stiffness, no damping and no links (out of scope)
+// stiffness, no damping, no links and no pressure (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
@@ -735,6 +750,8 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with damping (mpm_set_damping)");
     if (e->links.on())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with links (mpm_set_links)");
+    if (e->pressure.on())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pressure (mpm_set_pressure)");
     return 0;
 }
 // the refusal of a dt above a feature's mpm_<feature>_max_stable_dt (fields_stable)
@@ -762,10 +779,10 @@ static int fields_stable(const mpm_engine* e, float dt) {
     return 0;
 }
 // The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
-// takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness, damping or
-// links are set.
+// takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness, damping,
+// links or pressure are set.
 static float quiet_hint(const mpm_engine* e, float seconds) {
-    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->links.on() ? seconds : 0.f;
+    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->links.on() && !e->pressure.on() ? seconds : 0.f;
 }
 
 // ---- the solver calls -----------------------------------------------------
@@ -2279,6 +2296,55 @@ int mpm_link_force(const mpm_link_t* link, const float* xa, const float* xb, con
     REQUIRE(link && xa && xb && va && vb && f_on_a, "null argument");
     const float d[3] = {xb[0] - xa[0], xb[1] - xa[1], xb[2] - xa[2]}, w[3] = {vb[0] - va[0], vb[1] - va[1], vb[2] - va[2]};
     link_force(link->stiffness, link->rest_length, link->damping, (link->flags & MPM_LINK_TENSION_ONLY) != 0u, d, w, f_on_a);
+    return 0;
+} MPM_CATCH_ALL
+
+// ---- enclosed-volume pressure per cloth (mpm_cloth_host.h; mpm_pressure.h) ------------------------------------------------------
+int mpm_set_pressure(mpm_handle_t e, size_t n_cloths, const mpm_cloth_pressure_t* per_cloth) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "pressure is")) return rc;
+    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_pressure: n_cloths must be mpm_cloth_count (or 0: off)");
+    REQUIRE(n_cloths == 0 || per_cloth, "null pressure array");
+    return set_pressure(e, n_cloths, per_cloth);
+} MPM_CATCH_ALL
+
+int mpm_get_pressure(mpm_handle_t e, mpm_cloth_pressure_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    std::vector<mpm_cloth_pressure_t> t = e->pressure.set;   // (one entry per cloth; zeros where nothing was set)
+    t.resize(e->cloths.size(), mpm_cloth_pressure_t{MPM_PRESSURE_OFF, 0.f, 0.f, 0.f, 0.f});
+    return copy_out(t, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_pressure_forces(mpm_handle_t e, float* f_out) try {
+    READY(e);
+    REQUIRE(f_out || e->nv == 0, "null output");
+    return pressure_forces(e, f_out);
+} MPM_CATCH_ALL
+
+int mpm_pressure_state(mpm_handle_t e, mpm_cloth_pressure_state_t* out, size_t capacity, size_t* n_out) try {
+    READY(e);
+    if (int rc = single_engine_only(e, "mpm_pressure_state is")) return rc;
+    REQUIRE(out || capacity == 0, "null output");
+    return pressure_state(e, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_mesh_is_closed(const int32_t* indices, size_t n_faces, size_t n_verts, int32_t* edge_out) try {
+    REQUIRE(indices || n_faces == 0, "null indices");
+    for (size_t k = 0; k < 3 * n_faces; ++k)
+        REQUIRE(indices[k] >= 0 && (size_t)indices[k] < n_verts, "mpm_mesh_is_closed: a vertex id is out of range");
+    int32_t edge[2] = {0, 0};
+    const bool closed = mesh_is_closed(indices, n_faces, edge);
+    if (!closed && edge_out) {
+        edge_out[0] = edge[0];
+        edge_out[1] = edge[1];
+    }
+    return closed ? 1 : 0;
+} MPM_CATCH_ALL
+
+int mpm_pressure_vertex_force(float g, const float* x_own, size_t n, const float* x_b, const float* x_c, float* f_out) try {
+    REQUIRE(x_own && f_out && (n == 0 || (x_b && x_c)), "null argument");
+    pressure_vertex_force(g, x_own, n, x_b, x_c, f_out);
     return 0;
 } MPM_CATCH_ALL
 

@@ -23,6 +23,7 @@
 #include "mpm_bending.h"
 #include "mpm_damping.h"
 #include "mpm_links.h"
+#include "mpm_pressure.h"
 #include "mpm_measure.h"
 #include "mpm_grid_bodies.h"
 #include "mpm_team.h"
@@ -252,6 +253,19 @@ struct mpm_engine {
         float max_dt = INFINITY;         // the positive root of W dt^2 + 2 G dt = 4 (fields_stable)
         bool on() const { return args.n_rows > 0; }
     } links;
+    // enclosed-volume pressure per cloth (mpm_set_pressure; mpm_pressure.h): a table with a pressurised cloth switches
+    // k_pressure on behind k_link, and a cloth in gas mode k_pressure_volume and k_pressure_gauge in front of it.  The
+    // chunk arrays hold the gas cloths' chunks, then all cloths' (mpm_pressure_state); made at first use (`built`).
+    struct Pressure {
+        std::vector<mpm_cloth_pressure_t> set;   // the caller's table, as given (empty: off)
+        PressureArgs args{};                     // ... as k_pressure reads it (device memory, in `allocs`)
+        PressureVolumeArgs vol{};                // chunks, partial sums, parameters and state; ranges: all cloths'
+        const int4* d_ranges_gas = nullptr;      // [cloth] its chunks in the gas cloths' list
+        int n_gas_chunks = 0, n_all_chunks = 0;
+        bool built = false;
+        bool on() const { return args.n_rows > 0; }
+        bool gas() const { return n_gas_chunks > 0; }
+    } pressure;
     // the per-cloth report (mpm_measure, mpm_face_strain; mpm_measure.h): chunk table and scratch, made at first use
     struct Measure {
         bool built = false;
@@ -495,7 +509,7 @@ static bool is_rotation(const float* R) {
                        (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
     return std::fabs(det - 1.0) <= 1e-4;
 }
-// pins, grid bodies, force fields, bending stiffness, damping and links are refused on a partitioned or multi-rank engine (out of scope);
+// pins, grid bodies, force fields, bending stiffness, damping, links and pressure are refused on a partitioned or multi-rank engine (out of scope);
 // what_is: "pins are", "bending stiffness is", ...
 static int single_engine_only(const mpm_engine* e, const char* what_is) {
     if (e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on)

@@ -1,5 +1,6 @@
 // Vertex row tables: the one data structure behind bending (k_bend, k_bend_eval), hinge damping (k_bend_damp,
-// k_bend_damp_eval), links (k_link, k_link_eval) and the report's bending energy (measure_bend_row).  Host only, no HIP
+// k_bend_damp_eval), links (k_link, k_link_eval), pressure (k_pressure, k_pressure_eval) and the report's bending energy
+// (measure_bend_row).  Host only, no HIP
 // header: a plain C++17 program can include it (tests/test_row_tables.py does, under the address and undefined-behaviour
 // sanitizers).
 //

@@ -284,6 +284,42 @@ struct GpuMpmState {
                           float f_on_a[3]) {
         mpm_check(mpm_link_force(&link, xa, xb, va, vb, f_on_a));
     }
+    // Extension: enclosed-volume pressure per cloth (mpm_set_pressure) -- one entry per cloth in AddQRCloth order; an
+    // empty vector turns it off.  A synchronisation point, like SetBending.  There is no dt guard: watch PressureState.
+    void SetPressure(const std::vector<mpm_cloth_pressure_t>& per_cloth) {
+        mpm_check(mpm_set_pressure(h_, per_cloth.size(), per_cloth.data()));
+    }
+    std::vector<mpm_cloth_pressure_t> GetPressure() const {
+        size_t n = 0;
+        mpm_check(mpm_get_pressure(h_, nullptr, 0, &n));
+        std::vector<mpm_cloth_pressure_t> out(n);
+        mpm_check(mpm_get_pressure(h_, out.data(), n, &n));
+        return out;
+    }
+    // the pressure force on the current positions, 3 floats per vertex in the numbering of DumpCpuState
+    std::vector<float> PressureForces(size_t n_verts) const {
+        std::vector<float> f(3 * n_verts);
+        mpm_check(mpm_pressure_forces(h_, f.data()));
+        return f;
+    }
+    // volume, energy, gauge pressure and cap of every cloth on the current positions
+    std::vector<mpm_cloth_pressure_state_t> PressureState() const {
+        size_t n = 0;
+        mpm_check(mpm_pressure_state(h_, nullptr, 0, &n));
+        std::vector<mpm_cloth_pressure_state_t> out(n);
+        mpm_check(mpm_pressure_state(h_, out.data(), n, &n));
+        return out;
+    }
+    // host only: is the mesh closed and consistently wound?  `edge`, if given, receives the first offending directed edge
+    static bool MeshIsClosed(const std::vector<int32_t>& indices, size_t n_verts, int32_t* edge = nullptr) {
+        const int rc = mpm_mesh_is_closed(indices.data(), indices.size() / 3, n_verts, edge);
+        if (rc < 0) mpm_check(rc);
+        return rc == 1;
+    }
+    // host only: one row of the pressure kernel, see mpm_pressure_vertex_force
+    static void PressureVertexForce(float g, const float x_own[3], size_t n, const float* x_b, const float* x_c, float f_out[3]) {
+        mpm_check(mpm_pressure_vertex_force(g, x_own, n, x_b, x_c, f_out));
+    }
     // Extension: the per-cloth report (mpm_measure) -- masses, momenta, kinetic, potential, elastic and bending energies,
     // strain extremes, reduced on the device in double.  One row per cloth; `total`, if given, receives their sum.
     // System::CalcKineticEnergy is total.kinetic + total.kinetic_affine, CalcPotentialEnergy is gravity_potential +

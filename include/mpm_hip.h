@@ -914,6 +914,85 @@ MPM_API int mpm_links_max_stable_dt(mpm_handle_t h, float *dt_out);
 MPM_API int mpm_link_force(const mpm_link_t *link, const float xa[3], const float xb[3], const float va[3], const float vb[3],
                            float f_on_a[3]);
 
+/* ---- Enclosed-volume pressure per cloth: inflatable cloths (an extension) ----
+ * Every other force on the cloth is local: none knows that a cloth can enclose something, so a ball, a cushion, an
+ * airbag or a balloon in a gripper has no load that keeps it from collapsing.  mpm_set_pressure gives every cloth a
+ * gauge pressure g that pushes each face along its winding normal (a force field, mpm_set_force_fields, pushes along a
+ * fixed direction and cannot depend on a volume).  One mpm_cloth_pressure_t per cloth, in the order of the
+ * mpm_add_qr_cloth* calls:
+ *   MPM_PRESSURE_OFF       nothing (the other fields are not read beyond the finiteness check)
+ *   MPM_PRESSURE_CONSTANT  g = p: any finite value, either sign; the mesh may be open -- a follower load of p per unit
+ *                          of CURRENT area along each face's winding normal
+ *   MPM_PRESSURE_GAS       an isothermal gas in a closed cloth: pv > 0 (the product p V of the enclosed gas),
+ *                          p_ambient >= 0, p_max > p_ambient.  With V the cloth's current signed volume,
+ *                          g = min(pv / V, p_max) - p_ambient where V > 0, and g = p_max - p_ambient otherwise, formed
+ *                          in double and rounded to float once: never a NaN or an infinity.  A collapsed or inverted
+ *                          cloth gets the capped pressure, and mpm_pressure_state says so.
+ * Volume: V = 1/6 sum_faces x_a . (x_b x x_c), every term formed in double from the float positions, summed in id order
+ * in a fixed tree.  Force on vertex i: every face around it, rotated cyclically to read (i, b, c), in ascending face id,
+ *   f_i = (g / 6) sum (x_b - x_i) x (x_c - x_i)
+ * in float, every operation written out, no contraction, the one multiplication by g / 6 last.  Differences only: the
+ * force is translation invariant to the bit.  On an interior vertex of a closed, consistently wound mesh it is exactly
+ * g dV/dx_i, so the force is conservative: E = -p V (constant), E = -pv ln V + p_ambient V (gas, while not capped).
+ * Orientation: positive g pushes along the winding normal; gas mode requires V > 0 on the rest shape (reverse the winding
+ * otherwise).  One lane per vertex adds its faces in a fixed order, without atomics: V, g and the forces are the same
+ * bits whatever the particle order.
+ * The force joins the vertex forces of CalcFemStateAndForce (MPM_ARR_FORCES includes it; its kernels run behind the
+ * vertex-force, bending, bending-damping and link kernels and count under MPM_PHASE_VFORCE; the volume is reduced on the
+ * device inside the substep, a batch of mpm_run_substeps stays device resident).  It works with pins, per-cloth
+ * materials, grid bodies, force fields, bending, damping, links, deterministic mode, fast math and the coupled path.
+ * NO dt GUARD: the gas's stiffness (pv / V^2) grad V grad V^T + a geometric term depends on the state and is unbounded
+ * as V -> 0 below the cap; a limit computed at the rest shape would promise something it cannot keep.  Watch V and g
+ * through mpm_pressure_state and choose dt accordingly.
+ * mpm_set_pressure replaces the table (n_cloths = 0 turns pressure off, the table may then be NULL; otherwise n_cloths
+ * must equal mpm_cloth_count); it needs mpm_finalize, is ordered on the engine's stream and is a synchronisation point;
+ * substeps that mpm_run_substeps still owes are run first, with the table they were enqueued with.  With pressure off
+ * the engine launches exactly what it launches without this call.  While pressure is set the engine does not use the
+ * re-sort's quiet-time estimate, and every batched substep launches the vertex-force kernel.
+ * Refused with MPM_ERR_INVALID, the previous table staying in force and nothing enqueued: a call before mpm_finalize; a
+ * wrong n_cloths; a number that is not finite; an unknown mode; gas parameters outside the ranges above; gas on a mesh
+ * that is not closed and consistently wound (the message names the cloth and the first offending edge, vertex ids in
+ * the numbering of mpm_dump_cpu_state); gas on a rest volume <= 0; a table that does not fit 2^31 records; any
+ * partitioned or multi-rank engine -- this call on such an engine, and mpm_dist_init, the halo, chain, team and world
+ * substeps on an engine with pressure. */
+#define MPM_PRESSURE_OFF 0u
+#define MPM_PRESSURE_CONSTANT 1u
+#define MPM_PRESSURE_GAS 2u
+typedef struct mpm_cloth_pressure {
+    uint32_t mode;     /* MPM_PRESSURE_* */
+    float p;           /* constant: the gauge pressure, Pa */
+    float pv;          /* gas: p V of the enclosed gas, J, > 0 */
+    float p_ambient;   /* gas: Pa, >= 0 */
+    float p_max;       /* gas: the cap on the absolute pressure, Pa, > p_ambient */
+} mpm_cloth_pressure_t;
+typedef struct mpm_cloth_pressure_state {
+    double volume;     /* V, signed; reported for every cloth, pressurised or not, closed or not */
+    double energy;     /* -p V (constant), -pv ln V + p_ambient V (gas); 0 for an unpressurised cloth and while capped */
+    float gauge;       /* g; 0 for an unpressurised cloth */
+    uint32_t capped;   /* gas: V <= 0 or pv / V >= p_max */
+} mpm_cloth_pressure_state_t;
+MPM_API int mpm_set_pressure(mpm_handle_t h, size_t n_cloths, const mpm_cloth_pressure_t *per_cloth);
+/* The table as given: min(n, capacity) entries into out (may be NULL when capacity is 0), the cloth count into *n_out.
+ * Zeros (MPM_PRESSURE_OFF) while pressure is off. */
+MPM_API int mpm_get_pressure(mpm_handle_t h, mpm_cloth_pressure_t *out, size_t capacity, size_t *n_out);
+/* The pressure force on the current positions: f_out[3 * n_verts], in the vertex numbering of mpm_dump_cpu_state (zeros
+ * for the vertices of unpressurised cloths).  V and g are formed anew from the current positions, never taken from
+ * what the last substep left.  The device function of the substep's kernel; changes no state. */
+MPM_API int mpm_pressure_forces(mpm_handle_t h, float *f_out);
+/* Volume, energy, gauge pressure and cap of every cloth on the current positions: min(n, capacity) entries into out,
+ * the cloth count into *n_out.  Needs mpm_finalize; works with pressure off (volumes alone); refused on a partitioned
+ * or multi-rank engine (the volume would need a rank-ordered sum across the cut).  Changes no state. */
+MPM_API int mpm_pressure_state(mpm_handle_t h, mpm_cloth_pressure_state_t *out, size_t capacity, size_t *n_out);
+/* Host only (no handle, no device): the check mpm_set_pressure applies to a cloth in gas mode.  indices: 3 * n_faces
+ * vertex ids in [0, n_verts).  Returns 1 when every directed edge a -> b of the faces occurs exactly once and its
+ * reverse b -> a exactly once (closed and consistently wound), 0 otherwise with the first offending directed edge, in
+ * face order, in edge_out (may be NULL); MPM_ERR_INVALID for an id out of range. */
+MPM_API int mpm_mesh_is_closed(const int32_t *indices, size_t n_faces, size_t n_verts, int32_t edge_out[2]);
+/* Host only: the inline row function the pressure kernel calls, compiled for the host.  x_own: the vertex, x_b, x_c:
+ * 3 * n floats, entry e's corners b and c; f_out = (g / 6) sum_e (x_b - x_own) x (x_c - x_own), added in order. */
+MPM_API int mpm_pressure_vertex_force(float g, const float x_own[3], size_t n, const float *x_b, const float *x_c,
+                                      float f_out[3]);
+
 /* ---- Energy, momentum and strain report per cloth (an extension) ----
  * What System::CalcKineticEnergy / CalcPotentialEnergy answer for a Drake plant, and what a caller choosing dt or
  * calibrating a stiffness needs: one device-side reduction instead of seven downloads and a host restatement of the
@@ -981,9 +1060,9 @@ MPM_API int mpm_cloth_energy_density(const mpm_cloth_material_t *m, size_t n, co
 /* Runs n substeps with HIP events around every kernel group on the engine's
  * stream and returns the mean milliseconds per substep of each phase
  * (phase_ms[MPM_PHASE_COUNT]) and of the whole substep.  The launches are those of mpm_run_substeps, but every substep
- * carries its re-sort launches and none skips itself.  MPM_PHASE_VFORCE is the vertex-force kernel (and the bending
- * kernel behind it) wherever the engine launches it -- a mesh with a vertex of more than eight faces, an engine with
- * bending stiffness --; on every other engine ParticleToGrid sums the vertex forces itself and the phase is empty. */
+ * carries its re-sort launches and none skips itself.  MPM_PHASE_VFORCE is the vertex-force kernel (and the bending,
+ * link and pressure kernels behind it) wherever the engine launches it -- a mesh with a vertex of more than eight faces,
+ * an engine with bending stiffness, links or pressure --; on every other engine ParticleToGrid sums the vertex forces itself and the phase is empty. */
 MPM_API int mpm_profile_substeps(mpm_handle_t h, int n, float dt, int mpm_bc, float *phase_ms, float *total_ms);
 
 /* ---- multi-GPU: one engine per GPU, domains tiled along x ------------------
