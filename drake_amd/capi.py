@@ -250,6 +250,44 @@ def pressure_vertex_force(g, x_own, x_b, x_c):
     return out
 
 
+# mpm_cloth_shell_t (8 bytes) as a numpy record: GpuMpm.set_shell_bending takes, and get_shell_bending returns, arrays of
+# it, one per cloth
+SHELL_REST_SHAPE, SHELL_REST_FLAT = 0, 1
+SHELL_DTYPE = np.dtype([("stiffness", "<f4"), ("rest", "<u4")])
+assert SHELL_DTYPE.itemsize == 8
+
+
+def mesh_hinges(indices, n_verts):
+    """mpm_mesh_hinges: the hinges (n, 4) int32 (x0, x1 | x2, x3) of the (m, 3) int32 faces of one cloth, in ascending
+    (min(v0, v1), max(v0, v1)): every edge shared by exactly two faces.  Needs no engine and no GPU."""
+    lib = load_library()
+    t = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    n = C.c_size_t()
+
+    def call(out, cap):
+        rc = lib.mpm_mesh_hinges(t.ctypes.data if t.size else None, len(t), int(n_verts), out.ctypes.data if cap else None, cap,
+                                 C.byref(n))
+        if rc:
+            raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    call(None, 0)
+    out = np.zeros((int(n.value), 4), np.int32)
+    call(out, len(out))
+    return out
+
+
+def shell_hinge(x4, kc, psibar):
+    """mpm_shell_hinge: (the four corner records (4, 3) float32, psi float32, acts bool) of one hinge with the corner
+    positions x4 (4, 3) = x0, x1, x2, x3, evaluated on the host by the function the hinge kernel calls.  Needs no engine
+    and no GPU."""
+    lib = load_library()
+    x = np.ascontiguousarray(x4, np.float32).reshape(12)
+    rec, psi = np.zeros((4, 3), np.float32), C.c_float()
+    rc = lib.mpm_shell_hinge(x.ctypes.data, float(np.float32(kc)), float(np.float32(psibar)), rec.ctypes.data, C.byref(psi))
+    if rc < 0:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return rec, np.float32(psi.value), rc == 1
+
+
 def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
     """mpm_damping_face_records: the membrane damping kernel's face function on the host.  dminv3 (n, 3) = (Dm0, Dm1, Dm3),
     vol, mu, lam, beta (n,) (scalars are broadcast), x, v (n, 3, 3) corner positions and velocities; returns the corner
@@ -429,6 +467,8 @@ SYMBOLS = [
     "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
     "mpm_set_pressure", "mpm_get_pressure", "mpm_pressure_forces", "mpm_pressure_state", "mpm_mesh_is_closed",
     "mpm_pressure_vertex_force",
+    "mpm_set_shell_bending", "mpm_get_shell_bending", "mpm_shell_hinges", "mpm_shell_forces", "mpm_shell_state",
+    "mpm_shell_max_stable_dt", "mpm_mesh_hinges", "mpm_shell_hinge",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -567,6 +607,14 @@ def load_library(build: bool = True):
         "mpm_pressure_state": [vp, vp, sz, P(sz)],
         "mpm_mesh_is_closed": [vp, sz, sz, vp],
         "mpm_pressure_vertex_force": [f, vp, sz, vp, vp, vp],
+        "mpm_set_shell_bending": [vp, sz, vp, vp],
+        "mpm_get_shell_bending": [vp, vp, sz, P(sz)],
+        "mpm_shell_hinges": [vp, vp, vp, vp, sz, P(sz)],
+        "mpm_shell_forces": [vp, vp],
+        "mpm_shell_state": [vp, vp, vp, P(C.c_uint32)],
+        "mpm_shell_max_stable_dt": [vp, P(f)],
+        "mpm_mesh_hinges": [vp, sz, sz, vp, sz, P(sz)],
+        "mpm_shell_hinge": [vp, f, f, vp, P(f)],
         "mpm_set_damping": [vp, sz, vp],
         "mpm_get_damping": [vp, vp, sz, P(sz)],
         "mpm_damping_forces": [vp, vp],
@@ -969,6 +1017,73 @@ class GpuMpm:
     @staticmethod
     def pressure_vertex_force(g, x_own, x_b, x_c):
         return pressure_vertex_force(g, x_own, x_b, x_c)
+
+    def set_shell_bending(self, table, rest_pos=None):
+        """mpm_set_shell_bending: shell bending about a curved rest shape -- an array of SHELL_DTYPE in cloth order
+        (stiffness k in N m, rest SHELL_REST_SHAPE / SHELL_REST_FLAT), or a list of stiffnesses (rest shape); rest_pos
+        (n_verts, 3): the rest shape, default the mesh as added.  All zeros or an empty table switches it off.  A
+        synchronisation point."""
+        t = np.asarray(table)
+        if t.dtype != SHELL_DTYPE:
+            k = np.asarray(table, np.float32).reshape(-1)
+            t = np.zeros(len(k), SHELL_DTYPE)
+            t["stiffness"] = k
+        t = np.ascontiguousarray(t).reshape(-1)
+        r = None
+        if rest_pos is not None:
+            r = np.ascontiguousarray(rest_pos, np.float32).reshape(-1, 3)
+            assert len(r) == self.n_verts, (len(r), self.n_verts)
+        self._ck(self.lib.mpm_set_shell_bending(self.h, t.size, t.ctypes.data if t.size else None, r.ctypes.data if r is not None else None))
+
+    def get_shell_bending(self):
+        """mpm_get_shell_bending: the table in force, one SHELL_DTYPE record per cloth (zeros while off)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_shell_bending(self.h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), SHELL_DTYPE)
+        self._ck(self.lib.mpm_get_shell_bending(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
+    def shell_hinges(self):
+        """mpm_shell_hinges: the hinge table in force -- (ids (n, 4) int32 vertex ids x0, x1 | x2, x3 in dump_cpu_state's
+        numbering, kc (n,) float32, psibar (n,) float32)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_shell_hinges(self.h, None, None, None, 0, C.byref(n)))
+        m = int(n.value)
+        ids, kc, psibar = np.zeros((m, 4), np.int32), np.zeros(m, np.float32), np.zeros(m, np.float32)
+        if m:
+            self._ck(self.lib.mpm_shell_hinges(self.h, ids.ctypes.data, kc.ctypes.data, psibar.ctypes.data, m, C.byref(n)))
+        return ids, kc, psibar
+
+    def shell_forces(self):
+        """mpm_shell_forces: the shell bending force on the current positions, (n_verts, 3) float32 in dump_cpu_state's
+        numbering."""
+        out = np.zeros((self.n_verts, 3), np.float32)
+        self._ck(self.lib.mpm_shell_forces(self.h, _ptr(out)))
+        return out
+
+    def shell_state(self):
+        """mpm_shell_state: (energy per cloth (n_cloths,) float64, psi per hinge (n,) float32, the number of inactive
+        hinges) on the current positions."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_shell_hinges(self.h, None, None, None, 0, C.byref(n)))
+        energy, psi = np.zeros(max(self.cloth_count(), 1), np.float64), np.zeros(max(int(n.value), 1), np.float32)
+        inactive = C.c_uint32()
+        self._ck(self.lib.mpm_shell_state(self.h, energy.ctypes.data, psi.ctypes.data, C.byref(inactive)))
+        return energy[:self.cloth_count()], psi[:int(n.value)], int(inactive.value)
+
+    def shell_max_stable_dt(self) -> float:
+        """mpm_shell_max_stable_dt: the dt above which the substep entry points refuse (inf while shell bending is off)."""
+        dt = C.c_float()
+        self._ck(self.lib.mpm_shell_max_stable_dt(self.h, C.byref(dt)))
+        return float(dt.value)
+
+    @staticmethod
+    def mesh_hinges(indices, n_verts):
+        return mesh_hinges(indices, n_verts)
+
+    @staticmethod
+    def shell_hinge(x4, kc, psibar):
+        return shell_hinge(x4, kc, psibar)
 
     def measure(self, capacity: int | None = None):
         """mpm_measure: (rows, total) -- one MEASURE_DTYPE record per cloth (the first `capacity` of them if given) and

@@ -1,5 +1,6 @@
 // Host side of the per-cloth features: cloth materials, external force fields, row tables, bending stiffness, links,
-// pressure, damping and the per-cloth report -- what the entry points in mpm_engine.hip call once their arguments are checked.
+// pressure, shell bending, damping and the per-cloth report -- what the entry points in mpm_engine.hip call once their
+// arguments are checked.
 // Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
 #pragma once
 #include "mpm_host.h"
@@ -423,6 +424,125 @@ static int pressure_state(mpm_engine* e, mpm_cloth_pressure_state_t* out, size_t
     std::vector<mpm_cloth_pressure_state_t> rows(nc);
     if (nc) D2H(e, rows.data(), e->pressure.vol.state, nc * sizeof(mpm_cloth_pressure_state_t));
     return copy_out(rows, out, capacity, n_out);
+}
+
+// ---- shell bending about a curved rest shape (mpm_set_shell_bending, mpm_get_shell_bending, mpm_shell_hinges,
+// mpm_shell_forces, mpm_shell_state, mpm_shell_max_stable_dt; mpm_shell.h) ----
+// mpm_set_shell_bending: the numbers, the hinges and cbar on the host, the guard from the vertices' masses, psibar from
+// the device (k_hinge_rest on the rest positions), the swap.  A failure changes nothing: the new buffers go, the table in
+// force stays.
+static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_shell_t* per_cloth, const float* rest_pos) {
+    static_assert(sizeof(ClothShell) == sizeof(mpm_cloth_shell_t) && sizeof(ClothShell) == 8, "shell layouts differ");
+    const ClothShell* P = reinterpret_cast<const ClothShell*>(per_cloth);
+    const std::string refusal = shell_refusal(P, n_cloths);
+    if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    REQUIRE(e->np < (size_t)1 << 31, "shell bending: too many particles");
+    if (rest_pos && n_cloths)
+        for (size_t i = 0; i < 3 * e->nv; ++i) REQUIRE(std::isfinite(rest_pos[i]), "shell bending: rest_pos is not finite");
+    // the shape that gives cbar, the guard's geometry and psibar: rest_pos where given and asked for, else the mesh as added
+    std::vector<float> shape(e->h_pos.begin(), e->h_pos.begin() + (long)(3 * e->nv));
+    for (size_t c = 0; c < n_cloths && rest_pos; ++c)
+        if (P[c].rest == SHELL_REST_SHAPE) {
+            const mpm_engine::Cloth& cl = e->cloths[c];
+            std::copy(rest_pos + 3 * cl.first_vertex, rest_pos + 3 * (cl.first_vertex + cl.n_verts), shape.begin() + (long)(3 * cl.first_vertex));
+        }
+    ShellTable t;
+    if (n_cloths) {
+        std::string why;
+        if (!shell_table(e->cloths, e->h_idx.data(), e->nf, P, shape.data(), SHELL_SLICE, t, why)) return fail(MPM_ERR_INVALID, why);
+    } else {
+        t.slice_off.assign(1, 0u);
+    }
+    const size_t n = t.kc.size();
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    mpm_engine::Shell next;
+    FreshArrays fresh(e);
+    if (n) {
+        std::vector<float> mass;
+        if (int rc = vertex_masses(e, mass)) return rc;
+        next.max_dt = stable_dt_limit(std::sqrt(max_row_rate(t.rate_sum.data(), t.row_vertex.size(), 1.0,
+                                                             [&](size_t r) { return mass[(size_t)t.row_vertex[r]]; })));
+        if (int rc = rows_upload(e, fresh, t, &next.args)) return rc;
+        std::vector<int4> ids(n);
+        std::vector<float2> par(n);
+        const int nf = (int)e->nf;
+        for (size_t h = 0; h < n; ++h) {
+            ids[h] = make_int4(nf + t.ids4[4 * h], nf + t.ids4[4 * h + 1], nf + t.ids4[4 * h + 2], nf + t.ids4[4 * h + 3]);
+            par[h] = make_float2(t.kc[h], 0.f);
+        }
+        int4* d_ids = nullptr;
+        float2* d_par = nullptr;
+        float4* d_rec = nullptr;
+        if (int rc = fresh.alloc(&d_ids, n, false)) return rc;
+        if (int rc = fresh.alloc(&d_par, n, false)) return rc;
+        if (int rc = fresh.alloc(&d_rec, 4 * n, true)) return rc;
+        H2D(e, d_ids, ids.data(), n * sizeof(int4));
+        H2D(e, d_par, par.data(), n * sizeof(float2));
+        next.hinge = HingeArgs{d_ids, d_par, d_rec, (int)n};
+        next.args.rec = d_rec;
+        next.args.n_hinges = (int)n;
+        // psibar: the hinge function on the device, once, on the rest positions -- the psi it writes (plane 0's .w)
+        if (int rc = e->stage(shape.size() * 4)) return rc;
+        H2D(e, e->d_stage, shape.data(), shape.size() * 4);
+        hipLaunchKernelGGL(k_hinge_rest, rows_grid((int)n), dim3(256), 0, e->stream, next.hinge, (const float*)e->d_stage, nf, (int)e->nv);
+        HIP_TRY(hipGetLastError());
+        std::vector<float4> plane0(n);
+        D2H(e, plane0.data(), d_rec, n * sizeof(float4));
+        next.psibar.resize(n);
+        for (size_t h = 0; h < n; ++h) {
+            next.psibar[h] = P[t.hinge_cloth[h]].rest == SHELL_REST_FLAT ? 0.f : plane0[h].w;
+            par[h].y = next.psibar[h];
+        }
+        H2D(e, d_par, par.data(), n * sizeof(float2));
+        next.ids4.swap(t.ids4);
+        next.kc.swap(t.kc);
+        next.hinge_cloth.swap(t.hinge_cloth);
+    } else {
+        // (a synchronisation point either way: the kernels enqueued so far have read the old table)
+        HIP_TRY(hipStreamSynchronize(e->stream));
+    }
+    if (n_cloths) next.set.assign(per_cloth, per_cloth + n_cloths);
+    {   // the arrays of the table that was in force
+        const mpm_engine::Shell& o = e->shell;
+        rows_free(e, o.args);
+        void* old[] = {(void*)o.hinge.ids, (void*)o.hinge.par, (void*)o.hinge.rec};
+        for (void* q : old) e->dfree(q);
+    }
+    e->shell = next;
+    fresh.commit();
+    return 0;
+}
+
+// the hinge records of the current positions into Shell::hinge.rec (stream-ordered; e->dp: no gate)
+static int shell_measure(mpm_engine* e) {
+    hipLaunchKernelGGL(k_hinge_eval, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, e->dp, e->shell.hinge);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int shell_forces(mpm_engine* e, float* f_out) {
+    if (e->shell.on())
+        if (int rc = shell_measure(e)) return rc;
+    return rows_eval(e, k_hinge_gather_eval, e->shell.on() ? e->shell.args : ShellArgs{}, f_out);
+}
+// One float term per hinge from the device, added here per cloth in double in hinge order: a fixed order, no atomics
+static int shell_state(mpm_engine* e, double* energy_per_cloth, float* psi_out, uint32_t* inactive_out) {
+    const mpm_engine::Shell& sh = e->shell;
+    const size_t n = sh.on() ? (size_t)sh.hinge.n : 0;
+    std::fill(energy_per_cloth, energy_per_cloth + e->cloths.size(), 0.0);
+    uint32_t inactive = 0;
+    if (n) {
+        if (int rc = shell_measure(e)) return rc;
+        std::vector<float4> planes(3 * n);
+        D2H(e, planes.data(), sh.hinge.rec, 3 * n * sizeof(float4));
+        for (size_t h = 0; h < n; ++h) {
+            energy_per_cloth[(size_t)sh.hinge_cloth[h]] += (double)planes[n + h].w;
+            if (psi_out) psi_out[h] = planes[h].w;
+            if (!(planes[2 * n + h].w > 0.f)) inactive += 1;
+        }
+    }
+    if (inactive_out) *inactive_out = inactive;
+    return 0;
 }
 
 // ---- stiffness-proportional damping (mpm_set_damping, mpm_get_damping, mpm_damping_forces, mpm_damping_max_stable_dt,

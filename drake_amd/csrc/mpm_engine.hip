@@ -209,6 +209,12 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p) {
         }
         hipLaunchKernelGGL(k_pressure, rows_grid(ps.args.n_rows), dim3(256), 0, e->stream, p, ps.args);
     }
+    // (an engine with shell bending, mpm_set_shell_bending: the corner records of every hinge, one lane per hinge; then
+    // f += the records of every vertex, one lane per vertex of a cloth with k > 0)
+    if (e->shell.on()) {
+        hipLaunchKernelGGL(k_hinge, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, p, e->shell.hinge);
+        hipLaunchKernelGGL(k_hinge_gather, rows_grid(e->shell.args.n_rows), dim3(256), 0, e->stream, p, e->shell.args);
+    }
 }
 // (mpm_calc_fem_state_and_force: the two FEM kernels, whose forces a caller may read)
 static void launch_fem(mpm_engine* e, const DP& p, float dt) {
@@ -245,9 +251,9 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
 }
 // the vertex forces inside k_p2g, from the vertices' entries of DP::VF (single and partitioned domains alike since round
 // 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch, and so does an engine with bending
-// stiffness, links or pressure, whose k_bend, k_link and k_pressure add to the forces in DP::f
+// stiffness, links, pressure or shell bending, whose k_bend, k_link, k_pressure and k_hinge_gather add to the forces in DP::f
 static int fused_forces(const mpm_engine* e) {
-    return e->max_valence <= 8 && !e->bend.on() && !e->links.on() && !e->pressure.on() ? 1 : 0;
+    return e->max_valence <= 8 && !e->bend.on() && !e->links.on() && !e->pressure.on() && !e->shell.on() ? 1 : 0;
 }
 // the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins launches it (pins_ready has resolved the
 // table).  Everything after GridToParticle -- the coupled path's watch kernel included -- comes after it on the stream.
@@ -735,7 +741,7 @@ int mpm_sync(mpm_handle_t e) try {
 } MPM_CATCH_ALL
 
 // partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
-// stiffness, no damping, no links and no pressure (out of scope)
+// stiffness, no damping, no links, no pressure and no shell bending (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
@@ -752,6 +758,8 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with links (mpm_set_links)");
     if (e->pressure.on())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pressure (mpm_set_pressure)");
+    if (e->shell.on())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with shell bending (mpm_set_shell_bending)");
     return 0;
 }
 // the refusal of a dt above a feature's mpm_<feature>_max_stable_dt (fields_stable)
@@ -767,7 +775,10 @@ static int dt_above_limit(float dt, float max_dt, const char* feature, const cha
 // on the lumped system needs dt * omega <= 2, with Gershgorin's bound on omega^2 (a guard, not a guarantee).  And a dt
 // above mpm_damping_max_stable_dt on an engine with damping: the explicit viscous force needs dt * rho(M^-1 D) <= 2.  And
 // a dt above mpm_links_max_stable_dt on an engine with links: W dt^2 + 2 G dt <= 4 (mpm_links.h; a guard, not a guarantee).
+// And a dt above mpm_shell_max_stable_dt on an engine with shell bending (mpm_shell.h; a guard at the rest shape).
 static int fields_stable(const mpm_engine* e, float dt) {
+    if (e->shell.on() && !(dt <= e->shell.max_dt))
+        return dt_above_limit(dt, e->shell.max_dt, "shell", "shell bending", "dt or the stiffness");
     if (e->links.on() && !(dt <= e->links.max_dt))
         return dt_above_limit(dt, e->links.max_dt, "links", "link", "dt, the stiffness or the damping");
     if (e->damp.any() && !(dt <= e->damp.max_dt)) return dt_above_limit(dt, e->damp.max_dt, "damping", "damping", "dt or the coefficients");
@@ -780,9 +791,10 @@ static int fields_stable(const mpm_engine* e, float dt) {
 }
 // The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
 // takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness, damping,
-// links or pressure are set.
+// links, pressure or shell bending are set.
 static float quiet_hint(const mpm_engine* e, float seconds) {
-    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->links.on() && !e->pressure.on() ? seconds : 0.f;
+    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->links.on() && !e->pressure.on() && !e->shell.on() ? seconds
+                                                                                                                               : 0.f;
 }
 
 // ---- the solver calls -----------------------------------------------------
@@ -2346,6 +2358,76 @@ int mpm_pressure_vertex_force(float g, const float* x_own, size_t n, const float
     REQUIRE(x_own && f_out && (n == 0 || (x_b && x_c)), "null argument");
     pressure_vertex_force(g, x_own, n, x_b, x_c, f_out);
     return 0;
+} MPM_CATCH_ALL
+
+// ---- shell bending about a curved rest shape (mpm_cloth_host.h; mpm_shell.h) -------------------------------------------------------
+int mpm_set_shell_bending(mpm_handle_t e, size_t n_cloths, const mpm_cloth_shell_t* per_cloth, const float* rest_pos) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "shell bending is")) return rc;
+    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_shell_bending: n_cloths must be mpm_cloth_count (or 0: off)");
+    REQUIRE(n_cloths == 0 || per_cloth, "null shell bending array");
+    return set_shell_bending(e, n_cloths, per_cloth, rest_pos);
+} MPM_CATCH_ALL
+
+int mpm_get_shell_bending(mpm_handle_t e, mpm_cloth_shell_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    std::vector<mpm_cloth_shell_t> t = e->shell.set;   // (one entry per cloth; zeros where nothing was set)
+    t.resize(e->cloths.size(), mpm_cloth_shell_t{0.f, MPM_SHELL_REST_SHAPE});
+    return copy_out(t, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_shell_hinges(mpm_handle_t e, int32_t* ids4, float* kc, float* psibar, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(capacity == 0 || (ids4 && kc && psibar), "null output");
+    const mpm_engine::Shell& sh = e->shell;
+    const size_t n = std::min(capacity, sh.kc.size());
+    std::copy(sh.ids4.begin(), sh.ids4.begin() + (long)(4 * n), ids4);
+    std::copy(sh.kc.begin(), sh.kc.begin() + (long)n, kc);
+    std::copy(sh.psibar.begin(), sh.psibar.begin() + (long)n, psibar);
+    if (n_out) *n_out = sh.kc.size();
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_shell_forces(mpm_handle_t e, float* f_out) try {
+    READY(e);
+    REQUIRE(f_out || e->nv == 0, "null output");
+    return shell_forces(e, f_out);
+} MPM_CATCH_ALL
+
+int mpm_shell_state(mpm_handle_t e, double* energy_per_cloth, float* psi_out, uint32_t* inactive_out) try {
+    READY(e);
+    REQUIRE(energy_per_cloth || e->cloths.empty(), "null output");
+    return shell_state(e, energy_per_cloth, psi_out, inactive_out);
+} MPM_CATCH_ALL
+
+int mpm_shell_max_stable_dt(mpm_handle_t e, float* dt_out) try {
+    REQUIRE(e && dt_out, "null argument");
+    *dt_out = e->shell.on() ? e->shell.max_dt : INFINITY;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_mesh_hinges(const int32_t* indices, size_t n_faces, size_t n_verts, int32_t* ids4, size_t capacity, size_t* n_out) try {
+    REQUIRE(indices || n_faces == 0, "null indices");
+    REQUIRE(ids4 || capacity == 0, "null output");
+    REQUIRE(n_faces < (size_t)1 << 30, "mesh too large");
+    for (size_t k = 0; k < 3 * n_faces; ++k)
+        REQUIRE(indices[k] >= 0 && (size_t)indices[k] < n_verts, "mpm_mesh_hinges: a vertex id is out of range");
+    std::vector<ShellHinge> H;
+    mesh_hinges(indices, n_faces, H);
+    for (size_t h = 0; h < std::min(capacity, H.size()); ++h)
+        for (int j = 0; j < 4; ++j) ids4[4 * h + j] = H[h].v[j];
+    if (n_out) *n_out = H.size();
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_shell_hinge(const float* x12, float kc, float psibar, float* rec12_out, float* psi_out) try {
+    REQUIRE(x12 && rec12_out, "null argument");
+    float rec[4][3], psi;
+    const int on = shell_hinge(x12, x12 + 3, x12 + 6, x12 + 9, kc, psibar, rec, &psi) ? 1 : 0;
+    std::memcpy(rec12_out, rec, sizeof rec);
+    if (psi_out) *psi_out = psi;
+    return on;
 } MPM_CATCH_ALL
 
 // ---- the per-cloth report (mpm_cloth_host.h; mpm_measure.h) --------------------------------------------------------------------

@@ -24,6 +24,7 @@
 #include "mpm_damping.h"
 #include "mpm_links.h"
 #include "mpm_pressure.h"
+#include "mpm_shell.h"
 #include "mpm_measure.h"
 #include "mpm_grid_bodies.h"
 #include "mpm_team.h"
@@ -266,6 +267,18 @@ struct mpm_engine {
         bool on() const { return args.n_rows > 0; }
         bool gas() const { return n_gas_chunks > 0; }
     } pressure;
+    // shell bending about a curved rest shape (mpm_set_shell_bending; mpm_shell.h): a cloth with k > 0 and a hinge switches
+    // k_hinge and k_hinge_gather on behind k_pressure
+    struct Shell {
+        std::vector<mpm_cloth_shell_t> set;   // the caller's table, as given (empty: off)
+        HingeArgs hinge{};                    // the hinge table as k_hinge reads it (device memory, in `allocs`)
+        ShellArgs args{};                     // the gather table as k_hinge_gather reads it
+        std::vector<int32_t> ids4;            // [4 hinge] vertex ids, and
+        std::vector<float> kc, psibar;        // [hinge] float(k cbar), the psi of the rest shape (mpm_shell_hinges)
+        std::vector<int> hinge_cloth;         // [hinge]
+        float max_dt = INFINITY;              // the guard at the rest shape (fields_stable)
+        bool on() const { return hinge.n > 0; }
+    } shell;
     // the per-cloth report (mpm_measure, mpm_face_strain; mpm_measure.h): chunk table and scratch, made at first use
     struct Measure {
         bool built = false;
@@ -509,7 +522,8 @@ static bool is_rotation(const float* R) {
                        (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
     return std::fabs(det - 1.0) <= 1e-4;
 }
-// pins, grid bodies, force fields, bending stiffness, damping, links and pressure are refused on a partitioned or multi-rank engine (out of scope);
+// pins, grid bodies, force fields, bending stiffness, damping, links, pressure and shell bending are refused on a partitioned or multi-rank
+// engine (out of scope);
 // what_is: "pins are", "bending stiffness is", ...
 static int single_engine_only(const mpm_engine* e, const char* what_is) {
     if (e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on)

@@ -1,6 +1,6 @@
 // Vertex row tables: the one data structure behind bending (k_bend, k_bend_eval), hinge damping (k_bend_damp,
-// k_bend_damp_eval), links (k_link, k_link_eval), pressure (k_pressure, k_pressure_eval) and the report's bending energy
-// (measure_bend_row).  Host only, no HIP
+// k_bend_damp_eval), links (k_link, k_link_eval), pressure (k_pressure, k_pressure_eval), shell bending (k_hinge_gather,
+// k_hinge_gather_eval) and the report's bending energy (measure_bend_row).  Host only, no HIP
 // header: a plain C++17 program can include it (tests/test_row_tables.py does, under the address and undefined-behaviour
 // sanitizers).
 //
@@ -10,7 +10,8 @@
 // ent[slice_off[s] + 64 e + l], so a wave reads contiguous records per step, and slice_off[s + 1] - slice_off[s] is 64
 // times the slice's width.  slice_off has one more element than there are slices; its last is the number of records.  A
 // row shorter than its slice is padded with a record that must evaluate to an EXACT zero whatever the state and must name
-// a particle the row may read: each table pads with the row's own id and zero coefficients.  The lanes of the last slice
+// a particle the row may read: each table pads with the row's own id and zero coefficients (the shell table's records
+// name hinge records, not particles: its padding is a word that no record can be, and is skipped).  The lanes of the last slice
 // past the last row are never read; they hold the last row's padding.  Three device arrays carry a table (row_pid,
 // slice_off, ent: BendArgs, LinkArgs; uploaded by rows_upload, mpm_cloth_host.h).
 #pragma once

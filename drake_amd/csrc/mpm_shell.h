@@ -1,0 +1,515 @@
+// Shell bending about a curved rest shape (mpm_set_shell_bending, include/mpm_hip.h): the discrete-shells hinge model
+// (Grinspun et al. 2003, "Discrete shells") in the variable psi = 2 sin(theta / 2) (hinge energies in a function of
+// theta and the gradient of theta: Tamstorf and Grinspun 2013, "Discrete bending forces and their Jacobians").  Hinges
+// are those of mpm_set_bending: every edge shared by exactly two faces of one cloth; boundary edges and edges with more
+// than two faces form none.  A hinge is (x0, x1 | x2, x3): x0 -> x1 is the edge as face A, the face with the lower id,
+// runs it, x2 is opposite the edge in face A, x3 in face B; the hinges of all cloths with k > 0 are numbered in ascending
+// (cloth, min(v0, v1), max(v0, v1)).
+// All quantities are differences against x0 (translation invariant to the bit):
+//   e = x1 - x0,  a = x2 - x0,  b = x3 - x0,   nA = e x a,  nB = b x e                 (parallel on a flat hinge)
+//   nAh = nA / |nA|,  nBh = nB / |nB|,  sigma = +1 where e . (nA x nB) >= 0, else -1
+//   psi  = sigma |nAh - nBh|   = 2 sin(theta / 2),  theta = atan2(e^ . (nA x nB), nA . nB) the signed dihedral angle
+//   dpsi = 1/2 |nAh + nBh|     = cos(theta / 2) = d psi / d theta
+//   E_h  = 1/2 k cbar (psi - psibar)^2,   cbar = 3 |ebar|^2 / (Abar_A + Abar_B)   (rest edge length and rest areas)
+//   f_j  = -k cbar (psi - psibar) dpsi G_j,   G_j = grad_{x_j} theta:
+//     G2 = -|e| nA / |nA|^2,  G3 = -|e| nB / |nB|^2,  with wA = a . e / |e|^2,  wB = b . e / |e|^2
+//     G1 = -(wA G2 + wB G3),  G0 = -((1 - wA) G2 + (1 - wB) G3)                       (G0 + G1 + G2 + G3 = 0)
+// No trigonometric function: square roots and divisions only, correctly rounded whatever mpm_set_fast_math says,
+// every operation written out, contraction off (shell_hinge below: what k_hinge calls and what the host entry
+// mpm_shell_hinge runs).  Five square roots and five divisions per hinge.
+//
+// Why 2 sin(theta / 2): with psibar = 0 the energy of a hinge whose two triangles move rigidly is exactly the quadratic
+// model's 1/2 k c |K x|^2 (mpm_bending.h), so the same k means the same thing in both calls and this model is the
+// quadratic one's rotation-invariant continuation to curved rest shapes; and it is bounded: no infinite force.
+// ITS WEAKNESS: dpsi -> 0 as |theta| -> pi, so a hinge folded flat onto itself feels no restoring force, and psi jumps
+// from 2 to -2 there: the energy is discontinuous for psibar != 0 while the force is continuous.
+//
+// The rest shape is an exact equilibrium: psibar is not computed on the host -- mpm_set_shell_bending runs the hinge
+// function on the device once on the rest positions (k_hinge_rest) and keeps the psi it wrote, so on the rest positions
+// psi - psibar is an exact zero and every record and every vertex force is +-0.  cbar is formed in double on the host
+// and the product k cbar rounded to float once.  A hinge acts only while |e|^2, |nA|^2 and |nB|^2 are all >= 1e-30;
+// otherwise its four records are exact zeros, its psi is 0 and it counts as inactive: never a NaN or an infinity.
+//
+// Device, two passes behind k_pressure in launch_fem_vertices, no atomics but the error flag, both starting with
+// gated_out(p).  k_hinge, one lane per hinge in hinge order: four ids from the host-built table, four slots through
+// DP::imap, four positions -- three round trips of independent loads --, then four corner records as float4 into four
+// planes rec[j][h] (coalesced 16-byte stores); the .w of plane 0 carries psi, that of plane 1 the hinge's energy term
+// 1/2 kc (psi - psibar)^2, that of plane 2 is 1 for a hinge that acts and 0 otherwise.  k_hinge_gather, one lane per
+// row of a vertex row table (mpm_row_table.h, RowTable<uint32_t>: one row per vertex of the cloths with k > 0, a record
+// is hinge << 2 | corner in ascending hinge id, padding 0xFFFFFFFF adds nothing and reads nothing), reads 8 records at a
+// time and adds the records in stored order to DP::f.  Two passes because one evaluation per hinge then serves its four
+// vertices (a one-pass gather would run shell_hinge four times per hinge, once per corner) and psi and the energy come
+// for free; the price is 64 bytes written and read per hinge.  Table and order are those of the original ids: records,
+// psi and forces are the same bits whatever the particle order.
+//
+// THE dt GUARD (mpm_shell_max_stable_dt): dt <= 2 / sqrt(max_i (1 / m_i) sum_{h contains i} kc dpsibar^2 |Gbar_hi|
+// sum_j |Gbar_hj|), Gershgorin on the Gauss-Newton part of the stiffness, kc dpsi^2 G G^T, taken AT THE REST SHAPE
+// (max_row_rate).  It does not cover the geometric stiffness (psi - psibar) d(dpsi G) / dx of a deformed hinge, nor a
+// deformed hinge's larger |G| (|G2| = |e| / |nA| grows as a triangle collapses): a guard, not a guarantee.  How
+// conservative it is has not been measured.
+//
+// Roundings of one component of one record, for the bound of tests/shell_bending.py, first order, in units of 2^-24 of
+//   T = |kc| |G_hj| (kappa_A + kappa_B) (1 + |psi| + |psibar|),   kappa_A = |e| |a| / |nA|,  kappa_B = |e| |b| / |nB|
+// (the conditioning of the two normals; kappa >= 1, so kappa_A + kappa_B >= 2 and a plain relative rounding of a
+// quantity bounded by |kc| |G_hj| (|psi| + |psibar|) costs at most 1/2 unit):
+//   a normal: a component p - q of e x a carries the roundings of e and a (1 + 1), of each product (1) and of the
+//     subtraction (1) on |p| + |q|, and the vector of those |p| + |q| is at most sqrt(2) |e| |a| long: 4 sqrt(2) < 6
+//     kappa in the direction and the length of a normal
+//   psi: the directions of nAh and nBh, 6 kappa each                                                                 6
+//        their lengths (|n|^2: 3 on the square, 1.5 on the root; the root 1; the reciprocal 1; the product 1 = 4.5
+//        each, which enter |nAh - nBh| at most as they are), the subtraction (1), |d|^2 and its root (2.5):
+//        12.5 in all, at most 6.25 (kappa_A + kappa_B)                                                              6.25
+//        psi - psibar: one rounding of at most |psi| + |psibar|                                                      0.5
+//   dpsi, an absolute error that multiplies |kc| |psi - psibar| |G|: directions 6 kappa each, halved                   3
+//        lengths 4.5 each, halved; the sum (1), |s|^2 and its root (2.5), the half (0): 8 in all, at most              4
+//   m = -(kc (psi - psibar)) dpsi: two products                                                                       1
+//   G2 = -(|e| / |nA|^2) nA: |e| (e: 1, |e|^2: 1.5, the root: 1 = 3.5), |nA|^2 (twice the normal's 6 kappa, and 3),
+//        the division (1), nA's component (6 kappa), the product (1): 18 kappa + 9.5, at most 18 (kappa_A + kappa_B)
+//        - 18 + 9.5 < 18 (kappa_A + kappa_B); likewise G3                                                             18
+//   the record m G_j: one product                                                                                   0.5
+//   corners 0 and 1: wA = (a . e) / |e|^2 (the dot product 4 on |a| |e|, |e|^2 3, the reciprocal 1, the product 1),
+//        1 - wA (1), two products and their sum (2): counted on |wA| |G2| + |wB| |G3|, which is |G_hj| where the two
+//        terms do not cancel                                                                                          6
+//   second-order terms                                                                                               0.75
+// R_shell = 46.  A row with n records adds them in stored order, one rounding of a partial sum per record, each partial
+// sum at most the row's sum of T: R_i = 46 + n_i.  psi alone: at most 13 (kappa_A + kappa_B) (1 + |psi|) 2^-24.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "mpm_row_table.h"
+
+#ifdef __HIPCC__
+#define MPM_SHELL_FN __host__ __device__ inline
+#else
+#define MPM_SHELL_FN inline
+#endif
+
+namespace mpm {
+
+constexpr unsigned SHELL_REST_SHAPE = 0u, SHELL_REST_FLAT = 1u;   // mpm_cloth_shell_t::rest
+constexpr int SHELL_SLICE = 64, SHELL_BATCH = 8;
+constexpr uint32_t SHELL_PAD = 0xFFFFFFFFu;   // the gather table's padding record
+constexpr float SHELL_GATE = 1e-30f;          // a hinge acts while |e|^2, |nA|^2, |nB|^2 >= this
+constexpr float R_SHELL = 46.f;               // the counted roundings of one record (above)
+
+struct ClothShell {   // mirrors mpm_cloth_shell_t (include/mpm_hip.h)
+    float stiffness;
+    uint32_t rest;
+};
+
+// The four corner records rec[j] = f_j of one hinge and its psi; kc = float(k cbar).  false: the hinge does not act
+// (the records and psi are exact zeros).  No branch on the data but the final selection.
+MPM_SHELL_FN bool shell_hinge(const float x0[3], const float x1[3], const float x2[3], const float x3[3], float kc, float psibar,
+                              float rec[4][3], float* psi_out) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const float e0 = x1[0] - x0[0], e1 = x1[1] - x0[1], e2 = x1[2] - x0[2];
+    const float a0 = x2[0] - x0[0], a1 = x2[1] - x0[1], a2 = x2[2] - x0[2];
+    const float b0 = x3[0] - x0[0], b1 = x3[1] - x0[1], b2 = x3[2] - x0[2];
+    // nA = e x a, nB = b x e
+    const float A0 = e1 * a2 - e2 * a1, A1 = e2 * a0 - e0 * a2, A2 = e0 * a1 - e1 * a0;
+    const float B0 = b1 * e2 - b2 * e1, B1 = b2 * e0 - b0 * e2, B2 = b0 * e1 - b1 * e0;
+    const float ee = (e0 * e0 + e1 * e1) + e2 * e2;
+    const float AA = (A0 * A0 + A1 * A1) + A2 * A2;
+    const float BB = (B0 * B0 + B1 * B1) + B2 * B2;
+    const bool on = (ee >= SHELL_GATE) & (AA >= SHELL_GATE) & (BB >= SHELL_GATE);
+    const float le = sqrtf(ee), lA = sqrtf(AA), lB = sqrtf(BB);
+    const float rA = 1.f / lA, rB = 1.f / lB;
+    const float hA0 = A0 * rA, hA1 = A1 * rA, hA2 = A2 * rA;
+    const float hB0 = B0 * rB, hB1 = B1 * rB, hB2 = B2 * rB;
+    const float d0 = hA0 - hB0, d1 = hA1 - hB1, d2 = hA2 - hB2;
+    const float s0 = hA0 + hB0, s1 = hA1 + hB1, s2 = hA2 + hB2;
+    // the sign of theta: e . (nA x nB)
+    const float c0 = A1 * B2 - A2 * B1, c1 = A2 * B0 - A0 * B2, c2 = A0 * B1 - A1 * B0;
+    const float t = (e0 * c0 + e1 * c1) + e2 * c2;
+    const float mag = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+    const float psi = t >= 0.f ? mag : -mag;
+    const float dpsi = .5f * sqrtf((s0 * s0 + s1 * s1) + s2 * s2);
+    const float m = -(kc * (psi - psibar)) * dpsi;
+    const float gA = le / AA, gB = le / BB;   // G2 = -gA nA, G3 = -gB nB
+    const float re = 1.f / ee;
+    const float wA = ((a0 * e0 + a1 * e1) + a2 * e2) * re, wB = ((b0 * e0 + b1 * e1) + b2 * e2) * re;
+    const float uA = 1.f - wA, uB = 1.f - wB;
+    const float nA[3] = {A0, A1, A2}, nB[3] = {B0, B1, B2};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float f2 = m * -(gA * nA[k]), f3 = m * -(gB * nB[k]);
+        const float f1 = -(wA * f2 + wB * f3), f0 = -(uA * f2 + uB * f3);
+        rec[0][k] = on ? f0 : 0.f;
+        rec[1][k] = on ? f1 : 0.f;
+        rec[2][k] = on ? f2 : 0.f;
+        rec[3][k] = on ? f3 : 0.f;
+    }
+    *psi_out = on ? psi : 0.f;
+    return on;
+}
+
+// the hinge's energy term 1/2 kc (psi - psibar)^2, in float (the .w of plane 1)
+MPM_SHELL_FN float shell_energy_term(float kc, float psibar, float psi) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const float d = psi - psibar;
+    return (.5f * kc) * (d * d);
+}
+
+}  // namespace mpm
+
+#ifdef __HIPCC__
+#include "mpm_step.h"
+
+namespace mpm {
+
+struct HingeArgs {
+    const int4* ids;     // [hinge] particle ids (NfG + vertex) of x0, x1, x2, x3
+    const float2* par;   // [hinge] (kc, psibar)
+    float4* rec;         // [4][n] the corner records; .w: psi (plane 0), the energy term (1), 1 where the hinge acts (2)
+    int n;
+};
+struct ShellArgs {
+    const int* row_pid;          // [n_rows] particle id (NfG + vertex) of the row's vertex, ascending
+    const unsigned* slice_off;   // [slices + 1] first record of a slice; its width is (next - this) / 64
+    const unsigned* ent;         // records hinge << 2 | corner, SHELL_PAD: nothing
+    int n_rows;
+    const float4* rec;           // HingeArgs::rec
+    int n_hinges;
+};
+
+// the four planes of hinge h from four positions (what k_hinge, k_hinge_eval and k_hinge_rest share)
+MPM_DEV void hinge_store(const HingeArgs& a, int h, const float4 x[4], bool usable) {
+    const float2 q = a.par[h];
+    const float X[4][3] = {{x[0].x, x[0].y, x[0].z}, {x[1].x, x[1].y, x[1].z}, {x[2].x, x[2].y, x[2].z}, {x[3].x, x[3].y, x[3].z}};
+    float rec[4][3], psi;
+    const bool on = shell_hinge(X[0], X[1], X[2], X[3], q.x, q.y, rec, &psi) && usable;
+    const float w[4] = {on ? psi : 0.f, on ? shell_energy_term(q.x, q.y, psi) : 0.f, on ? 1.f : 0.f, 0.f};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        a.rec[(size_t)j * (size_t)a.n + (size_t)h] = on ? make_float4(rec[j][0], rec[j][1], rec[j][2], w[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// Hinge h on the current positions.  Every index into a per-particle array comes through DP::imap from an id of the
+// host-built table; an id outside the particle numbering or a slot that is no vertex slot is reported, never used as an
+// address: the hinge's records are then exact zeros.
+MPM_DEV void hinge_on_state(const DP& p, const PSet& S, const HingeArgs& a, int h, bool& bad) {
+    const int4 id = a.ids[h];
+    const int c[4] = {id.x, id.y, id.z, id.w};
+    int s[4];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ok = ok && c[j] >= p.NfG && c[j] < p.NpG;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = ok ? p.imap[c[j]] : -1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ok = ok && s[j] >= p.Nf && s[j] < p.Np;
+    float4 x[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = ok ? S.q[0][s[j]] : make_float4(0.f, 0.f, 0.f, 0.f);
+    bad |= !ok;
+    hinge_store(a, h, x, ok);
+}
+
+// Behind k_pressure (and k_vforce, k_bend, k_bend_damp, k_link) on the same stream, with the substep's DP: a substep that
+// skips itself (and is run again by the host) writes nothing and adds nothing, so that the force is added once.
+__global__ __launch_bounds__(256) void k_hinge(DP p, HingeArgs a) {
+    if (gated_out(p)) return;
+    const int h = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool bad = false;
+    if (h < a.n) hinge_on_state(p, p.set[p.ctl->cur], a, h, bad);
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
+}
+// mpm_shell_forces, mpm_shell_state: the same records without the gate
+__global__ __launch_bounds__(256) void k_hinge_eval(DP p, HingeArgs a) {
+    const int h = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool bad = false;
+    if (h < a.n) hinge_on_state(p, p.set[p.ctl->cur], a, h, bad);
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
+}
+// mpm_set_shell_bending: the same function on rest positions in original vertex order, pos[3 n_verts]; a.ids hold
+// particle ids, `nfg` is taken off.  The host has checked every id.  What it leaves in plane 0's .w is psibar.
+__global__ __launch_bounds__(256) void k_hinge_rest(HingeArgs a, const float* pos, int nfg, int n_verts) {
+    const int h = (int)(blockIdx.x * 256 + threadIdx.x);
+    if (h >= a.n) return;
+    const int4 id = a.ids[h];
+    const int c[4] = {id.x - nfg, id.y - nfg, id.z - nfg, id.w - nfg};
+    bool ok = true;
+    float4 x[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ok = ok && c[j] >= 0 && c[j] < n_verts;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float* q = pos + 3 * (size_t)(ok ? c[j] : 0);
+        x[j] = make_float4(q[0], q[1], q[2], 0.f);
+    }
+    hinge_store(a, h, x, ok);
+}
+
+// Row r of the gather table: the records of the row's vertex, added in stored order.  A record that names no hinge of
+// the table is reported and adds nothing.  false: the row's own vertex has no slot.
+MPM_DEV bool shell_row(const DP& p, const ShellArgs& a, int r, int& s_out, float f[3], bool& bad) {
+    const unsigned b0 = a.slice_off[r >> 6], b1 = a.slice_off[(r >> 6) + 1];
+    const int width = (int)((b1 - b0) / SHELL_SLICE);
+    const int s = p.imap[a.row_pid[r]];
+    s_out = s;
+    if (s < p.Nf || s >= p.Np) {
+        bad = true;
+        return false;
+    }
+    const unsigned* ent = a.ent + b0 + (r & 63);
+    float f0 = 0.f, f1 = 0.f, f2 = 0.f;
+    // SHELL_BATCH records at a time: the records, then the corner records they name -- two round trips of independent
+    // loads per batch.  A record past the width loads nothing and enters as padding.
+    for (int e0 = 0; e0 < width; e0 += SHELL_BATCH) {
+        unsigned q[SHELL_BATCH];
+        float4 g[SHELL_BATCH];
+        bool live[SHELL_BATCH];
+#pragma unroll
+        for (int u = 0; u < SHELL_BATCH; ++u) {
+            q[u] = SHELL_PAD;
+            if (e0 + u < width) q[u] = ent[(size_t)(e0 + u) * SHELL_SLICE];
+        }
+#pragma unroll
+        for (int u = 0; u < SHELL_BATCH; ++u) {
+            const unsigned h = q[u] >> 2, j = q[u] & 3u;
+            live[u] = q[u] != SHELL_PAD && h < (unsigned)a.n_hinges;
+            bad |= q[u] != SHELL_PAD && !live[u];
+            g[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live[u]) g[u] = a.rec[(size_t)j * (size_t)a.n_hinges + (size_t)h];
+        }
+#pragma unroll
+        for (int u = 0; u < SHELL_BATCH; ++u)   // (in stored order; padding adds nothing)
+            if (live[u]) {
+                f0 += g[u].x;
+                f1 += g[u].y;
+                f2 += g[u].z;
+            }
+    }
+    f[0] = f0; f[1] = f1; f[2] = f2;
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_hinge_gather(DP p, ShellArgs a) {
+    if (gated_out(p)) return;
+    const int r = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool bad = false;
+    if (r < a.n_rows) {
+        int s;
+        float f[3];
+        if (shell_row(p, a, r, s, f, bad)) {
+            p.f[0][s] += f[0];
+            p.f[1][s] += f[1];
+            p.f[2][s] += f[2];
+        }
+    }
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
+}
+
+// mpm_shell_forces: out[3 (pid - NfG) ..] = the row's force (vertices without a row stay as the caller left them: zero)
+__global__ __launch_bounds__(256) void k_hinge_gather_eval(DP p, ShellArgs a, float* out) {
+    const int r = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool bad = false;
+    if (r < a.n_rows) {
+        int s;
+        float f[3];
+        if (shell_row(p, a, r, s, f, bad)) {
+            float* o = out + 3 * (size_t)(a.row_pid[r] - p.NfG);
+            o[0] = f[0]; o[1] = f[1]; o[2] = f[2];
+        }
+    }
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
+}
+
+}  // namespace mpm
+#endif  // __HIPCC__
+
+namespace mpm {
+
+// ---- host: the hinge list, the rest quantities, the gather table, the guard's rate ----------------------------------
+struct ShellHinge {
+    int32_t v[4];           // x0, x1, x2, x3 in the numbering of `idx`
+    int32_t face_a, face_b; // face A (the lower id) and face B
+};
+
+// The hinges of the faces idx[3 n_faces] in ascending (min(v0, v1), max(v0, v1)): every edge shared by exactly two
+// faces; x0 -> x1 as face A runs it.  The ids must be valid (the caller checks).
+inline void mesh_hinges(const int32_t* idx, size_t n_faces, std::vector<ShellHinge>& out) {
+    struct Side {
+        int32_t u, v, from, to, w, face;   // edge (u < v), as the face runs it (from -> to), the vertex opposite, the face
+    };
+    std::vector<Side> sides;
+    sides.reserve(3 * n_faces);
+    for (size_t f = 0; f < n_faces; ++f)
+        for (int c = 0; c < 3; ++c) {
+            const int32_t a = idx[3 * f + c], b = idx[3 * f + (c + 1) % 3], w = idx[3 * f + (c + 2) % 3];
+            sides.push_back(Side{std::min(a, b), std::max(a, b), a, b, w, (int32_t)f});
+        }
+    std::sort(sides.begin(), sides.end(), [](const Side& p, const Side& q) {
+        return p.u != q.u ? p.u < q.u : (p.v != q.v ? p.v < q.v : p.face < q.face);
+    });
+    out.clear();
+    for (size_t k = 0; k < sides.size();) {
+        size_t m = k + 1;
+        while (m < sides.size() && sides[m].u == sides[k].u && sides[m].v == sides[k].v) ++m;
+        if (m - k == 2 && sides[k].u != sides[k].v) {
+            const Side &A = sides[k], &B = sides[k + 1];
+            out.push_back(ShellHinge{{A.from, A.to, A.w, B.w}, A.face, B.face});
+        }
+        k = m;
+    }
+}
+
+// What the host needs of one hinge at a rest shape, in double from float positions
+struct ShellRest {
+    double cbar;        // 3 |e|^2 / (A_A + A_B)
+    double dpsi;        // cos(theta / 2)
+    double G[4];        // |G_j|
+    int degenerate;     // 0: fine; 1: the edge has zero length; 2: face A has zero area; 3: face B
+};
+inline ShellRest shell_rest(const float* x0, const float* x1, const float* x2, const float* x3) {
+    ShellRest r{};
+    double e[3], a[3], b[3];
+    for (int k = 0; k < 3; ++k) {
+        e[k] = (double)x1[k] - (double)x0[k];
+        a[k] = (double)x2[k] - (double)x0[k];
+        b[k] = (double)x3[k] - (double)x0[k];
+    }
+    const double nA[3] = {e[1] * a[2] - e[2] * a[1], e[2] * a[0] - e[0] * a[2], e[0] * a[1] - e[1] * a[0]};
+    const double nB[3] = {b[1] * e[2] - b[2] * e[1], b[2] * e[0] - b[0] * e[2], b[0] * e[1] - b[1] * e[0]};
+    const double ee = e[0] * e[0] + e[1] * e[1] + e[2] * e[2];
+    const double lA = std::sqrt(nA[0] * nA[0] + nA[1] * nA[1] + nA[2] * nA[2]), lB = std::sqrt(nB[0] * nB[0] + nB[1] * nB[1] + nB[2] * nB[2]);
+    const double areas = .5 * lA + .5 * lB;
+    r.degenerate = !(ee > 0.0) || !std::isfinite(ee) ? 1 : (!(lA > 0.0) || !std::isfinite(lA) ? 2 : (!(lB > 0.0) || !std::isfinite(lB) ? 3 : 0));
+    if (r.degenerate) return r;
+    r.cbar = 3.0 * ee / areas;
+    if (!std::isfinite(r.cbar)) {
+        r.degenerate = 2;
+        return r;
+    }
+    double s2 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        const double s = nA[k] / lA + nB[k] / lB;
+        s2 += s * s;
+    }
+    r.dpsi = .5 * std::sqrt(s2);
+    const double le = std::sqrt(ee), gA = le / (lA * lA), gB = le / (lB * lB);
+    const double wA = (a[0] * e[0] + a[1] * e[1] + a[2] * e[2]) / ee, wB = (b[0] * e[0] + b[1] * e[1] + b[2] * e[2]) / ee;
+    double g0 = 0.0, g1 = 0.0;
+    for (int k = 0; k < 3; ++k) {
+        const double G2 = -gA * nA[k], G3 = -gB * nB[k];
+        const double G1 = -(wA * G2 + wB * G3), G0 = -((1.0 - wA) * G2 + (1.0 - wB) * G3);
+        g0 += G0 * G0;
+        g1 += G1 * G1;
+    }
+    r.G[0] = std::sqrt(g0);
+    r.G[1] = std::sqrt(g1);
+    r.G[2] = gA * lA;
+    r.G[3] = gB * lB;
+    return r;
+}
+
+// What mpm_set_shell_bending refuses before it looks at a mesh; empty: the numbers are fine
+inline std::string shell_refusal(const ClothShell* t, size_t n) {
+    for (size_t c = 0; c < n; ++c) {
+        const std::string at = "shell bending: cloth " + std::to_string(c);
+        if (!(std::isfinite(t[c].stiffness) && t[c].stiffness >= 0.f)) return at + ": the stiffness is negative or not finite";
+        if (t[c].rest > SHELL_REST_FLAT) return at + ": unknown rest";
+    }
+    return std::string();
+}
+
+// The gather table of a hinge list: ids4 [4 n] vertex ids; row_vertex: the vertices with a row, ascending; nf: the faces in
+// front.  A row's records are hinge << 2 | corner in ascending hinge id.  Needs no positions.
+inline bool shell_rows(const int32_t* ids4, size_t n_hinges, const std::vector<int>& row_vertex, size_t nf, size_t slice,
+                       RowTable<uint32_t>& out, std::string& why) {
+    out = RowTable<uint32_t>{};
+    const size_t n_rows = row_vertex.size();
+    std::vector<std::vector<uint32_t>> rows(n_rows);
+    for (size_t h = 0; h < n_hinges; ++h)
+        for (int j = 0; j < 4; ++j) {
+            const auto it = std::lower_bound(row_vertex.begin(), row_vertex.end(), (int)ids4[4 * h + j]);
+            if (it == row_vertex.end() || *it != (int)ids4[4 * h + j]) {
+                why = "shell bending: a hinge names a vertex without a row";
+                return false;
+            }
+            rows[(size_t)(it - row_vertex.begin())].push_back((uint32_t)h << 2 | (uint32_t)j);
+        }
+    for (size_t r = 0; r < n_rows; ++r) out.row_pid.push_back((int)(nf + (size_t)row_vertex[r]));
+    if (!sliced_ell(n_rows, slice, [&](size_t r) { return rows[r].size(); }, [&](size_t r, size_t q) { return rows[r][q]; },
+                    [&](size_t) { return SHELL_PAD; }, out.slice_off, out.ent)) {
+        why = "shell bending: the table is too large";
+        return false;
+    }
+    return true;
+}
+
+// The tables of all cloths as the host lays them out (no device is touched)
+struct ShellTable : RowTable<uint32_t> {   // the gather table: one row per vertex of the cloths with k > 0
+    std::vector<int32_t> ids4;      // [4 hinge] vertex ids (0-based over all cloths) of x0, x1, x2, x3
+    std::vector<float> kc;          // [hinge] float(k cbar)
+    std::vector<int> hinge_cloth;   // [hinge]
+    std::vector<int> row_vertex;    // [row] its vertex
+    std::vector<double> rate_sum;   // [row] sum_h kc dpsibar^2 |Gbar_hi| sum_j |Gbar_hj| (the guard)
+};
+
+// cloths: anything with first_vertex, n_verts, first_face, n_faces; h_idx: the faces' vertex ids (0-based over all
+// cloths); par: one ClothShell per cloth (stiffness 0: the cloth has no hinge and no row); shape: [3 n_verts] the
+// positions that give cbar of every cloth (and the guard's geometry; for a cloth with MPM_SHELL_REST_FLAT the guard
+// takes dpsibar = 1); nf: the faces in front; slice: rows per slice (SHELL_SLICE).  false with `why` set: a hinge of a cloth with k > 0 has a
+// zero rest edge or a zero rest area (the face is named), or the tables do not fit.
+template <class Cloth>
+inline bool shell_table(const std::vector<Cloth>& cloths, const int* h_idx, size_t nf, const ClothShell* par, const float* shape,
+                        size_t slice, ShellTable& out, std::string& why) {
+    out = ShellTable{};
+    for (size_t c = 0; c < cloths.size(); ++c) {
+        if (!(par[c].stiffness > 0.f)) continue;
+        const Cloth& cl = cloths[c];
+        std::vector<ShellHinge> H;
+        mesh_hinges(h_idx + 3 * cl.first_face, cl.n_faces, H);
+        const size_t row0 = out.row_vertex.size();
+        for (size_t v = 0; v < cl.n_verts; ++v) {
+            out.row_vertex.push_back((int)(cl.first_vertex + v));
+            out.rate_sum.push_back(0.0);
+        }
+        for (const ShellHinge& h : H) {
+            const size_t id = out.kc.size();
+            if (!(id < ((size_t)1 << 30) - 1)) {
+                why = "shell bending: too many hinges";
+                return false;
+            }
+            const ShellRest r = shell_rest(shape + 3 * (size_t)h.v[0], shape + 3 * (size_t)h.v[1], shape + 3 * (size_t)h.v[2],
+                                           shape + 3 * (size_t)h.v[3]);
+            if (r.degenerate) {
+                const size_t face = cl.first_face + (size_t)(r.degenerate == 3 ? h.face_b : h.face_a);
+                why = "shell bending: face " + std::to_string(face) +
+                      (r.degenerate == 1 ? " has a hinge edge of zero rest length" : " has zero rest area");
+                return false;
+            }
+            const float kc = (float)((double)par[c].stiffness * r.cbar);
+            if (!std::isfinite(kc)) {
+                why = "shell bending: face " + std::to_string(cl.first_face + (size_t)h.face_a) + ": k cbar is not a finite float";
+                return false;
+            }
+            const double dpsi = par[c].rest == SHELL_REST_FLAT ? 1.0 : r.dpsi;
+            const double gsum = ((r.G[0] + r.G[1]) + r.G[2]) + r.G[3];
+            for (int j = 0; j < 4; ++j) {
+                out.ids4.push_back(h.v[j]);
+                const size_t row = row0 + ((size_t)h.v[j] - cl.first_vertex);
+                out.rate_sum[row] += (double)kc * dpsi * dpsi * r.G[j] * gsum;
+            }
+            out.kc.push_back(kc);
+            out.hinge_cloth.push_back((int)c);
+        }
+    }
+    RowTable<uint32_t> rows;
+    if (!shell_rows(out.ids4.data(), out.kc.size(), out.row_vertex, nf, slice, rows, why)) return false;
+    static_cast<RowTable<uint32_t>&>(out) = rows;
+    return true;
+}
+
+}  // namespace mpm

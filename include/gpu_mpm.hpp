@@ -320,6 +320,38 @@ struct GpuMpmState {
     static void PressureVertexForce(float g, const float x_own[3], size_t n, const float* x_b, const float* x_c, float f_out[3]) {
         mpm_check(mpm_pressure_vertex_force(g, x_own, n, x_b, x_c, f_out));
     }
+    // Extension: shell bending about a curved rest shape (mpm_set_shell_bending), the hinge-angle model in psi = 2 sin(theta / 2)
+    // -- one entry per cloth in AddQRCloth order; rest_pos: 3 floats per vertex in the numbering of DumpCpuState, or empty:
+    // the mesh as added.  All zeros or an empty vector switches it off.  A synchronisation point, like SetBending.
+    void SetShellBending(const std::vector<mpm_cloth_shell_t>& per_cloth, const std::vector<float>& rest_pos = {}) {
+        mpm_check(mpm_set_shell_bending(h_, per_cloth.size(), per_cloth.data(), rest_pos.empty() ? nullptr : rest_pos.data()));
+    }
+    std::vector<mpm_cloth_shell_t> GetShellBending() const {
+        size_t n = 0;
+        mpm_check(mpm_get_shell_bending(h_, nullptr, 0, &n));
+        std::vector<mpm_cloth_shell_t> out(n);
+        mpm_check(mpm_get_shell_bending(h_, out.data(), n, &n));
+        return out;
+    }
+    // the shell force on the current positions, 3 floats per vertex in the numbering of DumpCpuState
+    std::vector<float> ShellForces(size_t n_verts) const {
+        std::vector<float> f(3 * n_verts);
+        mpm_check(mpm_shell_forces(h_, f.data()));
+        return f;
+    }
+    // the shell energy of every cloth on the current positions (not part of Measure's record)
+    std::vector<double> ShellEnergy(size_t n_cloths) const {
+        std::vector<double> e(n_cloths);
+        mpm_check(mpm_shell_state(h_, e.data(), nullptr, nullptr));
+        return e;
+    }
+    // the dt above which the substep entry points refuse an engine with shell bending (+inf while it is off); a guard at
+    // the rest shape
+    float ShellMaxStableDt() const {
+        float dt = 0.f;
+        mpm_check(mpm_shell_max_stable_dt(h_, &dt));
+        return dt;
+    }
     // Extension: the per-cloth report (mpm_measure) -- masses, momenta, kinetic, potential, elastic and bending energies,
     // strain extremes, reduced on the device in double.  One row per cloth; `total`, if given, receives their sum.
     // System::CalcKineticEnergy is total.kinetic + total.kinetic_affine, CalcPotentialEnergy is gravity_potential +

@@ -993,6 +993,92 @@ MPM_API int mpm_mesh_is_closed(const int32_t *indices, size_t n_faces, size_t n_
 MPM_API int mpm_pressure_vertex_force(float g, const float x_own[3], size_t n, const float *x_b, const float *x_c,
                                       float f_out[3]);
 
+/* ---- Shell bending about a curved rest shape: the hinge-angle model (an extension) ----
+ * mpm_set_bending's quadratic model is defined for a rest shape that is flat per hinge: it pulls a ball, a sleeve or a
+ * pre-formed cup towards a flat sheet and its energy is not zero on the shape the caller built.  mpm_set_shell_bending
+ * bends about the rest shape's own dihedral angles (discrete shells), in the variable psi = 2 sin(theta / 2).
+ * Hinges are exactly those of mpm_set_bending: every edge shared by exactly two faces of one cloth; boundary edges and
+ * edges with more than two faces form none.  A hinge is (x0, x1 | x2, x3): x0 -> x1 is the edge as face A, the face
+ * with the lower id, runs it; x2 is opposite the edge in face A, x3 in face B.  The hinges of the cloths with k > 0 are
+ * numbered in ascending (cloth, min(v0, v1), max(v0, v1)).  All quantities are differences against x0:
+ *   e = x1 - x0,  a = x2 - x0,  b = x3 - x0,   nA = e x a,  nB = b x e             (parallel on a flat hinge)
+ *   nAh = nA / |nA|,  nBh = nB / |nB|,  sigma = +1 where e . (nA x nB) >= 0, else -1
+ *   psi  = sigma |nAh - nBh| = 2 sin(theta / 2),   theta the signed dihedral angle, 0 on a flat hinge
+ *   dpsi = 1/2 |nAh + nBh|   = cos(theta / 2)
+ *   E_h  = 1/2 k cbar (psi - psibar)^2,   cbar = 3 |ebar|^2 / (Abar_A + Abar_B)   (rest edge length and rest areas)
+ *   f_j  = -k cbar (psi - psibar) dpsi G_j,   G_j = grad_{x_j} theta,   G2 = -|e| nA / |nA|^2,  G3 = -|e| nB / |nB|^2,
+ *          G1 = -(wA G2 + wB G3),  G0 = -((1 - wA) G2 + (1 - wB) G3),   wA = a . e / |e|^2,  wB = b . e / |e|^2
+ * in float, every operation written out, no contraction, no trigonometric function; the square roots and divisions are
+ * correctly rounded whatever mpm_set_fast_math says.  Differences only: the force is translation invariant to the bit.
+ * k is in N m and means what mpm_set_bending's k means: with psibar = 0 the energy of a hinge whose two triangles move
+ * rigidly equals the quadratic model's, so this model is its rotation-invariant continuation to curved rest shapes.
+ * It is bounded (no infinite force).  ITS WEAKNESS: dpsi -> 0 as |theta| -> pi, so a hinge folded flat onto itself
+ * feels no restoring force, and psi jumps from 2 to -2 there: the energy is discontinuous for psibar != 0 while the
+ * force is continuous.
+ * The rest shape: per cloth, MPM_SHELL_REST_SHAPE takes psibar and cbar from rest_pos (3 * n_verts floats in the vertex
+ * numbering of mpm_dump_cpu_state; only the cloth's own vertices are read) where rest_pos is given, else from the mesh
+ * as added; MPM_SHELL_REST_FLAT sets psibar = 0 and takes cbar from the mesh as added.  psibar is not computed on the
+ * host: the call runs the hinge function on the device once on the rest positions and keeps the psi it wrote, so on
+ * those positions psi - psibar is an exact zero and every vertex force is +-0: the rest shape is an exact equilibrium.
+ * cbar is formed in double on the host and k cbar rounded to float once.  A hinge acts only while |e|^2, |nA|^2 and
+ * |nB|^2 are all >= 1e-30; otherwise its records are exact zeros and it counts as inactive: never a NaN or an infinity.
+ * The force joins the vertex forces of CalcFemStateAndForce (MPM_ARR_FORCES includes it): two kernels behind the
+ * vertex-force, bending, link and pressure kernels, counted under MPM_PHASE_VFORCE -- one lane per hinge writes the four
+ * corner records, one lane per vertex adds its records in ascending hinge id, no atomics: records, psi and forces are
+ * the same bits whatever the particle order.  A cloth may have mpm_set_bending and this on: the forces add.
+ * Stiffness-proportional damping of these hinges is not provided: mpm_set_damping's bending part acts on the quadratic
+ * model only.  It works with pins, per-cloth materials, grid bodies, force fields, bending, damping, links, pressure,
+ * deterministic mode, fast math and the coupled path.
+ * STABILITY GUARD: the substep entry points that check mpm_bending_max_stable_dt refuse, before anything is enqueued,
+ *   dt > mpm_shell_max_stable_dt = 2 / sqrt(max_i (1 / m_i) sum_{h contains i} k cbar dpsibar^2 |Gbar_hi| sum_j |Gbar_hj|)
+ * (Gershgorin on the Gauss-Newton part of the stiffness).  It is a guard AT THE REST SHAPE: it does not cover the
+ * geometric stiffness of a deformed hinge, nor the larger |G| of a hinge whose triangles have collapsed.  How
+ * conservative it is has not been measured.  +inf while the feature is off.
+ * mpm_set_shell_bending replaces the table (all-zero stiffness or n_cloths = 0 switches the feature off, the table may
+ * then be NULL; otherwise n_cloths must equal mpm_cloth_count); it needs mpm_finalize, is ordered on the engine's stream
+ * and is a synchronisation point; substeps that mpm_run_substeps still owes are run first, with the table they were
+ * enqueued with.  With the feature off the engine launches exactly what it launches without this call.  While it is on
+ * the engine does not use the re-sort's quiet-time estimate, and every batched substep launches the vertex-force kernel.
+ * Refused with MPM_ERR_INVALID, the previous table staying in force and nothing enqueued: a call before mpm_finalize; a
+ * wrong n_cloths; a negative or non-finite stiffness; an unknown rest; a non-finite rest_pos; a zero rest area or a zero
+ * rest edge at a hinge of a cloth with k > 0 (the message names the face); any partitioned or multi-rank engine -- this
+ * call on such an engine, and mpm_dist_init, the halo, chain, team and world substeps on an engine with it on. */
+#define MPM_SHELL_REST_SHAPE 0u   /* psibar from rest_pos where given, else from the mesh as added */
+#define MPM_SHELL_REST_FLAT 1u    /* psibar = 0 */
+typedef struct mpm_cloth_shell {
+    float stiffness;   /* k in N m, >= 0; 0: the cloth has no hinge */
+    uint32_t rest;     /* MPM_SHELL_REST_* */
+} mpm_cloth_shell_t;
+MPM_API int mpm_set_shell_bending(mpm_handle_t h, size_t n_cloths, const mpm_cloth_shell_t *per_cloth,
+                                  const float *rest_pos /* [3 n_verts] or NULL */);
+/* The table as given: min(n, capacity) entries into out (may be NULL when capacity is 0), the cloth count into *n_out.
+ * Zeros while the feature is off. */
+MPM_API int mpm_get_shell_bending(mpm_handle_t h, mpm_cloth_shell_t *out, size_t capacity, size_t *n_out);
+/* The hinge table in force (the hinges of the cloths with k > 0, in hinge order): min(n, capacity) hinges into ids4
+ * (4 vertex ids x0, x1, x2, x3 each, in the numbering of mpm_dump_cpu_state), kc (float(k cbar)) and psibar (what the
+ * device wrote on the rest positions; 0 for MPM_SHELL_REST_FLAT); the hinge count into *n_out.  The outputs may be
+ * NULL when capacity is 0. */
+MPM_API int mpm_shell_hinges(mpm_handle_t h, int32_t *ids4, float *kc, float *psibar, size_t capacity, size_t *n_out);
+/* The shell force on the current positions: f_out[3 * n_verts], in the vertex numbering of mpm_dump_cpu_state (zeros for
+ * the vertices of cloths without it).  The device functions of the substep's kernels; changes no state. */
+MPM_API int mpm_shell_forces(mpm_handle_t h, float *f_out);
+/* On the current positions: energy_per_cloth[mpm_cloth_count] = sum of the hinges' float terms 1/2 kc (psi - psibar)^2,
+ * as the hinge kernel forms them, added in double in hinge order (a fixed order, no atomics: the same bits whatever
+ * the particle order); psi_out (one per hinge of mpm_shell_hinges, may be NULL): the hinge's psi, 0 for an inactive
+ * one; inactive_out (may be NULL): how many hinges do not act.  This energy is not part of mpm_measure's record.
+ * Changes no state. */
+MPM_API int mpm_shell_state(mpm_handle_t h, double *energy_per_cloth, float *psi_out, uint32_t *inactive_out);
+MPM_API int mpm_shell_max_stable_dt(mpm_handle_t h, float *dt_out);
+/* Host only (no handle, no device): the hinges of a mesh as mpm_set_shell_bending finds them for one cloth.  indices:
+ * 3 * n_faces vertex ids in [0, n_verts).  min(n, capacity) hinges into ids4 (x0, x1, x2, x3 each; may be NULL when
+ * capacity is 0), the hinge count into *n_out.  MPM_ERR_INVALID for an id out of range. */
+MPM_API int mpm_mesh_hinges(const int32_t *indices, size_t n_faces, size_t n_verts, int32_t *ids4, size_t capacity,
+                            size_t *n_out);
+/* Host only: the inline function the hinge kernel calls, compiled for the host.  x12: x0, x1, x2, x3; kc = float(k
+ * cbar); rec12_out: the four corner records f_0 .. f_3; psi_out (may be NULL): the hinge's psi.  Returns 1 where the
+ * hinge acts, 0 where it does not (exact zeros), a negative code on a null argument. */
+MPM_API int mpm_shell_hinge(const float x12[12], float kc, float psibar, float rec12_out[12], float *psi_out);
+
 /* ---- Energy, momentum and strain report per cloth (an extension) ----
  * What System::CalcKineticEnergy / CalcPotentialEnergy answer for a Drake plant, and what a caller choosing dt or
  * calibrating a stiffness needs: one device-side reduction instead of seven downloads and a host restatement of the
