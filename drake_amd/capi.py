@@ -83,6 +83,39 @@ class BodyMotion(C.Structure):
                          (C.c_float * 3)(*[float(x) for x in v]), (C.c_float * 3)(*[float(x) for x in w]))
 
 
+ANCHOR_TENSION_ONLY = 1
+# mpm_anchor_t (36 bytes) as a numpy record: GpuMpm.set_anchors also takes, and get_anchors returns, arrays of it
+ANCHOR_DTYPE = np.dtype([("vertex", "<u4"), ("body", "<u4"), ("p_BQ", "<f4", (3,)), ("stiffness", "<f4"), ("rest_length", "<f4"),
+                         ("damping", "<f4"), ("flags", "<u4")])
+assert ANCHOR_DTYPE.itemsize == 36
+
+
+class Anchor(C.Structure):
+    """mpm_anchor_t (include/mpm_hip.h): vertex `vertex` joined to the point p_BQ (body frame) of body `body` by a spring
+    (rest_length > 0), a zero-length spring (rest_length 0) or, with ANCHOR_TENSION_ONLY, a cord."""
+    _fields_ = [("vertex", C.c_uint32), ("body", C.c_uint32), ("p_BQ", C.c_float * 3), ("stiffness", C.c_float),
+                ("rest_length", C.c_float), ("damping", C.c_float), ("flags", C.c_uint32)]
+
+    def __init__(self, vertex=0, body=0, p_BQ=(0, 0, 0), stiffness=0.0, rest_length=0.0, damping=0.0, flags=0):
+        super().__init__(int(vertex), int(body), (C.c_float * 3)(*[float(x) for x in p_BQ]), float(stiffness), float(rest_length),
+                         float(damping), int(flags))
+
+
+assert C.sizeof(Anchor) == 36
+
+
+def anchor_point(motion, t, p_BQ):
+    """mpm_anchor_point: (y (3,), v_Q (3,)) float32, the attachment point p_BQ of a body with the BodyMotion `motion` at
+    clock t and its velocity, evaluated on the host by the functions the kernels call.  Needs no engine and no GPU."""
+    lib = load_library()
+    q = np.ascontiguousarray(p_BQ, np.float32).reshape(3)
+    y, vq = np.zeros(3, np.float32), np.zeros(3, np.float32)
+    rc = lib.mpm_anchor_point(C.byref(motion), float(t), q.ctypes.data, y.ctypes.data, vq.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return y, vq
+
+
 class GridCollider(C.Structure):
     """mpm_grid_collider_t: shape 0 sphere / 1 half-space; mode 0 fixed / 1 slip while approaching / 2 slip."""
     _fields_ = [("shape", C.c_int32), ("mode", C.c_int32), ("p", C.c_float * 3), ("n", C.c_float * 3),
@@ -465,6 +498,8 @@ SYMBOLS = [
     "mpm_bending_max_stable_dt", "mpm_bending_matrix", "mpm_measure", "mpm_face_strain", "mpm_cloth_energy_density",
     "mpm_set_damping", "mpm_get_damping", "mpm_damping_forces", "mpm_damping_max_stable_dt", "mpm_damping_face_records",
     "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
+    "mpm_set_anchors", "mpm_get_anchors", "mpm_anchor_forces", "mpm_anchor_state", "mpm_anchors_max_stable_dt",
+    "mpm_anchor_point",
     "mpm_set_pressure", "mpm_get_pressure", "mpm_pressure_forces", "mpm_pressure_state", "mpm_mesh_is_closed",
     "mpm_pressure_vertex_force",
     "mpm_set_shell_bending", "mpm_get_shell_bending", "mpm_shell_hinges", "mpm_shell_forces", "mpm_shell_state",
@@ -601,6 +636,12 @@ def load_library(build: bool = True):
         "mpm_link_energy": [vp, P(C.c_double), vp],
         "mpm_links_max_stable_dt": [vp, P(f)],
         "mpm_link_force": [vp, vp, vp, vp, vp, vp],
+        "mpm_set_anchors": [vp, sz, vp],
+        "mpm_get_anchors": [vp, vp, sz, P(sz)],
+        "mpm_anchor_forces": [vp, vp],
+        "mpm_anchor_state": [vp, P(C.c_double), vp, vp, P(C.c_double)],
+        "mpm_anchors_max_stable_dt": [vp, P(f)],
+        "mpm_anchor_point": [vp, C.c_double, vp, vp, vp],
         "mpm_set_pressure": [vp, sz, vp],
         "mpm_get_pressure": [vp, vp, sz, P(sz)],
         "mpm_pressure_forces": [vp, vp],
@@ -1327,6 +1368,54 @@ class GpuMpm:
         n = C.c_size_t()
         self._ck(self.lib.mpm_pins_inside_collider(self.h, C.byref(shape), int(body), _ptr(p), _ptr(R), C.byref(n)))
         return int(n.value)
+
+    # ---- anchors: springs and cords from cloth vertices to rigid bodies ----
+    def set_anchors(self, table):
+        """mpm_set_anchors: the anchors -- springs, zero-length springs and tension-only cords from cloth vertices (in
+        dump_cpu_state's numbering) to points of rigid bodies --, an array of ANCHOR_DTYPE or a list of Anchor; an empty
+        table clears them.  The bodies' motions are those of set_body_motions; the reactions arrive where the pins' do."""
+        if isinstance(table, np.ndarray):
+            t = np.ascontiguousarray(table, ANCHOR_DTYPE).reshape(-1)
+        else:
+            t = np.zeros(len(table), ANCHOR_DTYPE)
+            for i, a in enumerate(table):
+                t[i] = (a.vertex, a.body, tuple(a.p_BQ), a.stiffness, a.rest_length, a.damping, a.flags)
+        self._ck(self.lib.mpm_set_anchors(self.h, t.size, t.ctypes.data if t.size else None))
+
+    def get_anchors(self):
+        """mpm_get_anchors: the table in force, an array of ANCHOR_DTYPE."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_anchors(self.h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), ANCHOR_DTYPE)
+        self._ck(self.lib.mpm_get_anchors(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
+    def anchor_forces(self):
+        """mpm_anchor_forces: the anchors' force on the current state at the bodies' current clocks, (n_verts, 3) float32
+        in dump_cpu_state's numbering (zeros for vertices without an anchor); adds no impulse."""
+        out = np.zeros((self.n_verts, 3), np.float32)
+        self._ck(self.lib.mpm_anchor_forces(self.h, _ptr(out)))
+        return out
+
+    def anchor_state(self):
+        """mpm_anchor_state: dict(energy: sum of 1/2 k (l - L)^2 over the anchors that act, length (n,) float32,
+        point (n, 3) float32 the attachment points y, impulse_quantum: the quantum of the bodies' accumulators)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_anchors(self.h, None, 0, C.byref(n)))
+        k = int(n.value)
+        e, q = C.c_double(), C.c_double()
+        length, point = np.zeros(k, np.float32), np.zeros((k, 3), np.float32)
+        self._ck(self.lib.mpm_anchor_state(self.h, C.byref(e), length.ctypes.data if k else None, point.ctypes.data if k else None,
+                                           C.byref(q)))
+        return dict(energy=float(e.value), length=length, point=point, impulse_quantum=float(q.value))
+
+    def anchors_max_stable_dt(self) -> float:
+        """mpm_anchors_max_stable_dt: the dt above which the substep entry points refuse (inf while no anchor is set)."""
+        dt = C.c_float()
+        self._ck(self.lib.mpm_anchors_max_stable_dt(self.h, C.byref(dt)))
+        return float(dt.value)
+
+    anchor_point = staticmethod(anchor_point)
 
     def get_pins(self):
         """mpm_get_pins: -> (vertex (n,) uint32, body (n,) uint32, p_BQ (n, 3) float32)"""

@@ -10,11 +10,158 @@
 #include "mpm_host.h"
 #include "mpm_io.h"
 
+// ---- anchors: springs and cords from cloth vertices to rigid bodies (mpm_set_anchors, mpm_get_anchors, mpm_anchor_forces,
+// mpm_anchor_state, mpm_anchors_max_stable_dt, mpm_anchor_point; mpm_anchors.h) ----
+// The table `t` with its limit and the caller's anchors put in force: new device arrays, upload, swap.  The caller has
+// settled the owed substeps.  A failure changes nothing: the new buffers go, the table in force stays.
+static int anchors_swap(mpm_engine* e, AnchorTable& t, float max_dt, size_t n, const mpm_anchor_t* anchors) {
+    static_assert(sizeof(AnchorRecord) == sizeof(AnchorRec) && sizeof(AnchorOne) == sizeof(AnchorRec) && sizeof(AnchorRec) == 32,
+                  "anchor record layouts differ");
+    mpm_engine::Anchors next;
+    FreshArrays fresh(e);
+    if (int rc = rows_upload(e, fresh, t, &next.args)) return rc;
+    if (n) {   // (k_anchor_energy's records, behind the table's)
+        AnchorRec* d_one = nullptr;
+        if (int rc = fresh.alloc(&d_one, n, false)) return rc;
+        H2D(e, d_one, t.one.data(), n * sizeof(AnchorRec));
+        next.d_one = d_one;
+    }
+    rows_free(e, e->anchors.args);
+    AnchorRec* o_one = const_cast<AnchorRec*>(e->anchors.d_one);
+    e->dfree(o_one);
+    next.set.assign(anchors, anchors + n);
+    next.max_dt = max_dt;
+    next.unresolved = t.unresolved;
+    next.d_pose = e->anchors.d_pose;   // (the pose table outlives the anchor tables: anchors_ready sizes it)
+    next.cap_pose = e->anchors.cap_pose;
+    e->anchors = next;
+    fresh.commit();
+    return 0;
+}
+// mpm_set_anchors in three steps: the table on the host, its limit from the vertices' masses, the swap.  A body without
+// a motion yet leaves its records unresolved: anchors_ready lays the table out again once every body has its slot.
+static int set_anchors(mpm_engine* e, size_t n, const mpm_anchor_t* anchors) {
+    static_assert(sizeof(Anchor) == sizeof(mpm_anchor_t) && sizeof(Anchor) == 36, "anchor layouts differ");
+    const Anchor* A = reinterpret_cast<const Anchor*>(anchors);
+    const std::string refusal = anchor_table_refusal(A, n, e->nv);
+    if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    REQUIRE(e->np < (size_t)1 << 31, "anchors: too many particles");
+    const std::vector<uint32_t>& mb = e->pin.motion_body;
+    auto slot_of = [&](uint32_t body) {
+        const auto it = std::find(mb.begin(), mb.end(), body);
+        return it != mb.end() ? (uint32_t)(it - mb.begin()) : ANCHOR_NO_SLOT;
+    };
+    AnchorTable t;
+    std::string why;
+    if (!anchor_table(A, n, e->nf, e->nv, ANCHOR_SLICE, slot_of, t, why)) return fail(MPM_ERR_INVALID, why);
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    float max_dt = INFINITY;
+    if (n) {
+        std::vector<float> mass;
+        if (int rc = vertex_masses(e, mass)) return rc;
+        double W, G;
+        anchor_rates(t, mass.data(), e->nf, &W, &G);
+        max_dt = link_limit(W, G);
+    }
+    return anchors_swap(e, t, max_dt, n, anchors);
+}
+// What a launch of the anchor kernels needs: every anchor's body has a motion (MPM_ERR_INVALID otherwise, before
+// anything is enqueued), the table carries the motion slots, the pose table holds every slot and k_pin's ticket exists.
+static int anchors_ready(mpm_engine* e) {
+    mpm_engine::Anchors& an = e->anchors;
+    if (!an.on()) return 0;
+    mpm_engine::PinState& ps = e->pin;
+    if (an.unresolved) {
+        std::unordered_set<uint32_t> have(ps.motion_body.begin(), ps.motion_body.end());
+        for (const mpm_anchor_t& q : an.set)
+            if (!have.count(q.body))
+                return fail(MPM_ERR_INVALID, "anchor on body " + std::to_string(q.body) + ", which has no motion: call mpm_set_body_motions first");
+        const std::vector<mpm_anchor_t> again = an.set;   // (no substep has been enqueued with the unresolved table)
+        if (int rc = set_anchors(e, again.size(), again.data())) return rc;
+    }
+    if (an.cap_pose < ps.cap_mot) {
+        HIP_TRY(hipStreamSynchronize(e->stream));   // (earlier substeps may still read the old table)
+        e->dfree(an.d_pose);
+        an.cap_pose = 0;
+        if (int rc = e->dalloc(&an.d_pose, ps.cap_mot, true)) return rc;
+        an.cap_pose = ps.cap_mot;
+    }
+    if (!ps.d_ticket)
+        if (int rc = e->dalloc(&ps.d_ticket, 1, true)) return rc;
+    return 0;
+}
+// the table as a launch reads it, behind k_anchor_pose on the stream
+static AnchorArgs anchors_posed(mpm_engine* e) {
+    const mpm_engine::PinState& ps = e->pin;
+    AnchorArgs a = e->anchors.args;
+    a.pose = e->anchors.d_pose;
+    a.n_mot = (int)ps.motion_body.size();
+    hipLaunchKernelGGL(k_anchor_pose, dim3(((unsigned)a.n_mot + 63u) / 64u), dim3(64), 0, e->stream, (const BodyMotionDev*)ps.d_mot, a.n_mot,
+                       e->anchors.d_pose);
+    return a;
+}
+
+static int anchor_forces(mpm_engine* e, float* f_out) {
+    if (!e->anchors.on()) {
+        std::memset(f_out, 0, e->nv * 12);
+        return 0;
+    }
+    if (int rc = anchors_ready(e)) return rc;
+    return rows_eval(e, k_anchor_eval, anchors_posed(e), f_out);
+}
+
+// One double term, one float length and one float point per anchor from the device, the terms added here in anchor order:
+// a fixed order, no atomics (as link_energy)
+static int anchor_state(mpm_engine* e, double* energy_out, float* length_out, float* point_out, double* impulse_quantum_out) {
+    const size_t n = e->anchors.set.size();
+    double sum = 0.0;
+    if (n) {
+        if (int rc = anchors_ready(e)) return rc;
+        if (int rc = e->stage(n * 24)) return rc;
+        double* d_term = (double*)e->d_stage;
+        float* d_len = (float*)(d_term + n);
+        float* d_point = d_len + n;
+        const AnchorArgs a = anchors_posed(e);
+        hipLaunchKernelGGL(k_anchor_energy, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, e->stream, e->dp, e->anchors.d_one, (int)n,
+                           a.pose, a.n_mot, d_term, d_len, d_point);
+        std::vector<double> term(n);
+        D2H(e, term.data(), d_term, n * 8);
+        if (length_out) D2H(e, length_out, d_len, n * 4);
+        if (point_out) D2H(e, point_out, d_point, n * 12);
+        for (size_t i = 0; i < n; ++i) sum += term[i];
+    }
+    if (energy_out) *energy_out = sum;
+    // (what mpm_external_body_force_to_host multiplies the integer sums by)
+    if (impulse_quantum_out) *impulse_quantum_out = e->cb.imp_unfix > 0.0 ? e->cb.imp_unfix : e->dp.unfix_p;
+    return 0;
+}
+
+// host code only: pin_pose and anchor_point, compiled for the host
+static void anchor_point_host(const mpm_body_motion_t* m, double t, const float p_BQ[3], float y[3], float v_Q[3]) {
+    BodyMotionDev r{};
+    for (int i = 0; i < 3; ++i) {
+        r.p[i] = m->p_WB[i];
+        r.v[i] = m->v[i];
+        r.w[i] = m->w[i];
+    }
+    for (int i = 0; i < 9; ++i) r.R[i] = m->R_WB[i];
+    double pt[3], Rt[9];
+    pin_pose(r, t, pt, Rt);
+    float yy[3], vq[3];
+    anchor_point(pt, Rt, r.v, r.w, p_BQ, yy, vq);
+    for (int i = 0; i < 3; ++i) {
+        if (y) y[i] = yy[i];
+        if (v_Q) v_Q[i] = vq[i];
+    }
+}
+
 // ---- fixed constraints: checks of the substep entry points ------------------------------------------------------------
 // Every pin's body has a motion (MPM_ERR_INVALID otherwise, before anything is enqueued), and the device table is the
-// current pin set with each pin's motion slot resolved.
+// current pin set with each pin's motion slot resolved.  The same for the anchors (anchors_ready).
 static int pins_ready(mpm_engine* e) {
     mpm_engine::PinState& ps = e->pin;
+    if (int rc = anchors_ready(e)) return rc;
     if (ps.set.empty()) return 0;
     std::unordered_map<uint32_t, uint32_t> slot_of;
     for (size_t k = 0; k < ps.motion_body.size(); ++k) slot_of[ps.motion_body[k]] = (uint32_t)k;

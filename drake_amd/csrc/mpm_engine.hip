@@ -185,7 +185,7 @@ static void launch_fem_faces(mpm_engine* e, const DP& p, float dt) {
     // (an engine with membrane damping, mpm_set_damping: the same faces again, adding to the records just written)
     if (e->damp.membrane()) hipLaunchKernelGGL(k_damp, g, b, 0, e->stream, p, e->damp.args);
 }
-static void launch_fem_vertices(mpm_engine* e, const DP& p) {
+static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:CalcFemStateAndForce (vertex forces)");
     if (e->nv) hipLaunchKernelGGL(k_vforce, dim3((e->g_nv + 7u) & ~7u), dim3(256), 0, e->stream, p);
     // (an engine with bending stiffness, mpm_set_bending: f += -k Q x on the forces k_vforce has just written)
@@ -215,12 +215,19 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p) {
         hipLaunchKernelGGL(k_hinge, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, p, e->shell.hinge);
         hipLaunchKernelGGL(k_hinge_gather, rows_grid(e->shell.args.n_rows), dim3(256), 0, e->stream, p, e->shell.args);
     }
+    // (an engine with anchors, mpm_set_anchors: the bodies' poses at their clocks, one lane per motion; then f += the
+    // springs' and cords' forces, one lane per anchored vertex, and the reactions into the bodies' accumulators)
+    if (e->anchors.on()) {
+        const AnchorArgs a = anchors_posed(e);
+        const AnchorAcc acc{e->cb.body_acc, (int)e->cb.n_bodies, p.fix_p};
+        hipLaunchKernelGGL(k_anchor, rows_grid(a.n_rows), dim3(256), 0, e->stream, p, a, acc, dt);
+    }
 }
 // (mpm_calc_fem_state_and_force: the two FEM kernels, whose forces a caller may read)
 static void launch_fem(mpm_engine* e, const DP& p, float dt) {
     e->last_dt = dt;
     launch_fem_faces(e, p, dt);
-    launch_fem_vertices(e, p);
+    launch_fem_vertices(e, p, dt);
 }
 // `forces`: where k_p2g's vertex lanes find the force on their vertex (the kernel's template parameter: 0 = in p.f,
 // k_vforce ran; 1 = summed inside the kernel)
@@ -251,25 +258,28 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
 }
 // the vertex forces inside k_p2g, from the vertices' entries of DP::VF (single and partitioned domains alike since round
 // 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch, and so does an engine with bending
-// stiffness, links, pressure or shell bending, whose k_bend, k_link, k_pressure and k_hinge_gather add to the forces in DP::f
+// stiffness, links, pressure, shell bending or anchors, whose k_bend, k_link, k_pressure, k_hinge_gather and k_anchor add to
+// the forces in DP::f
 static int fused_forces(const mpm_engine* e) {
-    return e->max_valence <= 8 && !e->bend.on() && !e->links.on() && !e->pressure.on() && !e->shell.on() ? 1 : 0;
+    return e->max_valence <= 8 && !e->bend.on() && !e->links.on() && !e->pressure.on() && !e->shell.on() && !e->anchors.on() ? 1 : 0;
 }
-// the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins launches it (pins_ready has resolved the
-// table).  Everything after GridToParticle -- the coupled path's watch kernel included -- comes after it on the stream.
+// the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins or anchors launches it (pins_ready has
+// resolved the table).  An engine with anchors and no pins launches it with zero pins and one workgroup: its tail
+// advances the bodies' clocks.  Everything after GridToParticle -- the coupled path's watch kernel included -- comes
+// after it on the stream.
 static void launch_pins(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:Pins");
     const mpm_engine::PinState& ps = e->pin;
     PinArgs a{ps.d_pins, (int)ps.set.size(), ps.d_mot, (int)ps.motion_body.size(), e->cb.body_acc, (int)e->cb.n_bodies,
               p.fix_p, ps.d_ticket};
-    const unsigned groups = (unsigned)std::min<size_t>((ps.set.size() + 255) / 256, 1024);
+    const unsigned groups = (unsigned)std::max<size_t>(1, std::min<size_t>((ps.set.size() + 255) / 256, 1024));
     hipLaunchKernelGGL(k_pin, dim3(groups), dim3(256), 0, e->stream, p, a, dt);
 }
 // (`p` may carry a halo class restriction: only an engine without pins splits GridToParticle, see extensions_refused)
 static void launch_g2p(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:GridToParticle");
     hipLaunchKernelGGL(k_g2p, dim3(std::min(768u, p.capI)), dim3(G2P_THREADS), 0, e->stream, p, dt);
-    if (!e->pin.set.empty() && p.halo_cls < 0) launch_pins(e, p, dt);
+    if ((!e->pin.set.empty() || e->anchors.on()) && p.halo_cls < 0) launch_pins(e, p, dt);
 }
 static void launch_grid(mpm_engine* e, const DP& p, const GridColliders& gc) {
     TraceRange tr("mpm:UpdateGrid");
@@ -307,7 +317,7 @@ static void enqueue_substep_front(mpm_engine* e, const DP& p, float dt, Resort r
     launch_fem_faces(e, p, dt);
     if (mark) mark(MPM_PHASE_FEM);
     const int forces = fused_forces(e);
-    if (!forces) launch_fem_vertices(e, p);
+    if (!forces) launch_fem_vertices(e, p, dt);
     if (mark) mark(MPM_PHASE_VFORCE);
     launch_p2g(e, p, dt, forces);
     if (mark) mark(MPM_PHASE_P2G);
@@ -741,7 +751,7 @@ int mpm_sync(mpm_handle_t e) try {
 } MPM_CATCH_ALL
 
 // partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
-// stiffness, no damping, no links, no pressure and no shell bending (out of scope)
+// stiffness, no damping, no links, no pressure, no shell bending and no anchors (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
@@ -760,6 +770,8 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pressure (mpm_set_pressure)");
     if (e->shell.on())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with shell bending (mpm_set_shell_bending)");
+    if (e->anchors.on())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with anchors (mpm_set_anchors)");
     return 0;
 }
 // the refusal of a dt above a feature's mpm_<feature>_max_stable_dt (fields_stable)
@@ -775,8 +787,12 @@ static int dt_above_limit(float dt, float max_dt, const char* feature, const cha
 // on the lumped system needs dt * omega <= 2, with Gershgorin's bound on omega^2 (a guard, not a guarantee).  And a dt
 // above mpm_damping_max_stable_dt on an engine with damping: the explicit viscous force needs dt * rho(M^-1 D) <= 2.  And
 // a dt above mpm_links_max_stable_dt on an engine with links: W dt^2 + 2 G dt <= 4 (mpm_links.h; a guard, not a guarantee).
-// And a dt above mpm_shell_max_stable_dt on an engine with shell bending (mpm_shell.h; a guard at the rest shape).
+// And a dt above mpm_shell_max_stable_dt on an engine with shell bending (mpm_shell.h; a guard at the rest shape).  And a dt
+// above mpm_anchors_max_stable_dt on an engine with anchors (mpm_anchors.h; a guard of its own: a vertex with links and
+// anchors passes each on its own).
 static int fields_stable(const mpm_engine* e, float dt) {
+    if (e->anchors.on() && !(dt <= e->anchors.max_dt))
+        return dt_above_limit(dt, e->anchors.max_dt, "anchors", "anchor", "dt, the stiffness or the damping");
     if (e->shell.on() && !(dt <= e->shell.max_dt))
         return dt_above_limit(dt, e->shell.max_dt, "shell", "shell bending", "dt or the stiffness");
     if (e->links.on() && !(dt <= e->links.max_dt))
@@ -791,10 +807,12 @@ static int fields_stable(const mpm_engine* e, float dt) {
 }
 // The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
 // takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness, damping,
-// links, pressure or shell bending are set.
+// links, pressure, shell bending or anchors are set.
 static float quiet_hint(const mpm_engine* e, float seconds) {
-    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->links.on() && !e->pressure.on() && !e->shell.on() ? seconds
-                                                                                                                               : 0.f;
+    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->links.on() && !e->pressure.on() && !e->shell.on() &&
+                   !e->anchors.on()
+               ? seconds
+               : 0.f;
 }
 
 // ---- the solver calls -----------------------------------------------------
@@ -996,6 +1014,8 @@ int mpm_rebuild_mapping(mpm_handle_t e, int sort) try {
 } MPM_CATCH_ALL
 
 int mpm_calc_fem_state_and_force(mpm_handle_t e, float dt) try {
+    if (e && e->finalized)
+        if (int rc = anchors_ready(e)) return rc;   // (before the phase is held back or enqueued: k_anchor reads the motions)
     if (e && can_defer(e) && e->pend.n == 1) {
         READY_NO_SETTLE(e);
         e->pend.n = 2;
@@ -1085,6 +1105,7 @@ int mpm_update_grid_from_sums(mpm_handle_t e, int bc) try {
 int mpm_substep_begin(mpm_handle_t e, float dt) try {
     READY(e);
     if (int rc = fields_stable(e, dt)) return rc;
+    if (int rc = anchors_ready(e)) return rc;
     enqueue_substep_front(e, e->dp, dt, Resort::Full);
     enqueue_substep_rest(e, GridForm::Gather, e->dp, GridColliders{}, nullptr, 0.f);
     e->grid_state = 3;
@@ -2154,6 +2175,43 @@ int mpm_get_pins(mpm_handle_t e, mpm_pin_t* out, size_t capacity, size_t* n_out)
     READY(e);
     REQUIRE(out || capacity == 0, "null output");
     return copy_out(e->pin.set, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+// ---- anchors: springs and cords from cloth vertices to rigid bodies (mpm_bodies_host.h; mpm_anchors.h) ------------------------
+int mpm_set_anchors(mpm_handle_t e, size_t n, const mpm_anchor_t* anchors) try {
+    READY(e);
+    if (int rc = single_engine_only(e, "anchors are")) return rc;
+    REQUIRE(n == 0 || anchors, "null anchor array");
+    return set_anchors(e, n, anchors);
+} MPM_CATCH_ALL
+
+int mpm_get_anchors(mpm_handle_t e, mpm_anchor_t* out, size_t capacity, size_t* n_out) try {
+    READY(e);
+    REQUIRE(out || capacity == 0, "null output");
+    return copy_out(e->anchors.set, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_anchor_forces(mpm_handle_t e, float* f_out) try {
+    READY(e);
+    REQUIRE(f_out, "null output");
+    return anchor_forces(e, f_out);
+} MPM_CATCH_ALL
+
+int mpm_anchor_state(mpm_handle_t e, double* energy_out, float* length_out, float* point_out, double* impulse_quantum_out) try {
+    READY(e);
+    return anchor_state(e, energy_out, length_out, point_out, impulse_quantum_out);
+} MPM_CATCH_ALL
+
+int mpm_anchors_max_stable_dt(mpm_handle_t e, float* dt_out) try {
+    REQUIRE(e && dt_out, "null argument");
+    *dt_out = e->anchors.on() ? e->anchors.max_dt : INFINITY;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_anchor_point(const mpm_body_motion_t* motion, double t, const float* p_BQ, float* y, float* v_Q) try {
+    REQUIRE(motion && p_BQ, "null argument");
+    anchor_point_host(motion, t, p_BQ, y, v_Q);
+    return 0;
 } MPM_CATCH_ALL
 
 // ---- rigid bodies of the grid update (mpm_bodies_host.h; k_grid_bodies in mpm_grid_bodies.h) ------------------------------

@@ -25,6 +25,7 @@
 #include "mpm_links.h"
 #include "mpm_pressure.h"
 #include "mpm_shell.h"
+#include "mpm_anchors.h"
 #include "mpm_measure.h"
 #include "mpm_grid_bodies.h"
 #include "mpm_team.h"
@@ -279,6 +280,18 @@ struct mpm_engine {
         float max_dt = INFINITY;              // the guard at the rest shape (fields_stable)
         bool on() const { return hinge.n > 0; }
     } shell;
+    // anchors: springs and cords from cloth vertices to rigid bodies (mpm_set_anchors; mpm_anchors.h): a non-empty table
+    // switches k_anchor_pose and k_anchor on behind k_hinge_gather, and k_pin's clock tail behind GridToParticle
+    struct Anchors {
+        std::vector<mpm_anchor_t> set;       // the caller's table, as given
+        AnchorArgs args{};                   // ... as k_anchor reads it (device memory, in `allocs`)
+        const AnchorRec* d_one = nullptr;    // [anchor] k_anchor_energy's records
+        AnchorPose* d_pose = nullptr;        // [cap_pose] k_anchor_pose's table
+        size_t cap_pose = 0;
+        bool unresolved = false;             // some record's body had no motion slot when the table was laid out (anchors_ready)
+        float max_dt = INFINITY;             // link_limit of the guard's rates (fields_stable)
+        bool on() const { return args.n_rows > 0; }
+    } anchors;
     // the per-cloth report (mpm_measure, mpm_face_strain; mpm_measure.h): chunk table and scratch, made at first use
     struct Measure {
         bool built = false;

@@ -30,8 +30,9 @@ struct PinArgs {
     unsigned* ticket;      // arrival counter of the workgroups (the last one advances the clocks)
 };
 
-// R(t) = Rodrigues(t w) R_WB and p(t) = p_WB + t v, in double
-MPM_DEV void pin_pose(const BodyMotionDev& m, double t, double* pt, double* Rt) {
+// R(t) = Rodrigues(t w) R_WB and p(t) = p_WB + t v, in double.  Host and device (mpm_anchor_point runs it on the host):
+// sin and cos are each platform's own, so the two agree within a rounding of the result, not to the bit.
+__host__ __device__ __forceinline__ void pin_pose(const BodyMotionDev& m, double t, double* pt, double* Rt) {
     const double a[3] = {t * m.w[0], t * m.w[1], t * m.w[2]};
     const double th2 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
     double s, c;   // sin(th) / th, (1 - cos(th)) / th^2

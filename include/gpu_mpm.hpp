@@ -284,6 +284,46 @@ struct GpuMpmState {
                           float f_on_a[3]) {
         mpm_check(mpm_link_force(&link, xa, xb, va, vb, f_on_a));
     }
+    // Extension: anchors (mpm_set_anchors) -- springs and tension-only cords from cloth vertices to points of rigid bodies,
+    // whose motions are those of SetBodyMotions and whose reactions arrive where the pins' do; an empty vector clears them.
+    // A synchronisation point, like SetLinks.
+    void SetAnchors(const std::vector<mpm_anchor_t>& anchors) { mpm_check(mpm_set_anchors(h_, anchors.size(), anchors.data())); }
+    std::vector<mpm_anchor_t> GetAnchors() const {
+        size_t n = 0;
+        mpm_check(mpm_get_anchors(h_, nullptr, 0, &n));
+        std::vector<mpm_anchor_t> out(n);
+        mpm_check(mpm_get_anchors(h_, out.data(), n, &n));
+        return out;
+    }
+    // the anchors' force on the current state at the bodies' current clocks, 3 floats per vertex; adds no impulse
+    std::vector<float> AnchorForces(size_t n_verts) const {
+        std::vector<float> f(3 * n_verts);
+        mpm_check(mpm_anchor_forces(h_, f.data()));
+        return f;
+    }
+    // sum of 1/2 k (l - L)^2 over the anchors that act; `lengths` and `points` (3 per anchor), if given, receive every
+    // anchor's float length and attachment point; `impulse_quantum`, if given, the quantum of the bodies' accumulators
+    double AnchorState(std::vector<float>* lengths = nullptr, std::vector<float>* points = nullptr,
+                       double* impulse_quantum = nullptr) const {
+        double e = 0.0;
+        size_t n = 0;
+        mpm_check(mpm_get_anchors(h_, nullptr, 0, &n));
+        if (lengths) lengths->resize(n);
+        if (points) points->resize(3 * n);
+        mpm_check(mpm_anchor_state(h_, &e, lengths && n ? lengths->data() : nullptr, points && n ? points->data() : nullptr,
+                                   impulse_quantum));
+        return e;
+    }
+    // the dt above which the substep entry points refuse an engine with anchors (+inf while the table is empty)
+    float AnchorsMaxStableDt() const {
+        float dt = 0.f;
+        mpm_check(mpm_anchors_max_stable_dt(h_, &dt));
+        return dt;
+    }
+    // the attachment point of p_BQ and its velocity at the body's clock t, on the host: see mpm_anchor_point
+    static void AnchorPoint(const mpm_body_motion_t& motion, double t, const float p_BQ[3], float y[3], float v_Q[3]) {
+        mpm_check(mpm_anchor_point(&motion, t, p_BQ, y, v_Q));
+    }
     // Extension: enclosed-volume pressure per cloth (mpm_set_pressure) -- one entry per cloth in AddQRCloth order; an
     // empty vector turns it off.  A synchronisation point, like SetBending.  There is no dt guard: watch PressureState.
     void SetPressure(const std::vector<mpm_cloth_pressure_t>& per_cloth) {

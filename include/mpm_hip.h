@@ -914,6 +914,84 @@ MPM_API int mpm_links_max_stable_dt(mpm_handle_t h, float *dt_out);
 MPM_API int mpm_link_force(const mpm_link_t *link, const float xa[3], const float xb[3], const float va[3], const float vb[3],
                            float f_on_a[3]);
 
+/* ---- Anchors: springs and cords from cloth vertices to rigid bodies (an extension) ----
+ * A pin holds a vertex to a body rigidly; a link joins two cloth vertices compliantly.  An anchor is the compliant
+ * attachment to a body: a banner hung from a moving pole by cords, a parachute's lines to its payload, a tarp lashed to a
+ * truck bed, a sheet in a compliant clip, a tether that stops a flap at a length.  The body feels the tension.
+ * The attachment point.  Let t be the body's clock as it stands when CalcFemStateAndForce runs, that is at the start of
+ * the substep -- the clock of the pins, which mpm_set_body_motions restarts and which advances at the end of every
+ * GridToParticle that runs.  With p(t) = p_WB + t v and R(t) = Rodrigues(t w) R_WB,
+ *   y = p(t) + R(t) p_BQ;   v_Q = v + w x (y - p(t)),
+ * formed in double as the pins' kernel forms them and rounded to float once each (y32, v_Q32).
+ * The force on the vertex is the law of a link (above), evaluated by the same inline function with d = y32 - x and
+ * w = v_Q32 - v_vertex: L == 0 is a zero-length spring (the seam law), L > 0 a spring, MPM_ANCHOR_TENSION_ONLY a cord;
+ * the 1e-30 gate, the correctly rounded square root and divisions and the disabled contraction are those of a link.  A
+ * vertex's anchors are added in anchor order by one lane, without atomics: vertex forces are the same bits whatever the
+ * particle order.  The force joins the vertex forces of CalcFemStateAndForce behind the shell-bending kernels
+ * (MPM_ARR_FORCES includes it; its time counts under MPM_PHASE_VFORCE).
+ * The reaction.  With dt the substep's length, body `body` receives the force impulse l = -(double)f (double)dt and the
+ * torque impulse (y32 - p_WB) x l about the p_WB of its motion as set -- the convention of pins, so that one body's
+ * accumulator means one thing --, in the accumulators of the contact impulses (64-bit fixed point: the sums do not depend
+ * on the order; an overflow raises the range error as it does for pins) read by mpm_external_body_force_to_host and
+ * mpm_finalize_external_contact_forces.  An anchor whose body is >= the mpm_reallocate_external_bodies count acts on the
+ * vertex and adds no impulse.
+ * Exactly once.  A substep that skips itself and is run again adds neither force nor impulse.  Every
+ * CalcFemStateAndForce that does run adds the impulse: a caller of the phase-by-phase mpm_calc_fem_state_and_force who
+ * calls it twice for one substep has added it twice.
+ * Clocks.  An engine with anchors and no pins advances the clocks at the end of every GridToParticle that runs, exactly
+ * as one with pins does; an engine with both advances them once.
+ * While anchors are set the engine does not use the re-sort's quiet-time estimate to omit re-sort check launches, and
+ * every batched substep launches the vertex-force kernel.  With an empty table the engine launches exactly what it
+ * launches without this call.
+ * mpm_set_anchors replaces the table (n = 0 clears it, anchors may then be NULL); it needs mpm_finalize, is ordered on
+ * the engine's stream and is a synchronisation point; substeps that mpm_run_substeps still owes are run first, with the
+ * table they were enqueued with.  Duplicate (vertex, body) pairs are allowed; each is an anchor of its own: n anchors
+ * meant to act as one spring of stiffness K take K / n each.  A pinned vertex may also carry anchors.
+ * Motions may be set after anchors; a substep entry point (mpm_calc_fem_state_and_force included) called while some
+ * anchor's body has no motion is refused as it is for pins, and so are mpm_anchor_forces and mpm_anchor_state.
+ * Stability: the body's end is prescribed, so the factor is 1 where a link has 2: W = max_i (1 / m_i) sum k and
+ * G = max_i (1 / m_i) sum c over vertex i's anchors, m_i the vertex particle's mass as of mpm_set_anchors;
+ * mpm_anchors_max_stable_dt is the positive root of W dt^2 + 2 G dt = 4 (+inf while the table is empty), and the entry
+ * points that check mpm_links_max_stable_dt also return MPM_ERR_INVALID, before anything is enqueued, for a dt above it.
+ * This is a separate guard, not a guarantee: a vertex with links and anchors passes each guard on its own, and the bound
+ * does not cover the geometric stiffness of a compressed spring.
+ * It works with pins, per-cloth materials, grid bodies, force fields, bending, damping, links, pressure, shell bending,
+ * deterministic mode, fast math and the coupled path.
+ * Refused with MPM_ERR_INVALID, the previous table staying in force and nothing enqueued: a call before mpm_finalize; a
+ * vertex >= the vertex count; a non-finite p_BQ; a stiffness, rest_length or damping that is negative or not finite;
+ * unknown flags; a table that does not fit 2^31 records; any partitioned or multi-rank engine -- this call on such an
+ * engine, and mpm_dist_init, the halo, chain, team and world substeps on an engine with anchors. */
+#define MPM_ANCHOR_TENSION_ONLY 1u        /* acts only while length > rest_length (a cord) */
+typedef struct mpm_anchor {
+    uint32_t vertex;      /* vertex numbering of mpm_dump_cpu_state, over all cloths */
+    uint32_t body;        /* as mpm_pin_t::body: motion of that body, accumulator of that body */
+    float p_BQ[3];        /* attachment point in the body frame */
+    float stiffness;      /* k, N/m,   >= 0 */
+    float rest_length;    /* L, m,     >= 0; 0: a zero-length spring (the seam law) */
+    float damping;        /* c, N s/m, >= 0 */
+    uint32_t flags;       /* MPM_ANCHOR_TENSION_ONLY */
+} mpm_anchor_t;           /* 36 bytes */
+MPM_API int mpm_set_anchors(mpm_handle_t h, size_t n, const mpm_anchor_t *anchors);
+/* The table as given: min(n, capacity) entries into out (may be NULL when capacity is 0), n into *n_out. */
+MPM_API int mpm_get_anchors(mpm_handle_t h, mpm_anchor_t *out, size_t capacity, size_t *n_out);
+/* The anchors' force on the current state at the bodies' current clocks: f_out[3 * n_verts], in the vertex numbering of
+ * mpm_dump_cpu_state (zeros for vertices without an anchor).  The device function of the substep's kernel; changes no
+ * state and adds no impulse. */
+MPM_API int mpm_anchor_forces(mpm_handle_t h, float *f_out);
+/* On the current state at the bodies' current clocks; any output may be NULL; changes no state.
+ * energy_out: the sum of 1/2 k (l - L)^2 over the anchors that act (the link's gates, decided on the float differences),
+ * every term formed in double from the floats y32 and x, added in anchor order without atomics.  length_out (n): every
+ * anchor's length, acting or not, formed in double and rounded to float once.  point_out (3 n): every anchor's y32.
+ * impulse_quantum_out: one double, the quantum of the bodies' accumulators -- every impulse is rounded to a multiple of
+ * it before it is added, which states the rounding of a reaction sum.  This energy is not part of mpm_measure's record. */
+MPM_API int mpm_anchor_state(mpm_handle_t h, double *energy_out, float *length_out, float *point_out, double *impulse_quantum_out);
+MPM_API int mpm_anchors_max_stable_dt(mpm_handle_t h, float *dt_out);
+/* The attachment point on the host (no handle, no device): the pose function of the pins' and anchors' kernels and the
+ * two formulas above, compiled for the host, at clock t.  y, v_Q: 3 floats each, either may be NULL.  The motion is not
+ * validated.  sin and cos are each platform's own, so host and device agree within one float ulp of the components'
+ * scale, not to the bit.  The force of an anchor on its vertex is mpm_link_force with xb = y, vb = v_Q. */
+MPM_API int mpm_anchor_point(const mpm_body_motion_t *motion, double t, const float p_BQ[3], float y[3], float v_Q[3]);
+
 /* ---- Enclosed-volume pressure per cloth: inflatable cloths (an extension) ----
  * Every other force on the cloth is local: none knows that a cloth can enclose something, so a ball, a cushion, an
  * airbag or a balloon in a gripper has no load that keeps it from collapsing.  mpm_set_pressure gives every cloth a
@@ -1147,8 +1225,8 @@ MPM_API int mpm_cloth_energy_density(const mpm_cloth_material_t *m, size_t n, co
  * stream and returns the mean milliseconds per substep of each phase
  * (phase_ms[MPM_PHASE_COUNT]) and of the whole substep.  The launches are those of mpm_run_substeps, but every substep
  * carries its re-sort launches and none skips itself.  MPM_PHASE_VFORCE is the vertex-force kernel (and the bending,
- * link and pressure kernels behind it) wherever the engine launches it -- a mesh with a vertex of more than eight faces,
- * an engine with bending stiffness, links or pressure --; on every other engine ParticleToGrid sums the vertex forces itself and the phase is empty. */
+ * link, pressure, shell-bending and anchor kernels behind it) wherever the engine launches it -- a mesh with a vertex of
+ * more than eight faces, an engine with bending stiffness, links, pressure, shell bending or anchors --; on every other engine ParticleToGrid sums the vertex forces itself and the phase is empty. */
 MPM_API int mpm_profile_substeps(mpm_handle_t h, int n, float dt, int mpm_bc, float *phase_ms, float *total_ms);
 
 /* ---- multi-GPU: one engine per GPU, domains tiled along x ------------------
