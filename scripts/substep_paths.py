@@ -7,7 +7,11 @@ selects a variant built by scripts/build_history.sh) and compare the lines; unde
 scripts/substep_paths.py --skip coupled` the ordered list of (kernel, grid, workgroup) must be the same too
 (scripts/substep_paths.py --trace-list <kernel_trace.csv> prints it; the coupled path is left out there: its contact solve
 enqueues Newton iterations in speculative batches until the host sees the mailbox say "done", so the number of idle
-launches at the end of a solve depends on the host's timing).  Results: profiles/substep_paths_ab.txt."""
+launches at the end of a solve depends on the host's timing).  Results: profiles/substep_paths_ab.txt.
+
+--features: the scene of tests/feature_paths.py instead -- every cloth feature on -- through the fused entry points, the
+sums family, the seven calls and run_coupled_substeps; the hash covers the accumulators, the feature states and every
+force accessor as well (feature_paths.state)."""
 import csv
 import hashlib
 import os
@@ -39,8 +43,36 @@ def main(skip=()):
               st["resort_checks"], "err", st["error_flags"], flush=True)
 
 
+def features():
+    from tests import feature_paths as fp
+    from tests import substep_paths as sp
+    lib = os.path.basename(os.environ.get("MPM_HIP_LIBRARY", "default"))
+
+    def line(name, g):
+        st, stats = fp.state(g), g.stats()
+        print(lib, f"{name:28s}", fp.state_hash(st), "substeps", stats["substeps"], "rebuilds", stats["rebuilds"], "resort_checks",
+              stats["resort_checks"], "err", stats["error_flags"], flush=True)
+        g.destroy()
+
+    for name, (runner, env) in fp.FUSED.items():
+        g = fp.engine(env=env)
+        runner(g, -1)
+        line(name, g)
+    g = fp.engine()
+    sp._begin_end(g)
+    line("substep_begin_end", g)
+    g = fp.engine()
+    fp.seven_calls(g, fp.floor(), fp.N)
+    line("seven_calls", g)
+    g = fp.engine()
+    fp.coupled(g, fp.floor())
+    line("coupled", g)
+
+
 if __name__ == "__main__":
-    if len(sys.argv) == 3 and sys.argv[1] == "--trace-list":
+    if len(sys.argv) == 2 and sys.argv[1] == "--features":
+        features()
+    elif len(sys.argv) == 3 and sys.argv[1] == "--trace-list":
         trace_list(sys.argv[2])
     elif len(sys.argv) >= 2 and sys.argv[1] == "--skip":
         main(sys.argv[2:])

@@ -70,29 +70,29 @@ def engine(fan=True, pins=False, bending=False, defer_phases=True):
     return g
 
 
-def _phase_calls(g):
+def _phase_calls(g, bc=-1):
     for _ in range(N):
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(DT)
         g.particle_to_grid(DT)
-        g.update_grid(-1)
+        g.update_grid(bc)
         g.grid_to_particle(DT)
 
 
-def _run_substeps(g):
+def _run_substeps(g, bc=-1):
     for k in BATCHES:
-        g.run_substeps(k, DT, -1)
+        g.run_substeps(k, DT, bc)
 
 
-def _profile_substeps(g):
+def _profile_substeps(g, bc=-1):
     for k in BATCHES:
-        g.profile_substeps(k, DT, -1)
+        g.profile_substeps(k, DT, bc)
 
 
-def _begin_end(g):
+def _begin_end(g, bc=-1):
     for _ in range(N):
         g.substep_begin(DT)
-        g.substep_end(DT, -1)
+        g.substep_end(DT, bc)
 
 
 def _begin_end_halo(g):
