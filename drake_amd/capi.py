@@ -489,7 +489,7 @@ SYMBOLS = [
     "mpm_dist_plan_migration", "mpm_debug_throw", "mpm_debug_fail_alloc", "mpm_set_fast_math", "mpm_get_fast_math",
     "mpm_get_contact_pair_count", "mpm_download_contact_log", "mpm_last_contact_counts",
     "mpm_debug_contact_counters", "mpm_run_coupled_substeps", "mpm_chain_direct_prepare", "mpm_chain_direct_connect",
-    "mpm_debug_contact_count", "mpm_chain_direct_base", "mpm_chain_direct_connect_local", "mpm_team_prepare", "mpm_team_connect",
+    "mpm_debug_contact_count", "mpm_debug_contact_watch", "mpm_chain_direct_base", "mpm_chain_direct_connect_local", "mpm_team_prepare", "mpm_team_connect",
     "mpm_world_coupled_substeps", "mpm_set_pins", "mpm_set_body_motions", "mpm_pins_inside_collider", "mpm_get_pins",
     "mpm_add_qr_cloth_with_material", "mpm_get_cloth_info", "mpm_cloth_count", "mpm_set_grid_bodies",
     "mpm_get_grid_bodies", "mpm_set_force_fields", "mpm_get_force_fields", "mpm_force_field_acceleration",
@@ -610,6 +610,7 @@ def load_library(build: bool = True):
         "mpm_download_contact_log": [vp, vp, sz, P(sz)],
         "mpm_debug_contact_counters": [vp, P(C.c_uint64)],
         "mpm_debug_contact_count": [vp, i, i],
+        "mpm_debug_contact_watch": [vp, sz, vp, P(i)],
         "mpm_chain_direct_base": [vp, P(vp)],
         "mpm_chain_direct_connect_local": [vp, vp, vp],
         "mpm_team_prepare": [vp, sz, vp, P(vp)],
@@ -1453,6 +1454,17 @@ class GpuMpm:
     def debug_contact_count(self, count: int = -1, stamp_delta: int = 0):
         """tests: tamper with the pair count that generate_contact_pairs(want_count=False) left on the device"""
         self._ck(self.lib.mpm_debug_contact_count(self.h, count, stamp_delta))
+
+    def debug_contact_watch(self, colliders) -> bool:
+        """tests: one launch of the contact watch of run_coupled_substeps over the current state (mpm_debug_contact_watch);
+        True when some particle may be within the watch's margin of the inside of a collider"""
+        if isinstance(colliders, C.Array):
+            arr, nc = colliders, len(colliders)
+        else:
+            arr, nc = (Collider * max(len(colliders), 1))(*colliders), len(colliders)
+        hit = C.c_int()
+        self._ck(self.lib.mpm_debug_contact_watch(self.h, nc, arr, C.byref(hit)))
+        return bool(hit.value)
 
     def contact_log(self):
         """rows (residual, line-search evaluations, E(alpha), alpha, E(0), sum |Dir|^2, DoFs, 0) of the last solve's Newton

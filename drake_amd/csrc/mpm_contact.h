@@ -377,6 +377,46 @@ static int generate_contacts(mpm_engine* e, size_t n_col, const mpm_collider_t* 
     return 0;
 }
 
+// mpm_debug_contact_watch: one ungated k_ct_watch over the current state with a table of this call's own (more than
+// CT_COLLIDER_ARGS colliders: through a scratch allocation, as generate_contacts sends them through ContactBuffers::colliders)
+static int debug_contact_watch(mpm_engine* e, size_t n_col, const mpm_collider_t* cols, int* hit_out) {
+    static_assert(sizeof(Collider) == sizeof(mpm_collider_t), "collider layouts differ");
+    ContactBuffers& b = e->cb;
+    *hit_out = 0;
+    if (int rc = validate_colliders(n_col, cols)) return rc;
+    for (size_t j = 0; j < n_col; ++j)
+        REQUIRE(cols[j].body < std::max<size_t>(b.n_bodies, 1), "collider body index out of range");
+    if (int rc = validate_mesh_bodies(e)) return rc;
+    // (the mesh table as the next generation would upload it: last_mesh and its device copy change together, and a
+    // generation that finds them current uploads nothing; last_colliders and the pair buffers are not touched)
+    if (int rc = upload_mesh_table(e)) return rc;
+    struct Scratch {
+        Collider* p = nullptr;
+        ~Scratch() { if (p) (void)hipFree(p); }
+    } buf;
+    ColliderTable tab{};
+    tab.n = (int)n_col;
+    if (n_col <= (size_t)CT_COLLIDER_ARGS) {
+        std::memcpy(tab.c, cols, n_col * sizeof(Collider));
+    } else {
+        HIP_TRY(hipMalloc((void**)&buf.p, n_col * sizeof(Collider)));
+        H2D(e, buf.p, cols, n_col * sizeof(Collider));
+        tab.dev = buf.p;
+    }
+    tab.n_mesh = (int)b.last_mesh.size();
+    tab.mesh = b.mesh;
+    DP p = e->dp;
+    p.gated = 0;
+    const unsigned seq = ++e->watch_seq;
+    hipLaunchKernelGGL(tab.n_mesh ? k_ct_watch<true> : k_ct_watch<false>, dim3(1024), dim3(256), 0, e->stream, p, tab, seq);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    unsigned hit = 0;
+    D2H(e, &hit, &e->dp.ctl->watch_hit, sizeof(unsigned));
+    *hit_out = hit == seq ? 1 : 0;
+    return 0;
+}
+
 // mpm_collider_signed_distance: k_ct_sdf_query on the engine's stream, through a scratch allocation of this call
 static int collider_signed_distance(mpm_engine* e, const mpm_collider_t* col, size_t n, const float* x, float* phi, float* grad) {
     if (int rc = validate_colliders(1, col)) return rc;

@@ -1808,6 +1808,15 @@ int mpm_debug_contact_count(mpm_handle_t e, int count, int stamp_delta) try {
     return 0;
 } MPM_CATCH_ALL
 
+// Tests of k_ct_watch alone: see include/mpm_hip.h.  (READY: Finalize's first re-sort has set Ctl::nfa / nva.)
+int mpm_debug_contact_watch(mpm_handle_t e, size_t n_colliders, const mpm_collider_t* colliders, int* hit_out) try {
+    READY(e);
+    REQUIRE(hit_out, "null output");
+    REQUIRE(n_colliders == 0 || colliders, "null collider array");
+    REQUIRE(n_colliders <= 1024, "too many colliders");
+    return debug_contact_watch(e, n_colliders, colliders, hit_out);
+} MPM_CATCH_ALL
+
 int mpm_get_contact_pair_count(mpm_handle_t e, size_t* n_out) try {
     READY(e);
     REQUIRE(n_out, "null output");

@@ -489,6 +489,15 @@ MPM_API int mpm_debug_contact_counters(mpm_handle_t h, uint64_t out6[6]);
  * [0, capacity], MPM_ERR_INTERNAL for a stale one -- nothing indexed, nothing solved; pairs made again afterwards solve as
  * if nothing had happened.  Needs pairs counted on the device (n_contacts_out == NULL). */
 MPM_API int mpm_debug_contact_count(mpm_handle_t h, int count, int stamp_delta);
+/* Tests of the contact watch alone (the kernel behind a contact-free substep of mpm_run_coupled_substeps, which decides
+ * whether the next substep may go without pair generation and solve): one launch of it over the current particle state
+ * -- vertices where they are, faces at the centroid of their corners, formed by the kernel -- against the given
+ * colliders and the engine's mesh colliders, ungated.  *hit_out: 1 when some active particle may be within the watch's
+ * margin (a thousandth of a cell) of the inside of a collider, else 0.  Validates like mpm_generate_contact_pairs; leaves
+ * the pairs in the engine and the analytic colliders of the last generation as they are (the device table of the mesh
+ * colliders is brought up to date with the engine's set, as a generation would do).  Needs a finalized engine (the first
+ * re-sort has numbered the active particles).  A synchronisation point. */
+MPM_API int mpm_debug_contact_watch(mpm_handle_t h, size_t n_colliders, const mpm_collider_t *colliders, int *hit_out);
 MPM_API int mpm_download_contact_pairs(mpm_handle_t h, uint32_t *particle_in_contact_index, uint32_t *non_mpm_id,
                                        float *penetration_distance, float *normal, float *position, float *rigid_v,
                                        float *rigid_p_WB);

@@ -6,74 +6,12 @@ import numpy as np
 import pytest
 
 from tests.helpers import IMPULSE_RTOL
+from tests.pair_layouts import CYL_TOL, sdf_cylinder, sdf_ellipsoid
 from tests.test_contact_pairs_gpu import _rot, sdf as sdf_0123
 
 pytestmark = pytest.mark.gpu
 DT = 1e-3
 F = np.float32
-CYL_TOL = 4 * np.finfo(np.float32).eps     # the device's float-sized stand-in for Drake's 1e-14 (mpm_contact_dev.h)
-
-
-# ---- float64 restatements ----------------------------------------------------------------------------------------
-
-def sdf_cylinder(xb, R, h):
-    """Drake's cylinder: the (r, z) box [-R, R] x [-h, h], coordinates classified inside / boundary / outside."""
-    xb = np.asarray(xb, np.float64)
-    r = np.hypot(xb[:, 0], xb[:, 1])
-    z = xb[:, 2]
-    az = np.abs(z)
-    sz = np.where(z < 0, -1.0, 1.0)
-    tr, tz = CYL_TOL * max(1.0, R), CYL_TOL * max(1.0, h)
-    axis = r < tr
-    with np.errstate(invalid="ignore", divide="ignore"):
-        ux = np.where(axis, 1.0, xb[:, 0] / r)
-        uy = np.where(axis, 0.0, xb[:, 1] / r)
-    out_r, out_z = r > R + tr, az > h + tz
-    bnd_r, bnd_z = ~out_r & (r >= R - tr), ~out_z & (az >= h - tz)
-    outside = out_r | out_z
-    boundary = ~outside & (bnd_r | bnd_z)
-    cap = ~outside & ~boundary & (h - az < R - r)
-    dr = np.where(out_r | bnd_r, r - R, 0.0)
-    dz = np.where(out_z | bnd_z, sz * (az - h), 0.0)
-    lo = np.hypot(dr, dz)
-    w = np.where(bnd_r & bnd_z, np.sqrt(0.5), 1.0)
-    phi = np.where(outside, lo, np.where(boundary, np.where(bnd_r, w * (r - R), 0) + np.where(bnd_z, w * (az - h), 0),
-                                         np.where(cap, az - h, r - R)))
-    with np.errstate(invalid="ignore", divide="ignore"):
-        gr = np.where(outside, dr / lo, np.where(boundary, np.where(bnd_r, w, 0.0), np.where(cap, 0.0, 1.0)))
-        gz = np.where(outside, dz / lo, np.where(boundary, np.where(bnd_z, w * sz, 0.0), np.where(cap, sz, 0.0)))
-    return phi, np.stack([gr * ux, gr * uy, gz], 1)
-
-
-def sdf_ellipsoid(xb, radii, iters=200):
-    """Eberly: axes sorted descending, the query in the first octant, the secular equation's root by bisection
-    (vectorised; no coordinate may be exactly zero)."""
-    xb = np.asarray(xb, np.float64)
-    a = np.asarray(radii, np.float64)
-    order = np.argsort(-a, kind="stable")
-    e = a[order]
-    y = np.abs(xb[:, order])
-    z = y / e
-    g = (z * z).sum(1) - 1
-    r = (e / e[2]) ** 2
-    n = r * z
-    s0 = z[:, 2] - 1
-    s1 = np.where(g < 0, 0.0, np.sqrt(n[:, 0] ** 2 + n[:, 1] ** 2 + z[:, 2] ** 2) - 1)
-    for _ in range(iters):
-        s = 0.5 * (s0 + s1)
-        gs = (n[:, 0] / (s + r[0])) ** 2 + (n[:, 1] / (s + r[1])) ** 2 + (z[:, 2] / (s + 1)) ** 2 - 1
-        s0 = np.where(gs > 0, s, s0)
-        s1 = np.where(gs < 0, s, s1)
-    s = 0.5 * (s0 + s1)
-    x = r * y / (s[:, None] + r)
-    x = np.where((g == 0)[:, None], y, x)
-    dist = np.linalg.norm(x - y, axis=1)
-    N = np.empty_like(x)
-    N[:, order] = x
-    N = np.sign(xb) * N
-    grad = N / (a * a)
-    grad /= np.linalg.norm(grad, axis=1)[:, None]
-    return np.where(g < 0, -dist, dist), grad
 
 
 def world_sdf(c, pos):
