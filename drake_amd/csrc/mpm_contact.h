@@ -987,7 +987,8 @@ static int solve_once(mpm_engine* e, const SolveParams& prm, bool full_setup, So
     // block tables).  A wrong guess refuses the solve (CT_DONE_STALE), the caller repeats it with the full set-up.
     const bool reuse = !full_setup && b.last_unchanged && !dist && !e->ct_no_reuse;
     SolveCtx x{e, solve_geometry(b, p, full_setup), ContactDev{}, TeamDev{}};
-    enqueue_keys(x, prm, reuse, full_setup, false);
+    // (ranks of a partitioned domain solve together whatever their own counts: update_contact)
+    enqueue_keys(x, prm, reuse, full_setup, dist && p.dist.world > 1);
     if (int rc = enqueue_sort(&x, prm, reuse)) return rc;
     const ContactDev& c = x.c;
     if (reuse) {
@@ -1203,6 +1204,13 @@ static int newton_exact_host(const SolveCtx& x, const SolveParams& prm, SolveOut
         HIP_TRY(hipMemcpyAsync(&b.st->alpha, &alpha, 4, hipMemcpyHostToDevice, e->stream));
         launch_apply(x, 0);
         residual = std::sqrt(st.norm_dir_sq) / st.dofs;
+        if (iters < CT_LOG) {
+            // the iteration's row of mpm_download_contact_log, as k_ct_exact_finish writes it for the device-resident search
+            // (this loop used to leave the rows on the host only: the download returned `iters` rows of another solve)
+            const float row[CT_LOG_F] = {residual, (float)rf.evals, energy, alpha, oc->log.E0_last, (float)st.norm_dir_sq, (float)st.dofs, 0.f};
+            HIP_TRY(hipMemcpyAsync(b.it_log + (size_t)iters * CT_LOG_F, row, sizeof(row), hipMemcpyHostToDevice, e->stream));
+            HIP_TRY(hipStreamSynchronize(e->stream));   // (`row` is on this frame)
+        }
         iters += 1;
         oc->log.res.push_back(residual);
         oc->log.energy.push_back(energy);
@@ -1486,9 +1494,29 @@ static int update_contact(mpm_engine* e, int frame, int substep, const SolvePara
     } else {
         e->last_contact_prm = prm;
         // (the distributed paths are host-driven per iteration anyway: they work with a count the host knows)
-        if (partitioned_solve(e))
+        bool takes_part = false;
+        if (partitioned_solve(e)) {
             if (int rc = resolve_contact_count(e)) return rc;
-        if (!b.dev_counted && b.n == 0) return 0;   // cuda_mpm_solver.cu:216-217
+            // (without a transport there is nobody to wait for this rank: a rank without a pair returns as before)
+            if (e->dp.dist.world > 1 && (b.n > 0 || b.dev_counted || e->dist_allreduce || e->chain.comm)) {
+                // A rank without a pair takes part all the same: its neighbours wait for it in every exchange and in every
+                // all-reduce, its zone nodes see their contacts and it owns DoFs among them.  (Returning here left the
+                // other ranks waiting for ever.)  "Nobody has a contact" is decided by all ranks together, from the sum
+                // of the counts: then every rank returns, as a single engine does.
+                // (its buffers must exist; the per-pair arrays of a rank that has pairs hold them already and are left alone:
+                // growing them would discard the pairs)
+                if (int rc = ensure_contact_capacity(e, b.cap ? b.cap : (e->ct_initial_capacity ? e->ct_initial_capacity
+                                                                                                : std::max<size_t>(4096, e->np / 16))))
+                    return rc;
+                double total = (double)b.n;
+                H2D(e, b.st->red, &total, 8);
+                if (int rc = dist_allreduce(e, b.st->red, 1)) return rc;
+                D2H(e, &total, b.st->red, 8);
+                if (!(total > 0.0)) return 0;
+                takes_part = true;
+            }
+        }
+        if (!takes_part && !b.dev_counted && b.n == 0) return 0;   // cuda_mpm_solver.cu:216-217
         TraceRange tr_all("mpm:UpdateContact");
         if (int rc = solve_until_accepted(L, false, prm, before_impulse, &ocs)) return rc;
     }

@@ -1852,8 +1852,9 @@ int mpm_update_contact(mpm_handle_t e, int frame, int substep, float dt, float m
     if (iters_out) *iters_out = 0;
     if (residual_out) *residual_out = 0.f;
     e->last_contact = mpm_contact_stats_t{};
-    // (a rank of a TEAM takes part in the solve whatever its own pair count: "no contacts" is decided by all ranks together)
-    if (!e->cb.dev_counted && e->cb.n == 0 && !(e->dp.dist.on && e->team.on)) return 0;  // cuda_mpm_solver.cu:216-217
+    // (a rank of a partitioned domain takes part in the solve whatever its own pair count, on the team transport and on
+    // the host-driven ones, once it has a transport: "no contacts" is decided by all ranks together)
+    if (!e->cb.dev_counted && e->cb.n == 0 && !(e->dp.dist.on && (e->team.on || (e->dp.dist.world > 1 && (e->dist_allreduce || e->chain.comm))))) return 0;  // cuda_mpm_solver.cu:216-217
     REQUIRE(e->grid_state == 2, "UpdateContact before UpdateGrid");
     return update_contact(e, frame, substep, SolveParams(dt, mu, stiffness, damping, exact, max_iters), dump, iters_out, residual_out,
                           nullptr);

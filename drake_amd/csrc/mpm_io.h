@@ -307,7 +307,9 @@ static int download_grid(mpm_engine* e, int which, void* out, size_t bytes, size
     } else if (which == MPM_ARR_GRID_DIR) {
         // the relaxed Newton direction of the last UpdateContact iteration (nodes without contacts: 0)
         if (int rc_n = resolve_contact_count(e)) return rc_n;
-        REQUIRE(e->cb.n > 0 && e->cb.gD && e->grid_state == 2, "grid_Dir is only defined after UpdateContact");
+        // (a rank of a partitioned domain without a pair of its own has one too: at the zone nodes its neighbours' contacts reach)
+        REQUIRE((e->cb.n > 0 || (e->dp.dist.on && e->cb.last_iters > 0)) && e->cb.gD && e->grid_state == 2,
+                "grid_Dir is only defined after UpdateContact");
         field = e->cb.gD;
     } else if (e->grid_state == 3) {
         // raw sums already gathered (multi-GPU path)

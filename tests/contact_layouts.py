@@ -402,9 +402,10 @@ def contact_terms(lay, P, v, vp, ev=None):
                 ut=np.linalg.norm(ut, axis=1), phi0=phi0, yn0=yn0, e_yn0=e_yn0, ts=ts, du=du)
 
 
-def chain_lengths(keys, sequential=False):
+def chain_lengths(keys, sequential=False, received=None):
     """L_n per node of `nodes` (docstring): segments = contacts of one base cell inside one tile of 64 contacts in the
-    solve's order (ascending cell key, stable); the float oracle's sequential sums: N_n"""
+    solve's order (ascending cell key, stable); the float oracle's sequential sums: N_n.  received: dense keys of the
+    nodes whose sums take one more float addition (a partitioned domain adds the neighbour's sums there): L_n + 1"""
     base = keys[:, 0]
     order = np.argsort(base, kind="stable")
     sk = base[order]
@@ -419,19 +420,21 @@ def chain_lengths(keys, sequential=False):
     nodes, inv = np.unique(keys, return_inverse=True)
     inv = inv.reshape(keys.shape)
     N = np.bincount(inv.reshape(-1), minlength=len(nodes)).astype(np.float64)
+    more = 0.0 if received is None else np.isin(nodes, np.asarray(received)).astype(np.float64)
     if sequential:
-        return nodes, inv, N, N
+        return nodes, inv, N + more, N
     longest = np.zeros(len(nodes))
     np.maximum.at(longest, inv.reshape(-1), np.repeat(seg_len[seg_id], 27).astype(np.float64))
     # segments per node: distinct (node, segment) pairs
     pairs = np.unique(inv.reshape(-1) * (sid.max() + 1) + np.repeat(seg_id, 27))
     nseg = np.bincount(pairs // (sid.max() + 1), minlength=len(nodes)).astype(np.float64)
-    return nodes, inv, longest + 8 + nseg + 4, N
+    return nodes, inv, longest + 8 + nseg + 4 + more, N
 
 
-def direction(lay, P, wt, keys, mass_c, T, gm, gv, gvs, relax=RELAX, sequential=False, ev_grid=0.0):
-    """node sums, DoFs and the relaxed direction at the nodes that see contacts (dense keys `nodes`), with bounds"""
-    nodes, inv, L, N = chain_lengths(keys, sequential)
+def direction(lay, P, wt, keys, mass_c, T, gm, gv, gvs, relax=RELAX, sequential=False, ev_grid=0.0, received=None):
+    """node sums, DoFs and the relaxed direction at the nodes that see contacts (dense keys `nodes`), with bounds;
+    received: chain_lengths' (the nodes of a partitioned domain that add a neighbour's sums)"""
+    nodes, inv, L, N = chain_lengths(keys, sequential, received)
     nn = len(nodes)
     m = np.asarray(mass_c, np.float64)[:, None]
     f = inv.reshape(-1)

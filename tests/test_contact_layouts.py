@@ -46,8 +46,8 @@ def run_oracle(lay, real, iters=1, exact=False, relax=None):
     return o, pre, r
 
 
-def restate(lay, o, pre, sequential, relax=cl.RELAX):
-    """every restated phase of one Newton iteration on the oracle's inputs"""
+def restate(lay, o, pre, sequential, relax=cl.RELAX, received=None):
+    """every restated phase of one Newton iteration on the oracle's inputs (received: cl.chain_lengths')"""
     P = cl.params32(lay["params"])
     gm, gv, gvs = pre
     cp = lay["cp"]
@@ -55,7 +55,7 @@ def restate(lay, o, pre, sequential, relax=cl.RELAX):
     mass_c = lay["mass"][cp["particle"]].astype(np.float64)
     b, wt, keys, T = cl.prepare(lay, P, gm, gv, gvs, vp, mass_c)
     vel0, e0 = cl.gather(wt, keys, gv, gm)
-    dr = cl.direction(lay, P, wt, keys, mass_c, T, gm, gv, gvs, relax=relax, sequential=sequential)
+    dr = cl.direction(lay, P, wt, keys, mass_c, T, gm, gv, gvs, relax=relax, sequential=sequential, received=received)
     return dict(P=P, vp=vp, mass_c=mass_c, wt=wt, keys=keys, T=T, vel0=vel0, e0=e0, dr=dr)
 
 

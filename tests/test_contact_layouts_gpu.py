@@ -25,7 +25,8 @@ pytestmark = pytest.mark.gpu
 CANDIDATES = [2.0 ** -j for j in range(28)]
 
 
-def _engine(lay, deterministic=False, env=None):
+def _create(lay, deterministic=False, env=None):
+    """the layout's mesh in a finalised engine -> (engine, API slot of every particle of the layout)"""
     from drake_amd import ARR as A, GpuMpm
     env = dict(env or {})
     saved = {k: os.environ.get(k) for k in env}
@@ -50,29 +51,60 @@ def _engine(lay, deterministic=False, env=None):
     pids = g.download(A.PIDS)
     slot_of = np.empty_like(pids)
     slot_of[pids] = np.arange(len(pids))
+    return g, slot_of, pids
+
+
+def _upload(g, lay, pids):
     g.upload_particle_state(lay["pos"][pids], lay["vel"][pids], lay["C"][pids], lay["vol"][pids], None)
     g.reallocate_external_bodies(lay["n_bodies"])
+
+
+def _pre(g, lay, slot_of):
+    """the inputs of the solve as the engine holds them, and the API slots of the layout's contact particles"""
+    from drake_amd import ARR as A
+    s = slot_of[lay["cp"]["particle"]]
+    pre = dict(gm=g.download(A.GRID_MASSES), gv=g.download(A.GRID_MOMENTUM), gvs=g.download(A.GRID_V_STAR),
+               vp=g.download(A.VELOCITIES)[s].astype(np.float64), mass_all=g.download(A.MASSES))
+    pre["mass_c"] = pre["mass_all"][s].astype(np.float64)
+    return pre, s
+
+
+def _pairs(g, lay, s, sel=slice(None)):
+    cp = lay["cp"]
+    g.copy_contact_pairs(s[sel].astype(np.uint32), cp["body"][sel], cp["dist"][sel], cp["normal"][sel], cp["pos"][sel],
+                         cp["rigid_v"][sel], cp["p_WB"][sel])
+
+
+def _engine(lay, deterministic=False, env=None, before_pairs=None):
+    """before_pairs(g): runs between mpm_create (under `env`) + Finalize and the upload of the state"""
+    g, slot_of, pids = _create(lay, deterministic, env)
+    if before_pairs:
+        before_pairs(g)
+    k, d, dt, mu = cl.params32(lay["params"])
+    _upload(g, lay, pids)
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(dt)
     g.particle_to_grid(dt)
     g.update_grid(-1)
-    cp = lay["cp"]
-    s = slot_of[cp["particle"]]
-    pre = dict(gm=g.download(A.GRID_MASSES), gv=g.download(A.GRID_MOMENTUM), gvs=g.download(A.GRID_V_STAR),
-               vp=g.download(A.VELOCITIES)[s].astype(np.float64), mass_all=g.download(A.MASSES))
-    pre["mass_c"] = pre["mass_all"][s].astype(np.float64)
-    g.copy_contact_pairs(s.astype(np.uint32), cp["body"], cp["dist"], cp["normal"], cp["pos"], cp["rigid_v"], cp["p_WB"])
+    pre, s = _pre(g, lay, slot_of)
+    _pairs(g, lay, s)
     return g, pre
 
 
-def _solve(g, lay, iters, exact=False):
+def _outputs(g, rg):
     from drake_amd import ARR as A
-    k, d, dt, mu = cl.params32(lay["params"])
-    rg = g.update_contact(dt, mu, k, d, exact_line_search=exact, max_newton_iterations=iters)
+    n = rg["contacts"]
+    none = np.zeros((0, 3), np.float32)
     out = dict(rg=rg, cs=g.contact_stats(), D=g.download(A.GRID_DIR), gv1=g.download(A.GRID_MOMENTUM),
-               vel0=g.download(A.CONTACT_VEL0), vel=g.download(A.CONTACT_VEL), log=g.contact_log(), stats=g.stats())
+               vel0=g.download(A.CONTACT_VEL0) if n else none, vel=g.download(A.CONTACT_VEL) if n else none,
+               log=g.contact_log(), stats=g.stats())
     out["tau"], out["f"] = g.external_body_force_to_host()
     return out
+
+
+def _solve(g, lay, iters, exact=False):
+    k, d, dt, mu = cl.params32(lay["params"])
+    return _outputs(g, g.update_contact(dt, mu, k, d, exact_line_search=exact, max_newton_iterations=iters))
 
 
 def _record(what, ratio):
@@ -105,57 +137,71 @@ def _alpha_consistent(ls, alpha, chk, what):
             chk.fails += [] if a["E"] - E0["E"] <= slack else [f"{what}: accepted {alpha} was not acceptable"]
 
 
-def _iteration_checks(lay, pre, out, chk, relax=cl.RELAX):
+def _iteration_checks(lay, pre, out, chk, relax=cl.RELAX, part=None):
+    """part: `out` is what ONE RANK of a partitioned domain holds after the solve (tests/cut_layouts.py), `lay` and `pre`
+    are the union's (every node's grid values from its owner).  dict(sel: the rank's contacts, in the order it was given
+    them; list: the dense keys of the nodes it lists; received: the nodes that add a neighbour's sums (L_n + 1); D: the
+    union's direction, every node from its owner (the line search's sums are global); gm, gv: the rank's own grid before
+    the solve; gv1: the union's grid after it; f, tau: the impulses summed over the ranks, ranks: how many)"""
     P = cl.params32(lay["params"])
     gm, gv, gvs = pre["gm"], pre["gv"], pre["gvs"]
     b, wt, keys, T = cl.prepare(lay, P, gm, gv, gvs, pre["vp"], pre["mass_c"])
     cs = out["cs"]
-    nc = len(lay["cp"]["particle"])
+    sel = slice(None) if part is None else part["sel"]
+    nc = len(lay["cp"]["particle"][sel])
     assert out["stats"]["error_flags"] == 0, out["stats"]
-    assert cs["contacts"] == nc and cs["iterations"] == 1
+    assert cs["contacts"] == nc and cs["iterations"] == 1, (cs, nc)
     # set-up
     vel0, e0 = cl.gather(wt, keys, gv, gm)
-    chk("vel0", out["vel0"] - vel0, e0)
-    dr = cl.direction(lay, P, wt, keys, pre["mass_c"], T, gm, gv, gvs, relax=relax)
+    chk("vel0", out["vel0"] - vel0[sel], e0[sel])
+    dr = cl.direction(lay, P, wt, keys, pre["mass_c"], T, gm, gv, gvs, relax=relax,
+                      received=None if part is None else part["received"])
     nodes = dr["nodes"]
-    assert cs["nodes"] == len(nodes), (cs["nodes"], len(nodes))
+    listed = np.ones(len(nodes), bool) if part is None else np.isin(nodes, part["list"])
+    assert part is None or np.isin(part["list"], nodes).all()
+    assert cs["nodes"] == listed.sum(), (cs["nodes"], int(listed.sum()))
     # direction
     D = out["D"].astype(np.float64)
-    ok = dr["dof"] & ~dr["amb"]
+    ok = dr["dof"] & ~dr["amb"] & listed
     chk("Dir", D[nodes][ok] - dr["D"][ok], dr["eD"][ok])
-    off = ~dr["dof"] & ~dr["amb"]
+    off = ~dr["dof"] & ~dr["amb"] & listed
     assert not D[nodes][off].any(), f"{chk.tag}: a direction where the restatement has no DoF"
     rest = np.ones(len(D), bool)
-    rest[nodes] = False
-    assert not D[rest].any()
+    rest[nodes[listed]] = False
+    assert not D[rest].any(), f"{chk.tag}: a direction off the node list"
     lo, hi = int((dr["dof"] & ~dr["amb"]).sum()), int(dr["dof"].sum() + dr["amb"].sum())
     assert lo <= cs["dofs"] <= hi, (cs["dofs"], lo, hi)
     if not dr["amb"].any():
-        assert cs["dofs"] == lo
+        assert cs["dofs"] == lo, (cs["dofs"], lo)
         d = dr["D"] / relax
         chk("|Dir|^2", [cs["norm_dir_sq"] - dr["nd"]], [2 * (np.abs(d) * dr["eD"] / relax).sum() + cl.U32 * dr["nd"]])
     # line search on the engine's direction
     al = float(cs["alpha"])
     cands = [a for a in CANDIDATES if a >= al]
-    ls = cl.line_search(lay, P, wt, keys, pre["mass_c"], T, gm, gv, gvs, D, nodes, [0.0] + cands)
+    Dls = D if part is None else np.asarray(part["D"], np.float64)
+    ls = cl.line_search(lay, P, wt, keys, pre["mass_c"], T, gm, gv, gvs, Dls, nodes, [0.0] + cands)
     chk("E0", [cs["E0"] - ls[0]["E"]], [ls[0]["eE"]])
     chk("E(alpha)", [cs["energy"] - ls[-1]["E"]], [ls[-1]["eE"]])
     _alpha_consistent(ls, al, chk, "alpha")
     # the step on the grid: v - alpha D at the nodes that see contacts (m > 0), nothing elsewhere
-    v = gv.astype(np.float64).copy()
+    gm_own, gv_own = (gm, gv) if part is None else (part["gm"], part["gv"])
+    v = gv_own.astype(np.float64).copy()
     live = np.zeros(len(v), bool)
-    live[nodes] = gm[nodes] > 0
+    live[nodes[listed]] = gm_own[nodes[listed]] > 0
     want = v.copy()
     want[live] = v[live] - al * D[live]
     chk("grid v after the step", out["gv1"][live] - want[live], 2 * cl.U32 * (np.abs(want[live]) + al * np.abs(D[live])))
-    assert np.array_equal(out["gv1"][~live], gv[~live])
+    assert np.array_equal(out["gv1"][~live], gv_own[~live])
     # contact velocities after the solve and the impulses of every body
     q = tl.fixed_quanta(pre["mass_all"])[1]   # (the momentum quantum 1 / DP::fix_p)
-    imp = cl.impulses(lay, wt, keys, gm, gv, out["gv1"], pre["mass_c"], quantum=q)
-    chk("contact vel", out["vel"] - imp["v"], imp["ev"])
-    chk("F_f", out["f"] - imp["f"], imp["ef"])
-    chk("F_tau", out["tau"] - imp["tau"], imp["et"])
-    return dict(wt=wt, keys=keys, T=T, dr=dr, P=P)
+    imp = cl.impulses(lay, wt, keys, gm, gv, out["gv1"] if part is None else part["gv1"], pre["mass_c"], quantum=q)
+    chk("contact vel", out["vel"] - imp["v"][sel], imp["ev"][sel])
+    # (a partitioned domain: every rank's accumulator rounds once more, one quantum per rank)
+    more = 0.0 if part is None else part["ranks"] * q
+    f, tau = (out["f"], out["tau"]) if part is None else (part["f"], part["tau"])
+    chk("F_f", f - imp["f"], imp["ef"] + more)
+    chk("F_tau", tau - imp["tau"], imp["et"] + more)
+    return dict(wt=wt, keys=keys, T=T, dr=dr, P=P, ls=ls)
 
 
 @pytest.mark.parametrize("name", cl.NAMES)
