@@ -48,6 +48,16 @@ constexpr unsigned VF_CHUNK = 32;
 __host__ __device__ inline size_t vf_entry(unsigned k, unsigned j) {
     return (size_t)(k / VF_CHUNK) * (8u * VF_CHUNK) + j * VF_CHUNK + (k % VF_CHUNK);
 }
+// How many of a chunk's eight planes the READERS fetch (vertex_force_vf's PLANES; the layout and the writers are the same
+// for every engine).  A mesh is a property of the engine from Finalize on, and so is its largest valence V: the ranks of
+// a face's corners (fq[3].x, DP::fg[..].w) are below V, so k_fem and k_damp never write a plane >= V, and the planes at or
+// above a vertex's own valence hold +0 -- from the zero-filled allocation (Finalize, every resize of a partitioned
+// rank) and, at the vertex's new slot, from every re-sort (k_rb_finish: from the adjacency of a single domain, from the
+// face ids that travel with a vertex of a partitioned one, so also for a vertex that a migration has just brought).
+// With V <= VF_PLANES_REGULAR -- every regular triangulation with one diagonal direction, where an inner vertex has six
+// faces -- reading six planes gives the same sums as reading eight.
+constexpr int VF_PLANES_REGULAR = 6, VF_PLANES_ALL = 8;
+__host__ __device__ inline int vf_planes_of(int max_valence) { return max_valence <= VF_PLANES_REGULAR ? VF_PLANES_REGULAR : VF_PLANES_ALL; }
 struct PSet {
     float4* q[4];
     int* pid;      // slot -> original particle id ([faces | verts] order of Finalize)

@@ -187,7 +187,12 @@ static void launch_fem_faces(mpm_engine* e, const DP& p, float dt) {
 }
 static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:CalcFemStateAndForce (vertex forces)");
-    if (e->nv) hipLaunchKernelGGL(k_vforce, dim3((e->g_nv + 7u) & ~7u), dim3(256), 0, e->stream, p);
+    // (the instance that reads as many planes of DP::VF as the meshes' largest valence needs: vf_planes_of)
+    if (e->nv) {
+        const dim3 g((e->g_nv + 7u) & ~7u), b(256);
+        if (vf_planes_of(e->max_valence) == VF_PLANES_REGULAR) hipLaunchKernelGGL(k_vforce<VF_PLANES_REGULAR>, g, b, 0, e->stream, p);
+        else hipLaunchKernelGGL(k_vforce<VF_PLANES_ALL>, g, b, 0, e->stream, p);
+    }
     // (an engine with bending stiffness, mpm_set_bending: f += -k Q x on the forces k_vforce has just written)
     if (e->bend.on()) hipLaunchKernelGGL(k_bend, rows_grid(e->bend.args.n_rows), dim3(256), 0, e->stream, p, e->bend.args);
     // (... and with bending damping, mpm_set_damping: f += -beta k Q v from the same table)
@@ -236,23 +241,28 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
     const dim3 g(e->g_tile), b(P2G_THREADS);
     // (deterministic mode accumulates in fixed point: exact sums whatever the order of arrival, see k_p2g's EXACT)
     const bool exact = e->deterministic || e->p2g_fixed_point;
-#define MPM_P2G_LAUNCH(F)                                                                          \
+    // (V: the planes of DP::VF the vertex lanes read, from the meshes' largest valence -- vf_planes_of; only the
+    // FORCES = 1 instances read them)
+#define MPM_P2G_LAUNCH(F, V)                                                                       \
     do {                                                                                           \
-        if (exact) hipLaunchKernelGGL((k_p2g<F, 1>), g, b, 0, e->stream, p, dt);                   \
-        else hipLaunchKernelGGL((k_p2g<F, 0>), g, b, 0, e->stream, p, dt);                         \
+        if (exact) hipLaunchKernelGGL((k_p2g<F, 1, 0, V>), g, b, 0, e->stream, p, dt);             \
+        else hipLaunchKernelGGL((k_p2g<F, 0, 0, V>), g, b, 0, e->stream, p, dt);                   \
     } while (0)
     // (an engine with a table of force fields: the instances that evaluate it, mpm_set_force_fields)
-#define MPM_P2G_LAUNCH_FIELDS(F)                                                                                      \
+#define MPM_P2G_LAUNCH_FIELDS(F, V)                                                                                   \
     do {                                                                                                              \
         const ForceFieldTable* t = e->d_force_fields;                                                                 \
-        if (exact) hipLaunchKernelGGL((k_p2g<F, 1, 1, ForceFieldTable>), g, b, 0, e->stream, p, dt, t);        \
-        else hipLaunchKernelGGL((k_p2g<F, 0, 1, ForceFieldTable>), g, b, 0, e->stream, p, dt, t);              \
+        if (exact) hipLaunchKernelGGL((k_p2g<F, 1, 1, V, ForceFieldTable>), g, b, 0, e->stream, p, dt, t);     \
+        else hipLaunchKernelGGL((k_p2g<F, 0, 1, V, ForceFieldTable>), g, b, 0, e->stream, p, dt, t);           \
     } while (0)
+    const bool regular = vf_planes_of(e->max_valence) == VF_PLANES_REGULAR;
     if (!e->force_fields.empty()) {
-        if (forces == 1) MPM_P2G_LAUNCH_FIELDS(1);
-        else MPM_P2G_LAUNCH_FIELDS(0);
-    } else if (forces == 1) MPM_P2G_LAUNCH(1);
-    else MPM_P2G_LAUNCH(0);
+        if (forces == 1 && regular) MPM_P2G_LAUNCH_FIELDS(1, VF_PLANES_REGULAR);
+        else if (forces == 1) MPM_P2G_LAUNCH_FIELDS(1, VF_PLANES_ALL);
+        else MPM_P2G_LAUNCH_FIELDS(0, VF_PLANES_ALL);
+    } else if (forces == 1 && regular) MPM_P2G_LAUNCH(1, VF_PLANES_REGULAR);
+    else if (forces == 1) MPM_P2G_LAUNCH(1, VF_PLANES_ALL);
+    else MPM_P2G_LAUNCH(0, VF_PLANES_ALL);
 #undef MPM_P2G_LAUNCH_FIELDS
 #undef MPM_P2G_LAUNCH
 }

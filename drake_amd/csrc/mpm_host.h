@@ -315,7 +315,12 @@ struct mpm_engine {
         unsigned* d_ticket = nullptr;
         bool table_dirty = false;                // d_pins is not `set` yet (resolved at the next substep entry point)
     } pin;
-    int max_valence = 0;       // most faces around one vertex of the mesh (Finalize): above 8, k_vforce stays (see fused_forces)
+    // Most faces around one vertex of any cloth of the engine (Finalize, from the adjacency CSR it builds; a partitioned
+    // engine keeps the whole scene's on every rank).  Above 8, k_vforce stays (see fused_forces); at most 6, the kernels
+    // that sum a vertex's entries of DP::VF read six planes instead of eight (vf_planes_of, launch_p2g,
+    // launch_fem_vertices).  Invariant behind that: the planes at or above this number hold +0 after every re-sort and
+    // are never written by k_fem or k_damp (mpm_device.h at VF_PLANES_REGULAR).
+    int max_valence = 0;
     // launch geometry
     unsigned g_np = 0, g_nf = 0, g_nv = 0, g_tile = 0, g_grid = 0;
     // contacts / rigid bodies

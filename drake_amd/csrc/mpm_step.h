@@ -67,20 +67,26 @@ __global__ __launch_bounds__(256) void k_fem_mat(DP p, float dt, const ClothMat*
 }
 
 // the force on vertex k from its entries of DP::VF; false = they say "walk the CSR" (nothing usable summed)
+// PLANES: how many of the eight planes of a chunk are read -- VF_PLANES_ALL, or VF_PLANES_REGULAR for an engine whose
+// meshes have no vertex with more faces than that (vf_planes_of: the planes left out hold +0, and the sum below ends
+// with `+= -0` for each of them, which changes no bit of it -- not even the sign of a zero sum, (+-0) + (-0) = +-0).
+// Such an engine has no marked vertex either.
+template <int PLANES>
 MPM_DEV bool vertex_force_vf(const DP& p, int k, float& f0, float& f1, float& f2) {
-    // (one address for all eight loads: the planes of a chunk are 384 bytes apart, an immediate offset)
+    static_assert(PLANES == VF_PLANES_REGULAR || PLANES == VF_PLANES_ALL, "the two instances the launches choose between");
+    // (one address for all the loads: the planes of a chunk are 384 bytes apart, an immediate offset)
     const float* e0 = p.VF + vf_entry((unsigned)k, 0) * 3;
-    float3 g[8];
+    float3 g[PLANES];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) g[j] = *reinterpret_cast<const float3*>(e0 + (size_t)j * VF_CHUNK * 3);
+    for (int j = 0; j < PLANES; ++j) g[j] = *reinterpret_cast<const float3*>(e0 + (size_t)j * VF_CHUNK * 3);
     f0 = f1 = f2 = 0.f;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {   // (ascending original face id, as vertex_force_from; an empty entry adds -0)
+    for (int j = 0; j < PLANES; ++j) {   // (ascending original face id, as vertex_force_from; an empty entry adds -0)
         f0 += -g[j].x;
         f1 += -g[j].y;
         f2 += -g[j].z;
     }
-    return __float_as_uint(g[0].x) != VF_MARK;
+    return PLANES < VF_PLANES_ALL || __float_as_uint(g[0].x) != VF_MARK;
 }
 
 // more than 8 faces around vertex k: walk the original adjacency (the triples of these faces' corners are in G3)
@@ -102,12 +108,14 @@ MPM_DEV void vertex_force_csr(const DP& p, const PSet& S, int k, float& f0, floa
 // Vertex force = - sum over adjacent (face, corner) of that corner's force triple, summed in ascending original face
 // id (the order sequential atomics would produce): the vertex's row of DP::VF, or the adjacency CSR for a vertex with
 // more than eight faces.
+template <int PLANES>
 MPM_DEV void vertex_force_value(const DP& p, const PSet& S, int k, float& f0, float& f1, float& f2) {
-    if (!vertex_force_vf(p, k, f0, f1, f2)) vertex_force_csr(p, S, k, f0, f1, f2);
+    if (!vertex_force_vf<PLANES>(p, k, f0, f1, f2)) vertex_force_csr(p, S, k, f0, f1, f2);
 }
+template <int PLANES>
 MPM_DEV void vertex_force(const DP& p, const PSet& S, int k) {   // ... written to p.f
     float f0, f1, f2;
-    vertex_force_value(p, S, k, f0, f1, f2);
+    vertex_force_value<PLANES>(p, S, k, f0, f1, f2);
     const int s = p.Nf + k;
     p.f[0][s] = f0;
     p.f[1][s] = f1;
@@ -115,14 +123,15 @@ MPM_DEV void vertex_force(const DP& p, const PSet& S, int k) {   // ... written 
 }
 
 // (the phase-by-phase API and the partitioned-domain chains; mpm_run_substeps lets k_p2g do this per work
-// item, see k_p2g's FORCES)
+// item, see k_p2g's FORCES).  PLANES: see vertex_force_vf; launch_fem_vertices picks the instance.
+template <int PLANES>
 __global__ __launch_bounds__(256) void k_vforce(DP p) {
     if (gated_out(p)) return;
     const unsigned nva = (unsigned)p.ctl->nva;
     const unsigned chunk = xcd_chunk_active(blockIdx.x, nva);
     const int k = (int)(chunk * 256 + threadIdx.x);
     if (chunk == 0xFFFFFFFFu || k >= (int)nva) return;
-    vertex_force(p, p.set[p.ctl->cur], k);
+    vertex_force<PLANES>(p, p.set[p.ctl->cur], k);
 }
 
 // ---------------------------------------------------------------------------
@@ -142,9 +151,10 @@ __global__ __launch_bounds__(256) void k_vforce(DP p) {
 //      them in a wave-private LDS area, with the products px[i] * py[j] of their B-spline factors,
 //   3. per cell: 4 particles per MFMA step, 2 MFMAs per step (nodes 0-14 and 15-26).  Since round 6 the staged
 //      columns are the A operand and the weights the B operand: a lane's four accumulator registers
-//      are then the four TERMS (1, i, j, k) of one (node, component), folded in the lane with 4 products and 3
-//      sums -- rounds 1-5 had nodes as rows and folded across a quad with DPP -- and added to the tile: 2 LDS
-//      atomics (64 distinct words each) per cell, doubles or 64-bit fixed point (EXACT).
+//      are then the four TERMS (1, i, j, k) of one (node, component), folded in the lane with a product, two
+//      fused multiply-adds and a sum (one product more in fixed point) -- rounds 1-5 had nodes as rows and folded
+//      across a quad with DPP -- and added to the tile: 2 LDS atomics (64 distinct words each) per cell, doubles or
+//      64-bit fixed point (EXACT).
 // Replaces the warp-segmented scatter of cuda_mpm_kernels.cuh:418-543; the
 // order of particles inside a block is irrelevant.
 // ---------------------------------------------------------------------------
@@ -239,8 +249,8 @@ constexpr int P2G_WAVES = 8, P2G_THREADS = 64 * P2G_WAVES;
 // two workgroups per CU: 8 waves each at <= 128 VGPRs (4 per SIMD)
 // FORCES: where a vertex lane finds the internal force on its vertex.
 //   0  in p.f (k_vforce ran before this kernel: the phase-by-phase API, meshes with a vertex of more than eight faces)
-//   1  in the eight planes of DP::VF, summed here (one round trip of coalesced loads; a partitioned domain went through
-//      per-slot adjacency records and G3 until round 5: two dependent round trips, eight gathers)
+//   1  in the planes of DP::VF (PLANES of the eight), summed here (one round trip of coalesced loads; a partitioned
+//      domain went through per-slot adjacency records and G3 until round 5: two dependent round trips, eight gathers)
 // 1 saves the k_vforce launch of every substep.  Rounds 2-3 computed the forces of ALL vertices of an item in a
 // prologue of their own (two dependent round trips and a barrier that every workgroup of the launch walks through at
 // the same time: ~6 us in which nothing else happens); now each vertex lane fetches them with its particle records:
@@ -265,7 +275,10 @@ MPM_DEV f32x4 p2g_mfma(float y, float w, f32x4 acc) { return __builtin_amdgcn_mf
 // arguments and their code (launch_p2g picks the instance).  __restrict__: the table is read-only to the kernel, its
 // loads are scalar.
 MPM_DEV const ForceFieldTable* p2g_field_table(const ForceFieldTable* t) { return t; }
-template <int FORCES, int EXACT, int FIELDS = 0, typename... TABLE>
+// PLANES: the planes of DP::VF a vertex lane reads (FORCES = 1; see vertex_force_vf): launch_p2g picks the instance from
+// the engine's largest valence, next to EXACT and FIELDS -- a runtime count had cost more in scalar branches around the
+// loads than the loads themselves (DESIGN_HISTORY.md section 8, round 4).
+template <int FORCES, int EXACT, int FIELDS = 0, int PLANES = VF_PLANES_ALL, typename... TABLE>
 __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G_WAVES / 2, P2G_WAVES / 2))) void k_p2g(DP p, float dt, const TABLE* __restrict__... table) {
     static_assert(sizeof...(TABLE) == FIELDS, "the table is the argument of the FIELDS = 1 instances only");
     if (gated_out(p)) return;
@@ -390,7 +403,7 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
                 r.ta[0] = a.x; r.ta[1] = a.y; r.ta[2] = a.z; r.tb[0] = b.x; r.tb[1] = b.y; r.tb[2] = b.z;
                 const bool vert = r.act && !r.is_face;
                 if (FORCES == 1) {
-                    vertex_force_vf(p, vert ? (int)ii - p.Nf : 0, r.frc[0], r.frc[1], r.frc[2]);   // (vertex 0 for the other lanes: valid memory)
+                    vertex_force_vf<PLANES>(p, vert ? (int)ii - p.Nf : 0, r.frc[0], r.frc[1], r.frc[2]);   // (vertex 0 for the other lanes: valid memory)
                 } else {
                     force_of(vi, r.frc);
                 }
@@ -449,6 +462,8 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
                 }
 #pragma unroll
                 for (int r = 0; r < 3; ++r) {
+                    // (both forms and a select: one fma with the addend -0 off the gravity axis gives the same bits in three
+                    // vector instructions fewer per group and measured no faster)
                     float qq = r == p.M.gravity_axis ? fmaf(cur.v[r], m, m * gdt) : cur.v[r] * m;
                     qq += fext[r];
                     const float dot = fmaf(B[r * 3 + 2], st.fx[2], fmaf(B[r * 3], st.fx[0], B[r * 3 + 1] * st.fx[1]));
@@ -597,12 +612,21 @@ __global__ __launch_bounds__(P2G_THREADS) __attribute__((amdgpu_waves_per_eu(P2G
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const f32x4 a = t ? acc1 : acc0;
-                    // the four terms of this lane's (node, component): products, then the sums paired as (0 + 1) + (2 + 3)
+                    // The four terms of this lane's (node, component), x_r = a[r] * fac[r], summed in pairs: (x0 + x1) + (x2 + x3).
+                    // Two of the products ride in fused multiply-adds, with the same bits as products and sums of their
+                    // own: a factor is 0, 1 or 2 times the power of two of the scale, so x1 and x3 are EXACT (the scale is
+                    // 1 here or, in fixed point, far above 1 for any total mass below 2^47: nothing is pushed into the
+                    // subnormal range), and fma(a1, f1, x0) rounds the same real number x0 + x1 once, as the sum does.  A zero
+                    // product keeps its sign inside the fma, so the sum of two zeros gets the sign the separate sum gives it;
+                    // an infinite or NaN a[r] gives the same infinity or NaN either way (inf * 0 is NaN in both).  Only a
+                    // product beyond the largest float differs -- infinity then, a finite sum now where x0 cancels it: node
+                    // sums of ~1e38, or > 2^62 quanta, which fixed point reports either way (fix_worst).
+                    // Without the scale fac[0] is 1 for every lane that stores (delta >= 0), and x0 is a[0] itself.
                     float val;
                     {
 #pragma clang fp contract(off)
-                        const float x0 = a[0] * fac[t][0], x1 = a[1] * fac[t][1], x2 = a[2] * fac[t][2], x3 = a[3] * fac[t][3];
-                        val = (x0 + x1) + (x2 + x3);
+                        const float x0 = EXACT ? a[0] * fac[t][0] : a[0], x2 = a[2] * fac[t][2];
+                        val = fmaf(a[1], fac[t][1], x0) + fmaf(a[3], fac[t][3], x2);
                     }
                     if (delta[t] >= 0 && !(diag_flags(p) & 16)) {
                         if (EXACT) lds_add_fixed(tb + delta[t], val, fix_worst);
