@@ -1,0 +1,340 @@
+"""k_pin (drake_amd/csrc/mpm_pins.h) per pin and per body against the float64 restatement of tests/pin_layouts.py, on
+deterministic engines.
+
+The velocity GridToParticle left at a pinned vertex comes from a twin engine: an engine with the same pins that has run
+every call the pinned engine has run, hence holds the same state in the same particle order, and whose pins are cleared just
+before the compared substep.  After that substep every record that is not a pinned vertex's must equal the twin's to the
+bit -- k_pin writes its pins' records and nothing else -- and the twin's velocity at a pinned vertex is v_g2p.  (A twin that
+is given the pinned engine's state with mpm_upload_particle_state instead does not do: deterministic mode orders a cell's
+particles by their previous slots, so an engine's last bits are a function of its history, not of its state alone, and
+such a twin differs in the last bit of a few thousand records.)
+
+ 1. `many`, `regimes`, `materials` per pin: x, v, C and q[1].w of every pinned vertex within the derived bounds (C exact),
+    on a fresh engine, after mpm_rebuild_mapping(sort), and after a device re-sort inside one mpm_run_substeps batch.
+    Per body: the force and torque impulse of each of those substeps, read after a zeroing
+    mpm_reallocate_external_bodies, within the derived bounds; body 40 leaves every accumulator alone.
+ 2. The table's order does not matter, to the bit; mpm_run_substeps through re-sorts equals the phase calls, to the bit.
+ 3. `clocks`: every body's pins at the target of its own clock; an engine with anchors and no pins keeps the same clocks.
+ 4. `tile_fit`: need_rebuild after GridToParticle is the host's verdict, variant by variant; what the next
+    mpm_rebuild_mapping then reports."""
+import numpy as np
+import pytest
+
+from tests import anchors as an
+from tests import pin_layouts as pl
+from tests.test_pins_gpu import _same, _state
+
+pytestmark = pytest.mark.gpu
+ERR_DOMAIN = -6
+BATCH = 8          # substeps of the batch that re-sorts on the device
+
+
+def _A():
+    from drake_amd import ARR
+    return ARR
+
+
+def _record(what, ratio):
+    from tests import helpers
+    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
+
+
+def _engine(lay, pins=True):
+    """the layout's engine, deterministic, its motions and pins set; -> engine (with .density: float64 per vertex of what
+    k_pin multiplies q[0].w by)"""
+    from drake_amd import ClothMaterial, GpuMpm
+    mat = GpuMpm.default_material()
+    for k, val in lay.get("material", {}).items():
+        setattr(mat, k, val)
+    g = GpuMpm(pl.BITS, mat)
+    g.set_deterministic(True)
+    nv = np.cumsum([0] + [len(X) for X, _ in lay["cloths"]])
+    for c, (X, T) in enumerate(lay["cloths"]):
+        cm = None
+        if lay["densities"]:
+            cm = ClothMaterial.of(mat)
+            cm.density *= lay["densities"][c]
+        g.add_qr_cloth(X, lay["v0"][nv[c]:nv[c + 1]], T, cm)
+    g.finalize()
+    g.multi = bool(lay["densities"])
+    g.density = 1.0 if g.multi else float(np.float32(mat.density))
+    if lay["n_bodies"]:
+        g.reallocate_external_bodies(lay["n_bodies"])
+    if pins:
+        _set(g, lay["table"], lay["motions"])
+    return g
+
+
+def _set(g, table, motions):
+    from drake_amd import BodyMotion, Pin
+    if motions:
+        g.set_body_motions([BodyMotion(b, m[0], m[1].ravel(), m[2], m[3]) for b, m in motions.items()])
+    if table is not None:
+        g.set_pins([Pin(int(r["vertex"]), int(r["body"]), r["p_BQ"]) for r in table])
+
+
+def _phases(g, dt):
+    g.rebuild_mapping(False)
+    g.calc_fem_state_and_force(dt)
+    g.particle_to_grid(dt)
+    g.update_grid(-1)
+    g.grid_to_particle(dt)
+
+
+def _by_id(g):
+    """the particle arrays by particle id (faces first, then vertices), F by face"""
+    A = _A()
+    pid = g.download(A.PIDS)
+    out = {}
+    for k, w in (("x", A.POSITIONS), ("v", A.VELOCITIES), ("C", A.AFFINE), ("q0w", A.MASSES if g.multi else A.VOLUMES)):
+        a = g.download(w)
+        o = np.empty_like(a)
+        o[pid] = a
+        out[k] = o
+    out["F"] = g.download(A.DEFORMATION_GRADIENTS)
+    return out
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+def _check_pins(a, nf, table, ref, what, worst):
+    """x, v, C and q[1].w of the pinned vertices in state `a` (by particle id) against the restatement `ref`"""
+    ids = nf + table["vertex"].astype(np.int64)
+    ex, ev = np.abs(a["x"][ids] - ref["x"]) / ref["bx"], np.abs(a["v"][ids] - ref["vq"]) / ref["bv"]
+    worst["position"], worst["velocity"] = max(worst["position"], float(ex.max())), max(worst["velocity"], float(ev.max()))
+    assert ex.max() <= 1.0, (what, "position", float(ex.max()), int(table["body"][ex.max(axis=1).argmax()]))
+    assert ev.max() <= 1.0, (what, "velocity", float(ev.max()), int(table["body"][ev.max(axis=1).argmax()]))
+    assert np.array_equal(_bits(a["C"][ids].reshape(-1, 3, 3)), _bits(ref["C"])), (what, "C")     # (C8 is q[1].w: +0)
+
+
+STAGES = ("fresh", "after a sort", "after a device re-sort")
+
+
+def _substep(e, lay):
+    """a substep by phase calls behind a zeroing of the accumulators -> (state by particle id, (tau, f), quantum)"""
+    e.reallocate_external_bodies(lay["n_bodies"])
+    _phases(e, lay["dt"])
+    e.gpu_sync()
+    assert e.stats()["error_flags"] == 0, e.stats()
+    return _by_id(e), e.external_body_force_to_host(), e.anchor_state()["impulse_quantum"]
+
+
+def _between(e, lay, stage):
+    """what an engine runs between the compared substeps `stage` and `stage` + 1 -> the number of substeps"""
+    if stage == 0:                                                        # two substeps and another particle order
+        for _ in range(2):
+            e.substep(lay["dt"], -1)
+        pid0 = e.download(_A().PIDS)
+        e.rebuild_mapping(True)
+        assert not np.array_equal(pid0, e.download(_A().PIDS))
+        return 2
+    before = e.stats()["rebuilds"]                                         # a batch that re-sorts on the device
+    e.run_substeps(BATCH, lay["dt"], -1)
+    e.gpu_sync()
+    assert e.stats()["error_flags"] == 0 and e.stats()["rebuilds"] - before >= 1, e.stats()
+    return BATCH
+
+
+def _twin(lay, stage):
+    """an engine with the history of the pinned engine in front of compared substep `stage`, its pins cleared"""
+    e = _engine(lay)
+    for s in range(stage):
+        _substep(e, lay)
+        _between(e, lay, s)
+    e.set_pins([])
+    return e
+
+
+def _compare(g, a, acc, q, b, lay, clocks, what, worst):
+    """the pinned engine's state a and accumulators acc after a substep against the twin's state b and float64"""
+    table, motions, dt, nf = lay["table"], lay["motions"], lay["dt"], g.n_faces
+    ids = nf + table["vertex"].astype(np.int64)
+    free = np.ones(len(a["x"]), bool)
+    free[ids] = False
+    for k in ("x", "v", "C"):
+        differ = (_bits(a[k]) != _bits(b[k])).reshape(len(free), -1).any(axis=1) & free
+        assert not differ.any(), (what, k, int(differ.sum()), "records that are no pin's differ from the twin's")
+    assert np.array_equal(_bits(a["F"]), _bits(b["F"])) and np.array_equal(_bits(a["q0w"]), _bits(b["q0w"])), what
+    mass = a["q0w"][ids].astype(np.float64) * g.density
+    assert q > 0
+    ref = pl.restate(table, motions, clocks, dt, n_bodies=lay["n_bodies"], mass=mass, v_g2p=b["v"][ids], quantum=q)
+    _check_pins(a, nf, table, ref, what, worst)
+    assert np.abs(a["x"][ids] - b["x"][ids]).max() > 0                   # (the pins moved their vertices)
+    tau, f = acc
+    for body in range(lay["n_bodies"]):
+        if not ref["count"][body]:
+            assert not tau[body].any() and not f[body].any(), (what, body)
+            continue
+        ef = float(np.abs(f[body] - ref["f"][body]).max()) / ref["bf"][body]
+        et = float(np.abs(tau[body] - ref["tau"][body]).max()) / ref["btau"][body]
+        print(f"{what}: body {body}: {ref['count'][body]} pins, force {ef:.3g}, torque {et:.3g} of the bound; |impulse| "
+              f"{np.abs(ref['f'][body]).max():.3g}, bound {ref['bf'][body]:.3g}, quantum {q:.3g}")
+        worst["force"], worst["torque"] = max(worst["force"], ef), max(worst["torque"], et)
+        assert ef <= 1.0 and et <= 1.0, (what, body, ef, et)
+        assert np.abs(ref["f"][body]).max() > 1e3 * ref["bf"][body], (what, body)          # (the check sees the impulse)
+        assert np.abs(ref["tau"][body]).max() > 1e3 * ref["btau"][body], (what, body)
+    return ref["t"]
+
+
+# ---- 1 -------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["many", "regimes", "materials"])
+def test_pins_and_bodies_against_float64(name):
+    lay = pl.layout(name)
+    table, motions, dt = lay["table"], lay["motions"], lay["dt"]
+    g = _engine(lay)
+    worst = dict(position=0.0, velocity=0.0, force=0.0, torque=0.0)
+    clocks = {b: 0.0 for b in motions}
+    for stage, what in enumerate(STAGES):
+        twin = _twin(lay, stage)
+        a, acc, q = _substep(g, lay)
+        b, acc_twin, _ = _substep(twin, lay)
+        assert not acc_twin[0].any() and not acc_twin[1].any()
+        clocks = _compare(g, a, acc, q, b, lay, clocks, f"{name}, {what}", worst)
+        twin.destroy()
+        if stage + 1 < len(STAGES):
+            n = _between(g, lay, stage)
+            clocks = {b_: pl.clock_after([dt] * n, t) for b_, t in clocks.items()}
+    # body 40 is beyond the count: its pins moved (checked per pin above), and the accumulators after a fresh engine's
+    # first substep are those of an engine without body 40's pins
+    if pl.BODY_NONE in motions:
+        assert (table["body"] == pl.BODY_NONE).sum() > 100 and lay["n_bodies"] <= pl.BODY_NONE
+        out = []
+        for t in (table, table[table["body"] != pl.BODY_NONE]):
+            h = _engine(lay, pins=False)
+            _set(h, t, motions)
+            _phases(h, dt)
+            h.gpu_sync()
+            assert h.stats()["error_flags"] == 0
+            out.append(h.external_body_force_to_host())
+            h.destroy()
+        assert out[0][1].any() and np.array_equal(_bits(out[0][0]), _bits(out[1][0])) and np.array_equal(_bits(out[0][1]), _bits(out[1][1]))
+    for k, w in worst.items():
+        print(f"{name}: worst {k} error {w:.3g} of its bound")
+        _record(f"pins: {name} {k}", w)
+    g.destroy()
+
+
+# ---- 2 -------------------------------------------------------------------------------------------------------------
+def test_table_order_and_paths_agree_to_the_bit():
+    lay = pl.layout("many")
+    table = lay["table"]
+    perm = np.random.default_rng(5).permutation(len(table))
+    assert not np.array_equal(perm, np.arange(len(table)))
+    a, b, c = (_engine(lay, pins=False) for _ in range(3))
+    for g, t in ((a, table), (b, table[perm]), (c, table)):
+        _set(g, t, lay["motions"])
+    before = c.stats()["rebuilds"]
+    for _ in range(BATCH):
+        _phases(a, lay["dt"])
+        _phases(b, lay["dt"])
+    c.run_substeps(BATCH, lay["dt"], -1)
+    for g in (a, b, c):
+        g.gpu_sync()
+        assert g.stats()["error_flags"] == 0
+    assert c.stats()["rebuilds"] - before >= 1
+    sa = _state(a)
+    for body in (0, 1, 31, 32, 33):
+        assert sa["f"][body].any() and sa["tau"][body].any(), body
+    _same(sa, _state(b), "a permuted table")
+    _same(sa, _state(c), "run_substeps")
+    for g in (a, b, c):
+        g.destroy()
+
+
+# ---- 3 -------------------------------------------------------------------------------------------------------------
+def _run(g, dt, how):
+    if how == "phases":
+        _phases(g, dt)
+    elif how == "substep":
+        g.substep(dt, -1)
+    else:
+        g.run_substeps(1, dt, -1)
+
+
+@pytest.mark.parametrize("kind", ["pins", "anchors"])
+def test_clocks(kind):
+    """the schedule of pin_layouts.layout_clocks; with `anchors` the engine has no pin and an anchor that does nothing in
+    every pin's place: k_pin runs with zero pins, for its clock tail alone"""
+    lay = pl.layout("clocks")
+    table, motions = lay["table"], lay["motions"]
+    early = table["body"] < pl.CLOCK_EARLY
+    g = _engine(lay, pins=False)
+
+    def attach(t):
+        if kind == "pins":
+            _set(g, t, None)
+        else:
+            g.set_anchors(an.make_anchors([(r["vertex"], r["body"], r["p_BQ"], 0.0, 0.0, 0.0, 0) for r in t]))
+
+    _set(g, None, {b: m for b, m in motions.items() if b < pl.CLOCK_EARLY})
+    attach(table[early])
+    for dt, how in pl.CLOCK_STEPS[0]:
+        _run(g, dt, how)
+    _set(g, None, {b: m for b, m in motions.items() if b >= pl.CLOCK_EARLY})     # 18 motions: the table grows past 16 slots
+    attach(table)
+    for dt, how in pl.CLOCK_STEPS[1]:
+        _run(g, dt, how)
+    _set(g, None, {pl.CLOCK_RESET: lay["reset"]})
+    for dt, how in pl.CLOCK_STEPS[2]:
+        _run(g, dt, how)
+    g.gpu_sync()
+    assert g.stats()["error_flags"] == 0
+    ref = pl.restate(table, lay["final"], lay["expected"], 0.0)
+    if kind == "pins":
+        st = _by_id(g)
+        got = st["x"][g.n_faces + table["vertex"].astype(np.int64)]
+        gv = st["v"][g.n_faces + table["vertex"].astype(np.int64)]
+        assert (np.abs(gv - ref["vq"]) / ref["bv"]).max() <= 1.0
+    else:
+        got = g.anchor_state()["point"]
+        assert len(g.get_pins()[0]) == 0
+        assert np.array_equal(an.points(g.get_anchors(), lay["final"], lay["expected"])[0], ref["x"])
+    ratio = np.abs(got - ref["x"]) / ref["bx"]
+    for b in range(pl.CLOCK_BODIES):
+        assert ratio[table["body"] == b].max() <= 1.0, (kind, b, float(ratio[table["body"] == b].max()), lay["expected"][b])
+    print(f"clocks, {kind}: worst position error {ratio.max():.3g} of its bound")
+    _record(f"pins: clocks {kind}", float(ratio.max()))
+    g.destroy()
+
+
+# ---- 4 -------------------------------------------------------------------------------------------------------------
+def test_tile_fit_verdict_per_variant():
+    from drake_amd import MpmError
+    lay = pl.layout("tile_fit")
+    seen = []
+    for var in lay["variants"]:
+        name, pin, u, left, outside = var
+        table = pl.tile_fit_table(lay, var)
+        g = _engine(lay, pins=False)
+        _set(g, table, lay["motions"])
+        _phases(g, lay["dt"])
+        g.gpu_sync()
+        ctl = g.resort_table("CTL")
+        ref = pl.restate(table, lay["motions"], 0.0, lay["dt"])
+        x32 = ref["x"].astype(np.float32)
+        got = _by_id(g)["x"][g.n_faces + table["vertex"].astype(np.int64)]
+        assert np.array_equal(_bits(got), _bits(x32)), name
+        imap, src, pkey = (g.resort_table(w) for w in ("IMAP", "SRC_OF", "PKEY"))
+        want, ins = pl.host_verdicts(x32, table["vertex"], g.n_faces, imap, src, pkey)
+        # (the vertices are at rest: the tables bin them where the layout says)
+        for k, v in enumerate(table["vertex"]):
+            key = int(pkey[int(src[int(imap[g.n_faces + int(v)])])])
+            assert pl.block_coords(key >> 6) == pl.block_of(lay["X"][v]), (name, k)
+        assert bool(want.any()) == left and bool((~ins).any()) == outside, (name, want, ins)
+        assert want.sum() <= 1 and (not left or want[pin])
+        assert ctl["need_rebuild"] == int(left), (name, ctl)
+        rebuilds = g.stats()["rebuilds"]
+        err = None
+        try:
+            g.rebuild_mapping(False)
+            g.gpu_sync()
+        except MpmError as e:
+            err = e.code
+        assert err == (ERR_DOMAIN if outside else None), (name, err)
+        if not outside:
+            assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] - rebuilds == int(left), (name, g.stats(), rebuilds)
+        seen.append((name, left, outside))
+        g.destroy()
+    assert sum(l for _, l, _ in seen) == 8 and sum(o for _, _, o in seen) == 2 and len(seen) == 17
