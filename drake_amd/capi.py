@@ -339,6 +339,59 @@ def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
     return out
 
 
+WEAVE_DTYPE = np.dtype([("E_warp", "<f4"), ("E_weft", "<f4"), ("nu", "<f4"), ("G", "<f4"), ("warp_dir", "<f4", (3,))])
+assert WEAVE_DTYPE.itemsize == 28
+
+
+def weave(E_warp=0.0, E_weft=0.0, nu=0.0, G=0.0, warp_dir=(1.0, 0.0, 0.0)):
+    """one mpm_cloth_weave_t as a WEAVE_DTYPE record (all moduli zero: the cloth has no weave)"""
+    out = np.zeros((), WEAVE_DTYPE)
+    out["E_warp"], out["E_weft"], out["nu"], out["G"], out["warp_dir"] = E_warp, E_weft, nu, G, warp_dir
+    return out
+
+
+def weave_coefficients(E_warp, E_weft, nu, G):
+    """(ka, kb, kab, 2G) float32 as mpm_set_weave forms them: in double from the float constants, rounded once"""
+    Ea, Eb, nu, G = (float(np.float32(a)) for a in (E_warp, E_weft, nu, G))
+    D = 1.0 - nu * nu * Eb / Ea if Ea > 0 else 1.0
+    return np.array([Ea / D, Eb / D, nu * Eb / D if Ea > 0 else 0.0, 2.0 * G]).astype(np.float32)
+
+
+def weave_face_records(dminv3, vol, coef4, cs2, x):
+    """mpm_weave_face_records: the weave kernel's face function on the host.  dminv3 (n, 3) = (Dm0, Dm1, Dm3), vol (n,),
+    coef4 (n, 4) = (ka, kb, kab, 2G), cs2 (n, 2) = (c, s) (rows are broadcast), x (n, 3, 3) corner positions; returns
+    (records (n, 3, 3), strains (n, 3) = Eaa, Ebb, Eab, energies (n,) = vol Psi), float32.  Needs no engine and no GPU."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 3, 3)
+    n = len(x)
+    dm = np.ascontiguousarray(dminv3, np.float32).reshape(n, 3)
+    vol = np.ascontiguousarray(np.broadcast_to(np.asarray(vol, np.float32), (n,)))
+    coef = np.ascontiguousarray(np.broadcast_to(np.asarray(coef4, np.float32), (n, 4)))
+    cs = np.ascontiguousarray(np.broadcast_to(np.asarray(cs2, np.float32), (n, 2)))
+    rec, strain, energy = np.zeros((n, 3, 3), np.float32), np.zeros((n, 3), np.float32), np.zeros(n, np.float32)
+    rc = lib.mpm_weave_face_records(n, dm.ctypes.data, vol.ctypes.data, coef.ctypes.data, cs.ctypes.data, x.ctypes.data,
+                                    rec.ctypes.data, strain.ctypes.data, energy.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return rec, strain, energy
+
+
+def weave_face_axes(rest_x, dirs):
+    """mpm_weave_face_axes: ((c, s) (n, 2) float32, first bad face or -1) of the rest corners rest_x (n, 3, 3) and the
+    directions dirs (n, 3) (one row is broadcast).  A face whose direction is zero or within the 1e-3 cone of its normal
+    gets (0, 0); the C call then returns MPM_ERR_INVALID, which this wrapper reports through the index alone.  Needs no
+    engine and no GPU."""
+    lib = load_library()
+    X = np.ascontiguousarray(rest_x, np.float32).reshape(-1, 3, 3)
+    n = len(X)
+    d = np.ascontiguousarray(np.broadcast_to(np.asarray(dirs, np.float32), (n, 3)))
+    cs, bad = np.zeros((n, 2), np.float32), C.c_int32(-1)
+    rc = lib.mpm_weave_face_axes(n, X.ctypes.data, d.ctypes.data, cs.ctypes.data, C.byref(bad))
+    if rc and bad.value < 0:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return cs, int(bad.value)
+
+
 def grid_collider_preset(mpm_bc: int, sdf_friction: float = 0.3):
     """The collider table that reproduces the reference's scene mpm_bc (cuda_mpm_kernels.cuh:673-774)."""
     lib = load_library()
@@ -497,6 +550,8 @@ SYMBOLS = [
     "mpm_get_body_contact_materials", "mpm_set_bending", "mpm_get_bending", "mpm_bending_forces",
     "mpm_bending_max_stable_dt", "mpm_bending_matrix", "mpm_measure", "mpm_face_strain", "mpm_cloth_energy_density",
     "mpm_set_damping", "mpm_get_damping", "mpm_damping_forces", "mpm_damping_max_stable_dt", "mpm_damping_face_records",
+    "mpm_set_weave", "mpm_get_weave", "mpm_weave_axes", "mpm_weave_forces", "mpm_weave_strain", "mpm_weave_energy",
+    "mpm_weave_max_stable_dt", "mpm_weave_face_records", "mpm_weave_face_axes",
     "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
     "mpm_set_anchors", "mpm_get_anchors", "mpm_anchor_forces", "mpm_anchor_state", "mpm_anchors_max_stable_dt",
     "mpm_anchor_point",
@@ -662,6 +717,15 @@ def load_library(build: bool = True):
         "mpm_damping_forces": [vp, vp],
         "mpm_damping_max_stable_dt": [vp, P(f)],
         "mpm_damping_face_records": [sz, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mpm_set_weave": [vp, sz, vp, vp],
+        "mpm_get_weave": [vp, vp, sz, P(sz)],
+        "mpm_weave_axes": [vp, vp],
+        "mpm_weave_forces": [vp, vp, vp],
+        "mpm_weave_strain": [vp, vp],
+        "mpm_weave_energy": [vp, vp, sz, P(sz), P(C.c_double)],
+        "mpm_weave_max_stable_dt": [vp, P(f)],
+        "mpm_weave_face_records": [sz, vp, vp, vp, vp, vp, vp, vp, vp],
+        "mpm_weave_face_axes": [sz, vp, vp, vp, P(C.c_int32)],
         "mpm_measure": [vp, vp, sz, P(sz), vp],
         "mpm_face_strain": [vp, vp],
         "mpm_cloth_energy_density": [vp, sz, vp, vp],
@@ -979,6 +1043,70 @@ class GpuMpm:
     @staticmethod
     def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
         return damping_face_records(dminv3, vol, mu, lam, beta, x, v)
+
+    def set_weave(self, weaves, face_dirs=None):
+        """mpm_set_weave: one WEAVE_DTYPE record (capi.weave(...)) or (E_warp, E_weft, nu, G, dx, dy, dz) row per cloth,
+        in cloth order -- an orthotropic warp / weft / shear stiffness added to the isotropic membrane.  face_dirs:
+        None, or (n_faces, 3) rest-space directions per face (a zero row falls back to the cloth's warp_dir).  An
+        empty list or all-zero moduli switch the feature off."""
+        if isinstance(weaves, np.ndarray) and weaves.dtype == WEAVE_DTYPE:
+            w = np.ascontiguousarray(weaves).reshape(-1)
+        elif len(weaves) and isinstance(weaves[0], np.ndarray) and weaves[0].dtype == WEAVE_DTYPE:
+            w = np.array(list(weaves), WEAVE_DTYPE).reshape(-1)
+        else:
+            w = np.ascontiguousarray(weaves, np.float32).reshape(-1, 7).view(WEAVE_DTYPE).reshape(-1)
+        fd = None
+        if face_dirs is not None:
+            fd = np.ascontiguousarray(face_dirs, np.float32).reshape(-1, 3)
+            if len(fd) != self.n_faces:
+                raise ValueError("face_dirs must have one row per face")
+        self._ck(self.lib.mpm_set_weave(self.h, len(w), w.ctypes.data if len(w) else None, _ptr(fd) if fd is not None else None))
+
+    def get_weave(self):
+        """mpm_get_weave: the constants in force, (n_cloths,) WEAVE_DTYPE (zeros while off)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_weave(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, WEAVE_DTYPE)
+        self._ck(self.lib.mpm_get_weave(self.h, out.ctypes.data if out.size else None, len(out), C.byref(n)))
+        return out
+
+    def weave_axes(self):
+        """mpm_weave_axes: (c, s) per face, (n_faces, 2) float32 in original face order; (0, 0) where off."""
+        out = np.zeros((self.n_faces, 2), np.float32)
+        self._ck(self.lib.mpm_weave_axes(self.h, _ptr(out)))
+        return out
+
+    def weave_forces(self, records=False):
+        """mpm_weave_forces: the weave's force on the current positions, (n_verts, 3) float32 in the vertex numbering of
+        dump_cpu_state; with records=True also the corner records (n_faces, 3, 3) ([face][corner][component])."""
+        out = np.zeros((self.n_verts, 3), np.float32)
+        rec = np.zeros((self.n_faces, 3, 3), np.float32) if records else None
+        self._ck(self.lib.mpm_weave_forces(self.h, _ptr(out), _ptr(rec) if records else None))
+        return (out, rec) if records else out
+
+    def weave_strain(self):
+        """mpm_weave_strain: (Eaa, Ebb, Eab) per face, (n_faces, 3) float32 (zeros on a cloth without weave)."""
+        out = np.zeros((self.n_faces, 3), np.float32)
+        self._ck(self.lib.mpm_weave_strain(self.h, _ptr(out)))
+        return out
+
+    def weave_energy(self):
+        """mpm_weave_energy: (per cloth (n_cloths,) float64, total float) of the weave's elastic energy."""
+        n, total = C.c_size_t(), C.c_double()
+        self._ck(self.lib.mpm_weave_energy(self.h, None, 0, C.byref(n), None))
+        out = np.zeros(n.value, np.float64)
+        self._ck(self.lib.mpm_weave_energy(self.h, out.ctypes.data if out.size else None, len(out), C.byref(n), C.byref(total)))
+        return out, float(total.value)
+
+    def weave_max_stable_dt(self) -> float:
+        """mpm_weave_max_stable_dt: the dt above which the substep entry points refuse (inf while the weave is off)."""
+        dt = C.c_float()
+        self._ck(self.lib.mpm_weave_max_stable_dt(self.h, C.byref(dt)))
+        return float(dt.value)
+
+    @staticmethod
+    def weave_face_records(dminv3, vol, coef4, cs2, x):
+        return weave_face_records(dminv3, vol, coef4, cs2, x)
 
     def set_links(self, table):
         """mpm_set_links: the links between cloth vertices -- seams (rest_length 0), springs and tension-only cords --, an

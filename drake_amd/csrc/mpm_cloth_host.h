@@ -1,5 +1,5 @@
 // Host side of the per-cloth features: cloth materials, external force fields, row tables, bending stiffness, links,
-// pressure, shell bending, damping and the per-cloth report -- what the entry points in mpm_engine.hip call once their
+// pressure, shell bending, damping, the weave and the per-cloth report -- what the entry points in mpm_engine.hip call once their
 // arguments are checked.
 // Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
 #pragma once
@@ -679,6 +679,181 @@ static int damping_face_records(size_t n_faces, const float* dminv3, const float
         damp_face(dminv3[3 * f], dminv3[3 * f + 1], dminv3[3 * f + 2], vol[f], mu[f], lambda[f], beta[f], x, v, rec);
         std::memcpy(rec9_out + 9 * f, rec, sizeof rec);
     }
+    return 0;
+}
+
+// ---- woven cloth (mpm_set_weave, mpm_get_weave, mpm_weave_axes, mpm_weave_forces, mpm_weave_strain, mpm_weave_energy,
+// mpm_weave_max_stable_dt, mpm_weave_face_records, mpm_weave_face_axes; mpm_weave.h) ----
+// Puts the constants `w` (checked; one per cloth, or none) and the directions in force: k_weave's three tables, the
+// ranges of k_weave_energy and the stability limit.  The caller has settled the owed substeps.  A failure changes nothing.
+static int weave_apply(mpm_engine* e, std::vector<mpm_cloth_weave_t> w, const float* face_dirs) {
+    const size_t nc = w.size();
+    std::vector<float4> coef(std::max<size_t>(nc, 1), make_float4(0.f, 0.f, 0.f, 0.f));
+    bool any = false;
+    for (size_t c = 0; c < nc; ++c) {
+        float k[4];
+        weave_coefficients(w[c].E_warp, w[c].E_weft, w[c].nu, w[c].G, k);
+        coef[c] = make_float4(k[0], k[1], k[2], k[3]);
+        any = any || k[0] != 0.f || k[1] != 0.f || k[2] != 0.f || k[3] != 0.f;
+    }
+    mpm_engine::Weave next;
+    FreshArrays fresh(e);
+    if (any) {
+        std::vector<int> cloth_of_face(e->nf, 0);
+        std::vector<int2> ranges(nc);
+        next.axis.assign(2 * e->nf, 0.f);
+        for (size_t c = 0; c < nc; ++c) {
+            const mpm_engine::Cloth& cl = e->cloths[c];
+            ranges[c] = make_int2((int)cl.first_face, (int)(cl.first_face + cl.n_faces));
+            std::fill(cloth_of_face.begin() + (long)cl.first_face, cloth_of_face.begin() + (long)(cl.first_face + cl.n_faces), (int)c);
+            const float4 k = coef[c];
+            if (k.x == 0.f && k.y == 0.f && k.z == 0.f && k.w == 0.f) continue;
+            for (size_t f = cl.first_face; f < cl.first_face + cl.n_faces; ++f) {
+                float X[3][3];
+                for (int j = 0; j < 3; ++j) std::memcpy(X[j], &e->h_pos[(size_t)e->h_idx[3 * f + j] * 3], 12);
+                const float* d = w[c].warp_dir;
+                if (face_dirs && (face_dirs[3 * f] != 0.f || face_dirs[3 * f + 1] != 0.f || face_dirs[3 * f + 2] != 0.f))
+                    d = face_dirs + 3 * f;
+                if (!weave_face_axis(X, d, &next.axis[2 * f]))
+                    return fail(MPM_ERR_INVALID, "weave: face " + std::to_string(f) + " (cloth " + std::to_string(c) +
+                                                     "): the warp direction is zero or within 1e-3 of the face's rest normal");
+            }
+        }
+        // Gershgorin's row sums of the weave's stiffness at the rest shape, per vertex, over the vertices' masses
+        std::vector<float> wq, mass;
+        if (int rc = vertex_masses(e, mass, &wq)) return rc;
+        std::vector<float> dminv(e->nf * 4);
+        int* iota = nullptr;
+        if (int rc = device_iota(e, &iota)) return rc;
+        if (int rc = gather_to_host<F_DMINV>(e, dminv.data(), e->nf, iota)) return rc;
+        std::vector<double> K(e->nv, 0.0);
+        for (size_t f = 0; f < e->nf; ++f) {
+            const float4 c = coef[(size_t)cloth_of_face[f]];
+            const float k4[4] = {c.x, c.y, c.z, c.w};
+            const double kmax = weave_kmax(k4);
+            if (!(kmax > 0.0)) continue;
+            const double Dm0 = dminv[4 * f], Dm1 = dminv[4 * f + 1], Dm3 = dminv[4 * f + 3];
+            const double vol = std::fabs((double)wq[f]) / (e->multi_mat ? (double)e->h_rho_of_pid[f] : 1.0);
+            const double g[3] = {std::hypot(Dm0, Dm1 + Dm3), std::hypot(Dm0, Dm1), std::fabs(Dm3)};   // |columns of grad_N|
+            const double s = vol * kmax * (g[0] + g[1] + g[2]);
+            for (int k = 0; k < 3; ++k) K[(size_t)e->h_idx[3 * f + k]] += s * g[k];
+        }
+        next.max_dt = stable_dt_limit(std::sqrt(max_row_rate(K.data(), e->nv, 1.0, [&](size_t i) { return mass[i]; })));
+        float4* d_coef = nullptr;
+        int* d_cloth = nullptr;
+        float2* d_axis = nullptr;
+        int2* d_ranges = nullptr;
+        if (int rc = fresh.alloc(&d_coef, coef.size(), false)) return rc;
+        if (int rc = fresh.alloc(&d_cloth, std::max<size_t>(cloth_of_face.size(), 1), false)) return rc;
+        if (int rc = fresh.alloc(&d_axis, std::max<size_t>(e->nf, 1), false)) return rc;
+        if (int rc = fresh.alloc(&d_ranges, ranges.size(), false)) return rc;
+        H2D(e, d_coef, coef.data(), coef.size() * sizeof(float4));
+        if (e->nf) {
+            H2D(e, d_cloth, cloth_of_face.data(), cloth_of_face.size() * sizeof(int));
+            H2D(e, d_axis, next.axis.data(), next.axis.size() * sizeof(float));
+        }
+        H2D(e, d_ranges, ranges.data(), ranges.size() * sizeof(int2));
+        next.args = WeaveArgs{d_coef, d_cloth, d_axis};
+        next.d_ranges = d_ranges;
+    }
+    // (a synchronisation point: the kernels enqueued so far have read the old tables)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    {
+        float4* o_coef = const_cast<float4*>(e->weave.args.coef);
+        int* o_cloth = const_cast<int*>(e->weave.args.cloth_of_face);
+        float2* o_axis = const_cast<float2*>(e->weave.args.axis);
+        int2* o_ranges = const_cast<int2*>(e->weave.d_ranges);
+        e->dfree(o_coef);
+        e->dfree(o_cloth);
+        e->dfree(o_axis);
+        e->dfree(o_ranges);
+    }
+    next.w.swap(w);
+    e->weave = next;
+    fresh.commit();
+    return 0;
+}
+
+// mpm_weave_forces (f_out, rec_out), mpm_weave_strain (strain_out), mpm_weave_energy (per_cloth, capacity, n_out, total;
+// `total` non-null selects it): one launch of k_weave_eval on the current state, by original face id; zeros while off.
+static int weave_eval(mpm_engine* e, float* f_out, float* rec_out, float* strain_out, double* per_cloth, size_t capacity,
+                      size_t* n_out, double* total) {
+    const size_t nf = e->nf, nc = e->cloths.size();
+    if (f_out) std::memset(f_out, 0, e->nv * 12);
+    if (rec_out) std::memset(rec_out, 0, nf * 36);
+    if (strain_out) std::memset(strain_out, 0, nf * 12);
+    if (total) {
+        std::fill(per_cloth, per_cloth + std::min(capacity, nc), 0.0);
+        if (n_out) *n_out = nc;
+        *total = 0.0;
+    }
+    if (!e->weave.on() || nf == 0) return 0;
+    // records [9 nf], strains [3 nf], energies [nf] as floats, then (8-byte aligned) one double per cloth
+    const size_t n_float = 13 * nf, off_sums = (n_float * 4 + 7) / 8 * 8;
+    if (int rc = e->stage(off_sums + nc * 8)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, off_sums + nc * 8, e->stream));
+    float* d = (float*)e->d_stage;
+    hipLaunchKernelGGL(k_weave_eval, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, e->stream, e->dp, e->weave.args, d, d + 9 * nf,
+                       d + 12 * nf);
+    if (total)
+        hipLaunchKernelGGL(k_weave_energy, dim3((unsigned)nc), dim3(256), 0, e->stream, (const float*)(d + 12 * nf), e->weave.d_ranges,
+                           (double*)((char*)e->d_stage + off_sums));
+    HIP_TRY(hipGetLastError());
+    if (total) {
+        std::vector<double> rows(nc);
+        D2H(e, rows.data(), (char*)e->d_stage + off_sums, nc * 8);
+        std::copy(rows.begin(), rows.begin() + (long)std::min(capacity, nc), per_cloth);
+        for (double r : rows) *total += r;
+        return 0;
+    }
+    if (strain_out) {
+        D2H(e, strain_out, d + 9 * nf, nf * 12);
+        return 0;
+    }
+    std::vector<float> own;
+    float* h = rec_out;
+    if (!h) {
+        own.resize(9 * nf);
+        h = own.data();
+    }
+    D2H(e, h, d, nf * 36);
+    // a vertex's records in ascending original face id, as k_vforce sums them
+    for (size_t f = 0; f < nf; ++f)
+        for (int c = 0; c < 3; ++c) {
+            float* o = f_out + 3 * (size_t)e->h_idx[3 * f + c];
+            for (int k = 0; k < 3; ++k) o[k] += -h[9 * f + 3 * c + k];
+        }
+    return 0;
+}
+
+// host code only: the device function of the kernels, compiled for the host
+static int weave_face_records(size_t n, const float* dminv3, const float* vol, const float* coef4, const float* cs2, const float* x9,
+                              float* rec9_out, float* strain3_out, float* energy_out) {
+    for (size_t f = 0; f < n; ++f) {
+        float x[3][3], rec[3][3], strain[3], energy;
+        std::memcpy(x, x9 + 9 * f, sizeof x);
+        weave_face(dminv3[3 * f], dminv3[3 * f + 1], dminv3[3 * f + 2], vol[f], coef4 + 4 * f, cs2[2 * f], cs2[2 * f + 1], x, rec,
+                   strain, &energy);
+        if (rec9_out) std::memcpy(rec9_out + 9 * f, rec, sizeof rec);
+        if (strain3_out) std::memcpy(strain3_out + 3 * f, strain, sizeof strain);
+        if (energy_out) energy_out[f] = energy;
+    }
+    return 0;
+}
+// host code only: the axis function of weave_apply
+static int weave_face_axes(size_t n, const float* rest_x9, const float* dir3, float* cs2_out, int32_t* first_bad_out) {
+    int32_t bad = -1;
+    for (size_t f = 0; f < n; ++f) {
+        float X[3][3];
+        std::memcpy(X, rest_x9 + 9 * f, sizeof X);
+        if (!weave_face_axis(X, dir3 + 3 * f, cs2_out + 2 * f)) {
+            cs2_out[2 * f] = cs2_out[2 * f + 1] = 0.f;
+            if (bad < 0) bad = (int32_t)f;
+        }
+    }
+    if (first_bad_out) *first_bad_out = bad;
+    if (bad >= 0)
+        return fail(MPM_ERR_INVALID, "weave: face " + std::to_string(bad) + ": the direction is zero or within 1e-3 of the face's rest normal");
     return 0;
 }
 

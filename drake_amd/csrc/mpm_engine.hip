@@ -182,7 +182,10 @@ static void launch_fem_faces(mpm_engine* e, const DP& p, float dt) {
         else hipLaunchKernelGGL(k_fem_mat<0>, g, b, 0, e->stream, p, dt, t);
     } else if (e->fast_math) hipLaunchKernelGGL(k_fem<1>, g, b, 0, e->stream, p, dt);
     else hipLaunchKernelGGL(k_fem<0>, g, b, 0, e->stream, p, dt);
-    // (an engine with membrane damping, mpm_set_damping: the same faces again, adding to the records just written)
+    // (an engine with a weave, mpm_set_weave: the same faces again, adding to the records just written.  The order k_fem,
+    // k_weave, k_damp is part of the result: a record is the float sum in that order)
+    if (e->weave.on()) hipLaunchKernelGGL(k_weave, g, b, 0, e->stream, p, e->weave.args);
+    // (an engine with membrane damping, mpm_set_damping: the same faces once more)
     if (e->damp.membrane()) hipLaunchKernelGGL(k_damp, g, b, 0, e->stream, p, e->damp.args);
 }
 static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
@@ -761,7 +764,7 @@ int mpm_sync(mpm_handle_t e) try {
 } MPM_CATCH_ALL
 
 // partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
-// stiffness, no damping, no links, no pressure, no shell bending and no anchors (out of scope)
+// stiffness, no damping, no weave, no links, no pressure, no shell bending and no anchors (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
@@ -774,6 +777,8 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with bending stiffness (mpm_set_bending)");
     if (e->damp.any())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with damping (mpm_set_damping)");
+    if (e->weave.on())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with a weave (mpm_set_weave)");
     if (e->links.on())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with links (mpm_set_links)");
     if (e->pressure.on())
@@ -799,7 +804,8 @@ static int dt_above_limit(float dt, float max_dt, const char* feature, const cha
 // a dt above mpm_links_max_stable_dt on an engine with links: W dt^2 + 2 G dt <= 4 (mpm_links.h; a guard, not a guarantee).
 // And a dt above mpm_shell_max_stable_dt on an engine with shell bending (mpm_shell.h; a guard at the rest shape).  And a dt
 // above mpm_anchors_max_stable_dt on an engine with anchors (mpm_anchors.h; a guard of its own: a vertex with links and
-// anchors passes each on its own).
+// anchors passes each on its own).  And a dt above mpm_weave_max_stable_dt on an engine with a weave (mpm_weave.h; a
+// guard at the rest shape).
 static int fields_stable(const mpm_engine* e, float dt) {
     if (e->anchors.on() && !(dt <= e->anchors.max_dt))
         return dt_above_limit(dt, e->anchors.max_dt, "anchors", "anchor", "dt, the stiffness or the damping");
@@ -807,6 +813,7 @@ static int fields_stable(const mpm_engine* e, float dt) {
         return dt_above_limit(dt, e->shell.max_dt, "shell", "shell bending", "dt or the stiffness");
     if (e->links.on() && !(dt <= e->links.max_dt))
         return dt_above_limit(dt, e->links.max_dt, "links", "link", "dt, the stiffness or the damping");
+    if (e->weave.on() && !(dt <= e->weave.max_dt)) return dt_above_limit(dt, e->weave.max_dt, "weave", "weave", "dt or the moduli");
     if (e->damp.any() && !(dt <= e->damp.max_dt)) return dt_above_limit(dt, e->damp.max_dt, "damping", "damping", "dt or the coefficients");
     if (e->bend.on() && !(dt <= e->bend.max_dt)) return dt_above_limit(dt, e->bend.max_dt, "bending", "bending", "dt or the stiffness");
     if (e->force_fields.empty()) return 0;
@@ -817,9 +824,10 @@ static int fields_stable(const mpm_engine* e, float dt) {
 }
 // The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
 // takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness, damping,
-// links, pressure, shell bending or anchors are set.
+// the weave, links, pressure, shell bending or anchors are set.
 static float quiet_hint(const mpm_engine* e, float seconds) {
-    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->links.on() && !e->pressure.on() && !e->shell.on() &&
+    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->weave.on() && !e->links.on() && !e->pressure.on() &&
+                   !e->shell.on() &&
                    !e->anchors.on()
                ? seconds
                : 0.f;
@@ -2348,6 +2356,78 @@ int mpm_damping_face_records(size_t n_faces, const float* dminv3, const float* v
                              const float* beta, const float* x9, const float* v9, float* rec9_out) try {
     REQUIRE((dminv3 && vol && mu && lambda && beta && x9 && v9 && rec9_out) || n_faces == 0, "null array");
     return damping_face_records(n_faces, dminv3, vol, mu, lambda, beta, x9, v9, rec9_out);
+} MPM_CATCH_ALL
+
+// ---- woven cloth (mpm_cloth_host.h; mpm_weave.h) ---------------------------------------------------------------------------
+int mpm_set_weave(mpm_handle_t e, size_t n_cloths, const mpm_cloth_weave_t* w, const float* face_dirs) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "the weave is")) return rc;
+    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_weave: n_cloths must be mpm_cloth_count (or 0: off)");
+    REQUIRE(n_cloths == 0 || w, "null weave array");
+    for (size_t c = 0; c < n_cloths; ++c) {
+        float coef[4];
+        REQUIRE(weave_coefficients(w[c].E_warp, w[c].E_weft, w[c].nu, w[c].G, coef),
+                "weave: a constant is negative or not finite, D = 1 - nu^2 E_weft / E_warp <= 0, or E_warp = 0 with nu != 0");
+        REQUIRE(finite_n(w[c].warp_dir, 3), "weave: warp_dir is not finite");
+    }
+    if (face_dirs && n_cloths) REQUIRE(finite_n(face_dirs, (int)(3 * e->nf)), "weave: face_dirs is not finite");
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    return weave_apply(e, n_cloths ? std::vector<mpm_cloth_weave_t>(w, w + n_cloths) : std::vector<mpm_cloth_weave_t>(), face_dirs);
+} MPM_CATCH_ALL
+
+int mpm_get_weave(mpm_handle_t e, mpm_cloth_weave_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    std::vector<mpm_cloth_weave_t> w = e->weave.w;   // (one entry per cloth; zeros where nothing was set)
+    w.resize(e->cloths.size(), mpm_cloth_weave_t{0.f, 0.f, 0.f, 0.f, {0.f, 0.f, 0.f}});
+    return copy_out(w, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_weave_axes(mpm_handle_t e, float* cs_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE((e)->finalized, "call mpm_finalize first");
+    REQUIRE(cs_out || e->nf == 0, "null output");
+    if (e->weave.on()) std::copy(e->weave.axis.begin(), e->weave.axis.end(), cs_out);
+    else std::fill(cs_out, cs_out + 2 * e->nf, 0.f);
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_weave_forces(mpm_handle_t e, float* f_out, float* rec_out) try {
+    READY(e);
+    REQUIRE(f_out || e->nv == 0, "null output");
+    return weave_eval(e, f_out, rec_out, nullptr, nullptr, 0, nullptr, nullptr);
+} MPM_CATCH_ALL
+
+int mpm_weave_strain(mpm_handle_t e, float* out) try {
+    READY(e);
+    REQUIRE(out || e->nf == 0, "null output");
+    return weave_eval(e, nullptr, nullptr, out, nullptr, 0, nullptr, nullptr);
+} MPM_CATCH_ALL
+
+int mpm_weave_energy(mpm_handle_t e, double* per_cloth, size_t capacity, size_t* n_out, double* total) try {
+    READY(e);
+    REQUIRE(per_cloth || capacity == 0, "null output");
+    double none = 0.0;
+    return weave_eval(e, nullptr, nullptr, nullptr, per_cloth, capacity, n_out, total ? total : &none);
+} MPM_CATCH_ALL
+
+int mpm_weave_max_stable_dt(mpm_handle_t e, float* dt_out) try {
+    REQUIRE(e && dt_out, "null argument");
+    *dt_out = e->weave.on() ? e->weave.max_dt : INFINITY;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_weave_face_records(size_t n, const float* dminv3, const float* vol, const float* coef4, const float* cs2,
+                           const float* x9, float* rec9_out, float* strain3_out, float* energy_out) try {
+    REQUIRE((dminv3 && vol && coef4 && cs2 && x9) || n == 0, "null array");
+    return weave_face_records(n, dminv3, vol, coef4, cs2, x9, rec9_out, strain3_out, energy_out);
+} MPM_CATCH_ALL
+
+int mpm_weave_face_axes(size_t n, const float* rest_x9, const float* dir3, float* cs2_out, int32_t* first_bad_out) try {
+    REQUIRE((rest_x9 && dir3 && cs2_out) || n == 0, "null array");
+    REQUIRE(n < (size_t)1 << 31, "too many faces");
+    return weave_face_axes(n, rest_x9, dir3, cs2_out, first_bad_out);
 } MPM_CATCH_ALL
 
 // ---- links between cloth vertices (mpm_cloth_host.h; mpm_links.h) --------------------------------------------------------------

@@ -22,6 +22,7 @@
 #include "mpm_pins.h"
 #include "mpm_bending.h"
 #include "mpm_damping.h"
+#include "mpm_weave.h"
 #include "mpm_links.h"
 #include "mpm_pressure.h"
 #include "mpm_shell.h"
@@ -247,6 +248,15 @@ struct mpm_engine {
             return false;
         }
     } damp;
+    // woven cloth (mpm_set_weave; mpm_weave.h): k_weave behind k_fem and before k_damp for the cloths with a weave
+    struct Weave {
+        std::vector<mpm_cloth_weave_t> w;     // [cloth] as given; empty or all zero: off
+        std::vector<float> axis;              // [face][2] (c, s) by original face id, on the host (mpm_weave_axes)
+        WeaveArgs args{};                     // k_weave's tables (device memory, in `allocs`); coef == nullptr: off
+        const int2* d_ranges = nullptr;       // [cloth] (first face, end face) for k_weave_energy
+        float max_dt = INFINITY;              // 2 / sqrt(max_i (K_i / m_i)) (fields_stable)
+        bool on() const { return args.coef != nullptr; }
+    } weave;
     // links between cloth vertices (mpm_set_links; mpm_links.h): a non-empty table switches k_link on behind k_vforce
     struct Links {
         std::vector<mpm_link_t> set;     // the caller's table, as given
@@ -540,7 +550,7 @@ static bool is_rotation(const float* R) {
                        (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
     return std::fabs(det - 1.0) <= 1e-4;
 }
-// pins, grid bodies, force fields, bending stiffness, damping, links, pressure and shell bending are refused on a partitioned or multi-rank
+// pins, grid bodies, force fields, bending stiffness, damping, the weave, links, pressure and shell bending are refused on a partitioned or multi-rank
 // engine (out of scope);
 // what_is: "pins are", "bending stiffness is", ...
 static int single_engine_only(const mpm_engine* e, const char* what_is) {

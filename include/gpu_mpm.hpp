@@ -246,6 +246,52 @@ struct GpuMpmState {
         mpm_check(mpm_damping_face_records(n, dminv3, vol, mu, lambda, beta, x9, v9, rec.data()));
         return rec;
     }
+    // Extension: woven cloth (mpm_set_weave) -- orthotropic warp / weft / shear stiffness per cloth, added to the isotropic
+    // membrane; face_dirs: empty, or 3 floats per face (a zero entry falls back to the cloth's warp_dir).  All-zero moduli
+    // or an empty vector switches it off.  A synchronisation point, like SetBending.
+    void SetWeave(const std::vector<mpm_cloth_weave_t>& w, const std::vector<float>& face_dirs = {}) {
+        mpm_check(mpm_set_weave(h_, w.size(), w.data(), face_dirs.empty() ? nullptr : face_dirs.data()));
+    }
+    std::vector<mpm_cloth_weave_t> GetWeave() const {
+        size_t n = 0;
+        mpm_check(mpm_get_weave(h_, nullptr, 0, &n));
+        std::vector<mpm_cloth_weave_t> out(n);
+        mpm_check(mpm_get_weave(h_, out.data(), n, &n));
+        return out;
+    }
+    // (c, s) of the warp per face in the face's rest frame, 2 floats per face in the numbering of DumpCpuState
+    std::vector<float> WeaveAxes(size_t n_faces) const {
+        std::vector<float> cs(2 * n_faces);
+        mpm_check(mpm_weave_axes(h_, cs.data()));
+        return cs;
+    }
+    // the weave's force on the current positions, 3 floats per vertex; records: null, or 9 floats per face
+    std::vector<float> WeaveForces(size_t n_verts, std::vector<float>* records = nullptr, size_t n_faces = 0) const {
+        std::vector<float> f(3 * n_verts);
+        if (records) records->assign(9 * n_faces, 0.f);
+        mpm_check(mpm_weave_forces(h_, f.data(), records ? records->data() : nullptr));
+        return f;
+    }
+    // Eaa, Ebb, Eab per face
+    std::vector<float> WeaveStrain(size_t n_faces) const {
+        std::vector<float> out(3 * n_faces);
+        mpm_check(mpm_weave_strain(h_, out.data()));
+        return out;
+    }
+    // the weave's elastic energy per cloth; total: null, or the sum of the rows
+    std::vector<double> WeaveEnergy(double* total = nullptr) const {
+        size_t n = 0;
+        mpm_check(mpm_weave_energy(h_, nullptr, 0, &n, nullptr));
+        std::vector<double> out(n);
+        mpm_check(mpm_weave_energy(h_, out.data(), n, &n, total));
+        return out;
+    }
+    // the dt above which the substep entry points refuse an engine with a weave (+inf while it is off)
+    float WeaveMaxStableDt() const {
+        float dt = 0.f;
+        mpm_check(mpm_weave_max_stable_dt(h_, &dt));
+        return dt;
+    }
     // Extension: links between cloth vertices (mpm_set_links) -- seams, springs, tension-only cords; an empty vector
     // clears them.  A synchronisation point, like SetBending.
     void SetLinks(const std::vector<mpm_link_t>& links) { mpm_check(mpm_set_links(h_, links.size(), links.data())); }

@@ -864,6 +864,83 @@ MPM_API int mpm_damping_face_records(size_t n_faces, const float *dminv3, const 
                                      const float *lambda, const float *beta, const float *x9, const float *v9,
                                      float *rec9_out);
 
+/* ---- Woven cloth: orthotropic warp / weft / shear stiffness per cloth (an extension) ----
+ * The membrane of the face kernel is isotropic: one E, one nu per cloth.  Woven fabric has warp and weft moduli that
+ * differ by factors, and a shear modulus orders of magnitude below both.  The weave is an ADDED orthotropic St. Venant-
+ * Kirchhoff energy on the in-plane Green strain, resolved along per-face material axes; the isotropic model stays as
+ * the fabric's matrix (lower the cloth's E and let the weave carry the yarn directions).
+ * Per face with corners 0, 1, 2, rest Dm^-1 = [Dm0 Dm1; 0 Dm3] and rest volume vol (area x thickness): the rest frame
+ * is e1 along the rest edge 0 -> 1, e2 the in-plane perpendicular towards corner 2; the warp is the unit vector
+ * a = (c, s) in that frame, the weft b = (-s, c), and
+ *   F2  = [x1 - x0, x2 - x0] Dm^-1,  E = 1/2 (F2^T F2 - I),  Eaa = a^T E a,  Ebb = b^T E b,  Eab = a^T E b
+ *   Psi = 1/2 ka Eaa^2 + 1/2 kb Ebb^2 + kab Eaa Ebb + 2 G Eab^2                           (per rest volume)
+ *   Saa = ka Eaa + kab Ebb,  Sbb = kb Ebb + kab Eaa,  Sab = 2 G Eab,  S = Saa a a^T + Sbb b b^T + Sab (a b^T + b a^T)
+ *   P = F2 S,  corner records G_rec = vol P grad_N,  vertex force -sum G_rec.
+ * Stateless, rotation invariant, with an energy; total force and torque vanish.  The constants per cloth are in Pa like
+ * the cloth's E: E_warp, E_weft >= 0, G >= 0, nu the weft contraction per unit warp extension.  With
+ * D = 1 - nu^2 E_weft / E_warp:  ka = E_warp / D, kb = E_weft / D, kab = nu E_weft / D, formed in double and rounded once
+ * to float.  D must be > 0; E_warp = 0 requires nu = 0 (then ka = kab = 0, kb = E_weft).  A cloth whose four constants
+ * are zero has no weave: its faces write nothing.
+ * Axes: warp_dir is a rest-space direction per cloth; face_dirs (NULL, or 3 floats per face in the face numbering of
+ * mpm_dump_cpu_state) gives a direction per face, for panels cut on the bias; a face whose entry is (0, 0, 0) falls
+ * back to its cloth's warp_dir.  Once, at the call, on the host in double from the rest positions: the direction is
+ * projected onto the face's rest plane and normalised, and (c, s), its components on (e1, e2), are rounded to float.
+ * The kernel does not renormalise.  A projection shorter than 1e-3 |d| (a yarn that stands on the face), or a zero d,
+ * on a face of a cloth WITH weave is refused with MPM_ERR_INVALID; the message names the face.
+ * The force joins the vertex forces of CalcFemStateAndForce (MPM_ARR_FORCES includes it): its kernel runs directly
+ * behind the face kernel and BEFORE the membrane damping kernel, and adds its records to the elastic ones (it counts
+ * under MPM_PHASE_FEM).  It works with pins, per-cloth materials, grid bodies, force fields, bending, damping, links,
+ * pressure, shell bending, anchors, fast math, deterministic mode and the coupled path.
+ * mpm_set_weave needs mpm_finalize, is ordered on the engine's stream and is a synchronisation point; substeps that
+ * mpm_run_substeps still owes are run first, with the old table.  n_cloths must be mpm_cloth_count, or 0.  All-zero
+ * constants or n_cloths = 0 switches the feature off: the engine then launches exactly what it launches without this
+ * call.  While it is on the engine does not use the re-sort's quiet-time estimate to omit re-sort check launches.
+ * Stability: the entry points that check mpm_bending_max_stable_dt also return MPM_ERR_INVALID, before anything is
+ * enqueued, for a dt above
+ *   mpm_weave_max_stable_dt = 2 / sqrt( max_i (1 / m_i) sum_{faces f around i} vol_f kmax_f |g_i| (|g_0| + |g_1| + |g_2|) ),
+ * g_j the columns of the face's grad_N, m_i the vertex particle's mass as of the call, kmax the larger of 2G and the
+ * larger eigenvalue of [[ka, kab], [kab, kb]]: Gershgorin's bound at the REST shape.  It is a guard, not a guarantee
+ * (a stretched cloth is stiffer: F2 enters twice, and the geometric stiffness F2 -> F2 S is not in it), and how
+ * conservative it is has not been measured.  +inf while the feature is off.
+ * Refused with MPM_ERR_INVALID, nothing changed: a constant that is negative or not finite; D <= 0; E_warp = 0 with
+ * nu != 0; a wrong count; a call before mpm_finalize; a perpendicular or zero direction (above); any partitioned or
+ * multi-rank engine -- this call on such an engine, and mpm_dist_init, the halo, chain, team and world substeps on an
+ * engine with the weave on. */
+typedef struct mpm_cloth_weave {
+    float E_warp, E_weft, nu, G;   /* Pa, Pa, -, Pa */
+    float warp_dir[3];             /* rest-space direction of the warp; its length does not matter */
+} mpm_cloth_weave_t;
+MPM_API int mpm_set_weave(mpm_handle_t h, size_t n_cloths, const mpm_cloth_weave_t *w, const float *face_dirs);
+/* The constants in force: min(mpm_cloth_count, capacity) entries into out (zeros while off), the cloth count into *n_out. */
+MPM_API int mpm_get_weave(mpm_handle_t h, mpm_cloth_weave_t *out, size_t capacity, size_t *n_out);
+/* The axis table in force: cs_out[2 * n_faces] = (c, s) per face in the face numbering of mpm_dump_cpu_state; (0, 0)
+ * on the faces of a cloth without weave and everywhere while the feature is off. */
+MPM_API int mpm_weave_axes(mpm_handle_t h, float *cs_out);
+/* The weave's force on the current positions: f_out[3 * n_verts], in the vertex numbering of mpm_dump_cpu_state (zeros
+ * for the vertices of cloths without weave); rec_out (NULL, or [9 * n_faces]): every face's corner records G_rec
+ * ([corner][component]; the force on a corner is -G_rec).  The device function of the substep's kernel; a vertex's
+ * records are summed on the host in ascending face id, as the vertex-force kernel sums them.  Changes no state. */
+MPM_API int mpm_weave_forces(mpm_handle_t h, float *f_out, float *rec_out);
+/* out[3 * n_faces] = Eaa, Ebb, Eab per face, the floats the kernel forms (zeros on a cloth without weave). */
+MPM_API int mpm_weave_strain(mpm_handle_t h, float *out);
+/* Sum over the cloth's faces of the float vol Psi the kernel's face function forms, added in double in face order in a
+ * fixed tree, without atomics: the same bits whatever the particle order and the determinism mode.  min(cloth count,
+ * capacity) entries into per_cloth, the cloth count into *n_out, the sum of the rows in cloth order into *total (each
+ * may be NULL).  Zeros while the feature is off. */
+MPM_API int mpm_weave_energy(mpm_handle_t h, double *per_cloth, size_t capacity, size_t *n_out, double *total);
+MPM_API int mpm_weave_max_stable_dt(mpm_handle_t h, float *dt_out);
+/* The kernel's face function on the host (no handle, no device), face by face: dminv3[3 n] = (Dm0, Dm1, Dm3) of
+ * Dm^-1 = [Dm0 Dm1; 0 Dm3], vol[n], coef4[4 n] = (ka, kb, kab, 2G), cs2[2 n] = (c, s), x9[9 n] the corners' positions
+ * ([corner][component]); rec9_out[9 n] the corner records, strain3_out[3 n] = Eaa, Ebb, Eab, energy_out[n] = vol Psi
+ * (each output may be NULL). */
+MPM_API int mpm_weave_face_records(size_t n, const float *dminv3, const float *vol, const float *coef4, const float *cs2,
+                                   const float *x9, float *rec9_out, float *strain3_out, float *energy_out);
+/* The axis function of mpm_set_weave on the host (no handle, no device): rest_x9[9 n] the faces' rest corners, dir3[3 n]
+ * a direction per face; cs2_out[2 n] = (c, s).  A face whose direction is zero, not finite or within the 1e-3 cone of
+ * its normal gets (0, 0); *first_bad_out (may be NULL) is the first such face, or -1, and the call returns
+ * MPM_ERR_INVALID if there is one. */
+MPM_API int mpm_weave_face_axes(size_t n, const float *rest_x9, const float *dir3, float *cs2_out, int32_t *first_bad_out);
+
 /* ---- Links between cloth vertices: seams, springs and tension-only cords (an extension) ----
  * Every mpm_add_qr_cloth* call makes an island; pins are hard constraints to rigid bodies only.  A link joins two
  * distinct cloth vertices a, b -- of one cloth or of two -- by a damped spring: panels sewn into a garment, a sheet laced
@@ -1191,6 +1268,8 @@ MPM_API int mpm_shell_hinge(const float x12[12], float kc, float psibar, float r
  *   The potentials of force fields (mpm_set_force_fields) are NOT reported: most of them (drag, wind) have none.
  *   The elastic energy of the links (mpm_set_links) is NOT in this record either, whose layout is unchanged: links join
  *   cloths, so it belongs to no row; mpm_link_energy reports it.
+ *   The energy of the weave (mpm_set_weave) is NOT in this record either, whose layout is unchanged: elastic_in_plane is
+ *   the isotropic membrane's alone; mpm_weave_energy reports the weave's, per cloth.
  * gravity_potential is -sum m g x[gravity_axis] with g = mpm_material_t::gravity (signed) -- zero at the world origin.
  * The sums are formed in ORIGINAL id order in a fixed tree, without floating-point atomics: a row is the same bits
  * whatever the particle order (slot order, arrival order inside a cell, deterministic mode on or off). */
