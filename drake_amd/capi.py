@@ -392,6 +392,32 @@ def weave_face_axes(rest_x, dirs):
     return cs, int(bad.value)
 
 
+TEAR_DTYPE = np.dtype([("stretch_limit", "<f4"), ("reserved", "<f4", (3,))])
+assert TEAR_DTYPE.itemsize == 16
+
+
+def tear_limit_squared(stretch_limit):
+    """L of mpm_set_tearing: (float)(limit^2), formed in double from the float limit and rounded once (0 stays 0)"""
+    lim = np.asarray(stretch_limit, np.float32).astype(np.float64)
+    return (lim * lim).astype(np.float32)
+
+
+def tear_face(dminv3, x, L):
+    """mpm_tear_face: the tear kernel's face function on the host.  dminv3 (n, 3) = (Dm0, Dm1, Dm3), x (n, 3, 3) corner
+    positions, L (n,) or a scalar, the squared limit as a float; returns (mq (n, 2) float32 = (m, q), fails (n,) bool: the
+    larger eigenvalue m + sqrt(q) of F2^T F2 exceeds L).  Needs no engine and no GPU."""
+    lib = load_library()
+    x = np.ascontiguousarray(x, np.float32).reshape(-1, 3, 3)
+    n = len(x)
+    dm = np.ascontiguousarray(dminv3, np.float32).reshape(n, 3)
+    L = np.ascontiguousarray(np.broadcast_to(np.asarray(L, np.float32), (n,)))
+    mq, fails = np.zeros((n, 2), np.float32), np.zeros(n, np.uint8)
+    rc = lib.mpm_tear_face(n, dm.ctypes.data, x.ctypes.data, L.ctypes.data, mq.ctypes.data, fails.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return mq, fails.astype(bool)
+
+
 def grid_collider_preset(mpm_bc: int, sdf_friction: float = 0.3):
     """The collider table that reproduces the reference's scene mpm_bc (cuda_mpm_kernels.cuh:673-774)."""
     lib = load_library()
@@ -552,6 +578,7 @@ SYMBOLS = [
     "mpm_set_damping", "mpm_get_damping", "mpm_damping_forces", "mpm_damping_max_stable_dt", "mpm_damping_face_records",
     "mpm_set_weave", "mpm_get_weave", "mpm_weave_axes", "mpm_weave_forces", "mpm_weave_strain", "mpm_weave_energy",
     "mpm_weave_max_stable_dt", "mpm_weave_face_records", "mpm_weave_face_axes",
+    "mpm_set_tearing", "mpm_get_tearing", "mpm_set_torn_faces", "mpm_tear_state", "mpm_tear_measure", "mpm_tear_face",
     "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
     "mpm_set_anchors", "mpm_get_anchors", "mpm_anchor_forces", "mpm_anchor_state", "mpm_anchors_max_stable_dt",
     "mpm_anchor_point",
@@ -726,6 +753,12 @@ def load_library(build: bool = True):
         "mpm_weave_max_stable_dt": [vp, P(f)],
         "mpm_weave_face_records": [sz, vp, vp, vp, vp, vp, vp, vp, vp],
         "mpm_weave_face_axes": [sz, vp, vp, vp, P(C.c_int32)],
+        "mpm_set_tearing": [vp, sz, vp],
+        "mpm_get_tearing": [vp, vp, sz, P(sz)],
+        "mpm_set_torn_faces": [vp, vp],
+        "mpm_tear_state": [vp, vp, vp, sz, P(sz)],
+        "mpm_tear_measure": [vp, vp, vp],
+        "mpm_tear_face": [sz, vp, vp, vp, vp, vp],
         "mpm_measure": [vp, vp, sz, P(sz), vp],
         "mpm_face_strain": [vp, vp],
         "mpm_cloth_energy_density": [vp, sz, vp, vp],
@@ -1107,6 +1140,53 @@ class GpuMpm:
     @staticmethod
     def weave_face_records(dminv3, vol, coef4, cs2, x):
         return weave_face_records(dminv3, vol, coef4, cs2, x)
+
+    def set_tearing(self, limits):
+        """mpm_set_tearing: one stretch limit per cloth, in cloth order (0: the cloth never tears; else finite and > 1:
+        a face whose largest in-plane stretch exceeds it fails for good).  A TEAR_DTYPE array is taken as it is.  All
+        zeros switch the limits off.  A synchronisation point."""
+        if isinstance(limits, np.ndarray) and limits.dtype == TEAR_DTYPE:
+            t = np.ascontiguousarray(limits).reshape(-1)
+        else:
+            t = np.zeros(len(limits), TEAR_DTYPE)
+            t["stretch_limit"] = np.asarray(limits, np.float32).reshape(-1)
+        self._ck(self.lib.mpm_set_tearing(self.h, len(t), t.ctypes.data if len(t) else None))
+
+    def get_tearing(self):
+        """mpm_get_tearing: the stretch limits in force, (n_cloths,) float32 (zeros while off)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_tearing(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, TEAR_DTYPE)
+        self._ck(self.lib.mpm_get_tearing(self.h, out.ctypes.data if out.size else None, len(out), C.byref(n)))
+        return out["stretch_limit"].copy()
+
+    def set_torn_faces(self, torn):
+        """mpm_set_torn_faces: scissors / restore -- (n_faces,) flags in original face order replace every flag (non-zero:
+        torn).  Allowed while every limit is 0."""
+        t = np.ascontiguousarray(np.asarray(torn) != 0, np.uint8).reshape(-1)
+        if len(t) != getattr(self, "n_faces", len(t)):      # (before finalize the library refuses the call itself)
+            raise ValueError("torn must have one entry per face")
+        self._ck(self.lib.mpm_set_torn_faces(self.h, _ptr(t) if len(t) else None))
+
+    def tear_state(self):
+        """mpm_tear_state: (flags (n_faces,) bool in original face order, torn faces per cloth (n_cloths,) uint32)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_tear_state(self.h, None, None, 0, C.byref(n)))
+        torn, count = np.zeros(self.n_faces, np.uint8), np.zeros(n.value, np.uint32)
+        self._ck(self.lib.mpm_tear_state(self.h, _ptr(torn) if torn.size else None, count.ctypes.data if count.size else None,
+                                         len(count), C.byref(n)))
+        return torn.astype(bool), count
+
+    def tear_measure(self):
+        """mpm_tear_measure: ((m, q) per face (n_faces, 2) float32, would-fail verdicts (n_faces,) bool) of the substep's
+        face function on the current positions; changes no state."""
+        mq, fails = np.zeros((self.n_faces, 2), np.float32), np.zeros(self.n_faces, np.uint8)
+        self._ck(self.lib.mpm_tear_measure(self.h, _ptr(mq) if mq.size else None, _ptr(fails) if fails.size else None))
+        return mq, fails.astype(bool)
+
+    @staticmethod
+    def tear_face(dminv3, x, L):
+        return tear_face(dminv3, x, L)
 
     def set_links(self, table):
         """mpm_set_links: the links between cloth vertices -- seams (rest_length 0), springs and tension-only cords --, an

@@ -1,5 +1,5 @@
 // Host side of the per-cloth features: cloth materials, external force fields, row tables, bending stiffness, links,
-// pressure, shell bending, damping, the weave and the per-cloth report -- what the entry points in mpm_engine.hip call once their
+// pressure, shell bending, damping, the weave, tearing and the per-cloth report -- what the entry points in mpm_engine.hip call once their
 // arguments are checked.
 // Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
 #pragma once
@@ -857,6 +857,180 @@ static int weave_face_axes(size_t n, const float* rest_x9, const float* dir3, fl
     return 0;
 }
 
+// ---- tearing cloth (mpm_set_tearing, mpm_get_tearing, mpm_set_torn_faces, mpm_tear_state, mpm_tear_measure,
+// mpm_tear_face; mpm_tear.h) ----
+// the torn faces of every cloth, counted on the device (zeros while the tables do not exist)
+static int tear_counts(mpm_engine* e, std::vector<uint32_t>& n) {
+    const size_t nc = e->cloths.size();
+    n.assign(nc, 0u);
+    if (!e->tear.on() || nc == 0) return 0;
+    hipLaunchKernelGGL(k_tear_count, dim3((unsigned)nc), dim3(256), 0, e->stream, (const uint8_t*)e->tear.args.torn, e->tear.d_ranges,
+                       e->tear.d_count);
+    HIP_TRY(hipGetLastError());
+    D2H(e, n.data(), e->tear.d_count, nc * sizeof(uint32_t));
+    return 0;
+}
+// the feature of cloth c that does not compose with tearing (hinges across a torn face, a hole in a pressurised cloth:
+// out of scope), or null
+static const char* tear_conflict(const mpm_engine* e, size_t c) {
+    if (c < e->bend.k.size() && e->bend.k[c] > 0.f) return "bending stiffness (mpm_set_bending)";
+    if (c < e->shell.set.size() && e->shell.set[c].stiffness > 0.f) return "shell bending (mpm_set_shell_bending)";
+    if (c < e->pressure.set.size() && e->pressure.set[c].mode != MPM_PRESSURE_OFF) return "pressure (mpm_set_pressure)";
+    return nullptr;
+}
+// mpm_set_bending, mpm_set_shell_bending, mpm_set_pressure: refused for a cloth c with wants(c) that has a tear limit or
+// a torn face
+template <class Wants>
+static int tear_refuses(mpm_engine* e, size_t n_cloths, const char* call, Wants wants) {
+    if (!e->tear.on()) return 0;
+    bool any = false;
+    for (size_t c = 0; c < n_cloths; ++c) any = any || wants(c);
+    if (!any) return 0;
+    if (int rc = settle(e)) return rc;   // (the substeps still owed may tear)
+    std::vector<uint32_t> n;
+    if (int rc = tear_counts(e, n)) return rc;
+    for (size_t c = 0; c < n_cloths && c < n.size(); ++c)
+        if (wants(c) && (e->tear.limit(c) || n[c] != 0u))
+            return fail(MPM_ERR_INVALID, std::string(call) + ": cloth " + std::to_string(c) +
+                                             " has a tear limit or a torn face (mpm_set_tearing, mpm_set_torn_faces): hinges "
+                                             "and pressure across torn faces are not available");
+    return 0;
+}
+// Puts the limits `t` (checked; one per cloth, or none) in force, and the flags `torn` if given (n_faces bytes by
+// original id; null: the flags stay as they are).  The tables exist while some cloth has a limit or some face is
+// flagged; otherwise they are freed and the engine launches what it launched before.  The caller has settled the owed
+// substeps.  A failure changes nothing.
+static int tear_apply(mpm_engine* e, std::vector<mpm_cloth_tear_t> t, const uint8_t* torn) {
+    const size_t nc = e->cloths.size(), nf = e->nf;
+    std::vector<float> lim(std::max<size_t>(nc, 1), 0.f), L(std::max<size_t>(nc, 1), 0.f);
+    for (size_t c = 0; c < nc && c < t.size(); ++c) lim[c] = t[c].stretch_limit;
+    std::vector<size_t> first(nc), count(nc);
+    for (size_t c = 0; c < nc; ++c) {
+        first[c] = e->cloths[c].first_face;
+        count[c] = e->cloths[c].n_faces;
+    }
+    std::vector<int> cloth_of_face(std::max<size_t>(nf, 1), 0), ranges(2 * std::max<size_t>(nc, 1), 0);
+    if (!tear_tables(nc, first.data(), count.data(), lim.data(), nf, L.data(), cloth_of_face.data(), ranges.data()))
+        return fail(MPM_ERR_INVALID, "tearing: a stretch_limit is neither 0 nor a finite number > 1");
+    bool any = false;
+    for (size_t c = 0; c < nc; ++c) any = any || L[c] > 0.f;
+    std::vector<uint8_t> flags;
+    if (torn) {
+        flags.resize(nf);
+        for (size_t f = 0; f < nf; ++f) {
+            flags[f] = torn[f] != 0 ? 1 : 0;
+            any = any || flags[f] != 0;
+        }
+    } else if (!any) {
+        std::vector<uint32_t> n;
+        if (int rc = tear_counts(e, n)) return rc;
+        for (uint32_t k : n) any = any || k != 0u;
+    }
+    // (a synchronisation point: the kernels enqueued so far have read the old tables)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (!any || nf == 0 || nc == 0) {
+        mpm_engine::Tear& o = e->tear;
+        float* o_L = const_cast<float*>(o.args.L);
+        int* o_cloth = const_cast<int*>(o.args.cloth_of_face);
+        int2* o_ranges = const_cast<int2*>(o.d_ranges);
+        e->dfree(o_L);
+        e->dfree(o_cloth);
+        e->dfree(o.args.torn);
+        e->dfree(o_ranges);
+        e->dfree(o.d_count);
+        o = mpm_engine::Tear{};
+        o.t.swap(t);
+        return 0;
+    }
+    if (!e->tear.on()) {
+        mpm_engine::Tear next;
+        FreshArrays fresh(e);
+        float* d_L = nullptr;
+        int* d_cloth = nullptr;
+        uint8_t* d_torn = nullptr;
+        int2* d_ranges = nullptr;
+        if (int rc = fresh.alloc(&d_L, nc, false)) return rc;
+        if (int rc = fresh.alloc(&d_cloth, nf, false)) return rc;
+        if (int rc = fresh.alloc(&d_torn, nf, true)) return rc;
+        if (int rc = fresh.alloc(&d_ranges, nc, false)) return rc;
+        if (int rc = fresh.alloc(&next.d_count, nc, true)) return rc;
+        H2D(e, d_cloth, cloth_of_face.data(), nf * sizeof(int));
+        H2D(e, d_ranges, ranges.data(), nc * sizeof(int2));
+        H2D(e, d_L, L.data(), nc * sizeof(float));
+        if (torn) H2D(e, d_torn, flags.data(), nf);
+        next.args = TearArgs{d_L, d_cloth, d_torn};
+        next.d_ranges = d_ranges;
+        next.t.swap(t);
+        e->tear = next;
+        fresh.commit();
+        return 0;
+    }
+    H2D(e, const_cast<float*>(e->tear.args.L), L.data(), nc * sizeof(float));
+    if (torn) H2D(e, e->tear.args.torn, flags.data(), nf);
+    e->tear.t.swap(t);
+    return 0;
+}
+// mpm_set_tearing: the limits are checked by the entry point
+static int set_tearing(mpm_engine* e, size_t n_cloths, const mpm_cloth_tear_t* t) {
+    for (size_t c = 0; c < n_cloths; ++c)
+        if (t[c].stretch_limit > 0.f)
+            if (const char* other = tear_conflict(e, c))
+                return fail(MPM_ERR_INVALID, "mpm_set_tearing: cloth " + std::to_string(c) + " has " + other + ", which tearing does not compose with");
+    // substeps that mpm_run_substeps deferred are owed with the limits they were enqueued with
+    if (int rc = settle(e)) return rc;
+    return tear_apply(e, std::vector<mpm_cloth_tear_t>(t, t + n_cloths), nullptr);
+}
+// mpm_set_torn_faces: scissors / restore
+static int set_torn_faces(mpm_engine* e, const uint8_t* torn) {
+    for (size_t c = 0; c < e->cloths.size(); ++c) {
+        const mpm_engine::Cloth& cl = e->cloths[c];
+        bool cut = false;
+        for (size_t f = cl.first_face; f < cl.first_face + cl.n_faces; ++f) cut = cut || torn[f] != 0;
+        if (cut)
+            if (const char* other = tear_conflict(e, c))
+                return fail(MPM_ERR_INVALID, "mpm_set_torn_faces: cloth " + std::to_string(c) + " has " + other + ", which tearing does not compose with");
+    }
+    if (int rc = settle(e)) return rc;
+    return tear_apply(e, e->tear.t, torn);
+}
+// mpm_tear_state: the flags and the count per cloth (k_tear_count)
+static int tear_state(mpm_engine* e, uint8_t* torn_out, uint32_t* count_per_cloth, size_t capacity, size_t* n_out) {
+    std::vector<uint32_t> n;
+    if (int rc = tear_counts(e, n)) return rc;
+    if (count_per_cloth) std::copy(n.begin(), n.begin() + (long)std::min(capacity, n.size()), count_per_cloth);
+    if (n_out) *n_out = n.size();
+    if (torn_out && e->nf) {
+        if (e->tear.on()) D2H(e, torn_out, e->tear.args.torn, e->nf);
+        else std::memset(torn_out, 0, e->nf);
+    }
+    return 0;
+}
+// mpm_tear_measure: one launch of k_tear_eval on the current state, by original face id
+static int tear_measure(mpm_engine* e, float* mq_out, uint8_t* would_fail_out) {
+    const size_t nf = e->nf;
+    if (nf == 0) return 0;
+    if (int rc = e->stage(9 * nf)) return rc;
+    HIP_TRY(hipMemsetAsync(e->d_stage, 0, 9 * nf, e->stream));
+    float* d_mq = (float*)e->d_stage;
+    uint8_t* d_fail = (uint8_t*)e->d_stage + 8 * nf;
+    hipLaunchKernelGGL(k_tear_eval, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, e->stream, e->dp, e->tear.args, d_mq, d_fail);
+    HIP_TRY(hipGetLastError());
+    if (mq_out) D2H(e, mq_out, d_mq, 8 * nf);
+    if (would_fail_out) D2H(e, would_fail_out, d_fail, nf);
+    return 0;
+}
+// host code only: the device function of the kernels, compiled for the host
+static int tear_faces(size_t n, const float* dminv3, const float* x9, const float* L, float* mq_out, uint8_t* fails_out) {
+    for (size_t f = 0; f < n; ++f) {
+        float x[3][3], mq[2];
+        std::memcpy(x, x9 + 9 * f, sizeof x);
+        const bool fails = tear_face(dminv3[3 * f], dminv3[3 * f + 1], dminv3[3 * f + 2], L[f], x, mq);
+        if (mq_out) std::memcpy(mq_out + 2 * f, mq, sizeof mq);
+        if (fails_out) fails_out[f] = fails ? 1 : 0;
+    }
+    return 0;
+}
+
 // ---- the per-cloth report (mpm_measure, mpm_face_strain, mpm_cloth_energy_density; mpm_measure.h) ----
 // The chunk table: every cloth's faces, then every cloth's vertices, in runs of at most MEASURE_CHUNK original ids that
 // never straddle a cloth.  Built once; the vertex chunks' rows of the bending table follow mpm_set_bending.
@@ -922,6 +1096,7 @@ static MeasureArgs measure_args(const mpm_engine* e) {
     a.rows = ms.d_rows;
     a.mats = e->multi_mat ? e->d_cloth_mat : nullptr;
     a.bend = e->bend.args;
+    a.torn = e->tear.args.torn;
     return a;
 }
 

@@ -187,6 +187,8 @@ static void launch_fem_faces(mpm_engine* e, const DP& p, float dt) {
     if (e->weave.on()) hipLaunchKernelGGL(k_weave, g, b, 0, e->stream, p, e->weave.args);
     // (an engine with membrane damping, mpm_set_damping: the same faces once more)
     if (e->damp.membrane()) hipLaunchKernelGGL(k_damp, g, b, 0, e->stream, p, e->damp.args);
+    // (an engine with a tear limit or a torn face, mpm_set_tearing / mpm_set_torn_faces: last, it owns a torn face's records)
+    if (e->tear.on()) hipLaunchKernelGGL(k_tear, g, b, 0, e->stream, p, e->tear.args);
 }
 static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
     TraceRange tr("mpm:CalcFemStateAndForce (vertex forces)");
@@ -764,7 +766,7 @@ int mpm_sync(mpm_handle_t e) try {
 } MPM_CATCH_ALL
 
 // partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
-// stiffness, no damping, no weave, no links, no pressure, no shell bending and no anchors (out of scope)
+// stiffness, no damping, no weave, no tearing, no links, no pressure, no shell bending and no anchors (out of scope)
 static int extensions_refused(const mpm_engine* e, const char* what) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
@@ -779,6 +781,8 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with damping (mpm_set_damping)");
     if (e->weave.on())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with a weave (mpm_set_weave)");
+    if (e->tear.on())
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with tearing (mpm_set_tearing, mpm_set_torn_faces)");
     if (e->links.on())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with links (mpm_set_links)");
     if (e->pressure.on())
@@ -824,9 +828,9 @@ static int fields_stable(const mpm_engine* e, float dt) {
 }
 // The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
 // takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness, damping,
-// the weave, links, pressure, shell bending or anchors are set.
+// the weave, tearing, links, pressure, shell bending or anchors are set.
 static float quiet_hint(const mpm_engine* e, float seconds) {
-    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->weave.on() && !e->links.on() && !e->pressure.on() &&
+    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->weave.on() && !e->tear.on() && !e->links.on() && !e->pressure.on() &&
                    !e->shell.on() &&
                    !e->anchors.on()
                ? seconds
@@ -2295,6 +2299,7 @@ int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try
     if (int rc = single_engine_only(e, "bending stiffness is")) return rc;
     REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_bending: n_cloths must be mpm_cloth_count (or 0: off)");
     REQUIRE(n_cloths == 0 || stiffness, "null stiffness array");
+    if (int rc = tear_refuses(e, n_cloths, "mpm_set_bending", [&](size_t c) { return stiffness[c] > 0.f; })) return rc;
     return set_bending(e, n_cloths, stiffness);
 } MPM_CATCH_ALL
 
@@ -2430,6 +2435,51 @@ int mpm_weave_face_axes(size_t n, const float* rest_x9, const float* dir3, float
     return weave_face_axes(n, rest_x9, dir3, cs2_out, first_bad_out);
 } MPM_CATCH_ALL
 
+// ---- tearing cloth (mpm_cloth_host.h; mpm_tear.h) ------------------------------------------------------------------------------
+int mpm_set_tearing(mpm_handle_t e, size_t n_cloths, const mpm_cloth_tear_t* t) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "tearing is")) return rc;
+    REQUIRE(n_cloths == e->cloths.size(), "mpm_set_tearing: n_cloths must be mpm_cloth_count");
+    REQUIRE(n_cloths == 0 || t, "null tearing array");
+    for (size_t c = 0; c < n_cloths; ++c) {
+        float L;
+        REQUIRE(tear_limit(t[c].stretch_limit, &L), "tearing: a stretch_limit is neither 0 nor a finite number > 1");
+    }
+    return set_tearing(e, n_cloths, t);
+} MPM_CATCH_ALL
+
+int mpm_get_tearing(mpm_handle_t e, mpm_cloth_tear_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    std::vector<mpm_cloth_tear_t> t = e->tear.t;   // (one entry per cloth; zeros where nothing was set)
+    t.resize(e->cloths.size(), mpm_cloth_tear_t{0.f, {0.f, 0.f, 0.f}});
+    return copy_out(t, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_set_torn_faces(mpm_handle_t e, const uint8_t* torn) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "tearing is")) return rc;
+    REQUIRE(torn || e->nf == 0, "null flag array");
+    return set_torn_faces(e, torn);
+} MPM_CATCH_ALL
+
+int mpm_tear_state(mpm_handle_t e, uint8_t* torn_out, uint32_t* count_per_cloth, size_t capacity, size_t* n_out) try {
+    READY(e);
+    REQUIRE(count_per_cloth || capacity == 0, "null output");
+    return tear_state(e, torn_out, count_per_cloth, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_tear_measure(mpm_handle_t e, float* mq_out, uint8_t* would_fail_out) try {
+    READY(e);
+    if (int rc = single_engine_only(e, "mpm_tear_measure is")) return rc;
+    return tear_measure(e, mq_out, would_fail_out);
+} MPM_CATCH_ALL
+
+int mpm_tear_face(size_t n, const float* dminv3, const float* x9, const float* L, float* mq_out, uint8_t* fails_out) try {
+    REQUIRE((dminv3 && x9 && L) || n == 0, "null array");
+    return tear_faces(n, dminv3, x9, L, mq_out, fails_out);
+} MPM_CATCH_ALL
+
 // ---- links between cloth vertices (mpm_cloth_host.h; mpm_links.h) --------------------------------------------------------------
 int mpm_set_links(mpm_handle_t e, size_t n, const mpm_link_t* links) try {
     READY_NO_SETTLE(e);
@@ -2475,6 +2525,7 @@ int mpm_set_pressure(mpm_handle_t e, size_t n_cloths, const mpm_cloth_pressure_t
     if (int rc = single_engine_only(e, "pressure is")) return rc;
     REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_pressure: n_cloths must be mpm_cloth_count (or 0: off)");
     REQUIRE(n_cloths == 0 || per_cloth, "null pressure array");
+    if (int rc = tear_refuses(e, n_cloths, "mpm_set_pressure", [&](size_t c) { return per_cloth[c].mode != MPM_PRESSURE_OFF; })) return rc;
     return set_pressure(e, n_cloths, per_cloth);
 } MPM_CATCH_ALL
 
@@ -2524,6 +2575,7 @@ int mpm_set_shell_bending(mpm_handle_t e, size_t n_cloths, const mpm_cloth_shell
     if (int rc = single_engine_only(e, "shell bending is")) return rc;
     REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_shell_bending: n_cloths must be mpm_cloth_count (or 0: off)");
     REQUIRE(n_cloths == 0 || per_cloth, "null shell bending array");
+    if (int rc = tear_refuses(e, n_cloths, "mpm_set_shell_bending", [&](size_t c) { return per_cloth[c].stiffness > 0.f; })) return rc;
     return set_shell_bending(e, n_cloths, per_cloth, rest_pos);
 } MPM_CATCH_ALL
 

@@ -23,6 +23,7 @@
 #include "mpm_bending.h"
 #include "mpm_damping.h"
 #include "mpm_weave.h"
+#include "mpm_tear.h"
 #include "mpm_links.h"
 #include "mpm_pressure.h"
 #include "mpm_shell.h"
@@ -257,6 +258,15 @@ struct mpm_engine {
         float max_dt = INFINITY;              // 2 / sqrt(max_i (K_i / m_i)) (fields_stable)
         bool on() const { return args.coef != nullptr; }
     } weave;
+    // tearing cloth (mpm_set_tearing, mpm_set_torn_faces; mpm_tear.h): k_tear last in the face chain while the tables exist
+    struct Tear {
+        std::vector<mpm_cloth_tear_t> t;      // [cloth] as given; empty or all zero: no cloth has a limit
+        TearArgs args{};                      // k_tear's tables (device memory, in `allocs`); torn == nullptr: off
+        const int2* d_ranges = nullptr;       // [cloth] (first face, end face) for k_tear_count
+        uint32_t* d_count = nullptr;          // [cloth] k_tear_count's output
+        bool on() const { return args.torn != nullptr; }
+        bool limit(size_t c) const { return c < t.size() && t[c].stretch_limit > 0.f; }
+    } tear;
     // links between cloth vertices (mpm_set_links; mpm_links.h): a non-empty table switches k_link on behind k_vforce
     struct Links {
         std::vector<mpm_link_t> set;     // the caller's table, as given
@@ -550,7 +560,7 @@ static bool is_rotation(const float* R) {
                        (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
     return std::fabs(det - 1.0) <= 1e-4;
 }
-// pins, grid bodies, force fields, bending stiffness, damping, the weave, links, pressure and shell bending are refused on a partitioned or multi-rank
+// pins, grid bodies, force fields, bending stiffness, damping, the weave, tearing, links, pressure and shell bending are refused on a partitioned or multi-rank
 // engine (out of scope);
 // what_is: "pins are", "bending stiffness is", ...
 static int single_engine_only(const mpm_engine* e, const char* what_is) {

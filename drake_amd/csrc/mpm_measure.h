@@ -20,6 +20,10 @@
 // ascending order.  No floating-point atomic anywhere: which slot a particle sits in, in which order its cell received
 // it, deterministic mode on or off -- none of it reaches the arithmetic, and the rows are the same bits.
 //
+// On an engine with the flag table of mpm_tear.h a torn face contributes nothing to the three strain energies and is
+// left out of the stretch extremes (mpm_face_strain: its s1, s2, r22 are reported, its V psi is 0); its mass, momenta,
+// kinetic energies and its count stay.  Without the table nothing changes.
+//
 // A partitioned engine counts the particles the rank OWNS (q[0].w > 0) and skips ids without a slot; a face whose
 // corner is not on the rank is skipped too (an owned face always has its corners: the vertex band is wider).
 #pragma once
@@ -89,6 +93,7 @@ struct MeasureArgs {
     mpm_cloth_measure_t* rows;    // [chunk] partial sums
     const ClothMat* mats;         // [cloth] of a multi-material engine, else null (DP::M holds for every cloth)
     BendArgs bend;                // the table in force (n_rows = 0: off)
+    const uint8_t* torn;          // [original face id] the flags of mpm_tear.h, or null (no table: nothing below reads it)
 };
 
 // the partial sums of one lane, and of one workgroup
@@ -208,6 +213,9 @@ MPM_DEV bool measure_face(const DP& p, const PSet& S, int cur, const MeasureArgs
     e[3] *= V;
     e[4] *= V;
     e[5] *= V;
+    // a torn face (mpm_tear.h) stores no strain energy and is left out of the extremes; its mass and momenta stay
+    const bool torn = a.torn && a.torn[id] != 0;
+    if (torn) e[3] = e[4] = e[5] = 0.0;
     if (acc) {
         const float4 va = S.q[1][sa], vb = S.q[1][sb], vc = S.q[1][sc];
         const float4 q2 = S.q[2][s], q3 = S.q[3][s];
@@ -218,13 +226,14 @@ MPM_DEV bool measure_face(const DP& p, const PSet& S, int cur, const MeasureArgs
         const double v[3] = {((double)va.x + (double)vb.x + (double)vc.x) / 3.0, ((double)va.y + (double)vb.y + (double)vc.y) / 3.0,
                              ((double)va.z + (double)vb.z + (double)vc.z) / 3.0};
         measure_particle(p, *acc, (double)mf, x, v, C);
+        acc->faces += 1u;
+        if (torn) return true;
         acc->s[16] += e[3];
         acc->s[17] += e[4];
         acc->s[18] += e[5];
         acc->stretch_max = fmaxf(acc->stretch_max, (float)e[0]);
         acc->stretch_min = fminf(acc->stretch_min, (float)e[1]);
         acc->normal_min = fminf(acc->normal_min, (float)e[2]);
-        acc->faces += 1u;
     }
     return true;
 }

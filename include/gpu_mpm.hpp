@@ -292,6 +292,45 @@ struct GpuMpmState {
         mpm_check(mpm_weave_max_stable_dt(h_, &dt));
         return dt;
     }
+    // Extension: tearing cloth (mpm_set_tearing) -- one stretch limit per cloth (0: never tears; else finite and > 1); a
+    // face whose largest in-plane stretch exceeds it fails for good and exerts no force from then on.  A synchronisation
+    // point, like SetBending.
+    void SetTearing(const std::vector<float>& stretch_limits) {
+        std::vector<mpm_cloth_tear_t> t(stretch_limits.size(), mpm_cloth_tear_t{0.f, {0.f, 0.f, 0.f}});
+        for (size_t c = 0; c < t.size(); ++c) t[c].stretch_limit = stretch_limits[c];
+        mpm_check(mpm_set_tearing(h_, t.size(), t.data()));
+    }
+    std::vector<float> GetTearing() const {
+        size_t n = 0;
+        mpm_check(mpm_get_tearing(h_, nullptr, 0, &n));
+        std::vector<mpm_cloth_tear_t> t(n);
+        mpm_check(mpm_get_tearing(h_, t.data(), n, &n));
+        std::vector<float> out(n);
+        for (size_t c = 0; c < n; ++c) out[c] = t[c].stretch_limit;
+        return out;
+    }
+    // scissors / restore: one byte per face in the numbering of DumpCpuState, non-zero = torn; replaces every flag
+    void SetTornFaces(const std::vector<uint8_t>& torn) {
+        if (torn.size() != n_faces()) throw std::invalid_argument("SetTornFaces: one byte per face");
+        mpm_check(mpm_set_torn_faces(h_, torn.data()));
+    }
+    // the flags per face; counts: null, or the torn faces per cloth
+    std::vector<uint8_t> TearState(size_t n_faces, std::vector<uint32_t>* counts = nullptr) const {
+        size_t n = 0;
+        mpm_check(mpm_tear_state(h_, nullptr, nullptr, 0, &n));
+        std::vector<uint8_t> torn(n_faces);
+        std::vector<uint32_t> c(n);
+        mpm_check(mpm_tear_state(h_, torn.data(), c.data(), n, &n));
+        if (counts) counts->swap(c);
+        return torn;
+    }
+    // (m, q) per face on the current positions, 2 floats per face; would_fail: null, or the verdict per face
+    std::vector<float> TearMeasure(size_t n_faces, std::vector<uint8_t>* would_fail = nullptr) const {
+        std::vector<float> mq(2 * n_faces);
+        if (would_fail) would_fail->assign(n_faces, 0);
+        mpm_check(mpm_tear_measure(h_, mq.data(), would_fail ? would_fail->data() : nullptr));
+        return mq;
+    }
     // Extension: links between cloth vertices (mpm_set_links) -- seams, springs, tension-only cords; an empty vector
     // clears them.  A synchronisation point, like SetBending.
     void SetLinks(const std::vector<mpm_link_t>& links) { mpm_check(mpm_set_links(h_, links.size(), links.data())); }

@@ -941,6 +941,66 @@ MPM_API int mpm_weave_face_records(size_t n, const float *dminv3, const float *v
  * MPM_ERR_INVALID if there is one. */
 MPM_API int mpm_weave_face_axes(size_t n, const float *rest_x9, const float *dir3, float *cs2_out, int32_t *first_bad_out);
 
+/* ---- Tearing cloth: faces fail beyond a stretch limit, per cloth (an extension) ----
+ * Every other cloth feature is elastic or viscous; this one lets the cloth open.  Per cloth one number, stretch_limit:
+ * 0 (the cloth never tears) or a finite value > 1, the largest principal in-plane stretch a face survives.  Per face
+ * with rest Dm^-1 = [Dm0 Dm1; 0 Dm3] and the corner positions the face kernel has just used:
+ *   F2 = [x1 - x0, x2 - x0] Dm^-1,  C = F2^T F2,  m = 1/2 (C00 + C11),  q = (1/2 (C00 - C11))^2 + C01^2,
+ *   lambda1 = m + sqrt(q) (the square of the largest stretch);  the face FAILS when lambda1 > L = (float)(limit^2),
+ * L formed in double and rounded once, the comparison evaluated without the square root: h = L - m,
+ * fails = (h < 0) || (q > h h).  Host and device run one function and agree to the bit on m, q and the verdict.
+ * State: one byte per face, all zero when the feature is first switched on.  It is monotone: a substep only ever sets
+ * it (a face that failed stays failed when the load goes away, and when mpm_set_tearing changes or removes the
+ * limits); mpm_set_torn_faces alone clears it.
+ * A torn face, from the substep in which it fails: its corner records and its normal-column stress factor are
+ * overwritten with zeros at the end of the face pass, so it exerts no membrane force, no weave force
+ * (mpm_set_weave), no membrane damping force (mpm_set_damping) and no stress in ParticleToGrid.  Its face particle
+ * KEEPS its mass, its centroid position and velocity and the update of its deformation gradient: it still carries
+ * momentum through the grid and meets colliders.  Decisions within a substep are made face by face on the positions of
+ * the substep's start (Jacobi); the result does not depend on the particle order or on deterministic mode; a substep
+ * that skips itself marks nothing.
+ * It works with per-cloth materials, the weave, membrane damping, links, anchors, pins, force fields, grid bodies,
+ * contact, fast math, deterministic mode and every substep path.  It does NOT compose with hinges or pressure: a
+ * cloth with a tear limit or a torn face may not have bending stiffness > 0 (mpm_set_bending), shell bending
+ * stiffness > 0 (mpm_set_shell_bending) or a pressure mode other than off (mpm_set_pressure) -- whichever call comes
+ * second returns MPM_ERR_INVALID and names the other; a cloth without limit and without torn faces in the same
+ * engine keeps them all.  (Hinges across a torn face are left to a later extension.)
+ * mpm_weave_forces, mpm_weave_energy and mpm_damping_forces keep reporting what those features alone would give on
+ * every face, torn or not.  mpm_measure and mpm_face_strain: a torn face adds nothing to the three strain energies and
+ * is left out of the stretch extremes (mpm_face_strain reports its s1, s2, r22 and 0 for its energy); its mass, momenta
+ * and kinetic energies stay.
+ * mpm_set_tearing needs mpm_finalize, is ordered on the engine's stream and is a synchronisation point; substeps that
+ * mpm_run_substeps still owes are run first, with the old limits.  n_cloths must be mpm_cloth_count.  A table of zeros
+ * switches the limits off; if no face is torn either, the tables are freed and the engine launches exactly what it
+ * launches without this call.  While the tables exist the engine does not use the re-sort's quiet-time estimate.
+ * Refused with MPM_ERR_INVALID, nothing changed: a limit that is not 0 and not a finite number > 1 (NaN included); a
+ * wrong count; a call before mpm_finalize; the combinations above; any partitioned or multi-rank engine -- these calls
+ * on such an engine, and mpm_dist_init, the halo, chain, team and world substeps on an engine whose tables exist.
+ * The cost of the substep's kernel on a GPU has not been measured. */
+typedef struct mpm_cloth_tear {
+    float stretch_limit;   /* 0: never tears; else finite and > 1 */
+    float reserved[3];     /* not read */
+} mpm_cloth_tear_t;
+MPM_API int mpm_set_tearing(mpm_handle_t h, size_t n_cloths, const mpm_cloth_tear_t *t);
+/* The limits in force: min(mpm_cloth_count, capacity) entries into out (zeros while off), the cloth count into *n_out. */
+MPM_API int mpm_get_tearing(mpm_handle_t h, mpm_cloth_tear_t *out, size_t capacity, size_t *n_out);
+/* Scissors and restore: torn[n_faces], one byte per face in the face numbering of mpm_dump_cpu_state; non-zero marks
+ * the face torn, zero restores it.  Replaces every flag.  Allowed while every limit is 0 (a pre-cut cloth that does
+ * not tear further); an all-zero array with all limits 0 frees the tables.  A synchronisation point like
+ * mpm_set_tearing. */
+MPM_API int mpm_set_torn_faces(mpm_handle_t h, const uint8_t *torn);
+/* The flags (torn_out[n_faces], may be NULL) and the number of torn faces per cloth, counted on the device in face
+ * order: min(cloth count, capacity) entries into count_per_cloth, the cloth count into *n_out.  Zeros while off. */
+MPM_API int mpm_tear_state(mpm_handle_t h, uint8_t *torn_out, uint32_t *count_per_cloth, size_t capacity, size_t *n_out);
+/* The substep's face function on the current positions, state untouched: mq_out[2 * n_faces] = (m, q) per face,
+ * would_fail_out[n_faces] = the verdict against the face's cloth's limit (0 on a cloth without limit); either may be
+ * NULL.  Torn faces are evaluated like the others. */
+MPM_API int mpm_tear_measure(mpm_handle_t h, float *mq_out, uint8_t *would_fail_out);
+/* The kernel's face function on the host (no handle, no device), face by face: dminv3[3 n] = (Dm0, Dm1, Dm3), x9[9 n]
+ * the corners' positions ([corner][component]), L[n] the squared limit as a float; mq_out[2 n] = (m, q),
+ * fails_out[n] = (h < 0) || (q > h h) as it stands (the caller decides what L = 0 means); either output may be NULL. */
+MPM_API int mpm_tear_face(size_t n, const float *dminv3, const float *x9, const float *L, float *mq_out, uint8_t *fails_out);
+
 /* ---- Links between cloth vertices: seams, springs and tension-only cords (an extension) ----
  * Every mpm_add_qr_cloth* call makes an island; pins are hard constraints to rigid bodies only.  A link joins two
  * distinct cloth vertices a, b -- of one cloth or of two -- by a damped spring: panels sewn into a garment, a sheet laced
