@@ -392,6 +392,29 @@ def weave_face_axes(rest_x, dirs):
     return cs, int(bad.value)
 
 
+def link_break_squared(break_length):
+    """B2 of mpm_set_link_limits: (float)(break_length^2), formed in double from the float limit and rounded once (0
+    stays 0: the link never breaks)"""
+    b = np.asarray(break_length, np.float32).astype(np.float64)
+    return (b * b).astype(np.float32)
+
+
+def link_breaks(xa, xb, B2):
+    """mpm_link_breaks: the break kernel's link function on the host.  xa, xb (n, 3) the ends' positions, B2 (n,) or a
+    scalar, the squared limit as a float; returns (l2 (n,) float32 -- mpm_link_force's l2 of d = xb - xa --, breaks (n,)
+    bool: l2 > B2 as it stands, the caller decides what B2 = 0 means).  Needs no engine and no GPU."""
+    lib = load_library()
+    xa = np.ascontiguousarray(xa, np.float32).reshape(-1, 3)
+    n = len(xa)
+    xb = np.ascontiguousarray(xb, np.float32).reshape(n, 3)
+    B2 = np.ascontiguousarray(np.broadcast_to(np.asarray(B2, np.float32), (n,)))
+    l2, breaks = np.zeros(n, np.float32), np.zeros(n, np.uint8)
+    rc = lib.mpm_link_breaks(n, xa.ctypes.data, xb.ctypes.data, B2.ctypes.data, l2.ctypes.data, breaks.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return l2, breaks.astype(bool)
+
+
 TEAR_DTYPE = np.dtype([("stretch_limit", "<f4"), ("reserved", "<f4", (3,))])
 assert TEAR_DTYPE.itemsize == 16
 
@@ -580,6 +603,8 @@ SYMBOLS = [
     "mpm_weave_max_stable_dt", "mpm_weave_face_records", "mpm_weave_face_axes",
     "mpm_set_tearing", "mpm_get_tearing", "mpm_set_torn_faces", "mpm_tear_state", "mpm_tear_measure", "mpm_tear_face",
     "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
+    "mpm_set_link_limits", "mpm_get_link_limits", "mpm_set_broken_links", "mpm_link_break_state", "mpm_link_break_measure",
+    "mpm_link_breaks",
     "mpm_set_anchors", "mpm_get_anchors", "mpm_anchor_forces", "mpm_anchor_state", "mpm_anchors_max_stable_dt",
     "mpm_anchor_point",
     "mpm_set_pressure", "mpm_get_pressure", "mpm_pressure_forces", "mpm_pressure_state", "mpm_mesh_is_closed",
@@ -719,6 +744,12 @@ def load_library(build: bool = True):
         "mpm_link_energy": [vp, P(C.c_double), vp],
         "mpm_links_max_stable_dt": [vp, P(f)],
         "mpm_link_force": [vp, vp, vp, vp, vp, vp],
+        "mpm_set_link_limits": [vp, sz, vp],
+        "mpm_get_link_limits": [vp, vp, sz, P(sz)],
+        "mpm_set_broken_links": [vp, sz, vp],
+        "mpm_link_break_state": [vp, vp, P(C.c_uint32)],
+        "mpm_link_break_measure": [vp, vp, vp],
+        "mpm_link_breaks": [sz, vp, vp, vp, vp, vp],
         "mpm_set_anchors": [vp, sz, vp],
         "mpm_get_anchors": [vp, vp, sz, P(sz)],
         "mpm_anchor_forces": [vp, vp],
@@ -1228,6 +1259,50 @@ class GpuMpm:
     @staticmethod
     def link_force(link, xa, xb, va, vb):
         return link_force(link, xa, xb, va, vb)
+
+    def _n_links(self) -> int:
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_links(self.h, None, 0, C.byref(n)))
+        return int(n.value)
+
+    def set_link_limits(self, break_length=None):
+        """mpm_set_link_limits: one break_length per link, in link order (0: the link never breaks; else finite and >
+        rest_length: a link whose length exceeds it breaks for good and acts no more); None or an empty array switches
+        every limit off.  A synchronisation point."""
+        b = np.zeros(0, np.float32) if break_length is None else np.ascontiguousarray(break_length, np.float32).reshape(-1)
+        self._ck(self.lib.mpm_set_link_limits(self.h, b.size, b.ctypes.data if b.size else None))
+
+    def get_link_limits(self):
+        """mpm_get_link_limits: the break lengths in force, (n_links,) float32 (zeros while off)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_get_link_limits(self.h, None, 0, C.byref(n)))
+        out = np.zeros(int(n.value), np.float32)
+        self._ck(self.lib.mpm_get_link_limits(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
+        return out
+
+    def set_broken_links(self, broken):
+        """mpm_set_broken_links: scissors / restore -- (n_links,) flags in link order replace every flag (non-zero:
+        broken; zero: the link acts again).  Allowed while every limit is 0."""
+        t = np.ascontiguousarray(np.asarray(broken) != 0, np.uint8).reshape(-1)
+        self._ck(self.lib.mpm_set_broken_links(self.h, t.size, _ptr(t) if t.size else None))
+
+    def link_break_state(self):
+        """mpm_link_break_state: (flags (n_links,) bool in link order, the number of broken links, counted on the device)."""
+        broken, count = np.zeros(self._n_links(), np.uint8), C.c_uint32()
+        self._ck(self.lib.mpm_link_break_state(self.h, _ptr(broken) if broken.size else None, C.byref(count)))
+        return broken.astype(bool), int(count.value)
+
+    def link_break_measure(self):
+        """mpm_link_break_measure: (l2 per link (n_links,) float32, would-break verdicts (n_links,) bool) of the substep's
+        link function on the current positions; changes no state."""
+        n = self._n_links()
+        l2, breaks = np.zeros(n, np.float32), np.zeros(n, np.uint8)
+        self._ck(self.lib.mpm_link_break_measure(self.h, _ptr(l2) if n else None, _ptr(breaks) if n else None))
+        return l2, breaks.astype(bool)
+
+    @staticmethod
+    def link_breaks(xa, xb, B2):
+        return link_breaks(xa, xb, B2)
 
     def set_pressure(self, table):
         """mpm_set_pressure: the enclosed-volume pressure of every cloth, an array of PRESSURE_DTYPE in cloth order

@@ -1,5 +1,5 @@
 // Host side of the per-cloth features: cloth materials, external force fields, row tables, bending stiffness, links,
-// pressure, shell bending, damping, the weave, tearing and the per-cloth report -- what the entry points in mpm_engine.hip call once their
+// pressure, shell bending, damping, the weave, tearing, breakable links and the per-cloth report -- what the entry points in mpm_engine.hip call once their
 // arguments are checked.
 // Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
 #pragma once
@@ -243,6 +243,7 @@ static int bending_forces(mpm_engine* e, float* f_out) { return rows_eval(e, k_b
 // mpm_links_max_stable_dt; mpm_links.h) ----
 // The table `t` with its limit and the caller's links put in force: new device arrays, upload, swap.  The caller has
 // settled the owed substeps.  A failure changes nothing: the new buffers go, the table in force stays.
+static void link_break_free(mpm_engine* e);
 static int links_swap(mpm_engine* e, LinkTable& t, float max_dt, size_t n, const mpm_link_t* links) {
     static_assert(sizeof(LinkPair) == sizeof(float4), "link record layouts differ");
     mpm_engine::Links next;
@@ -257,6 +258,7 @@ static int links_swap(mpm_engine* e, LinkTable& t, float max_dt, size_t n, const
     rows_free(e, e->links.args);
     float4* o_pair = const_cast<float4*>(e->links.d_pair);
     e->dfree(o_pair);
+    link_break_free(e);   // (the limits and flags go with the table they belonged to: `next` has none)
     next.set.assign(links, links + n);
     next.max_dt = max_dt;
     e->links = next;
@@ -298,13 +300,153 @@ static int link_energy(mpm_engine* e, double* energy_out, float* length_out) {
         double* d_term = (double*)e->d_stage;
         float* d_len = (float*)(d_term + n);
         hipLaunchKernelGGL(k_link_energy, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, e->stream, e->dp, e->links.d_pair, (int)n,
-                           d_term, d_len);
+                           (const uint8_t*)e->links.brk.broken, d_term, d_len);
         std::vector<double> term(n);
         D2H(e, term.data(), d_term, n * 8);
         if (length_out) D2H(e, length_out, d_len, n * 4);
         for (size_t i = 0; i < n; ++i) sum += term[i];
     }
     *energy_out = sum;
+    return 0;
+}
+
+// ---- breakable links (mpm_set_link_limits, mpm_get_link_limits, mpm_set_broken_links, mpm_link_break_state,
+// mpm_link_break_measure, mpm_link_breaks; mpm_links.h) ----
+// the breaking tables released (the limits as given stay with the caller)
+static void link_break_free(mpm_engine* e) {
+    mpm_engine::Links& o = e->links;
+    float* o_B2 = const_cast<float*>(o.brk.B2);
+    unsigned* o_entry = const_cast<unsigned*>(o.brk.entry);
+    int2* o_range = const_cast<int2*>(o.d_range);
+    e->dfree(o_B2);
+    e->dfree(o_entry);
+    e->dfree(o.brk.broken);
+    e->dfree(o_range);
+    e->dfree(o.d_count);
+    o.brk = LinkBreakArgs{};
+    o.d_range = nullptr;
+    o.d_count = nullptr;
+}
+// the broken links, counted on the device in link order (k_tear_count on the single range (0, n)); 0 while the tables
+// do not exist
+static int link_break_count(mpm_engine* e, uint32_t* n_out) {
+    *n_out = 0u;
+    if (!e->links.breaking()) return 0;
+    hipLaunchKernelGGL(k_tear_count, dim3(1), dim3(256), 0, e->stream, (const uint8_t*)e->links.brk.broken, e->links.d_range,
+                       e->links.d_count);
+    HIP_TRY(hipGetLastError());
+    D2H(e, n_out, e->links.d_count, sizeof(uint32_t));
+    return 0;
+}
+// Puts the limits `limits` (checked; one per link, or none: all off) in force, and the flags `broken` if given (one byte
+// per link; null: the flags stay as they are).  The tables exist while some limit is > 0 or some flag is set; otherwise
+// they are freed and the engine launches what it launched before.  With flags given, LinkArgs::ent of the table in force
+// is rebuilt from the caller's links with the flagged links' entries replaced by their rows' padding, and uploaded: that
+// is scissors and restore alike.  The caller has settled the owed substeps.  A failure changes nothing.
+static int link_break_apply(mpm_engine* e, std::vector<float> limits, const uint8_t* broken) {
+    mpm_engine::Links& o = e->links;
+    const size_t n = o.set.size();
+    const Link* L = reinterpret_cast<const Link*>(o.set.data());
+    std::vector<float> B2(std::max<size_t>(n, 1), 0.f);
+    if (!limits.empty()) {
+        const std::string refusal = link_limits(limits.data(), L, n, B2.data());
+        if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    }
+    bool any = false;
+    for (size_t i = 0; i < n; ++i) any = any || B2[i] > 0.f;
+    std::vector<uint8_t> flags;
+    if (broken) {
+        flags.resize(n);
+        for (size_t i = 0; i < n; ++i) {
+            flags[i] = broken[i] != 0 ? 1 : 0;
+            any = any || flags[i] != 0;
+        }
+    } else if (!any) {
+        uint32_t k;
+        if (int rc = link_break_count(e, &k)) return rc;
+        any = k != 0u;
+    }
+    // the table on the host again, where its entries' places or its records are needed
+    LinkTable t;
+    const bool create = any && n != 0 && !o.breaking();
+    if (n != 0 && (create || (broken && o.breaking()))) {
+        std::string why;
+        if (!link_table(L, n, e->nf, e->nv, LINK_SLICE, t, why)) return fail(MPM_ERR_INVALID, why);
+        for (size_t i = 0; broken && i < n; ++i)
+            if (flags[i]) {
+                t.ent[t.entry_of_link[2 * i]] = LinkRecord{t.pair[i].a, 0.f, 0.f, 0.f};
+                t.ent[t.entry_of_link[2 * i + 1]] = LinkRecord{t.pair[i].b & ~LINK_FLAG_BIT, 0.f, 0.f, 0.f};
+            }
+    }
+    // (a synchronisation point: the kernels enqueued so far have read the old tables)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (create) {
+        FreshArrays fresh(e);
+        float* d_B2 = nullptr;
+        unsigned* d_entry = nullptr;
+        uint8_t* d_broken = nullptr;
+        int2* d_range = nullptr;
+        uint32_t* d_count = nullptr;
+        if (int rc = fresh.alloc(&d_B2, n, false)) return rc;
+        if (int rc = fresh.alloc(&d_entry, 2 * n, false)) return rc;
+        if (int rc = fresh.alloc(&d_broken, n, true)) return rc;
+        if (int rc = fresh.alloc(&d_range, 1, false)) return rc;
+        if (int rc = fresh.alloc(&d_count, 1, true)) return rc;
+        const int2 range = make_int2(0, (int)n);
+        H2D(e, d_entry, t.entry_of_link.data(), 2 * n * sizeof(unsigned));
+        H2D(e, d_range, &range, sizeof(range));
+        o.brk = LinkBreakArgs{o.d_pair, d_B2, d_entry, d_broken, const_cast<float4*>(o.args.ent), (int)n};
+        o.d_range = d_range;
+        o.d_count = d_count;
+        fresh.commit();
+    }
+    if (o.breaking()) {
+        if (broken) {
+            H2D(e, o.brk.ent, t.ent.data(), t.ent.size() * sizeof(LinkRecord));
+            H2D(e, o.brk.broken, flags.data(), n);
+        }
+        if (any) H2D(e, const_cast<float*>(o.brk.B2), B2.data(), n * sizeof(float));
+        else link_break_free(e);
+    }
+    o.limits.swap(limits);
+    return 0;
+}
+// mpm_link_break_state: the flags and their count
+static int link_break_state(mpm_engine* e, uint8_t* broken_out, uint32_t* count_out) {
+    uint32_t k;
+    if (int rc = link_break_count(e, &k)) return rc;
+    if (count_out) *count_out = k;
+    const size_t n = e->links.set.size();
+    if (broken_out && n) {
+        if (e->links.breaking()) D2H(e, broken_out, e->links.brk.broken, n);
+        else std::memset(broken_out, 0, n);
+    }
+    return 0;
+}
+// mpm_link_break_measure: one launch of k_link_break_eval on the current state, in link order
+static int link_break_measure(mpm_engine* e, float* l2_out, uint8_t* would_break_out) {
+    const size_t n = e->links.set.size();
+    if (n == 0) return 0;
+    if (int rc = e->stage(5 * n)) return rc;
+    float* d_l2 = (float*)e->d_stage;
+    uint8_t* d_br = (uint8_t*)e->d_stage + 4 * n;
+    hipLaunchKernelGGL(k_link_break_eval, dim3(((unsigned)n + 255u) / 256u), dim3(256), 0, e->stream, e->dp, e->links.d_pair,
+                       e->links.brk.B2, (int)n, d_l2, d_br);
+    HIP_TRY(hipGetLastError());
+    if (l2_out) D2H(e, l2_out, d_l2, 4 * n);
+    if (would_break_out) D2H(e, would_break_out, d_br, n);
+    return 0;
+}
+// host code only: the device function of the kernels, compiled for the host
+static int link_breaks_host(size_t n, const float* xa3, const float* xb3, const float* B2, float* l2_out, uint8_t* breaks_out) {
+    for (size_t i = 0; i < n; ++i) {
+        const float *xa = xa3 + 3 * i, *xb = xb3 + 3 * i;
+        const float d[3] = {xb[0] - xa[0], xb[1] - xa[1], xb[2] - xa[2]};
+        float l2;
+        const bool breaks = link_breaks(d, B2[i], &l2);
+        if (l2_out) l2_out[i] = l2;
+        if (breaks_out) breaks_out[i] = breaks ? 1 : 0;
+    }
     return 0;
 }
 

@@ -204,7 +204,11 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
     if (e->bend.on() && e->damp.bending())
         hipLaunchKernelGGL(k_bend_damp, rows_grid(e->bend.args.n_rows), dim3(256), 0, e->stream, p, e->bend.args,
                            (const float*)e->damp.d_beta_vertex);
-    // (an engine with links, mpm_set_links: f += the seams', springs' and cords' forces, one lane per linked vertex)
+    // (an engine with links, mpm_set_links: f += the seams', springs' and cords' forces, one lane per linked vertex; while
+    // some link has a break limit or is broken, mpm_set_link_limits / mpm_set_broken_links, k_link_break first: one lane
+    // per link, it owns a broken link's two records)
+    if (e->links.on() && e->links.breaking())
+        hipLaunchKernelGGL(k_link_break, rows_grid(e->links.brk.n), dim3(256), 0, e->stream, p, e->links.brk);
     if (e->links.on()) hipLaunchKernelGGL(k_link, rows_grid(e->links.args.n_rows), dim3(256), 0, e->stream, p, e->links.args);
     // (an engine with pressure, mpm_set_pressure: where a cloth is in gas mode, the gas cloths' volumes and gauge pressures
     // from the current positions, on the device; then f += the pressure force, one lane per vertex of a pressurised cloth)
@@ -2517,6 +2521,53 @@ int mpm_link_force(const mpm_link_t* link, const float* xa, const float* xb, con
     const float d[3] = {xb[0] - xa[0], xb[1] - xa[1], xb[2] - xa[2]}, w[3] = {vb[0] - va[0], vb[1] - va[1], vb[2] - va[2]};
     link_force(link->stiffness, link->rest_length, link->damping, (link->flags & MPM_LINK_TENSION_ONLY) != 0u, d, w, f_on_a);
     return 0;
+} MPM_CATCH_ALL
+
+// ---- breakable links (mpm_cloth_host.h; mpm_links.h) ----------------------------------------------------------------------------
+int mpm_set_link_limits(mpm_handle_t e, size_t n, const float* break_length) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "link limits are")) return rc;
+    REQUIRE(n == 0 || n == e->links.set.size(), "mpm_set_link_limits: n must be the link count or 0");
+    REQUIRE(n == 0 || break_length, "null limit array");
+    std::vector<float> limits(break_length, break_length + n), B2(std::max<size_t>(n, 1));
+    const std::string refusal = link_limits(limits.data(), reinterpret_cast<const Link*>(e->links.set.data()), n, B2.data());
+    if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    // substeps that mpm_run_substeps deferred are owed with the limits they were enqueued with
+    if (int rc = settle(e)) return rc;
+    return link_break_apply(e, limits, nullptr);
+} MPM_CATCH_ALL
+
+int mpm_get_link_limits(mpm_handle_t e, float* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(out || capacity == 0, "null output");
+    std::vector<float> b = e->links.limits;   // (one entry per link; zeros while off)
+    b.resize(e->links.set.size(), 0.f);
+    return copy_out(b, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_set_broken_links(mpm_handle_t e, size_t n, const uint8_t* broken) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "breakable links are")) return rc;
+    REQUIRE(n == e->links.set.size(), "mpm_set_broken_links: n must be the link count");
+    REQUIRE(n == 0 || broken, "null flag array");
+    if (int rc = settle(e)) return rc;
+    return link_break_apply(e, e->links.limits, broken);
+} MPM_CATCH_ALL
+
+int mpm_link_break_state(mpm_handle_t e, uint8_t* broken_out, uint32_t* count_out) try {
+    READY(e);
+    return link_break_state(e, broken_out, count_out);
+} MPM_CATCH_ALL
+
+int mpm_link_break_measure(mpm_handle_t e, float* l2_out, uint8_t* would_break_out) try {
+    READY(e);
+    if (int rc = single_engine_only(e, "mpm_link_break_measure is")) return rc;
+    return link_break_measure(e, l2_out, would_break_out);
+} MPM_CATCH_ALL
+
+int mpm_link_breaks(size_t n, const float* xa3, const float* xb3, const float* B2, float* l2_out, uint8_t* breaks_out) try {
+    REQUIRE((xa3 && xb3 && B2) || n == 0, "null array");
+    return link_breaks_host(n, xa3, xb3, B2, l2_out, breaks_out);
 } MPM_CATCH_ALL
 
 // ---- enclosed-volume pressure per cloth (mpm_cloth_host.h; mpm_pressure.h) ------------------------------------------------------

@@ -273,7 +273,14 @@ struct mpm_engine {
         LinkArgs args{};                 // ... as k_link reads it (device memory, in `allocs`)
         const float4* d_pair = nullptr;  // [link] k_link_energy's records
         float max_dt = INFINITY;         // the positive root of W dt^2 + 2 G dt = 4 (fields_stable)
+        // breakable links (mpm_set_link_limits, mpm_set_broken_links): the tables exist while some link has a limit or some
+        // flag is set, and k_link_break then runs in front of k_link; they go with the table they belonged to
+        std::vector<float> limits;       // [link] break_length as given; empty: all off
+        LinkBreakArgs brk{};             // k_link_break's tables (device memory, in `allocs`); B2 == nullptr: none
+        const int2* d_range = nullptr;   // the single range (0, n) for k_tear_count
+        uint32_t* d_count = nullptr;     // ... and its output
         bool on() const { return args.n_rows > 0; }
+        bool breaking() const { return brk.B2 != nullptr; }
     } links;
     // enclosed-volume pressure per cloth (mpm_set_pressure; mpm_pressure.h): a table with a pressurised cloth switches
     // k_pressure on behind k_link, and a cloth in gas mode k_pressure_volume and k_pressure_gauge in front of it.  The

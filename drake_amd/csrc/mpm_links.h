@@ -34,6 +34,30 @@
 //   seam    d (1), w (1), c w_j (1), the fused multiply-add (1) = 4
 // R_link = 18 (17 and one more for the second-order terms).  A row with n entries adds them in stored order, one
 // rounding of a partial sum per entry, each partial sum at most the row's sum of S: R_i = 18 + n_i, on sum S.
+//
+// Breakable links (mpm_set_link_limits, mpm_set_broken_links, mpm_link_break_state, mpm_link_break_measure,
+// mpm_link_breaks): link i may carry a break_length b_i (0: never breaks; else finite and > L).  The host forms
+// B2_i = (float)((double)b_i (double)b_i), rounded once; link_breaks, shared by host and device, forms link_force's l2
+// from d = x_b - x_a and answers l2 > B2 -- no square root, even in d, false for a NaN.  State: one byte per link in link
+// order, monotone (a substep only sets it; mpm_set_broken_links alone clears it).  k_link_break, one lane per link, runs
+// immediately in front of k_link while the breaking tables exist (some limit > 0 or some flag set): a link that is
+// broken, or has B2 == 0, returns at once; otherwise its two ids come from k_link_energy's pair record, its two slots
+// through DP::imap, its two positions from the current set -- three round trips of independent loads -- and where
+// link_breaks says so the lane sets the byte and overwrites the link's two entries of LinkArgs::ent (entry_of_link,
+// which link_table emits) with the rows' padding records (own id, 0, 0, 0): plain stores, one writer per link, an exact
+// +0 through the seam branch.  k_link, behind it on the stream and unchanged, never sees the broken link again, in the
+// substep in which it breaks included: elastic and damping part, every kind of link, both ends.  The verdict is formed
+// once per link on the positions of the substep's start (Jacobi): it does not depend on the other links, the particle
+// order or deterministic mode, and a substep that skips itself (gated_out) marks nothing.  No atomics but the error flag.
+// mpm_set_broken_links rebuilds ent on the host with the flagged links' entries padded and uploads it into the arrays in
+// force: that is also how a restore brings a link back.  mpm_links_max_stable_dt does NOT change when links break: it is
+// formed over the whole table, and breaking only removes non-negative terms from its row sums, so it stays a valid, more
+// conservative, guard.  Anchors (mpm_anchors.h) do not break yet.
+// Roundings of l2 (first order, units of 2^-24 of l2): each d_j carries 1, so each square 2; the product and the two
+// fused multiply-adds one each on partial sums of at most l2: 5, R_BREAK = 6 with one more for the second-order terms.
+// The cost of k_link_break on an MI355X: 5.2 us per substep on cloth_1m with one link per vertex (168,200 links, limits
+// on, none broken), k_link unchanged against the parent; a substep in which many links break has NOT been measured
+// (DESIGN.md section 3.3p).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -92,6 +116,17 @@ MPM_LINK_FN bool link_active(float L, bool tension_only, const float d[3]) {
 #endif
     const float l2 = fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0]));
     return (!(L > 0.f) | (l2 >= 1e-30f)) & (!tension_only | (sqrtf(l2) > L));
+}
+
+// whether a link breaks at the float differences d against B2 = (float)(break_length^2): l2 is link_force's, the
+// comparison is false for a NaN; *l2_out gets l2.  (The caller decides what B2 == 0 means.)
+MPM_LINK_FN bool link_breaks(const float d[3], float B2, float* l2_out) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const float l2 = fmaf(d[2], d[2], fmaf(d[1], d[1], d[0] * d[0]));
+    *l2_out = l2;
+    return l2 > B2;
 }
 
 }  // namespace mpm
@@ -207,8 +242,10 @@ __global__ __launch_bounds__(256) void k_link_eval(DP p, LinkArgs a, float* out)
 // not act: link_active on the float differences, as link_force decides), and its length, formed in double and rounded
 // to float once.  pair[i] = (bits of a's
 // particle id, bits of b's | LINK_FLAG_BIT, k, L).  An end without a vertex slot is reported; the link then counts as
-// of zero length.
-__global__ __launch_bounds__(256) void k_link_energy(DP p, const float4* pair, int n, double* term, float* length) {
+// of zero length.  broken (may be null): the flags of the breakable links; a broken link's term is 0, its length is
+// reported like any other.
+__global__ __launch_bounds__(256) void k_link_energy(DP p, const float4* pair, int n, const uint8_t* broken, double* term,
+                                                     float* length) {
     const int i = (int)(blockIdx.x * 256 + threadIdx.x);
     bool bad = false;
     if (i < n) {
@@ -225,13 +262,82 @@ __global__ __launch_bounds__(256) void k_link_energy(DP p, const float4* pair, i
             const double D0 = (double)xb.x - (double)xa.x, D1 = (double)xb.y - (double)xa.y, D2 = (double)xb.z - (double)xa.z;
             const double ld = sqrt(D0 * D0 + D1 * D1 + D2 * D2);
             l = (float)ld;
-            if (link_active(q.w, (__float_as_uint(q.y) & LINK_FLAG_BIT) != 0u, d)) {
+            const bool gone = broken && broken[i] != 0;
+            if (!gone && link_active(q.w, (__float_as_uint(q.y) & LINK_FLAG_BIT) != 0u, d)) {
                 const double st = ld - (double)q.w;
                 e = .5 * (double)q.z * st * st;
             }
         }
         term[i] = e;
         length[i] = l;
+    }
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
+}
+
+struct LinkBreakArgs {
+    const float4* pair;         // [link] k_link_energy's records: the two ends' particle ids
+    const float* B2;            // [link] (float)(break_length^2), 0: never breaks; nullptr: the tables do not exist
+    const unsigned* entry;      // [2 link] where the link's two entries are in `ent`: a's row, then b's row
+    uint8_t* broken;            // [link] 0 intact, 1 broken
+    float4* ent;                // LinkArgs::ent of the table in force
+    int n;
+};
+
+// Link i's float differences d = x_b - x_a on the current set, three round trips of independent loads (ids, slots,
+// positions).  false, with `bad` set: an end has no vertex slot; nothing is read through it.
+MPM_DEV bool link_ends(const DP& p, const PSet& S, const float4* pair, int i, unsigned& ida, unsigned& idb, float d[3], bool& bad) {
+    const float4 q = pair[i];
+    ida = __float_as_uint(q.x);
+    idb = __float_as_uint(q.y) & ~LINK_FLAG_BIT;
+    const int sa = p.imap[(int)ida], sb = p.imap[(int)idb];
+    if (!(sa >= p.Nf && sa < p.Np && sb >= p.Nf && sb < p.Np)) {
+        bad = true;
+        return false;
+    }
+    const float4 xa = S.q[0][sa], xb = S.q[0][sb];
+    d[0] = xb.x - xa.x;
+    d[1] = xb.y - xa.y;
+    d[2] = xb.z - xa.z;
+    return true;
+}
+
+// Immediately in front of k_link on the same stream, with the substep's DP, while the breaking tables exist: one lane
+// per link.  A link that breaks is marked and loses its two entries of the table k_link is about to read (one writer per
+// link: plain stores); a substep that skips itself marks nothing.
+__global__ __launch_bounds__(256) void k_link_break(DP p, LinkBreakArgs a) {
+    if (gated_out(p)) return;
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool bad = false;
+    if (i < a.n && a.broken[i] == 0) {
+        const float B2 = a.B2[i];
+        if (B2 != 0.f) {
+            unsigned ida, idb;
+            float d[3], l2;
+            if (link_ends(p, p.set[p.ctl->cur], a.pair, i, ida, idb, d, bad) && link_breaks(d, B2, &l2)) {
+                a.broken[i] = 1;
+                a.ent[a.entry[2 * (size_t)i]] = make_float4(__uint_as_float(ida), 0.f, 0.f, 0.f);
+                a.ent[a.entry[2 * (size_t)i + 1]] = make_float4(__uint_as_float(idb), 0.f, 0.f, 0.f);
+            }
+        }
+    }
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
+}
+
+// mpm_link_break_measure: l2 and the would-break verdict per link on the current state, broken links like the others;
+// the verdict is 0 for a link without a limit and while the tables do not exist (B2 == nullptr).  An end without a
+// vertex slot is reported; the link then gets l2 = 0 and verdict 0.  Changes no state.
+__global__ __launch_bounds__(256) void k_link_break_eval(DP p, const float4* pair, const float* B2, int n, float* l2_out,
+                                                         uint8_t* breaks_out) {
+    const int i = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool bad = false;
+    if (i < n) {
+        const float b2 = B2 ? B2[i] : 0.f;
+        unsigned ida, idb;
+        float d[3], l2 = 0.f;
+        bool breaks = false;
+        if (link_ends(p, p.set[p.ctl->cur], pair, i, ida, idb, d, bad)) breaks = link_breaks(d, b2, &l2);
+        l2_out[i] = l2;
+        breaks_out[i] = (b2 != 0.f && breaks) ? 1 : 0;
     }
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
 }
@@ -253,6 +359,7 @@ struct LinkPair {
 struct LinkTable : RowTable<LinkRecord> {
     std::vector<LinkPair> pair;        // [link] k_link_energy's records
     std::vector<double> k_sum, c_sum;  // [row] sum of k, sum of c over the row's links
+    std::vector<unsigned> entry_of_link;   // [2 link] where the link's entry in a's row, then in b's row, is in `ent`
 };
 
 // What mpm_set_links refuses, in the caller's numbering; empty: the table is fine
@@ -283,12 +390,15 @@ inline bool link_table(const Link* links, size_t n, size_t nf, size_t n_verts, s
     }
     for (size_t v = 0; v < n_verts; ++v) first[v + 1] += first[v];
     std::vector<LinkRecord> flat(2 * n);
+    std::vector<size_t> flat_of_link(2 * n);   // (a link's two places in `flat`: duplicate pairs get places of their own)
     {
         std::vector<size_t> fill(first.begin(), first.end() - 1);
         for (size_t i = 0; i < n; ++i) {
             const Link& q = links[i];
             const uint32_t flag = q.flags & LINK_TENSION_ONLY ? LINK_FLAG_BIT : 0u;
+            flat_of_link[2 * i] = fill[q.a];
             flat[fill[q.a]++] = LinkRecord{(uint32_t)(nf + q.b) | flag, q.stiffness, q.rest_length, q.damping};
+            flat_of_link[2 * i + 1] = fill[q.b];
             flat[fill[q.b]++] = LinkRecord{(uint32_t)(nf + q.a) | flag, q.stiffness, q.rest_length, q.damping};
             out.pair.push_back(LinkPair{(uint32_t)(nf + q.a), (uint32_t)(nf + q.b) | flag, q.stiffness, q.rest_length});
         }
@@ -313,7 +423,31 @@ inline bool link_table(const Link* links, size_t n, size_t nf, size_t n_verts, s
         why = "links: the table is too large";
         return false;
     }
+    // entry q of row r is at slice_off[r / slice] + q slice + r % slice (mpm_row_table.h)
+    std::vector<size_t> row_of_vertex(n_verts, 0);
+    for (size_t r = 0; r < row_vertex.size(); ++r) row_of_vertex[row_vertex[r]] = r;
+    out.entry_of_link.resize(2 * n);
+    for (size_t i = 0; i < n; ++i)
+        for (size_t end = 0; end < 2; ++end) {
+            const size_t v = end ? links[i].b : links[i].a, r = row_of_vertex[v], q = flat_of_link[2 * i + end] - first[v];
+            out.entry_of_link[2 * i + end] = (unsigned)((size_t)out.slice_off[r / slice] + q * slice + r % slice);
+        }
     return true;
+}
+
+// mpm_set_link_limits: B2[i] = (float)((double)b_i (double)b_i) for n checked limits; the refusal in the caller's
+// numbering, empty where the limits are fine.  (A non-zero limit whose square rounds to 0 is refused too: B2 == 0 is
+// what the kernel reads as "never breaks".)
+inline std::string link_limits(const float* break_length, const Link* links, size_t n, float* B2) {
+    for (size_t i = 0; i < n; ++i) {
+        const float b = break_length[i];
+        const std::string at = "link limits: link " + std::to_string(i);
+        if (!std::isfinite(b) || b < 0.f) return at + ": break_length is negative or not finite";
+        if (b != 0.f && !(b > links[i].rest_length)) return at + ": break_length is neither 0 nor > rest_length";
+        B2[i] = (float)((double)b * (double)b);
+        if (!std::isfinite(B2[i]) || (b != 0.f && !(B2[i] > 0.f))) return at + ": the square of break_length is not a finite positive float";
+    }
+    return std::string();
 }
 
 // The guard's rates on the vertices' masses (mass[vertex]): W = max_i (2 / m_i) sum_j k_ij, G = max_i (2 / m_i) sum_j c_ij

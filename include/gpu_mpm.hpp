@@ -369,6 +369,40 @@ struct GpuMpmState {
                           float f_on_a[3]) {
         mpm_check(mpm_link_force(&link, xa, xb, va, vb, f_on_a));
     }
+    // Extension: breakable links (mpm_set_link_limits) -- one break_length per link (0: never breaks; else finite and >
+    // rest_length); a link whose length exceeds it breaks for good and acts no more.  An empty vector switches every limit
+    // off.  A synchronisation point, like SetLinks.
+    void SetLinkLimits(const std::vector<float>& break_lengths) {
+        mpm_check(mpm_set_link_limits(h_, break_lengths.size(), break_lengths.data()));
+    }
+    std::vector<float> GetLinkLimits() const {
+        size_t n = 0;
+        mpm_check(mpm_get_link_limits(h_, nullptr, 0, &n));
+        std::vector<float> out(n);
+        mpm_check(mpm_get_link_limits(h_, out.data(), n, &n));
+        return out;
+    }
+    // scissors / restore: one byte per link in link order, non-zero = broken; replaces every flag
+    void SetBrokenLinks(const std::vector<uint8_t>& broken) { mpm_check(mpm_set_broken_links(h_, broken.size(), broken.data())); }
+    // the flags per link; count: null, or the number of broken links
+    std::vector<uint8_t> LinkBreakState(uint32_t* count = nullptr) const {
+        size_t n = 0;
+        mpm_check(mpm_get_links(h_, nullptr, 0, &n));
+        std::vector<uint8_t> broken(n);
+        uint32_t k = 0;
+        mpm_check(mpm_link_break_state(h_, broken.data(), &k));
+        if (count) *count = k;
+        return broken;
+    }
+    // l2 per link on the current positions; would_break: null, or the verdict per link
+    std::vector<float> LinkBreakMeasure(std::vector<uint8_t>* would_break = nullptr) const {
+        size_t n = 0;
+        mpm_check(mpm_get_links(h_, nullptr, 0, &n));
+        std::vector<float> l2(n);
+        if (would_break) would_break->assign(n, 0);
+        mpm_check(mpm_link_break_measure(h_, l2.data(), would_break ? would_break->data() : nullptr));
+        return l2;
+    }
     // Extension: anchors (mpm_set_anchors) -- springs and tension-only cords from cloth vertices to points of rigid bodies,
     // whose motions are those of SetBodyMotions and whose reactions arrive where the pins' do; an empty vector clears them.
     // A synchronisation point, like SetLinks.

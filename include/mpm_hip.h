@@ -1060,6 +1060,59 @@ MPM_API int mpm_links_max_stable_dt(mpm_handle_t h, float *dt_out);
 MPM_API int mpm_link_force(const mpm_link_t *link, const float xa[3], const float xb[3], const float va[3], const float vb[3],
                            float f_on_a[3]);
 
+/* ---- Breakable links: seams rip and cords snap beyond a length (an extension) ----
+ * Tearing lets the fabric open; this lets what holds it together fail.  Each link i of the table in force may carry a
+ * break_length b_i: 0 (the link never breaks) or a finite value > rest_length (for a seam: > 0).  The host forms
+ * B2_i = (float)((double)b_i (double)b_i), rounded once.  With d = x_b - x_a in float and the l2 of the link's force law,
+ *   l2 = fma(d2, d2, fma(d1, d1, d0 d0)),  the link BREAKS when l2 > B2_i
+ * -- no square root; false for a NaN position; even in d, and formed once per link, not per end.  Host and device run one
+ * function and agree to the bit on l2 and the verdict.  l2 is within 6 x 2^-24 l2 of the exact value on the float
+ * positions.
+ * State: one byte per link in link order, all zero when limits or flags are first set.  It is monotone: a substep only
+ * ever sets it (a link that broke stays broken when the load goes away, and when mpm_set_link_limits changes or removes
+ * the limits); mpm_set_broken_links alone clears it.  mpm_set_links replaces the table, and the limits and flags go with
+ * the table they belonged to: the new table starts with no limits and no flags.
+ * A broken link does not act, from the substep in which it breaks: the elastic and the damping part, every kind of link
+ * (seam, spring, tension-only), both ends.  Decisions within a substep are made link by link on the positions of the
+ * substep's start, the positions the link kernel reads (Jacobi); the result does not depend on the other links'
+ * decisions, the particle order or deterministic mode; a substep that skips itself marks nothing.  The kernel runs
+ * immediately in front of the link kernel, one lane per link, and counts under MPM_PHASE_VFORCE.
+ * mpm_link_forces and mpm_link_energy report what the substep applies: a broken link adds nothing to the forces, its
+ * energy term is 0, length_out still reports its length.  mpm_get_links keeps returning the table as given.
+ * mpm_links_max_stable_dt does NOT change when links break: it is formed over the whole table, and breaking only removes
+ * non-negative terms from its row sums, so it stays a valid, more conservative, guard.
+ * It works with everything links work with: tearing, pins, anchors, both bending models, pressure, damping, the weave,
+ * force fields, grid bodies, contact, fast math, deterministic mode and every non-partitioned substep path.  Anchors
+ * (mpm_set_anchors) do not break yet.
+ * Both setters need mpm_finalize, are ordered on the engine's stream and are synchronisation points; substeps that
+ * mpm_run_substeps still owes are run first, with the old limits.  The tables exist while some limit is > 0 or some flag
+ * is set; otherwise they are freed and the engine launches exactly what it launches without these calls.
+ * Refused with MPM_ERR_INVALID, nothing changed: a call before mpm_finalize; n different from the link count (0 allowed
+ * for the limits); a limit that is negative, NaN, infinite, non-zero and <= rest_length, or whose square is not a finite
+ * float (or is 0 for a non-zero limit) -- the message names the link; a null array with n > 0; any partitioned or
+ * multi-rank engine.
+ * The cost of the substep's kernel on an MI355X: 5.2 us per substep at 168,200 links with limits on and none broken; a
+ * substep in which many links break has not been measured. */
+/* n == the link count: one break_length per link; n == 0 (break_length may be NULL): all limits off */
+MPM_API int mpm_set_link_limits(mpm_handle_t h, size_t n, const float *break_length);
+/* The limits in force: min(link count, capacity) entries into out (zeros while off), the link count into *n_out. */
+MPM_API int mpm_get_link_limits(mpm_handle_t h, float *out, size_t capacity, size_t *n_out);
+/* Scissors and restore: broken[n], n the link count, one byte per link in link order; non-zero breaks the link, zero
+ * restores it.  Replaces every flag.  Allowed while every limit is 0 (a cord cut by hand); an all-zero array with all
+ * limits 0 frees the tables. */
+MPM_API int mpm_set_broken_links(mpm_handle_t h, size_t n, const uint8_t *broken);
+/* The flags (broken_out[link count], may be NULL) and the number of broken links (count_out, may be NULL), counted on the
+ * device in link order in a fixed tree.  Zeros while the tables do not exist. */
+MPM_API int mpm_link_break_state(mpm_handle_t h, uint8_t *broken_out, uint32_t *count_out);
+/* The substep's link function on the current positions, state untouched: l2_out[link count], would_break_out[link count]
+ * = the verdict against the link's limit (0 for a link without a limit, and while the tables do not exist); either may be
+ * NULL.  Broken links are evaluated like the others. */
+MPM_API int mpm_link_break_measure(mpm_handle_t h, float *l2_out, uint8_t *would_break_out);
+/* The kernel's link function on the host (no handle, no device), link by link: xa3[3 n], xb3[3 n] the ends' positions,
+ * B2[n] the squared limit as a float; l2_out[n], breaks_out[n] = (l2 > B2) as it stands (the caller decides what B2 = 0
+ * means); either output may be NULL. */
+MPM_API int mpm_link_breaks(size_t n, const float *xa3, const float *xb3, const float *B2, float *l2_out, uint8_t *breaks_out);
+
 /* ---- Anchors: springs and cords from cloth vertices to rigid bodies (an extension) ----
  * A pin holds a vertex to a body rigidly; a link joins two cloth vertices compliantly.  An anchor is the compliant
  * attachment to a body: a banner hung from a moving pole by cords, a parachute's lines to its payload, a tarp lashed to a

@@ -2,14 +2,16 @@
 """Cost of links between cloth vertices (mpm_set_links): the bench.py workload (cloth_1m, 16 sheets) on three engines --
 plain, `seams` (a few thousand links between neighbouring sheets: the first 256 vertices of every sheet joined to the
 same vertices of the next) and `dense` (one link per vertex: every vertex of an even sheet joined to the same vertex of
-the sheet above).  The links are springs at their rest length (L = the distance at the start), k such that dt is a
+the sheet above); `dense_limits` is `dense` with a break_length of 1 m on every link (mpm_set_link_limits: k_link_break
+runs in front of k_link, reads every link's ends and breaks nothing).  The links are springs at their rest length (L = the distance at the start), k such that dt is a
 quarter of mpm_links_max_stable_dt, c = 0: k_vforce and k_link run and every record is read and evaluated, while the
 trajectory stays close to the plain engine's.  Per round every engine runs once, in turn, in one process:
 mpm_profile_substeps' VFORCE phase (k_vforce + k_link on an engine with links, empty on the plain one, whose vertex
 forces are summed inside k_p2g; event time), its P2G phase, and the whole substep (wall time of mpm_run_substeps,
 synchronised at the end).  Medians over the rounds; the raw rounds are printed too.
 
-  python scripts/bench_links.py [--steps 40] [--warmup 10] [--rounds 5] [--config cloth_1m] [--engines plain,seams,dense]
+  python scripts/bench_links.py [--steps 40] [--warmup 10] [--rounds 5] [--config cloth_1m]
+                                [--engines plain,seams,dense,dense_limits]
 
 Prints one JSON record.
 """
@@ -33,7 +35,7 @@ def link_table(sheets, kind):
             n = min(256, len(sheets[s][0]), len(sheets[s + 1][0]))
             a.append(first[s] + np.arange(n))
             b.append(first[s + 1] + np.arange(n))
-    elif kind == "dense":
+    elif kind in ("dense", "dense_limits"):
         for s in range(0, len(sheets) - 1, 2):
             n = min(len(sheets[s][0]), len(sheets[s + 1][0]))
             a.append(first[s] + np.arange(n))
@@ -55,6 +57,8 @@ def engine(bits, sheets, kind, dt):
         g.set_links(t)
         t["stiffness"] *= np.float32((0.25 * g.links_max_stable_dt() / dt) ** 2)   # (the limit scales with 1 / sqrt(k))
         g.set_links(t)
+        if kind == "dense_limits":
+            g.set_link_limits(np.full(len(t), 1.0, np.float32))
     return g
 
 
@@ -93,6 +97,7 @@ def main():
         t = g.get_links()
         rows.append(dict(engine=k, links=int(len(t)), stiffness=float(t["stiffness"][0]) if len(t) else 0.0,
                          max_stable_dt=g.links_max_stable_dt(),
+                         limits=int((g.get_link_limits() > 0).sum()), broken=g.link_break_state()[1],
                          vforce_us=round(float(np.median([d["vforce"] for d in s["phases"]])) * 1e3, 2),
                          phases_us={p: round(float(np.median([d[p] for d in s["phases"]])) * 1e3, 2) for p in s["phases"][0]},
                          substep_us=round(float(np.median(s["substep_us"])), 2),
