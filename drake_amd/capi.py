@@ -441,6 +441,21 @@ def tear_face(dminv3, x, L):
     return mq, fails.astype(bool)
 
 
+def rest_shape_check(rest_pos, indices):
+    """mpm_rest_shape_check: what mpm_set_rest_shape checks, on the host.  rest_pos (n_verts, 3), indices (n_faces, 3);
+    returns (ok, first_bad_face): the first face whose first edge or area is zero or not finite, or -1; ok is False also
+    for an index out of range or a coordinate that is not finite.  Needs no engine and no GPU."""
+    lib = load_library()
+    pos = np.ascontiguousarray(rest_pos, np.float32).reshape(-1, 3)
+    idx = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    bad = C.c_int32(-1)
+    rc = lib.mpm_rest_shape_check(pos.ctypes.data if pos.size else None, len(pos), idx.ctypes.data if idx.size else None,
+                                  len(idx), C.byref(bad))
+    if rc not in (0, -1):      # (MPM_ERR_INVALID is the verdict, not a failure of the call)
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return rc == 0, int(bad.value)
+
+
 def grid_collider_preset(mpm_bc: int, sdf_friction: float = 0.3):
     """The collider table that reproduces the reference's scene mpm_bc (cuda_mpm_kernels.cuh:673-774)."""
     lib = load_library()
@@ -602,6 +617,7 @@ SYMBOLS = [
     "mpm_set_weave", "mpm_get_weave", "mpm_weave_axes", "mpm_weave_forces", "mpm_weave_strain", "mpm_weave_energy",
     "mpm_weave_max_stable_dt", "mpm_weave_face_records", "mpm_weave_face_axes",
     "mpm_set_tearing", "mpm_get_tearing", "mpm_set_torn_faces", "mpm_tear_state", "mpm_tear_measure", "mpm_tear_face",
+    "mpm_set_rest_shape", "mpm_get_rest_shape", "mpm_rest_shape_check",
     "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
     "mpm_set_link_limits", "mpm_get_link_limits", "mpm_set_broken_links", "mpm_link_break_state", "mpm_link_break_measure",
     "mpm_link_breaks",
@@ -790,6 +806,9 @@ def load_library(build: bool = True):
         "mpm_tear_state": [vp, vp, vp, sz, P(sz)],
         "mpm_tear_measure": [vp, vp, vp],
         "mpm_tear_face": [sz, vp, vp, vp, vp, vp],
+        "mpm_set_rest_shape": [vp, vp],
+        "mpm_get_rest_shape": [vp, vp, P(C.c_int)],
+        "mpm_rest_shape_check": [vp, sz, vp, sz, P(C.c_int32)],
         "mpm_measure": [vp, vp, sz, P(sz), vp],
         "mpm_face_strain": [vp, vp],
         "mpm_cloth_energy_density": [vp, sz, vp, vp],
@@ -1218,6 +1237,32 @@ class GpuMpm:
     @staticmethod
     def tear_face(dminv3, x, L):
         return tear_face(dminv3, x, L)
+
+    def set_rest_shape(self, rest_pos):
+        """mpm_set_rest_shape: the rest state -- Dm^-1, volumes, masses -- computed again from rest_pos (n_verts, 3) in
+        dump_cpu_state's vertex numbering, as mpm_finalize would have on cloths added there; None restores the positions
+        as added.  Positions, velocities, C, F and the particle order stay.  Refused while a table derived from the rest
+        shape is in force (bending, shell bending, weave, damping, pressure, links, anchors, pins): clear it, set the rest
+        shape, set it again.  A synchronisation point."""
+        if rest_pos is None:
+            self._ck(self.lib.mpm_set_rest_shape(self.h, None))
+            return
+        r = np.ascontiguousarray(rest_pos, np.float32).reshape(-1, 3)
+        if len(r) != getattr(self, "n_verts", len(r)):      # (before finalize the library refuses the call itself)
+            raise ValueError("rest_pos must have one row per vertex")
+        self._ck(self.lib.mpm_set_rest_shape(self.h, r.ctypes.data if r.size else None))
+
+    def get_rest_shape(self):
+        """mpm_get_rest_shape: (rest positions (n_verts, 3) float32 -- the positions as added until set_rest_shape --,
+        whether a rest shape given by the caller is in force)."""
+        # (before finalize the library refuses the call itself)
+        out, is_set = np.zeros((getattr(self, "n_verts", 0), 3), np.float32), C.c_int(0)
+        self._ck(self.lib.mpm_get_rest_shape(self.h, out.ctypes.data if out.size else None, C.byref(is_set)))
+        return out, bool(is_set.value)
+
+    @staticmethod
+    def rest_shape_check(rest_pos, indices):
+        return rest_shape_check(rest_pos, indices)
 
     def set_links(self, table):
         """mpm_set_links: the links between cloth vertices -- seams (rest_length 0), springs and tension-only cords --, an

@@ -1,5 +1,5 @@
 // Host side of the per-cloth features: cloth materials, external force fields, row tables, bending stiffness, links,
-// pressure, shell bending, damping, the weave, tearing, breakable links and the per-cloth report -- what the entry points in mpm_engine.hip call once their
+// pressure, shell bending, damping, the weave, tearing, breakable links, the rest shape and the per-cloth report -- what the entry points in mpm_engine.hip call once their
 // arguments are checked.
 // Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
 #pragma once
@@ -222,7 +222,7 @@ static int set_bending(mpm_engine* e, size_t n_cloths, const float* stiffness) {
         REQUIRE(std::isfinite(stiffness[c]) && stiffness[c] >= 0.f, "bending: a stiffness is negative or not finite");
     BendTable t;
     std::string why;
-    if (!bending_table(e->cloths, e->h_pos.data(), e->h_idx.data(), e->nf, n_cloths, stiffness, BEND_SLICE, t, why))
+    if (!bending_table(e->cloths, e->h_rest.data(), e->h_idx.data(), e->nf, n_cloths, stiffness, BEND_SLICE, t, why))
         return fail(MPM_ERR_INVALID, why);
     // substeps that mpm_run_substeps deferred are owed with the stiffness they were enqueued with
     if (int rc = settle(e)) return rc;
@@ -525,7 +525,7 @@ static int set_pressure(mpm_engine* e, size_t n_cloths, const mpm_cloth_pressure
             return fail(MPM_ERR_INVALID, "pressure: cloth " + std::to_string(c) + " is in gas mode but its mesh is not closed and consistently "
                         "wound: the edge " + std::to_string(edge[0]) + " -> " + std::to_string(edge[1]) +
                         " does not occur exactly once with its reverse exactly once");
-        if (!(mesh_volume(e->h_pos.data(), e->h_idx.data(), cl.first_face, cl.n_faces) > 0.0))
+        if (!(mesh_volume(e->h_rest.data(), e->h_idx.data(), cl.first_face, cl.n_faces) > 0.0))
             return fail(MPM_ERR_INVALID, "pressure: cloth " + std::to_string(c) + " is in gas mode but its rest volume is not positive: "
                         "reverse the winding of its faces");
     }
@@ -581,8 +581,9 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
     REQUIRE(e->np < (size_t)1 << 31, "shell bending: too many particles");
     if (rest_pos && n_cloths)
         for (size_t i = 0; i < 3 * e->nv; ++i) REQUIRE(std::isfinite(rest_pos[i]), "shell bending: rest_pos is not finite");
-    // the shape that gives cbar, the guard's geometry and psibar: rest_pos where given and asked for, else the mesh as added
-    std::vector<float> shape(e->h_pos.begin(), e->h_pos.begin() + (long)(3 * e->nv));
+    // the shape that gives cbar, the guard's geometry and psibar: rest_pos where given and asked for, else the rest shape
+    // in force (the mesh as added until mpm_set_rest_shape)
+    std::vector<float> shape(e->h_rest.begin(), e->h_rest.begin() + (long)(3 * e->nv));
     for (size_t c = 0; c < n_cloths && rest_pos; ++c)
         if (P[c].rest == SHELL_REST_SHAPE) {
             const mpm_engine::Cloth& cl = e->cloths[c];
@@ -852,7 +853,7 @@ static int weave_apply(mpm_engine* e, std::vector<mpm_cloth_weave_t> w, const fl
             if (k.x == 0.f && k.y == 0.f && k.z == 0.f && k.w == 0.f) continue;
             for (size_t f = cl.first_face; f < cl.first_face + cl.n_faces; ++f) {
                 float X[3][3];
-                for (int j = 0; j < 3; ++j) std::memcpy(X[j], &e->h_pos[(size_t)e->h_idx[3 * f + j] * 3], 12);
+                for (int j = 0; j < 3; ++j) std::memcpy(X[j], &e->h_rest[(size_t)e->h_idx[3 * f + j] * 3], 12);
                 const float* d = w[c].warp_dir;
                 if (face_dirs && (face_dirs[3 * f] != 0.f || face_dirs[3 * f + 1] != 0.f || face_dirs[3 * f + 2] != 0.f))
                     d = face_dirs + 3 * f;
@@ -1170,6 +1171,85 @@ static int tear_faces(size_t n, const float* dminv3, const float* x9, const floa
         if (mq_out) std::memcpy(mq_out + 2 * f, mq, sizeof mq);
         if (fails_out) fails_out[f] = fails ? 1 : 0;
     }
+    return 0;
+}
+
+// ---- the rest shape apart from the pose (mpm_set_rest_shape, mpm_get_rest_shape, mpm_rest_shape_check; mpm_rest.h) ----
+// host code only: the first face (or -1) whose rest edge e0 = xb - xa or rest area |e0 x e1| is zero, in double from the
+// float positions -- the two numbers Finalize divides by (the rotations' q2 and det Dm).  No conditioning threshold:
+// Finalize has none.  A non-finite coordinate makes its faces bad (the comparisons are false for a NaN).
+static int32_t rest_shape_first_bad_face(const float* rest_pos, const int32_t* indices, size_t n_faces) {
+    for (size_t f = 0; f < n_faces; ++f) {
+        const float *a = rest_pos + 3 * (size_t)indices[3 * f], *b = rest_pos + 3 * (size_t)indices[3 * f + 1],
+                    *c = rest_pos + 3 * (size_t)indices[3 * f + 2];
+        const double e0[3] = {(double)b[0] - a[0], (double)b[1] - a[1], (double)b[2] - a[2]};
+        const double e1[3] = {(double)c[0] - a[0], (double)c[1] - a[1], (double)c[2] - a[2]};
+        const double n[3] = {e0[1] * e1[2] - e0[2] * e1[1], e0[2] * e1[0] - e0[0] * e1[2], e0[0] * e1[1] - e0[1] * e1[0]};
+        const double l2 = e0[0] * e0[0] + e0[1] * e0[1] + e0[2] * e0[2], n2 = n[0] * n[0] + n[1] * n[1] + n[2] * n[2];
+        if (!(l2 > 0.0 && l2 < INFINITY) || !(n2 > 0.0 && n2 < INFINITY)) return (int32_t)f;
+    }
+    return -1;
+}
+static int rest_shape_check(const float* rest_pos, size_t n_verts, const int32_t* indices, size_t n_faces, int32_t* first_bad_face_out) {
+    if (first_bad_face_out) *first_bad_face_out = -1;
+    for (size_t i = 0; i < 3 * n_faces; ++i)
+        REQUIRE(indices[i] >= 0 && (size_t)indices[i] < n_verts, "triangle index out of range");
+    const int32_t bad = rest_shape_first_bad_face(rest_pos, indices, n_faces);
+    if (first_bad_face_out) *first_bad_face_out = bad;
+    if (bad >= 0)
+        return fail(MPM_ERR_INVALID, "rest shape: face " + std::to_string(bad) + ": its first edge or its area is zero or not finite");
+    for (size_t i = 0; i < 3 * n_verts; ++i) REQUIRE(std::isfinite(rest_pos[i]), "rest shape: a coordinate is not finite");
+    return 0;
+}
+// The table in force (or null) whose host side caches something derived from the rest positions, Dm^-1, the volumes or
+// the masses: mpm_set_rest_shape is refused while it is; the caller clears it, sets the rest shape and sets it again.
+//   bending        cotangent weights of h_rest; limit from the masses      shell bending  cbar, psibar, the guard's masses
+//   damping        Dm^-1, volumes and masses of its Gershgorin sums        the weave      axes from h_rest; Dm^-1, volumes, masses
+//   pressure       winding checked against the rest volume                 links          limit from the masses
+//   anchors        limit from the masses                                   pins           the bodies' impulse sums accumulate in
+//                                                                                         the scale set_fixed_point_scales derives
+//                                                                                         from the total mass
+// Materials, force fields, tear limits and flags, grid colliders and bodies and contact materials hold nothing of the kind.
+static const char* rest_shape_conflict(const mpm_engine* e) {
+    if (e->bend.on()) return "bending stiffness (mpm_set_bending)";
+    if (e->shell.on()) return "shell bending (mpm_set_shell_bending)";
+    if (e->weave.on()) return "a weave (mpm_set_weave)";
+    if (e->damp.any()) return "damping (mpm_set_damping)";
+    if (e->pressure.on()) return "pressure (mpm_set_pressure)";
+    if (e->links.on()) return "links (mpm_set_links)";
+    if (e->anchors.on()) return "anchors (mpm_set_anchors)";
+    if (!e->pin.set.empty()) return "pins (mpm_set_pins)";
+    return nullptr;
+}
+// mpm_set_rest_shape: the checks on the host in double, the owed substeps, then k_rest_faces and k_rest_vertices on the
+// current particle order and the fixed-point scales from the new masses.  rest_pos null: the positions as added.  A
+// refusal enqueues nothing: the rest state in force stays.
+static int set_rest_shape(mpm_engine* e, const float* rest_pos) {
+    if (const char* other = rest_shape_conflict(e))
+        return fail(MPM_ERR_INVALID, std::string("mpm_set_rest_shape: the engine has ") + other +
+                                         ", which holds values derived from the rest shape: clear it, set the rest shape, set it again");
+    const float* R = rest_pos ? rest_pos : e->h_pos.data();
+    for (size_t i = 0; i < 3 * e->nv; ++i) REQUIRE(std::isfinite(R[i]), "mpm_set_rest_shape: a coordinate is not finite");
+    const int32_t bad = rest_shape_first_bad_face(R, e->h_idx.data(), e->nf);
+    if (bad >= 0)
+        return fail(MPM_ERR_INVALID, "mpm_set_rest_shape: face " + std::to_string(bad) + ": its first rest edge or its rest area is zero");
+    // substeps that mpm_run_substeps deferred are owed with the rest state they were enqueued with
+    if (int rc = settle(e)) return rc;
+    const size_t nv = e->nv, nf = e->nf, np = e->np;
+    // staging: the rest positions, behind them the quarter volumes by original face id, then the densities by original id
+    const size_t off_quarter = 3 * nv, off_rho = off_quarter + nf, n_float = off_rho + (e->multi_mat ? np : 0);
+    if (int rc = e->stage(std::max<size_t>(n_float, 1) * 4)) return rc;
+    float* d = (float*)e->d_stage;
+    if (nv) H2D(e, d, R, 3 * nv * 4);
+    if (e->multi_mat) H2D(e, d + off_rho, e->h_rho_of_pid.data(), np * 4);
+    const RestArgs a{d, d + off_quarter, e->multi_mat ? d + off_rho : nullptr};
+    if (nf) hipLaunchKernelGGL(k_rest_faces, dim3(e->g_nf), dim3(256), 0, e->stream, e->dp, a);
+    if (nv) hipLaunchKernelGGL(k_rest_vertices, dim3(e->g_nv), dim3(256), 0, e->stream, e->dp, a);
+    HIP_TRY(hipGetLastError());
+    // (a synchronisation point: it reads the new masses back)
+    if (int rc = set_fixed_point_scales(e)) return rc;
+    e->h_rest.assign(R, R + 3 * nv);
+    e->rest_set = rest_pos != nullptr;
     return 0;
 }
 

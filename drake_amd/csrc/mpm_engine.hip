@@ -504,6 +504,8 @@ int mpm_finalize(mpm_handle_t e) try {
     // ---- host-side layout: [faces | verts], indices offset by +nf ---------
     // (cuda_mpm_model.cu:40-45)
     PSet& S0 = p.set[0];
+    e->h_rest = e->h_pos;   // (the rest shape is the pose the cloths were added in, until mpm_set_rest_shape)
+    e->rest_set = false;
     {
         std::vector<float> q0(np * 4, 0.f), q1(np * 4, 0.f);   // (x,y,z,vol) and (vx,vy,vz,C8); faces are filled on the device
         for (size_t i = 0; i < nv; ++i)
@@ -770,8 +772,10 @@ int mpm_sync(mpm_handle_t e) try {
 } MPM_CATCH_ALL
 
 // partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
-// stiffness, no damping, no weave, no tearing, no links, no pressure, no shell bending and no anchors (out of scope)
-static int extensions_refused(const mpm_engine* e, const char* what) {
+// stiffness, no damping, no weave, no tearing, no links, no pressure, no shell bending and no anchors (out of scope).
+// set_up: the call partitions the engine or joins it to other ranks (mpm_dist_init, chain, team, world), which an engine
+// with a rest shape of its own refuses too; the halo substeps of a single engine run on whatever rest state it holds.
+static int extensions_refused(const mpm_engine* e, const char* what, bool set_up = true) {
     if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
     if (e->multi_mat)
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on a multi-material engine (mpm_add_qr_cloth_with_material)");
@@ -795,6 +799,8 @@ static int extensions_refused(const mpm_engine* e, const char* what) {
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with shell bending (mpm_set_shell_bending)");
     if (e->anchors.on())
         return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with anchors (mpm_set_anchors)");
+    if (set_up && e->rest_set)
+        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with a rest shape of its own (mpm_set_rest_shape; null restores the positions as added)");
     return 0;
 }
 // the refusal of a dt above a feature's mpm_<feature>_max_stable_dt (fields_stable)
@@ -1156,7 +1162,7 @@ int mpm_substep_end(mpm_handle_t e, float dt, int bc) try {
 static int substep_begin_halo(mpm_handle_t e, float dt, int n, const int* bx_lo, const int* bx_hi, const int* shift_bx,
                               void* const* send_bufs, size_t cap, uint32_t* const* counters, bool lean) {
     READY(e);
-    if (int rc = extensions_refused(e, "halo substeps")) return rc;
+    if (int rc = extensions_refused(e, "halo substeps", false)) return rc;
     REQUIRE(n >= 0 && n <= 2 && (n == 0 || (bx_lo && bx_hi && shift_bx && send_bufs)), "bad halo zone list");
     REQUIRE(n == 0 || (cap > 0 && cap < (1u << 24)), "bad halo buffer");
     DP p = e->dp;   // per-launch copy: k_grid<0> packs the zones' sums into the send buffers as it gathers them
@@ -1195,7 +1201,7 @@ static void halo_zones_into(const mpm_engine* e, int* n, int* lo, int* hi) {
 // neighbours' sums, to be overlapped with the exchange.  Zones = the ranges given to begin.
 int mpm_substep_mid_halo(mpm_handle_t e, float dt, int bc) try {
     READY(e);
-    if (int rc = extensions_refused(e, "halo substeps")) return rc;
+    if (int rc = extensions_refused(e, "halo substeps", false)) return rc;
     REQUIRE(e->grid_state == 3 && !e->halo_mid_done, "mpm_substep_mid_halo needs mpm_substep_begin_halo first");
     GridColliders gc;
     if (int rc = grid_colliders_for(e, bc, &gc)) return rc;
@@ -1212,7 +1218,7 @@ int mpm_substep_mid_halo(mpm_handle_t e, float dt, int bc) try {
 static int substep_end_halo(mpm_handle_t e, float dt, int bc, int n, const void* const* recv_bufs, size_t cap, bool with_g2p,
                             bool lean) {
     READY(e);
-    if (int rc = extensions_refused(e, "halo substeps")) return rc;
+    if (int rc = extensions_refused(e, "halo substeps", false)) return rc;
     REQUIRE(n >= 0 && n <= 2 && (n == 0 || recv_bufs), "bad halo buffer list");
     REQUIRE(e->grid_state == 3, "mpm_substep_end_halo without mpm_substep_begin_halo");
     GridColliders gc;
@@ -2482,6 +2488,27 @@ int mpm_tear_measure(mpm_handle_t e, float* mq_out, uint8_t* would_fail_out) try
 int mpm_tear_face(size_t n, const float* dminv3, const float* x9, const float* L, float* mq_out, uint8_t* fails_out) try {
     REQUIRE((dminv3 && x9 && L) || n == 0, "null array");
     return tear_faces(n, dminv3, x9, L, mq_out, fails_out);
+} MPM_CATCH_ALL
+
+// ---- the rest shape apart from the pose (mpm_cloth_host.h; mpm_rest.h) ----------------------------------------------------------
+int mpm_set_rest_shape(mpm_handle_t e, const float* rest_pos) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "a rest shape of its own is")) return rc;
+    return set_rest_shape(e, rest_pos);
+} MPM_CATCH_ALL
+
+int mpm_get_rest_shape(mpm_handle_t e, float* rest_pos_out, int* is_set_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(e->finalized, "call mpm_finalize first");
+    if (rest_pos_out) std::copy(e->h_rest.begin(), e->h_rest.end(), rest_pos_out);
+    if (is_set_out) *is_set_out = e->rest_set ? 1 : 0;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_rest_shape_check(const float* rest_pos, size_t n_verts, const int32_t* indices, size_t n_faces, int32_t* first_bad_face_out) try {
+    REQUIRE((rest_pos || n_verts == 0) && (indices || n_faces == 0), "null array");
+    REQUIRE(n_faces < (size_t)1 << 31, "too many faces");
+    return rest_shape_check(rest_pos, n_verts, indices, n_faces, first_bad_face_out);
 } MPM_CATCH_ALL
 
 // ---- links between cloth vertices (mpm_cloth_host.h; mpm_links.h) --------------------------------------------------------------

@@ -24,6 +24,7 @@
 #include "mpm_damping.h"
 #include "mpm_weave.h"
 #include "mpm_tear.h"
+#include "mpm_rest.h"
 #include "mpm_links.h"
 #include "mpm_pressure.h"
 #include "mpm_shell.h"
@@ -114,6 +115,10 @@ struct mpm_engine {
     // staged cloth (AddQRCloth)
     std::vector<float> h_pos, h_vel;
     std::vector<int> h_idx;  // vertex ids local to the vertex array
+    // the rest shape (mpm_set_rest_shape; mpm_rest.h): the vertex positions the rest state in force was computed from --
+    // h_pos from mpm_finalize until the call.  What derives a table from the rest shape reads this, not the pose h_pos.
+    std::vector<float> h_rest;
+    bool rest_set = false;   // a rest shape other than the positions as added is in force
     size_t nv = 0, nf = 0, np = 0;
     // every cloth in call order, and the per-cloth materials (mpm_add_qr_cloth_with_material: at most
     // MAX_CLOTH_MATERIALS cloths; a face's cloth rides in fq[3].x, see FACE_CLOTH_SHIFT)
@@ -538,6 +543,8 @@ static int settle(mpm_engine* e, Ctl* fresh = nullptr);
 // the conditional re-sort
 static void launch_rebuild(mpm_engine* e, DP p, bool lean = false, float dt = 0.f);
 static int recover_slab_overflow(mpm_engine* e, Ctl& c);
+// the fixed-point scales of ParticleToGrid's tiles, from the total mass: again after every change of the masses
+static int set_fixed_point_scales(mpm_engine* e);
 
 #define READY_NO_SETTLE(e)                              \
     REQUIRE(e, "null handle");                          \

@@ -21,18 +21,7 @@ __global__ __launch_bounds__(256) void k_init_faces(DP p) {
     const int s0 = __float_as_int(f3.y), s1 = __float_as_int(f3.z), s2 = __float_as_int(f3.w);
     const float4 xa = S.q[0][s0], xb = S.q[0][s1], xc = S.q[0][s2];
     const float4 va = S.q[1][s0], vb = S.q[1][s1], vc = S.q[1][s2];
-    const float D0[3] = {xb.x - xa.x, xb.y - xa.y, xb.z - xa.z};
-    const float D1[3] = {xc.x - xa.x, xc.y - xa.y, xc.z - xa.z};
-    const float Ds[6] = {D0[0], D1[0], D0[1], D1[1], D0[2], D1[2]};
-    float Q[9], R[6];
-    givens_qr3<2>(Ds, Q, R);
-    const float Dmat[4] = {R[0], R[1], 0.f, R[3]};
-    float Di[4];
-    inv2(Dmat, Di);
-    const float cx = D0[1] * D1[2] - D1[1] * D0[2];
-    const float cy = D0[2] * D1[0] - D1[2] * D0[0];
-    const float cz = D0[0] * D1[1] - D1[0] * D0[1];
-    const float v4 = sqrtf(cx * cx + cy * cy + cz * cz) / 8.f * p.dx;
+#include "mpm_rest_face.inc"   // (Q, Di, v4 from xa, xb, xc: the text k_rest_faces shares)
     S.q[0][i] = make_float4((xa.x + xb.x + xc.x) / 3.f, (xa.y + xb.y + xc.y) / 3.f, (xa.z + xb.z + xc.z) / 3.f, v4);
     S.q[1][i] = make_float4((va.x + vb.x + vc.x) / 3.f, (va.y + vb.y + vc.y) / 3.f, (va.z + vb.z + vc.z) / 3.f, 0.f);
     pack_F(Q, S.fq[0][i], S.fq[1][i], S.f8[i]);

@@ -331,6 +331,24 @@ struct GpuMpmState {
         mpm_check(mpm_tear_measure(h_, mq.data(), would_fail ? would_fail->data() : nullptr));
         return mq;
     }
+    // Extension: the rest shape apart from the pose (mpm_set_rest_shape) -- Dm^-1, volumes and masses computed again from
+    // rest_pos (3 floats per vertex in the numbering of DumpCpuState), as Finalize would have on cloths added there; the
+    // state and the particle order stay.  Mass follows the rest shape.  Refused while a table derived from the rest shape
+    // is in force (see mpm_hip.h).  A synchronisation point, like SetBending.
+    void SetRestShape(const std::vector<float>& rest_pos) {
+        if (rest_pos.size() != 3 * n_verts()) throw std::invalid_argument("SetRestShape: three floats per vertex");
+        mpm_check(mpm_set_rest_shape(h_, rest_pos.data()));
+    }
+    // back to the positions as added
+    void ClearRestShape() { mpm_check(mpm_set_rest_shape(h_, nullptr)); }
+    // the rest shape in force; is_set: null, or whether the caller gave it
+    std::vector<float> GetRestShape(bool* is_set = nullptr) const {
+        std::vector<float> out(3 * n_verts());
+        int set = 0;
+        mpm_check(mpm_get_rest_shape(h_, out.data(), &set));
+        if (is_set) *is_set = set != 0;
+        return out;
+    }
     // Extension: links between cloth vertices (mpm_set_links) -- seams, springs, tension-only cords; an empty vector
     // clears them.  A synchronisation point, like SetBending.
     void SetLinks(const std::vector<mpm_link_t>& links) { mpm_check(mpm_set_links(h_, links.size(), links.data())); }

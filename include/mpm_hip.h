@@ -1001,6 +1001,54 @@ MPM_API int mpm_tear_measure(mpm_handle_t h, float *mq_out, uint8_t *would_fail_
  * fails_out[n] = (h < 0) || (q > h h) as it stands (the caller decides what L = 0 means); either output may be NULL. */
 MPM_API int mpm_tear_face(size_t n, const float *dminv3, const float *x9, const float *L, float *mq_out, uint8_t *fails_out);
 
+/* ---- Rest shape apart from the initial pose: pre-strained and re-shaped cloth (an extension) ----
+ * mpm_finalize takes the pose the cloths were added in as their stress-free shape.  mpm_set_rest_shape computes the rest
+ * state again from other vertex positions rest_pos[3 n_verts] (the vertex numbering of mpm_dump_cpu_state, over all
+ * cloths), on the particle order the engine has reached: a membrane stretched onto a frame, a garment whose flat pattern
+ * differs from the pose it starts in, cloth that shrinks or grows between batches of substeps, a restart from a deformed
+ * pose.  NULL restores the positions as added.
+ * After the call the rest state is, bit for bit, the one mpm_finalize would have computed had the cloths been added at
+ * rest_pos: Dm^-1 per face (MPM_ARR_DM_INVERSES), the face's static volume, every particle's volume -- a face's is
+ * |e0 x e1| / 8 dx, a vertex's the float sum of its faces' in ascending face id -- and, in a multi-material engine, its
+ * mass = volume x its cloth's density.
+ * THE MASS RULE: mass follows the rest shape.  The engine has one number per face for the volume of the elastic energy
+ * and the volume of the mass; a cloth pre-stretched onto a frame therefore has the mass of its rest shape (as the real
+ * one has), and the fixed-point scales of ParticleToGrid are derived again from the new total.
+ * Left alone: positions, velocities, C, F, torn flags and the particle order.  F's in-plane columns are rewritten by
+ * the next CalcFemStateAndForce from the deformed edges and the new Dm^-1; F's normal column stays the pose's.  The
+ * reports (mpm_measure, mpm_face_strain) read F as the last CalcFemStateAndForce wrote it: between this call and the
+ * next substep they still show the strain against the OLD rest shape (the masses are the new ones at once).
+ * Features set AFTERWARDS derive from the rest shape, not from the pose: the cotangent weights of mpm_set_bending, the
+ * default shape of mpm_set_shell_bending (its own rest_pos still overrides per cloth), the winding check of a gas
+ * pressure, the axes of mpm_set_weave (mpm_weave_axes), and every stability limit, which reads the new Dm^-1, volumes
+ * and masses.
+ * THE ORDERING RULE: the call needs mpm_finalize; substeps that mpm_run_substeps still owes are run first, with the old
+ * rest state; it is ordered on the engine's stream and is a synchronisation point.  Time-dependent rest shapes are set
+ * between batches, like time-dependent force fields.
+ * Refused with MPM_ERR_INVALID, the previous rest state staying in force to the bit (the first three are decided on the
+ * host, in double, before anything is enqueued):
+ *   - a coordinate that is not finite;
+ *   - a face whose first rest edge e0 = x1 - x0 or whose rest area |e0 x e1| is zero (mpm_rest_shape_check names the
+ *     first; there is no conditioning threshold, as mpm_finalize has none);
+ *   - a partitioned or multi-rank engine; and mpm_dist_init, the chain, team and world set-up and substeps on an engine
+ *     whose rest shape is set (NULL clears that; the halo substeps of a single engine run on whatever rest state it holds);
+ *   - a table in force whose host side holds values derived from the rest positions, Dm^-1, the volumes or the masses:
+ *     mpm_set_bending (weights, limit), mpm_set_shell_bending (cbar, psibar, limit), mpm_set_weave (axes, limit),
+ *     mpm_set_damping (row sums, masses, limit), mpm_set_pressure (with a cloth not off: the rest volume's sign),
+ *     mpm_set_links (limit from the masses; its break limits go with it), mpm_set_anchors (limit from the masses),
+ *     mpm_set_pins (the bodies' impulse sums are kept in the fixed-point scale of the total mass).  The caller clears
+ *     such a table, sets the rest shape and sets the table again.
+ *   Per-cloth materials, mpm_set_force_fields, mpm_set_tearing / mpm_set_torn_faces, grid colliders and bodies and
+ *   contact materials hold nothing of the kind and are accepted. */
+MPM_API int mpm_set_rest_shape(mpm_handle_t h, const float *rest_pos /* [3 n_verts], vertex numbering of mpm_dump_cpu_state; NULL = the positions as added */);
+/* The rest shape in force into rest_pos_out[3 n_verts] (may be NULL): the positions as added until mpm_set_rest_shape;
+ * *is_set_out (may be NULL) = 1 while a rest shape given by the caller is in force.  Needs mpm_finalize; no device work. */
+MPM_API int mpm_get_rest_shape(mpm_handle_t h, float *rest_pos_out /* [3 n_verts] */, int *is_set_out);
+/* Host only, no handle, no device: what mpm_set_rest_shape checks.  *first_bad_face_out (may be NULL) = the first face
+ * whose first edge or area, formed in double from the float positions, is zero or not finite, or -1; MPM_ERR_INVALID if
+ * there is one, if an index is out of range or if a coordinate is not finite. */
+MPM_API int mpm_rest_shape_check(const float *rest_pos, size_t n_verts, const int32_t *indices, size_t n_faces, int32_t *first_bad_face_out);
+
 /* ---- Links between cloth vertices: seams, springs and tension-only cords (an extension) ----
  * Every mpm_add_qr_cloth* call makes an island; pins are hard constraints to rigid bodies only.  A link joins two
  * distinct cloth vertices a, b -- of one cloth or of two -- by a damped spring: panels sewn into a garment, a sheet laced
