@@ -953,6 +953,24 @@ class GpuMpm:
         if rc != 0:
             raise MpmError(rc, (self.lib.mpm_last_error() or b"").decode())
 
+    def _table(self, fn, dtype, row=()):
+        """The two-call getter of a table: the count, then an array of that many `dtype` records (each of shape `row`)."""
+        n = C.c_size_t()
+        self._ck(fn(self.h, None, 0, C.byref(n)))
+        out = np.zeros((int(n.value),) + row, dtype)
+        self._ck(fn(self.h, _ptr(out) if out.size else None, len(out), C.byref(n)))
+        return out
+
+    def _max_stable_dt(self, fn) -> float:
+        dt = C.c_float()
+        self._ck(fn(self.h, C.byref(dt)))
+        return float(dt.value)
+
+    def _vertex_forces(self, fn):
+        out = np.zeros((self.n_verts, 3), np.float32)
+        self._ck(fn(self.h, _ptr(out)))
+        return out
+
     @staticmethod
     def default_material() -> Material:
         m = Material()
@@ -1077,23 +1095,15 @@ class GpuMpm:
 
     def get_bending(self):
         """mpm_get_bending: the stiffness in force, one float32 per cloth (zeros while off)."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_bending(self.h, None, 0, C.byref(n)))
-        out = np.zeros(int(n.value), np.float32)
-        self._ck(self.lib.mpm_get_bending(self.h, _ptr(out) if out.size else None, out.size, C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_get_bending, np.float32)
 
     def bending_forces(self):
         """mpm_bending_forces: -k Q x on the current positions, (n_verts, 3) float32 in dump_cpu_state's numbering."""
-        out = np.zeros((self.n_verts, 3), np.float32)
-        self._ck(self.lib.mpm_bending_forces(self.h, _ptr(out)))
-        return out
+        return self._vertex_forces(self.lib.mpm_bending_forces)
 
     def bending_max_stable_dt(self) -> float:
         """mpm_bending_max_stable_dt: the dt above which the substep entry points refuse (inf while bending is off)."""
-        dt = C.c_float()
-        self._ck(self.lib.mpm_bending_max_stable_dt(self.h, C.byref(dt)))
-        return float(dt.value)
+        return self._max_stable_dt(self.lib.mpm_bending_max_stable_dt)
 
     def set_damping(self, damping):
         """mpm_set_damping: (beta_membrane, beta_bending) in seconds for every cloth, in cloth order -- stiffness-
@@ -1104,24 +1114,16 @@ class GpuMpm:
 
     def get_damping(self):
         """mpm_get_damping: the coefficients in force, (n_cloths, 2) float32 (zeros while off)."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_damping(self.h, None, 0, C.byref(n)))
-        out = np.zeros((int(n.value), 2), np.float32)
-        self._ck(self.lib.mpm_get_damping(self.h, _ptr(out) if out.size else None, len(out), C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_get_damping, np.float32, (2,))
 
     def damping_forces(self):
         """mpm_damping_forces: the membrane + bending damping force on the current positions and velocities, (n_verts, 3)
         float32 in dump_cpu_state's numbering."""
-        out = np.zeros((self.n_verts, 3), np.float32)
-        self._ck(self.lib.mpm_damping_forces(self.h, _ptr(out)))
-        return out
+        return self._vertex_forces(self.lib.mpm_damping_forces)
 
     def damping_max_stable_dt(self) -> float:
         """mpm_damping_max_stable_dt: the dt above which the substep entry points refuse (inf while damping is off)."""
-        dt = C.c_float()
-        self._ck(self.lib.mpm_damping_max_stable_dt(self.h, C.byref(dt)))
-        return float(dt.value)
+        return self._max_stable_dt(self.lib.mpm_damping_max_stable_dt)
 
     @staticmethod
     def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
@@ -1147,11 +1149,7 @@ class GpuMpm:
 
     def get_weave(self):
         """mpm_get_weave: the constants in force, (n_cloths,) WEAVE_DTYPE (zeros while off)."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_weave(self.h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, WEAVE_DTYPE)
-        self._ck(self.lib.mpm_get_weave(self.h, out.ctypes.data if out.size else None, len(out), C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_get_weave, WEAVE_DTYPE)
 
     def weave_axes(self):
         """mpm_weave_axes: (c, s) per face, (n_faces, 2) float32 in original face order; (0, 0) where off."""
@@ -1183,9 +1181,7 @@ class GpuMpm:
 
     def weave_max_stable_dt(self) -> float:
         """mpm_weave_max_stable_dt: the dt above which the substep entry points refuse (inf while the weave is off)."""
-        dt = C.c_float()
-        self._ck(self.lib.mpm_weave_max_stable_dt(self.h, C.byref(dt)))
-        return float(dt.value)
+        return self._max_stable_dt(self.lib.mpm_weave_max_stable_dt)
 
     @staticmethod
     def weave_face_records(dminv3, vol, coef4, cs2, x):
@@ -1204,11 +1200,7 @@ class GpuMpm:
 
     def get_tearing(self):
         """mpm_get_tearing: the stretch limits in force, (n_cloths,) float32 (zeros while off)."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_tearing(self.h, None, 0, C.byref(n)))
-        out = np.zeros(n.value, TEAR_DTYPE)
-        self._ck(self.lib.mpm_get_tearing(self.h, out.ctypes.data if out.size else None, len(out), C.byref(n)))
-        return out["stretch_limit"].copy()
+        return self._table(self.lib.mpm_get_tearing, TEAR_DTYPE)["stretch_limit"].copy()
 
     def set_torn_faces(self, torn):
         """mpm_set_torn_faces: scissors / restore -- (n_faces,) flags in original face order replace every flag (non-zero:
@@ -1273,18 +1265,12 @@ class GpuMpm:
 
     def get_links(self):
         """mpm_get_links: the table in force, an array of LINK_DTYPE."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_links(self.h, None, 0, C.byref(n)))
-        out = np.zeros(int(n.value), LINK_DTYPE)
-        self._ck(self.lib.mpm_get_links(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_get_links, LINK_DTYPE)
 
     def link_forces(self):
         """mpm_link_forces: the links' force on the current positions and velocities, (n_verts, 3) float32 in
         dump_cpu_state's numbering (zeros for vertices without a link)."""
-        out = np.zeros((self.n_verts, 3), np.float32)
-        self._ck(self.lib.mpm_link_forces(self.h, _ptr(out)))
-        return out
+        return self._vertex_forces(self.lib.mpm_link_forces)
 
     def link_energy(self):
         """mpm_link_energy: (sum of 1/2 k (l - L)^2 over the links that act, every link's float length (n,) float32)."""
@@ -1297,9 +1283,7 @@ class GpuMpm:
 
     def links_max_stable_dt(self) -> float:
         """mpm_links_max_stable_dt: the dt above which the substep entry points refuse (inf while no link is set)."""
-        dt = C.c_float()
-        self._ck(self.lib.mpm_links_max_stable_dt(self.h, C.byref(dt)))
-        return float(dt.value)
+        return self._max_stable_dt(self.lib.mpm_links_max_stable_dt)
 
     @staticmethod
     def link_force(link, xa, xb, va, vb):
@@ -1319,11 +1303,7 @@ class GpuMpm:
 
     def get_link_limits(self):
         """mpm_get_link_limits: the break lengths in force, (n_links,) float32 (zeros while off)."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_link_limits(self.h, None, 0, C.byref(n)))
-        out = np.zeros(int(n.value), np.float32)
-        self._ck(self.lib.mpm_get_link_limits(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_get_link_limits, np.float32)
 
     def set_broken_links(self, broken):
         """mpm_set_broken_links: scissors / restore -- (n_links,) flags in link order replace every flag (non-zero:
@@ -1358,27 +1338,17 @@ class GpuMpm:
 
     def get_pressure(self):
         """mpm_get_pressure: the table in force, one PRESSURE_DTYPE record per cloth (zeros while off)."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_pressure(self.h, None, 0, C.byref(n)))
-        out = np.zeros(int(n.value), PRESSURE_DTYPE)
-        self._ck(self.lib.mpm_get_pressure(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_get_pressure, PRESSURE_DTYPE)
 
     def pressure_forces(self):
         """mpm_pressure_forces: the pressure force on the current positions, (n_verts, 3) float32 in dump_cpu_state's
         numbering; V and g are formed anew."""
-        out = np.zeros((self.n_verts, 3), np.float32)
-        self._ck(self.lib.mpm_pressure_forces(self.h, _ptr(out)))
-        return out
+        return self._vertex_forces(self.lib.mpm_pressure_forces)
 
     def pressure_state(self):
         """mpm_pressure_state: one PRESSURE_STATE_DTYPE record per cloth (volume, energy, gauge, capped) on the current
         positions; the volume of every cloth, pressurised or not."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_pressure_state(self.h, None, 0, C.byref(n)))
-        out = np.zeros(int(n.value), PRESSURE_STATE_DTYPE)
-        self._ck(self.lib.mpm_pressure_state(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_pressure_state, PRESSURE_STATE_DTYPE)
 
     @staticmethod
     def mesh_is_closed(indices, n_verts):
@@ -1407,11 +1377,7 @@ class GpuMpm:
 
     def get_shell_bending(self):
         """mpm_get_shell_bending: the table in force, one SHELL_DTYPE record per cloth (zeros while off)."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_shell_bending(self.h, None, 0, C.byref(n)))
-        out = np.zeros(int(n.value), SHELL_DTYPE)
-        self._ck(self.lib.mpm_get_shell_bending(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_get_shell_bending, SHELL_DTYPE)
 
     def shell_hinges(self):
         """mpm_shell_hinges: the hinge table in force -- (ids (n, 4) int32 vertex ids x0, x1 | x2, x3 in dump_cpu_state's
@@ -1427,9 +1393,7 @@ class GpuMpm:
     def shell_forces(self):
         """mpm_shell_forces: the shell bending force on the current positions, (n_verts, 3) float32 in dump_cpu_state's
         numbering."""
-        out = np.zeros((self.n_verts, 3), np.float32)
-        self._ck(self.lib.mpm_shell_forces(self.h, _ptr(out)))
-        return out
+        return self._vertex_forces(self.lib.mpm_shell_forces)
 
     def shell_state(self):
         """mpm_shell_state: (energy per cloth (n_cloths,) float64, psi per hinge (n,) float32, the number of inactive
@@ -1443,9 +1407,7 @@ class GpuMpm:
 
     def shell_max_stable_dt(self) -> float:
         """mpm_shell_max_stable_dt: the dt above which the substep entry points refuse (inf while shell bending is off)."""
-        dt = C.c_float()
-        self._ck(self.lib.mpm_shell_max_stable_dt(self.h, C.byref(dt)))
-        return float(dt.value)
+        return self._max_stable_dt(self.lib.mpm_shell_max_stable_dt)
 
     @staticmethod
     def mesh_hinges(indices, n_verts):
@@ -1713,18 +1675,12 @@ class GpuMpm:
 
     def get_anchors(self):
         """mpm_get_anchors: the table in force, an array of ANCHOR_DTYPE."""
-        n = C.c_size_t()
-        self._ck(self.lib.mpm_get_anchors(self.h, None, 0, C.byref(n)))
-        out = np.zeros(int(n.value), ANCHOR_DTYPE)
-        self._ck(self.lib.mpm_get_anchors(self.h, out.ctypes.data if out.size else None, out.size, C.byref(n)))
-        return out
+        return self._table(self.lib.mpm_get_anchors, ANCHOR_DTYPE)
 
     def anchor_forces(self):
         """mpm_anchor_forces: the anchors' force on the current state at the bodies' current clocks, (n_verts, 3) float32
         in dump_cpu_state's numbering (zeros for vertices without an anchor); adds no impulse."""
-        out = np.zeros((self.n_verts, 3), np.float32)
-        self._ck(self.lib.mpm_anchor_forces(self.h, _ptr(out)))
-        return out
+        return self._vertex_forces(self.lib.mpm_anchor_forces)
 
     def anchor_state(self):
         """mpm_anchor_state: dict(energy: sum of 1/2 k (l - L)^2 over the anchors that act, length (n,) float32,
@@ -1740,9 +1696,7 @@ class GpuMpm:
 
     def anchors_max_stable_dt(self) -> float:
         """mpm_anchors_max_stable_dt: the dt above which the substep entry points refuse (inf while no anchor is set)."""
-        dt = C.c_float()
-        self._ck(self.lib.mpm_anchors_max_stable_dt(self.h, C.byref(dt)))
-        return float(dt.value)
+        return self._max_stable_dt(self.lib.mpm_anchors_max_stable_dt)
 
     anchor_point = staticmethod(anchor_point)
 

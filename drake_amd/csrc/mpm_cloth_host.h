@@ -1014,11 +1014,11 @@ static int tear_counts(mpm_engine* e, std::vector<uint32_t>& n) {
     return 0;
 }
 // the feature of cloth c that does not compose with tearing (hinges across a torn face, a hole in a pressurised cloth:
-// out of scope), or null
+// out of scope), or null; of several the first in the order of mpm_features.h
 static const char* tear_conflict(const mpm_engine* e, size_t c) {
-    if (c < e->bend.k.size() && e->bend.k[c] > 0.f) return "bending stiffness (mpm_set_bending)";
-    if (c < e->shell.set.size() && e->shell.set[c].stiffness > 0.f) return "shell bending (mpm_set_shell_bending)";
-    if (c < e->pressure.set.size() && e->pressure.set[c].mode != MPM_PRESSURE_OFF) return "pressure (mpm_set_pressure)";
+    if (c < e->bend.k.size() && e->bend.k[c] > 0.f) return FEATURES[F_BENDING].phrase;
+    if (c < e->pressure.set.size() && e->pressure.set[c].mode != MPM_PRESSURE_OFF) return FEATURES[F_PRESSURE].phrase;
+    if (c < e->shell.set.size() && e->shell.set[c].stiffness > 0.f) return FEATURES[F_SHELL].phrase;
     return nullptr;
 }
 // mpm_set_bending, mpm_set_shell_bending, mpm_set_pressure: refused for a cloth c with wants(c) that has a tear limit or
@@ -1201,32 +1201,14 @@ static int rest_shape_check(const float* rest_pos, size_t n_verts, const int32_t
     for (size_t i = 0; i < 3 * n_verts; ++i) REQUIRE(std::isfinite(rest_pos[i]), "rest shape: a coordinate is not finite");
     return 0;
 }
-// The table in force (or null) whose host side caches something derived from the rest positions, Dm^-1, the volumes or
-// the masses: mpm_set_rest_shape is refused while it is; the caller clears it, sets the rest shape and sets it again.
-//   bending        cotangent weights of h_rest; limit from the masses      shell bending  cbar, psibar, the guard's masses
-//   damping        Dm^-1, volumes and masses of its Gershgorin sums        the weave      axes from h_rest; Dm^-1, volumes, masses
-//   pressure       winding checked against the rest volume                 links          limit from the masses
-//   anchors        limit from the masses                                   pins           the bodies' impulse sums accumulate in
-//                                                                                         the scale set_fixed_point_scales derives
-//                                                                                         from the total mass
-// Materials, force fields, tear limits and flags, grid colliders and bodies and contact materials hold nothing of the kind.
-static const char* rest_shape_conflict(const mpm_engine* e) {
-    if (e->bend.on()) return "bending stiffness (mpm_set_bending)";
-    if (e->shell.on()) return "shell bending (mpm_set_shell_bending)";
-    if (e->weave.on()) return "a weave (mpm_set_weave)";
-    if (e->damp.any()) return "damping (mpm_set_damping)";
-    if (e->pressure.on()) return "pressure (mpm_set_pressure)";
-    if (e->links.on()) return "links (mpm_set_links)";
-    if (e->anchors.on()) return "anchors (mpm_set_anchors)";
-    if (!e->pin.set.empty()) return "pins (mpm_set_pins)";
-    return nullptr;
-}
 // mpm_set_rest_shape: the checks on the host in double, the owed substeps, then k_rest_faces and k_rest_vertices on the
 // current particle order and the fixed-point scales from the new masses.  rest_pos null: the positions as added.  A
 // refusal enqueues nothing: the rest state in force stays.
 static int set_rest_shape(mpm_engine* e, const float* rest_pos) {
-    if (const char* other = rest_shape_conflict(e))
-        return fail(MPM_ERR_INVALID, std::string("mpm_set_rest_shape: the engine has ") + other +
+    // (a table in force whose host side caches something derived from the rest positions, Dm^-1, the volumes or the masses --
+    // FeatureRow::caches_rest, mpm_features.h: the caller clears it, sets the rest shape and sets it again)
+    if (const Feature other = rest_shape_blocker(feature_state(e)); other != F_NONE)
+        return fail(MPM_ERR_INVALID, std::string("mpm_set_rest_shape: the engine has ") + FEATURES[other].phrase +
                                          ", which holds values derived from the rest shape: clear it, set the rest shape, set it again");
     const float* R = rest_pos ? rest_pos : e->h_pos.data();
     for (size_t i = 0; i < 3 * e->nv; ++i) REQUIRE(std::isfinite(R[i]), "mpm_set_rest_shape: a coordinate is not finite");

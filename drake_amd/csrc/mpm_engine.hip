@@ -276,12 +276,9 @@ static void launch_p2g(mpm_engine* e, const DP& p, float dt, int forces = 0) {
 #undef MPM_P2G_LAUNCH
 }
 // the vertex forces inside k_p2g, from the vertices' entries of DP::VF (single and partitioned domains alike since round
-// 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch, and so does an engine with bending
-// stiffness, links, pressure, shell bending or anchors, whose k_bend, k_link, k_pressure, k_hinge_gather and k_anchor add to
-// the forces in DP::f
-static int fused_forces(const mpm_engine* e) {
-    return e->max_valence <= 8 && !e->bend.on() && !e->links.on() && !e->pressure.on() && !e->shell.on() && !e->anchors.on() ? 1 : 0;
-}
+// 5); a mesh with a vertex of more than eight faces keeps the k_vforce launch, and so does an engine with a feature whose
+// kernel adds to the forces in DP::f (FeatureRow::adds_to_f, mpm_features.h)
+static int fused_forces(const mpm_engine* e) { return forces_fusable(feature_state(e), e->max_valence) ? 1 : 0; }
 // the pins behind GridToParticle (k_pin, mpm_pins.h); only an engine with pins or anchors launches it (pins_ready has
 // resolved the table).  An engine with anchors and no pins launches it with zero pins and one workgroup: its tail
 // advances the bodies' clocks.  Everything after GridToParticle -- the coupled path's watch kernel included -- comes
@@ -771,81 +768,38 @@ int mpm_sync(mpm_handle_t e) try {
     return 0;
 } MPM_CATCH_ALL
 
-// partitioned and multi-rank engines have no pins, no per-cloth materials, no grid bodies, no force fields, no bending
-// stiffness, no damping, no weave, no tearing, no links, no pressure, no shell bending and no anchors (out of scope).
+// partitioned and multi-rank engines take none of the features of mpm_features.h (FeatureRow::partitioned; out of scope).
 // set_up: the call partitions the engine or joins it to other ranks (mpm_dist_init, chain, team, world), which an engine
 // with a rest shape of its own refuses too; the halo substeps of a single engine run on whatever rest state it holds.
 static int extensions_refused(const mpm_engine* e, const char* what, bool set_up = true) {
-    if (!e->pin.set.empty()) return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pins (mpm_set_pins)");
-    if (e->multi_mat)
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on a multi-material engine (mpm_add_qr_cloth_with_material)");
-    if (!e->grid_bodies.empty())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with grid bodies (mpm_set_grid_bodies)");
-    if (!e->force_fields.empty())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with force fields (mpm_set_force_fields)");
-    if (e->bend.on())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with bending stiffness (mpm_set_bending)");
-    if (e->damp.any())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with damping (mpm_set_damping)");
-    if (e->weave.on())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with a weave (mpm_set_weave)");
-    if (e->tear.on())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with tearing (mpm_set_tearing, mpm_set_torn_faces)");
-    if (e->links.on())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with links (mpm_set_links)");
-    if (e->pressure.on())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with pressure (mpm_set_pressure)");
-    if (e->shell.on())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with shell bending (mpm_set_shell_bending)");
-    if (e->anchors.on())
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with anchors (mpm_set_anchors)");
-    if (set_up && e->rest_set)
-        return fail(MPM_ERR_INVALID, std::string(what) + ": not available on an engine with a rest shape of its own (mpm_set_rest_shape; null restores the positions as added)");
-    return 0;
-}
-// the refusal of a dt above a feature's mpm_<feature>_max_stable_dt (fields_stable)
-static int dt_above_limit(float dt, float max_dt, const char* feature, const char* force, const char* reduce) {
-    char msg[200];
-    std::snprintf(msg, sizeof msg, "%s: dt = %g is above the limit mpm_%s_max_stable_dt = %g: the explicit %s force is unstable -- "
-                  "reduce %s", feature, (double)dt, feature, (double)max_dt, force, reduce);
-    return fail(MPM_ERR_INVALID, msg);
+    const Feature f = partition_blocker(feature_state(e), set_up);
+    if (f == F_NONE) return 0;
+    const FeatureRow& r = FEATURES[f];
+    return fail(MPM_ERR_INVALID, std::string(what) + ": not available on " + (r.on_tail ? r.on_tail : std::string("an engine with ") + r.phrase));
 }
 // An explicit linear drag beyond dt * gamma = 1 reverses the relative velocity: the substep entry points that take a dt
 // refuse it, once per call, before anything is enqueued.  (An engine without a table never gets past the first test.)
-// The same entry points refuse a dt above mpm_bending_max_stable_dt on an engine with bending stiffness: symplectic Euler
-// on the lumped system needs dt * omega <= 2, with Gershgorin's bound on omega^2 (a guard, not a guarantee).  And a dt
-// above mpm_damping_max_stable_dt on an engine with damping: the explicit viscous force needs dt * rho(M^-1 D) <= 2.  And
-// a dt above mpm_links_max_stable_dt on an engine with links: W dt^2 + 2 G dt <= 4 (mpm_links.h; a guard, not a guarantee).
-// And a dt above mpm_shell_max_stable_dt on an engine with shell bending (mpm_shell.h; a guard at the rest shape).  And a dt
-// above mpm_anchors_max_stable_dt on an engine with anchors (mpm_anchors.h; a guard of its own: a vertex with links and
-// anchors passes each on its own).  And a dt above mpm_weave_max_stable_dt on an engine with a weave (mpm_weave.h; a
-// guard at the rest shape).
+// The same entry points refuse a dt above mpm_<guard>_max_stable_dt of a feature in force that has a guard (the rows of
+// mpm_features.h; each guard is explained in its feature's header): of several, the last in table order.
 static int fields_stable(const mpm_engine* e, float dt) {
-    if (e->anchors.on() && !(dt <= e->anchors.max_dt))
-        return dt_above_limit(dt, e->anchors.max_dt, "anchors", "anchor", "dt, the stiffness or the damping");
-    if (e->shell.on() && !(dt <= e->shell.max_dt))
-        return dt_above_limit(dt, e->shell.max_dt, "shell", "shell bending", "dt or the stiffness");
-    if (e->links.on() && !(dt <= e->links.max_dt))
-        return dt_above_limit(dt, e->links.max_dt, "links", "link", "dt, the stiffness or the damping");
-    if (e->weave.on() && !(dt <= e->weave.max_dt)) return dt_above_limit(dt, e->weave.max_dt, "weave", "weave", "dt or the moduli");
-    if (e->damp.any() && !(dt <= e->damp.max_dt)) return dt_above_limit(dt, e->damp.max_dt, "damping", "damping", "dt or the coefficients");
-    if (e->bend.on() && !(dt <= e->bend.max_dt)) return dt_above_limit(dt, e->bend.max_dt, "bending", "bending", "dt or the stiffness");
-    if (e->force_fields.empty()) return 0;
+    const FeatureState s = feature_state(e);
+    const Feature f = violated_guard(s, dt);
+    if (f != F_NONE) {
+        const FeatureRow& r = FEATURES[f];
+        char msg[200];
+        std::snprintf(msg, sizeof msg, "%s: dt = %g is above the limit mpm_%s_max_stable_dt = %g: the explicit %s force is unstable -- "
+                      "reduce %s", r.guard, (double)dt, r.guard, (double)s.max_dt[f], r.force, r.reduce);
+        return fail(MPM_ERR_INVALID, msg);
+    }
+    if (!s.on[F_FORCE_FIELDS]) return 0;
     if (!((double)dt * e->force_fields_gamma <= 1.0))
         return fail(MPM_ERR_INVALID, "force fields: dt * (sum of gamma over the linear drag fields) = " +
                                          std::to_string((double)dt * e->force_fields_gamma) + " > 1: the explicit drag is unstable -- reduce dt or gamma");
     return 0;
 }
-// The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: with a table of force fields the host
-// takes it as 0, i.e. every batch starts with its re-sort check launches.  The same while bending stiffness, damping,
-// the weave, tearing, links, pressure, shell bending or anchors are set.
-static float quiet_hint(const mpm_engine* e, float seconds) {
-    return e->force_fields.empty() && !e->bend.on() && !e->damp.any() && !e->weave.on() && !e->tear.on() && !e->links.on() && !e->pressure.on() &&
-                   !e->shell.on() &&
-                   !e->anchors.on()
-               ? seconds
-               : 0.f;
-}
+// The quiet-time hint of the re-sort (Ctl::quiet_time) assumes gravity alone: while a feature that moves the cloth otherwise
+// is in force (FeatureRow::ends_quiet_hint) the host takes it as 0, i.e. every batch starts with its re-sort check launches.
+static float quiet_hint(const mpm_engine* e, float seconds) { return quiet_hint_holds(feature_state(e)) ? seconds : 0.f; }
 
 // ---- the solver calls -----------------------------------------------------
 static void launch_substep(mpm_engine* e, float dt, const GridColliders& gc, bool allow_gate, bool lean = false);
@@ -2190,17 +2144,36 @@ int mpm_newton_bisect_f32(mpm_rootfind_fn fn, void* user, float x_lo, float x_hi
     return newton_bisect(fn, user, x_lo, x_hi, guess, x_tol, f_tol, max_evals, flags, root_out, evals_out);
 } MPM_CATCH_ALL
 
+// ---- what the features' entry points share ----------------------------------------------------------------------------------
+// the preamble of a setter with one record per cloth: a finalized single engine, and a table of mpm_cloth_count records
+// (zero_is_off: or none at all)
+static int per_cloth_setter(mpm_engine* e, Feature f, const char* call, size_t n_cloths, const void* table, const char* null_table,
+                            bool zero_is_off = true) {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, FEATURES[f].what_is)) return rc;
+    REQUIRE((zero_is_off && n_cloths == 0) || n_cloths == e->cloths.size(),
+            std::string(call) + ": n_cloths must be mpm_cloth_count" + (zero_is_off ? " (or 0: off)" : ""));
+    REQUIRE(n_cloths == 0 || table, null_table);
+    return 0;
+}
+// mpm_<guard>_max_stable_dt: the guard's limit while the feature is in force, +inf otherwise
+static int max_stable_dt_out(const mpm_engine* e, Feature f, float* dt_out) {
+    REQUIRE(e && dt_out, "null argument");
+    *dt_out = max_stable_dt(feature_state(e), f);
+    return 0;
+}
+
 // ---- fixed constraints (mpm_bodies_host.h) --------------------------------------------------------------------------------
 int mpm_set_pins(mpm_handle_t e, size_t n, const mpm_pin_t* pins) try {
     READY(e);
-    if (int rc = single_engine_only(e, "pins are")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_PINS].what_is)) return rc;
     REQUIRE(n == 0 || pins, "null pin array");
     return set_pins(e, n, pins);
 } MPM_CATCH_ALL
 
 int mpm_set_body_motions(mpm_handle_t e, size_t n, const mpm_body_motion_t* m) try {
     READY(e);
-    if (int rc = single_engine_only(e, "pins are")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_PINS].what_is)) return rc;
     REQUIRE(n == 0 || m, "null motion array");
     return set_body_motions(e, n, m);
 } MPM_CATCH_ALL
@@ -2208,7 +2181,7 @@ int mpm_set_body_motions(mpm_handle_t e, size_t n, const mpm_body_motion_t* m) t
 int mpm_pins_inside_collider(mpm_handle_t e, const mpm_collider_t* shape, uint32_t body, const float p_WB[3],
                              const float R_WB[9], size_t* n_added) try {
     READY(e);
-    if (int rc = single_engine_only(e, "pins are")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_PINS].what_is)) return rc;
     REQUIRE(shape && p_WB && R_WB, "null argument");
     return pins_inside_collider(e, shape, body, p_WB, R_WB, n_added);
 } MPM_CATCH_ALL
@@ -2222,7 +2195,7 @@ int mpm_get_pins(mpm_handle_t e, mpm_pin_t* out, size_t capacity, size_t* n_out)
 // ---- anchors: springs and cords from cloth vertices to rigid bodies (mpm_bodies_host.h; mpm_anchors.h) ------------------------
 int mpm_set_anchors(mpm_handle_t e, size_t n, const mpm_anchor_t* anchors) try {
     READY(e);
-    if (int rc = single_engine_only(e, "anchors are")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_ANCHORS].what_is)) return rc;
     REQUIRE(n == 0 || anchors, "null anchor array");
     return set_anchors(e, n, anchors);
 } MPM_CATCH_ALL
@@ -2245,9 +2218,7 @@ int mpm_anchor_state(mpm_handle_t e, double* energy_out, float* length_out, floa
 } MPM_CATCH_ALL
 
 int mpm_anchors_max_stable_dt(mpm_handle_t e, float* dt_out) try {
-    REQUIRE(e && dt_out, "null argument");
-    *dt_out = e->anchors.on() ? e->anchors.max_dt : INFINITY;
-    return 0;
+    return max_stable_dt_out(e, F_ANCHORS, dt_out);
 } MPM_CATCH_ALL
 
 int mpm_anchor_point(const mpm_body_motion_t* motion, double t, const float* p_BQ, float* y, float* v_Q) try {
@@ -2260,7 +2231,7 @@ int mpm_anchor_point(const mpm_body_motion_t* motion, double t, const float* p_B
 int mpm_set_grid_bodies(mpm_handle_t e, size_t n, const mpm_grid_body_t* bodies) try {
     static_assert(sizeof(Collider) == sizeof(mpm_collider_t), "collider layouts differ");
     READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "grid bodies are")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_GRID_BODIES].what_is)) return rc;
     REQUIRE(n <= (size_t)MAX_GRID_COLLIDERS, "too many grid bodies (at most 16)");
     REQUIRE(n == 0 || bodies, "null grid body array");
     return set_grid_bodies(e, n, bodies);
@@ -2275,7 +2246,7 @@ int mpm_get_grid_bodies(mpm_handle_t e, mpm_grid_body_t* out, size_t capacity, s
 // ---- external force fields (mpm_cloth_host.h; mpm_fields.h) -----------------------------------------------------------------
 int mpm_set_force_fields(mpm_handle_t e, size_t n, const mpm_force_field_t* fields) try {
     READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "force fields are")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_FORCE_FIELDS].what_is)) return rc;
     if (int rc = validate_force_fields(n, fields)) return rc;
     return set_force_fields(e, n, fields);
 } MPM_CATCH_ALL
@@ -2305,20 +2276,14 @@ int mpm_bending_matrix(const float* pos, size_t n_verts, const int32_t* indices,
 } MPM_CATCH_ALL
 
 int mpm_set_bending(mpm_handle_t e, size_t n_cloths, const float* stiffness) try {
-    READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "bending stiffness is")) return rc;
-    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_bending: n_cloths must be mpm_cloth_count (or 0: off)");
-    REQUIRE(n_cloths == 0 || stiffness, "null stiffness array");
+    if (int rc = per_cloth_setter(e, F_BENDING, "mpm_set_bending", n_cloths, stiffness, "null stiffness array")) return rc;
     if (int rc = tear_refuses(e, n_cloths, "mpm_set_bending", [&](size_t c) { return stiffness[c] > 0.f; })) return rc;
     return set_bending(e, n_cloths, stiffness);
 } MPM_CATCH_ALL
 
 int mpm_get_bending(mpm_handle_t e, float* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
-    REQUIRE(out || capacity == 0, "null output");
-    std::vector<float> k = e->bend.k;   // (one entry per cloth; 0 where nothing was set)
-    k.resize(e->cloths.size(), 0.f);
-    return copy_out(k, out, capacity, n_out);
+    return padded_out(e->bend.k, e->cloths.size(), 0.f, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_bending_forces(mpm_handle_t e, float* f_out) try {
@@ -2328,17 +2293,12 @@ int mpm_bending_forces(mpm_handle_t e, float* f_out) try {
 } MPM_CATCH_ALL
 
 int mpm_bending_max_stable_dt(mpm_handle_t e, float* dt_out) try {
-    REQUIRE(e && dt_out, "null argument");
-    *dt_out = e->bend.on() ? e->bend.max_dt : INFINITY;
-    return 0;
+    return max_stable_dt_out(e, F_BENDING, dt_out);
 } MPM_CATCH_ALL
 
 // ---- stiffness-proportional damping (mpm_cloth_host.h; mpm_damping.h) ------------------------------------------------------
 int mpm_set_damping(mpm_handle_t e, size_t n_cloths, const mpm_cloth_damping_t* d) try {
-    READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "damping is")) return rc;
-    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_damping: n_cloths must be mpm_cloth_count (or 0: off)");
-    REQUIRE(n_cloths == 0 || d, "null damping array");
+    if (int rc = per_cloth_setter(e, F_DAMPING, "mpm_set_damping", n_cloths, d, "null damping array")) return rc;
     for (size_t c = 0; c < n_cloths; ++c)
         REQUIRE(std::isfinite(d[c].membrane) && d[c].membrane >= 0.f && std::isfinite(d[c].bending) && d[c].bending >= 0.f,
                 "damping: a coefficient is negative or not finite");
@@ -2349,10 +2309,7 @@ int mpm_set_damping(mpm_handle_t e, size_t n_cloths, const mpm_cloth_damping_t* 
 
 int mpm_get_damping(mpm_handle_t e, mpm_cloth_damping_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
-    REQUIRE(out || capacity == 0, "null output");
-    std::vector<mpm_cloth_damping_t> d = e->damp.d;   // (one entry per cloth; zeros where nothing was set)
-    d.resize(e->cloths.size(), mpm_cloth_damping_t{0.f, 0.f});
-    return copy_out(d, out, capacity, n_out);
+    return padded_out(e->damp.d, e->cloths.size(), mpm_cloth_damping_t{0.f, 0.f}, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_damping_forces(mpm_handle_t e, float* f_out) try {
@@ -2362,9 +2319,7 @@ int mpm_damping_forces(mpm_handle_t e, float* f_out) try {
 } MPM_CATCH_ALL
 
 int mpm_damping_max_stable_dt(mpm_handle_t e, float* dt_out) try {
-    REQUIRE(e && dt_out, "null argument");
-    *dt_out = e->damp.any() ? e->damp.max_dt : INFINITY;
-    return 0;
+    return max_stable_dt_out(e, F_DAMPING, dt_out);
 } MPM_CATCH_ALL
 
 int mpm_damping_face_records(size_t n_faces, const float* dminv3, const float* vol, const float* mu, const float* lambda,
@@ -2375,10 +2330,7 @@ int mpm_damping_face_records(size_t n_faces, const float* dminv3, const float* v
 
 // ---- woven cloth (mpm_cloth_host.h; mpm_weave.h) ---------------------------------------------------------------------------
 int mpm_set_weave(mpm_handle_t e, size_t n_cloths, const mpm_cloth_weave_t* w, const float* face_dirs) try {
-    READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "the weave is")) return rc;
-    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_weave: n_cloths must be mpm_cloth_count (or 0: off)");
-    REQUIRE(n_cloths == 0 || w, "null weave array");
+    if (int rc = per_cloth_setter(e, F_WEAVE, "mpm_set_weave", n_cloths, w, "null weave array")) return rc;
     for (size_t c = 0; c < n_cloths; ++c) {
         float coef[4];
         REQUIRE(weave_coefficients(w[c].E_warp, w[c].E_weft, w[c].nu, w[c].G, coef),
@@ -2393,10 +2345,7 @@ int mpm_set_weave(mpm_handle_t e, size_t n_cloths, const mpm_cloth_weave_t* w, c
 
 int mpm_get_weave(mpm_handle_t e, mpm_cloth_weave_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
-    REQUIRE(out || capacity == 0, "null output");
-    std::vector<mpm_cloth_weave_t> w = e->weave.w;   // (one entry per cloth; zeros where nothing was set)
-    w.resize(e->cloths.size(), mpm_cloth_weave_t{0.f, 0.f, 0.f, 0.f, {0.f, 0.f, 0.f}});
-    return copy_out(w, out, capacity, n_out);
+    return padded_out(e->weave.w, e->cloths.size(), mpm_cloth_weave_t{0.f, 0.f, 0.f, 0.f, {0.f, 0.f, 0.f}}, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_weave_axes(mpm_handle_t e, float* cs_out) try {
@@ -2428,9 +2377,7 @@ int mpm_weave_energy(mpm_handle_t e, double* per_cloth, size_t capacity, size_t*
 } MPM_CATCH_ALL
 
 int mpm_weave_max_stable_dt(mpm_handle_t e, float* dt_out) try {
-    REQUIRE(e && dt_out, "null argument");
-    *dt_out = e->weave.on() ? e->weave.max_dt : INFINITY;
-    return 0;
+    return max_stable_dt_out(e, F_WEAVE, dt_out);
 } MPM_CATCH_ALL
 
 int mpm_weave_face_records(size_t n, const float* dminv3, const float* vol, const float* coef4, const float* cs2,
@@ -2447,10 +2394,7 @@ int mpm_weave_face_axes(size_t n, const float* rest_x9, const float* dir3, float
 
 // ---- tearing cloth (mpm_cloth_host.h; mpm_tear.h) ------------------------------------------------------------------------------
 int mpm_set_tearing(mpm_handle_t e, size_t n_cloths, const mpm_cloth_tear_t* t) try {
-    READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "tearing is")) return rc;
-    REQUIRE(n_cloths == e->cloths.size(), "mpm_set_tearing: n_cloths must be mpm_cloth_count");
-    REQUIRE(n_cloths == 0 || t, "null tearing array");
+    if (int rc = per_cloth_setter(e, F_TEARING, "mpm_set_tearing", n_cloths, t, "null tearing array", false)) return rc;
     for (size_t c = 0; c < n_cloths; ++c) {
         float L;
         REQUIRE(tear_limit(t[c].stretch_limit, &L), "tearing: a stretch_limit is neither 0 nor a finite number > 1");
@@ -2460,15 +2404,12 @@ int mpm_set_tearing(mpm_handle_t e, size_t n_cloths, const mpm_cloth_tear_t* t) 
 
 int mpm_get_tearing(mpm_handle_t e, mpm_cloth_tear_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
-    REQUIRE(out || capacity == 0, "null output");
-    std::vector<mpm_cloth_tear_t> t = e->tear.t;   // (one entry per cloth; zeros where nothing was set)
-    t.resize(e->cloths.size(), mpm_cloth_tear_t{0.f, {0.f, 0.f, 0.f}});
-    return copy_out(t, out, capacity, n_out);
+    return padded_out(e->tear.t, e->cloths.size(), mpm_cloth_tear_t{0.f, {0.f, 0.f, 0.f}}, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_set_torn_faces(mpm_handle_t e, const uint8_t* torn) try {
     READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "tearing is")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_TEARING].what_is)) return rc;
     REQUIRE(torn || e->nf == 0, "null flag array");
     return set_torn_faces(e, torn);
 } MPM_CATCH_ALL
@@ -2493,7 +2434,7 @@ int mpm_tear_face(size_t n, const float* dminv3, const float* x9, const float* L
 // ---- the rest shape apart from the pose (mpm_cloth_host.h; mpm_rest.h) ----------------------------------------------------------
 int mpm_set_rest_shape(mpm_handle_t e, const float* rest_pos) try {
     READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "a rest shape of its own is")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_REST_SHAPE].what_is)) return rc;
     return set_rest_shape(e, rest_pos);
 } MPM_CATCH_ALL
 
@@ -2514,7 +2455,7 @@ int mpm_rest_shape_check(const float* rest_pos, size_t n_verts, const int32_t* i
 // ---- links between cloth vertices (mpm_cloth_host.h; mpm_links.h) --------------------------------------------------------------
 int mpm_set_links(mpm_handle_t e, size_t n, const mpm_link_t* links) try {
     READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "links are")) return rc;
+    if (int rc = single_engine_only(e, FEATURES[F_LINKS].what_is)) return rc;
     REQUIRE(n == 0 || links, "null link array");
     return set_links(e, n, links);
 } MPM_CATCH_ALL
@@ -2538,9 +2479,7 @@ int mpm_link_energy(mpm_handle_t e, double* energy_out, float* length_out) try {
 } MPM_CATCH_ALL
 
 int mpm_links_max_stable_dt(mpm_handle_t e, float* dt_out) try {
-    REQUIRE(e && dt_out, "null argument");
-    *dt_out = e->links.on() ? e->links.max_dt : INFINITY;
-    return 0;
+    return max_stable_dt_out(e, F_LINKS, dt_out);
 } MPM_CATCH_ALL
 
 int mpm_link_force(const mpm_link_t* link, const float* xa, const float* xb, const float* va, const float* vb, float* f_on_a) try {
@@ -2566,10 +2505,7 @@ int mpm_set_link_limits(mpm_handle_t e, size_t n, const float* break_length) try
 
 int mpm_get_link_limits(mpm_handle_t e, float* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
-    REQUIRE(out || capacity == 0, "null output");
-    std::vector<float> b = e->links.limits;   // (one entry per link; zeros while off)
-    b.resize(e->links.set.size(), 0.f);
-    return copy_out(b, out, capacity, n_out);
+    return padded_out(e->links.limits, e->links.set.size(), 0.f, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_set_broken_links(mpm_handle_t e, size_t n, const uint8_t* broken) try {
@@ -2599,20 +2535,14 @@ int mpm_link_breaks(size_t n, const float* xa3, const float* xb3, const float* B
 
 // ---- enclosed-volume pressure per cloth (mpm_cloth_host.h; mpm_pressure.h) ------------------------------------------------------
 int mpm_set_pressure(mpm_handle_t e, size_t n_cloths, const mpm_cloth_pressure_t* per_cloth) try {
-    READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "pressure is")) return rc;
-    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_pressure: n_cloths must be mpm_cloth_count (or 0: off)");
-    REQUIRE(n_cloths == 0 || per_cloth, "null pressure array");
+    if (int rc = per_cloth_setter(e, F_PRESSURE, "mpm_set_pressure", n_cloths, per_cloth, "null pressure array")) return rc;
     if (int rc = tear_refuses(e, n_cloths, "mpm_set_pressure", [&](size_t c) { return per_cloth[c].mode != MPM_PRESSURE_OFF; })) return rc;
     return set_pressure(e, n_cloths, per_cloth);
 } MPM_CATCH_ALL
 
 int mpm_get_pressure(mpm_handle_t e, mpm_cloth_pressure_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
-    REQUIRE(out || capacity == 0, "null output");
-    std::vector<mpm_cloth_pressure_t> t = e->pressure.set;   // (one entry per cloth; zeros where nothing was set)
-    t.resize(e->cloths.size(), mpm_cloth_pressure_t{MPM_PRESSURE_OFF, 0.f, 0.f, 0.f, 0.f});
-    return copy_out(t, out, capacity, n_out);
+    return padded_out(e->pressure.set, e->cloths.size(), mpm_cloth_pressure_t{MPM_PRESSURE_OFF, 0.f, 0.f, 0.f, 0.f}, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_pressure_forces(mpm_handle_t e, float* f_out) try {
@@ -2649,20 +2579,14 @@ int mpm_pressure_vertex_force(float g, const float* x_own, size_t n, const float
 
 // ---- shell bending about a curved rest shape (mpm_cloth_host.h; mpm_shell.h) -------------------------------------------------------
 int mpm_set_shell_bending(mpm_handle_t e, size_t n_cloths, const mpm_cloth_shell_t* per_cloth, const float* rest_pos) try {
-    READY_NO_SETTLE(e);
-    if (int rc = single_engine_only(e, "shell bending is")) return rc;
-    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_shell_bending: n_cloths must be mpm_cloth_count (or 0: off)");
-    REQUIRE(n_cloths == 0 || per_cloth, "null shell bending array");
+    if (int rc = per_cloth_setter(e, F_SHELL, "mpm_set_shell_bending", n_cloths, per_cloth, "null shell bending array")) return rc;
     if (int rc = tear_refuses(e, n_cloths, "mpm_set_shell_bending", [&](size_t c) { return per_cloth[c].stiffness > 0.f; })) return rc;
     return set_shell_bending(e, n_cloths, per_cloth, rest_pos);
 } MPM_CATCH_ALL
 
 int mpm_get_shell_bending(mpm_handle_t e, mpm_cloth_shell_t* out, size_t capacity, size_t* n_out) try {
     REQUIRE(e, "null handle");
-    REQUIRE(out || capacity == 0, "null output");
-    std::vector<mpm_cloth_shell_t> t = e->shell.set;   // (one entry per cloth; zeros where nothing was set)
-    t.resize(e->cloths.size(), mpm_cloth_shell_t{0.f, MPM_SHELL_REST_SHAPE});
-    return copy_out(t, out, capacity, n_out);
+    return padded_out(e->shell.set, e->cloths.size(), mpm_cloth_shell_t{0.f, MPM_SHELL_REST_SHAPE}, out, capacity, n_out);
 } MPM_CATCH_ALL
 
 int mpm_shell_hinges(mpm_handle_t e, int32_t* ids4, float* kc, float* psibar, size_t capacity, size_t* n_out) try {
@@ -2690,9 +2614,7 @@ int mpm_shell_state(mpm_handle_t e, double* energy_per_cloth, float* psi_out, ui
 } MPM_CATCH_ALL
 
 int mpm_shell_max_stable_dt(mpm_handle_t e, float* dt_out) try {
-    REQUIRE(e && dt_out, "null argument");
-    *dt_out = e->shell.on() ? e->shell.max_dt : INFINITY;
-    return 0;
+    return max_stable_dt_out(e, F_SHELL, dt_out);
 } MPM_CATCH_ALL
 
 int mpm_mesh_hinges(const int32_t* indices, size_t n_faces, size_t n_verts, int32_t* ids4, size_t capacity, size_t* n_out) try {

@@ -16,6 +16,7 @@
 
 #include "../../include/mpm_hip.h"
 #include "mpm_device.h"
+#include "mpm_features.h"
 #include "mpm_rebuild.h"
 #include "mpm_step.h"
 #include "mpm_contact_dev.h"
@@ -536,6 +537,15 @@ static int copy_out(const std::vector<T>& set, T* out, size_t capacity, size_t* 
     return 0;
 }
 
+// The getters of a table with one record per cloth (or, the link limits, per link): `n` entries, `zero` where nothing was
+// set
+template <class T>
+static int padded_out(std::vector<T> set, size_t n, const T& zero, T* out, size_t capacity, size_t* n_out) {
+    REQUIRE(out || capacity == 0, "null output");
+    set.resize(n, zero);
+    return copy_out(set, out, capacity, n_out);
+}
+
 // ---- what the features' host headers need from mpm_engine.hip -------------------------------------------------------------
 // (mpm_cloth_host.h, mpm_bodies_host.h, mpm_dist_host.h, mpm_chain_host.h: included by mpm_engine.hip, which defines these)
 // the owed substeps and the held-back phase calls, run before a call looks at or changes the state
@@ -574,9 +584,27 @@ static bool is_rotation(const float* R) {
                        (double)R[2] * ((double)R[3] * R[7] - (double)R[4] * R[6]);
     return std::fabs(det - 1.0) <= 1e-4;
 }
-// pins, grid bodies, force fields, bending stiffness, damping, the weave, tearing, links, pressure and shell bending are refused on a partitioned or multi-rank
-// engine (out of scope);
-// what_is: "pins are", "bending stiffness is", ...
+// Which features are in force, for the lists of mpm_features.h.  The ONLY place outside a feature's own host code and the
+// launch helpers that decides whether a feature is in force: one line per feature.
+static FeatureState feature_state(const mpm_engine* e) {
+    FeatureState s;
+    s.on[F_PINS] = !e->pin.set.empty();
+    s.on[F_MATERIALS] = e->multi_mat;
+    s.on[F_GRID_BODIES] = !e->grid_bodies.empty();
+    s.on[F_FORCE_FIELDS] = !e->force_fields.empty();
+    s.on[F_BENDING] = e->bend.on(), s.max_dt[F_BENDING] = e->bend.max_dt;
+    s.on[F_DAMPING] = e->damp.any(), s.max_dt[F_DAMPING] = e->damp.max_dt;
+    s.on[F_WEAVE] = e->weave.on(), s.max_dt[F_WEAVE] = e->weave.max_dt;
+    s.on[F_TEARING] = e->tear.on();
+    s.on[F_LINKS] = e->links.on(), s.max_dt[F_LINKS] = e->links.max_dt;
+    s.on[F_PRESSURE] = e->pressure.on();
+    s.on[F_SHELL] = e->shell.on(), s.max_dt[F_SHELL] = e->shell.max_dt;
+    s.on[F_ANCHORS] = e->anchors.on(), s.max_dt[F_ANCHORS] = e->anchors.max_dt;
+    s.on[F_REST_SHAPE] = e->rest_set;
+    return s;
+}
+// every feature of mpm_features.h is refused on a partitioned or multi-rank engine (out of scope);
+// what_is: the feature's FeatureRow::what_is ("pins are", "bending stiffness is", ...), or a call's own ("mpm_tear_measure is")
 static int single_engine_only(const mpm_engine* e, const char* what_is) {
     if (e->dp.dist.on || e->chain.comm || e->chain.direct || e->team.on)
         return fail(MPM_ERR_INVALID, std::string(what_is) + " not available on a partitioned or multi-rank engine");

@@ -160,13 +160,7 @@ struct GpuMpmState {
         mpm_check(mpm_set_body_motions(h_, motions.size(), motions.data()));
     }
     void SetPins(const std::vector<mpm_pin_t>& pins) { mpm_check(mpm_set_pins(h_, pins.size(), pins.data())); }
-    std::vector<mpm_pin_t> GetPins() const {
-        size_t n = 0;
-        mpm_check(mpm_get_pins(h_, nullptr, 0, &n));
-        std::vector<mpm_pin_t> out(n);
-        mpm_check(mpm_get_pins(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_pin_t> GetPins() const { return table<mpm_pin_t>(mpm_get_pins); }
     // Extension: rigid bodies in UpdateGrid's boundary condition (mpm_set_grid_bodies).  The table that
     // UpdateGrid(state, MPM_BC_BODIES) and the substep calls with that mpm_bc use: once per plant step, from the body
     // poses and spatial velocities of CalcAbstractStates, before its substeps.  The bodies' reactions arrive in
@@ -174,71 +168,31 @@ struct GpuMpmState {
     void SetGridBodies(const std::vector<mpm_grid_body_t>& bodies) {
         mpm_check(mpm_set_grid_bodies(h_, bodies.size(), bodies.data()));
     }
-    std::vector<mpm_grid_body_t> GetGridBodies() const {
-        size_t n = 0;
-        mpm_check(mpm_get_grid_bodies(h_, nullptr, 0, &n));
-        std::vector<mpm_grid_body_t> out(n);
-        mpm_check(mpm_get_grid_bodies(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_grid_body_t> GetGridBodies() const { return table<mpm_grid_body_t>(mpm_get_grid_bodies); }
     // Extension: external force fields evaluated inside ParticleToGrid (mpm_set_force_fields): off-axis gravity,
     // springs, drag towards a wind, drag along the cloth's normal.  Coefficients are per unit mass: a Drake force
     // density with coefficient c per unit volume maps to gamma = c / rho.  Once per plant step, before its substeps.
     void SetForceFields(const std::vector<mpm_force_field_t>& fields) {
         mpm_check(mpm_set_force_fields(h_, fields.size(), fields.data()));
     }
-    std::vector<mpm_force_field_t> GetForceFields() const {
-        size_t n = 0;
-        mpm_check(mpm_get_force_fields(h_, nullptr, 0, &n));
-        std::vector<mpm_force_field_t> out(n);
-        mpm_check(mpm_get_force_fields(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_force_field_t> GetForceFields() const { return table<mpm_force_field_t>(mpm_get_force_fields); }
     // Extension: bending stiffness per cloth (mpm_set_bending), the quadratic hinge energy on a flat rest shape; all
     // zeros or an empty vector switches it off.  A synchronisation point, like SetForceFields.
     void SetBending(const std::vector<float>& stiffness) { mpm_check(mpm_set_bending(h_, stiffness.size(), stiffness.data())); }
-    std::vector<float> GetBending() const {
-        size_t n = 0;
-        mpm_check(mpm_get_bending(h_, nullptr, 0, &n));
-        std::vector<float> out(n);
-        mpm_check(mpm_get_bending(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<float> GetBending() const { return table<float>(mpm_get_bending); }
     // -k Q x on the current positions, 3 floats per vertex in the numbering of DumpCpuState (a diagnostic)
-    std::vector<float> BendingForces(size_t n_verts) const {
-        std::vector<float> f(3 * n_verts);
-        mpm_check(mpm_bending_forces(h_, f.data()));
-        return f;
-    }
+    std::vector<float> BendingForces(size_t n_verts) const { return vertex_forces(mpm_bending_forces, n_verts); }
     // the dt above which the substep entry points refuse an engine with bending (+inf while it is off)
-    float BendingMaxStableDt() const {
-        float dt = 0.f;
-        mpm_check(mpm_bending_max_stable_dt(h_, &dt));
-        return dt;
-    }
+    float BendingMaxStableDt() const { return max_stable_dt(mpm_bending_max_stable_dt); }
     // Extension: stiffness-proportional damping per cloth (mpm_set_damping), the counterpart of Drake's
     // DeformableBodyConfig::stiffness_damping_coefficient: {membrane, bending} in seconds; all zeros or an empty vector
     // switches it off.  A synchronisation point, like SetBending.
     void SetDamping(const std::vector<mpm_cloth_damping_t>& d) { mpm_check(mpm_set_damping(h_, d.size(), d.data())); }
-    std::vector<mpm_cloth_damping_t> GetDamping() const {
-        size_t n = 0;
-        mpm_check(mpm_get_damping(h_, nullptr, 0, &n));
-        std::vector<mpm_cloth_damping_t> out(n);
-        mpm_check(mpm_get_damping(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_cloth_damping_t> GetDamping() const { return table<mpm_cloth_damping_t>(mpm_get_damping); }
     // the damping force on the current positions and velocities, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> DampingForces(size_t n_verts) const {
-        std::vector<float> f(3 * n_verts);
-        mpm_check(mpm_damping_forces(h_, f.data()));
-        return f;
-    }
+    std::vector<float> DampingForces(size_t n_verts) const { return vertex_forces(mpm_damping_forces, n_verts); }
     // the dt above which the substep entry points refuse an engine with damping (+inf while it is off)
-    float DampingMaxStableDt() const {
-        float dt = 0.f;
-        mpm_check(mpm_damping_max_stable_dt(h_, &dt));
-        return dt;
-    }
+    float DampingMaxStableDt() const { return max_stable_dt(mpm_damping_max_stable_dt); }
     // the membrane damping kernel's face function on the host: n faces, see mpm_damping_face_records
     static std::vector<float> DampingFaceRecords(size_t n, const float* dminv3, const float* vol, const float* mu,
                                                  const float* lambda, const float* beta, const float* x9, const float* v9) {
@@ -252,13 +206,7 @@ struct GpuMpmState {
     void SetWeave(const std::vector<mpm_cloth_weave_t>& w, const std::vector<float>& face_dirs = {}) {
         mpm_check(mpm_set_weave(h_, w.size(), w.data(), face_dirs.empty() ? nullptr : face_dirs.data()));
     }
-    std::vector<mpm_cloth_weave_t> GetWeave() const {
-        size_t n = 0;
-        mpm_check(mpm_get_weave(h_, nullptr, 0, &n));
-        std::vector<mpm_cloth_weave_t> out(n);
-        mpm_check(mpm_get_weave(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_cloth_weave_t> GetWeave() const { return table<mpm_cloth_weave_t>(mpm_get_weave); }
     // (c, s) of the warp per face in the face's rest frame, 2 floats per face in the numbering of DumpCpuState
     std::vector<float> WeaveAxes(size_t n_faces) const {
         std::vector<float> cs(2 * n_faces);
@@ -287,11 +235,7 @@ struct GpuMpmState {
         return out;
     }
     // the dt above which the substep entry points refuse an engine with a weave (+inf while it is off)
-    float WeaveMaxStableDt() const {
-        float dt = 0.f;
-        mpm_check(mpm_weave_max_stable_dt(h_, &dt));
-        return dt;
-    }
+    float WeaveMaxStableDt() const { return max_stable_dt(mpm_weave_max_stable_dt); }
     // Extension: tearing cloth (mpm_set_tearing) -- one stretch limit per cloth (0: never tears; else finite and > 1); a
     // face whose largest in-plane stretch exceeds it fails for good and exerts no force from then on.  A synchronisation
     // point, like SetBending.
@@ -352,19 +296,9 @@ struct GpuMpmState {
     // Extension: links between cloth vertices (mpm_set_links) -- seams, springs, tension-only cords; an empty vector
     // clears them.  A synchronisation point, like SetBending.
     void SetLinks(const std::vector<mpm_link_t>& links) { mpm_check(mpm_set_links(h_, links.size(), links.data())); }
-    std::vector<mpm_link_t> GetLinks() const {
-        size_t n = 0;
-        mpm_check(mpm_get_links(h_, nullptr, 0, &n));
-        std::vector<mpm_link_t> out(n);
-        mpm_check(mpm_get_links(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_link_t> GetLinks() const { return table<mpm_link_t>(mpm_get_links); }
     // the links' force on the current positions and velocities, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> LinkForces(size_t n_verts) const {
-        std::vector<float> f(3 * n_verts);
-        mpm_check(mpm_link_forces(h_, f.data()));
-        return f;
-    }
+    std::vector<float> LinkForces(size_t n_verts) const { return vertex_forces(mpm_link_forces, n_verts); }
     // sum of 1/2 k (l - L)^2 over the links that act; `lengths`, if given, receives every link's float length
     double LinkEnergy(std::vector<float>* lengths = nullptr) const {
         double e = 0.0;
@@ -377,11 +311,7 @@ struct GpuMpmState {
         return e;
     }
     // the dt above which the substep entry points refuse an engine with links (+inf while the table is empty)
-    float LinksMaxStableDt() const {
-        float dt = 0.f;
-        mpm_check(mpm_links_max_stable_dt(h_, &dt));
-        return dt;
-    }
+    float LinksMaxStableDt() const { return max_stable_dt(mpm_links_max_stable_dt); }
     // one link's force on its end a, on the host: see mpm_link_force
     static void LinkForce(const mpm_link_t& link, const float xa[3], const float xb[3], const float va[3], const float vb[3],
                           float f_on_a[3]) {
@@ -393,13 +323,7 @@ struct GpuMpmState {
     void SetLinkLimits(const std::vector<float>& break_lengths) {
         mpm_check(mpm_set_link_limits(h_, break_lengths.size(), break_lengths.data()));
     }
-    std::vector<float> GetLinkLimits() const {
-        size_t n = 0;
-        mpm_check(mpm_get_link_limits(h_, nullptr, 0, &n));
-        std::vector<float> out(n);
-        mpm_check(mpm_get_link_limits(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<float> GetLinkLimits() const { return table<float>(mpm_get_link_limits); }
     // scissors / restore: one byte per link in link order, non-zero = broken; replaces every flag
     void SetBrokenLinks(const std::vector<uint8_t>& broken) { mpm_check(mpm_set_broken_links(h_, broken.size(), broken.data())); }
     // the flags per link; count: null, or the number of broken links
@@ -425,19 +349,9 @@ struct GpuMpmState {
     // whose motions are those of SetBodyMotions and whose reactions arrive where the pins' do; an empty vector clears them.
     // A synchronisation point, like SetLinks.
     void SetAnchors(const std::vector<mpm_anchor_t>& anchors) { mpm_check(mpm_set_anchors(h_, anchors.size(), anchors.data())); }
-    std::vector<mpm_anchor_t> GetAnchors() const {
-        size_t n = 0;
-        mpm_check(mpm_get_anchors(h_, nullptr, 0, &n));
-        std::vector<mpm_anchor_t> out(n);
-        mpm_check(mpm_get_anchors(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_anchor_t> GetAnchors() const { return table<mpm_anchor_t>(mpm_get_anchors); }
     // the anchors' force on the current state at the bodies' current clocks, 3 floats per vertex; adds no impulse
-    std::vector<float> AnchorForces(size_t n_verts) const {
-        std::vector<float> f(3 * n_verts);
-        mpm_check(mpm_anchor_forces(h_, f.data()));
-        return f;
-    }
+    std::vector<float> AnchorForces(size_t n_verts) const { return vertex_forces(mpm_anchor_forces, n_verts); }
     // sum of 1/2 k (l - L)^2 over the anchors that act; `lengths` and `points` (3 per anchor), if given, receive every
     // anchor's float length and attachment point; `impulse_quantum`, if given, the quantum of the bodies' accumulators
     double AnchorState(std::vector<float>* lengths = nullptr, std::vector<float>* points = nullptr,
@@ -452,11 +366,7 @@ struct GpuMpmState {
         return e;
     }
     // the dt above which the substep entry points refuse an engine with anchors (+inf while the table is empty)
-    float AnchorsMaxStableDt() const {
-        float dt = 0.f;
-        mpm_check(mpm_anchors_max_stable_dt(h_, &dt));
-        return dt;
-    }
+    float AnchorsMaxStableDt() const { return max_stable_dt(mpm_anchors_max_stable_dt); }
     // the attachment point of p_BQ and its velocity at the body's clock t, on the host: see mpm_anchor_point
     static void AnchorPoint(const mpm_body_motion_t& motion, double t, const float p_BQ[3], float y[3], float v_Q[3]) {
         mpm_check(mpm_anchor_point(&motion, t, p_BQ, y, v_Q));
@@ -466,27 +376,11 @@ struct GpuMpmState {
     void SetPressure(const std::vector<mpm_cloth_pressure_t>& per_cloth) {
         mpm_check(mpm_set_pressure(h_, per_cloth.size(), per_cloth.data()));
     }
-    std::vector<mpm_cloth_pressure_t> GetPressure() const {
-        size_t n = 0;
-        mpm_check(mpm_get_pressure(h_, nullptr, 0, &n));
-        std::vector<mpm_cloth_pressure_t> out(n);
-        mpm_check(mpm_get_pressure(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_cloth_pressure_t> GetPressure() const { return table<mpm_cloth_pressure_t>(mpm_get_pressure); }
     // the pressure force on the current positions, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> PressureForces(size_t n_verts) const {
-        std::vector<float> f(3 * n_verts);
-        mpm_check(mpm_pressure_forces(h_, f.data()));
-        return f;
-    }
+    std::vector<float> PressureForces(size_t n_verts) const { return vertex_forces(mpm_pressure_forces, n_verts); }
     // volume, energy, gauge pressure and cap of every cloth on the current positions
-    std::vector<mpm_cloth_pressure_state_t> PressureState() const {
-        size_t n = 0;
-        mpm_check(mpm_pressure_state(h_, nullptr, 0, &n));
-        std::vector<mpm_cloth_pressure_state_t> out(n);
-        mpm_check(mpm_pressure_state(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_cloth_pressure_state_t> PressureState() const { return table<mpm_cloth_pressure_state_t>(mpm_pressure_state); }
     // host only: is the mesh closed and consistently wound?  `edge`, if given, receives the first offending directed edge
     static bool MeshIsClosed(const std::vector<int32_t>& indices, size_t n_verts, int32_t* edge = nullptr) {
         const int rc = mpm_mesh_is_closed(indices.data(), indices.size() / 3, n_verts, edge);
@@ -503,19 +397,9 @@ struct GpuMpmState {
     void SetShellBending(const std::vector<mpm_cloth_shell_t>& per_cloth, const std::vector<float>& rest_pos = {}) {
         mpm_check(mpm_set_shell_bending(h_, per_cloth.size(), per_cloth.data(), rest_pos.empty() ? nullptr : rest_pos.data()));
     }
-    std::vector<mpm_cloth_shell_t> GetShellBending() const {
-        size_t n = 0;
-        mpm_check(mpm_get_shell_bending(h_, nullptr, 0, &n));
-        std::vector<mpm_cloth_shell_t> out(n);
-        mpm_check(mpm_get_shell_bending(h_, out.data(), n, &n));
-        return out;
-    }
+    std::vector<mpm_cloth_shell_t> GetShellBending() const { return table<mpm_cloth_shell_t>(mpm_get_shell_bending); }
     // the shell force on the current positions, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> ShellForces(size_t n_verts) const {
-        std::vector<float> f(3 * n_verts);
-        mpm_check(mpm_shell_forces(h_, f.data()));
-        return f;
-    }
+    std::vector<float> ShellForces(size_t n_verts) const { return vertex_forces(mpm_shell_forces, n_verts); }
     // the shell energy of every cloth on the current positions (not part of Measure's record)
     std::vector<double> ShellEnergy(size_t n_cloths) const {
         std::vector<double> e(n_cloths);
@@ -524,11 +408,7 @@ struct GpuMpmState {
     }
     // the dt above which the substep entry points refuse an engine with shell bending (+inf while it is off); a guard at
     // the rest shape
-    float ShellMaxStableDt() const {
-        float dt = 0.f;
-        mpm_check(mpm_shell_max_stable_dt(h_, &dt));
-        return dt;
-    }
+    float ShellMaxStableDt() const { return max_stable_dt(mpm_shell_max_stable_dt); }
     // Extension: the per-cloth report (mpm_measure) -- masses, momenta, kinetic, potential, elastic and bending energies,
     // strain extremes, reduced on the device in double.  One row per cloth; `total`, if given, receives their sum.
     // System::CalcKineticEnergy is total.kinetic + total.kinetic_affine, CalcPotentialEnergy is gravity_potential +
@@ -566,6 +446,25 @@ struct GpuMpmState {
 
   private:
     template <typename U> friend class GpuMpmSolver;
+    // the two-call getter of a table: the count, then that many records
+    template <class R>
+    std::vector<R> table(int (*get)(mpm_handle_t, R*, size_t, size_t*)) const {
+        size_t n = 0;
+        mpm_check(get(h_, nullptr, 0, &n));
+        std::vector<R> out(n);
+        mpm_check(get(h_, out.data(), n, &n));
+        return out;
+    }
+    float max_stable_dt(int (*get)(mpm_handle_t, float*)) const {
+        float dt = 0.f;
+        mpm_check(get(h_, &dt));
+        return dt;
+    }
+    std::vector<float> vertex_forces(int (*get)(mpm_handle_t, float*), size_t n_verts) const {
+        std::vector<float> f(3 * n_verts);
+        mpm_check(get(h_, f.data()));
+        return f;
+    }
     mpm_handle_t h_ = nullptr;
     size_t n_bodies_ = 0, n_contacts_ = 0;
     std::vector<Vec3<T>> h_positions_;
