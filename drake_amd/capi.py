@@ -321,6 +321,39 @@ def shell_hinge(x4, kc, psibar):
     return rec, np.float32(psi.value), rc == 1
 
 
+# mpm_cloth_crease_t (16 bytes): GpuMpm.set_creases takes, and get_creases returns, arrays of it, one per cloth
+CREASE_DTYPE = np.dtype([("yield_angle", "<f4"), ("hardening", "<f4"), ("max_angle", "<f4"), ("reserved", "<f4")])
+assert CREASE_DTYPE.itemsize == 16
+
+
+def crease(yield_angle=0.0, hardening=0.0, max_angle=0.0):
+    """one mpm_cloth_crease_t as a CREASE_DTYPE record (yield_angle 0: the cloth's hinges are elastic)"""
+    out = np.zeros((), CREASE_DTYPE)
+    out["yield_angle"], out["hardening"], out["max_angle"] = yield_angle, hardening, max_angle
+    return out
+
+
+def crease_chord(angle):
+    """y and P of mpm_set_creases: (float)(2 sin(angle / 2)), formed in double from the float angle and rounded once"""
+    return (2.0 * np.sin(0.5 * np.asarray(angle, np.float32).astype(np.float64))).astype(np.float32)
+
+
+def crease_hinge(x4, psibar, y, eta, P):
+    """mpm_crease_hinge: the crease kernel's two inline functions on the host, hinge by hinge.  x4 (n, 4, 3) the corners
+    x0, x1, x2, x3; psibar, y, eta, P (n,) (scalars are broadcast); returns (psi, dpsi, the psibar the substep leaves
+    (n,) float32, yields (n,) bool).  Needs no engine and no GPU."""
+    lib = load_library()
+    x = np.ascontiguousarray(x4, np.float32).reshape(-1, 12)
+    n = len(x)
+    s = [np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), (n,))) for a in (psibar, y, eta, P)]
+    psi, dpsi, nxt, yields = np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint8)
+    rc = lib.mpm_crease_hinge(n, x.ctypes.data, s[0].ctypes.data, s[1].ctypes.data, s[2].ctypes.data, s[3].ctypes.data,
+                              psi.ctypes.data, dpsi.ctypes.data, nxt.ctypes.data, yields.ctypes.data)
+    if rc:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return psi, dpsi, nxt, yields.astype(bool)
+
+
 def damping_face_records(dminv3, vol, mu, lam, beta, x, v):
     """mpm_damping_face_records: the membrane damping kernel's face function on the host.  dminv3 (n, 3) = (Dm0, Dm1, Dm3),
     vol, mu, lam, beta (n,) (scalars are broadcast), x, v (n, 3, 3) corner positions and velocities; returns the corner
@@ -627,6 +660,7 @@ SYMBOLS = [
     "mpm_pressure_vertex_force",
     "mpm_set_shell_bending", "mpm_get_shell_bending", "mpm_shell_hinges", "mpm_shell_forces", "mpm_shell_state",
     "mpm_shell_max_stable_dt", "mpm_mesh_hinges", "mpm_shell_hinge",
+    "mpm_set_creases", "mpm_get_creases", "mpm_set_crease_state", "mpm_crease_state", "mpm_crease_measure", "mpm_crease_hinge",
 ]
 
 EXCHANGE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
@@ -786,6 +820,12 @@ def load_library(build: bool = True):
         "mpm_shell_max_stable_dt": [vp, P(f)],
         "mpm_mesh_hinges": [vp, sz, sz, vp, sz, P(sz)],
         "mpm_shell_hinge": [vp, f, f, vp, P(f)],
+        "mpm_set_creases": [vp, sz, vp],
+        "mpm_get_creases": [vp, vp, sz, P(sz)],
+        "mpm_set_crease_state": [vp, vp],
+        "mpm_crease_state": [vp, vp, vp, sz, P(sz)],
+        "mpm_crease_measure": [vp, vp, vp, vp],
+        "mpm_crease_hinge": [sz, vp, vp, vp, vp, vp, vp, vp, vp, vp],
         "mpm_set_damping": [vp, sz, vp],
         "mpm_get_damping": [vp, vp, sz, P(sz)],
         "mpm_damping_forces": [vp, vp],
@@ -1416,6 +1456,56 @@ class GpuMpm:
     @staticmethod
     def shell_hinge(x4, kc, psibar):
         return shell_hinge(x4, kc, psibar)
+
+    def _n_hinges(self) -> int:
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_shell_hinges(self.h, None, None, None, 0, C.byref(n)))
+        return int(n.value)
+
+    def set_creases(self, table=None):
+        """mpm_set_creases: plastic shell hinges -- an array of CREASE_DTYPE in cloth order (crease(...) makes one record;
+        yield_angle 0: the cloth's hinges are elastic).  None or all zeros switches yielding off and keeps the creases
+        made so far.  Needs shell bending on.  A synchronisation point."""
+        t = np.zeros(0, CREASE_DTYPE) if table is None else np.ascontiguousarray(np.asarray(table, CREASE_DTYPE)).reshape(-1)
+        self._ck(self.lib.mpm_set_creases(self.h, t.size, t.ctypes.data if t.size else None))
+
+    def get_creases(self):
+        """mpm_get_creases: the table in force, one CREASE_DTYPE record per cloth (zeros while off)."""
+        return self._table(self.lib.mpm_get_creases, CREASE_DTYPE)
+
+    def set_crease_state(self, psibar=None):
+        """mpm_set_crease_state: scissors / restore -- (n_hinges,) float32 in hinge order replace every hinge's psibar;
+        None irons the cloth: every hinge returns to its rest psibar to the bit.  Allowed while every yield_angle is 0."""
+        if psibar is None:
+            self._ck(self.lib.mpm_set_crease_state(self.h, None))
+            return
+        p = np.ascontiguousarray(psibar, np.float32).reshape(-1)
+        if len(p) != self._n_hinges():
+            raise ValueError("psibar must have one entry per hinge")
+        keep = p if p.size else np.zeros(1, np.float32)   # (no hinge: a valid address, nothing is read)
+        self._ck(self.lib.mpm_set_crease_state(self.h, keep.ctypes.data))
+
+    def crease_state(self):
+        """mpm_crease_state: (the psibar in force per hinge (n_hinges,) float32, creased hinges per cloth (n_cloths,)
+        uint32: those whose psibar differs from the rest value in bits)."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_crease_state(self.h, None, None, 0, C.byref(n)))
+        psibar, count = np.zeros(self._n_hinges(), np.float32), np.zeros(n.value, np.uint32)
+        self._ck(self.lib.mpm_crease_state(self.h, _ptr(psibar) if psibar.size else None, count.ctypes.data if count.size else None,
+                                           len(count), C.byref(n)))
+        return psibar, count
+
+    def crease_measure(self):
+        """mpm_crease_measure: (psi, dpsi, the psibar the next substep would leave), (n_hinges,) float32 each, of the
+        substep's hinge function on the current positions; changes no state."""
+        m = self._n_hinges()
+        out = [np.zeros(m, np.float32) for _ in range(3)]
+        self._ck(self.lib.mpm_crease_measure(self.h, *[_ptr(a) if m else None for a in out]))
+        return tuple(out)
+
+    @staticmethod
+    def crease_hinge(x4, psibar, y, eta, P):
+        return crease_hinge(x4, psibar, y, eta, P)
 
     def measure(self, capacity: int | None = None):
         """mpm_measure: (rows, total) -- one MEASURE_DTYPE record per cloth (the first `capacity` of them if given) and

@@ -1,5 +1,5 @@
 // Host side of the per-cloth features: cloth materials, external force fields, row tables, bending stiffness, links,
-// pressure, shell bending, damping, the weave, tearing, breakable links, the rest shape and the per-cloth report -- what the entry points in mpm_engine.hip call once their
+// pressure, shell bending and its creases, damping, the weave, tearing, breakable links, the rest shape and the per-cloth report -- what the entry points in mpm_engine.hip call once their
 // arguments are checked.
 // Included by mpm_engine.hip after mpm_host.h and mpm_io.h.
 #pragma once
@@ -649,7 +649,8 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
     {   // the arrays of the table that was in force
         const mpm_engine::Shell& o = e->shell;
         rows_free(e, o.args);
-        void* old[] = {(void*)o.hinge.ids, (void*)o.hinge.par, (void*)o.hinge.rec};
+        // (the crease parameters and state go with the hinge table they belonged to: `next` has none)
+        void* old[] = {(void*)o.hinge.ids, (void*)o.hinge.par, (void*)o.hinge.rec, (void*)o.cr.cr};
         for (void* q : old) e->dfree(q);
     }
     e->shell = next;
@@ -685,6 +686,132 @@ static int shell_state(mpm_engine* e, double* energy_per_cloth, float* psi_out, 
         }
     }
     if (inactive_out) *inactive_out = inactive;
+    return 0;
+}
+
+// ---- creases: plastic shell hinges (mpm_set_creases, mpm_get_creases, mpm_set_crease_state, mpm_crease_state,
+// mpm_crease_measure, mpm_crease_hinge; mpm_shell.h) ----
+// the psibar in force per hinge: hinge.par[h].y while the crease tables exist, else the rest value
+static int crease_current(mpm_engine* e, std::vector<float>& out) {
+    const mpm_engine::Shell& sh = e->shell;
+    out = sh.psibar;
+    if (!sh.creasing()) return 0;
+    std::vector<float2> par(out.size());
+    D2H(e, par.data(), sh.hinge.par, par.size() * sizeof(float2));
+    for (size_t h = 0; h < par.size(); ++h) out[h] = par[h].y;
+    return 0;
+}
+static bool same_bits(float a, float b) { return std::memcmp(&a, &b, 4) == 0; }
+// Puts the crease table `table` (one per cloth, or none: all elastic) in force and, with `replace`, the state: psibar[h]
+// per hinge, or the rest values where psibar is null (ironing).  The tables exist while some cloth yields or some hinge's
+// psibar differs from its rest value in bits; otherwise they are freed and the engine launches what it launched before.
+// The caller has settled the owed substeps.  A failure changes nothing.
+static int crease_apply(mpm_engine* e, std::vector<mpm_cloth_crease_t> table, bool replace, const float* psibar) {
+    static_assert(sizeof(ClothCrease) == sizeof(mpm_cloth_crease_t) && sizeof(ClothCrease) == 16, "crease layouts differ");
+    mpm_engine::Shell& sh = e->shell;
+    const size_t n = sh.kc.size(), nc = e->cloths.size();
+    std::vector<float> yep(3 * std::max<size_t>(nc, 1));
+    for (size_t c = 0; c < nc; ++c) yep[3 * c] = 0.f, yep[3 * c + 1] = 0.f, yep[3 * c + 2] = 2.f;
+    if (!table.empty()) {
+        const std::string refusal = crease_params(reinterpret_cast<const ClothCrease*>(table.data()), table.size(), yep.data());
+        if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    }
+    bool any = false;
+    std::vector<float4> rec(n);
+    for (size_t h = 0; h < n; ++h) {
+        const float* q = &yep[3 * (size_t)sh.hinge_cloth[h]];
+        rec[h] = make_float4(q[0], q[1], q[2], sh.psibar[h]);
+        if (!(std::fabs(sh.psibar[h]) <= q[2]))
+            return fail(MPM_ERR_INVALID, "creases: hinge " + std::to_string(h) + " of cloth " + std::to_string(sh.hinge_cloth[h]) +
+                                             ": its rest |psibar| is above 2 sin(max_angle / 2)");
+        any = any || q[0] > 0.f;
+    }
+    std::vector<float> state;
+    if (replace) {
+        state = sh.psibar;
+        for (size_t h = 0; psibar && h < n; ++h) {
+            const std::string at = "crease state: hinge " + std::to_string(h);
+            if (!std::isfinite(psibar[h])) return fail(MPM_ERR_INVALID, at + ": psibar is not finite");
+            if (!(std::fabs(psibar[h]) <= rec[h].z)) return fail(MPM_ERR_INVALID, at + ": |psibar| is above its cloth's 2 sin(max_angle / 2)");
+            state[h] = psibar[h];
+        }
+    } else if (int rc = crease_current(e, state)) return rc;
+    for (size_t h = 0; h < n; ++h) any = any || !same_bits(state[h], sh.psibar[h]);
+    // (a synchronisation point: the kernels enqueued so far have read the old tables)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (any && !sh.creasing()) {
+        FreshArrays fresh(e);
+        float4* d_cr = nullptr;
+        if (int rc = fresh.alloc(&d_cr, n, false)) return rc;
+        sh.cr = CreaseArgs{sh.hinge.ids, const_cast<float2*>(sh.hinge.par), d_cr, (int)n};
+        fresh.commit();
+    }
+    if (sh.creasing()) {
+        if (replace) {
+            std::vector<float2> par(n);
+            for (size_t h = 0; h < n; ++h) par[h] = make_float2(sh.kc[h], state[h]);
+            H2D(e, sh.cr.par, par.data(), n * sizeof(float2));
+        }
+        if (any) {
+            H2D(e, const_cast<float4*>(sh.cr.cr), rec.data(), n * sizeof(float4));
+        } else {   // (every psibar is its rest value again, to the bit: what k_hinge read before there were creases)
+            float4* d_cr = const_cast<float4*>(sh.cr.cr);
+            e->dfree(d_cr);
+            sh.cr = CreaseArgs{};
+        }
+    }
+    sh.crease.swap(table);
+    return 0;
+}
+// mpm_crease_state: the psibar in force, and per cloth the hinges whose psibar is not the rest value's bits
+static int crease_state(mpm_engine* e, float* psibar_out, uint32_t* creased_per_cloth, size_t capacity, size_t* n_out) {
+    std::vector<float> cur;
+    if (int rc = crease_current(e, cur)) return rc;
+    std::vector<uint32_t> count(e->cloths.size(), 0u);
+    for (size_t h = 0; h < cur.size(); ++h) {
+        if (psibar_out) psibar_out[h] = cur[h];
+        if (!same_bits(cur[h], e->shell.psibar[h])) count[(size_t)e->shell.hinge_cloth[h]] += 1u;
+    }
+    return copy_out(count, creased_per_cloth, capacity, n_out);
+}
+// mpm_crease_measure: one launch of k_crease_eval on the current state, in hinge order; while the tables do not exist,
+// with a record array of its own in which no hinge yields
+static int crease_measure(mpm_engine* e, float* psi_out, float* dpsi_out, float* next_out) {
+    const mpm_engine::Shell& sh = e->shell;
+    const size_t n = sh.kc.size();
+    if (n == 0) return 0;
+    CreaseArgs a = sh.cr;
+    // (the staging buffer: the records where they are made here, 16 bytes per hinge, then three float outputs)
+    if (int rc = e->stage(28 * n)) return rc;
+    if (!sh.creasing()) {
+        std::vector<float4> rec(n);
+        for (size_t h = 0; h < n; ++h) rec[h] = make_float4(0.f, 0.f, 2.f, sh.psibar[h]);
+        float4* d_cr = (float4*)e->d_stage;
+        H2D(e, d_cr, rec.data(), n * sizeof(float4));
+        a = CreaseArgs{sh.hinge.ids, const_cast<float2*>(sh.hinge.par), d_cr, (int)n};
+    }
+    float* d_out = (float*)e->d_stage + 4 * n;
+    hipLaunchKernelGGL(k_crease_eval, rows_grid((int)n), dim3(256), 0, e->stream, e->dp, a, d_out, d_out + n, d_out + 2 * n);
+    HIP_TRY(hipGetLastError());
+    if (psi_out) D2H(e, psi_out, d_out, 4 * n);
+    if (dpsi_out) D2H(e, dpsi_out, d_out + n, 4 * n);
+    if (next_out) D2H(e, next_out, d_out + 2 * n, 4 * n);
+    return 0;
+}
+// host code only: the device functions of the kernels, compiled for the host
+static int crease_hinge_host(size_t n, const float* x12, const float* psibar, const float* y, const float* eta, const float* P,
+                             float* psi_out, float* dpsi_out, float* psibar_out, uint8_t* yields_out) {
+    for (size_t i = 0; i < n; ++i) {
+        const float* x = x12 + 12 * i;
+        float psi, dpsi;
+        bool yields;
+        const bool on = shell_angle(x, x + 3, x + 6, x + 9, &psi, &dpsi);
+        const float next = crease_return(psi, dpsi, on, psibar[i], y[i], eta[i], P[i], &yields);
+        if (psi_out) psi_out[i] = psi;
+        if (dpsi_out) dpsi_out[i] = dpsi;
+        if (psibar_out) psibar_out[i] = next;
+        if (yields_out) yields_out[i] = yields ? 1 : 0;
+    }
     return 0;
 }
 

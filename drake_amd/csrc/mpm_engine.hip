@@ -224,7 +224,10 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
         hipLaunchKernelGGL(k_pressure, rows_grid(ps.args.n_rows), dim3(256), 0, e->stream, p, ps.args);
     }
     // (an engine with shell bending, mpm_set_shell_bending: the corner records of every hinge, one lane per hinge; then
-    // f += the records of every vertex, one lane per vertex of a cloth with k > 0)
+    // f += the records of every vertex, one lane per vertex of a cloth with k > 0; while some cloth creases or some hinge
+    // is creased, mpm_set_creases / mpm_set_crease_state, k_crease first: one lane per hinge, it owns the psibar k_hinge reads)
+    if (e->shell.on() && e->shell.creasing())
+        hipLaunchKernelGGL(k_crease, rows_grid(e->shell.cr.n), dim3(256), 0, e->stream, p, e->shell.cr);
     if (e->shell.on()) {
         hipLaunchKernelGGL(k_hinge, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, p, e->shell.hinge);
         hipLaunchKernelGGL(k_hinge_gather, rows_grid(e->shell.args.n_rows), dim3(256), 0, e->stream, p, e->shell.args);
@@ -2638,6 +2641,57 @@ int mpm_shell_hinge(const float* x12, float kc, float psibar, float* rec12_out, 
     std::memcpy(rec12_out, rec, sizeof rec);
     if (psi_out) *psi_out = psi;
     return on;
+} MPM_CATCH_ALL
+
+// ---- creases: plastic shell hinges (mpm_cloth_host.h; mpm_shell.h) ----------------------------------------------------------------
+// what the crease setters check first
+static int creases_ready(mpm_engine* e, const char* what_is) {
+    if (int rc = single_engine_only(e, what_is)) return rc;
+    REQUIRE(e->shell.on(), "creases need shell bending (mpm_set_shell_bending) on");
+    return 0;
+}
+int mpm_set_creases(mpm_handle_t e, size_t n_cloths, const mpm_cloth_crease_t* per_cloth) try {
+    READY_NO_SETTLE(e);
+    if (int rc = creases_ready(e, "creases are")) return rc;
+    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_creases: n_cloths must be the cloth count or 0");
+    REQUIRE(n_cloths == 0 || per_cloth, "null crease array");
+    std::vector<mpm_cloth_crease_t> table(per_cloth, per_cloth + n_cloths);
+    std::vector<float> yep(3 * std::max<size_t>(n_cloths, 1));
+    const std::string refusal = crease_params(reinterpret_cast<const ClothCrease*>(table.data()), n_cloths, yep.data());
+    if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    // substeps that mpm_run_substeps deferred are owed with the parameters they were enqueued with
+    if (int rc = settle(e)) return rc;
+    return crease_apply(e, table, false, nullptr);
+} MPM_CATCH_ALL
+
+int mpm_get_creases(mpm_handle_t e, mpm_cloth_crease_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    return padded_out(e->shell.crease, e->cloths.size(), mpm_cloth_crease_t{0.f, 0.f, 0.f, 0.f}, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_set_crease_state(mpm_handle_t e, const float* psibar) try {
+    READY_NO_SETTLE(e);
+    if (int rc = creases_ready(e, "creases are")) return rc;
+    if (int rc = settle(e)) return rc;
+    return crease_apply(e, e->shell.crease, true, psibar);
+} MPM_CATCH_ALL
+
+int mpm_crease_state(mpm_handle_t e, float* psibar_out, uint32_t* creased_per_cloth, size_t capacity, size_t* n_out) try {
+    READY(e);
+    REQUIRE(creased_per_cloth || capacity == 0, "null output");
+    return crease_state(e, psibar_out, creased_per_cloth, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_crease_measure(mpm_handle_t e, float* psi_out, float* dpsi_out, float* psibar_next_out) try {
+    READY(e);
+    if (int rc = single_engine_only(e, "mpm_crease_measure is")) return rc;
+    return crease_measure(e, psi_out, dpsi_out, psibar_next_out);
+} MPM_CATCH_ALL
+
+int mpm_crease_hinge(size_t n, const float* x12, const float* psibar, const float* y, const float* eta, const float* P, float* psi_out,
+                     float* dpsi_out, float* psibar_out, uint8_t* yields_out) try {
+    REQUIRE((x12 && psibar && y && eta && P) || n == 0, "null array");
+    return crease_hinge_host(n, x12, psibar, y, eta, P, psi_out, dpsi_out, psibar_out, yields_out);
 } MPM_CATCH_ALL
 
 // ---- the per-cloth report (mpm_cloth_host.h; mpm_measure.h) --------------------------------------------------------------------

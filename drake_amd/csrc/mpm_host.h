@@ -311,7 +311,13 @@ struct mpm_engine {
         std::vector<float> kc, psibar;        // [hinge] float(k cbar), the psi of the rest shape (mpm_shell_hinges)
         std::vector<int> hinge_cloth;         // [hinge]
         float max_dt = INFINITY;              // the guard at the rest shape (fields_stable)
+        // creases (mpm_set_creases, mpm_set_crease_state): the tables exist while some cloth has a yield angle or some
+        // hinge's psibar in force (hinge.par[h].y) differs from `psibar`, and k_crease then runs in front of k_hinge; they
+        // go with the hinge table they belonged to
+        std::vector<mpm_cloth_crease_t> crease;   // [cloth] as given; empty: all off
+        CreaseArgs cr{};                      // k_crease's tables (device memory, in `allocs`); cr == nullptr: none
         bool on() const { return hinge.n > 0; }
+        bool creasing() const { return cr.cr != nullptr; }
     } shell;
     // anchors: springs and cords from cloth vertices to rigid bodies (mpm_set_anchors; mpm_anchors.h): a non-empty table
     // switches k_anchor_pose and k_anchor on behind k_hinge_gather, and k_pin's clock tail behind GridToParticle

@@ -73,6 +73,51 @@
 //   second-order terms                                                                                               0.75
 // R_shell = 46.  A row with n records adds them in stored order, one rounding of a partial sum per record, each partial
 // sum at most the row's sum of T: R_i = 46 + n_i.  psi alone: at most 13 (kappa_A + kappa_B) (1 + |psi|) 2^-24.
+//
+// CREASES (mpm_set_creases, mpm_set_crease_state, mpm_crease_state, mpm_crease_measure, mpm_crease_hinge): plastic hinges.
+// psibar, the number par[h].y that k_hinge reads, evolves under a yield rule on the generalised moment conjugate to theta,
+// kc (psi - psibar) dpsi, per hinge with its cloth's (y, eta, P) (y = float(2 sin(yield_angle / 2)), eta the hardening
+// ratio in [0, 1), P = float(2 sin(max_angle / 2)), formed in double on the host and rounded once).  crease_return below:
+//   d = psi - psibar,  ad = |d|,  t = ad dpsi,  the hinge YIELDS where it acts, y > 0 and t > y (never on a NaN); then
+//   dy = y / dpsi,  dn = dy + eta (ad - dy),  psibar' = clamp(psi - copysign(dn, d), -P, P);  otherwise psibar' = psibar.
+// A return mapping: it runs BEFORE the force (k_crease immediately in front of k_hinge), so from the substep in which a
+// hinge yields its moment is at most kc (y + eta (t - y)), up to rounding; psibar moves towards psi and never past it
+// (dy < ad wherever t > y, and eta < 1).  On the moment and not on psi - psibar alone because dpsi -> 0 as |theta| -> pi:
+// a hinge folded flat onto itself, where psi jumps between +2 and -2, carries no moment and does not yield, so a sheet
+// folded in half does not flip its crease when theta wobbles across pi.  eta is the post-yield tangent over the elastic
+// one: 0 is perfectly plastic.
+// k_crease, one lane per hinge, 256 per block, gated_out(p) first, launched only while the crease tables exist: a lane
+// whose y is 0 returns at once; any other reads the four ids (and its psibar), the four slots through DP::imap and the
+// four positions -- three round trips of independent loads, the id and slot checks of hinge_on_state --, runs shell_angle
+// (shell_hinge's operations up to psi and dpsi, restated: the same bits) and crease_return, and stores par[h].y where the
+// hinge yields: a plain 4-byte store, one writer per hinge, no atomics but the error flag, no LDS.  Decisions are taken
+// hinge by hinge on the positions of the substep's start (Jacobi), so the result does not depend on the particle order or
+// on deterministic mode; a substep that skips itself changes nothing (with eta > 0 the update is not idempotent).
+// k_crease_eval (mpm_crease_measure): the same function without the gate and without the store.
+// The cost of k_crease on an MI355X: 14.8 us per substep on cloth_1m with shell bending on every sheet (990,720 hinges, a
+// yield angle set, no hinge yielding); k_hinge behind it finds the ids and positions in the L2 and runs 4 us shorter
+// (profiles/creases.txt).  A substep in which many hinges yield has not been measured.
+// NOT MODELLED: no rate dependence (no creep, no viscoplasticity), no softening (a crease never weakens the hinge), no
+// coupling between neighbouring hinges (each yields on its own moment), and the psi discontinuity at |theta| = pi of the
+// elastic model above stays: a crease with psibar != 0 sees the same jump of the energy there.
+// Roundings, for the bounds of tests/creases.py, first order, in units of 2^-24 of
+//   W = (kappa_A + kappa_B) (1 + |psi| + |psibar|)        (kappa_A + kappa_B >= 2: one rounding of a quantity bounded by
+//                                                          |psi| + |psibar| costs at most 1/2 unit)
+//   t: psi (above), times dpsi <= 1                                                                                  13
+//      d = psi - psibar: one rounding                                                                                0.5
+//      dpsi's absolute error (the "dpsi" lines above: 3 + 4), times ad <= |psi| + |psibar|                             7
+//      the product ad dpsi                                                                                           0.5
+//      second-order terms                                                                                              1
+// R_crease_t = 22: |t - t64| <= 22 W 2^-24; a hinge with |t64 - y| within that is UNDECIDED.
+//   psibar' of a hinge that yields, in units of W / dpsi (1 / dpsi >= 1 multiplies what enters through dy = y / dpsi):
+//      psi, which enters psi - copysign(dn, d) as (1 - eta) psi                                                       13
+//      d: one rounding, times eta                                                                                    0.5
+//      dy: dpsi's relative error 7 (kappa_A + kappa_B) / dpsi on dy < ad, times (1 - eta)                              7
+//          the division's rounding                                                                                   0.5
+//      the hardening line dy + eta (ad - dy): three roundings of at most ad                                          1.5
+//      the final subtraction, |psibar'| <= max(|psi|, |psibar|)                                                      0.5
+//      second-order terms                                                                                              1
+// R_crease = 24: |psibar' - psibar'64| <= 24 W / dpsi 2^-24 (the clamp is monotone and 1-Lipschitz: it adds nothing).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -97,10 +142,14 @@ constexpr int SHELL_SLICE = 64, SHELL_BATCH = 8;
 constexpr uint32_t SHELL_PAD = 0xFFFFFFFFu;   // the gather table's padding record
 constexpr float SHELL_GATE = 1e-30f;          // a hinge acts while |e|^2, |nA|^2, |nB|^2 >= this
 constexpr float R_SHELL = 46.f;               // the counted roundings of one record (above)
+constexpr float R_CREASE_T = 22.f, R_CREASE = 24.f;   // ... of a crease's t and of its psibar' (above)
 
 struct ClothShell {   // mirrors mpm_cloth_shell_t (include/mpm_hip.h)
     float stiffness;
     uint32_t rest;
+};
+struct ClothCrease {   // mirrors mpm_cloth_crease_t
+    float yield_angle, hardening, max_angle, reserved;
 };
 
 // The four corner records rec[j] = f_j of one hinge and its psi; kc = float(k cbar).  false: the hinge does not act
@@ -149,6 +198,54 @@ MPM_SHELL_FN bool shell_hinge(const float x0[3], const float x1[3], const float 
     }
     *psi_out = on ? psi : 0.f;
     return on;
+}
+
+// shell_hinge's operations up to psi and dpsi, restated in the same order: psi and the gate are shell_hinge's bits.
+// false: the hinge does not act (psi and dpsi are exact zeros).
+MPM_SHELL_FN bool shell_angle(const float x0[3], const float x1[3], const float x2[3], const float x3[3], float* psi_out, float* dpsi_out) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const float e0 = x1[0] - x0[0], e1 = x1[1] - x0[1], e2 = x1[2] - x0[2];
+    const float a0 = x2[0] - x0[0], a1 = x2[1] - x0[1], a2 = x2[2] - x0[2];
+    const float b0 = x3[0] - x0[0], b1 = x3[1] - x0[1], b2 = x3[2] - x0[2];
+    const float A0 = e1 * a2 - e2 * a1, A1 = e2 * a0 - e0 * a2, A2 = e0 * a1 - e1 * a0;
+    const float B0 = b1 * e2 - b2 * e1, B1 = b2 * e0 - b0 * e2, B2 = b0 * e1 - b1 * e0;
+    const float ee = (e0 * e0 + e1 * e1) + e2 * e2;
+    const float AA = (A0 * A0 + A1 * A1) + A2 * A2;
+    const float BB = (B0 * B0 + B1 * B1) + B2 * B2;
+    const bool on = (ee >= SHELL_GATE) & (AA >= SHELL_GATE) & (BB >= SHELL_GATE);
+    const float lA = sqrtf(AA), lB = sqrtf(BB);
+    const float rA = 1.f / lA, rB = 1.f / lB;
+    const float hA0 = A0 * rA, hA1 = A1 * rA, hA2 = A2 * rA;
+    const float hB0 = B0 * rB, hB1 = B1 * rB, hB2 = B2 * rB;
+    const float d0 = hA0 - hB0, d1 = hA1 - hB1, d2 = hA2 - hB2;
+    const float s0 = hA0 + hB0, s1 = hA1 + hB1, s2 = hA2 + hB2;
+    const float c0 = A1 * B2 - A2 * B1, c1 = A2 * B0 - A0 * B2, c2 = A0 * B1 - A1 * B0;
+    const float t = (e0 * c0 + e1 * c1) + e2 * c2;
+    const float mag = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+    const float psi = t >= 0.f ? mag : -mag;
+    const float dpsi = .5f * sqrtf((s0 * s0 + s1 * s1) + s2 * s2);
+    *psi_out = on ? psi : 0.f;
+    *dpsi_out = on ? dpsi : 0.f;
+    return on;
+}
+
+// The return mapping of one hinge (the header, CREASES): the psibar the substep leaves, and whether the hinge yields.
+// What a hinge that does not yield computes on the way (a division by dpsi = 0, a NaN) is never selected.
+MPM_SHELL_FN float crease_return(float psi, float dpsi, bool on, float psibar, float y, float eta, float P, bool* yields_out) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const float d = psi - psibar;
+    const float ad = fabsf(d);
+    const float t = ad * dpsi;
+    const bool yields = on && y > 0.f && t > y;
+    const float dy = y / dpsi;
+    const float dn = dy + eta * (ad - dy);
+    const float pn = psi - copysignf(dn, d);
+    *yields_out = yields;
+    return yields ? fminf(fmaxf(pn, -P), P) : psibar;
 }
 
 // the hinge's energy term 1/2 kc (psi - psibar)^2, in float (the .w of plane 1)
@@ -248,6 +345,70 @@ __global__ __launch_bounds__(256) void k_hinge_rest(HingeArgs a, const float* po
         x[j] = make_float4(q[0], q[1], q[2], 0.f);
     }
     hinge_store(a, h, x, ok);
+}
+
+struct CreaseArgs {
+    const int4* ids;    // HingeArgs::ids
+    float2* par;        // HingeArgs::par of the same table: .y is the psibar in force, which k_crease owns
+    const float4* cr;   // [hinge] (y, eta, P, psibar0) of the hinge's cloth and rest shape; nullptr: the tables do not exist
+    int n;
+};
+
+// Hinge h's psi, dpsi and the psibar the substep leaves, on the current positions: ids and psibar, slots, positions --
+// three round trips of independent loads, the checks of hinge_on_state.  A bad id is reported, never used as an address,
+// and the hinge then does not yield (psi = dpsi = 0, next = its psibar).  Returns whether the hinge yields.
+MPM_DEV bool crease_on_state(const DP& p, const PSet& S, const CreaseArgs& a, int h, const float4& c, float& psi, float& dpsi,
+                             float& next, bool& bad) {
+    const int4 id = a.ids[h];
+    const float psibar = a.par[h].y;
+    const int q[4] = {id.x, id.y, id.z, id.w};
+    int s[4];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ok = ok && q[j] >= p.NfG && q[j] < p.NpG;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = ok ? p.imap[q[j]] : -1;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) ok = ok && s[j] >= p.Nf && s[j] < p.Np;
+    float4 x[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) x[j] = ok ? S.q[0][s[j]] : make_float4(0.f, 0.f, 0.f, 0.f);
+    bad |= !ok;
+    const float X[4][3] = {{x[0].x, x[0].y, x[0].z}, {x[1].x, x[1].y, x[1].z}, {x[2].x, x[2].y, x[2].z}, {x[3].x, x[3].y, x[3].z}};
+    const bool on = shell_angle(X[0], X[1], X[2], X[3], &psi, &dpsi) && ok;
+    bool yields;
+    next = crease_return(psi, dpsi, on, psibar, c.x, c.y, c.z, &yields);
+    return yields;
+}
+
+// Immediately in front of k_hinge on the same stream, with the substep's DP, while the crease tables exist: one lane per
+// hinge.  A hinge that yields gets its new psibar (one writer per hinge: a plain store), which k_hinge then reads; a
+// substep that skips itself stores nothing.
+__global__ __launch_bounds__(256) void k_crease(DP p, CreaseArgs a) {
+    if (gated_out(p)) return;
+    const int h = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool bad = false;
+    if (h < a.n) {
+        const float4 c = a.cr[h];
+        if (c.x != 0.f) {
+            float psi, dpsi, next;
+            if (crease_on_state(p, p.set[p.ctl->cur], a, h, c, psi, dpsi, next, bad)) a.par[h].y = next;
+        }
+    }
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
+}
+// mpm_crease_measure: psi, dpsi and the psibar the substep would leave per hinge, without the gate and without the store
+__global__ __launch_bounds__(256) void k_crease_eval(DP p, CreaseArgs a, float* psi_out, float* dpsi_out, float* next_out) {
+    const int h = (int)(blockIdx.x * 256 + threadIdx.x);
+    bool bad = false;
+    if (h < a.n) {
+        float psi, dpsi, next;
+        crease_on_state(p, p.set[p.ctl->cur], a, h, a.cr[h], psi, dpsi, next, bad);
+        psi_out[h] = psi;
+        dpsi_out[h] = dpsi;
+        next_out[h] = next;
+    }
+    if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
 }
 
 // Row r of the gather table: the records of the row's vertex, added in stored order.  A record that names no hinge of
@@ -419,6 +580,26 @@ inline std::string shell_refusal(const ClothShell* t, size_t n) {
         const std::string at = "shell bending: cloth " + std::to_string(c);
         if (!(std::isfinite(t[c].stiffness) && t[c].stiffness >= 0.f)) return at + ": the stiffness is negative or not finite";
         if (t[c].rest > SHELL_REST_FLAT) return at + ": unknown rest";
+    }
+    return std::string();
+}
+
+// mpm_set_creases: y, eta and P of every cloth from its ClothCrease, yep[3 c ..]; y and P are formed in double and rounded
+// once, P of a cloth with max_angle 0 is 2.  The refusal in the caller's words, naming the cloth; empty: fine.
+inline std::string crease_params(const ClothCrease* t, size_t n, float* yep) {
+    // (max_angle may be pi as a float, which lies above pi: its chord still rounds to 2)
+    const double pi = 3.14159265358979323846, pi_float = (double)3.14159274101257324f;
+    for (size_t c = 0; c < n; ++c) {
+        const std::string at = "creases: cloth " + std::to_string(c);
+        const double ya = (double)t[c].yield_angle, ma = (double)t[c].max_angle;
+        if (!(t[c].yield_angle == 0.f || (std::isfinite(ya) && ya > 0.0 && ya < pi))) return at + ": yield_angle is neither 0 nor in (0, pi)";
+        if (!(t[c].hardening >= 0.f && t[c].hardening < 1.f)) return at + ": hardening is not in [0, 1)";
+        if (!(t[c].max_angle == 0.f || (std::isfinite(ma) && ma > 0.0 && ma <= pi_float))) return at + ": max_angle is neither 0 nor in (0, pi]";
+        const float y = t[c].yield_angle == 0.f ? 0.f : (float)(2.0 * std::sin(.5 * ya));
+        if (t[c].yield_angle != 0.f && !(y > 0.f)) return at + ": yield_angle is too small, 2 sin(yield_angle / 2) rounds to 0";
+        yep[3 * c] = y;
+        yep[3 * c + 1] = t[c].hardening;
+        yep[3 * c + 2] = t[c].max_angle == 0.f ? 2.f : (float)(2.0 * std::sin(.5 * ma));
     }
     return std::string();
 }

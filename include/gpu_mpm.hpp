@@ -398,6 +398,35 @@ struct GpuMpmState {
         mpm_check(mpm_set_shell_bending(h_, per_cloth.size(), per_cloth.data(), rest_pos.empty() ? nullptr : rest_pos.data()));
     }
     std::vector<mpm_cloth_shell_t> GetShellBending() const { return table<mpm_cloth_shell_t>(mpm_get_shell_bending); }
+    // Extension: creases (mpm_set_creases) -- plastic shell hinges, one {yield_angle, hardening, max_angle} per cloth
+    // (yield_angle 0: elastic); all zeros or an empty vector switches yielding off and keeps the creases made so far.
+    // Needs SetShellBending first, which also drops the crease parameters and state.  A synchronisation point.
+    void SetCreases(const std::vector<mpm_cloth_crease_t>& per_cloth) { mpm_check(mpm_set_creases(h_, per_cloth.size(), per_cloth.data())); }
+    std::vector<mpm_cloth_crease_t> GetCreases() const { return table<mpm_cloth_crease_t>(mpm_get_creases); }
+    // scissors / restore: one psibar per hinge in hinge order replaces every hinge's; an empty vector irons the cloth
+    void SetCreaseState(const std::vector<float>& psibar) { mpm_check(mpm_set_crease_state(h_, psibar.empty() ? nullptr : psibar.data())); }
+    // the psibar in force per hinge; counts: null, or the creased hinges per cloth
+    std::vector<float> CreaseState(std::vector<uint32_t>* counts = nullptr) const {
+        size_t n = 0, n_hinges = 0;
+        mpm_check(mpm_crease_state(h_, nullptr, nullptr, 0, &n));
+        mpm_check(mpm_shell_hinges(h_, nullptr, nullptr, nullptr, 0, &n_hinges));
+        std::vector<float> psibar(n_hinges);
+        std::vector<uint32_t> c(n);
+        mpm_check(mpm_crease_state(h_, psibar.data(), c.data(), n, &n));
+        if (counts) counts->swap(c);
+        return psibar;
+    }
+    // the substep's hinge function on the current positions, state untouched: the psibar the next substep would leave;
+    // psi and dpsi per hinge where asked for
+    std::vector<float> CreaseMeasure(std::vector<float>* psi = nullptr, std::vector<float>* dpsi = nullptr) const {
+        size_t n = 0;
+        mpm_check(mpm_shell_hinges(h_, nullptr, nullptr, nullptr, 0, &n));
+        std::vector<float> next(n);
+        if (psi) psi->resize(n);
+        if (dpsi) dpsi->resize(n);
+        mpm_check(mpm_crease_measure(h_, psi ? psi->data() : nullptr, dpsi ? dpsi->data() : nullptr, next.data()));
+        return next;
+    }
     // the shell force on the current positions, 3 floats per vertex in the numbering of DumpCpuState
     std::vector<float> ShellForces(size_t n_verts) const { return vertex_forces(mpm_shell_forces, n_verts); }
     // the shell energy of every cloth on the current positions (not part of Measure's record)

@@ -1404,6 +1404,65 @@ MPM_API int mpm_mesh_hinges(const int32_t *indices, size_t n_faces, size_t n_ver
  * hinge acts, 0 where it does not (exact zeros), a negative code on a null argument. */
 MPM_API int mpm_shell_hinge(const float x12[12], float kc, float psibar, float rec12_out[12], float *psi_out);
 
+/* ---- Creases: plastic shell hinges that keep a fold (an extension of shell bending) ----
+ * Shell bending is elastic: a sheet folded in half springs back flat.  With creases a hinge's rest value psibar, the
+ * number the hinge kernel reads, evolves on the device under a yield rule, so paper, foil, pressed fabric and pleats
+ * keep their folds.  Per cloth: y = float(2 sin(yield_angle / 2)), eta = hardening, P = float(2 sin(max_angle / 2))
+ * (max_angle 0 means pi, P = 2), formed in double and rounded once.  In every substep, BEFORE the hinge force, per hinge
+ * of a cloth with y > 0, with psi and dpsi of the shell block above on the positions of the substep's start:
+ *   d = psi - psibar,  ad = |d|,  t = ad dpsi;   the hinge yields where it acts and t > y (never on a NaN); then
+ *   dy = y / dpsi,  dn = dy + eta (ad - dy),  psibar' = min(max(psi - copysign(dn, d), -P), P);   else psibar' = psibar
+ * in float, every operation written out, no contraction, the division correctly rounded.  The rule acts on the
+ * generalised moment conjugate to theta, k cbar (psi - psibar) dpsi, not on psi - psibar alone: dpsi -> 0 as |theta| ->
+ * pi, so a hinge folded flat onto itself, where psi jumps between +2 and -2, carries no moment and does not yield -- a
+ * sheet folded in half does not flip its crease when theta wobbles across pi.  It is a return mapping: from the substep
+ * in which a hinge yields its moment is at most k cbar (y + eta (t - y)), up to rounding; psibar moves towards psi and
+ * never past it.  eta is the post-yield tangent over the elastic one; 0 is perfectly plastic.  psibar stays in [-P, P].
+ * NOT MODELLED: no rate dependence, no softening, no coupling between neighbouring hinges, and the psi discontinuity at
+ * |theta| = pi that the shell model documents stays.  Creases in mpm_set_bending's quadratic model are not provided.
+ * On the device: one kernel of one lane per hinge immediately in front of the hinge kernel, counted under
+ * MPM_PHASE_VFORCE, launched only while the crease tables exist: while some cloth has yield_angle > 0 or some hinge's
+ * psibar differs from its rest value.  Otherwise the engine launches exactly what it launches without these calls.
+ * Decisions are taken hinge by hinge (Jacobi), one writer per hinge, no atomics: the same bits whatever the particle
+ * order, deterministic mode or substep path; a substep that skips itself changes nothing.
+ * Reports: mpm_shell_hinges keeps reporting the REST psibar; mpm_shell_forces and mpm_shell_state use the psibar in
+ * force, so they show the creased forces and the elastic energy 1/2 k cbar (psi - psibar)^2.  mpm_shell_max_stable_dt
+ * does not change: its Gauss-Newton term does not contain psibar.
+ * mpm_set_shell_bending replaces the hinge table, and the crease parameters and state go with the table they belonged
+ * to (as link limits go with mpm_set_links): set them again afterwards.
+ * Every setter needs mpm_finalize and shell bending on, runs the substeps mpm_run_substeps still owes first (with the
+ * old values), is ordered on the engine's stream and is a synchronisation point.  Refused with MPM_ERR_INVALID, nothing
+ * changed, the message naming the cloth or hinge: a call before mpm_finalize; shell bending off; a wrong count;
+ * yield_angle neither 0 nor in (0, pi) (or so small that y rounds to 0), or NaN; hardening outside [0, 1); max_angle
+ * neither 0 nor in (0, pi]; a P below the rest |psibar| of a hinge of the cloth; mpm_set_crease_state with a non-finite
+ * value or |psibar| above its hinge's P; a null array with n > 0; any partitioned or multi-rank engine. */
+typedef struct mpm_cloth_crease {
+    float yield_angle;   /* rad; 0: the cloth's hinges are elastic; else in (0, pi) */
+    float hardening;     /* eta in [0, 1); 0: perfectly plastic */
+    float max_angle;     /* rad; 0: pi; else in (0, pi]: psibar stays within 2 sin(max_angle / 2) */
+    float reserved;      /* not read */
+} mpm_cloth_crease_t;
+/* n_cloths is 0 (the table may be NULL) or mpm_cloth_count.  All zeros switches yielding off and KEEPS the creases made
+ * so far (mpm_set_crease_state(h, NULL) removes them). */
+MPM_API int mpm_set_creases(mpm_handle_t h, size_t n_cloths, const mpm_cloth_crease_t *per_cloth);
+/* The table as given: min(mpm_cloth_count, capacity) entries into out (zeros while off), the cloth count into *n_out. */
+MPM_API int mpm_get_creases(mpm_handle_t h, mpm_cloth_crease_t *out, size_t capacity, size_t *n_out);
+/* Scissors and restore: psibar[n_hinges] (hinge order of mpm_shell_hinges) replaces every hinge's psibar, so it can
+ * pre-crease a cloth; NULL irons the cloth: every hinge returns to its rest psibar to the bit.  Allowed while every
+ * yield_angle is 0. */
+MPM_API int mpm_set_crease_state(mpm_handle_t h, const float *psibar);
+/* The psibar in force per hinge (psibar_out[n_hinges], may be NULL) and per cloth the number of hinges whose psibar
+ * differs from the rest value in bits: min(cloth count, capacity) entries into creased_per_cloth, the cloth count into
+ * *n_out.  Zeros while off. */
+MPM_API int mpm_crease_state(mpm_handle_t h, float *psibar_out, uint32_t *creased_per_cloth, size_t capacity, size_t *n_out);
+/* The substep's hinge function on the current positions, state untouched: psi, dpsi and the psibar the next substep
+ * would leave, per hinge; each may be NULL. */
+MPM_API int mpm_crease_measure(mpm_handle_t h, float *psi_out, float *dpsi_out, float *psibar_next_out);
+/* The kernel's two inline functions on the host (no handle, no device), hinge by hinge: x12[12 n] = x0, x1, x2, x3;
+ * psibar, y, eta, P [n]; psi_out, dpsi_out, psibar_out [n] and yields_out [n] may each be NULL. */
+MPM_API int mpm_crease_hinge(size_t n, const float *x12, const float *psibar, const float *y, const float *eta, const float *P,
+                             float *psi_out, float *dpsi_out, float *psibar_out, uint8_t *yields_out);
+
 /* ---- Energy, momentum and strain report per cloth (an extension) ----
  * What System::CalcKineticEnergy / CalcPotentialEnergy answer for a Drake plant, and what a caller choosing dt or
  * calibrating a stiffness needs: one device-side reduction instead of seven downloads and a host restatement of the

@@ -1,17 +1,19 @@
 #!/usr/bin/env python3
 """Cost of shell bending (mpm_set_shell_bending) on the bench.py workload (cloth_1m, 16 open sheets): `plain` against
 `flat` (mpm_set_bending on every sheet: k_vforce and k_bend) against `shell` (mpm_set_shell_bending on every sheet:
-k_vforce, k_hinge over every hinge, k_hinge_gather over every vertex).  The stiffness is the one at which dt is a
-quarter of the feature's own guard, so both models act and the trajectory stays stable.
+k_vforce, k_hinge over every hinge, k_hinge_gather over every vertex) against `creased` (the shell engine with
+mpm_set_creases at a yield angle of 1 rad on every sheet: k_crease runs in front of k_hinge, reads every hinge's corners,
+and no hinge yields).  The stiffness is the one at which dt is a quarter of the feature's own guard, so both models act
+and the trajectory stays stable.
 
 Per round every engine runs once, in turn, in one process: mpm_profile_substeps' VFORCE phase (k_vforce and the
 feature's kernels; empty on the plain engine, whose vertex forces are summed inside k_p2g; event time), and the whole
 substep (wall time of mpm_run_substeps, synchronised at the end).  Medians over the rounds; the raw rounds are printed too.
 
-  python scripts/bench_shell.py [--steps 40] [--warmup 10] [--rounds 5] [--engines plain,flat,shell]
+  python scripts/bench_shell.py [--steps 40] [--warmup 10] [--rounds 5] [--engines plain,flat,shell,creased]
 
 Prints one JSON record.  Under `rocprofv3 --kernel-trace --stats -- python scripts/bench_shell.py --engines shell
---rounds 2` the kernel summary gives k_hinge's and k_hinge_gather's own durations.
+--rounds 2` the kernel summary gives k_hinge's and k_hinge_gather's own durations, with `--engines creased` k_crease's.
 """
 import argparse
 import json
@@ -36,6 +38,11 @@ def engine(bits, cloths, kind, dt):
         set_k(1.0)
         set_k(float(np.float32((0.25 * limit() / dt) ** 2)))
         assert dt <= 0.26 * limit()
+    if kind == "creased":
+        from drake_amd import CREASE_DTYPE
+        t = np.zeros(len(cloths), CREASE_DTYPE)
+        t["yield_angle"] = 1.0
+        g.set_creases(t)
     return g
 
 
@@ -77,6 +84,8 @@ def main():
                          vforce_us_rounds=[round(d["vforce"] * 1e3, 2) for d in s["phases"]],
                          substep_us_rounds=[round(float(x), 2) for x in s["substep_us"]],
                          shell_energy=float(g.shell_state()[0].sum()), error_flags=int(st["error_flags"])))
+        if k == "creased":
+            rows[-1]["creased_hinges"] = int(g.crease_state()[1].sum())
         print(json.dumps(rows[-1]), file=sys.stderr, flush=True)
     for r in rows[1:]:
         r["substep_ratio"] = round(r["substep_us"] / rows[0]["substep_us"], 4)
