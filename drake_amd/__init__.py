@@ -14,5 +14,6 @@ from .capi import (MpmError, GpuMpm, load_library, library_path, Material, Colli
                    mesh_is_closed, pressure_vertex_force, SHELL_DTYPE, SHELL_REST_SHAPE, SHELL_REST_FLAT, mesh_hinges,
                    shell_hinge, Anchor, ANCHOR_DTYPE, ANCHOR_TENSION_ONLY, anchor_point, WEAVE_DTYPE, weave,
                    weave_coefficients, weave_face_records, weave_face_axes, TEAR_DTYPE, tear_face, tear_limit_squared,
-                   link_breaks, link_break_squared, rest_shape_check, CREASE_DTYPE, crease, crease_chord, crease_hinge)
+                   link_breaks, link_break_squared, rest_shape_check, CREASE_DTYPE, crease, crease_chord, crease_hinge,
+                   TEAR_CUTS_HINGES, TEAR_VENTS_GAS, mesh_hinge_faces)
 from . import scenes  # noqa: F401

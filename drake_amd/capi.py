@@ -286,6 +286,7 @@ def pressure_vertex_force(g, x_own, x_b, x_c):
 # mpm_cloth_shell_t (8 bytes) as a numpy record: GpuMpm.set_shell_bending takes, and get_shell_bending returns, arrays of
 # it, one per cloth
 SHELL_REST_SHAPE, SHELL_REST_FLAT = 0, 1
+TEAR_CUTS_HINGES, TEAR_VENTS_GAS = 1, 2   # mpm_set_tear_coupling's mask
 SHELL_DTYPE = np.dtype([("stiffness", "<f4"), ("rest", "<u4")])
 assert SHELL_DTYPE.itemsize == 8
 
@@ -304,6 +305,24 @@ def mesh_hinges(indices, n_verts):
             raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
     call(None, 0)
     out = np.zeros((int(n.value), 4), np.int32)
+    call(out, len(out))
+    return out
+
+
+def mesh_hinge_faces(indices, n_verts):
+    """mpm_mesh_hinge_faces: faces A and B (n, 2) int32, cloth-local ids, of every hinge of mesh_hinges, in the same order.
+    Needs no engine and no GPU."""
+    lib = load_library()
+    t = np.ascontiguousarray(indices, np.int32).reshape(-1, 3)
+    n = C.c_size_t()
+
+    def call(out, cap):
+        rc = lib.mpm_mesh_hinge_faces(t.ctypes.data if t.size else None, len(t), int(n_verts), out.ctypes.data if cap else None,
+                                      cap, C.byref(n))
+        if rc:
+            raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    call(None, 0)
+    out = np.zeros((int(n.value), 2), np.int32)
     call(out, len(out))
     return out
 
@@ -650,6 +669,7 @@ SYMBOLS = [
     "mpm_set_weave", "mpm_get_weave", "mpm_weave_axes", "mpm_weave_forces", "mpm_weave_strain", "mpm_weave_energy",
     "mpm_weave_max_stable_dt", "mpm_weave_face_records", "mpm_weave_face_axes",
     "mpm_set_tearing", "mpm_get_tearing", "mpm_set_torn_faces", "mpm_tear_state", "mpm_tear_measure", "mpm_tear_face",
+    "mpm_set_tear_coupling", "mpm_get_tear_coupling", "mpm_shell_cut_hinges", "mpm_pressure_vented", "mpm_mesh_hinge_faces",
     "mpm_set_rest_shape", "mpm_get_rest_shape", "mpm_rest_shape_check",
     "mpm_set_links", "mpm_get_links", "mpm_link_forces", "mpm_link_energy", "mpm_links_max_stable_dt", "mpm_link_force",
     "mpm_set_link_limits", "mpm_get_link_limits", "mpm_set_broken_links", "mpm_link_break_state", "mpm_link_break_measure",
@@ -846,6 +866,11 @@ def load_library(build: bool = True):
         "mpm_tear_state": [vp, vp, vp, sz, P(sz)],
         "mpm_tear_measure": [vp, vp, vp],
         "mpm_tear_face": [sz, vp, vp, vp, vp, vp],
+        "mpm_set_tear_coupling": [vp, C.c_uint32],
+        "mpm_get_tear_coupling": [vp, P(C.c_uint32)],
+        "mpm_shell_cut_hinges": [vp, vp, vp, sz, P(sz)],
+        "mpm_pressure_vented": [vp, vp, sz, P(sz)],
+        "mpm_mesh_hinge_faces": [vp, sz, sz, vp, sz, P(sz)],
         "mpm_set_rest_shape": [vp, vp],
         "mpm_get_rest_shape": [vp, vp, P(C.c_int)],
         "mpm_rest_shape_check": [vp, sz, vp, sz, P(C.c_int32)],
@@ -1270,6 +1295,36 @@ class GpuMpm:
     def tear_face(dminv3, x, L):
         return tear_face(dminv3, x, L)
 
+    def set_tear_coupling(self, mask):
+        """mpm_set_tear_coupling: TEAR_CUTS_HINGES | TEAR_VENTS_GAS -- shell bending and gas pressure on a cloth that tears
+        (a hinge with a torn face carries no moment; a gas cloth with a torn face has gauge 0).  0, the default: refused."""
+        self._ck(self.lib.mpm_set_tear_coupling(self.h, int(mask)))
+
+    def get_tear_coupling(self) -> int:
+        """mpm_get_tear_coupling: the mask in force."""
+        m = C.c_uint32()
+        self._ck(self.lib.mpm_get_tear_coupling(self.h, C.byref(m)))
+        return int(m.value)
+
+    def shell_cut_hinges(self):
+        """mpm_shell_cut_hinges: (cut (n_hinges,) bool per hinge of shell_hinges on the current flags, cut hinges per cloth
+        (n_cloths,) uint32)."""
+        n, nh = C.c_size_t(), C.c_size_t()
+        self._ck(self.lib.mpm_shell_hinges(self.h, None, None, None, 0, C.byref(nh)))
+        self._ck(self.lib.mpm_shell_cut_hinges(self.h, None, None, 0, C.byref(n)))
+        cut, count = np.zeros(int(nh.value), np.uint8), np.zeros(n.value, np.uint32)
+        self._ck(self.lib.mpm_shell_cut_hinges(self.h, _ptr(cut) if cut.size else None, count.ctypes.data if count.size else None,
+                                               len(count), C.byref(n)))
+        return cut.astype(bool), count
+
+    def pressure_vented(self):
+        """mpm_pressure_vented: (n_cloths,) bool, the gas cloths with a torn face on the current flags."""
+        n = C.c_size_t()
+        self._ck(self.lib.mpm_pressure_vented(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, np.uint8)
+        self._ck(self.lib.mpm_pressure_vented(self.h, _ptr(out) if out.size else None, len(out), C.byref(n)))
+        return out.astype(bool)
+
     def set_rest_shape(self, rest_pos):
         """mpm_set_rest_shape: the rest state -- Dm^-1, volumes, masses -- computed again from rest_pos (n_verts, 3) in
         dump_cpu_state's vertex numbering, as mpm_finalize would have on cloths added there; None restores the positions
@@ -1452,6 +1507,10 @@ class GpuMpm:
     @staticmethod
     def mesh_hinges(indices, n_verts):
         return mesh_hinges(indices, n_verts)
+
+    @staticmethod
+    def mesh_hinge_faces(indices, n_verts):
+        return mesh_hinge_faces(indices, n_verts)
 
     @staticmethod
     def shell_hinge(x4, kc, psibar):

@@ -472,11 +472,13 @@ static int pressure_swap(mpm_engine* e, const PressureTable& t, size_t n_cloths,
     if (int rc = rows_upload(e, fresh, t, &next.args)) return rc;
     int4 *d_chunks = nullptr, *d_rg = nullptr, *d_ra = nullptr;
     double* d_partial = nullptr;
+    uint32_t* d_vent = nullptr;
     ClothPressure* d_par = nullptr;
     ClothPressureState* d_state = nullptr;
     int* d_row_cloth = nullptr;
     if (int rc = fresh.alloc(&d_chunks, std::max<size_t>(chunks.size(), 1), false)) return rc;
     if (int rc = fresh.alloc(&d_partial, std::max<size_t>(chunks.size(), 1), true)) return rc;
+    if (int rc = fresh.alloc(&d_vent, std::max<size_t>(chunks.size(), 1), true)) return rc;
     if (int rc = fresh.alloc(&d_rg, std::max<size_t>(nc, 1), false)) return rc;
     if (int rc = fresh.alloc(&d_ra, std::max<size_t>(nc, 1), false)) return rc;
     if (int rc = fresh.alloc(&d_par, std::max<size_t>(nc, 1), true)) return rc;
@@ -494,7 +496,7 @@ static int pressure_swap(mpm_engine* e, const PressureTable& t, size_t n_cloths,
     next.args.row_cloth = d_row_cloth;
     next.args.par = d_par;
     next.args.state = d_state;
-    next.vol = PressureVolumeArgs{d_chunks, d_partial, d_ra, d_par, d_state, 0};
+    next.vol = PressureVolumeArgs{d_chunks, d_partial, d_ra, d_par, d_state, 0, d_vent, nullptr};
     next.d_ranges_gas = d_rg;
     next.n_gas_chunks = n_gas;
     next.n_all_chunks = (int)chunks.size() - n_gas;
@@ -504,7 +506,7 @@ static int pressure_swap(mpm_engine* e, const PressureTable& t, size_t n_cloths,
         const mpm_engine::Pressure& o = e->pressure;
         rows_free(e, o.args);
         void* old[] = {(void*)o.args.row_cloth, (void*)o.vol.chunks, (void*)o.vol.partial, (void*)o.vol.ranges, (void*)o.vol.par,
-                       (void*)o.vol.state, (void*)o.d_ranges_gas};
+                       (void*)o.vol.state, (void*)o.d_ranges_gas, (void*)o.vol.vent};
         for (void* q : old) e->dfree(q);
     }
     e->pressure = next;
@@ -541,6 +543,29 @@ static int set_pressure(mpm_engine* e, size_t n_cloths, const mpm_cloth_pressure
     return pressure_swap(e, t, n_cloths, per_cloth);
 }
 
+// The tear flags as a kernel of the feature behind `bit` (MPM_TEAR_CUTS_HINGES, MPM_TEAR_VENTS_GAS) is to see them in this
+// launch: null unless mpm_set_tear_coupling has set the bit and the tear tables exist.  The pointer is not kept in a
+// feature's own arguments -- tear_apply allocates and frees the array -- so every launch and every query takes a copy of
+// its arguments and sets it there (as anchors_posed builds its own).  Null is the parent arithmetic of every kernel.
+static const uint8_t* coupled_tear_flags(const mpm_engine* e, uint32_t bit) {
+    return (e->tear_coupling & bit) != 0u && e->tear.on() ? e->tear.args.torn : nullptr;
+}
+static PressureVolumeArgs pressure_volume_args(const mpm_engine* e) {
+    PressureVolumeArgs a = e->pressure.vol;
+    a.torn = coupled_tear_flags(e, MPM_TEAR_VENTS_GAS);
+    return a;
+}
+static HingeArgs hinge_args(const mpm_engine* e) {
+    HingeArgs a = e->shell.hinge;
+    a.torn = coupled_tear_flags(e, MPM_TEAR_CUTS_HINGES);
+    return a;
+}
+static CreaseArgs crease_args(const mpm_engine* e) {
+    CreaseArgs a = e->shell.cr;
+    a.torn = coupled_tear_flags(e, MPM_TEAR_CUTS_HINGES);
+    return a;
+}
+
 // V, E, g and the cap of every cloth from the current positions into Pressure::vol.state (stream-ordered; e->dp: no gate)
 static int pressure_measure(mpm_engine* e) {
     mpm_engine::Pressure& ps = e->pressure;
@@ -549,9 +574,10 @@ static int pressure_measure(mpm_engine* e) {
         t.slice_off.assign(1, 0u);
         if (int rc = pressure_swap(e, t, 0, nullptr)) return rc;
     }
+    const PressureVolumeArgs va = pressure_volume_args(e);
     if (ps.n_all_chunks)
-        hipLaunchKernelGGL(k_pressure_volume, dim3((unsigned)ps.n_all_chunks), dim3(256), 0, e->stream, e->dp, ps.vol, ps.n_gas_chunks);
-    if (!e->cloths.empty()) hipLaunchKernelGGL(k_pressure_gauge, dim3((unsigned)e->cloths.size()), dim3(64), 0, e->stream, e->dp, ps.vol);
+        hipLaunchKernelGGL(k_pressure_volume, dim3((unsigned)ps.n_all_chunks), dim3(256), 0, e->stream, e->dp, va, ps.n_gas_chunks);
+    if (!e->cloths.empty()) hipLaunchKernelGGL(k_pressure_gauge, dim3((unsigned)e->cloths.size()), dim3(64), 0, e->stream, e->dp, va);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -615,14 +641,19 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
             par[h] = make_float2(t.kc[h], 0.f);
         }
         int4* d_ids = nullptr;
+        int2* d_faces = nullptr;
         float2* d_par = nullptr;
         float4* d_rec = nullptr;
         if (int rc = fresh.alloc(&d_ids, n, false)) return rc;
+        if (int rc = fresh.alloc(&d_faces, n, false)) return rc;
         if (int rc = fresh.alloc(&d_par, n, false)) return rc;
         if (int rc = fresh.alloc(&d_rec, 4 * n, true)) return rc;
         H2D(e, d_ids, ids.data(), n * sizeof(int4));
         H2D(e, d_par, par.data(), n * sizeof(float2));
-        next.hinge = HingeArgs{d_ids, d_par, d_rec, (int)n};
+        // (faces A and B per hinge as global face ids, for the cut rule of mpm_set_tear_coupling; t.faces2 is [2 hinge])
+        static_assert(sizeof(int2) == 2 * sizeof(int32_t), "int2 layout");
+        H2D(e, d_faces, t.faces2.data(), n * sizeof(int2));
+        next.hinge = HingeArgs{d_ids, d_par, d_rec, (int)n, d_faces, nullptr, (int)e->nf};
         next.args.rec = d_rec;
         next.args.n_hinges = (int)n;
         // psibar: the hinge function on the device, once, on the rest positions -- the psi it writes (plane 0's .w)
@@ -650,7 +681,7 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
         const mpm_engine::Shell& o = e->shell;
         rows_free(e, o.args);
         // (the crease parameters and state go with the hinge table they belonged to: `next` has none)
-        void* old[] = {(void*)o.hinge.ids, (void*)o.hinge.par, (void*)o.hinge.rec, (void*)o.cr.cr};
+        void* old[] = {(void*)o.hinge.ids, (void*)o.hinge.par, (void*)o.hinge.rec, (void*)o.cr.cr, (void*)o.hinge.faces};
         for (void* q : old) e->dfree(q);
     }
     e->shell = next;
@@ -660,7 +691,7 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
 
 // the hinge records of the current positions into Shell::hinge.rec (stream-ordered; e->dp: no gate)
 static int shell_measure(mpm_engine* e) {
-    hipLaunchKernelGGL(k_hinge_eval, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, e->dp, e->shell.hinge);
+    hipLaunchKernelGGL(k_hinge_eval, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, e->dp, hinge_args(e));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -743,7 +774,7 @@ static int crease_apply(mpm_engine* e, std::vector<mpm_cloth_crease_t> table, bo
         FreshArrays fresh(e);
         float4* d_cr = nullptr;
         if (int rc = fresh.alloc(&d_cr, n, false)) return rc;
-        sh.cr = CreaseArgs{sh.hinge.ids, const_cast<float2*>(sh.hinge.par), d_cr, (int)n};
+        sh.cr = CreaseArgs{sh.hinge.ids, const_cast<float2*>(sh.hinge.par), d_cr, (int)n, sh.hinge.faces, nullptr, sh.hinge.n_faces};
         fresh.commit();
     }
     if (sh.creasing()) {
@@ -780,7 +811,7 @@ static int crease_measure(mpm_engine* e, float* psi_out, float* dpsi_out, float*
     const mpm_engine::Shell& sh = e->shell;
     const size_t n = sh.kc.size();
     if (n == 0) return 0;
-    CreaseArgs a = sh.cr;
+    CreaseArgs a = crease_args(e);
     // (the staging buffer: the records where they are made here, 16 bytes per hinge, then three float outputs)
     if (int rc = e->stage(28 * n)) return rc;
     if (!sh.creasing()) {
@@ -788,7 +819,7 @@ static int crease_measure(mpm_engine* e, float* psi_out, float* dpsi_out, float*
         for (size_t h = 0; h < n; ++h) rec[h] = make_float4(0.f, 0.f, 2.f, sh.psibar[h]);
         float4* d_cr = (float4*)e->d_stage;
         H2D(e, d_cr, rec.data(), n * sizeof(float4));
-        a = CreaseArgs{sh.hinge.ids, const_cast<float2*>(sh.hinge.par), d_cr, (int)n};
+        a = CreaseArgs{sh.hinge.ids, const_cast<float2*>(sh.hinge.par), d_cr, (int)n, sh.hinge.faces, a.torn, sh.hinge.n_faces};
     }
     float* d_out = (float*)e->d_stage + 4 * n;
     hipLaunchKernelGGL(k_crease_eval, rows_grid((int)n), dim3(256), 0, e->stream, e->dp, a, d_out, d_out + n, d_out + 2 * n);
@@ -1142,10 +1173,17 @@ static int tear_counts(mpm_engine* e, std::vector<uint32_t>& n) {
 }
 // the feature of cloth c that does not compose with tearing (hinges across a torn face, a hole in a pressurised cloth:
 // out of scope), or null; of several the first in the order of mpm_features.h
+// (mpm_set_tear_coupling lifts two of them: shell bending with MPM_TEAR_CUTS_HINGES, gas mode with MPM_TEAR_VENTS_GAS;
+// quadratic bending and constant pressure stay refused whatever the mask)
+static bool tear_couples_shell(const mpm_engine* e) { return (e->tear_coupling & MPM_TEAR_CUTS_HINGES) != 0u; }
+static bool tear_couples_pressure(const mpm_engine* e, uint32_t mode) {
+    return (e->tear_coupling & MPM_TEAR_VENTS_GAS) != 0u && mode == MPM_PRESSURE_GAS;
+}
 static const char* tear_conflict(const mpm_engine* e, size_t c) {
     if (c < e->bend.k.size() && e->bend.k[c] > 0.f) return FEATURES[F_BENDING].phrase;
-    if (c < e->pressure.set.size() && e->pressure.set[c].mode != MPM_PRESSURE_OFF) return FEATURES[F_PRESSURE].phrase;
-    if (c < e->shell.set.size() && e->shell.set[c].stiffness > 0.f) return FEATURES[F_SHELL].phrase;
+    if (c < e->pressure.set.size() && e->pressure.set[c].mode != MPM_PRESSURE_OFF && !tear_couples_pressure(e, e->pressure.set[c].mode))
+        return FEATURES[F_PRESSURE].phrase;
+    if (c < e->shell.set.size() && e->shell.set[c].stiffness > 0.f && !tear_couples_shell(e)) return FEATURES[F_SHELL].phrase;
     return nullptr;
 }
 // mpm_set_bending, mpm_set_shell_bending, mpm_set_pressure: refused for a cloth c with wants(c) that has a tear limit or
@@ -1298,6 +1336,81 @@ static int tear_faces(size_t n, const float* dminv3, const float* x9, const floa
         if (mq_out) std::memcpy(mq_out + 2 * f, mq, sizeof mq);
         if (fails_out) fails_out[f] = fails ? 1 : 0;
     }
+    return 0;
+}
+
+// ---- tearing composed with shell bending and gas (mpm_set_tear_coupling, mpm_get_tear_coupling, mpm_shell_cut_hinges,
+// mpm_pressure_vented, mpm_mesh_hinge_faces; mpm_shell.h CUT HINGES, mpm_pressure.h VENTED GAS) ----
+// mpm_set_tear_coupling: the mask is checked by the entry point and the owed substeps are settled.  A bit may not be
+// cleared while some cloth holds the combination it permits: a tear limit or a torn face (counted on the device, as
+// tear_refuses does) together with shell k > 0 (MPM_TEAR_CUTS_HINGES) or gas mode (MPM_TEAR_VENTS_GAS).
+static int set_tear_coupling(mpm_engine* e, uint32_t mask) {
+    const uint32_t cleared = e->tear_coupling & ~mask;
+    if (cleared != 0u && e->tear.on()) {
+        std::vector<uint32_t> n;
+        if (int rc = tear_counts(e, n)) return rc;
+        for (size_t c = 0; c < e->cloths.size(); ++c) {
+            if (!(e->tear.limit(c) || n[c] != 0u)) continue;
+            const bool shell = (cleared & MPM_TEAR_CUTS_HINGES) != 0u && c < e->shell.set.size() && e->shell.set[c].stiffness > 0.f;
+            const bool gas = (cleared & MPM_TEAR_VENTS_GAS) != 0u && c < e->pressure.set.size() && e->pressure.set[c].mode == MPM_PRESSURE_GAS;
+            if (shell || gas)
+                return fail(MPM_ERR_INVALID, "mpm_set_tear_coupling: cloth " + std::to_string(c) +
+                                                 " has a tear limit or a torn face (mpm_set_tearing, mpm_set_torn_faces) and " +
+                                                 (shell ? "shell bending (mpm_set_shell_bending)" : "gas pressure (mpm_set_pressure)") +
+                                                 ": " + (shell ? "MPM_TEAR_CUTS_HINGES" : "MPM_TEAR_VENTS_GAS") +
+                                                 " cannot be cleared while it does");
+        }
+    }
+    e->tear_coupling = mask;
+    return 0;
+}
+// mpm_shell_cut_hinges: the hinge records of the current positions and flags (k_hinge_eval), then plane 3's .w per hinge
+static int shell_cut_hinges(mpm_engine* e, uint8_t* cut_out, uint32_t* cut_per_cloth, size_t capacity, size_t* n_out) {
+    const mpm_engine::Shell& sh = e->shell;
+    const size_t n = sh.on() ? (size_t)sh.hinge.n : 0;
+    std::vector<uint32_t> count(e->cloths.size(), 0u);
+    if (n) {
+        if (int rc = shell_measure(e)) return rc;
+        std::vector<float4> plane3(n);
+        D2H(e, plane3.data(), sh.hinge.rec + 3 * n, n * sizeof(float4));
+        for (size_t h = 0; h < n; ++h) {
+            const bool cut = plane3[h].w > 0.f;
+            if (cut_out) cut_out[h] = cut ? 1 : 0;
+            if (cut) count[(size_t)sh.hinge_cloth[h]] += 1u;
+        }
+    }
+    return copy_out(count, cut_per_cloth, capacity, n_out);
+}
+// mpm_pressure_vented: volumes and gauges anew (pressure_measure), then the words k_pressure_volume left per chunk of
+// the list of all cloths, ORed per cloth; a cloth is vented only in gas mode
+static int pressure_vented_cloths(mpm_engine* e, uint8_t* vented_per_cloth, size_t capacity, size_t* n_out) {
+    const size_t nc = e->cloths.size();
+    std::vector<uint8_t> vented(nc, 0);
+    if (coupled_tear_flags(e, MPM_TEAR_VENTS_GAS) && e->pressure.gas()) {
+        if (int rc = pressure_measure(e)) return rc;
+        const mpm_engine::Pressure& ps = e->pressure;
+        std::vector<uint32_t> words((size_t)ps.n_all_chunks);
+        std::vector<int4> chunks((size_t)ps.n_all_chunks);
+        if (ps.n_all_chunks) {
+            D2H(e, words.data(), ps.vol.vent + ps.n_gas_chunks, words.size() * sizeof(uint32_t));
+            D2H(e, chunks.data(), ps.vol.chunks + ps.n_gas_chunks, chunks.size() * sizeof(int4));
+        }
+        for (size_t k = 0; k < words.size(); ++k) {
+            const size_t c = (size_t)chunks[k].x;
+            if (words[k] != 0u && c < ps.set.size() && ps.set[c].mode == MPM_PRESSURE_GAS) vented[c] = 1;
+        }
+    }
+    return copy_out(vented, vented_per_cloth, capacity, n_out);
+}
+// host only: faces A and B of every hinge of mesh_hinges, cloth-local ids
+static int mesh_hinge_faces(const int32_t* indices, size_t n_faces, int32_t* faces2, size_t capacity, size_t* n_out) {
+    std::vector<ShellHinge> H;
+    mesh_hinges(indices, n_faces, H);
+    for (size_t h = 0; h < std::min(capacity, H.size()); ++h) {
+        faces2[2 * h] = H[h].face_a;
+        faces2[2 * h + 1] = H[h].face_b;
+    }
+    if (n_out) *n_out = H.size();
     return 0;
 }
 

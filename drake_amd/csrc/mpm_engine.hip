@@ -212,10 +212,16 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
     if (e->links.on()) hipLaunchKernelGGL(k_link, rows_grid(e->links.args.n_rows), dim3(256), 0, e->stream, p, e->links.args);
     // (an engine with pressure, mpm_set_pressure: where a cloth is in gas mode, the gas cloths' volumes and gauge pressures
     // from the current positions, on the device; then f += the pressure force, one lane per vertex of a pressurised cloth)
+    // TEARING COMPOSED WITH GAS AND SHELL BENDING (mpm_set_tear_coupling).  The order is part of the result: k_tear ran LAST
+    // in launch_fem_faces, in front of every kernel here, so the tear flags these kernels read are this substep's -- a face
+    // that fails in a substep vents its cloth (k_pressure_volume, k_pressure_gauge) and cuts its hinges (k_crease, k_hinge)
+    // in that same substep, whatever the particle order and the determinism mode; a substep that skips itself marks
+    // nothing and changes nothing.  The pointer to the flags goes into a copy of the arguments per launch
+    // (pressure_volume_args, crease_args, hinge_args) and is null while the mode is off: the launches of an engine without it.
     if (e->pressure.on()) {
         const mpm_engine::Pressure& ps = e->pressure;
         if (ps.gas()) {
-            PressureVolumeArgs va = ps.vol;
+            PressureVolumeArgs va = pressure_volume_args(e);
             va.ranges = ps.d_ranges_gas;
             va.only_gas = 1;
             hipLaunchKernelGGL(k_pressure_volume, dim3((unsigned)ps.n_gas_chunks), dim3(256), 0, e->stream, p, va, 0);
@@ -227,9 +233,9 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
     // f += the records of every vertex, one lane per vertex of a cloth with k > 0; while some cloth creases or some hinge
     // is creased, mpm_set_creases / mpm_set_crease_state, k_crease first: one lane per hinge, it owns the psibar k_hinge reads)
     if (e->shell.on() && e->shell.creasing())
-        hipLaunchKernelGGL(k_crease, rows_grid(e->shell.cr.n), dim3(256), 0, e->stream, p, e->shell.cr);
+        hipLaunchKernelGGL(k_crease, rows_grid(e->shell.cr.n), dim3(256), 0, e->stream, p, crease_args(e));
     if (e->shell.on()) {
-        hipLaunchKernelGGL(k_hinge, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, p, e->shell.hinge);
+        hipLaunchKernelGGL(k_hinge, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, p, hinge_args(e));
         hipLaunchKernelGGL(k_hinge_gather, rows_grid(e->shell.args.n_rows), dim3(256), 0, e->stream, p, e->shell.args);
     }
     // (an engine with anchors, mpm_set_anchors: the bodies' poses at their clocks, one lane per motion; then f += the
@@ -2434,6 +2440,46 @@ int mpm_tear_face(size_t n, const float* dminv3, const float* x9, const float* L
     return tear_faces(n, dminv3, x9, L, mq_out, fails_out);
 } MPM_CATCH_ALL
 
+// ---- tearing composed with shell bending and gas (mpm_cloth_host.h; mpm_shell.h, mpm_pressure.h) -------------------------------
+int mpm_set_tear_coupling(mpm_handle_t e, uint32_t mask) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "tear coupling is")) return rc;
+    REQUIRE((mask & ~(MPM_TEAR_CUTS_HINGES | MPM_TEAR_VENTS_GAS)) == 0u, "mpm_set_tear_coupling: unknown bit in the mask");
+    // substeps that mpm_run_substeps deferred are owed with the mode they were enqueued with
+    if (int rc = settle(e)) return rc;
+    return set_tear_coupling(e, mask);
+} MPM_CATCH_ALL
+
+int mpm_get_tear_coupling(mpm_handle_t e, uint32_t* mask_out) try {
+    REQUIRE(e, "null handle");
+    REQUIRE(mask_out, "null output");
+    *mask_out = e->tear_coupling;
+    return 0;
+} MPM_CATCH_ALL
+
+int mpm_shell_cut_hinges(mpm_handle_t e, uint8_t* cut_out, uint32_t* cut_per_cloth, size_t capacity, size_t* n_out) try {
+    READY(e);
+    if (int rc = single_engine_only(e, "mpm_shell_cut_hinges is")) return rc;
+    REQUIRE(cut_per_cloth || capacity == 0, "null output");
+    return shell_cut_hinges(e, cut_out, cut_per_cloth, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_pressure_vented(mpm_handle_t e, uint8_t* vented_per_cloth, size_t capacity, size_t* n_out) try {
+    READY(e);
+    if (int rc = single_engine_only(e, "mpm_pressure_vented is")) return rc;
+    REQUIRE(vented_per_cloth || capacity == 0, "null output");
+    return pressure_vented_cloths(e, vented_per_cloth, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_mesh_hinge_faces(const int32_t* indices, size_t n_faces, size_t n_verts, int32_t* faces2, size_t capacity, size_t* n_out) try {
+    REQUIRE(indices || n_faces == 0, "null indices");
+    REQUIRE(faces2 || capacity == 0, "null output");
+    REQUIRE(n_faces < (size_t)1 << 30, "mesh too large");
+    for (size_t k = 0; k < 3 * n_faces; ++k)
+        REQUIRE(indices[k] >= 0 && (size_t)indices[k] < n_verts, "mpm_mesh_hinge_faces: a vertex id is out of range");
+    return mesh_hinge_faces(indices, n_faces, faces2, capacity, n_out);
+} MPM_CATCH_ALL
+
 // ---- the rest shape apart from the pose (mpm_cloth_host.h; mpm_rest.h) ----------------------------------------------------------
 int mpm_set_rest_shape(mpm_handle_t e, const float* rest_pos) try {
     READY_NO_SETTLE(e);
@@ -2539,7 +2585,10 @@ int mpm_link_breaks(size_t n, const float* xa3, const float* xb3, const float* B
 // ---- enclosed-volume pressure per cloth (mpm_cloth_host.h; mpm_pressure.h) ------------------------------------------------------
 int mpm_set_pressure(mpm_handle_t e, size_t n_cloths, const mpm_cloth_pressure_t* per_cloth) try {
     if (int rc = per_cloth_setter(e, F_PRESSURE, "mpm_set_pressure", n_cloths, per_cloth, "null pressure array")) return rc;
-    if (int rc = tear_refuses(e, n_cloths, "mpm_set_pressure", [&](size_t c) { return per_cloth[c].mode != MPM_PRESSURE_OFF; })) return rc;
+    // (with MPM_TEAR_VENTS_GAS in force, mpm_set_tear_coupling, gas mode alone composes with tearing)
+    if (int rc = tear_refuses(e, n_cloths, "mpm_set_pressure", [&](size_t c) {
+            return per_cloth[c].mode != MPM_PRESSURE_OFF && !tear_couples_pressure(e, per_cloth[c].mode);
+        })) return rc;
     return set_pressure(e, n_cloths, per_cloth);
 } MPM_CATCH_ALL
 
@@ -2583,7 +2632,10 @@ int mpm_pressure_vertex_force(float g, const float* x_own, size_t n, const float
 // ---- shell bending about a curved rest shape (mpm_cloth_host.h; mpm_shell.h) -------------------------------------------------------
 int mpm_set_shell_bending(mpm_handle_t e, size_t n_cloths, const mpm_cloth_shell_t* per_cloth, const float* rest_pos) try {
     if (int rc = per_cloth_setter(e, F_SHELL, "mpm_set_shell_bending", n_cloths, per_cloth, "null shell bending array")) return rc;
-    if (int rc = tear_refuses(e, n_cloths, "mpm_set_shell_bending", [&](size_t c) { return per_cloth[c].stiffness > 0.f; })) return rc;
+    // (with MPM_TEAR_CUTS_HINGES in force, mpm_set_tear_coupling, shell bending composes with tearing)
+    if (int rc = tear_refuses(e, n_cloths, "mpm_set_shell_bending", [&](size_t c) {
+            return per_cloth[c].stiffness > 0.f && !tear_couples_shell(e);
+        })) return rc;
     return set_shell_bending(e, n_cloths, per_cloth, rest_pos);
 } MPM_CATCH_ALL
 

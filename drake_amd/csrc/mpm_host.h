@@ -273,6 +273,9 @@ struct mpm_engine {
         bool on() const { return args.torn != nullptr; }
         bool limit(size_t c) const { return c < t.size() && t[c].stretch_limit > 0.f; }
     } tear;
+    // tearing composed with shell bending and gas (mpm_set_tear_coupling): MPM_TEAR_CUTS_HINGES | MPM_TEAR_VENTS_GAS.  No
+    // state but this mask: cut hinges and vented cloths are functions of tear.args.torn, evaluated in the substep
+    uint32_t tear_coupling = 0u;
     // links between cloth vertices (mpm_set_links; mpm_links.h): a non-empty table switches k_link on behind k_vforce
     struct Links {
         std::vector<mpm_link_t> set;     // the caller's table, as given

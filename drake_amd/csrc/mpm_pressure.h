@@ -33,6 +33,19 @@
 // row's force to DP::f.  Table, chunk list and order are those of the original ids: V, g and the forces are the same
 // bits whatever the particle order.  No atomics but the error flag.
 //
+// VENTED GAS (mpm_set_tear_coupling with MPM_TEAR_VENTS_GAS, mpm_pressure_vented): a cloth in gas mode with at least one
+// torn face (mpm_tear.h) is VENTED: its gauge is +0.0f, its energy 0, capped 0; its volume is still reported.  "Vented" is
+// not stored: k_pressure_volume reads the tear flag of every face it visits (by the same original id, in the same round
+// trip as the corner ids), ORs them along the sum's path and writes one word per chunk beside the partial sum;
+// k_pressure_gauge ORs the cloth's chunks in its fixed order and, if any is set, writes the vented state and does not
+// form a gauge.  Re-evaluated in every substep and in every query from the flags, so a restored cloth
+// (mpm_set_torn_faces) re-inflates by the gas law on its current volume.  k_pressure is unchanged: it reads the state's
+// gauge, and s = 0 / 6 makes every force an exact zero.  k_tear runs with the face kernels, in front of these, so a face
+// that fails in a substep vents its cloth in that same substep.  The pointer to the flags is set per launch and null unless
+// the mode is set and the tear tables exist: null is the arithmetic and the stores of an engine without the mode.
+// NOT MODELLED: a leak rate and partial venting.  One torn face empties the cloth at once, whatever the size of the hole,
+// and pv does not change: the gas is all there again when the faces are restored.
+//
 // Roundings of one component of a row's force, for the bound of tests/pressure.py, in units of 2^-24 of
 // T = |g| / 6 sum_entries |d_b| |d_c|, d_b = x_b - x_i, d_c = x_c - x_i:
 //   one entry's component d_b[j] d_c[k] - d_b[k] d_c[j]: each product carries its two differences (1 + 1) and its own
@@ -125,6 +138,15 @@ MPM_PRESSURE_FN ClothPressureState pressure_gauge(const ClothPressure& q, double
     }
     return s;
 }
+// ... of a VENTED cloth (the header, VENTED GAS): the volume is reported, the gauge is +0, the energy 0, no cap
+MPM_PRESSURE_FN ClothPressureState pressure_vented(double V) {
+    ClothPressureState s;
+    s.volume = V;
+    s.energy = 0.0;
+    s.gauge = 0.f;
+    s.capped = 0u;
+    return s;
+}
 
 }  // namespace mpm
 
@@ -149,6 +171,8 @@ struct PressureVolumeArgs {
     const ClothPressure* par;    // [cloth], or null: no cloth is pressurised
     ClothPressureState* state;   // [cloth]
     int only_gas;                // the substep's launch: the cloths in gas mode alone are written
+    uint32_t* vent;              // [chunk] beside `partial`: non-zero where a face of the chunk is torn (written while torn != null)
+    const uint8_t* torn;         // [original face id] TearArgs::torn, set per launch (the header, VENTED GAS); nullptr: nothing vents
 };
 
 // Row r of the table on the current positions.  Every index into a per-particle array comes through DP::imap from an id
@@ -258,6 +282,7 @@ __global__ __launch_bounds__(256) void k_pressure_volume(DP p, PressureVolumeArg
     static_assert(PRESSURE_CHUNK == 4 * 256, "four ids per lane");
     if (gated_out(p)) return;
     __shared__ double sh[4];
+    __shared__ uint32_t shv[4];
     const int k = base + (int)blockIdx.x;
     const int4 ch = a.chunks[k];
     const int cur = p.ctl->cur;
@@ -266,12 +291,15 @@ __global__ __launch_bounds__(256) void k_pressure_volume(DP p, PressureVolumeArg
     bool ok[4];
     int c[4][3], s[4][3];
     float4 x[4][3];
+    uint8_t flag[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int u = 0; u < 4; ++u) {
         const int id = ch.y + (int)threadIdx.x + 256 * u;
         ok[u] = id < ch.z;
         c[u][0] = c[u][1] = c[u][2] = -1;
         if (!ok[u]) continue;
+        // (the face's tear flag, by the same original id and in the same round trip as its corner ids)
+        if (a.torn) flag[u] = a.torn[id];
         if (p.idx_orig[0]) {
             c[u][0] = p.idx_orig[0][id]; c[u][1] = p.idx_orig[1][id]; c[u][2] = p.idx_orig[2][id];
         } else {   // (a rank that gave the scene's tables back keeps the corners' ids per slot)
@@ -313,9 +341,20 @@ __global__ __launch_bounds__(256) void k_pressure_volume(DP p, PressureVolumeArg
 #pragma unroll
     for (int off = 1; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
     if ((threadIdx.x & 63u) == 0u) sh[threadIdx.x >> 6] = acc;
+    // (the chunk's flags, ORed along the sum's path: through the wave, then the four waves through the LDS)
+    uint32_t any = 0u;
+    if (a.torn) {   // (a kernel argument: the same in every lane)
+        any = (uint32_t)(flag[0] | flag[1] | flag[2] | flag[3]);
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) any |= __shfl_xor(any, off);
+        if ((threadIdx.x & 63u) == 0u) shv[threadIdx.x >> 6] = any;
+    }
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
     __syncthreads();
-    if (threadIdx.x == 0u) a.partial[k] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+    if (threadIdx.x == 0u) {
+        a.partial[k] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+        if (a.torn) a.vent[k] = ((shv[0] | shv[1]) | shv[2]) | shv[3];
+    }
 }
 
 // One workgroup (one wave) per cloth: lane r < PRESSURE_RUNS adds its run of the cloth's chunk sums in ascending order,
@@ -323,6 +362,7 @@ __global__ __launch_bounds__(256) void k_pressure_volume(DP p, PressureVolumeArg
 __global__ __launch_bounds__(64) void k_pressure_gauge(DP p, PressureVolumeArgs a) {
     if (gated_out(p)) return;
     __shared__ double sh[PRESSURE_RUNS];
+    __shared__ uint32_t shv[PRESSURE_RUNS];
     const int c = (int)blockIdx.x;
     ClothPressure par;
     par.mode = PRESSURE_OFF;
@@ -337,12 +377,21 @@ __global__ __launch_bounds__(64) void k_pressure_gauge(DP p, PressureVolumeArgs 
         const int k1 = min(n, (run + 1) * per);
         for (int k = run * per; k < k1; ++k) acc += a.partial[rg.x + k];
         sh[run] = acc;
+        if (a.torn) {   // (the chunks' flags in the same fixed order)
+            uint32_t any = 0u;
+            for (int k = run * per; k < k1; ++k) any |= a.vent[rg.x + k];
+            shv[run] = any;
+        }
     }
     __syncthreads();
     if (threadIdx.x == 0u) {
         double t = sh[0];
         for (int r = 1; r < PRESSURE_RUNS; ++r) t += sh[r];
-        a.state[c] = pressure_gauge(par, t / 6.0);
+        uint32_t any = 0u;
+        if (a.torn)
+            for (int r = 0; r < PRESSURE_RUNS; ++r) any |= shv[r];
+        if (any != 0u && par.mode == PRESSURE_GAS) a.state[c] = pressure_vented(t / 6.0);
+        else a.state[c] = pressure_gauge(par, t / 6.0);
     }
 }
 

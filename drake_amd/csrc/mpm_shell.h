@@ -46,7 +46,21 @@
 // sum_j |Gbar_hj|), Gershgorin on the Gauss-Newton part of the stiffness, kc dpsi^2 G G^T, taken AT THE REST SHAPE
 // (max_row_rate).  It does not cover the geometric stiffness (psi - psibar) d(dpsi G) / dx of a deformed hinge, nor a
 // deformed hinge's larger |G| (|G2| = |e| / |nA| grows as a triangle collapses): a guard, not a guarantee.  How
-// conservative it is has not been measured.
+// conservative it is has not been measured.  It is NOT recomputed when hinges are cut (below) and stays a bound: every term
+// of a row's Gershgorin sum is non-negative, so a row that loses hinges only loses terms.
+//
+// CUT HINGES (mpm_set_tear_coupling with MPM_TEAR_CUTS_HINGES, mpm_shell_cut_hinges): on a cloth that tears (mpm_tear.h) a
+// hinge one of whose two faces is torn carries no moment.  "Cut" is not stored: it is torn[face A] | torn[face B],
+// evaluated by k_hinge and k_crease in every substep from the tear flags (one byte per original face id) through a
+// host-built table of the hinges' two GLOBAL face ids (HingeArgs::faces), so scissors and restore (mpm_set_torn_faces)
+// need no code of their own and a re-sort moves nothing.  A cut hinge is an unusable one: its four records are +0, its
+// psi 0, its energy term 0, plane 2's .w 0 (it counts as inactive); plane 3's .w, spare until now, is 1 for it and 0
+// otherwise, which is where mpm_shell_cut_hinges reads the cut state.  k_crease: a cut hinge does not yield and keeps its
+// psibar, so a hinge restored by mpm_set_torn_faces acts again with the psibar it had.  The pointer to the flags is put
+// into a copy of the arguments per launch and is null unless the mode is set and the tear tables exist: a null pointer is
+// the arithmetic, the loads and the stores of an engine without the mode.  ORDER: k_tear runs last of the face kernels,
+// k_crease and k_hinge among the vertex kernels behind them, so a face that fails in a substep cuts its hinges in that
+// same substep.  k_hinge_gather is unchanged.
 //
 // Roundings of one component of one record, for the bound of tests/shell_bending.py, first order, in units of 2^-24 of
 //   T = |kc| |G_hj| (kappa_A + kappa_B) (1 + |psi| + |psibar|),   kappa_A = |e| |a| / |nA|,  kappa_B = |e| |b| / |nB|
@@ -267,8 +281,12 @@ namespace mpm {
 struct HingeArgs {
     const int4* ids;     // [hinge] particle ids (NfG + vertex) of x0, x1, x2, x3
     const float2* par;   // [hinge] (kc, psibar)
-    float4* rec;         // [4][n] the corner records; .w: psi (plane 0), the energy term (1), 1 where the hinge acts (2)
+    float4* rec;         // [4][n] the corner records; .w: psi (plane 0), the energy term (1), 1 where the hinge acts (2),
+                         // 1 where the hinge is cut (3)
     int n;
+    const int2* faces;     // [hinge] faces A and B, GLOBAL original face ids (the cloth's first face + the cloth-local id)
+    const uint8_t* torn;   // [n_faces] TearArgs::torn, set per launch (the header, CUT HINGES); nullptr: no hinge is cut
+    int n_faces;           // what a face id is checked against before it indexes `torn`
 };
 struct ShellArgs {
     const int* row_pid;          // [n_rows] particle id (NfG + vertex) of the row's vertex, ascending
@@ -280,36 +298,51 @@ struct ShellArgs {
 };
 
 // the four planes of hinge h from four positions (what k_hinge, k_hinge_eval and k_hinge_rest share)
-MPM_DEV void hinge_store(const HingeArgs& a, int h, const float4 x[4], bool usable) {
+MPM_DEV void hinge_store(const HingeArgs& a, int h, const float4 x[4], bool usable, bool cut = false) {
     const float2 q = a.par[h];
     const float X[4][3] = {{x[0].x, x[0].y, x[0].z}, {x[1].x, x[1].y, x[1].z}, {x[2].x, x[2].y, x[2].z}, {x[3].x, x[3].y, x[3].z}};
     float rec[4][3], psi;
     const bool on = shell_hinge(X[0], X[1], X[2], X[3], q.x, q.y, rec, &psi) && usable;
-    const float w[4] = {on ? psi : 0.f, on ? shell_energy_term(q.x, q.y, psi) : 0.f, on ? 1.f : 0.f, 0.f};
+    const float w[4] = {on ? psi : 0.f, on ? shell_energy_term(q.x, q.y, psi) : 0.f, on ? 1.f : 0.f, cut ? 1.f : 0.f};
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-        a.rec[(size_t)j * (size_t)a.n + (size_t)h] = on ? make_float4(rec[j][0], rec[j][1], rec[j][2], w[j]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        a.rec[(size_t)j * (size_t)a.n + (size_t)h] = on ? make_float4(rec[j][0], rec[j][1], rec[j][2], w[j]) : make_float4(0.f, 0.f, 0.f, j == 3 ? w[3] : 0.f);
+}
+
+// Whether hinge h is CUT on the flags `torn` (the header, CUT HINGES): the flags of its two faces, read by the ids fc of
+// the host-built table.  An id outside [0, n_faces) is reported through `ok`, never used as an address, and cuts nothing.
+// The two byte loads depend on the table alone, not on a slot or a position: a caller issues them beside its slot loads.
+MPM_DEV bool hinge_cut(const uint8_t* torn, int n_faces, const int2& fc, bool& ok) {
+    const bool ids = fc.x >= 0 && fc.x < n_faces && fc.y >= 0 && fc.y < n_faces;
+    ok = ok && ids;
+    const uint8_t ta = ids ? torn[fc.x] : (uint8_t)0, tb = ids ? torn[fc.y] : (uint8_t)0;
+    return (ta | tb) != 0;
 }
 
 // Hinge h on the current positions.  Every index into a per-particle array comes through DP::imap from an id of the
 // host-built table; an id outside the particle numbering or a slot that is no vertex slot is reported, never used as an
 // address: the hinge's records are then exact zeros.
+// While a.torn is set the hinge's two face ids come with the vertex ids (the first round trip) and the faces' two flags
+// with the slots (the second): still three round trips of independent loads.
 MPM_DEV void hinge_on_state(const DP& p, const PSet& S, const HingeArgs& a, int h, bool& bad) {
     const int4 id = a.ids[h];
+    int2 fc = make_int2(0, 0);
+    if (a.torn) fc = a.faces[h];
     const int c[4] = {id.x, id.y, id.z, id.w};
     int s[4];
-    bool ok = true;
+    bool ok = true, cut = false;
 #pragma unroll
     for (int j = 0; j < 4; ++j) ok = ok && c[j] >= p.NfG && c[j] < p.NpG;
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] = ok ? p.imap[c[j]] : -1;
+    if (a.torn) cut = hinge_cut(a.torn, a.n_faces, fc, ok);
 #pragma unroll
     for (int j = 0; j < 4; ++j) ok = ok && s[j] >= p.Nf && s[j] < p.Np;
     float4 x[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) x[j] = ok ? S.q[0][s[j]] : make_float4(0.f, 0.f, 0.f, 0.f);
     bad |= !ok;
-    hinge_store(a, h, x, ok);
+    hinge_store(a, h, x, ok && !cut, cut);
 }
 
 // Behind k_pressure (and k_vforce, k_bend, k_bend_damp, k_link) on the same stream, with the substep's DP: a substep that
@@ -352,22 +385,36 @@ struct CreaseArgs {
     float2* par;        // HingeArgs::par of the same table: .y is the psibar in force, which k_crease owns
     const float4* cr;   // [hinge] (y, eta, P, psibar0) of the hinge's cloth and rest shape; nullptr: the tables do not exist
     int n;
+    const int2* faces;     // HingeArgs::faces
+    const uint8_t* torn;   // HingeArgs::torn, set per launch; nullptr: no hinge is cut
+    int n_faces;
 };
 
 // Hinge h's psi, dpsi and the psibar the substep leaves, on the current positions: ids and psibar, slots, positions --
 // three round trips of independent loads, the checks of hinge_on_state.  A bad id is reported, never used as an address,
 // and the hinge then does not yield (psi = dpsi = 0, next = its psibar).  Returns whether the hinge yields.
+// While a.torn is set, the face ids come with the vertex ids and the two flags with the slots, as in hinge_on_state; a
+// CUT hinge loads no position: it does not yield and keeps its psibar (psi = dpsi = 0, next = its psibar).
 MPM_DEV bool crease_on_state(const DP& p, const PSet& S, const CreaseArgs& a, int h, const float4& c, float& psi, float& dpsi,
                              float& next, bool& bad) {
     const int4 id = a.ids[h];
     const float psibar = a.par[h].y;
+    int2 fc = make_int2(0, 0);
+    if (a.torn) fc = a.faces[h];
     const int q[4] = {id.x, id.y, id.z, id.w};
     int s[4];
-    bool ok = true;
+    bool ok = true, cut = false;
 #pragma unroll
     for (int j = 0; j < 4; ++j) ok = ok && q[j] >= p.NfG && q[j] < p.NpG;
 #pragma unroll
     for (int j = 0; j < 4; ++j) s[j] = ok ? p.imap[q[j]] : -1;
+    if (a.torn) cut = hinge_cut(a.torn, a.n_faces, fc, ok);
+    if (cut) {
+        bad |= !ok;
+        psi = dpsi = 0.f;
+        next = psibar;
+        return false;
+    }
 #pragma unroll
     for (int j = 0; j < 4; ++j) ok = ok && s[j] >= p.Nf && s[j] < p.Np;
     float4 x[4];
@@ -634,6 +681,7 @@ struct ShellTable : RowTable<uint32_t> {   // the gather table: one row per vert
     std::vector<int32_t> ids4;      // [4 hinge] vertex ids (0-based over all cloths) of x0, x1, x2, x3
     std::vector<float> kc;          // [hinge] float(k cbar)
     std::vector<int> hinge_cloth;   // [hinge]
+    std::vector<int32_t> faces2;    // [2 hinge] faces A and B as GLOBAL face ids: the cloth's first_face + the cloth-local id
     std::vector<int> row_vertex;    // [row] its vertex
     std::vector<double> rate_sum;   // [row] sum_h kc dpsibar^2 |Gbar_hi| sum_j |Gbar_hj| (the guard)
 };
@@ -685,6 +733,8 @@ inline bool shell_table(const std::vector<Cloth>& cloths, const int* h_idx, size
             }
             out.kc.push_back(kc);
             out.hinge_cloth.push_back((int)c);
+            out.faces2.push_back((int32_t)(cl.first_face + (size_t)h.face_a));
+            out.faces2.push_back((int32_t)(cl.first_face + (size_t)h.face_b));
         }
     }
     RowTable<uint32_t> rows;

@@ -275,6 +275,34 @@ struct GpuMpmState {
         mpm_check(mpm_tear_measure(h_, mq.data(), would_fail ? would_fail->data() : nullptr));
         return mq;
     }
+    // Extension: tearing composed with shell bending and gas (mpm_set_tear_coupling) -- MPM_TEAR_CUTS_HINGES: a hinge with
+    // a torn face carries no moment; MPM_TEAR_VENTS_GAS: a gas cloth with a torn face has gauge 0.  0, the default, keeps
+    // both combinations refused.
+    void SetTearCoupling(uint32_t mask) { mpm_check(mpm_set_tear_coupling(h_, mask)); }
+    uint32_t GetTearCoupling() const {
+        uint32_t mask = 0;
+        mpm_check(mpm_get_tear_coupling(h_, &mask));
+        return mask;
+    }
+    // one byte per hinge of the table in force (n_hinges: mpm_shell_hinges' count): 1 where the hinge is cut on the current
+    // flags; counts: null, or the cut hinges per cloth
+    std::vector<uint8_t> ShellCutHinges(size_t n_hinges, std::vector<uint32_t>* counts = nullptr) const {
+        size_t n = 0;
+        mpm_check(mpm_shell_cut_hinges(h_, nullptr, nullptr, 0, &n));
+        std::vector<uint8_t> cut(n_hinges);
+        std::vector<uint32_t> c(n);
+        mpm_check(mpm_shell_cut_hinges(h_, cut.data(), c.data(), n, &n));
+        if (counts) counts->swap(c);
+        return cut;
+    }
+    // per cloth: 1 where a gas cloth is vented on the current flags
+    std::vector<uint8_t> PressureVented() const {
+        size_t n = 0;
+        mpm_check(mpm_pressure_vented(h_, nullptr, 0, &n));
+        std::vector<uint8_t> v(n);
+        mpm_check(mpm_pressure_vented(h_, v.data(), n, &n));
+        return v;
+    }
     // Extension: the rest shape apart from the pose (mpm_set_rest_shape) -- Dm^-1, volumes and masses computed again from
     // rest_pos (3 floats per vertex in the numbering of DumpCpuState), as Finalize would have on cloths added there; the
     // state and the particle order stay.  Mass follows the rest shape.  Refused while a table derived from the rest shape

@@ -964,7 +964,7 @@ MPM_API int mpm_weave_face_axes(size_t n, const float *rest_x9, const float *dir
  * cloth with a tear limit or a torn face may not have bending stiffness > 0 (mpm_set_bending), shell bending
  * stiffness > 0 (mpm_set_shell_bending) or a pressure mode other than off (mpm_set_pressure) -- whichever call comes
  * second returns MPM_ERR_INVALID and names the other; a cloth without limit and without torn faces in the same
- * engine keeps them all.  (Hinges across a torn face are left to a later extension.)
+ * engine keeps them all -- unless mpm_set_tear_coupling (below) lifts the refusal for shell bending or for gas mode.
  * mpm_weave_forces, mpm_weave_energy and mpm_damping_forces keep reporting what those features alone would give on
  * every face, torn or not.  mpm_measure and mpm_face_strain: a torn face adds nothing to the three strain energies and
  * is left out of the stretch extremes (mpm_face_strain reports its s1, s2, r22 and 0 for its energy); its mass, momenta
@@ -1000,6 +1000,50 @@ MPM_API int mpm_tear_measure(mpm_handle_t h, float *mq_out, uint8_t *would_fail_
  * the corners' positions ([corner][component]), L[n] the squared limit as a float; mq_out[2 n] = (m, q),
  * fails_out[n] = (h < 0) || (q > h h) as it stands (the caller decides what L = 0 means); either output may be NULL. */
 MPM_API int mpm_tear_face(size_t n, const float *dminv3, const float *x9, const float *L, float *mq_out, uint8_t *fails_out);
+
+/* ---- Tearing composed with shell bending and gas: cut hinges, vented cloths (a mode of the engine) ----
+ * Paper and foil bend, keep creases and rip; a balloon bursts.  By default a cloth that may tear can have neither
+ * shell bending nor pressure (above).  mpm_set_tear_coupling switches on, per engine, the rule for where they meet:
+ *   MPM_TEAR_CUTS_HINGES  shell bending (mpm_set_shell_bending, creases included) on a cloth that tears: a hinge one of
+ *                         whose two faces is torn is CUT -- it carries no moment: its four corner records are +0, its psi
+ *                         0, its energy term 0, mpm_shell_state counts it as inactive; it does not yield and keeps its
+ *                         psibar (mpm_set_creases), so a hinge restored by mpm_set_torn_faces acts again with the psibar
+ *                         it had.
+ *   MPM_TEAR_VENTS_GAS    gas mode (MPM_PRESSURE_GAS) on a cloth that tears: a cloth with at least one torn face is
+ *                         VENTED -- its gauge is +0.0f, its energy 0, capped 0, every pressure force an exact zero; its
+ *                         volume is still reported.
+ * Neither is stored: both are functions of the tear flags, evaluated in every substep and in every query
+ * (mpm_shell_forces, mpm_shell_state, mpm_crease_measure, mpm_pressure_forces, mpm_pressure_state), so scissors and
+ * restore work as they are and a restored cloth re-inflates by the gas law on its current volume.  The tearing kernel
+ * runs last of the face kernels, the hinge and pressure kernels behind it: a face that fails in a substep cuts its hinges
+ * and vents its cloth IN THAT SAME SUBSTEP, whatever the particle order and the determinism mode; a substep that skips
+ * itself changes nothing.
+ * NOT MODELLED: a leak rate and partial venting (one torn face empties the cloth at once; pv does not change).  Still
+ * refused, whatever the mask, with the messages above: quadratic bending k > 0 (mpm_set_bending; its matrix is
+ * assembled per vertex row and a hinge cannot be taken out of it -- MPM_SHELL_REST_FLAT is the same model's
+ * continuation) and MPM_PRESSURE_CONSTANT on a cloth that tears.  mpm_shell_max_stable_dt is unchanged and stays a bound:
+ * a row's Gershgorin sum only loses non-negative terms when hinges are cut.
+ * The default is 0: every call, message and launch is that of an engine without this call, and so it is with a bit set
+ * while no cloth holds the combination.  mpm_set_tear_coupling needs mpm_finalize and runs the substeps that
+ * mpm_run_substeps still owes first, with the mode they were enqueued with.  Refused with MPM_ERR_INVALID, nothing
+ * changed: a call before mpm_finalize; an unknown bit; a partitioned or multi-rank engine; clearing a bit while some
+ * cloth holds the combination that bit permits -- a tear limit or a torn face (counted on the device) together with
+ * shell k > 0 (MPM_TEAR_CUTS_HINGES) or gas mode (MPM_TEAR_VENTS_GAS); the message names the cloth and both calls. */
+#define MPM_TEAR_CUTS_HINGES 1u   /* shell bending on a cloth that tears: a hinge with a torn face carries no moment */
+#define MPM_TEAR_VENTS_GAS   2u   /* gas pressure on a cloth that tears: a cloth with a torn face has gauge 0 */
+MPM_API int mpm_set_tear_coupling(mpm_handle_t h, uint32_t mask);
+MPM_API int mpm_get_tear_coupling(mpm_handle_t h, uint32_t *mask_out);
+/* per hinge of mpm_shell_hinges: 1 where the hinge is cut on the current flags (cut_out, one byte for EVERY hinge of the
+ * table, may be NULL); counts per cloth: min(cloth count, capacity) entries into cut_per_cloth, the cloth count into
+ * *n_out.  Zeros while MPM_TEAR_CUTS_HINGES is not set.  Changes no state. */
+MPM_API int mpm_shell_cut_hinges(mpm_handle_t h, uint8_t *cut_out, uint32_t *cut_per_cloth, size_t capacity, size_t *n_out);
+/* per cloth: 1 where the cloth is vented on the current flags; min(cloth count, capacity) entries, the cloth count into
+ * *n_out.  Zeros while MPM_TEAR_VENTS_GAS is not set.  Changes no state. */
+MPM_API int mpm_pressure_vented(mpm_handle_t h, uint8_t *vented_per_cloth, size_t capacity, size_t *n_out);
+/* host only: faces A and B of every hinge of mpm_mesh_hinges, same order, cloth-local ids: min(n, capacity) pairs into
+ * faces2 (may be NULL when capacity is 0), the hinge count into *n_out.  MPM_ERR_INVALID for an id out of range. */
+MPM_API int mpm_mesh_hinge_faces(const int32_t *indices, size_t n_faces, size_t n_verts, int32_t *faces2, size_t capacity,
+                                 size_t *n_out);
 
 /* ---- Rest shape apart from the initial pose: pre-strained and re-shaped cloth (an extension) ----
  * mpm_finalize takes the pose the cloths were added in as their stress-free shape.  mpm_set_rest_shape computes the rest
@@ -1279,7 +1323,8 @@ MPM_API int mpm_anchor_point(const mpm_body_motion_t *motion, double t, const fl
  * that is not closed and consistently wound (the message names the cloth and the first offending edge, vertex ids in
  * the numbering of mpm_dump_cpu_state); gas on a rest volume <= 0; a table that does not fit 2^31 records; any
  * partitioned or multi-rank engine -- this call on such an engine, and mpm_dist_init, the halo, chain, team and world
- * substeps on an engine with pressure. */
+ * substeps on an engine with pressure; a mode other than off on a cloth with a tear limit or a torn face
+ * (mpm_set_tearing), unless mpm_set_tear_coupling with MPM_TEAR_VENTS_GAS permits gas mode there. */
 #define MPM_PRESSURE_OFF 0u
 #define MPM_PRESSURE_CONSTANT 1u
 #define MPM_PRESSURE_GAS 2u
@@ -1367,7 +1412,9 @@ MPM_API int mpm_pressure_vertex_force(float g, const float x_own[3], size_t n, c
  * Refused with MPM_ERR_INVALID, the previous table staying in force and nothing enqueued: a call before mpm_finalize; a
  * wrong n_cloths; a negative or non-finite stiffness; an unknown rest; a non-finite rest_pos; a zero rest area or a zero
  * rest edge at a hinge of a cloth with k > 0 (the message names the face); any partitioned or multi-rank engine -- this
- * call on such an engine, and mpm_dist_init, the halo, chain, team and world substeps on an engine with it on. */
+ * call on such an engine, and mpm_dist_init, the halo, chain, team and world substeps on an engine with it on; k > 0 on
+ * a cloth with a tear limit or a torn face (mpm_set_tearing), unless mpm_set_tear_coupling with MPM_TEAR_CUTS_HINGES
+ * permits it. */
 #define MPM_SHELL_REST_SHAPE 0u   /* psibar from rest_pos where given, else from the mesh as added */
 #define MPM_SHELL_REST_FLAT 1u    /* psibar = 0 */
 typedef struct mpm_cloth_shell {
