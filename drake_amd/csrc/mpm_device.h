@@ -41,6 +41,12 @@ constexpr unsigned ERR_SLABS = 32u;     // the re-sort made more work items than
 //   fq[3] = (0, v0, v1, v2)   v* = slots of the three corner vertices (int bits)
 //   c8    = C8 of the face particle as GridToParticle left it: k_fem reads it here instead of fetching
 //           the 16-byte record q[1] for 4 useful bytes (q[1].w carries the same value for ParticleToGrid)
+// Between the substeps of one batch (DP::lean_g2p) fq[1] and f8 -- F's in-plane columns, 20 of the 36 bytes -- are NOT
+// kept current: they are e Dm^-1 of the corner positions the last k_fem gathered (fem_inplane below), so the next k_fem
+// forms them again from those positions, which k_g2p leaves per VERTEX slot in
+//   xp[slot - Nf] = the vertex's q[0] record as the last lean k_g2p loaded it (the position k_fem gathered in that substep)
+// 16 bytes per vertex, gathered through the L2 by the six faces around it, for 20 bytes written and 20 read per face
+// (there are twice as many faces as vertices).  Ctl::f_inplane_stale says which of the two holds: see there.
 constexpr unsigned VF_MARK = 0x7FB0A5C3u;   // (a NaN pattern: see DP::VF)
 // entry (rank j, vertex k) of DP::VF, in units of 12-byte entries: vertices in chunks of 32, a chunk's eight rank planes
 // next to each other (8 x 384 bytes = 24 full 128-byte lines)
@@ -64,6 +70,7 @@ struct PSet {
     float4* fq[4];
     float* f8;
     float* c8;
+    float4* xp;    // [vertex slot - Nf], see above (moved by the re-sort; only a single-domain engine has it)
 };
 
 MPM_DEV void unpack_C(const float4& q1, const float4& q2, const float4& q3, float* C) {
@@ -109,6 +116,13 @@ struct Ctl {
     // minimum over the particles this rank holds (k_dist_mig_reduce).  The ranks agree on the minimum and migrate again
     // when half of it has passed (mpm_chain_substeps, drake_amd/dist.py: DomainChain).
     float mig_quiet;
+    // 1: fq[1] / f8 (F's in-plane columns) in memory are older than the state: the last substep that ran was a lean one
+    // (DP::lean_g2p), whose k_fem did not store them and whose k_g2p left the corner positions they are made of in
+    // PSet::xp.  Written by thread 0 of every k_g2p that runs (lean: 1, full: 0) and by nothing else, read by the k_fem of
+    // the NEXT substep that runs -- never written while a k_fem is in flight.  The truth lives here and not on the host
+    // because gated substeps skip themselves: a skipped substep leaves the flag and both kinds of storage alone, and the
+    // non-lean substeps that settle() runs on top of a lean one find 1 here.  0 from mpm_finalize on.
+    int f_inplane_stale;
 };
 
 // Partitioned domain: ranks cut ONE domain into x slabs at block boundaries.  Every
@@ -188,7 +202,13 @@ struct DP {
                            // enqueued): k_rb_finish does not move the x / v records of face particles; per launch
     int lean_g2p;          // 1: another substep of the same mpm_run_substeps batch follows, nobody can look at the state
                            // in between: k_g2p leaves the x / v records of the face particles alone (see g2p_particle),
-                           // k_p2g keeps the vertex forces of its work items in LDS only; per substep
+                           // k_p2g keeps the vertex forces of its work items in LDS only, k_fem does not store F's in-plane
+                           // columns (fq[1], f8) and k_g2p leaves the vertex positions they are made of in PSet::xp instead
+                           // (Ctl::f_inplane_stale); per substep.  Off in a partitioned domain.
+                           // Everything that reads a face's x / v records, the vertex forces or the full F from memory --
+                           // downloads, mpm_measure, the migration's records, an upload followed by a substep -- runs
+                           // behind a non-lean substep or a settle(): the last substep of every batch is full, and the
+                           // substeps settle() repeats are.  (The re-sort MOVES fq[1], f8 and xp, stale or not.)
     int fem_fast;          // mpm_set_fast_math: k_fem<1> runs (the re-sort forms a face's centroid the way k_fem will)
     float anticip;         // re-sort: cells a particle is binned ahead per unit of velocity (0 = by position), see k_rb_count
     // fixed-point scales of the LDS tile accumulators (powers of two), see k_p2g
@@ -296,10 +316,29 @@ MPM_DEV int diag_flags(const DP& p) { return MPM_DIAG ? p.dbg : 0; }
 // The deformation gradient of a face (row-major F[0..8]) in its three planes: fq[0] = (F2, F5, F8, F0), fq[1] = (F1, F3,
 // F4, F6), f8 = F7.  The normal column F[:,2] comes first and together: it is the factor b of tau = a (x) b that
 // k_p2g needs, which reads it from here instead of from a second copy (8 bytes per face less for k_fem to write).
-MPM_DEV void pack_F(const float* F, float4& r0, float4& r1, float& r2) {
-    r0 = make_float4(F[2], F[5], F[8], F[0]);
+// pack_F_normal: the record k_fem stores in EVERY substep; pack_F_inplane: the two a lean substep leaves out (see PSet).
+MPM_DEV void pack_F_normal(const float* F, float4& r0) { r0 = make_float4(F[2], F[5], F[8], F[0]); }
+MPM_DEV void pack_F_inplane(const float* F, float4& r1, float& r2) {
     r1 = make_float4(F[1], F[3], F[4], F[6]);
     r2 = F[7];
+}
+MPM_DEV void pack_F(const float* F, float4& r0, float4& r1, float& r2) {
+    pack_F_normal(F, r0);
+    pack_F_inplane(F, r1, r2);
+}
+// F's in-plane columns (entries 0, 1, 3, 4, 6, 7 of F) of a face with corners x0, x1, x2 and Dm^-1 = [Dm0 Dm1; 0 Dm3]:
+// e Dm^-1 with e = the two edges from corner 0 (the Dm^-1[2] = 0 terms are left out).  ONE statement of it, with the fused
+// multiply-add spelt out: k_fem forms them for the state it stores and, behind a lean substep, AGAIN for the substep
+// before from the positions in PSet::xp -- the same bits only if both are the same instructions.  e0 Dm1 + e1 Dm3 is
+// the product e1 Dm3 rounded, then fused with e0 Dm1: what the compiler had chosen in all four instances of the kernel
+// when the choice was its own, so the trajectories are those of the engine before.
+MPM_DEV void fem_inplane(const float* x0, const float* x1, const float* x2, float Dm0, float Dm1, float Dm3, float* F) {
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float e0 = x1[d] - x0[d], e1 = x2[d] - x0[d];
+        F[d * 3 + 0] = e0 * Dm0;
+        F[d * 3 + 1] = fmaf(e0, Dm1, e1 * Dm3);
+    }
 }
 MPM_DEV void unpack_F(const float4& r0, const float4& r1, float r2, float* F) {
     F[2] = r0.x; F[5] = r0.y; F[8] = r0.z; F[0] = r0.w;

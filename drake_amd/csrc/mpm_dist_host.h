@@ -139,6 +139,8 @@ static int dist_resize(mpm_engine* e, size_t new_nf, size_t new_nv, bool first) 
         for (int d = 0; d < 4; ++d) p.set[s].q[d] = q_base[s] + (size_t)d * new_q_stride;
     for (int d = 0; d < 3; ++d) p.f[d] = f_base + (size_t)d * new_q_stride;
     if (first) {
+        // (a partitioned domain runs no lean substeps: nothing writes or reads PSet::xp, DP::lean_g2p)
+        for (int s = 0; s < 2; ++s) e->dfree(p.set[s].xp);
         // the whole scene's topology tables
         for (int d = 0; d < 3; ++d) {
             int* t = const_cast<int*>(p.idx_orig[d]);

@@ -449,6 +449,7 @@ int mpm_finalize(mpm_handle_t e) try {
         for (int d = 0; d < 4; ++d) ALLOC(S.fq[d], nf, true);
         ALLOC(S.f8, nf, true);
         ALLOC(S.c8, nf, true);
+        ALLOC(S.xp, nv, true);   // (per vertex slot: the positions behind F's in-plane columns inside a batch, see PSet)
         ALLOC(S.pid, np, true);
     }
     ALLOC(p.ta, std::max<size_t>(nf, 1), true);   // (k_p2g's vertex lanes read element 0 when an item has no face)
@@ -1432,7 +1433,7 @@ int mpm_get_stats(mpm_handle_t e, mpm_stats_t* out) try {
         size_t pb = 0, sb = 0;
         for (int s = 0; s < 2; ++s) {
             const PSet& S = p.set[s];
-            pb += e->bytes_of(S.q[0]) + e->bytes_of(S.pid) + e->bytes_of(S.f8) + e->bytes_of(S.c8) + e->bytes_of(p.fg[s]);
+            pb += e->bytes_of(S.q[0]) + e->bytes_of(S.pid) + e->bytes_of(S.f8) + e->bytes_of(S.c8) + e->bytes_of(S.xp) + e->bytes_of(p.fg[s]);
             for (int d = 0; d < 4; ++d) pb += e->bytes_of(S.fq[d]);
             for (int d = 0; d < 2; ++d) pb += e->bytes_of(p.vg[s][d]);
         }

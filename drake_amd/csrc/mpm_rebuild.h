@@ -661,6 +661,8 @@ __global__ __launch_bounds__(256) void k_rb_finish(DP p) {
             D.f8[j] = S.f8[i];
             D.c8[j] = S.c8[i];
         } else if (!p.dist.on) {
+            // (the position the last lean k_g2p left for k_fem travels with the vertex, PSet::xp: current or not)
+            D.xp[j - (unsigned)p.Nf] = S.xp[i - (unsigned)p.Nf];
             // The vertex's entries of DP::VF at the new slot: zeros where it has no face (k_fem rewrites the others
             // before anything reads them), or the mark that sends a vertex with more than eight faces to the CSR.
             const int vo = pid - p.NfG;

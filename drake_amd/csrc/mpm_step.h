@@ -834,7 +834,8 @@ MPM_DEV int g2p_particle(const DP& p, const PSet& S, const float4* tile, unsigne
         // (an explicit fused multiply-add: left to the compiler, WHICH of the two products is fused changes from build to
         // build with the scheduling of the code around it, and C with it in the last bit)
         for (int c = 0; c < 3; ++c) Cn[r * 3 + c] = fmaf(ca, sc * nC[r * 3 + c], cb * (sc * nC[c * 3 + r]));
-    // four 16-byte stores per particle (in this order: it keeps the kernel at 126 VGPRs without scratch)
+    // up to four 16-byte stores per particle (in this order: it keeps the kernel within the registers of its occupancy
+    // without scratch)
     const float xn = x + nv[0] * dt, yn = y + nv[1] * dt, zn = z + nv[2] * dt;
     // A face particle's position and velocity are only looked at from outside (downloads): CalcFemStateAndForce
     // replaces them by the means of the corners before anything in a substep reads them (the re-sort bins a face by
@@ -846,6 +847,10 @@ MPM_DEV int g2p_particle(const DP& p, const PSet& S, const float4* tile, unsigne
     // (in this order: another one costs the kernel its register budget)
     S.q[2][i] = make_float4(Cn[0], Cn[1], Cn[2], Cn[3]);
     S.q[3][i] = make_float4(Cn[4], Cn[5], Cn[6], Cn[7]);
+    // A vertex between the substeps of a batch: the record this lane loaded -- the position this substep's k_fem gathered --
+    // goes to PSet::xp, from which the next k_fem forms the in-plane columns of F that this substep's did not store
+    // (Ctl::f_inplane_stale; before the advected position replaces it)
+    if (p.lean_g2p && !is_face) S.xp[i - (unsigned)p.Nf] = make_float4(x, y, z, vol);
     if (full) {
         S.q[0][i] = make_float4(xn, yn, zn, vol);
         S.q[1][i] = make_float4(nv[0], nv[1], nv[2], Cn[8]);
@@ -867,7 +872,12 @@ __global__ __launch_bounds__(G2P_THREADS) __attribute__((amdgpu_waves_per_eu(G2P
         if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(&p.ctl->skipped, 1u);
         return;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) p.ctl->time_since_resort += dt;   // (see Ctl::quiet_time)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        p.ctl->time_since_resort += dt;   // (see Ctl::quiet_time)
+        // what the next k_fem finds: this substep's did not store F's in-plane columns, and the vertex lanes below leave
+        // the positions they are made of in PSet::xp -- or it did, and they do not
+        p.ctl->f_inplane_stale = p.lean_g2p;
+    }
     const PSet& S = p.set[ctl->cur];
     const unsigned n_items = ctl->n_items;
     for (unsigned q = blockIdx.x; q < n_items; q += gridDim.x) {
