@@ -15,5 +15,5 @@ from .capi import (MpmError, GpuMpm, load_library, library_path, Material, Colli
                    shell_hinge, Anchor, ANCHOR_DTYPE, ANCHOR_TENSION_ONLY, anchor_point, WEAVE_DTYPE, weave,
                    weave_coefficients, weave_face_records, weave_face_axes, TEAR_DTYPE, tear_face, tear_limit_squared,
                    link_breaks, link_break_squared, rest_shape_check, CREASE_DTYPE, crease, crease_chord, crease_hinge,
-                   TEAR_CUTS_HINGES, TEAR_VENTS_GAS, mesh_hinge_faces)
+                   TEAR_CUTS_HINGES, TEAR_VENTS_GAS, mesh_hinge_faces, SHELL_DAMPING_DTYPE, shell_hinge_damped)
 from . import scenes  # noqa: F401

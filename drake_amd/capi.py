@@ -340,6 +340,26 @@ def shell_hinge(x4, kc, psibar):
     return rec, np.float32(psi.value), rc == 1
 
 
+# mpm_cloth_shell_damping_t (8 bytes): GpuMpm.set_shell_damping takes, and get_shell_damping returns, arrays of it
+SHELL_DAMPING_DTYPE = np.dtype([("beta", "<f4"), ("reserved", "<f4")])
+assert SHELL_DAMPING_DTYPE.itemsize == 8
+
+
+def shell_hinge_damped(x4, v4, kc, psibar, bkc):
+    """mpm_shell_hinge_damped: (the four corner records (4, 3) float32 of the elastic and the damping moment together, psi,
+    psidot float32, acts bool) of one hinge with corner positions x4 and velocities v4 (4, 3), evaluated on the host by
+    the function the damped hinge kernel calls.  Needs no engine and no GPU."""
+    lib = load_library()
+    x = np.ascontiguousarray(x4, np.float32).reshape(12)
+    v = np.ascontiguousarray(v4, np.float32).reshape(12)
+    rec, psi, psidot = np.zeros((4, 3), np.float32), C.c_float(), C.c_float()
+    rc = lib.mpm_shell_hinge_damped(x.ctypes.data, v.ctypes.data, float(np.float32(kc)), float(np.float32(psibar)),
+                                    float(np.float32(bkc)), rec.ctypes.data, C.byref(psi), C.byref(psidot))
+    if rc < 0:
+        raise MpmError(rc, (lib.mpm_last_error() or b"").decode())
+    return rec, np.float32(psi.value), np.float32(psidot.value), rc == 1
+
+
 # mpm_cloth_crease_t (16 bytes): GpuMpm.set_creases takes, and get_creases returns, arrays of it, one per cloth
 CREASE_DTYPE = np.dtype([("yield_angle", "<f4"), ("hardening", "<f4"), ("max_angle", "<f4"), ("reserved", "<f4")])
 assert CREASE_DTYPE.itemsize == 16
@@ -680,6 +700,7 @@ SYMBOLS = [
     "mpm_pressure_vertex_force",
     "mpm_set_shell_bending", "mpm_get_shell_bending", "mpm_shell_hinges", "mpm_shell_forces", "mpm_shell_state",
     "mpm_shell_max_stable_dt", "mpm_mesh_hinges", "mpm_shell_hinge",
+    "mpm_set_shell_damping", "mpm_get_shell_damping", "mpm_shell_damping_forces", "mpm_shell_damping_state", "mpm_shell_hinge_damped",
     "mpm_set_creases", "mpm_get_creases", "mpm_set_crease_state", "mpm_crease_state", "mpm_crease_measure", "mpm_crease_hinge",
 ]
 
@@ -840,6 +861,11 @@ def load_library(build: bool = True):
         "mpm_shell_max_stable_dt": [vp, P(f)],
         "mpm_mesh_hinges": [vp, sz, sz, vp, sz, P(sz)],
         "mpm_shell_hinge": [vp, f, f, vp, P(f)],
+        "mpm_set_shell_damping": [vp, sz, vp],
+        "mpm_get_shell_damping": [vp, vp, sz, P(sz)],
+        "mpm_shell_damping_forces": [vp, vp],
+        "mpm_shell_damping_state": [vp, vp, vp],
+        "mpm_shell_hinge_damped": [vp, vp, f, f, f, vp, P(f), P(f)],
         "mpm_set_creases": [vp, sz, vp],
         "mpm_get_creases": [vp, vp, sz, P(sz)],
         "mpm_set_crease_state": [vp, vp],
@@ -1515,6 +1541,39 @@ class GpuMpm:
     @staticmethod
     def shell_hinge(x4, kc, psibar):
         return shell_hinge(x4, kc, psibar)
+
+    def set_shell_damping(self, beta=None):
+        """mpm_set_shell_damping: stiffness-proportional damping of the shell hinges -- an array of SHELL_DAMPING_DTYPE in
+        cloth order, or a list of beta (seconds).  None, an empty list or all zeros switches it off.  Needs shell bending
+        on; tightens shell_max_stable_dt.  A synchronisation point."""
+        t = np.zeros(0, SHELL_DAMPING_DTYPE) if beta is None else np.asarray(beta)
+        if t.dtype != SHELL_DAMPING_DTYPE:
+            b = np.asarray(beta, np.float32).reshape(-1)
+            t = np.zeros(len(b), SHELL_DAMPING_DTYPE)
+            t["beta"] = b
+        t = np.ascontiguousarray(t).reshape(-1)
+        self._ck(self.lib.mpm_set_shell_damping(self.h, t.size, t.ctypes.data if t.size else None))
+
+    def get_shell_damping(self):
+        """mpm_get_shell_damping: the table in force, one SHELL_DAMPING_DTYPE record per cloth (zeros while off)."""
+        return self._table(self.lib.mpm_get_shell_damping, SHELL_DAMPING_DTYPE)
+
+    def shell_damping_forces(self):
+        """mpm_shell_damping_forces: the hinge damping force alone on the current positions and velocities, (n_verts, 3)
+        float32 in dump_cpu_state's numbering."""
+        return self._vertex_forces(self.lib.mpm_shell_damping_forces)
+
+    def shell_damping_state(self):
+        """mpm_shell_damping_state: (dissipated power per cloth (n_cloths,) float64, psidot per hinge (n,) float32) on the
+        current positions and velocities."""
+        n = self._n_hinges()
+        power, psidot = np.zeros(max(self.cloth_count(), 1), np.float64), np.zeros(max(n, 1), np.float32)
+        self._ck(self.lib.mpm_shell_damping_state(self.h, power.ctypes.data, psidot.ctypes.data))
+        return power[:self.cloth_count()], psidot[:n]
+
+    @staticmethod
+    def shell_hinge_damped(x4, v4, kc, psibar, bkc):
+        return shell_hinge_damped(x4, v4, kc, psibar, bkc)
 
     def _n_hinges(self) -> int:
         n = C.c_size_t()

@@ -555,9 +555,11 @@ static PressureVolumeArgs pressure_volume_args(const mpm_engine* e) {
     a.torn = coupled_tear_flags(e, MPM_TEAR_VENTS_GAS);
     return a;
 }
+// (the damper's bkc likewise: the array belongs to mpm_set_shell_damping, null while no cloth has beta > 0)
 static HingeArgs hinge_args(const mpm_engine* e) {
     HingeArgs a = e->shell.hinge;
     a.torn = coupled_tear_flags(e, MPM_TEAR_CUTS_HINGES);
+    a.bkc = e->shell.d_bkc;
     return a;
 }
 static CreaseArgs crease_args(const mpm_engine* e) {
@@ -632,6 +634,16 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
         if (int rc = vertex_masses(e, mass)) return rc;
         next.max_dt = stable_dt_limit(std::sqrt(max_row_rate(t.rate_sum.data(), t.row_vertex.size(), 1.0,
                                                              [&](size_t r) { return mass[(size_t)t.row_vertex[r]]; })));
+        // (what mpm_set_shell_damping's guard needs per row: the row's rate as max_row_rate forms it, and its cloth)
+        next.max_dt_elastic = next.max_dt;
+        next.row_rate.assign(t.row_vertex.size(), 0.0);
+        for (size_t r = 0; r < t.row_vertex.size(); ++r)
+            if (t.rate_sum[r] > 0.0) {
+                const double m = (double)mass[(size_t)t.row_vertex[r]];
+                next.row_rate[r] = m > 0.0 ? 1.0 * t.rate_sum[r] / m : (double)INFINITY;
+            }
+        next.row_cloth.swap(t.row_cloth);
+        next.cbar.swap(t.cbar);
         if (int rc = rows_upload(e, fresh, t, &next.args)) return rc;
         std::vector<int4> ids(n);
         std::vector<float2> par(n);
@@ -653,7 +665,7 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
         // (faces A and B per hinge as global face ids, for the cut rule of mpm_set_tear_coupling; t.faces2 is [2 hinge])
         static_assert(sizeof(int2) == 2 * sizeof(int32_t), "int2 layout");
         H2D(e, d_faces, t.faces2.data(), n * sizeof(int2));
-        next.hinge = HingeArgs{d_ids, d_par, d_rec, (int)n, d_faces, nullptr, (int)e->nf};
+        next.hinge = HingeArgs{d_ids, d_par, d_rec, (int)n, d_faces, nullptr, (int)e->nf, nullptr};
         next.args.rec = d_rec;
         next.args.n_hinges = (int)n;
         // psibar: the hinge function on the device, once, on the rest positions -- the psi it writes (plane 0's .w)
@@ -680,8 +692,9 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
     {   // the arrays of the table that was in force
         const mpm_engine::Shell& o = e->shell;
         rows_free(e, o.args);
-        // (the crease parameters and state go with the hinge table they belonged to: `next` has none)
-        void* old[] = {(void*)o.hinge.ids, (void*)o.hinge.par, (void*)o.hinge.rec, (void*)o.cr.cr, (void*)o.hinge.faces};
+        // (the crease parameters and state, and the damper's table and bkc (mpm_set_shell_damping), go with the hinge
+        // table they belonged to: `next` has none)
+        void* old[] = {(void*)o.hinge.ids, (void*)o.hinge.par, (void*)o.hinge.rec, (void*)o.cr.cr, (void*)o.hinge.faces, (void*)o.d_bkc};
         for (void* q : old) e->dfree(q);
     }
     e->shell = next;
@@ -691,7 +704,7 @@ static int set_shell_bending(mpm_engine* e, size_t n_cloths, const mpm_cloth_she
 
 // the hinge records of the current positions into Shell::hinge.rec (stream-ordered; e->dp: no gate)
 static int shell_measure(mpm_engine* e) {
-    hipLaunchKernelGGL(k_hinge_eval, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, e->dp, hinge_args(e));
+    hipLaunchKernelGGL(k_hinge_eval<0>, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, e->dp, hinge_args(e));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -717,6 +730,83 @@ static int shell_state(mpm_engine* e, double* energy_per_cloth, float* psi_out, 
         }
     }
     if (inactive_out) *inactive_out = inactive;
+    return 0;
+}
+
+// ---- hinge damping (mpm_set_shell_damping, mpm_get_shell_damping, mpm_shell_damping_forces, mpm_shell_damping_state;
+// mpm_shell.h HINGE DAMPING) ----
+// Puts the table (one per cloth, or none) in force: bkc = float(beta k cbar) per hinge, formed in double and rounded once,
+// and the damped guard.  The arrays exist while some cloth has beta > 0; otherwise they are freed and the engine launches
+// what it launched before, with the elastic guard to the bit.  The caller has checked the numbers and settled the owed
+// substeps.  A failure changes nothing.
+static int set_shell_damping(mpm_engine* e, size_t n_cloths, const mpm_cloth_shell_damping_t* per_cloth) {
+    static_assert(sizeof(ClothShellDamping) == sizeof(mpm_cloth_shell_damping_t) && sizeof(ClothShellDamping) == 8, "shell damping layouts differ");
+    mpm_engine::Shell& sh = e->shell;
+    const size_t n = sh.kc.size();
+    // (`given`: some cloth has beta > 0, the table is kept; `any`: such a cloth has a hinge, the arrays exist)
+    bool given = false, any = false;
+    for (size_t c = 0; c < n_cloths; ++c) given = given || per_cloth[c].beta > 0.f;
+    std::vector<float> bkc(n, 0.f);
+    for (size_t h = 0; given && h < n; ++h) {
+        const size_t c = (size_t)sh.hinge_cloth[h];
+        any = any || per_cloth[c].beta > 0.f;
+        bkc[h] = (float)((double)per_cloth[c].beta * (double)sh.set[c].stiffness * sh.cbar[h]);
+        if (!std::isfinite(bkc[h]))
+            return fail(MPM_ERR_INVALID, "shell damping: hinge " + std::to_string(h) + " of cloth " + std::to_string(c) + ": beta k cbar is not a finite float");
+    }
+    float max_dt = sh.max_dt_elastic;
+    if (any) {
+        double W, G;
+        shell_damped_rates(sh.row_rate, sh.row_cloth, reinterpret_cast<const ClothShellDamping*>(per_cloth), &W, &G);
+        if (G > 0.0) max_dt = link_limit(W, G);
+    }
+    // (a synchronisation point: the kernels enqueued so far have read the old table)
+    HIP_TRY(hipStreamSynchronize(e->stream));
+    if (any) {
+        float* d_bkc = const_cast<float*>(sh.d_bkc);
+        if (!d_bkc) {
+            FreshArrays fresh(e);
+            if (int rc = fresh.alloc(&d_bkc, n, false)) return rc;
+            fresh.commit();
+        }
+        H2D(e, d_bkc, bkc.data(), n * sizeof(float));
+        sh.d_bkc = d_bkc;
+    } else {
+        float* d_bkc = const_cast<float*>(sh.d_bkc);
+        e->dfree(d_bkc);
+        sh.d_bkc = nullptr;
+    }
+    if (given) sh.damping.assign(per_cloth, per_cloth + n_cloths);
+    else sh.damping.clear();
+    sh.max_dt = max_dt;
+    return 0;
+}
+// the damping part's records of the current positions and velocities into Shell::hinge.rec (stream-ordered; no gate): the
+// planes are free between substeps, which rewrite them before they read them
+static int shell_damping_measure(mpm_engine* e) {
+    hipLaunchKernelGGL(k_hinge_eval<2>, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, e->dp, hinge_args(e));
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+static int shell_damping_forces(mpm_engine* e, float* f_out) {
+    if (e->shell.on())
+        if (int rc = shell_damping_measure(e)) return rc;
+    return rows_eval(e, k_hinge_gather_eval, e->shell.on() ? e->shell.args : ShellArgs{}, f_out);
+}
+// One float term per hinge from the device, added here per cloth in double in hinge order: a fixed order, no atomics
+static int shell_damping_state(mpm_engine* e, double* power_per_cloth, float* psidot_out) {
+    const mpm_engine::Shell& sh = e->shell;
+    const size_t n = sh.on() ? (size_t)sh.hinge.n : 0;
+    std::fill(power_per_cloth, power_per_cloth + e->cloths.size(), 0.0);
+    if (n) {
+        if (int rc = shell_damping_measure(e)) return rc;
+        std::vector<float4> planes(2 * n);
+        D2H(e, planes.data(), sh.hinge.rec, 2 * n * sizeof(float4));
+        for (size_t h = 0; h < n; ++h) {
+            power_per_cloth[(size_t)sh.hinge_cloth[h]] += (double)planes[n + h].w;
+            if (psidot_out) psidot_out[h] = planes[h].w;
+        }
+    }
     return 0;
 }
 

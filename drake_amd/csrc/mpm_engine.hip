@@ -231,11 +231,13 @@ static void launch_fem_vertices(mpm_engine* e, const DP& p, float dt) {
     }
     // (an engine with shell bending, mpm_set_shell_bending: the corner records of every hinge, one lane per hinge; then
     // f += the records of every vertex, one lane per vertex of a cloth with k > 0; while some cloth creases or some hinge
-    // is creased, mpm_set_creases / mpm_set_crease_state, k_crease first: one lane per hinge, it owns the psibar k_hinge reads)
+    // is creased, mpm_set_creases / mpm_set_crease_state, k_crease first: one lane per hinge, it owns the psibar k_hinge reads;
+    // while some cloth's hinges are damped, mpm_set_shell_damping, k_hinge<1> in k_hinge<0>'s place: no further launch)
     if (e->shell.on() && e->shell.creasing())
         hipLaunchKernelGGL(k_crease, rows_grid(e->shell.cr.n), dim3(256), 0, e->stream, p, crease_args(e));
     if (e->shell.on()) {
-        hipLaunchKernelGGL(k_hinge, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, p, hinge_args(e));
+        if (e->shell.damped()) hipLaunchKernelGGL(k_hinge<1>, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, p, hinge_args(e));
+        else hipLaunchKernelGGL(k_hinge<0>, rows_grid(e->shell.hinge.n), dim3(256), 0, e->stream, p, hinge_args(e));
         hipLaunchKernelGGL(k_hinge_gather, rows_grid(e->shell.args.n_rows), dim3(256), 0, e->stream, p, e->shell.args);
     }
     // (an engine with anchors, mpm_set_anchors: the bodies' poses at their clocks, one lane per motion; then f += the
@@ -2693,6 +2695,49 @@ int mpm_shell_hinge(const float* x12, float kc, float psibar, float* rec12_out, 
     const int on = shell_hinge(x12, x12 + 3, x12 + 6, x12 + 9, kc, psibar, rec, &psi) ? 1 : 0;
     std::memcpy(rec12_out, rec, sizeof rec);
     if (psi_out) *psi_out = psi;
+    return on;
+} MPM_CATCH_ALL
+
+// ---- hinge damping: state of shell bending (mpm_cloth_host.h; mpm_shell.h HINGE DAMPING) ---------------------------------------
+int mpm_set_shell_damping(mpm_handle_t e, size_t n_cloths, const mpm_cloth_shell_damping_t* per_cloth) try {
+    READY_NO_SETTLE(e);
+    if (int rc = single_engine_only(e, "shell damping is")) return rc;
+    REQUIRE(e->shell.on(), "shell damping needs shell bending (mpm_set_shell_bending) on");
+    REQUIRE(n_cloths == 0 || n_cloths == e->cloths.size(), "mpm_set_shell_damping: n_cloths must be the cloth count or 0");
+    REQUIRE(n_cloths == 0 || per_cloth, "null shell damping array");
+    const std::string refusal = shell_damping_refusal(reinterpret_cast<const ClothShellDamping*>(per_cloth), n_cloths);
+    if (!refusal.empty()) return fail(MPM_ERR_INVALID, refusal);
+    // substeps that mpm_run_substeps deferred are owed with the table they were enqueued with
+    if (int rc = settle(e)) return rc;
+    return set_shell_damping(e, n_cloths, per_cloth);
+} MPM_CATCH_ALL
+
+int mpm_get_shell_damping(mpm_handle_t e, mpm_cloth_shell_damping_t* out, size_t capacity, size_t* n_out) try {
+    REQUIRE(e, "null handle");
+    return padded_out(e->shell.damping, e->cloths.size(), mpm_cloth_shell_damping_t{0.f, 0.f}, out, capacity, n_out);
+} MPM_CATCH_ALL
+
+int mpm_shell_damping_forces(mpm_handle_t e, float* f_out) try {
+    READY(e);
+    REQUIRE(f_out || e->nv == 0, "null output");
+    return shell_damping_forces(e, f_out);
+} MPM_CATCH_ALL
+
+int mpm_shell_damping_state(mpm_handle_t e, double* power_per_cloth, float* psidot_out) try {
+    READY(e);
+    REQUIRE(power_per_cloth || e->cloths.empty(), "null output");
+    return shell_damping_state(e, power_per_cloth, psidot_out);
+} MPM_CATCH_ALL
+
+int mpm_shell_hinge_damped(const float* x12, const float* v12, float kc, float psibar, float bkc, float* rec12_out, float* psi_out,
+                           float* psidot_out) try {
+    REQUIRE(x12 && v12 && rec12_out, "null argument");
+    float rec[4][3], psi, psidot, power;
+    const int on = shell_hinge_damped(reinterpret_cast<const float(*)[3]>(x12), reinterpret_cast<const float(*)[3]>(v12), kc, psibar, bkc,
+                                      rec, &psi, &psidot, &power) ? 1 : 0;
+    std::memcpy(rec12_out, rec, sizeof rec);
+    if (psi_out) *psi_out = psi;
+    if (psidot_out) *psidot_out = psidot;
     return on;
 } MPM_CATCH_ALL
 

@@ -319,8 +319,17 @@ struct mpm_engine {
         // go with the hinge table they belonged to
         std::vector<mpm_cloth_crease_t> crease;   // [cloth] as given; empty: all off
         CreaseArgs cr{};                      // k_crease's tables (device memory, in `allocs`); cr == nullptr: none
+        // hinge damping (mpm_set_shell_damping; mpm_shell.h HINGE DAMPING): the tables exist while some cloth has beta > 0,
+        // and k_hinge<1> then runs in k_hinge<0>'s place; they go with the hinge table they belonged to
+        std::vector<mpm_cloth_shell_damping_t> damping;   // [cloth] as given; empty: off
+        const float* d_bkc = nullptr;         // [hinge] float(beta k cbar) (device memory, in `allocs`); nullptr: off
+        std::vector<double> cbar;             // [hinge] 3 |ebar|^2 / (Abar_A + Abar_B), as kc was formed from it
+        std::vector<double> row_rate;         // [row] the guard's row sum over the row's mass (inf where the mass is not positive)
+        std::vector<int> row_cloth;           // [row] its cloth
+        float max_dt_elastic = INFINITY;      // max_dt of the table without a damper, to the bit
         bool on() const { return hinge.n > 0; }
         bool creasing() const { return cr.cr != nullptr; }
+        bool damped() const { return d_bkc != nullptr; }
     } shell;
     // anchors: springs and cords from cloth vertices to rigid bodies (mpm_set_anchors; mpm_anchors.h): a non-empty table
     // switches k_anchor_pose and k_anchor on behind k_hinge_gather, and k_pin's clock tail behind GridToParticle

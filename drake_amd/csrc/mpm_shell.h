@@ -132,6 +132,61 @@
 //      the final subtraction, |psibar'| <= max(|psi|, |psibar|)                                                      0.5
 //      second-order terms                                                                                              1
 // R_crease = 24: |psibar' - psibar'64| <= 24 W / dpsi 2^-24 (the clamp is monotone and 1-Lipschitz: it adds nothing).
+//
+// HINGE DAMPING (mpm_set_shell_damping, mpm_shell_damping_forces, mpm_shell_damping_state, mpm_shell_hinge_damped):
+// stiffness-proportional damping of these hinges, per cloth, beta in seconds.  Not a feature of its own: state of shell
+// bending, as creases are -- the tables go with the hinge table they belonged to.  Per hinge of a cloth with beta > 0, with
+// the corner velocities as differences against corner 0 (Galilean invariant to the bit), w_j = v_j - v_0:
+//   thetadot = sum_j G_j . v_j = G2 . (w2 - wA w1) + G3 . (w3 - wB w1) = -(gA nA . (w2 - wA w1) + gB nB . (w3 - wB w1))
+//   psidot   = dpsi thetadot
+//   m_d      = -(bkc psidot) dpsi,     bkc = float(beta k cbar), formed in double on the host and rounded once
+//   f_j      = (m_el + m_d) G_j,       m_el = -(kc (psi - psibar)) dpsi as above
+// which is -beta times the Gauss-Newton stiffness kc dpsi^2 G G^T applied to the velocities: the matrix the guard bounds,
+// the stiffness half of a Rayleigh pair.  Linear in v, an exact zero for a common velocity, zero up to rounding for a
+// rigid rotation, dissipative (-sum_j f_j . v_j = bkc psidot^2 >= 0), bounded where the elastic force is and gone where
+// dpsi -> 0.  THE ORDER OF OPERATIONS (shell_hinge_core below, MODE != 0; contraction off, every division correctly
+// rounded): the geometry exactly as shell_hinge forms it up to wA and wB; then per component k
+//   w1 = v1 - v0, w2 = v2 - v0, w3 = v3 - v0;   p2 = w2 - wA * w1,  p3 = w3 - wB * w1;
+//   sA = (nA[0] * p2[0] + nA[1] * p2[1]) + nA[2] * p2[2],  sB likewise with nB and p3;
+//   thetadot = -(gA * sA + gB * sB);  psidot = dpsi * thetadot;  m_d = -(bkc * psidot) * dpsi;
+//   m = bkc != 0 ? m_el + m_d : m_el   (a SELECTION: a hinge with bkc = 0 gives shell_hinge's bits, whatever its
+//   velocities, a NaN included, and no signed zero is added);  the four records from m as shell_hinge forms them.
+// One evaluation and one set of four records per hinge: k_hinge_gather is unchanged.  An unusable or cut hinge writes exact
+// zeros as before, so a cut hinge is not damped.  The hinge's power term is the float (bkc * psidot) * psidot.
+// k_hinge is a template on the mode: k_hinge<0> is the kernel without damping (the same loads, arithmetic and stores);
+// k_hinge<1>, launched in its place while a cloth has beta > 0, also loads the four corner velocities from S.q[1] in the
+// round trip of the four positions -- still three dependent round trips -- and bkc from HingeArgs::bkc beside the ids.
+// HingeArgs::bkc is set in the per-launch copy of the arguments and is null while the damper is off.  k_hinge_eval<2>
+// (mpm_shell_damping_forces, mpm_shell_damping_state) leaves m_el out and reuses the record planes, which every substep
+// rewrites before it reads them: plane 0's .w is psidot, plane 1's the power term; a null bkc is bkc = 0 there.
+// NOT MODELLED: no mass-proportional part; the damping moment does not enter the crease yield rule (k_crease is untouched
+// and yields on the elastic moment alone); the geometric stiffness is not damped.
+// THE dt GUARD with damping: symplectic Euler on x'' = -W x - G x' is stable iff W dt^2 + 2 G dt <= 4 (link_limit,
+// mpm_links.h); W is the elastic guard's max row rate, G the same maximum with every row's sum times its cloth's beta (a
+// row's hinges all belong to one cloth).  While no cloth has beta > 0 the limit is the elastic expression, to the bit.
+// Like the elastic guard it holds at the rest shape and is not a guarantee; how conservative it is has not been measured.
+// Roundings of one component of one record of the damping part, for the bound of tests/shell_damping.py, first order, in
+// units of 2^-24 of
+//   D = |bkc| dpsi |G_hj| V (kappa_A + kappa_B),   V = |G2| (|w2| + (|a| / |e|) |w1|) + |G3| (|w3| + (|b| / |e|) |w1|)
+// (the atoms are the differences e, a, b, w_j; V bounds |thetadot| and every partial sum on the way, |a| / |e| >= |wA|
+// because wA's own error is relative to |a| |e| / |e|^2 and not to |wA|; V >= sum_j |G_j| |w_j|, with equality up to the
+// cancellation inside G1.  dpsi <= 1 and kappa_A + kappa_B >= 2: a plain relative rounding of the result costs 1/2):
+//   thetadot, per side, relative to |G2| (|w2| + (|a| / |e|) |w1|):
+//        w1 (1), wA (the dot product 4, |e|^2 3, the reciprocal 1, the product 1 = 9), wA * w1 (1), w2 and the
+//        subtraction (1 + 1, on the other part: the larger part counts)                                  12
+//        nA's components 6 kappa_A, the dot product nA . p2 (3)                                 6 kappa + 3
+//        gA = |e| / |nA|^2 (|e| 3.5, |nA|^2 12 kappa + 3, the division 1)                    12 kappa + 7.5
+//        the product gA * sA                                                                              1
+//        18 kappa + 23.5 <= 18 (kappa_A + kappa_B) - 18 + 23.5 <= 20.75 (kappa_A + kappa_B)                      20.75
+//        the sum of the two sides (1 rounding of at most V)                                                        0.5
+//   psidot = dpsi * thetadot: dpsi's absolute error (3 + 4 above) times |thetadot| <= V, the product (0.5)          7.5
+//   m_d = -(bkc * psidot) * dpsi: the product (0.5), dpsi's absolute error again (7), the product (0.5)               8
+//   m = m_el + m_d: one rounding of at most |m_el| + |m_d|, 0.5 here and 0.5 on T (above)                           0.5
+//   G2 / G3 (18), the record m G_j (0.5), corners 0 and 1 (6), as for R_shell                                      24.5
+//   second-order terms                                                                                             0.75
+// R_shell_damp = 62.5: a damped hinge's record lies within ((R_shell + 0.5) T + 62.5 D) 2^-24 of the float64 one, the
+// damping part alone (k_hinge_eval<2>) within 62 D 2^-24; a row adds its n_i.  psidot alone: at most 29 V (kappa_A +
+// kappa_B) 2^-24.  Second order is NOT covered where dpsi itself is of the order of its error (|theta| within 1e-5 of pi).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -157,6 +212,7 @@ constexpr uint32_t SHELL_PAD = 0xFFFFFFFFu;   // the gather table's padding reco
 constexpr float SHELL_GATE = 1e-30f;          // a hinge acts while |e|^2, |nA|^2, |nB|^2 >= this
 constexpr float R_SHELL = 46.f;               // the counted roundings of one record (above)
 constexpr float R_CREASE_T = 22.f, R_CREASE = 24.f;   // ... of a crease's t and of its psibar' (above)
+constexpr float R_SHELL_DAMP = 62.5f, R_SHELL_PSIDOT = 29.f;   // ... of a record's damping part and of psidot (above)
 
 struct ClothShell {   // mirrors mpm_cloth_shell_t (include/mpm_hip.h)
     float stiffness;
@@ -165,11 +221,19 @@ struct ClothShell {   // mirrors mpm_cloth_shell_t (include/mpm_hip.h)
 struct ClothCrease {   // mirrors mpm_cloth_crease_t
     float yield_angle, hardening, max_angle, reserved;
 };
+struct ClothShellDamping {   // mirrors mpm_cloth_shell_damping_t
+    float beta, reserved;
+};
 
 // The four corner records rec[j] = f_j of one hinge and its psi; kc = float(k cbar).  false: the hinge does not act
-// (the records and psi are exact zeros).  No branch on the data but the final selection.
-MPM_SHELL_FN bool shell_hinge(const float x0[3], const float x1[3], const float x2[3], const float x3[3], float kc, float psibar,
-                              float rec[4][3], float* psi_out) {
+// (the records and psi are exact zeros).  No branch on the data but the final selections.
+// MODE 0: the elastic hinge, no velocity is read (v may be null).  MODE 1: the damped hinge (the header, HINGE DAMPING):
+// v[4][3] the corner velocities, bkc = float(beta k cbar); *psidot_out = psidot, *power_out = (bkc psidot) psidot, zeros
+// for a hinge that does not act.  MODE 2: the damping part alone (m_el left out).
+template <int MODE>
+MPM_SHELL_FN bool shell_hinge_core(const float x0[3], const float x1[3], const float x2[3], const float x3[3], const float (*v)[3],
+                                   float kc, float psibar, float bkc, float rec[4][3], float* psi_out, float* psidot_out,
+                                   float* power_out) {
 #ifdef __clang__
 #pragma clang fp contract(off)
 #endif
@@ -195,12 +259,32 @@ MPM_SHELL_FN bool shell_hinge(const float x0[3], const float x1[3], const float 
     const float mag = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
     const float psi = t >= 0.f ? mag : -mag;
     const float dpsi = .5f * sqrtf((s0 * s0 + s1 * s1) + s2 * s2);
-    const float m = -(kc * (psi - psibar)) * dpsi;
+    const float m_el = -(kc * (psi - psibar)) * dpsi;
     const float gA = le / AA, gB = le / BB;   // G2 = -gA nA, G3 = -gB nB
     const float re = 1.f / ee;
     const float wA = ((a0 * e0 + a1 * e1) + a2 * e2) * re, wB = ((b0 * e0 + b1 * e1) + b2 * e2) * re;
     const float uA = 1.f - wA, uB = 1.f - wB;
     const float nA[3] = {A0, A1, A2}, nB[3] = {B0, B1, B2};
+    float m = m_el;
+    if (MODE != 0) {
+        float p2[3], p3[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float w1 = v[1][k] - v[0][k], w2 = v[2][k] - v[0][k], w3 = v[3][k] - v[0][k];
+            p2[k] = w2 - wA * w1;
+            p3[k] = w3 - wB * w1;
+        }
+        const float sA = (nA[0] * p2[0] + nA[1] * p2[1]) + nA[2] * p2[2];
+        const float sB = (nB[0] * p3[0] + nB[1] * p3[1]) + nB[2] * p3[2];
+        const float thetadot = -(gA * sA + gB * sB);
+        const float psidot = dpsi * thetadot;
+        const float bp = bkc * psidot;
+        const float m_d = -bp * dpsi;
+        const bool damped = bkc != 0.f;
+        m = MODE == 2 ? (damped ? m_d : 0.f) : (damped ? m_el + m_d : m_el);
+        *psidot_out = on ? psidot : 0.f;
+        *power_out = on && damped ? bp * psidot : 0.f;
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         const float f2 = m * -(gA * nA[k]), f3 = m * -(gB * nB[k]);
@@ -212,6 +296,16 @@ MPM_SHELL_FN bool shell_hinge(const float x0[3], const float x1[3], const float 
     }
     *psi_out = on ? psi : 0.f;
     return on;
+}
+MPM_SHELL_FN bool shell_hinge(const float x0[3], const float x1[3], const float x2[3], const float x3[3], float kc, float psibar,
+                              float rec[4][3], float* psi_out) {
+    return shell_hinge_core<0>(x0, x1, x2, x3, nullptr, kc, psibar, 0.f, rec, psi_out, nullptr, nullptr);
+}
+// The damped hinge: x[4][3], v[4][3]; with `elastic` false the damping part alone.  Returns psidot through psidot_out.
+MPM_SHELL_FN bool shell_hinge_damped(const float (*x)[3], const float (*v)[3], float kc, float psibar, float bkc, float rec[4][3],
+                                     float* psi_out, float* psidot_out, float* power_out, bool elastic = true) {
+    return elastic ? shell_hinge_core<1>(x[0], x[1], x[2], x[3], v, kc, psibar, bkc, rec, psi_out, psidot_out, power_out)
+                   : shell_hinge_core<2>(x[0], x[1], x[2], x[3], v, kc, psibar, bkc, rec, psi_out, psidot_out, power_out);
 }
 
 // shell_hinge's operations up to psi and dpsi, restated in the same order: psi and the gate are shell_hinge's bits.
@@ -287,6 +381,7 @@ struct HingeArgs {
     const int2* faces;     // [hinge] faces A and B, GLOBAL original face ids (the cloth's first face + the cloth-local id)
     const uint8_t* torn;   // [n_faces] TearArgs::torn, set per launch (the header, CUT HINGES); nullptr: no hinge is cut
     int n_faces;           // what a face id is checked against before it indexes `torn`
+    const float* bkc;      // [hinge] float(beta k cbar), set per launch (the header, HINGE DAMPING); nullptr: no damper
 };
 struct ShellArgs {
     const int* row_pid;          // [n_rows] particle id (NfG + vertex) of the row's vertex, ascending
@@ -297,13 +392,23 @@ struct ShellArgs {
     int n_hinges;
 };
 
-// the four planes of hinge h from four positions (what k_hinge, k_hinge_eval and k_hinge_rest share)
-MPM_DEV void hinge_store(const HingeArgs& a, int h, const float4 x[4], bool usable, bool cut = false) {
+// the four planes of hinge h from four positions (what k_hinge, k_hinge_eval and k_hinge_rest share); MODE != 0: and
+// from four velocities and the hinge's bkc (shell_hinge_core); MODE 2: the .w of planes 0 and 1 are psidot and the power term
+template <int MODE = 0>
+MPM_DEV void hinge_store(const HingeArgs& a, int h, const float4 x[4], bool usable, bool cut = false, const float4* v = nullptr,
+                         float bkc = 0.f) {
     const float2 q = a.par[h];
     const float X[4][3] = {{x[0].x, x[0].y, x[0].z}, {x[1].x, x[1].y, x[1].z}, {x[2].x, x[2].y, x[2].z}, {x[3].x, x[3].y, x[3].z}};
-    float rec[4][3], psi;
-    const bool on = shell_hinge(X[0], X[1], X[2], X[3], q.x, q.y, rec, &psi) && usable;
-    const float w[4] = {on ? psi : 0.f, on ? shell_energy_term(q.x, q.y, psi) : 0.f, on ? 1.f : 0.f, cut ? 1.f : 0.f};
+    float rec[4][3], psi, psidot = 0.f, power = 0.f;
+    bool on;
+    if (MODE == 0) {
+        on = shell_hinge(X[0], X[1], X[2], X[3], q.x, q.y, rec, &psi) && usable;
+    } else {
+        const float V[4][3] = {{v[0].x, v[0].y, v[0].z}, {v[1].x, v[1].y, v[1].z}, {v[2].x, v[2].y, v[2].z}, {v[3].x, v[3].y, v[3].z}};
+        on = shell_hinge_core<MODE>(X[0], X[1], X[2], X[3], V, q.x, q.y, bkc, rec, &psi, &psidot, &power) && usable;
+    }
+    const float w[4] = {on ? (MODE == 2 ? psidot : psi) : 0.f, on ? (MODE == 2 ? power : shell_energy_term(q.x, q.y, psi)) : 0.f,
+                        on ? 1.f : 0.f, cut ? 1.f : 0.f};
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         a.rec[(size_t)j * (size_t)a.n + (size_t)h] = on ? make_float4(rec[j][0], rec[j][1], rec[j][2], w[j]) : make_float4(0.f, 0.f, 0.f, j == 3 ? w[3] : 0.f);
@@ -324,8 +429,13 @@ MPM_DEV bool hinge_cut(const uint8_t* torn, int n_faces, const int2& fc, bool& o
 // address: the hinge's records are then exact zeros.
 // While a.torn is set the hinge's two face ids come with the vertex ids (the first round trip) and the faces' two flags
 // with the slots (the second): still three round trips of independent loads.
+// MODE != 0 (the header, HINGE DAMPING): bkc comes with the ids and the four velocities with the four positions; a null
+// a.bkc (k_hinge_eval<2> on an engine without the damper) is bkc = 0.
+template <int MODE>
 MPM_DEV void hinge_on_state(const DP& p, const PSet& S, const HingeArgs& a, int h, bool& bad) {
     const int4 id = a.ids[h];
+    float bkc = 0.f;
+    if (MODE != 0 && a.bkc) bkc = a.bkc[h];
     int2 fc = make_int2(0, 0);
     if (a.torn) fc = a.faces[h];
     const int c[4] = {id.x, id.y, id.z, id.w};
@@ -341,24 +451,33 @@ MPM_DEV void hinge_on_state(const DP& p, const PSet& S, const HingeArgs& a, int 
     float4 x[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) x[j] = ok ? S.q[0][s[j]] : make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 v[4];
+    if (MODE != 0) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = ok ? S.q[1][s[j]] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
     bad |= !ok;
-    hinge_store(a, h, x, ok && !cut, cut);
+    hinge_store<MODE>(a, h, x, ok && !cut, cut, v, bkc);
 }
 
 // Behind k_pressure (and k_vforce, k_bend, k_bend_damp, k_link) on the same stream, with the substep's DP: a substep that
 // skips itself (and is run again by the host) writes nothing and adds nothing, so that the force is added once.
+// MODE 0: no damper; MODE 1: while a cloth has beta > 0 (mpm_set_shell_damping), in its place.
+template <int MODE>
 __global__ __launch_bounds__(256) void k_hinge(DP p, HingeArgs a) {
     if (gated_out(p)) return;
     const int h = (int)(blockIdx.x * 256 + threadIdx.x);
     bool bad = false;
-    if (h < a.n) hinge_on_state(p, p.set[p.ctl->cur], a, h, bad);
+    if (h < a.n) hinge_on_state<MODE>(p, p.set[p.ctl->cur], a, h, bad);
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
 }
-// mpm_shell_forces, mpm_shell_state: the same records without the gate
+// mpm_shell_forces, mpm_shell_state: the same records without the gate (MODE 0: the elastic part alone, whatever the
+// damper); mpm_shell_damping_forces, mpm_shell_damping_state: MODE 2, the damping part alone
+template <int MODE>
 __global__ __launch_bounds__(256) void k_hinge_eval(DP p, HingeArgs a) {
     const int h = (int)(blockIdx.x * 256 + threadIdx.x);
     bool bad = false;
-    if (h < a.n) hinge_on_state(p, p.set[p.ctl->cur], a, h, bad);
+    if (h < a.n) hinge_on_state<MODE>(p, p.set[p.ctl->cur], a, h, bad);
     if (__ballot(bad) && (threadIdx.x & 63) == 0) atomicOr(&p.ctl->error, ERR_CAPACITY);
 }
 // mpm_set_shell_bending: the same function on rest positions in original vertex order, pos[3 n_verts]; a.ids hold
@@ -651,6 +770,30 @@ inline std::string crease_params(const ClothCrease* t, size_t n, float* yep) {
     return std::string();
 }
 
+// What mpm_set_shell_damping refuses before it looks at the hinges; empty: the numbers are fine
+inline std::string shell_damping_refusal(const ClothShellDamping* t, size_t n) {
+    for (size_t c = 0; c < n; ++c) {
+        const std::string at = "shell damping: cloth " + std::to_string(c);
+        if (!(std::isfinite(t[c].beta) && t[c].beta >= 0.f)) return at + ": beta is negative or not finite";
+        if (!(t[c].reserved == 0.f)) return at + ": reserved must be 0";
+    }
+    return std::string();
+}
+// The damped guard's two rates (the header, HINGE DAMPING): row_rate[r] is the elastic guard's row sum over the row's mass,
+// W their maximum over the rows that count (max_row_rate's rule), G the maximum of row_rate[r] beta[row_cloth[r]].
+inline void shell_damped_rates(const std::vector<double>& row_rate, const std::vector<int>& row_cloth, const ClothShellDamping* t,
+                               double* W, double* G) {
+    double w = 0.0, g = 0.0;
+    for (size_t r = 0; r < row_rate.size(); ++r)
+        if (row_rate[r] > 0.0) {
+            w = std::max(w, row_rate[r]);
+            const double beta = (double)t[(size_t)row_cloth[r]].beta;
+            if (beta > 0.0) g = std::max(g, row_rate[r] * beta);
+        }
+    *W = w;
+    *G = g;
+}
+
 // The gather table of a hinge list: ids4 [4 n] vertex ids; row_vertex: the vertices with a row, ascending; nf: the faces in
 // front.  A row's records are hinge << 2 | corner in ascending hinge id.  Needs no positions.
 inline bool shell_rows(const int32_t* ids4, size_t n_hinges, const std::vector<int>& row_vertex, size_t nf, size_t slice,
@@ -680,6 +823,8 @@ inline bool shell_rows(const int32_t* ids4, size_t n_hinges, const std::vector<i
 struct ShellTable : RowTable<uint32_t> {   // the gather table: one row per vertex of the cloths with k > 0
     std::vector<int32_t> ids4;      // [4 hinge] vertex ids (0-based over all cloths) of x0, x1, x2, x3
     std::vector<float> kc;          // [hinge] float(k cbar)
+    std::vector<double> cbar;       // [hinge] the rest shape's cbar (mpm_set_shell_damping: bkc = float(beta k cbar))
+    std::vector<int> row_cloth;     // [row] its cloth
     std::vector<int> hinge_cloth;   // [hinge]
     std::vector<int32_t> faces2;    // [2 hinge] faces A and B as GLOBAL face ids: the cloth's first_face + the cloth-local id
     std::vector<int> row_vertex;    // [row] its vertex
@@ -704,6 +849,7 @@ inline bool shell_table(const std::vector<Cloth>& cloths, const int* h_idx, size
         for (size_t v = 0; v < cl.n_verts; ++v) {
             out.row_vertex.push_back((int)(cl.first_vertex + v));
             out.rate_sum.push_back(0.0);
+            out.row_cloth.push_back((int)c);
         }
         for (const ShellHinge& h : H) {
             const size_t id = out.kc.size();
@@ -732,6 +878,7 @@ inline bool shell_table(const std::vector<Cloth>& cloths, const int* h_idx, size
                 out.rate_sum[row] += (double)kc * dpsi * dpsi * r.G[j] * gsum;
             }
             out.kc.push_back(kc);
+            out.cbar.push_back(r.cbar);
             out.hinge_cloth.push_back((int)c);
             out.faces2.push_back((int32_t)(cl.first_face + (size_t)h.face_a));
             out.faces2.push_back((int32_t)(cl.first_face + (size_t)h.face_b));

@@ -426,6 +426,21 @@ struct GpuMpmState {
         mpm_check(mpm_set_shell_bending(h_, per_cloth.size(), per_cloth.data(), rest_pos.empty() ? nullptr : rest_pos.data()));
     }
     std::vector<mpm_cloth_shell_t> GetShellBending() const { return table<mpm_cloth_shell_t>(mpm_get_shell_bending); }
+    // Extension: hinge damping (mpm_set_shell_damping) -- stiffness-proportional damping of the shell hinges, one {beta, 0}
+    // per cloth (beta in seconds, 0: not damped); all zeros or an empty vector switches it off.  State of shell bending:
+    // needs SetShellBending first, which also drops the table.  Tightens ShellMaxStableDt.  A synchronisation point.
+    void SetShellDamping(const std::vector<mpm_cloth_shell_damping_t>& per_cloth) {
+        mpm_check(mpm_set_shell_damping(h_, per_cloth.size(), per_cloth.data()));
+    }
+    std::vector<mpm_cloth_shell_damping_t> GetShellDamping() const { return table<mpm_cloth_shell_damping_t>(mpm_get_shell_damping); }
+    // the damping part alone on the current positions and velocities, 3 floats per vertex in the numbering of DumpCpuState
+    std::vector<float> ShellDampingForces(size_t n_verts) const { return vertex_forces(mpm_shell_damping_forces, n_verts); }
+    // the power the hinge dampers of every cloth dissipate on the current state
+    std::vector<double> ShellDampingPower(size_t n_cloths) const {
+        std::vector<double> p(n_cloths);
+        mpm_check(mpm_shell_damping_state(h_, p.data(), nullptr));
+        return p;
+    }
     // Extension: creases (mpm_set_creases) -- plastic shell hinges, one {yield_angle, hardening, max_angle} per cloth
     // (yield_angle 0: elastic); all zeros or an empty vector switches yielding off and keeps the creases made so far.
     // Needs SetShellBending first, which also drops the crease parameters and state.  A synchronisation point.

@@ -1396,14 +1396,15 @@ MPM_API int mpm_pressure_vertex_force(float g, const float x_own[3], size_t n, c
  * vertex-force, bending, link and pressure kernels, counted under MPM_PHASE_VFORCE -- one lane per hinge writes the four
  * corner records, one lane per vertex adds its records in ascending hinge id, no atomics: records, psi and forces are
  * the same bits whatever the particle order.  A cloth may have mpm_set_bending and this on: the forces add.
- * Stiffness-proportional damping of these hinges is not provided: mpm_set_damping's bending part acts on the quadratic
- * model only.  It works with pins, per-cloth materials, grid bodies, force fields, bending, damping, links, pressure,
+ * Stiffness-proportional damping of these hinges is mpm_set_shell_damping (below); mpm_set_damping's bending part acts
+ * on the quadratic model only.  It works with pins, per-cloth materials, grid bodies, force fields, bending, damping, links, pressure,
  * deterministic mode, fast math and the coupled path.
  * STABILITY GUARD: the substep entry points that check mpm_bending_max_stable_dt refuse, before anything is enqueued,
  *   dt > mpm_shell_max_stable_dt = 2 / sqrt(max_i (1 / m_i) sum_{h contains i} k cbar dpsibar^2 |Gbar_hi| sum_j |Gbar_hj|)
  * (Gershgorin on the Gauss-Newton part of the stiffness).  It is a guard AT THE REST SHAPE: it does not cover the
  * geometric stiffness of a deformed hinge, nor the larger |G| of a hinge whose triangles have collapsed.  How
- * conservative it is has not been measured.  +inf while the feature is off.
+ * conservative it is has not been measured.  +inf while the feature is off.  mpm_set_shell_damping's beta TIGHTENS this
+ * guard (below).
  * mpm_set_shell_bending replaces the table (all-zero stiffness or n_cloths = 0 switches the feature off, the table may
  * then be NULL; otherwise n_cloths must equal mpm_cloth_count); it needs mpm_finalize, is ordered on the engine's stream
  * and is a synchronisation point; substeps that mpm_run_substeps still owes are run first, with the table they were
@@ -1450,6 +1451,66 @@ MPM_API int mpm_mesh_hinges(const int32_t *indices, size_t n_faces, size_t n_ver
  * cbar); rec12_out: the four corner records f_0 .. f_3; psi_out (may be NULL): the hinge's psi.  Returns 1 where the
  * hinge acts, 0 where it does not (exact zeros), a negative code on a null argument. */
 MPM_API int mpm_shell_hinge(const float x12[12], float kc, float psibar, float rec12_out[12], float *psi_out);
+
+/* ---- Hinge damping: stiffness-proportional damping of the shell hinges, per cloth (state of shell bending) ----
+ * A tube, a rolled sheet or a creased fold set in motion rings until the transfer scheme happens to eat the motion:
+ * mpm_set_damping covers the membrane and the quadratic hinge model, links and anchors carry their own damping, and this
+ * call is the damper of the shell hinges.  Per hinge of a cloth with beta > 0 (seconds), with e, a, b, nA, nB, wA, wB,
+ * dpsi and G_j of the shell block above, gA = |e| / |nA|^2, gB = |e| / |nB|^2, and the corner velocities as differences
+ * against corner 0, w_j = v_j - v_0 (Galilean invariant to the bit):
+ *   thetadot = sum_j G_j . v_j = -(gA nA . (w2 - wA w1) + gB nB . (w3 - wB w1))
+ *   psidot   = dpsi thetadot
+ *   m_d      = -(bkc psidot) dpsi,    bkc = float(beta k cbar), formed in double on the host and rounded once
+ *   f_j      = (m_el + m_d) G_j,      m_el = -(k cbar (psi - psibar)) dpsi the elastic moment above
+ * This is -beta times the Gauss-Newton stiffness k cbar dpsi^2 G G^T applied to the velocities: the matrix the guard
+ * bounds, and the stiffness half of a Rayleigh pair, as mpm_set_damping is.  It is linear in v, an exact zero for a common
+ * velocity, zero up to rounding for a rigid rotation, dissipative (-sum_j f_j . v_j = bkc psidot^2 >= 0), bounded where
+ * the elastic force is bounded and gone where dpsi -> 0, like the elastic moment.  In float, every operation written out,
+ * no contraction, the same function on host and device (mpm_shell_hinge_damped).  A hinge whose bkc is 0 (a cloth with
+ * beta = 0 on a damped engine) gives the undamped hinge's bits.
+ * NOT MODELLED: no mass-proportional part; the damping moment does not enter the crease yield rule (mpm_set_creases
+ * yields on the elastic moment alone); the geometric stiffness is not damped.
+ * It is STATE OF SHELL BENDING, not a feature of its own: it needs shell bending on, mpm_set_shell_bending replaces the
+ * hinge table and the damping table goes with the table it belonged to (mpm_get_shell_damping then returns zeros), and
+ * whatever holds for an engine with shell bending holds for it -- partitioned and multi-rank engines refuse it, the rest
+ * shape cannot be replaced under it.  It adds no launch: while some cloth has beta > 0 the hinge kernel's damped instance
+ * runs in the undamped one's place and also reads the four corner velocities.  A cut hinge (mpm_set_tear_coupling) carries
+ * no moment and is not damped.  MPM_ARR_FORCES includes the damping force; mpm_shell_forces and mpm_shell_state keep
+ * reporting the elastic part alone.
+ * STABILITY GUARD: beta TIGHTENS mpm_shell_max_stable_dt.  With W the rate of the elastic guard above (dt <= 2 / sqrt(W))
+ * and G the same maximum with every row's sum times its cloth's beta, the limit becomes that of symplectic Euler on a
+ * damped oscillator, the positive root of W dt^2 + 2 G dt = 4 (as mpm_links_max_stable_dt), rounded down; the refusal is
+ * worded as the shell guard's.  While no cloth has beta > 0 it is the elastic limit to the bit.  Like the elastic guard it
+ * holds AT THE REST SHAPE and is not a guarantee.  How conservative it is has not been measured.
+ * mpm_set_shell_damping replaces the table (all-zero beta or n_cloths = 0 switches it off and frees the tables, the table
+ * may then be NULL; otherwise n_cloths must equal mpm_cloth_count); it needs mpm_finalize and shell bending in force, runs
+ * the substeps mpm_run_substeps still owes first, and is a synchronisation point.  Off means off: the engine then launches
+ * exactly what it launched before the call.  beta > 0 on a cloth without hinges is accepted and does nothing.
+ * Refused with MPM_ERR_INVALID, nothing enqueued, the previous table staying in force: a call before mpm_finalize; shell
+ * bending off; a wrong n_cloths; a negative or non-finite beta; a non-zero reserved; a beta k cbar that is no finite
+ * float; any partitioned or multi-rank engine. */
+typedef struct mpm_cloth_shell_damping {
+    float beta;       /* seconds, >= 0; 0: the cloth's hinges are not damped */
+    float reserved;   /* must be 0 */
+} mpm_cloth_shell_damping_t;
+MPM_API int mpm_set_shell_damping(mpm_handle_t h, size_t n_cloths, const mpm_cloth_shell_damping_t *per_cloth);
+/* The table as given: min(n, capacity) entries into out (may be NULL when capacity is 0), the cloth count into *n_out.
+ * Zeros while the damper is off. */
+MPM_API int mpm_get_shell_damping(mpm_handle_t h, mpm_cloth_shell_damping_t *out, size_t capacity, size_t *n_out);
+/* The damping part alone on the current positions and velocities: f_out[3 * n_verts], in the vertex numbering of
+ * mpm_dump_cpu_state (zeros while the damper is off).  The device functions of the substep's kernels; changes no state. */
+MPM_API int mpm_shell_damping_forces(mpm_handle_t h, float *f_out);
+/* On the current positions and velocities: power_per_cloth[mpm_cloth_count] = sum of the hinges' float terms
+ * (bkc psidot) psidot, the dissipated power, as the hinge kernel forms them, added in double in hinge order (a fixed
+ * order, no atomics); psidot_out (one per hinge of mpm_shell_hinges, may be NULL): the hinge's psidot, 0 for a hinge that
+ * does not act -- reported whether or not the hinge's cloth is damped.  Changes no state. */
+MPM_API int mpm_shell_damping_state(mpm_handle_t h, double *power_per_cloth, float *psidot_out);
+/* Host only: the inline function the damped hinge kernel calls, compiled for the host.  x12, v12: positions and
+ * velocities of x0, x1, x2, x3; kc = float(k cbar); bkc = float(beta k cbar); rec12_out: the four corner records of the
+ * elastic and the damping moment together; psi_out, psidot_out (may be NULL).  Returns 1 where the hinge acts, 0 where it
+ * does not (exact zeros, whatever the velocities), a negative code on a null argument. */
+MPM_API int mpm_shell_hinge_damped(const float x12[12], const float v12[12], float kc, float psibar, float bkc,
+                                   float rec12_out[12], float *psi_out, float *psidot_out);
 
 /* ---- Creases: plastic shell hinges that keep a fold (an extension of shell bending) ----
  * Shell bending is elastic: a sheet folded in half springs back flat.  With creases a hinge's rest value psibar, the

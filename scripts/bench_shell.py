@@ -3,14 +3,15 @@
 `flat` (mpm_set_bending on every sheet: k_vforce and k_bend) against `shell` (mpm_set_shell_bending on every sheet:
 k_vforce, k_hinge over every hinge, k_hinge_gather over every vertex) against `creased` (the shell engine with
 mpm_set_creases at a yield angle of 1 rad on every sheet: k_crease runs in front of k_hinge, reads every hinge's corners,
-and no hinge yields).  The stiffness is the one at which dt is a quarter of the feature's own guard, so both models act
+and no hinge yields) against `damped` (the shell engine with mpm_set_shell_damping, beta = dt / 2 on every sheet: k_hinge<1>
+runs in k_hinge<0>'s place and also reads every hinge's four corner velocities).  The stiffness is the one at which dt is a quarter of the feature's own guard, so both models act
 and the trajectory stays stable.
 
 Per round every engine runs once, in turn, in one process: mpm_profile_substeps' VFORCE phase (k_vforce and the
 feature's kernels; empty on the plain engine, whose vertex forces are summed inside k_p2g; event time), and the whole
 substep (wall time of mpm_run_substeps, synchronised at the end).  Medians over the rounds; the raw rounds are printed too.
 
-  python scripts/bench_shell.py [--steps 40] [--warmup 10] [--rounds 5] [--engines plain,flat,shell,creased]
+  python scripts/bench_shell.py [--steps 40] [--warmup 10] [--rounds 5] [--engines plain,flat,shell,creased,damped]
 
 Prints one JSON record.  Under `rocprofv3 --kernel-trace --stats -- python scripts/bench_shell.py --engines shell
 --rounds 2` the kernel summary gives k_hinge's and k_hinge_gather's own durations, with `--engines creased` k_crease's.
@@ -43,6 +44,9 @@ def engine(bits, cloths, kind, dt):
         t = np.zeros(len(cloths), CREASE_DTYPE)
         t["yield_angle"] = 1.0
         g.set_creases(t)
+    if kind == "damped":
+        g.set_shell_damping([0.5 * dt] * len(cloths))
+        assert dt <= g.shell_max_stable_dt()
     return g
 
 
