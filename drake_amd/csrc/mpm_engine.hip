@@ -793,6 +793,10 @@ static int extensions_refused(const mpm_engine* e, const char* what, bool set_up
 // refuse it, once per call, before anything is enqueued.  (An engine without a table never gets past the first test.)
 // The same entry points refuse a dt above mpm_<guard>_max_stable_dt of a feature in force that has a guard (the rows of
 // mpm_features.h; each guard is explained in its feature's header): of several, the last in table order.
+// Each guard bounds its own force alone, at the rest shape, with the membrane force left out, and each is tested alone: a
+// dt that every guard accepts can still be unstable for the sum of the forces ("What the dt guards bound",
+// has the measured margins and a counter-example).  A step of 1 / sum_f (1 / max_dt_f) over the guards in force is
+// sufficient for the sum; this function does not ask for it.
 static int fields_stable(const mpm_engine* e, float dt) {
     const FeatureState s = feature_state(e);
     const Feature f = violated_guard(s, dt);

@@ -109,7 +109,9 @@ inline Feature partition_blocker(const FeatureState& s, bool set_up) {
             return (Feature)f;
     return F_NONE;
 }
-// the guard that dt violates: the LAST such feature in table order (a NaN dt violates every guard in force)
+// the guard that dt violates: the LAST such feature in table order (a NaN dt violates every guard in force).  Every feature
+// is tested alone: the guards do not compose, and a dt below all of them is not thereby stable for the sum of the forces
+// ("What the dt guards bound"; 1 / sum_f (1 / max_dt[f]) over the guards in force would be sufficient).
 inline Feature violated_guard(const FeatureState& s, float dt) {
     for (int f = F_COUNT - 1; f >= 0; --f)
         if (FEATURES[f].guard && s.on[f] && !(dt <= s.max_dt[f])) return (Feature)f;

@@ -458,7 +458,11 @@ inline void link_rates(const LinkTable& t, const float* mass, size_t nf, double*
 }
 // mpm_links_max_stable_dt: symplectic Euler on x'' = -W x - G x' (v' = v + dt (-W x - G v), x' = x + dt v') is stable
 // iff W dt^2 + 2 G dt <= 4.  The positive root of that quadratic, 4 / (G + sqrt(G^2 + 4 W)) (2 / G where W = 0), as the
-// float not above it; INFINITY when nothing limits the step.
+// float not above it; INFINITY when nothing limits the step.  W and G are maxima over rows that need not be one row's, and
+// a table's stiffness and damping matrices need not commute: the root is a bound all the same (tests/test_guards.py takes
+// the one-step matrix's spectral radius; DESIGN.md, "What the dt guards bound", has the margins).  It bounds the links'
+// force alone, with every spring at its rest length; the load W dt^2 + 2 G dt is convex in dt and 4 at the root, so the
+// loads of several such guards in force sum to at most 4 at dt = 1 / sum (1 / root).
 inline float link_limit(double W, double G) {
     if (!(W > 0.0) && !(G > 0.0)) return INFINITY;
     if (!std::isfinite(W) || !std::isfinite(G)) return 0.f;

@@ -45,8 +45,9 @@
 // THE dt GUARD (mpm_shell_max_stable_dt): dt <= 2 / sqrt(max_i (1 / m_i) sum_{h contains i} kc dpsibar^2 |Gbar_hi|
 // sum_j |Gbar_hj|), Gershgorin on the Gauss-Newton part of the stiffness, kc dpsi^2 G G^T, taken AT THE REST SHAPE
 // (max_row_rate).  It does not cover the geometric stiffness (psi - psibar) d(dpsi G) / dx of a deformed hinge, nor a
-// deformed hinge's larger |G| (|G2| = |e| / |nA| grows as a triangle collapses): a guard, not a guarantee.  How
-// conservative it is has not been measured.  It is NOT recomputed when hinges are cut (below) and stays a bound: every term
+// deformed hinge's larger |G| (|G2| = |e| / |nA| grows as a triangle collapses): a guard, not a guarantee.  At the rest
+// shape it is between 0.58 and 0.81 of the true limit of this force alone; it says nothing about this force together
+// with another ("What the dt guards bound").  It is NOT recomputed when hinges are cut (below) and stays a bound: every term
 // of a row's Gershgorin sum is non-negative, so a row that loses hinges only loses terms.
 //
 // CUT HINGES (mpm_set_tear_coupling with MPM_TEAR_CUTS_HINGES, mpm_shell_cut_hinges): on a cloth that tears (mpm_tear.h) a
@@ -164,7 +165,9 @@
 // THE dt GUARD with damping: symplectic Euler on x'' = -W x - G x' is stable iff W dt^2 + 2 G dt <= 4 (link_limit,
 // mpm_links.h); W is the elastic guard's max row rate, G the same maximum with every row's sum times its cloth's beta (a
 // row's hinges all belong to one cloth).  While no cloth has beta > 0 the limit is the elastic expression, to the bit.
-// Like the elastic guard it holds at the rest shape and is not a guarantee; how conservative it is has not been measured.
+// Like the elastic guard it holds at the rest shape, for this force alone, and is not a guarantee; the stiffness and the
+// damping matrix do not commute once cloths differ in beta, and the root is a bound all the same ("What the dt
+// guards bound", has the measured margins).
 // Roundings of one component of one record of the damping part, for the bound of tests/shell_damping.py, first order, in
 // units of 2^-24 of
 //   D = |bkc| dpsi |G_hj| V (kappa_A + kappa_B),   V = |G2| (|w2| + (|a| / |e|) |w1|) + |G3| (|w3| + (|b| / |e|) |w1|)

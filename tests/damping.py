@@ -133,6 +133,30 @@ def power64(dm, vol, mu, lam, beta, xc, vc):
     return float(np.sum(vol * beta * (2.0 * mu * np.einsum("fab,fab->f", E, E) + lam * tr * tr)))
 
 
+# ---- the guard -----------------------------------------------------------------------------------------------------------
+def guard64(mv, T, rest, lame, betas, cof, hinges=None, ks=None, first=None):
+    """mpm_damping_max_stable_dt restated: 2 / max_i (1 / m_i) [sum_{f around i} beta_m vol_f (2 mu + 2 lambda) |g_i|
+    (|g_0| + |g_1| + |g_2|) + beta_b sum_j |k Q_ij|], g_j the columns of grad_N = Dm^-T [[-1, 1, 0], [-1, 0, 1]], m_i = mv[i]
+    the vertex masses; rest = (dm, vol) per face, lame[c] = (mu, lambda) and betas[c] = (membrane, bending) per cloth, cof
+    the cloth of every face; hinges[c] = (tests/bending.py's hinges, ...) or None, ks[c] the bending stiffness and
+    first[c] the first vertex of cloth c"""
+    mv = np.asarray(mv, np.float64)
+    dm, vol = (a.astype(np.float64) for a in rest)
+    gn = np.stack([np.hypot(dm[:, 0], dm[:, 1] + dm[:, 2]), np.hypot(dm[:, 0], dm[:, 1]), np.abs(dm[:, 2])], 1)
+    mu = np.array([float(lame[c][0]) for c in cof])
+    lam = np.array([float(lame[c][1]) for c in cof])
+    bm = np.array([float(betas[c][0]) for c in cof])
+    w = bm * vol * (2 * mu + 2 * lam) * gn.sum(axis=1)
+    D = np.zeros(len(mv))
+    np.add.at(D, np.asarray(T).reshape(-1), (w[:, None] * gn).reshape(-1))
+    for c, hp in enumerate(hinges or []):
+        if hp is None:
+            continue
+        Q = bd.q_dense(first[c + 1] - first[c], hp[0])[0]
+        D[first[c]:first[c + 1]] += float(betas[c][1]) * np.abs(float(np.float32(ks[c])) * Q).sum(axis=1)
+    return 2.0 / float((D / mv).max())
+
+
 # ---- the kernel's arithmetic in float32 --------------------------------------------------------------------------------
 def _f(a):
     return np.asarray(a, np.float32)

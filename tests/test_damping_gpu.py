@@ -311,28 +311,13 @@ def test_more_than_256_cloths():
 
 
 def _guard64(g, T, rest, lame, betas, cof, hinges=None, ks=None, first=None):
-    """mpm_damping_max_stable_dt restated: 2 / max_i (1 / m_i) [sum_{f around i} beta_m vol_f (2 mu + 2 lambda) |g_i|
-    (|g_0| + |g_1| + |g_2|) + beta_b sum_j |k Q_ij|], g_j the columns of grad_N = Dm^-T [[-1, 1, 0], [-1, 0, 1]], m_i the
-    vertex particle's MPM_ARR_MASSES"""
+    """tests/damping.py's guard64 on the vertex particles' MPM_ARR_MASSES"""
     A = _A()
     nf = g.n_faces
     pids, m = g.download(A.PIDS), g.download(A.MASSES).astype(np.float64)
     mv = np.zeros(g.n_verts)
     mv[pids[pids >= nf] - nf] = m[pids >= nf]
-    dm, vol = (a.astype(np.float64) for a in rest)
-    gn = np.stack([np.hypot(dm[:, 0], dm[:, 1] + dm[:, 2]), np.hypot(dm[:, 0], dm[:, 1]), np.abs(dm[:, 2])], 1)
-    mu = np.array([float(lame[c][0]) for c in cof])
-    lam = np.array([float(lame[c][1]) for c in cof])
-    bm = np.array([float(betas[c][0]) for c in cof])
-    w = bm * vol * (2 * mu + 2 * lam) * gn.sum(axis=1)
-    D = np.zeros(g.n_verts)
-    np.add.at(D, np.asarray(T).reshape(-1), (w[:, None] * gn).reshape(-1))
-    for c, hp in enumerate(hinges or []):
-        if hp is None:
-            continue
-        Q = bd.q_dense(first[c + 1] - first[c], hp[0])[0]
-        D[first[c]:first[c + 1]] += float(betas[c][1]) * np.abs(float(np.float32(ks[c])) * Q).sum(axis=1)
-    return 2.0 / float((D / mv).max())
+    return dp.guard64(mv, T, rest, lame, betas, cof, hinges, ks, first)
 
 
 @pytest.mark.parametrize("scene", ["big", "pair_multi"])
