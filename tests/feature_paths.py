@@ -21,10 +21,9 @@ Every stiffness is set, its guard read, and rescaled so that DT is SHARE (a hair
 the guard itself cannot break DT <= guard / 2) of the guard: once, on a probe engine with everything on (PARAMS); every
 other engine gets the same numbers, so that the engines of a composition differ in what is switched on and in nothing
 else.  No GPU is touched at import."""
-import os
-
 import numpy as np
 
+from tests import harness
 from tests import substep_paths as sp
 
 DT = sp.DT
@@ -145,18 +144,9 @@ def perturbed_state(seed=7):
 def _create(env):
     """GpuMpm(6) under the environment switches `env` (read per handle, at mpm_create)"""
     from drake_amd import GpuMpm
-    env = dict(env or {})
-    assert set(env) <= set(ENV_SWITCHES), env
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    assert set(env or {}) <= set(ENV_SWITCHES), env
+    with harness.environ(env):
         return GpuMpm(6)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 def vertices(g, which):

@@ -17,10 +17,13 @@
  7. Clocks: with anchors and no pins the clock advances with every substep; with pins on the same body, once.
  8. A cord stops a fall.   9. Weight at rest, against a pinned twin.
 10. Scheduling through re-sorts, and the coupled path.   11. Refusals."""
+import functools
+
 import numpy as np
 import pytest
 
 from tests import anchors as an
+from tests import harness as hs
 from tests import links as lk
 from tests import transfer_layouts as tl
 
@@ -31,52 +34,8 @@ DT = 1e-5          # a substep far inside every scene's stability guard
 CASES = [(s, st) for s in an.SCENES for st in an.STATES]
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
-def _engine(cloths, bits=6, deterministic=True, material=None, bodies=an.N_BODIES):
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for X, T in cloths:
-        g.add_qr_cloth(X, np.zeros_like(X), T)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.asarray(v, np.float32)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, None)
-
-
-def _vertices(g, which):
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros((g.n_verts,) + a.shape[1:], a.dtype)
-    out[pids[pids >= g.n_faces] - g.n_faces] = a[pids >= g.n_faces]
-    return out
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32 if a.dtype.itemsize == 4 else np.uint64)
+_engine = functools.partial(hs.engine, bodies=an.N_BODIES)
+_state = functools.partial(hs.state, bodies=True)
 
 
 def _motions(motions):
@@ -105,30 +64,18 @@ def _scene_engine(name, anchors=None, clock=True, material=None):
     return g, anchors, motions, X
 
 
-def _state(g):
-    A = _A()
-    tau, f = g.external_body_force_to_host()
-    return dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS),
-                F=g.download(A.DEFORMATION_GRADIENTS), tau=tau, f=f)
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), (what, k, float(np.abs(a[k].astype(np.float64) - b[k]).max()))
-
-
 # ---- 1 -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name,st", CASES)
 def test_forces_against_float64(name, st):
     g, anchors, motions, X = _scene_engine(name)
     assert np.array_equal(g.get_anchors(), anchors)
     x0, v0 = an.state(st, name, X)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     f = g.anchor_forces()
     ref, bound, y32, _ = an.vertex_forces64(anchors, x0, v0, motions, an.CLOCK)
     w = lk.margin(f - ref, bound)
     print(f"anchor forces: {name} {st}: {w:.3g} of the bound, largest force {np.abs(f).max():.3g}")
-    _record(f"anchor forces: {name} {st}", w)
+    hs.record(f"anchor forces: {name} {st}", w)
     assert w <= 1.0, w
     anchored = np.zeros(len(X), bool)
     anchored[anchors["vertex"]] = True
@@ -139,7 +86,7 @@ def test_forces_against_float64(name, st):
     ulp = np.spacing(np.abs(y64).astype(np.float32)).astype(np.float64)
     wp = float((np.abs(point.astype(np.float64) - y64) / ulp).max())
     print(f"anchor points: {name} {st}: {wp:.3g} ulp")
-    _record(f"anchor points: {name} {st}", wp)
+    hs.record(f"anchor points: {name} {st}", wp)
     assert wp <= 1.0, wp
     if name == "mixed":
         assert not f[an.DEGENERATE_VERTEX].any()                 # l2 < 1e-30 with L > 0: an exact zero
@@ -150,23 +97,23 @@ def test_forces_against_float64(name, st):
 # ---- 2 -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(an.SCENES))
 def test_total_forces_include_anchors(name):
-    A = _A()
+    A = hs.ARR()
     g, anchors, motions, X = _scene_engine(name, clock=False)     # (both engines fresh: the same F, the clocks at zero)
     twin = _engine(an.scene(name)[0], material=dict(gravity=0.0))
     x0, v0 = an.state("random", name, X)
     out = []
     for e in (g, twin):
-        _upload(e, x0, v0)
+        hs.upload(e, x0, v0)
         e.rebuild_mapping(False)
         e.calc_fem_state_and_force(DT)
-        out.append(_vertices(e, A.FORCES))
+        out.append(hs.vertices(e, A.FORCES))
     fa = g.anchor_forces()
     assert fa.any() and out[1].any()
     tot = out[1].astype(np.float64) + fa.astype(np.float64)
     err = np.abs(out[0].astype(np.float64) - tot)
     w = float((err / np.maximum(U * np.abs(out[0]).astype(np.float64), 1e-300))[err > 0].max()) if (err > 0).any() else 0.0
     print(f"total forces: {name}: {w:.3g} of one rounding of the sum")
-    _record(f"anchors: total forces {name}", w)
+    hs.record(f"anchors: total forces {name}", w)
     assert w <= 1.0, w
     assert not twin.anchor_forces().any() and twin.anchors_max_stable_dt() == np.inf and len(twin.get_anchors()) == 0
     for e in (g, twin):
@@ -175,24 +122,16 @@ def test_total_forces_include_anchors(name):
 
 
 # ---- 3 -------------------------------------------------------------------------------------------------------------
-def _phases(g, dt):
-    g.rebuild_mapping(False)
-    g.calc_fem_state_and_force(dt)
-    g.particle_to_grid(dt)
-    g.update_grid(-1)
-    g.grid_to_particle(dt)
-
-
 def test_reaction():
     table = an.one_per_vertex(an.scene("mixed")[1])
     assert {an.BODY_FAR, an.BODY_NONE} <= set(table["body"].tolist())
-    runs = (lambda g: g.substep(DT, -1), lambda g: g.run_substeps(1, DT, -1), lambda g: _phases(g, DT))
+    runs = (lambda g: g.substep(DT, -1), lambda g: g.run_substeps(1, DT, -1), lambda g: hs.phases(g, DT))
     states = []
     for k, run in enumerate(runs):
         g, anchors, motions, X = _scene_engine("mixed", anchors=table)
         assert DT <= g.anchors_max_stable_dt()
         x0, v0 = an.state("random", "mixed", X)
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         f = g.anchor_forces().astype(np.float64)
         st = g.anchor_state()
         y, q = st["point"].astype(np.float64), st["impulse_quantum"]
@@ -227,13 +166,13 @@ def test_reaction():
             worst = max(worst, ef / tol_f, et / tol_tau)
             assert ef <= tol_f and et <= tol_tau, (b, ef, tol_f, et, tol_tau)
             assert np.abs(want_f).max() > 1e3 * tol_f             # (the check sees the impulse)
-        _record("anchors: reaction", worst)
+        hs.record("anchors: reaction", worst)
         # the body beyond the count: no accumulator, and its vertices feel the force
         none = anchors["vertex"][anchors["body"] == an.BODY_NONE]
         assert len(none) and np.abs(f[none]).max() > 0
         g.destroy()
-    _same_bits(states[0], states[1], "substep against run_substeps(1)")
-    _same_bits(states[0], states[2], "substep against the phase calls")
+    hs.same_bits(states[0], states[1], "substep against run_substeps(1)")
+    hs.same_bits(states[0], states[2], "substep against the phase calls")
     assert states[0]["f"].any() and states[0]["tau"].any()
 
 
@@ -242,17 +181,17 @@ def test_reaction():
 def test_energy_and_lengths_against_float64(name, st):
     g, anchors, motions, X = _scene_engine(name)
     x0, v0 = an.state(st, name, X)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     s = g.anchor_state()
     _, _, y32, _ = an.points(anchors, motions, an.CLOCK)
     assert np.array_equal(s["point"], y32)                        # (the energy below is stated on the engine's own points)
     ref, bound, l64 = an.energy64(anchors, x0, s["point"])
     w = abs(s["energy"] - ref) / bound
     print(f"anchor energy: {name} {st}: {s['energy']:.9e}, {w:.3g} of the bound")
-    _record(f"anchor energy: {name} {st}", w)
+    hs.record(f"anchor energy: {name} {st}", w)
     assert ref > 0 and w <= 1.0, (s["energy"], ref, bound)
     wl = float((np.abs(s["length"].astype(np.float64) - l64) / np.maximum(U * l64 * (1 + 2.0 ** -20), 1e-300))[l64 > 0].max())
-    _record(f"anchor lengths: {name} {st}", wl)
+    hs.record(f"anchor lengths: {name} {st}", wl)
     assert wl <= 1.0 and not s["length"][l64 == 0].any(), wl
     g.rebuild_mapping(True)                                       # the same bits in another particle order
     s2 = g.anchor_state()
@@ -273,7 +212,7 @@ def test_anchors_that_do_nothing_add_an_exact_zero(case):
     """40 substeps through re-sorts, the sheets flying: a table of anchors with k = c = 0, or of cords far longer than
     any distance the run reaches, against an engine that never called mpm_set_anchors -- x, v, C, F and the accumulators
     bit for bit, and the forces of CalcFemStateAndForce before the first substep"""
-    A = _A()
+    A = hs.ARR()
     cloths, table, motions, X = an.scene("mixed")
     x0, v0 = _flying("mixed")
     t = _null(table) if case == "null" else table.copy()
@@ -287,25 +226,25 @@ def test_anchors_that_do_nothing_add_an_exact_zero(case):
     before = es[0].stats()["rebuilds"]
     forces = []
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(tl.DT)
         forces.append(g.download(A.FORCES))
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         for _ in range(4):
             g.run_substeps(10, tl.DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0, g.stats()
-    assert np.array_equal(_bits(forces[0]), _bits(forces[1]))
+    assert np.array_equal(hs.bits(forces[0]), hs.bits(forces[1]))
     assert es[0].stats()["rebuilds"] - before >= 1
     assert not es[0].anchor_forces().any() and es[0].anchor_state()["length"].max() < 10.0
-    _same_bits(_state(es[0]), _state(es[1]), case)
+    hs.same_bits(_state(es[0]), _state(es[1]), case)
     for g in es:
         g.destroy()
 
 
 def test_the_degenerate_spring_and_off_means_off():
-    A = _A()
+    A = hs.ARR()
     cloths, table, motions, X = an.scene("mixed")
     x0, v0 = an.state("random", "mixed", X)
     es = [_engine(cloths), _engine(cloths)]
@@ -318,14 +257,14 @@ def test_the_degenerate_spring_and_off_means_off():
     assert es[1].anchors_max_stable_dt() < np.inf
     forces = []
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(DT)
         forces.append(g.download(A.FORCES))
     assert es[1].anchor_state()["length"][0] == 0 and not es[1].anchor_forces().any()
-    assert np.array_equal(_bits(forces[0]), _bits(forces[1]))
+    assert np.array_equal(hs.bits(forces[0]), hs.bits(forces[1]))
     a, b = es[0].external_body_force_to_host(), es[1].external_body_force_to_host()
-    assert np.array_equal(_bits(a[0]), _bits(b[0])) and np.array_equal(_bits(a[1]), _bits(b[1]))
+    assert np.array_equal(hs.bits(a[0]), hs.bits(b[0])) and np.array_equal(hs.bits(a[1]), hs.bits(b[1]))
     # cleared: the launches of an engine that never had anchors -- no re-sort check more, an empty vertex-force phase
     es[1].set_anchors(table)
     es[1].set_anchors(table[:0])
@@ -333,12 +272,12 @@ def test_the_degenerate_spring_and_off_means_off():
     x1, v1 = _flying("mixed")
     checks = [g.stats()["resort_checks"] for g in es]
     for g in es:
-        _upload(g, x1, v1)
+        hs.upload(g, x1, v1)
         for _ in range(4):
             g.run_substeps(10, tl.DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
-    _same_bits(_state(es[0]), _state(es[1]), "set and cleared")
+    hs.same_bits(_state(es[0]), _state(es[1]), "set and cleared")
     assert es[0].stats()["resort_checks"] - checks[0] == es[1].stats()["resort_checks"] - checks[1]
     ph = [g.profile_substeps(2, tl.DT, -1)[0]["vforce"] for g in es]
     print(f"vertex-force phase, never set / cleared: {ph}")
@@ -359,22 +298,22 @@ def test_particle_order():
         if k:
             # a forced re-sort: the state five cells further along x, two substeps; then everything as at the start
             before = g.stats()["rebuilds"]
-            _upload(g, x0 + np.array([5.0 / 64, 0, 0], np.float32), v0)
+            hs.upload(g, x0 + np.array([5.0 / 64, 0, 0], np.float32), v0)
             g.run_substeps(2, DT, -1)
             g.gpu_sync()
             assert g.stats()["rebuilds"] > before
             g.rebuild_mapping(True)
             g.reallocate_external_bodies(an.N_BODIES)
             g.set_body_motions(_motions(motions))
-        _upload(g, x0, v0)
-        pids = g.download(_A().PIDS)
+        hs.upload(g, x0, v0)
+        pids = g.download(hs.ARR().PIDS)
         f = g.anchor_forces()
         g.substep(DT, -1)
         g.gpu_sync()
         out.append((pids, f) + g.external_body_force_to_host())
     assert not np.array_equal(out[0][0], out[1][0])
     for a, b in zip(out[0][1:], out[1][1:]):
-        assert a.any() and np.array_equal(_bits(a), _bits(b))
+        assert a.any() and np.array_equal(hs.bits(a), hs.bits(b))
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -400,13 +339,13 @@ def test_clocks(pinned):
     for _ in range(2):
         g.substep(tl.DT, -1)
     for _ in range(2):
-        _phases(g, tl.DT)
+        hs.phases(g, tl.DT)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0
     y64, _, _, _ = an.points(soft, {0: m}, n * float(np.float32(tl.DT)))
     point = g.anchor_state()["point"].astype(np.float64)
     w = float((np.abs(point - y64) / np.spacing(np.abs(y64).astype(np.float32))).max())
-    _record(f"anchors: clock after {n} substeps, pinned {pinned}", w)
+    hs.record(f"anchors: clock after {n} substeps, pinned {pinned}", w)
     assert w <= 1.0, w
     moved = np.abs(y64 - an.points(soft, {0: m}, (n - 1) * float(np.float32(tl.DT)))[0]).max()
     assert moved > 50 * np.spacing(np.float32(0.5))               # (one substep more or less would show)
@@ -430,7 +369,7 @@ def test_a_cord_stops_a_fall():
     s = 4 M |g| / k: twice the factor 2 of a suddenly loaded spring with the whole weight on one cord.  k is chosen so
     that s = H0, and the step count so that free fall, 1/2 |g| t^2 >= L + 2 s, carries the twin's corners to twice L + s
     from their attachment points."""
-    A = _A()
+    A = hs.ARR()
     L, grav = 2 * an.H0, 9.8
     twin, anchors, motions = _hung(L=L)
     M = float(twin.download(A.MASSES).astype(np.float64).sum())
@@ -448,10 +387,10 @@ def test_a_cord_stops_a_fall():
     for e in (g, twin):
         e.gpu_sync()
         assert e.stats()["error_flags"] == 0
-    far = np.linalg.norm(_vertices(twin, A.POSITIONS)[anchors["vertex"]].astype(np.float64) - y, axis=1).min()
+    far = np.linalg.norm(hs.vertices(twin, A.POSITIONS)[anchors["vertex"]].astype(np.float64) - y, axis=1).min()
     print(f"cords: M = {M:.4g} kg, k = {k:.4g} N/m, {steps} substeps; longest cord {longest:.5f} of L + s = {L + s:.5f}; "
           f"the twin's corners at {far:.5f}")
-    _record("anchors: longest cord over L + 4 M g / k", longest / (L + s))
+    hs.record("anchors: longest cord over L + 4 M g / k", longest / (L + s))
     assert far >= 2 * (L + s), (far, L + s)
     assert L < longest <= L + s, (longest, L + s)
     g.destroy()
@@ -463,12 +402,12 @@ def test_weight_at_rest():
     vertical force over a window against M |g|.  A twin whose corners are pinned to the same still body sets the margin:
     the anchors' deviation may be 4 x the twin's, or 1e-3 M |g|, whichever is larger."""
     from drake_amd import Pin
-    A = _A()
+    A = hs.ARR()
     grav, L, window, chunk = 9.8, 2 * an.H0, 400, 400
     devs = {}
     probe, anchors, motions = _hung(L=L)
     M = float(probe.download(A.MASSES).astype(np.float64).sum())
-    m_corner = float(_vertices(probe, A.MASSES)[anchors["vertex"]].astype(np.float64).min())
+    m_corner = float(hs.vertices(probe, A.MASSES)[anchors["vertex"]].astype(np.float64).min())
     k = 4 * M * grav / an.H0
     probe.set_anchors(an.scene_hung(k=k, c=0.2 * np.sqrt(k * m_corner), L=L)[1])
     dt = min(tl.DT, 0.5 * probe.anchors_max_stable_dt())         # (one dt for both twins)
@@ -498,7 +437,7 @@ def test_weight_at_rest():
         print(f"weight at rest, {kind}: {len(speeds)} chunks of {chunk}, speed_max {speeds[-1]:.3g}, body force {f[0]} N, "
               f"M |g| = {M * grav:.6g} N, deviation {devs[kind]:.3g} of it")
         g.destroy()
-    _record("anchors: weight at rest over the margin", devs["anchors"] / max(4 * devs["pins"], 1e-3))
+    hs.record("anchors: weight at rest over the margin", devs["anchors"] / max(4 * devs["pins"], 1e-3))
     assert devs["anchors"] <= max(4 * devs["pins"], 1e-3), devs
 
 
@@ -508,7 +447,7 @@ def test_scheduling_through_resorts_and_the_coupled_path():
     cloths, _, _, X = an.scene("hung")
     vb = (4.0, 0.3, 0.0)
     probe = _engine(cloths, bodies=0)
-    m_corner = float(_vertices(probe, _A().MASSES)[[0, 11, 132, 143]].astype(np.float64).min())
+    m_corner = float(hs.vertices(probe, hs.ARR().MASSES)[[0, 11, 132, 143]].astype(np.float64).min())
     probe.destroy()
     # (cords soft enough for tl.DT: W dt^2 = 0.02 and 2 G dt = 0.1 of the guard's 4)
     _, anchors, motions = an.scene_hung(k=0.02 * m_corner / tl.DT ** 2, c=0.05 * m_corner / tl.DT, L=4 * an.H0)
@@ -521,7 +460,7 @@ def test_scheduling_through_resorts_and_the_coupled_path():
         g.set_body_motions(_motions(motions))
         g.set_anchors(anchors)
         assert tl.DT <= 0.5 * g.anchors_max_stable_dt()
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         es.append(g)
     before = es[0].stats()["rebuilds"]
     es[0].run_substeps(n, tl.DT, -1)
@@ -532,14 +471,14 @@ def test_scheduling_through_resorts_and_the_coupled_path():
         assert g.stats()["error_flags"] == 0, g.stats()
     assert es[0].stats()["rebuilds"] - before >= 2, es[0].stats()
     s = [_state(g) for g in es]
-    _same_bits(s[0], s[1], "run_substeps(n) against n substeps")
+    hs.same_bits(s[0], s[1], "run_substeps(n) against n substeps")
     assert s[0]["f"][0].any() and es[0].anchor_forces().any()     # (the cords pulled: the body felt it)
     es[1].destroy()
     # the coupled path: a sphere (body 1) under the sheet, the anchored body 0 still
     g = es[0]
     g.reallocate_external_bodies(2)
     g.set_body_motions(_motions({0: an.motion32(an.scene("hung")[2][0][0], np.eye(3), (0, 0, 0), (0, 0, 0))}))
-    _upload(g, X)
+    hs.upload(g, X)
     ball = [Collider(1, body=1, p_WB=(0.375 + 5.5 * an.H0, 0.375 + 5.5 * an.H0, 0.5 - 0.03 - 0.002), dims=(0.03, 0, 0))]
     res = g.run_coupled_substeps(60, tl.DT, ball, 0.5, 1e5, 1e-4)
     g.gpu_sync()
@@ -547,7 +486,7 @@ def test_scheduling_through_resorts_and_the_coupled_path():
     tau, f = g.external_body_force_to_host()
     print(f"coupled: contacts {max(r['contacts'] for r in res)}, anchored body {f[0]}, sphere {f[1]}")
     assert max(r["contacts"] for r in res) > 0 and f[0].any() and f[1].any()
-    assert np.isfinite(g.download(_A().VELOCITIES)).all()
+    assert np.isfinite(g.download(hs.ARR().VELOCITIES)).all()
     g.destroy()
 
 
@@ -585,9 +524,9 @@ def test_refusals():
     assert g.stats()["substeps"] == before
     g.set_body_motions(_motions(motions))
     x0, v0 = an.state("random", "mixed", X)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     g.substep(DT, -1)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     good, lim = g.get_anchors(), g.anchors_max_stable_dt()
     assert np.array_equal(good, table)
     f_before, acc_before = g.anchor_forces(), g.external_body_force_to_host()
@@ -607,9 +546,9 @@ def test_refusals():
     # a table that does not fit 2^31 records is refused by its count, before an anchor is read
     assert g.lib.mpm_set_anchors(g.h, 1 << 31, good.ctypes.data) == -1 and "too large" in g.lib.mpm_last_error().decode()
     assert np.array_equal(g.get_anchors(), good) and g.anchors_max_stable_dt() == lim
-    assert np.array_equal(_bits(g.anchor_forces()), _bits(f_before))
+    assert np.array_equal(hs.bits(g.anchor_forces()), hs.bits(f_before))
     acc = g.external_body_force_to_host()
-    assert np.array_equal(_bits(acc[0]), _bits(acc_before[0])) and np.array_equal(_bits(acc[1]), _bits(acc_before[1]))
+    assert np.array_equal(hs.bits(acc[0]), hs.bits(acc_before[0])) and np.array_equal(hs.bits(acc[1]), hs.bits(acc_before[1]))
     # partitioned, halo, team and chain calls on an engine with anchors
     nb = 64 // 4
     refused(lambda: g.dist_init(0, 1, [0, nb], 2, 2, 2), says="anchors")
@@ -617,7 +556,7 @@ def test_refusals():
     refused(lambda: g.team_prepare(), says="anchors")
     refused(lambda: g.chain_substeps(1, DT), says="anchors")
     # the dt guard: the limit is the restatement's; at it the substep runs, just above it every entry point refuses
-    mass = _vertices(g, _A().MASSES).astype(np.float64)
+    mass = hs.vertices(g, hs.ARR().MASSES).astype(np.float64)
     assert abs(lim / an.max_stable_dt(good, mass) - 1.0) < 1e-5
     before = g.stats()["substeps"]
     big = float(np.nextafter(np.float32(lim), np.float32(np.inf)))

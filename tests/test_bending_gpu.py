@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests import bending as bd
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
@@ -23,43 +24,6 @@ pytestmark = pytest.mark.gpu
 U = bd.U
 DT = 2e-4
 PAIRS = [(m, s) for m in bd.MESHES for s in bd.STATES]
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
-def _engine(cloths, bits=6, deterministic=True, material=None, bodies=0):
-    """cloths: [(X (n, 3) float32 rest positions, T)]"""
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for X, T in cloths:
-        g.add_qr_cloth(X, np.zeros_like(X), T)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, vel=(0.0, 0.0, 0.0), F=None):
-    """vertex positions x (n_verts, 3) in original order; a face particle sits at its corners' mean"""
-    x = np.asarray(x, np.float32)
-    cen = x[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)
-    pos = np.concatenate([cen, x])
-    pids = g.download(_A().PIDS)
-    v = np.broadcast_to(np.asarray(vel, np.float32), pos.shape).copy()
-    g.upload_particle_state(pos[pids], v, np.zeros((len(pos), 9), np.float32), None, F)
 
 
 def _stiffness_for(g, n_cloths, dt, share=0.25, which=None):
@@ -76,10 +40,6 @@ def _stiffness_for(g, n_cloths, dt, share=0.25, which=None):
     return ks
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _check_forces(g, H, k, P, what):
     x = g.dump_cpu_state()[0]
     f = g.bending_forces()
@@ -87,7 +47,7 @@ def _check_forces(g, H, k, P, what):
     B, R = bd.bound(float(np.float32(k)), H, x), bd.rounding_count(P)
     w = bd.margin(f - ref, B, R)
     print(f"bending forces: {what}: {w:.3g} of the bound, {bd.margin(f - ref, B, 1.0):.3g} of 2^-24 B_i")
-    _record(f"bending forces: {what}", w)
+    hs.record(f"bending forces: {what}", w)
     assert w <= 1.0, (what, w)
     return x, f, ref, B
 
@@ -99,11 +59,11 @@ def test_forces_against_float64(name, st):
     H = bd.hinges(X, T)
     Q, P = bd.q_dense(len(X), H)
     k = 2.5e-5
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     g.set_bending([k])
     assert np.array_equal(g.get_bending(), np.array([k], np.float32))
     x0 = bd.state(st, X)
-    _upload(g, x0)
+    hs.upload(g, x0)
     x, f0, ref, B = _check_forces(g, H, k, P, f"{name} {st}")
     assert np.array_equal(x, x0)
     if st == "affine":
@@ -115,19 +75,19 @@ def test_forces_against_float64(name, st):
     # substeps that force a re-sort: the state five cells further along x, two short substeps
     before = g.stats()["rebuilds"]
     shift = np.array([5.0 / 64, 0.0, 0.0], np.float32)
-    _upload(g, x0 + shift)
+    hs.upload(g, x0 + shift)
     g.run_substeps(2, 1e-5, -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
     _check_forces(g, H, k, P, f"{name} {st} after a re-sort")
     # the first positions again, in the new particle order: the same bits
-    _upload(g, x0)
+    hs.upload(g, x0)
     f1 = g.bending_forces()
-    assert np.array_equal(_bits(f1), _bits(f0)), float(np.abs(f1 - f0).max())
+    assert np.array_equal(hs.bits(f1), hs.bits(f0)), float(np.abs(f1 - f0).max())
     g.rebuild_mapping(True)
     _check_forces(g, H, k, P, f"{name} {st} after sort = 1")
     f2 = g.bending_forces()
-    assert np.array_equal(_bits(f2), _bits(f0)), float(np.abs(f2 - f0).max())
+    assert np.array_equal(hs.bits(f2), hs.bits(f0)), float(np.abs(f2 - f0).max())
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -138,10 +98,10 @@ def test_two_cloths_one_without_bending():
     Xb = (Xb + np.array([0.0, 0.0, 0.05], np.float32)).astype(np.float32)
     Ha, Hb = bd.hinges(Xa, Ta), bd.hinges(Xb, Tb)
     (_, Pa), (_, Pb) = bd.q_dense(len(Xa), Ha), bd.q_dense(len(Xb), Hb)
-    g = _engine([(Xa, Ta), (Xb, Tb)])
+    g = hs.engine([(Xa, Ta), (Xb, Tb)])
     assert g.cloth_count() == 2 and not g.get_bending().any()
     xa, xb = bd.state("cylinder3", Xa), bd.state("perturbed", Xb)
-    _upload(g, np.concatenate([xa, xb]))
+    hs.upload(g, np.concatenate([xa, xb]))
     na = len(Xa)
     for ks in ((3e-5, 0.0), (0.0, 7e-5), (3e-5, 7e-5)):
         g.set_bending(ks)
@@ -153,7 +113,7 @@ def test_two_cloths_one_without_bending():
                 continue
             ref, B = bd.force64(float(np.float32(k)), H, x), bd.bound(float(np.float32(k)), H, x)
             w = bd.margin(fc - ref, B, bd.rounding_count(P))
-            _record(f"bending forces: two cloths {ks}", w)
+            hs.record(f"bending forces: two cloths {ks}", w)
             assert w <= 1.0 and fc.any(), (ks, w)
     g.destroy()
 
@@ -162,15 +122,15 @@ def test_two_cloths_one_without_bending():
 @pytest.mark.parametrize("name", ["jittered", "fan"])
 def test_total_forces_include_bending(name):
     """(the fan's hub has 12 faces: its membrane force comes from the adjacency walk, the jittered sheet's from DP::VF)"""
-    A = _A()
+    A = hs.ARR()
     X, T = bd.mesh(name)
-    a, b = _engine([(X, T)]), _engine([(X, T)])
+    a, b = hs.engine([(X, T)]), hs.engine([(X, T)])
     a.set_bending([4e-5])
     x0 = bd.state("cylinder3", X)
     nf = len(T)
     out = []
     for g in (a, b):
-        _upload(g, x0)
+        hs.upload(g, x0)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(DT)
         f, pids = g.download(A.FORCES), g.download(A.PIDS)
@@ -183,7 +143,7 @@ def test_total_forces_include_bending(name):
     err = np.abs(out[0].astype(np.float64) - tot)
     w = float((err / np.maximum(U * np.abs(out[0]).astype(np.float64), 1e-300))[err > 0].max()) if (err > 0).any() else 0.0
     print(f"total forces: {name}: {w:.3g} of one rounding of the sum")
-    _record(f"bending: total forces {name}", w)
+    hs.record(f"bending: total forces {name}", w)
     assert w <= 1.0, w
     assert not b.bending_forces().any() and b.bending_max_stable_dt() == np.inf
     for g in (a, b):
@@ -196,12 +156,12 @@ def test_total_forces_include_bending(name):
 def test_p2g_node_by_node(mode):
     from tests import helpers
     helpers.tag_default_engine(mode == "default")
-    A = _A()
+    A = hs.ARR()
     X, T = bd.mesh("jittered")
     nf = len(T)
-    g = _engine([(X, T)], deterministic=mode == "deterministic")
+    g = hs.engine([(X, T)], deterministic=mode == "deterministic")
     _stiffness_for(g, 1, tl.DT)
-    _upload(g, bd.state("cylinder3", X), vel=(0.3, -0.2, 0.1))
+    hs.upload(g, bd.state("cylinder3", X), v=(0.3, -0.2, 0.1))
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(tl.DT)
     d = {k: g.download(a) for k, a in (("pids", A.PIDS), ("x", A.POSITIONS), ("v", A.VELOCITIES), ("C", A.AFFINE),
@@ -219,7 +179,7 @@ def test_p2g_node_by_node(mode):
     for field, err, bnd in (("mass", np.abs(gm - r["m"]), bm), ("momentum", np.abs(gmv - r["mv"]), bmv)):
         w = tl.margin(err, bnd)
         print(f"bending p2g [{mode}] {field}: {w:.4g} of the bound")
-        _record(f"bending: p2g [{mode}] {field}", w)
+        hs.record(f"bending: p2g [{mode}] {field}", w)
         assert w <= 1.0, (field, w)
     assert np.array_equal(flags, r["flags"])
     # bending is in the sums: without it the momentum is outside the bound
@@ -230,27 +190,16 @@ def test_p2g_node_by_node(mode):
 
 
 # ---- 4 -------------------------------------------------------------------------------------------------------------
-def _state(g):
-    A = _A()
-    return dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS),
-                F=g.download(A.DEFORMATION_GRADIENTS))
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), (what, k, float(np.abs(a[k].astype(np.float64) - b[k]).max()))
-
-
 def test_scheduling_through_resorts():
     """a bent sheet that flies and falls through several re-sorts, deterministic: run_substeps(n), n x substep and n x
     the five phase calls give the same bits in x, v, C and F -- a force added twice under the gate would not"""
     X, T = bd.mesh("regular")
     x0 = bd.state("cylinder30", X)
     n = 60
-    es = [_engine([(X, T)]) for _ in range(3)]
+    es = [hs.engine([(X, T)]) for _ in range(3)]
     for g in es:
         _stiffness_for(g, 1, tl.DT)
-        _upload(g, x0, vel=(3.0, 0.4, 0.0))
+        hs.upload(g, x0, v=(3.0, 0.4, 0.0))
     before = es[0].stats()["rebuilds"]
     es[0].run_substeps(n, tl.DT, -1)
     for _ in range(n):
@@ -266,9 +215,9 @@ def test_scheduling_through_resorts():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0, g.stats()
     assert es[0].stats()["rebuilds"] - before >= 3, es[0].stats()
-    s = [_state(g) for g in es]
-    _same_bits(s[0], s[1], "run_substeps(n) against n substeps")
-    _same_bits(s[0], s[2], "run_substeps(n) against the phase calls")
+    s = [hs.state(g) for g in es]
+    hs.same_bits(s[0], s[1], "run_substeps(n) against n substeps")
+    hs.same_bits(s[0], s[2], "run_substeps(n) against the phase calls")
     assert es[0].bending_forces().any()
     for g in es:
         g.destroy()
@@ -277,16 +226,16 @@ def test_scheduling_through_resorts():
 def test_coupled_path_runs():
     from drake_amd import Collider
     X, T = bd.mesh("regular")
-    g = _engine([(X, T)], bodies=1)
+    g = hs.engine([(X, T)], bodies=1)
     _stiffness_for(g, 1, tl.DT)
     x0 = bd.state("cylinder30", X)
-    _upload(g, x0)
+    hs.upload(g, x0)
     floor = [Collider(0, body=0, p_WB=(0.5, 0.5, float(x0[:, 2].min()) - 0.002))]
     res = g.run_coupled_substeps(40, tl.DT, floor, 0.5, 1e5, 1e-4)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0
     assert max(r["contacts"] for r in res) > 0, "the sheet never reached the floor"
-    assert np.isfinite(g.download(_A().VELOCITIES)).all()
+    assert np.isfinite(g.download(hs.ARR().VELOCITIES)).all()
     g.destroy()
 
 
@@ -296,7 +245,7 @@ def test_off_means_off():
     bit, and with the same number of re-sort check launches (the quiet-time hint is in use again)"""
     from drake_amd import scenes
     pos, idx = scenes.cloth_sheet(32, 0.3, 0.6, (0.3, 0.5))
-    es = [_engine([(pos, idx.reshape(-1, 3))]) for _ in range(3)]
+    es = [hs.engine([(pos, idx.reshape(-1, 3))]) for _ in range(3)]
     es[1].set_bending([0.0])
     es[2].set_bending([1e-5])
     assert es[2].bending_max_stable_dt() < np.inf
@@ -305,7 +254,7 @@ def test_off_means_off():
     vel = np.array([4.0, 0.3, 0.0], np.float32) + 0.05 * np.random.default_rng(3).normal(size=pos.shape).astype(np.float32)
     before = es[0].stats()["rebuilds"]
     for g in es:
-        pids = g.download(_A().PIDS)
+        pids = g.download(hs.ARR().PIDS)
         allv = np.concatenate([vel[g._tri].mean(axis=1), vel]).astype(np.float32)
         g.upload_particle_state(None, allv[pids], None, None, None)
         for _ in range(4):
@@ -313,9 +262,9 @@ def test_off_means_off():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 2, es[0].stats()
-    s = [_state(g) for g in es]
-    _same_bits(s[0], s[1], "all zeros")
-    _same_bits(s[0], s[2], "set and cleared")
+    s = [hs.state(g) for g in es]
+    hs.same_bits(s[0], s[1], "all zeros")
+    hs.same_bits(s[0], s[2], "set and cleared")
     assert es[0].stats()["resort_checks"] == es[1].stats()["resort_checks"] == es[2].stats()["resort_checks"]
     for g in es:
         g.destroy()
@@ -356,7 +305,7 @@ def test_bent_sheet_unbends():
       bound, the membrane force within a few roundings of its terms.
     * The twin without bending moves at most 1/2 a T^2, a = 16 (lambda + 2 mu) / rho s / h: its only force comes from
       the rounding of the positions, a strain of at most s = 8 u max|x| / h per face."""
-    A = _A()
+    A = hs.ARR()
     X, T = bd.mesh("regular")
     H = bd.hinges(X, T)
     Q, P = bd.q_dense(len(X), H)
@@ -364,11 +313,11 @@ def test_bent_sheet_unbends():
     x0 = _inscribed_cylinder(X, 6 * h).astype(np.float32)
     rot = _frames(x0, T) @ np.linalg.inv(_frames(X, T))
     mat = dict(gravity=0.0)
-    a, b = _engine([(X, T)], material=mat), _engine([(X, T)], material=mat)
+    a, b = hs.engine([(X, T)], material=mat), hs.engine([(X, T)], material=mat)
     ks = _stiffness_for(a, 1, DT)
     for g in (a, b):
         F0 = g.download(A.DEFORMATION_GRADIENTS).reshape(-1, 3, 3).astype(np.float64)
-        _upload(g, x0, F=(rot @ F0).astype(np.float32).reshape(-1, 9))
+        hs.upload(g, x0, F=(rot @ F0).astype(np.float32).reshape(-1, 9))
     E0 = bd.energy64(ks[0], H, x0)
     f0 = a.bending_forces().astype(np.float64)
     B0 = bd.bound(ks[0], H, x0)
@@ -399,7 +348,7 @@ def test_bent_sheet_unbends():
     bound = steps * (128 * U * gross + DT * U * float((bd.rounding_count(P) * B0 + 16 * np.abs(f0).max(axis=1)).sum()))
     print(f"unbending: momentum added by the substeps {mom:.3e}, bound {bound:.3e}, gross {gross:.3e}; "
           f"sum m v at the end {np.abs(momentum(a)[0]).max():.3e}")
-    _record("bending: momentum of the unbending sheet", mom / bound)
+    hs.record("bending: momentum of the unbending sheet", mom / bound)
     assert gross > 0 and mom <= bound, (mom, bound)
     # the twin
     mt = b.default_material()
@@ -409,7 +358,7 @@ def test_bent_sheet_unbends():
     still = 0.5 * (16 * (lam + 2 * mu) / mt.density * s / h) * (steps * DT) ** 2
     moved = float(np.abs(b.dump_cpu_state()[0] - x0).max())
     print(f"unbending: the twin moved {moved:.3e}, bound {still:.3e}; the bent sheet {np.abs(x1 - x0).max():.3e}")
-    _record("bending: the twin without bending", moved / still)
+    hs.record("bending: the twin without bending", moved / still)
     assert moved <= still, (moved, still)
     assert float(np.abs(x1 - x0).max()) > still, "the bending force moves the sheet"
     for g in (a, b):
@@ -437,22 +386,22 @@ def test_refusals():
     Xd = X.copy()
     i, j, k = T[7]
     Xd[k] = 0.5 * (Xd[i] + Xd[j])
-    gd = _engine([(Xd, T), (X + np.array([0, 0, 0.05], np.float32), T)])
+    gd = hs.engine([(Xd, T), (X + np.array([0, 0, 0.05], np.float32), T)])
     refused(lambda: gd.set_bending([1e-5, 1e-5]), says="face 7")
     assert not gd.get_bending().any() and gd.bending_max_stable_dt() == np.inf
     gd.set_bending([0.0, 1e-5])
     gd.destroy()
 
-    g = _engine([(X, T)], bodies=1)
+    g = hs.engine([(X, T)], bodies=1)
     good = _stiffness_for(g, 1, tl.DT, share=0.9)
     lim = g.bending_max_stable_dt()
     x0 = bd.state("cylinder30", X)
-    _upload(g, x0)
+    hs.upload(g, x0)
     f_before = g.bending_forces()
     for bad in ([-1e-5], [np.nan], [np.inf], [1e-5, 1e-5]):
         refused(lambda bad=bad: g.set_bending(bad))
     assert np.array_equal(g.get_bending(), np.array(good, np.float32)) and g.bending_max_stable_dt() == lim
-    assert np.array_equal(_bits(g.bending_forces()), _bits(f_before))
+    assert np.array_equal(hs.bits(g.bending_forces()), hs.bits(f_before))
     # partitioned, halo, team and chain calls on an engine with bending
     nb = 64 // 4
     refused(lambda: g.dist_init(0, 1, [0, nb], 2, 2, 2), says="bending")

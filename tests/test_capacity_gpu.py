@@ -5,20 +5,15 @@ import os
 import numpy as np
 import pytest
 
+from tests import harness
+
 pytestmark = pytest.mark.gpu
 DT = 1e-3
 
 
 def _with_env(name, value, fn):
-    old = os.environ.get(name)
-    os.environ[name] = str(value)
-    try:
+    with harness.environ({name: str(value)}):
         return fn()
-    finally:
-        if old is None:
-            del os.environ[name]
-        else:
-            os.environ[name] = old
 
 
 def _spread_scene(bits=6):

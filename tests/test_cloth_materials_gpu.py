@@ -7,17 +7,13 @@ import numpy as np
 import pytest
 
 from tests.helpers import close, natural_scales
+from tests import harness as hs
 
 pytestmark = pytest.mark.gpu
 DT = 1e-3
 ERR_INVALID = -1
 # different from mpm_default_material in every per-cloth field
 M_FIELDS = dict(youngs_modulus=2.5e5, poisson_ratio=0.22, density=1300.0, gamma=40.0, K=2.0e5, c_F=15.0)
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
 
 
 def _cm(**kw):
@@ -61,16 +57,8 @@ def _engine(sheets, materials=None, engine_material=None, deterministic=True, fa
     return g
 
 
-def _phases(g, dt=DT, bc=-1):
-    g.rebuild_mapping(False)
-    g.calc_fem_state_and_force(dt)
-    g.particle_to_grid(dt)
-    g.update_grid(bc)
-    g.grid_to_particle(dt)
-
-
 def _state(g, grid=True):
-    A = _A()
+    A = hs.ARR()
     s = {k: g.download(getattr(A, k)) for k in ("POSITIONS", "VELOCITIES", "AFFINE", "DEFORMATION_GRADIENTS", "FORCES",
                                                  "TAUS", "MASSES", "PIDS")}
     if grid:
@@ -93,7 +81,7 @@ def _same(a, b, what):
 # sums differ in their last bits, so the power of two derived from them could differ -- but only when the total mass lies
 # within about 1e-7 (relative) of a power of two.  The scenes of these tests are checked to be far from that boundary.
 def _far_from_power_of_two(g):
-    m = float(np.sum(g.download(_A().MASSES).astype(np.float64)))
+    m = float(np.sum(g.download(hs.ARR().MASSES).astype(np.float64)))
     r = np.log2(m)
     assert abs(r - np.round(r)) > 1e-4, m
 
@@ -101,7 +89,7 @@ def _far_from_power_of_two(g):
 def _run(g, path, n, colliders=None):
     if path == "phases":
         for _ in range(n):
-            _phases(g)
+            hs.phases(g, DT)
     elif path == "run_substeps":
         g.run_substeps(n, DT, -1)
     else:
@@ -147,7 +135,7 @@ def test_same_material_same_bits_outside_deterministic_mode():
     """without deterministic mode ParticleToGrid's float sums depend on the order of arrival, so whole substeps are not
     reproducible run to run on any engine; CalcFemStateAndForce is (fixed summation order): after it the forces, taus,
     F and masses are equal to the bit, and one whole substep agrees to float rounding"""
-    A = _A()
+    A = hs.ARR()
     sheets = _sheets()
     M = _cm(**M_FIELDS)
     for fast_math in (False, True):
@@ -166,7 +154,7 @@ def test_same_material_same_bits_outside_deterministic_mode():
 
 
 def _by_pid(g, arr):
-    pid = g.download(_A().PIDS)
+    pid = g.download(hs.ARR().PIDS)
     out = np.empty_like(arr)
     out[pid] = arr
     return out
@@ -188,7 +176,7 @@ def _two_sheets_scaled():
 
 
 def _scaling_check(g, nfa, nva, what):
-    A = _A()
+    A = hs.ARR()
     nf = g.n_faces
     f, tau, m = (_by_pid(g, g.download(a)) for a in (A.FORCES, A.TAUS, A.MASSES))
     ia = np.concatenate([np.arange(nfa), nf + np.arange(nva)])   # A's particle ids ...
@@ -203,7 +191,7 @@ def test_exact_power_of_two_scaling():
     """B has E, K, gamma and rho doubled, the same nu, c_F = 0: after CalcFemStateAndForce its vertex forces, taus and
     masses are exactly twice A's; again after 30 substeps with re-sorts, with A's state uploaded into both sheets (the
     per-face lookup after the slots have been shuffled)"""
-    A = _A()
+    A = hs.ARR()
     sheets, ma, mb = _two_sheets_scaled()
     nva, nfa = sheets[0][0].shape[0], sheets[0][2].size // 3
     g = _engine(sheets, materials=[ma, mb])
@@ -218,7 +206,7 @@ def test_exact_power_of_two_scaling():
     assert np.array_equal(vol[ib], vol[ia])
     assert np.all(np.abs(vol[ia] - mass[ia].astype(np.float64) / ma.density) <= np.spacing(vol[ia]))
     for k in range(30):
-        _phases(g)
+        hs.phases(g, DT)
         if k % 7 == 0:
             g.rebuild_mapping(True)   # (a slot sort as well: the API order moves too)
     g.gpu_sync()
@@ -252,7 +240,7 @@ def test_three_materials_against_single_sheet_oracles():
     every sheet matches a CPU oracle that holds only that sheet, with that material"""
     from oracle import oracle as orc
     from tests.helpers import _MATERIAL_FIELDS
-    A = _A()
+    A = hs.ARR()
     mats = [dict(youngs_modulus=2e5, poisson_ratio=0.25, density=800.0, gamma=0.0, K=1e5, c_F=0.0),
             dict(youngs_modulus=6e5, poisson_ratio=0.35, density=2500.0, gamma=50.0, K=3e5, c_F=20.0),
             dict(youngs_modulus=1e6, poisson_ratio=0.1, density=4000.0, gamma=10.0, K=5e4, c_F=5.0)]
@@ -274,7 +262,7 @@ def test_three_materials_against_single_sheet_oracles():
     for n_done, n in ((0, 1), (1, 20)):
         scs = [natural_scales(o, DT) for o in oracles]
         for _ in range(n - n_done):
-            _phases(g)
+            hs.phases(g, DT)
             for o in oracles:
                 o.substep(DT, -1)
         g.gpu_sync()
@@ -298,7 +286,7 @@ def test_three_materials_against_single_sheet_oracles():
 def _balance(g, boxes, ids, faces, dt, n_settle, n_win):
     """coupled substeps: settle, then a window of n_win; -> per sheet (impulse on its body over the window,
     m g T - (p(T) - p(0)) + sum of d, mass)"""
-    A = _A()
+    A = hs.ARR()
     corners = g.download(A.INDICES).reshape(-1, 3)
     g.run_coupled_substeps(n_settle, dt, boxes, 0.5, 1e5, 1e-4)
 
@@ -351,7 +339,7 @@ def test_contact_momentum_balance_two_densities():
     info = [g.cloth_info(c) for c in range(2)]
     faces = [i["first_face"] + np.arange(i["n_faces"]) for i in info]
     ids = [np.concatenate([f, nf + i["first_vertex"] + np.arange(i["n_verts"])]) for f, i in zip(faces, info)]
-    vols = _by_pid(g, g.download(_A().VOLUMES)).astype(np.float64)
+    vols = _by_pid(g, g.download(hs.ARR().VOLUMES)).astype(np.float64)
     multi = _balance(g, boxes, ids, faces, dt, n_settle, n_win)
     T = n_win * float(np.float32(dt))
     for c in range(2):
@@ -460,6 +448,6 @@ def test_refusals_and_getters():
     for g in (a, b):
         g.finalize()
         for _ in range(5):
-            _phases(g)
+            hs.phases(g, DT)
         g.gpu_sync()
     _same(_state(a), _state(b), "after refusals")

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests import contact_layouts as cl
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 ALPHAS = [2.0 ** -j for j in range(8)]
@@ -57,11 +58,6 @@ def restate(lay, o, pre, sequential, relax=cl.RELAX, received=None):
     vel0, e0 = cl.gather(wt, keys, gv, gm)
     dr = cl.direction(lay, P, wt, keys, mass_c, T, gm, gv, gvs, relax=relax, sequential=sequential, received=received)
     return dict(P=P, vp=vp, mass_c=mass_c, wt=wt, keys=keys, T=T, vel0=vel0, e0=e0, dr=dr)
-
-
-def _record(what, ratio):
-    from tests.helpers import MARGINS
-    MARGINS.append((ratio, what, 1.0, ratio, ratio))
 
 
 @pytest.mark.parametrize("name", cl.NAMES)
@@ -218,7 +214,7 @@ def test_float_oracle_within_the_bounds(name):
     R = restate(lay, o, pre, sequential=True)
     worst = _check(lay, o, pre, r, R, True, name)
     for k, v in worst.items():
-        _record(f"float oracle within the contact bound: {name} {k}", v)
+        hs.record(f"float oracle within the contact bound: {name} {k}", v)
     assert all(v <= 1.0 for v in worst.values()), worst
 
 

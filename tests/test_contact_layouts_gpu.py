@@ -12,12 +12,11 @@ module, contact by contact, node by node and body by body:
     exact       the exact line search ends where the restated dE/dalpha vanishes within its bound (or at alpha = 1 with
                 dE(1) < 0)
 Each phase is judged on the engine's own inputs of that phase (the grid after UpdateGrid, the direction it computed)."""
-import os
-
 import numpy as np
 import pytest
 
 from tests import contact_layouts as cl
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
@@ -28,19 +27,10 @@ CANDIDATES = [2.0 ** -j for j in range(28)]
 def _create(lay, deterministic=False, env=None):
     """the layout's mesh in a finalised engine -> (engine, API slot of every particle of the layout)"""
     from drake_amd import ARR as A, GpuMpm
-    env = dict(env or {})
-    saved = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with hs.environ(env):
         mat = GpuMpm.default_material()
         mat.gravity_axis = lay["gravity_axis"]
         g = GpuMpm(lay["bits"], mat)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     g.set_deterministic(deterministic)
     for rest, vel, idx in lay["cloths"]:
         g.add_qr_cloth(rest, vel, idx)
@@ -54,7 +44,7 @@ def _create(lay, deterministic=False, env=None):
     return g, slot_of, pids
 
 
-def _upload(g, lay, pids):
+def _upload_layout(g, lay, pids):
     g.upload_particle_state(lay["pos"][pids], lay["vel"][pids], lay["C"][pids], lay["vol"][pids], None)
     g.reallocate_external_bodies(lay["n_bodies"])
 
@@ -81,7 +71,7 @@ def _engine(lay, deterministic=False, env=None, before_pairs=None):
     if before_pairs:
         before_pairs(g)
     k, d, dt, mu = cl.params32(lay["params"])
-    _upload(g, lay, pids)
+    _upload_layout(g, lay, pids)
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(dt)
     g.particle_to_grid(dt)
@@ -107,18 +97,13 @@ def _solve(g, lay, iters, exact=False):
     return _outputs(g, g.update_contact(dt, mu, k, d, exact_line_search=exact, max_newton_iterations=iters))
 
 
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
 class _Checks:
     def __init__(self, tag):
         self.tag, self.fails = tag, []
 
     def __call__(self, field, err, bound):
         w = cl.margin(np.abs(np.asarray(err, np.float64)), np.asarray(bound, np.float64))
-        _record(f"contact layouts: {self.tag} {field}", w)
+        hs.record(f"contact layouts: {self.tag} {field}", w)
         if not w <= 1.0:
             self.fails.append(f"{field}: {w:.3g} x the bound")
 
@@ -276,5 +261,5 @@ def test_exact_line_search_ends_at_the_restated_root(name):
     at_root = abs(a["dE"]) <= a["edE"] + f_tol + 2 * x_tol * abs(a["d2E"])
     at_end = al == 1.0 and one["dE"] < one["edE"]
     r = abs(a["dE"]) / (a["edE"] + f_tol + 2 * x_tol * abs(a["d2E"]))
-    _record(f"contact layouts: {name} exact search dE(alpha)", r if not at_end else 0.0)
+    hs.record(f"contact layouts: {name} exact search dE(alpha)", r if not at_end else 0.0)
     assert at_root or at_end, (al, a, one)

@@ -11,6 +11,7 @@ import pytest
 
 from tests import contact_layouts as cl
 from tests import contact_materials as cm
+from tests import harness as hs
 from tests import transfer_layouts as tl
 from tests import test_contact_layouts_gpu as base
 from tests import test_contact_noroundtrip_gpu as nr
@@ -143,7 +144,7 @@ def test_exact_line_search_with_the_table_ends_at_the_restated_root():
     at_root = abs(a["dE"]) <= a["edE"] + f_tol + 2 * x_tol * abs(a["d2E"])
     at_end = al == 1.0 and one["dE"] < one["edE"]
     r = abs(a["dE"]) / (a["edE"] + f_tol + 2 * x_tol * abs(a["d2E"]))
-    base._record("contact materials: bodies exact search dE(alpha)", r if not at_end else 0.0)
+    hs.record("contact materials: bodies exact search dE(alpha)", r if not at_end else 0.0)
     assert at_root or at_end, (al, a, one)
 
 

@@ -9,10 +9,10 @@ synchronises >= 3 times per Newton iteration).
 * a settled scene, whose pair list repeats from substep to substep: the previous solve's sorted order, per-cell runs and
   node list are reused (verified on the device, entry by entry); results equal to the bit those of the full set-up; a
   list that changes after a repeat is caught on the device and the solve repeated with the full set-up."""
-import os
-
 import numpy as np
 import pytest
+
+from tests import harness
 
 pytestmark = pytest.mark.gpu
 DT, MU, K, D = 2e-4, 1.0, 1e6, 1e-5      # config 3's parameters (mpm_bagging.cc:9,15-17)
@@ -23,17 +23,8 @@ def _engine(env=None, sheets=None, bodies=1):
     from drake_amd import GpuMpm, scenes
     # (deterministic from Finalize's own first sort on: two engines then agree to the bit, and a difference between two
     # of them is a difference between the paths under test)
-    env = dict(env or {}, MPM_DETERMINISTIC="1")
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with harness.environ(dict(env or {}, MPM_DETERMINISTIC="1")):
         g = GpuMpm(6)     # (environment switches are read per handle, at mpm_create)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     scenes.populate(g, [(p.copy(), v.copy(), i.copy()) for p, v, i in sheets])
     g.reallocate_external_bodies(bodies)
     return g

@@ -38,6 +38,7 @@ import pytest
 
 from tests import contact_layouts as cl
 from tests import cut_layouts as ct
+from tests import harness as hs
 from tests import test_contact_layouts_gpu as single
 from tests import transfer_layouts as tl
 
@@ -109,7 +110,7 @@ class _World:
         self.w = LocalWorld(self.engines, self.cuts, Z, 0, 0, capacity_blocks=512, migrate_every=1000, migrate_capacity=8192,
                             device=torch.device("cuda", 0))
         for g in self.engines:
-            single._upload(g, lay, self.pids)
+            single._upload_layout(g, lay, self.pids)
         self.parts = ct.split(lay, cuts, Z)
         self.timeout = _timeout(lay["name"])
         self.bar = threading.Barrier(self.world)
@@ -490,7 +491,7 @@ def test_exact_line_search_of_the_world_ends_at_the_restated_root():
     at_root = abs(a["dE"]) <= a["edE"] + f_tol + 2 * x_tol * abs(a["d2E"])
     at_end = al == 1.0 and one["dE"] < one["edE"]
     r = abs(a["dE"]) / (a["edE"] + f_tol + 2 * x_tol * abs(a["d2E"]))
-    single._record("contact partition: cut exact search dE(alpha)", r if not at_end else 0.0)
+    hs.record("contact partition: cut exact search dE(alpha)", r if not at_end else 0.0)
     assert at_root or at_end, (al, a, one)
     W.destroy()
 

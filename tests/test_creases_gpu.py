@@ -19,6 +19,7 @@ import pytest
 
 from tests import bending as bd
 from tests import creases as cr
+from tests import harness as hs
 from tests import shell_bending as sb
 
 pytestmark = pytest.mark.gpu
@@ -26,47 +27,6 @@ pytestmark = pytest.mark.gpu
 U, F = cr.U, np.float32
 DT = 2e-4
 TINY_DT = 1e-5
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _engine(cloths, bits=6, deterministic=True, material=None):
-    """cloths: [(X (n, 3) float32 positions as added, T)]"""
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for X, T in cloths:
-        g.add_qr_cloth(X, np.zeros_like(X), T)
-    g.finalize()
-    g._tri = np.concatenate([T.reshape(-1, 3) + o for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, F)
-    v = np.zeros_like(x) if v is None else np.asarray(v, F)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(F)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), F), None, None)
-
-
-def _vertices(g, which):
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros((g.n_verts,) + a.shape[1:], a.dtype)
-    out[pids[pids >= g.n_faces] - g.n_faces] = a[pids >= g.n_faces]
-    return out
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, F).view(np.uint32)
 
 
 def _table(rows):
@@ -96,21 +56,21 @@ def _check_step(g, x0, H, rows, hinge_cloth, what, step):
     """the state x0 uploaded, the measure taken, `step` run, and psibar against the measure, the host function and float64
     -> (psibar before, psibar after, yields of the host function)"""
     from drake_amd import crease_hinge
-    _upload(g, x0)
+    hs.upload(g, x0)
     before, _ = g.crease_state()
     psi_m, dpsi_m, next_m = g.crease_measure()
-    assert np.array_equal(_bits(g.crease_state()[0]), _bits(before))          # (the measure changes no state)
+    assert np.array_equal(hs.bits(g.crease_state()[0]), hs.bits(before))          # (the measure changes no state)
     step(g)
     after, count = g.crease_state()
     assert g.stats()["error_flags"] == 0
     y, eta, P = cr.hinge_records(hinge_cloth, rows)
     psi_h, dpsi_h, next_h, yields_h = crease_hinge(np.asarray(x0, F)[H].reshape(-1, 4, 3), before, y, eta, P)
-    assert np.array_equal(_bits(next_m), _bits(after)), (what, int((_bits(next_m) != _bits(after)).sum()))
-    assert np.array_equal(_bits(after), _bits(next_h)), (what, int((_bits(after) != _bits(next_h)).sum()))
-    assert np.array_equal(_bits(psi_m), _bits(psi_h)) and np.array_equal(_bits(dpsi_m), _bits(dpsi_h)), what
+    assert np.array_equal(hs.bits(next_m), hs.bits(after)), (what, int((hs.bits(next_m) != hs.bits(after)).sum()))
+    assert np.array_equal(hs.bits(after), hs.bits(next_h)), (what, int((hs.bits(after) != hs.bits(next_h)).sum()))
+    assert np.array_equal(hs.bits(psi_m), hs.bits(psi_h)) and np.array_equal(hs.bits(dpsi_m), hs.bits(dpsi_h)), what
     act = sb.active(x0, H)
     ref, decided = cr.verdict64(x0, H, before, y, act)
-    changed = _bits(after) != _bits(before)
+    changed = hs.bits(after) != hs.bits(before)
     assert np.array_equal(yields_h[decided], ref[decided]), what
     assert not (changed & ~yields_h).any()
     want, bound = cr.return64(x0, H, before, y, eta, P, act)
@@ -128,12 +88,12 @@ def test_one_substep_against_float64_the_host_function_and_a_twin(name, st):
     X, T, rest = sb.mesh(name)
     H = sb.hinges(T)
     if len(H) == 0:
-        g = _engine([(X, T)])
+        g = hs.engine([(X, T)])
         with pytest.raises(Exception, match="shell bending"):
             g.set_creases(_table([(0.05, 0.0, 0.0)]))
         g.destroy()
         return
-    g, twin = _engine([(X, T)]), _engine([(X, T)])
+    g, twin = hs.engine([(X, T)]), hs.engine([(X, T)])
     for e in (g, twin):
         e.set_shell_bending([sb.K], rest)
     x0 = sb.state(name, st)
@@ -144,21 +104,21 @@ def test_one_substep_against_float64_the_host_function_and_a_twin(name, st):
         g.set_crease_state(None)
         g.set_creases(_table(rows))
         before, after, yields = _check_step(g, x0, H, rows, np.zeros(len(H), int), f"{name} {st} at {angle}", step)
-        assert np.array_equal(_bits(before), _bits(g.shell_hinges()[2]))
+        assert np.array_equal(hs.bits(before), hs.bits(g.shell_hinges()[2]))
         if st in ("rest", "rigid", "collinear"):
             assert not yields.any() and g.crease_state()[1][0] == 0
         if st == "perturbed" and len(H) > 1:
             assert yields.any() and not yields.all()
         # the twin: no yield anywhere, psibar set to the same values, the same positions -> the same forces, to the bit
-        x1 = _vertices(g, _A().POSITIONS)
+        x1 = hs.vertices(g, hs.ARR().POSITIONS)
         twin.set_crease_state(after)
-        _upload(twin, x1)
-        assert np.array_equal(_bits(twin.crease_state()[0]), _bits(after))
-        assert np.array_equal(_bits(g.shell_forces()), _bits(twin.shell_forces())), (name, st, angle)
-        assert np.array_equal(_bits(g.shell_state()[1]), _bits(twin.shell_state()[1]))
+        hs.upload(twin, x1)
+        assert np.array_equal(hs.bits(twin.crease_state()[0]), hs.bits(after))
+        assert np.array_equal(hs.bits(g.shell_forces()), hs.bits(twin.shell_forces())), (name, st, angle)
+        assert np.array_equal(hs.bits(g.shell_state()[1]), hs.bits(twin.shell_state()[1]))
         assert np.array_equal(g.shell_state()[0].view(np.uint64), twin.shell_state()[0].view(np.uint64))
         # (mpm_shell_hinges keeps reporting the rest values)
-        assert np.array_equal(_bits(g.shell_hinges()[2]), _bits(before))
+        assert np.array_equal(hs.bits(g.shell_hinges()[2]), hs.bits(before))
     for e in (g, twin):
         assert e.stats()["error_flags"] == 0
         e.destroy()
@@ -169,7 +129,7 @@ def test_one_substep_against_float64_the_host_function_and_a_twin(name, st):
 def test_strips_around_a_wave_and_a_block(n_faces):
     X, T, x = cr.strip(n_faces)
     H = sb.hinges(T)
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     g.set_shell_bending([sb.K])
     assert np.array_equal(g.shell_hinges()[0], H) and len(H) == n_faces - 1
     for angle in cr.YIELD_ANGLES:
@@ -178,14 +138,14 @@ def test_strips_around_a_wave_and_a_block(n_faces):
         g.set_creases(_table(rows))
         before, after, yields = _check_step(g, x, H, rows, np.zeros(len(H), int), f"strip of {n_faces} faces at {angle}", _fem)
         assert yields.any() and not yields.all()
-        assert yields[-1] == (_bits(after)[-1] != _bits(before)[-1])      # (the last lane: alone in its wave or block)
-        assert g.crease_state()[1][0] == int((_bits(after) != _bits(before)).sum())
+        assert yields[-1] == (hs.bits(after)[-1] != hs.bits(before)[-1])      # (the last lane: alone in its wave or block)
+        assert g.crease_state()[1][0] == int((hs.bits(after) != hs.bits(before)).sum())
     g.destroy()
 
 
 def test_three_cloths_plastic_elastic_and_clamped():
     cloths, rows, x = cr.three_cloths()
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_shell_bending([sb.K] * 3)
     ids, _, psibar0 = g.shell_hinges()
     first = np.cumsum([0] + [len(X) for X, _ in cloths])
@@ -196,7 +156,7 @@ def test_three_cloths_plastic_elastic_and_clamped():
     before, after, yields = _check_step(g, x, ids.astype(np.int64), rows, hinge_cloth, "three cloths", _fem)
     count = g.crease_state()[1]
     assert count[0] > 0 and count[1] == 0 and count[2] > 0
-    assert not (_bits(after) != _bits(before))[hinge_cloth == 1].any() and not yields[hinge_cloth == 1].any()
+    assert not (hs.bits(after) != hs.bits(before))[hinge_cloth == 1].any() and not yields[hinge_cloth == 1].any()
     P = cr.chord(1.0)
     assert np.abs(after[hinge_cloth == 0]).max() > P and np.all(np.abs(after[hinge_cloth == 2]) <= P)
     # a second pass with the folds opened to 2.2 rad (on the same positions the hinges of cloth 0 would sit exactly at their
@@ -204,7 +164,7 @@ def test_three_cloths_plastic_elastic_and_clamped():
     # at the clamp P = 2 sin(0.5)
     x2 = cr.three_cloths(2.2)[2]
     _, after2, _ = _check_step(g, x2, ids.astype(np.int64), rows, hinge_cloth, "three cloths, opened to 2.2", _fem)
-    moved = _bits(after2) != _bits(after)
+    moved = hs.bits(after2) != hs.bits(after)
     assert moved[hinge_cloth == 2].any() and not moved[hinge_cloth == 1].any()
     assert (np.abs(after2[hinge_cloth == 2]) == P).any() and np.all(np.abs(after2[hinge_cloth == 2]) <= P)      # (the clamp acts)
     g.destroy()
@@ -217,7 +177,7 @@ def test_particle_order():
     both by original id, the vertex-force chain run without a re-sort in between: different slots, the same psibar bits,
     and the same in default (non-deterministic) mode."""
     from tests import rest_shape as rs
-    A = _A()
+    A = hs.ARR()
     pos, idx = rs.sheet()
     wide = rs.spread(idx)
     assert rs.one_per_cell(wide, idx)
@@ -225,17 +185,17 @@ def test_particle_order():
     x = pos.astype(np.float64)
     x[:, 2] += 0.25 * (0.2 / rs.SHEET_RES) * np.random.default_rng(5).uniform(-1, 1, len(x))
     x = x.astype(F)
-    es = [_engine([(pos, idx.reshape(-1))]), _engine([(pos, idx.reshape(-1))]), _engine([(pos, idx.reshape(-1))], deterministic=False)]
-    _upload(es[1], wide)
+    es = [hs.engine([(pos, idx.reshape(-1))]), hs.engine([(pos, idx.reshape(-1))]), hs.engine([(pos, idx.reshape(-1))], deterministic=False)]
+    hs.upload(es[1], wide)
     es[1].rebuild_mapping(True)
     assert not np.array_equal(es[0].download(A.PIDS), es[1].download(A.PIDS)), "the two engines hold the same particle order"
     out = []
     for g in es:
         g.set_shell_bending([sb.K])
         g.set_creases(_table([(0.05, 0.5, 0.0)]))
-        _upload(g, x)
+        hs.upload(g, x)
         g.calc_fem_state_and_force(TINY_DT)
-        out.append((_bits(g.crease_state()[0]), _bits(g.crease_measure()[2]), _bits(g.shell_forces())))
+        out.append((hs.bits(g.crease_state()[0]), hs.bits(g.crease_measure()[2]), hs.bits(g.shell_forces())))
     assert not np.array_equal(es[0].download(A.PIDS), es[1].download(A.PIDS))
     yields, decided = cr.verdict64(x, H, np.zeros(len(H), F), cr.chord(0.05), sb.active(x, H))
     assert yields.any() and not yields.all() and out[0][0].any()
@@ -356,11 +316,11 @@ def test_sums_path_with_and_without_skipped_substeps():
 def test_off_means_off():
     """40 deterministic substeps through re-sorts on engines with shell bending: never called == creases set and cleared
     again with no hinge creased, to the bit and with the same counters of substeps, re-sorts and re-sort checks"""
-    A = _A()
+    A = hs.ARR()
     X, T = bd.sheet(12, 12)
     x0 = cr.fold_state(X, 0.3, seed=1)
     v0 = np.tile(np.array([4.0, 0.3, 0.0], F), (len(X), 1))
-    es = [_engine([(X, T)]) for _ in range(2)]
+    es = [hs.engine([(X, T)]) for _ in range(2)]
     for g in es:
         _scale_k(g, lambda k: g.set_shell_bending([k]), DT)
     es[1].set_creases(_table([(0.05, 0.5, 0.0)]))
@@ -369,7 +329,7 @@ def test_off_means_off():
     assert not es[1].get_creases()["yield_angle"].any() and es[1].crease_state()[1][0] == 0
     before = es[0].stats()["rebuilds"]
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         for _ in range(4):
             g.run_substeps(10, DT, -1)
         g.gpu_sync()
@@ -380,7 +340,7 @@ def test_off_means_off():
     for key in ("substeps", "rebuilds", "resort_checks"):
         assert es[0].stats()[key] == es[1].stats()[key], key
     assert es[0].shell_forces().any()
-    assert np.array_equal(_bits(es[1].crease_state()[0]), _bits(es[1].shell_hinges()[2]))
+    assert np.array_equal(hs.bits(es[1].crease_state()[0]), hs.bits(es[1].shell_hinges()[2]))
     for g in es:
         g.destroy()
 
@@ -389,26 +349,26 @@ def test_yields_zero_with_creases_present_freezes_the_state():
     X, T = bd.sheet(12, 12)
     H = sb.hinges(T)
     x = cr.fold_state(X, 0.8, seed=2)
-    g, twin = _engine([(X, T)]), _engine([(X, T)])
+    g, twin = hs.engine([(X, T)]), hs.engine([(X, T)])
     for e in (g, twin):
         e.set_shell_bending([sb.K])
     g.set_creases(_table([(0.05, 0.0, 0.0)]))
-    _upload(g, x)
+    hs.upload(g, x)
     _fem(g)
     creased, count = g.crease_state()
     assert count[0] > 0
     g.set_creases(None)                                   # all zeros: yielding off, the creases stay
     assert not g.get_creases()["yield_angle"].any()
-    assert np.array_equal(_bits(g.crease_state()[0]), _bits(creased)) and g.crease_state()[1][0] == count[0]
+    assert np.array_equal(hs.bits(g.crease_state()[0]), hs.bits(creased)) and g.crease_state()[1][0] == count[0]
     x2 = cr.fold_state(X, 1.4, seed=3)
-    _upload(g, x2)
+    hs.upload(g, x2)
     _fem(g)
-    assert np.array_equal(_bits(g.crease_state()[0]), _bits(creased))            # frozen
-    assert np.array_equal(_bits(g.crease_measure()[2]), _bits(creased))
+    assert np.array_equal(hs.bits(g.crease_state()[0]), hs.bits(creased))            # frozen
+    assert np.array_equal(hs.bits(g.crease_measure()[2]), hs.bits(creased))
     twin.set_crease_state(creased)
-    _upload(twin, x2)
+    hs.upload(twin, x2)
     f, ft = g.shell_forces(), twin.shell_forces()
-    assert np.array_equal(_bits(f), _bits(ft)) and f.any()
+    assert np.array_equal(hs.bits(f), hs.bits(ft)) and f.any()
     # ... and they are the forces of the creased psibar, not of the rest values
     kc = g.shell_hinges()[1]
     act = sb.active(x2, H)
@@ -424,7 +384,7 @@ def test_yields_zero_with_creases_present_freezes_the_state():
 def test_set_iron_and_reset():
     X, T, rest = sb.mesh("book")
     H = sb.hinges(T)
-    g, never = _engine([(X, T)]), _engine([(X, T)])
+    g, never = hs.engine([(X, T)]), hs.engine([(X, T)])
     for e in (g, never):
         e.set_shell_bending([sb.K], rest)
     psibar0 = g.shell_hinges()[2]
@@ -434,27 +394,27 @@ def test_set_iron_and_reset():
     given[::5] = psibar0[::5]
     g.set_crease_state(given)                             # allowed while every yield is 0: a pre-creased cloth
     got, count = g.crease_state()
-    assert np.array_equal(_bits(got), _bits(given)) and count[0] == int((_bits(given) != _bits(psibar0)).sum()) > 0
-    assert np.array_equal(_bits(g.shell_hinges()[2]), _bits(psibar0))
+    assert np.array_equal(hs.bits(got), hs.bits(given)) and count[0] == int((hs.bits(given) != hs.bits(psibar0)).sum()) > 0
+    assert np.array_equal(hs.bits(g.shell_hinges()[2]), hs.bits(psibar0))
     x = sb.state("book", "perturbed")
     for e in (g, never):
-        _upload(e, x)
-    assert not np.array_equal(_bits(g.shell_forces()), _bits(never.shell_forces()))
+        hs.upload(e, x)
+    assert not np.array_equal(hs.bits(g.shell_forces()), hs.bits(never.shell_forces()))
     g.set_crease_state(None)                              # ironing
     got, count = g.crease_state()
-    assert np.array_equal(_bits(got), _bits(psibar0)) and count[0] == 0
-    assert np.array_equal(_bits(g.shell_forces()), _bits(never.shell_forces()))
-    assert np.array_equal(_bits(g.shell_state()[1]), _bits(never.shell_state()[1]))
+    assert np.array_equal(hs.bits(got), hs.bits(psibar0)) and count[0] == 0
+    assert np.array_equal(hs.bits(g.shell_forces()), hs.bits(never.shell_forces()))
+    assert np.array_equal(hs.bits(g.shell_state()[1]), hs.bits(never.shell_state()[1]))
     # mpm_set_shell_bending again drops the parameters and the creases with the table they belonged to
     g.set_creases(_table([(0.05, 0.25, 0.0)]))
     g.set_crease_state(given)
     g.set_shell_bending([sb.K], rest)
     assert not g.get_creases()["yield_angle"].any() and not g.get_creases()["hardening"].any()
     got, count = g.crease_state()
-    assert np.array_equal(_bits(got), _bits(psibar0)) and count[0] == 0
-    assert np.array_equal(_bits(g.shell_forces()), _bits(never.shell_forces()))
+    assert np.array_equal(hs.bits(got), hs.bits(psibar0)) and count[0] == 0
+    assert np.array_equal(hs.bits(g.shell_forces()), hs.bits(never.shell_forces()))
     _fem(g)
-    assert np.array_equal(_bits(g.crease_state()[0]), _bits(psibar0))
+    assert np.array_equal(hs.bits(g.crease_state()[0]), hs.bits(psibar0))
     # ... and shell bending off leaves nothing to crease
     g.set_shell_bending([0.0])
     assert len(g.crease_state()[0]) == 0 and g.crease_state()[1][0] == 0
@@ -480,7 +440,7 @@ def test_a_folded_sheet_keeps_its_fold_with_creases_and_opens_without():
     H = sb.hinges(T)
     line = np.all(np.abs(X[H[:, :2], 0] - sb.CENTER[0]) < 1e-9, axis=1)
     assert line.sum() == 4
-    es = [_engine([(folded, T)], material=dict(gravity=0.0)) for _ in range(2)]
+    es = [hs.engine([(folded, T)], material=dict(gravity=0.0)) for _ in range(2)]
 
     def flat(g):
         def set_with(k):
@@ -540,7 +500,7 @@ def test_refusals():
     _refused(lambda: g0.set_creases(None), says="finalize")
     _refused(lambda: g0.set_crease_state(None), says="finalize")
     g0.destroy()
-    g = _engine([(X, T), (Xs, Ts)])
+    g = hs.engine([(X, T), (Xs, Ts)])
     # shell bending off
     _refused(lambda: g.set_creases(None), says="shell bending")
     _refused(lambda: g.set_crease_state(None), says="shell bending")
@@ -556,7 +516,7 @@ def test_refusals():
     def unchanged():
         assert np.array_equal(g.get_creases(), good)
         got, count = g.crease_state()
-        assert np.array_equal(_bits(got), _bits(state)) and count.sum() == n
+        assert np.array_equal(hs.bits(got), hs.bits(state)) and count.sum() == n
     unchanged()
     # a wrong count, a null array
     _refused(lambda: g.set_creases(good[:1]), says="cloth count")

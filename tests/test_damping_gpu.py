@@ -27,6 +27,7 @@ import pytest
 
 from tests import bending as bd
 from tests import damping as dp
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
@@ -37,20 +38,6 @@ DT = 2e-4              # of the dynamics tests
 SHARE = 0.25           # of mpm_damping_max_stable_dt that a test's dt is, where it does not say otherwise
 # (the scenes' coefficients and bending stiffnesses are sized for tests/transfer_layouts.py's DT = 1e-3)
 UP = np.array([0.0, 0.0, 0.05], np.float32)
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
 
 
 def _lame32(E, nu):
@@ -85,39 +72,8 @@ def _meshes(scene):
     return out
 
 
-def _engine(meshes, mats=None, bits=6, deterministic=True, material=None, bodies=0):
-    from drake_amd import ClothMaterial, GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for c, (X, T) in enumerate(meshes):
-        m = None
-        if mats is not None:
-            m = ClothMaterial.of(mat)
-            for k, val in mats[c].items():
-                setattr(m, k, val)
-        g.add_qr_cloth(X, np.zeros_like(X), T, m)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(meshes, np.cumsum([0] + [len(X) for X, _ in meshes[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None, F=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.broadcast_to(np.asarray(v, np.float32), x.shape)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, F)
-
-
 def _vertex_state(g):
-    A = _A()
+    A = hs.ARR()
     nf = g.n_faces
     pids, v = g.download(A.PIDS), g.download(A.VELOCITIES)
     vv = np.zeros((g.n_verts, 3), np.float32)
@@ -128,7 +84,7 @@ def _vertex_state(g):
 def _rest(g):
     """(dm (nf, 3), vol (nf,)) float32 in original face order, of a SINGLE-material engine (whose MPM_ARR_VOLUMES is the
     record the face kernels read)"""
-    A = _A()
+    A = hs.ARR()
     nf = g.n_faces
     pids, vol = g.download(A.PIDS), g.download(A.VOLUMES)
     vf = np.zeros(nf, np.float32)
@@ -163,10 +119,10 @@ def _scene(scene):
         m = dict(youngs_modulus=base.youngs_modulus, poisson_ratio=base.poisson_ratio)
         m.update({k: v for k, v in (mats[c] if mats else {}).items() if k in m})
         lame.append(_lame32(m["youngs_modulus"], m["poisson_ratio"]))
-    single = _engine(meshes)                     # (rest records: Finalize's geometry does not depend on the material)
+    single = hs.engine(meshes)                     # (rest records: Finalize's geometry does not depend on the material)
     rest = _rest(single)
     single.destroy()
-    g = _engine(meshes, mats)
+    g = hs.engine(meshes, mats=mats)
     ks = [0.0] * len(meshes)
     if any(bend_on):
         g.set_bending([float(b) for b in bend_on])
@@ -192,7 +148,7 @@ def _scene(scene):
 
 def _prepared(scene, **kw):
     s = _scene(scene)
-    g = _engine(s["meshes"], s["mats"], **kw)
+    g = hs.engine(s["meshes"], mats=s["mats"], **kw)
     if any(s["ks"]):
         g.set_bending(s["ks"])
     g.set_damping(s["betas"])
@@ -226,7 +182,7 @@ def _check_forces(g, s, what):
     err = np.abs(f.astype(np.float64) - ref)
     w = float(np.where(err == 0, 0.0, err / np.maximum(tol, 1e-300)).max())
     print(f"damping forces: {what}: {w:.3g} of the tolerance")
-    _record(f"damping forces: {what}", w)
+    hs.record(f"damping forces: {what}", w)
     assert w <= 1.0, (what, w)
     return x, v, f, ref
 
@@ -246,7 +202,7 @@ def test_forces_against_float64(scene):
     for st in bd.STATES:
         for vn in dp.VELOCITIES:
             x0, v0 = _states(s, st, vn)
-            _upload(g, x0, v0)
+            hs.upload(g, x0, v0)
             x, v, f, ref = _check_forces(g, s, f"{scene} {st} {vn}")
             assert np.array_equal(x, x0) and np.array_equal(v, v0)
             assert not f[undamped].any()
@@ -254,21 +210,21 @@ def test_forces_against_float64(scene):
                 assert np.all(np.abs(f[~undamped]).max(axis=1) > 0), "a vertex was left out"
     # substeps that force a re-sort: the state five cells further along x, two short substeps
     x0, v0 = _states(s, "cylinder30", "random")
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     f0 = g.damping_forces()
     before = g.stats()["rebuilds"]
-    _upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], np.float32), v0)
+    hs.upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], np.float32), v0)
     g.run_substeps(2, 1e-5, -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
     _check_forces(g, s, f"{scene} after a re-sort")
     # the first state again, in the new particle order: the same bits
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     f1 = g.damping_forces()
-    assert np.array_equal(_bits(f1), _bits(f0)), float(np.abs(f1 - f0).max())
+    assert np.array_equal(hs.bits(f1), hs.bits(f0)), float(np.abs(f1 - f0).max())
     g.rebuild_mapping(True)
     _check_forces(g, s, f"{scene} after sort = 1")
-    assert np.array_equal(_bits(g.damping_forces()), _bits(f0))
+    assert np.array_equal(hs.bits(g.damping_forces()), hs.bits(f0))
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -283,7 +239,7 @@ def test_more_than_256_cloths():
     for c in range(n):
         off = np.array([(c % 20 - 9.5) * 2.5 * bd.H0, (c // 20 - 7.0) * 2.5 * bd.H0, 0.0])
         meshes.append(((X0.astype(np.float64) + off).astype(np.float32), T0))
-    g = _engine(meshes)
+    g = hs.engine(meshes)
     assert g.cloth_count() == n
     on = np.zeros((n, 2))
     on[::3, 0] = 1.0 + (np.arange(0, n, 3) % 7) / 7.0
@@ -295,12 +251,12 @@ def test_more_than_256_cloths():
     T = np.concatenate([T0 + 4 * c for c in range(n)])
     x = bd.state("perturbed", X)
     v = dp.velocity("random", x).astype(np.float32)
-    _upload(g, x, v)
+    hs.upload(g, x, v)
     f = g.damping_forces()
     beta_f = np.repeat(betas[:, 0], 2)
     ref, B = dp.forces64(X, T, x, v, lame, beta_f, rest=rest)
     w = dp.margin(f - ref, B, R)
-    _record("damping forces: 300 cloths", w)
+    hs.record("damping forces: 300 cloths", w)
     assert w <= 1.0, w
     damped = np.repeat(betas[:, 0] > 0, 4)
     assert not f[~damped].any() and np.all(np.abs(f[damped]).max(axis=1) > 0)
@@ -312,7 +268,7 @@ def test_more_than_256_cloths():
 
 def _guard64(g, T, rest, lame, betas, cof, hinges=None, ks=None, first=None):
     """tests/damping.py's guard64 on the vertex particles' MPM_ARR_MASSES"""
-    A = _A()
+    A = hs.ARR()
     nf = g.n_faces
     pids, m = g.download(A.PIDS), g.download(A.MASSES).astype(np.float64)
     mv = np.zeros(g.n_verts)
@@ -353,14 +309,14 @@ def test_device_records_are_the_host_function_bits():
     X = np.concatenate([(X0.astype(np.float64) + np.array([(c % 8 - 3.5) * 2 * bd.H0, (c // 8 - 3.5) * 2 * bd.H0, 0.0])) for c in range(n)])
     X = (X + 0.1 * bd.H0 * r.normal(size=X.shape) * np.array([1, 1, 0])).astype(np.float32)
     T = np.arange(3 * n, dtype=np.int32).reshape(n, 3)
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     betas = _betas_for(g, [(1.0, 0.0)], dt=tl.DT)
     rest = _rest(g)
     mu, lam = _lame32(g.default_material().youngs_modulus, g.default_material().poisson_ratio)
     for st in bd.STATES:
         x = bd.state(st, X)
         v = dp.velocity("random", x).astype(np.float32)
-        _upload(g, x, v)
+        hs.upload(g, x, v)
         f = g.damping_forces()
         rec = damping_face_records(rest[0], rest[1], mu, lam, betas[0][0], dp.corners(T, x), dp.corners(T, v))
         assert np.abs(rec).max() > 0
@@ -374,17 +330,17 @@ def test_total_forces_include_damping(scene):
     """(the fan's hub has 12 faces: its records go through DP::G3 and the adjacency walk, the others through DP::VF;
     pair_multi runs k_fem_mat; membrane damping only, so that the vertex force is one sum of records)"""
     from tests import fem_regimes as fr
-    A = _A()
+    A = hs.ARR()
     s = _scene(scene)
     betas = s["betas"].copy()
     betas[:, 1] = 0.0
-    a, b = _engine(s["meshes"], s["mats"]), _engine(s["meshes"], s["mats"])
+    a, b = hs.engine(s["meshes"], mats=s["mats"]), hs.engine(s["meshes"], mats=s["mats"])
     a.set_damping(betas)
     x0, v0 = _states(s, "affine", "random")
     nf, T = len(s["T"]), s["T"]
     out = []
     for g in (a, b):
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         F_up = g.download(A.DEFORMATION_GRADIENTS)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(tl.DT)
@@ -416,7 +372,7 @@ def test_total_forces_include_damping(scene):
     err = np.abs(out[0].astype(np.float64) - out[1].astype(np.float64) - fd.astype(np.float64))
     w = float(np.where(err == 0, 0.0, err / np.maximum(tol, 1e-300)).max())
     print(f"total forces: {scene}: {w:.3g} of the tolerance; |damping| / |elastic| = {np.abs(fd).max() / np.abs(out[1]).max():.3g}")
-    _record(f"damping: total forces {scene}", w)
+    hs.record(f"damping: total forces {scene}", w)
     assert w <= 1.0, w
     assert np.abs(fd).max() > 1e3 * tol.max(), "the damping force is far above the tolerance"
     assert not b.damping_forces().any() and b.damping_max_stable_dt() == np.inf
@@ -430,13 +386,13 @@ def test_total_forces_include_damping(scene):
 def test_p2g_node_by_node(mode):
     from tests import helpers
     helpers.tag_default_engine(mode == "default")
-    A = _A()
+    A = hs.ARR()
     s = _scene("regular")
     nf = len(s["T"])
-    g = _engine(s["meshes"], deterministic=mode == "deterministic")
+    g = hs.engine(s["meshes"], deterministic=mode == "deterministic")
     _betas_for(g, [(1.0, 0.0)], dt=tl.DT)
     x0, v0 = _states(s, "affine", "shear")
-    _upload(g, x0, 0.1 * v0)
+    hs.upload(g, x0, 0.1 * v0)
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(tl.DT)
     d = {k: g.download(a) for k, a in (("pids", A.PIDS), ("x", A.POSITIONS), ("v", A.VELOCITIES), ("C", A.AFFINE),
@@ -454,7 +410,7 @@ def test_p2g_node_by_node(mode):
     for field, err, bnd in (("mass", np.abs(gm - r["m"]), bm), ("momentum", np.abs(gmv - r["mv"]), bmv)):
         w = tl.margin(err, bnd)
         print(f"damping p2g [{mode}] {field}: {w:.4g} of the bound")
-        _record(f"damping: p2g [{mode}] {field}", w)
+        hs.record(f"damping: p2g [{mode}] {field}", w)
         assert w <= 1.0, (field, w)
     assert np.array_equal(flags, r["flags"])
     # damping is in the sums: without it the momentum is outside the bound
@@ -465,17 +421,6 @@ def test_p2g_node_by_node(mode):
 
 
 # ---- 4 -------------------------------------------------------------------------------------------------------------
-def _state(g):
-    A = _A()
-    return dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS),
-                F=g.download(A.DEFORMATION_GRADIENTS))
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), (what, k, float(np.abs(a[k].astype(np.float64) - b[k]).max()))
-
-
 @pytest.mark.parametrize("scene", ["regular", "big"])
 def test_scheduling_through_resorts(scene):
     """a strained sheet that flies through several re-sorts, deterministic: run_substeps(n), n x substep and n x the five
@@ -489,7 +434,7 @@ def test_scheduling_through_resorts(scene):
     x0, v0 = _states(s, "cylinder30", "dilation")
     v0 = (0.05 * v0 + np.array([3.0, 0.4, 0.0], np.float32)).astype(np.float32)
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
     before = es[0].stats()["rebuilds"]
     # (in batches of 10, so that the substeps that skipped themselves can be counted before the next call runs them again)
     # One single substep first: it carries its re-sort launches and moves the engine's count of substeps by one, so that
@@ -516,9 +461,9 @@ def test_scheduling_through_resorts(scene):
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0, g.stats()
     assert es[0].stats()["rebuilds"] - before >= 3, es[0].stats()
-    st = [_state(g) for g in es]
-    _same_bits(st[0], st[1], "run_substeps(n) against n substeps")
-    _same_bits(st[0], st[2], "run_substeps(n) against the phase calls")
+    st = [hs.state(g) for g in es]
+    hs.same_bits(st[0], st[1], "run_substeps(n) against n substeps")
+    hs.same_bits(st[0], st[2], "run_substeps(n) against the phase calls")
     assert es[0].damping_forces().any()
     for g in es:
         g.destroy()
@@ -528,13 +473,13 @@ def test_coupled_path_runs():
     from drake_amd import Collider
     g, s = _prepared("regular", bodies=1)
     x0, v0 = _states(s, "cylinder30", "dilation")
-    _upload(g, x0, 0.05 * v0)
+    hs.upload(g, x0, 0.05 * v0)
     floor = [Collider(0, body=0, p_WB=(0.5, 0.5, float(x0[:, 2].min()) - 0.002))]
     res = g.run_coupled_substeps(40, tl.DT, floor, 0.5, 1e5, 1e-4)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0
     assert max(r["contacts"] for r in res) > 0, "the sheet never reached the floor"
-    assert np.isfinite(g.download(_A().VELOCITIES)).all()
+    assert np.isfinite(g.download(hs.ARR().VELOCITIES)).all()
     g.destroy()
 
 
@@ -545,7 +490,7 @@ def test_off_means_off():
     quiet-time hint is in use again)"""
     from drake_amd import scenes
     pos, idx = scenes.cloth_sheet(32, 0.3, 0.6, (0.3, 0.5))
-    es = [_engine([(pos, idx.reshape(-1, 3))]) for _ in range(3)]
+    es = [hs.engine([(pos, idx.reshape(-1, 3))]) for _ in range(3)]
     es[1].set_damping([(0.0, 0.0)])
     es[2].set_damping([(1e-5, 1e-5)])
     assert es[2].damping_max_stable_dt() < np.inf
@@ -555,7 +500,7 @@ def test_off_means_off():
     vel = np.array([4.0, 0.3, 0.0], np.float32) + 0.05 * np.random.default_rng(3).normal(size=pos.shape).astype(np.float32)
     before = es[0].stats()["rebuilds"]
     for g in es:
-        pids = g.download(_A().PIDS)
+        pids = g.download(hs.ARR().PIDS)
         allv = np.concatenate([vel[g._tri].mean(axis=1), vel]).astype(np.float32)
         g.upload_particle_state(None, allv[pids], None, None, None)
         for _ in range(2):
@@ -563,9 +508,9 @@ def test_off_means_off():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 1, es[0].stats()
-    st = [_state(g) for g in es]
-    _same_bits(st[0], st[1], "all zeros")
-    _same_bits(st[0], st[2], "set and cleared")
+    st = [hs.state(g) for g in es]
+    hs.same_bits(st[0], st[1], "all zeros")
+    hs.same_bits(st[0], st[2], "set and cleared")
     for k in ("substeps", "rebuilds", "resort_checks"):
         assert es[0].stats()[k] == es[1].stats()[k] == es[2].stats()[k], k
     for g in es:
@@ -599,19 +544,19 @@ def test_rigid_motion_is_not_damped():
     rotation's kinetic energy (2e-4 of the total) in the one substep: 1e4 tolerances."""
     s = _scene("regular")
     mat = dict(gravity=0.0)
-    a, b = _engine(s["meshes"], material=mat), _engine(s["meshes"], material=mat)
+    a, b = hs.engine(s["meshes"], material=mat), hs.engine(s["meshes"], material=mat)
     _betas_for(a, [(1.0, 0.0)], share=0.05)
     X = s["X"].astype(np.float64)
     w, v0 = np.array([0.0, 0.0, 0.125]), np.array([0.5, 0.25, 0.0])
     v = (v0 + np.cross(w, X - bd.CENTER)).astype(np.float32)
     for g in (a, b):
-        _upload(g, s["X"], v)
+        hs.upload(g, s["X"], v)
         g.run_substeps(1, DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     ta, tb = a.measure()[1], b.measure()[1]
     # the sums of the absolute terms, as tests/measure.py forms them (a face at the mean of its corners)
-    A = _A()
+    A = hs.ARR()
     pids, m = b.download(A.PIDS), b.download(A.MASSES).astype(np.float64)
     mo = np.zeros(len(m))
     mo[pids] = m
@@ -622,8 +567,8 @@ def test_rigid_motion_is_not_damped():
     wk = abs(float(ta["kinetic"]) - float(tb["kinetic"])) / (1e-9 * float(tb["kinetic"]))
     wl = float((np.abs(np.asarray(ta["angular_momentum"]) - np.asarray(tb["angular_momentum"])) / (1e-9 * abs_L)).max())
     print(f"rigid motion: kinetic {wk:.3g}, angular momentum {wl:.3g} of 1e-9 of the absolute terms")
-    _record("damping: rigid motion, kinetic energy", wk)
-    _record("damping: rigid motion, angular momentum", wl)
+    hs.record("damping: rigid motion, kinetic energy", wk)
+    hs.record("damping: rigid motion, angular momentum", wl)
     assert float(tb["kinetic"]) > 0 and abs(float(tb["angular_momentum"][2])) > 0
     assert wk <= 1.0 and wl <= 1.0, (wk, wl)
     # Ten substeps: the damper now sees rounded rigid fields in a running engine.  The two float32 trajectories may
@@ -638,8 +583,8 @@ def test_rigid_motion_is_not_damped():
     wk = abs(float(ta["kinetic"]) - float(tb["kinetic"])) / (8 * U * float(tb["kinetic"]))
     wl = float((np.abs(np.asarray(ta["angular_momentum"]) - np.asarray(tb["angular_momentum"])) / (8 * U * abs_L)).max())
     print(f"rigid motion, 10 substeps: kinetic {wk:.3g}, angular momentum {wl:.3g} of 8 x 2^-24 of the absolute terms")
-    _record("damping: rigid motion after 10 substeps, kinetic energy", wk)
-    _record("damping: rigid motion after 10 substeps, angular momentum", wl)
+    hs.record("damping: rigid motion after 10 substeps, kinetic energy", wk)
+    hs.record("damping: rigid motion after 10 substeps, angular momentum", wl)
     assert wk <= 1.0 and wl <= 1.0, (wk, wl)
     for g in (a, b):
         g.destroy()
@@ -686,12 +631,12 @@ def test_released_sheet_loses_energy(case):
       at the start (the strain only relaxes from there; 64 roundings is more than either face kernel's chain) plus the
       bending rows' own bounds."""
     from tests import fem_regimes as fr
-    A = _A()
+    A = hs.ARR()
     h = bd.H0 if case == "stretched" else 1.0 / 64
     X, T = bd.sheet(13, 13, h=h)
     steps, every = 24, 4
     mat = dict(gravity=0.0)
-    a, b = _engine([(X, T)], material=mat), _engine([(X, T)], material=mat)
+    a, b = hs.engine([(X, T)], material=mat), hs.engine([(X, T)], material=mat)
     rest = _rest(a)
     lame = _lame32(a.default_material().youngs_modulus, a.default_material().poisson_ratio)
     F = None
@@ -710,7 +655,7 @@ def test_released_sheet_loses_energy(case):
         betas = _betas_for(a, [(0.0, 1.0)])
     assert DT <= a.damping_max_stable_dt() and DT <= a.bending_max_stable_dt()
     for g in (a, b):
-        _upload(g, x0, None, F)
+        hs.upload(g, x0, None, F)
     # F_i at the start
     F_up = a.download(A.DEFORMATION_GRADIENTS).astype(np.float64)
     base = a.default_material()
@@ -762,7 +707,7 @@ def test_released_sheet_loses_energy(case):
         bound = steps * (128 * U * gross[e] + DT * U * (float(Fi.sum(axis=0).max()) + bend_rows + extra[e]))
         mom = float(np.abs(added[e]).max())
         print(f"{case}: momentum added by the substeps, {name}: {mom:.3e}, bound {bound:.3e}, gross {gross[e]:.3e}")
-        _record(f"damping: momentum of the {case} sheet, {name}", mom / bound)
+        hs.record(f"damping: momentum of the {case} sheet, {name}", mom / bound)
         assert gross[e] > 0 and mom <= bound, (name, mom, bound)
     for g in (a, b):
         g.destroy()
@@ -788,19 +733,19 @@ def test_refusals():
     refused(lambda: g0.set_damping([(1e-4, 0.0)]), says="finalize")
     g0.destroy()
 
-    g = _engine([(X, T)], bodies=1)
+    g = hs.engine([(X, T)], bodies=1)
     g.set_damping([(0.0, 1e-3)])        # bending damping on a cloth without bending stiffness: accepted, does nothing
     assert not g.damping_forces().any() and np.array_equal(g.get_damping(), np.array([(0.0, 1e-3)], np.float32))
     good = _betas_for(g, [(1.0, 0.0)], dt=tl.DT, share=0.9)
     lim = g.damping_max_stable_dt()
     s = _scene("regular")
     x0, v0 = _states(s, "cylinder30", "shear")
-    _upload(g, x0, 0.1 * v0)
+    hs.upload(g, x0, 0.1 * v0)
     f_before = g.damping_forces()
     for bad in ([(-1e-5, 0.0)], [(0.0, -1e-5)], [(np.nan, 0.0)], [(0.0, np.inf)], [(1e-5, 0.0), (1e-5, 0.0)]):
         refused(lambda bad=bad: g.set_damping(bad))
     assert np.array_equal(g.get_damping(), good) and g.damping_max_stable_dt() == lim
-    assert np.array_equal(_bits(g.damping_forces()), _bits(f_before))
+    assert np.array_equal(hs.bits(g.damping_forces()), hs.bits(f_before))
     # partitioned, halo, team and chain calls on an engine with damping
     nb = 64 // 4
     refused(lambda: g.dist_init(0, 1, [0, nb], 2, 2, 2), says="damping")

@@ -16,6 +16,8 @@ tools/skylark/cuda.bzl:66-80).  Both run here, in one process, on the same state
 import numpy as np
 import pytest
 
+from tests import harness
+
 pytestmark = pytest.mark.gpu
 
 
@@ -89,16 +91,12 @@ def test_the_switch_may_change_between_substeps():
     """mpm_set_fast_math between two batches of substeps (it settles first: substeps that mpm_run_substeps deferred run
     with the arithmetic they were enqueued with): the run is reproducible -- in deterministic mode to the bit -- and differs
     from a run that never switched."""
-    import os
     from drake_amd import ARR as A, GpuMpm, scenes
     sheets = scenes.cloth_stack(3, 24, 6, z0=0.5, side=0.3, seed=11, vel_amp=0.3)
 
     def run(plan):
-        os.environ["MPM_DETERMINISTIC"] = "1"     # (read at mpm_create: Finalize's own first sort is canonical too)
-        try:
+        with harness.environ({"MPM_DETERMINISTIC": "1"}):     # (read at mpm_create: Finalize's own first sort is canonical too)
             g = GpuMpm(6)
-        finally:
-            del os.environ["MPM_DETERMINISTIC"]
         scenes.populate(g, [(p.copy(), v.copy(), i.copy()) for p, v, i in sheets])
         for mode, n in plan:
             g.set_fast_math(mode)

@@ -24,24 +24,20 @@ through re-sorts, owed substeps and substeps that skip themselves:
  8. particle order: accessors and measure() are the same bits after re-sorts.
 
 No tolerance here is a new number: bit equality, the per-feature modules' own bounds, and U = 2^-24 per stage."""
+import functools
+
 import numpy as np
 import pytest
 
 from tests import feature_paths as fp
+from tests import harness as hs
 
 pytestmark = pytest.mark.gpu
 
 _CACHE = {}
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, "feature paths: " + what + helpers.TAG, 1.0, ratio, ratio))
+_record = functools.partial(hs.record, prefix="feature paths: ")
 
 
 def _result(name, features=fp.EVERYTHING, grid_bodies=False):
@@ -121,7 +117,7 @@ def test_every_feature_acts_in_that_run():
 # ---- 3 -------------------------------------------------------------------------------------------------------------------
 def test_sums_family_refusals_and_the_forces_of_substep_begin():
     from drake_amd import GpuMpm, MpmError
-    A = _A()
+    A = hs.ARR()
     x0, v0 = fp.perturbed_state()
     g, twin = fp.engine(), fp.engine()
     zones, bufs = GpuMpm.halo_zone_args([], []), GpuMpm.halo_buffer_args([])
@@ -252,13 +248,13 @@ def _forces_of(features, x0, v0, F0, clock=False):
     fp.upload(g, x0, v0, F0)
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(fp.DT)
-    return g, fp.vertices(g, _A().FORCES)
+    return g, fp.vertices(g, hs.ARR().FORCES)
 
 
 def _composition():
     if "composition" in _CACHE:
         return _CACHE["composition"]
-    A = _A()
+    A = hs.ARR()
     x0, v0 = fp.perturbed_state()
     probe = fp.engine(fp.NOTHING)
     F0 = probe.download(A.DEFORMATION_GRADIENTS)       # (Finalize's F: the clock substeps of an engine with anchors move it)
@@ -355,7 +351,7 @@ def test_every_accessor_passes_its_own_float64_check_with_everything_on():
     from tests import links as lk
     from tests import pressure as pr
     from tests import shell_bending as sb
-    A = _A()
+    A = hs.ARR()
     c, s, p = _composition(), fp.scene(), fp.params()
     x0, v0, acc = c["x0"], c["v0"], c["acc"]
     first, nv = s["first"], len(x0)
@@ -436,7 +432,7 @@ def test_every_accessor_passes_its_own_float64_check_with_everything_on():
 def test_particle_order():
     """the state with everything on, uploaded in two particle orders -- as finalised, and after substeps five cells further
     along x, their re-sorts and RebuildMapping(sort = 1): the accessors, the feature states and measure() are the same bits"""
-    A = _A()
+    A = hs.ARR()
     s = fp.scene()
     c = _composition()
     x0, v0, F0 = c["x0"], c["v0"], c["F0"]

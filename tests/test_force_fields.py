@@ -8,15 +8,11 @@ import numpy as np
 import pytest
 
 from tests import force_fields as ff
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LAYOUTS = ("dense", "kinds", "materials", "magnitudes")
-
-
-def _record(what, ratio):
-    from tests.helpers import MARGINS
-    MARGINS.append((ratio, what, 1.0, ratio, ratio))
 
 
 def _c(fields):
@@ -63,7 +59,7 @@ def test_host_evaluation_against_float64(name, kind):
     a64, T = ff.accel64(fields, x, v, d if faces else None, faces)
     assert np.isfinite(got).all()
     w = tl.margin(np.abs(got.astype(np.float64) - a64), ff.accel_bound(T))
-    _record(f"force fields: host evaluation {name} [{kind}]", w)
+    hs.record(f"force fields: host evaluation {name} [{kind}]", w)
     assert w <= 1.0, w
     # where no field acts the result is exactly zero, and the table does act on a good part of the particles
     assert (got[(T == 0).all(axis=1)] == 0).all()
@@ -108,7 +104,7 @@ def test_float32_restatement_within_the_extended_node_bound(name, table):
         imp = tl.f32(lay["mass"])[:, None] * (tl.f32(a) * np.float32(tl.DT32))
         r2, _, _ = ff.p2g64_fields(fields, *args, accel=imp.astype(np.float64) / (lay["mass"].astype(np.float64)[:, None] * tl.DT32))
         w = tl.margin(np.abs(r2["mv"] - r["mv"]), bmv)
-        _record(f"force fields: {what} within the node bound: {name} {table}", w)
+        hs.record(f"force fields: {what} within the node bound: {name} {table}", w)
         assert w <= 1.0, (what, w)
     # the table reaches the layout: some particle inside and (regions) some outside every regioned field
     assert (T > 0).any()

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests import force_fields as ff
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
@@ -26,20 +27,10 @@ U = 2.0 ** -24
 _RUNS = {}
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
 def _c(fields):
     from drake_amd import ForceField
     return [ForceField(kind=f["kind"], gamma=float(f["gamma"]), u0=f["u0"], G=f["G"], x0=f["x0"],
                        region=(f["lo"], f["hi"]) if f["flags"] & ff.FF_REGION else None, flags=f["flags"]) for f in fields]
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
 
 
 def _layout_engine(name, table, mode):
@@ -56,7 +47,7 @@ def _run(name, table, mode):
     key = (name, table, mode)
     if key in _RUNS:
         return _RUNS[key]
-    A = _A()
+    A = hs.ARR()
     lay, fields, g = _layout_engine(name, table, mode)
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(DT)
@@ -101,7 +92,7 @@ def test_p2g_with_fields_node_by_node(name, table, mode):
 
     def check(field, err, bound):
         w = tl.margin(err, bound)
-        _record(f"force fields: {name} {table} [{mode}] {field}", w)
+        hs.record(f"force fields: {name} {table} [{mode}] {field}", w)
         print(f"force fields: {name} {table} [{mode}] {field}: {w:.4g} of the bound")
         if not w <= 1.0:
             fails.append(f"{field}: {w:.3g} x the bound")
@@ -123,7 +114,7 @@ def test_p2g_with_fields_node_by_node(name, table, mode):
 @pytest.mark.parametrize("name", LAYOUTS)
 def test_fused_instance_equals_phase_calls(name):
     """deterministic mode: mpm_substep (k_p2g<1, 1, 1>) is bit-equal to the phase calls (k_vforce, k_p2g<0, 1, 1>)"""
-    A = _A()
+    A = hs.ARR()
     d = _run(name, "eight", "deterministic")
     _, _, g = _layout_engine(name, "eight", "deterministic")
     g.substep(DT, -1)
@@ -136,39 +127,11 @@ def test_fused_instance_equals_phase_calls(name):
 
 
 # ---- scenes of whole sheets ----------------------------------------------------------------------------------------
-def _sheet_engine(sheets, material=None, bodies=0, deterministic=True, bits=6):
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for s in sheets:
-        g.add_qr_cloth(*s)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    return g
-
-
 def _flat_sheet(res=24, side=0.3, z=0.6, center=(0.5, 0.5), vel=(0.0, 0.0, 0.0)):
     from drake_amd import scenes
     pos, idx = scenes.cloth_sheet(res, side, z, center)
     v = np.broadcast_to(np.asarray(vel, np.float32), pos.shape).copy()
     return [(pos, v, idx)]
-
-
-def _state(g, F=True):
-    A = _A()
-    s = dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS))
-    if F:
-        s["F"] = g.download(A.DEFORMATION_GRADIENTS)
-    return s
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), (what, k, float(np.abs(a[k].astype(np.float64) - b[k]).max()))
 
 
 def test_no_table_no_change():
@@ -178,7 +141,7 @@ def test_no_table_no_change():
     from tests import helpers
     sheets = _flat_sheet(res=32, side=0.3, z=0.6, center=(0.3, 0.5), vel=(4.0, 0.3, 0.0))
     sheets[0][1][:] += 0.05 * np.random.default_rng(3).normal(size=sheets[0][1].shape).astype(np.float32)
-    never, cleared, zero = (_sheet_engine(sheets) for _ in range(3))
+    never, cleared, zero = (hs.engine(sheets) for _ in range(3))
     cleared.set_force_fields(_c(ff.table("eight")))
     assert len(cleared.get_force_fields()) == 8
     cleared.set_force_fields([])
@@ -191,8 +154,8 @@ def test_no_table_no_change():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert never.stats()["rebuilds"] - before >= 2, never.stats()
-    a, b, c = _state(never), _state(cleared), _state(zero)
-    _same_bits(a, b, "set and cleared")
+    a, b, c = hs.state(never), hs.state(cleared), hs.state(zero)
+    hs.same_bits(a, b, "set and cleared")
     assert np.array_equal(a["pids"], c["pids"])
     vmax = float(np.abs(a["v"]).max())
     helpers.close(c["v"], a["v"], scale=vmax, what="force fields: zero table v")
@@ -202,7 +165,7 @@ def test_no_table_no_change():
 
 
 def _vertex_velocities(g, nf):
-    A = _A()
+    A = hs.ARR()
     return g.download(A.VELOCITIES)[g.download(A.PIDS) >= nf].astype(np.float64)
 
 
@@ -218,7 +181,7 @@ def test_terminal_speed():
     out = {}
     for gam in (0.0, gamma):
         sheets = _flat_sheet(res=24, side=0.25, z=0.75, center=(0.4, 0.45), vel=v0)
-        g = _sheet_engine(sheets)
+        g = hs.engine(sheets)
         nf = len(sheets[0][2]) // 3
         g.set_force_fields([ForceField(FF_DRAG, gamma=gam, u0=w)])
         for _ in range(n // 20):
@@ -236,7 +199,7 @@ def test_terminal_speed():
     err = float(np.abs(out[gamma] - ref[None]).max())
     tol = max(helpers.RTOL * vmax, 4.0 * yard)
     print(f"terminal speed: err {err:.3e}, yardstick (gamma = 0) {yard:.3e}, RTOL max|v| {helpers.RTOL * vmax:.3e}")
-    _record("force fields: terminal speed", err / tol)
+    hs.record("force fields: terminal speed", err / tol)
     # the drag matters: without it the sheet would be far from the recurrence
     assert float(np.abs(out[0.0] - ref[None]).max()) > 100 * tol
     assert err <= tol, (err, tol, yard)
@@ -246,20 +209,20 @@ def test_hover():
     """ACCEL u0 = -g e cancels gravity: a sheet at rest keeps |v| below 50 x 4u x |g| dt over 50 substeps"""
     from drake_amd import ForceField
     sheets = _flat_sheet(res=24, side=0.3, z=0.6)
-    g = _sheet_engine(sheets)
+    g = hs.engine(sheets)
     g.set_force_fields([ForceField(u0=(0.0, 0.0, -G32))])
     g.run_substeps(50, DT, -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0
-    v = float(np.abs(g.download(_A().VELOCITIES)).max())
+    v = float(np.abs(g.download(hs.ARR().VELOCITIES)).max())
     bound = 50 * 4 * U * abs(G32) * float(np.float32(DT))
     print(f"hover: max|v| {v:.3e}, bound {bound:.3e}")
-    _record("force fields: hover", v / bound)
+    hs.record("force fields: hover", v / bound)
     assert v <= bound, (v, bound)
     # (without the field the sheet falls: 50 substeps of gravity)
-    h = _sheet_engine(sheets)
+    h = hs.engine(sheets)
     h.run_substeps(50, DT, -1)
-    assert float(np.abs(h.download(_A().VELOCITIES)).max()) > 0.4
+    assert float(np.abs(h.download(hs.ARR().VELOCITIES)).max()) > 0.4
     for s in (g, h):
         s.destroy()
 
@@ -270,7 +233,7 @@ def test_scheduling_through_resorts():
     from drake_amd import ForceField
     sheets = _flat_sheet(res=24, side=0.2, z=0.6, center=(0.3, 0.5), vel=(2.5, 0.0, 0.0))
     field = ForceField(u0=(-5.0 * G32, 0.0, 0.0), region=((0.45, 0.0, 0.0), (0.5, 1.0, 1.0)))
-    a, b = _sheet_engine(sheets), _sheet_engine(sheets)
+    a, b = hs.engine(sheets), hs.engine(sheets)
     for g in (a, b):
         g.set_force_fields([field])
     before = a.stats()["rebuilds"]
@@ -281,8 +244,8 @@ def test_scheduling_through_resorts():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0, g.stats()
     assert a.stats()["rebuilds"] - before >= 3, a.stats()
-    sa, sb = _state(a), _state(b)
-    _same_bits(sa, sb, "run_substeps(120) against 120 substeps")
+    sa, sb = hs.state(a), hs.state(b)
+    hs.same_bits(sa, sb, "run_substeps(120) against 120 substeps")
     # the cloth went through the region: it ends faster than it started
     assert float(sa["v"][:, 0].min()) > 2.6, float(sa["v"][:, 0].min())
     for g in (a, b):
@@ -300,8 +263,8 @@ def test_coupled_path():
     from tests import helpers
     sheets = _flat_sheet(res=24, side=0.3, z=0.492)
     floor = [Collider(0, body=0, p_WB=(0.5, 0.5, 0.49))]
-    a = _sheet_engine(sheets, dict(gravity=G32), bodies=1)
-    b = _sheet_engine(sheets, dict(gravity=2.0 * G32), bodies=1)
+    a = hs.engine(sheets, material=dict(gravity=G32), bodies=1)
+    b = hs.engine(sheets, material=dict(gravity=2.0 * G32), bodies=1)
     a.set_force_fields([ForceField(u0=(0.0, 0.0, G32))])
     n = 40
     ra = a.run_coupled_substeps(n, DT, floor, 0.5, 1e5, 1e-4)
@@ -315,11 +278,11 @@ def test_coupled_path():
     (_, fa), (_, fb) = a.external_body_force_to_host(), b.external_body_force_to_host()
     assert float(np.abs(fb).max()) > 0
     helpers.close(fa, fb, scale=float(np.abs(fb).max()), rtol=helpers.IMPULSE_RTOL, what="force fields: coupled body impulse")
-    A = _A()
+    A = hs.ARR()
     assert np.array_equal(a.download(A.PIDS), b.download(A.PIDS))
     helpers.close(a.download(A.POSITIONS), b.download(A.POSITIONS), scale=1.0, what="force fields: coupled positions")
     # (and the field is what makes them agree: engine A without it falls half as fast)
-    c = _sheet_engine(sheets, dict(gravity=G32), bodies=1)
+    c = hs.engine(sheets, material=dict(gravity=G32), bodies=1)
     rc = c.run_coupled_substeps(n, DT, floor, 0.5, 1e5, 1e-4)
     assert [r["contacts"] for r in rc] != [r["contacts"] for r in rb]
     for g in (a, b, c):
@@ -333,7 +296,7 @@ def test_combinations_run():
     fields = _c(ff.table("eight"))
     # pins
     sheets = _flat_sheet(res=20, side=0.3, z=0.6)
-    g = _sheet_engine(sheets, bodies=1)
+    g = hs.engine(sheets, bodies=1)
     x, _ = g.dump_cpu_state()
     g.set_body_motions([BodyMotion(0, (0, 0, 0), np.eye(3).ravel(), (0, 0, 0), (0, 0, 0))])
     g.set_pins([Pin(v, 0, x[v]) for v in (0, 19)])
@@ -345,13 +308,13 @@ def test_combinations_run():
     assert np.abs(pinned - x[[0, 19]]).max() < 1e-5
     g.destroy()
     # grid bodies
-    g = _sheet_engine(sheets, bodies=1)
+    g = hs.engine(sheets, bodies=1)
     g.set_grid_bodies([GridBody(Collider(1, body=0, p_WB=(0.5, 0.5, 0.53), dims=(0.06, 0, 0)), mode=0)])
     g.set_force_fields(fields)
     g.run_substeps(20, DT, BC_BODIES)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0
-    assert np.isfinite(g.download(_A().VELOCITIES)).all()
+    assert np.isfinite(g.download(hs.ARR().VELOCITIES)).all()
     g.destroy()
     # per-cloth materials, the batched path
     mat = GpuMpm.default_material()
@@ -371,7 +334,7 @@ def test_combinations_run():
 
 def test_refusals():
     from drake_amd import FF_DRAG, FF_NORMAL_DRAG, Collider, ForceField, MpmError
-    g = _sheet_engine(_flat_sheet(res=20, side=0.3, z=0.6), bodies=1)
+    g = hs.engine(_flat_sheet(res=20, side=0.3, z=0.6), bodies=1)
 
     def refused(call, says=None):
         with pytest.raises(MpmError) as e:

@@ -21,6 +21,7 @@
    recorded.
 
 Every guard / true-limit ratio goes through helpers.MARGINS into the suite's report."""
+import functools
 import math
 
 import numpy as np
@@ -30,6 +31,7 @@ from tests import anchors as an
 from tests import bending as bd
 from tests import damping as dp
 from tests import guards as gd
+from tests import harness as hs
 from tests import links as lk
 from tests import shell_bending as sb
 from tests import shell_damping as sd
@@ -44,64 +46,23 @@ UP = np.array([0.0, 0.0, 0.05], np.float32)
 MATS = (dict(youngs_modulus=2.5e5, poisson_ratio=0.25), dict(youngs_modulus=6e5, density=1300.0))
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
+_engine = functools.partial(hs.engine, material=dict(gravity=0.0))
+_by_id = functools.partial(hs.by_id, split=True)
 
 
-def _record(what, ratio):
-    from tests import helpers
+def _margin(what, ratio):
     print(f"guards [engine]: {what}: {ratio:.4f}")
-    helpers.MARGINS.append((ratio, "guards: " + what + helpers.TAG, 1.0, ratio, ratio))
-
-
-def _engine(cloths, mats=None, bodies=0):
-    """cloths: [(X (n, 3) float32 positions as added, T)]; mats: per-cloth material overrides or None"""
-    from drake_amd import ClothMaterial, GpuMpm
-    mat = GpuMpm.default_material()
-    mat.gravity = 0.0
-    g = GpuMpm(6, mat)
-    g.set_deterministic(True)
-    for c, (X, T) in enumerate(cloths):
-        m = None
-        if mats is not None:
-            m = ClothMaterial.of(mat)
-            for k, val in mats[c].items():
-                setattr(m, k, val)
-        g.add_qr_cloth(X, np.zeros_like(X), T, m)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.asarray(v, np.float32)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, None)
-
-
-def _by_id(g, which):
-    """(face part, vertex part) of a per-particle array in original order"""
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros_like(a)
-    out[pids] = a
-    return out[:g.n_faces], out[g.n_faces:]
+    hs.record(what, ratio, prefix="guards: ")
 
 
 def _masses(g):
-    return _by_id(g, _A().MASSES)[1].astype(np.float64)
+    return _by_id(g, hs.ARR().MASSES)[1].astype(np.float64)
 
 
 def _rest_records(g):
     """(dm (nf, 3), vol (nf,)) float32 in original face order, of a SINGLE-material engine (whose MPM_ARR_VOLUMES is the
     record the face kernels read)"""
-    return g.download(_A().DM_INVERSES).reshape(g.n_faces, 4)[:, [0, 1, 3]].copy(), _by_id(g, _A().VOLUMES)[0].copy()
+    return g.download(hs.ARR().DM_INVERSES).reshape(g.n_faces, 4)[:, [0, 1, 3]].copy(), _by_id(g, hs.ARR().VOLUMES)[0].copy()
 
 
 def _lame32(E, nu):
@@ -145,7 +106,7 @@ class Rig:
 
 def _scene_engine(scene):
     cloths, mats, rest = _cloths(scene)
-    g = _engine(cloths, mats)
+    g = _engine(cloths, mats=mats)
     if rest is not None:
         g.set_rest_shape(rest)
     X, T, cof, first = _joined(cloths)
@@ -357,7 +318,7 @@ def anchors_rig(table):
     g.set_body_motions([BodyMotion(b, q[0], q[1].ravel(), q[2], q[3]) for b, q in motions.items()])
     g.set_anchors(anchors)
     x0 = X
-    _upload(g, x0)
+    hs.upload(g, x0)
     y32 = g.anchor_state()["point"]
     vq32 = an.points(anchors, motions, 0.0)[3]
     n = len(X)
@@ -409,7 +370,7 @@ def test_the_engines_guard_is_below_the_true_limit(name):
     guard = rig.guard()
     assert math.isfinite(guard) and guard > 0
     limit = gd.true_limit(rig.K, rig.D, rig.m, start=guard)
-    _record(f"guard / true limit, {name}", guard / limit)
+    _margin(f"guard / true limit, {name}", guard / limit)
     assert guard <= limit * (1.0 + 1e-6), (name, guard, limit)
     if rig.K is not None and rig.D is not None:
         r = gd.spectral_radius(rig.K, rig.D, rig.m, guard)
@@ -471,7 +432,7 @@ def test_the_device_force_has_that_spectrum(name, kind):
     forces = rig.forces or (rig.forces_K if kind == "K" else rig.forces_D)
 
     def device(x32, v32):
-        _upload(g, x32, v32)
+        hs.upload(g, x32, v32)
         return forces().astype(np.float64), np.zeros((len(x32), 3))
 
     q_dev, _, _ = secant(device, rig.x0, phi, a, rig.m, kind)
@@ -479,11 +440,11 @@ def test_the_device_force_has_that_spectrum(name, kind):
     err = abs(q_dev / q_ref - 1.0)
     print(f"guards [engine]: spectrum {name} {kind}: a = 2^{int(round(math.log2(a / H0)))} H0, lambda_max {lam:.6g}, float64 secant "
           f"{q_ref / lam:.5f} of it, device / float64 - 1 = {err:.2e}, carried bound {rel:.2e}")
-    _record(f"device secant against float64, {name} {kind}", err / rel if err > 0 else 0.0)
+    _margin(f"device secant against float64, {name} {kind}", err / rel if err > 0 else 0.0)
     assert err <= rel, (name, kind, err, rel)
     guard = rig.guard()
     top = 2.0 / math.sqrt(q_dev) if kind == "K" else 2.0 / q_dev
-    _record(f"guard / limit of the device's quotient, {name} {kind}", guard / top)
+    _margin(f"guard / limit of the device's quotient, {name} {kind}", guard / top)
     assert guard <= top * (1.0 + rel), (name, kind, guard, top)
     assert g.stats()["error_flags"] == 0
     g.destroy()
@@ -509,7 +470,7 @@ def test_the_fan_with_both_bending_models():
     K = gd.sanity(gd.bending_K(kb, X, T)[0]) + gd.sanity(gd.shell_K(X.astype(np.float64), ids.astype(np.int64), kc, psibar))
     limit = gd.true_limit(K, None, m)
     guards = [gb, gs]
-    _record("true limit / min(guard), fan with both bending models", limit / min(guards))
+    _margin("true limit / min(guard), fan with both bending models", limit / min(guards))
     for dt in (gd.composed_limit(guards), gd.composed_limit_elastic(guards)):
         assert dt <= limit * (1.0 + 1e-6) and gd.spectral_radius(K, None, m, dt) <= 1.0 + gd.RADIUS_TOL
     assert limit < min(guards), (limit, guards)
@@ -538,7 +499,7 @@ def test_a_patch_of_feature_paths_cloth_1():
     n = len(X)
     cm = fp.cloth_material(1)
     mats = [dict(youngs_modulus=cm.youngs_modulus, density=cm.density)]
-    g = _engine([(X, T)], mats)
+    g = _engine([(X, T)], mats=mats)
     m = _masses(g)
     g.set_bending([1e-5])
     kb = float(F(1e-5 * (fp.SHARE * g.bending_max_stable_dt() / fp.DT) ** 2))
@@ -567,8 +528,8 @@ def test_a_patch_of_feature_paths_cloth_1():
     dt = gd.composed_limit(guards)
     r = gd.spectral_radius(K, D, m, dt)
     limit = gd.true_limit(K, D, m, start=dt)
-    _record("true limit / min(guard), patch of feature_paths cloth 1", limit / min(guards))
-    _record("composed limit / true limit, patch of feature_paths cloth 1", dt / limit)
+    _margin("true limit / min(guard), patch of feature_paths cloth 1", limit / min(guards))
+    _margin("composed limit / true limit, patch of feature_paths cloth 1", dt / limit)
     assert r <= 1.0 + gd.RADIUS_TOL, r
     assert gd.spectral_radius(K, D, m, fp.DT) <= 1.0 + gd.RADIUS_TOL
     assert g.stats()["error_flags"] == 0

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 
 from tests import halo_layouts as hl
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
@@ -79,7 +80,7 @@ def _particles(g):
                                           ("F", A.DEFORMATION_GRADIENTS))}
 
 
-def _same_bits(got, want, what):
+def _same_words(got, want, what):
     got, want = np.asarray(got), np.asarray(want)
     assert got.shape == want.shape, (what, got.shape, want.shape)
     if got.dtype.kind == "f":
@@ -90,19 +91,19 @@ def _same_bits(got, want, what):
 
 def _same_state(a, b, what):
     for k in ("pids", "x", "v", "C", "F"):
-        _same_bits(a[k], b[k], f"{what}: particles {k}")
+        _same_words(a[k], b[k], f"{what}: particles {k}")
 
 
 def _same_grid(a, b, what):
     for k in ("gm", "gv", "gvs"):
-        _same_bits(a[k], b[k], f"{what}: grid {k}")
+        _same_words(a[k], b[k], f"{what}: grid {k}")
 
 
 def _grid_is(grid, raw_after, what):
     m, gv, gvs = hl.update_ref(raw_after)
-    _same_bits(grid["gm"], m, f"{what}: GRID_MASSES against the restatement")
-    _same_bits(grid["gvs"], gvs, f"{what}: GRID_V_STAR against the restatement")
-    _same_bits(grid["gv"], gv, f"{what}: GRID_MOMENTUM against the restatement")
+    _same_words(grid["gm"], m, f"{what}: GRID_MASSES against the restatement")
+    _same_words(grid["gvs"], gvs, f"{what}: GRID_V_STAR against the restatement")
+    _same_words(grid["gv"], gv, f"{what}: GRID_MOMENTUM against the restatement")
 
 
 def _ok(g):
@@ -259,7 +260,7 @@ def test_add(name, which):
     g.halo_add(buf.data_ptr(), CAP)
     _ok(g)
     want = hl.add_ref(raw0, act, entries)
-    _same_bits(_raw(g), want, f"{name} {which}: the dense sums after halo_add")
+    _same_words(_raw(g), want, f"{name} {which}: the dense sums after halo_add")
     if name != "empty":
         assert (hl.words(want) != hl.words(raw0)).any()          # (the add matters)
     assert np.array_equal(_host(buf), hl.write_buffer(CAP, entries, extra_words=TAIL))
@@ -343,11 +344,6 @@ def test_two_zones_folded_add_and_one_buffer_for_both(name, which):
 
 
 # ---- e. the split update ---------------------------------------------------------------------------------------------------
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what, 1.0, ratio, ratio))
-
-
 @pytest.mark.parametrize("nz", (1, 2))
 @pytest.mark.parametrize("name,which", [(n, "left") for n in hl.NAMES] + [("straddle", "right"), ("one_sided", "right")])
 def test_split_update_equals_the_unsplit_one(name, which, nz):
@@ -375,14 +371,14 @@ def test_split_update_equals_the_unsplit_one(name, which, nz):
     bx = hl.block_coords(np.arange(hl.NBLOCKS))[0]
     done = np.repeat(hl.selected(bx, [z[:2] for z in zones], 0), 64)
     want_mid = np.concatenate([np.where(done[:, None], gv0, ref["raw0"][:, :3]), m0[:, None]], axis=1)
-    _same_bits(mid_raw, want_mid, what + ": the grid between mid and end")
+    _same_words(mid_raw, want_mid, what + ": the grid between mid and end")
     # every particle carries post-exchange values: GridToParticle of the restated grid on the positions before it
     x0 = ref["before"]
     assert np.array_equal(x0["pids"], state["pids"])
     p = tl.g2p64(x0["x"], hl.update_ref(want_raw)[1], hl.BITS)
     worst = {k: tl.margin(np.abs(state[k] - p[k]), p["b" + k]) for k in ("v", "C", "x")}
     for k, w in worst.items():
-        _record(f"halo exchange: split update, {name} {which} {nz} zones, g2p {k}", w)
+        hs.record(f"halo exchange: split update, {name} {which} {nz} zones, g2p {k}", w)
     assert all(w <= 1.0 for w in worst.values()), worst
     if name != "empty":   # (the received sums matter to particles near the cut: v against the pre-exchange grid differs)
         q = tl.g2p64(x0["x"], hl.update_ref(ref["raw0"])[1], hl.BITS)
@@ -511,13 +507,13 @@ def test_two_ranks_against_their_union(name, pitch):
     assert len(shared) > 20
     cells = (shared[:, None] * 64 + np.arange(64)).reshape(-1)
     # the same pair of numbers on both ranks: identical sums, then identical velocities -- in every one of the substeps
-    _same_bits(frame("left", L["raw1"])[cells], frame("right", R["raw1"])[cells], f"{name} pitch {pitch}: summed raw sums")
+    _same_words(frame("left", L["raw1"])[cells], frame("right", R["raw1"])[cells], f"{name} pitch {pitch}: summed raw sums")
     assert (hl.words(L["raw1"][cells]) != hl.words(L["raw0"][cells])).any()
     for k in ("gm", "gv", "gvs"):
-        _same_bits(frame("left", L["grid"][k])[cells], frame("right", R["grid"][k])[cells], f"{name} pitch {pitch}: {k}")
+        _same_words(frame("left", L["grid"][k])[cells], frame("right", R["grid"][k])[cells], f"{name} pitch {pitch}: {k}")
     for step in range(3):
         a, b = frame("left", L["gvs"][step])[cells], frame("right", R["gvs"][step])[cells]
-        _same_bits(a, b, f"{name} pitch {pitch}: GRID_V_STAR after substep {step + 1}")
+        _same_words(a, b, f"{name} pitch {pitch}: GRID_V_STAR after substep {step + 1}")
         assert a.any()
     # the sums against the float64 sums over both ranks' particles
     both = {k: np.concatenate([L["inputs"][k], R["inputs"][k]]) for k in ("x", "v", "C", "m", "taus", "f")}
@@ -595,7 +591,7 @@ def test_two_ranks_against_their_union(name, pitch):
         worst[f"{w} against the union engine x"] = tl.margin(np.abs(got_x - u["state"]["x"][su]),
                                                              p["bx"] + pu["bx"] + tl.DT32 * spread["bv"] / s + moved["x"])
     for k, v in worst.items():
-        _record(f"halo exchange: two ranks and the union, {name} pitch {pitch}, {k}", v)
+        hs.record(f"halo exchange: two ranks and the union, {name} pitch {pitch}, {k}", v)
         if not v <= 1.0:
             fails.append(f"{k}: {v:.3g} x the bound")
     assert not fails, fails

@@ -16,12 +16,10 @@ tests/link_breaking.py.
 8. Dynamics: a seam thrown apart rips and the strips part, its twin without limits holds; a strip hung by two cords
    swings on one after the other is cut.
 9. Refusals, each with nothing changed."""
-import contextlib
-import os
-
 import numpy as np
 import pytest
 
+from tests import harness as hs
 from tests import link_breaking as lb
 from tests import links as lk
 from tests import substep_paths as sp
@@ -31,49 +29,6 @@ pytestmark = pytest.mark.gpu
 
 U = lb.U
 _CACHE = {}
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _engine(cloths, bits=6, deterministic=True, material=None, bodies=0):
-    """cloths: [(X (n, 3) float32 rest positions, T)]"""
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for X, T in cloths:
-        g.add_qr_cloth(X, np.zeros_like(X), T)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.asarray(v, np.float32)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, None)
-
-
-def _vertices(g, which):
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros((g.n_verts,) + a.shape[1:], a.dtype)
-    out[pids[pids >= g.n_faces] - g.n_faces] = a[pids >= g.n_faces]
-    return out
 
 
 def _fem(g):
@@ -109,7 +64,7 @@ def refused(call, says=None):
 @pytest.mark.parametrize("name", list(lb.SCENES))
 def test_flags_are_float64_verdicts_and_measure_is_the_host_bits(name):
     cloths, links, X = lb.scene(name)
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_links(links)
     n = len(links)
     assert not g.link_break_measure()[1].any() and g.link_break_state()[1] == 0
@@ -119,14 +74,14 @@ def test_flags_are_float64_verdicts_and_measure_is_the_host_bits(name):
         b = lb.limits(name, links, x)
         g.set_link_limits(None)
         g.set_broken_links(np.zeros(n, bool))
-        _upload(g, x, v)
+        hs.upload(g, x, v)
         g.set_link_limits(b)
         assert np.array_equal(g.get_link_limits(), b)
         flags, count = g.link_break_state()
         assert not flags.any() and count == 0
         l2h, bh = _host(links, x, b)
         l2, would = g.link_break_measure()
-        assert np.array_equal(_bits(l2), _bits(l2h)) and np.array_equal(would, bh), (st, int((would != bh).sum()))
+        assert np.array_equal(hs.bits(l2), hs.bits(l2h)) and np.array_equal(would, bh), (st, int((would != bh).sum()))
         _fem(g)
         flags, count = g.link_break_state()
         ref, decided, _ = lb.verdicts64(links, x, b)
@@ -136,7 +91,7 @@ def test_flags_are_float64_verdicts_and_measure_is_the_host_bits(name):
         seen += (int(flags.sum()), int((~flags).sum()))
         # measured again, the state is untouched and broken links are evaluated like the others
         l2b, wouldb = g.link_break_measure()
-        assert np.array_equal(_bits(l2b), _bits(l2h)) and np.array_equal(wouldb, bh)
+        assert np.array_equal(hs.bits(l2b), hs.bits(l2h)) and np.array_equal(wouldb, bh)
         assert np.array_equal(g.link_break_state()[0], flags)
         f = g.link_forces()
         if name in lb.ROWS:
@@ -151,32 +106,32 @@ def test_flags_are_float64_verdicts_and_measure_is_the_host_bits(name):
 # ---- 2, 3 ----------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["stack", "rows65"])
 def test_forces_and_energy_of_a_mixed_table(name):
-    A = _A()
+    A = hs.ARR()
     cloths, links, X = lb.scene(name)
     x, v = lb.state("random", X)
     b = lb.limits(name, links, x)
     broken = lb.verdicts64(links, x, b)[0]
     assert broken.any() and not broken.all()
-    a, t = _engine(cloths), _engine(cloths)
+    a, t = hs.engine(cloths), hs.engine(cloths)
     a.set_links(links)
     a.set_link_limits(b)
     t.set_links(_without(links, broken))
     lim = a.links_max_stable_dt()
     out = []
     for g in (a, t):
-        _upload(g, x, v)
+        hs.upload(g, x, v)
         _fem(g)
-        out.append((g.link_forces(), _vertices(g, A.FORCES), g.link_energy()))
+        out.append((g.link_forces(), hs.vertices(g, A.FORCES), g.link_energy()))
     assert np.array_equal(a.link_break_state()[0], broken)
     (fa, Fa, (ea, la)), (ft, Ft, (et, lt)) = out
-    assert fa.any() and np.array_equal(_bits(fa), _bits(ft)) and np.array_equal(_bits(Fa), _bits(Ft))
+    assert fa.any() and np.array_equal(hs.bits(fa), hs.bits(ft)) and np.array_equal(hs.bits(Fa), hs.bits(Ft))
     # the energy: the twin's terms of the broken links are 0 because their k is; the lengths are all there
-    assert ea == et and ea > 0 and np.array_equal(_bits(la), _bits(lt)) and la[broken].all()
+    assert ea == et and ea > 0 and np.array_equal(hs.bits(la), hs.bits(lt)) and la[broken].all()
     ref, bound, _ = lk.energy64(_without(links, broken), x)
     assert abs(ea - ref) <= bound, (ea, ref, bound)
     # the guard is the whole table's
     assert a.links_max_stable_dt() == lim
-    full = _engine(cloths)
+    full = hs.engine(cloths)
     full.set_links(links)
     assert full.links_max_stable_dt() == lim and lim <= t.links_max_stable_dt()
     full.destroy()
@@ -196,9 +151,9 @@ def test_one_link_at_a_time_is_antisymmetric_to_the_bit():
     from drake_amd import capi
     cloths, links, X = lb.scene("stack")
     x, v = lb.state("random", X)
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_links(links)
-    _upload(g, x, v)
+    hs.upload(g, x, v)
     n = len(links)
     acted = 0
     for i in range(n):
@@ -229,17 +184,17 @@ def test_monotone_flags_scissors_and_restore():
     b = lb.limits("stack", links, x)
     broken = lb.verdicts64(links, x, b)[0]
     n = len(links)
-    g, fresh = _engine(cloths), _engine(cloths)
+    g, fresh = hs.engine(cloths), hs.engine(cloths)
     g.set_links(links)
     fresh.set_links(links)
     g.set_link_limits(b)
-    _upload(g, x, v)
+    hs.upload(g, x, v)
     _fem(g)
     assert np.array_equal(g.link_break_state()[0], broken)
     # the load goes away: every length halves about the centre, nothing would break, the flags stay
     c = x.astype(np.float64).mean(axis=0)
     calm = (c + 0.5 * (x.astype(np.float64) - c)).astype(np.float32)
-    _upload(g, calm, v)
+    hs.upload(g, calm, v)
     assert not g.link_break_measure()[1].any()
     _fem(g)
     flags, count = g.link_break_state()
@@ -247,40 +202,40 @@ def test_monotone_flags_scissors_and_restore():
     # the limits go away: the flags stay, and so does what the substep applies
     g.set_link_limits(None)
     assert not g.get_link_limits().any() and np.array_equal(g.link_break_state()[0], broken)
-    _upload(g, x, v)
+    hs.upload(g, x, v)
     _fem(g)
     assert np.array_equal(g.link_break_state()[0], broken) and not g.link_break_measure()[1].any()
-    twin = _engine(cloths)
+    twin = hs.engine(cloths)
     twin.set_links(_without(links, broken))
-    _upload(twin, x, v)
-    assert np.array_equal(_bits(g.link_forces()), _bits(twin.link_forces()))
+    hs.upload(twin, x, v)
+    assert np.array_equal(hs.bits(g.link_forces()), hs.bits(twin.link_forces()))
     # scissors: the array replaces every flag
     chosen = np.arange(n) % 3 == 1
     g.set_broken_links(chosen)
     flags, count = g.link_break_state()
     assert np.array_equal(flags, chosen) and count == int(chosen.sum())
     twin.set_links(_without(links, chosen))
-    _upload(twin, x, v)
-    assert np.array_equal(_bits(g.link_forces()), _bits(twin.link_forces()))
+    hs.upload(twin, x, v)
+    assert np.array_equal(hs.bits(g.link_forces()), hs.bits(twin.link_forces()))
     e, length = g.link_energy()
     assert e == twin.link_energy()[0] and length[chosen].all()
     # restore: after an all-zero array the engine is a fresh one's bits
     g.set_broken_links(np.zeros(n, bool))
     assert g.link_break_state()[1] == 0 and not g.link_break_state()[0].any()
-    _upload(fresh, x, v)
-    assert np.array_equal(_bits(g.link_forces()), _bits(fresh.link_forces()))
+    hs.upload(fresh, x, v)
+    assert np.array_equal(hs.bits(g.link_forces()), hs.bits(fresh.link_forces()))
     # (the total forces are not compared: this engine's deformation gradients have a history of their own)
     _fem(g)
-    assert not g.link_break_state()[0].any() and np.array_equal(_bits(g.link_forces()), _bits(fresh.link_forces()))
+    assert not g.link_break_state()[0].any() and np.array_equal(hs.bits(g.link_forces()), hs.bits(fresh.link_forces()))
     # mpm_set_links: the limits and flags go with the table they belonged to
     g.set_link_limits(b)
     g.set_broken_links(chosen)
     g.set_links(links)
     assert not g.get_link_limits().any() and g.link_break_state()[1] == 0 and not g.link_break_state()[0].any()
-    _upload(g, x, v)
+    hs.upload(g, x, v)
     _fem(g)
     assert not g.link_break_state()[0].any()
-    assert np.array_equal(_bits(g.link_forces()), _bits(fresh.link_forces()))
+    assert np.array_equal(hs.bits(g.link_forces()), hs.bits(fresh.link_forces()))
     for e_ in (g, fresh, twin):
         assert e_.stats()["error_flags"] == 0
         e_.destroy()
@@ -290,12 +245,12 @@ def test_monotone_flags_scissors_and_restore():
 def test_particle_order_and_deterministic_mode():
     """flags, l2 and link forces by link / original vertex id are the same bits on an engine whose slots have moved
     (substeps through a re-sort, then the full sort) as on a fresh one, and in default mode"""
-    A = _A()
+    A = hs.ARR()
     cloths, links, X = lb.scene("rows65")
-    g, fresh, dflt = _engine(cloths), _engine(cloths), _engine(cloths, deterministic=False)
+    g, fresh, dflt = hs.engine(cloths), hs.engine(cloths), hs.engine(cloths, deterministic=False)
     pid0 = g.download(A.PIDS)
     x0, v0 = lb.state("random", X)
-    _upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], np.float32), v0 + np.array([3.0, 0.5, 0.0], np.float32))
+    hs.upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], np.float32), v0 + np.array([3.0, 0.5, 0.0], np.float32))
     g.run_substeps(12, 1e-4, -1)
     g.gpu_sync()
     g.rebuild_mapping(True)
@@ -306,10 +261,10 @@ def test_particle_order_and_deterministic_mode():
     for e in (g, fresh, dflt):
         e.set_links(links)
         e.set_link_limits(b)
-        _upload(e, x, v)
+        hs.upload(e, x, v)
         _fem(e)
         flags, count = e.link_break_state()
-        res.append((flags, np.array([count]), _bits(e.link_break_measure()[0]), _bits(e.link_forces()), _bits(e.link_energy()[1])))
+        res.append((flags, np.array([count]), hs.bits(e.link_break_measure()[0]), hs.bits(e.link_forces()), hs.bits(e.link_energy()[1])))
     assert res[0][0].any() and not res[0][0].all()
     for k in (1, 2):
         for a, c in zip(res[0], res[k]):
@@ -323,20 +278,6 @@ def test_particle_order_and_deterministic_mode():
 PATH_DELTAS = (1e-5, 5e-5, 2e-4, 1e-3, 1.0)     # m above the length at the start: from "at once" to "never"
 SPARSE_CHECKS = {"MPM_RESORT_EVERY": "12", "MPM_QUIET_FACTOR": "0"}   # substeps skip themselves (tests/feature_paths.py)
 ACCEPTED = ("run_substeps", "profile_substeps", "phase_calls", "phase_calls_undeferred", "substep_begin_end", "coupled")
-
-
-@contextlib.contextmanager
-def _environment(env):
-    old = {k: os.environ.get(k) for k in env or {}}
-    os.environ.update(env or {})
-    try:
-        yield
-    finally:
-        for k, val in old.items():
-            if val is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = val
 
 
 def _soft(g, links, dt, share=0.25):
@@ -359,10 +300,10 @@ def _armed(env=None, **kw):
     and cords at their rest length, the seams 1e-4 as stiff (they pull from the start, and the lower sheet must still
     reach the coupled path's floor) -- and limits PATH_DELTAS above the lengths at the start: no link would break on
     the state at the start, some break on the way, some never"""
-    with _environment(env):
+    with hs.environ(env):
         g = sp.engine(fan=True, **kw)
-    A = _A()
-    x = _vertices(g, A.POSITIONS).astype(np.float64)
+    A = hs.ARR()
+    x = hs.vertices(g, A.POSITIONS).astype(np.float64)
     va = np.arange(0, 1024, 3)
     l0 = np.linalg.norm(x[1024 + va] - x[va], axis=1)
     rows = [(int(a), 1024 + int(a), 1e-4 if i % 3 == 0 else 1.0, 0.0 if i % 3 == 0 else float(l0[i]), 0.01,
@@ -376,13 +317,13 @@ def _armed(env=None, **kw):
 
 
 def _words(g):
-    A = _A()
+    A = hs.ARR()
     g.gpu_sync()
-    st = {k: _bits(g.download(arr)).copy() for k, arr in (("pos", A.POSITIONS), ("vel", A.VELOCITIES), ("C", A.AFFINE),
+    st = {k: hs.bits(g.download(arr)).copy() for k, arr in (("pos", A.POSITIONS), ("vel", A.VELOCITIES), ("C", A.AFFINE),
                                                           ("F", A.DEFORMATION_GRADIENTS), ("pids", A.PIDS))}
     flags, count = g.link_break_state()
     st["broken"], st["count"] = flags.astype(np.uint32), np.array([count], np.uint32)
-    st["link_forces"] = _bits(g.link_forces()).copy()
+    st["link_forces"] = hs.bits(g.link_forces()).copy()
     return st
 
 
@@ -469,11 +410,11 @@ def test_halo_paths_stay_refused():
 def test_off_means_off():
     """40 deterministic substeps through re-sorts on engines with links: never called == limits set and cleared again
     with no flag set, to the bit, and with the same number of re-sort check launches"""
-    A = _A()
+    A = hs.ARR()
     cloths, links, X = lb.scene("stack")
     x0 = X.copy()
     v0 = np.array([4.0, 0.3, 0.0], np.float32) + 0.05 * np.random.default_rng(3).normal(size=x0.shape).astype(np.float32)
-    es = [_engine(cloths) for _ in range(2)]
+    es = [hs.engine(cloths) for _ in range(2)]
     for g in es:
         soft = _soft(g, links, tl.DT)
     es[1].set_link_limits(lb.limits("stack", soft, x0))
@@ -482,14 +423,14 @@ def test_off_means_off():
     assert not es[1].get_link_limits().any() and es[1].link_break_state()[1] == 0
     before = es[0].stats()["rebuilds"]
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         for _ in range(4):
             g.run_substeps(10, tl.DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 1, es[0].stats()
     for which in (A.POSITIONS, A.VELOCITIES, A.AFFINE, A.DEFORMATION_GRADIENTS, A.PIDS):
-        assert np.array_equal(_bits(es[0].download(which)), _bits(es[1].download(which))), which
+        assert np.array_equal(hs.bits(es[0].download(which)), hs.bits(es[1].download(which))), which
     for key in ("substeps", "rebuilds", "resort_checks"):
         assert es[0].stats()[key] == es[1].stats()[key], key
     assert es[0].link_forces().any()
@@ -510,7 +451,7 @@ def test_a_seam_thrown_apart_rips_and_its_twin_holds():
       half a period, and no flag is set.
     * With break_length = 1.25 g0, well inside the twin's reach, every stitch breaks, and from then on the strips fly free:
       the mean gap grows from sample to sample and ends beyond the twin's bound."""
-    A = _A()
+    A = hs.ARR()
     n, m, h, dt = 4, 24, lk.H0, 1e-3
     g0 = 8 * h
     sa = lk.sheet(n, m, (0.375, 0.375, 0.5))
@@ -518,7 +459,7 @@ def test_a_seam_thrown_apart_rips_and_its_twin_holds():
     X = np.concatenate([sa[0], sb[0]])
     base = lk.make_links([((n - 1) * m + j, n * m + j, 1.0, 0.0, 0.0, 0) for j in range(m)])
     mat = dict(gravity=0.0)
-    a, b = _engine([sa, sb], material=mat), _engine([sa, sb], material=mat)
+    a, b = hs.engine([sa, sb], material=mat), hs.engine([sa, sb], material=mat)
     links = _soft(a, base, dt, share=0.1)
     b.set_links(links)
     k = float(links["stiffness"][0])
@@ -537,10 +478,10 @@ def test_a_seam_thrown_apart_rips_and_its_twin_holds():
     v0 = np.zeros_like(X)
     v0[:n * m, 0], v0[n * m:, 0] = -V, V
     a.set_link_limits(np.full(m, 1.25 * g0, np.float32))
-    gap = lambda g: float(np.diff(_vertices(g, A.POSITIONS)[[links["a"], links["b"]]][:, :, 0], axis=0).mean())   # noqa: E731
+    gap = lambda g: float(np.diff(hs.vertices(g, A.POSITIONS)[[links["a"], links["b"]]][:, :, 0], axis=0).mean())   # noqa: E731
     gaps = [[], []]
     for q, g in enumerate((a, b)):
-        _upload(g, X, v0)
+        hs.upload(g, X, v0)
         done = 0
         for s in range(1, 9):
             upto = steps * s // 8
@@ -572,12 +513,12 @@ def test_a_strip_hung_by_two_cords_swings_on_one_when_the_other_is_cut():
       sqrt((M g / k)^2 + 2 M g H / k).  The held end's distance from the bar stays below L + smax, and smax is less than
       half of the drop asserted for the cut end (checked on these numbers alone)."""
     from drake_amd import BodyMotion, Pin
-    A = _A()
+    A = hs.ARR()
     n, m, h, dt = 3, 24, lk.H0, 5e-5
     L = 8 * h
     strip = lk.sheet(n, m, (0.4375, 0.3125, 0.5))
     bar = lk.sheet(2, m, (0.4375, 0.3125, 0.5 + L))
-    g = _engine([strip, bar], bodies=1)
+    g = hs.engine([strip, bar], bodies=1)
     nv = n * m
     g.set_body_motions([BodyMotion(0)])
     g.set_pins([Pin(nv + q, 0, bar[0][q]) for q in range(2 * m)])
@@ -592,14 +533,14 @@ def test_a_strip_hung_by_two_cords_swings_on_one_when_the_other_is_cut():
     g.run_substeps(20, dt, -1)
     g.set_broken_links([False, True])
     assert g.link_break_state()[1] == 1
-    z_cut0 = float(_vertices(g, A.POSITIONS)[ends[1], 2])
+    z_cut0 = float(hs.vertices(g, A.POSITIONS)[ends[1], 2])
     steps = 2000
     smax = Mg / k + float(np.sqrt((Mg / k) ** 2 + 2 * Mg * (m - 1) * h / k))
     assert smax < 0.5 * 0.25 * 9.81 * (steps * dt) ** 2, smax
     g.run_substeps(steps, dt, -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0
-    x = _vertices(g, A.POSITIONS).astype(np.float64)
+    x = hs.vertices(g, A.POSITIONS).astype(np.float64)
     t = steps * dt
     drop = z_cut0 - x[ends[1], 2]
     held = float(np.linalg.norm(x[ends[0]] - x[tops[0]]))
@@ -631,9 +572,9 @@ def test_refusals():
     refused(lambda: g0.set_broken_links(np.zeros(0, bool)), says="finalize")
     g0.destroy()
 
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_links(links)
-    _upload(g, x, v)
+    hs.upload(g, x, v)
     g.set_link_limits(b)
     _fem(g)
     flags = g.link_break_state()[0]
@@ -644,7 +585,7 @@ def test_refusals():
         assert np.array_equal(g.get_link_limits(), b)
         got, count = g.link_break_state()
         assert np.array_equal(got, flags) and count == int(flags.sum())
-        assert np.array_equal(_bits(g.link_forces()), _bits(f_before))
+        assert np.array_equal(hs.bits(g.link_forces()), hs.bits(f_before))
 
     spring = int(np.nonzero((links["rest_length"] > 0) & (b > 0))[0][0])
 

@@ -16,6 +16,7 @@
 import numpy as np
 import pytest
 
+from tests import harness as hs
 from tests import links as lk
 from tests import transfer_layouts as tl
 
@@ -25,63 +26,14 @@ U = lk.U
 CASES = [(s, st) for s in lk.SCENES for st in lk.STATES]
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
-def _engine(cloths, bits=6, deterministic=True, material=None, bodies=0):
-    """cloths: [(X (n, 3) float32 rest positions, T)]"""
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for X, T in cloths:
-        g.add_qr_cloth(X, np.zeros_like(X), T)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.asarray(v, np.float32)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, None)
-
-
-def _vertices(g, which):
-    """a per-particle array of the engine, for the vertices in original order"""
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros((g.n_verts,) + a.shape[1:], a.dtype)
-    out[pids[pids >= g.n_faces] - g.n_faces] = a[pids >= g.n_faces]
-    return out
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
 def _check_forces(g, links, what):
-    A = _A()
-    x, v = _vertices(g, A.POSITIONS), _vertices(g, A.VELOCITIES)
+    A = hs.ARR()
+    x, v = hs.vertices(g, A.POSITIONS), hs.vertices(g, A.VELOCITIES)
     f = g.link_forces()
     ref, bound, _ = lk.vertex_forces64(links, x, v, len(x))
     w = lk.margin(f - ref, bound)
     print(f"link forces: {what}: {w:.3g} of the bound")
-    _record(f"link forces: {what}", w)
+    hs.record(f"link forces: {what}", w)
     assert w <= 1.0, (what, w)
     linked = np.zeros(len(x), bool)
     linked[links["a"]] = linked[links["b"]] = True
@@ -93,30 +45,30 @@ def _check_forces(g, links, what):
 @pytest.mark.parametrize("name,st", CASES)
 def test_forces_against_float64(name, st):
     cloths, links, X = lk.scene(name)
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_links(links)
     assert np.array_equal(g.get_links(), links)
     x0, v0 = lk.state(st, name, X)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     x, v, f0 = _check_forces(g, links, f"{name} {st}")
     assert np.array_equal(x, x0) and np.array_equal(v, v0)
     assert f0.any()
     # substeps that force a re-sort: the state five cells further along x, two short substeps
     before = g.stats()["rebuilds"]
     shift = np.array([5.0 / 64, 0.0, 0.0], np.float32)
-    _upload(g, x0 + shift, v0)
+    hs.upload(g, x0 + shift, v0)
     g.run_substeps(2, min(1e-5, 0.5 * g.links_max_stable_dt()), -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
     _check_forces(g, links, f"{name} {st} after a re-sort")
     # the first state again, in the new particle order: the same bits
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     f1 = g.link_forces()
-    assert np.array_equal(_bits(f1), _bits(f0)), float(np.abs(f1 - f0).max())
+    assert np.array_equal(hs.bits(f1), hs.bits(f0)), float(np.abs(f1 - f0).max())
     g.rebuild_mapping(True)
     _check_forces(g, links, f"{name} {st} after sort = 1")
     f2 = g.link_forces()
-    assert np.array_equal(_bits(f2), _bits(f0)), float(np.abs(f2 - f0).max())
+    assert np.array_equal(hs.bits(f2), hs.bits(f0)), float(np.abs(f2 - f0).max())
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -124,30 +76,30 @@ def test_forces_against_float64(name, st):
 # ---- 2 -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(lk.SCENES))
 def test_total_forces_include_links(name):
-    A = _A()
+    A = hs.ARR()
     cloths, links, X = lk.scene(name)
-    a, b = _engine(cloths), _engine(cloths)
+    a, b = hs.engine(cloths), hs.engine(cloths)
     a.set_links(links)
     x0, v0 = lk.state("random", name, X)
     out = []
     for g in (a, b):
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(min(1e-5, 0.5 * a.links_max_stable_dt()))
-        out.append(_vertices(g, A.FORCES))
+        out.append(hs.vertices(g, A.FORCES))
     fl = a.link_forces()
     assert fl.any() and out[1].any()
     tot = out[1].astype(np.float64) + fl.astype(np.float64)
     err = np.abs(out[0].astype(np.float64) - tot)
     w = float((err / np.maximum(U * np.abs(out[0]).astype(np.float64), 1e-300))[err > 0].max()) if (err > 0).any() else 0.0
     print(f"total forces: {name}: {w:.3g} of one rounding of the sum")
-    _record(f"links: total forces {name}", w)
+    hs.record(f"links: total forces {name}", w)
     assert w <= 1.0, w
     # the links' total: every link's two halves cancel to the bit, what is left is the rounding of the rows' additions
     _, _, acc = lk.vertex_forces64(links, x0, v0, len(X))
     total = np.abs(fl.astype(np.float64).sum(axis=0)).max()
     print(f"sum of the link forces: {total:.3e}, bound {acc.sum():.3e}, gross {np.abs(fl).sum():.3e}")
-    _record(f"links: sum of the link forces {name}", total / acc.sum())
+    hs.record(f"links: sum of the link forces {name}", total / acc.sum())
     assert total <= acc.sum()
     assert not b.link_forces().any() and b.links_max_stable_dt() == np.inf and len(b.get_links()) == 0
     for g in (a, b):
@@ -159,19 +111,19 @@ def test_total_forces_include_links(name):
 @pytest.mark.parametrize("name,st", [("mixed", "rest"), ("mixed", "random"), ("seam", "random")])
 def test_energy_against_float64(name, st):
     cloths, links, X = lk.scene(name)
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_links(links)
     x0, v0 = lk.state(st, name, X)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     e, length = g.link_energy()
     ref, bound, l64 = lk.energy64(links, x0)
     w = abs(e - ref) / bound
     print(f"link energy: {name} {st}: {e:.9e}, {w:.3g} of the bound")
-    _record(f"link energy: {name} {st}", w)
+    hs.record(f"link energy: {name} {st}", w)
     assert ref > 0 and w <= 1.0, (e, ref, bound)
     # the lengths: one float rounding of the square root formed in double
     wl = float((np.abs(length.astype(np.float64) - l64) / np.maximum(U * l64 * (1 + 2.0 ** -20), 1e-300))[l64 > 0].max())
-    _record(f"link lengths: {name} {st}", wl)
+    hs.record(f"link lengths: {name} {st}", wl)
     assert wl <= 1.0 and not length[l64 == 0].any(), wl
     # the same bits in another particle order
     g.rebuild_mapping(True)
@@ -182,17 +134,6 @@ def test_energy_against_float64(name, st):
 
 
 # ---- 4, 5, 6 ---------------------------------------------------------------------------------------------------------
-def _state(g):
-    A = _A()
-    return dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS),
-                F=g.download(A.DEFORMATION_GRADIENTS))
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), (what, k, float(np.abs(a[k].astype(np.float64) - b[k]).max()))
-
-
 def _flying(name, seed=3):
     """the scene at rest, flying along x and y fast enough for several re-sorts in a few dozen substeps of tl.DT"""
     cloths, links, X = lk.scene(name)
@@ -222,33 +163,33 @@ def test_links_that_do_nothing_add_an_exact_zero():
     k = c = 0: both engines run the same kernels, and after the same substeps through re-sorts x, v, C, F are bit-equal"""
     cloths, links, x0, v0 = _flying("mixed")
     n = 40
-    ref = _engine(cloths)
-    _upload(ref, x0, v0)
+    ref = hs.engine(cloths)
+    hs.upload(ref, x0, v0)
     reach = 0.0
     for _ in range(4):                      # (the plain engine's trajectory is the two others': the links do nothing)
         ref.run_substeps(n // 4, tl.DT, -1)
-        x = _vertices(ref, _A().POSITIONS).astype(np.float64)
+        x = hs.vertices(ref, hs.ARR().POSITIONS).astype(np.float64)
         reach = max(reach, float(np.linalg.norm(x[links["b"]] - x[links["a"]], axis=1).max()))
     ref.destroy()
     cords, nulls = links.copy(), links.copy()
     cords["flags"], cords["rest_length"] = lk.TENSION, np.float32(2 * reach)
     cords["stiffness"], cords["damping"] = 1e-6, 1e-9        # (soft: the stability guard lets tl.DT pass)
     nulls["stiffness"] = nulls["damping"] = 0.0
-    es = [_engine(cloths) for _ in range(2)]
+    es = [hs.engine(cloths) for _ in range(2)]
     es[0].set_links(cords)
     es[1].set_links(nulls)
     before = es[0].stats()["rebuilds"]
     for g in es:
         assert g.links_max_stable_dt() > tl.DT
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         for _ in range(4):
             g.run_substeps(n // 4, tl.DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0, g.stats()
     assert es[0].stats()["rebuilds"] - before >= 1, es[0].stats()
     assert not es[0].link_forces().any()
-    assert np.linalg.norm(np.diff(_vertices(es[0], _A().POSITIONS)[[links["a"], links["b"]]], axis=0)[0], axis=1).max() < 2 * reach
-    _same_bits(_state(es[0]), _state(es[1]), "slack cords against k = c = 0")
+    assert np.linalg.norm(np.diff(hs.vertices(es[0], hs.ARR().POSITIONS)[[links["a"], links["b"]]], axis=0)[0], axis=1).max() < 2 * reach
+    hs.same_bits(hs.state(es[0]), hs.state(es[1]), "slack cords against k = c = 0")
     for g in es:
         g.destroy()
 
@@ -258,10 +199,10 @@ def test_scheduling_through_resorts():
     calls give the same bits in x, v, C and F -- a force added twice under the gate would not"""
     cloths, links, x0, v0 = _flying("mixed")
     n = 60
-    es = [_engine(cloths) for _ in range(3)]
+    es = [hs.engine(cloths) for _ in range(3)]
     for g in es:
         _soft(g, links, tl.DT)
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
     before = es[0].stats()["rebuilds"]
     es[0].run_substeps(n, tl.DT, -1)
     for _ in range(n):
@@ -277,9 +218,9 @@ def test_scheduling_through_resorts():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0, g.stats()
     assert es[0].stats()["rebuilds"] - before >= 3, es[0].stats()
-    s = [_state(g) for g in es]
-    _same_bits(s[0], s[1], "run_substeps(n) against n substeps")
-    _same_bits(s[0], s[2], "run_substeps(n) against the phase calls")
+    s = [hs.state(g) for g in es]
+    hs.same_bits(s[0], s[1], "run_substeps(n) against n substeps")
+    hs.same_bits(s[0], s[2], "run_substeps(n) against the phase calls")
     assert es[0].link_forces().any()
     for g in es:
         g.destroy()
@@ -288,16 +229,16 @@ def test_scheduling_through_resorts():
 def test_coupled_path_runs():
     from drake_amd import Collider
     cloths, links, X = lk.scene("mixed")
-    g = _engine(cloths, bodies=1)
+    g = hs.engine(cloths, bodies=1)
     _soft(g, links, tl.DT)
     x0 = X.copy()
-    _upload(g, x0)
+    hs.upload(g, x0)
     floor = [Collider(0, body=0, p_WB=(0.5, 0.5, float(x0[:, 2].min()) - 0.002))]
     res = g.run_coupled_substeps(40, tl.DT, floor, 0.5, 1e5, 1e-4)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0
     assert max(r["contacts"] for r in res) > 0, "the sheets never reached the floor"
-    assert np.isfinite(g.download(_A().VELOCITIES)).all()
+    assert np.isfinite(g.download(hs.ARR().VELOCITIES)).all()
     g.destroy()
 
 
@@ -305,20 +246,20 @@ def test_off_means_off():
     """40 deterministic substeps through re-sorts: never set == set and cleared, to the bit, and with the same number of
     re-sort check launches (the quiet-time hint is in use again)"""
     cloths, links, x0, v0 = _flying("seam")
-    es = [_engine(cloths) for _ in range(2)]
+    es = [hs.engine(cloths) for _ in range(2)]
     es[1].set_links(links)
     assert es[1].links_max_stable_dt() < np.inf and len(es[1].get_links()) == len(links)
     es[1].set_links(links[:0])
     assert len(es[1].get_links()) == 0 and es[1].links_max_stable_dt() == np.inf and not es[1].link_forces().any()
     before = es[0].stats()["rebuilds"]
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         for _ in range(4):
             g.run_substeps(10, tl.DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 2, es[0].stats()
-    _same_bits(_state(es[0]), _state(es[1]), "set and cleared")
+    hs.same_bits(hs.state(es[0]), hs.state(es[1]), "set and cleared")
     assert es[0].stats()["resort_checks"] == es[1].stats()["resort_checks"]
     for g in es:
         g.destroy()
@@ -342,7 +283,7 @@ def test_seamed_strips_close_their_gap():
       same substep.  Per substep it stays within 128 u sum m |v| (the two transfers' roundings, as in
       tests/test_bending_gpu.py) + dt u (sum_i n_i sum S, the rounding of the link rows' additions: every link's two
       halves cancel to the bit, + 16 sum_i |f_i| for the membrane's, f the total vertex forces)."""
-    A = _A()
+    A = hs.ARR()
     n, m, h, dt = 4, 24, lk.H0, 1e-3
     g0 = 8 * h
     sa = lk.sheet(n, m, (0.375, 0.375, 0.5))
@@ -350,7 +291,7 @@ def test_seamed_strips_close_their_gap():
     X = np.concatenate([sa[0], sb[0]])
     base = lk.make_links([((n - 1) * m + j, n * m + j, 1.0, 0.0, 0.0, 0) for j in range(m)])
     mat = dict(gravity=0.0)
-    a, b = _engine([sa, sb], material=mat), _engine([sa, sb], material=mat)
+    a, b = hs.engine([sa, sb], material=mat), hs.engine([sa, sb], material=mat)
     links = _soft(a, base, dt)
     k = float(links["stiffness"][0])
     assert abs(a.links_max_stable_dt() / (4 * dt) - 1.0) < 1e-2
@@ -376,8 +317,8 @@ def test_seamed_strips_close_their_gap():
         a.rebuild_mapping(False)
         a.calc_fem_state_and_force(dt)
         p0, _ = momentum(a)
-        f = _vertices(a, A.FORCES).astype(np.float64)
-        _, _, acc = lk.vertex_forces64(links, _vertices(a, A.POSITIONS), _vertices(a, A.VELOCITIES), len(X))
+        f = hs.vertices(a, A.FORCES).astype(np.float64)
+        _, _, acc = lk.vertex_forces64(links, hs.vertices(a, A.POSITIONS), hs.vertices(a, A.VELOCITIES), len(X))
         a.particle_to_grid(dt)
         a.update_grid(-1)
         a.grid_to_particle(dt)
@@ -388,21 +329,21 @@ def test_seamed_strips_close_their_gap():
     for g in (a, b):
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
-    gap = lambda g: float(np.diff(_vertices(g, A.POSITIONS)[[links["a"], links["b"]]][:, :, 0], axis=0).mean())   # noqa: E731
+    gap = lambda g: float(np.diff(hs.vertices(g, A.POSITIONS)[[links["a"], links["b"]]][:, :, 0], axis=0).mean())   # noqa: E731
     ga, gb = gap(a), gap(b)
     print(f"seam: mean gap {g0:.5f} -> {ga:.5f} after {steps} substeps (g0 / 2 = {g0 / 2:.5f}); the twin's {gb:.5f}")
-    _record("links: mean seam gap after T / 4 over g0 / 2", ga / (g0 / 2))
+    hs.record("links: mean seam gap after T / 4 over g0 / 2", ga / (g0 / 2))
     assert ga < g0 / 2, (ga, g0)
     mom = float(np.abs(added).max())
     print(f"seam: momentum added by the substeps {mom:.3e}, bound {bound:.3e}")
-    _record("links: momentum of the seamed strips", mom / bound)
+    hs.record("links: momentum of the seamed strips", mom / bound)
     assert mom <= bound, (mom, bound)
     lam = mt.youngs_modulus * mt.poisson_ratio / ((1 + mt.poisson_ratio) * (1 - 2 * mt.poisson_ratio))
     mu_l = mt.youngs_modulus / (2 * (1 + mt.poisson_ratio))
     s = 8 * U * float(np.abs(X).max()) / h
     still = 0.5 * (16 * (lam + 2 * mu_l) / mt.density * s / h) * (steps * dt) ** 2
     moved = abs(gb - g0)
-    _record("links: the twin without links", moved / (2 * still))
+    hs.record("links: the twin without links", moved / (2 * still))
     assert moved <= 2 * still, (moved, still)
     for g in (a, b):
         g.destroy()
@@ -428,11 +369,11 @@ def test_refusals():
     refused(lambda: g0.set_links(links), says="finalize")
     g0.destroy()
 
-    g = _engine(cloths, bodies=1)
+    g = hs.engine(cloths, bodies=1)
     good = _soft(g, links, tl.DT, share=0.9)
     lim = g.links_max_stable_dt()
     x0, v0 = lk.state("random", "seam", X)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     f_before = g.link_forces()
 
     def bad(**kw):
@@ -449,7 +390,7 @@ def test_refusals():
     # a table that does not fit 2^31 records is refused by its count, before a link is read
     assert g.lib.mpm_set_links(g.h, 1 << 30, good.ctypes.data) == -1 and "too large" in g.lib.mpm_last_error().decode()
     assert np.array_equal(g.get_links(), good) and g.links_max_stable_dt() == lim
-    assert np.array_equal(_bits(g.link_forces()), _bits(f_before))
+    assert np.array_equal(hs.bits(g.link_forces()), hs.bits(f_before))
     # partitioned, halo, team and chain calls on an engine with links
     nb = 64 // 4
     refused(lambda: g.dist_init(0, 1, [0, nb], 2, 2, 2), says="links")
@@ -466,7 +407,7 @@ def test_refusals():
         refused(call, says="mpm_links_max_stable_dt")
     assert g.stats()["substeps"] == before
     # the limit is the restatement's
-    mass = _vertices(g, _A().MASSES).astype(np.float64)
+    mass = hs.vertices(g, hs.ARR().MASSES).astype(np.float64)
     assert abs(lim / lk.max_stable_dt(good, mass) - 1.0) < 1e-5
     g.run_substeps(2, tl.DT, -1)
     ph, _ = g.profile_substeps(2, tl.DT, -1)

@@ -25,6 +25,7 @@ import numpy as np
 import pytest
 
 from tests import bending as bd
+from tests import harness as hs
 from tests import measure as ms
 from tests import transfer_layouts as tl
 
@@ -34,16 +35,6 @@ U = ms.U
 DT = 2e-4
 DX = 1.0 / 64
 _CACHE = {}
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
 
 
 def _meshes():
@@ -78,7 +69,7 @@ def _engine(deterministic=True, multi=True, bodies=0, meshes=None):
 
 
 def _download(g):
-    A = _A()
+    A = hs.ARR()
     nf = g.n_faces
     return dict(pids=g.download(A.PIDS), x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE),
                 m=g.download(A.MASSES), vol=g.download(A.VOLUMES), F=g.download(A.DEFORMATION_GRADIENTS),
@@ -124,11 +115,11 @@ def _state():
     return _CACHE["state"]
 
 
-def _upload(g, st=None, shift=(0.0, 0.0, 0.0)):
+def _upload_state(g, st=None, shift=(0.0, 0.0, 0.0)):
     st = st or _state()
     x = (st["x"] + np.asarray(shift, np.float32)).astype(np.float32)
     pos = np.concatenate([x[st["tri"]].astype(np.float64).mean(axis=1).astype(np.float32), x])
-    pids = g.download(_A().PIDS)
+    pids = g.download(hs.ARR().PIDS)
     g.upload_particle_state(pos[pids], st["v"][pids], st["C"][pids], None, st["F"])
 
 
@@ -156,7 +147,7 @@ def _bending_refs():
 def _prepared(deterministic=True, bodies=0):
     g = _engine(deterministic, bodies=bodies)
     g.set_bending(_stiffness())
-    _upload(g)
+    _upload_state(g)
     return g
 
 
@@ -182,7 +173,7 @@ def _check_rows(rows, total, ref_rows, what):
         worst = max(worst, ms.compare(row, ref, f"{what}: cloth {c}"))
     worst = max(worst, ms.compare(total, ms.total_of(ref_rows), f"{what}: total"))
     print(f"{what}: worst {worst:.3g} of the bound")
-    _record(f"measure: {what}", worst)
+    hs.record(f"measure: {what}", worst)
 
 
 # ---- 1 -------------------------------------------------------------------------------------------------------------
@@ -218,7 +209,7 @@ def test_face_strain_per_face():
     bnd = 8 * U * faces["VB"] + U * np.abs(faces["Vpsi"])
     w = float((err / bnd).max())
     print(f"face strain: V psi worst {w:.3g} of the bound")
-    _record("measure: face strain V psi", w)
+    hs.record("measure: face strain V psi", w)
     assert w <= 1.0, w
     # in another particle order: the same bits
     g.rebuild_mapping(True)
@@ -235,9 +226,9 @@ def test_rows_are_the_same_bits_in_every_particle_order():
     g = _prepared()
     b0 = _bytes(*g.measure())
     assert len(b0) == 4 * 184
-    pids0 = g.download(_A().PIDS)
+    pids0 = g.download(hs.ARR().PIDS)
     g.rebuild_mapping(True)
-    assert not np.array_equal(g.download(_A().PIDS), pids0), "sort = 1 changed the slot order"
+    assert not np.array_equal(g.download(hs.ARR().PIDS), pids0), "sort = 1 changed the slot order"
     assert _bytes(*g.measure()) == b0
     # a non-deterministic engine given the same upload
     h = _prepared(deterministic=False)
@@ -246,12 +237,12 @@ def test_rows_are_the_same_bits_in_every_particle_order():
     # substeps that force a re-sort (the state five cells further along x), then the same upload again
     before = g.stats()["rebuilds"]
     imap0 = g.resort_table("IMAP").copy()
-    _upload(g, shift=(5.0 / 64, 0.0, 0.0))
+    _upload_state(g, shift=(5.0 / 64, 0.0, 0.0))
     g.run_substeps(2, 1e-5, -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
     assert not np.array_equal(g.resort_table("IMAP"), imap0), "the re-sort moved particles to other slots"
-    _upload(g)
+    _upload_state(g)
     assert _bytes(*g.measure()) == b0
     g.destroy()
 
@@ -262,7 +253,7 @@ _PARTICLE_ARRAYS = ("POSITIONS", "VELOCITIES", "VOLUMES", "AFFINE", "PIDS", "IND
 
 
 def _arrays(g):
-    return {k: g.download(getattr(_A(), k)).tobytes() for k in _PARTICLE_ARRAYS}
+    return {k: g.download(getattr(hs.ARR(), k)).tobytes() for k in _PARTICLE_ARRAYS}
 
 
 def test_a_call_changes_nothing():
@@ -292,7 +283,7 @@ def test_measuring_between_batches_leaves_the_trajectory_alone():
         assert g.stats()["error_flags"] == 0, g.stats()
     assert len(set(float(k) for k in seen)) == 3, "the state moves between the calls"
     for k in ("POSITIONS", "VELOCITIES", "AFFINE", "DEFORMATION_GRADIENTS", "MASSES"):
-        assert a.download(getattr(_A(), k)).tobytes() == b.download(getattr(_A(), k)).tobytes(), k
+        assert a.download(getattr(hs.ARR(), k)).tobytes() == b.download(getattr(hs.ARR(), k)).tobytes(), k
     assert _bytes(*a.measure()) == _bytes(*b.measure())
     for g in (a, b):
         g.destroy()
@@ -319,7 +310,7 @@ def test_p2g_identity():
     The engine runs with the double tile (not deterministic): no fixed-point quantum enters."""
     from drake_amd import GpuMpm
     from tests import helpers
-    A = _A()
+    A = hs.ARR()
     X, T = bd.sheet(24, 24)
     g = GpuMpm(6, GpuMpm.default_material())
     g.add_qr_cloth(X, np.zeros_like(X), T)
@@ -373,7 +364,7 @@ def test_a_state_the_engine_reached():
     g.set_force_fields([ForceField(FF_DRAG, gamma=5.0)])
     st = dict(_state())
     st["v"] = (st["v"] + np.array([3.0, 0.3, -1.0], np.float32)).astype(np.float32)
-    _upload(g, st)
+    _upload_state(g, st)
     z_floor = float(st["x"][:, 2].min()) - 0.002
     res = g.run_coupled_substeps(30, DT, [Collider(0, body=0, p_WB=(0.5, 0.5, z_floor))], 0.5, 1e5, 1e-4)
     g.gpu_sync()
@@ -391,14 +382,14 @@ def test_partitioned_ranks_add_up():
     from drake_amd import MpmError
     nb = 64 // 4
     single = _engine(multi=False)
-    _upload(single)
+    _upload_state(single)
     ref_rows, _ = _restate(single, bending=False)
     rows1, total1 = single.measure()
     _check_rows(rows1, total1, ref_rows, "single-material engine")
     ranks = []
     for rk in range(2):
         g = _engine(multi=False)
-        _upload(g)
+        _upload_state(g)
         g.dist_init(rk, 2, [0, nb // 2, nb], 2, 2, 2)
         ranks.append(g)
     got = [g.measure() for g in ranks]
@@ -420,7 +411,7 @@ def test_partitioned_ranks_add_up():
         assert min(got[0][0][c]["stretch_min"], got[1][0][c]["stretch_min"]) == rows1[c]["stretch_min"]
         assert min(got[0][0][c]["normal_min"], got[1][0][c]["normal_min"]) == rows1[c]["normal_min"]
     print(f"partition: the ranks' rows against the single engine's: worst {worst:.3g} of the bound")
-    _record("measure: two ranks against one engine", worst)
+    hs.record("measure: two ranks against one engine", worst)
     # mpm_face_strain is refused on a partitioned engine, nothing enqueued
     s0 = ranks[0].stats()
     with pytest.raises(MpmError) as e:

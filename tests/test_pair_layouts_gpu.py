@@ -15,11 +15,10 @@ on.  A face whose centroid alone is inside exists for the sphere, the box corner
 the mesh ball among them, are too large or too flat for a triangle's corners to stay outside.
 
 Not covered at these sizes: the grid-stride second pass of the watch (more than 262144 active particles)."""
-import os
-
 import numpy as np
 import pytest
 
+from tests import harness as hs
 from tests import pair_layouts as pl
 from tests import sdf_mesh_reference as meshref
 
@@ -39,17 +38,8 @@ def _col(c):
 def _engine(lay, sort=False, env=None, n_bodies=None):
     """-> (engine with the layout's rest mesh, PIDS: API slot -> original id)"""
     from drake_amd import ARR as A, GpuMpm
-    env = dict(env or {})
-    saved = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with hs.environ(env):
         g = GpuMpm(lay["bits"])
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     g.add_qr_cloth(lay["rest"], np.zeros_like(lay["rest"]), lay["idx"])
     g.finalize()
     g.reallocate_external_bodies(n_bodies or max(lay["n_bodies"], 64))
@@ -61,7 +51,7 @@ def _engine(lay, sort=False, env=None, n_bodies=None):
     return g, pids
 
 
-def _upload(g, pids, pos, vel):
+def _upload_layout(g, pids, pos, vel):
     g.upload_particle_state(pos[pids], vel[pids], None, None, None)
 
 
@@ -115,11 +105,6 @@ def _mesh_ev(lay, lattice, mc):
     return dict(phi=phi, grad=grad, rv=v + np.cross(w, d), b=b, din=din, dout=dout, body=int(mc.body), p=p, name="mesh")
 
 
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
 def _check_rows(tag, lay, ev, rows, pids, values=True):
     """the row, membership and value checks of the module docstring; -> the set of (original id, collider index) present"""
     n = len(rows["particle"])
@@ -157,7 +142,7 @@ def _check_rows(tag, lay, ev, rows, pids, values=True):
                                   ("normal", np.abs(rows["normal"][m] + e["grad"][o]).max(1), e["b"]["grad"][o]),
                                   ("rigid_v", np.abs(rows["rigid_v"][m] - e["rv"][o]).max(1), e["b"]["rv"][o])):
             w = pl.margin(err, bound)
-            _record(f"pair layouts: {tag} {e['name']} {field}", w)
+            hs.record(f"pair layouts: {tag} {e['name']} {field}", w)
             if not w <= 1.0:
                 fails.append(f"{e['name']} (collider {k}) {field}: {w:.3g} x the bound")
     assert not fails, f"{tag}:\n" + "\n".join(fails)
@@ -184,7 +169,7 @@ def _by_original(rows, pids):
 def test_rows_membership_and_values(name):
     lay = pl.layout(name)
     g, pids = _engine(lay)
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     rows = _generate(g, lay["cols"], poison=lay)
     ev = _analytic_ev(lay, lay["cols"])
     n = len(rows["particle"])
@@ -211,7 +196,7 @@ def test_count_left_on_the_device_is_the_solve_s_count():
     lay = pl.layout("empty")
     cols = [pl.Col(0, 1, p=(0.5, 0.5, 0.3), R=pl.rot((1, 0.2, 0), 0.3), v=(0, 0, 0.1), w=(0.1, 0, 0))]
     g, pids = _engine(lay)
-    _upload(g, pids, lay["pos"], lay["vel"] * F(0.01))
+    _upload_layout(g, pids, lay["pos"], lay["vel"] * F(0.01))
     ev = _analytic_ev(lay, cols)
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(DT)
@@ -233,7 +218,7 @@ def test_count_left_on_the_device_is_the_solve_s_count():
 def test_conventions_are_exact():
     lay = pl.layout("conventions")
     g, pids = _engine(lay)
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     rows = _generate(g, lay["cols"], poison=lay)
     orig = pids[rows["particle"].astype(np.int64)]
     for k, j, phi, grad in lay["exact"]:
@@ -280,7 +265,7 @@ def _mesh_engine(lay, p, R, body, v=(0.05, 0, -0.1), w=(0.3, 1.0, 0)):
 def test_shell_generator_query_and_regeneration_agree():
     lay = pl.layout("shell")
     g, pids = _engine(lay)
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     rows = _generate(g, lay["cols"], poison=lay)
     ev = _analytic_ev(lay, lay["cols"])
     present = _check_rows("shell", lay, ev, rows, pids)
@@ -308,7 +293,7 @@ def test_shell_of_a_mesh_collider():
     assert np.abs(phi64).max() <= pl.SHELL_BAND and (phi64 < 0).any() and (phi64 > 0).any()
     g, pids, lattice2, mc = _mesh_engine(lay, p, R, body=1)
     assert np.array_equal(lattice[0], lattice2[0])
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     rows = _generate(g, [], poison=lay)
     ev = [_mesh_ev(lay, lattice, mc)]
     present = _check_rows("shell mesh", lay, ev, rows, pids)
@@ -330,7 +315,7 @@ def test_blocks_structural_slots_in_both_slot_orders(n):
     engines = [_engine(lay, sort=False, n_bodies=32), _engine(lay, sort=True, n_bodies=32)]
     assert np.array_equal(engines[0][1], np.arange(n)) and not np.array_equal(engines[1][1], np.arange(n))
     for g, pids in engines:
-        _upload(g, pids, lay["pos"], lay["vel"])
+        _upload_layout(g, pids, lay["pos"], lay["vel"])
     slots = pl.block_slots(n)
     for which, (_, pids_of_set) in enumerate(engines):       # the spheres about the structural slots of either order
         particles = pids_of_set[slots]
@@ -379,7 +364,7 @@ def test_tables_sixteen_and_seventeen_colliders_in_all_instances():
                                                     body=mesh_body)
             else:
                 g, pids = _engine(lay)
-            _upload(g, pids, lay["pos"], lay["vel"])
+            _upload_layout(g, pids, lay["pos"], lay["vel"])
             ev = _analytic_ev(lay, cols) + ([_mesh_ev(lay, lattice, mc)] if mesh else [])
             all17 = _generate(g, cols, poison=lay)
             present = _check_rows(tag, lay, ev, all17, pids)
@@ -426,13 +411,13 @@ def test_capacity_boundary_regrows_without_changing_a_row():
     N = sum(int(e["din"].sum()) for e in ev)
     assert k >= 3 and 50 < N < lay["n"]
     g, pids = _engine(lay)
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     ref = _generate(g, lay["cols"], poison=lay)
     g.destroy()
     assert len(ref["particle"]) == N
     for cap, overflows in ((N, 0), (N - 1, 1)):
         g, pids = _engine(lay, env=dict(MPM_CT_INITIAL_CAPACITY=str(_initial_capacity_for(cap))))
-        _upload(g, pids, lay["pos"], lay["vel"])
+        _upload_layout(g, pids, lay["pos"], lay["vel"])
         rows = _generate(g, lay["cols"])              # (no poison: it would size the buffers)
         assert rows["overflows"] == overflows == g.contact_counters()["repeated_overflow"], (cap, rows["overflows"])
         _same_rows(ref, rows, f"capacity {cap}")
@@ -520,7 +505,7 @@ def test_watch_hits_and_misses_per_kind(kind, bits):
     margin = float(F(1e-3) * F(lay["dx"]))
     fails = []
     # nothing near: no hit (every kind: the layout keeps 0.03 away, far beyond the ellipsoid's scaling too)
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     assert g.debug_contact_watch(ce) is False
     assert g.debug_contact_watch([_col(k) for k in lay["cols"]]) is False
     whos = ["vertex"] + (["face"] if kind in (1, 2, 3) else [])
@@ -537,7 +522,7 @@ def test_watch_hits_and_misses_per_kind(kind, bits):
                 if who == "face":
                     corners = lay["T"] + lay["idx"][particle]
                     assert np.all(phi[corners] > margin + pl.DECIDE * bnd[corners])
-                _upload(g, pids, pos, lay["vel"])
+                _upload_layout(g, pids, pos, lay["vel"])
                 if g.debug_contact_watch(ce) is not True:
                     fails.append(f"no hit: {who} {particle} at phi64 = {got:.6g} (margin {margin:.6g}, bound {b0:.3g})")
             # must not hit: the same point at margin + 8 x bound, by as little as float32 allows
@@ -555,7 +540,7 @@ def test_watch_hits_and_misses_per_kind(kind, bits):
                     phis = pl.world_sdf64(scaled, pl.watch_points(lay, pos))[0]
                     sure = bool(np.all(phis > pl.DECIDE * bnd * s))
                     assert sure == (floor is floors[-1]), (floor, phis.min())
-                _upload(g, pids, pos, lay["vel"])
+                _upload_layout(g, pids, pos, lay["vel"])
                 if sure and g.debug_contact_watch(ce) is not False:
                     fails.append(f"hit: {who} {particle} at phi64 = {got:.6g} >= margin + 8 x bound (margin {margin:.6g}, bound {b0:.3g})")
     g.destroy()
@@ -571,7 +556,7 @@ def test_watch_hits_and_misses_of_a_mesh_collider():
     lay, g, pids, ends, lattice, mc = _watch_engine(6, MESH_WATCH_POSE)
     st = _MeshStates(lay, lattice, mc)
     margin = float(F(1e-3) * F(lay["dx"]))
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     assert g.debug_contact_watch([]) is False
     fails = []
     for v in ends["vertex"]:
@@ -586,14 +571,14 @@ def test_watch_hits_and_misses_of_a_mesh_collider():
             assert below.sum() == 1 and below[v], (v, name, phi[v], bnd[v], np.sort(phi)[:3])
             if target is not None:
                 assert abs(phi[v] - target) <= 2.0 ** -22, (v, name, phi[v])
-            _upload(g, pids, pos, lay["vel"])
+            _upload_layout(g, pids, pos, lay["vel"])
             if g.debug_contact_watch([]) is not True:
                 fails.append(f"no hit: vertex {v} at interpolant = {phi[v]:.6g} ({name}; margin {margin:.6g}, bound {bnd[v]:.3g})")
         _, r = st.radius(v, lambda phi, b: phi >= margin + b)                           # the first radius at or above it
         for r_out in (r, r + 0.5 * lay["dx"]):
             pos, phi, bnd = st.at(v, r_out)
             assert np.all(phi >= margin + bnd), (v, phi[v], bnd[v])
-            _upload(g, pids, pos, lay["vel"])
+            _upload_layout(g, pids, pos, lay["vel"])
             if g.debug_contact_watch([]) is not False:
                 fails.append(f"hit: vertex {v} at interpolant = {phi[v]:.6g} >= margin + bound (margin {margin:.6g}, bound {bnd[v]:.3g})")
     g.destroy()
@@ -603,7 +588,7 @@ def test_watch_hits_and_misses_of_a_mesh_collider():
 def test_watch_with_more_than_sixteen_colliders():
     """17 colliders travel through the debug entry's own device table"""
     lay, g, pids, _ = _watch_engine(6)
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     far = [pl.Col(1, 1 + k, p=(0.1 + 0.04 * k, 0.5, 0.92), dims=(0.01, 0, 0)) for k in range(17)]
     assert g.debug_contact_watch([_col(c) for c in far]) is False
     far[16] = pl.Col(1, 17, p=lay["pos"][lay["T"] + 5], dims=(0.01, 0, 0))
@@ -622,7 +607,7 @@ def test_debug_watch_validates_like_the_generator_and_leaves_the_pairs_alone():
     assert e.value.code == -1
     raw.destroy()
     g, pids = _engine(lay, n_bodies=8)
-    _upload(g, pids, lay["pos"], lay["vel"])
+    _upload_layout(g, pids, lay["pos"], lay["vel"])
     inside = [pl.Col(0, 1, p=(0.5, 0.5, 0.3), R=pl.rot((1, 0.2, 0), 0.3))]
     rows = _generate(g, inside, poison=lay)
     assert len(rows["particle"]) > 10
@@ -667,7 +652,7 @@ def test_watch_says_no_means_the_generator_makes_no_pair(fast):
                 assert -2 * delta <= got <= -0.5 * delta, (name, got)
                 states.append((f"face inside by {name}", pos, particle))
         for name, pos, inside in states:
-            _upload(g, pids, pos, lay["vel"] * F(0.0))
+            _upload_layout(g, pids, pos, lay["vel"] * F(0.0))
             hit = g.debug_contact_watch(ce)
             g.calc_fem_state_and_force(DT)
             n = g.generate_contact_pairs(ce)
@@ -711,7 +696,7 @@ def test_watch_says_no_means_no_pair_for_a_mesh_collider(fast):
     assert any(d is True for _, _, d in states)
     fails = []
     for name, pos, decided in states:
-        _upload(g, pids, pos, lay["vel"] * F(0.0))
+        _upload_layout(g, pids, pos, lay["vel"] * F(0.0))
         hit = g.debug_contact_watch([])
         g.calc_fem_state_and_force(DT)
         n = g.generate_contact_pairs([])

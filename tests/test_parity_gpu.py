@@ -4,19 +4,15 @@ import numpy as np
 import pytest
 
 from tests.helpers import RTOL, build_pair, close, natural_scales
+from tests import harness as hs
 
 pytestmark = pytest.mark.gpu
 
 DT = 1e-3
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
 def test_finalize_matches_initialize_fem_state():
-    A = _A()
+    A = hs.ARR()
     o, g = build_pair()
     close(g.download(A.VOLUMES), o.vol, what="volumes")
     close(g.download(A.DEFORMATION_GRADIENTS), o.F, scale=1.0, what="F0")
@@ -32,7 +28,7 @@ def test_finalize_matches_initialize_fem_state():
 
 
 def test_keys_bit_exact_and_sort_maps():
-    A = _A()
+    A = hs.ARR()
     o, g = build_pair()
     o.rebuild_mapping(False)
     g.rebuild_mapping(False)
@@ -49,7 +45,7 @@ def test_keys_bit_exact_and_sort_maps():
 
 @pytest.mark.parametrize("bc", [-1, 0, 1, 2, 3])
 def test_phase_by_phase(bc):
-    A = _A()
+    A = hs.ARR()
     # place the sheets where the analytic colliders of that scene live
     z0 = {-1: 0.5, 0: 0.56, 1: 0.75, 2: 0.11, 3: 0.5}[bc]
     side = {-1: 0.3, 0: 0.3, 1: 0.34, 2: 0.3, 3: 0.5}[bc]
@@ -103,7 +99,7 @@ def test_phase_by_phase(bc):
 def test_trajectory_with_sorts_and_rebuilds():
     """20 substeps; the reference-style sort every 4th step on both sides; the engine's
     own block re-sort triggers by itself.  Compared in original particle order."""
-    A = _A()
+    A = hs.ARR()
     o, g = build_pair(layers=4, res=24, vel_amp=1.0)
     for step in range(20):
         srt = step % 4 == 0
@@ -163,7 +159,7 @@ def test_vertex_with_more_than_eight_faces():
     (fused_forces, mpm_engine.hip), and the faces around the hub write their triples to G3.  A fan of 12 faces next to a
     regular sheet, against the oracle, phase by phase and batched, across re-sorts."""
     from drake_amd import scenes
-    A = _A()
+    A = hs.ARR()
     dx = 1.0 / 64
 
     def sheets():
@@ -223,7 +219,7 @@ def test_double_and_fixed_point_tiles_of_p2g_agree(monkeypatch):
     re-sort left them, which differs between two engines outside deterministic mode: that is the rounding noise the
     comparison allows for.)"""
     from drake_amd import GpuMpm, scenes
-    A = _A()
+    A = hs.ARR()
 
     def grid(fixed):
         if fixed:
@@ -259,7 +255,7 @@ def test_substep_equals_phase_calls(deterministic):
     40 runs of this scene: in 30 the largest difference is 0.02-0.04 noises; in 8 face 2439 flips at substep 3 and ends
     6.3-6.9 noises apart, in 2 face 2664 at substep 5).  Hence there: nine in ten particles within 0.4 noises, all but
     2 % within 4, nobody beyond 40."""
-    A = _A()
+    A = hs.ARR()
     o, g1 = build_pair(seed=11, deterministic=deterministic)
     _, g2 = build_pair(seed=11, deterministic=deterministic)
     sc = natural_scales(o, DT)
@@ -293,7 +289,7 @@ def test_batched_substeps_with_resorts_in_between_equal_phase_calls():
     synchronisation point (Ctl::skipped / settle).  Sheets that cross a cell every other substep force
     re-sorts inside the batch: the result must be the one of phase-by-phase calls, which re-sort on demand
     before every substep."""
-    A = _A()
+    A = hs.ARR()
     o, g1 = build_pair(seed=5, vel_amp=0.1)
     _, g2 = build_pair(seed=5, vel_amp=0.1)
     vel = o.vel.copy()

@@ -21,22 +21,13 @@ import numpy as np
 import pytest
 
 from tests import anchors as an
+from tests import harness as hs
 from tests import pin_layouts as pl
 from tests.test_pins_gpu import _same, _state
 
 pytestmark = pytest.mark.gpu
 ERR_DOMAIN = -6
 BATCH = 8          # substeps of the batch that re-sorts on the device
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
 
 
 def _engine(lay, pins=True):
@@ -73,17 +64,9 @@ def _set(g, table, motions):
         g.set_pins([Pin(int(r["vertex"]), int(r["body"]), r["p_BQ"]) for r in table])
 
 
-def _phases(g, dt):
-    g.rebuild_mapping(False)
-    g.calc_fem_state_and_force(dt)
-    g.particle_to_grid(dt)
-    g.update_grid(-1)
-    g.grid_to_particle(dt)
-
-
 def _by_id(g):
     """the particle arrays by particle id (faces first, then vertices), F by face"""
-    A = _A()
+    A = hs.ARR()
     pid = g.download(A.PIDS)
     out = {}
     for k, w in (("x", A.POSITIONS), ("v", A.VELOCITIES), ("C", A.AFFINE), ("q0w", A.MASSES if g.multi else A.VOLUMES)):
@@ -115,7 +98,7 @@ STAGES = ("fresh", "after a sort", "after a device re-sort")
 def _substep(e, lay):
     """a substep by phase calls behind a zeroing of the accumulators -> (state by particle id, (tau, f), quantum)"""
     e.reallocate_external_bodies(lay["n_bodies"])
-    _phases(e, lay["dt"])
+    hs.phases(e, lay["dt"])
     e.gpu_sync()
     assert e.stats()["error_flags"] == 0, e.stats()
     return _by_id(e), e.external_body_force_to_host(), e.anchor_state()["impulse_quantum"]
@@ -126,9 +109,9 @@ def _between(e, lay, stage):
     if stage == 0:                                                        # two substeps and another particle order
         for _ in range(2):
             e.substep(lay["dt"], -1)
-        pid0 = e.download(_A().PIDS)
+        pid0 = e.download(hs.ARR().PIDS)
         e.rebuild_mapping(True)
-        assert not np.array_equal(pid0, e.download(_A().PIDS))
+        assert not np.array_equal(pid0, e.download(hs.ARR().PIDS))
         return 2
     before = e.stats()["rebuilds"]                                         # a batch that re-sorts on the device
     e.run_substeps(BATCH, lay["dt"], -1)
@@ -204,7 +187,7 @@ def test_pins_and_bodies_against_float64(name):
         for t in (table, table[table["body"] != pl.BODY_NONE]):
             h = _engine(lay, pins=False)
             _set(h, t, motions)
-            _phases(h, dt)
+            hs.phases(h, dt)
             h.gpu_sync()
             assert h.stats()["error_flags"] == 0
             out.append(h.external_body_force_to_host())
@@ -212,7 +195,7 @@ def test_pins_and_bodies_against_float64(name):
         assert out[0][1].any() and np.array_equal(_bits(out[0][0]), _bits(out[1][0])) and np.array_equal(_bits(out[0][1]), _bits(out[1][1]))
     for k, w in worst.items():
         print(f"{name}: worst {k} error {w:.3g} of its bound")
-        _record(f"pins: {name} {k}", w)
+        hs.record(f"pins: {name} {k}", w)
     g.destroy()
 
 
@@ -227,8 +210,8 @@ def test_table_order_and_paths_agree_to_the_bit():
         _set(g, t, lay["motions"])
     before = c.stats()["rebuilds"]
     for _ in range(BATCH):
-        _phases(a, lay["dt"])
-        _phases(b, lay["dt"])
+        hs.phases(a, lay["dt"])
+        hs.phases(b, lay["dt"])
     c.run_substeps(BATCH, lay["dt"], -1)
     for g in (a, b, c):
         g.gpu_sync()
@@ -246,7 +229,7 @@ def test_table_order_and_paths_agree_to_the_bit():
 # ---- 3 -------------------------------------------------------------------------------------------------------------
 def _run(g, dt, how):
     if how == "phases":
-        _phases(g, dt)
+        hs.phases(g, dt)
     elif how == "substep":
         g.substep(dt, -1)
     else:
@@ -295,7 +278,7 @@ def test_clocks(kind):
     for b in range(pl.CLOCK_BODIES):
         assert ratio[table["body"] == b].max() <= 1.0, (kind, b, float(ratio[table["body"] == b].max()), lay["expected"][b])
     print(f"clocks, {kind}: worst position error {ratio.max():.3g} of its bound")
-    _record(f"pins: clocks {kind}", float(ratio.max()))
+    hs.record(f"pins: clocks {kind}", float(ratio.max()))
     g.destroy()
 
 
@@ -309,7 +292,7 @@ def test_tile_fit_verdict_per_variant():
         table = pl.tile_fit_table(lay, var)
         g = _engine(lay, pins=False)
         _set(g, table, lay["motions"])
-        _phases(g, lay["dt"])
+        hs.phases(g, lay["dt"])
         g.gpu_sync()
         ctl = g.resort_table("CTL")
         ref = pl.restate(table, lay["motions"], 0.0, lay["dt"])

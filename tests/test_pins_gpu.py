@@ -1,14 +1,13 @@
 """Fixed constraints (pins, include/mpm_hip.h: mpm_set_pins, mpm_set_body_motions, mpm_pins_inside_collider) on the
 device: against the CPU oracle with the pins emulated on the host (tests/pin_reference.py), the substep paths against
 each other to the bit, a coupled run, the reaction, tile crossings, the selection, clearing and the refusals."""
-import os
-
 import numpy as np
 import pytest
 
 from tests.helpers import build_pair, close, natural_scales
 from tests.pin_layouts import clock_after, pin_bounds
 from tests.pin_reference import PinEmulator, face_recentring, rodrigues
+from tests import harness as hs
 
 pytestmark = pytest.mark.gpu
 DT = 1e-3
@@ -16,11 +15,6 @@ MOTION = ((0.5, 0.5, 0.5), rodrigues([0.1, 0.2, 0.3]), (0.05, -0.02, 0.01), (0.3
 # a pinned vertex against the float64 target: the kernel evaluates the target in double and rounds once.  The bound per pin
 # and component is tests/pin_layouts.py's: half a float32 ulp of the value plus the double term counted there.
 ERR_INVALID, ERR_DOMAIN = -1, -6
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
 
 
 def _motion(body, m):
@@ -42,16 +36,8 @@ def _pins_for(g, every=20, body=0, motion=MOTION, verts=None):
     return pins, [Pin(v, b, qq) for v, b, qq in pins]
 
 
-def _phases(g, dt=DT, bc=-1):
-    g.rebuild_mapping(False)
-    g.calc_fem_state_and_force(dt)
-    g.particle_to_grid(dt)
-    g.update_grid(bc)
-    g.grid_to_particle(dt)
-
-
 def _state(g):
-    A = _A()
+    A = hs.ARR()
     tau, f = g.external_body_force_to_host()
     return dict(pos=g.download(A.POSITIONS), vel=g.download(A.VELOCITIES), C=g.download(A.AFFINE), tau=tau, f=f)
 
@@ -63,17 +49,8 @@ def _same(a, b, what=""):
 
 def _engine(sheets, env=None, bodies=1):
     from drake_amd import GpuMpm, scenes
-    env = dict(env or {}, MPM_DETERMINISTIC="1")
-    old = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with hs.environ(dict(env or {}, MPM_DETERMINISTIC="1")):
         g = GpuMpm(6)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     scenes.populate(g, [(p.copy(), v.copy(), i.copy()) for p, v, i in sheets])
     g.reallocate_external_bodies(bodies)
     return g
@@ -82,7 +59,7 @@ def _engine(sheets, env=None, bodies=1):
 def test_pins_against_the_oracle():
     """20 phase-by-phase substeps, 5 % of the vertices pinned to a translating and rotating body: the state against the
     oracle with the pins emulated on the host; the pinned vertices against the float64 target."""
-    A = _A()
+    A = hs.ARR()
     o, g = build_pair(domain_bits=6, layers=2, res=16, vel_amp=0.2)
     sc = natural_scales(o, DT)
     g.reallocate_external_bodies(1)
@@ -94,7 +71,7 @@ def test_pins_against_the_oracle():
     for _ in range(20):
         o.substep(DT, -1)
         em.apply(o, DT, nf, dens)
-        _phases(g)
+        hs.phases(g, DT)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0
     pid = g.download(A.PIDS)
@@ -139,7 +116,7 @@ def test_paths_agree_to_the_bit():
         g.set_body_motions([_motion(0, motion)])
     a, b, c, d = engines
     for _ in range(n):
-        _phases(a)
+        hs.phases(a, DT)
         b.substep(DT, -1)
     c.run_substeps(n, DT, -1)
     far = [Collider(1, body=1, p_WB=(0.9, 0.1, 0.1), dims=(0.02, 0, 0))]
@@ -197,7 +174,7 @@ def test_reaction_momentum_identity_on_the_device():
     pins' force impulse of substep k from mpm_external_body_force_to_host, d the face re-centring term of
     tests/test_pins.py).  Tolerance 1e-5 of M |g| dt: float32 sums over the grid and the particles (the float32 oracle
     meets 1e-6)."""
-    A = _A()
+    A = hs.ARR()
     o, g = build_pair(domain_bits=6, layers=2, res=16, vel_amp=0.2, deterministic=True)
     g.reallocate_external_bodies(1)
     pins, arr = _pins_for(g)
@@ -251,7 +228,7 @@ def test_pins_crossing_tiles_resort_and_match_host_emulation():
     a.run_substeps(n, DT, -1)
     a.gpu_sync()
     for _ in range(n):
-        _phases(b)
+        hs.phases(b, DT)
     b.gpu_sync()
     sa, sb = a.stats(), b.stats()
     assert sa["error_flags"] == 0 and sb["error_flags"] == 0
@@ -294,7 +271,7 @@ def test_selection_matches_host_phi(kind):
 
 
 def test_cleared_pins_equal_an_engine_that_never_had_pins():
-    A = _A()
+    A = hs.ARR()
     sheets = _moving_sheets(seed=6, vx=0.5)
     a, b = _engine(sheets), _engine(sheets)
     a.set_pins(_pins_for(a)[1])

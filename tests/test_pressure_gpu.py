@@ -17,6 +17,7 @@ import math
 import numpy as np
 import pytest
 
+from tests import harness as hs
 from tests import pressure as pr
 from tests import transfer_layouts as tl
 
@@ -26,59 +27,9 @@ U = pr.U
 CASES = [(s, st) for s in pr.SCENES for st in pr.STATES]
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
-def _engine(cloths, bits=6, deterministic=True, material=None, bodies=0):
-    """cloths: [(X (n, 3) float32 rest positions, T)]"""
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for X, T in cloths:
-        g.add_qr_cloth(X, np.zeros_like(X), T)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.asarray(v, np.float32)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, None)
-
-
-def _vertices(g, which):
-    """a per-particle array of the engine, for the vertices in original order"""
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros((g.n_verts,) + a.shape[1:], a.dtype)
-    out[pids[pids >= g.n_faces] - g.n_faces] = a[pids >= g.n_faces]
-    return out
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype.itemsize == 4 else a.view(np.uint64)
-
-
 def _check_state(g, table, T, cf, what):
     """mpm_pressure_state against the restatement on the engine's own positions; returns the records"""
-    x = _vertices(g, _A().POSITIONS)
+    x = hs.vertices(g, hs.ARR().POSITIONS)
     got = g.pressure_state()
     want = pr.cloth_states(table, x, T, cf)
     assert len(got) == len(want)
@@ -87,7 +38,7 @@ def _check_state(g, table, T, cf, what):
         wv = abs(float(got["volume"][c]) - V) / pr.volume_bound(x, Tc)
         print(f"pressure state: {what}: cloth {c}: V = {got['volume'][c]:.9e} ({wv:.3g} of the bound), g = {got['gauge'][c]:.7g}, "
               f"capped = {got['capped'][c]}")
-        _record(f"pressure volume: {what} cloth {c}", wv)
+        hs.record(f"pressure volume: {what} cloth {c}", wv)
         assert wv <= 1.0, (what, c, got["volume"][c], V)
         # the gauge: the restatement's V differs from the engine's within the bound above, far below a float rounding
         assert abs(float(got["gauge"][c]) - float(gq)) <= U * abs(float(gq)) * (1 + 2.0 ** -20), (what, c, got["gauge"][c], gq)
@@ -102,14 +53,14 @@ def _check_state(g, table, T, cf, what):
 
 def _check_forces(g, scene, what):
     cloths, table, X, T, cv, cf = scene
-    x = _vertices(g, _A().POSITIONS)
+    x = hs.vertices(g, hs.ARR().POSITIONS)
     f = g.pressure_forces()
     st = g.pressure_state()
     # (the engine's own gauge pressures, checked against the restatement in _check_state: the force bound is the row's)
     ref, bound, _ = pr.vertex_forces64(table, x, T, cv, cf, g_of_cloth=st["gauge"])
     w = pr.margin(f - ref, bound)
     print(f"pressure forces: {what}: {w:.3g} of the bound")
-    _record(f"pressure forces: {what}", w)
+    hs.record(f"pressure forces: {what}", w)
     assert w <= 1.0, (what, w)
     off = (table["mode"] == pr.OFF)[cv]
     assert not f[off].any() and np.isfinite(f).all()
@@ -121,11 +72,11 @@ def _check_forces(g, scene, what):
 def test_forces_and_state_against_float64(name, st):
     scene = pr.scene(name)
     cloths, table, X, T, cv, cf = scene
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_pressure(table)
     assert np.array_equal(g.get_pressure(), table)
     x0 = pr.state(st, X, cv)
-    _upload(g, x0)
+    hs.upload(g, x0)
     _check_state(g, table, T, cf, f"{name} {st}")
     x, f0, s0 = _check_forces(g, scene, f"{name} {st}")
     assert np.array_equal(x, x0) and f0.any()
@@ -133,7 +84,7 @@ def test_forces_and_state_against_float64(name, st):
     assert np.array_equal(s0["capped"][gas] != 0, np.full(gas.sum(), st == "collapsed"))
     # substeps that force a re-sort: the state five cells further along x, two short substeps
     before = g.stats()["rebuilds"]
-    _upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], np.float32))
+    hs.upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], np.float32))
     g.run_substeps(2, 1e-5, -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
@@ -142,11 +93,11 @@ def test_forces_and_state_against_float64(name, st):
     for sort in (False, True):
         if sort:
             g.rebuild_mapping(True)
-        _upload(g, x0)
+        hs.upload(g, x0)
         f1, s1 = g.pressure_forces(), g.pressure_state()
-        assert np.array_equal(_bits(f1), _bits(f0)), (sort, float(np.abs(f1 - f0).max()))
-        assert np.array_equal(_bits(s1["volume"]), _bits(s0["volume"])) and np.array_equal(_bits(s1["gauge"]), _bits(s0["gauge"]))
-        assert np.array_equal(s1["capped"], s0["capped"]) and np.array_equal(_bits(s1["energy"]), _bits(s0["energy"]))
+        assert np.array_equal(hs.bits(f1), hs.bits(f0)), (sort, float(np.abs(f1 - f0).max()))
+        assert np.array_equal(hs.bits(s1["volume"]), hs.bits(s0["volume"])) and np.array_equal(hs.bits(s1["gauge"]), hs.bits(s0["gauge"]))
+        assert np.array_equal(s1["capped"], s0["capped"]) and np.array_equal(hs.bits(s1["energy"]), hs.bits(s0["energy"]))
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -154,7 +105,7 @@ def test_forces_and_state_against_float64(name, st):
 def test_low_p_max_caps_and_an_engine_that_never_set_reports_volumes():
     scene = pr.scene("mixed")
     cloths, table, X, T, cv, cf = scene
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     # never set: volumes alone
     got = _check_state(g, pr.make_table([(pr.OFF, 0, 0, 0, 0)] * 4), T, cf, "never set")
     assert (got["volume"][[0, 2, 3]] > 0).all() and not g.get_pressure()["mode"].any() and not g.pressure_forces().any()
@@ -174,24 +125,24 @@ def test_low_p_max_caps_and_an_engine_that_never_set_reports_volumes():
 # ---- 3 -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", ["mixed", "gas_bipyramid"])
 def test_total_forces_include_pressure(name):
-    A = _A()
+    A = hs.ARR()
     cloths, table, X, T, cv, cf = pr.scene(name)
-    a, b = _engine(cloths), _engine(cloths)
+    a, b = hs.engine(cloths), hs.engine(cloths)
     a.set_pressure(table)
     x0 = pr.state("random", X, cv)
     out = []
     for g in (a, b):
-        _upload(g, x0)
+        hs.upload(g, x0)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(1e-5)
-        out.append(_vertices(g, A.FORCES))
+        out.append(hs.vertices(g, A.FORCES))
     fp = a.pressure_forces()
     assert fp.any() and out[1].any()
     tot = out[1].astype(np.float64) + fp.astype(np.float64)
     err = np.abs(out[0].astype(np.float64) - tot)
     w = float((err / np.maximum(U * np.abs(out[0]).astype(np.float64), 1e-300))[err > 0].max()) if (err > 0).any() else 0.0
     print(f"total forces: {name}: {w:.3g} of one rounding of the sum")
-    _record(f"pressure: total forces {name}", w)
+    hs.record(f"pressure: total forces {name}", w)
     assert w <= 1.0, w
     assert not b.pressure_forces().any()
     for g in (a, b):
@@ -200,17 +151,6 @@ def test_total_forces_include_pressure(name):
 
 
 # ---- 4, 5 ------------------------------------------------------------------------------------------------------------
-def _state(g):
-    A = _A()
-    return dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS),
-                F=g.download(A.DEFORMATION_GRADIENTS))
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), (what, k, float(np.abs(a[k].astype(np.float64) - b[k]).max()))
-
-
 def _flying(name, seed=3):
     """the scene at rest, flying along x and y fast enough for several re-sorts in a few dozen substeps of tl.DT"""
     scene = pr.scene(name)
@@ -226,10 +166,10 @@ def test_scheduling_through_resorts():
     from drake_amd import Collider
     (cloths, table, X, T, cv, cf), x0, v0 = _flying("mixed")
     n = 40
-    es = [_engine(cloths, bodies=1) for _ in range(3)]
+    es = [hs.engine(cloths, bodies=1) for _ in range(3)]
     for g in es:
         g.set_pressure(table)
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
     before = es[0].stats()["rebuilds"]
     es[0].run_substeps(n, tl.DT, -1)
     for _ in range(n):
@@ -246,9 +186,9 @@ def test_scheduling_through_resorts():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0, g.stats()
     assert es[0].stats()["rebuilds"] - before >= 2, es[0].stats()
-    s = [_state(g) for g in es]
-    _same_bits(s[0], s[1], "run_substeps(n) against the phase calls")
-    _same_bits(s[0], s[2], "run_substeps(n) against the coupled path")
+    s = [hs.state(g) for g in es]
+    hs.same_bits(s[0], s[1], "run_substeps(n) against the phase calls")
+    hs.same_bits(s[0], s[2], "run_substeps(n) against the coupled path")
     ps = [g.pressure_state() for g in es]
     for q in ps[1:]:
         assert q.tobytes() == ps[0].tobytes()
@@ -263,20 +203,20 @@ def test_off_means_off():
     """40 deterministic substeps through re-sorts: never set == set and cleared, to the bit, and with the same number of
     re-sort check launches (the quiet-time hint is in use again)"""
     (cloths, table, X, T, cv, cf), x0, v0 = _flying("mixed")
-    es = [_engine(cloths) for _ in range(2)]
+    es = [hs.engine(cloths) for _ in range(2)]
     es[1].set_pressure(table)
     assert es[1].pressure_forces().any()
     es[1].set_pressure(table[:0])
     assert not es[1].get_pressure()["mode"].any() and len(es[1].get_pressure()) == 4 and not es[1].pressure_forces().any()
     before = es[0].stats()["rebuilds"]
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         for _ in range(4):
             g.run_substeps(10, tl.DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 2, es[0].stats()
-    _same_bits(_state(es[0]), _state(es[1]), "set and cleared")
+    hs.same_bits(hs.state(es[0]), hs.state(es[1]), "set and cleared")
     assert es[0].stats()["resort_checks"] == es[1].stats()["resort_checks"]
     for g in es:
         g.destroy()
@@ -301,9 +241,9 @@ def test_refusals():
     refused(lambda: g0.set_pressure(good), says="finalize")
     g0.destroy()
 
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_pressure(good)
-    _upload(g, pr.state("random", X, cv))
+    hs.upload(g, pr.state("random", X, cv))
     f_before, s_before = g.pressure_forces(), g.pressure_state()
 
     def bad(c, **kw):
@@ -328,7 +268,7 @@ def test_refusals():
     for t, says in tables:
         refused(lambda t=t: g.set_pressure(t), says=says)
         assert np.array_equal(g.get_pressure(), good)
-    assert np.array_equal(_bits(g.pressure_forces()), _bits(f_before)) and g.pressure_state().tobytes() == s_before.tobytes()
+    assert np.array_equal(hs.bits(g.pressure_forces()), hs.bits(f_before)) and g.pressure_state().tobytes() == s_before.tobytes()
     # partitioned, halo, team and chain calls on an engine with pressure
     nb = 64 // 4
     refused(lambda: g.dist_init(0, 1, [0, nb], 2, 2, 2), says="pressure")
@@ -347,7 +287,7 @@ def test_refusals():
 
     # gas on a rest volume <= 0: the icosphere wound inside out
     Xi, Ti = pr.mesh("icosphere")
-    h = _engine([(Xi, Ti[:, [0, 2, 1]].copy())])
+    h = hs.engine([(Xi, Ti[:, [0, 2, 1]].copy())])
     refused(lambda: h.set_pressure(pr.make_table([pr.gas_row("icosphere")])), says=("cloth 0", "reverse the winding"))
     h.set_pressure(pr.make_table([(pr.CONSTANT, 10.0, 0, 0, 0)]))    # (a constant pressure takes any mesh)
     assert h.pressure_state()["volume"][0] < 0
@@ -358,10 +298,10 @@ def test_refusals():
 def _inflate(table_of, what):
     """the icosphere without gravity beside an unpressurised twin, n substeps of dt through the phase calls; returns
     (V per substep, g per substep, the twin's volumes, momentum added, its bound, the last state record, the table)"""
-    A = _A()
+    A = hs.ARR()
     X, T = pr.mesh("icosphere")
     cv, cf = np.zeros(len(X), int), np.zeros(len(T), int)
-    a, b = (_engine([(X, T)], material=dict(gravity=0.0)) for _ in range(2))
+    a, b = (hs.engine([(X, T)], material=dict(gravity=0.0)) for _ in range(2))
     mass = a.download(A.MASSES).astype(np.float64).sum()
     x64 = X.astype(np.float64)
     area = 0.5 * np.linalg.norm(np.cross(x64[T[:, 1]] - x64[T[:, 0]], x64[T[:, 2]] - x64[T[:, 0]]), axis=1).sum()
@@ -388,7 +328,7 @@ def _inflate(table_of, what):
         a.rebuild_mapping(False)
         a.calc_fem_state_and_force(dt)
         p0 = momentum(a)
-        _, bd, _ = pr.vertex_forces64(table, _vertices(a, A.POSITIONS), T, cv, cf)
+        _, bd, _ = pr.vertex_forces64(table, hs.vertices(a, A.POSITIONS), T, cv, cf)
         a.particle_to_grid(dt)
         a.update_grid(-1)
         a.grid_to_particle(dt)
@@ -411,9 +351,9 @@ def _check_inflation(Vs, Vb, mom, bound, what):
     print(f"{what}: V {Vs[0]:.6e} -> {Vs[-1]:.6e} (+{rise / Vs[0]:.3%}); the twin's |dV| {np.abs(Vb - Vb[0]).max():.3e}; "
           f"momentum added {mom:.3e}, bound {bound:.3e}")
     assert (np.diff(Vs) > 0).all(), np.diff(Vs)
-    _record(f"pressure: {what}: the twin's volume change over a tenth of the rise", float(np.abs(Vb - Vb[0]).max() / (0.1 * rise)))
+    hs.record(f"pressure: {what}: the twin's volume change over a tenth of the rise", float(np.abs(Vb - Vb[0]).max() / (0.1 * rise)))
     assert np.abs(Vb - Vb[0]).max() < 0.1 * rise
-    _record(f"pressure: {what}: momentum added over the rounding bound", mom / bound)
+    hs.record(f"pressure: {what}: momentum added over the rounding bound", mom / bound)
     assert mom <= bound, (mom, bound)
 
 
@@ -446,7 +386,7 @@ def test_gas_inflates_the_icosphere_and_its_pressure_falls():
     assert last["capped"][0] == 0
     want = np.float32(float(table["pv"][0]) / float(last["volume"][0]) - float(table["p_ambient"][0]))
     assert float(table["pv"][0]) / float(last["volume"][0]) < float(table["p_max"][0])
-    assert _bits(last["gauge"][:1])[0] == _bits(np.array([want], np.float32))[0], (last["gauge"][0], want)
+    assert hs.bits(last["gauge"][:1])[0] == hs.bits(np.array([want], np.float32))[0], (last["gauge"][0], want)
 
 
 # ---- with every other per-cloth feature --------------------------------------------------------------------------------
@@ -479,7 +419,7 @@ def test_works_with_the_other_features():
     """the mixed scene on a multi-material engine with a force field, bending, damping, links and fast math: the pressure
     forces are the restatement's, the total vertex forces are the twin's plus the pressure's within one rounding of the
     sum, and substeps through every path run clean"""
-    A = _A()
+    A = hs.ARR()
     scene = pr.scene("mixed")
     cloths, table, X, T, cv, cf = scene
     a, b = _featured_engine(cloths, True, table), _featured_engine(cloths, False, table)
@@ -487,16 +427,16 @@ def test_works_with_the_other_features():
     x0 = pr.state("random", X, cv)
     out = []
     for g in (a, b):
-        _upload(g, x0)
+        hs.upload(g, x0)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(dt)
-        out.append(_vertices(g, A.FORCES))
+        out.append(hs.vertices(g, A.FORCES))
     _check_forces(a, scene, "mixed random, every feature on")
     fp = a.pressure_forces()
     tot = out[1].astype(np.float64) + fp.astype(np.float64)
     err = np.abs(out[0].astype(np.float64) - tot)
     w = float((err / np.maximum(U * np.abs(out[0]).astype(np.float64), 1e-300))[err > 0].max()) if (err > 0).any() else 0.0
-    _record("pressure: total forces, every feature on", w)
+    hs.record("pressure: total forces, every feature on", w)
     assert fp.any() and w <= 1.0, w
     a.run_substeps(8, dt, -1)
     for _ in range(2):

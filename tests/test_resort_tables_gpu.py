@@ -11,21 +11,15 @@ against the numpy restatement of tests/resort_reference.py:
 on the static layouts of tests/transfer_layouts.py plus two interleaved previous orders (default and deterministic
 mode), on sequences of re-sorts (shrink and move, a sheet in motion phase by phase, a batch of whole substeps), and on
 the two ranks of a partitioned domain after migrations in both directions."""
-import os
-
 import numpy as np
 import pytest
 
+from tests import harness as hs
 from tests import resort_reference as rr
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
 MODES = ("default", "deterministic")
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
 
 
 def _before(g, with_state=True):
@@ -68,7 +62,7 @@ def _check(g, before, deterministic, where, gravity_axis=None, binning=True, max
         ref_q = rr.quiet_time(xs, vs, rr.key_cells(got), prm["bits"], mat.gravity, gravity_axis, np.ones(len(slots), bool))
         ratio = rr.quiet_ratio(ctl["quiet_time"], ref_q)
         print(f"quiet time{where}: engine {ctl['quiet_time']!r}, float64 {ref_q[0]!r}, allowed [{ref_q[1]!r}, {ref_q[2]!r}], ratio {ratio:.3g}")
-        _record(f"re-sort tables: quiet time{where}", ratio)
+        hs.record(f"re-sort tables: quiet time{where}", ratio)
         assert ratio <= 1.0, f"quiet_time{where}: {ctl['quiet_time']!r}, float64 {ref_q[0]!r}, allowed [{ref_q[1]!r}, {ref_q[2]!r}]"
         pos_prev = np.zeros((prm["Np"], 3))
         pos_prev[slots] = xs
@@ -154,16 +148,8 @@ def test_shrink_and_move(mode):
 def _moving_sheet(env, deterministic):
     """a 24 x 24 sheet on the 64^3 grid moving at 0.3 cells per substep along x"""
     from drake_amd import GpuMpm, scenes
-    saved = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with hs.environ(env):
         g = GpuMpm(6)
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     g.set_deterministic(deterministic)
     sheets = scenes.cloth_stack(1, 24, 6, z0=0.5, side=0.25, seed=21, vel_amp=0.2, center=(0.3, 0.5))
     for pos, vel, idx in sheets:

@@ -15,11 +15,12 @@ their float64 rest states and the sheets are tests/rest_shape.py's; the bounds a
    re-sort of a state with one particle per cell (tests/rest_shape.py: spread); the scene keeps its 5 % stretch and
    0.08 shear.
 3. Off means off.  4. Features set afterwards follow the rest shape.  5. Refusals.  6. Physics."""
-import os
+import functools
 
 import numpy as np
 import pytest
 
+from tests import harness as hs
 from tests import rest_meshes as rm
 from tests import rest_shape as rs
 from tests import substep_paths as sp
@@ -31,74 +32,21 @@ REST_FIELDS = ("Dm", "vol", "mass")
 _CACHE = {}
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _engine(cloths, densities=None, deterministic=False, material=None, env=None, bits=rs.BITS):
-    """cloths: [(pos, vel, idx)]; densities: one per cloth (a multi-material engine); material: fields of the engine's"""
-    from drake_amd import ClothMaterial, GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update(env or {})
-    try:
-        g = GpuMpm(bits, mat)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    if deterministic:
-        g.set_deterministic(True)
-    for i, (pos, vel, idx) in enumerate(cloths):
-        m = None
-        if densities is not None:
-            m = ClothMaterial.of(mat)
-            m.density = densities[i]
-        g.add_qr_cloth(pos, np.zeros_like(pos) if vel is None else vel, idx, material=m)
-    g.finalize()
-    offs = np.cumsum([0] + [len(c[0]) for c in cloths[:-1]])
-    g._tri = np.concatenate([np.asarray(c[2]).reshape(-1, 3) + o for c, o in zip(cloths, offs)])
-    return g
+_engine = functools.partial(hs.engine, bits=rs.BITS, deterministic=None)
 
 
 def _same(a, b, fields, what=""):
     for f in fields:
         assert a[f].dtype == b[f].dtype and a[f].shape == b[f].shape, (what, f)
-        bad = np.flatnonzero(np.any((_bits(a[f]) != _bits(b[f])).reshape(len(a[f]), -1), axis=1))
+        bad = np.flatnonzero(np.any((hs.bits(a[f]) != hs.bits(b[f])).reshape(len(a[f]), -1), axis=1))
         assert bad.size == 0, (what, f, int(bad.size), bad[:8])
 
 
-def _by_id(g, which):
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros_like(a)
-    out[pids] = a
-    return out
-
-
-def _state(g):
+def _state_by_id(g):
     """x, v, C by original id, F by face, the slot order"""
-    A = _A()
-    return dict(x=_by_id(g, A.POSITIONS), v=_by_id(g, A.VELOCITIES), C=_by_id(g, A.AFFINE), F=g.download(A.DEFORMATION_GRADIENTS),
+    A = hs.ARR()
+    return dict(x=hs.by_id(g, A.POSITIONS), v=hs.by_id(g, A.VELOCITIES), C=hs.by_id(g, A.AFFINE), F=g.download(A.DEFORMATION_GRADIENTS),
                 pids=g.download(A.PIDS))
-
-
-def _upload(g, x, v=None, F=None):
-    """vertex positions and velocities (n_verts, 3) by original id; a face particle gets its corners' means; C = 0"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.broadcast_to(np.asarray(v, np.float32), x.shape)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, F)
 
 
 def _cloths(case, which):
@@ -131,23 +79,23 @@ def _twin(name, kind, multi, moved=False):
     """-> (a, b, before, after): the rest states of A and B by original id, B's state before and after the call"""
     c = rs.case(name, kind)
     n_cloths = len(c["parts"]) if c["parts"] is not None else 1
-    dens = list(rs.DENSITIES[:n_cloths]) if multi else None
-    A = _engine(_cloths(c, "rest"), dens)
-    B = _engine(_cloths(c, "pose"), dens, env={"MPM_RESORT_EVERY": "1", "MPM_QUIET_FACTOR": "0"} if moved else None)
+    mats = [dict(density=d) for d in rs.DENSITIES[:n_cloths]] if multi else None
+    A = _engine(_cloths(c, "rest"), mats=mats)
+    B = _engine(_cloths(c, "pose"), mats=mats, env={"MPM_RESORT_EVERY": "1", "MPM_QUIET_FACTOR": "0"} if moved else None)
     if moved:
         # five cells along x, a dozen substeps with their re-sort, then the full sort: every slot has moved
-        pid0, before_rebuilds = B.download(_A().PIDS), B.stats()["rebuilds"]
-        _upload(B, c["pose"].pos + np.array([5.0 / 64, 0.0, 0.0], np.float32), np.array([3.0, 0.5, 0.0], np.float32))
+        pid0, before_rebuilds = B.download(hs.ARR().PIDS), B.stats()["rebuilds"]
+        hs.upload(B, c["pose"].pos + np.array([5.0 / 64, 0.0, 0.0], np.float32), np.array([3.0, 0.5, 0.0], np.float32))
         B.run_substeps(12, 1e-4, -1)
         B.gpu_sync()
         B.rebuild_mapping(True)
-        assert B.stats()["rebuilds"] > before_rebuilds and not np.array_equal(B.download(_A().PIDS), pid0), "no slot moved"
-    before = _state(B)
+        assert B.stats()["rebuilds"] > before_rebuilds and not np.array_equal(B.download(hs.ARR().PIDS), pid0), "no slot moved"
+    before = _state_by_id(B)
     assert B.get_rest_shape()[1] is False and np.array_equal(B.get_rest_shape()[0], c["pose"].pos)
     B.set_rest_shape(c["rest"].pos)
     got, is_set = B.get_rest_shape()
-    assert is_set and np.array_equal(_bits(got), _bits(c["rest"].pos))
-    after = _state(B)
+    assert is_set and np.array_equal(hs.bits(got), hs.bits(c["rest"].pos))
+    after = _state_by_id(B)
     a, b = rm.of_engine(A, masses=True), rm.of_engine(B, masses=True)
     for g in (A, B):
         assert g.stats()["error_flags"] == 0, g.stats()
@@ -163,7 +111,7 @@ def test_twin_finalized_on_the_rest_shape(name, kind, multi):
     _same(a, b, REST_FIELDS, (name, kind, multi))
     # what the call leaves alone
     for k in before:
-        assert np.array_equal(_bits(before[k]), _bits(after[k])), (name, kind, k)
+        assert np.array_equal(hs.bits(before[k]), hs.bits(after[k])), (name, kind, k)
     assert np.array_equal(b["pos"][c["rest"].nf:], c["pose"].pos)
     # ... and against float64, under rest_meshes' bounds (F0 is the twin's: B's F stays the pose's)
     if not multi:
@@ -182,7 +130,7 @@ def test_twin_finalized_on_the_rest_shape(name, kind, multi):
                              [np.full(r.nv, d, np.float32) for (r, _), d in zip(parts, rs.DENSITIES)])
         one = _twin(name, kind, False)[1]
         expect = one["vol"] * rho
-        bad = np.flatnonzero(_bits(b["mass"]) != _bits(expect))
+        bad = np.flatnonzero(hs.bits(b["mass"]) != hs.bits(expect))
         assert bad.size == 0, (name, kind, bad[:8])
         _same(one, b, ("Dm",), (name, kind, "Dm of one material"))
 
@@ -192,7 +140,7 @@ def test_twin_after_substeps_that_moved_every_slot(multi):
     a, b, before, after = _twin("valence", "scale", multi, moved=True)
     _same(a, b, REST_FIELDS, ("valence", "scale", multi, "moved"))
     for k in before:
-        assert np.array_equal(_bits(before[k]), _bits(after[k])), k
+        assert np.array_equal(hs.bits(before[k]), hs.bits(after[k])), k
     assert not np.array_equal(before["x"][rs.case("valence", "scale")["rest"].nf:], rs.case("valence", "scale")["pose"].pos)
 
 
@@ -240,19 +188,19 @@ def _dyn_twins(env=None, same_order=True):
     B = _engine([(pose, vel, idx)], deterministic=True, env=env)
     B.set_rest_shape(rest)
     _same(rm.of_engine(A, masses=True), rm.of_engine(B, masses=True), REST_FIELDS, "dynamics twins")
-    sb = _state(B)
+    sb = _state_by_id(B)
     assert B.n_faces == 242
     if same_order:
         wide = rs.spread(idx)
         assert rs.one_per_cell(wide, idx)
         for g in (A, B):
             before = g.stats()["rebuilds"]
-            _upload(g, wide)
+            hs.upload(g, wide)
             g.rebuild_mapping(True)
             assert g.stats()["rebuilds"] > before
-        assert np.array_equal(A.download(_A().PIDS), B.download(_A().PIDS))
+        assert np.array_equal(A.download(hs.ARR().PIDS), B.download(hs.ARR().PIDS))
     for g in (A, B):            # (B too: both then owe the same re-sort)
-        pids = g.download(_A().PIDS)
+        pids = g.download(hs.ARR().PIDS)
         g.upload_particle_state(sb["x"][pids], sb["v"][pids], np.zeros((len(pids), 9), np.float32), None, sb["F"])
     return A, B
 
@@ -260,17 +208,17 @@ def _dyn_twins(env=None, same_order=True):
 def _fresh_forces(g):
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(sp.DT)
-    return _by_id(g, _A().FORCES)
+    return hs.by_id(g, hs.ARR().FORCES)
 
 
 def _compare(A, B, what):
-    sa, sb = _state(A), _state(B)
+    sa, sb = _state_by_id(A), _state_by_id(B)
     for k in ("x", "v", "C", "F"):
-        bad = int((_bits(sa[k]) != _bits(sb[k])).sum())
+        bad = int((hs.bits(sa[k]) != hs.bits(sb[k])).sum())
         assert bad == 0, (what, k, bad)
     fa, fb = _fresh_forces(A), _fresh_forces(B)
-    assert np.array_equal(_bits(fa), _bits(fb)), (what, "forces")
-    _same(dict(F=A.download(_A().DEFORMATION_GRADIENTS)), dict(F=B.download(_A().DEFORMATION_GRADIENTS)), ("F",), what)
+    assert np.array_equal(hs.bits(fa), hs.bits(fb)), (what, "forces")
+    _same(dict(F=A.download(hs.ARR().DEFORMATION_GRADIENTS)), dict(F=B.download(hs.ARR().DEFORMATION_GRADIENTS)), ("F",), what)
     return sa, fa
 
 
@@ -278,7 +226,7 @@ def test_same_forces_after_one_fem_pass():
     """(a face's F and its corner records, and a vertex's sum over them in ascending face id, do not depend on the
     particle order: here the twins keep the orders Finalize gave them)"""
     A, B = _dyn_twins(same_order=False)
-    x0 = _state(B)["x"]
+    x0 = _state_by_id(B)["x"]
     sa, fa = _compare(A, B, "one CalcFemStateAndForce")
     nf = B.n_faces
     assert np.abs(fa[nf:]).max() > 0 and not fa[:nf].any()
@@ -297,7 +245,7 @@ def test_same_dynamics_on_every_substep_path(name):
     family, runner, kw = sp.PATHS[name]
     env = {"MPM_DEFER_PHASES": "0"} if kw.get("defer_phases") is False else None
     A, B = _dyn_twins(env=env)
-    x0 = _state(B)["x"]
+    x0 = _state_by_id(B)["x"]
     for g in (A, B):
         runner(g)
         g.gpu_sync()
@@ -316,7 +264,7 @@ EVERY_ARRAY = ("POSITIONS", "VELOCITIES", "VOLUMES", "MASSES", "AFFINE", "PIDS",
 
 
 def _everything(g):
-    A = _A()
+    A = hs.ARR()
     return {k: g.download(getattr(A, k)) for k in EVERY_ARRAY}
 
 
@@ -326,11 +274,11 @@ def test_off_means_off(multi):
     then a 20-substep trajectory through a re-sort and the launch counters, to the bit"""
     rest, pose, vel, idx = _dyn_sheets()
     vel = vel + np.array([2.0, 0.3, 0.0], np.float32)          # (4 m/s: a cell in 8 substeps of 5e-4 s)
-    dens = [rs.DENSITIES[0]] if multi else None
-    es = [_engine([(pose, vel, idx)], dens, deterministic=True) for _ in range(3)]
+    mats = [dict(density=rs.DENSITIES[0])] if multi else None
+    es = [_engine([(pose, vel, idx)], mats=mats, deterministic=True) for _ in range(3)]
     es[1].set_rest_shape(pose)
     es[2].set_rest_shape(rest)
-    assert not np.array_equal(es[2].download(_A().DM_INVERSES), es[0].download(_A().DM_INVERSES))
+    assert not np.array_equal(es[2].download(hs.ARR().DM_INVERSES), es[0].download(hs.ARR().DM_INVERSES))
     es[2].set_rest_shape(None)
     assert [g.get_rest_shape()[1] for g in es] == [False, True, False]
     for g in es:
@@ -365,14 +313,14 @@ def test_bending_set_afterwards_is_the_twins():
     out = []
     for g in (A, B):
         g.set_bending([1e-4])
-        _upload(g, bump)
+        hs.upload(g, bump)
         out.append((g.bending_forces(), g.bending_max_stable_dt()))
-    assert np.array_equal(_bits(out[0][0]), _bits(out[1][0])) and out[0][1] == out[1][1] and np.isfinite(out[0][1])
+    assert np.array_equal(hs.bits(out[0][0]), hs.bits(out[1][0])) and out[0][1] == out[1][1] and np.isfinite(out[0][1])
     assert np.abs(out[0][0]).max() > 0
     # an engine at the pose without the call has other weights (the pose is sheared: other cotangents)
     Cg = _engine([(pose, None, idx)])
     Cg.set_bending([1e-4])
-    _upload(Cg, bump)
+    hs.upload(Cg, bump)
     assert not np.array_equal(Cg.bending_forces(), out[0][0])
     for g in (A, B, Cg):
         assert g.stats()["error_flags"] == 0
@@ -388,12 +336,12 @@ def test_weave_axes_are_the_rest_shapes():
     B.set_weave([weave(E_warp=2e5, E_weft=1e5, nu=0.1, G=5e4, warp_dir=d)])
     got = B.weave_axes()
     want, bad = weave_face_axes(rest[idx], d)
-    assert bad == -1 and np.array_equal(_bits(got), _bits(want))
+    assert bad == -1 and np.array_equal(hs.bits(got), hs.bits(want))
     assert not np.array_equal(got, weave_face_axes(pose[idx], d)[0])
     # ... and the limit was formed from the rest shape's Dm^-1, volumes and masses: the twin's
     A = _engine([(rest, None, idx)])
     A.set_weave([weave(E_warp=2e5, E_weft=1e5, nu=0.1, G=5e4, warp_dir=d)])
-    assert A.weave_max_stable_dt() == B.weave_max_stable_dt() and np.array_equal(_bits(A.weave_axes()), _bits(got))
+    assert A.weave_max_stable_dt() == B.weave_max_stable_dt() and np.array_equal(hs.bits(A.weave_axes()), hs.bits(got))
     for g in (A, B):
         g.destroy()
 
@@ -405,9 +353,9 @@ def test_shell_bending_defaults_to_the_rest_shape():
     B.set_rest_shape(rest)
     B.set_shell_bending([1e-4])
     assert np.abs(B.shell_hinges()[2]).max() > 0.01          # psibar: the arc's hinge angles (0.09 rad across an edge)
-    _upload(B, rest)
+    hs.upload(B, rest)
     assert not B.shell_forces().any()
-    _upload(B, flat)
+    hs.upload(B, flat)
     assert np.abs(B.shell_forces()).max() > 0
     # without the call the default is the pose: zeros on the flat sheet
     Cg = _engine([(flat, None, idx)])
@@ -460,7 +408,7 @@ def test_refusals():
     def unchanged(what):
         _same(held, rm.of_engine(g, masses=True), ("F0", "Dm", "pos", "vel", "vol", "mass"), what)
         got, is_set = g.get_rest_shape()
-        assert is_set and np.array_equal(_bits(got), _bits(other)), what
+        assert is_set and np.array_equal(hs.bits(got), hs.bits(other)), what
 
     const = np.zeros(1, PRESSURE_DTYPE)
     const["mode"], const["p"] = PRESSURE_CONSTANT, 10.0
@@ -549,14 +497,14 @@ def _relaxed(pos, idx, rest=None, upload=None, gravity=0.0, steps=RELAX_STEPS, p
         g.set_body_motions([BodyMotion(0, p_WB=(0, 0, 0))])
         g.set_pins([Pin(int(v), 0, at[v]) for v in pins])
     if upload is not None:
-        _upload(g, upload)
+        hs.upload(g, upload)
     left = steps
     while left > 0:
         g.run_substeps(min(500, left), PHYS_DT, -1)
         left -= 500
     g.gpu_sync()
     nf = g.n_faces
-    x = _by_id(g, _A().POSITIONS)[nf:]
+    x = hs.by_id(g, hs.ARR().POSITIONS)[nf:]
     rows, total = g.measure()
     assert g.stats()["error_flags"] == 0, g.stats()
     g.destroy()
@@ -606,7 +554,7 @@ def test_measured_mass_is_the_rest_shapes():
     rest, pose, vel, idx = _dyn_sheets()
     A, B = _engine([(rest, None, idx)]), _engine([(pose, None, idx)])
     B.set_rest_shape(rest)
-    want = float(_by_id(A, _A().MASSES).astype(np.float64).sum())
+    want = float(hs.by_id(A, hs.ARR().MASSES).astype(np.float64).sum())
     got = float(B.measure()[1]["mass"])
     print(f"rest shape: measured mass {got!r}, the twin's {want!r}")
     assert abs(got - want) <= ms.bound_of("mass", want)

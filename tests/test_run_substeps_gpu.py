@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from drake_amd import scenes
+from tests import harness
 
 pytestmark = pytest.mark.gpu
 
@@ -141,19 +142,11 @@ def test_quiet_time_spares_the_check_launches():
     conditional re-sort.  The estimate is a hint -- a wrong one defers substeps, it cannot change results -- so the
     test checks (a) that it is a lower bound of the time to the first re-sort of a falling cloth, (b) that the
     launches are indeed left out, (c) that the trajectory is the one of an engine that never trusts it."""
-    import os
     from drake_amd import ARR as A, GpuMpm
 
     def engine(factor):
-        old = os.environ.get("MPM_QUIET_FACTOR")
-        os.environ["MPM_QUIET_FACTOR"] = factor
-        try:
+        with harness.environ({"MPM_QUIET_FACTOR": factor}):
             g = GpuMpm(7)
-        finally:
-            if old is None:
-                del os.environ["MPM_QUIET_FACTOR"]
-            else:
-                os.environ["MPM_QUIET_FACTOR"] = old
         g.set_deterministic(True)
         scenes.populate(g, scenes.cloth_stack(4, 100, 7, z0=0.6, vel_amp=0.05, seed=5))
         return g
@@ -189,19 +182,11 @@ def test_phase_calls_held_back_until_the_substep_is_complete():
     """The reference's five calls per substep launch nothing until GridToParticle arrives and then go the way of
     mpm_run_substeps(1); a call that looks at an intermediate state first launches what was held back.  Against an
     engine that launches every call at once (MPM_DEFER_PHASES=0): the same bits everywhere a caller can look."""
-    import os
     from drake_amd import ARR as A, GpuMpm
 
     def engine(defer):
-        old = os.environ.get("MPM_DEFER_PHASES")
-        os.environ["MPM_DEFER_PHASES"] = defer
-        try:
+        with harness.environ({"MPM_DEFER_PHASES": defer}):
             g = GpuMpm(7)
-        finally:
-            if old is None:
-                del os.environ["MPM_DEFER_PHASES"]
-            else:
-                os.environ["MPM_DEFER_PHASES"] = old
         g.set_deterministic(True)
         sheets = scenes.cloth_stack(4, 100, 7, z0=0.45, vel_amp=0.3, seed=3)
         for pos, vel, idx in sheets:
@@ -254,22 +239,13 @@ def test_long_mixed_run_matches_an_engine_without_the_scheduling():
     the engine with the quiet time, the held-back phase calls, the lean modes and a re-sort check every fourth substep
     against one with all of that switched off (a check with every substep, every call launched at once) -- the same
     bits at every look and at the end (scratch/soak.py is the 3000-substep version)."""
-    import os
     from drake_amd import ARR as A, BC_TABLE, GpuMpm, GridCollider
 
     def engine(on):
         env = dict(MPM_QUIET_FACTOR="0.5" if on else "0", MPM_DEFER_PHASES="1" if on else "0",
                    MPM_RESORT_EVERY="4" if on else "1")
-        old = {k: os.environ.get(k) for k in env}
-        os.environ.update(env)
-        try:
+        with harness.environ(env):
             g = GpuMpm(7)
-        finally:
-            for k, v in old.items():
-                if v is None:
-                    os.environ.pop(k, None)
-                else:
-                    os.environ[k] = v
         g.set_deterministic(True)
         sheets = scenes.cloth_stack(6, 120, 7, z0=0.55, vel_amp=0.4, seed=11)
         for pos, vel, idx in sheets:

@@ -18,7 +18,9 @@ import numpy as np
 import pytest
 
 from tests import bending as bd
+from tests import harness as hs
 from tests import shell_bending as sb
+from tests import shell_scenes as ss
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
@@ -27,79 +29,10 @@ U = sb.U
 DT = 2e-4
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
-def _engine(cloths, bits=6, deterministic=True, material=None, bodies=0, fast_math=False, materials=None):
-    """cloths: [(X (n, 3) float32 positions as added, T)]"""
-    from drake_amd import ClothMaterial, GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    if fast_math:
-        g.set_fast_math(True)
-    for c, (X, T) in enumerate(cloths):
-        if materials:
-            m = ClothMaterial.of(mat)
-            m.youngs_modulus *= 1.0 + 0.25 * c
-            m.density *= 1.0 + 0.1 * c
-            g.add_qr_cloth(X, np.zeros_like(X), T, m)
-        else:
-            g.add_qr_cloth(X, np.zeros_like(X), T)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.asarray(v, np.float32)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, None)
-
-
-def _vertices(g, which):
-    """a per-particle array of the engine, for the vertices in original order"""
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros((g.n_verts,) + a.shape[1:], a.dtype)
-    out[pids[pids >= g.n_faces] - g.n_faces] = a[pids >= g.n_faces]
-    return out
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype.itemsize == 4 else a.view(np.uint64)
-
-
-def _scale_k(g, set_with, dt, share=0.5):
-    """k such that dt is `share` of mpm_shell_max_stable_dt (the limit scales with 1 / sqrt(k)); set_with(k) sets it"""
-    set_with(1.0)
-    lim = g.shell_max_stable_dt()
-    assert np.isfinite(lim) and lim > 0
-    k = float(np.float32((share * lim / dt) ** 2))
-    set_with(k)
-    assert abs(g.shell_max_stable_dt() * share / dt - 1.0) < 1e-3
-    return k
-
-
 def _check(g, H, what, cloth_of_hinge=None, n_cloths=1):
     """forces, psi, energies and the inactive count of the engine on its own positions against the float64 model with the
     engine's own kc and psibar (checked by the caller); returns (x, f, psi, energies)"""
-    x32 = _vertices(g, _A().POSITIONS)
+    x32 = hs.vertices(g, hs.ARR().POSITIONS)
     ids, kc, psibar = g.shell_hinges()
     assert np.array_equal(ids, H)
     f = g.shell_forces()
@@ -121,9 +54,9 @@ def _check(g, H, what, cloth_of_hinge=None, n_cloths=1):
         err, tol = abs(float(E[c]) - E64[ch == c].sum()), Eb[ch == c].sum() + 1e-15 * E64[ch == c].sum()
         we = max(we, err / tol if err > 0 else 0.0)
     print(f"shell bending: {what}: force {w:.3g}, psi {wp:.3g}, energy {we:.3g} of the bound; inactive {inactive}")
-    _record(f"shell forces: {what}", w)
-    _record(f"shell psi: {what}", wp)
-    _record(f"shell energy: {what}", we)
+    hs.record(f"shell forces: {what}", w)
+    hs.record(f"shell psi: {what}", wp)
+    hs.record(f"shell energy: {what}", we)
     assert w <= 1.0 and wp <= 1.0 and we <= 1.0, (what, w, wp, we)
     assert not f[N == 0].any() and not psi[~on].any()
     return x32, f, psi, E
@@ -149,7 +82,7 @@ def _check_table(g, name, k):
 def test_forces_psi_and_energy_against_float64(name, st):
     from drake_amd import SHELL_DTYPE
     X, T, rest = sb.mesh(name)
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     g.set_shell_bending([sb.K], rest)
     want = np.zeros(1, SHELL_DTYPE)
     want["stiffness"] = sb.K
@@ -157,11 +90,11 @@ def test_forces_psi_and_energy_against_float64(name, st):
     H = _check_table(g, name, sb.K)
     assert (g.shell_max_stable_dt() < np.inf) == (len(H) > 0)
     x0 = sb.state(name, st)
-    _upload(g, x0)
+    hs.upload(g, x0)
     x, f0, psi0, E0 = _check(g, H, f"{name} {st}")
     assert np.array_equal(x, x0)
     if st == "rest":
-        assert not f0.any() and not E0.any() and np.array_equal(_bits(psi0), _bits(g.shell_hinges()[2]))     # every float is +-0
+        assert not f0.any() and not E0.any() and np.array_equal(hs.bits(psi0), hs.bits(g.shell_hinges()[2]))     # every float is +-0
     elif st == "collinear":
         assert g.shell_state()[2] == 1 and not f0.any() and not psi0.any()
     elif len(H) and st != "rigid":
@@ -170,7 +103,7 @@ def test_forces_psi_and_energy_against_float64(name, st):
     # face of zero area the membrane model cannot step)
     if st != "collinear":
         before = g.stats()["rebuilds"]
-        _upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], np.float32))
+        hs.upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], np.float32))
         g.run_substeps(2, 1e-5, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
@@ -179,11 +112,11 @@ def test_forces_psi_and_energy_against_float64(name, st):
     for sort in (False, True):
         if sort:
             g.rebuild_mapping(True)
-        _upload(g, x0)
+        hs.upload(g, x0)
         f1 = g.shell_forces()
         E1, psi1, _ = g.shell_state()
-        assert np.array_equal(_bits(f1), _bits(f0)), (sort, float(np.abs(f1 - f0).max()))
-        assert np.array_equal(_bits(psi1), _bits(psi0)) and np.array_equal(_bits(E1), _bits(E0))
+        assert np.array_equal(hs.bits(f1), hs.bits(f0)), (sort, float(np.abs(f1 - f0).max()))
+        assert np.array_equal(hs.bits(psi1), hs.bits(psi0)) and np.array_equal(hs.bits(E1), hs.bits(E0))
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -192,30 +125,30 @@ def test_flat_rest_option_and_both_models_on_one_cloth():
     """MPM_SHELL_REST_FLAT: psibar = 0 and cbar from the mesh as added whatever rest_pos says; mpm_set_bending beside it
     adds its own force"""
     from drake_amd import SHELL_DTYPE, SHELL_REST_FLAT
-    A = _A()
+    A = hs.ARR()
     X, T, rest = sb.mesh("book")
     H = sb.hinges(T)
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     t = np.zeros(1, SHELL_DTYPE)
     t["stiffness"], t["rest"] = sb.K, SHELL_REST_FLAT
     g.set_shell_bending(t, rest)
     ids, kc, psibar = g.shell_hinges()
     want = float(np.float32(sb.K)) * sb.cbar64(X.astype(np.float64), H)
     assert not psibar.any() and (np.abs(kc - want) <= 1.0001 * U * want).all() and np.array_equal(g.get_shell_bending(), t)
-    _upload(g, rest)
+    hs.upload(g, rest)
     _, f, psi, E = _check(g, H, "book, flat rest shape, folded")
     assert f.any() and abs(np.abs(psi).max() - 2 * np.sin(0.5)) < 1e-4 and E[0] > 0
     # with the quadratic model beside it: MPM_ARR_FORCES carries both (against a twin with the quadratic model alone)
-    b = _engine([(X, T)])
+    b = hs.engine([(X, T)])
     out = []
     for e in (g, b):
         e.set_bending([sb.K])
-        _upload(e, rest)
+        hs.upload(e, rest)
         e.rebuild_mapping(False)
         e.calc_fem_state_and_force(1e-5)
-        out.append(_vertices(e, A.FORCES).astype(np.float64))
+        out.append(hs.vertices(e, A.FORCES).astype(np.float64))
     err = np.abs(out[0] - (out[1] + f.astype(np.float64)))
-    assert g.bending_forces().any() and np.array_equal(_bits(g.shell_forces()), _bits(f)) and (err <= U * np.abs(out[0])).all()
+    assert g.bending_forces().any() and np.array_equal(hs.bits(g.shell_forces()), hs.bits(f)) and (err <= U * np.abs(out[0])).all()
     for e in (g, b):
         assert e.stats()["error_flags"] == 0
         e.destroy()
@@ -225,65 +158,36 @@ def test_flat_rest_option_and_both_models_on_one_cloth():
 @pytest.mark.parametrize("name", ["jittered", "tube", "icosphere2"])
 def test_translation_invariance_to_the_bit(name):
     X, T, rest = sb.mesh(name)
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     g.set_shell_bending([sb.K], rest)
     x0 = (np.round(sb.state(name, "perturbed").astype(np.float64) * 2.0 ** 16) / 2.0 ** 16).astype(np.float32)
     x1 = x0 + np.array([2.0 ** -4, -2.0 ** -4, 2.0 ** -4], np.float32)
     assert np.array_equal(x1.astype(np.float64) - x0.astype(np.float64), np.broadcast_to([2.0 ** -4, -2.0 ** -4, 2.0 ** -4], x0.shape))
     out = []
     for x in (x0, x1):
-        _upload(g, x)
-        assert np.array_equal(_vertices(g, _A().POSITIONS), x)
+        hs.upload(g, x)
+        assert np.array_equal(hs.vertices(g, hs.ARR().POSITIONS), x)
         out.append((g.shell_forces(), g.shell_state()))
-    assert out[0][0].any() and np.array_equal(_bits(out[0][0]), _bits(out[1][0]))
-    assert np.array_equal(_bits(out[0][1][1]), _bits(out[1][1][1])) and np.array_equal(_bits(out[0][1][0]), _bits(out[1][1][0]))
+    assert out[0][0].any() and np.array_equal(hs.bits(out[0][0]), hs.bits(out[1][0]))
+    assert np.array_equal(hs.bits(out[0][1][1]), hs.bits(out[1][1][1])) and np.array_equal(hs.bits(out[0][1][0]), hs.bits(out[1][1][0]))
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
 
 # ---- the two-cloth scene of the scheduling tests ---------------------------------------------------------------------------
-def _scene():
-    """the tube and the book side by side: (cloths as added, rest_pos of all vertices, hinges in global ids, cloth of hinge)"""
-    Xt, Tt, _ = sb.mesh("tube")
-    Xb, Tb, rb = sb.mesh("book")
-    st, sh = np.array([-0.15, 0.0, 0.0], np.float32), np.array([0.12, 0.0, 0.0], np.float32)
-    cloths = [(Xt + st, Tt), (Xb + sh, Tb)]
-    rest = np.concatenate([Xt + st, rb + sh])
-    Ht, Hb = sb.hinges(Tt), sb.hinges(Tb) + len(Xt)
-    return cloths, rest, np.concatenate([Ht, Hb]), np.concatenate([np.zeros(len(Ht), int), np.ones(len(Hb), int)])
-
-
-def _flying(seed=3):
-    cloths, rest, H, ch = _scene()
-    x0 = rest.copy()
-    v0 = np.array([4.0, 0.3, 0.0], np.float32) + 0.05 * np.random.default_rng(seed).normal(size=x0.shape).astype(np.float32)
-    return cloths, rest, H, ch, x0, v0
-
-
-def _state(g):
-    A = _A()
-    return dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS),
-                F=g.download(A.DEFORMATION_GRADIENTS))
-
-
-def _same_bits(a, b, what):
-    for k in a:
-        assert np.array_equal(_bits(a[k]), _bits(b[k])), (what, k, float(np.abs(a[k].astype(np.float64) - b[k]).max()))
-
-
 # ---- 3 -------------------------------------------------------------------------------------------------------------------
 def test_total_forces_include_the_shell_force():
-    A = _A()
-    cloths, rest, H, ch = _scene()
-    a, b = _engine(cloths), _engine(cloths)
+    A = hs.ARR()
+    cloths, rest, H, ch = ss.scene()
+    a, b = hs.engine(cloths), hs.engine(cloths)
     a.set_shell_bending([sb.K, 2 * sb.K], rest)
     x0 = bd.perturbed(rest, seed=7).astype(np.float32)
     out = []
     for g in (a, b):
-        _upload(g, x0)
+        hs.upload(g, x0)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(1e-5)
-        out.append(_vertices(g, A.FORCES))
+        out.append(hs.vertices(g, A.FORCES))
     _check(a, H, "tube and book, perturbed", ch, 2)
     fs = a.shell_forces()
     assert fs.any() and out[1].any()
@@ -291,7 +195,7 @@ def test_total_forces_include_the_shell_force():
     err = np.abs(out[0].astype(np.float64) - tot)
     w = float((err / np.maximum(U * np.abs(out[0]).astype(np.float64), 1e-300))[err > 0].max()) if (err > 0).any() else 0.0
     print(f"total forces: {w:.3g} of one rounding of the sum")
-    _record("shell: total forces", w)
+    hs.record("shell: total forces", w)
     assert w <= 1.0, w
     assert not b.shell_forces().any() and b.shell_max_stable_dt() == np.inf
     for g in (a, b):
@@ -305,13 +209,13 @@ def test_scheduling_through_resorts():
     run_coupled_substeps(n) with a collider nobody touches give the same bits in x, v, C and F -- a force added twice
     under the gate, or hinge records left from another substep, would not -- and the same psi and energies"""
     from drake_amd import Collider
-    cloths, rest, H, ch, x0, v0 = _flying()
+    cloths, rest, H, ch, x0, v0 = ss.flying()
     n = 40
-    es = [_engine(cloths, bodies=1) for _ in range(3)]
-    k = _scale_k(es[0], lambda k: es[0].set_shell_bending([k, k], rest), tl.DT)
+    es = [hs.engine(cloths, bodies=1) for _ in range(3)]
+    k = ss.scale_k(es[0], lambda k: es[0].set_shell_bending([k, k], rest), tl.DT)
     for g in es:
         g.set_shell_bending([k, k], rest)
-        _upload(g, x0 + 0.05 * sb.H0 * np.random.default_rng(1).normal(size=x0.shape).astype(np.float32), v0)
+        hs.upload(g, x0 + 0.05 * sb.H0 * np.random.default_rng(1).normal(size=x0.shape).astype(np.float32), v0)
     before = es[0].stats()["rebuilds"]
     es[0].run_substeps(n, tl.DT, -1)
     for _ in range(n):
@@ -328,12 +232,12 @@ def test_scheduling_through_resorts():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0, g.stats()
     assert es[0].stats()["rebuilds"] - before >= 2, es[0].stats()
-    s = [_state(g) for g in es]
-    _same_bits(s[0], s[1], "run_substeps(n) against the phase calls")
-    _same_bits(s[0], s[2], "run_substeps(n) against the coupled path")
+    s = [hs.state(g) for g in es]
+    hs.same_bits(s[0], s[1], "run_substeps(n) against the phase calls")
+    hs.same_bits(s[0], s[2], "run_substeps(n) against the coupled path")
     ps = [g.shell_state() for g in es]
     for q in ps[1:]:
-        assert np.array_equal(_bits(q[0]), _bits(ps[0][0])) and np.array_equal(_bits(q[1]), _bits(ps[0][1])) and q[2] == ps[0][2]
+        assert np.array_equal(hs.bits(q[0]), hs.bits(ps[0][0])) and np.array_equal(hs.bits(q[1]), hs.bits(ps[0][1])) and q[2] == ps[0][2]
     assert es[0].shell_forces().any() and np.isfinite(s[0]["v"]).all()
     _check(es[0], H, "tube and book after 40 substeps in flight", ch, 2)
     ph, _ = es[0].profile_substeps(2, tl.DT, -1)
@@ -345,10 +249,10 @@ def test_scheduling_through_resorts():
 def test_off_means_off():
     """40 deterministic substeps through re-sorts: never set == set and cleared, to the bit, and with the same number of
     re-sort check launches (the quiet-time hint is in use again); an all-zero table is off as well"""
-    cloths, rest, H, ch, x0, v0 = _flying()
-    es = [_engine(cloths) for _ in range(3)]
+    cloths, rest, H, ch, x0, v0 = ss.flying()
+    es = [hs.engine(cloths) for _ in range(3)]
     es[1].set_shell_bending([sb.K, sb.K], rest)
-    _upload(es[1], bd.perturbed(rest, seed=7).astype(np.float32))
+    hs.upload(es[1], bd.perturbed(rest, seed=7).astype(np.float32))
     assert es[1].shell_forces().any() and es[1].shell_max_stable_dt() < np.inf
     es[1].set_shell_bending([])
     es[2].set_shell_bending([sb.K, sb.K], rest)
@@ -358,14 +262,14 @@ def test_off_means_off():
         assert g.shell_max_stable_dt() == np.inf and len(g.shell_hinges()[1]) == 0
     before = es[0].stats()["rebuilds"]
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         for _ in range(4):
             g.run_substeps(10, tl.DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 2, es[0].stats()
     for g in es[1:]:
-        _same_bits(_state(es[0]), _state(g), "set and cleared")
+        hs.same_bits(hs.state(es[0]), hs.state(g), "set and cleared")
         assert es[0].stats()["resort_checks"] == g.stats()["resort_checks"]
     for g in es:
         g.destroy()
@@ -382,7 +286,7 @@ def test_refusals_and_the_guard():
         for s in (says,) if isinstance(says, str) else says:
             assert s in str(e.value), e.value
 
-    cloths, rest, H, ch = _scene()
+    cloths, rest, H, ch = ss.scene()
     # before Finalize
     g0 = GpuMpm(6)
     for Xc, Tc in cloths:
@@ -390,11 +294,11 @@ def test_refusals_and_the_guard():
     refused(lambda: g0.set_shell_bending([sb.K, sb.K]), says="finalize")
     g0.destroy()
 
-    g = _engine(cloths, bodies=1)
-    k = _scale_k(g, lambda k: g.set_shell_bending([k, k], rest), tl.DT, share=0.9)
+    g = hs.engine(cloths, bodies=1)
+    k = ss.scale_k(g, lambda k: g.set_shell_bending([k, k], rest), tl.DT, share=0.9)
     good = g.get_shell_bending()
     lim = g.shell_max_stable_dt()
-    _upload(g, bd.perturbed(rest, seed=7).astype(np.float32))
+    hs.upload(g, bd.perturbed(rest, seed=7).astype(np.float32))
     f_before, s_before, t_before = g.shell_forces(), g.shell_state(), g.shell_hinges()
 
     def table(ks, rests=(0, 0)):
@@ -436,10 +340,10 @@ def test_refusals_and_the_guard():
     # with k = 0 on the cloth nobody asks for its rest shape
     g.set_shell_bending([k, 0.0], flat_face)
     g.set_shell_bending([k, k], rest)
-    assert np.array_equal(_bits(g.shell_forces()), _bits(f_before))
+    assert np.array_equal(hs.bits(g.shell_forces()), hs.bits(f_before))
     s1, t1 = g.shell_state(), g.shell_hinges()
-    assert all(np.array_equal(_bits(p), _bits(q)) for p, q in zip(s1[:2], s_before[:2])) and s1[2] == s_before[2]
-    assert all(np.array_equal(_bits(p), _bits(q)) for p, q in zip(t1, t_before))
+    assert all(np.array_equal(hs.bits(p), hs.bits(q)) for p, q in zip(s1[:2], s_before[:2])) and s1[2] == s_before[2]
+    assert all(np.array_equal(hs.bits(p), hs.bits(q)) for p, q in zip(t1, t_before))
     # partitioned, halo, team and chain calls on an engine with shell bending
     nb = 64 // 4
     refused(lambda: g.dist_init(0, 1, [0, nb], 2, 2, 2), says="shell bending")
@@ -475,12 +379,16 @@ FEATURES = ["pins", "materials", "force_fields", "bending", "damping", "links", 
 def test_works_with(feature):
     """the tube and the book, perturbed, with one other feature on: eight substeps, finite results, no error flag, and the
     shell forces still the model's"""
-    from drake_amd import BodyMotion, Collider, ForceField, Pin, links
+    from drake_amd import BodyMotion, Collider, ForceField, GpuMpm, Pin, links
     from tests import pressure as pr
-    A = _A()
-    cloths, rest, H, ch = _scene()
-    g = _engine(cloths, bodies=1, deterministic=feature != "default_engine", fast_math=feature == "fast_math",
-                materials=feature == "materials")
+    A = hs.ARR()
+    cloths, rest, H, ch = ss.scene()
+    mats = None
+    if feature == "materials":      # (of the engine's float32 fields: the products round once, into the cloth's fields)
+        m0 = GpuMpm.default_material()
+        mats = [dict(youngs_modulus=m0.youngs_modulus * (1.0 + 0.25 * c), density=m0.density * (1.0 + 0.1 * c)) for c in range(len(cloths))]
+    g = hs.engine(cloths, bodies=1, deterministic=feature != "default_engine", fast_math=True if feature == "fast_math" else None,
+                  mats=mats)
     x0 = bd.perturbed(rest, seed=7).astype(np.float32)
     lims = []
     if feature == "pins":
@@ -502,7 +410,7 @@ def test_works_with(feature):
         g.set_pressure(pr.make_table([(pr.CONSTANT, 20.0, 0, 0, 0), (pr.OFF, 0, 0, 0, 0)]))
     g.set_shell_bending([sb.K, sb.K], rest)
     dt = min([1e-4, 0.5 * g.shell_max_stable_dt()] + [0.5 * q for q in lims])
-    _upload(g, x0)
+    hs.upload(g, x0)
     _check(g, H, f"with {feature}", ch, 2)
     if feature == "coupled":
         far = [Collider(1, body=0, p_WB=(0.9, 0.1, 0.1), dims=(0.02, 0, 0))]
@@ -527,8 +435,8 @@ def test_a_rolled_rest_shape_curls_a_flat_sheet():
     1.8327e-2 J."""
     X, T = bd.sheet(9, 8)
     rest = bd.cylinder(X, 4 * sb.H0).astype(np.float32)
-    g = _engine([(X, T)], material=dict(gravity=0.0))
-    _scale_k(g, lambda k: g.set_shell_bending([k], rest), DT)
+    g = hs.engine([(X, T)], material=dict(gravity=0.0))
+    ss.scale_k(g, lambda k: g.set_shell_bending([k], rest), DT)
     _, _, psibar = g.shell_hinges()
     E0, psi0, _ = g.shell_state()
     assert not psi0.any() and np.abs(psibar).max() > 0.1 and E0[0] > 0
@@ -553,8 +461,8 @@ def test_a_tube_keeps_its_shape_under_this_model_and_not_under_the_flat_one():
     bending plus 2^-20 H0.  Measured on an MI355X, the first run: none 0, flat 1.375109e-3 (17.6 % of H0), shell 0 -- the
     shell twin's forces are exact zeros, so nothing moves."""
     X, T, _ = sb.mesh("tube")
-    es = [_engine([(X, T)], material=dict(gravity=0.0)) for _ in range(3)]
-    k = _scale_k(es[2], lambda k: es[2].set_shell_bending([k]), DT)
+    es = [hs.engine([(X, T)], material=dict(gravity=0.0)) for _ in range(3)]
+    k = ss.scale_k(es[2], lambda k: es[2].set_shell_bending([k]), DT)
     es[1].set_bending([k])
     assert es[1].bending_forces().any() and not es[2].shell_forces().any()
     moved = []
@@ -562,7 +470,7 @@ def test_a_tube_keeps_its_shape_under_this_model_and_not_under_the_flat_one():
         g.run_substeps(40, DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
-        moved.append(float(np.abs(_vertices(g, _A().POSITIONS).astype(np.float64) - X).max()))
+        moved.append(float(np.abs(hs.vertices(g, hs.ARR().POSITIONS).astype(np.float64) - X).max()))
         g.destroy()
     none, flat, shell = moved
     print(f"tube: largest displacement after 40 substeps: none {none:.6e}, flat {flat:.6e}, shell {shell:.6e} (H0 = {sb.H0:.4e})")

@@ -16,31 +16,26 @@ the float32 restatement and the counted bound (R_SHELL_DAMP = 62.5 + n_i per row
 9. The guard; refusals.
 10. Dynamics, orderings only."""
 
+import functools
+
 import numpy as np
 import pytest
 
 from tests import bending as bd
 from tests import creases as cr
+from tests import harness as hs
 from tests import shell_bending as sb
 from tests import shell_damping as sd
-from tests import test_shell_bending_gpu as tsb
+from tests import shell_scenes as ss
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
 
 U = sb.U
 F = np.float32
-_engine, _upload, _vertices, _bits = tsb._engine, tsb._upload, tsb._vertices, tsb._bits
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, "shell damping: " + what + helpers.TAG, 1.0, ratio, ratio))
+_record = functools.partial(hs.record, prefix="shell damping: ")
 
 
 def _refused(call, says=()):
@@ -68,8 +63,8 @@ def _check(g, x0, v0, H, kc, psibar, bkc, what, cloth_of_hinge=None, n_cloths=1)
     fd = g.shell_damping_forces()
     power, pd = g.shell_damping_state()
     rec, _, pd32, pw32, on = sd.hinges32(x0, v0, H, kc, psibar, bkc, elastic=False)
-    assert np.array_equal(_bits(fd), _bits(sb.gather32(rec, H, len(x0)))), (what, float(np.abs(fd - sb.gather32(rec, H, len(x0))).max()))
-    assert np.array_equal(_bits(pd), _bits(pd32)), what
+    assert np.array_equal(hs.bits(fd), hs.bits(sb.gather32(rec, H, len(x0)))), (what, float(np.abs(fd - sb.gather32(rec, H, len(x0))).max()))
+    assert np.array_equal(hs.bits(pd), hs.bits(pd32)), what
     ch = np.zeros(len(H), int) if cloth_of_hinge is None else cloth_of_hinge
     for c in range(n_cloths):
         assert power[c] == _sum_in_order(pw32[ch == c]) and power[c] >= 0.0, (what, c)
@@ -95,10 +90,10 @@ def _check(g, x0, v0, H, kc, psibar, bkc, what, cloth_of_hinge=None, n_cloths=1)
 @pytest.mark.parametrize("name,st", sb.CASES)
 def test_forces_psidot_and_power_against_float64_and_the_restatement(name, st):
     from drake_amd import SHELL_DAMPING_DTYPE
-    A = _A()
+    A = hs.ARR()
     X, T, rest = sb.mesh(name)
     H = sb.hinges(T)
-    a, b = _engine([(X, T)]), _engine([(X, T)])
+    a, b = hs.engine([(X, T)]), hs.engine([(X, T)])
     a.set_shell_bending([sb.K], rest)
     if len(H) == 0:                    # (no hinge: shell bending is not in force)
         _refused(lambda: a.set_shell_damping([sd.BETA]), says="shell bending")
@@ -117,19 +112,19 @@ def test_forces_psidot_and_power_against_float64_and_the_restatement(name, st):
     el32 = sb.gather32(sb.hinges32(x0, H, kc, psibar)[0], H, len(x0))
     for kind in sd.VELOCITIES:
         v0 = sd.velocity(name, st, kind)
-        _upload(a, x0, v0)
+        hs.upload(a, x0, v0)
         fd = _check(a, x0, v0, H, kc, psibar, bkc, f"{name} {st} {kind}")
         if kind in ("zero", "common"):
             assert not fd.any()
-        assert np.array_equal(_bits(a.shell_forces()), _bits(el32))            # (the elastic part alone, whatever v)
+        assert np.array_equal(hs.bits(a.shell_forces()), hs.bits(el32))            # (the elastic part alone, whatever v)
         if st == "collinear":          # (its face of zero area: the membrane model's forces are not finite there)
             continue
         out = []
         for g in (a, b):
-            _upload(g, x0, v0)
+            hs.upload(g, x0, v0)
             g.rebuild_mapping(False)
             g.calc_fem_state_and_force(dt)
-            out.append(_vertices(g, A.FORCES).astype(np.float64))
+            out.append(hs.vertices(g, A.FORCES).astype(np.float64))
         full = sb.gather32(sd.hinges32(x0, v0, H, kc, psibar, bkc)[0], H, len(x0)).astype(np.float64)
         err = np.abs(out[0] - (out[1] + full))
         assert (err <= U * np.abs(out[0])).all(), (name, st, kind, float((err / np.maximum(np.abs(out[0]), 1e-300)).max()))
@@ -144,27 +139,27 @@ def test_strips_around_a_wave_and_a_block(n_faces):
     X, T, x = cr.strip(n_faces)
     H = sb.hinges(T)
     assert len(H) == n_faces - 1
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     g.set_shell_bending([sb.K])
     g.set_shell_damping([sd.BETA])
     ids, kc, psibar = g.shell_hinges()
     bkc = _bkc(sd.BETA, sb.K, sb.cbar64(X.astype(np.float64), H))
     v = np.random.default_rng(n_faces).normal(size=x.shape).astype(F)
-    _upload(g, x, v)
+    hs.upload(g, x, v)
     fd = _check(g, x, v, H, kc, psibar, bkc, f"strip of {n_faces} faces")
     assert fd[H[-1]].any() and fd[H[0]].any()             # (the last hinge of the last wave wrote its records)
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(min(1e-5, 0.5 * g.shell_max_stable_dt()))
-    assert np.isfinite(_vertices(g, _A().FORCES)).all() and g.stats()["error_flags"] == 0
+    assert np.isfinite(hs.vertices(g, hs.ARR().FORCES)).all() and g.stats()["error_flags"] == 0
     g.destroy()
 
 
 # ---- 3 -------------------------------------------------------------------------------------------------------------------
 def test_three_cloths_damped_undamped_and_without_shell():
-    A = _A()
+    A = hs.ARR()
     cloths, _, x = cr.three_cloths(0.8)
     first = np.cumsum([0] + [len(X) for X, _ in cloths])
-    a, b = _engine(cloths), _engine(cloths)
+    a, b = hs.engine(cloths), hs.engine(cloths)
     for g in (a, b):
         g.set_shell_bending([sb.K, sb.K, 0.0])
     a.set_shell_damping([sd.BETA, 0.0, sd.BETA])          # (beta > 0 on the cloth without hinges: accepted, does nothing)
@@ -177,7 +172,7 @@ def test_three_cloths_damped_undamped_and_without_shell():
     bkc = _bkc(sd.BETA, sb.K, sb.cbar64(Xall, H))
     bkc[ch == 1] = 0.0
     v = np.random.default_rng(9).normal(size=x.shape).astype(F)
-    _upload(a, x, v)
+    hs.upload(a, x, v)
     fd = _check(a, x, v, H, kc, psibar, bkc, "three cloths", ch, 3)
     power, pd = a.shell_damping_state()
     assert fd[first[0]:first[1]].any() and not fd[first[1]:].any()
@@ -185,16 +180,16 @@ def test_three_cloths_damped_undamped_and_without_shell():
     dt = min(1e-5, 0.5 * a.shell_max_stable_dt())
     out = []
     for g in (a, b):
-        _upload(g, x, v)
+        hs.upload(g, x, v)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(dt)
-        out.append(_vertices(g, A.FORCES))
+        out.append(hs.vertices(g, A.FORCES))
     # the undamped shell cloth and the cloth without shell bending: the twin's bits; the damped one differs
-    assert np.array_equal(_bits(out[0][first[1]:]), _bits(out[1][first[1]:]))
-    assert not np.array_equal(_bits(out[0][:first[1]]), _bits(out[1][:first[1]]))
+    assert np.array_equal(hs.bits(out[0][first[1]:]), hs.bits(out[1][first[1]:]))
+    assert not np.array_equal(hs.bits(out[0][:first[1]]), hs.bits(out[1][:first[1]]))
     assert not b.shell_damping_forces().any() and not b.get_shell_damping()["beta"].any()
     pb, pdb = b.shell_damping_state()
-    assert not pb.any() and np.array_equal(_bits(pdb), _bits(pd))                 # (psidot without a damper: the same bits)
+    assert not pb.any() and np.array_equal(hs.bits(pdb), hs.bits(pd))                 # (psidot without a damper: the same bits)
     for g in (a, b):
         assert g.stats()["error_flags"] == 0
         g.destroy()
@@ -203,26 +198,26 @@ def test_three_cloths_damped_undamped_and_without_shell():
 # ---- 4 -------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("deterministic", [True, False])
 def test_particle_order_and_determinism_mode(deterministic):
-    cloths, rest, H, ch = tsb._scene()
-    g = _engine(cloths, deterministic=deterministic)
+    cloths, rest, H, ch = ss.scene()
+    g = hs.engine(cloths, deterministic=deterministic)
     g.set_shell_bending([sb.K, sb.K], rest)
     g.set_shell_damping([sd.BETA, 0.5 * sd.BETA])
     x0 = bd.perturbed(rest, seed=7).astype(F)
     v0 = np.random.default_rng(4).normal(size=x0.shape).astype(F)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     f0, s0 = g.shell_damping_forces(), g.shell_damping_state()
     assert f0.any()
     before = g.stats()["rebuilds"]
-    _upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], F), np.zeros_like(v0))
+    hs.upload(g, x0 + np.array([5.0 / 64, 0.0, 0.0], F), np.zeros_like(v0))
     g.run_substeps(2, 1e-5, -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
     for sort in (False, True):
         if sort:
             g.rebuild_mapping(True)
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         f1, s1 = g.shell_damping_forces(), g.shell_damping_state()
-        assert np.array_equal(_bits(f1), _bits(f0)) and np.array_equal(_bits(s1[0]), _bits(s0[0])) and np.array_equal(_bits(s1[1]), _bits(s0[1]))
+        assert np.array_equal(hs.bits(f1), hs.bits(f0)) and np.array_equal(hs.bits(s1[0]), hs.bits(s0[0])) and np.array_equal(hs.bits(s1[1]), hs.bits(s0[1]))
     g.destroy()
 
 
@@ -296,7 +291,7 @@ def test_coupled_equals_the_seven_calls_through_skipped_substeps():
 def test_creases_yield_on_the_elastic_moment_alone(beta):
     from drake_amd import CREASE_DTYPE
     cloths, rows, x = cr.three_cloths()
-    g = _engine(cloths)
+    g = hs.engine(cloths)
     g.set_shell_bending([sb.K] * 3)
     t = np.zeros(3, CREASE_DTYPE)
     for c, (ya, eta, ma) in enumerate(rows):
@@ -304,18 +299,18 @@ def test_creases_yield_on_the_elastic_moment_alone(beta):
     g.set_creases(t)
     g.set_shell_damping([beta] * 3)
     v = np.random.default_rng(3).normal(size=x.shape).astype(F)
-    _upload(g, x, v)
+    hs.upload(g, x, v)
     psi, dpsi, nxt = g.crease_measure()
     before = g.crease_state()[0]
     g.rebuild_mapping(False)
     g.calc_fem_state_and_force(min(1e-5, 0.5 * g.shell_max_stable_dt()))
     after = g.crease_state()[0]
-    assert np.array_equal(_bits(after), _bits(nxt)) and (_bits(after) != _bits(before)).any()
+    assert np.array_equal(hs.bits(after), hs.bits(nxt)) and (hs.bits(after) != hs.bits(before)).any()
     # whatever beta: the same psibar as the undamped engine leaves (computed once, shared)
     key = "psibar"
     if key not in _CREASED:
-        _CREASED[key] = _bits(after).copy()
-    assert np.array_equal(_bits(after), _CREASED[key])
+        _CREASED[key] = hs.bits(after).copy()
+    assert np.array_equal(hs.bits(after), _CREASED[key])
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -328,7 +323,7 @@ def test_a_cut_hinge_is_not_damped_and_acts_again_when_restored():
     from drake_amd import TEAR_CUTS_HINGES
     X, T, rest = sb.mesh("book")
     H = sb.hinges(T)
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     g.set_tear_coupling(TEAR_CUTS_HINGES)
     g.set_shell_bending([sb.K], rest)
     g.set_shell_damping([sd.BETA])
@@ -342,20 +337,20 @@ def test_a_cut_hinge_is_not_damped_and_acts_again_when_restored():
     assert cut.any() and not cut.all()
     for seed, scale in ((1, 1.0), (2, 1e3)):
         v0 = (scale * np.random.default_rng(seed).normal(size=x0.shape)).astype(F)
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         whole = g.shell_damping_forces()
         g.set_torn_faces(torn)
         assert np.array_equal(g.shell_cut_hinges()[0], cut)
         rec = sd.hinges32(x0, v0, H, kc, psibar, bkc, elastic=False)[0]
         rec[cut] = 0.0                                       # (a cut hinge's four records are exact zeros)
         fd = g.shell_damping_forces()
-        assert np.array_equal(_bits(fd), _bits(sb.gather32(rec, H, len(x0)))) and not np.array_equal(_bits(fd), _bits(whole))
+        assert np.array_equal(hs.bits(fd), hs.bits(sb.gather32(rec, H, len(x0)))) and not np.array_equal(hs.bits(fd), hs.bits(whole))
         power, pd = g.shell_damping_state()
         assert not pd[cut].any() and pd[~cut].any()
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(min(1e-5, 0.5 * g.shell_max_stable_dt()))
         g.set_torn_faces(np.zeros(len(T), np.uint8))
-        assert np.array_equal(_bits(g.shell_damping_forces()), _bits(whole))
+        assert np.array_equal(hs.bits(g.shell_damping_forces()), hs.bits(whole))
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -364,26 +359,26 @@ def test_a_cut_hinge_is_not_damped_and_acts_again_when_restored():
 def test_off_means_off():
     """40 deterministic substeps through re-sorts: never called == called with zeros == set and cleared, to the bit, with
     the same guard and the same number of re-sort check launches"""
-    cloths, rest, H, ch, x0, v0 = tsb._flying()
-    es = [_engine(cloths) for _ in range(4)]
-    k = tsb._scale_k(es[0], lambda k: es[0].set_shell_bending([k, k], rest), tl.DT)
+    cloths, rest, H, ch, x0, v0 = ss.flying()
+    es = [hs.engine(cloths) for _ in range(4)]
+    k = ss.scale_k(es[0], lambda k: es[0].set_shell_bending([k, k], rest), tl.DT)
     for g in es[1:]:
         g.set_shell_bending([k, k], rest)
     lim = es[0].shell_max_stable_dt()
     es[1].set_shell_damping([0.0, 0.0])
     es[2].set_shell_damping([0.5 * tl.DT, 0.25 * tl.DT])
     assert es[2].shell_max_stable_dt() < lim
-    _upload(es[2], bd.perturbed(rest, seed=7).astype(F), v0)
+    hs.upload(es[2], bd.perturbed(rest, seed=7).astype(F), v0)
     assert es[2].shell_damping_forces().any()
     es[2].set_shell_damping([])
     es[3].set_shell_damping([0.5 * tl.DT, 0.0])
     es[3].set_shell_damping([0.0, 0.0])
     for g in es:
         assert not g.get_shell_damping()["beta"].any() and len(g.get_shell_damping()) == 2
-        assert _bits(np.array([g.shell_max_stable_dt()], F))[0] == _bits(np.array([lim], F))[0]
+        assert hs.bits(np.array([g.shell_max_stable_dt()], F))[0] == hs.bits(np.array([lim], F))[0]
     before = es[0].stats()["rebuilds"]
     for g in es:
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         assert not g.shell_damping_forces().any() and not g.shell_damping_state()[0].any()
         for _ in range(4):
             g.run_substeps(10, tl.DT, -1)
@@ -391,22 +386,22 @@ def test_off_means_off():
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 2
     for g in es[1:]:
-        tsb._same_bits(tsb._state(es[0]), tsb._state(g), "the damper off")
+        hs.same_bits(hs.state(es[0]), hs.state(g), "the damper off")
         assert es[0].stats()["resort_checks"] == g.stats()["resort_checks"]
-        assert np.array_equal(_bits(es[0].shell_state()[0]), _bits(g.shell_state()[0]))
+        assert np.array_equal(hs.bits(es[0].shell_state()[0]), hs.bits(g.shell_state()[0]))
     for g in es:
         g.destroy()
 
 
 def test_set_get_replace_and_the_table_goes_with_the_hinge_table():
     from drake_amd import SHELL_DAMPING_DTYPE
-    cloths, rest, H, ch = tsb._scene()
-    g = _engine(cloths)
+    cloths, rest, H, ch = ss.scene()
+    g = hs.engine(cloths)
     g.set_shell_bending([sb.K, sb.K], rest)
     lim = g.shell_max_stable_dt()
     x0 = bd.perturbed(rest, seed=7).astype(F)
     v0 = np.random.default_rng(4).normal(size=x0.shape).astype(F)
-    _upload(g, x0, v0)
+    hs.upload(g, x0, v0)
     g.set_shell_damping([sd.BETA, 0.0])
     f1, l1 = g.shell_damping_forces(), g.shell_max_stable_dt()
     t = np.zeros(2, SHELL_DAMPING_DTYPE)
@@ -418,12 +413,12 @@ def test_set_get_replace_and_the_table_goes_with_the_hinge_table():
     f2, l2 = g.shell_damping_forces(), g.shell_max_stable_dt()
     assert f2[n0:].any() and l2 < l1 and np.abs(f2[:n0]).max() > np.abs(f1[:n0]).max()
     g.set_shell_damping(t)
-    assert np.array_equal(_bits(g.shell_damping_forces()), _bits(f1)) and g.shell_max_stable_dt() == l1
+    assert np.array_equal(hs.bits(g.shell_damping_forces()), hs.bits(f1)) and g.shell_max_stable_dt() == l1
     # mpm_set_shell_bending replaces the hinge table: the damper's table goes with it
     g.set_shell_bending([sb.K, sb.K], rest)
     assert not g.get_shell_damping()["beta"].any() and g.shell_max_stable_dt() == lim and not g.shell_damping_forces().any()
     g.set_shell_damping(t)
-    assert np.array_equal(_bits(g.shell_damping_forces()), _bits(f1))
+    assert np.array_equal(hs.bits(g.shell_damping_forces()), hs.bits(f1))
     g.set_shell_bending([])
     assert not g.get_shell_damping()["beta"].any() and g.shell_max_stable_dt() == np.inf
     assert g.stats()["error_flags"] == 0
@@ -433,17 +428,17 @@ def test_set_get_replace_and_the_table_goes_with_the_hinge_table():
 # ---- 9 -------------------------------------------------------------------------------------------------------------------
 def test_the_guard_and_the_refusals():
     from drake_amd import SHELL_DAMPING_DTYPE, GpuMpm
-    cloths, rest, H, ch = tsb._scene()
+    cloths, rest, H, ch = ss.scene()
     g0 = GpuMpm(6)
     for Xc, Tc in cloths:
         g0.add_qr_cloth(Xc, np.zeros_like(Xc), Tc)
     _refused(lambda: g0.set_shell_damping([sd.BETA, sd.BETA]), says="finalize")
     g0.destroy()
 
-    g = _engine(cloths, bodies=1)
+    g = hs.engine(cloths, bodies=1)
     _refused(lambda: g.set_shell_damping([sd.BETA, sd.BETA]), says="shell bending")
     _refused(lambda: g.set_shell_damping([]), says="shell bending")
-    k = tsb._scale_k(g, lambda k: g.set_shell_bending([k, k], rest), tl.DT, share=0.5)
+    k = ss.scale_k(g, lambda k: g.set_shell_bending([k, k], rest), tl.DT, share=0.5)
     lim = g.shell_max_stable_dt()
     betas = np.array([0.5 * tl.DT, 2.0 * tl.DT], F)
     g.set_shell_damping(betas)
@@ -451,7 +446,7 @@ def test_the_guard_and_the_refusals():
     # the value: the float64 restatement on the engine's own kc and masses, rounded down.  The engine's doubles are formed
     # in another order (1e-15), so the two floats agree or, where the bound lies that close to a float, are neighbours
     mat = GpuMpm.default_material()
-    mass = np.abs(_vertices(g, _A().VOLUMES).reshape(-1)).astype(F) * F(mat.density)
+    mass = np.abs(hs.vertices(g, hs.ARR().VOLUMES).reshape(-1)).astype(F) * F(mat.density)
     ids, kc, psibar = g.shell_hinges()
     rates = sd.row_rates(rest.astype(np.float64), H, kc, mass.astype(np.float64))
     n0 = len(cloths[0][0])
@@ -466,13 +461,13 @@ def test_the_guard_and_the_refusals():
     for call in (lambda: g.run_substeps(2, above, -1), lambda: g.substep(above, -1), lambda: g.particle_to_grid(above)):
         _refused(call, says=("shell bending", "mpm_shell_max_stable_dt", "dt or the stiffness"))
     assert g.stats()["substeps"] == before
-    _upload(g, rest, np.zeros_like(rest))
+    hs.upload(g, rest, np.zeros_like(rest))
     g.run_substeps(1, got, -1)
     g.gpu_sync()
     assert g.stats()["substeps"] == before + 1 and g.stats()["error_flags"] == 0
     # refusals, one by one: the table and the guard stay
     x0 = bd.perturbed(rest, seed=7).astype(F)
-    _upload(g, x0, np.random.default_rng(4).normal(size=x0.shape).astype(F))
+    hs.upload(g, x0, np.random.default_rng(4).normal(size=x0.shape).astype(F))
     f_before = g.shell_damping_forces()
     bad_reserved = np.zeros(2, SHELL_DAMPING_DTYPE)
     bad_reserved["beta"], bad_reserved["reserved"] = sd.BETA, (0.0, 1.0)
@@ -483,7 +478,7 @@ def test_the_guard_and_the_refusals():
                        (lambda: g.set_shell_damping(bad_reserved), ("cloth 1", "reserved"))):
         _refused(call, says=says)
         assert np.array_equal(g.get_shell_damping(), good) and g.shell_max_stable_dt() == got
-        assert np.array_equal(_bits(g.shell_damping_forces()), _bits(f_before))
+        assert np.array_equal(hs.bits(g.shell_damping_forces()), hs.bits(f_before))
     assert g.lib.mpm_set_shell_damping(g.h, 2, None) == -1
     # a partitioned engine is refused through shell bending: neither call goes through there
     g.set_shell_bending([])
@@ -509,14 +504,14 @@ def test_a_bent_sheet_loses_energy_faster_the_larger_beta():
     and lower still with four times the beta; the dissipated power is never negative"""
     X, T = bd.sheet(9, 9)
     x0 = sb.fold(X, 0.8).astype(F)
-    es = [_engine([(X, T)], material=dict(gravity=0.0)) for _ in range(3)]
-    k = tsb._scale_k(es[0], lambda k: es[0].set_shell_bending([k]), tl.DT, share=0.1)
+    es = [hs.engine([(X, T)], material=dict(gravity=0.0)) for _ in range(3)]
+    k = ss.scale_k(es[0], lambda k: es[0].set_shell_bending([k]), tl.DT, share=0.1)
     traces = []
     for g, beta in zip(es, (0.0, 10 * tl.DT, 40 * tl.DT)):
         g.set_shell_bending([k])
         g.set_shell_damping([beta])
         assert tl.DT <= g.shell_max_stable_dt()
-        _upload(g, x0)
+        hs.upload(g, x0)
         trace = [_total(g)]
         for _ in range(10):
             g.run_substeps(30, tl.DT, -1)
@@ -543,14 +538,14 @@ def test_a_struck_tube_settles_while_its_undamped_twin_rings():
     X, T = sb.tube(around=12, along=6, radius=4 * sb.H0, h=2 * sb.H0)      # (about one vertex per grid cell)
     a = np.arctan2(X[:, 2] - sb.CENTER[2], X[:, 0] - sb.CENTER[0]).astype(np.float64)
     v0 = (0.05 * np.cos(2 * a))[:, None] * np.stack([np.cos(a), np.zeros_like(a), np.sin(a)], axis=1)
-    es = [_engine([(X, T)], material=dict(gravity=0.0, gamma=0.0)) for _ in range(2)]
-    k = tsb._scale_k(es[0], lambda k: es[0].set_shell_bending([k]), tl.DT, share=SHARE)
+    es = [hs.engine([(X, T)], material=dict(gravity=0.0, gamma=0.0)) for _ in range(2)]
+    k = ss.scale_k(es[0], lambda k: es[0].set_shell_bending([k]), tl.DT, share=SHARE)
     out = []
     for g, beta in zip(es, (0.0, STRONG * tl.DT)):
         g.set_shell_bending([k])
         g.set_shell_damping([beta])
         assert tl.DT <= g.shell_max_stable_dt()
-        _upload(g, X, v0.astype(F))
+        hs.upload(g, X, v0.astype(F))
         trace = []
         for _ in range(24):
             g.run_substeps(5, tl.DT, -1)

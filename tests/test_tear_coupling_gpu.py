@@ -18,6 +18,7 @@ import pytest
 
 from tests import bending as bd
 from tests import creases as cr
+from tests import harness as hs
 from tests import pressure as pr
 from tests import shell_bending as sb
 from tests import tear_coupling as tc
@@ -31,51 +32,6 @@ DT = 2e-4
 TINY_DT = 1e-5
 MESHES = ("tube", "book", "icosphere1", "icosphere2", "jittered")
 STATES = ("perturbed", "affine", "rigid")
-
-
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _engine(cloths, bits=6, deterministic=True, material=None, bodies=0):
-    """cloths: [(X (n, 3) float32 positions as added, T)]"""
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    g = GpuMpm(bits, mat)
-    g.set_deterministic(deterministic)
-    for X, T in cloths:
-        g.add_qr_cloth(X, np.zeros_like(X), np.asarray(T, np.int32).reshape(-1))
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([np.asarray(T).reshape(-1, 3) + o
-                             for (X, T), o in zip(cloths, np.cumsum([0] + [len(X) for X, _ in cloths[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, F)
-    v = np.zeros_like(x) if v is None else np.broadcast_to(np.asarray(v, F), x.shape)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(F)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), F), None, None)
-
-
-def _vertices(g, which):
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros((g.n_verts,) + a.shape[1:], a.dtype)
-    out[pids[pids >= g.n_faces] - g.n_faces] = a[pids >= g.n_faces]
-    return out
-
-
-def _bits(a):
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype.itemsize == 4 else a.view(np.uint64)
 
 
 def _fem(g, dt=TINY_DT):
@@ -126,7 +82,7 @@ def test_mode_default_set_get_and_refusals():
     refused(lambda: g0.set_tear_coupling(1), says="finalize")
     g0.destroy()
 
-    g = _engine([(Xs, Ts), (Xi, Ti)], bodies=1)
+    g = hs.engine([(Xs, Ts), (Xi, Ti)], bodies=1)
     nf = g.n_faces
     gas1 = _gas({1: pr.gas_row("icosphere")}, 2)
     const1 = _gas({1: (pr.CONSTANT, 10.0, 0, 0, 0)}, 2)
@@ -249,11 +205,11 @@ def _check_cut_statics(g, x32, H, FAB, torn, what, cloth_of_hinge=None, n_cloths
 def test_cut_hinges_statics_every_pattern(name, st):
     X, T, rest = sb.mesh(name)
     H, FAB = sb.hinges(T), tc.hinge_faces(T)
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     g.set_tear_coupling(tc.CUTS_HINGES)
     g.set_shell_bending([sb.K], rest)
     x0 = sb.state(name, st)
-    _upload(g, x0)
+    hs.upload(g, x0)
     worst = 0.0
     f_none = None
     for pat in tc.PATTERNS:
@@ -287,11 +243,11 @@ def test_cut_counts_per_cloth_on_two_cloths():
         v0, f0 = v0 + len(X), f0 + len(T)
     H, FAB = np.concatenate(Hs), np.concatenate(FABs)
     ch = np.concatenate([np.full(len(h), c) for c, h in enumerate(Hs)])
-    g = _engine([(X, T) for X, T, _ in cloths])
+    g = hs.engine([(X, T) for X, T, _ in cloths])
     g.set_tear_coupling(3)
     g.set_shell_bending([sb.K, sb.K], np.concatenate([r for _, _, r in cloths]))
     x0 = np.concatenate([bd.perturbed(r, seed=3 + c) for c, (_, _, r) in enumerate(cloths)]).astype(F)
-    _upload(g, x0)
+    hs.upload(g, x0)
     n0 = len(cloths[0][1])
     torn1, _ = tc.pattern("a_b_both", cloths[1][1], len(cloths[1][0]))
     torn = np.concatenate([np.zeros(n0, bool), torn1])
@@ -323,21 +279,21 @@ def test_strips_around_a_wave_and_a_block(n_faces):
             torn[b] = True
     want = tc.cut(torn, FAB)
     assert want[-1] and not want[0] and (n_faces < 66 or (want[63] and want[64])) and (n_faces < 258 or (want[255] and want[256]))
-    g = _engine([(X, T)])
+    g = hs.engine([(X, T)])
     g.set_tear_coupling(1)
     g.set_shell_bending([sb.K])
     rows = [(cr.YIELD_ANGLES[0], 0.0, 0.0)]
     g.set_creases(_crease_table(rows))
-    _upload(g, x)
+    hs.upload(g, x)
     g.set_torn_faces(torn)
     _check_cut_statics(g, x, H, FAB, torn, f"strip of {n_faces} faces")
     before = g.crease_state()[0]
     psi_m, dpsi_m, next_m = g.crease_measure()
-    assert np.array_equal(_bits(next_m[want]), _bits(before[want])) and not psi_m[want].any() and not dpsi_m[want].any()
+    assert np.array_equal(hs.bits(next_m[want]), hs.bits(before[want])) and not psi_m[want].any() and not dpsi_m[want].any()
     _fem(g)
     after = g.crease_state()[0]
-    assert np.array_equal(_bits(after), _bits(next_m))
-    assert np.array_equal(_bits(after[want]), _bits(before[want])) and (_bits(after) != _bits(before))[~want].any()
+    assert np.array_equal(hs.bits(after), hs.bits(next_m))
+    assert np.array_equal(hs.bits(after[want]), hs.bits(before[want])) and (hs.bits(after) != hs.bits(before))[~want].any()
     assert g.stats()["error_flags"] == 0
     g.destroy()
 
@@ -346,7 +302,7 @@ def test_strips_around_a_wave_and_a_block(n_faces):
 def _decided_state(s, g):
     """the `uniaxial` state of tests/tearing.py, lifted out of its plane by a fifth of a spacing at random (a flat sheet has
     no shell force), at the first scale along x about 1 at which float64 decides every face (tearing.py's rule, cap 0)"""
-    A = _A()
+    A = hs.ARR()
     nf = g.n_faces
     dm = g.download(A.DM_INVERSES).reshape(nf, 4)[:, [0, 1, 3]].copy()
     base = tr.state("uniaxial", s).astype(np.float64)
@@ -364,9 +320,9 @@ def _decided_state(s, g):
 
 
 def test_a_face_that_fails_cuts_its_hinges_in_the_same_substep():
-    A = _A()
+    A = hs.ARR()
     s = tr.scene("quad12")
-    a, b = _engine(s["meshes"]), _engine(s["meshes"])
+    a, b = hs.engine(s["meshes"]), hs.engine(s["meshes"])
     x, ref = _decided_state(s, a)
     T = s["T"]
     H, FAB = sb.hinges(T), tc.hinge_faces(T)
@@ -377,12 +333,12 @@ def test_a_face_that_fails_cuts_its_hinges_in_the_same_substep():
     out = []
     for g in (a, b):
         g.set_tearing(s["limits"])
-        _upload(g, x)
+        hs.upload(g, x)
         _fem(g)
-        out.append((g.tear_state()[0], _vertices(g, A.FORCES).copy(), g.shell_forces(), g.shell_cut_hinges()[0]))
+        out.append((g.tear_state()[0], hs.vertices(g, A.FORCES).copy(), g.shell_forces(), g.shell_cut_hinges()[0]))
     assert np.array_equal(out[0][0], ref) and np.array_equal(out[1][0], ref)
-    assert np.array_equal(_bits(out[0][1]), _bits(out[1][1])), int((_bits(out[0][1]) != _bits(out[1][1])).sum())
-    assert np.array_equal(_bits(out[0][2]), _bits(out[1][2]))
+    assert np.array_equal(hs.bits(out[0][1]), hs.bits(out[1][1])), int((hs.bits(out[0][1]) != hs.bits(out[1][1])).sum())
+    assert np.array_equal(hs.bits(out[0][2]), hs.bits(out[1][2]))
     cut = tc.cut(ref, FAB)
     assert np.array_equal(out[0][3], cut) and cut.any() and not cut.all()
     # the shell part is there on the vertices without a cut hinge, and the total force holds it
@@ -391,9 +347,9 @@ def test_a_face_that_fails_cuts_its_hinges_in_the_same_substep():
         free[H[cut, j]] = False
     assert free.any() and out[0][2][free].any()
     a.set_shell_bending([])
-    _upload(a, x)
+    hs.upload(a, x)
     _fem(a)
-    assert not np.array_equal(_vertices(a, A.FORCES)[free], out[0][1][free])
+    assert not np.array_equal(hs.vertices(a, A.FORCES)[free], out[0][1][free])
     for g in (a, b):
         assert g.stats()["error_flags"] == 0
         g.destroy()
@@ -403,14 +359,14 @@ def test_a_face_that_fails_cuts_its_hinges_in_the_same_substep():
 def test_restore_brings_the_hinges_back_with_their_psibar():
     X, T, rest = sb.mesh("book")
     H, FAB = sb.hinges(T), tc.hinge_faces(T)
-    a, b = _engine([(X, T)]), _engine([(X, T)])
+    a, b = hs.engine([(X, T)]), hs.engine([(X, T)])
     x = sb.state("book", "perturbed")
     pb = (0.3 * np.random.default_rng(9).uniform(-1, 1, len(H))).astype(F)
     for g in (a, b):
         g.set_tear_coupling(1)
         g.set_shell_bending([sb.K], rest)
         g.set_crease_state(pb)
-        _upload(g, x)
+        hs.upload(g, x)
     torn, _ = tc.pattern("vertex_all", T, len(X))
     a.set_torn_faces(torn)
     cut_forces = a.shell_forces()
@@ -419,10 +375,10 @@ def test_restore_brings_the_hinges_back_with_their_psibar():
     assert np.array_equal(a.shell_cut_hinges()[0], tc.cut(torn, FAB))
     a.set_torn_faces(np.zeros(len(T), bool))
     assert not a.shell_cut_hinges()[0].any() and not a.shell_cut_hinges()[1].any()
-    assert np.array_equal(_bits(a.crease_state()[0]), _bits(pb))
+    assert np.array_equal(hs.bits(a.crease_state()[0]), hs.bits(pb))
     fa, fb = a.shell_forces(), b.shell_forces()
-    assert np.array_equal(_bits(fa), _bits(fb)) and not np.array_equal(fa, cut_forces)
-    assert np.array_equal(_bits(a.shell_state()[1]), _bits(b.shell_state()[1])) and a.shell_state()[2] == b.shell_state()[2]
+    assert np.array_equal(hs.bits(fa), hs.bits(fb)) and not np.array_equal(fa, cut_forces)
+    assert np.array_equal(hs.bits(a.shell_state()[1]), hs.bits(b.shell_state()[1])) and a.shell_state()[2] == b.shell_state()[2]
     for g in (a, b):
         assert g.stats()["error_flags"] == 0
         g.destroy()
@@ -431,7 +387,7 @@ def test_restore_brings_the_hinges_back_with_their_psibar():
 # ---- 6 -------------------------------------------------------------------------------------------------------------------
 def test_creases_a_cut_hinge_keeps_its_psibar_and_an_uncut_one_is_unmoved_by_the_cuts():
     cloths, rows, x = cr.three_cloths()
-    a, b = _engine(cloths), _engine(cloths)
+    a, b = hs.engine(cloths), hs.engine(cloths)
     nfc = len(cloths[0][1])
     torn = np.zeros(3 * nfc, bool)
     torn[np.random.default_rng(2).choice(3 * nfc, 3 * nfc // 4, replace=False)[::3]] = True          # a quarter of the faces
@@ -442,7 +398,7 @@ def test_creases_a_cut_hinge_keeps_its_psibar_and_an_uncut_one_is_unmoved_by_the
         g.set_creases(_crease_table(rows))
         if g is a:
             g.set_torn_faces(torn)
-        _upload(g, x)
+        hs.upload(g, x)
         before = g.crease_state()[0]
         measure = g.crease_measure()
         _fem(g)
@@ -451,14 +407,14 @@ def test_creases_a_cut_hinge_keeps_its_psibar_and_an_uncut_one_is_unmoved_by_the
     cut = tc.cut(torn, FAB)
     assert np.array_equal(a.shell_cut_hinges()[0], cut) and cut.any() and not cut.all()
     (before_a, after_a, m_a), (before_b, after_b, m_b) = out
-    assert np.array_equal(_bits(before_a), _bits(before_b))
-    moved_b = _bits(after_b) != _bits(before_b)
+    assert np.array_equal(hs.bits(before_a), hs.bits(before_b))
+    moved_b = hs.bits(after_b) != hs.bits(before_b)
     assert moved_b[cut].any() and moved_b[~cut].any(), "no hinge yields on either side of the cut"
-    assert np.array_equal(_bits(after_a[~cut]), _bits(after_b[~cut]))          # (Jacobi, hinge by hinge)
-    assert np.array_equal(_bits(after_a[cut]), _bits(before_a[cut]))
-    assert np.array_equal(_bits(m_a[2][cut]), _bits(before_a[cut])) and np.array_equal(_bits(m_a[2]), _bits(after_a))
+    assert np.array_equal(hs.bits(after_a[~cut]), hs.bits(after_b[~cut]))          # (Jacobi, hinge by hinge)
+    assert np.array_equal(hs.bits(after_a[cut]), hs.bits(before_a[cut]))
+    assert np.array_equal(hs.bits(m_a[2][cut]), hs.bits(before_a[cut])) and np.array_equal(hs.bits(m_a[2]), hs.bits(after_a))
     assert not m_a[0][cut].any() and not m_a[1][cut].any()
-    assert np.array_equal(_bits(m_a[0][~cut]), _bits(m_b[0][~cut])) and np.array_equal(_bits(m_a[1][~cut]), _bits(m_b[1][~cut]))
+    assert np.array_equal(hs.bits(m_a[0][~cut]), hs.bits(m_b[0][~cut])) and np.array_equal(hs.bits(m_a[1][~cut]), hs.bits(m_b[1][~cut]))
     for g in (a, b):
         assert g.stats()["error_flags"] == 0
         g.destroy()
@@ -469,7 +425,7 @@ def test_particle_order():
     """tests/rest_shape.py's construction: one engine in Finalize's order, one re-sorted while every particle had a cell to
     itself, one in default mode; the same stretched and bent state by original id: the same flags, cut hinges and forces"""
     from tests import rest_shape as rs
-    A = _A()
+    A = hs.ARR()
     pos, idx = rs.sheet()
     wide = rs.spread(idx)
     assert rs.one_per_cell(wide, idx)
@@ -477,8 +433,8 @@ def test_particle_order():
     x = tr._uniaxial(pos.astype(np.float64))
     x[:, 2] += 0.25 * (0.2 / rs.SHEET_RES) * np.random.default_rng(5).uniform(-1, 1, len(x))
     x = x.astype(F)
-    es = [_engine([(pos, idx)]), _engine([(pos, idx)]), _engine([(pos, idx)], deterministic=False)]
-    _upload(es[1], wide)
+    es = [hs.engine([(pos, idx)]), hs.engine([(pos, idx)]), hs.engine([(pos, idx)], deterministic=False)]
+    hs.upload(es[1], wide)
     es[1].rebuild_mapping(True)
     assert not np.array_equal(es[0].download(A.PIDS), es[1].download(A.PIDS)), "the two engines hold the same particle order"
     out = []
@@ -486,10 +442,10 @@ def test_particle_order():
         g.set_tear_coupling(1)
         g.set_shell_bending([sb.K])
         g.set_tearing([tr.LIMIT])
-        _upload(g, x)
+        hs.upload(g, x)
         g.calc_fem_state_and_force(TINY_DT)
         torn = g.tear_state()[0]
-        out.append((torn, g.shell_cut_hinges()[0], _bits(_vertices(g, A.FORCES)), _bits(g.shell_forces())))
+        out.append((torn, g.shell_cut_hinges()[0], hs.bits(hs.vertices(g, A.FORCES)), hs.bits(g.shell_forces())))
     assert not np.array_equal(es[0].download(A.PIDS), es[1].download(A.PIDS))
     torn = out[0][0]
     assert torn.any() and not torn.all() and np.array_equal(out[0][1], tc.cut(torn, FAB)) and out[0][3].any()
@@ -626,15 +582,15 @@ def test_coupled_equals_the_seven_calls():
 
 # ---- 9 -------------------------------------------------------------------------------------------------------------------
 def _trajectory_state(g):
-    A = _A()
+    A = hs.ARR()
     g.gpu_sync()
-    st = dict(x=_bits(g.download(A.POSITIONS)), v=_bits(g.download(A.VELOCITIES)), C=_bits(g.download(A.AFFINE)),
-              F=_bits(g.download(A.DEFORMATION_GRADIENTS)), pids=g.download(A.PIDS))
+    st = dict(x=hs.bits(g.download(A.POSITIONS)), v=hs.bits(g.download(A.VELOCITIES)), C=hs.bits(g.download(A.AFFINE)),
+              F=hs.bits(g.download(A.DEFORMATION_GRADIENTS)), pids=g.download(A.PIDS))
     E, psi, inactive = g.shell_state()
-    st.update(E=_bits(E), psi=_bits(psi), inactive=np.array([inactive]), shell=_bits(g.shell_forces()),
-              pressure=_bits(g.pressure_forces()), ps=np.frombuffer(g.pressure_state().tobytes(), np.uint8),
+    st.update(E=hs.bits(E), psi=hs.bits(psi), inactive=np.array([inactive]), shell=hs.bits(g.shell_forces()),
+              pressure=hs.bits(g.pressure_forces()), ps=np.frombuffer(g.pressure_state().tobytes(), np.uint8),
               torn=g.tear_state()[0], cut=g.shell_cut_hinges()[0], cut_count=g.shell_cut_hinges()[1],
-              vented=g.pressure_vented(), psibar=_bits(g.crease_state()[0]))
+              vented=g.pressure_vented(), psibar=hs.bits(g.crease_state()[0]))
     return st
 
 
@@ -644,7 +600,7 @@ def test_off_means_off_with_the_mode_set_and_nothing_torn():
     from drake_amd import scenes
     pos, idx = scenes.cloth_sheet(24, 0.25, 0.6, (0.35, 0.5))
     Xi, Ti = pr.icosphere((0.7, 0.5, 0.6), pr.ICO_R)
-    es = [_engine([(pos, idx.reshape(-1, 3)), (Xi, Ti)]) for _ in range(2)]
+    es = [hs.engine([(pos, idx.reshape(-1, 3)), (Xi, Ti)]) for _ in range(2)]
     es[1].set_tear_coupling(3)
     V0 = pr.volume64(Xi, Ti)
     vel = np.array([3.0, 0.3, 0.0], F) + 0.05 * np.random.default_rng(3).normal(size=(len(pos) + len(Xi), 3)).astype(F)
@@ -652,7 +608,7 @@ def test_off_means_off_with_the_mode_set_and_nothing_torn():
         k = _scale_k(g, lambda k: g.set_shell_bending([k, 0.0]), DT)
         g.set_creases(_crease_table([(0.02, 0.5, 0.0), (0.0, 0.0, 0.0)]))
         g.set_pressure(_gas({1: (pr.GAS, 0.0, F(1.5 * 100.0 * V0), 100.0, 1000.0)}, 2))
-        pids = g.download(_A().PIDS)
+        pids = g.download(hs.ARR().PIDS)
         allv = np.concatenate([vel[g._tri].mean(axis=1), vel]).astype(F)
         g.upload_particle_state(None, allv[pids], None, None, None)
         for _ in range(2):
@@ -673,13 +629,13 @@ def test_off_means_off_with_the_mode_set_and_nothing_torn():
 def test_off_means_off_with_tearing_on_a_cloth_without_hinges_and_gas():
     """mask 3 and tearing on a cloth that has neither shell bending nor pressure: mask 0's bits"""
     s = tr.scene("pair")
-    es = [_engine(s["meshes"]) for _ in range(2)]
+    es = [hs.engine(s["meshes"]) for _ in range(2)]
     es[1].set_tear_coupling(3)
     x0 = tr.state("uniaxial", s)
     out = []
     for g in es:
         g.set_tearing(s["limits"])
-        _upload(g, x0)
+        hs.upload(g, x0)
         g.run_substeps(20, DT, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
@@ -695,14 +651,14 @@ def test_off_means_off_with_tearing_on_a_cloth_without_hinges_and_gas():
 def test_vented_gas():
     """two gas cloths: the icosphere, and the icosphere of 1280 faces -- two chunks of k_pressure_volume -- with a face of
     its SECOND chunk cut; a twin without cuts; an engine without pressure"""
-    A = _A()
+    A = hs.ARR()
     X0, T0 = pr.mesh("icosphere")                                   # at (0.3, 0.3, 0.5), radius 1/32
     X1, T1 = pr.mesh("icosphere3")                                  # at (0.5, 0.5, 0.4), radius 6/128: no grid node in common
     cloths = [(X0, T0), (X1, T1)]
     n0, n1, v0 = len(T0), len(T1), len(X0)
     assert n1 == 1280
     table = pr.make_table([pr.gas_row("icosphere"), pr.gas_row("icosphere3")])
-    a, b, bare = (_engine(cloths, material=dict(gravity=0.0)) for _ in range(3))
+    a, b, bare = (hs.engine(cloths, material=dict(gravity=0.0)) for _ in range(3))
     for g in (a, b):
         g.set_tear_coupling(tc.VENTS_GAS)
         g.set_pressure(table)
@@ -715,19 +671,19 @@ def test_vented_gas():
     # the substep's own values: the total forces behind CalcFemStateAndForce
     for g in (a, b, bare):
         _fem(g, dt)
-    fa, fb, f0 = (_vertices(g, A.FORCES) for g in (a, b, bare))
+    fa, fb, f0 = (hs.vertices(g, A.FORCES) for g in (a, b, bare))
     assert np.array_equal(fa[v0:], f0[v0:]), "the vented cloth feels a pressure force"
-    assert np.array_equal(_bits(fa[:v0]), _bits(fb[:v0])) and not np.array_equal(fb[v0:], f0[v0:])
+    assert np.array_equal(hs.bits(fa[:v0]), hs.bits(fb[:v0])) and not np.array_equal(fb[v0:], f0[v0:])
     for g in (a, b, bare):
         g.particle_to_grid(dt)
         g.update_grid(-1)
         g.grid_to_particle(dt)
         g.gpu_sync()
-    x = _vertices(a, A.POSITIONS)
+    x = hs.vertices(a, A.POSITIONS)
     Tg = np.concatenate([T0, T1 + v0])
     cf = np.concatenate([np.zeros(n0, int), np.ones(n1, int)])
     st = a.pressure_state()
-    assert _bits(st["gauge"][1:2])[0] == 0 and st["energy"][1] == 0.0 and st["capped"][1] == 0          # exactly +0
+    assert hs.bits(st["gauge"][1:2])[0] == 0 and st["energy"][1] == 0.0 and st["capped"][1] == 0          # exactly +0
     V1 = pr.volume64(x, Tg[cf == 1])
     assert abs(st["volume"][1] - V1) <= pr.volume_bound(x, Tg[cf == 1]) and V1 > 0
     fp_ = a.pressure_forces()
@@ -736,19 +692,19 @@ def test_vented_gas():
     assert tc.gauge(table[1], V1, True)[0] == st["gauge"][1]
     # the other cloth: the twin's bits, particle by particle, and its state record
     for arr in (A.POSITIONS, A.VELOCITIES):
-        pa, pb = _vertices(a, arr), _vertices(b, arr)
-        assert np.array_equal(_bits(pa[:v0]), _bits(pb[:v0])), arr
+        pa, pb = hs.vertices(a, arr), hs.vertices(b, arr)
+        assert np.array_equal(hs.bits(pa[:v0]), hs.bits(pb[:v0])), arr
     Fa, Fb = a.download(A.DEFORMATION_GRADIENTS), b.download(A.DEFORMATION_GRADIENTS)      # (per face, in original face order)
-    assert len(Fa) == n0 + n1 and np.array_equal(_bits(Fa[:n0]), _bits(Fb[:n0])) and Fa[:n0].any()
+    assert len(Fa) == n0 + n1 and np.array_equal(hs.bits(Fa[:n0]), hs.bits(Fb[:n0])) and Fa[:n0].any()
     sb_ = b.pressure_state()
     assert st[0].tobytes() == sb_[0].tobytes() and sb_["gauge"][1] > 0
-    assert not np.array_equal(_vertices(a, A.VELOCITIES)[v0:], _vertices(b, A.VELOCITIES)[v0:])
+    assert not np.array_equal(hs.vertices(a, A.VELOCITIES)[v0:], hs.vertices(b, A.VELOCITIES)[v0:])
     # restore: the gas law on the current volume
     a.set_torn_faces(np.zeros(n0 + n1, bool))
     st = a.pressure_state()
     assert not a.pressure_vented().any()
     want = F(float(table["pv"][1]) / float(st["volume"][1]) - float(table["p_ambient"][1]))
-    assert _bits(st["gauge"][1:2])[0] == _bits(np.array([want], F))[0] and want > 0 and st["capped"][1] == 0
+    assert hs.bits(st["gauge"][1:2])[0] == hs.bits(np.array([want], F))[0] and want > 0 and st["capped"][1] == 0
     assert pr.gauge(table[1], float(st["volume"][1]))[0] == st["gauge"][1]
     assert a.pressure_forces()[v0:].any()
     for g in (a, b, bare):
@@ -797,20 +753,20 @@ def test_paper_the_notched_strip_with_shell_bending_parts():
         t["stiffness"], t["rest"] = k, SHELL_REST_FLAT
         return t
 
-    g0 = _engine([(X, T)], material=dict(gravity=0.0))
+    g0 = hs.engine([(X, T)], material=dict(gravity=0.0))
     g0.set_shell_bending(shell(1e-6))
     refused(lambda: g0.set_torn_faces(notch), says="mpm_set_shell_bending")
     refused(lambda: g0.set_tearing([tr.LIMIT]), says="mpm_set_shell_bending")
     g0.destroy()
 
-    g = _engine([(X, T)], material=dict(gravity=0.0))
+    g = hs.engine([(X, T)], material=dict(gravity=0.0))
     g.set_tear_coupling(tc.CUTS_HINGES)
     _scale_k(g, lambda k: g.set_shell_bending(shell(k)), STRIP_DT)
     g.set_torn_faces(notch)
     g.set_tearing([tr.LIMIT])
-    _upload(g, X, v0)
+    hs.upload(g, X, v0)
     flags = []
-    A = _A()
+    A = hs.ARR()
     for _ in range(STRIP_SAMPLES):
         g.run_substeps(STRIP_EVERY, STRIP_DT, -1)
         x = g.dump_cpu_state()[0].astype(np.float64)
@@ -842,9 +798,9 @@ BALLOON_DT, BALLOON_N = 1e-4, 24
 def _balloon(limit):
     """the inflating gas icosphere of tests/test_pressure_gpu.py (no gravity; the pressure moves the surface by about 1 % of
     the radius in 12 substeps) -> per substep (stretch_max, gauge, volume, torn faces)"""
-    A = _A()
+    A = hs.ARR()
     X, T = pr.mesh("icosphere")
-    g = _engine([(X, T)], material=dict(gravity=0.0))
+    g = hs.engine([(X, T)], material=dict(gravity=0.0))
     mass = g.download(A.MASSES).astype(np.float64).sum()
     x64 = X.astype(np.float64)
     area = 0.5 * np.linalg.norm(np.cross(x64[T[:, 1]] - x64[T[:, 0]], x64[T[:, 2]] - x64[T[:, 0]]), axis=1).sum()
@@ -885,7 +841,7 @@ def test_a_balloon_bursts():
     for i, r in enumerate(run):
         if i < k:
             assert r[1] > 0 and not r[4]
-            assert _bits(np.array([r[1]]))[0] == _bits(np.array([twin[i][1]]))[0] and r[2] == twin[i][2]
+            assert hs.bits(np.array([r[1]]))[0] == hs.bits(np.array([twin[i][1]]))[0] and r[2] == twin[i][2]
         else:
-            assert _bits(np.array([r[1]], F))[0] == 0 and r[4], (i, r)          # exactly +0 from that substep on
+            assert hs.bits(np.array([r[1]], F))[0] == 0 and r[4], (i, r)          # exactly +0 from that substep on
     assert run[-1][2] < twin[-1][2], (run[-1][2], twin[-1][2])

@@ -12,12 +12,13 @@ the scenes, the states and the bound that says which faces are undecided; undeci
    that skipped themselves included; run_coupled_substeps against the seven calls to the bit; substep_begin / end
    against itself under sparse re-sort checks; a shuffled particle order gives the same flags by original id.
 5. Off means off.  6. Dynamics.  7. Refusals."""
-import os
+import functools
 
 import numpy as np
 import pytest
 
 from tests import bending as bd
+from tests import harness as hs
 from tests import tearing as tr
 
 pytestmark = pytest.mark.gpu
@@ -26,60 +27,11 @@ U = tr.U
 _CACHE = {}
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _engine(meshes, bits=6, deterministic=True, material=None, bodies=0, env=None):
-    from drake_amd import GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update(env or {})
-    try:
-        g = GpuMpm(bits, mat)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    g.set_deterministic(deterministic)
-    for X, T in meshes:
-        g.add_qr_cloth(X, np.zeros_like(X), T)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(meshes, np.cumsum([0] + [len(X) for X, _ in meshes[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.broadcast_to(np.asarray(v, np.float32), x.shape)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, None)
-
-
-def _by_id(g, which):
-    nf = g.n_faces
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros_like(a)
-    out[pids] = a
-    return out[:nf], out[nf:]
+_by_id = functools.partial(hs.by_id, split=True)
 
 
 def _rest(g):
-    A = _A()
+    A = hs.ARR()
     nf = g.n_faces
     return g.download(A.DM_INVERSES).reshape(nf, 4)[:, [0, 1, 3]].copy(), _by_id(g, A.VOLUMES)[0].copy()
 
@@ -110,7 +62,7 @@ def refused(call, says=None):
 def test_flags_are_float64_verdicts_and_measure_is_the_host_bits(name):
     from drake_amd import tear_face
     s = tr.scene(name)
-    g = _engine(s["meshes"])
+    g = hs.engine(s["meshes"])
     g.set_tearing(s["limits"])
     assert np.array_equal(g.get_tearing(), s["limits"])
     dm, _ = _rest(g)
@@ -119,7 +71,7 @@ def test_flags_are_float64_verdicts_and_measure_is_the_host_bits(name):
     for st in tr.STATES:
         x = tr.state(st, s)
         g.set_torn_faces(np.zeros(g.n_faces, np.uint8))       # (restore: the flags are monotone across the states)
-        _upload(g, x)
+        hs.upload(g, x)
         assert np.array_equal(g.dump_cpu_state()[0], x)
         _fem(g)
         torn, count = g.tear_state()
@@ -132,7 +84,7 @@ def test_flags_are_float64_verdicts_and_measure_is_the_host_bits(name):
         assert np.array_equal(count, np.bincount(s["cof"], weights=torn, minlength=len(s["limits"])).astype(np.uint32))
         mq, would = g.tear_measure()
         host_mq, host_fails = tear_face(dm, xc, s["L_f"])
-        assert np.array_equal(_bits(mq), _bits(host_mq)), (name, st)
+        assert np.array_equal(hs.bits(mq), hs.bits(host_mq)), (name, st)
         assert np.array_equal(would, host_fails & tears) and np.array_equal(would, torn), (name, st)
     print(f"tearing flags {name}: {skipped} undecided faces skipped over {len(tr.STATES)} states")
     assert g.stats()["error_flags"] == 0
@@ -175,9 +127,9 @@ def test_forces_of_torn_intact_and_mixed_vertices(name, fused, extras):
     from tests import fem_regimes as fr
     from tests import transfer_layouts as tl
     from tests import weave as wv
-    A = _A()
+    A = hs.ARR()
     s = tr.scene(name)
-    a, b = _engine(s["meshes"]), _engine(s["meshes"])
+    a, b = hs.engine(s["meshes"]), hs.engine(s["meshes"])
     a.set_tearing(s["limits"])
     table = betas = None
     for g in (a, b):
@@ -187,7 +139,7 @@ def test_forces_of_torn_intact_and_mixed_vertices(name, fused, extras):
     out = []
     F_up = None
     for g in (a, b):
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         F_up = g.download(A.DEFORMATION_GRADIENTS)
         _fem(g, dt=0.5 * tl.DT, p2g=fused)                          # (ParticleToGrid checks dt against the weave's guard)
         out.append(_by_id(g, A.FORCES)[1].copy())
@@ -201,7 +153,7 @@ def test_forces_of_torn_intact_and_mixed_vertices(name, fused, extras):
     mixed = ~all_torn & ~none_torn
     assert all_torn.any() and none_torn.any() and mixed.any()
     assert not fa[all_torn].any(), "a vertex whose faces are all torn has a force"
-    assert np.array_equal(_bits(fa[none_torn]), _bits(fb[none_torn]))
+    assert np.array_equal(hs.bits(fa[none_torn]), hs.bits(fb[none_torn]))
     assert np.abs(fb[all_torn]).max() > 0 and not np.array_equal(fa[mixed], fb[mixed])
     # the float64 records of the intact faces
     dm, vol = _rest(a)
@@ -248,7 +200,7 @@ def test_forces_of_torn_intact_and_mixed_vertices(name, fused, extras):
 # ---- 3 -------------------------------------------------------------------------------------------------------------------
 def test_scissors_counts_and_monotone_flags():
     s = tr.scene("pair")
-    g = _engine(s["meshes"])
+    g = hs.engine(s["meshes"])
     nf = g.n_faces
     assert not g.tear_state()[0].any() and not g.tear_state()[1].any() and not g.get_tearing().any()
     cut = np.zeros(nf, bool)
@@ -258,12 +210,12 @@ def test_scissors_counts_and_monotone_flags():
     assert np.array_equal(torn, cut) and np.array_equal(count, np.bincount(s["cof"], weights=cut).astype(np.uint32))
     g.set_tearing(s["limits"])
     assert np.array_equal(g.tear_state()[0], cut), "mpm_set_tearing changed the flags"
-    _upload(g, tr.state("uniaxial", s))
+    hs.upload(g, tr.state("uniaxial", s))
     _fem(g)
     loaded = g.tear_state()[0]
     assert np.all(loaded[cut]) and loaded.sum() > cut.sum() and not loaded[(s["cof"] == 1) & ~cut].any()
     # the load goes, the flags stay; the limits go, the flags stay
-    _upload(g, s["X"])
+    hs.upload(g, s["X"])
     _fem(g)
     assert np.array_equal(g.tear_state()[0], loaded) and not g.tear_measure()[1].any()
     g.set_tearing([0.0, 0.0])
@@ -385,8 +337,8 @@ def test_sums_family_with_tearing():
     twin.calc_fem_state_and_force(fp.DT)
     ta, tb = g.tear_state()[0], twin.tear_state()[0]
     assert ta.any() and np.array_equal(ta, tb)
-    fa, fb = fp.vertices(g, _A().FORCES), fp.vertices(twin, _A().FORCES)
-    assert np.array_equal(_bits(fa), _bits(fb))
+    fa, fb = fp.vertices(g, hs.ARR().FORCES), fp.vertices(twin, hs.ARR().FORCES)
+    assert np.array_equal(hs.bits(fa), hs.bits(fb))
     g.substep_end(fp.DT, -1)
     for e in (g, twin):
         e.destroy()
@@ -412,21 +364,21 @@ def test_particle_order():
     fresh engines in both modes too (the moved engine's deformation gradients have a history of their own)"""
     s = tr.scene("quad12")
     env = {"MPM_RESORT_EVERY": "1", "MPM_QUIET_FACTOR": "0"}
-    g, fresh, dflt = _engine(s["meshes"], env=env), _engine(s["meshes"]), _engine(s["meshes"], deterministic=False)
-    pid0 = g.download(_A().PIDS)
-    _upload(g, tr.state("shear_rot", s) + np.array([5.0 / 64, 0.0, 0.0], np.float32), np.array([3.0, 0.5, 0.0], np.float32))
+    g, fresh, dflt = hs.engine(s["meshes"], env=env), hs.engine(s["meshes"]), hs.engine(s["meshes"], deterministic=False)
+    pid0 = g.download(hs.ARR().PIDS)
+    hs.upload(g, tr.state("shear_rot", s) + np.array([5.0 / 64, 0.0, 0.0], np.float32), np.array([3.0, 0.5, 0.0], np.float32))
     g.run_substeps(12, 1e-4, -1)
     g.gpu_sync()
     g.rebuild_mapping(True)
-    assert not np.array_equal(g.download(_A().PIDS), pid0), "no slot moved"
+    assert not np.array_equal(g.download(hs.ARR().PIDS), pid0), "no slot moved"
     x = tr.state("uniaxial_rot", s)
     res = []
     for e in (g, fresh, dflt):
         e.set_tearing(s["limits"])
-        _upload(e, x)
+        hs.upload(e, x)
         _fem(e)
         torn, count = e.tear_state()
-        res.append((torn, count, _bits(e.tear_measure()[0]), _bits(_by_id(e, _A().FORCES)[1])))
+        res.append((torn, count, hs.bits(e.tear_measure()[0]), hs.bits(_by_id(e, hs.ARR().FORCES)[1])))
     assert res[0][0].any() and not res[0][0].all()
     for k in (1, 2):
         for a, b in zip(res[0][:3], res[k][:3]):
@@ -438,19 +390,13 @@ def test_particle_order():
 
 
 # ---- 5 -------------------------------------------------------------------------------------------------------------------
-def _state(g):
-    A = _A()
-    return dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS),
-                F=g.download(A.DEFORMATION_GRADIENTS))
-
-
 def test_off_means_off():
     """20 deterministic substeps through re-sorts: never set == a table of zeros == set, cleared and restored, to the bit
     in x, v, C and F, and with the same launch counters (the quiet-time hint is in use again)"""
     from drake_amd import scenes
     from tests import transfer_layouts as tl
     pos, idx = scenes.cloth_sheet(32, 0.3, 0.6, (0.3, 0.5))
-    es = [_engine([(pos, idx.reshape(-1, 3))]) for _ in range(3)]
+    es = [hs.engine([(pos, idx.reshape(-1, 3))]) for _ in range(3)]
     es[1].set_tearing([0.0])
     es[2].set_tearing([1.5])
     es[2].set_torn_faces(np.arange(es[2].n_faces) % 7 == 0)
@@ -462,7 +408,7 @@ def test_off_means_off():
     vel = np.array([4.0, 0.3, 0.0], np.float32) + 0.05 * np.random.default_rng(3).normal(size=pos.shape).astype(np.float32)
     before = es[0].stats()["rebuilds"]
     for g in es:
-        pids = g.download(_A().PIDS)
+        pids = g.download(hs.ARR().PIDS)
         allv = np.concatenate([vel[g._tri].mean(axis=1), vel]).astype(np.float32)
         g.upload_particle_state(None, allv[pids], None, None, None)
         for _ in range(2):
@@ -470,10 +416,10 @@ def test_off_means_off():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 1, es[0].stats()
-    st = [_state(g) for g in es]
+    st = [hs.state(g) for g in es]
     for k in (1, 2):
         for key in st[0]:
-            assert np.array_equal(_bits(st[0][key]), _bits(st[k][key])), (k, key)
+            assert np.array_equal(hs.bits(st[0][key]), hs.bits(st[k][key])), (k, key)
         for key in ("substeps", "rebuilds", "resort_checks"):
             assert es[0].stats()[key] == es[k].stats()[key], (k, key)
     for g in es:
@@ -485,12 +431,12 @@ def test_a_cloth_without_limit_is_its_twins_bits_while_the_other_tears():
     it, the second without: 20 substeps leave the second cloth's particles with the bits of a twin engine without
     tearing, while the first cloth tears and differs"""
     s = tr.scene("pair")
-    a, b = _engine(s["meshes"]), _engine(s["meshes"])
+    a, b = hs.engine(s["meshes"]), hs.engine(s["meshes"])
     a.set_tearing(s["limits"])
     x0 = tr.state("uniaxial", s)
     x0[s["first"][1]:] = tr.state("shear", s)[s["first"][1]:] * np.float32(1.0)     # (the second cloth strained too)
     for g in (a, b):
-        _upload(g, x0)
+        hs.upload(g, x0)
         g.run_substeps(20, 2e-4, -1)
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
@@ -499,10 +445,10 @@ def test_a_cloth_without_limit_is_its_twins_bits_while_the_other_tears():
     xa, va = a.dump_cpu_state()[:2]
     xb, vb = b.dump_cpu_state()[:2]
     second = slice(s["first"][1], None)
-    assert np.array_equal(_bits(xa[second]), _bits(xb[second])) and np.array_equal(_bits(va[second]), _bits(vb[second]))
+    assert np.array_equal(hs.bits(xa[second]), hs.bits(xb[second])) and np.array_equal(hs.bits(va[second]), hs.bits(vb[second]))
     assert not np.array_equal(xa[:s["first"][1]], xb[:s["first"][1]])
-    Fa, Fb = a.download(_A().DEFORMATION_GRADIENTS), b.download(_A().DEFORMATION_GRADIENTS)
-    assert np.array_equal(_bits(Fa[s["cof"] == 1]), _bits(Fb[s["cof"] == 1]))
+    Fa, Fb = a.download(hs.ARR().DEFORMATION_GRADIENTS), b.download(hs.ARR().DEFORMATION_GRADIENTS)
+    assert np.array_equal(hs.bits(Fa[s["cof"] == 1]), hs.bits(Fb[s["cof"] == 1]))
     for g in (a, b):
         g.destroy()
 
@@ -522,7 +468,7 @@ def _strip(limit):
     column's faces, the notch)"""
     n, m = STRIP_N, STRIP_M
     X, T = bd.sheet(n, m)
-    g = _engine([(X, T)], material=dict(gravity=0.0))
+    g = hs.engine([(X, T)], material=dict(gravity=0.0))
     col = n // 2 - 1                                                # quads between vertex columns 9 and 10
     quad_of_face = np.arange(len(T)) // 2                           # (sheet(): two faces per quad, quads in (i, j) order)
     in_col = quad_of_face // (m - 1) == col
@@ -533,7 +479,7 @@ def _strip(limit):
     v0[:(col + 1) * m, 0], v0[(col + 1) * m:, 0] = -STRIP_V, STRIP_V
     g.set_torn_faces(notch)
     g.set_tearing([limit])
-    _upload(g, X, v0)
+    hs.upload(g, X, v0)
     xs, flags = [], []
     for _ in range(STRIP_SAMPLES):
         g.run_substeps(STRIP_EVERY, STRIP_DT, -1)
@@ -609,7 +555,7 @@ def _hanging(cut_row):
     from drake_amd import BodyMotion, Pin
     X, T = bd.sheet(13, 13, h=HANG_H)
     X = np.stack([X[:, 0], np.full(len(X), 0.5, np.float32), 0.5 + (X[:, 1] - 0.5)], 1).astype(np.float32)
-    g = _engine([(X, T)], bits=7, bodies=1)
+    g = hs.engine([(X, T)], bits=7, bodies=1)
     g.set_body_motions([BodyMotion(0)])
     top = np.nonzero(X[:, 2] >= X[:, 2].max() - 1e-6)[0]
     g.set_pins([Pin(int(v), 0, X[v]) for v in top])
@@ -648,9 +594,9 @@ def test_measure_drops_the_torn_faces_share_and_keeps_the_momenta():
     bits, the cut faces report V psi = 0 and leave the stretch extremes"""
     from tests import damping as dp
     s = tr.scene("quad12")
-    g = _engine(s["meshes"])
+    g = hs.engine(s["meshes"])
     x = tr.state("uniaxial", s)
-    _upload(g, x, dp.velocity("random", x).astype(np.float32))
+    hs.upload(g, x, dp.velocity("random", x).astype(np.float32))
     _fem(g)
     rows0, tot0 = g.measure()
     fs0 = g.face_strain()
@@ -667,8 +613,8 @@ def test_measure_drops_the_torn_faces_share_and_keeps_the_momenta():
         if key in tot0.dtype.names:
             assert np.array_equal(np.asarray(tot0[key]), np.asarray(tot1[key])), key
     assert "mass" in tot0.dtype.names and "momentum" in tot0.dtype.names
-    assert not fs1[cut, 3].any() and np.array_equal(_bits(fs1[~cut]), _bits(fs0[~cut]))
-    assert np.array_equal(_bits(fs1[:, :3]), _bits(fs0[:, :3]))
+    assert not fs1[cut, 3].any() and np.array_equal(hs.bits(fs1[~cut]), hs.bits(fs0[~cut]))
+    assert np.array_equal(hs.bits(fs1[:, :3]), hs.bits(fs0[:, :3]))
     assert tot1["stretch_max"] == fs0[~cut, 0].max() < tot0["stretch_max"]
     g.set_torn_faces(np.zeros(g.n_faces, bool))
     assert g.measure()[1].tobytes() == tot0.tobytes()
@@ -687,7 +633,7 @@ def test_refusals():
     refused(lambda: g0.set_torn_faces(np.zeros(len(T), bool)), says="finalize")
     g0.destroy()
 
-    g = _engine(s["meshes"], bodies=1)
+    g = hs.engine(s["meshes"], bodies=1)
     nf = g.n_faces
     for bad in ([1.0, 0.0], [0.5, 0.0], [-1.1, 0.0], [np.nan, 0.0], [np.inf, 0.0], [1.1, 0.999]):
         refused(lambda bad=bad: g.set_tearing(bad), says="stretch_limit")

@@ -4,6 +4,7 @@ per-node / per-particle bounds are real rounding bounds (the float build of the 
 import numpy as np
 import pytest
 
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 
@@ -117,11 +118,6 @@ def _transfers(o):
     return r, (gm, gmv, flags), gv, g
 
 
-def _record(what, ratio, rel):
-    from tests.helpers import MARGINS
-    MARGINS.append((ratio, what, 1.0, rel, rel))
-
-
 @pytest.mark.parametrize("name", tl.NAMES)
 def test_restatements_match_the_double_oracle(name):
     lay = tl.layout(name)
@@ -158,7 +154,7 @@ def test_float_oracle_within_the_rounding_bounds(name):
     worst["g2p C"] = tl.margin(np.abs(o.C - g["C"]), g["bC"])
     worst["g2p x"] = tl.margin(np.abs(o.pos - g["x"]), g["bx"])
     for k, v in worst.items():
-        _record(f"float oracle within the transfer bound: {name} {k}", v, v)
+        hs.record(f"float oracle within the transfer bound: {name} {k}", v)
     assert all(v <= 1.0 for v in worst.values()), worst
     # (and the float grid update is the float32 quotient of its own sums)
     assert np.array_equal(tl.grid32(gm, gmv, lay["bits"]), gv)

@@ -10,11 +10,10 @@ Each phase is judged on the engine's own inputs of that phase (downloaded after 
 engine (double LDS tiles), deterministic mode (64-bit fixed-point tiles, canonical order) and MPM_P2G_FIXED=1 alone.
 The fused vertex-force instance k_p2g<1, .> (what mpm_substep runs) is covered by a twin engine in deterministic mode:
 its substep is bit-equal to the phase calls in positions, velocities and affine matrices."""
-import os
-
 import numpy as np
 import pytest
 
+from tests import harness as hs
 from tests import transfer_layouts as tl
 
 pytestmark = pytest.mark.gpu
@@ -28,9 +27,7 @@ def _engine(lay, mode):
     env = {"MPM_ANTICIPATE": str(lay["anticipate"]), **lay["env"]}
     if mode == "p2g_fixed":
         env["MPM_P2G_FIXED"] = "1"
-    saved = {k: os.environ.get(k) for k in env}
-    os.environ.update(env)
-    try:
+    with hs.environ(env):
         mat = GpuMpm.default_material()
         mat.gravity_axis = lay["gravity_axis"]
         g = GpuMpm(lay["bits"], mat)
@@ -46,12 +43,6 @@ def _engine(lay, mode):
         # (the anticipatory binning needs a known substep length: one FEM pass sets it)
         g.calc_fem_state_and_force(tl.DT)
         g.gpu_sync()
-    finally:
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
     from drake_amd import ARR as A
     pids = g.download(A.PIDS)
     # the uploaded positions force a re-sort at the next RebuildMapping
@@ -85,11 +76,6 @@ def _run(name, mode):
     return d
 
 
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, what + helpers.TAG, 1.0, ratio, ratio))
-
-
 def _p2g_inputs(d):
     face = d["pids"] < d["lay"]["nf"]
     taus = np.where(face[:, None], d["taus"], 0.0)     # (the kernel's face lanes take tau, vertex lanes the force)
@@ -118,7 +104,7 @@ def test_transfers_phase_by_phase(name, mode):
     def check(field, err, bound):
         w = tl.margin(err, bound)
         worst[field] = w
-        _record(f"transfer layouts: {name} [{mode}] {field}", w)
+        hs.record(f"transfer layouts: {name} [{mode}] {field}", w)
         if not w <= 1.0:
             e = np.asarray(err, np.float64).reshape(len(err), -1).max(axis=1)
             b = np.asarray(bound, np.float64).reshape(len(bound), -1).max(axis=1)

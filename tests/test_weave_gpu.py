@@ -10,12 +10,13 @@
    seven calls.
 5. Off means off.  6. More than 256 cloths.  7. Dynamics: hanging twins, and the energy of a released sheet.
 8. The guard and the refusals."""
-import os
+import functools
 
 import numpy as np
 import pytest
 
 from tests import bending as bd
+from tests import harness as hs
 from tests import weave as wv
 
 pytestmark = pytest.mark.gpu
@@ -25,14 +26,9 @@ R = wv.rounding_count()
 _CACHE = {}
 
 
-def _A():
-    from drake_amd import ARR
-    return ARR
-
-
-def _record(what, ratio):
-    from tests import helpers
-    helpers.MARGINS.append((ratio, "weave: " + what + helpers.TAG, 1.0, ratio, ratio))
+_record = functools.partial(hs.record, prefix="weave: ")
+_engine = functools.partial(hs.engine, fast_math=False)
+_by_id = functools.partial(hs.by_id, split=True)
 
 
 def _note(line):
@@ -40,64 +36,10 @@ def _note(line):
     print("weave_margins: " + line)
 
 
-def _bits(a):
-    return np.ascontiguousarray(a).view(np.uint32)
-
-
-def _engine(meshes, mats=None, bits=6, deterministic=True, fast_math=False, material=None, bodies=0, env=None):
-    from drake_amd import ClothMaterial, GpuMpm
-    mat = GpuMpm.default_material()
-    for k, val in (material or {}).items():
-        setattr(mat, k, val)
-    old = {k: os.environ.get(k) for k in (env or {})}
-    os.environ.update(env or {})
-    try:
-        g = GpuMpm(bits, mat)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    g.set_deterministic(deterministic)
-    g.set_fast_math(fast_math)
-    for c, (X, T) in enumerate(meshes):
-        m = None
-        if mats is not None:
-            m = ClothMaterial.of(mat)
-            for k, val in mats[c].items():
-                setattr(m, k, val)
-        g.add_qr_cloth(X, np.zeros_like(X), T, m)
-    g.finalize()
-    if bodies:
-        g.reallocate_external_bodies(bodies)
-    g._tri = np.concatenate([T + o for (X, T), o in zip(meshes, np.cumsum([0] + [len(X) for X, _ in meshes[:-1]]))])
-    return g
-
-
-def _upload(g, x, v=None):
-    """vertex positions and velocities (n_verts, 3) in original order; a face particle gets its corners' means"""
-    x = np.asarray(x, np.float32)
-    v = np.zeros_like(x) if v is None else np.broadcast_to(np.asarray(v, np.float32), x.shape)
-    mean = lambda a: a[g._tri].astype(np.float64).mean(axis=1).astype(np.float32)   # noqa: E731
-    pos, vel = np.concatenate([mean(x), x]), np.concatenate([mean(v), v])
-    pids = g.download(_A().PIDS)
-    g.upload_particle_state(pos[pids], vel[pids], np.zeros((len(pos), 9), np.float32), None, None)
-
-
-def _by_id(g, which):
-    """(face part, vertex part) of a per-particle array in original order"""
-    nf = g.n_faces
-    a, pids = g.download(which), g.download(_A().PIDS)
-    out = np.zeros_like(a)
-    out[pids] = a
-    return out[:nf], out[nf:]
-
-
 def _rest(g):
     """(dm (nf, 3), vol (nf,)) float32 in original face order, of a SINGLE-material engine (whose MPM_ARR_VOLUMES is the
     record the face kernels read)"""
-    A = _A()
+    A = hs.ARR()
     nf = g.n_faces
     return g.download(A.DM_INVERSES).reshape(nf, 4)[:, [0, 1, 3]].copy(), _by_id(g, A.VOLUMES)[0].copy()
 
@@ -142,8 +84,8 @@ def _check(g, s, cs, x, what):
     host_rec, host_strain, host_energy = weave_face_records(dm, vol, s["coef_f"], cs, xc)
     # (a face without weave: the engine writes nothing, +0; the host function forms products with zero coefficients, -0)
     host_rec = np.where(s["woven"][:, None, None], host_rec, 0.0).astype(np.float32)
-    assert np.array_equal(_bits(rec), _bits(host_rec)), (what, int((_bits(rec) != _bits(host_rec)).sum()))
-    assert np.array_equal(_bits(g.weave_strain()), _bits(np.where(s["woven"][:, None], host_strain, 0.0).astype(np.float32))), what
+    assert np.array_equal(hs.bits(rec), hs.bits(host_rec)), (what, int((hs.bits(rec) != hs.bits(host_rec)).sum()))
+    assert np.array_equal(hs.bits(g.weave_strain()), hs.bits(np.where(s["woven"][:, None], host_strain, 0.0).astype(np.float32))), what
     assert w_rec <= 1.0 and w_f <= 1.0, (what, w_rec, w_f)
     assert not rec[~s["woven"]].any()
     return w_rec, w_f, f, host_energy
@@ -160,18 +102,18 @@ def test_forces_against_float64(name, mode):
     det, fast = MODES[mode]
     helpers.tag_default_engine(not det)
     s = _scene(name)
-    g = _engine(s["meshes"], s["mats"], deterministic=det, fast_math=fast)
+    g = _engine(s["meshes"], mats=s["mats"], deterministic=det, fast_math=fast)
     assert g.cloth_count() == len(s["meshes"])
     worst = [0.0, 0.0]
     for case in wv.axis_cases(name):
         cs = _set_case(g, s, case)
-        assert np.array_equal(_bits(g.weave_axes()), _bits(cs)), (name, case)
+        assert np.array_equal(hs.bits(g.weave_axes()), hs.bits(cs)), (name, case)
         got = g.get_weave()
         assert np.array_equal(np.array([got["E_warp"], got["E_weft"], got["nu"], got["G"]]).T,
                               wv.axis_case(s, case)[0][:, :4])
         for st in wv.STATES:
             x = wv.state(st, s)
-            _upload(g, x)
+            hs.upload(g, x)
             assert np.array_equal(g.dump_cpu_state()[0], x)
             w_rec, w_f, f, _ = _check(g, s, cs, x, f"{name} {case} {st} [{mode}]")
             worst = [max(worst[0], w_rec), max(worst[1], w_f)]
@@ -200,11 +142,11 @@ def test_total_forces_include_the_weave(name, damped):
     from tests import damping as dp
     from tests import fem_regimes as fr
     from tests import transfer_layouts as tl
-    A = _A()
+    A = hs.ARR()
     s = _scene(name)
     dm, vol = s["rest"]
     T, nf = s["T"], len(s["T"])
-    a, b = _engine(s["meshes"], s["mats"]), _engine(s["meshes"], s["mats"])
+    a, b = _engine(s["meshes"], mats=s["mats"]), _engine(s["meshes"], mats=s["mats"])
     cs = _set_case(a, s, "30")
     betas = None
     if damped:
@@ -216,7 +158,7 @@ def test_total_forces_include_the_weave(name, damped):
     v0 = dp.velocity("random", x0).astype(np.float32)
     out = []
     for g in (a, b):
-        _upload(g, x0, v0)
+        hs.upload(g, x0, v0)
         F_up = g.download(A.DEFORMATION_GRADIENTS)
         g.rebuild_mapping(False)
         g.calc_fem_state_and_force(tl.DT)
@@ -271,23 +213,23 @@ def test_particle_order_and_energy():
     for e in (g, fresh, dflt):
         cs = _set_case(e, s, "130")
     x0 = wv.state("cylinder3", s)
-    pid0 = g.download(_A().PIDS)
+    pid0 = g.download(hs.ARR().PIDS)
     before = g.stats()["rebuilds"]
     # (the rotated sheet of `affine`, five cells along x: another order of the cells than the flat rest sheet's)
-    _upload(g, wv.state("affine", s) + np.array([5.0 / 64, 0.0, 0.0], np.float32), np.array([3.0, 0.5, 0.0], np.float32))
+    hs.upload(g, wv.state("affine", s) + np.array([5.0 / 64, 0.0, 0.0], np.float32), np.array([3.0, 0.5, 0.0], np.float32))
     g.run_substeps(12, 1e-4, -1)
     g.gpu_sync()
     assert g.stats()["error_flags"] == 0 and g.stats()["rebuilds"] > before, g.stats()
     g.rebuild_mapping(True)       # (and the full sort, as tests/test_feature_paths_gpu.test_particle_order does)
-    assert not np.array_equal(g.download(_A().PIDS), pid0), "no slot moved"
+    assert not np.array_equal(g.download(hs.ARR().PIDS), pid0), "no slot moved"
     res = []
     for e in (g, fresh, dflt):
-        _upload(e, x0)
+        hs.upload(e, x0)
         f, rec = e.weave_forces(records=True)
         res.append((f, rec, e.weave_strain(), e.weave_energy()))
     for k in (1, 2):
         for a, b in zip(res[0][:3], res[k][:3]):
-            assert np.array_equal(_bits(a), _bits(b))
+            assert np.array_equal(hs.bits(a), hs.bits(b))
         assert np.array_equal(res[0][3][0].view(np.uint64), res[k][3][0].view(np.uint64)) and res[0][3][1] == res[k][3][1]
     xc = wv.corners(s["T"], x0)
     ref = float(wv.energy64(dm, vol, s["coef_f"], cs, xc).sum())
@@ -407,10 +349,10 @@ def test_sums_family_with_the_weave():
     g.substep_begin(fp.DT)
     twin.rebuild_mapping(False)
     twin.calc_fem_state_and_force(fp.DT)
-    fa, fb = fp.vertices(g, _A().FORCES), fp.vertices(twin, _A().FORCES)
-    assert fa.any() and np.array_equal(_bits(fa), _bits(fb))
+    fa, fb = fp.vertices(g, hs.ARR().FORCES), fp.vertices(twin, hs.ARR().FORCES)
+    assert fa.any() and np.array_equal(hs.bits(fa), hs.bits(fb))
     wa, wb = g.weave_forces(), twin.weave_forces()
-    assert wa.any() and np.array_equal(_bits(wa), _bits(wb))
+    assert wa.any() and np.array_equal(hs.bits(wa), hs.bits(wb))
     g.substep_end(fp.DT, -1)
     twin.destroy()
     run = fp.engine()
@@ -426,12 +368,6 @@ def test_sums_family_with_the_weave():
 
 
 # ---- 5 -------------------------------------------------------------------------------------------------------------------
-def _state(g):
-    A = _A()
-    return dict(x=g.download(A.POSITIONS), v=g.download(A.VELOCITIES), C=g.download(A.AFFINE), pids=g.download(A.PIDS),
-                F=g.download(A.DEFORMATION_GRADIENTS))
-
-
 def test_off_means_off():
     """20 deterministic substeps through re-sorts: never set == all zeros == n_cloths = 0 == set and cleared, to the bit in
     x, v, C and F, and with the same launch counters (the quiet-time hint is in use again)"""
@@ -450,7 +386,7 @@ def test_off_means_off():
     vel = np.array([4.0, 0.3, 0.0], np.float32) + 0.05 * np.random.default_rng(3).normal(size=pos.shape).astype(np.float32)
     before = es[0].stats()["rebuilds"]
     for g in es:
-        pids = g.download(_A().PIDS)
+        pids = g.download(hs.ARR().PIDS)
         allv = np.concatenate([vel[g._tri].mean(axis=1), vel]).astype(np.float32)
         g.upload_particle_state(None, allv[pids], None, None, None)
         for _ in range(2):
@@ -458,10 +394,10 @@ def test_off_means_off():
         g.gpu_sync()
         assert g.stats()["error_flags"] == 0
     assert es[0].stats()["rebuilds"] - before >= 1, es[0].stats()
-    st = [_state(g) for g in es]
+    st = [hs.state(g) for g in es]
     for k in (1, 2, 3):
         for key in st[0]:
-            assert np.array_equal(_bits(st[0][key]), _bits(st[k][key])), (k, key)
+            assert np.array_equal(hs.bits(st[0][key]), hs.bits(st[k][key])), (k, key)
         for key in ("substeps", "rebuilds", "resort_checks"):
             assert es[0].stats()[key] == es[k].stats()[key], (k, key)
     for g in es:
@@ -495,21 +431,21 @@ def test_more_than_256_cloths():
     cs, bad = weave_face_axes(wv.corners(T, X), table[:, 4:7])
     assert bad == -1
     cs[1::2] = 0.0
-    assert np.array_equal(_bits(g.weave_axes()), _bits(cs))
+    assert np.array_equal(hs.bits(g.weave_axes()), hs.bits(cs))
     dm, vol = _rest(g)
     x = bd.state("perturbed", X)
-    _upload(g, x)
+    hs.upload(g, x)
     f, rec = g.weave_forces(records=True)
     host = weave_face_records(dm, vol, coef, cs, wv.corners(T, x))[0]
     host[1::2] = 0.0          # (the engine writes nothing there; the host function forms -0 from zero coefficients)
-    assert np.array_equal(_bits(rec), _bits(host)) and np.array_equal(_bits(f.reshape(n, 3, 3)), _bits(0.0 - host))
+    assert np.array_equal(hs.bits(rec), hs.bits(host)) and np.array_equal(hs.bits(f.reshape(n, 3, 3)), hs.bits(0.0 - host))
     w = wv.margin(rec - wv.records64(dm, vol, coef, cs, wv.corners(T, x)), wv.record_bound(dm, vol, coef, cs, wv.corners(T, x)), R)
     _record("300 cloths", w)
     assert w <= 1.0, w
     assert not rec[1::2].any() and np.all(np.abs(rec[0::2]).max(axis=(1, 2)) > 0)
     rows, total = g.weave_energy()
     assert len(rows) == n and not rows[1::2].any() and (rows[0::2] > 0).all() and total == float(np.add.reduce(rows))
-    mass = _by_id(g, _A().MASSES)[1].astype(np.float64)
+    mass = _by_id(g, hs.ARR().MASSES)[1].astype(np.float64)
     lim = wv.guard64(T, dm, vol, coef, mass)
     assert abs(g.weave_max_stable_dt() / lim - 1.0) < 1e-6, (g.weave_max_stable_dt(), lim)
     assert g.stats()["error_flags"] == 0
@@ -601,7 +537,7 @@ def test_released_sheet_does_not_gain_energy():
 
     series = {}
     for name, g in (("weave", a), ("twin", b)):
-        _upload(g, x0)
+        hs.upload(g, x0)
         s = [total(g, name == "weave")]
         for _ in range(steps // every):
             g.run_substeps(every, dt, -1)
@@ -625,9 +561,9 @@ def test_guard_against_the_formula(name):
     """mpm_weave_max_stable_dt against guard64 from DM_INVERSES, the rest volumes, MPM_ARR_MASSES and the float table.
     1e-6: the engine forms the same sums in double from the same floats and rounds the result to float, towards zero."""
     s = _scene(name)
-    g = _engine(s["meshes"], s["mats"])
+    g = _engine(s["meshes"], mats=s["mats"])
     _set_case(g, s, "30")
-    mass = _by_id(g, _A().MASSES)[1].astype(np.float64)
+    mass = _by_id(g, hs.ARR().MASSES)[1].astype(np.float64)
     lim = wv.guard64(s["T"], s["rest"][0], s["rest"][1], s["coef_f"], mass)
     got = g.weave_max_stable_dt()
     print(f"weave guard {name}: engine {got:.9g}, formula {lim:.9g}")
@@ -657,7 +593,7 @@ def test_refusals():
     g.set_weave(good)
     lim = g.weave_max_stable_dt()
     x0 = bd.state("cylinder30", X)
-    _upload(g, x0)
+    hs.upload(g, x0)
     f_before, axes_before = g.weave_forces(), g.weave_axes()
     assert f_before.any()
     nf = g.n_faces
@@ -676,7 +612,7 @@ def test_refusals():
         refused(lambda bad=bad: g.set_weave(bad))
     refused(lambda: g.set_weave(good, perp), says="face 17")
     assert np.array_equal(g.get_weave().view(np.float32).reshape(-1, 7), good) and g.weave_max_stable_dt() == lim
-    assert np.array_equal(_bits(g.weave_forces()), _bits(f_before)) and np.array_equal(_bits(g.weave_axes()), _bits(axes_before))
+    assert np.array_equal(hs.bits(g.weave_forces()), hs.bits(f_before)) and np.array_equal(hs.bits(g.weave_axes()), hs.bits(axes_before))
     # E_warp = 0 with nu = 0 is legal: kb = E_weft alone; a zero direction on a cloth WITHOUT weave is accepted
     g.set_weave([(0.0, 1e4, 0.0, 1e2, 1, 0, 0)])
     assert g.weave_forces().any()
