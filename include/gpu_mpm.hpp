@@ -137,7 +137,8 @@ struct GpuMpmState {
         return std::make_tuple(pos, idx);
     }
     void ReallocateContacts(size_t) {}  // implicit in CopyContactPairs
-    // extension: bitwise run-to-run reproducibility (see mpm_set_deterministic)
+    // extension: bitwise run-to-run reproducibility (see mpm_set_deterministic).  Call it before Finalize: the order inside
+    // a cell is canonical from Finalize's own first sort on; switched on later, every re-sort keeps the order that sort left
     void SetDeterministic(bool on) { mpm_check(mpm_set_deterministic(h_, on ? 1 : 0)); }
     void ReallocateExternelBodies(size_t n) { mpm_check(mpm_reallocate_external_bodies(h_, n)); n_bodies_ = n; }
     void ExternelBodyForceToHost() {
@@ -181,7 +182,7 @@ struct GpuMpmState {
     void SetBending(const std::vector<float>& stiffness) { mpm_check(mpm_set_bending(h_, stiffness.size(), stiffness.data())); }
     std::vector<float> GetBending() const { return table<float>(mpm_get_bending); }
     // -k Q x on the current positions, 3 floats per vertex in the numbering of DumpCpuState (a diagnostic)
-    std::vector<float> BendingForces(size_t n_verts) const { return vertex_forces(mpm_bending_forces, n_verts); }
+    std::vector<float> BendingForces(size_t n_verts) const { return vertex_forces(mpm_bending_forces, n_verts, "BendingForces"); }
     // the dt above which the substep entry points refuse an engine with bending (+inf while it is off)
     float BendingMaxStableDt() const { return max_stable_dt(mpm_bending_max_stable_dt); }
     // Extension: stiffness-proportional damping per cloth (mpm_set_damping), the counterpart of Drake's
@@ -190,7 +191,7 @@ struct GpuMpmState {
     void SetDamping(const std::vector<mpm_cloth_damping_t>& d) { mpm_check(mpm_set_damping(h_, d.size(), d.data())); }
     std::vector<mpm_cloth_damping_t> GetDamping() const { return table<mpm_cloth_damping_t>(mpm_get_damping); }
     // the damping force on the current positions and velocities, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> DampingForces(size_t n_verts) const { return vertex_forces(mpm_damping_forces, n_verts); }
+    std::vector<float> DampingForces(size_t n_verts) const { return vertex_forces(mpm_damping_forces, n_verts, "DampingForces"); }
     // the dt above which the substep entry points refuse an engine with damping (+inf while it is off)
     float DampingMaxStableDt() const { return max_stable_dt(mpm_damping_max_stable_dt); }
     // the membrane damping kernel's face function on the host: n faces, see mpm_damping_face_records
@@ -209,19 +210,27 @@ struct GpuMpmState {
     std::vector<mpm_cloth_weave_t> GetWeave() const { return table<mpm_cloth_weave_t>(mpm_get_weave); }
     // (c, s) of the warp per face in the face's rest frame, 2 floats per face in the numbering of DumpCpuState
     std::vector<float> WeaveAxes(size_t n_faces) const {
+        expect("WeaveAxes", "n_faces", n_faces, this->n_faces());
         std::vector<float> cs(2 * n_faces);
         mpm_check(mpm_weave_axes(h_, cs.data()));
         return cs;
     }
-    // the weave's force on the current positions, 3 floats per vertex; records: null, or 9 floats per face
+    // the weave's force on the current positions, 3 floats per vertex; records: null, or receives 9 floats per face of the
+    // engine (n_faces: 0, or the engine's face count)
     std::vector<float> WeaveForces(size_t n_verts, std::vector<float>* records = nullptr, size_t n_faces = 0) const {
+        expect("WeaveForces", "n_verts", n_verts, this->n_verts());
         std::vector<float> f(3 * n_verts);
-        if (records) records->assign(9 * n_faces, 0.f);
+        if (records) {
+            const size_t nf = this->n_faces();
+            if (n_faces != 0) expect("WeaveForces", "n_faces", n_faces, nf);
+            records->assign(9 * nf, 0.f);
+        }
         mpm_check(mpm_weave_forces(h_, f.data(), records ? records->data() : nullptr));
         return f;
     }
     // Eaa, Ebb, Eab per face
     std::vector<float> WeaveStrain(size_t n_faces) const {
+        expect("WeaveStrain", "n_faces", n_faces, this->n_faces());
         std::vector<float> out(3 * n_faces);
         mpm_check(mpm_weave_strain(h_, out.data()));
         return out;
@@ -260,6 +269,7 @@ struct GpuMpmState {
     }
     // the flags per face; counts: null, or the torn faces per cloth
     std::vector<uint8_t> TearState(size_t n_faces, std::vector<uint32_t>* counts = nullptr) const {
+        expect("TearState", "n_faces", n_faces, this->n_faces());
         size_t n = 0;
         mpm_check(mpm_tear_state(h_, nullptr, nullptr, 0, &n));
         std::vector<uint8_t> torn(n_faces);
@@ -270,6 +280,7 @@ struct GpuMpmState {
     }
     // (m, q) per face on the current positions, 2 floats per face; would_fail: null, or the verdict per face
     std::vector<float> TearMeasure(size_t n_faces, std::vector<uint8_t>* would_fail = nullptr) const {
+        expect("TearMeasure", "n_faces", n_faces, this->n_faces());
         std::vector<float> mq(2 * n_faces);
         if (would_fail) would_fail->assign(n_faces, 0);
         mpm_check(mpm_tear_measure(h_, mq.data(), would_fail ? would_fail->data() : nullptr));
@@ -287,6 +298,7 @@ struct GpuMpmState {
     // one byte per hinge of the table in force (n_hinges: mpm_shell_hinges' count): 1 where the hinge is cut on the current
     // flags; counts: null, or the cut hinges per cloth
     std::vector<uint8_t> ShellCutHinges(size_t n_hinges, std::vector<uint32_t>* counts = nullptr) const {
+        expect("ShellCutHinges", "n_hinges", n_hinges, ShellHingeCount());
         size_t n = 0;
         mpm_check(mpm_shell_cut_hinges(h_, nullptr, nullptr, 0, &n));
         std::vector<uint8_t> cut(n_hinges);
@@ -326,7 +338,7 @@ struct GpuMpmState {
     void SetLinks(const std::vector<mpm_link_t>& links) { mpm_check(mpm_set_links(h_, links.size(), links.data())); }
     std::vector<mpm_link_t> GetLinks() const { return table<mpm_link_t>(mpm_get_links); }
     // the links' force on the current positions and velocities, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> LinkForces(size_t n_verts) const { return vertex_forces(mpm_link_forces, n_verts); }
+    std::vector<float> LinkForces(size_t n_verts) const { return vertex_forces(mpm_link_forces, n_verts, "LinkForces"); }
     // sum of 1/2 k (l - L)^2 over the links that act; `lengths`, if given, receives every link's float length
     double LinkEnergy(std::vector<float>* lengths = nullptr) const {
         double e = 0.0;
@@ -379,7 +391,7 @@ struct GpuMpmState {
     void SetAnchors(const std::vector<mpm_anchor_t>& anchors) { mpm_check(mpm_set_anchors(h_, anchors.size(), anchors.data())); }
     std::vector<mpm_anchor_t> GetAnchors() const { return table<mpm_anchor_t>(mpm_get_anchors); }
     // the anchors' force on the current state at the bodies' current clocks, 3 floats per vertex; adds no impulse
-    std::vector<float> AnchorForces(size_t n_verts) const { return vertex_forces(mpm_anchor_forces, n_verts); }
+    std::vector<float> AnchorForces(size_t n_verts) const { return vertex_forces(mpm_anchor_forces, n_verts, "AnchorForces"); }
     // sum of 1/2 k (l - L)^2 over the anchors that act; `lengths` and `points` (3 per anchor), if given, receive every
     // anchor's float length and attachment point; `impulse_quantum`, if given, the quantum of the bodies' accumulators
     double AnchorState(std::vector<float>* lengths = nullptr, std::vector<float>* points = nullptr,
@@ -406,7 +418,7 @@ struct GpuMpmState {
     }
     std::vector<mpm_cloth_pressure_t> GetPressure() const { return table<mpm_cloth_pressure_t>(mpm_get_pressure); }
     // the pressure force on the current positions, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> PressureForces(size_t n_verts) const { return vertex_forces(mpm_pressure_forces, n_verts); }
+    std::vector<float> PressureForces(size_t n_verts) const { return vertex_forces(mpm_pressure_forces, n_verts, "PressureForces"); }
     // volume, energy, gauge pressure and cap of every cloth on the current positions
     std::vector<mpm_cloth_pressure_state_t> PressureState() const { return table<mpm_cloth_pressure_state_t>(mpm_pressure_state); }
     // host only: is the mesh closed and consistently wound?  `edge`, if given, receives the first offending directed edge
@@ -426,6 +438,12 @@ struct GpuMpmState {
         mpm_check(mpm_set_shell_bending(h_, per_cloth.size(), per_cloth.data(), rest_pos.empty() ? nullptr : rest_pos.data()));
     }
     std::vector<mpm_cloth_shell_t> GetShellBending() const { return table<mpm_cloth_shell_t>(mpm_get_shell_bending); }
+    // the hinges of the table in force (mpm_shell_hinges' count): the extent of ShellCutHinges, CreaseState, CreaseMeasure
+    size_t ShellHingeCount() const {
+        size_t n = 0;
+        mpm_check(mpm_shell_hinges(h_, nullptr, nullptr, nullptr, 0, &n));
+        return n;
+    }
     // Extension: hinge damping (mpm_set_shell_damping) -- stiffness-proportional damping of the shell hinges, one {beta, 0}
     // per cloth (beta in seconds, 0: not damped); all zeros or an empty vector switches it off.  State of shell bending:
     // needs SetShellBending first, which also drops the table.  Tightens ShellMaxStableDt.  A synchronisation point.
@@ -434,9 +452,10 @@ struct GpuMpmState {
     }
     std::vector<mpm_cloth_shell_damping_t> GetShellDamping() const { return table<mpm_cloth_shell_damping_t>(mpm_get_shell_damping); }
     // the damping part alone on the current positions and velocities, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> ShellDampingForces(size_t n_verts) const { return vertex_forces(mpm_shell_damping_forces, n_verts); }
+    std::vector<float> ShellDampingForces(size_t n_verts) const { return vertex_forces(mpm_shell_damping_forces, n_verts, "ShellDampingForces"); }
     // the power the hinge dampers of every cloth dissipate on the current state
     std::vector<double> ShellDampingPower(size_t n_cloths) const {
+        expect("ShellDampingPower", "n_cloths", n_cloths, this->n_cloths());
         std::vector<double> p(n_cloths);
         mpm_check(mpm_shell_damping_state(h_, p.data(), nullptr));
         return p;
@@ -471,9 +490,10 @@ struct GpuMpmState {
         return next;
     }
     // the shell force on the current positions, 3 floats per vertex in the numbering of DumpCpuState
-    std::vector<float> ShellForces(size_t n_verts) const { return vertex_forces(mpm_shell_forces, n_verts); }
+    std::vector<float> ShellForces(size_t n_verts) const { return vertex_forces(mpm_shell_forces, n_verts, "ShellForces"); }
     // the shell energy of every cloth on the current positions (not part of Measure's record)
     std::vector<double> ShellEnergy(size_t n_cloths) const {
+        expect("ShellEnergy", "n_cloths", n_cloths, this->n_cloths());
         std::vector<double> e(n_cloths);
         mpm_check(mpm_shell_state(h_, e.data(), nullptr, nullptr));
         return e;
@@ -504,6 +524,7 @@ struct GpuMpmState {
     }
     // (s1, s2, r22, V psi) per face in original face order (mpm_face_strain; single engines only)
     std::vector<float> FaceStrain(size_t n_faces) const {
+        expect("FaceStrain", "n_faces", n_faces, this->n_faces());
         std::vector<float> s(4 * n_faces);
         mpm_check(mpm_face_strain(h_, s.data()));
         return s;
@@ -532,7 +553,15 @@ struct GpuMpmState {
         mpm_check(get(h_, &dt));
         return dt;
     }
-    std::vector<float> vertex_forces(int (*get)(mpm_handle_t, float*), size_t n_verts) const {
+    // the evaluators take their extent from the caller, as the reference's signatures do; the C ABI writes the engine's
+    // own, so any other number is refused here instead of overrunning (or half filling) the buffer
+    static void expect(const char* method, const char* what, size_t given, size_t engine) {
+        if (given != engine)
+            throw std::invalid_argument(std::string(method) + ": " + what + " is " + std::to_string(given) +
+                                        ", the engine has " + std::to_string(engine));
+    }
+    std::vector<float> vertex_forces(int (*get)(mpm_handle_t, float*), size_t n_verts, const char* method) const {
+        expect(method, "n_verts", n_verts, this->n_verts());
         std::vector<float> f(3 * n_verts);
         mpm_check(get(h_, f.data()));
         return f;
@@ -648,7 +677,10 @@ class GpuMpmSolver {
     // Extension: the arithmetic of CalcFemStateAndForce (correctly rounded by default, like the reference's build).
     void SetFastMath(GpuMpmState<T>* s, bool on) const { mpm_check(mpm_set_fast_math(s->h_, on ? 1 : 0)); }
     void DownloadContactPairs(const GpuMpmState<T>& s, MpmParticleContactPairs<T>* c) const {
-        const size_t n = s.n_contacts_;
+        // the engine writes the pairs it holds: its own count, not the one this object last heard of (none after
+        // GenerateContactPairsOnDevice, an older one after a call made through another copy of the state)
+        size_t n = 0;
+        mpm_check(mpm_get_contact_pair_count(s.h_, &n));
         c->particle_in_contact_index.resize(n); c->non_mpm_id.resize(n); c->penetration_distance.resize(n);
         c->normal.resize(n); c->particle_in_contact_position.resize(n); c->rigid_v.resize(n); c->rigid_p_WB.resize(n);
         mpm_check(mpm_download_contact_pairs(s.h_, c->particle_in_contact_index.data(), c->non_mpm_id.data(),
